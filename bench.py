@@ -51,12 +51,6 @@ ROOT = Path(__file__).resolve().parent
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
 
-# The HIP runtime maps a process's streams onto 4 hardware queues by default; the pipelined schedule has 7+ streams with work in
-# flight (six pass workers, the decode engine, the vocoder's side chains) and streams that share a queue run one behind the
-# other.  8 queues: +2.8 % with the engine, +5 % without, same box (profiles/r5_engine_sweep.txt); with eight pass workers 16
-# queues are another +2.5 % (299.9 / 300.2 -> 305.4 / 309.8 alternating on one box, profiles/r5_wide_step_products.txt; with
-# six workers 16 gained nothing).  Must be set before the runtime starts; an explicit setting of the caller wins.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 # dmabuf IPC: RCCL across processes needs it on this driver (exported on the GPU boxes; a rank started by torch.distributed.run from a
 # bare environment gets it here, before the runtime starts)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -68,6 +62,10 @@ import torch.distributed as dist
 AUDIO_SECONDS = 10.0
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E ~8 TB/s
 MFMA_F16_PEAK_TFLOPS = 2500.0  # dense fp16/bf16 MFMA peak (no sparsity)
+
+
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs: all files together, headers included
+DUMP_SEED = 20240901  # --dump-outputs: the sample positions of waveforms too long to store whole
 
 
 def parse_args():
@@ -127,9 +125,52 @@ def parse_args():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch check only: every rank joins a gloo group on the CPU, rank 0 prints the rank count it saw "
                          "(tests/test_bench_launch_cpu.py); no device, no model")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's batch) as DIR/<name>.npy in float64 "
+                         "(text_ids, text_lens, unit_ids, unit_lens, wav_lens; ids padded with -1) and float32 (wav: the waveforms, "
+                         "padded with 0, or a fixed seeded sample of their positions, wav_index, when the whole would pass "
+                         f"{DUMP_LIMIT_BYTES // 10**6} MB); inputs and weights are seeded, so two builds can be compared file by file")
     ap.add_argument("--stagger", type=float, default=-1.0,
                     help="start offset between micro-batch threads in the timed region, seconds (<0: warm-up step time / threads)")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, text_ids, units, wavs):
+    """--dump-outputs: what one pass returned to its caller (text ids, unit ids, waveforms), as arrays: one row per utterance,
+    ragged rows padded (ids with -1, samples with 0) and their lengths stored next to them.  The waveforms are stored whole if
+    everything fits under DUMP_LIMIT_BYTES, else at the same DUMP_SEED-drawn positions in every row (``wav_index``)."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+
+    def padded(rows, fill, dtype):
+        a = np.full((len(rows), max((len(r) for r in rows), default=0)), fill, dtype=dtype)
+        for i, r in enumerate(rows):
+            a[i, : len(r)] = r
+        return a
+
+    def host(x):
+        return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+    ids = [host(t).reshape(-1) for t in text_ids]
+    us = [host(u).reshape(-1) for u in units]
+    ws = [host(w).reshape(-1).astype(np.float32) for w in wavs]
+    arrays = {"text_ids": padded(ids, -1, np.float64), "text_lens": np.asarray([len(t) for t in ids], dtype=np.float64),
+              "unit_ids": padded(us, -1, np.float64), "unit_lens": np.asarray([len(u) for u in us], dtype=np.float64),
+              "wav_lens": np.asarray([len(w) for w in ws], dtype=np.float64)}
+    width = max((len(w) for w in ws), default=0)
+    room = DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values()) - 7 * 4096  # bytes left; 4 KB per .npy header is ample
+    if len(ws) * width * 4 <= room:
+        arrays["wav"] = padded(ws, 0.0, np.float32)
+    else:  # a sampled position costs a float32 per row and its float64 entry in wav_index
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(width, size=room // (4 * len(ws) + 8), replace=False))
+        wav = np.zeros((len(ws), len(idx)), dtype=np.float32)
+        for i, w in enumerate(ws):
+            inside = idx < len(w)
+            wav[i, inside] = w[idx[inside]]
+        arrays["wav"], arrays["wav_index"] = wav, idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def prof_report(lib):
@@ -874,6 +915,10 @@ def main():
         dist.all_gather_into_tensor(every, mine)
         per_rank_s = [float(x) for x in every.tolist()]
         elapsed = max(per_rank_s)  # the job ends with its slowest rank
+    dumped = None
+    if args.dump_outputs and rank == 0:  # the last timed pass's results, before any later pass can replace them
+        dumped = dump_outputs(args.dump_outputs, last["text_ids"], last["units"], last["wavs"])
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {dumped}")
     stage_snapshot = dict(stage_ms)
     # per-slice T2U data of the LAST TIMED pass (later runs - profiled pass, latency, extras - overwrite the views' copies)
     # (pipelined passes: the worker that ran the last pass holds the whole batch)
@@ -928,7 +973,6 @@ def main():
                 "gather_ms": ({"mean": round(1e3 * float(np.mean(gather_s[-args.steps:])), 3), "max": round(1e3 * float(np.max(gather_s[-args.steps:])), 3),
                                "calls": len(gather_s[-args.steps:])} if gather_s else None),
                 "hip_graph_decoder_step": bool(translator.use_graph),
-                "hip_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"),
                 "microbatches_in_flight": batcher.groups,
                 "pass_latency_ms": (round(1e3 * float(np.mean(batcher.last_pass_seconds)), 1) if args.pipeline_passes and free_run and
                                     getattr(batcher, "last_pass_seconds", None) else round(ms_per_step, 1)),
@@ -940,6 +984,8 @@ def main():
             "stage_ms_last_step_slice0": {k: round(v, 3) for k, v in stage_snapshot.items()},
             "load_seconds": round(load_s, 1),
         }
+        if dumped is not None:
+            result["dumped_outputs"] = {"dir": str(args.dump_outputs), "shapes": dumped}
         result["config"]["hbm_in_use_gb_after_timed_region"] = hbm_after_timed_gb
         if engine_stats is not None:
             # the shared chain over the timed region: what a pass costs in steps and what a useful row-step costs in engine time

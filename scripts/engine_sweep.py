@@ -9,12 +9,9 @@ measurement of bench.py without the parity / profile / extras blocks.  Prints on
 pass, engine statistics, ids of the last pass compared with the golden fixture)."""
 import argparse
 import json
-import os
 import sys
 import time
 from pathlib import Path
-
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")  # as bench.py does (the runtime's default of 4 hardware queues serialises streams)
 
 import torch
 

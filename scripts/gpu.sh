@@ -161,7 +161,7 @@ for task in "$@"; do
       tail -1 ${O}_esweep.err | cut -c1-300; cut -c1-700 ${O}_esweep.jsonl ;;
     esweepenv)
       # scripts/engine_sweep.py (one configuration, $ESWEEP) once per environment setting of $SWEEP (';'-separated), e.g.
-      # SWEEP="SC_VOC_GROUPS=8;SC_VOC_GROUPS=12 SC_VOC_GROUP_OVERHEAD=120;GPU_MAX_HW_QUEUES=16"
+      # SWEEP="SC_VOC_GROUPS=8;SC_VOC_GROUPS=12 SC_VOC_GROUP_OVERHEAD=120"
       IFS=';' read -ra SW <<< "$SWEEP"
       i=0
       for e in "${SW[@]}"; do

@@ -7,6 +7,9 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
+import torch
+
 ROOT = Path(__file__).resolve().parent.parent
 spec = importlib.util.spec_from_file_location("bench", ROOT / "bench.py")
 bench = importlib.util.module_from_spec(spec)
@@ -116,3 +119,29 @@ def test_roofline_bookkeeping_and_pmc_lookup():
         assert val is None and src.startswith("stale: profiles/" + tmp.name)
     finally:
         tmp.unlink(missing_ok=True)
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: ragged ids / units / waveforms of one pass as float64 / float32 .npy files, lengths next to them; waveforms
+    too long for the limit are sampled at the same seeded positions on every run."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--dump-outputs", str(tmp_path)])
+    assert bench.parse_args().dump_outputs == str(tmp_path)
+    text_ids = [[3, 10, 11, 3], [3, 12, 3]]
+    units = [np.arange(7, dtype=np.int32), np.arange(5, dtype=np.int32)]
+    wavs = [torch.linspace(-1, 1, 900).reshape(1, 1, -1), torch.ones(1, 1, 400)]
+    shapes = bench.dump_outputs(tmp_path / "whole", text_ids, units, wavs)
+    got = {p.stem: np.load(p) for p in (tmp_path / "whole").glob("*.npy")}
+    assert set(got) == {"text_ids", "text_lens", "unit_ids", "unit_lens", "wav", "wav_lens"} and shapes["wav"] == [2, 900]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["text_ids"].tolist() == [[3, 10, 11, 3], [3, 12, 3, -1]] and got["text_lens"].tolist() == [4, 3]
+    assert got["unit_ids"][1, 5:].tolist() == [-1, -1] and got["wav_lens"].tolist() == [900, 400]
+    assert np.array_equal(got["wav"][0], wavs[0].reshape(-1).numpy()) and got["wav"][1, 400:].max() == 0
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 7 * 4096 + 4000)  # room for ~230 positions: the sampled layout
+    for run in ("a", "b"):
+        bench.dump_outputs(tmp_path / run, text_ids, units, wavs)
+    a = {p.stem: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    b = {p.stem: np.load(p) for p in (tmp_path / "b").glob("*.npy")}
+    idx = a["wav_index"].astype(np.int64)
+    assert 0 < len(idx) < 900 and np.array_equal(idx, np.unique(idx)) and np.array_equal(idx, b["wav_index"])
+    assert np.array_equal(a["wav"][0], wavs[0].reshape(-1).numpy()[idx]) and np.array_equal(a["wav"], b["wav"])
+    assert sum(p.stat().st_size for p in (tmp_path / "a").glob("*.npy")) <= bench.DUMP_LIMIT_BYTES

@@ -5,8 +5,6 @@ against the reference's own ``convert_unity_checkpoint`` / ``_fairseq_key_map`` 
 import json
 from pathlib import Path
 
-from typing import Any, Mapping
-
 import pytest
 import torch
 
@@ -79,9 +77,11 @@ def test_builtin_char_alphabet_offers_no_pieces_for_a_published_checkpoint():
 
 
 def test_vocoder_checkpoint_conversion_matches_the_reference_converter():
-    """The reference's own convert_vocoder_checkpoint (models/vocoder/loader.py:20-36), cut out of its file and executed
-    when /root/reference is present; the expectations below are its outputs either way."""
-    fairseq = {"generator": {"conv_pre.bias": torch.zeros(2), "resblocks.0.convs1.0.weight_g": torch.ones(1), "dict.weight": torch.ones(3)}}
+    """The reference's own convert_vocoder_checkpoint (models/vocoder/loader.py:20-36), cut out of its file and executed on
+    the same two inputs when the fixture was minted (tests/golden/make_source_goldens.py -> reference_source_facts.json)."""
+    from tests.golden.make_source_goldens import vocoder_inputs
+
+    fairseq, converted_sd = vocoder_inputs()
     out = ck.convert_vocoder_checkpoint(fairseq)
     assert set(out) == {"code_generator.conv_pre.bias", "code_generator.resblocks.0.convs1.0.weight_g", "code_generator.dict.weight"}
     assert out["code_generator.dict.weight"] is fairseq["generator"]["dict.weight"]
@@ -91,16 +91,7 @@ def test_vocoder_checkpoint_conversion_matches_the_reference_converter():
     assert ck.convert_vocoder_checkpoint(dict(out)).keys() == out.keys()  # bare converted state dict
     with pytest.raises(KeyError):
         ck.convert_vocoder_checkpoint({"model": {"generator.conv_pre.bias": torch.zeros(2)}})  # not a published layout
-    import ast
-    from pathlib import Path
-
-    ref = Path("/root/reference/src/seamless_communication/models/vocoder/loader.py")
-    if ref.exists():
-        tree = ast.parse(ref.read_text())
-        fn = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "convert_vocoder_checkpoint")
-        ns = {"Mapping": Mapping, "Any": Any, "VocoderConfig": object}
-        exec(compile(ast.Module([fn], []), str(ref), "exec"), ns)
-        ref_out = ns["convert_vocoder_checkpoint"]({"generator": dict(fairseq["generator"])}, None)
-        assert set(ref_out["model"]) == set(out) and "generator" not in ref_out
-        ref_pass = ns["convert_vocoder_checkpoint"]({"model": dict(out)}, None)
-        assert set(ref_pass["model"]) == set(out)
+    ref = json.loads((Path(__file__).parent / "golden" / "reference_source_facts.json").read_text())["vocoder_conversion"]
+    assert set(ref["from_fairseq"]["model"]) == set(out) and ref["from_fairseq"]["top"] == ["model"]
+    assert set(converted_sd) == set(out)
+    assert set(ref["already_converted"]["model"]) == set(out)

@@ -3,7 +3,7 @@ different steps - the case every trained checkpoint produces and the finished-ro
 (inference/generator.py:261-291; ggml/examples/unity/fairseq2.cpp:1535-1563).
 
 CPU side: the oracle's greedy search on these weights is pinned against the reference's compiled `generate_sequence`
-(beam_size 1) - natural EOS included, no crafted projection row - and the settings the GPU tests rely on keep the spread
+(beam_size 1; its answers recorded in tests/golden/compiled_ref_calls.npz, tests/ref_replay.py) - natural EOS included, no crafted projection row - and the settings the GPU tests rely on keep the spread
 of stopping steps they promise.
 """
 import math
@@ -11,10 +11,10 @@ import math
 import pytest
 import torch
 
-from oracle import ggml_ref
 from oracle import unity as ou
 from seamless_communication_amd import synthetic as syn
 from tests import common
+from tests import ref_replay as ggml_ref
 
 AUDIO = (2.0, 1.37, 0.9, 1.8, 2.4, 0.6, 1.1, 1.6)
 
@@ -60,7 +60,6 @@ def test_settings_keep_their_spread(spec, distinct, shortest):
     assert min(min(m) for m in margins) > 1e-4, "near-tie: a different summation order could flip an id"
 
 
-@pytest.mark.skipif(not ggml_ref.available(), reason="oracle/_ref/libggml_ref.so not built (run oracle/build_ref.sh)")
 @pytest.mark.parametrize("spec", [common.EOS_SPREAD, common.EOS_MIXED])
 def test_natural_eos_ids_equal_the_compiled_reference(spec):
     """generate_sequence of the reference's fairseq2.cpp (beam_size 1) on the ramp weights: EOS wins on its own, ids exact."""

@@ -1,6 +1,7 @@
 """Pins the CPU oracle (oracle/unity.py) against the reference's OWN native restatement of the
 fairseq2 modules, executed: ggml/examples/unity/fairseq2.cpp compiled from /root/reference by
-oracle/build_ref.sh (oracle/_ref/libggml_ref.so) and driven with the tiny synthetic checkpoint.
+oracle/build_ref.sh (oracle/_ref/libggml_ref.so) and driven with the tiny synthetic checkpoint.  Its answers are recorded
+in tests/golden/compiled_ref_calls.npz (tests/ref_replay.py), so the module runs without the library.
 
 What this pins: LayerNorm / Linear / FFN (ReLU, SiLU), multi-head attention
 (scaling, head split, causal mask), the pre-LN encoder layer + encoder stack (a12), the decoder layer and
@@ -19,11 +20,9 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ggml_ref
 from oracle import unity as ou
 from tests import common
-
-pytestmark = pytest.mark.skipif(not ggml_ref.available(), reason="oracle/_ref/libggml_ref.so not built (run oracle/build_ref.sh)")
+from tests import ref_replay as ggml_ref
 
 ATOL = 2e-4
 ATOL_TABLE = 3e-3  # paths through ggml's fp16 exp / SiLU tables

@@ -3,7 +3,8 @@ relative-position attention and the BatchNorm convolution module) pinned twice:
 
   * against the reference's OWN native restatement, executed: RelativePositionMHA_forward, ConvModule_forward and
     StandardConformerEncoderLayer_forward of ggml/examples/unity/fairseq2.cpp:605-756 (oracle/_ref/libggml_ref.so),
-    which hard-codes 16 heads -> a 128-wide toy layer with 8-wide heads;
+    which hard-codes 16 heads -> a 128-wide toy layer with 8-wide heads (its answers recorded in
+    tests/golden/compiled_ref_calls.npz, tests/ref_replay.py);
   * against HF transformers' SeamlessM4T (v1) port, executed (tests/golden/hf_conformer_v1_ref.npz): head size 64,
     padded batch, and the relative position table formula, which the reference takes from fairseq2.
 
@@ -15,9 +16,9 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import ggml_ref
 from oracle import unity as ou
 from seamless_communication_amd.config import tiny_config
+from tests import ref_replay as ggml_ref
 
 GOLD = np.load(Path(__file__).parent / "golden" / "hf_conformer_v1_ref.npz")
 PFX = "speech_encoder.inner.layers.0"
@@ -66,9 +67,6 @@ def test_batchnorm_conv_module_and_block_match_hf_port():
 # --------------------------------------------------------------------------------------------------------------------- #
 # the reference's compiled fairseq2.cpp
 # --------------------------------------------------------------------------------------------------------------------- #
-needs_ref = pytest.mark.skipif(not ggml_ref.available(), reason="oracle/_ref/libggml_ref.so not built (run oracle/build_ref.sh)")
-
-
 def _toy_v1_layer(seed=11):
     """One v1 Conformer layer, model_dim 128, 16 heads of 8 (fairseq2.cpp:622 hard-codes H = 16), ffn 256, kernel 31."""
     g = torch.Generator().manual_seed(seed)
@@ -121,7 +119,6 @@ def ref_env():
     ref.close()
 
 
-@needs_ref
 def test_relpos_attention_matches_compiled_reference(ref_env):
     cfg, P, ref = ref_env
     x = torch.randn(1, 37, 128, generator=torch.Generator().manual_seed(3))
@@ -135,7 +132,6 @@ def test_relpos_attention_matches_compiled_reference(ref_env):
     assert float((plain - want.reshape(got.shape)).abs().max()) > 3e-2
 
 
-@needs_ref
 def test_conv_module_and_layer_match_compiled_reference(ref_env):
     cfg, P, ref = ref_env
     x = torch.randn(1, 45, 128, generator=torch.Generator().manual_seed(4))

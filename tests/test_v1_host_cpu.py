@@ -1,6 +1,6 @@
 """CPU: host-side pieces of the v1 path - architecture tables, the unit n-gram filter of the autoregressive
 T2U, the unit tokenizer's AR prompt - against the reference's own numbers / code."""
-import ast
+import json
 from pathlib import Path
 
 import numpy as np
@@ -11,7 +11,7 @@ from seamless_communication_amd.config import seamless_m4t_large, seamless_m4t_m
 from seamless_communication_amd.inference.generator import remove_consecutive_repeated_ngrams
 from seamless_communication_amd.tokenizer import UnitTokenizer
 
-REF_GENERATOR = Path("/root/reference/src/seamless_communication/inference/generator.py")
+SOURCE_FACTS = json.loads((Path(__file__).parent / "golden" / "reference_source_facts.json").read_text())
 
 
 def test_v1_architecture_tables():
@@ -45,19 +45,16 @@ def test_unit_tokenizer_ar_prompt_and_vocabulary():
     assert dec.shape == (1, 5) and dec[0, 0] == tok.lang_to_index("fra") and dec[0, 1:3].tolist() == [10, 11]
 
 
-@pytest.mark.skipif(not REF_GENERATOR.exists(), reason="/root/reference is not present")
 def test_unit_ngram_filter_equals_reference_function():
-    """inference/generator.py:39-56, cut out of the reference file and executed."""
-    tree = ast.parse(REF_GENERATOR.read_text())
-    fn = next(n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "remove_consecutive_repeated_ngrams")
-    ns = {}
-    exec(compile(ast.Module(body=[ast.parse("from typing import List").body[0], fn], type_ignores=[]), "ref", "exec"), ns)
-    ref = ns["remove_consecutive_repeated_ngrams"]
-    rng = np.random.RandomState(3)
-    cases = [[], [5], [1, 1, 1, 1], [1, 2, 1, 2, 3], [4, 4, 5, 5, 4, 4], list(range(10)) * 3, [7, 8, 9, 7, 8, 9, 7, 8]]
-    cases += [rng.randint(0, 4, size=rng.randint(1, 60)).tolist() for _ in range(200)]
-    for seq in cases:
-        assert remove_consecutive_repeated_ngrams(list(seq)) == ref(list(seq)), seq
+    """inference/generator.py:39-56, cut out of the reference file and executed on these cases
+    (tests/golden/make_source_goldens.py -> reference_source_facts.json)."""
+    from tests.golden.make_source_goldens import ngram_cases
+
+    ref = SOURCE_FACTS["ngram_filter"]
+    cases = ngram_cases()
+    assert cases == ref["cases"] and len(cases) == 207
+    for seq, want in zip(cases, ref["outputs"]):
+        assert remove_consecutive_repeated_ngrams(list(seq)) == want, seq
     assert remove_consecutive_repeated_ngrams([1, 2, 1, 2, 3]) == [1, 2, 3]
     assert remove_consecutive_repeated_ngrams([3, 3, 3], min_size=1, max_size=1) == [3]
 
