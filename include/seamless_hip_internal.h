@@ -136,6 +136,15 @@ int sc_op_attention(const float* d_q, const float* d_k, const float* d_v, float*
                     int32_t sq, int32_t skv, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
                     const int32_t* d_kv_lens, int32_t causal, const float* d_rel_k, int32_t rel_left,
                     int32_t rel_right);
+/* sc_op_attention with every field of the kernel's argument block (kernels.h: AttnArgs); a null pointer turns its
+ * feature off.  d_row_off: packed rows, item n at rows d_row_off[n] .. + d_kv_lens[n].  d_rp_table [2*skv-1][rp_ld] with
+ * d_q_bias_u / d_q_bias_v [heads*64]: Transformer-XL relative positions.  d_out_hi / d_out_lo (fp16, row stride ldoh):
+ * the result as two fp16 planes instead of d_out. */
+int sc_op_attention_ex(const float* d_q, const float* d_k, const float* d_v, float* d_out, int32_t nb, int32_t heads,
+                       int32_t sq, int32_t skv, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                       const int32_t* d_kv_lens, int32_t causal, const float* d_rel_k, int32_t rel_left,
+                       int32_t rel_right, const int32_t* d_row_off, const float* d_rp_table, int64_t rp_ld,
+                       const float* d_q_bias_u, const float* d_q_bias_v, void* d_out_hi, void* d_out_lo, int64_t ldoh);
 int sc_op_glu_dwconv(const float* d_x, const float* d_w, float* d_y, int32_t nb, int32_t T, int32_t C, int32_t k,
                      const int32_t* d_lens);
 /* Fused element-wise passes of the Conformer stack (k_norm.hip); fused = 0 runs the separate launches they replace, the

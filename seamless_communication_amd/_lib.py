@@ -172,6 +172,8 @@ SIGNATURES = {
     "sc_op_resblock_pair": (C.c_int, [_P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _i, C.c_float, _P, _P]),
     "sc_op_attention": (C.c_int, [_P, _P, _P, _P, _i, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _i,
                                   _P, _i, _i]),
+    "sc_op_attention_ex": (C.c_int, [_P, _P, _P, _P, _i, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _i,
+                                     _P, _i, _i, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64]),
     "sc_op_glu_dwconv": (C.c_int, [_P, _P, _P, _i, _i, _i, _i, _P]),
     "sc_op_argmax": (C.c_int, [_P, _i, _i, _P, _P]),
 }

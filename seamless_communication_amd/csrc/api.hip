@@ -1302,6 +1302,43 @@ int sc_op_attention(const float* d_q, const float* d_k, const float* d_v, float*
     SC_API_END
 }
 
+int sc_op_attention_ex(const float* d_q, const float* d_k, const float* d_v, float* d_out, int32_t nb, int32_t heads,
+                       int32_t sq, int32_t skv, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, const int32_t* d_kv_lens,
+                       int32_t causal, const float* d_rel_k, int32_t rel_left, int32_t rel_right, const int32_t* d_row_off,
+                       const float* d_rp_table, int64_t rp_ld, const float* d_q_bias_u, const float* d_q_bias_v, void* d_out_hi,
+                       void* d_out_lo, int64_t ldoh) {
+    SC_API_BEGIN
+    AttnArgs a;
+    a.q = d_q;
+    a.k = d_k;
+    a.v = d_v;
+    a.out = d_out;
+    a.ldq = ldq;
+    a.ldk = ldk;
+    a.ldv = ldv;
+    a.ldo = ldo;
+    a.nb = nb;
+    a.heads = heads;
+    a.Sq = sq;
+    a.Skv = skv;
+    a.kv_lens = d_kv_lens;
+    a.causal = causal;
+    a.rel_k = d_rel_k;
+    a.rel_left = rel_left;
+    a.rel_right = rel_right;
+    a.row_off = d_row_off;
+    a.rp_table = d_rp_table;
+    a.rp_ld = rp_ld;
+    a.q_bias_u = d_q_bias_u;
+    a.q_bias_v = d_q_bias_v;
+    a.out_hi = static_cast<__half*>(d_out_hi);
+    a.out_lo = static_cast<__half*>(d_out_lo);
+    a.ldoh = ldoh;
+    launch_attention(a, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
 int sc_op_glu_dwconv(const float* d_x, const float* d_w, float* d_y, int32_t nb, int32_t T, int32_t C, int32_t k,
                      const int32_t* d_lens) {
     SC_API_BEGIN

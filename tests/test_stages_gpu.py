@@ -84,6 +84,54 @@ def test_greedy_text_ids_bit_exact(env, report_dir):
         assert got == seqs
 
 
+# The encoder's length limit (4096 fbank frames): 40 s is 3998 frames, 1999 attention positions (63 key tiles, 16 query
+# workgroups per head), next to a 3.1 s item.  start = 1 picks waveforms whose greedy decode keeps every top-2 logit
+# margin of the oracle above 1e-3, so that exact ids are a fair bar.
+LONG = (40.0, 3.1)
+LONG_START = 1
+
+
+def test_encoder_matches_oracle_at_40s(env, report_dir):
+    """fbank, then the encoder at T = 1999: Shaw attention, the fused GLU / depthwise conv / LayerNorm kernels."""
+    from oracle import unity as ou
+
+    cfg, tt, ct, orc, hip = env
+    ws = common.waves(LONG, start=LONG_START)
+    fb, lens = orc.collate_fbank(ws)
+    wav, ns = common.pad_waves(ws)
+    fb_hip, frames = hip.fbank(torch.from_numpy(wav).cuda(), ns)
+    assert frames.tolist() == lens.tolist() and max(frames.tolist()) > 3990
+    assert tuple(fb_hip.shape) == tuple(fb.shape)
+    fb_err = float((fb_hip.cpu() - fb).abs().max())
+    ref, ref_lens = ou.encode_speech(orc.P, cfg, fb, lens)
+    out, out_lens = hip.encode_speech(fb.cuda().contiguous(), lens.tolist())
+    assert out_lens.tolist() == ref_lens.tolist()
+    errs = []
+    for b in range(fb.shape[0]):
+        n = int(ref_lens[b])
+        errs.append(float((out[b, :n].cpu() - ref[b, :n]).abs().max()))
+    _log(report_dir, "encoder_40s", frames=frames.tolist(), fbank_err=fb_err, errs=errs, ref_absmax=float(ref.abs().max()))
+    assert fb_err < 2e-3  # as test_fbank_matches_oracle
+    assert max(errs) < 2e-4
+
+
+def test_greedy_text_ids_bit_exact_at_40s(env, report_dir):
+    cfg, tt, ct, orc, hip = env
+    fb, lens = orc.collate_fbank(common.waves(LONG, start=LONG_START))
+    seqs, enc, enc_lens, margins = orc.s2tt(fb, lens, "fra", (1, 200), 20)
+    min_margin = min(min(m) for m in margins)
+    assert min_margin > 1e-3, min_margin
+    prefix = tt.target_prefix("fra")
+    for use_graph in (False, True):
+        ids, out_lens, scores, hidden = hip.generate_text(
+            enc.cuda().contiguous(), enc_lens.tolist(), prefix, soft_max_seq_len=(1, 200), hard_max_seq_len=20,
+            use_graph=use_graph,
+        )
+        got = [ids[b, : out_lens[b]].tolist() for b in range(len(seqs))]
+        _log(report_dir, "greedy_40s", use_graph=use_graph, got=got, ref=seqs, min_margin=min_margin)
+        assert got == seqs
+
+
 def test_generated_hidden_equals_teacher_forced_pass(env, report_dir):
     from oracle import unity as ou
 

@@ -50,8 +50,18 @@ def test_v1_checkpoint_schema():
 @pytest.mark.parametrize("seconds", [(2.0, 1.37), (6.1,), (3.0, 5.2, 0.9)])
 def test_v1_encoder_matches_oracle(seconds):
     """S = 99 ... 304 positions: one to three 128-query workgroups, up to ten 32-key tiles, padded items."""
+    _check_encoder(seconds)
+
+
+def test_v1_encoder_matches_oracle_at_40s():
+    """The encoder's length limit (4096 fbank frames): 3998 frames = 1999 positions, 63 key tiles and 16 query
+    workgroups per head, next to a 3.1 s item; also the batch-norm convolution module at T = 1999."""
+    _check_encoder((40.0, 3.1), start=1)
+
+
+def _check_encoder(seconds, start=0):
     cfg, tt, orc, hip = _models()
-    ws = common.waves(seconds)
+    ws = common.waves(seconds, start=start)
     fb_ref, lens_ref = orc.collate_fbank(ws)
     ref, ref_lens = orc.encode_speech(fb_ref, lens_ref)
     wav, ns = common.pad_waves(ws)
