@@ -16,7 +16,6 @@
 #   pyt          pytest on $PYT (files / -k expressions)           benchsweep  benchfast under each setting of $SWEEP
 #   argsweep     benchfast with each extra argument list of $ARGSWEEP (e.g. "--microbatches 1;--free-run")
 #   pstest       GEMM op tests (bit identity of the kernel variants)       gemmab   scripts/gemm_bench.py at SC_PS_TILE=128 / 256
-#   gemmhalf     scripts/gemm_bench.py at SC_PS_HALF=0 / 1 (barrier in front of the slab / mid-slab)
 #   dgemm        scripts/gemm_bench.py --decoder-shapes: the decoder step's products at 128 - 320 rows on the DMA GEMM
 #   pyprof       rocprofv3 kernel stats of `python $PYPROF` under each setting of $SWEEP
 #   esweep       scripts/engine_sweep.py: decode-engine / schedule settings on one model load ($ESWEEP)
@@ -206,9 +205,6 @@ for task in "$@"; do
     gemmab)
       # pre-split GEMM: round-1 tile choice (128 x 128) against the 8-wave 256 x 256 tile, encoder shapes
       for t in 128 256; do ( SC_PS_TILE=$t timeout 200 python scripts/gemm_bench.py --quick --presplit-only > ${O}_gemm_tile$t.txt 2>&1 ); grep presplit ${O}_gemm_tile$t.txt | cut -c1-170; done ;;
-    gemmhalf)
-      # pre-split GEMM: barrier in front of the slab (SC_PS_HALF=0) against the mid-slab barrier schedule, encoder shapes
-      for t in 0 1; do ( SC_PS_HALF=$t timeout 200 python scripts/gemm_bench.py --quick --presplit-only > ${O}_gemm_half$t.txt 2>&1 ); echo "--- SC_PS_HALF=$t"; grep presplit ${O}_gemm_half$t.txt | cut -c1-170; done ;;
     *) echo "unknown task $task" ;;
   esac
 done

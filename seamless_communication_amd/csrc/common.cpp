@@ -27,8 +27,6 @@ const Knob knob_table[] = {
     {"SC_DEBUG_FILL", 0, "fill fresh scratch blocks with NaN (tests)"},
     // results change
     {"SC_SPLIT_MODE", 1, "1: Conformer products on the hi fp16 plane only (precision study)"},
-    {"SC_ATTN_F32", 1, "attention on the exact-fp32 matrix instruction (round 1)"},
-    {"SC_ATTN_VALU", 1, "attention on the vector ALU (round 1)"},
     {"SC_DECODER_GEN1", 1, "decoder step on the first-generation kernels"},
     {"SC_DECODER_GEN2", 1, "decoder step on the second-generation chain"},
     {"SC_DECODE_STEPWISE", 1, "teacher-forced pass step by step instead of one batched forward"},
@@ -36,7 +34,6 @@ const Knob knob_table[] = {
     // same bits, another schedule / kernel variant
     {"SC_GEMM_GENERAL", 0, "general GEMM kernel instead of the fast path"}, {"SC_GEMM_PF2", 0, "GEMM prefetch depth"},
     {"SC_GEMM_GROUP_M", 0, "GEMM workgroup order"}, {"SC_GEMM_TILE", 0, "GEMM tile override"},
-    {"SC_PS_ILV", 0, "DMA GEMM: interleaved issue"}, {"SC_PS_HALF", 0, "DMA GEMM: mid-slab barrier"}, {"SC_PS_PP", 0, "0: 8-wave DMA GEMM in lock step instead of alternating load / compute segments"},
     {"SC_PS_TILE", 0, "DMA GEMM: largest tile"}, {"SC_PS_MIN256", 0, "DMA GEMM: tiles needed for 256 x 256"},
     {"SC_PS_MIN128", 0, "DMA GEMM: tiles needed for 128 x 128"},
     {"SC_PRESPLIT", 0, "0: Conformer operands split on the fly"}, {"SC_ENC_FUSE", 0, "0: separate Conformer element-wise launches"},
@@ -45,9 +42,7 @@ const Knob knob_table[] = {
     {"SC_G3_TILES", 0, "0: FFN-out of wide steps on the weight-stationary row-group walk instead of tile-owning waves"},
     {"SC_G3_TOUCH", 0, "weight-stationary products: bit 0 cooperative L2 touch of the activations, bit 1 K slices per XCD (FFN-out); default 3"},
     {"SC_D3_FFN_IN", 0, "decoder step: FFN-in workgroup shape"}, {"SC_D3_FFN_OUT", 0, "decoder step: FFN-out workgroup shape"},
-    {"SC_MMA_GRAPH", 0, "streaming decoder step from a captured graph"}, 
     {"SC_T2U_GROUPS", 0, "NAR T2U: length buckets"}, {"SC_T2U_PACKED", 0, "0: NAR decoder on padded buckets"},
-    {"SC_T2U_FUSED_ARGMAX", 0, "0: unit logits written out, arg-max as its own launch"},
     {"SC_VOC_PS", 0, "0: vocoder wide stages on the register-staged convolution"}, {"SC_VOC_MRF", 0, "0: narrow vocoder stages as nine pair launches"},
     {"SC_VOC_GROUPS", 0, "vocoder: length buckets"}, {"SC_VOC_GROUP_OVERHEAD", 0, "vocoder: bucket planning overhead rows"},
     {"SC_VOC_STREAMS", 0, "vocoder: side chains"},

@@ -1,430 +1,32 @@
-// Attention kernels (head_dim = 64), fp32 math on the vector ALU.
+// Attention kernels (head_dim = 64).
 //
-// attn_kernel: flash-style tiled attention for a 64-query x 64-key tile per
-//   iteration, K/V tiles staged in LDS, online softmax with wave shuffles,
-//   optional key-length mask, causal mask and Shaw relative-position keys
-//   (logits[i][j] += q_i . R[clamp(j-i,-L,R)+L], the q.R table is computed
-//   once per query tile instead of materialising the (S,S,64) relative keys
-//   of the reference's einsum).
-// decode_attn_kernel: one query per (batch, head) against a KV cache, with the
-//   append of the new key/value row fused in.
-//
-// fp32 everywhere: attention is < 6 % of the encoder FLOPs and the parity
-// target is the fp32 CPU reference; see DESIGN.md for the MFMA follow-up.
+// attn_mfma16_kernel<MODE>: flash-style attention of the speech encoders on the matrix cores, every fp32 operand carried as
+//   two fp16 halves; 128 queries per workgroup, K/V tiles of 32 keys in LDS, online soft-max, optional key-length mask,
+//   causal mask and packed (varlen) items; MODE 1 adds Shaw relative-position keys (v2 encoder:
+//   logits[i][j] += q_i . R[clamp(j-i,-L,R)+L], the q.R table is computed once per workgroup instead of materialising the
+//   (S,S,64) relative keys of the reference's einsum), MODE 2 Transformer-XL relative positions (v1 encoder).
+// decode_attn_kernel: one query per (batch, head) against a KV cache, with the append of the new key/value row fused in
+//   (the first-generation decoder step, kept for the geometries the packed step kernels of k_dstep.hip do not take).
 #include <cstdlib>
 
 #include "kernels.h"
 
 namespace sc {
 
-static constexpr int HD = 64;   // head dim
-static constexpr int BQ = 64;   // queries per block
-static constexpr int BKV = 64;  // keys per iteration
-static constexpr int QS = 68;   // padded LDS row stride (floats) for Q / K / P tiles
-static constexpr int MAX_REL = 96;
-
-template <bool SHAW>
-__global__ __launch_bounds__(256) void attn_kernel(AttnArgs p) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* sQ = smem;                 // [BQ][QS]
-    float* sK = sQ + BQ * QS;         // [BKV][QS]   (also P tile)
-    float* sV = sK + BKV * QS;        // [BKV][HD]
-    float* sQR = sV + BKV * HD;       // [BQ][npos]  (SHAW only)
-
-    const int tid = threadIdx.x;
-    const int tx = tid & 15, ty = tid >> 4;
-    const int q0 = blockIdx.x * BQ;
-    const int h = blockIdx.y;
-    const int n = blockIdx.z;
-    const int kv_len = p.kv_lens ? min(p.kv_lens[n], p.Skv) : p.Skv;
-    const int shift = p.Skv - p.Sq;  // absolute position of query i is i + shift
-    const int npos = p.rel_left + 1 + p.rel_right;
-    const float scale = 0.125f;  // 64^-0.5
-
-    // ---- stage Q tile -------------------------------------------------------
-    for (int idx = tid; idx < BQ * (HD / 4); idx += 256) {
-        const int r = idx >> 4, c4 = idx & 15;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (q0 + r < p.Sq)
-            v = *reinterpret_cast<const float4*>(p.q + ((int64_t)n * p.Sq + q0 + r) * p.ldq + h * HD + c4 * 4);
-        *reinterpret_cast<float4*>(&sQ[r * QS + c4 * 4]) = v;
-    }
-    if (SHAW) {
-        // relative keys R[npos][64] staged (temporarily) over the K/V region
-        float* sR = sK;
-        for (int idx = tid; idx < npos * (HD / 4); idx += 256) {
-            const int r = idx >> 4, c4 = idx & 15;
-            *reinterpret_cast<float4*>(&sR[r * QS + c4 * 4]) =
-                *reinterpret_cast<const float4*>(p.rel_k + r * HD + c4 * 4);
-        }
-        __syncthreads();
-        for (int idx = tid; idx < BQ * npos; idx += 256) {
-            const int r = idx / npos, e = idx - r * npos;
-            float acc = 0.f;
-#pragma unroll
-            for (int d = 0; d < HD; d += 4) {
-                const float4 a = *reinterpret_cast<const float4*>(&sQ[r * QS + d]);
-                const float4 b = *reinterpret_cast<const float4*>(&sR[e * QS + d]);
-                acc = fmaf(a.x, b.x, acc);
-                acc = fmaf(a.y, b.y, acc);
-                acc = fmaf(a.z, b.z, acc);
-                acc = fmaf(a.w, b.w, acc);
-            }
-            sQR[r * npos + e] = acc;
-        }
-    }
-    __syncthreads();
-
-    float m_i[4], l_i[4], o[4][4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        m_i[r] = -1e30f;
-        l_i[r] = 0.f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) o[r][c] = 0.f;
-    }
-
-    // keys beyond this bound are masked for every query of the tile
-    int k_end = kv_len;
-    if (p.causal) k_end = min(k_end, q0 + BQ - 1 + shift + 1);
-
-    for (int k0 = 0; k0 < k_end; k0 += BKV) {
-        // ---- stage K and V tiles ----------------------------------------------
-        for (int idx = tid; idx < BKV * (HD / 4); idx += 256) {
-            const int r = idx >> 4, c4 = idx & 15;
-            float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
-            if (k0 + r < kv_len) {
-                const int64_t row = (int64_t)n * p.Skv + k0 + r;
-                kv = *reinterpret_cast<const float4*>(p.k + row * p.ldk + h * HD + c4 * 4);
-                vv = *reinterpret_cast<const float4*>(p.v + row * p.ldv + h * HD + c4 * 4);
-            }
-            *reinterpret_cast<float4*>(&sK[r * QS + c4 * 4]) = kv;
-            *reinterpret_cast<float4*>(&sV[r * HD + c4 * 4]) = vv;
-        }
-        __syncthreads();
-
-        // ---- S = Q K^T : thread owns rows ty+16r, cols tx+16c -------------------
-        float sc_[4][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) sc_[r][c] = 0.f;
-#pragma unroll 4
-        for (int d = 0; d < HD; d += 4) {
-            float4 qa[4], kb[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) qa[r] = *reinterpret_cast<const float4*>(&sQ[(ty + 16 * r) * QS + d]);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) kb[c] = *reinterpret_cast<const float4*>(&sK[(tx + 16 * c) * QS + d]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    float a = sc_[r][c];
-                    a = fmaf(qa[r].x, kb[c].x, a);
-                    a = fmaf(qa[r].y, kb[c].y, a);
-                    a = fmaf(qa[r].z, kb[c].z, a);
-                    a = fmaf(qa[r].w, kb[c].w, a);
-                    sc_[r][c] = a;
-                }
-        }
-        // ---- bias, scale, masks, online softmax ---------------------------------
-        float alpha[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int qi = q0 + ty + 16 * r;
-            const int qabs = qi + shift;
-            float mx = -INFINITY;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const int kj = k0 + tx + 16 * c;
-                float s = sc_[r][c];
-                if (SHAW) {
-                    int rel = kj - qabs;
-                    rel = max(-p.rel_left, min(p.rel_right, rel)) + p.rel_left;
-                    s += sQR[(ty + 16 * r) * npos + rel];
-                }
-                s *= scale;
-                const bool ok = (kj < kv_len) && (!p.causal || kj <= qabs);
-                s = ok ? s : -INFINITY;
-                sc_[r][c] = s;
-                mx = fmaxf(mx, s);
-            }
-#pragma unroll
-            for (int off = 8; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-            const float m_new = fmaxf(m_i[r], mx);
-            alpha[r] = expf(m_i[r] - m_new);
-            float rs = 0.f;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float pv = expf(sc_[r][c] - m_new);
-                sc_[r][c] = pv;
-                rs += pv;
-            }
-#pragma unroll
-            for (int off = 8; off > 0; off >>= 1) rs += __shfl_xor(rs, off);
-            l_i[r] = l_i[r] * alpha[r] + rs;
-            m_i[r] = m_new;
-        }
-        __syncthreads();  // everyone is done reading sK
-        float* sP = sK;
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) sP[(ty + 16 * r) * QS + tx + 16 * c] = sc_[r][c];
-        __syncthreads();
-        // ---- O = alpha*O + P V : thread owns rows ty+16r, dims 4*tx .. 4*tx+3 ------
-        // (contiguous dims: one 16-byte LDS read per V row instead of four 4-byte ones; the 16 lanes of a
-        // row group read 256 contiguous bytes, the 4 row groups of a wave read the same address)
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) o[r][c] *= alpha[r];
-#pragma unroll 4
-        for (int j = 0; j < BKV; j += 4) {
-            float4 pa[4], vb[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) pa[r] = *reinterpret_cast<const float4*>(&sP[(ty + 16 * r) * QS + j]);
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) vb[jj] = *reinterpret_cast<const float4*>(&sV[(j + jj) * HD + 4 * tx]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                o[r][0] = fmaf(pa[r].w, vb[3].x, fmaf(pa[r].z, vb[2].x, fmaf(pa[r].y, vb[1].x, fmaf(pa[r].x, vb[0].x, o[r][0]))));
-                o[r][1] = fmaf(pa[r].w, vb[3].y, fmaf(pa[r].z, vb[2].y, fmaf(pa[r].y, vb[1].y, fmaf(pa[r].x, vb[0].y, o[r][1]))));
-                o[r][2] = fmaf(pa[r].w, vb[3].z, fmaf(pa[r].z, vb[2].z, fmaf(pa[r].y, vb[1].z, fmaf(pa[r].x, vb[0].z, o[r][2]))));
-                o[r][3] = fmaf(pa[r].w, vb[3].w, fmaf(pa[r].z, vb[2].w, fmaf(pa[r].y, vb[1].w, fmaf(pa[r].x, vb[0].w, o[r][3]))));
-            }
-        }
-        __syncthreads();  // before the next tile overwrites sK / sV
-    }
-
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int qi = q0 + ty + 16 * r;
-        if (qi >= p.Sq) continue;
-        const float inv = l_i[r] > 0.f ? 1.0f / l_i[r] : 0.f;
-        if (p.out_hi) {  // two fp16 planes for launch_gemm_presplit (the output projection) instead of fp32
-            typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-            typedef float f4_t __attribute__((ext_vector_type(4)));
-            const f4_t of = {o[r][0] * inv, o[r][1] * inv, o[r][2] * inv, o[r][3] * inv};
-            const h4_t hi = __builtin_convertvector(of, h4_t);
-            const f4_t back = __builtin_convertvector(hi, f4_t);
-            const int64_t off = ((int64_t)n * p.Sq + qi) * p.ldoh + h * HD + 4 * tx;
-            *reinterpret_cast<h4_t*>(p.out_hi + off) = hi;
-            *reinterpret_cast<h4_t*>(p.out_lo + off) = __builtin_convertvector(of - back, h4_t);
-            continue;
-        }
-        float* orow = p.out + ((int64_t)n * p.Sq + qi) * p.ldo + h * HD;
-        *reinterpret_cast<float4*>(orow + 4 * tx) = make_float4(o[r][0] * inv, o[r][1] * inv, o[r][2] * inv, o[r][3] * inv);
-    }
-}
+static constexpr int HD = 64;  // head dim
 
 // ------------------------------------------------------------------------------------------------- //
-// attn_mfma_kernel: the same attention on the matrix cores with fp32 operands
-// (v_mfma_f32_32x32x2_f32: exact fp32 products and accumulation, 64 FLOP/clk/SIMD = the fp32 vector rate,
-// but the operands of a 32x32x2 step are 2 values per lane instead of LDS traffic for every fmaf).
-// A workgroup = 4 waves x 32 queries; K/V tiles of 32 keys in LDS.  Everything is kept TRANSPOSED so that a
-// query is a LANE (column) in every accumulator:
-//   S^T[key][query] = K . Q^T      A = K tile from LDS (16-byte reads: 4 contraction steps per read),
-//                                  B = Q^T held in 32 registers per lane for the whole kernel;
-//   O^T[dim][query] += V^T . P^T   A = V^T from LDS, B = P^T = the S^T accumulator registers themselves
-//                                  (step s of half h contracts the key that register s of that half holds),
-// so the soft-max runs per lane (16 registers + one cross-half shuffle), the probabilities never leave the
-// registers, and the running rescale of O is a per-lane multiply.  Shaw term: q.R table per query in LDS
-// (computed once per workgroup), indexed by clamp(j - i).  The result goes through LDS once for 16-byte row stores.
-// ------------------------------------------------------------------------------------------------- //
-static constexpr int MQ = 128;   // queries per workgroup
-static constexpr int MKV = 32;   // keys per iteration
-static constexpr int KS = 68;    // padded row stride of the K tile / R staging / output tile (floats)
-
-template <bool SHAW>
-__global__ __launch_bounds__(256) void attn_mfma_kernel(AttnArgs p) {
-    typedef float f16v __attribute__((ext_vector_type(16)));
-    typedef float f4v __attribute__((ext_vector_type(4)));
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* sK = smem;                    // [MKV][KS]; after the loop: output tiles [4 waves][32][KS] start here
-    float* sV = sK + MKV * KS;           // [MKV][HD]
-    float* sQR = smem + 4 * 32 * KS;     // [MQ][npos]   (SHAW only; placed behind the output-tile region)
-    float* sR = smem;                    // [npos][KS] staging of the relative keys before the loop (over the K/V tiles)
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ql = lane & 31, hh = lane >> 5;
-    const int h = blockIdx.y, n = blockIdx.z;
-    const int q0 = blockIdx.x * MQ + wave * 32;
-    const int qi = q0 + ql;
-    const int kv_len = p.kv_lens ? min(p.kv_lens[n], p.Skv) : p.Skv;
-    const int shift = p.Skv - p.Sq;
-    const int qabs = qi + shift;
-    const int npos = p.rel_left + 1 + p.rel_right;
-    const float scale = 0.125f;
-
-    // Q^T operand: step s (0..31) of half hh contracts dim 8*(s>>2) + 4*hh + (s&3)
-    float qreg[32];
-    {
-        const bool qok = qi < p.Sq;
-        const float* qp = p.q + ((int64_t)n * p.Sq + (qok ? qi : 0)) * p.ldq + h * HD + 4 * hh;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) {
-            f4v v = {0.f, 0.f, 0.f, 0.f};
-            if (qok) v = *reinterpret_cast<const f4v*>(qp + 8 * g);
-            qreg[4 * g + 0] = v[0];
-            qreg[4 * g + 1] = v[1];
-            qreg[4 * g + 2] = v[2];
-            qreg[4 * g + 3] = v[3];
-        }
-    }
-    if (SHAW) {
-        for (int idx = tid; idx < npos * (HD / 4); idx += 256) {
-            const int r = idx >> 4, c4 = idx & 15;
-            *reinterpret_cast<f4v*>(&sR[r * KS + c4 * 4]) = *reinterpret_cast<const f4v*>(p.rel_k + r * HD + c4 * 4);
-        }
-        __syncthreads();
-        // (q.R)^T[e][query] = R . Q^T on the matrix cores: three 32-row fragments cover the npos <= 96 relative keys
-        // (rows >= npos read stale LDS and are not stored)
-#pragma unroll 1
-        for (int f = 0; f < 3; ++f) {
-            if (f * 32 >= npos) break;
-            f16v qr;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) qr[r] = 0.f;
-#pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                const f4v r4 = *reinterpret_cast<const f4v*>(&sR[(f * 32 + ql) * KS + 8 * g + 4 * hh]);
-                qr = __builtin_amdgcn_mfma_f32_32x32x2f32(r4[0], qreg[4 * g + 0], qr, 0, 0, 0);
-                qr = __builtin_amdgcn_mfma_f32_32x32x2f32(r4[1], qreg[4 * g + 1], qr, 0, 0, 0);
-                qr = __builtin_amdgcn_mfma_f32_32x32x2f32(r4[2], qreg[4 * g + 2], qr, 0, 0, 0);
-                qr = __builtin_amdgcn_mfma_f32_32x32x2f32(r4[3], qreg[4 * g + 3], qr, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int e = f * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                if (e < npos) sQR[(wave * 32 + ql) * npos + e] = qr[r];
-            }
-        }
-    }
-
-    f16v o0, o1;  // O^T: dims 0..31 / 32..63 (rows) x queries (lanes)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        o0[r] = 0.f;
-        o1[r] = 0.f;
-    }
-    float m_i = -1e30f, l_i = 0.f;
-
-    // keys beyond this bound are masked for every query of the workgroup
-    int k_end = kv_len;
-    if (p.causal) k_end = min(k_end, (int)(blockIdx.x * MQ) + MQ - 1 + shift + 1);
-
-    for (int k0 = 0; k0 < k_end; k0 += MKV) {
-        __syncthreads();  // previous tile fully consumed (also orders the sQR writes before their first use)
-        for (int idx = tid; idx < MKV * (HD / 4); idx += 256) {
-            const int r = idx >> 4, c4 = idx & 15;
-            f4v kv = {0.f, 0.f, 0.f, 0.f}, vv = kv;
-            if (k0 + r < kv_len) {
-                const int64_t row = (int64_t)n * p.Skv + k0 + r;
-                kv = *reinterpret_cast<const f4v*>(p.k + row * p.ldk + h * HD + c4 * 4);
-                vv = *reinterpret_cast<const f4v*>(p.v + row * p.ldv + h * HD + c4 * 4);
-            }
-            *reinterpret_cast<f4v*>(&sK[r * KS + c4 * 4]) = kv;
-            *reinterpret_cast<f4v*>(&sV[r * HD + c4 * 4]) = vv;
-        }
-        __syncthreads();
-
-        // ---- S^T = K . Q^T (rows = keys, lanes = queries) ---------------------------------
-        f16v st;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) st[r] = 0.f;
-#pragma unroll
-        for (int g = 0; g < 8; ++g) {
-            const f4v k4 = *reinterpret_cast<const f4v*>(&sK[ql * KS + 8 * g + 4 * hh]);  // key = lane & 31
-            st = __builtin_amdgcn_mfma_f32_32x32x2f32(k4[0], qreg[4 * g + 0], st, 0, 0, 0);
-            st = __builtin_amdgcn_mfma_f32_32x32x2f32(k4[1], qreg[4 * g + 1], st, 0, 0, 0);
-            st = __builtin_amdgcn_mfma_f32_32x32x2f32(k4[2], qreg[4 * g + 2], st, 0, 0, 0);
-            st = __builtin_amdgcn_mfma_f32_32x32x2f32(k4[3], qreg[4 * g + 3], st, 0, 0, 0);
-        }
-        // ---- bias, scale, masks, online soft-max: register r of half hh is key (r&3) + 8*(r>>2) + 4*hh ----
-        float mx = -INFINITY;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int kj = k0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-            float sc = st[r];
-            if (SHAW) {
-                int rel = kj - qabs;
-                rel = max(-p.rel_left, min(p.rel_right, rel)) + p.rel_left;
-                sc += sQR[(wave * 32 + ql) * npos + rel];
-            }
-            sc *= scale;
-            const bool ok = (kj < kv_len) && (!p.causal || kj <= qabs);
-            sc = ok ? sc : -INFINITY;
-            st[r] = sc;
-            mx = fmaxf(mx, sc);
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_i, mx);
-        const float alpha = expf(m_i - m_new);
-        float rs = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float pv = expf(st[r] - m_new);
-            st[r] = pv;
-            rs += pv;
-        }
-        rs += __shfl_xor(rs, 32);
-        l_i = l_i * alpha + rs;
-        m_i = m_new;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            o0[r] *= alpha;
-            o1[r] *= alpha;
-        }
-        // ---- O^T += V^T . P^T: step s of half hh contracts key (s&3) + 8*(s>>2) + 4*hh = register s ----
-#pragma unroll
-        for (int sidx = 0; sidx < 16; ++sidx) {
-            const int key = (sidx & 3) + 8 * (sidx >> 2) + 4 * hh;
-            const float v0 = sV[key * HD + ql];
-            const float v1 = sV[key * HD + 32 + ql];
-            o0 = __builtin_amdgcn_mfma_f32_32x32x2f32(v0, st[sidx], o0, 0, 0, 0);
-            o1 = __builtin_amdgcn_mfma_f32_32x32x2f32(v1, st[sidx], o1, 0, 0, 0);
-        }
-    }
-
-    // ---- O^T (dims x queries) -> this wave's [32 queries][64 dims] tile in LDS -> 16-byte row stores ----
-    __syncthreads();  // every wave is done with the K/V tiles
-    float* ot = smem + wave * (32 * KS);
-    const float inv = l_i > 0.f ? 1.0f / l_i : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int d = (r & 3) + 8 * (r >> 2) + 4 * hh;
-        ot[ql * KS + d] = o0[r] * inv;
-        ot[ql * KS + 32 + d] = o1[r] * inv;
-    }
-    // lanes 0..15 / 16..31 / ... take rows; 16 lanes x 16 bytes = one 256-byte row of this head
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-        const int row = it * 4 + (lane >> 4);
-        const int c0 = (lane & 15) * 4;
-        const int qq = q0 + row;
-        const f4v of = *reinterpret_cast<const f4v*>(&ot[row * KS + c0]);
-        if (qq >= p.Sq) continue;
-        if (p.out_hi) {
-            typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-            const h4_t hi = __builtin_convertvector(of, h4_t);
-            const f4v back = __builtin_convertvector(hi, f4v);
-            const int64_t off = ((int64_t)n * p.Sq + qq) * p.ldoh + h * HD + c0;
-            *reinterpret_cast<h4_t*>(p.out_hi + off) = hi;
-            *reinterpret_cast<h4_t*>(p.out_lo + off) = __builtin_convertvector(of - back, h4_t);
-        } else {
-            *reinterpret_cast<f4v*>(p.out + ((int64_t)n * p.Sq + qq) * p.ldo + h * HD + c0) = of;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------- //
-// attn_mfma16_kernel: the same transposed scheme on v_mfma_f32_32x32x16_f16 with every fp32 operand carried as two fp16
-// halves (hi = fp16(a), lo = fp16(a - hi), the split of the product kernels, kernels.h): a product a.b is the three
-// terms  a_hi.b_hi + a_hi.b_lo + a_lo.b_hi  accumulated in fp32 (the dropped a_lo.b_lo is 2^-22 of the product), i.e.
-// 12 matrix instructions of 32 cycles per 32 x 32 x 64 block instead of 32 fp32 ones of 64 cycles (5.3 x fewer matrix
-// cycles).  What changes against attn_mfma_kernel:
+// attn_mfma16_kernel.  A workgroup = 4 waves x 32 queries; K/V tiles of 32 keys in LDS.  Everything is kept TRANSPOSED so
+// that a query is a LANE (column) in every accumulator:
+//   S^T[key][query] = K . Q^T      A = K tile from LDS, B = Q^T held in registers for the whole kernel;
+//   O^T[dim][query] += V^T . P^T   A = V^T from LDS, B = P^T = the S^T accumulator registers themselves,
+// so the soft-max runs per lane (16 registers + one cross-half shuffle), the probabilities never leave the registers, and
+// the running rescale of O is a per-lane multiply.  The result goes through LDS once for 16-byte row stores.
+// The matrix instruction is v_mfma_f32_32x32x16_f16 with every fp32 operand carried as two fp16 halves (hi = fp16(a),
+// lo = fp16(a - hi), the split of the product kernels, kernels.h): a product a.b is the three terms
+// a_hi.b_hi + a_hi.b_lo + a_lo.b_hi  accumulated in fp32 (the dropped a_lo.b_lo is 2^-22 of the product), i.e. 12 matrix
+// instructions of 32 cycles per 32 x 32 x 64 block instead of 32 exact-fp32 ones (v_mfma_f32_32x32x2_f32) of 64 cycles
+// (5.3 x fewer matrix cycles).  Details:
 //   * K tile in LDS as two fp16 planes [key][64 dims] (row stride 144 B: the 16 lanes of a ds_read_b128 group hit 16
 //     distinct 16-byte slots), A operand of S^T = K . Q^T: lane (key, half) reads dims 16c + 8 half .. + 7 of chunk c;
 //   * Q^T as 4 + 4 half8 registers per lane (hi, lo), loaded once;
@@ -433,8 +35,12 @@ __global__ __launch_bounds__(256) void attn_mfma_kernel(AttnArgs p) {
 //     so P^T = registers 8c .. 8c+7 converted to hi / lo IS the B operand of O^T += V^T . P^T, no data movement;
 //   * soft-max in the base-2 domain on v_exp_f32 (exp2 of (s - m) . log2 e);
 //   * the next K/V tile's global loads are issued before the current tile's arithmetic (register prefetch).
-// The q.R table of the Shaw term stays on the exact fp32 matrix instruction (once per workgroup).
+// The q.R table of the Shaw term (one row per query in LDS, indexed by clamp(j - i)) is computed once per workgroup on the
+// exact fp32 matrix instruction.
 // ------------------------------------------------------------------------------------------------- //
+static constexpr int MQ = 128;   // queries per workgroup
+static constexpr int MKV = 32;   // keys per iteration
+static constexpr int KS = 68;    // padded row stride of the R staging / output tile (floats)
 typedef _Float16 a16_h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 a16_h4 __attribute__((ext_vector_type(4)));
 static constexpr int KH_LD = 72;  // halfs per K-plane row (64 dims + 8 pad)
@@ -498,7 +104,9 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
     const float* qrow = p.q + (qbase + (qok ? qi : 0)) * p.ldq + h * HD;
 
     if (SHAW) {
-        // (q.R)^T[e][query] = R . Q^T on the exact fp32 matrix instruction, as in attn_mfma_kernel
+        // (q.R)^T[e][query] = R . Q^T on the exact fp32 matrix instruction (v_mfma_f32_32x32x2_f32): Q^T step s (0..31) of half
+        // hh contracts dim 8*(s>>2) + 4*hh + (s&3); three 32-row fragments cover the npos <= 96 relative keys (rows >= npos
+        // read stale LDS and are not stored)
         float qreg[32];
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
@@ -790,10 +398,6 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
 }
 
 static bool g_attn_attr_set = false;
-static bool f32_mfma_env() {
-    static const bool v = knob::value("SC_ATTN_F32", 0) != 0;
-    return v;
-}
 
 void launch_attention(const AttnArgs& a, hipStream_t s) {
     SC_CHECK(a.nb > 0 && a.heads > 0 && a.Sq > 0 && a.Skv > 0, "attention: empty problem");
@@ -801,69 +405,27 @@ void launch_attention(const AttnArgs& a, hipStream_t s) {
     SC_CHECK(a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.ldv % 4 == 0 && a.ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0,
              "attention: row strides must be multiples of 4 and the output 16-byte aligned");
     const int npos = a.rel_left + 1 + a.rel_right;
-    SC_CHECK(!a.rel_k || npos <= MAX_REL, "attention: %d relative positions > %d", npos, MAX_REL);
+    SC_CHECK(npos <= 96, "attention: %d relative positions > 96", npos);  // the q.R table: three 32-row fragments
+    SC_CHECK(!a.row_off || (a.kv_lens && a.Sq == a.Skv && !a.causal), "attention: packed rows need kv_lens and Sq == Skv");
+    if (a.rp_table)
+        SC_CHECK(!a.rel_k && !a.causal && a.Sq == a.Skv && a.q_bias_u && a.q_bias_v && a.rp_ld % 4 == 0,
+                 "attention: relative positions need self-attention (Sq == Skv), both query biases and a 16-byte aligned table");
     if (!g_attn_attr_set) {
-        SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_kernel<true>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_kernel<false>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma16_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
+        SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma16_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
+        SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma16_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
         g_attn_attr_set = true;
     }
-    static const bool use_valu = knob::value("SC_ATTN_VALU", 0) != 0;
-    if (!use_valu) {
-        static bool mfma_attr = false;
-        if (!mfma_attr) {
-            SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_kernel<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
-            SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma_kernel<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
-            SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma16_kernel<0>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
-            SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma16_kernel<1>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
-            SC_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_mfma16_kernel<2>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024));
-            mfma_attr = true;
-        }
-        const double pairs = a.pairs > 0 ? a.pairs : (double)a.nb * a.Sq * a.Skv;
-        prof::Scope scope(a.rel_k ? "attention_shaw" : "attention", 4.0 * a.heads * pairs * HD,
-                          4.0 * a.nb * a.heads * HD * (2.0 * a.Sq + 2.0 * a.Skv), s);
-        size_t lds = (size_t)(4 * 32 * KS) * sizeof(float);  // K/V tiles, later the four output tiles
-        SC_CHECK(npos <= 96, "attention: relative table too large");
-        if (a.rel_k) lds += (size_t)(MQ * npos) * sizeof(float);
-        SC_CHECK(!a.row_off || (a.kv_lens && a.Sq == a.Skv && !a.causal && !f32_mfma_env()), "attention: packed rows need kv_lens, Sq == Skv and the fp16-split kernel");
-        if (a.rp_table) {
-            SC_CHECK(!a.rel_k && !a.causal && a.Sq == a.Skv && a.q_bias_u && a.q_bias_v && a.rp_ld % 4 == 0 && !use_valu,
-                     "attention: relative positions need self-attention (Sq == Skv), both query biases and a 16-byte aligned table");
-            lds += (size_t)(4 * 64 * 32) * sizeof(float);
-        }
-        dim3 grid(cdiv(a.Sq, MQ), a.heads, a.nb);
-        // SC_ATTN_F32=1: the exact-fp32 matrix instruction (round 1) instead of the three-term fp16 split (development A/B)
-        const bool f32_mfma = f32_mfma_env();
-        if (f32_mfma) {
-            if (a.rel_k) hipLaunchKernelGGL((attn_mfma_kernel<true>), grid, dim3(256), lds, s, a);
-            else hipLaunchKernelGGL((attn_mfma_kernel<false>), grid, dim3(256), lds, s, a);
-        } else {
-            if (a.rp_table) hipLaunchKernelGGL((attn_mfma16_kernel<2>), grid, dim3(256), lds, s, a);
-            else if (a.rel_k) hipLaunchKernelGGL((attn_mfma16_kernel<1>), grid, dim3(256), lds, s, a);
-            else hipLaunchKernelGGL((attn_mfma16_kernel<0>), grid, dim3(256), lds, s, a);
-        }
-        SC_LAUNCH_CHECK();
-        return;
-    }
-    SC_CHECK(!a.row_off && !a.rp_table, "attention: packed rows / relative positions are not built for the vector-ALU kernel");
-    dim3 grid(cdiv(a.Sq, BQ), a.heads, a.nb);
-    prof::Scope scope(a.rel_k ? "attention_shaw" : "attention", 4.0 * a.nb * a.heads * (double)a.Sq * a.Skv * HD,
+    const double pairs = a.pairs > 0 ? a.pairs : (double)a.nb * a.Sq * a.Skv;
+    prof::Scope scope(a.rel_k ? "attention_shaw" : "attention", 4.0 * a.heads * pairs * HD,
                       4.0 * a.nb * a.heads * HD * (2.0 * a.Sq + 2.0 * a.Skv), s);
-    size_t lds = (size_t)(BQ * QS + BKV * QS + BKV * HD) * sizeof(float);
-    if (a.rel_k) {
-        // the R staging area (npos rows of QS floats) must fit in the K+V region
-        SC_CHECK(npos * QS <= BKV * QS + BKV * HD, "attention: relative table too large");
-        lds += (size_t)BQ * npos * sizeof(float);
-        hipLaunchKernelGGL((attn_kernel<true>), grid, dim3(256), lds, s, a);
-    } else {
-        hipLaunchKernelGGL((attn_kernel<false>), grid, dim3(256), lds, s, a);
-    }
+    size_t lds = (size_t)(4 * 32 * KS) * sizeof(float);  // K/V tiles, later the four output tiles
+    if (a.rel_k) lds += (size_t)(MQ * npos) * sizeof(float);
+    if (a.rp_table) lds += (size_t)(4 * 64 * 32) * sizeof(float);
+    dim3 grid(cdiv(a.Sq, MQ), a.heads, a.nb);
+    if (a.rp_table) hipLaunchKernelGGL((attn_mfma16_kernel<2>), grid, dim3(256), lds, s, a);
+    else if (a.rel_k) hipLaunchKernelGGL((attn_mfma16_kernel<1>), grid, dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((attn_mfma16_kernel<0>), grid, dim3(256), lds, s, a);
     SC_LAUNCH_CHECK();
 }
 

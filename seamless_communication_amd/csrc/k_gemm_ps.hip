@@ -121,46 +121,54 @@ __device__ __forceinline__ void ps_epilogue(const GemmPsArgs& p, const float* ep
     }
 }
 
-// ILV: the DMA instructions that refill the free stage are issued BETWEEN the matrix instructions of the current slab
-// (one after each hi/lo pair) instead of as a block in front of them: an LDS-DMA issue costs the wave 60-180 cycles
-// (MI355X_MICROARCH.md, per-instruction constants), six of them in a row are as long as the slab's 16 MFMAs, and with
-// the block form the matrix pipe of the SIMD idles through them unless the other resident workgroup happens to be in its
-// compute phase.  Same instructions, same arithmetic order: bit-identical results.
-// SPLIT = false (measurement only, SC_SPLIT_MODE): the lo plane is neither fetched nor multiplied - A rounded to fp16 once.
 // WGM x WGN waves per workgroup.  2 x 2 waves on a 128 x 128 (64 x 64) tile is the round-1 shape; 4 x 2 waves on a
 // 256 x 256 tile (wave tile 64 x 128) halves the barriers per MFMA (32 matrix instructions per slab and wave instead of
 // 16) and takes the fragment reads from 0.75 to 0.5 ds_read_b128 per MFMA at the same 6 DMAs per wave and slab; its
 // three stages fill 144 KB of the 160 KB LDS (one workgroup of 8 waves per CU = the same 2 waves per SIMD).
-// HALF (needs ILV and SPLIT): the slab's barrier sits in the MIDDLE of its matrix instructions instead of in front of them.
-// With the barrier in front, all eight waves leave it together, request their 16 fragments together (128 KB of LDS reads per
-// workgroup) and nobody has a matrix instruction to issue until the first ones are back; the hi/lo pairs of the slab's second
-// 16-wide K chunk and the next slab's first-chunk fragments are then fetched under running MFMAs:
-//     step s:  read chunk-1 fragments of slab s | MFMA chunk 0 (fragments carried in registers) + DMAs 3..5 of slab s+2
-//              wait for slab s+1's DMAs, BARRIER | read chunk-0 fragments of slab s+1 | MFMA chunk 1 + DMAs 0..2 of slab s+3
-// After the barrier every wave has matrix work in registers at once.  The barrier of step s also says that every wave is
-// done reading slab s (both chunks: lgkmcnt(0) in front of it), so slab s+3 may land in the same stage from there on.
-// Same instructions and the same accumulation order as the other schedules: bit-identical results.
+// SPLIT = false (GemmPsArgs::split == 0): the lo plane is neither fetched nor multiplied - A rounded to fp16 once.
 // AMAX: the epilogue keeps, per row, the largest value of the wave's columns and its (lowest) column instead of writing the
 // tile (GemmPsArgs::amax); a separate instantiation, so that the other kernels' code does not change by a single instruction.
-// PP (8 waves, needs SPLIT): the two waves of a SIMD take TURNS.  With HALF both run the same program in lock step - both ask LDS
-// for fragments at the same time, both issue their DMAs at the same time, both want the matrix pipe at the same time - and
-// the pipe measured 47 - 53 % busy (profiles/r3_gemm_ps256_pmc_sq.txt).  Here every 16-wide K chunk of a slab is a LOAD
-// segment (the chunk's 8 fragment reads into registers + 3 of the wave's 6 DMAs of the slab two ahead) and a COMPUTE segment
-// (the chunk's 16 matrix instructions out of registers, nothing else, s_setprio 1), one s_barrier after each; waves 0-3 (one
-// per SIMD) load while waves 4-7 compute and the other way round:
-//     segment 4s   : waves 0-3  LOAD (s, 0)      waves 4-7  COMPUTE (s-1, 1)
-//     segment 4s+1 : waves 0-3  COMPUTE (s, 0)   waves 4-7  LOAD (s, 0)
-//     segment 4s+2 : waves 0-3  LOAD (s, 1)      waves 4-7  COMPUTE (s, 0)
-//     segment 4s+3 : waves 0-3  COMPUTE (s, 1)   waves 4-7  LOAD (s, 1);  all: wait for slab s+1
-// A wave's matrix instructions find the pipe free (its partner is in its load segment), and its loads cost no matrix time.
-// Ordering: the DMAs of slab s+1 are awaited (counted vmcnt, the 6 of slab s+2 stay in flight) in front of the barrier that
-// ends segment 4s+3 and read from segment 4s+4 on; a stage is refilled (slab s+2 -> stage of slab s-1) from segment 4s on, its
-// last reads were issued in segment 4s-1 and retired (lgkmcnt(0)) in front of that segment's barrier.  Same instructions per
-// accumulator in the same order (slab, 16-wide K chunk, hi then lo): bit-identical to every other schedule.
-template <int BM, int BN, int WGM, int WGN, bool ILV, bool SPLIT, bool CONV = false, bool HALF = false, bool AMAX = false, int PP = 0>
+//
+// The K loop's schedule follows from SPLIT and the wave count; every schedule issues the same instructions per accumulator
+// in the same order (slab, 16-wide K chunk, hi then lo): bit-identical results.
+// In all of them the DMA instructions that refill the free stage are issued BETWEEN the matrix instructions of a slab
+// instead of as a block in front of them: an LDS-DMA issue costs the wave 60-180 cycles (MI355X_MICROARCH.md,
+// per-instruction constants), six of them in a row are as long as the slab's 16 MFMAs, and with the block form the matrix
+// pipe of the SIMD idles through them unless the other resident workgroup happens to be in its compute phase.
+//   * hi plane only (PS_STEP): one barrier in front of each slab, DMA q of the refill after the q-th MFMA.
+//   * split, 4 waves (mid-slab barrier): the slab's barrier sits in the MIDDLE of its matrix instructions instead of in
+//     front of them.  With the barrier in front, all the waves leave it together, request their 16 fragments together
+//     (128 KB of LDS reads per 8-wave workgroup) and nobody has a matrix instruction to issue until the first ones are
+//     back; the hi/lo pairs of the slab's second 16-wide K chunk and the next slab's first-chunk fragments are then
+//     fetched under running MFMAs:
+//       step s:  read chunk-1 fragments of slab s | MFMA chunk 0 (fragments carried in registers) + DMAs 3..5 of slab s+2
+//                wait for slab s+1's DMAs, BARRIER | read chunk-0 fragments of slab s+1 | MFMA chunk 1 + DMAs 0..2 of slab s+3
+//     After the barrier every wave has matrix work in registers at once.  The barrier of step s also says that every wave
+//     is done reading slab s (both chunks: lgkmcnt(0) in front of it), so slab s+3 may land in the same stage from there on.
+//   * split, 8 waves (alternating segments): the two waves of a SIMD take TURNS.  With the mid-slab barrier both run the
+//     same program in lock step - both ask LDS for fragments at the same time, both issue their DMAs at the same time, both
+//     want the matrix pipe at the same time - and the pipe measured 47 - 53 % busy (profiles/r3_gemm_ps256_pmc_sq.txt).
+//     Here every 16-wide K chunk of a slab is a LOAD segment (the chunk's 8 fragment reads into registers + 3 of the
+//     wave's 6 DMAs of the slab two ahead) and a COMPUTE segment (the chunk's 16 matrix instructions out of registers,
+//     nothing else, s_setprio 1), one s_barrier after each; waves 0-3 (one per SIMD) load while waves 4-7 compute and the
+//     other way round:
+//       segment 4s   : waves 0-3  LOAD (s, 0)      waves 4-7  COMPUTE (s-1, 1)
+//       segment 4s+1 : waves 0-3  COMPUTE (s, 0)   waves 4-7  LOAD (s, 0)
+//       segment 4s+2 : waves 0-3  LOAD (s, 1)      waves 4-7  COMPUTE (s, 0)
+//       segment 4s+3 : waves 0-3  COMPUTE (s, 1)   waves 4-7  LOAD (s, 1);  all: wait for slab s+1
+//     A wave's matrix instructions find the pipe free (its partner is in its load segment), and its loads cost no matrix
+//     time.  Moving some of a chunk's DMAs from the load segment in between the compute segment's matrix instructions
+//     measured slower, and neither dropping the priorities, nor raising the load segment's, nor whole-slab segments (two
+//     barriers per slab) moved the time (profiles/r5_gemm_alternating_schedule.txt).
+//     Ordering: the DMAs of slab s+1 are awaited (counted vmcnt, the 6 of slab s+2 stay in flight) in front of the barrier
+//     that ends segment 4s+3 and read from segment 4s+4 on; a stage is refilled (slab s+2 -> stage of slab s-1) from
+//     segment 4s on, its last reads were issued in segment 4s-1 and retired (lgkmcnt(0)) in front of that segment's barrier.
+template <int BM, int BN, int WGM, int WGN, bool SPLIT, bool CONV, bool AMAX>
 __global__ __launch_bounds__(WGM* WGN * 64) void gemm_ps_kernel(GemmPsArgs p, int tiles_n, int tiles_total, int tiles_per_xcd,
                                                                  uint32_t a_bytes, uint32_t w_bytes) {
     constexpr int NWAVE = WGM * WGN;
+    constexpr bool ALTERNATE = SPLIT && NWAVE == 8;  // the K loop's schedule, see above
+    constexpr bool MID_BARRIER = SPLIT && !ALTERNATE;
     constexpr int WM = BM / WGM, WN = BN / WGN;
     constexpr int TM = WM / 32, TN = WN / 32;
     constexpr int ACH = BM / (16 * NWAVE);  // 1 KB chunks (16 rows) of the A tile per wave
@@ -297,27 +305,10 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm_ps_kernel(GemmPsArgs p, in
             PS_DMA(rw, &BB[(wave * BCH + j) * 512], b_voff[j], (KOFF));                        \
     } while (0)
 
-#define PS_COMPUTE(AH, AL, BB)                                                                                         \
-    do {                                                                                                               \
-        _Pragma("unroll") for (int kc = 0; kc < 2; ++kc) {                                                             \
-            half8_t ah[TM], al[TM], bf[TN];                                                                            \
-            _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                           \
-                ah[i] = *reinterpret_cast<const half8_t*>(reinterpret_cast<const char*>(AH) + a_off[i][kc]);            \
-                al[i] = *reinterpret_cast<const half8_t*>(reinterpret_cast<const char*>(AL) + a_off[i][kc]);            \
-            }                                                                                                          \
-            _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                             \
-                bf[j] = *reinterpret_cast<const half8_t*>(reinterpret_cast<const char*>(BB) + b_off[j][kc]);            \
-            _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                             \
-                _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                       \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bf[j], acc[i][j], 0, 0, 0);               \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bf[j], acc[i][j], 0, 0, 0);               \
-                }                                                                                                      \
-        }                                                                                                              \
-    } while (0)
-
     constexpr int NDMA = 2 * ACH + BCH;                   // DMA slots per wave and slab (the lo slots stay empty without SPLIT)
     constexpr int NLIVE = SPLIT ? NDMA : ACH + BCH;       // DMA instructions really issued per wave and slab
     static_assert(NDMA == 6 || NDMA == 3, "two or one 1 KB chunk per operand and wave");
+    static_assert(NLIVE < 16, "vmcnt(NLIVE) in the low bits of s_waitcnt");
 
 // DMA number Q (0 .. NDMA-1) of a slab, in the order of PS_ISSUE: A_hi / A_lo chunk pairs, then the W chunks
 #define PS_DMA_Q(Q, AH, AL, BB, KOFF)                                                                         \
@@ -329,76 +320,54 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm_ps_kernel(GemmPsArgs p, in
             PS_DMA(rw, &BB[(wave * BCH + ((Q) - 2 * ACH)) * 512], b_voff[(Q) - 2 * ACH], (KOFF));              \
         }                                                                                                     \
     } while (0)
+#define PS_LDS8(BASE, OFF) (*reinterpret_cast<const half8_t*>(reinterpret_cast<const char*>(BASE) + (OFF)))
 
-// PS_COMPUTE with (a) every fragment of the slab (both 16-wide K chunks) requested from LDS before the first matrix
-// instruction, so that the LDS latency of the second chunk runs under the first chunk's MFMAs, and (b) the refill of
-// stage (NAH, NAL, NB) spread over the slab: DMA q follows the q-th hi/lo MFMA pair
-#define PS_COMPUTE_ILV(AH, AL, BB, DO_ISSUE, NAH, NAL, NB, KOFF)                                                       \
+// Hi plane only.  Slab S sits in stage (CAH, CB); the DMAs of slab S+1 (if any) are the youngest outstanding ones: wait
+// until only those remain, make the landed data visible to every wave, then request every fragment of the slab (both
+// 16-wide K chunks) from LDS before the first matrix instruction, so that the LDS latency of the second chunk runs under
+// the first chunk's MFMAs, and spread the refill of the stage read at slab S-1 (NAH, NB) over the slab: DMA slot q
+// follows the q-th MFMA.
+#define PS_STEP(S, CAH, CB, NAH, NB)                                                                                   \
     do {                                                                                                               \
-        half8_t ah[2][TM], al[2][TM], bf[2][TN];                                                                       \
+        if ((S) + 1 < nslab) __builtin_amdgcn_s_waitcnt(0x0070 | NLIVE); /* vmcnt(NLIVE) lgkmcnt(0) */                \
+        else __builtin_amdgcn_s_waitcnt(0x0070);                         /* vmcnt(0) lgkmcnt(0) */                     \
+        __builtin_amdgcn_s_barrier();                                                                                  \
+        asm volatile("" ::: "memory");                                                                                 \
+        const bool more_ = (S) + 2 < nslab;                                                                            \
+        half8_t ah[2][TM], bf[2][TN];                                                                                  \
         _Pragma("unroll") for (int kc = 0; kc < 2; ++kc) {                                                             \
-            _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                           \
-                ah[kc][i] = *reinterpret_cast<const half8_t*>(reinterpret_cast<const char*>(AH) + a_off[i][kc]);        \
-                if (SPLIT) al[kc][i] = *reinterpret_cast<const half8_t*>(reinterpret_cast<const char*>(AL) + a_off[i][kc]); \
-            }                                                                                                          \
-            _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                             \
-                bf[kc][j] = *reinterpret_cast<const half8_t*>(reinterpret_cast<const char*>(BB) + b_off[j][kc]);        \
+            _Pragma("unroll") for (int i = 0; i < TM; ++i) ah[kc][i] = PS_LDS8(CAH, a_off[i][kc]);                     \
+            _Pragma("unroll") for (int j = 0; j < TN; ++j) bf[kc][j] = PS_LDS8(CB, b_off[j][kc]);                      \
         }                                                                                                              \
-        if (DO_ISSUE) PS_NEXT_ADDR();                                                                                  \
+        if (more_) PS_NEXT_ADDR();                                                                                     \
         __builtin_amdgcn_sched_barrier(0);                                                                             \
         int q_ = 0;                                                                                                    \
         _Pragma("unroll") for (int kc = 0; kc < 2; ++kc) {                                                             \
             _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                             \
                 _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                       \
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[kc][i], bf[kc][j], acc[i][j], 0, 0, 0);       \
-                    if (SPLIT) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[kc][i], bf[kc][j], acc[i][j], 0, 0, 0); \
                     if (q_ < NDMA) {                                                                                   \
                         __builtin_amdgcn_sched_barrier(0);                                                             \
-                        if (DO_ISSUE) PS_DMA_Q(q_, NAH, NAL, NB, KOFF);                                                \
+                        if (more_) PS_DMA_Q(q_, NAH, NAH, NB, ((S) + 2) * (PBK * 2));                                  \
                         __builtin_amdgcn_sched_barrier(0);                                                             \
                     }                                                                                                  \
                     ++q_;                                                                                              \
                 }                                                                                                      \
         }                                                                                                              \
-        /* tiles with fewer MFMA pairs than DMAs (64 x 64: 2 pairs, 3 DMAs): the rest follows the last pair */         \
+        /* tiles with fewer MFMAs than DMA slots (64 x 64: 2 MFMAs, 3 slots): the rest follows the last one */         \
         _Pragma("unroll") for (int q2 = 2 * TM * TN; q2 < NDMA; ++q2)                                                  \
-            if (DO_ISSUE) PS_DMA_Q(q2, NAH, NAL, NB, KOFF);                                                            \
-    } while (0)
-
-// Slab S sits in stage (CUR); the DMAs of slab S+1 (if any) are the youngest outstanding ones: wait until only
-// those remain, make the landed data visible to every wave, then refill the stage that was read at slab S-1.
-#define PS_STEP(S, CAH, CAL, CB, NAH, NAL, NB)                                                 \
-    do {                                                                                       \
-        if ((S) + 1 < nslab) {                                                                 \
-            if (NLIVE == 6) __builtin_amdgcn_s_waitcnt(0x0076);      /* vmcnt(6) lgkmcnt(0) */ \
-            else if (NLIVE == 4) __builtin_amdgcn_s_waitcnt(0x0074); /* vmcnt(4) */            \
-            else if (NLIVE == 3) __builtin_amdgcn_s_waitcnt(0x0073); /* vmcnt(3) */            \
-            else __builtin_amdgcn_s_waitcnt(0x0072);                 /* vmcnt(2) */            \
-        } else {                                                                               \
-            __builtin_amdgcn_s_waitcnt(0x0070); /* vmcnt(0) lgkmcnt(0) */                      \
-        }                                                                                      \
-        __builtin_amdgcn_s_barrier();                                                          \
-        asm volatile("" ::: "memory");                                                         \
-        if (ILV) {                                                                             \
-            const bool more_ = (S) + 2 < nslab;                                                \
-            PS_COMPUTE_ILV(CAH, CAL, CB, more_, NAH, NAL, NB, ((S) + 2) * (PBK * 2));          \
-        } else {                                                                               \
-            if ((S) + 2 < nslab) PS_ISSUE(NAH, NAL, NB, ((S) + 2) * (PBK * 2));                \
-            PS_COMPUTE(CAH, CAL, CB);                                                          \
-        }                                                                                      \
-        asm volatile("" ::: "memory");                                                         \
+            if (more_) PS_DMA_Q(q2, NAH, NAH, NB, ((S) + 2) * (PBK * 2));                                              \
+        asm volatile("" ::: "memory");                                                                                 \
     } while (0)
 
     const int nslab = p.K / PBK;
-    if constexpr (PP > 0) {
-        static_assert(PP == 0 || (ILV && SPLIT && NWAVE == 8 && NDMA == 6), "the alternating schedule is written for the split 8-wave tile");
-        constexpr int NH = NDMA / 2;  // DMAs of a slab per 16-wide K chunk and wave
-        constexpr int NL = PP - 1;    // ... of which the LOAD segment issues NL, the COMPUTE segment (between its matrix instructions) NH - NL
+    if constexpr (ALTERNATE) {
+        static_assert(NDMA == 6, "the alternating schedule is written for the split 8-wave tile");
+        constexpr int NH = NDMA / 2;  // DMAs of a slab per 16-wide K chunk and wave, all issued by the chunk's LOAD segment
         const bool grp_b = __builtin_amdgcn_readfirstlane(wave) >= NWAVE / 2;
         half8_t f_ah[TM], f_al[TM], f_bf[TN];  // the fragments of one 16-wide K chunk
-#define PS_LDS8(BASE, OFF) (*reinterpret_cast<const half8_t*>(reinterpret_cast<const char*>(BASE) + (OFF)))
-// LOAD segment of chunk KC of slab S (stage C*): the chunk's 8 fragment reads, then NL of the wave's DMAs of slab S+2 (stage
-// N*), then every read retired (the stage may be refilled one segment after the barrier that follows)
+// LOAD segment of chunk KC of slab S (stage C*): the chunk's 8 fragment reads, then the wave's NH DMAs of that chunk for
+// slab S+2 (stage N*), then every read retired (the stage may be refilled one segment after the barrier that follows)
 #define PP_LOADSEG(S, KC, CAH, CAL, CB, NAH, NAL, NB)                                           \
     do {                                                                                        \
         _Pragma("unroll") for (int j = 0; j < TN; ++j) f_bf[j] = PS_LDS8(CB, b_off[j][KC]);     \
@@ -407,35 +376,22 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm_ps_kernel(GemmPsArgs p, in
             f_al[i] = PS_LDS8(CAL, a_off[i][KC]);                                               \
         }                                                                                       \
         __builtin_amdgcn_sched_barrier(0);                                                      \
-        if (NL > 0 && (S) + 2 < nslab) {                                                        \
+        if ((S) + 2 < nslab) {                                                                  \
             if ((KC) == 0) PS_NEXT_ADDR();                                                      \
-            _Pragma("unroll") for (int q = (KC) * NH; q < (KC) * NH + NL; ++q) PS_DMA_Q(q, NAH, NAL, NB, ((S) + 2) * (PBK * 2)); \
+            _Pragma("unroll") for (int q = (KC) * NH; q < (KC) * NH + NH; ++q) PS_DMA_Q(q, NAH, NAL, NB, ((S) + 2) * (PBK * 2)); \
         }                                                                                       \
         __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0), vmcnt untouched */                   \
         __builtin_amdgcn_sched_barrier(0);                                                      \
     } while (0)
 // COMPUTE segment: the chunk's hi products of all eight accumulators, then the lo products (an accumulator's two instructions
-// are eight issues apart; its order hi, lo is the one of every other schedule); if DO_DMA, the DMAs Q0 .. Q0 + NH - NL - 1
-// of slab SLAB (stage N*) spread between them (an LDS-DMA issue among matrix instructions costs the wave ~60 cycles, in a
-// segment that carries fragment reads 100 - 185: MI355X_MICROARCH.md)
-#define PP_MFMA(DO_DMA, Q0, SLAB, NAH, NAL, NB)                                                                    \
+// are eight issues apart; its order hi, lo is the one of every other schedule)
+#define PP_COMPUTE()                                                                                               \
     do {                                                                                                           \
-        constexpr int NC_ = NH - NL; /* DMAs of this segment */                                                    \
-        const bool dma_ = (DO_DMA);                                                                                \
-        if (NC_ > 0 && dma_ && (Q0) == 0) PS_NEXT_ADDR();                                                          \
         __builtin_amdgcn_s_setprio(1);                                                                             \
         _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                                           \
             _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                         \
-                _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                   \
+                _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                     \
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h_ == 0 ? f_ah[i] : f_al[i], f_bf[j], acc[i][j], 0, 0, 0); \
-                    const int n_ = h_ * TM * TN + i * TN + j + 1; /* matrix instructions issued so far */          \
-                    _Pragma("unroll") for (int d_ = 0; d_ < NC_; ++d_)                                             \
-                        if (n_ == (d_ + 1) * (2 * TM * TN) / (NC_ + 1)) {                                          \
-                            __builtin_amdgcn_sched_barrier(0);                                                     \
-                            if (dma_) PS_DMA_Q((Q0) + d_, NAH, NAL, NB, (SLAB) * (PBK * 2));                       \
-                            __builtin_amdgcn_sched_barrier(0);                                                     \
-                        }                                                                                          \
-                }                                                                                                  \
         __builtin_amdgcn_s_setprio(0);                                                                             \
     } while (0)
 #define PP_BARRIER()                            \
@@ -445,37 +401,36 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm_ps_kernel(GemmPsArgs p, in
         asm volatile("" ::: "memory");          \
         __builtin_amdgcn_sched_barrier(0);      \
     } while (0)
-// slab S (stage C*; O* = stage of slab S+1, N* = stage of slab S+2, the one slab S-1 sat in): four segments.  ROLE_B = false
-// (waves 0-3): load / compute / load / compute; true (waves 4-7): compute (the previous chunk) / load / compute / load.  The
-// two roles are two separate loops (no control flow joins inside the K loop: the 128 accumulator registers stay where they
-// are); both execute the same number of barriers.  At the end of the step slab S+1 must have landed: waves 0-3 have issued
-// all 6 DMAs of slab S+2 by then, waves 4-7 only NH + NL of them (their second compute segment of the slab is the first
-// segment of the next step).
-#define PP_STEP(ROLE_B, S, CAH, CAL, CB, OAH, OAL, OB, NAH, NAL, NB)                            \
+// slab S (stage C*; N* = stage of slab S+2, the one slab S-1 sat in): four segments.  ROLE_B = false (waves 0-3): load /
+// compute / load / compute; true (waves 4-7): compute (the previous chunk) / load / compute / load.  The two roles are two
+// separate loops (no control flow joins inside the K loop: the 128 accumulator registers stay where they are); both execute
+// the same number of barriers.  At the end of the step both roles have issued all 6 DMAs of slab S+2, and slab S+1 must
+// have landed.
+#define PP_STEP(ROLE_B, S, CAH, CAL, CB, NAH, NAL, NB)                                          \
     do {                                                                                        \
         if (!(ROLE_B)) PP_LOADSEG(S, 0, CAH, CAL, CB, NAH, NAL, NB);                            \
-        else if ((S) > 0) PP_MFMA((S) + 1 < nslab, NH + NL, (S) + 1, OAH, OAL, OB);             \
+        else if ((S) > 0) PP_COMPUTE();                                                         \
         PP_BARRIER();                                                                           \
-        if (!(ROLE_B)) PP_MFMA((S) + 2 < nslab, NL, (S) + 2, NAH, NAL, NB);                     \
+        if (!(ROLE_B)) PP_COMPUTE();                                                            \
         else PP_LOADSEG(S, 0, CAH, CAL, CB, NAH, NAL, NB);                                      \
         PP_BARRIER();                                                                           \
         if (!(ROLE_B)) PP_LOADSEG(S, 1, CAH, CAL, CB, NAH, NAL, NB);                            \
-        else PP_MFMA((S) + 2 < nslab, NL, (S) + 2, NAH, NAL, NB);                               \
+        else PP_COMPUTE();                                                                      \
         PP_BARRIER();                                                                           \
-        if (!(ROLE_B)) PP_MFMA((S) + 2 < nslab, NH + NL, (S) + 2, NAH, NAL, NB);                \
+        if (!(ROLE_B)) PP_COMPUTE();                                                            \
         else PP_LOADSEG(S, 1, CAH, CAL, CB, NAH, NAL, NB);                                      \
-        if ((S) + 2 < nslab) __builtin_amdgcn_s_waitcnt((ROLE_B) ? (0x0070 | (NH + NL)) : 0x0076); \
+        if ((S) + 2 < nslab) __builtin_amdgcn_s_waitcnt(0x0076); /* vmcnt(6) lgkmcnt(0) */      \
         else __builtin_amdgcn_s_waitcnt(0x0070);                                                \
         PP_BARRIER();                                                                           \
     } while (0)
 #define PP_LOOP(ROLE_B)                                                                         \
     do {                                                                                        \
         for (int s = 0; s < nslab; s += 3) {                                                    \
-            PP_STEP(ROLE_B, s, sAh0, sAl0, sB0, sAh1, sAl1, sB1, sAh2, sAl2, sB2);              \
-            if (s + 1 < nslab) PP_STEP(ROLE_B, s + 1, sAh1, sAl1, sB1, sAh2, sAl2, sB2, sAh0, sAl0, sB0); \
-            if (s + 2 < nslab) PP_STEP(ROLE_B, s + 2, sAh2, sAl2, sB2, sAh0, sAl0, sB0, sAh1, sAl1, sB1); \
+            PP_STEP(ROLE_B, s, sAh0, sAl0, sB0, sAh2, sAl2, sB2);                               \
+            if (s + 1 < nslab) PP_STEP(ROLE_B, s + 1, sAh1, sAl1, sB1, sAh0, sAl0, sB0);        \
+            if (s + 2 < nslab) PP_STEP(ROLE_B, s + 2, sAh2, sAl2, sB2, sAh1, sAl1, sB1);        \
         }                                                                                       \
-        if (ROLE_B) PP_MFMA(false, 0, 0, sAh0, sAl0, sB0); /* the last chunk of waves 4-7 */    \
+        if (ROLE_B) PP_COMPUTE(); /* the last chunk of waves 4-7 */                             \
     } while (0)
         PS_ISSUE(sAh0, sAl0, sB0, 0);
         if (nslab > 1) PS_ISSUE(sAh1, sAl1, sB1, PBK * 2);
@@ -488,13 +443,10 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm_ps_kernel(GemmPsArgs p, in
 #undef PP_STEP
 #undef PP_BARRIER
 #undef PP_LOADSEG
-#undef PP_MFMA
-#undef PS_LDS8
-    } else if constexpr (HALF) {
-        static_assert(!HALF || (ILV && SPLIT), "the mid-slab barrier schedule is written for the split, interleaved kernel");
+#undef PP_COMPUTE
+    } else if constexpr (MID_BARRIER) {
         constexpr int NH = NDMA / 2;  // DMAs of a slab issued in the second half of step s-3; the rest in the first half of step s-2
         half8_t c_ah[TM], c_al[TM], c_bf[TN];  // chunk-0 fragments of the current slab, carried from the previous step
-#define PS_LDS8(BASE, OFF) (*reinterpret_cast<const half8_t*>(reinterpret_cast<const char*>(BASE) + (OFF)))
 #define PS_READ_C0(AH, AL, BB)                                                                  \
     do {                                                                                        \
         _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                        \
@@ -574,19 +526,17 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm_ps_kernel(GemmPsArgs p, in
         }
 #undef PS_HSTEP
 #undef PS_READ_C0
-#undef PS_LDS8
     } else {
-    PS_ISSUE(sAh0, sAl0, sB0, 0);
-    if (nslab > 1) PS_ISSUE(sAh1, sAl1, sB1, PBK * 2);
-    for (int s = 0; s < nslab; s += 3) {
-        PS_STEP(s, sAh0, sAl0, sB0, sAh2, sAl2, sB2);
-        if (s + 1 < nslab) PS_STEP(s + 1, sAh1, sAl1, sB1, sAh0, sAl0, sB0);
-        if (s + 2 < nslab) PS_STEP(s + 2, sAh2, sAl2, sB2, sAh1, sAl1, sB1);
-    }
+        PS_ISSUE(sAh0, sAl0, sB0, 0);
+        if (nslab > 1) PS_ISSUE(sAh1, sAl1, sB1, PBK * 2);
+        for (int s = 0; s < nslab; s += 3) {
+            PS_STEP(s, sAh0, sB0, sAh2, sB2);
+            if (s + 1 < nslab) PS_STEP(s + 1, sAh1, sB1, sAh0, sB0);
+            if (s + 2 < nslab) PS_STEP(s + 2, sAh2, sB2, sAh1, sB1);
+        }
     }
 #undef PS_STEP
-#undef PS_COMPUTE
-#undef PS_COMPUTE_ILV
+#undef PS_LDS8
 #undef PS_DMA_Q
 #undef PS_NEXT_ADDR
 #undef PS_ISSUE
@@ -659,37 +609,15 @@ void launch_ps_cfg(const GemmPsArgs& a, hipStream_t s) {
     snprintf(name, sizeof(name), "gemm_%dx%d_presplit", BM, BN);
     prof::Scope scope(name, 2.0 * a.M * (double)a.N * a.K,
                       4.0 * a.M * (double)a.K + 2.0 * a.N * (double)a.K + (a.amax ? 8.0 * a.M * (double)a.amax_ld : 4.0 * a.M * (double)a.N * (a.res ? 2.0 : 1.0)), s);
-    static const bool ilv = knob::value("SC_PS_ILV", 1) != 0;  // A/B switch (development)
     const dim3 grid(tiles_per_xcd * 8), block(WGM * WGN * 64);
     const uint32_t ab = (uint32_t)((int64_t)a.M * a.lda * 2), wb = (uint32_t)((int64_t)a.N * a.ldw * 2);
-    static const bool half = knob::value("SC_PS_HALF", 1) != 0;  // mid-slab barrier schedule (A/B switch)
-    // the 8-wave tile on the alternating schedule (SC_PS_PP=0: the lock-step mid-slab-barrier schedule, same bits)
-    // SC_PS_PP=0: the lock-step schedule (HALF).  Template value n = 1 .. 4: alternating, n - 1 of a chunk's 3 DMAs in the load
-    // segment, the rest between the compute segment's matrix instructions; 4 is shipped
-    static const int pp = knob::value("SC_PS_PP", 4);
-    if constexpr (BM == 256) {
-        if (pp > 0 && a.split) {
-#define PS_PP_LAUNCH(N)                                                                                                                             \
-    do {                                                                                                                                            \
-        if (a.amax) hipLaunchKernelGGL((gemm_ps_kernel<BM, BN, WGM, WGN, true, true, false, false, true, N>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb); \
-        else if (a.conv_taps > 0) hipLaunchKernelGGL((gemm_ps_kernel<BM, BN, WGM, WGN, true, true, true, false, false, N>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb); \
-        else hipLaunchKernelGGL((gemm_ps_kernel<BM, BN, WGM, WGN, true, true, false, false, false, N>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb); \
-    } while (0)
-            // 1 .. 3 measured slower, and neither dropping the priorities, nor raising the load segment's, nor whole-slab segments
-            // (two barriers per slab) moved the time: profiles/r5_gemm_alternating_schedule.txt
-            PS_PP_LAUNCH(4);
-#undef PS_PP_LAUNCH
-            return;
-        }
-    }
-    if (a.amax) hipLaunchKernelGGL((gemm_ps_kernel<BM, BN, WGM, WGN, true, true, false, true, true>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb);
-    else if (!a.split && a.conv_taps > 0) hipLaunchKernelGGL((gemm_ps_kernel<BM, BN, WGM, WGN, true, false, true>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb);
-    else if (!a.split) hipLaunchKernelGGL((gemm_ps_kernel<BM, BN, WGM, WGN, true, false>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb);
-    else if (a.conv_taps > 0 && half) hipLaunchKernelGGL((gemm_ps_kernel<BM, BN, WGM, WGN, true, true, true, true>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb);
-    else if (a.conv_taps > 0) hipLaunchKernelGGL((gemm_ps_kernel<BM, BN, WGM, WGN, true, true, true>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb);
-    else if (ilv && half) hipLaunchKernelGGL((gemm_ps_kernel<BM, BN, WGM, WGN, true, true, false, true>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb);
-    else if (ilv) hipLaunchKernelGGL((gemm_ps_kernel<BM, BN, WGM, WGN, true, true>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb);
-    else hipLaunchKernelGGL((gemm_ps_kernel<BM, BN, WGM, WGN, false, true>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb);
+    const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb); };
+    const bool conv = a.conv_taps > 0;
+    if (a.amax) launch(gemm_ps_kernel<BM, BN, WGM, WGN, true, false, true>);  // split, plain product (launch_gemm_presplit)
+    else if (a.split && conv) launch(gemm_ps_kernel<BM, BN, WGM, WGN, true, true, false>);
+    else if (a.split) launch(gemm_ps_kernel<BM, BN, WGM, WGN, true, false, false>);
+    else if (conv) launch(gemm_ps_kernel<BM, BN, WGM, WGN, false, true, false>);
+    else launch(gemm_ps_kernel<BM, BN, WGM, WGN, false, false, false>);
 }
 
 // tile choice: 256 x 256 (8 waves) once it fills the chip about once, 128 x 128 down to one round of 256 tiles,

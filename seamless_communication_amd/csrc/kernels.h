@@ -442,7 +442,7 @@ struct AttnArgs {
     const float* q_bias_u = nullptr;
     const float* q_bias_v = nullptr;
     // packed (varlen) self-attention: item n owns rows row_off[n] .. row_off[n] + kv_lens[n] of q / k / v / out (no padding
-    // rows between items); Sq = Skv = the longest item (grid size only).  Needs kv_lens; fp16-split MFMA kernel only.
+    // rows between items); Sq = Skv = the longest item (grid size only).  Needs kv_lens.
     const int* row_off = nullptr;
     double pairs = 0;  // profiler only: sum over items of (queries x keys) really computed (0: nb * Sq * Skv)
     // optional: write the result as two fp16 planes (hi, lo) for launch_gemm_presplit instead of `out`

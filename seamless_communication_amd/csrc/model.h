@@ -236,21 +236,13 @@ class Engine;
 
 // State bag of the streaming decoder between sc_mma_begin and the sc_mma_step calls of one policy round.
 // Kept ACROSS policy rounds while the geometry fits (max_len unchanged, encoder length within cap_enc): the buffers then
-// keep their addresses and the two captured single-token step graphs (without / with the p_choose hook) stay valid.
+// keep their addresses.
 struct MmaState {
     int s_enc = 0, cap = 0, pos = 0;
     int cap_enc = 0;  // rows per layer of `cross` (>= s_enc; rows behind s_enc are never attended: key mask)
     Buf<float> kv, cross, kenergy, work, pchoose;
     Buf<int> ints;
     Buf<__half> planes;  // split planes of the second-generation step (alloc_step2 layout)
-    hipGraph_t graph[2] = {nullptr, nullptr};
-    hipGraphExec_t exec[2] = {nullptr, nullptr};
-    ~MmaState() {
-        for (int i = 0; i < 2; ++i) {
-            if (exec[i]) (void)hipGraphExecDestroy(exec[i]);
-            if (graph[i]) (void)hipGraphDestroy(graph[i]);
-        }
-    }
 };
 
 // One handle: the model description plus its own stream, scratch pool and per-call results.

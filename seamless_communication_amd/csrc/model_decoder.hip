@@ -834,11 +834,11 @@ void run_mma_begin(Model& m, const float* d_enc, int s_enc, int max_len) {
     size_t work_n = 0;
     mma_work(m, nullptr, &work_n);
     // The state is kept across policy rounds while it fits: a streaming session calls sc_mma_begin once per segment with a
-    // growing encoder length and the same max_len; buffers that keep their addresses keep the captured step graphs valid.
+    // growing encoder length and the same max_len.
     if (!m.mma || m.mma->cap != max_len || m.mma->cap_enc < s_enc) {
         const int grow = m.mma ? m.mma->cap_enc + m.mma->cap_enc / 2 : 0;
         const int cap_enc = std::min(4096, (int)align_up((int64_t)std::max(s_enc, grow), 64));
-        m.mma.reset();  // the previous buffers (and graphs) go first
+        m.mma.reset();  // the previous buffers go first
         std::unique_ptr<MmaState> st(new MmaState());
         st->cap = max_len;
         st->cap_enc = cap_enc;
@@ -939,40 +939,15 @@ void run_mma_step(Model& m, const int32_t* h_tokens, int n_tokens, const int32_t
         c.vcache.push_back(st.kv.get() + (int64_t)(2 * li + 1) * layer_stride);
         c.cross_kv.push_back(st.cross.get() + (int64_t)li * st.cap_enc * 2 * M);
     }
-    // SC_MMA_GRAPH=1: one token = one replay of a captured graph (gen-2 steps only).  Measured on the full-size model
-    // (profiles/r2_stream_latency_graph.jsonl): no gain - a one-row step is 1.3 ms of dependent GPU work + the vocabulary
-    // projection whichever way it is launched (the eager launches run ahead of the GPU) - and every growth of the encoder
-    // buffer costs a re-capture (8 ms); default: eager launches.
-    static const bool use_graph = knob::value("SC_MMA_GRAPH", 0) != 0;
-    auto step = [&](bool with_pchoose) {
-        c.pchoose = with_pchoose;
-        const int gi = with_pchoose ? 1 : 0;
-        if (!gen2 || !use_graph || prof::enabled()) {
-            decoder_step(m, c, /*project=*/false);  // advances *d_pos
-            return;
-        }
-        if (!st.exec[gi]) {
-            std::lock_guard<std::mutex> lock(g_capture_mutex);
-            SC_HIP(hipStreamBeginCapture(m.stream, hipStreamCaptureModeThreadLocal));
-            try {
-                decoder_step(m, c, /*project=*/false);
-            } catch (...) {
-                hipGraph_t dead = nullptr;
-                (void)hipStreamEndCapture(m.stream, &dead);
-                if (dead) (void)hipGraphDestroy(dead);
-                throw;
-            }
-            SC_HIP(hipStreamEndCapture(m.stream, &st.graph[gi]));
-            SC_HIP(hipGraphInstantiate(&st.exec[gi], st.graph[gi], nullptr, nullptr, 0));
-        }
-        SC_HIP(hipGraphLaunch(st.exec[gi], m.stream));
-    };
     for (int t0 = 0; t0 < n_tokens; t0 += 32) {
         const int nt = std::min(32, n_tokens - t0);
         SC_HIP(hipMemcpyAsync(d_feed, h_tokens + t0, (size_t)nt * 4, hipMemcpyHostToDevice, m.stream));
         for (int t = 0; t < nt; ++t) {
             SC_HIP(hipMemcpyAsync(c.d_tok, d_feed + t, 4, hipMemcpyDeviceToDevice, m.stream));
-            step(t0 + t == n_tokens - 1);
+            // eager launches: replaying a captured step measured no gain (a one-row step is 1.3 ms of dependent GPU work
+            // either way, profiles/r2_stream_latency_graph.jsonl)
+            c.pchoose = t0 + t == n_tokens - 1;
+            decoder_step(m, c, /*project=*/false);  // advances *d_pos
             SC_HIP(hipMemcpyAsync(d_features + (int64_t)(t0 + t) * M, c.hN, (size_t)M * 4, hipMemcpyDeviceToDevice, m.stream));
         }
         SC_HIP(hipStreamSynchronize(m.stream));  // the pageable source of d_feed may be reused

@@ -123,16 +123,12 @@ def gemm_ps_isa(tmp_path_factory):
     return _isa("k_gemm_ps.hip", tmp_path_factory.mktemp("gemmps"))
 
 
-# template arguments: tile, waves, ILV, SPLIT, CONV, HALF (mid-slab barrier), AMAX (arg-max epilogue), PP (alternating load /
-# compute segments: the shipped schedule of the 8-wave tile, linted separately below)
-@pytest.mark.parametrize("inst,mfmas_per_slab", [("gemm_ps_kernelILi256ELi256ELi4ELi2ELb1ELb1ELb0ELb1ELb0ELi0E", 32),
-                                                 ("gemm_ps_kernelILi256ELi256ELi4ELi2ELb1ELb1ELb1ELb1ELb0ELi0E", 32),
-                                                 ("gemm_ps_kernelILi128ELi128ELi2ELi2ELb1ELb1ELb0ELb1ELb0ELi0E", 16),
-                                                 ("gemm_ps_kernelILi256ELi256ELi4ELi2ELb1ELb1ELb0ELb0ELb0ELi0E", 32),
-                                                 ("gemm_ps_kernelILi128ELi128ELi2ELi2ELb1ELb1ELb0ELb0ELb0ELi0E", 16),
+# template arguments: tile, waves, SPLIT, CONV, AMAX (arg-max epilogue).  The split 4-wave tiles run the mid-slab barrier
+# schedule linted here; the split 8-wave tile alternates load / compute segments (linted separately below)
+@pytest.mark.parametrize("inst,mfmas_per_slab", [("gemm_ps_kernelILi128ELi128ELi2ELi2ELb1ELb0ELb0E", 16),
+                                                 ("gemm_ps_kernelILi128ELi128ELi2ELi2ELb1ELb1ELb0E", 16),
                                                  # the arg-max epilogue (unit projection): same slab loop
-                                                 ("gemm_ps_kernelILi256ELi256ELi4ELi2ELb1ELb1ELb0ELb1ELb1ELi0E", 32),
-                                                 ("gemm_ps_kernelILi128ELi128ELi2ELi2ELb1ELb1ELb0ELb1ELb1ELi0E", 16)])
+                                                 ("gemm_ps_kernelILi128ELi128ELi2ELi2ELb1ELb0ELb1E", 16)])
 def test_dma_gemm_slab_loop_keeps_its_pipeline(gemm_ps_isa, inst, mfmas_per_slab):
     """The K loop of the pre-split GEMM (plain and implicit-conv variant): no scratch, DMAs issued as
     `buffer_load_dwordx4 ... lds` between the matrix instructions, one s_barrier per slab, and the only full drain
@@ -154,11 +150,11 @@ def test_dma_gemm_slab_loop_keeps_its_pipeline(gemm_ps_isa, inst, mfmas_per_slab
     assert any(o.startswith("buffer_load_dwordx4") for o in ops[first:last])
 
 
-@pytest.mark.parametrize("inst", ["gemm_ps_kernelILi256ELi256ELi4ELi2ELb1ELb1ELb0ELb0ELb0ELi4E",   # plain
-                                  "gemm_ps_kernelILi256ELi256ELi4ELi2ELb1ELb1ELb1ELb0ELb0ELi4E",   # implicit convolution
-                                  "gemm_ps_kernelILi256ELi256ELi4ELi2ELb1ELb1ELb0ELb0ELb1ELi4E"])  # arg-max epilogue
+@pytest.mark.parametrize("inst", ["gemm_ps_kernelILi256ELi256ELi4ELi2ELb1ELb0ELb0E",   # plain
+                                  "gemm_ps_kernelILi256ELi256ELi4ELi2ELb1ELb1ELb0E",   # implicit convolution
+                                  "gemm_ps_kernelILi256ELi256ELi4ELi2ELb1ELb0ELb1E"])  # arg-max epilogue
 def test_dma_gemm_alternating_schedule_keeps_its_segments(gemm_ps_isa, inst):
-    """The 8-wave tile's alternating schedule (k_gemm_ps.hip, PP): no scratch (the two roles are two loops - one loop with a
+    """The split 8-wave tile's alternating schedule (k_gemm_ps.hip): no scratch (the two roles are two loops - one loop with a
     role branch per segment spilt 900 bytes per lane); a COMPUTE segment is `s_setprio 1`, 16 matrix instructions and nothing
     else, `s_setprio 0`; a LOAD segment is 8 fragment reads, 3 DMAs, lgkmcnt(0); segments end in a barrier; the DMAs of the
     slab two ahead are left in flight by a counted vmcnt(6), and only tail branches drain."""
