@@ -30,12 +30,17 @@ and finish inside the timed region; the wall time of a single pass is reported a
 reports it under ``extra.lockstep``.
 
 Rank 0 prints ONE JSON line.  ``value`` is utterances/s over all GPUs (weak
-scaling: per-GPU batch fixed).  ``roofline`` describes the kernel family with
-the largest share of GPU time, from per-launch HIP events recorded on the
-library's own stream in one extra profiled step after the timed region;
-``cpu_baseline`` is the CPU oracle (a port of the reference's fairseq2 path,
-the reference itself is not runnable offline) on ONE utterance of the same
-workload on this host's cores (rank 0, N=1 only).
+scaling: per-GPU batch fixed).  A plain run does only what that figure needs:
+set up, warm up, time the K steps, write ``--dump-outputs`` if asked, print the
+line (``roofline`` and ``cpu_baseline`` null).  ``--full`` adds everything
+else, each part still switched off by its own ``--no-*`` option: ``roofline``
+describes the kernel family with the largest share of GPU time, from per-launch
+HIP events recorded on the library's own stream in one extra profiled step
+after the timed region; ``latency_batch1``, the secondary lines under
+``extra`` (N=1 only) and ``parity`` (the timed batch against the oracle's
+committed ids); ``cpu_baseline`` is the CPU oracle (a port of the reference's
+fairseq2 path, the reference itself is not runnable offline) on ONE utterance
+of the same workload on this host's cores (rank 0, N=1 only).
 """
 from __future__ import annotations
 
@@ -132,7 +137,14 @@ def parse_args():
                          f"{DUMP_LIMIT_BYTES // 10**6} MB); inputs and weights are seeded, so two builds can be compared file by file")
     ap.add_argument("--stagger", type=float, default=-1.0,
                     help="start offset between micro-batch threads in the timed region, seconds (<0: warm-up step time / threads)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the profiled pass (roofline), the batch-1 "
+                         "latency, the secondary lines (extra), the parity check against the oracle's committed ids and the CPU "
+                         "baseline; --no-profile-step / --no-latency / --no-extra / --no-cpu-baseline drop single parts of it")
+    args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, the timed steps, --dump-outputs, the line
+        args.no_profile_step = args.no_latency = args.no_extra = args.no_cpu_baseline = True
+    return args
 
 
 def dump_outputs(out_dir, text_ids, units, wavs):
@@ -948,7 +960,7 @@ def main():
             "value": utt_per_s, "unit": "utterances/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "ms_each_step": [round(1e3 * (b - a), 1) for a, b in zip(step_marks, step_marks[1:])],
-            "dtype": "f32 activations x f16 weights, f32 accumulate", "data": "synthetic",
+            "dtype": "f32 activations x f16 weights, f32 accumulate", "data": "synthetic", "full": bool(args.full),
             "rtf": (elapsed / args.steps) / (B * AUDIO_SECONDS),
             "config": {
                 "workload": "S2ST 10 s 16 kHz audio -> text -> units -> 16 kHz waveform (BASELINE configs[2])",
@@ -1181,22 +1193,22 @@ def main():
         dist.barrier()
 
     if rank == 0:
-        # every utterance of the timed batch against the oracle's committed ids (tests/golden/fullsize_ref.json)
-        try:
-            result["parity"] = parity_from_goldens(args, eff_groups, {"text_ids": timed_text_ids}, B, t2u_snapshot, first_index=rank * B)
-        except Exception as e:  # noqa: BLE001  (a fixture / shape surprise must not lose the measured line)
-            result["parity"] = {"n_checked": 0, "error": repr(e)[:300]}
-        if world == 1 and not args.no_cpu_baseline:
-            log("CPU baseline (oracle: warm-up + 3 passes) in a child process ...")
-            base = cpu_baseline(args)
-            # ... and two utterances against the oracle run live in this job (the cpu_baseline child)
-            result["parity"]["live_oracle"] = parity_block(base, translator, model, wav_host, ns, opts, last, device)
-            base.pop("checked", None)
-            result["cpu_baseline"] = base
-        else:
-            result["cpu_baseline"] = None
-        # the driver keeps `config` verbatim: the parity verdict travels there too
-        result["config"]["parity"] = result["parity"]
+        result["cpu_baseline"] = None
+        if args.full:
+            # every utterance of the timed batch against the oracle's committed ids (tests/golden/fullsize_ref.json)
+            try:
+                result["parity"] = parity_from_goldens(args, eff_groups, {"text_ids": timed_text_ids}, B, t2u_snapshot, first_index=rank * B)
+            except Exception as e:  # noqa: BLE001  (a fixture / shape surprise must not lose the measured line)
+                result["parity"] = {"n_checked": 0, "error": repr(e)[:300]}
+            if world == 1 and not args.no_cpu_baseline:
+                log("CPU baseline (oracle: warm-up + 3 passes) in a child process ...")
+                base = cpu_baseline(args)
+                # ... and two utterances against the oracle run live in this job (the cpu_baseline child)
+                result["parity"]["live_oracle"] = parity_block(base, translator, model, wav_host, ns, opts, last, device)
+                base.pop("checked", None)
+                result["cpu_baseline"] = base
+            # the driver keeps `config` verbatim: the parity verdict travels there too
+            result["config"]["parity"] = result["parity"]
         print(json.dumps(result), flush=True)
     try:
         batcher.close()  # worker pool and (if still there) the decode engine's thread

@@ -5,7 +5,7 @@
 # `timeout` so that a hung kernel cannot hold the box.  Tasks:
 #   tests        the whole `-m gpu` suite                       fullsize   tests/test_fullsize_gpu.py only
 #   quick        op + stage tests (tiny model)                  smoke      __graft_entry__.smoke()
-#   bench        python bench.py $BENCH_ARGS                    benchfast  bench without cpu baseline / latency
+#   bench        python bench.py --full $BENCH_ARGS             benchfast  the same without cpu baseline / latency / extras
 #   rocprof      rocprofv3 --kernel-trace --stats of `bench.py $PROF_ARGS` (the driver's command line by default)
 #   pmc          FETCH_SIZE / WRITE_SIZE passes (separate runs) + scripts/pmc_summary.py
 #   dstep        scripts/dstep_bench.py (decoder step timing per batch size)         dtrace   kernel trace of it + gap analysis
@@ -32,7 +32,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 TAG=$1; shift
 O=gpurun_out/$TAG
 BENCH_ARGS=${BENCH_ARGS:---steps 5 --warmup 2}
-PROF_ARGS=${PROF_ARGS:---steps 3 --warmup 1 --no-cpu-baseline --no-latency --no-extra}
+PROF_ARGS=${PROF_ARGS:---steps 3 --warmup 1 --full --no-cpu-baseline --no-latency --no-extra}
 
 line() { python - "$1" <<'PY'
 import json, sys
@@ -66,16 +66,16 @@ for task in "$@"; do
     smoke)
       ( timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > ${O}_smoke.log 2>&1; echo "smoke exit $?" >> ${O}_smoke.log ); tail -2 ${O}_smoke.log | cut -c1-300 ;;
     bench)
-      ( timeout 900 python bench.py $BENCH_ARGS > ${O}_bench.json 2> ${O}_bench.err; echo "exit $?" >> ${O}_bench.err ); tail -3 ${O}_bench.err | cut -c1-300; line ${O}_bench.json ;;
+      ( timeout 900 python bench.py --full $BENCH_ARGS > ${O}_bench.json 2> ${O}_bench.err; echo "exit $?" >> ${O}_bench.err ); tail -3 ${O}_bench.err | cut -c1-300; line ${O}_bench.json ;;
     benchfast)
-      ( timeout 600 python bench.py $BENCH_ARGS --no-cpu-baseline --no-latency --no-extra > ${O}_benchfast.json 2> ${O}_benchfast.err; echo "exit $?" >> ${O}_benchfast.err ); tail -2 ${O}_benchfast.err | cut -c1-300; line ${O}_benchfast.json ;;
+      ( timeout 600 python bench.py --full $BENCH_ARGS --no-cpu-baseline --no-latency --no-extra > ${O}_benchfast.json 2> ${O}_benchfast.err; echo "exit $?" >> ${O}_benchfast.err ); tail -2 ${O}_benchfast.err | cut -c1-300; line ${O}_benchfast.json ;;
     argsweep)
       # benchfast once per extra argument list of $ARGSWEEP (';'-separated: ARGSWEEP="--microbatches 2;--free-run")
       IFS=';' read -ra SW <<< "$ARGSWEEP"
       i=0
       for e in "${SW[@]}"; do
         i=$((i+1))
-        ( timeout 400 python bench.py $BENCH_ARGS --no-cpu-baseline --no-latency --no-extra $e > ${O}_argsweep_$i.json 2> ${O}_argsweep_$i.err; echo "exit $?" >> ${O}_argsweep_$i.err )
+        ( timeout 400 python bench.py --full $BENCH_ARGS --no-cpu-baseline --no-latency --no-extra $e > ${O}_argsweep_$i.json 2> ${O}_argsweep_$i.err; echo "exit $?" >> ${O}_argsweep_$i.err )
         echo "--- $e"; tail -1 ${O}_argsweep_$i.err; line ${O}_argsweep_$i.json
       done ;;
     benchsweep)
@@ -83,7 +83,7 @@ for task in "$@"; do
       IFS=';' read -ra SW <<< "$SWEEP"
       for e in "${SW[@]}"; do
         n=$(echo "$e" | tr ' =' '__')
-        ( env $e timeout 400 python bench.py $BENCH_ARGS --no-cpu-baseline --no-latency --no-extra > ${O}_sweep_$n.json 2> ${O}_sweep_$n.err; echo "exit $?" >> ${O}_sweep_$n.err )
+        ( env $e timeout 400 python bench.py --full $BENCH_ARGS --no-cpu-baseline --no-latency --no-extra > ${O}_sweep_$n.json 2> ${O}_sweep_$n.err; echo "exit $?" >> ${O}_sweep_$n.err )
         echo "--- $e"; tail -1 ${O}_sweep_$n.err; line ${O}_sweep_$n.json
       done ;;
     rocprof)

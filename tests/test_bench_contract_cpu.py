@@ -25,6 +25,20 @@ def test_argument_contract(monkeypatch):
     assert (a.gpus, a.steps, a.warmup) == (8, 5, 2)
 
 
+def test_plain_run_measures_the_headline_only(monkeypatch):
+    """Without --full a run skips every part the headline does not need (profiled pass, batch-1 latency, secondary lines,
+    CPU baseline; the parity check is gated on `full` in main()); --full runs them, each still switched off by its --no-* option."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse_args()
+    assert a.full is False and a.no_profile_step and a.no_latency and a.no_extra and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse_args()
+    assert a.full is True and not (a.no_profile_step or a.no_latency or a.no_extra or a.no_cpu_baseline)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-extra", "--no-latency"])
+    a = bench.parse_args()
+    assert a.no_extra and a.no_latency and not (a.no_profile_step or a.no_cpu_baseline)
+
+
 def test_cpu_baseline_worker_reports_the_oracle_on_one_utterance():
     """1 warm-up + 3 timed passes (median), per-stage split, and the ids / arg-max margins of the checked utterances."""
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--cpu-baseline-worker", "--arch", "tiny_v2", "--text-len", "10",

@@ -67,7 +67,7 @@ def test_bench_two_ranks_over_rccl():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs (one rank per GPU)")
     root = Path(__file__).resolve().parent.parent
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-latency",
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-latency",
                         "--no-extra", "--no-profile-step"], capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-800:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
