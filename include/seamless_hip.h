@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SC_ABI_VERSION 9
+#define SC_ABI_VERSION 10
 #define SC_MAX_UPSAMPLES 8
 #define SC_MAX_RESBLOCK_KERNELS 4
 #define SC_MAX_RESBLOCK_DILATIONS 4
@@ -207,6 +207,19 @@ int32_t sc_text_max_len(const sc_model* m, const sc_gen_opts* opts, int32_t s_en
 int sc_generate_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
                      const sc_gen_opts* opts, const int32_t* h_prefix, int32_t prefix_len, int32_t* h_out_ids,
                      int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden);
+
+/* Greedy generation that also returns what the reference's Transcriber hooks into the model (ABI 10;
+ * inference/transcriber.py:39-57, 124-127): per utterance and per FED position p (prompt positions included) the
+ * probabilities of the last decoder layer's encoder-decoder attention of the query fed at p, summed over the heads,
+ * d_xattn [n][max_len][s_enc] on the device (0 behind the utterance's encoder length), and h_step_lprob [n][max_len] on the
+ * host: the log-probability (after the step rules) of the token chosen at p, 0 at prompt positions.  Positions at which an
+ * utterance was not fed (after its EOS) are 0 in both.  max_len = sc_text_max_len(opts, s_enc).  Ids, lengths, scores and
+ * decoder outputs equal sc_generate_text's bit for bit.  Greedy only (beam_size 1, no_repeat_ngram_size 0) on the row-group
+ * decoder step (1..64 rows, heads of width 64, at most 16); other cases fail.  Runs on the handle's own step chain even
+ * with a decode engine attached. */
+int sc_generate_text_capture(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
+                             const sc_gen_opts* opts, const int32_t* h_prefix, int32_t prefix_len, int32_t* h_out_ids,
+                             int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden, float* d_xattn, float* h_step_lprob);
 
 /* Decode engine (ABI 8; no reference counterpart - the reference generates one batch at a time, inference/generator.py:
  * 227-299, and has no serving layer).  ONE greedy decoder-step chain per GPU, shared by every handle it is attached to: a

@@ -16,7 +16,7 @@ import os
 _VARIANT = os.environ.get("SC_LIB_VARIANT", "")
 LIB_PATH = Path(__file__).resolve().parent / (f"libseamless_hip.{_VARIANT}.so" if _VARIANT else "libseamless_hip.so")
 
-SC_ABI_VERSION = 9
+SC_ABI_VERSION = 10
 SC_MAX_UPSAMPLES = 8
 SC_MAX_RESBLOCK_KERNELS = 4
 SC_MAX_RESBLOCK_DILATIONS = 4
@@ -121,6 +121,7 @@ SIGNATURES = {
     "sc_mma_step": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "sc_text_max_len": (_i, [_P, C.POINTER(sc_gen_opts), _i]),
     "sc_generate_text": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P]),
+    "sc_generate_text_capture": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P, _P, _P]),
     "sc_decode_text": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P]),
     "sc_engine_create": (_P, [_P, C.POINTER(sc_engine_opts)]),
     "sc_engine_free": (None, [_P]),

@@ -247,6 +247,21 @@ int sc_generate_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, 
     SC_API_END
 }
 
+int sc_generate_text_capture(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
+                             const sc_gen_opts* opts, const int32_t* h_prefix, int32_t prefix_len, int32_t* h_out_ids,
+                             int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden, float* d_xattn, float* h_step_lprob) {
+    SC_API_BEGIN
+    SC_CHECK(m && d_enc && h_enc_lens && opts && h_prefix && h_out_ids && h_out_lens && d_xattn && h_step_lprob,
+             "sc_generate_text_capture: null argument");
+    SC_HIP(hipSetDevice(m->m.device));
+    XattnCapture xc;
+    xc.d_xattn = d_xattn;
+    xc.h_step_lprob = h_step_lprob;
+    run_generate_text(m->m, d_enc, n, s_enc, h_enc_lens, *opts, h_prefix, prefix_len, h_out_ids, h_out_lens, h_out_scores,
+                      d_dec_hidden, nullptr, 0, &xc);
+    SC_API_END
+}
+
 sc_engine* sc_engine_create(sc_model* m, const sc_engine_opts* opts) {
     sc_engine* h = nullptr;
     try {

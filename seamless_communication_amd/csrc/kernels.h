@@ -600,6 +600,31 @@ struct RowSwapArgs {
 };
 void launch_row_swap(const RowSwapArgs& a, hipStream_t s);
 
+// Greedy generation with cross-attention capture (k_xattn.hip; sc_generate_text_capture): one launch after a step of the
+// row-group chain.  Row slot b that was fed at this step (position *d_pos - 1) gets the soft-max of the LAST decoder layer's
+// encoder-decoder attention summed over the heads in head order, xattn[slot_utt[b]][pos][0 .. s_enc) (0 behind the row's
+// encoder length), and the log-probability of the token the step chose, lprob[slot_utt[b]][pos] (0 without am_part: a
+// prompt position fed without vocabulary projection).  Rows behind *d_rows and rows finished at an earlier step are skipped.
+constexpr int XCAP_MAX_HEADS = 16;
+struct XattnCapArgs {
+    const float* q = nullptr;       // [nb][M] complete query rows of the last layer's cross attention (StepCtx::qkvr)
+    const float* kv = nullptr;      // the last layer's encoder K / V [nb][s_enc][2M], keys at column 0, head h at h * 64
+    const int* enc_lens = nullptr;  // [nb]
+    const int* d_pos = nullptr;     // position counter, already advanced by the step
+    const int* d_rows = nullptr;    // live rows (null: all)
+    const int* finished = nullptr;
+    const int* out_len = nullptr;
+    const int* slot_utt = nullptr;  // [nb]: utterance held by slot b (the live-row compaction moves rows)
+    const float4* am_part = nullptr;  // the step's arg-max records [am_tiles][nb] (null: the step did not project)
+    int am_tiles = 0;
+    const float* eos_logit = nullptr;
+    int force_eos_step = -1;
+    float* xattn = nullptr;  // [utterances][cap][s_enc]
+    float* lprob = nullptr;  // [utterances][cap]
+    int nb = 0, s_enc = 0, heads = 0, cap = 0;
+};
+void launch_xattn_capture(const XattnCapArgs& a, hipStream_t s);
+
 // ---- decode engine (k_engine.hip, engine.hip) ---------------------------------------------------------------------
 // One greedy step chain per GPU shared by every pass in flight.  A ROW STATE r (0 .. rows-1) owns everything that lives as
 // long as a hypothesis: K / V cache rows, encoder K / V, token history, captured decoder outputs, position, flags.  A SLOT s

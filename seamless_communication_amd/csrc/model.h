@@ -335,10 +335,15 @@ void run_encode_text(Model& m, const int32_t* h_tokens, int n, int s_text, const
 int text_max_len(const Model& m, const sc_gen_opts& o, int s_enc);
 int decoder_step_family(const Model& m, int rows, int caller);
 void ngram_blocked_tokens(const int32_t* seq, int S, int G, std::vector<int32_t>& out);
+// sc_generate_text_capture: where the greedy step's cross-attention capture (k_xattn.hip) goes, per utterance
+struct XattnCapture {
+    float* d_xattn = nullptr;       // [n][max_len][s_enc] on the device
+    float* h_step_lprob = nullptr;  // [n][max_len] on the host
+};
 void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens,
                        const sc_gen_opts& o, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
                        int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, const int32_t* h_forced_tokens,
-                       int forced_len);
+                       int forced_len, const XattnCapture* xcap = nullptr);
 void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const int32_t* h_text_lens,
                  const int32_t* h_text_seqs, float duration_factor, int32_t* h_unit_lens, int32_t* out_su,
                  int32_t* out_sc);

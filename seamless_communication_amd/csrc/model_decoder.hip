@@ -987,9 +987,17 @@ struct DecodeSession {
     std::vector<Buf<float>> caches;
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
+    // cross-attention capture (sc_generate_text_capture): its own step graph (the step + the capture launch) and the buffers
+    // that graph writes, allocated by the first capture call on this session; a plain call never replays this graph
+    Buf<float> xattn, xlprob;  // [n][max_len][s_enc], [n][max_len]
+    Buf<int> slot_tab;         // [n] utterance held by each row slot
+    hipGraph_t cgraph = nullptr;
+    hipGraphExec_t cexec = nullptr;
     ~DecodeSession() {
         if (exec) (void)hipGraphExecDestroy(exec);
         if (graph) (void)hipGraphDestroy(graph);
+        if (cexec) (void)hipGraphExecDestroy(cexec);
+        if (cgraph) (void)hipGraphDestroy(cgraph);
     }
 };
 
@@ -1162,7 +1170,7 @@ void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, con
 void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens,
                        const sc_gen_opts& o, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
                        int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, const int32_t* h_forced_tokens,
-                       int forced_len) {
+                       int forced_len, const XattnCapture* xcap) {
     const sc_config& cfg = m.cfg;
     const int M = cfg.model_dim;
     SC_CHECK(n > 0 && s_enc > 0, "sc_generate_text: empty batch");
@@ -1179,6 +1187,11 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
     } else {
         SC_CHECK(o.beam_size >= 1, "sc_generate_text: beam_size=%d", o.beam_size);
         SC_CHECK(o.no_repeat_ngram_size >= 0, "sc_generate_text: no_repeat_ngram_size=%d", o.no_repeat_ngram_size);
+        // the capture covers the greedy step chain only: the reference sums the attention over all beams of its beam batch,
+        // whose layout this library does not reproduce, and the step processors run in the host-driven loop
+        SC_CHECK(!xcap || (o.beam_size == 1 && o.no_repeat_ngram_size == 0),
+                 "sc_generate_text_capture: greedy generation only (beam_size=%d, no_repeat_ngram_size=%d are not supported)",
+                 o.beam_size, o.no_repeat_ngram_size);
         if (o.beam_size > 1 || o.no_repeat_ngram_size > 0) {  // step processors run in the host-driven step loop
             if (m.engine) m.engine->expect(m, -n);
             run_generate_text_beam(m, d_enc, n, s_enc, h_enc_lens, o, h_prefix, prefix_len, h_out_ids, h_out_lens, h_scores,
@@ -1196,7 +1209,9 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
         SC_CHECK(h_enc_lens[i] > 0 && h_enc_lens[i] <= s_enc, "sc_generate_text: enc_lens[%d]=%d out of range", i, h_enc_lens[i]);
 
     // ---- decode engine (sc_engine_attach): the rows join the GPU's shared step chain (engine.hip) -------------------------
-    if (!forced && m.engine) {
+    // (a capture call does not fit: it runs on the handle's own chain, whose step the capture launch follows)
+    if (!forced && m.engine && xcap) m.engine->expect(m, -n);
+    if (!forced && m.engine && !xcap) {
         if (m.engine->fits(n, s_enc, max_len, prefix_len, o) && m.engine->has_company()) {
             m.engine->generate(m, d_enc, n, s_enc, h_enc_lens, h_prefix, prefix_len, max_len, h_out_ids, h_out_lens, h_scores, d_dec_hidden);
             return;
@@ -1227,6 +1242,28 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
         S = m.dec_session.get();
     }
     StepCtx& c = S->c;
+    if (xcap) {
+        SC_CHECK(xcap->d_xattn && xcap->h_step_lprob, "sc_generate_text_capture: null capture buffer");
+        SC_CHECK(c.gen3 && c.d_rows == c.d_rows_greedy && c.am_tiles > 0,
+                 "sc_generate_text_capture: needs the row-group decoder step (greedy, 1..64 rows; %d rows here)", n);
+        SC_CHECK(cfg.num_heads <= XCAP_MAX_HEADS && M == cfg.num_heads * 64, "sc_generate_text_capture: %d heads of width %d (<= %d heads of 64)",
+                 cfg.num_heads, M / cfg.num_heads, XCAP_MAX_HEADS);
+        if (!S->xattn) {
+            S->xattn = Buf<float>(m.pp(), (size_t)n * max_len * s_enc);
+            S->xlprob = Buf<float>(m.pp(), (size_t)n * max_len);
+            S->slot_tab = Buf<int>(m.pp(), (size_t)n);
+        }
+    }
+    // the capture launch behind a step (projected: the step chose tokens)
+    auto capture_node = [&](bool projected) {
+        XattnCapArgs x;
+        x.q = c.qkvr, x.kv = c.cross_kv.back(), x.enc_lens = c.d_enc_lens, x.d_pos = c.d_pos, x.d_rows = c.d_rows;
+        x.finished = c.d_finished, x.out_len = c.d_out_len, x.slot_utt = S->slot_tab;
+        if (projected) x.am_part = c.am_part, x.am_tiles = vocab3_groups(n), x.eos_logit = c.am_eos_logit, x.force_eos_step = c.force_eos_step;
+        x.xattn = S->xattn, x.lprob = S->xlprob;
+        x.nb = n, x.s_enc = s_enc, x.heads = cfg.num_heads, x.cap = max_len;
+        launch_xattn_capture(x, m.stream);
+    };
 
     // encoder-decoder K/V once per utterance (fairseq2 caches them in the state bag at step 0)
     for (int li = 0; li < cfg.dec_layers; ++li) project_cross_kv(m, d_enc, m.dec[li].cross_kv, c.cross_kv[li], n * s_enc);
@@ -1247,6 +1284,13 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
     SC_HIP(hipMemcpyAsync(c.d_hist, hist.data(), hist.size() * 4, hipMemcpyHostToDevice, m.stream));
     SC_HIP(hipMemsetAsync(S->fl.get(), 0, (size_t)2 * n * 4, m.stream));
     if (c.dec_hidden) SC_HIP(hipMemsetAsync(c.dec_hidden, 0, (size_t)n * (max_len - 1) * M * 4, m.stream));
+    std::vector<int> slot_utt(n);
+    for (int b = 0; b < n; ++b) slot_utt[b] = b;
+    if (xcap) {
+        SC_HIP(hipMemsetAsync(S->xattn.get(), 0, (size_t)n * max_len * s_enc * 4, m.stream));
+        SC_HIP(hipMemsetAsync(S->xlprob.get(), 0, (size_t)n * max_len * 4, m.stream));
+        SC_HIP(hipMemcpyAsync(S->slot_tab.get(), slot_utt.data(), (size_t)n * 4, hipMemcpyHostToDevice, m.stream));
+    }
 
     // ---- feed the known tokens (prompt echo / teacher forcing) ---------------------
     // positions 0 .. feed_len-2 are fed without projection; the next input is read from hist.
@@ -1286,6 +1330,7 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
     };
     for (int t = 0; t + 1 < feed_len; ++t) {
         fed_step();
+        if (xcap) capture_node(false);
         SC_HIP(hipMemcpy2DAsync(c.d_tok, 4, c.d_hist + t + 1, (size_t)max_len * 4, 4, n, hipMemcpyDeviceToDevice, m.stream));
     }
     if (forced) {
@@ -1313,12 +1358,32 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
                          M % 4 == 0 && knob::live("SC_GREEDY_COMPACT", 1) != 0;
     // steps between two looks of the host at the finished flags (each is a stream synchronisation); SC_GREEDY_POLL for A/B runs
     const int poll = std::min(64, std::max(1, knob::live("SC_GREEDY_POLL", 4)));
-    std::vector<int> slot_utt(n);
-    for (int b = 0; b < n; ++b) slot_utt[b] = b;
     int live_slots = n;
     bool moved = false;
     for (int step = first; step <= max_len - 2; ++step) {
-        if (use_graph) {
+        if (xcap) {
+            if (!use_graph) {
+                decoder_step(m, c, true);
+                capture_node(true);
+            } else {
+                if (!S->cexec) {  // as the plain step graph below, with the capture launch at its end
+                    std::lock_guard<std::mutex> lock(g_capture_mutex);
+                    SC_HIP(hipStreamBeginCapture(m.stream, hipStreamCaptureModeThreadLocal));
+                    try {
+                        decoder_step(m, c, true);
+                        capture_node(true);
+                    } catch (...) {
+                        hipGraph_t dead = nullptr;
+                        (void)hipStreamEndCapture(m.stream, &dead);
+                        if (dead) (void)hipGraphDestroy(dead);
+                        throw;
+                    }
+                    SC_HIP(hipStreamEndCapture(m.stream, &S->cgraph));
+                    SC_HIP(hipGraphInstantiate(&S->cexec, S->cgraph, nullptr, nullptr, 0));
+                }
+                SC_HIP(hipGraphLaunch(S->cexec, m.stream));
+            }
+        } else if (use_graph) {
             if (!S->exec) {
                 // Thread-local capture: another handle's host thread may allocate scratch (hipMalloc) while
                 // this one records; captures and instantiations are serialised process-wide.
@@ -1380,6 +1445,9 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
                     }
                     launch_row_swap(rs, m.stream);
                     SC_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.d_rows_greedy), want, 1, m.stream));
+                    // the capture's slot -> utterance table (slot_utt is next written after the stream synchronisation of
+                    // the next look, so the copy has its source until then)
+                    if (xcap) SC_HIP(hipMemcpyAsync(S->slot_tab.get(), slot_utt.data(), (size_t)n * 4, hipMemcpyHostToDevice, m.stream));
                     live_slots = want;
                     moved = true;
                 }
@@ -1391,6 +1459,10 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
     SC_HIP(hipMemcpyAsync(hist.data(), c.d_hist, hist.size() * 4, hipMemcpyDeviceToHost, m.stream));
     SC_HIP(hipMemcpyAsync(lens.data(), c.d_out_len, (size_t)n * 4, hipMemcpyDeviceToHost, m.stream));
     SC_HIP(hipMemcpyAsync(scores.data(), c.d_score, (size_t)n * 4, hipMemcpyDeviceToHost, m.stream));
+    if (xcap) {  // indexed by utterance already
+        SC_HIP(hipMemcpyAsync(xcap->d_xattn, S->xattn.get(), (size_t)n * max_len * s_enc * 4, hipMemcpyDeviceToDevice, m.stream));
+        SC_HIP(hipMemcpyAsync(xcap->h_step_lprob, S->xlprob.get(), (size_t)n * max_len * 4, hipMemcpyDeviceToHost, m.stream));
+    }
     if (want_hidden) {
         const size_t row = (size_t)(max_len - 1) * M;
         if (!moved) {

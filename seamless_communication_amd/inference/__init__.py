@@ -1,4 +1,6 @@
 from .generator import NGramRepeatBlockProcessor, SequenceGeneratorOptions
+from .transcriber import Transcriber, Transcription, TranscriptionToken, TranscriptionTokenStats
 from .translator import BatchedSpeechOutput, Modality, Task, Translator
 
-__all__ = ["BatchedSpeechOutput", "Modality", "NGramRepeatBlockProcessor", "SequenceGeneratorOptions", "Task", "Translator"]
+__all__ = ["BatchedSpeechOutput", "Modality", "NGramRepeatBlockProcessor", "SequenceGeneratorOptions", "Task", "Transcriber", "Transcription", "TranscriptionToken",
+           "TranscriptionTokenStats", "Translator"]

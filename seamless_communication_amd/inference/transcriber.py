@@ -1,0 +1,264 @@
+"""Drop-in ``Transcriber``: speech recognition with word-level timestamps, on one MI355X.
+
+Mirrors src/seamless_communication/inference/transcriber.py of the reference: ``TranscriptionTokenStats`` /
+``TranscriptionToken`` / ``Transcription``, ``Transcriber.__init__``, ``generate_lis``, ``_extract_timestamps``,
+``_collect_word_level_stats`` and ``transcribe`` - same names, arguments and results.  The reference hooks the last
+decoder layer's encoder-decoder attention and runs a beam search of width 1; here the greedy decoder step of
+libseamless_hip records the same attention rows on the device (sc_generate_text_capture), and the timestamp and word
+bookkeeping below runs on the host in numpy.
+
+Not available (``NotImplementedError``): ``denoise=True`` (the Demucs denoiser is not part of
+this project), inputs longer than ``chunk_size_sec`` (the reference splits them with Silero VAD, which cannot be
+obtained offline) and ``beam_size > 1``.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from pathlib import Path
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+from torch import Tensor
+
+from ..runtime import HipS2STModel
+from ..tokenizer import NllbTextTokenizer
+from .. import cards as _cards
+from .translator import _ARCHS, _load_state_dict, _resolve_card
+
+# generator options the reference passes to fairseq2's BeamSearchSeq2SeqGenerator (transcriber.py run_inference); the
+# defaults are fairseq2 0.2's, which the reference tree does not hold - chosen here, stated in INTEGRATION.md section 5
+GENERATOR_DEFAULTS: Dict[str, Any] = {
+    "min_gen_len": 1,
+    "max_gen_len": 128,
+    "max_seq_len": 1024,
+    "echo_prompt": False,
+    "normalize_scores": True,
+    "unk_penalty": 0.0,
+    "len_penalty": 1.0,
+}
+
+
+@dataclass
+class TranscriptionTokenStats:
+    text: str
+    time_s: float
+    scores: List[float]
+
+
+@dataclass
+class TranscriptionToken:
+    text: str
+    time_s: float
+    prob: float
+
+
+class Transcription:
+    text: str
+    tokens: List[TranscriptionToken]
+
+    def __init__(self, tokens: List[TranscriptionToken]):
+        self.tokens = tokens
+        self.text = " ".join(t.text for t in tokens)
+
+    def __add__(self, other: "Transcription") -> "Transcription":
+        self.text += " " + other.text
+        self.tokens += other.tokens
+        return self
+
+    def __str__(self) -> str:
+        return self.text
+
+    def __repr__(self) -> str:
+        return self.text
+
+
+def median_filter_2d(a: np.ndarray, width: int) -> np.ndarray:
+    """scipy.signal.medfilt2d(a, (width, width)) in numpy: the median of the width x width window around every element,
+    zero outside the array.  The window holds an odd number of values, so the median is one of them."""
+    if width < 1 or width % 2 == 0:
+        raise ValueError("Each element of kernel_size should be odd.")
+    a = np.asarray(a, dtype=np.float64)
+    r = width // 2
+    windows = np.lib.stride_tricks.sliding_window_view(np.pad(a, r), (width, width))
+    return np.median(windows.reshape(a.shape[0], a.shape[1], width * width), axis=-1)
+
+
+class Transcriber:
+    def __init__(
+        self,
+        model_name_or_card: Union[str, Dict[str, Any]],
+        device: torch.device = torch.device("cuda"),
+        dtype: torch.dtype = torch.float32,
+    ):
+        card = _resolve_card(model_name_or_card)
+        arch = card.get("model_arch", "base_v2")
+        if arch not in _ARCHS:
+            raise ValueError(f"unsupported model_arch '{arch}' (supported: {sorted(_ARCHS)})")
+        dev = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
+        if dev.type != "cuda":
+            raise ValueError("the MI355X-native Transcriber runs on a HIP device only (device='cuda[:N]')")
+        self.device = dev
+        self.dtype = dtype
+        self.cfg = _ARCHS[arch]()
+        # the speech encoder and the text decoder only: no text encoder, no T2U model, no vocoder
+        unity_sd = _load_state_dict(card, self.cfg, "unity", with_t2u=False)
+        self.tokenizer = NllbTextTokenizer(self.cfg.text_vocab_size, card.get("langs", _cards.TEXT_LANGS),
+                                           card.get("default_lang", "eng"), card.get("tokenizer_path"))
+        self.model = HipS2STModel(self.cfg, unity_sd, None, device=dev.index or 0)
+        self.use_graph = True  # replay the decoder step from a captured hipGraph (not part of the reference API)
+
+    @staticmethod
+    def generate_lis(arr: List[Tuple[int, int]]) -> Tuple[int, List[Tuple[int, int]]]:
+        """Longest strictly increasing subsequence -> (its length, the subsequence).  O(n^2): for each element the longest
+        run ending there and its predecessor (the first predecessor that gives the longest run); the run ends at the first
+        element of maximal length."""
+        n = len(arr)
+        run = [1] * n
+        pred = list(range(n))
+        for i in range(1, n):
+            for j in range(i):
+                if arr[i] > arr[j] and run[j] + 1 > run[i]:
+                    run[i] = run[j] + 1
+                    pred[i] = j
+        best, end = 0, 0
+        for i in range(n):
+            if run[i] > best:
+                best, end = run[i], i
+        chain = [arr[end]]
+        while pred[end] != end:
+            end = pred[end]
+            chain.append(arr[end])
+        chain.reverse()
+        return best, chain
+
+    @classmethod
+    def _extract_timestamps(cls, attn_weights, audio_len, filter_width) -> List[float]:
+        """One attention row per emitted token (after the first row, which the prompt produced) over the encoder positions
+        without the first and the last -> the start time of every token."""
+        rows = np.array([list(r)[1:-1] for r in attn_weights][1:], dtype=np.float64)
+        n_tokens, n_steps = rows.shape
+        rows = rows / rows.sum(axis=0, keepdims=True)  # every encoder position distributed over the tokens
+        rows = median_filter_2d(rows, filter_width)
+        best_token = np.argmax(rows, axis=0)  # per encoder position: the token it belongs to (first on ties)
+        # tokens in order along increasing positions; (token, -position) makes the earliest position of a token win
+        _, chain = cls.generate_lis([(tok, -pos) for pos, tok in enumerate(best_token)])
+        first_pos = {tok: -neg_pos for tok, neg_pos in chain}
+        starts: List[int] = []
+        last = 0
+        for t in range(n_tokens):
+            last = first_pos.get(t, last)  # tokens outside the chain start where the previous one did
+            starts.append(last)
+        step_s = audio_len / n_steps
+        return [step_s * s for s in starts]
+
+    @classmethod
+    def _collect_word_level_stats(cls, pieces: List[str], token_timestamps: List[float],
+                                  step_scores: List[float]) -> List[TranscriptionToken]:
+        """Pieces -> words: a piece that starts with U+2581 opens a word when it starts strictly later than the current
+        word; a word's probability is the mean of exp(score) of its pieces."""
+        assert len(pieces) == len(token_timestamps) and len(token_timestamps) == len(step_scores)
+        words: List[TranscriptionTokenStats] = []
+        for piece, t, score in zip(pieces, token_timestamps, step_scores):
+            opens = not words or (piece.startswith("▁") and t > words[-1].time_s)
+            if opens:
+                words.append(TranscriptionTokenStats(piece.replace("▁", " ").strip(), t, [np.exp(score)]))
+            else:
+                words[-1].text += piece.replace("▁", " ")
+                words[-1].scores.append(np.exp(score))
+        return [TranscriptionToken(w.text, w.time_s, np.mean(w.scores).item()) for w in words]
+
+    # ---- the device part: fbank -> speech encoder -> greedy decoding with the attention capture -------------------------
+    def _gen_limits(self, opts: Dict[str, Any], prefix_len: int, frames: int) -> Tuple[Tuple[float, int], int, float]:
+        o = dict(GENERATOR_DEFAULTS)
+        unknown = set(opts) - set(o)
+        if unknown:
+            raise TypeError(f"unexpected sequence generator option(s) {sorted(unknown)}")
+        o.update(opts)
+        if o["echo_prompt"]:
+            raise NotImplementedError("echo_prompt=True: the reference's timestamp rows assume the prompt is not echoed")
+        if int(o["min_gen_len"]) != 1:
+            raise NotImplementedError("min_gen_len != 1 is not supported by the Transcriber")
+        gen = o["max_gen_len"]
+        if isinstance(gen, (tuple, list)):  # (a, b): int(a * source_len + b) generated tokens
+            soft = (float(gen[0]), int(gen[1]) + prefix_len)
+        else:
+            soft = (0.0, 0)
+            o["max_seq_len"] = min(int(o["max_seq_len"]), prefix_len + int(gen))
+        return soft, int(o["max_seq_len"]), float(o["unk_penalty"])
+
+    def _decode(self, wav: Tensor, sample_rate: int, src_lang: str, opts: Dict[str, Any]):
+        """-> (token ids without prompt and EOS, step scores of those tokens, attention rows of the reference's hook
+        without its last row)."""
+        model = self.model
+        w = wav[:, 0].to(torch.float32).contiguous().unsqueeze(0).to(self.device)
+        # standardize=True, waveform_scale 2**15 inside the HIP front end; no padding, no padding mask
+        fb, frames = model.fbank(w, [w.shape[1]], standardize=True, pad_to_multiple=1, sample_rate=int(sample_rate))
+        enc, enc_lens = model.encode_speech(fb, frames)
+        prefix = self.tokenizer.target_prefix(src_lang)
+        soft, hard, unk = self._gen_limits(opts, len(prefix), int(frames[0]))
+        ids, lens, _, xattn, step_lprob, _ = model.generate_text_capture(
+            enc, enc_lens.tolist(), prefix, soft_max_seq_len=soft, hard_max_seq_len=hard, unk_penalty=unk,
+            use_graph=self.use_graph, source_len=int(frames[0]))
+        return restate_hook_rows(ids[0], int(lens[0]), len(prefix), xattn[0, :, : int(enc_lens[0])].cpu().numpy(), step_lprob[0])
+
+    @torch.inference_mode()
+    def transcribe(
+        self,
+        audio: Union[str, Tensor],
+        src_lang: str,
+        filter_width: int = 3,
+        sample_rate: int = 16000,
+        denoise: bool = False,
+        denoise_config: Optional[Any] = None,
+        chunk_size_sec: int = 20,
+        pause_length_sec: float = 1,
+        **sequence_generator_options: Dict,
+    ) -> Optional[Transcription]:
+        """audio: a file path or a (T, C) waveform tensor at ``sample_rate`` -> the words with their start times and
+        probabilities.  ``sequence_generator_options``: BeamSearchSeq2SeqGenerator's (beam_size 1 only)."""
+        if denoise:
+            raise NotImplementedError("denoise=True: the Demucs denoiser is not part of this project")
+        if isinstance(audio, (str, Path)):
+            from ..evaluate import load_audio  # evaluate imports this package: not at module level
+
+            data, rate = load_audio(Path(audio), all_channels=True)
+            wav = torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32))
+        else:
+            wav, rate = audio, sample_rate
+            if wav.dim() != 2:
+                raise ValueError("the audio tensor must be (T, C)")
+        if int(rate) != sample_rate:
+            raise AssertionError(f"decoded sample rate {rate} != sample_rate {sample_rate}")
+        length_seconds = wav.size(0) / sample_rate
+        if length_seconds > chunk_size_sec:
+            raise NotImplementedError(f"input of {length_seconds:.2f} s > chunk_size_sec={chunk_size_sec}: the reference segments "
+                                      "long input with Silero VAD, which cannot be obtained offline")
+        opts = dict(sequence_generator_options)
+        beam_size = opts.pop("beam_size", None) or 1
+        if beam_size > 1:
+            raise NotImplementedError("beam_size > 1: the attention capture runs on the greedy decoder step only")
+        token_ids, step_scores, rows = self._decode(wav, sample_rate, src_lang, opts)
+        if not token_ids:  # EOS first: no token, no timestamp
+            return Transcription([])
+        times = self._extract_timestamps(rows, length_seconds, filter_width)
+        pieces = [self.tokenizer.index_to_token(t) for t in token_ids]
+        return Transcription(self._collect_word_level_stats(pieces=pieces, token_timestamps=times, step_scores=step_scores))
+
+
+def restate_hook_rows(ids: np.ndarray, length: int, prefix_len: int, xattn: np.ndarray,
+                      step_lprob: np.ndarray) -> Tuple[List[int], List[float], List[List[float]]]:
+    """What the reference's run_inference takes from its generator and hook, from one utterance's capture: ids [max_len]
+    (prompt, tokens, EOS; ``length`` of them), xattn [max_len][s_enc] and step_lprob [max_len] per fed position.
+
+    The hook records one row per decoder call: the prompt without its last token is fed first (one call per prompt
+    position but the last), then every step feeds one position, up to the step that chose EOS.  The reference keeps
+    the tokens without EOS, their step scores and the rows without the last: rows of positions 0 .. length-3, scores of
+    positions prefix_len-1 .. length-3 (position p chooses token p + 1)."""
+    token_ids = [int(t) for t in ids[prefix_len : length - 1]]
+    fed = length - 1  # positions 0 .. length-2 were fed
+    scores = [float(s) for s in step_lprob[prefix_len - 1 : fed - 1]]
+    # with the NLLB prompt [EOS, lang] the fast-forward is one call of one position: one row per fed position throughout
+    # (a longer prompt would take the hook's other branch, which keeps the heads apart; the Transcriber never feeds one)
+    rows = [[float(v) for v in xattn[p]] for p in range(fed - 1)]
+    return token_ids, scores, rows

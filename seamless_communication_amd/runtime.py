@@ -284,6 +284,33 @@ class HipS2STModel:
                                         _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden)), "sc_generate_text")
         return ids, lens, scores, hidden
 
+    def generate_text_capture(self, enc: torch.Tensor, enc_lens: Sequence[int], prefix: Sequence[int],
+                              soft_max_seq_len=(1, 200), hard_max_seq_len: int = 1024, min_seq_len: int = 1,
+                              unk_penalty: float = 0.0, use_graph: bool = True, want_hidden: bool = False,
+                              source_len: int = 0):
+        """Greedy generation with the decoder's cross-attention capture (sc_generate_text_capture; the Transcriber's input).
+        -> (ids, lens, scores, xattn (n, max_len, s_enc) float32 on the device, step_lprob (n, max_len) float32, hidden or
+        None).  xattn[b, p]: the last decoder layer's encoder-decoder attention probabilities of the query fed at position
+        p, summed over the heads; step_lprob[b, p]: log-probability of the token chosen at p (0 at prompt positions).
+        Greedy only: the arguments are generate_text's without the beam-search and step-processor options."""
+        assert enc.is_cuda and enc.is_contiguous()
+        n, s_enc, M = enc.shape
+        o = self._gen_opts(1, soft_max_seq_len, hard_max_seq_len, min_seq_len, unk_penalty, use_graph, 1.0, True, 0, source_len)
+        max_len = self.lib.sc_text_max_len(self.handle, C.byref(o), s_enc)
+        ids = np.zeros((n, max_len), dtype=np.int32)
+        lens = np.zeros(n, dtype=np.int32)
+        scores = np.zeros(n, dtype=np.float32)
+        step_lprob = np.zeros((n, max_len), dtype=np.float32)
+        xattn = torch.empty(n, max_len, s_enc, dtype=torch.float32, device=self.device)
+        hidden = torch.empty(n, max_len - 1, M, dtype=torch.float32, device=self.device) if want_hidden else None
+        pre = _i32(prefix)
+        el = _i32(enc_lens)
+        self._after_torch()
+        check(self.lib.sc_generate_text_capture(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(pre), len(pre),
+                                                _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden), _ptr(xattn), _ptr(step_lprob)),
+              "sc_generate_text_capture")
+        return ids, lens, scores, xattn, step_lprob, hidden
+
     def decode_text(self, enc: torch.Tensor, enc_lens: Sequence[int], tokens: np.ndarray) -> torch.Tensor:
         """Teacher-forced decoder pass: tokens (n, s_text) -> hidden (n, s_text, M)."""
         n, s_enc, M = enc.shape
