@@ -157,6 +157,31 @@ int sc_op_layernorm2(const float* d_x, const float* d_ga, const float* d_ba, con
                      void* d_yh_f16, void* d_yl_f16, int32_t rows, int32_t C, int32_t fused);
 int sc_op_argmax(const float* d_logits, int32_t rows, int32_t V, int32_t* d_idx, float* d_lprob);
 
+/* Beam-search step kernels (k_beam.hip) through the launchers the text decoder's beam search calls (tests/test_beam_kernels_gpu.py).
+ * sc_op_beam_candidates: best K candidates (d_cand_val / d_cand_idx [n_utt][K], flattened beam * V + token) of each utterance's
+ * `beams` logit rows [n_utt*beams][ld] under the step rules; chunked = 1 runs the four-kernel search and fails unless the shape
+ * is one it takes, 0 the single-workgroup kernel.  d_seqs [n_utt*beams][seq_ld] (nullable): S tokens per row for the n-gram
+ * blocker of size G (logits of blocked tokens are overwritten with -inf).  d_rows (chunked only) / d_slots: live rows / slots
+ * (device counts, nullable).
+ * sc_op_beam_select: one candidate walk (kernels.h: BeamSelectArgs, n slots); sc_op_beam_compact: BeamCompactArgs;
+ * sc_op_gather_cache: dst[l][r][t] = src[l][src_row[r]][t] for t < len; sc_op_row_token_lprob: log-softmax value of `token` in
+ * rows 0, row_stride, 2 * row_stride, ... */
+int sc_op_beam_candidates(float* d_logits, int64_t ld, int32_t n_utt, int32_t beams, int32_t V, const float* d_cum, int32_t first_step,
+                          int32_t no_eos, int32_t force_eos, int32_t pad_idx, int32_t eos_idx, int32_t unk_idx, float unk_penalty, int32_t K,
+                          float* d_cand_val, int32_t* d_cand_idx, const int32_t* d_seqs, int32_t seq_ld, int32_t S, int32_t G,
+                          const int32_t* d_rows, const int32_t* d_slots, int32_t chunked);
+int sc_op_beam_select(const float* d_cand_val, const int32_t* d_cand_idx, const int32_t* d_seqs_cur, int32_t* d_seqs_new, float* d_fin_score,
+                      int32_t* d_fin_len, int32_t* d_fin_seq, int32_t* d_fin_count, int32_t* d_done, int32_t* d_remaining, int32_t* d_tok,
+                      int32_t* d_src_row, float* d_cum, int32_t* d_anc, int32_t anc_ld, const int32_t* d_slot_utt, const int32_t* d_slots,
+                      int32_t n, int32_t beams, int32_t K, int32_t V, int32_t max_len, int32_t step, int32_t eos_idx, int32_t pad_idx,
+                      int32_t normalize, float len_penalty);
+int sc_op_beam_compact(const int32_t* d_done, int32_t* d_slot_utt, int32_t* d_slots, int32_t* d_rows, int32_t* d_seqs, float* d_cum,
+                       int32_t* d_tok, int32_t* d_enc_lens, int32_t* d_anc, int32_t n, int32_t beams, int32_t max_len, int32_t anc_ld,
+                       int32_t seq_len, int32_t anc_len);
+int sc_op_gather_cache(const float* d_src, float* d_dst, const int32_t* d_src_row, int32_t rows, int32_t len, int32_t cap, int32_t M,
+                       int32_t layers, int64_t layer_stride);
+int sc_op_row_token_lprob(const float* d_logits, int64_t ld, int32_t rows, int32_t V, int32_t row_stride, int32_t token, float* d_out);
+
 #ifdef __cplusplus
 }
 #endif

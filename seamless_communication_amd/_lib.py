@@ -177,6 +177,13 @@ SIGNATURES = {
                                      _P, _i, _i, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int64]),
     "sc_op_glu_dwconv": (C.c_int, [_P, _P, _P, _i, _i, _i, _i, _P]),
     "sc_op_argmax": (C.c_int, [_P, _i, _i, _P, _P]),
+    "sc_op_beam_candidates": (C.c_int, [_P, C.c_int64, _i, _i, _i, _P, _i, _i, _i, _i, _i, _i, C.c_float, _i, _P, _P, _P, _i, _i, _i,
+                                        _P, _P, _i]),
+    "sc_op_beam_select": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _i, _i, _i, _i, _i, _i, _i, _i,
+                                    _i, C.c_float]),
+    "sc_op_beam_compact": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _i]),
+    "sc_op_gather_cache": (C.c_int, [_P, _P, _P, _i, _i, _i, _i, _i, C.c_int64]),
+    "sc_op_row_token_lprob": (C.c_int, [_P, C.c_int64, _i, _i, _i, _i, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

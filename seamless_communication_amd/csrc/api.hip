@@ -64,6 +64,11 @@ struct OpScratch {  // hipMalloc'ed scratch of one op call
         for (void* p : ptrs) (void)hipFree(p);
     }
 };
+std::vector<int32_t> op_read_ints(const int32_t* d, size_t n) {  // n ints of device memory, synchronously
+    std::vector<int32_t> h(n);
+    if (n) SC_HIP(hipMemcpy(h.data(), d, n * 4, hipMemcpyDeviceToHost));
+    return h;
+}
 }  // namespace
 
 extern "C" {
@@ -1400,6 +1405,106 @@ int sc_op_layernorm2(const float* d_x, const float* d_ga, const float* d_ba, con
 int sc_op_argmax(const float* d_logits, int32_t rows, int32_t V, int32_t* d_idx, float* d_lprob) {
     SC_API_BEGIN
     launch_argmax_rows(d_logits, V, rows, V, nullptr, -1, -1, -1, -1, -1, 0.f, d_idx, d_lprob, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+// beam-search step kernels (k_beam.hip) through the launchers run_generate_beam calls.  Index arrays that the kernels follow
+// into other buffers (slot -> utterance, candidate -> beam, source rows) are checked on the host first (op_read_ints): a test
+// that hands in a bad one gets an error, not an out-of-bounds access.
+
+int sc_op_beam_candidates(float* d_logits, int64_t ld, int32_t n_utt, int32_t beams, int32_t V, const float* d_cum, int32_t first_step,
+                          int32_t no_eos, int32_t force_eos, int32_t pad_idx, int32_t eos_idx, int32_t unk_idx, float unk_penalty, int32_t K,
+                          float* d_cand_val, int32_t* d_cand_idx, const int32_t* d_seqs, int32_t seq_ld, int32_t S, int32_t G,
+                          const int32_t* d_rows, const int32_t* d_slots, int32_t chunked) {
+    SC_API_BEGIN
+    SC_CHECK(d_logits && d_cum && d_cand_val && d_cand_idx && n_utt >= 1 && V >= 1 && ld >= V, "sc_op_beam_candidates: bad arguments");
+    SC_CHECK(!d_seqs || (G >= 0 && S >= 0 && seq_ld >= S), "sc_op_beam_candidates: bad n-gram arguments (S=%d G=%d seq_ld=%d)", S, G, seq_ld);
+    if (d_slots) SC_CHECK(op_read_ints(d_slots, 1)[0] <= n_utt, "sc_op_beam_candidates: *d_slots > n_utt");
+    if (chunked) {
+        SC_CHECK(beam_chunked(V, beams, K), "sc_op_beam_candidates: the chunked search does not take V=%d beams=%d K=%d", V, beams, K);
+        if (d_rows) SC_CHECK(op_read_ints(d_rows, 1)[0] <= n_utt * beams, "sc_op_beam_candidates: *d_rows > n_utt * beams");
+        OpScratch scratch;
+        const int rows = n_utt * beams;
+        float* ws_f = scratch.get<float>(beam_ws_floats(rows, K));
+        int* ws_i = scratch.get<int>(beam_ws_ints(rows, K));
+        SC_HIP(hipMemsetAsync(ws_f, 0xff, beam_ws_floats(rows, K) * 4, g_op_stream));  // NaN / -1: unwritten entries show
+        SC_HIP(hipMemsetAsync(ws_i, 0xff, beam_ws_ints(rows, K) * 4, g_op_stream));
+        launch_beam_candidates_chunked(d_logits, ld, n_utt, beams, V, d_cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx,
+                                       unk_penalty, K, d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, ws_f, ws_i, g_op_stream, d_rows, d_slots);
+        SC_HIP(hipStreamSynchronize(g_op_stream));
+    } else {
+        SC_CHECK(!d_rows, "sc_op_beam_candidates: d_rows is an argument of the chunked search only (the single-workgroup one takes d_slots)");
+        launch_beam_candidates(d_logits, ld, n_utt, beams, V, d_cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K,
+                               d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, g_op_stream, d_slots);
+        SC_HIP(hipStreamSynchronize(g_op_stream));
+    }
+    SC_API_END
+}
+
+int sc_op_beam_select(const float* d_cand_val, const int32_t* d_cand_idx, const int32_t* d_seqs_cur, int32_t* d_seqs_new, float* d_fin_score,
+                      int32_t* d_fin_len, int32_t* d_fin_seq, int32_t* d_fin_count, int32_t* d_done, int32_t* d_remaining, int32_t* d_tok,
+                      int32_t* d_src_row, float* d_cum, int32_t* d_anc, int32_t anc_ld, const int32_t* d_slot_utt, const int32_t* d_slots,
+                      int32_t n, int32_t beams, int32_t K, int32_t V, int32_t max_len, int32_t step, int32_t eos_idx, int32_t pad_idx,
+                      int32_t normalize, float len_penalty) {
+    SC_API_BEGIN
+    SC_CHECK(d_cand_val && d_cand_idx && d_seqs_cur && d_seqs_new && d_fin_score && d_fin_len && d_fin_seq && d_fin_count && d_done &&
+                 d_remaining && d_tok && d_src_row && d_cum && (!d_anc || anc_ld >= 1),
+             "sc_op_beam_select: null argument");
+    SC_CHECK(n >= 1 && beams >= 1 && K >= 1 && V >= 1 && step >= 0 && step + 1 < max_len, "sc_op_beam_select: bad shape (n=%d beams=%d K=%d "
+             "V=%d step=%d max_len=%d)", n, beams, K, V, step, max_len);
+    for (int32_t c : op_read_ints(d_cand_idx, (size_t)n * K))
+        SC_CHECK(c >= 0 && (int64_t)c < (int64_t)beams * V, "sc_op_beam_select: candidate index %d outside beams * V", c);
+    if (d_slot_utt)
+        for (int32_t u : op_read_ints(d_slot_utt, n)) SC_CHECK(u >= 0 && u < n, "sc_op_beam_select: slot_utt entry %d outside 0..%d", u, n - 1);
+    const std::vector<int32_t> done = op_read_ints(d_done, n), count = op_read_ints(d_fin_count, n);
+    for (int u = 0; u < n; ++u)  // a searching utterance has a free hypothesis slot
+        SC_CHECK(done[u] || (count[u] >= 0 && count[u] < beams), "sc_op_beam_select: fin_count[%d] = %d with done = 0", u, count[u]);
+    BeamSelectArgs a;
+    a.cand_val = d_cand_val, a.cand_idx = d_cand_idx, a.seqs_cur = d_seqs_cur, a.seqs_new = d_seqs_new;
+    a.fin_score = d_fin_score, a.fin_len = d_fin_len, a.fin_seq = d_fin_seq, a.fin_count = d_fin_count, a.done = d_done;
+    a.remaining = d_remaining, a.tok = d_tok, a.src_row = d_src_row, a.cum = d_cum, a.anc = d_anc, a.anc_ld = anc_ld;
+    a.slot_utt = d_slot_utt, a.d_slots = d_slots;
+    a.beams = beams, a.K = K, a.V = V, a.max_len = max_len, a.step = step;
+    a.eos_idx = eos_idx, a.pad_idx = pad_idx, a.normalize = normalize, a.len_penalty = len_penalty;
+    launch_beam_select(a, n, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_beam_compact(const int32_t* d_done, int32_t* d_slot_utt, int32_t* d_slots, int32_t* d_rows, int32_t* d_seqs, float* d_cum,
+                       int32_t* d_tok, int32_t* d_enc_lens, int32_t* d_anc, int32_t n, int32_t beams, int32_t max_len, int32_t anc_ld,
+                       int32_t seq_len, int32_t anc_len) {
+    SC_API_BEGIN
+    SC_CHECK(d_slot_utt && d_slots && n >= 1 && n <= 1024, "sc_op_beam_compact: bad arguments (n=%d)", n);
+    SC_CHECK(seq_len >= 0 && seq_len <= max_len && anc_len >= 0 && (!d_anc || anc_len <= anc_ld), "sc_op_beam_compact: bad lengths");
+    const int32_t slots = op_read_ints(d_slots, 1)[0];
+    SC_CHECK(slots >= 0 && slots <= n, "sc_op_beam_compact: *d_slots = %d outside 0..%d", slots, n);
+    for (int32_t u : op_read_ints(d_slot_utt, slots)) SC_CHECK(u >= 0 && u < n, "sc_op_beam_compact: slot_utt entry %d outside 0..%d", u, n - 1);
+    BeamCompactArgs a;
+    a.done = d_done, a.slot_utt = d_slot_utt, a.d_slots = d_slots, a.d_rows = d_rows;
+    a.seqs = d_seqs, a.cum = d_cum, a.tok = d_tok, a.enc_lens = d_enc_lens, a.anc = d_anc;
+    a.n = n, a.beams = beams, a.max_len = max_len, a.anc_ld = anc_ld, a.seq_len = seq_len, a.anc_len = anc_len;
+    launch_beam_compact(a, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_gather_cache(const float* d_src, float* d_dst, const int32_t* d_src_row, int32_t rows, int32_t len, int32_t cap, int32_t M,
+                       int32_t layers, int64_t layer_stride) {
+    SC_API_BEGIN
+    SC_CHECK(d_src && d_dst && d_src_row && rows >= 1 && layers >= 1 && len <= cap && layer_stride >= (int64_t)rows * cap * M,
+             "sc_op_gather_cache: bad arguments");
+    for (int32_t r : op_read_ints(d_src_row, rows)) SC_CHECK(r >= 0 && r < rows, "sc_op_gather_cache: source row %d outside 0..%d", r, rows - 1);
+    launch_gather_cache(d_src, d_dst, d_src_row, rows, len, cap, M, layers, layer_stride, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_row_token_lprob(const float* d_logits, int64_t ld, int32_t rows, int32_t V, int32_t row_stride, int32_t token, float* d_out) {
+    SC_API_BEGIN
+    SC_CHECK(d_logits && d_out && rows >= 1 && V >= 1 && ld >= V && row_stride >= 1, "sc_op_row_token_lprob: bad arguments");
+    launch_row_token_lprob(d_logits, ld, rows, V, row_stride, token, d_out, g_op_stream);
     SC_HIP(hipStreamSynchronize(g_op_stream));
     SC_API_END
 }

@@ -43,6 +43,18 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* red) {
 
 __device__ __forceinline__ bool better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
 
+// Order-preserving map of a non-NaN fp32 value to int32 (-0 and +0 map to the same key; -inf to the smallest key) and back.
+// beam_candidates_kernel orders its per-thread lists by these keys: with fp32 comparisons in that insertion network, the
+// compiled kernel dropped every -inf candidate of a thread whose list had not yet taken a finite value (a forced-EOS step:
+// the list filled with another thread's -inf entries out of index order, or with the 0x7fffffff sentinel), although the
+// source and its IR order them correctly.  Integer keys give the same total order as better() without float compares.
+__device__ __forceinline__ int order_key(float v) {
+    const int k = __float_as_int(v + 0.f);  // -0 + 0 = +0
+    return k >= 0 ? k : k ^ 0x7fffffff;
+}
+__device__ __forceinline__ float key_value(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
+__device__ __forceinline__ bool better_key(int v, int i, int w, int j) { return v > w || (v == w && i < j); }
+
 __global__ __launch_bounds__(256) void beam_candidates_kernel(float* logits, int64_t ld, int beams, int V,
                                                               const float* __restrict__ cum, int first_step, int no_eos,
                                                               int force_eos, int pad_idx, int eos_idx, int unk_idx,
@@ -51,7 +63,7 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(float* logits, int
                                                               int seq_ld, int S, int G, const int* __restrict__ d_slots) {
     __shared__ float red[4];
     __shared__ float lse[BEAM_MAX_K];
-    __shared__ float s_val[256];
+    __shared__ int s_key[256];
     __shared__ int s_idx[256];
     __shared__ int s_winner;
     const int n = blockIdx.x, tid = threadIdx.x;
@@ -84,15 +96,16 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(float* logits, int
         }
         __syncthreads();
     }
-    // per-thread best-K list, sorted best first
-    float tv[BEAM_MAX_K];
+    // per-thread best-K list of (order_key(value), flattened index), sorted best first
+    const int empty = order_key(-INFINITY);
+    int tv[BEAM_MAX_K];
     int ti[BEAM_MAX_K];
 #pragma unroll
     for (int q = 0; q < BEAM_MAX_K; ++q) {
-        tv[q] = -INFINITY;
+        tv[q] = empty;
         ti[q] = 0x7fffffff;
     }
-    float wv = -INFINITY;  // the list's current K-th entry (kept in scalars: no dynamic register indexing)
+    int wv = empty;  // the list's current K-th entry (kept in scalars: no dynamic register indexing)
     int wi = 0x7fffffff;
     for (int b = 0; b < nb; ++b) {
         const float* row = logits + ((int64_t)n * beams + b) * ld;
@@ -104,16 +117,16 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(float* logits, int
             if (force_eos && t != eos_idx) lp = -INFINITY;
             if (t == pad_idx) lp = -INFINITY;
             if (t == unk_idx) lp -= unk_penalty;
-            const float v = lp + base;
+            const int v = order_key(lp + base);
             const int idx = b * V + t;
-            if (better(v, idx, wv, wi)) {
+            if (better_key(v, idx, wv, wi)) {
                 // insertion into the sorted list (K <= 16, fully unrolled compare-and-shift)
-                float cv = v;
+                int cv = v;
                 int ci = idx;
 #pragma unroll
                 for (int q = 0; q < BEAM_MAX_K; ++q) {
-                    if (q < K && better(cv, ci, tv[q], ti[q])) {
-                        const float ov = tv[q];
+                    if (q < K && better_key(cv, ci, tv[q], ti[q])) {
+                        const int ov = tv[q];
                         const int oi = ti[q];
                         tv[q] = cv;
                         ti[q] = ci;
@@ -131,7 +144,7 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(float* logits, int
     // K rounds of block-wide arg-best over the list heads
     int head = 0;
     for (int r = 0; r < K; ++r) {
-        float hv = -INFINITY;
+        int hv = empty;
         int hi = 0x7fffffff;
 #pragma unroll
         for (int q = 0; q < BEAM_MAX_K; ++q)
@@ -139,18 +152,18 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(float* logits, int
                 hv = tv[q];
                 hi = ti[q];
             }
-        s_val[tid] = hv;
+        s_key[tid] = hv;
         s_idx[tid] = hi;
         __syncthreads();
         for (int o = 128; o > 0; o >>= 1) {
-            if (tid < o && better(s_val[tid + o], s_idx[tid + o], s_val[tid], s_idx[tid])) {
-                s_val[tid] = s_val[tid + o];
+            if (tid < o && better_key(s_key[tid + o], s_idx[tid + o], s_key[tid], s_idx[tid])) {
+                s_key[tid] = s_key[tid + o];
                 s_idx[tid] = s_idx[tid + o];
             }
             __syncthreads();
         }
         if (tid == 0) {
-            cand_val[(int64_t)n * K + r] = s_val[0];
+            cand_val[(int64_t)n * K + r] = key_value(s_key[0]);
             cand_idx[(int64_t)n * K + r] = s_idx[0];
             s_winner = s_idx[0];
         }

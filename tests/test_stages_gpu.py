@@ -296,6 +296,53 @@ def test_beam_search_ids_match_oracle(env, report_dir, beam, hard_max, min_len):
         assert err < 1e-5, err
 
 
+@pytest.mark.parametrize("beam,opts", [(5, dict(unk_penalty=0.75)), (5, dict(unk_penalty=-5.0)), (5, dict(len_penalty=0.6)),
+                                        (5, dict(len_penalty=1.3)), (5, dict(normalize_scores=False)), (8, {})])
+def test_beam_search_options_match_oracle(env, report_dir, beam, opts):
+    """The search options the other GPU tests leave at their defaults (the device kernels hold their own copy of each rule:
+    UNK penalty in the candidate search, length penalty and normalisation in the candidate walk) and the largest beam: ids
+    exact, best score within 2e-4, against oracle.beam_search_generate on the SAME encoder output."""
+    from oracle import unity as ou
+
+    cfg, tt, ct, orc, hip = env
+    fb, lens = orc.collate_fbank(common.waves((2.0, 1.37, 0.9)))
+    enc, enc_lens = hip.encode_speech(fb.cuda(), lens.tolist())
+    prefix = tt.target_prefix("fra")
+    want, every = ou.beam_search_generate(orc.P, cfg, enc.cpu(), torch.from_numpy(enc_lens.astype(np.int64)), prefix, beam,
+                                          hard_max_seq_len=12, pos_table=orc.pos_table, return_all=True, **opts)
+    ids, out_lens, scores, _ = hip.generate_text(enc, enc_lens.tolist(), prefix, beam_size=beam, hard_max_seq_len=12, want_hidden=False,
+                                                 **opts)
+    got = [ids[b, : out_lens[b]].tolist() for b in range(len(want))]
+    _log(report_dir, "beam_opts", beam=beam, opts=opts, got=got, scores=scores.tolist(), ref_scores=[round(e[0][0], 5) for e in every])
+    assert got == want
+    for b in range(len(want)):
+        assert abs(float(scores[b]) - every[b][0][0]) < 2e-4
+    if opts.get("unk_penalty", 0) < 0:  # the rule is really exercised: UNK made it into a finished hypothesis
+        assert any(cfg.unk_idx in seq[len(prefix):] for e in every for _, seq in e)
+
+
+def test_beam_size_above_eight_fails_cleanly(env):
+    """beam_size 9: the library refuses it (SC_CHECK, an error status, no crash; the handle stays usable) and so does
+    Translator.predict (its own range check)."""
+    from seamless_communication_amd._lib import SeamlessHipError
+    from seamless_communication_amd.inference import SequenceGeneratorOptions, Translator
+    from seamless_communication_amd.inference.translator import DEFAULT_CARDS
+
+    cfg, tt, ct, orc, hip = env
+    fb, lens = orc.collate_fbank(common.waves((1.2,)))
+    enc, enc_lens = hip.encode_speech(fb.cuda(), lens.tolist())
+    prefix = tt.target_prefix("fra")
+    with pytest.raises(SeamlessHipError, match="beam_size 9 > 8"):
+        hip.generate_text(enc, enc_lens.tolist(), prefix, beam_size=9, hard_max_seq_len=8, want_hidden=False)
+    ids, out_lens, _, _ = hip.generate_text(enc, enc_lens.tolist(), prefix, beam_size=8, hard_max_seq_len=8, want_hidden=False)
+    assert 1 <= int(out_lens[0]) <= 8
+    card = dict(DEFAULT_CARDS["seamlessM4T_v2_large"], model_arch="tiny_v2")
+    tr = Translator(card, dict(DEFAULT_CARDS["vocoder_v2"]), device=torch.device("cuda", 0))
+    src = {"seqs": fb.cuda(), "seq_lens": lens, "is_ragged": False}
+    with pytest.raises(ValueError, match="beam_size"):
+        tr.predict(src, "S2TT", "fra", text_generation_opts=SequenceGeneratorOptions(beam_size=9, hard_max_seq_len=8))
+
+
 @pytest.mark.parametrize("n_utt,beam", [(16, 5), (27, 4)])
 def test_beam_search_wide_step_matches_oracle(env, report_dir, n_utt, beam):
     """More than 64 live rows (the API default beam 5 at the benchmark batch is 64 x 5 = 320): the decoder step cuts every
