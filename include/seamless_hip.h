@@ -208,6 +208,22 @@ int sc_generate_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, 
                      const sc_gen_opts* opts, const int32_t* h_prefix, int32_t prefix_len, int32_t* h_out_ids,
                      int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden);
 
+/* sc_generate_text with a banned-sequence step processor (additive, ABI 10; fairseq2 0.2 BannedSequenceProcessor, the step
+ * processor of the reference's MinTox re-decode, toxicity/mintox.py): h_banned_tokens / h_banned_offsets [n_banned + 1] are the
+ * banned token sequences in CSR form (sequence q = tokens[offsets[q] .. offsets[q+1])).  At every step but the forced-EOS
+ * one, for a row whose sequence so far (prompt included) has S tokens and every banned sequence b of length L: if L - 1 <= S
+ * and the row's last L - 1 tokens equal b[0 .. L-1), the log-probability of b[L-1] becomes -inf (blocked after the row's
+ * log-sum-exp, not renormalised; L == 1 bans its token always).  May be combined with opts->no_repeat_ngram_size.
+ * n_banned == 0 is sc_generate_text.  With n_banned > 0 the call runs the host-driven step loop for every beam_size (1
+ * included), never the decode engine; ids, lengths, scores and decoder outputs are otherwise what sc_generate_text documents.
+ * The list is copied to the device once per call.  Limits (SC_ERR_INVALID before any device work): n_banned <= 4096, 1..64
+ * tokens per sequence, 65536 tokens in all, every token inside the text vocabulary.  sc_generate_text_capture and sc_s2st
+ * take no banned sequences. */
+int sc_generate_text_banned(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
+                            const sc_gen_opts* opts, const int32_t* h_prefix, int32_t prefix_len, int32_t* h_out_ids,
+                            int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden, const int32_t* h_banned_tokens,
+                            const int32_t* h_banned_offsets /* [n_banned + 1] */, int32_t n_banned);
+
 /* Greedy generation that also returns what the reference's Transcriber hooks into the model (ABI 10;
  * inference/transcriber.py:39-57, 124-127): per utterance and per FED position p (prompt positions included) the
  * probabilities of the last decoder layer's encoder-decoder attention of the query fed at p, summed over the heads,
@@ -350,6 +366,13 @@ int32_t sc_text_to_char_seqs(int32_t vocab, const int32_t* h_tok_len, const uint
  * NGramRepeatBlockProcessor(ngram_size) blocks after the `len` tokens of `h_seq`.  Writes at most `cap`
  * of them to h_out (in window order, duplicates kept) and returns how many there are, or a negative status. */
 int32_t sc_ngram_blocked_tokens(const int32_t* h_seq, int32_t len, int32_t ngram_size, int32_t* h_out, int32_t cap);
+
+/* Host logic of the banned-sequence step processor (no device work; callable without a GPU): the tokens that the list of
+ * sc_generate_text_banned (same limits, except that there is no vocabulary to check tokens against) blocks after the `len`
+ * tokens of `h_seq`.  Writes at most `cap` of them to h_out (in banned-list order, duplicates kept) and returns how many
+ * there are, or a negative status. */
+int32_t sc_banned_blocked_tokens(const int32_t* h_seq, int32_t len, const int32_t* h_banned_tokens, const int32_t* h_banned_offsets,
+                                 int32_t n_banned, int32_t* h_out, int32_t cap);
 
 /* The kernel-level test hooks (sc_op_*) and the dispatch introspection the parity tests drive are exported too but are NOT part
  * of the drop-in boundary: include/seamless_hip_internal.h. */

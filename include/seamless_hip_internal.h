@@ -170,6 +170,14 @@ int sc_op_beam_candidates(float* d_logits, int64_t ld, int32_t n_utt, int32_t be
                           int32_t no_eos, int32_t force_eos, int32_t pad_idx, int32_t eos_idx, int32_t unk_idx, float unk_penalty, int32_t K,
                           float* d_cand_val, int32_t* d_cand_idx, const int32_t* d_seqs, int32_t seq_ld, int32_t S, int32_t G,
                           const int32_t* d_rows, const int32_t* d_slots, int32_t chunked);
+/* sc_op_beam_candidates plus a banned-sequence list in DEVICE memory (CSR: d_banned_tokens, d_banned_offsets [n_banned + 1];
+ * tests/test_banned_gpu.py): runs beam_candidates_banned_kernel / step_processors_kernel.  Needs d_seqs; the list is read
+ * back and checked against the limits of sc_generate_text_banned before the launch.  n_banned == 0 is sc_op_beam_candidates. */
+int sc_op_beam_candidates_banned(float* d_logits, int64_t ld, int32_t n_utt, int32_t beams, int32_t V, const float* d_cum,
+                                 int32_t first_step, int32_t no_eos, int32_t force_eos, int32_t pad_idx, int32_t eos_idx, int32_t unk_idx,
+                                 float unk_penalty, int32_t K, float* d_cand_val, int32_t* d_cand_idx, const int32_t* d_seqs,
+                                 int32_t seq_ld, int32_t S, int32_t G, const int32_t* d_rows, const int32_t* d_slots, int32_t chunked,
+                                 const int32_t* d_banned_tokens, const int32_t* d_banned_offsets, int32_t n_banned);
 int sc_op_beam_select(const float* d_cand_val, const int32_t* d_cand_idx, const int32_t* d_seqs_cur, int32_t* d_seqs_new, float* d_fin_score,
                       int32_t* d_fin_len, int32_t* d_fin_seq, int32_t* d_fin_count, int32_t* d_done, int32_t* d_remaining, int32_t* d_tok,
                       int32_t* d_src_row, float* d_cum, int32_t* d_anc, int32_t anc_ld, const int32_t* d_slot_utt, const int32_t* d_slots,

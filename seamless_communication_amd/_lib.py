@@ -121,6 +121,7 @@ SIGNATURES = {
     "sc_mma_step": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "sc_text_max_len": (_i, [_P, C.POINTER(sc_gen_opts), _i]),
     "sc_generate_text": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P]),
+    "sc_generate_text_banned": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P, _P, _P, _i]),
     "sc_generate_text_capture": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P, _P, _P]),
     "sc_decode_text": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P]),
     "sc_engine_create": (_P, [_P, C.POINTER(sc_engine_opts)]),
@@ -145,6 +146,7 @@ SIGNATURES = {
     "sc_text_to_char_seqs": (C.c_int32, [C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32,
                                          _P, _P, C.c_int32, _P]),
     "sc_ngram_blocked_tokens": (C.c_int32, [_PI, C.c_int32, C.c_int32, _PI, C.c_int32]),
+    "sc_banned_blocked_tokens": (C.c_int32, [_PI, C.c_int32, _PI, _PI, C.c_int32, _PI, C.c_int32]),
     "sc_op_knob": (C.c_int, [C.c_char_p, C.c_int]),
     "sc_op_force_general_gemm": (C.c_int, [C.c_int]),
     "sc_op_single_plane": (C.c_int, [C.c_int]),
@@ -179,6 +181,8 @@ SIGNATURES = {
     "sc_op_argmax": (C.c_int, [_P, _i, _i, _P, _P]),
     "sc_op_beam_candidates": (C.c_int, [_P, C.c_int64, _i, _i, _i, _P, _i, _i, _i, _i, _i, _i, C.c_float, _i, _P, _P, _P, _i, _i, _i,
                                         _P, _P, _i]),
+    "sc_op_beam_candidates_banned": (C.c_int, [_P, C.c_int64, _i, _i, _i, _P, _i, _i, _i, _i, _i, _i, C.c_float, _i, _P, _P, _P, _i, _i,
+                                               _i, _P, _P, _i, _P, _P, _i]),
     "sc_op_beam_select": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _i, _i, _i, _i, _i, _i, _i, _i,
                                     _i, C.c_float]),
     "sc_op_beam_compact": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _i]),
@@ -208,6 +212,20 @@ def load_library() -> C.CDLL:
         raise SeamlessHipError(f"ABI mismatch: library {lib.sc_abi_version()} vs binding {SC_ABI_VERSION}")
     _lib = lib
     return lib
+
+
+def banned_csr(banned_seqs):
+    """Token sequences -> (tokens int32, offsets int32 [n + 1]): the CSR form sc_generate_text_banned and
+    sc_banned_blocked_tokens take.  An empty sequence is a ``ValueError`` (the C side would refuse it too)."""
+    import numpy as np
+
+    seqs = [[int(t) for t in (s.tolist() if hasattr(s, "tolist") else s)] for s in banned_seqs]
+    if any(len(s) == 0 for s in seqs):
+        raise ValueError("a banned sequence must hold at least one token")
+    off = np.zeros(len(seqs) + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.int64)
+    tok = np.asarray([t for s in seqs for t in s], dtype=np.int32)
+    return tok, off
 
 
 def check(status: int, what: str) -> None:

@@ -252,6 +252,22 @@ int sc_generate_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, 
     SC_API_END
 }
 
+int sc_generate_text_banned(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
+                            const sc_gen_opts* opts, const int32_t* h_prefix, int32_t prefix_len, int32_t* h_out_ids,
+                            int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden, const int32_t* h_banned_tokens,
+                            const int32_t* h_banned_offsets, int32_t n_banned) {
+    SC_API_BEGIN
+    SC_CHECK(m && d_enc && h_enc_lens && opts && h_prefix && h_out_ids && h_out_lens, "sc_generate_text_banned: null argument");
+    SC_CHECK(n_banned >= 0 && (n_banned == 0 || (h_banned_tokens && h_banned_offsets)), "sc_generate_text_banned: bad banned list");
+    BannedHost b;
+    b.tokens = h_banned_tokens, b.offsets = h_banned_offsets, b.n = n_banned;
+    validate_banned_host(b.tokens, b.offsets, b.n, m->m.cfg.text_vocab_size, nullptr);  // refused before any device work
+    SC_HIP(hipSetDevice(m->m.device));
+    run_generate_text(m->m, d_enc, n, s_enc, h_enc_lens, *opts, h_prefix, prefix_len, h_out_ids, h_out_lens, h_out_scores,
+                      d_dec_hidden, nullptr, 0, nullptr, n_banned > 0 ? &b : nullptr);
+    SC_API_END
+}
+
 int sc_generate_text_capture(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
                              const sc_gen_opts* opts, const int32_t* h_prefix, int32_t prefix_len, int32_t* h_out_ids,
                              int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden, float* d_xattn, float* h_step_lprob) {
@@ -529,6 +545,25 @@ int32_t sc_ngram_blocked_tokens(const int32_t* h_seq, int32_t len, int32_t ngram
                  "sc_ngram_blocked_tokens: bad argument");
         std::vector<int32_t> out;
         sc::ngram_blocked_tokens(h_seq, len, ngram_size, out);
+        for (size_t i = 0; i < out.size() && i < (size_t)cap; ++i) h_out[i] = out[i];
+        return (int32_t)out.size();
+    } catch (const sc::Error& e) {
+        return e.code;
+    } catch (const std::exception& e) {
+        sc::set_error("unexpected C++ exception: %s", e.what());
+        return SC_ERR_INTERNAL;
+    }
+}
+
+int32_t sc_banned_blocked_tokens(const int32_t* h_seq, int32_t len, const int32_t* h_banned_tokens, const int32_t* h_banned_offsets,
+                                 int32_t n_banned, int32_t* h_out, int32_t cap) {
+    try {
+        SC_CHECK(len >= 0 && cap >= 0 && (h_seq || len == 0) && (h_out || cap == 0), "sc_banned_blocked_tokens: bad argument");
+        sc::validate_banned_host(h_banned_tokens, h_banned_offsets, n_banned, -1, nullptr);
+        sc::BannedHost b;
+        b.tokens = h_banned_tokens, b.offsets = h_banned_offsets, b.n = n_banned;
+        std::vector<int32_t> out;
+        sc::banned_blocked_tokens(h_seq, len, b, out);
         for (size_t i = 0; i < out.size() && i < (size_t)cap; ++i) h_out[i] = out[i];
         return (int32_t)out.size();
     } catch (const sc::Error& e) {
@@ -1413,11 +1448,25 @@ int sc_op_argmax(const float* d_logits, int32_t rows, int32_t V, int32_t* d_idx,
 // into other buffers (slot -> utterance, candidate -> beam, source rows) are checked on the host first (op_read_ints): a test
 // that hands in a bad one gets an error, not an out-of-bounds access.
 
-int sc_op_beam_candidates(float* d_logits, int64_t ld, int32_t n_utt, int32_t beams, int32_t V, const float* d_cum, int32_t first_step,
-                          int32_t no_eos, int32_t force_eos, int32_t pad_idx, int32_t eos_idx, int32_t unk_idx, float unk_penalty, int32_t K,
-                          float* d_cand_val, int32_t* d_cand_idx, const int32_t* d_seqs, int32_t seq_ld, int32_t S, int32_t G,
-                          const int32_t* d_rows, const int32_t* d_slots, int32_t chunked) {
+static int op_beam_candidates(float* d_logits, int64_t ld, int32_t n_utt, int32_t beams, int32_t V, const float* d_cum, int32_t first_step,
+                              int32_t no_eos, int32_t force_eos, int32_t pad_idx, int32_t eos_idx, int32_t unk_idx, float unk_penalty, int32_t K,
+                              float* d_cand_val, int32_t* d_cand_idx, const int32_t* d_seqs, int32_t seq_ld, int32_t S, int32_t G,
+                              const int32_t* d_rows, const int32_t* d_slots, int32_t chunked, const int32_t* d_banned_tokens,
+                              const int32_t* d_banned_offsets, int32_t n_banned) {
     SC_API_BEGIN
+    // the device list is read back and checked on the host first: a bad one is an error, not an out-of-bounds access
+    BannedList bl;
+    if (n_banned != 0) {
+        SC_CHECK(n_banned > 0 && n_banned <= BANNED_MAX_SEQS && d_banned_tokens && d_banned_offsets && d_seqs,
+                 "sc_op_beam_candidates_banned: bad banned list (n_banned=%d; needs d_seqs)", n_banned);
+        const std::vector<int32_t> off = op_read_ints(d_banned_offsets, (size_t)n_banned + 1);
+        SC_CHECK(off[0] == 0 && off[n_banned] >= 0 && off[n_banned] <= BANNED_MAX_TOKENS, "sc_op_beam_candidates_banned: bad offsets");
+        for (int q = 0; q < n_banned; ++q) SC_CHECK(off[q + 1] >= off[q], "sc_op_beam_candidates_banned: offsets decrease at %d", q);
+        const std::vector<int32_t> tok = op_read_ints(d_banned_tokens, (size_t)off[n_banned]);
+        validate_banned_host(tok.data(), off.data(), n_banned, V, &bl.max_len);
+        bl.tokens = d_banned_tokens, bl.offsets = d_banned_offsets, bl.n = n_banned;
+    }
+    const BannedList* banned = bl.n > 0 ? &bl : nullptr;
     SC_CHECK(d_logits && d_cum && d_cand_val && d_cand_idx && n_utt >= 1 && V >= 1 && ld >= V, "sc_op_beam_candidates: bad arguments");
     SC_CHECK(!d_seqs || (G >= 0 && S >= 0 && seq_ld >= S), "sc_op_beam_candidates: bad n-gram arguments (S=%d G=%d seq_ld=%d)", S, G, seq_ld);
     if (d_slots) SC_CHECK(op_read_ints(d_slots, 1)[0] <= n_utt, "sc_op_beam_candidates: *d_slots > n_utt");
@@ -1431,15 +1480,33 @@ int sc_op_beam_candidates(float* d_logits, int64_t ld, int32_t n_utt, int32_t be
         SC_HIP(hipMemsetAsync(ws_f, 0xff, beam_ws_floats(rows, K) * 4, g_op_stream));  // NaN / -1: unwritten entries show
         SC_HIP(hipMemsetAsync(ws_i, 0xff, beam_ws_ints(rows, K) * 4, g_op_stream));
         launch_beam_candidates_chunked(d_logits, ld, n_utt, beams, V, d_cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx,
-                                       unk_penalty, K, d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, ws_f, ws_i, g_op_stream, d_rows, d_slots);
+                                       unk_penalty, K, d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, ws_f, ws_i, g_op_stream, d_rows, d_slots, banned);
         SC_HIP(hipStreamSynchronize(g_op_stream));
     } else {
         SC_CHECK(!d_rows, "sc_op_beam_candidates: d_rows is an argument of the chunked search only (the single-workgroup one takes d_slots)");
         launch_beam_candidates(d_logits, ld, n_utt, beams, V, d_cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K,
-                               d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, g_op_stream, d_slots);
+                               d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, g_op_stream, d_slots, banned);
         SC_HIP(hipStreamSynchronize(g_op_stream));
     }
     SC_API_END
+}
+
+int sc_op_beam_candidates(float* d_logits, int64_t ld, int32_t n_utt, int32_t beams, int32_t V, const float* d_cum, int32_t first_step,
+                          int32_t no_eos, int32_t force_eos, int32_t pad_idx, int32_t eos_idx, int32_t unk_idx, float unk_penalty, int32_t K,
+                          float* d_cand_val, int32_t* d_cand_idx, const int32_t* d_seqs, int32_t seq_ld, int32_t S, int32_t G,
+                          const int32_t* d_rows, const int32_t* d_slots, int32_t chunked) {
+    return op_beam_candidates(d_logits, ld, n_utt, beams, V, d_cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K,
+                              d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, d_rows, d_slots, chunked, nullptr, nullptr, 0);
+}
+
+int sc_op_beam_candidates_banned(float* d_logits, int64_t ld, int32_t n_utt, int32_t beams, int32_t V, const float* d_cum,
+                                 int32_t first_step, int32_t no_eos, int32_t force_eos, int32_t pad_idx, int32_t eos_idx, int32_t unk_idx,
+                                 float unk_penalty, int32_t K, float* d_cand_val, int32_t* d_cand_idx, const int32_t* d_seqs,
+                                 int32_t seq_ld, int32_t S, int32_t G, const int32_t* d_rows, const int32_t* d_slots, int32_t chunked,
+                                 const int32_t* d_banned_tokens, const int32_t* d_banned_offsets, int32_t n_banned) {
+    return op_beam_candidates(d_logits, ld, n_utt, beams, V, d_cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K,
+                              d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, d_rows, d_slots, chunked, d_banned_tokens, d_banned_offsets,
+                              n_banned);
 }
 
 int sc_op_beam_select(const float* d_cand_val, const int32_t* d_cand_idx, const int32_t* d_seqs_cur, int32_t* d_seqs_new, float* d_fin_score,

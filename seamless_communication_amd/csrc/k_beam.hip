@@ -11,6 +11,9 @@
 //   Step processor (NGramRepeatBlockProcessor): the tokens that would complete an n-gram already in the row's
 //   sequence (read from the device-resident sequence buffer) are overwritten with -inf in the logit row AFTER
 //   the row's log-sum-exp is known, i.e. the log-probability is blocked, not renormalised.
+//   Step processor (BannedSequenceProcessor, the MinTox re-decode): a list of banned token sequences (CSR in device memory);
+//   a sequence whose first L-1 tokens equal the last L-1 tokens of the row's sequence blocks its last token the same way
+//   (banned_block_row; beam_candidates_banned_kernel / step_processors_kernel - a call without a list launches neither).
 // beam_select_kernel: the per-step candidate walk (finalise EOS hypotheses, refill the beams, append tokens);
 //   sequences, finished hypotheses and counters live in device memory, the host only polls `remaining`.
 // row_token_lprob_kernel: log-softmax value of ONE given token per row (scores of the echoed prompt).
@@ -55,12 +58,34 @@ __device__ __forceinline__ int order_key(float v) {
 __device__ __forceinline__ float key_value(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
 __device__ __forceinline__ bool better_key(int v, int i, int w, int j) { return v > w || (v == w && i < j); }
 
-__global__ __launch_bounds__(256) void beam_candidates_kernel(float* logits, int64_t ld, int beams, int V,
-                                                              const float* __restrict__ cum, int first_step, int no_eos,
-                                                              int force_eos, int pad_idx, int eos_idx, int unk_idx,
-                                                              float unk_penalty, int K, float* __restrict__ cand_val,
-                                                              int* __restrict__ cand_idx, const int* __restrict__ seqs,
-                                                              int seq_ld, int S, int G, const int* __restrict__ d_slots) {
+// BannedSequenceProcessor for one row, by the whole workgroup.  seq: the row's S tokens so far (prompt included).  Banned
+// sequence q = tokens[offsets[q] .. offsets[q+1]) of length L (1 <= L <= BANNED_MAX_LEN, checked by the launcher): when its
+// first L-1 tokens equal the row's last L-1 tokens (right-aligned, over its own length only; L-1 > S never matches; L == 1
+// always does) the logit of its last token becomes -inf.  The row's tail (min(S, max_len - 1) tokens) is staged once in LDS
+// (s_tail: BANNED_MAX_LEN ints), threads stride over the sequences; several threads may store the same -inf to one address.
+// Every thread of the workgroup must call it (barriers); the caller orders the stores before later reads of the row.
+__device__ __forceinline__ void banned_block_row(float* row, int V, const int* __restrict__ seq, int S, const BannedList& bl, int* s_tail) {
+    const int T = min(S, min(bl.max_len, BANNED_MAX_LEN) - 1);
+    __syncthreads();  // s_tail may still be read for the previous row
+    for (int i = threadIdx.x; i < T; i += 256) s_tail[i] = seq[S - T + i];
+    __syncthreads();
+    for (int q = threadIdx.x; q < bl.n; q += 256) {
+        const int o = bl.offsets[q];
+        const int P = bl.offsets[q + 1] - o - 1;  // prefix length
+        if (P < 0 || P > T) continue;             // P > T: longer than the row's sequence (P <= max_len - 1 always)
+        bool same = true;
+        for (int e = 0; e < P; ++e) same = same && (bl.tokens[o + e] == s_tail[T - P + e]);
+        const int t = bl.tokens[o + P];
+        if (same && t >= 0 && t < V) row[t] = -INFINITY;
+    }
+}
+
+template <bool BANNED>
+__device__ __forceinline__ void beam_candidates_body(float* logits, int64_t ld, int beams, int V, const float* __restrict__ cum,
+                                                     int first_step, int no_eos, int force_eos, int pad_idx, int eos_idx, int unk_idx,
+                                                     float unk_penalty, int K, float* __restrict__ cand_val, int* __restrict__ cand_idx,
+                                                     const int* __restrict__ seqs, int seq_ld, int S, int G,
+                                                     const int* __restrict__ d_slots, const BannedList& bl) {
     __shared__ float red[4];
     __shared__ float lse[BEAM_MAX_K];
     __shared__ int s_key[256];
@@ -95,6 +120,14 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(float* logits, int
             }
         }
         __syncthreads();
+    }
+    if constexpr (BANNED) {
+        __shared__ int s_tail[BANNED_MAX_LEN];
+        if (seqs && bl.n > 0) {  // uniform over the workgroup
+            for (int b = 0; b < nb; ++b)
+                banned_block_row(logits + ((int64_t)n * beams + b) * ld, V, seqs + ((int64_t)n * beams + b) * seq_ld, S, bl, s_tail);
+            __syncthreads();
+        }
     }
     // per-thread best-K list of (order_key(value), flattened index), sorted best first
     const int empty = order_key(-INFINITY);
@@ -173,6 +206,28 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(float* logits, int
     }
 }
 
+__global__ __launch_bounds__(256) void beam_candidates_kernel(float* logits, int64_t ld, int beams, int V,
+                                                              const float* __restrict__ cum, int first_step, int no_eos,
+                                                              int force_eos, int pad_idx, int eos_idx, int unk_idx,
+                                                              float unk_penalty, int K, float* __restrict__ cand_val,
+                                                              int* __restrict__ cand_idx, const int* __restrict__ seqs,
+                                                              int seq_ld, int S, int G, const int* __restrict__ d_slots) {
+    beam_candidates_body<false>(logits, ld, beams, V, cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val,
+                                cand_idx, seqs, seq_ld, S, G, d_slots, BannedList{});
+}
+
+// the same search with a banned-sequence list (launched only when the call carries one)
+__global__ __launch_bounds__(256) void beam_candidates_banned_kernel(float* logits, int64_t ld, int beams, int V,
+                                                                     const float* __restrict__ cum, int first_step, int no_eos,
+                                                                     int force_eos, int pad_idx, int eos_idx, int unk_idx,
+                                                                     float unk_penalty, int K, float* __restrict__ cand_val,
+                                                                     int* __restrict__ cand_idx, const int* __restrict__ seqs,
+                                                                     int seq_ld, int S, int G, const int* __restrict__ d_slots,
+                                                                     BannedList bl) {
+    beam_candidates_body<true>(logits, ld, beams, V, cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val,
+                               cand_idx, seqs, seq_ld, S, G, d_slots, bl);
+}
+
 __global__ __launch_bounds__(256) void row_token_lprob_kernel(const float* __restrict__ logits, int64_t ld, int V,
                                                               int row_stride, int token, float* __restrict__ out) {
     __shared__ float red[4];
@@ -244,6 +299,29 @@ __global__ __launch_bounds__(256) void ngram_block_kernel(float* logits, int64_t
         const int t = seq[j + G - 1];
         if (same && t >= 0 && t < V) row[t] = -INFINITY;
     }
+}
+
+// both step processors in one launch (a call with a banned-sequence list): the n-gram rule as above when G is active, then
+// the banned sequences; one workgroup per row.  On the first step only beam 0 of an utterance competes: the other rows are
+// left alone (as in the single-workgroup search).
+__global__ __launch_bounds__(256) void step_processors_kernel(float* logits, int64_t ld, int V, int beams, int first_step,
+                                                              const int* __restrict__ seqs, int seq_ld, int S, int G, BannedList bl,
+                                                              const int* __restrict__ d_rows) {
+    __shared__ int s_tail[BANNED_MAX_LEN];
+    if (d_rows && (int)blockIdx.x >= *d_rows) return;
+    if (first_step && blockIdx.x % beams != 0) return;
+    float* row = logits + (int64_t)blockIdx.x * ld;
+    const int* seq = seqs + (int64_t)blockIdx.x * seq_ld;
+    if (G > 0 && G < S) {
+        const int* tail = seq + S - (G - 1);
+        for (int j = threadIdx.x; j + G <= S; j += 256) {
+            bool same = true;
+            for (int e = 0; e + 1 < G; ++e) same = same && (seq[j + e] == tail[e]);
+            const int t = seq[j + G - 1];
+            if (same && t >= 0 && t < V) row[t] = -INFINITY;
+        }
+    }
+    banned_block_row(row, V, seq, S, bl, s_tail);
 }
 
 // block-wide arg-best of one (value, flattened index) per thread; every thread returns the winner
@@ -526,14 +604,51 @@ __global__ __launch_bounds__(256) void gather_cache_kernel(const float* __restri
 
 }  // namespace
 
+// Limits of a banned-sequence list, on the host before any launch.  tokens / offsets == null: the shape only (a device list
+// whose contents banned_list_upload checked).  V < 0: no vocabulary to check against.
+void validate_banned_host(const int32_t* tokens, const int32_t* offsets, int n_banned, int V, int* out_max_len) {
+    SC_CHECK(n_banned >= 0 && n_banned <= BANNED_MAX_SEQS, "banned sequences: %d sequences (at most %d)", n_banned, BANNED_MAX_SEQS);
+    int max_len = 0;
+    if (n_banned > 0) {
+        SC_CHECK(tokens && offsets, "banned sequences: null list");
+        SC_CHECK(offsets[0] == 0, "banned sequences: offsets[0] = %d", offsets[0]);
+        for (int q = 0; q < n_banned; ++q) {
+            const int64_t L = (int64_t)offsets[q + 1] - offsets[q];
+            SC_CHECK(L >= 1 && L <= BANNED_MAX_LEN, "banned sequences: sequence %d has %lld tokens (1..%d)", q, (long long)L, BANNED_MAX_LEN);
+            max_len = std::max(max_len, (int)L);
+        }
+        const int total = offsets[n_banned];
+        SC_CHECK(total <= BANNED_MAX_TOKENS, "banned sequences: %d tokens in all (at most %d)", total, BANNED_MAX_TOKENS);
+        if (V >= 0)
+            for (int i = 0; i < total; ++i)
+                SC_CHECK(tokens[i] >= 0 && tokens[i] < V, "banned sequences: token %d outside the vocabulary of %d", tokens[i], V);
+    }
+    if (out_max_len) *out_max_len = max_len;
+}
+
+namespace {
+void check_banned_list(const BannedList& bl, int seq_ld, int S) {
+    SC_CHECK(bl.tokens && bl.offsets && bl.n <= BANNED_MAX_SEQS && bl.max_len >= 1 && bl.max_len <= BANNED_MAX_LEN,
+             "banned sequences: bad device list (n=%d max_len=%d)", bl.n, bl.max_len);
+    SC_CHECK(S >= 0 && S <= seq_ld, "banned sequences: %d tokens in rows of %d", S, seq_ld);
+}
+}  // namespace
+
 void launch_beam_candidates(float* logits, int64_t ld, int n_utt, int beams, int V, const float* cum, int first_step,
                             int no_eos, int force_eos, int pad_idx, int eos_idx, int unk_idx, float unk_penalty, int K,
-                            float* cand_val, int* cand_idx, const int* seqs, int seq_ld, int S, int G, hipStream_t s, const int* d_slots) {
+                            float* cand_val, int* cand_idx, const int* seqs, int seq_ld, int S, int G, hipStream_t s, const int* d_slots,
+                            const BannedList* banned) {
     SC_CHECK(K >= 1 && K <= BEAM_MAX_K && beams >= 1 && beams <= BEAM_MAX_K, "beam search: beam_size %d / K %d out of range (max %d candidates)",
              beams, K, BEAM_MAX_K);
     SC_CHECK((int64_t)beams * V < (1ll << 31) - 1, "beam search: beam * vocabulary overflows the candidate index");
-    hipLaunchKernelGGL(beam_candidates_kernel, dim3(n_utt), dim3(256), 0, s, logits, ld, beams, V, cum, first_step, no_eos, force_eos,
-                       pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val, cand_idx, seqs, seq_ld, S, G, d_slots);
+    if (banned && banned->n > 0 && seqs) {
+        check_banned_list(*banned, seq_ld, S);
+        hipLaunchKernelGGL(beam_candidates_banned_kernel, dim3(n_utt), dim3(256), 0, s, logits, ld, beams, V, cum, first_step, no_eos,
+                           force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val, cand_idx, seqs, seq_ld, S, G, d_slots, *banned);
+    } else {
+        hipLaunchKernelGGL(beam_candidates_kernel, dim3(n_utt), dim3(256), 0, s, logits, ld, beams, V, cum, first_step, no_eos, force_eos,
+                           pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val, cand_idx, seqs, seq_ld, S, G, d_slots);
+    }
     SC_LAUNCH_CHECK();
 }
 
@@ -549,7 +664,7 @@ size_t beam_ws_ints(int rows, int K) { return (size_t)rows * BEAM_CH * K; }
 void launch_beam_candidates_chunked(float* logits, int64_t ld, int n_utt, int beams, int V, const float* cum, int first_step, int no_eos,
                                     int force_eos, int pad_idx, int eos_idx, int unk_idx, float unk_penalty, int K, float* cand_val,
                                     int* cand_idx, const int* seqs, int seq_ld, int S, int G, float* ws_f, int* ws_i, hipStream_t s,
-                                    const int* d_rows, const int* d_slots) {
+                                    const int* d_rows, const int* d_slots, const BannedList* banned) {
     SC_CHECK(K >= 1 && K <= BEAM_MAX_K && beams >= 1 && beams <= BEAM_MAX_K, "beam search: beam_size %d / K %d out of range (max %d candidates)",
              beams, K, BEAM_MAX_K);
     SC_CHECK((int64_t)beams * V < (1ll << 31) - 1, "beam search: beam * vocabulary overflows the candidate index");
@@ -560,7 +675,13 @@ void launch_beam_candidates_chunked(float* logits, int64_t ld, int n_utt, int be
     float2* part = reinterpret_cast<float2*>(ws_f);
     float* pval = ws_f + (size_t)rows * BEAM_CH * 2;
     hipLaunchKernelGGL(beam_lse_partial_kernel, dim3(BEAM_CH, rows), dim3(256), 0, s, logits, ld, V, clen, part, d_rows);
-    if (seqs && G > 0 && G < S) hipLaunchKernelGGL(ngram_block_kernel, dim3(rows), dim3(256), 0, s, logits, ld, V, seqs, seq_ld, S, G, d_rows);
+    if (banned && banned->n > 0 && seqs) {  // both step processors in ONE launch
+        check_banned_list(*banned, seq_ld, S);
+        hipLaunchKernelGGL(step_processors_kernel, dim3(rows), dim3(256), 0, s, logits, ld, V, beams, first_step, seqs, seq_ld, S, G, *banned,
+                           d_rows);
+    } else if (seqs && G > 0 && G < S) {
+        hipLaunchKernelGGL(ngram_block_kernel, dim3(rows), dim3(256), 0, s, logits, ld, V, seqs, seq_ld, S, G, d_rows);
+    }
     hipLaunchKernelGGL(beam_topk_partial_kernel, dim3(BEAM_CH, rows), dim3(256), 0, s, logits, ld, beams, V, clen, cum, first_step, no_eos,
                        force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, part, pval, ws_i, d_rows);
     hipLaunchKernelGGL(beam_merge_kernel, dim3(n_utt), dim3(256), 0, s, pval, ws_i, beams * BEAM_CH * K, K, cand_val, cand_idx, d_slots);

@@ -340,10 +340,18 @@ struct XattnCapture {
     float* d_xattn = nullptr;       // [n][max_len][s_enc] on the device
     float* h_step_lprob = nullptr;  // [n][max_len] on the host
 };
+// sc_generate_text_banned: the caller's banned token sequences (host CSR; BannedSequenceProcessor), copied to the device once
+// per call by run_generate_beam; banned_blocked_tokens is the host restatement of the rule (sc_banned_blocked_tokens)
+struct BannedHost {
+    const int32_t* tokens = nullptr;
+    const int32_t* offsets = nullptr;  // [n + 1]
+    int n = 0;
+};
+void banned_blocked_tokens(const int32_t* seq, int S, const BannedHost& b, std::vector<int32_t>& out);
 void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens,
                        const sc_gen_opts& o, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
                        int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, const int32_t* h_forced_tokens,
-                       int forced_len, const XattnCapture* xcap = nullptr);
+                       int forced_len, const XattnCapture* xcap = nullptr, const BannedHost* banned = nullptr);
 void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const int32_t* h_text_lens,
                  const int32_t* h_text_seqs, float duration_factor, int32_t* h_unit_lens, int32_t* out_su,
                  int32_t* out_sc);
@@ -362,7 +370,7 @@ void run_t2u_ar(Model& m, const float* d_dec_hidden, int n, int s_text, const in
 void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, const int* d_text_lens, float* d_out);
 void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                        const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                       float* d_dec_hidden, int max_len);
+                       float* d_dec_hidden, int max_len, const BannedHost* banned = nullptr);
 void run_vocode(Model& m, const int32_t* h_units, int n, int s_units, const int32_t* h_lang, const int32_t* h_spkr,
                 float* d_wav, const int32_t* h_unit_lens = nullptr);
 std::vector<std::vector<int>> plan_length_groups(const std::vector<int>& lens, int overhead_rows, int max_groups);

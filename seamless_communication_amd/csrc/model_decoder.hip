@@ -28,7 +28,7 @@ int text_max_len(const Model& m, const sc_gen_opts& o, int s_enc) {
 
 void run_generate_text_beam(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                             const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                            float* d_dec_hidden);
+                            float* d_dec_hidden, const BannedHost* banned = nullptr);
 
 namespace {
 
@@ -1170,7 +1170,7 @@ void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, con
 void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens,
                        const sc_gen_opts& o, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
                        int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, const int32_t* h_forced_tokens,
-                       int forced_len, const XattnCapture* xcap) {
+                       int forced_len, const XattnCapture* xcap, const BannedHost* banned) {
     const sc_config& cfg = m.cfg;
     const int M = cfg.model_dim;
     SC_CHECK(n > 0 && s_enc > 0, "sc_generate_text: empty batch");
@@ -1192,10 +1192,12 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
         SC_CHECK(!xcap || (o.beam_size == 1 && o.no_repeat_ngram_size == 0),
                  "sc_generate_text_capture: greedy generation only (beam_size=%d, no_repeat_ngram_size=%d are not supported)",
                  o.beam_size, o.no_repeat_ngram_size);
-        if (o.beam_size > 1 || o.no_repeat_ngram_size > 0) {  // step processors run in the host-driven step loop
+        const bool has_banned = banned && banned->n > 0;
+        SC_CHECK(!xcap || !has_banned, "sc_generate_text_capture: banned sequences are not supported");
+        if (o.beam_size > 1 || o.no_repeat_ngram_size > 0 || has_banned) {  // step processors run in the host-driven step loop
             if (m.engine) m.engine->expect(m, -n);
             run_generate_text_beam(m, d_enc, n, s_enc, h_enc_lens, o, h_prefix, prefix_len, h_out_ids, h_out_lens, h_scores,
-                                   d_dec_hidden);
+                                   d_dec_hidden, has_banned ? banned : nullptr);
             return;
         }
         SC_CHECK(prefix_len >= 1, "sc_generate_text: the prompt must hold at least one token");
@@ -1510,12 +1512,24 @@ void ngram_blocked_tokens(const int32_t* seq, int S, int G, std::vector<int32_t>
         if (std::equal(seq + j, seq + j + G - 1, tail)) out.push_back(seq[j + G - 1]);
 }
 
+// Tokens the banned-sequence processor blocks for one row (fairseq2 0.2 BannedSequenceProcessor, restated; the class is
+// not part of the reference tree): sequence q of length L blocks its last token when its first L-1 tokens equal the last L-1 tokens of seq
+// (L-1 > S: no match; L == 1: always).  In banned-list order, duplicates kept.
+void banned_blocked_tokens(const int32_t* seq, int S, const BannedHost& b, std::vector<int32_t>& out) {
+    for (int q = 0; q < b.n; ++q) {
+        const int32_t* w = b.tokens + b.offsets[q];
+        const int P = b.offsets[q + 1] - b.offsets[q] - 1;
+        if (P < 0 || P > S) continue;
+        if (std::equal(w, w + P, seq + S - P)) out.push_back(w[P]);
+    }
+}
+
 void run_generate_text_beam(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                             const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                            float* d_dec_hidden) {
+                            float* d_dec_hidden, const BannedHost* banned) {
     const DecStack W = unity_stack(m);
     run_generate_beam(m, W, d_enc, n, s_enc, h_enc_lens, o, h_prefix, prefix_len, h_out_ids, h_out_lens, h_scores, d_dec_hidden,
-                      text_max_len(m, o, s_enc));
+                      text_max_len(m, o, s_enc), banned);
 }
 
 // UnitYT2UModel generation of the v1 models (inference/generator.py:316-336): T2U encoder over the text decoder output,
@@ -1545,7 +1559,7 @@ void run_t2u_ar(Model& m, const float* d_dec_hidden, int n, int s_text, const in
 // Beam search over one decoder stack (the UnitY text decoder or the v1 autoregressive unit decoder).
 void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                        const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                       float* d_dec_hidden, int max_len) {
+                       float* d_dec_hidden, int max_len, const BannedHost* banned) {
     struct VocabView {  // the names the body used for the text vocabulary, now the stack's
         int pad_idx, unk_idx, eos_idx, text_max_seq_len, model_dim, dec_ffn_dim;
     };
@@ -1563,6 +1577,20 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
     SC_CHECK(s_enc <= 4096, "sc_generate_text: encoder length %d > 4096", s_enc);
     for (int i = 0; i < n; ++i)
         SC_CHECK(h_enc_lens[i] > 0 && h_enc_lens[i] <= s_enc, "sc_generate_text: enc_lens[%d]=%d out of range", i, h_enc_lens[i]);
+    // BannedSequenceProcessor: the list is checked on the host (before any launch) and copied to the device once per call
+    BannedList bl;
+    Buf<int> d_banned(m.pp(), 4);
+    if (banned && banned->n > 0) {
+        validate_banned_host(banned->tokens, banned->offsets, banned->n, V, &bl.max_len);
+        const int total = banned->offsets[banned->n];
+        d_banned = Buf<int>(m.pp(), (size_t)total + banned->n + 1);
+        SC_HIP(hipMemcpyAsync(d_banned.get(), banned->tokens, (size_t)total * 4, hipMemcpyHostToDevice, m.stream));
+        SC_HIP(hipMemcpyAsync(d_banned.get() + total, banned->offsets, (size_t)(banned->n + 1) * 4, hipMemcpyHostToDevice, m.stream));
+        SC_HIP(hipStreamSynchronize(m.stream));  // the list is the caller's
+        bl.tokens = d_banned.get();
+        bl.offsets = d_banned.get() + total;
+        bl.n = banned->n;
+    }
     const float len_penalty = o.len_penalty;
     const bool normalize = o.normalize_scores != 0;
 
@@ -1796,17 +1824,17 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
             decoder_step(m, c, /*project=*/false);  // feeds d_tok at position `step`, advances *d_pos
         }
         project_rows();
-        // n-gram processor: not on the forced-EOS step (blocking EOS there would leave no hypothesis)
-        const bool ban = G > 0 && step != max_len - 2;
+        // step processors: not on the forced-EOS step (blocking EOS there would leave no hypothesis)
+        const bool ban = (G > 0 || bl.n > 0) && step != max_len - 2;
         if (chunked) {
             launch_beam_candidates_chunked(c.logits, ldl, n, B, V, d_cum, step == start, step < o.min_seq_len, step == max_len - 2,
                                            cfg.pad_idx, cfg.eos_idx, cfg.unk_idx, o.unk_penalty, K, d_cand_val, d_cand_idx,
                                            ban ? d_seqs_cur : nullptr, max_len, step + 1, G, ws_f, ws_i, m.stream,
-                                           compact ? d_rows_live : nullptr, compact ? d_slots : nullptr);
+                                           compact ? d_rows_live : nullptr, compact ? d_slots : nullptr, bl.n > 0 ? &bl : nullptr);
         } else {
             launch_beam_candidates(c.logits, ldl, n, B, V, d_cum, step == start, step < o.min_seq_len, step == max_len - 2, cfg.pad_idx,
                                    cfg.eos_idx, cfg.unk_idx, o.unk_penalty, K, d_cand_val, d_cand_idx, ban ? d_seqs_cur : nullptr, max_len,
-                                   step + 1, G, m.stream, compact ? d_slots : nullptr);
+                                   step + 1, G, m.stream, compact ? d_slots : nullptr, bl.n > 0 ? &bl : nullptr);
         }
         BeamSelectArgs a;
         a.cand_val = d_cand_val;

@@ -1,6 +1,6 @@
-from .generator import NGramRepeatBlockProcessor, SequenceGeneratorOptions
+from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, SequenceGeneratorOptions
 from .transcriber import Transcriber, Transcription, TranscriptionToken, TranscriptionTokenStats
 from .translator import BatchedSpeechOutput, Modality, Task, Translator
 
-__all__ = ["BatchedSpeechOutput", "Modality", "NGramRepeatBlockProcessor", "SequenceGeneratorOptions", "Task", "Transcriber", "Transcription", "TranscriptionToken",
+__all__ = ["BannedSequenceProcessor", "BatchedSpeechOutput", "Modality", "NGramRepeatBlockProcessor", "SequenceGeneratorOptions", "Task", "Transcriber", "Transcription", "TranscriptionToken",
            "TranscriptionTokenStats", "Translator"]

@@ -41,6 +41,44 @@ class NGramRepeatBlockProcessor:
             probs[r, windows[r, hit, -1].to(torch.int64)] = fill
 
 
+class BannedSequenceProcessor:
+    """The step processor of the reference's MinTox re-decode (toxicity/mintox.py:125-135, 162; class from fairseq2 0.2
+    ``fairseq2.generation`` - not part of the reference tree, restated from its published behaviour: parity unpinned).
+
+    ``banned_seqs``: token sequences (sequences of ints or 1-D tensors).  Called with ``seqs`` (rows, S) = the sequences
+    generated so far (prompt included) and ``probs`` (rows, V): for every banned sequence ``b`` of length ``L`` whose first
+    ``L - 1`` tokens equal the last ``L - 1`` tokens of a row (right-aligned, each over its own length; a prefix longer than
+    the row never matches; ``L == 1`` always does), ``b[-1]`` is blocked in that row (``-inf`` for log-probabilities, ``0``
+    for probabilities).  An empty list is a no-op, an empty sequence a ``ValueError``.  On the HIP path the list itself
+    goes to the device (``sc_generate_text_banned``) and the rule runs inside the beam-search step; ``__call__`` is the
+    host restatement for other callers."""
+
+    def __init__(self, banned_seqs) -> None:
+        self.banned_seqs: List[List[int]] = []
+        for s in banned_seqs:
+            toks = [int(t) for t in (s.tolist() if hasattr(s, "tolist") else s)]
+            if not toks:
+                raise ValueError("`banned_seqs` must not contain an empty sequence.")
+            self.banned_seqs.append(toks)
+
+    def __call__(self, seqs, probs, lprob: bool = False) -> None:
+        import torch
+
+        if not self.banned_seqs:
+            return
+        rows, seq_len = seqs.shape
+        fill = -torch.inf if lprob else 0.0
+        for b in self.banned_seqs:
+            p = len(b) - 1
+            if p > seq_len:
+                continue
+            if p == 0:
+                probs[:, b[0]] = fill
+                continue
+            hit = (seqs[:, seq_len - p:].to(torch.int64) == torch.tensor(b[:-1], dtype=torch.int64, device=seqs.device)).all(dim=1)
+            probs[hit, b[-1]] = fill
+
+
 @dataclass
 class SequenceGeneratorOptions:
     """Holds the options to pass to a sequence generator."""

@@ -5,9 +5,12 @@ Mirrors src/seamless_communication/inference/translator.py of the reference:
 ``Task`` / ``Modality`` (:53-63), ``BatchedSpeechOutput`` (:66-75),
 ``Translator.__init__`` (:79-154), ``get_prediction`` (:155-196),
 ``get_modalities_from_task_str`` (:199-213), ``predict`` (:216-428) — same
-argument names, defaults, return types and error behaviour.  mintox and the
-expressive (prosody) inputs are outside the hot path
-and raise ``NotImplementedError``.
+argument names, defaults, return types and error behaviour.  ``apply_mintox``
+(:128-132, :263-266, :335-379) runs the reference's MinTox flow: the checker is
+loaded from ``Translator.mintox_card`` and the re-decode bans the words' token
+sequences inside the HIP beam-search step (``toxicity/mintox.py``).  The
+expressive (prosody) inputs are outside the hot path and
+raise ``NotImplementedError``.
 
 Models are named by asset cards like in the reference; a card is a dict with
 the reference schema (``model_arch``, ``checkpoint``, ...).  Offline, the
@@ -33,7 +36,7 @@ from .. import synthetic as _syn
 from ..config import S2STConfig, seamless_m4t_large, seamless_m4t_medium, seamless_m4t_v2_large, tiny_config, tiny_v1_config
 from ..runtime import HipS2STModel
 from ..tokenizer import CharTokenizer, NllbTextTokenizer, UnitTokenizer
-from .generator import NGramRepeatBlockProcessor, SequenceGeneratorOptions
+from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, SequenceGeneratorOptions
 
 logger = logging.getLogger(__name__)
 
@@ -163,8 +166,6 @@ class Translator:
         input_modality: Optional[Modality] = None,
         output_modality: Optional[Modality] = None,
     ):
-        if apply_mintox:
-            raise NotImplementedError("mintox is outside the MI355X S2ST hot path (SURVEY.md section 8)")
         card = _resolve_card(model_name_or_card)
         arch = card.get("model_arch", "base_v2")
         if arch not in _ARCHS:
@@ -206,7 +207,13 @@ class Translator:
         if with_t2u and getattr(self.model, "t2u_variant", 0) == 0:
             self.model.set_nar_tables(self.text_tokenizer, self.char_tokenizer)
         self.has_vocoder = vocoder_sd is not None
-        self.apply_mintox = False
+        # translator.py:128-132; the word lists are the user's data: `mintox_card` names where they are
+        self.bad_word_checker = None
+        if apply_mintox:
+            from ..toxicity.etox_bad_word_checker import load_etox_bad_word_checker
+
+            self.bad_word_checker = load_etox_bad_word_checker(self.mintox_card)
+        self.apply_mintox = apply_mintox
         # introspection for the batch driver / bench (not part of the reference API)
         self.use_graph = True  # replay the decoder step from a captured hipGraph
         self.last_text_ids: List[List[int]] = []
@@ -249,6 +256,11 @@ class Translator:
     #   "error" refuse.
     multi_channel: str = "first"
 
+    # The asset card `apply_mintox=True` loads the ETOX checker from (translator.py:130 names "mintox"): the bare name has
+    # no offline source, so set a card dict (toxicity/etox_bad_word_checker.py: load_etox_bad_word_checker) on the class
+    # or a subclass before constructing; `self.bad_word_checker` may also be assigned afterwards.
+    mintox_card: Union[str, Dict[str, Any]] = "mintox"
+
     def _collate_audio(self, audio: Tensor, sample_rate: int = 16000) -> SequenceData:
         """convert_to_fbank + Collater(pad_value=0, pad_to_multiple=2) (translator.py:135-146, :293): the front-end works at the
         waveform's own ``sample_rate`` (no resampling, like fairseq2n's converter)."""
@@ -285,6 +297,8 @@ class Translator:
         input_modality, output_modality = self.get_modalities_from_task_str(task_str)
         if prosody_encoder_input is not None:
             raise NotImplementedError("expressive (prosody) models are outside the MI355X S2ST hot path")
+        if self.apply_mintox and not (src_lang is not None or src_text is not None):  # translator.py:263-266
+            raise ValueError("`src_lang` must be specified when `apply_mintox` is `True` or you need to specify src_text.")
 
         if isinstance(input, dict):
             src = input
@@ -341,6 +355,45 @@ class Translator:
             unit_generation_ngram_filtering=unit_generation_ngram_filtering, duration_factor=duration_factor,
             prosody_encoder_input=prosody_encoder_input, _trace=trace,
         )
+        if self.apply_mintox and task_str.upper() != Task.ASR.name:  # translator.py:335-379
+            if input_modality == Modality.SPEECH:
+                if src_text is not None:
+                    src_texts = [src_text]
+                else:  # no transcript given: an ASR pass over the same input supplies the source text
+                    src_texts, _ = self.predict(
+                        input=input, task_str=Task.ASR.name, tgt_lang=tgt_lang, src_lang=src_lang,
+                        text_generation_opts=text_generation_opts, unit_generation_opts=unit_generation_opts, spkr=spkr,
+                        sample_rate=sample_rate, unit_generation_ngram_filtering=unit_generation_ngram_filtering)
+            else:
+                assert isinstance(input, str)
+                src_texts = [input]
+            assert src_lang is not None
+            assert self.bad_word_checker is not None
+            from ..toxicity.mintox import mintox_pipeline
+
+            redo: Dict[str, Any] = {"use_graph": self.use_graph}
+            n_rows = len(texts)
+            texts, units_t = mintox_pipeline(
+                model=self.model, text_tokenizer=self.text_tokenizer, unit_tokenizer=self.unit_tokenizer, device=self.device,
+                src_lang=src_lang, tgt_lang=tgt_lang, model_input={**src, "seqs": seqs}, input_modality=input_modality,
+                output_modality=output_modality, src_texts=src_texts, original_texts=texts, original_units=units_t,
+                unit_generation_ngram_filtering=unit_generation_ngram_filtering, text_generation_opts=text_generation_opts,
+                unit_generation_opts=unit_generation_opts, bad_word_checker=self.bad_word_checker,
+                duration_factor=duration_factor, prosody_encoder_input=prosody_encoder_input, _trace=redo)
+            if "text_ids" in redo:  # rows were generated again: the introspection data describe the last generation call
+                if len(redo["text_ids"]) == n_rows:
+                    trace = redo
+                else:  # a part of the batch: the rows generated again replace their per-row data
+                    rows = redo["mintox_rows"]
+                    for k, r in enumerate(rows):
+                        trace["text_ids"][r] = redo["text_ids"][k]
+                    old_t2u, new_t2u = trace.get("t2u"), redo.get("t2u")
+                    trace["t2u"] = None
+                    if old_t2u is not None and new_t2u is not None:  # the unit lengths let the vocoder skip the padding
+                        lens = np.array(old_t2u["unit_lens"], copy=True)
+                        lens[rows] = new_t2u["unit_lens"]
+                        trace["t2u"] = {"unit_lens": lens}
+                    trace["stage_ms"] = redo["stage_ms"]
         self.last_text_ids = trace["text_ids"]
         self.last_stage_ms = trace["stage_ms"]
         self.last_t2u = trace.get("t2u")
@@ -443,10 +496,16 @@ class Translator:
         if not 1 <= text_generation_opts.beam_size <= 8:
             raise ValueError("beam_size must be in [1, 8] on the HIP path")
         ngram = 0
+        step_kw: Dict[str, Any] = {}  # passed only when set: models without the keyword keep working
         if text_generation_opts.step_processor is not None:
-            if not isinstance(text_generation_opts.step_processor, NGramRepeatBlockProcessor):
-                raise NotImplementedError("the HIP path runs NGramRepeatBlockProcessor step processors only")
-            ngram = text_generation_opts.step_processor.ngram_size
+            proc = text_generation_opts.step_processor
+            if isinstance(proc, NGramRepeatBlockProcessor):
+                ngram = proc.ngram_size
+            elif isinstance(proc, BannedSequenceProcessor):
+                if proc.banned_seqs:
+                    step_kw["banned_seqs"] = proc.banned_seqs
+            else:
+                raise NotImplementedError("the HIP path runs NGramRepeatBlockProcessor and BannedSequenceProcessor step processors only")
         trace = _trace if _trace is not None else {}
         want_speech = output_modality == Modality.SPEECH
 
@@ -472,6 +531,7 @@ class Translator:
             # (speech) or the source tokens (text), generator.py:261-263 -- not to the adaptor's 8x shorter output
             # (fairseq2 0.2 takes the longest sequence of the padding mask when there is one, the padded width otherwise)
             source_len=int(max(src_lens)) if padding_mask is not None else int(seqs.shape[1]),
+            **step_kw,
         )
         t2 = time.perf_counter()
         text_ids = [ids[b, : out_lens[b]].tolist() for b in range(ids.shape[0])]

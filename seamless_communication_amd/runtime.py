@@ -264,10 +264,11 @@ class HipS2STModel:
                       soft_max_seq_len=(1, 200), hard_max_seq_len: int = 1024, min_seq_len: int = 1,
                       unk_penalty: float = 0.0, use_graph: bool = True, want_hidden: bool = True,
                       len_penalty: float = 1.0, normalize_scores: bool = True, no_repeat_ngram_size: int = 0,
-                      source_len: int = 0):
+                      source_len: int = 0, banned_seqs=None):
         """-> (ids (n, max_len) int32, lens (n,), scores (n,), hidden (n, max_len-1, M) or None).
         ``source_len``: padded length of the source sequences the soft length rule refers to (fbank frames for speech);
-        0 = the encoder output length."""
+        0 = the encoder output length.  ``banned_seqs``: token sequences (lists of ints) for the banned-sequence step
+        processor (sc_generate_text_banned); None or an empty list is the plain call."""
         assert enc.is_cuda and enc.is_contiguous()
         n, s_enc, M = enc.shape
         o = self._gen_opts(beam_size, soft_max_seq_len, hard_max_seq_len, min_seq_len, unk_penalty, use_graph, len_penalty,
@@ -280,6 +281,12 @@ class HipS2STModel:
         pre = _i32(prefix)
         el = _i32(enc_lens)
         self._after_torch()
+        if banned_seqs is not None and len(banned_seqs) > 0:
+            b_tok, b_off = _lib.banned_csr(banned_seqs)
+            check(self.lib.sc_generate_text_banned(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(pre), len(pre),
+                                                   _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden), _ptr(b_tok), _ptr(b_off),
+                                                   len(b_off) - 1), "sc_generate_text_banned")
+            return ids, lens, scores, hidden
         check(self.lib.sc_generate_text(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(pre), len(pre),
                                         _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden)), "sc_generate_text")
         return ids, lens, scores, hidden

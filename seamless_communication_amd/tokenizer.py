@@ -267,6 +267,11 @@ class NllbTextTokenizer:
             )
         return TextTokenEncoder(self, prefix, [eos], device)
 
+    def create_raw_encoder(self, *, device=None, pin_memory: bool = False) -> "TextTokenEncoder":
+        """fairseq2 ``NllbTokenizer.create_raw_encoder`` (call site toxicity/mintox.py:128): the pieces of the text only, no
+        language token and no ``</s>``."""
+        return TextTokenEncoder(self, [], [], device)
+
     def encode_pieces(self, text: str) -> List[int]:
         """text -> piece ids (no control symbols).  With a SentencePiece model: its own segmentation, ids shifted
         by the ``<pad>@0`` slot.  Synthetic vocabulary: SentencePiece-style normalisation (dummy prefix, spaces ->
