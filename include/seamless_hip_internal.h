@@ -32,6 +32,16 @@ int sc_op_knob(const char* name, int dflt);
 /* 1: route every dense product to the general MFMA kernel instead of the double-buffered fast path
  * (the two produce identical bits; used by the parity tests and for A/B timing). */
 int sc_op_force_general_gemm(int on);
+/* Host planning of the vocoder's packed pass (no device work; callable without a GPU).  sc_op_voc_pack_plan: `n` items of
+ * h_need unit rows each, in their order, cut into consecutive groups of at most budget_rows rows (a longer item is a group of
+ * its own); returns the number of groups and writes at most `cap` of the groups' first items, followed by n.
+ * sc_op_voc_tile_first: h_off [n + 1] unit-row offsets, `mul` rows per unit row, tiles of tile_rows rows counted from every
+ * item's first row -> h_first [n + 1], the first tile (workgroup) of every item and their number.
+ * sc_op_last_vocoder_packed_groups: packed groups of the handle's last sc_vocode* call, 0 when it ran the padded batch or the
+ * length buckets (SC_VOC_PACKED=0, unit_lens == NULL, a geometry the packed kernels do not take). */
+int32_t sc_op_voc_pack_plan(const int32_t* h_need, int32_t n, int64_t budget_rows, int32_t* h_group_first, int32_t cap);
+int32_t sc_op_voc_tile_first(const int32_t* h_off, int32_t n, int32_t mul, int32_t tile_rows, int32_t* h_first);
+int32_t sc_op_last_vocoder_packed_groups(sc_model* m);
 /* the ResBlock op hooks below (sc_op_resblock_pair, sc_op_resblock_pair_ps, sc_op_mrf_fused) multiply the hi fp16 plane of
  * their activations only - the vocoder's shipped variants - while this is on (default off: the two-plane variants) */
 int sc_op_single_plane(int on);

@@ -149,6 +149,9 @@ SIGNATURES = {
     "sc_banned_blocked_tokens": (C.c_int32, [_PI, C.c_int32, _PI, _PI, C.c_int32, _PI, C.c_int32]),
     "sc_op_knob": (C.c_int, [C.c_char_p, C.c_int]),
     "sc_op_force_general_gemm": (C.c_int, [C.c_int]),
+    "sc_op_voc_pack_plan": (C.c_int32, [_PI, C.c_int32, C.c_int64, _PI, C.c_int32]),
+    "sc_op_voc_tile_first": (C.c_int32, [_PI, C.c_int32, C.c_int32, C.c_int32, _PI]),
+    "sc_op_last_vocoder_packed_groups": (C.c_int32, [_P]),
     "sc_op_single_plane": (C.c_int, [C.c_int]),
     "sc_op_layernorm": (C.c_int, [_P, _P, _P, _P, _i, _i, _i]),
     "sc_op_linear": (C.c_int, [_P, _P, _P, _P, _P, _i, _i, _i, _i, C.c_float, _i, _i]),

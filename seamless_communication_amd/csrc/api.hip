@@ -586,6 +586,29 @@ int sc_op_single_plane(int on) {
     return SC_OK;
 }
 
+// host planning of the packed vocoder pass (no device work)
+int32_t sc_op_voc_pack_plan(const int32_t* h_need, int32_t n, int64_t budget_rows, int32_t* h_group_first, int32_t cap) {
+    try {
+        SC_CHECK(h_need && n > 0 && budget_rows > 0 && (h_group_first || cap == 0) && cap >= 0, "sc_op_voc_pack_plan: bad argument");
+        const std::vector<int> first = sc::plan_packed_groups(std::vector<int>(h_need, h_need + n), budget_rows);
+        for (size_t i = 0; i < first.size() && i < (size_t)cap; ++i) h_group_first[i] = first[i];
+        return (int32_t)first.size() - 1;
+    } catch (const sc::Error& e) {
+        return e.code;
+    }
+}
+int32_t sc_op_voc_tile_first(const int32_t* h_off, int32_t n, int32_t mul, int32_t tile_rows, int32_t* h_first) {
+    try {
+        SC_CHECK(h_off && h_first && n > 0 && mul > 0 && tile_rows > 0, "sc_op_voc_tile_first: bad argument");
+        const std::vector<int> first = sc::packed_tile_first(std::vector<int>(h_off, h_off + n + 1), mul, tile_rows);
+        for (int i = 0; i <= n; ++i) h_first[i] = first[i];
+        return SC_OK;
+    } catch (const sc::Error& e) {
+        return e.code;
+    }
+}
+int32_t sc_op_last_vocoder_packed_groups(sc_model* m) { return m ? m->m.last_vocoder_packed_groups : -1; }
+
 int sc_op_force_general_gemm(int on) {
     sc::g_force_general_gemm.store(on ? 1 : 0);
     return SC_OK;

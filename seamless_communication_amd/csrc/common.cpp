@@ -46,6 +46,8 @@ const Knob knob_table[] = {
     {"SC_VOC_PS", 0, "0: vocoder wide stages on the register-staged convolution"}, {"SC_VOC_MRF", 0, "0: narrow vocoder stages as nine pair launches"},
     {"SC_VOC_GROUPS", 0, "vocoder: length buckets"}, {"SC_VOC_GROUP_OVERHEAD", 0, "vocoder: bucket planning overhead rows"},
     {"SC_VOC_STREAMS", 0, "vocoder: side chains"},
+    {"SC_VOC_PACKED", 0, "0: ragged vocoder batches in length buckets on side chains instead of the packed pass"},
+    {"SC_VOC_PACK_ROWS", 0, "vocoder: unit rows per packed group"},
     {"SC_ENGINE_RG_SMALL", 0, "decode engine: rows per row group, N = 1024 products"},
     // re-read per call
     {"SC_BEAM_COMPACT", 2, "0: beam search keeps finished utterances' slots"},

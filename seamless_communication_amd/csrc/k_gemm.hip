@@ -71,17 +71,24 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     // ---- per-thread A rows (fixed over the K loop) ---------------------------
     const int a_kq = tid & 7;  // which float4 of the 32-wide K slab
     const int a_r = tid >> 3;  // 0..31
-    int a_n[A_IT], a_q[A_IT], a_len[A_IT];
+    int a_row0[A_IT], a_q[A_IT], a_len[A_IT];  // first input row of the item, row inside the item, valid input rows
+    GemmItemCursor cur;
+    if (p.item_off && m0 + a_r < p.M) cur.init(p, m0 + a_r);
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) {
         const int m = m0 + a_r + 32 * i;
-        if (m < p.M) {
+        if (m < p.M && p.item_off) {
+            cur.seek(p, m);
+            a_row0[i] = cur.in_row0(p);
+            a_q[i] = cur.q(m);
+            a_len[i] = cur.t_in(p);
+        } else if (m < p.M) {
             const int n = m / p.rows_per_batch;
-            a_n[i] = n;
+            a_row0[i] = n * p.t_in;
             a_q[i] = m - n * p.rows_per_batch;
             a_len[i] = p.in_lens ? min(p.in_lens[n], p.t_in) : p.t_in;
         } else {
-            a_n[i] = 0;
+            a_row0[i] = 0;
             a_q[i] = 0;
             a_len[i] = -1;  // nothing valid
         }
@@ -104,7 +111,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (tap_ok && src_t >= 0 && src_t < a_len[i]) {
                     v = *reinterpret_cast<const float4*>(
-                        p.A + ((int64_t)a_n[i] * p.t_in + src_t) * p.lda + c0);
+                        p.A + ((int64_t)a_row0[i] + src_t) * p.lda + c0);
                 }
                 a_reg[i] = v;
             }
@@ -120,7 +127,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (tap_ok && src_t >= 0 && src_t < a_len[i]) {
                     v = *reinterpret_cast<const float4*>(
-                        p.A + ((int64_t)a_n[i] * p.t_in + src_t) * p.lda + c0);
+                        p.A + ((int64_t)a_row0[i] + src_t) * p.lda + c0);
                 }
                 a_reg[i] = v;
             }
@@ -136,7 +143,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
                     const int src_t = a_q[i] * p.stride + tap * p.dil - p.pad;
                     float v = 0.f;
                     if (tap < p.taps && src_t >= 0 && src_t < a_len[i]) {
-                        v = p.A[((int64_t)a_n[i] * p.t_in + src_t) * p.lda + c];
+                        v = p.A[((int64_t)a_row0[i] + src_t) * p.lda + c];
                     }
                     e[j] = v;
                 }
@@ -220,7 +227,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
     }
 
     // ---- epilogue: C/D fragment map col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
-    const bool plain_rows = (p.rows_per_batch == p.M) && p.out_mul == 1 && out_off == 0 && p.t_out == p.M;
+    const bool plain_rows = !p.item_off && (p.rows_per_batch == p.M) && p.out_mul == 1 && out_off == 0 && p.t_out == p.M;
+    if (p.item_off && m0 + wm * WM + 4 * (lane >> 5) < p.M) cur.init(p, m0 + wm * WM + 4 * (lane >> 5));
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -230,6 +238,11 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
             int64_t row;
             if (plain_rows) {
                 row = m;
+            } else if (p.item_off) {
+                cur.seek(p, m);
+                const int dst_t = cur.q(m) * p.out_mul + out_off;
+                if (dst_t < 0 || dst_t >= cur.t_out(p)) continue;
+                row = cur.out_row0(p) + dst_t;
             } else {
                 const int n = m / p.rows_per_batch;
                 const int q = m - n * p.rows_per_batch;

@@ -54,6 +54,8 @@ __device__ __forceinline__ void epilogue(const GemmArgs& p, float16_t (&acc)[TM]
         col[j] = n0w + j * 32 + (lane & 31);
         bcol[j] = (p.bias && col[j] < p.N) ? p.bias[col[j]] : 0.f;
     }
+    GemmItemCursor cur;  // packed items: this lane's rows come in ascending order
+    if (p.item_off && m0w + 4 * (lane >> 5) < p.M) cur.init(p, m0w + 4 * (lane >> 5));
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -63,6 +65,11 @@ __device__ __forceinline__ void epilogue(const GemmArgs& p, float16_t (&acc)[TM]
             int64_t row;
             if (plain_rows) {
                 row = m;
+            } else if (p.item_off) {
+                cur.seek(p, m);
+                const int dst_t = cur.q(m) * p.out_mul + out_off;
+                if (dst_t < 0 || dst_t >= cur.t_out(p)) continue;
+                row = cur.out_row0(p) + dst_t;
             } else {
                 const int n = m / p.rows_per_batch;
                 const int q = m - n * p.rows_per_batch;
@@ -105,6 +112,8 @@ __device__ __forceinline__ void epilogue_lds(const GemmArgs& p, float16_t (&acc)
 #pragma unroll
         for (int e = 0; e < 4; ++e) b4[e] = (col + e < p.N) ? p.bias[col + e] : 0.f;
     }
+    GemmItemCursor cur;  // packed items: this lane's rows come in ascending order
+    if (p.item_off && m0w + row_in < p.M) cur.init(p, m0w + row_in);
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -120,6 +129,11 @@ __device__ __forceinline__ void epilogue_lds(const GemmArgs& p, float16_t (&acc)
             int64_t row;
             if (plain_rows) {
                 row = m;
+            } else if (p.item_off) {
+                cur.seek(p, m);
+                const int dst_t = cur.q(m) * p.out_mul + out_off;
+                if (dst_t < 0 || dst_t >= cur.t_out(p)) continue;
+                row = cur.out_row0(p) + dst_t;
             } else {
                 const int n = m / p.rows_per_batch;
                 const int q = m - n * p.rows_per_batch;
@@ -193,10 +207,17 @@ __global__ __launch_bounds__(256) void gemm_fast_kernel(GemmArgs p, int tiles_n,
     const int a_r = tid >> 3;  // 0..31
     const float* a_base[A_IT];  // &A[item n][row 0][a_kq*4]
     int a_t0[A_IT], a_len[A_IT];
+    GemmItemCursor cur;
+    if (p.item_off && m0 + a_r < p.M) cur.init(p, m0 + a_r);
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) {
         const int m = m0 + a_r + 32 * i;
-        if (m < p.M) {
+        if (m < p.M && p.item_off) {
+            cur.seek(p, m);
+            a_base[i] = p.A + (int64_t)cur.in_row0(p) * p.lda + a_kq * 4;
+            a_t0[i] = cur.q(m) * p.stride - p.pad;
+            a_len[i] = cur.t_in(p);
+        } else if (m < p.M) {
             const int n = m / p.rows_per_batch;
             const int q = m - n * p.rows_per_batch;
             a_base[i] = p.A + (int64_t)n * p.t_in * p.lda + a_kq * 4;
@@ -331,7 +352,7 @@ __global__ __launch_bounds__(256) void gemm_fast_kernel(GemmArgs p, int tiles_n,
 #undef SC_COMPUTE_SLAB
 
     // ---- epilogue: C/D fragment map col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5) ------
-    const bool plain_rows = (p.rows_per_batch == p.M) && p.out_mul == 1 && out_off == 0 && p.t_out == p.M;
+    const bool plain_rows = !p.item_off && (p.rows_per_batch == p.M) && p.out_mul == 1 && out_off == 0 && p.t_out == p.M;
     const int m0w = m0 + wm * WM, n0w = n0 + wn * WN;
 #define SC_EPI(ACT)                                                                               \
     do {                                                                                          \
@@ -397,10 +418,17 @@ __global__ __launch_bounds__(256) void gemm_fast2_kernel(GemmArgs p, int tiles_n
     const int a_kq = tid & 7;
     const int a_r = tid >> 3;
     int a_row0[A_IT], a_t0[A_IT], a_len[A_IT];  // first row of the item, first source row, valid rows
+    GemmItemCursor cur;
+    if (p.item_off && m0 + a_r < p.M) cur.init(p, m0 + a_r);
 #pragma unroll
     for (int i = 0; i < A_IT; ++i) {
         const int m = m0 + a_r + 32 * i;
-        if (m < p.M) {
+        if (m < p.M && p.item_off) {
+            cur.seek(p, m);
+            a_row0[i] = cur.in_row0(p);
+            a_t0[i] = cur.q(m) * p.stride - p.pad;
+            a_len[i] = cur.t_in(p);
+        } else if (m < p.M) {
             const int n = m / p.rows_per_batch;
             const int q = m - n * p.rows_per_batch;
             a_row0[i] = n * p.t_in;
@@ -536,7 +564,7 @@ __global__ __launch_bounds__(256) void gemm_fast2_kernel(GemmArgs p, int tiles_n
 #undef SC2_STORE
 #undef SC2_COMPUTE
 
-    const bool plain_rows = (p.rows_per_batch == p.M) && p.out_mul == 1 && out_off == 0 && p.t_out == p.M;
+    const bool plain_rows = !p.item_off && (p.rows_per_batch == p.M) && p.out_mul == 1 && out_off == 0 && p.t_out == p.M;
     const int m0w = m0 + wm * WM, n0w = n0 + wn * WN;
     // epilogue through LDS (the last barrier of the K loop has retired every LDS read of the tile)
     float* ep = reinterpret_cast<float*>(smem_all) + wave * (32 * EP_LD);
@@ -570,9 +598,10 @@ void launch_fast_cfg(const GemmArgs& a, hipStream_t s) {
     const dim3 grid(tiles_per_xcd * 8);
     // prefetch-distance-2 variant (raw buffer loads): both operands must be addressable with 31-bit byte offsets
     static const int env_pf2 = knob::value("SC_GEMM_PF2", GEMM_PF2_DEFAULT);
-    const int64_t a_bytes64 = (int64_t)(a.M / a.rows_per_batch) * a.t_in * a.lda * 4;
+    // packed items: the input holds M - n_items * item_extra rows
+    const int64_t a_bytes64 = (a.item_off ? (int64_t)a.M - (int64_t)a.n_items * a.item_extra : (int64_t)(a.M / a.rows_per_batch) * a.t_in) * a.lda * 4;
     const int64_t w_bytes64 = (int64_t)a.N * a.ldw * 2;
-    if (env_pf2 && a.K % (2 * FBK) == 0 && a.M % a.rows_per_batch == 0 && a_bytes64 < (1ll << 31) && w_bytes64 < (1ll << 31)) {
+    if (env_pf2 && a.K % (2 * FBK) == 0 && (a.item_off || a.M % a.rows_per_batch == 0) && a_bytes64 < (1ll << 31) && w_bytes64 < (1ll << 31)) {
         const float slope = a.in_act == IN_LRELU_01 ? 0.1f : a.in_act == IN_LRELU_001 ? 0.01f : 0.f;
         if (a.in_act == IN_NONE)
             hipLaunchKernelGGL((gemm_fast2_kernel<BM, BN, WGM, WGN, false>), grid, dim3(256), 0, s, a, tiles_n, tiles_mn,

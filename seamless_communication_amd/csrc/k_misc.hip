@@ -389,9 +389,10 @@ __global__ __launch_bounds__(256) void vocoder_embed_kernel(const int* __restric
                                                             const int* __restrict__ lang_idx,
                                                             const __half* __restrict__ spkr, int Sp,
                                                             const int* __restrict__ spkr_idx,
-                                                            float* __restrict__ out) {
+                                                            float* __restrict__ out, const int* __restrict__ item_off, int n_items) {
     const int row = blockIdx.x;
-    const int n = row / T;
+    // packed items: row belongs to the item whose unit rows [item_off[i], item_off[i + 1]) hold it
+    const int n = item_off ? item_search(n_items, row, [&](int i) { return item_off[i]; }) : row / T;
     const int C = Lg + E + Sp;
     const __half* l = lang + (int64_t)lang_idx[n] * Lg;
     const __half* d = dict + (int64_t)units[row] * E;
@@ -407,10 +408,11 @@ __global__ __launch_bounds__(256) void vocoder_embed_kernel(const int* __restric
 }
 void launch_vocoder_embed(const int* units, int nb, int T, const __half* dict, int E, const __half* lang, int Lg,
                           const int* lang_idx, const __half* spkr, int Sp, const int* spkr_idx, float* out,
-                          hipStream_t s) {
-    if (nb * T <= 0) return;
-    hipLaunchKernelGGL(vocoder_embed_kernel, dim3(nb * T), dim3(256), 0, s, units, T, dict, E, lang, Lg, lang_idx, spkr,
-                       Sp, spkr_idx, out);
+                          hipStream_t s, const int* item_off, int rows_total) {
+    const int rows = item_off ? rows_total : nb * T;
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(vocoder_embed_kernel, dim3(rows), dim3(256), 0, s, units, T, dict, E, lang, Lg, lang_idx, spkr,
+                       Sp, spkr_idx, out, item_off, nb);
     SC_LAUNCH_CHECK();
 }
 
@@ -470,14 +472,21 @@ void launch_avg3(const float* a, const float* b, const float* c, float* out, int
 // owns one output sample: K * C fp32 FMAs in tap-major order against the weights in LDS (broadcast reads).
 template <int C, int K>
 __global__ __launch_bounds__(256) void conv_to_mono_kernel(const float* __restrict__ x, const __half* __restrict__ w, const float* __restrict__ bias,
-                                                           float slope, int act, float* __restrict__ y, int T) {
+                                                           float slope, int act, float* __restrict__ y, int T,
+                                                           const int* __restrict__ item_off, int item_mul) {
     constexpr int RS = C + 4, ROWS = 256 + K - 1, VPR = C / 4;
     typedef float f4_t __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) float tile[ROWS * RS];
     __shared__ __attribute__((aligned(16))) float sw[K * C];
     const int tid = threadIdx.x, n = blockIdx.y;
     const int t0 = blockIdx.x * 256;
-    const float* __restrict__ xn = x + (int64_t)n * T * C;
+    int64_t row0 = (int64_t)n * T;
+    if (item_off) {  // packed items: the grid covers the longest one, tiles counted from each item's first row
+        row0 = (int64_t)item_off[n] * item_mul;
+        T = (item_off[n + 1] - item_off[n]) * item_mul;
+        if (t0 >= T) return;
+    }
+    const float* __restrict__ xn = x + row0 * C;
     for (int i = tid; i < ROWS * VPR; i += 256) {
         const int r = i / VPR, c4 = i - r * VPR;
         const int t = t0 - K / 2 + r;
@@ -502,7 +511,7 @@ __global__ __launch_bounds__(256) void conv_to_mono_kernel(const float* __restri
             for (int j = 0; j < 4; ++j) acc = fmaf(xv[j], wv[j], acc);
         }
     acc += bias ? bias[0] : 0.f;
-    y[(int64_t)n * T + t] = act == ACT_TANH ? tanhf(acc) : acc;
+    y[row0 + t] = act == ACT_TANH ? tanhf(acc) : acc;
 }
 
 bool conv_to_mono_supported(int cin, int cout, int k, int stride, int pad, int dil, int act) {
@@ -510,11 +519,44 @@ bool conv_to_mono_supported(int cin, int cout, int k, int stride, int pad, int d
 }
 
 void launch_conv_to_mono(const float* x, const __half* w_packed, const float* bias, int nb, int T, int cin, int k, float in_slope, int act,
-                         float* y, hipStream_t s) {
+                         float* y, hipStream_t s, const int* item_off, int item_mul, int64_t rows_total) {
     SC_CHECK(conv_to_mono_supported(cin, 1, k, 1, (k - 1) / 2, 1, act), "conv_to_mono: unsupported cin=%d k=%d act=%d", cin, k, act);
     if (nb <= 0 || T <= 0) return;
-    prof::Scope scope("conv_to_mono", 2.0 * nb * (double)T * cin * k, 4.0 * nb * (double)T * (cin + 1), s);
-    hipLaunchKernelGGL((conv_to_mono_kernel<16, 7>), dim3(cdiv(T, 256), nb), dim3(256), 0, s, x, w_packed, bias, in_slope, act, y, T);
+    const double rows = item_off ? (double)rows_total : nb * (double)T;
+    prof::Scope scope("conv_to_mono", 2.0 * rows * cin * k, 4.0 * rows * (cin + 1), s);
+    hipLaunchKernelGGL((conv_to_mono_kernel<16, 7>), dim3(cdiv(T, 256), nb), dim3(256), 0, s, x, w_packed, bias, in_slope, act, y, T, item_off,
+                       item_mul);
+    SC_LAUNCH_CHECK();
+}
+
+// row_pos[r] = {position of row r inside its item, rows of that item} for packed items at `mul` rows per unit row: the
+// table the DMA GEMM's packed convolution mode reads (GemmPsArgs::row_pos)
+__global__ void item_row_pos_kernel(const int* __restrict__ item_off, int n_items, int mul, int rows, int2* __restrict__ row_pos) {
+    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += gridDim.x * blockDim.x) {
+        const int n = item_search(n_items, r, [&](int i) { return item_off[i] * mul; });
+        row_pos[r] = make_int2(r - item_off[n] * mul, (item_off[n + 1] - item_off[n]) * mul);
+    }
+}
+void launch_item_row_pos(const int* item_off, int n_items, int mul, int rows, int2* row_pos, hipStream_t s) {
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(item_row_pos_kernel, dim3(grid_for(rows)), dim3(256), 0, s, item_off, n_items, mul, rows, row_pos);
+    SC_LAUNCH_CHECK();
+}
+
+// dst[item_of[i]][0 .. len) = src[item_off[i] * mul ...): the packed vocoder's waveforms into the caller's padded rows
+__global__ void scatter_items_kernel(const float* __restrict__ src, const int* __restrict__ item_off, const int* __restrict__ item_of, int mul,
+                                     int64_t dst_stride, float* __restrict__ dst) {
+    const int i = blockIdx.y;
+    const int len = (item_off[i + 1] - item_off[i]) * mul;
+    const float* __restrict__ s = src + (int64_t)item_off[i] * mul;
+    float* __restrict__ d = dst + (int64_t)item_of[i] * dst_stride;
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < len; t += gridDim.x * blockDim.x) d[t] = s[t];
+}
+void launch_scatter_items(const float* src, const int* item_off, const int* item_of, int n_items, int mul, int longest, int64_t dst_stride,
+                          float* dst, hipStream_t s) {
+    if (n_items <= 0 || longest <= 0) return;
+    hipLaunchKernelGGL(scatter_items_kernel, dim3(std::min(cdiv(longest, 256), 256), n_items), dim3(256), 0, s, src, item_off, item_of, mul,
+                       dst_stride, dst);
     SC_LAUNCH_CHECK();
 }
 

@@ -172,7 +172,8 @@ __global__ __launch_bounds__(256) void resblock_pair_kernel(ResPairArgs p, int t
     constexpr int VPR = C / 4;         // float4 per row
     extern __shared__ __attribute__((aligned(16))) unsigned char rb_smem[];
 
-    const int k = p.k, dil = p.dil, T = p.T;
+    const int k = p.k, dil = p.dil;
+    int T = p.T;
     const int H2 = (k - 1) / 2, H1 = dil * (k - 1) / 2;
     const int TT = RB_M1 - 2 * H2;  // output rows per workgroup
     const int R0 = RB_M1 + 2 * H1;  // staged x rows
@@ -191,9 +192,20 @@ __global__ __launch_bounds__(256) void resblock_pair_kernel(ResPairArgs p, int t
     const int ldb = (PER_TAP ? C : k * C) + 8;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = blockIdx.x / tiles;
-    const int t0 = (blockIdx.x - n * tiles) * TT;
-    const float* __restrict__ xn = p.x + (int64_t)n * T * C;
+    int n, tile;
+    int64_t row0;  // first row of the item
+    if (p.item_off) {
+        n = item_search(p.nb, (int)blockIdx.x, [&](int i) { return p.tile_first[i]; });
+        tile = blockIdx.x - p.tile_first[n];
+        row0 = (int64_t)p.item_off[n] * p.item_mul;
+        T = (p.item_off[n + 1] - p.item_off[n]) * p.item_mul;
+    } else {
+        n = blockIdx.x / tiles;
+        tile = blockIdx.x - n * tiles;
+        row0 = (int64_t)n * T;
+    }
+    const int t0 = tile * TT;
+    const float* __restrict__ xn = p.x + row0 * C;
     const float slope = p.slope;
 
     // ---- 1. x tile (+ halo) -> LeakyReLU -> hi/lo planes --------------------------------------
@@ -294,7 +306,7 @@ __global__ __launch_bounds__(256) void resblock_pair_kernel(ResPairArgs p, int t
             }
         }
         __syncthreads();
-        float* __restrict__ outn = p.out + (int64_t)n * T * C;
+        float* __restrict__ outn = p.out + row0 * C;
         for (int idx = tid; idx < TT * VPR; idx += 256) {
             const int i = idx / VPR, c4 = idx - i * VPR;
             const int t = t0 + i;
@@ -302,7 +314,7 @@ __global__ __launch_bounds__(256) void resblock_pair_kernel(ResPairArgs p, int t
             const int64_t off = (int64_t)t * C + c4 * 4;
             f32x4_t v = *reinterpret_cast<const f32x4_t*>(ep + i * EPS + c4 * 4) + *reinterpret_cast<const f32x4_t*>(xn + off);
             if (p.avg_a) {
-                const int64_t g = (int64_t)n * T * C + off;
+                const int64_t g = row0 * C + off;
                 v = ((*reinterpret_cast<const f32x4_t*>(p.avg_a + g) + *reinterpret_cast<const f32x4_t*>(p.avg_b + g)) + v) / 3.0f;
             }
             *reinterpret_cast<f32x4_t*>(outn + off) = v;
@@ -417,12 +429,13 @@ __device__ __forceinline__ void mrf_put(_Float16* __restrict__ ph, _Float16* __r
 // EDGE: the tile reaches outside [0, T) and rows there must read / be forced to zero; interior tiles skip the tests
 template <int C, bool EDGE, bool SINGLE>
 __device__ __forceinline__ void mrf_tile(const MrfArgs& p, _Float16* __restrict__ ph, _Float16* __restrict__ pl, _Float16* __restrict__ sW1,
-                                         _Float16* __restrict__ sW2, const float* __restrict__ sBias, int n, int t_first, int lane, int wave) {
+                                         _Float16* __restrict__ sW2, const float* __restrict__ sBias, int64_t row0, int T, int t_first, int lane,
+                                         int wave) {
     constexpr int CS = C + 8;
-    const int T = p.T, halo = p.halo;
+    const int halo = p.halo;
     const int TT = MRF_R - 2 * halo;
     const float slope = p.slope;
-    const float* __restrict__ xn = p.x + (int64_t)n * T * C;
+    const float* __restrict__ xn = p.x + row0 * C;  // row0: first row of the item, T: its rows
     const int col = lane & 31;
     const bool colok = col < C;
     const int jbase = 32 * wave + 4 * (lane >> 5);  // tile row of accumulator register r: jbase + (r & 3) + 8 * (r >> 2)
@@ -536,7 +549,7 @@ __device__ __forceinline__ void mrf_tile(const MrfArgs& p, _Float16* __restrict_
     }
 
     if (colok) {
-        float* __restrict__ outb = p.out + (int64_t)n * T * C + (int64_t)(t_first + jbase) * C + col;
+        float* __restrict__ outb = p.out + row0 * C + (int64_t)(t_first + jbase) * C + col;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int j = jbase + (r & 3) + 8 * (r >> 2);
@@ -564,8 +577,18 @@ __global__ __launch_bounds__(MRF_THREADS) void mrf_fused_kernel(MrfArgs p, int t
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = blockIdx.x / tiles;
-    const int tile = blockIdx.x - n * tiles;
+    int n, tile, T = p.T;
+    int64_t row0;
+    if (p.item_off) {
+        n = item_search(p.nb, (int)blockIdx.x, [&](int i) { return p.tile_first[i]; });
+        tile = blockIdx.x - p.tile_first[n];
+        row0 = (int64_t)p.item_off[n] * p.item_mul;
+        T = (p.item_off[n + 1] - p.item_off[n]) * p.item_mul;
+    } else {
+        n = blockIdx.x / tiles;
+        tile = blockIdx.x - n * tiles;
+        row0 = (int64_t)n * T;
+    }
     const int t_first = tile * (MRF_R - 2 * p.halo) - p.halo;  // time of tile row 0
 
     // weights of the first pair, every bias, planes start as zeros (the guard rows stay zero)
@@ -587,8 +610,8 @@ __global__ __launch_bounds__(MRF_THREADS) void mrf_fused_kernel(MrfArgs p, int t
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (t_first < 0 || t_first + MRF_R > p.T) mrf_tile<C, true, SINGLE>(p, ph, pl, sW1, sW2, sBias, n, t_first, lane, wave);
-    else mrf_tile<C, false, SINGLE>(p, ph, pl, sW1, sW2, sBias, n, t_first, lane, wave);
+    if (t_first < 0 || t_first + MRF_R > T) mrf_tile<C, true, SINGLE>(p, ph, pl, sW1, sW2, sBias, row0, T, t_first, lane, wave);
+    else mrf_tile<C, false, SINGLE>(p, ph, pl, sW1, sW2, sBias, row0, T, t_first, lane, wave);
 }
 
 }  // namespace
@@ -607,7 +630,7 @@ void launch_cfg(const ResPairArgs& a, hipStream_t s) {
     }
     const int H2 = (a.k - 1) / 2, H1 = a.dil * (a.k - 1) / 2;
     const int TT = RB_M1 - 2 * H2;
-    const int tiles = cdiv(a.T, TT);
+    const int tiles = a.item_off ? 0 : cdiv(a.T, TT);
     // activations: two planes of R0 rows, or (SINGLE) one plane - but never less than the fp32 epilogue tile that reuses the space
     const size_t act_halfs = SINGLE ? std::max<size_t>((size_t)(RB_M1 + 2 * H1) * (C + 8), (size_t)RB_M1 * (C + 4) * 2)
                                     : (size_t)2 * (RB_M1 + 2 * H1) * (C + 8);
@@ -615,10 +638,10 @@ void launch_cfg(const ResPairArgs& a, hipStream_t s) {
     SC_CHECK(lds <= 120 * 1024, "resblock pair: %zu bytes of LDS (C=%d k=%d dil=%d)", lds, C, a.k, a.dil);
     char name[48];
     snprintf(name, sizeof(name), "resblock_pair_c%d", C);
-    const double rows = (double)a.nb * a.T;
+    const double rows = (double)a.nb * a.T;  // packed items: T is the mean item length (these figures only)
     prof::Scope scope(name, 2.0 * 2.0 * rows * C * (double)C * a.k,
                       4.0 * rows * C * (a.avg_a ? 4.0 : 2.0) + 2.0 * 2.0 * C * (double)C * a.k, s);
-    hipLaunchKernelGGL((resblock_pair_kernel<C, SINGLE>), dim3((unsigned)(a.nb * tiles)), dim3(256), lds, s, a, tiles);
+    hipLaunchKernelGGL((resblock_pair_kernel<C, SINGLE>), dim3((unsigned)(a.item_off ? a.total_tiles : a.nb * tiles)), dim3(256), lds, s, a, tiles);
 }
 
 }  // namespace
@@ -630,7 +653,10 @@ bool resblock_pair_supported(int C, int k, int dil) {
     return RB_M1 - (k - 1) >= 32 && lds <= 120 * 1024;
 }
 
+int resblock_pair_tile_rows(int k) { return RB_M1 - 2 * ((k - 1) / 2); }
+
 void launch_resblock_pair(const ResPairArgs& a, hipStream_t s) {
+    SC_CHECK(!a.item_off || (a.tile_first && a.total_tiles > 0 && a.item_mul > 0), "resblock pair: packed items without a tile table");
     SC_CHECK(resblock_pair_supported(a.C, a.k, a.dil), "resblock pair: unsupported C=%d k=%d dil=%d", a.C, a.k, a.dil);
     SC_CHECK(a.nb > 0 && a.T > 0, "resblock pair: empty problem");
     SC_CHECK(a.ldw1 % 8 == 0 && a.ldw2 % 8 == 0 && a.ldw1 >= (int64_t)a.k * a.C && a.ldw2 >= (int64_t)a.k * a.C,
@@ -682,7 +708,7 @@ void launch_mrf_cfg(MrfArgs a, hipStream_t s) {
     }
     a.halo = mrf_halo(a);
     const int TT = MRF_R - 2 * a.halo;
-    const int tiles = cdiv(a.T, TT);
+    const int tiles = a.item_off ? 0 : cdiv(a.T, TT);
     SC_CHECK((int64_t)a.nb * tiles < (1ll << 31), "mrf: grid too large");
     char name[48];
     snprintf(name, sizeof(name), "mrf_fused_c%d", C);
@@ -693,11 +719,19 @@ void launch_mrf_cfg(MrfArgs a, hipStream_t s) {
         wbytes += 3.0 * 2.0 * 2.0 * C * (double)C * a.k[j];
     }
     prof::Scope scope(name, flops, 4.0 * rows * C * 2.0 + wbytes, s);
-    hipLaunchKernelGGL((mrf_fused_kernel<C, SINGLE>), dim3((unsigned)(a.nb * tiles)), dim3(MRF_THREADS), LDS, s, a, tiles);
+    hipLaunchKernelGGL((mrf_fused_kernel<C, SINGLE>), dim3((unsigned)(a.item_off ? a.total_tiles : a.nb * tiles)), dim3(MRF_THREADS), LDS, s, a, tiles);
 }
 }  // namespace
 
+int mrf_tile_rows(const int* k, const int* dil) {
+    MrfArgs a;
+    for (int j = 0; j < 3; ++j) a.k[j] = k[j];
+    for (int q = 0; q < 9; ++q) a.dil[q] = dil[q];
+    return MRF_R - 2 * mrf_halo(a);
+}
+
 void launch_mrf_fused(const MrfArgs& a, hipStream_t s) {
+    SC_CHECK(!a.item_off || (a.tile_first && a.total_tiles > 0 && a.item_mul > 0), "mrf: packed items without a tile table");
     SC_CHECK(mrf_fused_supported(a.C, a.k, a.dil), "mrf: unsupported C=%d k=(%d,%d,%d)", a.C, a.k[0], a.k[1], a.k[2]);
     SC_CHECK(a.nb > 0 && a.T > 0 && a.x && a.out && a.x != a.out, "mrf: empty problem or in-place call");
     for (int q = 0; q < 9; ++q) {

@@ -48,7 +48,53 @@ struct GemmArgs {
     int phases = 1;
     int split = 1;  // 1: hi+lo split (near-fp32), 0: single fp16 rounding of A
     double algo_flops = 0;  // algorithmic FLOPs of this launch for the profiler (0: 2*M*N*taps*cin*phases)
+    // packed items (the ragged vocoder pass): item i holds unit rows [item_off[i], item_off[i + 1]) and, at this product's
+    // input rate, the input rows [item_off[i] * item_mul, item_off[i + 1] * item_mul) - items back to back, no rows in
+    // between.  Its GEMM rows start at item_off[i] * item_mul + i * item_extra (item_extra = rows_per_batch - t_in of the
+    // uniform form: 1 for the polyphase transposed convolution), its output rows at item_off[i] * item_mul * item_out_mul
+    // (item_out_mul = t_out / t_in of the uniform form).  Replaces rows_per_batch / t_in / t_out, which are unused then;
+    // M = item_off[n_items] * item_mul + n_items * item_extra.  in_lens must be null.
+    const int* item_off = nullptr;  // [n_items + 1] on the device, null: uniform batch
+    int n_items = 0, item_mul = 1, item_extra = 0, item_out_mul = 1;
 };
+
+#if defined(__HIPCC__)
+// largest i in [0, n) with first(i) <= key, for a non-decreasing first() with first(0) <= key
+template <typename F>
+__device__ __forceinline__ int item_search(int n, int key, F first) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (first(mid) <= key) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// Walks the GEMM rows of a packed product in ascending order: seek(m) moves to the item that holds row m (m < M, not
+// below the previous row), one comparison per row and one table read per item boundary.
+struct GemmItemCursor {
+    int n = 0, start = 0, next = 0x7fffffff;  // item, its first GEMM row, the next item's first GEMM row
+    __device__ __forceinline__ static int first(const GemmArgs& p, int i) { return p.item_off[i] * p.item_mul + i * p.item_extra; }
+    __device__ __forceinline__ void init(const GemmArgs& p, int m) {
+        n = item_search(p.n_items, m, [&](int i) { return first(p, i); });
+        start = first(p, n);
+        next = first(p, n + 1);
+    }
+    __device__ __forceinline__ void seek(const GemmArgs& p, int m) {
+        while (m >= next) {
+            ++n;
+            start = next;
+            next = first(p, n + 1);
+        }
+    }
+    __device__ __forceinline__ int q(int m) const { return m - start; }                        // row inside the item
+    __device__ __forceinline__ int in_row0(const GemmArgs& p) const { return start - n * p.item_extra; }
+    __device__ __forceinline__ int t_in(const GemmArgs& p) const { return next - start - p.item_extra; }
+    __device__ __forceinline__ int t_out(const GemmArgs& p) const { return t_in(p) * p.item_out_mul; }
+    __device__ __forceinline__ int64_t out_row0(const GemmArgs& p) const { return (int64_t)in_row0(p) * p.item_out_mul; }
+};
+#endif
 
 void launch_gemm(const GemmArgs& a, hipStream_t s);
 // k_gemm2.hip: double-buffered, XCD-aware fast path for split products with cin % 32 == 0 (same bits)
@@ -118,8 +164,15 @@ struct ResPairArgs {
     const float* avg_a = nullptr;
     const float* avg_b = nullptr;
     int single = 0;  // the hi fp16 plane of the activations only: one matrix instruction per fragment, no lo plane in LDS (the vocoder's default)
+    // packed items (see GemmArgs::item_off): nb items, item i holds the rows [item_off[i] * item_mul, item_off[i + 1] * item_mul)
+    // of x / out (T: the mean item length, for the profiler's figures only); a workgroup owns a tile of ONE item, tiles counted from the item's first row, and
+    // tile_first[i] (nb + 1 entries, resblock_tile_first / mrf_tile_first) is the first workgroup of item i
+    const int* item_off = nullptr;
+    const int* tile_first = nullptr;
+    int item_mul = 1, total_tiles = 0;
 };
 bool resblock_pair_supported(int C, int k, int dil);
+int resblock_pair_tile_rows(int k);  // output rows a workgroup owns
 void launch_resblock_pair(const ResPairArgs& a, hipStream_t s);
 
 // k_resblock.hip: the three ResBlocks (kernel sizes k[0..2], three dilation pairs each) of a narrow stage and their
@@ -140,8 +193,15 @@ struct MrfArgs {
     const float* b1[9] = {};
     const float* b2[9] = {};
     int single = 0;  // the hi fp16 plane of the activations only: one matrix instruction per fragment, no lo plane in LDS (the vocoder's default)
+    // packed items (see GemmArgs::item_off): nb items, item i holds the rows [item_off[i] * item_mul, item_off[i + 1] * item_mul)
+    // of x / out (T: the mean item length, for the profiler's figures only); a workgroup owns a tile of ONE item, tiles counted from the item's first row, and
+    // tile_first[i] (nb + 1 entries, resblock_tile_first / mrf_tile_first) is the first workgroup of item i
+    const int* item_off = nullptr;
+    const int* tile_first = nullptr;
+    int item_mul = 1, total_tiles = 0;
 };
 bool mrf_fused_supported(int C, const int* k, const int* dil);
+int mrf_tile_rows(const int* k, const int* dil);  // output rows a workgroup owns
 void launch_mrf_fused(const MrfArgs& a, hipStream_t s);
 
 // out[m][n] = alpha*act(sum_k x[m][k]*W[n][k] + bias[n]) + res[m][n], exact fp32 FMA, M <= 8.
@@ -579,12 +639,19 @@ void launch_durations(const float* h /*[rows][H]*/, int64_t ld, const float* w, 
                       int min_dur, int* durations, hipStream_t s);
 void launch_vocoder_embed(const int* units, int nb, int T, const __half* dict, int E,
                           const __half* lang, int Lg, const int* lang_idx, const __half* spkr, int Sp,
-                          const int* spkr_idx, float* out /*[nb*T][Lg+E+Sp]*/, hipStream_t s);
+                          const int* spkr_idx, float* out /*[nb*T][Lg+E+Sp]*/, hipStream_t s,
+                          const int* item_off = nullptr /*packed items: [nb + 1] unit-row offsets, T unused*/, int rows_total = 0);
 void launch_avg3(const float* a, const float* b, const float* c, float* out, int64_t n, hipStream_t s);
 // Conv1d(cin -> 1, k taps, 'same') with LeakyReLU(in_slope) on the input and `act` on the output (k_misc.hip: the vocoder's conv_post)
 bool conv_to_mono_supported(int cin, int cout, int k, int stride, int pad, int dil, int act);
 void launch_conv_to_mono(const float* x, const __half* w_packed, const float* bias, int nb, int T, int cin, int k, float in_slope, int act,
-                         float* y, hipStream_t s);
+                         float* y, hipStream_t s, const int* item_off = nullptr /*packed items: T = the longest item's rows*/,
+                         int item_mul = 1, int64_t rows_total = 0);
+// packed items (GemmArgs::item_off) at `mul` rows per unit row: the {position, item length} table of GemmPsArgs::row_pos
+void launch_item_row_pos(const int* item_off, int n_items, int mul, int rows, int2* row_pos, hipStream_t s);
+// dst[item_of[i] * dst_stride + t] = src[item_off[i] * mul + t] for t < (item_off[i + 1] - item_off[i]) * mul
+void launch_scatter_items(const float* src, const int* item_off, const int* item_of, int n_items, int mul, int longest, int64_t dst_stride,
+                          float* dst, hipStream_t s);
 void launch_fill_i32(int* p, int v, int n, hipStream_t s);
 void launch_add_i32(int* p, int v, hipStream_t s);
 

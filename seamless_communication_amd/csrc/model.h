@@ -1,6 +1,7 @@
 // Host-side runtime of libseamless_hip: weights resident in HBM, a caching
 // device allocator for activations, and the per-stage launch sequences.
 #pragma once
+#include <algorithm>
 #include <map>
 #include <functional>
 #include <memory>
@@ -273,6 +274,7 @@ struct Model : ModelData {
     int last_n = 0, last_su = 0, last_sc = 0;
     int64_t last_padded_unit_rows = 0;  // unit rows the NAR decoder really computed (length buckets), vs last_n * last_su
     int64_t last_vocoder_unit_rows = 0; // unit frames the vocoder really computed in the last sc_vocode* call
+    int last_vocoder_packed_groups = 0; // groups of the packed pass in the last sc_vocode* call; 0: padded batch / length buckets
 
     std::unique_ptr<MmaState> mma;  // buffers come from `pool`: released before it (see ~Model)
 
@@ -386,8 +388,37 @@ inline void project_cross_kv(Model& m, const float* d_enc, const Linear& L, floa
 }
 void layernorm(Model& m, const float* x, const LNorm& L, float* y, int rows, int act = ACT_NONE,
                const int* lens = nullptr, int t_per_batch = 1);
+// Packed items of a ragged batch (the vocoder's packed pass): item i holds the unit rows [off[i], off[i + 1]) of every
+// buffer, items back to back with no rows in between; at a stage that runs `mul` rows per unit row, the rows
+// [off[i] * mul, off[i + 1] * mul).  Kernels take the device copy of `off` (GemmArgs::item_off and its kin).
+struct PackedItems {
+    std::vector<int> off;        // [n + 1], off[0] = 0
+    const int* d_off = nullptr;  // the same on the device
+    int n = 0;
+    // tile tables of the fused narrow-stage kernels (packed_tile_first), [n + 1] each, behind one another: table 4 * stage + j
+    // for the pair kernel at ResBlock j's kernel size (j < 3), 4 * stage + 3 for the multi-receptive-field kernel
+    std::vector<int> tabs;
+    const int* d_tabs = nullptr;
+    const int* d_tab(int idx) const { return d_tabs + (size_t)idx * (n + 1); }
+    int tab_total(int idx) const { return tabs[(size_t)idx * (n + 1) + n]; }
+    int rows() const { return off.empty() ? 0 : off.back(); }
+    int longest() const {
+        int l = 0;
+        for (int i = 0; i < n; ++i) l = std::max(l, off[i + 1] - off[i]);
+        return l;
+    }
+};
+// Host-side planning of the packed vocoder pass (plain C++; sc_op_voc_pack_plan tests it without a device): items in their
+// given order, cut into consecutive groups of at most `budget_rows` unit rows each (an item longer than the budget is a
+// group of its own).  Returns the first item of every group, and the number of items behind them.
+std::vector<int> plan_packed_groups(const std::vector<int>& need, int64_t budget_rows);
+// first workgroup of every item ([n + 1]) when item i takes ceil(len_i * mul / tile_rows) tiles counted from its first row
+std::vector<int> packed_tile_first(const std::vector<int>& off, int mul, int tile_rows);
+
+// pk != null (stride 1, 'same' padding, no d_in_lens): packed items at `mul` rows per unit row; nb / t_in are unused
 void conv1d(Model& m, const float* x, const Conv& c, const float* res, float* y, int nb, int t_in, int stride, int pad,
-            int dil, const int* d_in_lens, int in_act, int act);
-void conv_transpose1d(Model& m, const float* x, const ConvT& c, float* y, int nb, int t_in, int in_act);
+            int dil, const int* d_in_lens, int in_act, int act, const PackedItems* pk = nullptr, int mul = 1);
+void conv_transpose1d(Model& m, const float* x, const ConvT& c, float* y, int nb, int t_in, int in_act, const PackedItems* pk = nullptr,
+                      int mul = 1);
 
 }  // namespace sc

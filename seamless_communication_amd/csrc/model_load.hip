@@ -704,14 +704,21 @@ void layernorm(Model& m, const float* x, const LNorm& L, float* y, int rows, int
 }
 
 void conv1d(Model& m, const float* x, const Conv& c, const float* res, float* y, int nb, int t_in, int stride, int pad,
-            int dil, const int* d_in_lens, int in_act, int act) {
+            int dil, const int* d_in_lens, int in_act, int act, const PackedItems* pk, int mul) {
+    if (pk) {
+        SC_CHECK(stride == 1 && 2 * pad == dil * (c.k - 1) && !d_in_lens && mul >= 1 && (int64_t)pk->rows() * mul < (1ll << 31),
+                 "conv1d: packed items need stride 1 and 'same' padding");
+        nb = pk->n;
+        t_in = pk->longest() * mul;
+    }
     const int t_out = (t_in + 2 * pad - dil * (c.k - 1) - 1) / stride + 1;
     if (nb <= 0 || t_out <= 0) return;
     // one output channel (the vocoder's conv_post): a direct fp32 kernel instead of an MFMA tile with one live column
     if (!res && !d_in_lens && g_force_general_gemm.load(std::memory_order_relaxed) == 0 &&
         conv_to_mono_supported(c.cin, c.cout, c.k, stride, pad, dil, act)) {
         const float slope = in_act == IN_LRELU_01 ? 0.1f : in_act == IN_LRELU_001 ? 0.01f : 1.0f;
-        launch_conv_to_mono(x, c.w, c.b, nb, t_in, c.cin, c.k, slope, act, y, m.stream);
+        launch_conv_to_mono(x, c.w, c.b, nb, t_in, c.cin, c.k, slope, act, y, m.stream, pk ? pk->d_off : nullptr, mul,
+                            pk ? (int64_t)pk->rows() * mul : 0);
         return;
     }
     GemmArgs a;
@@ -738,6 +745,12 @@ void conv1d(Model& m, const float* x, const Conv& c, const float* res, float* y,
     a.in_lens = d_in_lens;
     a.in_act = in_act;
     a.act = act;
+    if (pk) {
+        a.M = pk->rows() * mul;
+        a.item_off = pk->d_off;
+        a.n_items = pk->n;
+        a.item_mul = mul;
+    }
     launch_gemm(a, m.stream);
 }
 
@@ -778,7 +791,12 @@ void conv1d_presplit(Model& m, const __half* xh, const __half* xl, const Conv& c
 
 // ConvTranspose1d(k, stride s, padding (k-s)/2) as s polyphase convolutions:
 // out[q*s + r - p] = sum_j x[q - j] . w[:, :, r + s*j]   
-void conv_transpose1d(Model& m, const float* x, const ConvT& c, float* y, int nb, int t_in, int in_act) {
+void conv_transpose1d(Model& m, const float* x, const ConvT& c, float* y, int nb, int t_in, int in_act, const PackedItems* pk, int mul) {
+    if (pk) {
+        SC_CHECK(mul >= 1 && ((int64_t)pk->rows() * mul + pk->n) * c.stride < (1ll << 31), "conv_transpose1d: packed items too long");
+        nb = pk->n;
+        t_in = pk->longest() * mul;
+    }
     if (nb <= 0 || t_in <= 0) return;
     GemmArgs a;
     a.A = x;
@@ -806,6 +824,15 @@ void conv_transpose1d(Model& m, const float* x, const ConvT& c, float* y, int nb
     a.phases = c.stride;
     a.in_act = in_act;
     a.algo_flops = 2.0 * nb * (double)t_in * c.cin * c.cout * c.k;
+    if (pk) {
+        a.M = pk->rows() * mul + pk->n;
+        a.item_off = pk->d_off;
+        a.n_items = pk->n;
+        a.item_mul = mul;
+        a.item_extra = 1;
+        a.item_out_mul = c.stride;
+        a.algo_flops = 2.0 * pk->rows() * (double)mul * c.cin * c.cout * c.k;
+    }
     launch_gemm(a, m.stream);
 }
 

@@ -499,18 +499,26 @@ void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const i
 
 namespace {
 
-// Generator.forward on one padded batch [n][T] of unit ids already on the device -> d_wav [n][T * hop]
-void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_spkr, int n, int T, float* d_wav) {
+// Generator.forward on one padded batch [n][T] of unit ids already on the device -> d_wav [n][T * hop].
+// pk != null: packed items instead (model.h: PackedItems) - d_units holds pk->rows() unit ids, items back to back, d_wav
+// receives pk->rows() * hop samples in the same order, T is unused.  Every kernel then takes an item's first row and length
+// from the item table: a convolution sees zeros beyond an item's own two ends and a fused kernel's tiles are counted from the
+// item's first row, so an item's arithmetic is what it is as a row of a padded batch of its own length.
+void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_spkr, int n, int T, float* d_wav,
+                  const PackedItems* pk = nullptr) {
     const sc_config& c = m.cfg;
     const int E = c.voc_embedding_dim, Lg = c.voc_lang_embedding_dim, Sp = c.voc_spkr_embedding_dim;
     int ch = c.voc_upsample_initial_channel;
     int t = T;
+    int rate = 1;                                                          // rows per unit row at the current stage
+    const size_t rows0 = pk ? (size_t)pk->rows() : (size_t)n * T;  // unit rows in all
     Buf<float> x;
     {
-        Buf<float> in(m.pp(), (size_t)n * T * (E + Lg + Sp));
-        launch_vocoder_embed(d_units, n, T, m.voc_dict, E, m.voc_lang, Lg, d_lang, m.voc_spkr, Sp, d_spkr, in, m.stream);
-        x = Buf<float>(m.pp(), (size_t)n * T * ch);
-        conv1d(m, in, m.voc_pre, nullptr, x, n, T, 1, 3, 1, nullptr, IN_NONE, ACT_NONE);
+        Buf<float> in(m.pp(), rows0 * (E + Lg + Sp));
+        launch_vocoder_embed(d_units, n, T, m.voc_dict, E, m.voc_lang, Lg, d_lang, m.voc_spkr, Sp, d_spkr, in, m.stream, pk ? pk->d_off : nullptr,
+                             (int)rows0);
+        x = Buf<float>(m.pp(), rows0 * ch);
+        conv1d(m, in, m.voc_pre, nullptr, x, n, T, 1, 3, 1, nullptr, IN_NONE, ACT_NONE, pk, 1);
     }
     const int nk = c.voc_num_resblock_kernels;
     SC_CHECK(nk == 3, "sc_vocode: %d resblock kernels (only 3 is implemented)", nk);
@@ -526,11 +534,18 @@ void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_
     for (int i = 0; i < c.voc_num_upsamples; ++i) {
         const ConvT& up = m.voc_ups[i];
         const int t2 = t * up.stride;
+        const int rate2 = rate * up.stride;
         ch = up.cout;
-        const size_t sz = (size_t)n * t2 * ch;
-        Buf<float> y(m.pp(), sz), tmp(m.pp(), sz), ra(m.pp(), sz), rb(m.pp(), sz);
-        Buf<float> rout[3] = {Buf<float>(m.pp(), sz), Buf<float>(m.pp(), sz), Buf<float>(m.pp(), sz)};
-        conv_transpose1d(m, x, up, y, n, t, IN_LRELU_01);
+        const size_t rows = rows0 * rate2;  // rows of this stage in all
+        const size_t sz = rows * ch;
+        // scratch of the stage, allocated by the path that uses it (the fused narrow-stage kernel needs y and x only; a packed
+        // pass holds the whole batch at once: eight buffers of the widest kind would be 6 GB per worker)
+        Buf<float> y(m.pp(), sz), tmp, ra, rb, rout[3];
+        const auto need = [&](Buf<float>& b) -> float* {
+            if (!b.get()) b = Buf<float>(m.pp(), sz);
+            return b.get();
+        };
+        conv_transpose1d(m, x, up, y, n, t, IN_LRELU_01, pk, rate);
         // narrow stages: each dilation pair is one kernel with the intermediate in LDS, and the last pair of
         // the third ResBlock also applies the average over the three ResBlocks (k_resblock.hip)
         bool fused_avg = false;
@@ -541,7 +556,7 @@ void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_
         // the fp32 residual stream.  SC_VOC_PS=0: the register-staged kernel (k_gemm2.hip) as before.
         static const bool voc_ps = knob::value("SC_VOC_PS", 1) != 0;
         bool wide_ps = voc_ps && g_force_general_gemm.load(std::memory_order_relaxed) == 0 && ch >= 128 && ch % 32 == 0 &&
-                       (int64_t)n * t2 * ch * 2 < (1ll << 31);
+                       (int64_t)sz * 2 < (1ll << 31);
         for (int j = 0; j < nk && wide_ps; ++j) {
             const ResBlock& r = m.voc_res[i * nk + j];
             for (size_t d = 0; d < r.dil.size(); ++d)
@@ -559,6 +574,14 @@ void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_
             __half* pt_l = one_plane ? nullptr : py_l + sz;
             __half* pn_l = one_plane ? nullptr : pt_l + sz;
             launch_lrelu_split_f32(y, 0.1f, py_h, py_l, (int64_t)sz, m.stream);
+            // packed items: the {position, item length} of every row at this stage's rate, made on the device from the item table
+            Buf<int2> row_pos;
+            if (pk) {
+                row_pos = Buf<int2>(m.pp(), rows);
+                launch_item_row_pos(pk->d_off, pk->n, rate2, (int)rows, row_pos.get(), m.stream);
+            }
+            for (int j = 0; j < nk; ++j) need(rout[j]);
+            need(ra), need(rb);
             for (int j = 0; j < nk; ++j) {
                 const ResBlock& r = m.voc_res[i * nk + j];
                 const float* cur = y;
@@ -570,9 +593,9 @@ void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_
                     float* dst = last ? rout[j].get() : ((d & 1) ? rb.get() : ra.get());
                     const int split = one_plane ? 0 : 1;
                     conv1d_presplit(m, ch_, cl_, r.convs1[d], nullptr, nullptr, pt_h, pt_l, n, t2, (k * r.dil[d] - r.dil[d]) / 2, r.dil[d], nullptr,
-                                    ACT_NONE, 0, nullptr, 0.1f, split);
+                                    ACT_NONE, (int)rows, row_pos.get(), 0.1f, split);
                     conv1d_presplit(m, pt_h, pt_l, r.convs2[d], cur, dst, last ? nullptr : pn_h, last ? nullptr : pn_l, n, t2, (k2 - 1) / 2, 1,
-                                    nullptr, ACT_NONE, 0, nullptr, 0.1f, split);
+                                    nullptr, ACT_NONE, (int)rows, row_pos.get(), 0.1f, split);
                     cur = dst;
                     ch_ = pn_h;
                     cl_ = pn_l;
@@ -580,6 +603,7 @@ void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_
             }
             launch_avg3(rout[0], rout[1], rout[2], x, (int64_t)sz, m.stream);
             t = t2;
+            rate = rate2;
             continue;
         }
         // the two narrowest stages (C = 32, 16): the three ResBlocks and their average in one kernel, the residual
@@ -605,12 +629,19 @@ void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_
                 a.x = y.get();
                 a.out = x.get();
                 a.nb = n;
-                a.T = t2;
+                a.T = pk ? (int)((rows + n - 1) / n) : t2;
                 a.C = ch;
                 a.slope = 0.1f;
                 a.single = (voc_single & 4) ? 1 : 0;
+                if (pk) {
+                    a.item_off = pk->d_off;
+                    a.item_mul = rate2;
+                    a.tile_first = pk->d_tab(4 * i + 3);
+                    a.total_tiles = pk->tab_total(4 * i + 3);
+                }
                 launch_mrf_fused(a, m.stream);
                 t = t2;
+                rate = rate2;
                 continue;
             }
         }
@@ -620,10 +651,13 @@ void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_
             const int nd = (int)r.dil.size();
             for (int d = 0; d < nd; ++d) {
                 const int k = r.convs1[d].k;
-                float* dst = (d == nd - 1) ? rout[j].get() : ((d & 1) ? rb.get() : ra.get());
                 const bool fuse = g_force_general_gemm.load(std::memory_order_relaxed) == 0 && r.convs2[d].k == k &&
                                   r.convs1[d].cin == ch && r.convs1[d].cout == ch && r.convs2[d].cin == ch &&
                                   r.convs2[d].cout == ch && resblock_pair_supported(ch, k, r.dil[d]);
+                // packed items run on the fused pair kernel only (run_vocode checks the geometry before it packs)
+                SC_CHECK(fuse || !pk, "sc_vocode: packed items on a ResBlock shape the pair kernel does not take");
+                const bool avg_here = fuse && j == nk - 1 && d == nd - 1;
+                float* dst = avg_here ? x.get() : (d == nd - 1) ? need(rout[j]) : ((d & 1) ? need(rb) : need(ra));
                 if (fuse) {
                     ResPairArgs a;
                     a.x = cur;
@@ -634,22 +668,27 @@ void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_
                     a.ldw2 = r.convs2[d].kpad;
                     a.b2 = r.convs2[d].b;
                     a.nb = n;
-                    a.T = t2;
+                    a.T = pk ? (int)((rows + n - 1) / n) : t2;
                     a.C = ch;
                     a.k = k;
                     a.dil = r.dil[d];
                     a.slope = 0.1f;
                     a.single = (voc_single & 4) ? 1 : 0;
-                    if (j == nk - 1 && d == nd - 1) {
+                    if (pk) {
+                        a.item_off = pk->d_off;
+                        a.item_mul = rate2;
+                        a.tile_first = pk->d_tab(4 * i + j);
+                        a.total_tiles = pk->tab_total(4 * i + j);
+                    }
+                    if (avg_here) {
                         a.avg_a = rout[0];
                         a.avg_b = rout[1];
-                        dst = x.get();
                         fused_avg = true;
                     }
                     a.out = dst;
                     launch_resblock_pair(a, m.stream);
                 } else {
-                    conv1d(m, cur, r.convs1[d], nullptr, tmp, n, t2, 1, (k * r.dil[d] - r.dil[d]) / 2, r.dil[d], nullptr,
+                    conv1d(m, cur, r.convs1[d], nullptr, need(tmp), n, t2, 1, (k * r.dil[d] - r.dil[d]) / 2, r.dil[d], nullptr,
                            IN_LRELU_01, ACT_NONE);
                     conv1d(m, tmp, r.convs2[d], cur, dst, n, t2, 1, (k - 1) / 2, 1, nullptr, IN_LRELU_01, ACT_NONE);
                 }
@@ -658,9 +697,10 @@ void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_
         }
         if (!fused_avg) launch_avg3(rout[0], rout[1], rout[2], x, (int64_t)sz, m.stream);
         t = t2;
+        rate = rate2;
     }
     // F.leaky_relu default slope 0.01, conv_post, tanh (hifigan.py:192-194)
-    conv1d(m, x, m.voc_post, nullptr, d_wav, n, t, 1, 3, 1, nullptr, IN_LRELU_001, ACT_TANH);
+    conv1d(m, x, m.voc_post, nullptr, d_wav, n, t, 1, 3, 1, nullptr, IN_LRELU_001, ACT_TANH, pk, rate);
 }
 
 // Unit frames of context a kept output sample can depend on, per side: conv_pre (3) + per stage the transposed
@@ -687,7 +727,109 @@ int vocoder_halo_units(const Model& m) {
     return (int)halo + 8;
 }
 
+// The packed pass's geometry check and index bounds.  Returns the largest number of unit rows one packed group may hold
+// (every stage's buffers, tables and grids stay below 2^31 elements / bytes where a kernel addresses them with 32 bits),
+// 0 when some stage would run on a kernel that does not take packed items (vocode_batch's choice of path per stage,
+// restated: DMA GEMM for C >= 128, the fused multi-receptive-field kernel, or the fused pair kernel).
+int64_t vocoder_packed_row_cap(const Model& m, int hop) {
+    const sc_config& c = m.cfg;
+    const int nk = c.voc_num_resblock_kernels;
+    if (nk != 3) return 0;
+    static const bool voc_ps = knob::value("SC_VOC_PS", 1) != 0;
+    static const bool voc_mrf = knob::value("SC_VOC_MRF", 1) != 0;
+    int64_t per_row = (int64_t)hop * 4;  // bytes / elements per unit row that must stay below 2^31
+    per_row = std::max<int64_t>(per_row, (int64_t)(c.voc_embedding_dim + c.voc_lang_embedding_dim + c.voc_spkr_embedding_dim) * 4);
+    int rate = 1;
+    for (int i = 0; i < c.voc_num_upsamples; ++i) {
+        const ConvT& up = m.voc_ups[i];
+        rate *= up.stride;
+        const int ch = up.cout;
+        per_row = std::max<int64_t>(per_row, (int64_t)(rate + 1) * std::max(ch, 2) * 4);  // fp32 rows, planes, {pos, len}, the + 1 rows of ConvTranspose
+        bool same = true, pairs = true;
+        for (int j = 0; j < nk; ++j) {
+            const ResBlock& r = m.voc_res[i * nk + j];
+            for (size_t d = 0; d < r.dil.size(); ++d) {
+                const Conv &c1 = r.convs1[d], &c2 = r.convs2[d];
+                same = same && c1.cin == ch && c1.cout == ch && c2.cin == ch && c2.cout == ch && (c1.k & 1) && (c2.k & 1);
+                pairs = pairs && c2.k == c1.k && resblock_pair_supported(ch, c1.k, r.dil[d]);
+            }
+        }
+        if (!same) return 0;
+        bool wide = voc_ps && ch >= 128 && ch % 32 == 0;
+        for (int j = 0; j < nk && wide; ++j) {
+            const ResBlock& r = m.voc_res[i * nk + j];
+            for (size_t d = 0; d < r.dil.size(); ++d) wide = wide && r.convs1[d].kpad == ch * r.convs1[d].k && r.convs2[d].kpad == ch * r.convs2[d].k;
+        }
+        if (wide) continue;
+        int k[3], dil[9];
+        bool mrf = voc_mrf;
+        for (int j = 0; j < nk && mrf; ++j) {
+            const ResBlock& r = m.voc_res[i * nk + j];
+            mrf = r.dil.size() == 3;
+            for (int d = 0; d < 3 && mrf; ++d) {
+                mrf = r.convs1[d].k == r.convs1[0].k && r.convs2[d].k == r.convs1[d].k;
+                dil[j * 3 + d] = r.dil[d];
+            }
+            if (mrf) k[j] = r.convs1[0].k;
+        }
+        if (mrf && mrf_fused_supported(ch, k, dil)) continue;
+        if (!pairs) return 0;
+    }
+    return ((1ll << 31) - 1) / per_row - c.voc_num_upsamples - 64;
+}
+
+// tile tables of the fused narrow-stage kernels for one packed group (PackedItems::tabs)
+void vocoder_tile_tables(const Model& m, PackedItems& pk) {
+    const sc_config& c = m.cfg;
+    const int nk = c.voc_num_resblock_kernels;
+    pk.tabs.assign((size_t)4 * c.voc_num_upsamples * (pk.n + 1), 0);
+    int rate = 1;
+    for (int i = 0; i < c.voc_num_upsamples; ++i) {
+        rate *= m.voc_ups[i].stride;
+        int k[3] = {1, 1, 1}, dil[9] = {1, 1, 1, 1, 1, 1, 1, 1, 1};
+        bool mrf = nk == 3;
+        for (int j = 0; j < nk && j < 3; ++j) {
+            const ResBlock& r = m.voc_res[i * nk + j];
+            if (r.convs1.empty()) continue;
+            k[j] = r.convs1[0].k;
+            mrf = mrf && r.dil.size() == 3;
+            for (size_t d = 0; d < r.dil.size() && d < 3; ++d) dil[j * 3 + d] = r.dil[d];
+            if ((k[j] & 1) == 0 || resblock_pair_tile_rows(k[j]) < 1) continue;
+            const std::vector<int> t = packed_tile_first(pk.off, rate, resblock_pair_tile_rows(k[j]));
+            std::copy(t.begin(), t.end(), pk.tabs.begin() + (size_t)(4 * i + j) * (pk.n + 1));
+        }
+        if (mrf && mrf_fused_supported(m.voc_ups[i].cout, k, dil)) {
+            const std::vector<int> t = packed_tile_first(pk.off, rate, mrf_tile_rows(k, dil));
+            std::copy(t.begin(), t.end(), pk.tabs.begin() + (size_t)(4 * i + 3) * (pk.n + 1));
+        }
+    }
+}
+
 }  // namespace
+
+std::vector<int> plan_packed_groups(const std::vector<int>& need, int64_t budget_rows) {
+    std::vector<int> first;
+    int64_t rows = 0;
+    for (int i = 0; i < (int)need.size(); ++i) {
+        if (i == 0 || rows + need[i] > budget_rows) {
+            first.push_back(i);
+            rows = 0;
+        }
+        rows += need[i];
+    }
+    first.push_back((int)need.size());
+    return first;
+}
+
+std::vector<int> packed_tile_first(const std::vector<int>& off, int mul, int tile_rows) {
+    std::vector<int> first(off.size(), 0);
+    for (size_t i = 0; i + 1 < off.size(); ++i) {
+        const int64_t tiles = ((int64_t)(off[i + 1] - off[i]) * mul + tile_rows - 1) / tile_rows;
+        SC_CHECK(first[i] + tiles < (1ll << 31), "packed items: %lld tiles", (long long)(first[i] + tiles));
+        first[i + 1] = first[i] + (int)tiles;
+    }
+    return first;
+}
 
 // rows of fp16 embeddings as fp32: out[r][:] = table[idx[r]][:]
 __global__ void embed_rows_f16_kernel(const int* __restrict__ idx, const __half* __restrict__ table, int E, float* __restrict__ out) {
@@ -727,6 +869,7 @@ void run_vocode(Model& m, const int32_t* h_units, int n, int T, const int32_t* h
     const sc_config& c = m.cfg;
     SC_CHECK(c.has_vocoder, "sc_vocode: the model was loaded without a vocoder");
     prof::set_tag("voc");
+    m.last_vocoder_packed_groups = 0;
     SC_CHECK(n > 0 && T > 0, "sc_vocode: empty batch");
     for (int i = 0; i < n; ++i) {
         SC_CHECK(h_lang[i] >= 0 && h_lang[i] < c.voc_num_langs, "sc_vocode: lang index %d out of range", h_lang[i]);
@@ -750,7 +893,7 @@ void run_vocode(Model& m, const int32_t* h_units, int n, int T, const int32_t* h
         SC_HIP(hipStreamSynchronize(m.stream));
         return;
     }
-    // ---- ragged: one pass per length bucket --------------------------------------------------------------------
+    // ---- ragged ------------------------------------------------------------------------------------------------
     // The reference vocodes the padded batch (pads are unit id 1, translator.py:407) and keeps the first
     // int(T_wav * len(speech_units) / T) samples of each row (:411-419).  A kept sample depends on a bounded window of
     // unit frames, so row i is computed on min(T, len_i + halo) frames: either the padded row itself, or a row whose
@@ -758,6 +901,64 @@ void run_vocode(Model& m, const int32_t* h_units, int n, int T, const int32_t* h
     const int halo = vocoder_halo_units(m);
     std::vector<int> need(n);
     for (int i = 0; i < n; ++i) need[i] = std::min(T, h_unit_lens[i] + halo);
+    // ---- packed pass (default): every item on exactly need[i] frames, items back to back, no rows in between ---------
+    // One chain of ~150 launches over all items instead of one per length bucket: the 256- / 128-channel ResBlock
+    // convolutions see all rows at once (256 x 256 tiles of the DMA GEMM at C = 256 where a bucket stayed on 128 x 128 /
+    // 64 x 64), nothing is padded up to a bucket's longest item, and the side chains are not needed.  Every kernel takes the
+    // items' first rows and lengths from one small table (vocode_batch).  The items go in groups of at most
+    // SC_VOC_PACK_ROWS unit rows (the activations of a whole group are alive at once: ~125 MB per 1 000 unit rows in the
+    // 64-channel stage), one group after the other on the handle's stream; the default holds the 64 x 10 s benchmark batch
+    // (~36 k rows) in one group.  SC_VOC_PACKED=0, or a geometry the packed kernels do not take: the length buckets below.
+    {
+        static const bool want_packed = knob::value("SC_VOC_PACKED", 1) != 0;
+        static const int pack_rows = std::max(1, knob::value("SC_VOC_PACK_ROWS", 49152));
+        const int64_t cap = vocoder_packed_row_cap(m, hop);
+        const int64_t budget = std::min<int64_t>(pack_rows, cap);
+        bool packed = want_packed && cap > 0 && g_force_general_gemm.load(std::memory_order_relaxed) == 0;
+        for (int i = 0; i < n && packed; ++i) packed = need[i] <= cap;
+        if (packed) {
+            SC_HIP(hipMemsetAsync(d_wav, 0, (size_t)n * T * hop * sizeof(float), m.stream));
+            const std::vector<int> first = plan_packed_groups(need, budget);
+            std::vector<std::vector<int32_t>> staging;  // host side of the asynchronous copies, until the synchronisation below
+            staging.reserve(first.size() - 1);
+            int64_t rows_done = 0;
+            for (size_t g = 0; g + 1 < first.size(); ++g) {
+                const int i0 = first[g], ng = first[g + 1] - first[g];
+                PackedItems pk;
+                pk.n = ng;
+                pk.off.assign(ng + 1, 0);
+                for (int gi = 0; gi < ng; ++gi) pk.off[gi + 1] = pk.off[gi] + need[i0 + gi];
+                const int R = pk.rows();
+                rows_done += R;
+                vocoder_tile_tables(m, pk);
+                // one upload: [offsets | tile tables | lang | spkr | item -> caller's row | unit ids]
+                const size_t n_tab = pk.tabs.size();
+                staging.emplace_back((size_t)(ng + 1) + n_tab + 3 * (size_t)ng + R);
+                std::vector<int32_t>& h = staging.back();
+                int32_t* w = h.data();
+                w = std::copy(pk.off.begin(), pk.off.end(), w);
+                w = std::copy(pk.tabs.begin(), pk.tabs.end(), w);
+                for (int gi = 0; gi < ng; ++gi) w[gi] = h_lang[i0 + gi], w[ng + gi] = h_spkr[i0 + gi], w[2 * ng + gi] = i0 + gi;
+                w += 3 * ng;
+                for (int gi = 0; gi < ng; ++gi) w = std::copy(h_units + (size_t)(i0 + gi) * T, h_units + (size_t)(i0 + gi) * T + need[i0 + gi], w);
+                Buf<int> d_all(m.pp(), h.size());
+                SC_HIP(hipMemcpyAsync(d_all.get(), h.data(), h.size() * 4, hipMemcpyHostToDevice, m.stream));
+                pk.d_off = d_all.get();
+                pk.d_tabs = pk.d_off + (ng + 1);
+                const int* d_lang = pk.d_tabs + n_tab;
+                const int* d_item = d_lang + 2 * ng;
+                const int* d_units = d_item + ng;
+                Buf<float> gw(m.pp(), (size_t)R * hop);
+                vocode_batch(m, d_units, d_lang, d_lang + ng, ng, pk.longest(), gw, &pk);
+                launch_scatter_items(gw, pk.d_off, d_item, ng, hop, pk.longest() * hop, (int64_t)T * hop, d_wav, m.stream);
+            }
+            m.last_vocoder_unit_rows = rows_done;
+            m.last_vocoder_packed_groups = (int)first.size() - 1;
+            SC_HIP(hipStreamSynchronize(m.stream));
+            return;
+        }
+    }
+    // ---- one pass per length bucket ----------------------------------------------------------------------------
     static const int group_overhead = std::max(0, knob::value("SC_VOC_GROUP_OVERHEAD", 250));
     const std::vector<std::vector<int>> groups = plan_length_groups(need, group_overhead, max_groups);
     SC_HIP(hipMemsetAsync(d_wav, 0, (size_t)n * T * hop * sizeof(float), m.stream));
