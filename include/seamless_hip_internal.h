@@ -1,6 +1,6 @@
 /*
  * seamless_hip_internal.h - entry points of libseamless_hip.so that are NOT part of the drop-in boundary: kernel-level hooks
- * the parity tests drive (tests/test_ops_gpu.py, test_dstep_gpu.py, test_dstep3_gpu.py: every hand-written kernel against a
+ * the parity tests drive (tests/test_ops_gpu.py, test_dstep_gpu.py, test_dstep3_gpu.py, test_engine_kernels_gpu.py: every hand-written kernel against a
  * PyTorch restatement and against its own variants, bit for bit where the variants claim it), a dependent-chain
  * micro-benchmark, and the introspection of the decoder-step dispatch.  Nothing here has a reference counterpart and nothing
  * of it is needed to run the model; a binding of the reference uses include/seamless_hip.h only.
@@ -199,6 +199,54 @@ int sc_op_beam_compact(const int32_t* d_done, int32_t* d_slot_utt, int32_t* d_sl
 int sc_op_gather_cache(const float* d_src, float* d_dst, const int32_t* d_src_row, int32_t rows, int32_t len, int32_t cap, int32_t M,
                        int32_t layers, int64_t layer_stride);
 int sc_op_row_token_lprob(const float* d_logits, int64_t ld, int32_t rows, int32_t V, int32_t row_stride, int32_t token, float* d_out);
+
+/* Decode-engine and beam modes of the decoder-step kernels, the engine's bookkeeping (k_engine.hip) and the greedy bookkeeping
+ * (k_misc.hip) through the launchers the model calls (tests/test_engine_kernels_gpu.py).  A slot table d_slot_rp is [slots][2]
+ * ints {row state, position}.  Every hook reads its index tables back and refuses an entry outside the buffers the caller
+ * described (n_states row states, cache_rows cache rows, ...) before it launches anything.
+ * sc_op_dstep_attention_ex: sc_op_dstep_attention with the remaining fields of the kernel's argument block (kernels.h:
+ * DAttnArgs) as nullable device pointers, nb up to 512 (output planes of the row slots a step of that width uses) and caches
+ * of cache_rows rows: d_slot_rp / d_slot_lane (engine: caches and d_lens by row state / lane, q and d_out by slot, `pos`
+ * unused), d_anc [nb][cap] (beam self-attention), kv_row_div / d_kv_item (beam cross-attention), d_rows (live rows).  Rows the
+ * kernel skips read back as NaN in d_out.
+ * sc_op_engine_step_close: the closing pair of an engine step, launch_vocab3 with the per-slot step rules (x [M][K], W [N][K]
+ * fp16) + launch_engine_finalize on the caller's EngineRows arrays (hist [n_states][cap]).
+ * sc_op_engine_admit: d_recs [n][4 + 12] ints {row state, limit, prefix_len, enc_len, prefix tokens} (EngineAdmitRec).
+ * sc_op_engine_set_slots: d_rids [2][slots] row states, then lanes.  sc_op_engine_retire: record i = {h_rid[i], h_dst_rows[i],
+ * h_dst[i]} from HOST arrays (h_dst: device pointers, NULL allowed), d_hidden [n_states][cap - 1][M], d_stage [n][2 + cap].
+ * sc_op_dstep3_embed_ex: launch_embed3 -> x [rows][C] (NaN where the kernel wrote nothing); d_tok [n_states], embedding
+ * [vocab][C] fp16, position table [n_pos][C]; without d_slot_rp every row at `pos`.
+ * sc_op_dstep3_reduce_capture_ex: launch_reduce3 as the last launch of a step: x += bias + partials [S][rows][C], d_h =
+ * LayerNorm(x), captured row -> d_hrow[owner * hrow_bs + position * C] for position < hrow_rows (owner / position from the slot
+ * table, the row itself at `pos` without it).
+ * sc_op_step_update / sc_op_row_swap: launch_step_update at host position `pos`; launch_row_swap on d_k / d_v
+ * [layers][n_rows][cap][M], d_cross [layers][n_rows][s_enc][2M], pairs from the host arrays h_src / h_dst. */
+int sc_op_dstep_attention_ex(const float* d_proj, int32_t S, const float* d_bias, float* d_kcache, float* d_vcache, int32_t cap,
+                             int32_t cache_rows, int32_t pos, const int32_t* d_lens, int32_t cross, int32_t nb, int32_t heads,
+                             const int32_t* d_slot_rp, const int32_t* d_slot_lane, const int32_t* d_anc, const int32_t* d_kv_item,
+                             int32_t kv_row_div, const int32_t* d_rows, float* d_out);
+int sc_op_engine_step_close(const float* d_x, const void* d_w_f16, int32_t M, int32_t N, int32_t K, int32_t min_step_for_eos, int32_t pad_idx,
+                            int32_t eos_idx, int32_t unk_idx, float unk_penalty, int32_t* d_slot_rp, const int32_t* d_rows, int32_t n_states,
+                            int32_t cap, int32_t* d_tok, int32_t* d_pos, int32_t* d_finished, int32_t* d_out_len, const int32_t* d_limit,
+                            const int32_t* d_prefix_len, float* d_score, int32_t* d_hist);
+int sc_op_engine_admit(const int32_t* d_recs, int32_t n, int32_t n_states, int32_t cap, int32_t pad_idx, int32_t* d_tok, int32_t* d_pos,
+                       int32_t* d_finished, int32_t* d_out_len, int32_t* d_limit, int32_t* d_prefix_len, int32_t* d_enc_lens, float* d_score,
+                       int32_t* d_hist);
+int sc_op_engine_set_slots(const int32_t* d_rids, int32_t n_live, int32_t slots, int32_t n_states, int32_t* d_slot_rp, int32_t* d_slot_lane,
+                           const int32_t* d_pos, int32_t* d_rows);
+int sc_op_engine_retire(const int32_t* h_rid, const int32_t* h_dst_rows, float* const* h_dst, int32_t n, int32_t n_states, int32_t cap, int32_t M,
+                        const int32_t* d_out_len, const float* d_score, const int32_t* d_hist, const float* d_hidden, int32_t* d_stage);
+int sc_op_dstep3_embed_ex(const int32_t* d_tok, const void* d_embed_f16, float scale, const float* d_pos_table, int32_t pos,
+                          const int32_t* d_slot_rp, const int32_t* d_rows, int32_t rows, int32_t C, int32_t n_states, int32_t n_pos, int32_t vocab,
+                          float* d_x);
+int sc_op_dstep3_reduce_capture_ex(const float* d_partial, int32_t S, const float* d_bias, float* d_x_inout, const float* d_gamma, const float* d_beta,
+                                   float* d_h, float* d_hrow, int64_t hrow_bs, int32_t hrow_rows, int32_t pos, const int32_t* d_slot_rp,
+                                   const int32_t* d_rows, int32_t rows, int32_t C, int32_t n_states);
+int sc_op_step_update(int32_t* d_next_tok, int32_t* d_hist, int32_t hist_ld, int32_t* d_finished, int32_t* d_out_len, const float* d_lprob,
+                      float* d_score, int32_t nb, int32_t pos, int32_t pad_idx, int32_t eos_idx, int32_t* d_n_unfinished);
+int sc_op_row_swap(float* d_k, float* d_v, float* d_cross, int32_t layers, int32_t pairs, const int32_t* h_src, const int32_t* h_dst, int32_t n_rows,
+                   int32_t M, int32_t cap, int32_t s_enc, int32_t filled, int32_t* d_tok, int32_t* d_finished, int32_t* d_out_len,
+                   int32_t* d_enc_lens, float* d_lprob, float* d_score, int32_t* d_hist, float* d_hidden);
 
 #ifdef __cplusplus
 }

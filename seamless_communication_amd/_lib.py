@@ -191,6 +191,15 @@ SIGNATURES = {
     "sc_op_beam_compact": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _i]),
     "sc_op_gather_cache": (C.c_int, [_P, _P, _P, _i, _i, _i, _i, _i, C.c_int64]),
     "sc_op_row_token_lprob": (C.c_int, [_P, C.c_int64, _i, _i, _i, _i, _P]),
+    "sc_op_dstep_attention_ex": (C.c_int, [_P, _i, _P, _P, _P, _i, _i, _i, _P, _i, _i, _i, _P, _P, _P, _P, _i, _P, _P]),
+    "sc_op_engine_step_close": (C.c_int, [_P, _P, _i, _i, _i, _i, _i, _i, _i, C.c_float, _P, _P, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sc_op_engine_admit": (C.c_int, [_P, _i, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sc_op_engine_set_slots": (C.c_int, [_P, _i, _i, _i, _P, _P, _P, _P]),
+    "sc_op_engine_retire": (C.c_int, [_P, _P, _P, _i, _i, _i, _i, _P, _P, _P, _P, _P]),
+    "sc_op_dstep3_embed_ex": (C.c_int, [_P, _P, C.c_float, _P, _i, _P, _P, _i, _i, _i, _i, _i, _P]),
+    "sc_op_dstep3_reduce_capture_ex": (C.c_int, [_P, _i, _P, _P, _P, _P, _P, _P, C.c_int64, _i, _i, _P, _P, _i, _i, _i]),
+    "sc_op_step_update": (C.c_int, [_P, _P, _i, _P, _P, _P, _P, _i, _i, _i, _i, _P]),
+    "sc_op_row_swap": (C.c_int, [_P, _P, _P, _i, _i, _P, _P, _i, _i, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1599,4 +1599,306 @@ int sc_op_row_token_lprob(const float* d_logits, int64_t ld, int32_t rows, int32
     SC_API_END
 }
 
+/* ---- decode-engine / beam modes of the step kernels and the engine / greedy bookkeeping (tests/test_engine_kernels_gpu.py) ----
+ * Every hook reads the index tables it is handed back to the host and refuses entries that would take a kernel outside the
+ * buffers the caller described: the kernels themselves trust their tables. */
+static int op_row_slots(int rows) { return rows <= 32 ? 32 : (rows <= 64 ? 64 : (int)align_up(rows, 32)); }  // StepCtx::rb
+
+static void op_check_slot_table(const char* who, const int32_t* d_slot_rp, int32_t slots, int32_t n_states, int32_t pos_end) {
+    const std::vector<int32_t> rp = op_read_ints(d_slot_rp, (size_t)2 * slots);
+    for (int s = 0; s < slots; ++s)
+        SC_CHECK(rp[2 * s] >= 0 && rp[2 * s] < n_states && rp[2 * s + 1] >= 0 && rp[2 * s + 1] < pos_end,
+                 "%s: slot %d = {row state %d, position %d} outside %d row states / %d positions", who, s, rp[2 * s], rp[2 * s + 1], n_states, pos_end);
+}
+
+/* sc_op_dstep_attention with the remaining fields of DAttnArgs (nullable device pointers) and up to 512 rows.  The caches hold
+ * `cache_rows` rows ([cache_rows][cap][M], cross: [cache_rows][cap][2M]); d_lens is indexed like the caches' owner (row state
+ * in engine mode, live row otherwise).  The output planes are NaN before the launch: a row the kernel skips reads back as NaN. */
+int sc_op_dstep_attention_ex(const float* d_proj, int32_t S, const float* d_bias, float* d_kcache, float* d_vcache, int32_t cap,
+                             int32_t cache_rows, int32_t pos, const int32_t* d_lens, int32_t cross, int32_t nb, int32_t heads,
+                             const int32_t* d_slot_rp, const int32_t* d_slot_lane, const int32_t* d_anc, const int32_t* d_kv_item,
+                             int32_t kv_row_div, const int32_t* d_rows, float* d_out) {
+    SC_API_BEGIN
+    SC_CHECK(nb >= 1 && nb <= 512 && heads >= 1 && S >= 1 && cap >= 1 && cache_rows >= 1 && kv_row_div >= 1 && d_proj && d_kcache && d_out,
+             "sc_op_dstep_attention_ex: bad shape");
+    SC_CHECK(cross ? d_lens != nullptr : (d_vcache != nullptr && pos >= 0 && pos < cap), "sc_op_dstep_attention_ex: bad cache arguments");
+    int live = nb;
+    if (d_rows) {
+        live = op_read_ints(d_rows, 1)[0];
+        SC_CHECK(live >= 0 && live <= nb, "sc_op_dstep_attention_ex: *d_rows = %d outside 0..%d", live, nb);
+    }
+    if (d_slot_rp) {
+        // self-attention indexes nothing by the row state: its cache row is the slot's lane
+        op_check_slot_table("sc_op_dstep_attention_ex", d_slot_rp, nb, cross ? cache_rows : 0x7fffffff, cap);
+        if (!cross) {
+            SC_CHECK(d_slot_lane, "sc_op_dstep_attention_ex: the engine's self-attention needs d_slot_lane");
+            for (int32_t l : op_read_ints(d_slot_lane, nb)) SC_CHECK(l >= 0 && l < cache_rows, "sc_op_dstep_attention_ex: lane %d outside 0..%d", l, cache_rows - 1);
+        }
+    } else if (cross) {
+        if (d_kv_item) {
+            for (int32_t u : op_read_ints(d_kv_item, (size_t)(nb - 1) / kv_row_div + 1))
+                SC_CHECK(u >= 0 && u < cache_rows, "sc_op_dstep_attention_ex: kv_item entry %d outside 0..%d", u, cache_rows - 1);
+        } else {
+            SC_CHECK((nb - 1) / kv_row_div < cache_rows, "sc_op_dstep_attention_ex: %d rows / %d need more than %d cache rows", nb, kv_row_div, cache_rows);
+        }
+    } else {
+        SC_CHECK(nb <= cache_rows, "sc_op_dstep_attention_ex: %d rows append to %d cache rows", nb, cache_rows);
+        if (d_anc) {
+            SC_CHECK((int64_t)cache_rows * cap * heads * 64 * 4 < (1ll << 32), "sc_op_dstep_attention_ex: cache too large for the ancestor-table addressing");
+            const std::vector<int32_t> anc = op_read_ints(d_anc, (size_t)nb * cap);
+            for (int b = 0; b < nb; ++b)
+                for (int j = 0; j <= pos; ++j)
+                    SC_CHECK(anc[(size_t)b * cap + j] >= 0 && anc[(size_t)b * cap + j] < cache_rows, "sc_op_dstep_attention_ex: anc[%d][%d] = %d outside 0..%d",
+                             b, j, anc[(size_t)b * cap + j], cache_rows - 1);
+        }
+    }
+    OpScratch scratch;
+    const int M = heads * 64, RB = op_row_slots(nb);
+    __half* oh = scratch.get<__half>((size_t)M * RB);
+    __half* ol = scratch.get<__half>((size_t)M * RB);
+    int* d_pos = scratch.get<int>(4);
+    SC_HIP(hipMemsetAsync(oh, 0xff, (size_t)M * RB * 2, g_op_stream));
+    SC_HIP(hipMemsetAsync(ol, 0xff, (size_t)M * RB * 2, g_op_stream));
+    SC_HIP(hipMemcpyAsync(d_pos, &pos, 4, hipMemcpyHostToDevice, g_op_stream));
+    DAttnArgs a;
+    a.q = d_proj;
+    a.S = S;
+    a.bias = d_bias;
+    a.cap = cap;
+    a.Oh = oh, a.Ol = ol, a.ORB = RB;
+    a.nb = nb, a.heads = heads;
+    a.d_rows = d_rows;
+    a.slot_rp = reinterpret_cast<const int2*>(d_slot_rp);
+    if (cross) {
+        a.ldq = M, a.sstride = (int64_t)nb * M;
+        a.kcache = d_kcache, a.vcache = d_kcache + M;
+        a.cache_ld = 2 * M, a.cache_bs = (int64_t)cap * 2 * M;
+        a.kv_lens = d_lens;
+        a.kv_row_div = kv_row_div, a.kv_item = d_kv_item;
+    } else {
+        a.ldq = 3 * M, a.sstride = (int64_t)nb * 3 * M;
+        a.koff = M, a.voff = 2 * M;
+        a.kcache = d_kcache, a.vcache = d_vcache;
+        a.cache_ld = M, a.cache_bs = (int64_t)cap * M;
+        a.d_pos = d_pos;
+        a.anc = d_anc;
+        a.slot_lane = d_slot_lane;
+    }
+    launch_dattn(a, cross != 0, g_op_stream);
+    launch_planes_to_rows(oh, ol, RB, d_out, M, nb, M, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+/* The closing pair of an engine step: launch_vocab3 in slot mode (x [M][K] fp32 -> planes, W [N][K] fp16 packed here) and
+ * launch_engine_finalize on the caller's EngineRows arrays (n_states row states, hist [n_states][cap]).  Slot m of the first
+ * *d_rows works on row state d_slot_rp[m].x at position d_slot_rp[m].y. */
+int sc_op_engine_step_close(const float* d_x, const void* d_w_f16, int32_t M, int32_t N, int32_t K, int32_t min_step_for_eos, int32_t pad_idx,
+                            int32_t eos_idx, int32_t unk_idx, float unk_penalty, int32_t* d_slot_rp, const int32_t* d_rows, int32_t n_states,
+                            int32_t cap, int32_t* d_tok, int32_t* d_pos, int32_t* d_finished, int32_t* d_out_len, const int32_t* d_limit,
+                            const int32_t* d_prefix_len, float* d_score, int32_t* d_hist) {
+    SC_API_BEGIN
+    SC_CHECK(vocab3_supported(M, N, K), "sc_op_engine_step_close: M=%d N=%d K=%d unsupported", M, N, K);
+    SC_CHECK(d_x && d_w_f16 && d_slot_rp && d_rows && n_states >= 1 && cap >= 2 && d_tok && d_pos && d_finished && d_out_len && d_limit &&
+                 d_prefix_len && d_score && d_hist,
+             "sc_op_engine_step_close: null argument");
+    const int32_t live = op_read_ints(d_rows, 1)[0];
+    SC_CHECK(live >= 0 && live <= M, "sc_op_engine_step_close: *d_rows = %d outside 0..%d", live, M);
+    op_check_slot_table("sc_op_engine_step_close", d_slot_rp, M, n_states, cap - 1);  // hist[r][pos + 1] is written
+    OpScratch scratch;
+    const int RB = op_row_slots(M);
+    const int groups = vocab3_groups(M);
+    __half* wp = scratch.get<__half>((size_t)packed_weight_halfs(N, K));
+    __half* ah = scratch.get<__half>((size_t)K * RB);
+    __half* al = scratch.get<__half>((size_t)K * RB);
+    float4* part = scratch.get<float4>((size_t)groups * M);
+    float* eos_logit = scratch.get<float>(M);
+    SC_HIP(hipMemsetAsync(part, 0xff, (size_t)groups * M * sizeof(float4), g_op_stream));
+    SC_HIP(hipMemsetAsync(eos_logit, 0xff, (size_t)M * 4, g_op_stream));
+    launch_pack_weight(static_cast<const __half*>(d_w_f16), K, N, K, wp, g_op_stream);
+    SC_HIP(hipMemsetAsync(ah, 0xff, (size_t)K * RB * 2, g_op_stream));
+    SC_HIP(hipMemsetAsync(al, 0xff, (size_t)K * RB * 2, g_op_stream));
+    launch_rows_to_planes(d_x, K, M, K, RB, ah, al, g_op_stream);
+    Vocab3Args v;
+    v.Wp = wp, v.Ah = ah, v.Al = al, v.RB = RB, v.M = M, v.N = N, v.K = K;
+    v.am_part = part, v.am_tiles_cap = groups, v.am_eos_logit = eos_logit;
+    v.am_min_step_for_eos = min_step_for_eos;
+    v.am_pad_idx = pad_idx, v.am_eos_idx = eos_idx, v.am_unk_idx = unk_idx, v.am_unk_penalty = unk_penalty;
+    v.d_rows = d_rows;
+    v.slot_rp = reinterpret_cast<const int2*>(d_slot_rp), v.limit_row = d_limit;
+    launch_vocab3(v, g_op_stream);
+    EngineFinalizeArgs f;
+    f.part = part, f.tiles = groups, f.slots = M, f.eos_logit = eos_logit;
+    f.slot_rp = reinterpret_cast<int2*>(d_slot_rp), f.d_rows = d_rows, f.pad_idx = pad_idx, f.eos_idx = eos_idx;
+    f.rows.tok = d_tok, f.rows.pos = d_pos, f.rows.finished = d_finished, f.rows.out_len = d_out_len;
+    f.rows.limit = const_cast<int32_t*>(d_limit), f.rows.prefix_len = const_cast<int32_t*>(d_prefix_len), f.rows.score = d_score;
+    f.rows.hist = d_hist, f.rows.cap = cap, f.rows.M = K;
+    launch_engine_finalize(f, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+/* launch_engine_admit: d_recs [n][4 + ENGINE_MAX_PREFIX] ints = {row state, limit, prefix_len, enc_len, prefix tokens} */
+int sc_op_engine_admit(const int32_t* d_recs, int32_t n, int32_t n_states, int32_t cap, int32_t pad_idx, int32_t* d_tok, int32_t* d_pos,
+                       int32_t* d_finished, int32_t* d_out_len, int32_t* d_limit, int32_t* d_prefix_len, int32_t* d_enc_lens, float* d_score,
+                       int32_t* d_hist) {
+    SC_API_BEGIN
+    static_assert(sizeof(EngineAdmitRec) == (4 + ENGINE_MAX_PREFIX) * 4, "EngineAdmitRec is a row of ints");
+    SC_CHECK(d_recs && n >= 0 && n_states >= 1 && cap >= 1 && d_tok && d_pos && d_finished && d_out_len && d_limit && d_prefix_len && d_enc_lens &&
+                 d_score && d_hist,
+             "sc_op_engine_admit: null argument");
+    const std::vector<int32_t> recs = op_read_ints(d_recs, (size_t)n * (4 + ENGINE_MAX_PREFIX));
+    for (int i = 0; i < n; ++i) {
+        const int32_t* r = recs.data() + (size_t)i * (4 + ENGINE_MAX_PREFIX);
+        SC_CHECK(r[0] >= 0 && r[0] < n_states && r[2] >= 1 && r[2] <= ENGINE_MAX_PREFIX, "sc_op_engine_admit: record %d: row state %d, prefix of %d", i, r[0], r[2]);
+    }
+    EngineRows R;
+    R.tok = d_tok, R.pos = d_pos, R.finished = d_finished, R.out_len = d_out_len, R.limit = d_limit, R.prefix_len = d_prefix_len;
+    R.enc_lens = d_enc_lens, R.score = d_score, R.hist = d_hist, R.cap = cap;
+    launch_engine_admit(reinterpret_cast<const EngineAdmitRec*>(d_recs), n, R, pad_idx, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+/* launch_engine_set_slots: d_rids [2][slots] = row states, then K / V lanes; d_pos [n_states] */
+int sc_op_engine_set_slots(const int32_t* d_rids, int32_t n_live, int32_t slots, int32_t n_states, int32_t* d_slot_rp, int32_t* d_slot_lane,
+                           const int32_t* d_pos, int32_t* d_rows) {
+    SC_API_BEGIN
+    SC_CHECK(d_rids && slots >= 1 && n_live >= 0 && n_live <= slots && n_states >= 1 && d_slot_rp && d_slot_lane && d_pos && d_rows,
+             "sc_op_engine_set_slots: bad argument");
+    for (int32_t r : op_read_ints(d_rids, n_live)) SC_CHECK(r >= 0 && r < n_states, "sc_op_engine_set_slots: row state %d outside 0..%d", r, n_states - 1);
+    launch_engine_set_slots(d_rids, n_live, slots, reinterpret_cast<int2*>(d_slot_rp), d_slot_lane, d_pos, d_rows, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+/* launch_engine_retire: record i = {h_rid[i], h_dst_rows[i], h_dst[i]} (host arrays; h_dst holds device pointers, entries may
+ * be NULL); d_hidden [n_states][cap - 1][M]; d_stage [n][2 + cap] */
+int sc_op_engine_retire(const int32_t* h_rid, const int32_t* h_dst_rows, float* const* h_dst, int32_t n, int32_t n_states, int32_t cap, int32_t M,
+                        const int32_t* d_out_len, const float* d_score, const int32_t* d_hist, const float* d_hidden, int32_t* d_stage) {
+    SC_API_BEGIN
+    SC_CHECK(h_rid && h_dst_rows && h_dst && n >= 0 && n_states >= 1 && cap >= 2 && d_out_len && d_score && d_hist && d_hidden && d_stage,
+             "sc_op_engine_retire: null argument");
+    std::vector<EngineRetireRec> recs(n);
+    for (int i = 0; i < n; ++i) {
+        SC_CHECK(h_rid[i] >= 0 && h_rid[i] < n_states && h_dst_rows[i] >= 0, "sc_op_engine_retire: record %d: row state %d, %d rows", i, h_rid[i], h_dst_rows[i]);
+        recs[i].rid = h_rid[i], recs[i].dst_rows = h_dst_rows[i], recs[i].dst = h_dst[i];
+    }
+    OpScratch scratch;
+    EngineRetireRec* d_recs = scratch.get<EngineRetireRec>((size_t)std::max(n, 1));
+    if (n) SC_HIP(hipMemcpyAsync(d_recs, recs.data(), (size_t)n * sizeof(EngineRetireRec), hipMemcpyHostToDevice, g_op_stream));
+    EngineRows R;
+    R.out_len = const_cast<int32_t*>(d_out_len), R.score = const_cast<float*>(d_score), R.hist = const_cast<int32_t*>(d_hist);
+    R.hidden = const_cast<float*>(d_hidden), R.cap = cap, R.M = M;
+    launch_engine_retire(d_recs, n, R, d_stage, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+/* launch_embed3 with the engine's slot table (nullable, like d_rows): x [rows][C] = embed[tok[..]] * scale + pos_table[..] read
+ * back from the k-group-major stream, which is NaN before the launch.  d_tok holds n_states tokens (rows without the table),
+ * the embedding `vocab` rows, the position table n_pos rows; pos: the scalar position without the table. */
+int sc_op_dstep3_embed_ex(const int32_t* d_tok, const void* d_embed_f16, float scale, const float* d_pos_table, int32_t pos,
+                          const int32_t* d_slot_rp, const int32_t* d_rows, int32_t rows, int32_t C, int32_t n_states, int32_t n_pos, int32_t vocab,
+                          float* d_x) {
+    SC_API_BEGIN
+    SC_CHECK(d_tok && d_embed_f16 && d_pos_table && d_x && rows >= 1 && rows <= 512 && n_states >= 1 && pos >= 0 && pos < n_pos && vocab >= 1,
+             "sc_op_dstep3_embed_ex: bad argument");
+    SC_CHECK(d_slot_rp || n_states >= rows, "sc_op_dstep3_embed_ex: %d rows read %d tokens", rows, n_states);
+    if (d_slot_rp) op_check_slot_table("sc_op_dstep3_embed_ex", d_slot_rp, rows, n_states, n_pos);
+    for (int32_t t : op_read_ints(d_tok, n_states)) SC_CHECK(t >= 0 && t < vocab, "sc_op_dstep3_embed_ex: token %d outside 0..%d", t, vocab - 1);
+    if (d_rows) {
+        const int32_t live = op_read_ints(d_rows, 1)[0];
+        SC_CHECK(live >= 0 && live <= rows, "sc_op_dstep3_embed_ex: *d_rows = %d outside 0..%d", live, rows);
+    }
+    OpScratch scratch;
+    const int RB = op_row_slots(rows);
+    float* xg = scratch.get<float>((size_t)C * RB);
+    int* d_pos = scratch.get<int>(4);
+    SC_HIP(hipMemsetAsync(xg, 0xff, (size_t)C * RB * 4, g_op_stream));
+    SC_HIP(hipMemcpyAsync(d_pos, &pos, 4, hipMemcpyHostToDevice, g_op_stream));
+    launch_embed3(d_tok, static_cast<const __half*>(d_embed_f16), scale, d_pos_table, d_pos, xg, RB, rows, C, g_op_stream,
+                  reinterpret_cast<const int2*>(d_slot_rp), d_rows);
+    launch_kgm_to_rows(xg, RB, d_x, C, rows, C, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+/* launch_reduce3 as the step's last launch runs it: x [rows][C] += bias + sum of the S partials [S][rows][C], h =
+ * LayerNorm(x) -> d_h [rows][C] and the captured row d_hrow[owner][pos][C] (owner stride hrow_bs floats, positions
+ * 0 .. hrow_rows-1; owner / position = the slot table's, without it the row itself at `pos`).  d_hrow holds n_states owners. */
+int sc_op_dstep3_reduce_capture_ex(const float* d_partial, int32_t S, const float* d_bias, float* d_x_inout, const float* d_gamma, const float* d_beta,
+                                   float* d_h, float* d_hrow, int64_t hrow_bs, int32_t hrow_rows, int32_t pos, const int32_t* d_slot_rp,
+                                   const int32_t* d_rows, int32_t rows, int32_t C, int32_t n_states) {
+    SC_API_BEGIN
+    SC_CHECK(d_partial && d_x_inout && d_gamma && d_beta && d_h && d_hrow && S >= 1 && rows >= 1 && rows <= 512 && n_states >= 1 && pos >= 0 &&
+                 hrow_rows >= 0 && hrow_bs >= (int64_t)hrow_rows * C,
+             "sc_op_dstep3_reduce_capture_ex: bad argument");
+    SC_CHECK(d_slot_rp || n_states >= rows, "sc_op_dstep3_reduce_capture_ex: %d rows capture into %d owners", rows, n_states);
+    if (d_slot_rp) op_check_slot_table("sc_op_dstep3_reduce_capture_ex", d_slot_rp, rows, n_states, 0x7fffffff);
+    if (d_rows) {
+        const int32_t live = op_read_ints(d_rows, 1)[0];
+        SC_CHECK(live >= 0 && live <= rows, "sc_op_dstep3_reduce_capture_ex: *d_rows = %d outside 0..%d", live, rows);
+    }
+    OpScratch scratch;
+    const int RB = op_row_slots(rows);
+    float* xg = scratch.get<float>((size_t)C * RB);
+    int* d_pos = scratch.get<int>(4);
+    SC_HIP(hipMemsetAsync(xg, 0xff, (size_t)C * RB * 4, g_op_stream));
+    SC_HIP(hipMemcpyAsync(d_pos, &pos, 4, hipMemcpyHostToDevice, g_op_stream));
+    launch_rows_to_kgm(d_x_inout, C, rows, C, RB, xg, g_op_stream);
+    Reduce3Args r;
+    r.partial = d_partial, r.S = S, r.bias = d_bias, r.xg = xg, r.XRB = RB, r.rows = rows, r.C = C;
+    r.gamma = d_gamma, r.beta = d_beta, r.hfix = d_h;
+    r.hrow = d_hrow, r.hrow_bs = hrow_bs, r.hrow_rows = hrow_rows, r.d_pos = d_pos;
+    r.d_rows = d_rows, r.slot_rp = reinterpret_cast<const int2*>(d_slot_rp);
+    launch_reduce3(r, g_op_stream);
+    launch_kgm_to_rows(xg, RB, d_x_inout, C, rows, C, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+/* launch_step_update at host position `pos` (hist [nb][hist_ld]; d_score / d_n_unfinished nullable) */
+int sc_op_step_update(int32_t* d_next_tok, int32_t* d_hist, int32_t hist_ld, int32_t* d_finished, int32_t* d_out_len, const float* d_lprob,
+                      float* d_score, int32_t nb, int32_t pos, int32_t pad_idx, int32_t eos_idx, int32_t* d_n_unfinished) {
+    SC_API_BEGIN
+    SC_CHECK(d_next_tok && d_hist && d_finished && d_out_len && (d_lprob || !d_score) && nb >= 1 && pos >= 0 && pos + 1 < hist_ld,
+             "sc_op_step_update: bad argument");
+    OpScratch scratch;
+    int* d_pos = scratch.get<int>(4);
+    SC_HIP(hipMemcpyAsync(d_pos, &pos, 4, hipMemcpyHostToDevice, g_op_stream));
+    launch_step_update(d_next_tok, d_hist, hist_ld, d_finished, d_out_len, d_lprob, d_score, nb, d_pos, pad_idx, eos_idx, d_n_unfinished, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+/* launch_row_swap: d_k / d_v [layers][n_rows][cap][M], d_cross [layers][n_rows][s_enc][2M], h_src / h_dst [pairs] host arrays,
+ * per-row state of n_rows rows, d_hidden [n_rows][cap - 1][M] or NULL */
+int sc_op_row_swap(float* d_k, float* d_v, float* d_cross, int32_t layers, int32_t pairs, const int32_t* h_src, const int32_t* h_dst, int32_t n_rows,
+                   int32_t M, int32_t cap, int32_t s_enc, int32_t filled, int32_t* d_tok, int32_t* d_finished, int32_t* d_out_len,
+                   int32_t* d_enc_lens, float* d_lprob, float* d_score, int32_t* d_hist, float* d_hidden) {
+    SC_API_BEGIN
+    SC_CHECK(d_k && d_v && d_cross && h_src && h_dst && layers >= 1 && layers <= ROWSWAP_MAX_LAYERS && pairs >= 0 && pairs <= ROWSWAP_MAX_PAIRS &&
+                 n_rows >= 1 && n_rows <= 256 && cap >= 2 && s_enc >= 1,
+             "sc_op_row_swap: bad argument");
+    RowSwapArgs a;
+    for (int li = 0; li < layers; ++li) {
+        a.k[li] = d_k + (int64_t)li * n_rows * cap * M;
+        a.v[li] = d_v + (int64_t)li * n_rows * cap * M;
+        a.cross[li] = d_cross + (int64_t)li * n_rows * s_enc * 2 * M;
+    }
+    a.layers = layers, a.pairs = pairs;
+    for (int i = 0; i < pairs; ++i) {
+        SC_CHECK(h_src[i] >= 0 && h_src[i] < n_rows && h_dst[i] >= 0 && h_dst[i] < n_rows, "sc_op_row_swap: pair %d = (%d, %d) outside 0..%d", i, h_src[i],
+                 h_dst[i], n_rows - 1);
+        a.src[i] = (unsigned char)h_src[i], a.dst[i] = (unsigned char)h_dst[i];
+    }
+    a.M = M, a.cap = cap, a.s_enc = s_enc, a.filled = filled;
+    a.tok = d_tok, a.finished = d_finished, a.out_len = d_out_len, a.enc_lens = d_enc_lens, a.lprob = d_lprob, a.score = d_score;
+    a.hist = d_hist, a.hidden = d_hidden;
+    launch_row_swap(a, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
 }  // extern "C"

@@ -15,10 +15,13 @@ from seamless_communication_amd.tokenizer import CharTokenizer, NllbTextTokenize
 # eos_ramp settings of the tiny model (synthetic.EosRamp) under which a greedy batch stops on its own (lengths of the eight
 # utterances of tests/test_oracle_eos_cpu.py: AUDIO): EOS_SPREAD rows that finish at 5 different steps (8 ... 12 tokens),
 # EOS_MIXED rows that finish on the second generated token next to rows that run to 16 / 17, EOS_EARLY rows that all finish
-# on the first generated token (before the host's first look at the finished flags)
+# on the first generated token (before the host's first look at the finished flags), EOS_LONG (with a length cap of 150) rows
+# that stop after 15 / 16 tokens next to rows of about 80, 120 and 137 tokens and one that runs into the cap: a weak ramp, so
+# that most rows pass its top around position 80
 EOS_SPREAD = "20,1,0,1"
 EOS_MIXED = "30,1,0,2"
 EOS_EARLY = "10,1.2,0.2,1.5"
+EOS_LONG = "120,0.02,0,1.4"
 
 
 @functools.lru_cache(maxsize=6)

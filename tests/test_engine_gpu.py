@@ -28,7 +28,7 @@ def _log(report_dir, name, **kw):
         f.write(name + " " + " ".join(f"{k}={v}" for k, v in kw.items()) + "\n")
 
 
-def _env(spec, reps):
+def _env(spec, reps, cap=CAP):
     if not torch.cuda.is_available():
         pytest.fail("GPU test selected but no HIP device is visible")
     cfg, sd, vsd, tt, ct = common.tiny_bundle(eos_ramp=spec)
@@ -37,7 +37,7 @@ def _env(spec, reps):
     for rep in range(reps):
         ws += common.waves(AUDIO, start=100 * rep)
     fb, lens = orc.collate_fbank(ws)
-    seqs, enc, enc_lens, margins = orc.s2tt(fb, lens, "fra", (1, 200), CAP)
+    seqs, enc, enc_lens, margins = orc.s2tt(fb, lens, "fra", (1, 200), cap)
     return cfg, tt, hip, seqs, enc.cuda().contiguous(), enc_lens.tolist(), int(lens.max())
 
 
@@ -107,6 +107,43 @@ def test_rows_through_the_engine_equal_rows_generated_alone(spec, use_graph, rep
         eng.close()
     _log(report_dir, "engine_vs_alone", spec=spec, use_graph=use_graph, lens=want_lens, **st)
     assert st["rows_retired"] == 24 and st["rows_admitted"] == 24 and st["requests"] == 3 and st["max_live"] <= 6
+    assert st["useful_row_steps"] == sum(n - 1 for n in want_lens)
+    for (lo, hi), (ids, lens, scores, hid) in zip(spans, outs):
+        for b in range(lo, hi):
+            a_ids, a_lens, a_scores, a_hid = alone[b]
+            n = int(a_lens[0])
+            assert int(lens[b - lo]) == n == want_lens[b], (b, lens[b - lo], n)
+            assert ids[b - lo].tolist() == a_ids[0].tolist(), b          # the whole row: padding behind the hypothesis included
+            assert scores[b - lo] == a_scores[0], (b, scores[b - lo], a_scores[0])
+            assert torch.equal(hid[b - lo, : n - 1], a_hid[0, : n - 1]), b
+            if n - 1 < hid.shape[1]:  # zeros behind the hypothesis
+                assert float(hid[b - lo, n - 1:].abs().max()) == 0.0, b
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_long_rows_through_the_engine_equal_rows_generated_alone(use_graph, report_dir):
+    """Lanes of 150 positions: hypotheses of more than 64 and more than 128 tokens (several 64-key trips of the attention
+    kernel's online soft-max) next to rows that stop after 15 ... 17 tokens, as two requests through a 5-slot engine - a lane a
+    short row leaves is taken by a row that then runs far past the previous occupant's keys, and the other way round.  Same
+    assertions as test_rows_through_the_engine_equal_rows_generated_alone."""
+    from seamless_communication_amd.runtime import DecodeEngine
+
+    cap = 150
+    cfg, tt, hip, seqs, enc, enc_lens, src_len = _env(common.EOS_LONG, 2, cap)
+    prefix = tt.target_prefix("fra")
+    want_lens = [len(s) for s in seqs]
+    assert len(seqs) == 16 and max(want_lens) > 129 and min(want_lens) < 20 and any(65 < n <= 128 for n in want_lens), want_lens
+    alone = _alone(hip, enc, enc_lens, prefix, src_len, cap)
+    assert [a[0][0, : a[1][0]].tolist() for a in alone] == seqs  # the premise: a row alone gives the oracle's ids
+    eng = DecodeEngine(hip, max_len=cap, s_enc=enc.shape[1], slots=5, rows=16, poll=2, use_graph=use_graph)
+    try:
+        spans = [(0, 6), (6, 16)]
+        outs = _through_engine(hip, eng, enc, enc_lens, prefix, src_len, spans, caps=[cap, cap], use_graph=use_graph, stagger=0.003)
+        st = eng.stats()
+    finally:
+        eng.close()
+    _log(report_dir, "engine_long_rows", use_graph=use_graph, lens=want_lens, **st)
+    assert st["rows_retired"] == 16 and st["rows_admitted"] == 16 and st["requests"] == 2 and st["max_live"] <= 5
     assert st["useful_row_steps"] == sum(n - 1 for n in want_lens)
     for (lo, hi), (ids, lens, scores, hid) in zip(spans, outs):
         for b in range(lo, hi):
