@@ -374,6 +374,36 @@ int32_t sc_ngram_blocked_tokens(const int32_t* h_seq, int32_t len, int32_t ngram
 int32_t sc_banned_blocked_tokens(const int32_t* h_seq, int32_t len, const int32_t* h_banned_tokens, const int32_t* h_banned_offsets,
                                  int32_t n_banned, int32_t* h_out, int32_t cap);
 
+/* UnitY2 forced aligner (the `nar_t2u_aligner` card; added within ABI v10, purely additive).  A handle of its own: the aligner
+ * is a separate checkpoint with its own vocabularies, stream and scratch pool.  Configuration as
+ * models/aligner/builder.py:64-87 (`nar_t2u_aligner_base`: model_dim = feat_dim = 1024, 2 text layers, 3 feature layers,
+ * temperature 1.0, reduction_factor 1, 10943 characters, 10082 units).  Tensor names are those of the converted checkpoint
+ * (models/aligner/loader.py:22-57): alignment_frontend.embed_text.weight, alignment_frontend.embed_unit.weight,
+ * alignment_encoder.t_conv.{1 + 3 i}.{weight,bias}, alignment_encoder.f_conv.{1 + 3 i}.{weight,bias} (the positions of the
+ * Conv1d modules inside the nn.Sequential of models/aligner/model.py:99-144); weights are held as fp16, biases as fp32. */
+typedef struct sc_aligner_config {
+    int32_t abi_version; /* must be SC_ABI_VERSION */
+    int32_t model_dim, feat_dim; /* multiples of 32 */
+    int32_t text_layers, feat_layers; /* Conv1d(k=3, pad=1) + ReLU each, the last one Conv1d(k=1) (stride reduction_factor on the feature side) */
+    float temperature;
+    int32_t reduction_factor;
+    int32_t char_vocab_size, unit_vocab_size;
+} sc_aligner_config;
+typedef struct sc_aligner sc_aligner;
+sc_aligner* sc_aligner_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_aligner_config* cfg, int device);
+void sc_aligner_free(sc_aligner* a);
+/* UnitY2AlignmentModel.forward (models/aligner/model.py:293-304: frontend :68-71, encoder :146-190, viterbi_decode :246-277)
+ * on a ragged batch: h_text_ids [n][s_text] char ids (alignment_frontend.tokenize_text), h_unit_ids [n][s_unit] unit ids of
+ * the NAR unit encoder (tokenize_unit), positions behind an item's length hold any id of the vocabulary.  h_durations
+ * [n][s_text]: frames of every character, zeros behind the text length; with reduction_factor > 1 they count REDUCED frames
+ * (ceil(unit_len / reduction_factor) in all) and the caller applies postprocess_alignment (model.py:192-209).
+ * d_lprob_or_null: device buffer [n][ceil(s_unit / reduction_factor)][s_text] that receives attn_lprob (-inf behind the text
+ * length, zeros behind the feature length).  The search (model.py:212-243) runs on the device with a double-precision Q and
+ * the reference's tie rule; limits: 2048 characters and 8192 (reduced) frames per item, SC_ERR_INVALID above. */
+int sc_align(sc_aligner* a, const int32_t* h_text_ids, int32_t n, int32_t s_text, const int32_t* h_text_lens,
+             const int32_t* h_unit_ids, int32_t s_unit, const int32_t* h_unit_lens, int32_t* h_durations,
+             float* d_lprob_or_null);
+
 /* The kernel-level test hooks (sc_op_*) and the dispatch introspection the parity tests drive are exported too but are NOT part
  * of the drop-in boundary: include/seamless_hip_internal.h. */
 

@@ -247,6 +247,15 @@ int sc_op_step_update(int32_t* d_next_tok, int32_t* d_hist, int32_t hist_ld, int
 int sc_op_row_swap(float* d_k, float* d_v, float* d_cross, int32_t layers, int32_t pairs, const int32_t* h_src, const int32_t* h_dst, int32_t n_rows,
                    int32_t M, int32_t cap, int32_t s_enc, int32_t filled, int32_t* d_tok, int32_t* d_finished, int32_t* d_out_len,
                    int32_t* d_enc_lens, float* d_lprob, float* d_score, int32_t* d_hist, float* d_hidden);
+/* Forced aligner kernels by themselves (k_align.hip; tests/test_aligner_gpu.py).  sc_op_align_lprob: encoder states in
+ * (d_text [n][s_text][C], d_feat [n][s_feat][C] fp32, C % 32 == 0; lengths on the host), d_lprob [n][s_feat][s_text] out: the
+ * masked log-softmax of -temperature * L2 distance.  sc_op_mas: d_lprob [n][s_feat][s_text] and the lengths in, h_durations
+ * [n][s_text] out (zeros behind the text length): the monotonic alignment search with the reference's arithmetic (float32
+ * values added into a double Q, ties to the upper row).  Items above 2048 text positions or 8192 frames: SC_ERR_INVALID. */
+int sc_op_align_lprob(const float* d_text, const float* d_feat, int32_t n, int32_t s_text, int32_t s_feat, int32_t C,
+                      const int32_t* h_text_lens, const int32_t* h_feat_lens, float temperature, float* d_lprob);
+int sc_op_mas(const float* d_lprob, int32_t n, int32_t s_text, int32_t s_feat, const int32_t* h_text_lens, const int32_t* h_feat_lens,
+              int32_t* h_durations);
 
 #ifdef __cplusplus
 }

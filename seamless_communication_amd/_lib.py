@@ -97,6 +97,13 @@ class sc_engine_stats(C.Structure):
     ]
 
 
+class sc_aligner_config(C.Structure):
+    _fields_ = [
+        ("abi_version", _i), ("model_dim", _i), ("feat_dim", _i), ("text_layers", _i), ("feat_layers", _i),
+        ("temperature", C.c_float), ("reduction_factor", _i), ("char_vocab_size", _i), ("unit_vocab_size", _i),
+    ]
+
+
 _P = C.c_void_p
 _PI = C.POINTER(C.c_int32)
 
@@ -147,6 +154,11 @@ SIGNATURES = {
                                          _P, _P, C.c_int32, _P]),
     "sc_ngram_blocked_tokens": (C.c_int32, [_PI, C.c_int32, C.c_int32, _PI, C.c_int32]),
     "sc_banned_blocked_tokens": (C.c_int32, [_PI, C.c_int32, _PI, _PI, C.c_int32, _PI, C.c_int32]),
+    "sc_aligner_load": (_P, [C.POINTER(sc_tensor_desc), C.c_size_t, C.POINTER(sc_aligner_config), C.c_int]),
+    "sc_aligner_free": (None, [_P]),
+    "sc_align": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P, _P, _P]),
+    "sc_op_align_lprob": (C.c_int, [_P, _P, _i, _i, _i, _i, _P, _P, C.c_float, _P]),
+    "sc_op_mas": (C.c_int, [_P, _i, _i, _i, _P, _P, _P]),
     "sc_op_knob": (C.c_int, [C.c_char_p, C.c_int]),
     "sc_op_force_general_gemm": (C.c_int, [C.c_int]),
     "sc_op_voc_pack_plan": (C.c_int32, [_PI, C.c_int32, C.c_int64, _PI, C.c_int32]),

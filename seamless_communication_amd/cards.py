@@ -51,6 +51,16 @@ def vocoder_lang_spkr_idx_map() -> Dict[str, Any]:
     }
 
 
+def nar_t2u_aligner_card() -> Dict[str, Any]:
+    """cards/nar_t2u_aligner.yaml: the aligner shares the unit languages and the number of units of the UnitY2 card; its
+    ``char_tokenizer`` and ``checkpoint`` are URLs there - offline the card names a local SentencePiece model
+    (``char_tokenizer_path``) and a ``file://`` checkpoint, or seeded weights."""
+    return {
+        "name": "nar_t2u_aligner", "model_type": "unity2_aligner", "model_arch": "nar_t2u_aligner",
+        "checkpoint": "synthetic://20240901", "num_units": NUM_UNITS, "unit_langs": list(UNIT_LANGS),
+    }
+
+
 def load_card_file(path: str) -> Dict[str, Any]:
     """Read one reference-schema YAML card from a local file (no asset store,
     no network); ``base:`` chains are resolved by the caller."""

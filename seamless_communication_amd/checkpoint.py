@@ -231,8 +231,37 @@ def convert_vocoder_checkpoint(checkpoint: Mapping[str, Any]) -> Dict[str, torch
     return {f"code_generator.{k}": v for k, v in checkpoint["generator"].items()}
 
 
+ALIGNER_MARKER = "alignment_encoder.t_conv.1.weight"
+
+
+def convert_unity2_aligner_checkpoint(checkpoint: Mapping[str, Any], char_spm_tokens: Optional[Sequence[str]] = None) -> Dict[str, torch.Tensor]:
+    """models/aligner/loader.py:22-57.  The published layout is ``{"text_emb_state": {"weight"}, "unit_emb_state": {"weight"},
+    "aligner_state": {<encoder keys>}}``: the embeddings move to ``alignment_frontend.embed_{text,unit}.weight``, the encoder
+    keys get the ``alignment_encoder.`` prefix and the rows of the char embedding are re-ordered from the fairseq dictionary's
+    sorted order to the SentencePiece model's (:func:`char_index_mapping`).  A checkpoint whose ``model`` entry already holds
+    ``alignment_encoder.t_conv.1.weight`` passes through.  Returns the state dict (the reference returns the checkpoint whose
+    ``model`` entry is that dict)."""
+    if "model" in checkpoint and ALIGNER_MARKER in checkpoint["model"]:
+        return dict(checkpoint["model"])
+    sd: Dict[str, torch.Tensor] = {f"alignment_encoder.{k}": v for k, v in checkpoint["aligner_state"].items()}
+    for side in ("text", "unit"):
+        state = checkpoint[f"{side}_emb_state"]
+        if set(state) != {"weight"}:
+            raise KeyError(f"{side}_emb_state holds {sorted(state)}; only 'weight' is known")
+        sd[f"alignment_frontend.embed_{side}.weight"] = state["weight"]
+    if char_spm_tokens is None:
+        raise ValueError("the aligner checkpoint carries a char embedding: pass the char tokenizer's pieces (char_spm_tokens)")
+    mapping = char_index_mapping(char_spm_tokens)
+    char_embeds = sd["alignment_frontend.embed_text.weight"]
+    with torch.inference_mode():
+        char_embeds[torch.arange(len(mapping))] = char_embeds[mapping]
+    return sd
+
+
 def load_converted_checkpoint(path: str, kind: str, char_spm_tokens: Optional[Sequence[str]] = None) -> Dict[str, torch.Tensor]:
     ckpt = torch.load(path, map_location="cpu", weights_only=True)
     if kind == "vocoder":
         return convert_vocoder_checkpoint(ckpt)
+    if kind == "aligner":
+        return convert_unity2_aligner_checkpoint(ckpt, char_spm_tokens=char_spm_tokens)
     return convert_unity_checkpoint(ckpt, char_spm_tokens=char_spm_tokens)

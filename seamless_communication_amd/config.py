@@ -130,6 +130,32 @@ def seamless_m4t_v2_large() -> S2STConfig:
     return S2STConfig()
 
 
+@dataclass
+class AlignerConfig:
+    """UnitY2 forced aligner (models/aligner/builder.py:64-87, the only architecture: ``nar_t2u_aligner``)."""
+
+    name: str = "nar_t2u_aligner"
+    model_dim: int = 1024
+    feat_dim: int = 1024
+    num_text_layers: int = 2
+    num_feat_layers: int = 3
+    temperature: float = 1.0
+    reduction_factor: int = 1
+    unit_vocab_size: int = 10082
+    unit_pad_idx: int = 1
+    char_vocab_size: int = 10943
+
+
+def nar_t2u_aligner() -> AlignerConfig:
+    return AlignerConfig()
+
+
+def tiny_aligner_config(reduction_factor: int = 1) -> AlignerConfig:
+    """A small aligner of the same structure for parity tests: the vocabularies of tiny_config()."""
+    return AlignerConfig(name="tiny_aligner", model_dim=64, feat_dim=64, reduction_factor=reduction_factor, unit_vocab_size=340,
+                         char_vocab_size=96)
+
+
 def seamless_m4t_large() -> S2STConfig:
     """seamlessM4T_large (v1), unity arch `base` (models/unity/builder.py:109-134): w2v-BERT 600m with relative positions,
     NLLB dense_1b, vocabulary 256102.  The speech encoder, text encoder / decoder run on this path; the v1 autoregressive T2U

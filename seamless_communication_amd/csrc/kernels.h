@@ -704,6 +704,23 @@ struct XattnCapArgs {
 };
 void launch_xattn_capture(const XattnCapArgs& a, hipStream_t s);
 
+// ---- UnitY2 forced aligner (k_align.hip; reference models/aligner/model.py) --------------------------------------
+// out[row] = table[ids[row]] (fp16 table, no scale, no positions)
+void launch_align_embed(const int* ids, int rows, const __half* table, int C, float* out, hipStream_t s);
+// lprob[b][f][t] = log_softmax_t(-temperature * ||feat[b][f] - text[b][t]||_2): text [n][St][C], feat [n][Sf][C] fp32
+// (C % 32 == 0), ragged by the device length tables; text positions behind an item's length are -inf, feature rows behind
+// its length zeros
+void launch_align_lprob(const float* text, const float* feat, int n, int St, int Sf, int C, const int* d_text_lens, const int* d_feat_lens,
+                        float temperature, float* lprob, hipStream_t s);
+// Monotonic alignment search + back-track of every item of lprob [n][Sf][St]: dur [n][St] int32 (zeros behind the text
+// length).  bits: scratch of n * mas_bits_words(max_text_len, Sf) 64-bit words (one decision bit per cell).  Limits:
+// max_text_len <= mas_max_text() (2048), max_feat_len <= mas_max_feat() (8192); above, an error and no launch.
+int mas_max_text();
+int mas_max_feat();
+size_t mas_bits_words(int max_text_len, int Sf);
+void launch_mas(const float* lprob, int n, int St, int Sf, const int* d_text_lens, const int* d_feat_lens, int max_text_len,
+                int max_feat_len, unsigned long long* bits, int* dur, hipStream_t s);
+
 // ---- decode engine (k_engine.hip, engine.hip) ---------------------------------------------------------------------
 // One greedy step chain per GPU shared by every pass in flight.  A ROW STATE r (0 .. rows-1) owns everything that lives as
 // long as a hypothesis: K / V cache rows, encoder K / V, token history, captured decoder outputs, position, flags.  A SLOT s

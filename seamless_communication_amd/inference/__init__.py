@@ -1,6 +1,7 @@
+from .aligner import AlignmentExtractor, word_timestamps
 from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, SequenceGeneratorOptions
 from .transcriber import Transcriber, Transcription, TranscriptionToken, TranscriptionTokenStats
 from .translator import BatchedSpeechOutput, Modality, Task, Translator
 
-__all__ = ["BannedSequenceProcessor", "BatchedSpeechOutput", "Modality", "NGramRepeatBlockProcessor", "SequenceGeneratorOptions", "Task", "Transcriber", "Transcription", "TranscriptionToken",
-           "TranscriptionTokenStats", "Translator"]
+__all__ = ["AlignmentExtractor", "BannedSequenceProcessor", "BatchedSpeechOutput", "Modality", "NGramRepeatBlockProcessor", "SequenceGeneratorOptions", "Task", "Transcriber", "Transcription", "TranscriptionToken",
+           "TranscriptionTokenStats", "Translator", "word_timestamps"]

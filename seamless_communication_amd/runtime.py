@@ -46,6 +46,26 @@ def _ptr(a) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 
 
+def _tensor_descs(tensors: Dict[str, torch.Tensor]):
+    """name -> tensor as the sc_tensor_desc array the load entries take (fp16 / fp32, contiguous), and the tensors it points into."""
+    keep: List[torch.Tensor] = []
+    descs = (_lib.sc_tensor_desc * len(tensors))()
+    for i, (k, v) in enumerate(tensors.items()):
+        if v.dtype not in (torch.float16, torch.float32):
+            v = v.to(torch.float32)
+        v = v.detach().contiguous()
+        keep.append(v)
+        d = descs[i]
+        d.name = k.encode()
+        d.dtype = _lib.SC_F16 if v.dtype == torch.float16 else _lib.SC_F32
+        d.ndim = v.dim()
+        for j, s in enumerate(v.shape):
+            d.shape[j] = s
+        d.data = v.data_ptr()
+        d.on_device = 1 if v.is_cuda else 0
+    return descs, keep
+
+
 class HipS2STModel:
     """Weights of one UnitY2 (+ vocoder) model resident in one GPU's HBM."""
 
@@ -90,21 +110,7 @@ class HipS2STModel:
         if vocoder_state_dict is not None:
             for k, v in vocoder_state_dict.items():
                 tensors[k] = v  # dur_predictor.* included: sc_vocoder_durations (dur_prediction=True, translator.py:385-389)
-        keep: List[torch.Tensor] = []
-        descs = (_lib.sc_tensor_desc * len(tensors))()
-        for i, (k, v) in enumerate(tensors.items()):
-            if v.dtype not in (torch.float16, torch.float32):
-                v = v.to(torch.float32)
-            v = v.detach().contiguous()
-            keep.append(v)
-            d = descs[i]
-            d.name = k.encode()
-            d.dtype = _lib.SC_F16 if v.dtype == torch.float16 else _lib.SC_F32
-            d.ndim = v.dim()
-            for j, s in enumerate(v.shape):
-                d.shape[j] = s
-            d.data = v.data_ptr()
-            d.on_device = 1 if v.is_cuda else 0
+        descs, keep = _tensor_descs(tensors)  # `keep` holds the converted tensors until the library has copied them
         self.has_vocoder_dur_predictor = vocoder_state_dict is not None and any(
             ".dur_predictor." in k for k in vocoder_state_dict)
         ccfg = _lib.make_config(cfg, has_t2u=has_t2u, has_vocoder=vocoder_state_dict is not None,
@@ -490,3 +496,79 @@ class DecodeEngine:
             self.close()
         except Exception:
             pass
+
+
+def postprocess_alignment(durations: np.ndarray, text_lens: Sequence[int], feat_lens: Sequence[int], reduction_factor: int) -> np.ndarray:
+    """UnitY2AlignmentEncoder.postprocess_alignment (models/aligner/model.py:192-209): durations counted in reduced frames
+    -> full-rate frames, the last character that reaches the item's real length truncated to it, zeros behind."""
+    dur = np.asarray(durations, dtype=np.int64) * int(reduction_factor)
+    csum = np.cumsum(dur, axis=1)
+    for b in range(dur.shape[0]):
+        for t in range(int(text_lens[b])):
+            if csum[b, t] >= feat_lens[b]:
+                dur[b, t] = feat_lens[b] - (csum[b, t - 1] if t else 0)
+                if t < text_lens[b] - 1:
+                    dur[b, t + 1:] = 0
+                break
+    return dur
+
+
+class HipAligner:
+    """The UnitY2 forced aligner resident in one GPU's HBM (``sc_aligner_*``): a handle of its own, next to any
+    :class:`HipS2STModel` on the same device."""
+
+    def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], device: int = 0) -> None:
+        self.lib = _lib.load_library()
+        self.cfg = cfg
+        self.device_index = int(device)
+        self.device = torch.device("cuda", self.device_index)
+        if not torch.cuda.is_available():
+            raise SeamlessHipError("no HIP device is visible; the HIP path has no CPU fallback")
+        descs, keep = _tensor_descs(state_dict)
+        c = _lib.sc_aligner_config()
+        c.abi_version = _lib.SC_ABI_VERSION
+        c.model_dim, c.feat_dim = int(cfg.model_dim), int(cfg.feat_dim)
+        c.text_layers, c.feat_layers = int(cfg.num_text_layers), int(cfg.num_feat_layers)
+        c.temperature, c.reduction_factor = float(cfg.temperature), int(cfg.reduction_factor)
+        c.char_vocab_size, c.unit_vocab_size = int(cfg.char_vocab_size), int(cfg.unit_vocab_size)
+        self.handle = self.lib.sc_aligner_load(descs, len(state_dict), C.byref(c), self.device_index)
+        if not self.handle:
+            msg = self.lib.sc_last_error()
+            raise SeamlessHipError(f"sc_aligner_load failed: {msg.decode() if msg else '?'}")
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self.lib.sc_aligner_free(self.handle)
+            self.handle = None
+
+    def __del__(self) -> None:  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def align(self, text_ids: Sequence[Sequence[int]], unit_ids: Sequence[Sequence[int]],
+              return_lprob: bool = False) -> Tuple[np.ndarray, Optional[torch.Tensor]]:
+        """Ragged batch of (char ids, unit ids) pairs -> durations (n, longest text) int64, zeros behind an item's text
+        length, in full-rate frames; and attn_lprob (n, longest reduced unit length, longest text) on the device when asked."""
+        n = len(text_ids)
+        if n == 0 or n != len(unit_ids):
+            raise ValueError("align() takes as many unit sequences as texts, at least one")
+        tl = _i32([len(t) for t in text_ids])
+        ul = _i32([len(u) for u in unit_ids])
+        if tl.min() < 1 or ul.min() < 1:
+            raise ValueError("every text and every unit sequence must hold at least one symbol")
+        st, su = int(tl.max()), int(ul.max())
+        tid = np.zeros((n, st), dtype=np.int32)
+        uid = np.full((n, su), self.cfg.unit_pad_idx, dtype=np.int32)
+        for b in range(n):
+            tid[b, : tl[b]] = np.asarray(text_ids[b], dtype=np.int64)
+            uid[b, : ul[b]] = np.asarray(unit_ids[b], dtype=np.int64)
+        rf = int(self.cfg.reduction_factor)
+        dur = np.zeros((n, st), dtype=np.int32)
+        lprob = torch.empty(n, (su - 1) // rf + 1, st, dtype=torch.float32, device=self.device) if return_lprob else None
+        check(self.lib.sc_align(self.handle, _ptr(tid), n, st, _ptr(tl), _ptr(uid), su, _ptr(ul), _ptr(dur), _ptr(lprob)), "sc_align")
+        out = dur.astype(np.int64)
+        if rf > 1:
+            out = postprocess_alignment(out, tl, ul, rf)
+        return out, lprob

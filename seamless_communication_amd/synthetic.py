@@ -490,6 +490,28 @@ def make_vocoder_state_dict(
     return g.sd.resolve()
 
 
+# Seeded aligner weights.  With unit-variance convolutions the score matrix is nearly flat (the log-probabilities of a row
+# differ by 0.15 at most and the alignment path hangs on margins of 1e-4); four times larger weights spread a row over ~2.7
+# and give path margins with a median of 4e-2, which is what a parity test can tell from float noise.
+ALIGNER_CONV_GAIN = 4.0
+
+
+def make_aligner_state_dict(cfg, seed: int = DEFAULT_SEED, dtype: torch.dtype = torch.float16) -> Dict[str, torch.Tensor]:
+    """State dict of UnitY2AlignmentModel (models/aligner/model.py) in the converted layout (loader.py:22-57); ``cfg`` is a
+    :class:`~seamless_communication_amd.config.AlignerConfig`."""
+    g = _Gen(seed, dtype)
+    g.normal("alignment_frontend.embed_text.weight", (cfg.char_vocab_size, cfg.model_dim), 1.0)
+    g.normal("alignment_frontend.embed_unit.weight", (cfg.unit_vocab_size, cfg.feat_dim), 1.0)
+    for stack, layers, first_in in (("t_conv", cfg.num_text_layers, cfg.model_dim), ("f_conv", cfg.num_feat_layers, cfg.feat_dim)):
+        for i in range(layers):
+            k = 3 if i < layers - 1 else 1
+            cin = first_in if i == 0 else cfg.model_dim
+            p = f"alignment_encoder.{stack}.{1 + 3 * i}"
+            g.uniform(p + ".weight", (cfg.model_dim, cin, k), ALIGNER_CONV_GAIN * math.sqrt(3.0 / (cin * k)))
+            g.uniform(p + ".bias", (cfg.model_dim,), 0.02)
+    return g.sd.resolve()
+
+
 def synthetic_waveform(index: int, seconds: float = 10.0, sample_rate: int = 16000) -> torch.Tensor:
     """SURVEY.md section 8(d) synthetic audio: 0.1*N(0,1) noise + three tones
     (220/440/1760 Hz, amplitude 0.2) under a 4 Hz envelope, in [-1, 1)."""

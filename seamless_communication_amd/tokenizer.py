@@ -396,3 +396,50 @@ class CharTokenizer:
         if self._spm is not None:
             return int(self._spm.piece_to_id(ch))
         return self._map.get(ch, self.vocab_info.unk_idx)
+
+    def create_raw_encoder(self, *, device=None, pin_memory: bool = False) -> "CharTokenEncoder":
+        """char_tokenizer.py:62-66: the SentencePiece encoder without prefix / suffix symbols."""
+        return CharTokenEncoder(self, device)
+
+    def create_decoder(self) -> "CharTokenDecoder":
+        return CharTokenDecoder(self)
+
+
+class CharTokenEncoder:
+    """``text -> 1-D int64 tensor`` of char ids, and ``encode_as_tokens(text) -> list of pieces`` (fairseq2
+    ``SentencePieceEncoder``).  Without a SentencePiece model the built-in alphabet is applied the way a char-level model
+    with its default normaliser would: runs of white space become one space piece, one more in front of the text."""
+
+    def __init__(self, tokenizer: CharTokenizer, device=None) -> None:
+        self.tokenizer = tokenizer
+        self.device = device
+
+    def encode_as_tokens(self, text: str) -> List[str]:
+        t = self.tokenizer
+        if t._spm is not None:
+            return list(t._spm.encode(text, out_type=str))
+        words = text.split()
+        return list(SPACE + SPACE.join(words)) if words else []
+
+    def __call__(self, text: str):
+        import torch
+
+        t = self.tokenizer
+        ids = list(t._spm.encode(text)) if t._spm is not None else [t.token_to_index(c) for c in self.encode_as_tokens(text)]
+        return torch.tensor(ids, dtype=torch.int64, device=self.device)
+
+
+class CharTokenDecoder:
+    """1-D tensor of char ids -> text (fairseq2 ``SentencePieceDecoder``); control symbols decode to nothing."""
+
+    def __init__(self, tokenizer: CharTokenizer) -> None:
+        self.tokenizer = tokenizer
+
+    def __call__(self, token_indices) -> str:
+        t = self.tokenizer
+        ids = [int(i) for i in (token_indices.tolist() if hasattr(token_indices, "tolist") else token_indices)]
+        if t._spm is not None:
+            return t._spm.decode(ids)
+        inv = {v: k for k, v in t._map.items()}
+        text = "".join(inv.get(i, "") if i != t.vocab_info.unk_idx else " \u2047 " for i in ids)
+        return text.replace(SPACE, " ").lstrip(" ")
