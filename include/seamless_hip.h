@@ -404,6 +404,44 @@ int sc_align(sc_aligner* a, const int32_t* h_text_ids, int32_t n, int32_t s_text
              const int32_t* h_unit_ids, int32_t s_unit, const int32_t* h_unit_lens, int32_t* h_durations,
              float* d_lprob_or_null);
 
+/* UnitExtractor (the `xlsr2_1b_v2` card + a k-means table; added within ABI v10, purely additive).  A handle of its own.
+ * Configuration as models/unit_extractor/wav2vec2_layer_output.py:23-53 (model_dim 1280, 16 heads, FFN 5120, 48 layers,
+ * extractor (512,10,5) + 4 x (512,3,2) + 2 x (512,2,2) with bias and per-layer LayerNorm, position conv k = 128 in 16 groups).
+ * The head dimension model_dim / heads must be 64 or 80.  Tensor names are fairseq2's:
+ *   encoder_frontend.feature_extractor.layers.{i}.conv.{weight,bias}, ...layers.{i}.layer_norm.{weight,bias},
+ *   encoder_frontend.post_extract_layer_norm.*, encoder_frontend.model_dim_proj.*,
+ *   encoder_frontend.pos_encoder.conv.{weight,bias} - `weight` [model_dim][model_dim / groups][k] with the weight-norm
+ *   (weight_g, weight_v, dim = 2) already folded, kept as fp32,
+ *   encoder.layers.{i}.{self_attn_layer_norm,ffn_layer_norm}.*, encoder.layers.{i}.self_attn.{q,k,v,output}_proj.*,
+ *   encoder.layers.{i}.ffn.{inner,output}_proj.*, and kmeans.centroids [model_dim][num_centroids] (kmeans.py:19-21).
+ * Linear / Conv1d weights are held as fp16, everything else as fp32. */
+#define SC_UE_MAX_FE_LAYERS 8
+typedef struct sc_unit_extractor_config {
+    int32_t abi_version; /* must be SC_ABI_VERSION */
+    int32_t model_dim, heads, ffn_dim, layers;
+    int32_t feature_dim; /* width of the convolutional feature extractor */
+    int32_t fe_layers;   /* <= SC_UE_MAX_FE_LAYERS; layer 0 has one input channel */
+    int32_t fe_kernel[SC_UE_MAX_FE_LAYERS], fe_stride[SC_UE_MAX_FE_LAYERS];
+    int32_t pos_conv_kernel, pos_conv_groups;
+    int32_t num_centroids;
+} sc_unit_extractor_config;
+typedef struct sc_unit_extractor sc_unit_extractor;
+sc_unit_extractor* sc_unit_extractor_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_unit_extractor_config* cfg, int device);
+void sc_unit_extractor_free(sc_unit_extractor* u);
+/* frames the extractor table yields for num_samples samples: floor((L - k) / s) + 1 per layer, 0 when the input is too short */
+int32_t sc_unit_extractor_num_frames(const sc_unit_extractor_config* cfg, int64_t num_samples);
+/* UnitExtractor.predict (unit_extractor.py:62-98) on a ragged batch of mono 16 kHz waveforms: h_wav [n][wav_stride] on the
+ * host, h_num_samples [n].  Every item is normalised over its own samples (an odd length counts one more sample of value 1.0,
+ * the reference's Collater(pad_value=1, pad_to_multiple=2); the frame count comes from the unpadded length), runs the feature
+ * extractor, the projection, the position encoder and Transformer layers 0 .. out_layer_idx - later layers are not run, the
+ * final encoder LayerNorm is not applied - and the k-means arg-min (lowest index among equal distances).
+ * h_units [n][max_frames] int32 (zeros behind an item's frames), h_frames [n]; d_features_or_null: device buffer
+ * [n][longest item's frames][model_dim] that receives the layer output (rows behind an item's frames are undefined).
+ * SC_ERR_INVALID, with nothing launched: out_layer_idx outside 0 .. layers-1, an item with fewer samples than one frame needs
+ * or with more than 4096 frames (1 310 800 samples at the xlsr2_1b_v2 table), max_frames below the longest item. */
+int sc_extract_units(sc_unit_extractor* u, const float* h_wav, int32_t n, int64_t wav_stride, const int32_t* h_num_samples,
+                     int32_t out_layer_idx, int32_t* h_units, int32_t max_frames, int32_t* h_frames, float* d_features_or_null);
+
 /* The kernel-level test hooks (sc_op_*) and the dispatch introspection the parity tests drive are exported too but are NOT part
  * of the drop-in boundary: include/seamless_hip_internal.h. */
 

@@ -256,6 +256,20 @@ int sc_op_align_lprob(const float* d_text, const float* d_feat, int32_t n, int32
                       const int32_t* h_text_lens, const int32_t* h_feat_lens, float temperature, float* d_lprob);
 int sc_op_mas(const float* d_lprob, int32_t n, int32_t s_text, int32_t s_feat, const int32_t* h_text_lens, const int32_t* h_feat_lens,
               int32_t* h_durations);
+/* UnitExtractor kernels by themselves (k_attn80.hip, k_w2v2.hip; tests/test_unit_extractor_gpu.py).
+ * sc_op_attention_hd: plain attention with a key-length mask at head_dim 64 (the kernel of sc_op_attention) or 80.
+ * sc_op_w2v2_frontend: utterance statistics (d_stats [nb][2] = mean, 1/sqrt(var + 1e-5); odd lengths count one more sample of
+ *   1.0) and the first extractor layer with its LayerNorm + GELU fused: d_w [C][k], d_out [nb][t_rows][C].
+ * sc_op_w2v2_pos_conv: d_y = d_x + GELU(grouped Conv1d_k(d_x) + bias), last step dropped; d_w [C][C / groups][k] fp32.
+ * sc_op_kmeans: d_idx[r] = argmin_j |x_r - c_j|^2 for d_centroids [C][K] fp32 (lowest j among equal distances). */
+int sc_op_attention_hd(const float* d_q, const float* d_k, const float* d_v, float* d_out, int32_t nb, int32_t heads, int32_t sq, int32_t skv,
+                       int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, const int32_t* d_kv_lens, int32_t head_dim);
+int sc_op_w2v2_frontend(const float* d_wav, int64_t wav_stride, const int32_t* h_num_samples, int32_t nb, const float* d_w, const float* d_bias,
+                        const float* d_gamma, const float* d_beta, int32_t C, int32_t k, int32_t stride, float* d_out, int32_t t_rows,
+                        float* d_stats);
+int sc_op_w2v2_pos_conv(const float* d_x, const float* d_w, const float* d_bias, float* d_y, int32_t nb, int32_t T, int32_t C, int32_t groups,
+                        int32_t k, const int32_t* d_lens);
+int sc_op_kmeans(const float* d_x, const float* d_centroids, int32_t rows, int32_t C, int32_t K, int32_t* d_idx);
 
 #ifdef __cplusplus
 }

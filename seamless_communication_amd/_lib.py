@@ -97,6 +97,13 @@ class sc_engine_stats(C.Structure):
     ]
 
 
+class sc_unit_extractor_config(C.Structure):
+    _fields_ = [
+        ("abi_version", _i), ("model_dim", _i), ("heads", _i), ("ffn_dim", _i), ("layers", _i), ("feature_dim", _i), ("fe_layers", _i),
+        ("fe_kernel", _i * 8), ("fe_stride", _i * 8), ("pos_conv_kernel", _i), ("pos_conv_groups", _i), ("num_centroids", _i),
+    ]
+
+
 class sc_aligner_config(C.Structure):
     _fields_ = [
         ("abi_version", _i), ("model_dim", _i), ("feat_dim", _i), ("text_layers", _i), ("feat_layers", _i),
@@ -159,6 +166,14 @@ SIGNATURES = {
     "sc_align": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P, _P, _P]),
     "sc_op_align_lprob": (C.c_int, [_P, _P, _i, _i, _i, _i, _P, _P, C.c_float, _P]),
     "sc_op_mas": (C.c_int, [_P, _i, _i, _i, _P, _P, _P]),
+    "sc_unit_extractor_load": (_P, [C.POINTER(sc_tensor_desc), C.c_size_t, C.POINTER(sc_unit_extractor_config), C.c_int]),
+    "sc_unit_extractor_free": (None, [_P]),
+    "sc_unit_extractor_num_frames": (C.c_int32, [C.POINTER(sc_unit_extractor_config), C.c_int64]),
+    "sc_extract_units": (C.c_int, [_P, _P, _i, C.c_int64, _P, _i, _P, _i, _P, _P]),
+    "sc_op_attention_hd": (C.c_int, [_P, _P, _P, _P, _i, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _i]),
+    "sc_op_w2v2_frontend": (C.c_int, [_P, C.c_int64, _P, _i, _P, _P, _P, _P, _i, _i, _i, _P, _i, _P]),
+    "sc_op_w2v2_pos_conv": (C.c_int, [_P, _P, _P, _P, _i, _i, _i, _i, _i, _P]),
+    "sc_op_kmeans": (C.c_int, [_P, _P, _i, _i, _i, _P]),
     "sc_op_knob": (C.c_int, [C.c_char_p, C.c_int]),
     "sc_op_force_general_gemm": (C.c_int, [C.c_int]),
     "sc_op_voc_pack_plan": (C.c_int32, [_PI, C.c_int32, C.c_int64, _PI, C.c_int32]),

@@ -61,6 +61,11 @@ def nar_t2u_aligner_card() -> Dict[str, Any]:
     }
 
 
+def xlsr2_1b_v2_card() -> Dict[str, Any]:
+    """cards/xlsr2_1b_v2.yaml of the reference; the published checkpoint is not reachable offline."""
+    return {"name": "xlsr2_1b_v2", "model_type": "wav2vec2", "model_arch": "xlsr2_1b_v2", "checkpoint": "synthetic://0"}
+
+
 def load_card_file(path: str) -> Dict[str, Any]:
     """Read one reference-schema YAML card from a local file (no asset store,
     no network); ``base:`` chains are resolved by the caller."""

@@ -265,3 +265,35 @@ def load_converted_checkpoint(path: str, kind: str, char_spm_tokens: Optional[Se
     if kind == "aligner":
         return convert_unity2_aligner_checkpoint(ckpt, char_spm_tokens=char_spm_tokens)
     return convert_unity_checkpoint(ckpt, char_spm_tokens=char_spm_tokens)
+
+
+def convert_wav2vec2_checkpoint(checkpoint: Mapping[str, Any]) -> Dict[str, torch.Tensor]:
+    """fairseq wav2vec 2.0 names -> fairseq2's, the shared entries of models/conformer_shaw/loader.py:44-71 plus
+    ``final_layer_norm`` -> ``ffn_layer_norm``; quantiser, mask and projection-head tensors are dropped.  A dict that is
+    already fairseq2-keyed (``encoder_frontend.*``) passes through."""
+    sd = checkpoint.get("model", checkpoint)
+    if any(k.startswith("encoder_frontend.") for k in sd):
+        return {k: v for k, v in sd.items() if k.startswith(("encoder_frontend.", "encoder."))}
+    rules = [
+        (re.compile(r"^encoder\.layers\.([0-9]+)\.self_attn\.out_proj\."), r"encoder.layers.\1.self_attn.output_proj."),
+        (re.compile(r"^encoder\.layers\.([0-9]+)\.fc1\."), r"encoder.layers.\1.ffn.inner_proj."),
+        (re.compile(r"^encoder\.layers\.([0-9]+)\.fc2\."), r"encoder.layers.\1.ffn.output_proj."),
+        (re.compile(r"^encoder\.layers\.([0-9]+)\.final_layer_norm\."), r"encoder.layers.\1.ffn_layer_norm."),
+        (re.compile(r"^encoder\.pos_conv\.0\."), r"encoder_frontend.pos_encoder.conv."),
+        (re.compile(r"^feature_extractor\.conv_layers\.([0-9]+)\.0\."), r"encoder_frontend.feature_extractor.layers.\1.conv."),
+        (re.compile(r"^feature_extractor\.conv_layers\.([0-9]+)\.2\.1\."), r"encoder_frontend.feature_extractor.layers.\1.layer_norm."),
+        (re.compile(r"^layer_norm\."), r"encoder_frontend.post_extract_layer_norm."),
+        (re.compile(r"^post_extract_proj\."), r"encoder_frontend.model_dim_proj."),
+    ]
+    dropped = ("quantizer.", "project_q.", "final_proj.", "mask_emb", "encoder.layer_norm.", "mlm_proj.")
+    out: Dict[str, torch.Tensor] = {}
+    for k, v in sd.items():
+        if k.startswith(dropped):
+            continue
+        for pat, rep in rules:
+            k2, n = pat.subn(rep, k)
+            if n:
+                k = k2
+                break
+        out[k] = v
+    return out

@@ -14,7 +14,7 @@ The S2ST path is speech in -> text -> units -> waveform; the NLLB text encoder
 from __future__ import annotations
 
 from dataclasses import dataclass, field, asdict
-from typing import List
+from typing import List, Tuple
 
 
 @dataclass
@@ -144,6 +144,47 @@ class AlignerConfig:
     unit_vocab_size: int = 10082
     unit_pad_idx: int = 1
     char_vocab_size: int = 10943
+
+
+@dataclass
+class Wav2Vec2UnitConfig:
+    """wav2vec 2.0 encoder of the UnitExtractor (models/unit_extractor/wav2vec2_layer_output.py:23-53, ``xlsr2_1b_v2``):
+    pre-norm Transformer, convolutional position encoder, LayerNorm after every extractor convolution, no feature LayerNorm."""
+
+    name: str = "xlsr2_1b_v2"
+    model_dim: int = 1280
+    num_heads: int = 16
+    ffn_dim: int = 5120
+    num_layers: int = 48
+    feature_dim: int = 512
+    layer_descs: Tuple[Tuple[int, int, int], ...] = ((512, 10, 5),) + ((512, 3, 2),) * 4 + ((512, 2, 2),) * 2
+    pos_conv_kernel: int = 128
+    pos_conv_groups: int = 16
+
+    def num_frames(self, num_samples: int) -> int:
+        """floor((L - k) / s) + 1 per extractor layer; 0 when the input is too short for one frame."""
+        n = int(num_samples)
+        for _, k, s in self.layer_descs:
+            if n < k:
+                return 0
+            n = (n - k) // s + 1
+        return n
+
+    def min_samples(self) -> int:
+        n = 1
+        for _, k, s in reversed(self.layer_descs):
+            n = (n - 1) * s + k
+        return n
+
+
+def xlsr2_1b_v2(num_layers: int = 48) -> Wav2Vec2UnitConfig:
+    return Wav2Vec2UnitConfig(num_layers=num_layers)
+
+
+def tiny_w2v2_config(head_dim: int = 80) -> Wav2Vec2UnitConfig:
+    """A small encoder of the same structure for parity tests: 2 heads of 80 (the XLS-R head size) or 64, conv width 32."""
+    return Wav2Vec2UnitConfig(name=f"tiny_w2v2_{head_dim}", model_dim=2 * head_dim, num_heads=2, ffn_dim=320 if head_dim == 80 else 256, num_layers=3,
+                              feature_dim=32, layer_descs=((32, 10, 5),) + ((32, 3, 2),) * 4 + ((32, 2, 2),) * 2)
 
 
 def nar_t2u_aligner() -> AlignerConfig:

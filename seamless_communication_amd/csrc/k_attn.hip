@@ -400,6 +400,11 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
 static bool g_attn_attr_set = false;
 
 void launch_attention(const AttnArgs& a, hipStream_t s) {
+    if (a.head_dim == 80) {
+        launch_attention80(a, s);
+        return;
+    }
+    SC_CHECK(a.head_dim == HD, "attention: head_dim=%d (64 and 80 exist)", a.head_dim);
     SC_CHECK(a.nb > 0 && a.heads > 0 && a.Sq > 0 && a.Skv > 0, "attention: empty problem");
     SC_CHECK(a.out || (a.out_hi && a.out_lo && a.ldoh % 4 == 0), "attention: no output");
     SC_CHECK(a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.ldv % 4 == 0 && a.ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0,

@@ -35,6 +35,7 @@ __device__ __forceinline__ float apply_act(float v, int act) {
     if (act == ACT_RELU) return v > 0.f ? v : 0.f;
     if (act == ACT_SILU) return v / (1.f + expf(-v));
     if (act == ACT_TANH) return tanhf(v);
+    if (act == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
     return v;
 }
 
@@ -297,6 +298,7 @@ void launch_gemm(const GemmArgs& a, hipStream_t s) {
     SC_CHECK(a.rows_per_batch > 0 && a.cin > 0, "gemm: rows_per_batch/cin unset");
     // SC_GEMM_GENERAL=1 forces the general kernel (A/B timing of the two paths; same bits either way)
     static const bool env_general = knob::is_set("SC_GEMM_GENERAL");
+    SC_CHECK(a.act >= ACT_NONE && a.act <= ACT_GELU, "gemm: unknown activation %d", a.act);
     if (!env_general && !g_force_general_gemm.load(std::memory_order_relaxed) && gemm_fast_eligible(a)) {
         launch_gemm_fast(a, s);
         return;

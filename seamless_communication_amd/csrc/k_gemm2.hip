@@ -41,6 +41,7 @@ __device__ __forceinline__ float act_fn(float v) {
     if (ACT == ACT_RELU) return v > 0.f ? v : 0.f;
     if (ACT == ACT_SILU) return v / (1.f + expf(-v));
     if (ACT == ACT_TANH) return tanhf(v);
+    if (ACT == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
     return v;
 }
 
@@ -362,7 +363,8 @@ __global__ __launch_bounds__(256) void gemm_fast_kernel(GemmArgs p, int tiles_n,
     if (p.act == ACT_NONE) SC_EPI(ACT_NONE);
     else if (p.act == ACT_RELU) SC_EPI(ACT_RELU);
     else if (p.act == ACT_SILU) SC_EPI(ACT_SILU);
-    else SC_EPI(ACT_TANH);
+    else if (p.act == ACT_TANH) SC_EPI(ACT_TANH);
+    else SC_EPI(ACT_GELU);
 #undef SC_EPI
 }
 
@@ -576,7 +578,8 @@ __global__ __launch_bounds__(256) void gemm_fast2_kernel(GemmArgs p, int tiles_n
     if (p.act == ACT_NONE) SC_EPI(ACT_NONE);
     else if (p.act == ACT_RELU) SC_EPI(ACT_RELU);
     else if (p.act == ACT_SILU) SC_EPI(ACT_SILU);
-    else SC_EPI(ACT_TANH);
+    else if (p.act == ACT_TANH) SC_EPI(ACT_TANH);
+    else SC_EPI(ACT_GELU);
 #undef SC_EPI
 }
 
@@ -643,6 +646,7 @@ bool gemm_fast_eligible(const GemmArgs& a) {
 
 // Tile choice mirrors launch_gemm (k_gemm.hip) so that both paths cover the same shapes.
 void launch_gemm_fast(const GemmArgs& a, hipStream_t s) {
+    SC_CHECK(a.act >= ACT_NONE && a.act <= ACT_GELU, "gemm (fast path): activation %d has no epilogue here", a.act);
     const int64_t tiles128 = (int64_t)cdiv(a.M, 128) * cdiv(a.N, 128) * a.phases;
     if (a.N <= 32) {
         if ((int64_t)cdiv(a.M, 256) * a.phases >= 512) launch_fast_cfg<256, 32, 4, 1>(a, s);

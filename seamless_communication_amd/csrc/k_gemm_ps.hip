@@ -639,6 +639,7 @@ int ps_tile(int M, int N) {
 void launch_gemm_presplit(const GemmPsArgs& a, hipStream_t s) {
     SC_CHECK(a.Ah && (a.Al || !a.split) && a.W && (a.C || a.Ch || a.amax), "presplit gemm: null operand");
     SC_CHECK(a.Ch || !a.Cl, "presplit gemm: a lo output plane needs its hi plane");
+    SC_CHECK(a.act >= ACT_NONE && a.act <= ACT_TANH, "presplit gemm: activation %d has no epilogue here", a.act);
     SC_CHECK(a.M > 0 && a.N > 0 && a.K > 0 && a.K % PBK == 0, "presplit gemm: M=%d N=%d K=%d (K must be a multiple of 32)", a.M, a.N, a.K);
     SC_CHECK(a.lda % 8 == 0 && a.ldw % 8 == 0 && a.ldw >= a.K, "presplit gemm: lda=%lld ldw=%lld", (long long)a.lda,
              (long long)a.ldw);

@@ -258,6 +258,7 @@ int skinny_argmax_tiles(int M, int N) {
 
 void launch_skinny(const SkinnyArgs& a0, hipStream_t s) {
     SkinnyArgs a = a0;
+    SC_CHECK(a.act >= ACT_NONE && a.act <= ACT_TANH, "skinny gemm: activation %d has no epilogue here", a.act);
     SC_CHECK(a.M >= 1 && a.M <= 64, "skinny gemm: M=%d out of range [1,64]", a.M);
     SC_CHECK(a.K % 64 == 0 && a.ldw % 8 == 0 && a.lda % 4 == 0, "skinny gemm: K=%d ldw=%lld lda=%lld alignment", a.K,
              (long long)a.ldw, (long long)a.lda);

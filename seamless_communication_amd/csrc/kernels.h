@@ -18,7 +18,9 @@
 
 namespace sc {
 
-enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_TANH = 3 };
+// ACT_GELU: exact (erf) GELU; implemented by launch_gemm (both the fast and the general kernel) and the LayerNorm
+// launchers - launch_gemm_presplit and launch_skinny refuse it
+enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_TANH = 3, ACT_GELU = 4 };
 enum InAct { IN_NONE = 0, IN_LRELU_01 = 1, IN_LRELU_001 = 2 };
 
 struct GemmArgs {
@@ -509,8 +511,12 @@ struct AttnArgs {
     __half* out_hi = nullptr;
     __half* out_lo = nullptr;
     int64_t ldoh = 0;
+    // 64: the kernel of k_attn.hip (every mode above).  80: k_attn80.hip (wav2vec 2.0 / XLS-R), plain mode with kv_lens only,
+    // head h at column h*80, logits scaled by 80^-0.5
+    int head_dim = 64;
 };
 void launch_attention(const AttnArgs& a, hipStream_t s);
+void launch_attention80(const AttnArgs& a, hipStream_t s);  // k_attn80.hip; reached through launch_attention
 
 // Single-query attention over a KV cache (decoder step).  q: [nb][heads*64];
 // key/value row j of (b, h) lives at base + b*cache_bs + j*cache_ld + h*64.  If k_new != null the
@@ -720,6 +726,29 @@ int mas_max_feat();
 size_t mas_bits_words(int max_text_len, int Sf);
 void launch_mas(const float* lprob, int n, int St, int Sf, const int* d_text_lens, const int* d_feat_lens, int max_text_len,
                 int max_feat_len, unsigned long long* bits, int* dur, hipStream_t s);
+
+// ---- wav2vec 2.0 front end of the UnitExtractor (k_w2v2.hip; reference models/unit_extractor) ---------------------
+// stats[2 i] = mean, stats[2 i + 1] = 1 / sqrt(biased variance + 1e-5) of item i's samples (F.layer_norm over the utterance).
+// An odd num_samples[i] counts one more sample of value 1.0 (the reference's Collater(pad_value=1, pad_to_multiple=2)).
+void launch_w2v2_wave_stats(const float* wav, int64_t wav_stride, const int* num_samples, int nb, float* stats, hipStream_t s);
+// First extractor layer on the normalised waveform: Conv1d(1 -> C, k taps, stride, bias, no padding), LayerNorm over the C
+// channels (eps 1e-5) and exact GELU in one pass; out [nb][t_rows][C], row t of item i from samples t*stride .. + k - 1
+// (samples behind the item's - padded - length read as zeros).  w fp32 [C][k].  C % 4 == 0, C <= 1024, k <= 16.
+void launch_w2v2_conv0(const float* wav, int64_t wav_stride, const int* num_samples, const float* stats, int nb, const float* w,
+                       const float* bias, const float* gamma, const float* beta, int C, int k, int stride, float* out, int t_rows,
+                       hipStream_t s);
+// Position encoder: y = x + GELU(conv(x) + bias), conv = grouped Conv1d(C -> C, k taps, padding k/2, `groups` groups) with its
+// last output step dropped (k even); x / y [nb][T][C] fp32 (y != x), rows t >= lens[i] of x read as zeros (lens nullable).
+// w fp32 packed [group][tap][c_in][c_out] (launch_w2v2_pack_pos_weight from the checkpoint's [C][C/groups][k]).
+// C / groups <= 128.
+void launch_w2v2_pack_pos_weight(const float* w, float* dst, int C, int groups, int k, hipStream_t s);
+void launch_w2v2_pos_conv(const float* x, const float* w_packed, const float* bias, float* y, int nb, int T, int C, int groups, int k,
+                          const int* lens, hipStream_t s);
+// k-means operands (kmeans.py:24-30 as an arg-max, see model_w2v2.hip): rows of x [rows][C] as planes [rows][2C] = [x | x]
+void launch_w2v2_dup_split(const float* x, int64_t ldx, int rows, int C, __half* hi, __half* lo, hipStream_t s);
+// centroids cent [C][K] fp32 (the reference's transposed layout) -> W [K][2C] = [fp16(c) | fp16(c - fp16(c))] and
+// bias[j] = -||c_hi + c_lo||^2 / 2 (fp32 sum in ascending channel order)
+void launch_w2v2_pack_centroids(const float* cent, int C, int K, __half* W, float* bias, hipStream_t s);
 
 // ---- decode engine (k_engine.hip, engine.hip) ---------------------------------------------------------------------
 // One greedy step chain per GPU shared by every pass in flight.  A ROW STATE r (0 .. rows-1) owns everything that lives as

@@ -654,7 +654,7 @@ void load_model(Model& m, const sc_tensor_desc* t, size_t n) {
 void linear(Model& m, const float* x, int64_t ldx, const Linear& L, const float* res, int64_t ldr, float* y,
             int64_t ldy, int rows, int act, float alpha, bool row_independent) {
     if (rows <= 0) return;
-    if (!row_independent && rows <= 64 && L.in % 64 == 0 && ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
+    if (!row_independent && act != ACT_GELU && rows <= 64 && L.in % 64 == 0 && ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
         SkinnyArgs a;
         a.A = x;
         a.lda = ldx;

@@ -1,7 +1,8 @@
 from .aligner import AlignmentExtractor, word_timestamps
 from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, SequenceGeneratorOptions
 from .transcriber import Transcriber, Transcription, TranscriptionToken, TranscriptionTokenStats
+from .unit_extractor import UnitExtractor
 from .translator import BatchedSpeechOutput, Modality, Task, Translator
 
 __all__ = ["AlignmentExtractor", "BannedSequenceProcessor", "BatchedSpeechOutput", "Modality", "NGramRepeatBlockProcessor", "SequenceGeneratorOptions", "Task", "Transcriber", "Transcription", "TranscriptionToken",
-           "TranscriptionTokenStats", "Translator", "word_timestamps"]
+           "TranscriptionTokenStats", "Translator", "UnitExtractor", "word_timestamps"]

@@ -5,9 +5,10 @@ text, how many units (20 ms each) every character lasts.  The reference computes
 monotonic alignment search per item on the host in Python; here the whole call - embeddings, convolution stacks, distance,
 log-softmax, search and back-track - runs inside libseamless_hip (``sc_align``), batched and ragged.
 
-Not available (``NotImplementedError``): audio input.  The reference turns a waveform into units with ``UnitExtractor``
-(XLS-R 1B + k-means), a second model that is not part of this project: pass units (an integer tensor, or the reference's
-space-separated string).  ``extract_alignments`` (many pairs in one call) and ``word_timestamps`` are additions.
+Audio input: the reference turns a waveform into units with ``UnitExtractor`` (XLS-R 1B + k-means), a second model.  The
+constructor's ``unit_extractor_*`` arguments raise ``NotImplementedError``; assign an ``inference.UnitExtractor`` to the
+``unit_extractor`` attribute (and ``unit_extractor_output_layer``) to send waveforms and paths through it, or pass units (an
+integer tensor, or the reference's space-separated string).  ``extract_alignments`` (many pairs in one call) and ``word_timestamps`` are additions.
 """
 from __future__ import annotations
 
@@ -147,6 +148,11 @@ class AlignmentExtractor:
             return audio.reshape(-1)
         if isinstance(audio, str) and audio and all(p.isdigit() for p in audio.split(" ")):
             return torch.tensor([int(u) for u in audio.split(" ")])
+        if getattr(self, "unit_extractor", None) is not None:
+            # alignment_extractor.py:94: an assigned extractor (inference.UnitExtractor) turns waveforms and paths into units
+            if not self.unit_extractor_output_layer:
+                raise ValueError("set unit_extractor_output_layer (the reference uses 35) next to unit_extractor")
+            return self.unit_extractor.predict(audio, self.unit_extractor_output_layer - 1)
         raise NotImplementedError("audio input (a waveform tensor or a path) needs the UnitExtractor (XLS-R 1B + k-means), which is not "
                                   "part of this project: pass the units as an integer tensor or a space-separated string")
 

@@ -572,3 +572,77 @@ class HipAligner:
         if rf > 1:
             out = postprocess_alignment(out, tl, ul, rf)
         return out, lprob
+
+
+def fold_weight_norm_dim2(weight_g: torch.Tensor, weight_v: torch.Tensor) -> torch.Tensor:
+    """``torch.nn.utils.weight_norm(conv, dim=2)`` of the wav2vec 2.0 position convolution folded once: g * v / |v| with the
+    norm over (out, in) per tap, in float64, returned as fp32."""
+    v = weight_v.detach().to("cpu", torch.float64)
+    g = weight_g.detach().to("cpu", torch.float64).reshape(1, 1, -1)
+    return (g * v / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()).to(torch.float32)
+
+
+class HipUnitExtractor:
+    """wav2vec 2.0 encoder + k-means table resident in one GPU's HBM (``sc_unit_extractor_*``): a handle of its own."""
+
+    def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], centroids: torch.Tensor, device: int = 0) -> None:
+        self.lib = _lib.load_library()
+        self.cfg = cfg
+        self.device_index = int(device)
+        self.device = torch.device("cuda", self.device_index)
+        if not torch.cuda.is_available():
+            raise SeamlessHipError("no HIP device is visible; the HIP path has no CPU fallback")
+        if centroids.dim() != 2 or centroids.shape[0] != cfg.model_dim:
+            raise ValueError(f"centroids must be [model_dim={cfg.model_dim}, K] (the reference's transposed table), got {tuple(centroids.shape)}")
+        sd = {k: v for k, v in state_dict.items() if k.startswith(("encoder_frontend.", "encoder.layers."))}
+        pre = "encoder_frontend.pos_encoder.conv."
+        if pre + "weight_g" in sd:
+            sd[pre + "weight"] = fold_weight_norm_dim2(sd.pop(pre + "weight_g"), sd.pop(pre + "weight_v"))
+        keep16 = (".conv.weight", "_proj.weight")
+        sd = {k: (v.to(torch.float16) if k.endswith(keep16) and not k.startswith(pre) and ".layers.0.conv." not in k else v.to(torch.float32))
+              for k, v in sd.items()}
+        sd["kmeans.centroids"] = centroids.detach().to(torch.float32)
+        descs, keep = _tensor_descs(sd)
+        c = _lib.sc_unit_extractor_config()
+        c.abi_version = _lib.SC_ABI_VERSION
+        c.model_dim, c.heads, c.ffn_dim, c.layers = int(cfg.model_dim), int(cfg.num_heads), int(cfg.ffn_dim), int(cfg.num_layers)
+        c.feature_dim, c.fe_layers = int(cfg.feature_dim), len(cfg.layer_descs)
+        for i, (_, k, s) in enumerate(cfg.layer_descs):
+            c.fe_kernel[i], c.fe_stride[i] = int(k), int(s)
+        c.pos_conv_kernel, c.pos_conv_groups = int(cfg.pos_conv_kernel), int(cfg.pos_conv_groups)
+        c.num_centroids = int(centroids.shape[1])
+        self._c = c
+        self.handle = self.lib.sc_unit_extractor_load(descs, len(sd), C.byref(c), self.device_index)
+        if not self.handle:
+            msg = self.lib.sc_last_error()
+            raise SeamlessHipError(f"sc_unit_extractor_load failed: {msg.decode() if msg else '?'}")
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self.lib.sc_unit_extractor_free(self.handle)
+            self.handle = None
+
+    def __del__(self) -> None:  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def extract(self, waves: Sequence[np.ndarray], out_layer_idx: int, return_features: bool = False):
+        """Ragged batch of mono fp32 waveforms -> (units (n, longest) int64 zero-padded, frames (n,), layer output
+        (n, longest, model_dim) on the device or None) in ONE device call."""
+        n = len(waves)
+        if n == 0:
+            raise ValueError("extract() takes at least one waveform")
+        ns = _i32([len(w) for w in waves])
+        stride = int(ns.max())
+        wav = np.zeros((n, stride), dtype=np.float32)
+        for b, w in enumerate(waves):
+            wav[b, : ns[b]] = np.asarray(w, dtype=np.float32).reshape(-1)
+        tf = max(1, max(self.cfg.num_frames(int(x)) for x in ns))
+        units = np.zeros((n, tf), dtype=np.int32)
+        frames = np.zeros(n, dtype=np.int32)
+        feats = torch.empty(n, tf, self.cfg.model_dim, dtype=torch.float32, device=self.device) if return_features else None
+        check(self.lib.sc_extract_units(self.handle, _ptr(wav), n, stride, _ptr(ns), int(out_layer_idx), _ptr(units), tf, _ptr(frames), _ptr(feats)),
+              "sc_extract_units")
+        return units.astype(np.int64), frames, feats

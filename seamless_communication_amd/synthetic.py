@@ -524,3 +524,45 @@ def synthetic_waveform(index: int, seconds: float = 10.0, sample_rate: int = 160
     for f in (220.0, 440.0, 1760.0):
         x = x + 0.2 * env * torch.sin(2 * math.pi * f * t + 0.3 * index)
     return x.clamp_(-1.0, 1.0 - 2**-15).to(torch.float32)
+
+
+def make_w2v2_state_dict(cfg, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """State dict of the UnitExtractor's wav2vec 2.0 encoder under fairseq2's names (``cfg``: a
+    :class:`~seamless_communication_amd.config.Wav2Vec2UnitConfig`); every value is fp16-representable."""
+    g = torch.Generator().manual_seed(seed)
+
+    def rnd(*shape, scale=1.0):
+        return (torch.randn(*shape, generator=g) * scale).to(torch.float16).to(torch.float32)
+
+    sd: Dict[str, torch.Tensor] = {}
+    F, M = cfg.feature_dim, cfg.model_dim
+    cin = 1
+    for i, (co, k, _) in enumerate(cfg.layer_descs):
+        p = f"encoder_frontend.feature_extractor.layers.{i}."
+        sd[p + "conv.weight"] = rnd(co, cin, k, scale=(cin * k) ** -0.5)
+        sd[p + "conv.bias"] = rnd(co, scale=0.1)
+        sd[p + "layer_norm.weight"] = 1 + rnd(co, scale=0.1)
+        sd[p + "layer_norm.bias"] = rnd(co, scale=0.1)
+        cin = co
+    sd["encoder_frontend.post_extract_layer_norm.weight"] = 1 + rnd(F, scale=0.1)
+    sd["encoder_frontend.post_extract_layer_norm.bias"] = rnd(F, scale=0.1)
+    sd["encoder_frontend.model_dim_proj.weight"] = rnd(M, F, scale=F ** -0.5)
+    sd["encoder_frontend.model_dim_proj.bias"] = rnd(M, scale=0.1)
+    cg, K = M // cfg.pos_conv_groups, cfg.pos_conv_kernel
+    sd["encoder_frontend.pos_encoder.conv.weight_v"] = rnd(M, cg, K, scale=(cg * K) ** -0.5)
+    sd["encoder_frontend.pos_encoder.conv.weight_g"] = (sd["encoder_frontend.pos_encoder.conv.weight_v"].pow(2).sum(dim=(0, 1), keepdim=True).sqrt()
+                                                        * (1 + rnd(1, 1, K, scale=0.1))).to(torch.float16).to(torch.float32)
+    sd["encoder_frontend.pos_encoder.conv.bias"] = rnd(M, scale=0.1)
+    for i in range(cfg.num_layers):
+        p = f"encoder.layers.{i}."
+        for ln in ("self_attn_layer_norm", "ffn_layer_norm"):
+            sd[p + ln + ".weight"] = 1 + rnd(M, scale=0.1)
+            sd[p + ln + ".bias"] = rnd(M, scale=0.1)
+        for pr in ("q_proj", "k_proj", "v_proj", "output_proj"):
+            sd[p + f"self_attn.{pr}.weight"] = rnd(M, M, scale=M ** -0.5)
+            sd[p + f"self_attn.{pr}.bias"] = rnd(M, scale=0.1)
+        sd[p + "ffn.inner_proj.weight"] = rnd(cfg.ffn_dim, M, scale=M ** -0.5)
+        sd[p + "ffn.inner_proj.bias"] = rnd(cfg.ffn_dim, scale=0.1)
+        sd[p + "ffn.output_proj.weight"] = rnd(M, cfg.ffn_dim, scale=cfg.ffn_dim ** -0.5)
+        sd[p + "ffn.output_proj.bias"] = rnd(M, scale=0.1)
+    return sd
