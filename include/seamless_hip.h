@@ -442,6 +442,34 @@ int32_t sc_unit_extractor_num_frames(const sc_unit_extractor_config* cfg, int64_
 int sc_extract_units(sc_unit_extractor* u, const float* h_wav, int32_t n, int64_t wav_stride, const int32_t* h_num_samples,
                      int32_t out_layer_idx, int32_t* h_units, int32_t max_frames, int32_t* h_frames, float* d_features_or_null);
 
+/* ProsodyEncoder: the ECAPA-TDNN of SeamlessExpressive (models/pretssel/ecapa_tdnn.py, arch `base` of ecapa_tdnn_builder.py;
+ * added within ABI v10, purely additive).  A handle of its own.  n_blocks = entries of channels / kernel_sizes / dilations in
+ * use (5 at `base`: one TDNN block, three SE-Res2Net blocks, the aggregation).  Tensor names are the module's own:
+ *   blocks.0.{conv,norm}.*, blocks.{i}.tdnn1.{conv,norm}.*, blocks.{i}.res2net_block.blocks.{j}.{conv,norm}.*,
+ *   blocks.{i}.tdnn2.{conv,norm}.*, blocks.{i}.se_block.conv{1,2}.*, mfa.{conv,norm}.*, asp.tdnn.{conv,norm}.*, asp.conv.*,
+ *   asp_norm.*, fc.*; Conv1d weights [out][in][k].  Conv1d weights are held as fp16, everything else as fp32.
+ * Limits (SC_ERR_INVALID from sc_prosody_encoder_load): channels[0 .. n_blocks-2] equal (no shortcut convolution) and a
+ * multiple of 32, channels[n_blocks-1] = (n_blocks - 2) * channels[0], kernel 3 in the SE-Res2Net blocks and 1 in the
+ * aggregation, a Res2Net chunk channels / res2net_scale of 32 or 64, res2net_scale 2..8, dilations 1..8, global_context = 1. */
+#define SC_PE_MAX_BLOCKS 8
+typedef struct sc_prosody_encoder_config {
+    int32_t abi_version; /* must be SC_ABI_VERSION */
+    int32_t input_dim, embed_dim, res2net_scale, se_channels, attention_channels, global_context, n_blocks;
+    int32_t channels[SC_PE_MAX_BLOCKS], kernel_sizes[SC_PE_MAX_BLOCKS], dilations[SC_PE_MAX_BLOCKS];
+} sc_prosody_encoder_config;
+typedef struct sc_prosody_encoder sc_prosody_encoder;
+sc_prosody_encoder* sc_prosody_encoder_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_prosody_encoder_config* cfg, int device);
+void sc_prosody_encoder_free(sc_prosody_encoder* p);
+/* ECAPA_TDNN.forward (ecapa_tdnn.py:111-143) on a padded batch: d_fbank [n][t_rows][input_dim] fp32 on the device,
+ * h_lens_or_null [n] valid frames per item (NULL: every item has t_rows frames and no mask is applied, the reference's
+ * padding_mask=None), d_out [n][embed_dim]: L2-normalised rows.  Rows of d_fbank behind an item's length are read as zeros; the
+ * TDNN blocks then compute those frames like real ones, as the reference does on a zero-padded batch, so an item's result in a
+ * ragged batch is the reference's padded-batch result, not the item's result alone.  d_gcmvn_mean_or_null / d_gcmvn_std_or_null
+ * [input_dim] (both or neither): (x - mean) / std is applied to the frames in front of each length on the way in.
+ * SC_ERR_INVALID, with nothing launched: a length outside 1..t_rows, t_rows above 4096, n outside 1..4096. */
+int sc_prosody_encode(sc_prosody_encoder* p, const float* d_fbank, int32_t n, int32_t t_rows, const int32_t* h_lens_or_null,
+                      const float* d_gcmvn_mean_or_null, const float* d_gcmvn_std_or_null, float* d_out);
+
 /* The kernel-level test hooks (sc_op_*) and the dispatch introspection the parity tests drive are exported too but are NOT part
  * of the drop-in boundary: include/seamless_hip_internal.h. */
 

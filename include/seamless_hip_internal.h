@@ -271,6 +271,29 @@ int sc_op_w2v2_pos_conv(const float* d_x, const float* d_w, const float* d_bias,
                         int32_t k, const int32_t* d_lens);
 int sc_op_kmeans(const float* d_x, const float* d_centroids, int32_t rows, int32_t C, int32_t K, int32_t* d_idx);
 
+/* ProsodyEncoder kernels by themselves (k_ecapa.hip; tests/test_prosody_encoder_gpu.py).  Lengths are host arrays (NULL: every
+ * item has T frames); a length outside 1..T is refused before anything is launched.
+ * sc_op_ecapa_chain: the fused Res2Net chain of one SE-Res2Net block: d_x / d_out [nb][T][scale * chunk]; d_w [scale - 1][chunk]
+ *   [chunk][3] fp16 (Conv1d layout, packed here), d_bias / d_gamma / d_beta [scale - 1][chunk].  sc_op_ecapa_chain_tile: frames
+ *   a workgroup stores at this scale and dilation (<= 0: unsupported).
+ * sc_op_ecapa_relu_ln: y = act(LayerNorm(relu(x + item_bias[row / t_per_item]))), eps 1e-12, act 0 or 3 (tanh); d_item_bias nullable.
+ * sc_op_ecapa_se_gate: d_gate [nb][C] = sigmoid(W2 relu(W1 mean_t(x) + b1) + b2); w1 [S][C], w2 [C][S] fp16.
+ * sc_op_ecapa_pool: d_gstats [nb][2C] (nullable) = masked mean | std of d_x [nb][T][C]; d_pooled [nb][2C] (nullable, needs
+ *   d_logits [nb][T][C]) = attentive mean | std under the masked softmax over time.
+ * sc_op_ecapa_tail: d_out [nb][E] = normalize(W LayerNorm(pooled) + b); d_w [E][C2] fp16.
+ * sc_op_prosody_last_launches: kernel launches of the handle's last sc_prosody_encode call. */
+int sc_op_ecapa_chain(const float* d_x, const void* d_w_f16, const float* d_bias, const float* d_gamma, const float* d_beta, float* d_out, int32_t nb,
+                      int32_t T, int32_t chunk, int32_t scale, int32_t dil);
+int32_t sc_op_ecapa_chain_tile(int32_t chunk, int32_t scale, int32_t dil);
+int sc_op_ecapa_relu_ln(const float* d_x, const float* d_item_bias, int32_t t_per_item, const float* d_gamma, const float* d_beta, float* d_y,
+                        int32_t rows, int32_t C, int32_t act);
+int sc_op_ecapa_se_gate(const float* d_x, int32_t nb, int32_t T, const int32_t* h_lens, int32_t C, int32_t S, const void* d_w1_f16, const float* d_b1,
+                        const void* d_w2_f16, const float* d_b2, float* d_gate);
+int sc_op_ecapa_pool(const float* d_x, const float* d_logits, int32_t nb, int32_t T, int32_t C, const int32_t* h_lens, float* d_pooled, float* d_gstats);
+int sc_op_ecapa_tail(const float* d_pooled, int32_t nb, int32_t C2, const float* d_gamma, const float* d_beta, const void* d_w_f16, const float* d_bias,
+                     int32_t E, float* d_out);
+int32_t sc_op_prosody_last_launches(sc_prosody_encoder* p);
+
 #ifdef __cplusplus
 }
 #endif

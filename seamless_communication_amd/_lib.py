@@ -104,6 +104,13 @@ class sc_unit_extractor_config(C.Structure):
     ]
 
 
+class sc_prosody_encoder_config(C.Structure):
+    _fields_ = [
+        ("abi_version", _i), ("input_dim", _i), ("embed_dim", _i), ("res2net_scale", _i), ("se_channels", _i), ("attention_channels", _i),
+        ("global_context", _i), ("n_blocks", _i), ("channels", _i * 8), ("kernel_sizes", _i * 8), ("dilations", _i * 8),
+    ]
+
+
 class sc_aligner_config(C.Structure):
     _fields_ = [
         ("abi_version", _i), ("model_dim", _i), ("feat_dim", _i), ("text_layers", _i), ("feat_layers", _i),
@@ -174,6 +181,16 @@ SIGNATURES = {
     "sc_op_w2v2_frontend": (C.c_int, [_P, C.c_int64, _P, _i, _P, _P, _P, _P, _i, _i, _i, _P, _i, _P]),
     "sc_op_w2v2_pos_conv": (C.c_int, [_P, _P, _P, _P, _i, _i, _i, _i, _i, _P]),
     "sc_op_kmeans": (C.c_int, [_P, _P, _i, _i, _i, _P]),
+    "sc_prosody_encoder_load": (_P, [C.POINTER(sc_tensor_desc), C.c_size_t, C.POINTER(sc_prosody_encoder_config), C.c_int]),
+    "sc_prosody_encoder_free": (None, [_P]),
+    "sc_prosody_encode": (C.c_int, [_P, _P, _i, _i, _P, _P, _P, _P]),
+    "sc_op_ecapa_chain": (C.c_int, [_P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _i]),
+    "sc_op_ecapa_chain_tile": (C.c_int32, [_i, _i, _i]),
+    "sc_op_ecapa_relu_ln": (C.c_int, [_P, _P, _i, _P, _P, _P, _i, _i, _i]),
+    "sc_op_ecapa_se_gate": (C.c_int, [_P, _i, _i, _P, _i, _i, _P, _P, _P, _P, _P]),
+    "sc_op_ecapa_pool": (C.c_int, [_P, _P, _i, _i, _i, _P, _P, _P]),
+    "sc_op_ecapa_tail": (C.c_int, [_P, _i, _i, _P, _P, _P, _P, _i, _P]),
+    "sc_op_prosody_last_launches": (C.c_int32, [_P]),
     "sc_op_knob": (C.c_int, [C.c_char_p, C.c_int]),
     "sc_op_force_general_gemm": (C.c_int, [C.c_int]),
     "sc_op_voc_pack_plan": (C.c_int32, [_PI, C.c_int32, C.c_int64, _PI, C.c_int32]),

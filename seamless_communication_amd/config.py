@@ -187,6 +187,35 @@ def tiny_w2v2_config(head_dim: int = 80) -> Wav2Vec2UnitConfig:
                               feature_dim=32, layer_descs=((32, 10, 5),) + ((32, 3, 2),) * 4 + ((32, 2, 2),) * 2)
 
 
+@dataclass
+class EcapaTDNNConfig:
+    """ECAPA-TDNN prosody encoder of SeamlessExpressive (models/pretssel/ecapa_tdnn_builder.py, arch ``base``): one TDNN block,
+    ``len(channels) - 2`` SE-Res2Net blocks, multi-layer feature aggregation, attentive statistics pooling, a projection."""
+
+    name: str = "base"
+    channels: Tuple[int, ...] = (512, 512, 512, 512, 1536)
+    kernel_sizes: Tuple[int, ...] = (5, 3, 3, 3, 1)
+    dilations: Tuple[int, ...] = (1, 2, 3, 4, 1)
+    attention_channels: int = 128
+    res2net_scale: int = 8
+    se_channels: int = 128
+    global_context: bool = True
+    groups: Tuple[int, ...] = (1, 1, 1, 1, 1)
+    embed_dim: int = 512
+    input_dim: int = 80
+
+
+def ecapa_tdnn_config(arch: str = "base") -> EcapaTDNNConfig:
+    """``base``: the reference's only architecture.  ``small``: the same structure at a quarter of the width (Res2Net chunks of
+    32 channels) for parity tests."""
+    if arch == "base":
+        return EcapaTDNNConfig()
+    if arch == "small":
+        return EcapaTDNNConfig(name="small", channels=(128, 128, 128, 128, 384), attention_channels=32, res2net_scale=4, se_channels=32,
+                               embed_dim=64)
+    raise ValueError(f"unknown ECAPA-TDNN arch '{arch}' (supported: base, small)")
+
+
 def nar_t2u_aligner() -> AlignerConfig:
     return AlignerConfig()
 

@@ -750,6 +750,48 @@ void launch_w2v2_dup_split(const float* x, int64_t ldx, int rows, int C, __half*
 // bias[j] = -||c_hi + c_lo||^2 / 2 (fp32 sum in ascending channel order)
 void launch_w2v2_pack_centroids(const float* cent, int C, int K, __half* W, float* bias, hipStream_t s);
 
+// ---- ECAPA-TDNN prosody encoder (k_ecapa.hip; reference models/pretssel/ecapa_tdnn.py) ------------------------------
+// The Res2Net chain of one SE-Res2Net block in one launch: out[:, 0:CW] = x[:, 0:CW]; y_1 = B_0(x_1), y_i = B_{i-1}(x_i + y_{i-1}),
+// B = Conv1d(CW -> CW, k = 3, dilation dil, 'same') + ReLU + LayerNorm(CW, eps 1e-12); out[:, i CW : (i + 1) CW] = y_i.  x / out
+// [nb][T][ldx / ldo] fp32 (out != x), frames outside [0, T) zeros at the input of every stage.  w[i]: packed tap-major
+// [CW][ldw] fp16 (launch_pack_conv_weight), bias / gamma / beta [CW] fp32.  CW in {32, 64}, dil <= 8.
+constexpr int ECAPA_MAX_SCALE = 8;
+struct EcapaChainArgs {
+    const float* x = nullptr;
+    int64_t ldx = 0;
+    float* out = nullptr;
+    int64_t ldo = 0;
+    const __half* w[ECAPA_MAX_SCALE - 1] = {};
+    int64_t ldw = 0;
+    const float* bias[ECAPA_MAX_SCALE - 1] = {};
+    const float* gamma[ECAPA_MAX_SCALE - 1] = {};
+    const float* beta[ECAPA_MAX_SCALE - 1] = {};
+    int nb = 0, T = 0, CW = 0, scale = 0, dil = 1;
+};
+bool ecapa_chain_supported(int chunk, int scale, int k, int dil);
+int ecapa_chain_tile_rows(int scale, int dil);  // frames a workgroup stores
+void launch_ecapa_chain(const EcapaChainArgs& a, hipStream_t s);
+// y[row] = act(LayerNorm(relu(x[row] + item_bias[row / t_per_item]))) over C channels, eps 1e-12; act ACT_NONE / ACT_TANH; y may be x
+void launch_ecapa_relu_ln(const float* x, int64_t ldx, const float* item_bias, int t_per_item, const float* g, const float* b, float* y, int64_t ldy,
+                          int rows, int C, int act, hipStream_t s);
+// gate[n][C] = sigmoid(W2 relu(W1 s + b1) + b2), s = sum over t < lens[n] of x[n][t] / lens[n] (lens null: T); w1 [S][C], w2 [C][S] fp16
+void launch_ecapa_se_gate(const float* x, int64_t ldx, int nb, int T, const int* d_lens, int C, int S, const __half* w1, const float* b1,
+                          const __half* w2, const float* b2, float* gate, hipStream_t s);
+// out = y * gate[item] + res on every frame
+void launch_ecapa_se_apply(const float* y, int64_t ldy, const float* gate, const float* res, int64_t ldr, float* out, int64_t ldo, int nb, int T, int C,
+                           hipStream_t s);
+// gstats[n] = [mean | sqrt(max(variance around the mean, 1e-12))] of x [nb][T][C] over the frames t < lens[n]
+void launch_ecapa_gstats(const float* x, int nb, int T, int C, const int* d_lens, float* gstats, hipStream_t s);
+// out[n][j] = W[j][k0 .. k0 + K) . v[n] + bias[j]
+void launch_ecapa_item_bias(const __half* W, int64_t ldw, int k0, const float* bias, const float* v, int nb, int K, int N, float* out, hipStream_t s);
+// pooled[n] = [sum_t a_t x_t | sqrt(max(sum_t a_t (x_t - mean)^2, 1e-12))], a = softmax over t < lens[n] of logits [nb][T][C] per channel
+void launch_ecapa_pool(const float* x, const float* logits, int nb, int T, int C, const int* d_lens, float* pooled, hipStream_t s);
+// out[n] = normalize(W LayerNorm(pooled[n]) + bias): LayerNorm(C2, eps 1e-12), W [E][ldw] fp16, L2 norm clamped at 1e-12
+void launch_ecapa_tail(const float* pooled, int nb, int C2, const float* g, const float* b, const __half* W, int64_t ldw, const float* bias, int E,
+                       float* out, hipStream_t s);
+// y = (x - mean) / std on the frames t < lens[n] of x [nb][T][D], zeros behind
+void launch_ecapa_gcmvn(const float* x, const float* mean, const float* stdv, const int* d_lens, int nb, int T, int D, float* y, hipStream_t s);
+
 // ---- decode engine (k_engine.hip, engine.hip) ---------------------------------------------------------------------
 // One greedy step chain per GPU shared by every pass in flight.  A ROW STATE r (0 .. rows-1) owns everything that lives as
 // long as a hypothesis: K / V cache rows, encoder K / V, token history, captured decoder outputs, position, flags.  A SLOT s

@@ -646,3 +646,79 @@ class HipUnitExtractor:
         check(self.lib.sc_extract_units(self.handle, _ptr(wav), n, stride, _ptr(ns), int(out_layer_idx), _ptr(units), tf, _ptr(frames), _ptr(feats)),
               "sc_extract_units")
         return units.astype(np.int64), frames, feats
+
+
+class HipProsodyEncoder:
+    """ECAPA-TDNN prosody encoder resident in one GPU's HBM (``sc_prosody_encoder_*``): a handle of its own."""
+
+    MAX_FRAMES = 4096
+
+    def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], device: int = 0) -> None:
+        self.lib = _lib.load_library()
+        self.cfg = cfg
+        self.device_index = int(device)
+        self.device = torch.device("cuda", self.device_index)
+        if not torch.cuda.is_available():
+            raise SeamlessHipError("no HIP device is visible; the HIP path has no CPU fallback")
+        if any(int(g) != 1 for g in cfg.groups):
+            raise ValueError(f"groups={tuple(cfg.groups)}: only groups of 1 (arch base) are built")
+        if not (len(cfg.channels) == len(cfg.kernel_sizes) == len(cfg.dilations)) or not 3 <= len(cfg.channels) <= 8:
+            raise ValueError("channels, kernel_sizes and dilations must have the same 3..8 entries")
+        from .synthetic import strip_ecapa_prefix
+
+        sd = strip_ecapa_prefix(state_dict)
+        sd = {k: (v.to(torch.float16) if k.endswith(".weight") and v.dim() == 3 else v.to(torch.float32)) for k, v in sd.items()}
+        descs, keep = _tensor_descs(sd)
+        c = _lib.sc_prosody_encoder_config()
+        c.abi_version = _lib.SC_ABI_VERSION
+        c.input_dim, c.embed_dim, c.res2net_scale = int(cfg.input_dim), int(cfg.embed_dim), int(cfg.res2net_scale)
+        c.se_channels, c.attention_channels, c.global_context = int(cfg.se_channels), int(cfg.attention_channels), int(bool(cfg.global_context))
+        c.n_blocks = len(cfg.channels)
+        for i in range(c.n_blocks):
+            c.channels[i], c.kernel_sizes[i], c.dilations[i] = int(cfg.channels[i]), int(cfg.kernel_sizes[i]), int(cfg.dilations[i])
+        self._c = c
+        self.handle = self.lib.sc_prosody_encoder_load(descs, len(sd), C.byref(c), self.device_index)
+        if not self.handle:
+            msg = self.lib.sc_last_error()
+            raise SeamlessHipError(f"sc_prosody_encoder_load failed: {msg.decode() if msg else '?'}")
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self.lib.sc_prosody_encoder_free(self.handle)
+            self.handle = None
+
+    def __del__(self) -> None:  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def encode(self, fbank: torch.Tensor, lens=None, gcmvn_mean: Optional[torch.Tensor] = None, gcmvn_std: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fbank (B, T, input_dim) on the device, lens (B,) or None -> (B, embed_dim) float32 on the device, L2-normalised rows.
+        Rows behind an item's length are read as zeros; gcmvn (both or neither, (input_dim,)) is applied on the device."""
+        if fbank.dim() != 3 or fbank.shape[2] != self.cfg.input_dim:
+            raise ValueError(f"fbank must be (B, T, {self.cfg.input_dim}), got {tuple(fbank.shape)}")
+        if fbank.device != self.device:
+            raise ValueError(f"fbank lives on {fbank.device}, the encoder on {self.device}")
+        x = fbank.detach().to(torch.float32).contiguous()
+        n, t = int(x.shape[0]), int(x.shape[1])
+        hl = None
+        if lens is not None:
+            hl = _i32(lens.detach().cpu().numpy() if isinstance(lens, torch.Tensor) else lens).reshape(-1)
+            if hl.shape[0] != n:
+                raise ValueError(f"{hl.shape[0]} lengths for {n} items")
+        mean = std = None
+        if (gcmvn_mean is None) != (gcmvn_std is None):
+            raise ValueError("gcmvn_mean and gcmvn_std go together")
+        if gcmvn_mean is not None:
+            mean = torch.as_tensor(gcmvn_mean, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+            std = torch.as_tensor(gcmvn_std, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+            if mean.numel() != self.cfg.input_dim or std.numel() != self.cfg.input_dim:
+                raise ValueError(f"gcmvn statistics must hold {self.cfg.input_dim} values")
+        out = torch.empty(n, self.cfg.embed_dim, dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()  # the handle runs on a stream of its own
+        check(self.lib.sc_prosody_encode(self.handle, _ptr(x), n, t, _ptr(hl), _ptr(mean), _ptr(std), _ptr(out)), "sc_prosody_encode")
+        return out
+
+    def last_launches(self) -> int:
+        return int(self.lib.sc_op_prosody_last_launches(self.handle))

@@ -566,3 +566,63 @@ def make_w2v2_state_dict(cfg, seed: int = 0) -> Dict[str, torch.Tensor]:
         sd[p + "ffn.output_proj.weight"] = rnd(M, cfg.ffn_dim, scale=cfg.ffn_dim ** -0.5)
         sd[p + "ffn.output_proj.bias"] = rnd(M, scale=0.1)
     return sd
+
+
+ECAPA_PREFIXES = ("prosody_encoder_model.", "prosody_encoder.")
+
+
+def make_ecapa_state_dict(cfg, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """State dict of the ECAPA-TDNN prosody encoder under the module's own names (models/pretssel/ecapa_tdnn.py; ``cfg``: a
+    :class:`~seamless_communication_amd.config.EcapaTDNNConfig`).  Every value is fp16-representable; Conv1d weights are
+    N(0, 2 / fan_in) (activations stay alive through the ReLUs), LayerNorm gains lie near 1."""
+    g = torch.Generator().manual_seed(seed)
+
+    def rnd(*shape, scale=1.0):
+        return (torch.randn(*shape, generator=g) * scale).to(torch.float16).to(torch.float32)
+
+    sd: Dict[str, torch.Tensor] = {}
+
+    def conv(p, co, ci, k, gain=2.0):
+        sd[p + ".weight"] = rnd(co, ci, k, scale=(gain / (ci * k)) ** 0.5)
+        sd[p + ".bias"] = rnd(co, scale=0.1)
+
+    def tdnn(p, co, ci, k):
+        conv(p + ".conv", co, ci, k)
+        sd[p + ".norm.weight"] = (1 + rnd(co, scale=0.1)).to(torch.float16).to(torch.float32)
+        sd[p + ".norm.bias"] = rnd(co, scale=0.1)
+
+    ch = cfg.channels
+    tdnn("blocks.0", ch[0], cfg.input_dim, cfg.kernel_sizes[0])
+    for i in range(1, len(ch) - 1):
+        p = f"blocks.{i}"
+        w = ch[i] // cfg.res2net_scale
+        tdnn(p + ".tdnn1", ch[i], ch[i - 1], 1)
+        for j in range(cfg.res2net_scale - 1):
+            tdnn(p + f".res2net_block.blocks.{j}", w, w, cfg.kernel_sizes[i])
+        tdnn(p + ".tdnn2", ch[i], ch[i], 1)
+        conv(p + ".se_block.conv1", cfg.se_channels, ch[i], 1)
+        conv(p + ".se_block.conv2", ch[i], cfg.se_channels, 1)
+        if ch[i - 1] != ch[i]:
+            conv(p + ".shortcut", ch[i], ch[i - 1], 1, gain=1.0)
+    tdnn("mfa", ch[-1], ch[-1], cfg.kernel_sizes[-1])
+    tdnn("asp.tdnn", cfg.attention_channels, ch[-1] * (3 if cfg.global_context else 1), 1)
+    conv("asp.conv", ch[-1], cfg.attention_channels, 1)
+    sd["asp_norm.weight"] = (1 + rnd(2 * ch[-1], scale=0.1)).to(torch.float16).to(torch.float32)
+    sd["asp_norm.bias"] = rnd(2 * ch[-1], scale=0.1)
+    conv("fc", cfg.embed_dim, 2 * ch[-1], 1, gain=1.0)
+    return sd
+
+
+def strip_ecapa_prefix(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The prosody encoder's tensors under the module's own names, from a state dict that holds them bare, under
+    ``prosody_encoder_model.`` (an expressive UnitY checkpoint, unity/loader.py:341) or under ``prosody_encoder.`` (the PRETSSEL
+    vocoder's attribute).  Other tensors of the checkpoint are dropped."""
+    for pre in ECAPA_PREFIXES:
+        sub = {k[len(pre):]: v for k, v in state_dict.items() if k.startswith(pre)}
+        if sub:
+            return sub
+    roots = ("blocks.", "mfa.", "asp.", "asp_norm.", "fc.")
+    sub = {k: v for k, v in state_dict.items() if k.startswith(roots)}
+    if not sub:
+        raise ValueError("the state dict holds no ECAPA-TDNN tensors (bare, under prosody_encoder_model. or under prosody_encoder.)")
+    return sub
