@@ -470,6 +470,41 @@ void sc_prosody_encoder_free(sc_prosody_encoder* p);
 int sc_prosody_encode(sc_prosody_encoder* p, const float* d_fbank, int32_t n, int32_t t_rows, const int32_t* h_lens_or_null,
                       const float* d_gcmvn_mean_or_null, const float* d_gcmvn_std_or_null, float* d_out);
 
+/* ---- PRETSSEL acoustic model: units + prosody vector -> mel spectrogram (reference models/generator/vocoder.py:488-513, the first
+ * half of PretsselVocoder.forward; the waveform generator behind it is not built) -------------------------------------------
+ * A handle of its own.  sc_pretssel_load takes the module's own state-dict names (the reference loader converts nothing):
+ *   encoder_frontend.{embed_tokens.weight, pos_emb_alpha, embed_lang.weight}, {encoder,decoder}.layers.N.{self_attn.{q,k,v,output}_proj,
+ *   self_attn_layer_norm, conv1d.conv{1,2}, conv1d_layer_norm, film.proj}.*, .film.{s_gamma,s_beta},
+ *   decoder_frontend.variance_adaptor.{pitch,vuv,energy}_predictor.{conv{1,2}.0, ln{1,2}, proj, film.proj}.*, .film.{s_gamma,s_beta},
+ *   decoder_frontend.variance_adaptor.embed_{pitch,energy}.*, decoder_frontend.pos_emb_alpha, final_proj.*,
+ *   layers.{i}.0.{weight,bias}, layers.{i}.1.{weight,bias,running_mean,running_var} for the post_layers post-net blocks, and three
+ *   tables the caller builds: pos_encoder.freqs [max_seq_len][model_dim] (sinusoidal, fairseq layout, first row = position
+ *   pad_idx + 1), gcmvn_mean / gcmvn_std [mel_dim].  Other tensors (the prosody encoder, the waveform half) are ignored.
+ * Limits (SC_ERR_INVALID from sc_pretssel_load): model_dim = heads * 128, at most 512; pred_hidden_dim a multiple of 64 up to 1024;
+ * conv_inner_dim a multiple of 32 up to 8192; post_dim a multiple of 32 up to 4096; odd kernel sizes up to 31; 1..32 layers per
+ * stack; post_layers 2..8; mel_dim a multiple of 4 up to 96. */
+typedef struct sc_pretssel_config {
+    int32_t abi_version; /* must be SC_ABI_VERSION */
+    int32_t model_dim, num_heads, enc_layers, dec_layers, conv_inner_dim, conv_kernel;
+    int32_t film_cond_dim, lang_embed_dim, num_langs; /* film_cond_dim = prosody vector + lang_embed_dim */
+    int32_t pred_hidden_dim, pred_kernel;
+    int32_t vocab_size, pad_idx, max_seq_len, mel_dim;
+    int32_t post_layers, post_dim, post_kernel;
+    float upsample_delta;
+} sc_pretssel_config;
+typedef struct sc_pretssel sc_pretssel;
+sc_pretssel* sc_pretssel_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_pretssel_config* cfg, int device);
+void sc_pretssel_free(sc_pretssel* p);
+/* One packed pass over all items.  h_tokens / h_durations [n][s_tok] (host; tokens already offset and EOS-terminated, rows
+ * padded behind h_tok_lens[i]), lang_index the row of embed_lang, d_prosody [n][film_cond_dim - lang_embed_dim] fp32 on the
+ * device, d_mel [n][t_cap][mel_dim] fp32 on the device, h_frame_lens [n] (nullable) receives the frames of every item (the sum of
+ * its durations).  Item i's frames are the reference's PADDED-BATCH result (the post-net sees final_proj's bias on the rows
+ * between an item's end and the batch maximum); rows of d_mel behind an item's frames are zeros.
+ * SC_ERR_INVALID, with nothing launched: an item without tokens or without frames, a negative duration, a token outside the
+ * vocabulary, a token count or frame count + pad_idx + 1 above max_seq_len, frames above t_cap, lang_index outside the table. */
+int sc_pretssel_mel(sc_pretssel* p, const int32_t* h_tokens, int32_t n, int32_t s_tok, const int32_t* h_tok_lens, const int32_t* h_durations,
+                    int32_t lang_index, const float* d_prosody, float* d_mel, int32_t t_cap, int32_t* h_frame_lens_or_null);
+
 /* The kernel-level test hooks (sc_op_*) and the dispatch introspection the parity tests drive are exported too but are NOT part
  * of the drop-in boundary: include/seamless_hip_internal.h. */
 

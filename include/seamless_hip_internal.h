@@ -294,6 +294,34 @@ int sc_op_ecapa_tail(const float* d_pooled, int32_t nb, int32_t C2, const float*
                      int32_t E, float* d_out);
 int32_t sc_op_prosody_last_launches(sc_prosody_encoder* p);
 
+/* PRETSSEL kernels by themselves (k_attn128.hip, k_pretssel.hip; tests/test_pretssel_gpu.py).  Device pointers unless named h_.
+ * sc_op_attention128: launch_attention at head_dim 128: q / k / v rows with strides ld*, d_kv_lens (nullable), d_row_off (nullable:
+ *   packed rows, needs d_kv_lens and sq == skv), fp32 rows d_out (ldo) or the planes d_out_hi / d_out_lo (ldoh) when those are given.
+ * sc_op_pretssel_film: d_out [n][N] = mul * (W [N][P + Lg] fp16 . [pros_i | lang] + bias) + add.
+ * sc_op_pretssel_film_ln: LayerNorm -> FiLM -> mask (kernels.h: PretsselLnArgs); d_film / d_row_item / d_y / the planes nullable.
+ * sc_op_pretssel_var_tail: kernels.h: PretsselTailArgs; d_x [rows][C] is updated in place, d_vals [rows][3] nullable.
+ * sc_op_pretssel_upsample: h_tok_lens [n], h_dur: the items' durations back to back; d_x the tokens back to back [sum lens][C];
+ *   d_y [sum frames][C]; d_pos_table nullable; d_wsum [sum frames] nullable.  sc_op_pretssel_ups_cutoff: the energy cut-off.
+ * sc_op_pretssel_postnet: the post-net of a loaded handle on d_proj (packed frames [sum lens][mel], h_frame_lens [n]) -> d_mel
+ *   [n][t_cap][mel] (de-normalised, zeros behind the frames).  sc_op_pretssel_postnet_tile(rows, dim): rows of the product tile.
+ * sc_op_pretssel_last_launches: kernel launches of the handle's last sc_pretssel_mel call (the memset of the output and the
+ *   uploads of the row tables are copies, not kernels, and are not counted). */
+int sc_op_attention128(const float* d_q, const float* d_k, const float* d_v, float* d_out, int32_t nb, int32_t heads, int32_t sq, int32_t skv,
+                       int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, const int32_t* d_kv_lens, const int32_t* d_row_off, void* d_out_hi,
+                       void* d_out_lo, int64_t ldoh);
+int sc_op_pretssel_film(const float* d_pros, int32_t P, const float* d_lang, int32_t Lg, const void* d_w_f16, const float* d_bias, const float* d_mul,
+                        const float* d_add, int32_t n, int32_t N, float* d_out);
+int sc_op_pretssel_film_ln(const float* d_x, const float* d_gamma, const float* d_beta, const float* d_film, int32_t film_ld, int32_t film_off,
+                           const int32_t* d_row_item, float* d_y, void* d_yh_f16, void* d_yl_f16, int32_t rows, int32_t C, int32_t groups);
+int sc_op_pretssel_var_tail(const float* d_f, const float* d_pw, const float* d_pb, const float* d_wp, const float* d_bp, const float* d_we,
+                            const float* d_be, float* d_x, float* d_vals, int32_t rows, int32_t H, int32_t C);
+int sc_op_pretssel_upsample(const float* d_x, const int32_t* h_tok_lens, const int32_t* h_dur, int32_t n, int32_t C, float delta,
+                            const float* d_pos_table, float pos_alpha, float* d_y, void* d_yh_f16, void* d_yl_f16, float* d_wsum);
+float sc_op_pretssel_ups_cutoff(void);
+int sc_op_pretssel_postnet(sc_pretssel* p, const float* d_proj, int32_t n, const int32_t* h_frame_lens, float* d_mel, int32_t t_cap);
+int32_t sc_op_pretssel_postnet_tile(int32_t rows, int32_t dim);
+int32_t sc_op_pretssel_last_launches(sc_pretssel* p);
+
 #ifdef __cplusplus
 }
 #endif

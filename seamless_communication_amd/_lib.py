@@ -104,6 +104,14 @@ class sc_unit_extractor_config(C.Structure):
     ]
 
 
+class sc_pretssel_config(C.Structure):
+    _fields_ = [
+        ("abi_version", _i), ("model_dim", _i), ("num_heads", _i), ("enc_layers", _i), ("dec_layers", _i), ("conv_inner_dim", _i), ("conv_kernel", _i),
+        ("film_cond_dim", _i), ("lang_embed_dim", _i), ("num_langs", _i), ("pred_hidden_dim", _i), ("pred_kernel", _i), ("vocab_size", _i),
+        ("pad_idx", _i), ("max_seq_len", _i), ("mel_dim", _i), ("post_layers", _i), ("post_dim", _i), ("post_kernel", _i), ("upsample_delta", C.c_float),
+    ]
+
+
 class sc_prosody_encoder_config(C.Structure):
     _fields_ = [
         ("abi_version", _i), ("input_dim", _i), ("embed_dim", _i), ("res2net_scale", _i), ("se_channels", _i), ("attention_channels", _i),
@@ -191,6 +199,18 @@ SIGNATURES = {
     "sc_op_ecapa_pool": (C.c_int, [_P, _P, _i, _i, _i, _P, _P, _P]),
     "sc_op_ecapa_tail": (C.c_int, [_P, _i, _i, _P, _P, _P, _P, _i, _P]),
     "sc_op_prosody_last_launches": (C.c_int32, [_P]),
+    "sc_pretssel_load": (_P, [C.POINTER(sc_tensor_desc), C.c_size_t, C.POINTER(sc_pretssel_config), C.c_int]),
+    "sc_pretssel_free": (None, [_P]),
+    "sc_pretssel_mel": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P, _P, _i, _P]),
+    "sc_op_attention128": (C.c_int, [_P, _P, _P, _P, _i, _i, _i, _i, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_int64]),
+    "sc_op_pretssel_film": (C.c_int, [_P, _i, _P, _i, _P, _P, _P, _P, _i, _i, _P]),
+    "sc_op_pretssel_film_ln": (C.c_int, [_P, _P, _P, _P, _i, _i, _P, _P, _P, _P, _i, _i, _i]),
+    "sc_op_pretssel_var_tail": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i]),
+    "sc_op_pretssel_upsample": (C.c_int, [_P, _P, _P, _i, _i, C.c_float, _P, C.c_float, _P, _P, _P, _P]),
+    "sc_op_pretssel_ups_cutoff": (C.c_float, []),
+    "sc_op_pretssel_postnet": (C.c_int, [_P, _P, _i, _P, _P, _i]),
+    "sc_op_pretssel_postnet_tile": (C.c_int32, [_i, _i]),
+    "sc_op_pretssel_last_launches": (C.c_int32, [_P]),
     "sc_op_knob": (C.c_int, [C.c_char_p, C.c_int]),
     "sc_op_force_general_gemm": (C.c_int, [C.c_int]),
     "sc_op_voc_pack_plan": (C.c_int32, [_PI, C.c_int32, C.c_int64, _PI, C.c_int32]),

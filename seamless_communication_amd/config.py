@@ -216,6 +216,47 @@ def ecapa_tdnn_config(arch: str = "base") -> EcapaTDNNConfig:
     raise ValueError(f"unknown ECAPA-TDNN arch '{arch}' (supported: base, small)")
 
 
+@dataclass
+class PretsselConfig:
+    """Acoustic model of the PRETSSEL vocoder (models/generator/builder.py, archs ``16khz`` / ``24khz``: identical up to the mel
+    spectrogram): unit embedding, FiLM-conditioned FFT encoder, variance adaptor with Gaussian upsampling, FFT decoder,
+    projection to the mel bins and the Conv-BatchNorm-Tanh post-net."""
+
+    name: str = "24khz"
+    model_dim: int = 256
+    num_heads: int = 2
+    encoder_layers: int = 4
+    decoder_layers: int = 4
+    conv_inner_dim: int = 1024
+    conv_kernel: int = 9
+    film_cond_dim: int = 576
+    lang_embed_dim: int = 64
+    num_langs: int = 6
+    pred_hidden_dim: int = 512
+    pred_kernel: int = 5
+    vocab_size: int = 10004
+    pad_idx: int = 1
+    eos_idx: int = 2
+    max_seq_len: int = 10000
+    mel_dim: int = 80
+    post_layers: int = 5
+    post_dim: int = 512
+    post_kernel: int = 5
+    upsample_delta: float = 0.1
+    prosody_encoder: EcapaTDNNConfig = field(default_factory=EcapaTDNNConfig)
+
+
+def pretssel_config(arch: str = "24khz") -> PretsselConfig:
+    """``16khz`` / ``24khz``: the reference's architectures (they differ in the waveform generator only; ``16khz`` ships without
+    languages in its builder, the card supplies them).  ``small``: 1 + 1 layers at the same width and head size for parity tests."""
+    if arch in ("16khz", "24khz"):
+        return PretsselConfig(name=arch)
+    if arch == "small":
+        return PretsselConfig(name="small", encoder_layers=1, decoder_layers=1, conv_inner_dim=256, pred_hidden_dim=128, post_dim=128, num_langs=2,
+                              film_cond_dim=64 + 64, prosody_encoder=ecapa_tdnn_config("small"))
+    raise ValueError(f"unknown PRETSSEL arch '{arch}' (supported: 16khz, 24khz, small)")
+
+
 def nar_t2u_aligner() -> AlignerConfig:
     return AlignerConfig()
 

@@ -404,7 +404,11 @@ void launch_attention(const AttnArgs& a, hipStream_t s) {
         launch_attention80(a, s);
         return;
     }
-    SC_CHECK(a.head_dim == HD, "attention: head_dim=%d (64 and 80 exist)", a.head_dim);
+    if (a.head_dim == 128) {
+        launch_attention128(a, s);
+        return;
+    }
+    SC_CHECK(a.head_dim == HD, "attention: head_dim=%d (64, 80 and 128 exist)", a.head_dim);
     SC_CHECK(a.nb > 0 && a.heads > 0 && a.Sq > 0 && a.Skv > 0, "attention: empty problem");
     SC_CHECK(a.out || (a.out_hi && a.out_lo && a.ldoh % 4 == 0), "attention: no output");
     SC_CHECK(a.ldq % 4 == 0 && a.ldk % 4 == 0 && a.ldv % 4 == 0 && a.ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(a.out) & 15) == 0,

@@ -668,6 +668,8 @@ void launch_gemm_presplit(const GemmPsArgs& a, hipStream_t s) {
     SC_LAUNCH_CHECK();
 }
 
+int gemm_presplit_tile(int M, int N) { return ps_tile(M, N); }
+
 // every tile shape has two waves side by side (WGN = 2): two partial results per tile column
 int gemm_presplit_amax_chunks(int M, int N) { return 2 * cdiv(N, ps_tile(M, N)); }
 

@@ -147,6 +147,7 @@ struct GemmPsArgs {
     int amax_ld = 0;
 };
 void launch_gemm_presplit(const GemmPsArgs& a, hipStream_t s);
+int gemm_presplit_tile(int M, int N);         // rows (= columns) of the tile launch_gemm_presplit chooses for this shape
 int gemm_presplit_amax_chunks(int M, int N);  // partial results per row the tile choice for this shape produces
 void launch_amax_finish(const float2* part, int ld, int rows, int* out_idx, hipStream_t s);
 
@@ -512,11 +513,13 @@ struct AttnArgs {
     __half* out_lo = nullptr;
     int64_t ldoh = 0;
     // 64: the kernel of k_attn.hip (every mode above).  80: k_attn80.hip (wav2vec 2.0 / XLS-R), plain mode with kv_lens only,
-    // head h at column h*80, logits scaled by 80^-0.5
+    // head h at column h*80, logits scaled by 80^-0.5.  128: k_attn128.hip (PRETSSEL), kv_lens, packed rows and plane output,
+    // head h at column h*128, logits scaled by 128^-0.5
     int head_dim = 64;
 };
 void launch_attention(const AttnArgs& a, hipStream_t s);
 void launch_attention80(const AttnArgs& a, hipStream_t s);  // k_attn80.hip; reached through launch_attention
+void launch_attention128(const AttnArgs& a, hipStream_t s);  // k_attn128.hip; reached through launch_attention
 
 // Single-query attention over a KV cache (decoder step).  q: [nb][heads*64];
 // key/value row j of (b, h) lives at base + b*cache_bs + j*cache_ld + h*64.  If k_new != null the
@@ -791,6 +794,83 @@ void launch_ecapa_tail(const float* pooled, int nb, int C2, const float* g, cons
                        float* out, hipStream_t s);
 // y = (x - mean) / std on the frames t < lens[n] of x [nb][T][D], zeros behind
 void launch_ecapa_gcmvn(const float* x, const float* mean, const float* stdv, const int* d_lens, int nb, int T, int D, float* y, hipStream_t s);
+
+// ---- PRETSSEL acoustic model (k_pretssel.hip; reference models/generator/vocoder.py:488-513) --------------------------
+// Every FiLM projection of a call: out[i][j] = mul[j] * (W[j] . [pros_i | lang] + bias[j]) + add[j] for the N stacked output rows
+// of all FiLM layers (W [N][P + Lg] fp16; mul = s_gamma / s_beta, add = 1 / 0 of the gamma / beta halves), fp32 FMA
+void launch_pretssel_film(const float* pros, int P, const float* lang, int Lg, const __half* W, const float* bias, const float* mul, const float* add,
+                          int n, int N, float* out, hipStream_t s);
+// y = mask(FiLM(LayerNorm(x))) per row and group: x [rows][ldx] holds `groups` slices of C channels, g / b [groups][C] (eps 1e-5);
+// film (nullable) [items][film_ld]: group grp of item i reads gamma' at film_off + grp * 2C, beta' behind it, y = gamma' * ln + beta';
+// row_item[row] (nullable: item 0) names the row's item, < 0 marks a row behind its item's length: exact zeros.
+// y (fp32) and / or the planes yh / yl.  C a multiple of 64 up to 1024.
+struct PretsselLnArgs {
+    const float* x = nullptr;
+    int64_t ldx = 0;
+    const float* g = nullptr;
+    const float* b = nullptr;
+    const float* film = nullptr;
+    int64_t film_ld = 0;
+    int film_off = 0;
+    const int* row_item = nullptr;
+    float* y = nullptr;
+    int64_t ldy = 0;
+    __half* yh = nullptr;
+    __half* yl = nullptr;
+    int64_t ldh = 0;
+    int rows = 0, C = 0, groups = 1;
+};
+bool pretssel_ln_supported(int C);
+void launch_pretssel_film_ln(const PretsselLnArgs& a, hipStream_t s);
+// variance adaptor tail (length_regulator.py:295-312): f [rows][3][H] = the pitch / voiced / energy predictors' rows behind their
+// FiLM, pw [3][H] / pb [3] their projections; pitch = vuv >= 0 ? pitch : 0; x [rows][C] += (pitch wp + bp) + (energy we + be).
+// vals (nullable) [rows][3]: the three projections.
+struct PretsselTailArgs {
+    const float* f = nullptr;
+    const float* pw = nullptr;
+    const float* pb = nullptr;
+    const float* wp = nullptr;
+    const float* bp = nullptr;
+    const float* we = nullptr;
+    const float* be = nullptr;
+    float* x = nullptr;
+    float* vals = nullptr;
+    int rows = 0, H = 0, C = 0;
+};
+void launch_pretssel_var_tail(const PretsselTailArgs& a, hipStream_t s);
+// Gaussian upsampling (length_regulator.py:42-96) of packed items: tokens [tok_off[i], tok_off[i + 1]) of x [tokens][C] with
+// durations dur become the frames [frame_off[i], frame_off[i + 1]); y[m] = softmax_k(-delta (t - c_k)^2) . x + pos_alpha *
+// pos_table[t] (pos_table nullable).  centre: scratch [tokens].  wsum (nullable) [frames]: the kept soft-max mass relative to the
+// row maximum.  Tokens whose energy lies more than pretssel_ups_cutoff() under the row maximum are dropped (k_pretssel.hip).
+constexpr int PRETSSEL_UPS_VPL = 8;  // C <= 512
+struct PretsselUpsArgs {
+    const float* x = nullptr;
+    const int* dur = nullptr;
+    const int* tok_off = nullptr;
+    const int* frame_off = nullptr;
+    float* centre = nullptr;
+    const float* pos_table = nullptr;
+    float pos_alpha = 0.f, delta = 0.1f;
+    float* y = nullptr;
+    __half* yh = nullptr;
+    __half* yl = nullptr;
+    float* wsum = nullptr;
+    int n = 0, frames = 0, C = 0;
+};
+float pretssel_ups_cutoff();
+void launch_pretssel_upsample(const PretsselUpsArgs& a, hipStream_t s);
+// y[m] = embed[tok[m]] + alpha * pos_table[row_t[m]] as fp32 rows and planes
+void launch_pretssel_embed_pos(const int* tok, const int* row_t, const __half* embed, const float* pos_table, float alpha, int rows, int C, float* y,
+                               __half* yh, __half* yl, hipStream_t s);
+// post-net over the EXTENDED rows: item i's frames followed by its halo rows (ext_item[m], ext_pos[m] = {position, frames + halo})
+//   _in:      planes [ext_rows][CP] of the projection rows (halo rows: the projection's bias; columns C .. CP-1 zeros)
+//   _bn_tanh: planes of tanh(x * scale + shift)
+//   _out:     mel[i][t][C] (row stride t_cap) = (proj + x * scale + shift) * gstd + gmean on the frame rows
+void launch_pretssel_postnet_in(const float* proj, const float* bias, const int* ext_item, const int2* ext_pos, const int* frame_off, int ext_rows, int C,
+                                int CP, __half* yh, __half* yl, hipStream_t s);
+void launch_pretssel_postnet_bn_tanh(const float* x, const float* scale, const float* shift, int rows, int C, __half* yh, __half* yl, hipStream_t s);
+void launch_pretssel_postnet_out(const float* x, const float* scale, const float* shift, const float* proj, const float* gstd, const float* gmean,
+                                 const int* ext_item, const int2* ext_pos, const int* frame_off, int ext_rows, int C, int t_cap, float* mel, hipStream_t s);
 
 // ---- decode engine (k_engine.hip, engine.hip) ---------------------------------------------------------------------
 // One greedy step chain per GPU shared by every pass in flight.  A ROW STATE r (0 .. rows-1) owns everything that lives as

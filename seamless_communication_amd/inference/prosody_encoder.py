@@ -1,9 +1,9 @@
 """``ProsodyEncoder``: the ECAPA-TDNN of SeamlessExpressive (models/pretssel/ecapa_tdnn.py, arch ``base``) on one MI355X.
 
 An 80-bin fbank of the source utterance, normalised with global mean and variance (gcmvn), becomes one L2-normalised vector per
-utterance; the whole call runs inside libseamless_hip (``sc_prosody_encode``).  Its two consumers in the reference - the
-FiLM-conditioned UnitY2 T2U and the PRETSSEL vocoder - are not part of this project yet, and ``Translator`` still refuses
-``prosody_encoder_input``; this class is the handle they will take their conditioning vector from.
+utterance; the whole call runs inside libseamless_hip (``sc_prosody_encode``).  Its first consumer is the mel stage of
+:class:`PretsselGenerator`; T2U FiLM and the waveform half are not built yet, and ``Translator`` still refuses
+``prosody_encoder_input``.
 
 A ragged batch reproduces the reference on the zero-padded batch: its TDNN blocks ignore the padding mask, so the frames behind
 a shorter item's length are computed like real ones and reach the item's last valid frames through the k = 3 / k = 5

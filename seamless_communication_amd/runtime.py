@@ -722,3 +722,101 @@ class HipProsodyEncoder:
 
     def last_launches(self) -> int:
         return int(self.lib.sc_op_prosody_last_launches(self.handle))
+
+
+class HipPretssel:
+    """Acoustic model of the PRETSSEL vocoder resident in one GPU's HBM (``sc_pretssel_*``): a handle of its own.  The prosody
+    encoder is a separate handle (:class:`HipProsodyEncoder`); this one takes its vector."""
+
+    _FP32_2D = ("embed_lang.weight", "_predictor.proj.weight", "embed_pitch.weight", "embed_energy.weight")
+
+    @classmethod
+    def select_tensors(cls, cfg, state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """The acoustic model's tensors of a checkpoint in the precision the library holds them in (matrices and convolutions
+        fp16, the rest fp32).  The prosody encoder, the waveform half (``layers.<post_layers>...``, ``mean``, ``scale``) and the
+        BatchNorm counters are not this handle's and are left out, not refused."""
+        roots = ("encoder_frontend.embed_tokens.", "encoder_frontend.pos_emb_alpha", "encoder_frontend.embed_lang.", "encoder.layers.", "decoder_frontend.",
+                 "decoder.layers.", "final_proj.")
+        post = tuple(f"layers.{i}." for i in range(cfg.post_layers))
+        sd = {}
+        for k, v in state_dict.items():
+            if not (k.startswith(roots) or k.startswith(post)) or k.endswith("num_batches_tracked"):
+                continue
+            matrix = k.endswith(".weight") and v.dim() >= 2 and not k.endswith(cls._FP32_2D)
+            sd[k] = v.to(torch.float16) if matrix else v.to(torch.float32).reshape(-1) if v.dim() == 0 else v.to(torch.float32)
+        return sd
+
+    def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], gcmvn_mean, gcmvn_std, device: int = 0) -> None:
+        self.lib = _lib.load_library()
+        self.cfg = cfg
+        self.device_index = int(device)
+        self.device = torch.device("cuda", self.device_index)
+        if not torch.cuda.is_available():
+            raise SeamlessHipError("no HIP device is visible; the HIP path has no CPU fallback")
+        sd = self.select_tensors(cfg, state_dict)
+        sd["pos_encoder.freqs"] = sinusoidal_freqs(cfg.max_seq_len, cfg.model_dim, cfg.pad_idx)
+        mean = torch.as_tensor(gcmvn_mean, dtype=torch.float64).reshape(-1).to(torch.float32)
+        std = torch.as_tensor(gcmvn_std, dtype=torch.float64).reshape(-1).to(torch.float32)
+        if mean.numel() != cfg.mel_dim or std.numel() != cfg.mel_dim:
+            raise ValueError(f"gcmvn statistics must hold {cfg.mel_dim} values")
+        sd["gcmvn_mean"], sd["gcmvn_std"] = mean, std
+        descs, keep = _tensor_descs(sd)
+        c = _lib.sc_pretssel_config()
+        c.abi_version = _lib.SC_ABI_VERSION
+        c.model_dim, c.num_heads, c.enc_layers, c.dec_layers = int(cfg.model_dim), int(cfg.num_heads), int(cfg.encoder_layers), int(cfg.decoder_layers)
+        c.conv_inner_dim, c.conv_kernel = int(cfg.conv_inner_dim), int(cfg.conv_kernel)
+        c.film_cond_dim, c.lang_embed_dim, c.num_langs = int(cfg.film_cond_dim), int(cfg.lang_embed_dim), int(cfg.num_langs)
+        c.pred_hidden_dim, c.pred_kernel = int(cfg.pred_hidden_dim), int(cfg.pred_kernel)
+        c.vocab_size, c.pad_idx, c.max_seq_len, c.mel_dim = int(cfg.vocab_size), int(cfg.pad_idx), int(cfg.max_seq_len), int(cfg.mel_dim)
+        c.post_layers, c.post_dim, c.post_kernel = int(cfg.post_layers), int(cfg.post_dim), int(cfg.post_kernel)
+        c.upsample_delta = float(cfg.upsample_delta)
+        self._c = c
+        self.handle = self.lib.sc_pretssel_load(descs, len(sd), C.byref(c), self.device_index)
+        if not self.handle:
+            msg = self.lib.sc_last_error()
+            raise SeamlessHipError(f"sc_pretssel_load failed: {msg.decode() if msg else '?'}")
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self.lib.sc_pretssel_free(self.handle)
+            self.handle = None
+
+    def __del__(self) -> None:  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def mel(self, tokens, tok_lens, durations, lang_index: int, prosody: torch.Tensor) -> Tuple[torch.Tensor, np.ndarray]:
+        """tokens / durations (B, S) host integers (rows padded behind tok_lens), prosody (B, film_cond_dim - lang_embed_dim) on the
+        device -> (mel (B, T_max, mel_dim) float32 on the device with zeros behind each item's frames, frames per item)."""
+        tk, du, tl = _i32(tokens), _i32(durations), _i32(tok_lens).reshape(-1)
+        if tk.ndim != 2 or tk.shape != du.shape or tl.shape[0] != tk.shape[0]:
+            raise ValueError("tokens and durations must be (B, S) with B lengths")
+        n, s = int(tk.shape[0]), int(tk.shape[1])
+        if prosody.device != self.device:
+            raise ValueError(f"the prosody vectors live on {prosody.device}, the model on {self.device}")
+        pv = prosody.detach().to(torch.float32).contiguous()
+        if tuple(pv.shape) != (n, self.cfg.film_cond_dim - self.cfg.lang_embed_dim):
+            raise ValueError(f"prosody must be ({n}, {self.cfg.film_cond_dim - self.cfg.lang_embed_dim}), got {tuple(pv.shape)}")
+        frames = np.array([int(du[i, :max(int(tl[i]), 0)].sum()) for i in range(n)], dtype=np.int64)
+        t_cap = int(max(1, min(int(frames.max(initial=1)), self.cfg.max_seq_len)))
+        out = torch.empty(n, t_cap, self.cfg.mel_dim, dtype=torch.float32, device=self.device)
+        flens = np.zeros(n, dtype=np.int32)
+        torch.cuda.current_stream(self.device).synchronize()  # the handle runs on a stream of its own
+        check(self.lib.sc_pretssel_mel(self.handle, _ptr(tk), n, s, _ptr(tl), _ptr(du), int(lang_index), _ptr(pv), _ptr(out), t_cap, _ptr(flens)),
+              "sc_pretssel_mel")
+        return out, flens
+
+    def postnet(self, proj: torch.Tensor, frame_lens) -> torch.Tensor:
+        """Kernel-level hook: packed projection rows (sum lens, mel_dim) on the device -> de-normalised mel (B, T_max, mel_dim)."""
+        fl = _i32(frame_lens).reshape(-1)
+        x = proj.detach().to(torch.float32).contiguous()
+        t_cap = int(fl.max())
+        out = torch.empty(fl.shape[0], t_cap, self.cfg.mel_dim, dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        check(self.lib.sc_op_pretssel_postnet(self.handle, _ptr(x), int(fl.shape[0]), _ptr(fl), _ptr(out), t_cap), "sc_op_pretssel_postnet")
+        return out
+
+    def last_launches(self) -> int:
+        return int(self.lib.sc_op_pretssel_last_launches(self.handle))

@@ -626,3 +626,80 @@ def strip_ecapa_prefix(state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.T
     if not sub:
         raise ValueError("the state dict holds no ECAPA-TDNN tensors (bare, under prosody_encoder_model. or under prosody_encoder.)")
     return sub
+
+
+def make_pretssel_state_dict(cfg, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """State dict of the PRETSSEL acoustic model under the module's own names (models/generator/vocoder.py; ``cfg``: a
+    :class:`~seamless_communication_amd.config.PretsselConfig`), the prosody encoder under ``encoder_frontend.prosody_encoder.``.
+    Every value is fp16-representable; ``pos_emb_alpha``, ``s_gamma`` and ``s_beta`` are not 1, the BatchNorm variances lie in
+    0.5 .. 1.5.  The waveform half of a full checkpoint is not generated."""
+    g = torch.Generator().manual_seed(seed)
+
+    def q(t):
+        return t.to(torch.float16).to(torch.float32)
+
+    def rnd(*shape, scale=1.0):
+        return q(torch.randn(*shape, generator=g) * scale)
+
+    def uni(*shape, lo=0.0, hi=1.0):
+        return q(torch.rand(*shape, generator=g) * (hi - lo) + lo)
+
+    sd: Dict[str, torch.Tensor] = {}
+    for k, v in make_ecapa_state_dict(cfg.prosody_encoder, seed + 1).items():
+        sd["encoder_frontend.prosody_encoder." + k] = v
+    M, Ci, H, D = cfg.model_dim, cfg.conv_inner_dim, cfg.pred_hidden_dim, cfg.film_cond_dim
+
+    def lin(p, o, i, gain=1.0):
+        sd[p + ".weight"] = rnd(o, i, scale=(gain / i) ** 0.5)
+        sd[p + ".bias"] = rnd(o, scale=0.1)
+
+    def conv(p, co, ci, k, gain=2.0):
+        sd[p + ".weight"] = rnd(co, ci, k, scale=(gain / (ci * k)) ** 0.5)
+        sd[p + ".bias"] = rnd(co, scale=0.1)
+
+    def ln(p, d):
+        sd[p + ".weight"] = q(1 + rnd(d, scale=0.1))
+        sd[p + ".bias"] = rnd(d, scale=0.1)
+
+    def film(p, d):
+        lin(p + ".proj", 2 * d, D, gain=0.25)
+        sd[p + ".s_gamma"] = uni(1, lo=0.5, hi=0.9)
+        sd[p + ".s_beta"] = uni(1, lo=1.1, hi=1.5)
+
+    sd["encoder_frontend.embed_tokens.weight"] = rnd(cfg.vocab_size, M)
+    sd["encoder_frontend.embed_tokens.weight"][cfg.pad_idx] = 0
+    sd["encoder_frontend.pos_emb_alpha"] = uni(1, lo=0.6, hi=0.9)
+    sd["encoder_frontend.embed_lang.weight"] = rnd(cfg.num_langs, cfg.lang_embed_dim)
+    for stack, n in (("encoder", cfg.encoder_layers), ("decoder", cfg.decoder_layers)):
+        for i in range(n):
+            p = f"{stack}.layers.{i}"
+            for name in ("q_proj", "k_proj", "v_proj", "output_proj"):
+                lin(f"{p}.self_attn.{name}", M, M)
+            ln(p + ".self_attn_layer_norm", M)
+            conv(p + ".conv1d.conv1", Ci, M, cfg.conv_kernel)
+            conv(p + ".conv1d.conv2", M, Ci, cfg.conv_kernel, gain=1.0)
+            ln(p + ".conv1d_layer_norm", M)
+            film(p + ".film", M)
+    va = "decoder_frontend.variance_adaptor."
+    for name in ("pitch_predictor", "vuv_predictor", "energy_predictor"):
+        p = va + name
+        conv(p + ".conv1.0", H, M, cfg.pred_kernel)
+        ln(p + ".ln1", H)
+        conv(p + ".conv2.0", H, H, cfg.pred_kernel)
+        ln(p + ".ln2", H)
+        film(p + ".film", H)
+        lin(p + ".proj", 1, H)
+    for name in ("embed_pitch", "embed_energy"):
+        sd[va + name + ".weight"] = rnd(M, 1, 1, scale=0.5)
+        sd[va + name + ".bias"] = rnd(M, scale=0.1)
+    sd["decoder_frontend.pos_emb_alpha"] = uni(1, lo=1.1, hi=1.4)
+    lin("final_proj", cfg.mel_dim, M)
+    for i in range(cfg.post_layers):
+        ci = cfg.mel_dim if i == 0 else cfg.post_dim
+        co = cfg.mel_dim if i == cfg.post_layers - 1 else cfg.post_dim
+        conv(f"layers.{i}.0", co, ci, cfg.post_kernel, gain=1.0)
+        sd[f"layers.{i}.1.weight"] = q(1 + rnd(co, scale=0.1))
+        sd[f"layers.{i}.1.bias"] = rnd(co, scale=0.1)
+        sd[f"layers.{i}.1.running_mean"] = rnd(co, scale=0.1)
+        sd[f"layers.{i}.1.running_var"] = uni(co, lo=0.5, hi=1.5)
+    return sd
