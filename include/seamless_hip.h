@@ -471,7 +471,7 @@ int sc_prosody_encode(sc_prosody_encoder* p, const float* d_fbank, int32_t n, in
                       const float* d_gcmvn_mean_or_null, const float* d_gcmvn_std_or_null, float* d_out);
 
 /* ---- PRETSSEL acoustic model: units + prosody vector -> mel spectrogram (reference models/generator/vocoder.py:488-513, the first
- * half of PretsselVocoder.forward; the waveform generator behind it is not built) -------------------------------------------
+ * half of PretsselVocoder.forward; the waveform generator behind it is sc_pretssel_wave below) ------------------------------
  * A handle of its own.  sc_pretssel_load takes the module's own state-dict names (the reference loader converts nothing):
  *   encoder_frontend.{embed_tokens.weight, pos_emb_alpha, embed_lang.weight}, {encoder,decoder}.layers.N.{self_attn.{q,k,v,output}_proj,
  *   self_attn_layer_norm, conv1d.conv{1,2}, conv1d_layer_norm, film.proj}.*, .film.{s_gamma,s_beta},
@@ -504,6 +504,41 @@ void sc_pretssel_free(sc_pretssel* p);
  * vocabulary, a token count or frame count + pad_idx + 1 above max_seq_len, frames above t_cap, lang_index outside the table. */
 int sc_pretssel_mel(sc_pretssel* p, const int32_t* h_tokens, int32_t n, int32_t s_tok, const int32_t* h_tok_lens, const int32_t* h_durations,
                     int32_t lang_index, const float* d_prosody, float* d_mel, int32_t t_cap, int32_t* h_frame_lens_or_null);
+
+/* ---- PRETSSEL waveform generator: mel spectrogram -> waveform (reference models/generator/vocoder.py:515-573, the second half of
+ * PretsselVocoder.forward; added within ABI v10, purely additive) ----------------------------------------------------------
+ * A handle of its own (sc_pretssel ignores these tensors).  sc_pretssel_wave_load takes the module's own names.  With P =
+ * post_layers, U = num_upsamples and the 32 stream layers in four chunks of 8 at layers.{P, P+9, P+17+U, P+25+4U}:
+ *   SConv: layers.N.conv.conv.{bias,weight_g,weight_v}; residual block: layers.N.block.{1,3}.conv.conv.*; transposed:
+ *   layers.N.convtr.convtr.*; LSTM: layers.N.lstm.{weight,bias}_{ih,hh}_l{0,1}; conv_pre layers.{P+8}, ups layers.{P+17+i},
+ *   conv_post layers.{P+33+4U}: .{bias,weight_g,weight_v}; HiFi-GAN ResBlocks layers.{P+25+U+j}.convs{1,2}.D.*; mean, scale.
+ * Weight norm is folded at load.  Matrices and convolution weights are held as fp16, everything else as fp32.
+ * Limits (SC_ERR_INVALID from sc_pretssel_wave_load, as are a missing tensor and a zero in `scale`): mel_dim a multiple of 4
+ * up to 128; 1..8 upsamples with kernel = 2 * rate, upsample_initial_channel divisible by 2^U with at least 4 channels left;
+ * 3 ResBlock kernels (odd) x 3 dilations, every stage on a kernel that takes packed items (C >= 128 a multiple of 32, or the
+ * fused narrow-stage kernels); 4 ratios of 1..16; 16 * n_filters (the LSTM width) a multiple of 32 up to 2048; dimension 1..1024;
+ * post_layers 0..64. */
+typedef struct sc_pretssel_wave_config {
+    int32_t abi_version; /* must be SC_ABI_VERSION */
+    int32_t mel_dim, post_layers;
+    int32_t upsample_initial_channel, num_upsamples;
+    int32_t upsample_rates[SC_MAX_UPSAMPLES], upsample_kernel_sizes[SC_MAX_UPSAMPLES];
+    int32_t resblock_kernel_sizes[3], resblock_dilation_sizes[3][3];
+    int32_t n_filters, ratios[4], dimension; /* ratios in the decoder's order (the reference's [8, 5, 4, 2]) */
+} sc_pretssel_wave_config;
+typedef struct sc_pretssel_wave_model sc_pretssel_wave_model;
+sc_pretssel_wave_model* sc_pretssel_wave_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_pretssel_wave_config* cfg, int device);
+void sc_pretssel_wave_free(sc_pretssel_wave_model* p);
+/* Every item by itself, as the reference loops: d_mel [n][t_cap][mel_dim] fp32 on the device (sc_pretssel_mel's output), of which
+ * item i's first h_frame_lens[i] rows are used; d_wav [n][wav_cap] fp32 on the device receives frames * hop samples per item
+ * (hop = the product of the upsample rates) and zeros behind them; h_wav_lens_or_null [n] the sample counts.  An item's samples do
+ * not depend on its companions, to the bit.  The items are packed and go in groups of at most 2^22 samples (32 channels x 4 B per
+ * sample and tensor at sample rate: 512 MB).  flags bit 0: the HiFi-GAN ResBlock products on two fp16 planes instead of the unit
+ * vocoder's default (hi plane only).
+ * SC_ERR_INVALID, with nothing launched: n outside 1..1024, an item without frames, frames above t_cap, frames * hop above
+ * wav_cap or above 2^22. */
+int sc_pretssel_wave(sc_pretssel_wave_model* p, const float* d_mel, int32_t n, int32_t t_cap, const int32_t* h_frame_lens, float* d_wav, int32_t wav_cap,
+                     int32_t* h_wav_lens_or_null, int32_t flags);
 
 /* The kernel-level test hooks (sc_op_*) and the dispatch introspection the parity tests drive are exported too but are NOT part
  * of the drop-in boundary: include/seamless_hip_internal.h. */

@@ -322,6 +322,39 @@ int sc_op_pretssel_postnet(sc_pretssel* p, const float* d_proj, int32_t n, const
 int32_t sc_op_pretssel_postnet_tile(int32_t rows, int32_t dim);
 int32_t sc_op_pretssel_last_launches(sc_pretssel* p);
 
+/* Kernels of the PRETSSEL waveform generator's SEANet half by themselves (k_seanet.hip; tests/test_pretssel_wave_gpu.py).  Packed
+ * items: the rows [time][C] of item i follow those of item i - 1, h_lens [n] on the host.
+ * sc_op_lstm2: y = LSTM(x) + x, 2 layers, weights [4H][H] fp16 in torch.nn.LSTM's layout (gates i, f, g, o), biases fp32; one
+ *   input product and longest + 1 step launches (*h_launches_or_null); *d_max_pre_or_null: largest |gate pre-activation|.
+ * sc_op_seanet_resblock: y = x + conv_k1(ELU(conv_k3(ELU(x)))), d_w1 [C/2][C][3], d_w2 [C][C/2][1] fp16, C = 32 / 64;
+ *   sc_op_seanet_resblock_tile: rows of one workgroup's tile.
+ * sc_op_sconv: the "streamable" convolution, padding_total = k - stride split (total - total / 2) left / (total / 2) right plus
+ *   the zeros the last window needs; d_w fp32 [cout][cin][k].  transposed != 0: k = 2 * stride, d_w [cin][cout][k], the output
+ *   trimmed by the same split (stride * len rows out).  in_act 0 none / 1 ELU / 2 Tanh.  h_out_lens [n] receives the lengths.
+ * sc_op_seanet_tail: d_wav = 0.8 * conv_k(ELU(h)) + tanh(skip) on the first h_out_lens[i] samples of every item; d_h packed by
+ *   h_dec_lens [rows][cin], d_w [1][cin][k] fp16, d_skip packed by h_out_lens; wav_stride != 0: d_wav [n][wav_stride]. */
+/* sc_op_pretssel_wave_probe: the stage outputs of the handle's NEXT sc_pretssel_wave call (one group only), packed item after
+ * item, into device buffers of the caller's (each nullable): d_hifi [sum samples] the HiFi-GAN's output, d_lstm_enc / d_lstm_dec
+ * [sum steps][16 * n_filters], d_dec [sum decoder samples][n_filters] the decoder's last residual block.
+ * sc_op_pretssel_wave_lens: steps and decoder samples of an item of `frames` frames.  sc_op_pretssel_wave_last_launches: kernel
+ * launches of the SEANet half in the last call (the LSTMs: steps + 2 each).  sc_op_pretssel_wave_stage_ms: h_ms6 receives the last
+ * call's device time per stage from events on the handle's stream: normalisation + HiFi-GAN, encoder, encoder LSTM, the two
+ * convolutions around the bottleneck, decoder LSTM, decoder + tail. */
+int sc_op_pretssel_wave_probe(sc_pretssel_wave_model* p, float* d_hifi, float* d_lstm_enc, float* d_lstm_dec, float* d_dec);
+int sc_op_pretssel_wave_lens(sc_pretssel_wave_model* p, int32_t frames, int32_t* h_steps, int32_t* h_dec_len);
+int32_t sc_op_pretssel_wave_last_launches(sc_pretssel_wave_model* p);
+int sc_op_pretssel_wave_stage_ms(sc_pretssel_wave_model* p, float* h_ms6);
+int sc_op_lstm2(const float* d_x, const int32_t* h_lens, int32_t n, int32_t H, const void* d_wih0_f16, const void* d_whh0_f16, const float* d_b_ih0,
+                const float* d_b_hh0, const void* d_wih1_f16, const void* d_whh1_f16, const float* d_b_ih1, const float* d_b_hh1, float* d_y,
+                float* d_max_pre_or_null, int32_t* h_launches_or_null);
+int32_t sc_op_seanet_resblock_tile(void);
+int sc_op_seanet_resblock(const float* d_x, const int32_t* h_lens, int32_t n, int32_t C, const void* d_w1_f16, const float* d_b1, const void* d_w2_f16,
+                          const float* d_b2, float* d_y);
+int sc_op_sconv(const float* d_x, const int32_t* h_lens, int32_t n, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t transposed,
+                int32_t in_act, const float* d_w, const float* d_bias, const float* d_res_or_null, float* d_y, int32_t* h_out_lens);
+int sc_op_seanet_tail(const float* d_h, const int32_t* h_dec_lens, const int32_t* h_out_lens, int32_t n, int32_t cin, int32_t k, const void* d_w_f16,
+                      const float* d_bias, const float* d_skip, float* d_wav, int64_t wav_stride);
+
 #ifdef __cplusplus
 }
 #endif

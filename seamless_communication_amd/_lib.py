@@ -112,6 +112,14 @@ class sc_pretssel_config(C.Structure):
     ]
 
 
+class sc_pretssel_wave_config(C.Structure):
+    _fields_ = [
+        ("abi_version", _i), ("mel_dim", _i), ("post_layers", _i), ("upsample_initial_channel", _i), ("num_upsamples", _i),
+        ("upsample_rates", _i * 8), ("upsample_kernel_sizes", _i * 8), ("resblock_kernel_sizes", _i * 3), ("resblock_dilation_sizes", (_i * 3) * 3),
+        ("n_filters", _i), ("ratios", _i * 4), ("dimension", _i),
+    ]
+
+
 class sc_prosody_encoder_config(C.Structure):
     _fields_ = [
         ("abi_version", _i), ("input_dim", _i), ("embed_dim", _i), ("res2net_scale", _i), ("se_channels", _i), ("attention_channels", _i),
@@ -211,6 +219,18 @@ SIGNATURES = {
     "sc_op_pretssel_postnet": (C.c_int, [_P, _P, _i, _P, _P, _i]),
     "sc_op_pretssel_postnet_tile": (C.c_int32, [_i, _i]),
     "sc_op_pretssel_last_launches": (C.c_int32, [_P]),
+    "sc_pretssel_wave_load": (_P, [C.POINTER(sc_tensor_desc), C.c_size_t, C.POINTER(sc_pretssel_wave_config), C.c_int]),
+    "sc_pretssel_wave_free": (None, [_P]),
+    "sc_pretssel_wave": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P, _i]),
+    "sc_op_pretssel_wave_probe": (C.c_int, [_P, _P, _P, _P, _P]),
+    "sc_op_pretssel_wave_lens": (C.c_int, [_P, _i, _P, _P]),
+    "sc_op_pretssel_wave_last_launches": (C.c_int32, [_P]),
+    "sc_op_pretssel_wave_stage_ms": (C.c_int, [_P, _P]),
+    "sc_op_lstm2": (C.c_int, [_P, _P, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sc_op_seanet_resblock_tile": (C.c_int32, []),
+    "sc_op_seanet_resblock": (C.c_int, [_P, _P, _i, _i, _P, _P, _P, _P, _P]),
+    "sc_op_sconv": (C.c_int, [_P, _P, _i, _i, _i, _i, _i, _i, _i, _P, _P, _P, _P, _P]),
+    "sc_op_seanet_tail": (C.c_int, [_P, _P, _P, _i, _i, _i, _P, _P, _P, _P, C.c_int64]),
     "sc_op_knob": (C.c_int, [C.c_char_p, C.c_int]),
     "sc_op_force_general_gemm": (C.c_int, [C.c_int]),
     "sc_op_voc_pack_plan": (C.c_int32, [_PI, C.c_int32, C.c_int64, _PI, C.c_int32]),

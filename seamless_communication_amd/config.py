@@ -14,7 +14,7 @@ The S2ST path is speech in -> text -> units -> waveform; the NLLB text encoder
 from __future__ import annotations
 
 from dataclasses import dataclass, field, asdict
-from typing import List, Tuple
+from typing import Any, Dict, List, Tuple
 
 
 @dataclass
@@ -217,6 +217,50 @@ def ecapa_tdnn_config(arch: str = "base") -> EcapaTDNNConfig:
 
 
 @dataclass
+class PretsselWaveConfig:
+    """Waveform generator of the PRETSSEL vocoder (models/generator/builder.py): the mel HiFi-GAN, and the SEANet-style encoder,
+    two 2-layer LSTMs and decoder over its output.  The defaults are arch ``24khz``."""
+
+    upsample_rates: List[int] = field(default_factory=lambda: [5, 4, 4, 3])
+    upsample_kernel_sizes: List[int] = field(default_factory=lambda: [10, 8, 8, 6])
+    upsample_initial_channel: int = 512
+    resblock_kernel_sizes: List[int] = field(default_factory=lambda: [3, 7, 11])
+    resblock_dilation_sizes: List[List[int]] = field(default_factory=lambda: [[1, 3, 5], [1, 3, 5], [1, 3, 5]])
+    n_filters: int = 32
+    ratios: List[int] = field(default_factory=lambda: [8, 5, 4, 2])
+    dimension: int = 128
+    kernel_size: int = 7
+    residual_kernel_size: int = 3
+
+    @property
+    def hop(self) -> int:
+        h = 1
+        for r in self.upsample_rates:
+            h *= r
+        return h
+
+    def layer_index(self, post_layers: int) -> Dict[str, Any]:
+        """Where the pieces sit in ``PretsselVocoder.layers``: the 32 stream layers go in four chunks of 8 around conv_pre, the
+        upsampling convolutions, the HiFi-GAN ResBlocks and conv_post."""
+        p, u = post_layers, len(self.upsample_rates)
+        chunk = [p, p + 9, p + 17 + u, p + 25 + 4 * u]
+        return {"stream": [chunk[i // 8] + i % 8 for i in range(32)], "conv_pre": p + 8, "ups": [p + 17 + i for i in range(u)],
+                "resblocks": [p + 25 + u + i for i in range(3 * u)], "conv_post": p + 33 + 4 * u}
+
+    def lengths(self, frames: int) -> Tuple[int, int, int]:
+        """(samples, LSTM steps, decoder samples) of an item of ``frames`` mel frames: every strided level rounds up, the decoder
+        runs on the rounded-up length."""
+        n = frames * self.hop
+        steps = n
+        for r in reversed(self.ratios):
+            steps = -(-steps // r)
+        dec = steps
+        for r in self.ratios:
+            dec *= r
+        return n, steps, dec
+
+
+@dataclass
 class PretsselConfig:
     """Acoustic model of the PRETSSEL vocoder (models/generator/builder.py, archs ``16khz`` / ``24khz``: identical up to the mel
     spectrogram): unit embedding, FiLM-conditioned FFT encoder, variance adaptor with Gaussian upsampling, FFT decoder,
@@ -244,16 +288,22 @@ class PretsselConfig:
     post_kernel: int = 5
     upsample_delta: float = 0.1
     prosody_encoder: EcapaTDNNConfig = field(default_factory=EcapaTDNNConfig)
+    waveform: PretsselWaveConfig = field(default_factory=PretsselWaveConfig)
 
 
 def pretssel_config(arch: str = "24khz") -> PretsselConfig:
     """``16khz`` / ``24khz``: the reference's architectures (they differ in the waveform generator only; ``16khz`` ships without
     languages in its builder, the card supplies them).  ``small``: 1 + 1 layers at the same width and head size for parity tests."""
-    if arch in ("16khz", "24khz"):
+    if arch == "24khz":
         return PretsselConfig(name=arch)
+    if arch == "16khz":
+        return PretsselConfig(name=arch, waveform=PretsselWaveConfig(upsample_rates=[5, 4, 4, 2], upsample_kernel_sizes=[10, 8, 8, 4]))
     if arch == "small":
+        # waveform half: one wide (128) and two narrow (64, 32) HiFi-GAN stages through the rates 5 and 3, a 128-wide LSTM
         return PretsselConfig(name="small", encoder_layers=1, decoder_layers=1, conv_inner_dim=256, pred_hidden_dim=128, post_dim=128, num_langs=2,
-                              film_cond_dim=64 + 64, prosody_encoder=ecapa_tdnn_config("small"))
+                              film_cond_dim=64 + 64, prosody_encoder=ecapa_tdnn_config("small"),
+                              waveform=PretsselWaveConfig(upsample_rates=[5, 3, 2], upsample_kernel_sizes=[10, 6, 4], upsample_initial_channel=256, n_filters=8,
+                                                          dimension=32))
     raise ValueError(f"unknown PRETSSEL arch '{arch}' (supported: 16khz, 24khz, small)")
 
 

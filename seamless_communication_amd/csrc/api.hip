@@ -1136,7 +1136,8 @@ int sc_op_conv_transpose1d(const float* d_x, const void* d_v_f16, const void* d_
                            int32_t nb, int32_t t_in, int32_t cin, int32_t cout, int32_t k, int32_t stride, int32_t pad,
                            int32_t in_act) {
     SC_API_BEGIN
-    SC_CHECK(pad == (k - stride) / 2 && k - 2 * pad == stride, "sc_op_conv_transpose1d: unsupported geometry");
+    // k - stride odd: padding rounded up with output_padding 1 (the PRETSSEL generator's upsampling convolutions at odd rates)
+    SC_CHECK(k >= stride && pad == (k - stride + 1) / 2 && k - 2 * pad + (k - stride) % 2 == stride, "sc_op_conv_transpose1d: unsupported geometry");
     Model tmp;
     ConvT c;
     c.cin = cin;

@@ -872,6 +872,81 @@ void launch_pretssel_postnet_bn_tanh(const float* x, const float* scale, const f
 void launch_pretssel_postnet_out(const float* x, const float* scale, const float* shift, const float* proj, const float* gstd, const float* gmean,
                                  const int* ext_item, const int2* ext_pos, const int* frame_off, int ext_rows, int C, int t_cap, float* mel, hipStream_t s);
 
+// ---- PRETSSEL waveform generator, SEANet half (k_seanet.hip; reference models/generator/streamable.py, vocoder.py:556-572) ---
+// Packed items: rows [time][C] of every item back to back, row_off / in_off / out_off [n + 1] on the device.
+// 2-layer LSTM (gate order i, f, g, o), one launch per step: the launch at t computes layer 0 at step t (xproj = x . W_ih0^T
+// for all rows comes from one product up front) and layer 1 at step t - 1 from [h0 ; h1] against w1 = [W_ih1 | W_hh1], and
+// writes y = h1 + x.  Steps 0 .. longest item inclusive: T + 1 launches.  c0 / c1 [n][H] start as zeros.
+struct LstmStepArgs {
+    const float* xproj = nullptr;  // [rows][4H]
+    const float* x = nullptr;      // [rows][H]
+    const __half* whh0 = nullptr;  // [4H][H]
+    const __half* w1 = nullptr;    // [4H][2H]
+    const float* b_ih0 = nullptr;
+    const float* b_hh0 = nullptr;
+    const float* b_ih1 = nullptr;
+    const float* b_hh1 = nullptr;
+    float* h0 = nullptr;  // [rows][H]
+    float* h1 = nullptr;  // [rows][H]
+    float* c0 = nullptr;  // [n][H]
+    float* c1 = nullptr;
+    float* y = nullptr;   // [rows][H]
+    float* max_pre = nullptr;  // nullable: largest |gate pre-activation|
+    const int* row_off = nullptr;
+    int H = 0;
+};
+bool lstm2_supported(int H);  // a multiple of 32 up to 2048
+void launch_lstm2_step(const LstmStepArgs& a, int n, int t, hipStream_t s);
+// y = x + conv_k1(ELU(conv_k3(ELU(x)))), C -> C / 2 -> C, at C = 32 / 64; w1 [C/2][3 * C] tap-major, w2 [C][C/2] fp16
+constexpr int SEANET_RES_TILE = 64;
+struct SeanetResArgs {
+    const float* x = nullptr;
+    const __half* w1 = nullptr;
+    const float* b1 = nullptr;
+    const __half* w2 = nullptr;
+    const float* b2 = nullptr;
+    float* y = nullptr;  // must not alias x
+    const int* row_off = nullptr;
+    int n = 0, longest = 0, C = 0;
+};
+bool seanet_resblock_supported(int C);
+void launch_seanet_resblock(const SeanetResArgs& a, hipStream_t s);
+// streamable convolutions: y[q] = bias + sum_tap w[tap] . in_act(x[q * stride + tap - left]) (+ res), zeros outside the item;
+// transposed (k = 2 * stride): y[p] = bias + the two taps of the untrimmed output at p + left.  wt [k * cin][cout] fp16.
+enum SeanetInAct { SEANET_IN_NONE = 0, SEANET_IN_ELU = 1, SEANET_IN_TANH = 2 };
+struct SconvArgs {
+    const float* x = nullptr;
+    const __half* wt = nullptr;
+    const float* bias = nullptr;
+    const float* res = nullptr;  // indexed like y; the forward convolution only
+    float* y = nullptr;
+    const int* in_off = nullptr;
+    const int* out_off = nullptr;
+    int n = 0, longest_out = 0, cin = 0, cout = 0, k = 0, stride = 1, left = 0, in_act = SEANET_IN_NONE;
+};
+bool sconv_supported(int cin, int cout, int k, int stride);  // the input window of a tile fits 48 KB of LDS
+void launch_sconv(const SconvArgs& a, hipStream_t s);
+void launch_sconvtr(const SconvArgs& a, hipStream_t s);
+// wav[t] = 0.8 * (bias + conv_k(ELU(h)))[t] + tanh(skip[t]) for t < the item's output length; h on the decoder's own length
+struct SeanetTailArgs {
+    const float* h = nullptr;     // [decoder rows][cin]
+    const __half* w = nullptr;    // [k * cin] tap-major
+    const float* bias = nullptr;  // [1]
+    const float* skip = nullptr;  // packed by out_off
+    float* wav = nullptr;         // wav_stride != 0: [n][wav_stride], else packed by out_off
+    const int* in_off = nullptr;
+    const int* out_off = nullptr;
+    int64_t wav_stride = 0;
+    int n = 0, longest_out = 0, cin = 0, k = 0;
+};
+bool seanet_tail_supported(int cin, int k);  // odd k; the weights and a tile's activated rows fit 48 KB of LDS
+void launch_seanet_tail(const SeanetTailArgs& a, hipStream_t s);
+// mel [n][t_cap][dim] -> out [off[n]][dim] = (mel - mean) / scale on every item's own rows, items back to back
+void launch_mel_norm_pack(const float* mel, const float* mean, const float* scale, const int* off, int n, int longest, int t_cap, int dim, float* out,
+                          hipStream_t s);
+// [d0][d1][k] fp32 (Conv1d: [cout][cin][k]; transposed: ConvTranspose1d's [cin][cout][k]) -> [k * cin][cout] fp16
+void launch_pack_sconv_weight(const float* w, __half* dst, int cin, int cout, int k, bool transposed, hipStream_t s);
+
 // ---- decode engine (k_engine.hip, engine.hip) ---------------------------------------------------------------------
 // One greedy step chain per GPU shared by every pass in flight.  A ROW STATE r (0 .. rows-1) owns everything that lives as
 // long as a hypothesis: K / V cache rows, encoder K / V, token history, captured decoder outputs, position, flags.  A SLOT s

@@ -318,7 +318,19 @@ struct SideScope {
 };
 
 // stage implementations (model_*.hip)
+struct PackedItems;
 void load_model(Model& m, const sc_tensor_desc* t, size_t n);
+void upload_tensors(Model& m, const sc_tensor_desc* t, size_t n);
+struct HifiganNames {
+    std::string pre, post;
+    std::vector<std::string> ups, res;
+};
+void load_hifigan_stack(Model& m, const HifiganNames& nm, int in_dim);
+// The HiFi-GAN stack on packed items from conv_pre's input rows [pk.rows()][in_dim] -> d_out [pk.rows() * hop], conv_post without
+// the tanh.  pk.off / pk.n / pk.d_off set by the caller.  plane_split: bit 0 wide stages, bit 2 narrow stages on two fp16 planes
+// (0: the unit vocoder's default, hi plane only).  Synchronises the handle's stream.
+void run_hifigan_rows(Model& m, const float* d_rows_in, PackedItems& pk, float* d_out, int plane_split);
+int64_t hifigan_packed_row_cap(const Model& m, int hop);  // unit rows one packed group may hold; 0: a geometry the packed kernels do not take
 // sample_rate: the waveform's own rate (16000 = the model's; others get their own window / shift / FFT size / mel banks)
 void run_fbank(Model& m, const float* d_wav, int n, int64_t wav_stride, const int32_t* h_ns, int standardize,
                float* d_out, int t_rows, int32_t* h_frames, int sample_rate = 16000);
@@ -420,5 +432,20 @@ void conv1d(Model& m, const float* x, const Conv& c, const float* res, float* y,
             int dil, const int* d_in_lens, int in_act, int act, const PackedItems* pk = nullptr, int mul = 1);
 void conv_transpose1d(Model& m, const float* x, const ConvT& c, float* y, int nb, int t_in, int in_act, const PackedItems* pk = nullptr,
                       int mul = 1);
+
+// 2-layer LSTM with the `y + x` skip (the waveform generator's StreamableLSTM): fp16 weights, gate order i, f, g, o
+struct Lstm2 {
+    const __half* wih0 = nullptr;  // [4H][H]
+    const __half* whh0 = nullptr;  // [4H][H]
+    const __half* w1 = nullptr;    // [4H][2H] = [W_ih1 | W_hh1]
+    const float* b_ih0 = nullptr;
+    const float* b_hh0 = nullptr;
+    const float* b_ih1 = nullptr;
+    const float* b_hh1 = nullptr;
+    int H = 0;
+};
+// packed items (d_off [n + 1]): xproj [rows][4H], h0 / h1 [rows][H], c [2][n][H] are scratch; returns the launches made
+int run_lstm2(const Lstm2& w, const float* x, const int* d_off, int n, int rows, int longest, float* xproj, float* h0, float* h1, float* c, float* y,
+              float* max_pre, hipStream_t s);
 
 }  // namespace sc

@@ -289,10 +289,11 @@ struct Loader {
         c.cout = cout;
         c.k = k;
         c.stride = stride;
-        c.pad = (k - stride) / 2;
+        // k - stride odd (the PRETSSEL generator's k = 2u at odd u): padding rounded up with output_padding 1, still stride * L out
+        c.pad = (k - stride + 1) / 2;
         c.taps = cdiv(k, stride);
         c.kpad = (int)align_up((int64_t)cin * c.taps, 32);
-        SC_CHECK(k - 2 * c.pad == stride, "sc_load: '%s' ConvTranspose1d(k=%d,stride=%d) does not upsample by its stride",
+        SC_CHECK(k >= stride && k - 2 * c.pad + (k - stride) % 2 == stride, "sc_load: '%s' ConvTranspose1d(k=%d,stride=%d) does not upsample by its stride",
                  p.c_str(), k, stride);
         const __half* v = f16(p + ".weight_v", {cin, cout, k});
         const __half* g = f16(p + ".weight_g", {cin, 1, 1});
@@ -343,12 +344,8 @@ void build_fbank_consts(Model& m) {
 
 }  // namespace
 
-void load_model(Model& m, const sc_tensor_desc* t, size_t n) {
-    const sc_config& c = m.cfg;
-    SC_CHECK(c.model_dim == c.num_heads * 64, "sc_load: head_dim must be 64 (model_dim=%d, heads=%d)", c.model_dim,
-             c.num_heads);
-    SC_CHECK(c.model_dim % 32 == 0, "sc_load: model_dim must be a multiple of 32");
-    // ---- upload ----------------------------------------------------------------
+// the caller's tensors into memory the handle owns, by name (m.raw); tied tensors share storage
+void upload_tensors(Model& m, const sc_tensor_desc* t, size_t n) {
     std::unordered_map<const void*, void*> seen;  // tied tensors share storage
     for (size_t i = 0; i < n; ++i) {
         const sc_tensor_desc& d = t[i];
@@ -375,6 +372,14 @@ void load_model(Model& m, const sc_tensor_desc* t, size_t n) {
         }
         m.raw[d.name] = std::move(r);
     }
+}
+
+void load_model(Model& m, const sc_tensor_desc* t, size_t n) {
+    const sc_config& c = m.cfg;
+    SC_CHECK(c.model_dim == c.num_heads * 64, "sc_load: head_dim must be 64 (model_dim=%d, heads=%d)", c.model_dim,
+             c.num_heads);
+    SC_CHECK(c.model_dim % 32 == 0, "sc_load: model_dim must be a multiple of 32");
+    upload_tensors(m, t, n);
     Loader L(m);
     const int M = c.model_dim;
     build_fbank_consts(m);
@@ -643,6 +648,35 @@ void load_model(Model& m, const sc_tensor_desc* t, size_t n) {
             m.vdp_proj_b = L.f32(d + ".proj.bias", {1});
         }
     }
+    SC_HIP(hipStreamSynchronize(m.stream));
+}
+
+// The HiFi-GAN stack of a handle whose tensors carry other names (the PRETSSEL waveform generator: layers.N): geometry from
+// m.cfg's voc_* fields, conv_pre over `in_dim` input channels.  res holds num_upsamples * num_resblock_kernels names.
+void load_hifigan_stack(Model& m, const HifiganNames& nm, int in_dim) {
+    const sc_config& c = m.cfg;
+    Loader L(m);
+    const int nk = c.voc_num_resblock_kernels;
+    SC_CHECK((int)nm.ups.size() == c.voc_num_upsamples && (int)nm.res.size() == c.voc_num_upsamples * nk, "load_hifigan_stack: %zu + %zu names", nm.ups.size(),
+             nm.res.size());
+    int ch = c.voc_upsample_initial_channel;
+    m.voc_pre = L.conv_wn(nm.pre, ch, in_dim, 7);
+    for (int i = 0; i < c.voc_num_upsamples; ++i) {
+        m.voc_ups.push_back(L.convT_wn(nm.ups[i], ch, ch / 2, c.voc_upsample_kernel_sizes[i], c.voc_upsample_rates[i]));
+        ch /= 2;
+        for (int j = 0; j < nk; ++j) {
+            ResBlock rb;
+            const std::string& r = nm.res[(size_t)i * nk + j];
+            const int rk = c.voc_resblock_kernel_sizes[j];
+            for (int d = 0; d < c.voc_num_resblock_dilations; ++d) {
+                rb.convs1.push_back(L.conv_wn(r + ".convs1." + std::to_string(d), ch, ch, rk));
+                rb.convs2.push_back(L.conv_wn(r + ".convs2." + std::to_string(d), ch, ch, rk));
+                rb.dil.push_back(c.voc_resblock_dilation_sizes[j][d]);
+            }
+            m.voc_res.push_back(std::move(rb));
+        }
+    }
+    m.voc_post = L.conv_wn(nm.post, 1, ch, 7);
     SC_HIP(hipStreamSynchronize(m.stream));
 }
 

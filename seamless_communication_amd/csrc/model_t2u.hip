@@ -504,8 +504,11 @@ namespace {
 // receives pk->rows() * hop samples in the same order, T is unused.  Every kernel then takes an item's first row and length
 // from the item table: a convolution sees zeros beyond an item's own two ends and a fused kernel's tiles are counted from the
 // item's first row, so an item's arithmetic is what it is as a row of a padded batch of its own length.
+// d_rows_in != null: the stack starts from conv_pre's input rows [unit rows][voc_pre.cin] instead of the embedded units (the
+// PRETSSEL waveform generator: normalised mel rows); post_act: the activation behind conv_post; plane_split >= 0 overrides the
+// process-wide SC_VOC_SPLIT for this call (bit 0 wide stages, bit 2 narrow stages on two planes).
 void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_spkr, int n, int T, float* d_wav,
-                  const PackedItems* pk = nullptr) {
+                  const PackedItems* pk = nullptr, const float* d_rows_in = nullptr, int post_act = ACT_TANH, int plane_split = -1) {
     const sc_config& c = m.cfg;
     const int E = c.voc_embedding_dim, Lg = c.voc_lang_embedding_dim, Sp = c.voc_spkr_embedding_dim;
     int ch = c.voc_upsample_initial_channel;
@@ -513,7 +516,10 @@ void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_
     int rate = 1;                                                          // rows per unit row at the current stage
     const size_t rows0 = pk ? (size_t)pk->rows() : (size_t)n * T;  // unit rows in all
     Buf<float> x;
-    {
+    if (d_rows_in) {
+        x = Buf<float>(m.pp(), rows0 * ch);
+        conv1d(m, d_rows_in, m.voc_pre, nullptr, x, n, T, 1, 3, 1, nullptr, IN_NONE, ACT_NONE, pk, 1);
+    } else {
         Buf<float> in(m.pp(), rows0 * (E + Lg + Sp));
         launch_vocoder_embed(d_units, n, T, m.voc_dict, E, m.voc_lang, Lg, d_lang, m.voc_spkr, Sp, d_spkr, in, m.stream, pk ? pk->d_off : nullptr,
                              (int)rows0);
@@ -529,7 +535,8 @@ void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_
     // averages stay fp32.  Measured at full size: max |wav - oracle| 8e-5 against 6e-5 with both planes
     // (profiles/r6_vocoder_single_plane.txt).  SC_VOC_SPLIT=1 (with SC_DEBUG_NUMERICS=1) restores the two-plane products:
     // bit 0 wide stages (C >= 128, DMA GEMM), bit 2 narrow stages (C <= 64, k_resblock.hip).
-    static const int voc_split = knob::value("SC_VOC_SPLIT", 0);
+    static const int voc_split_knob = knob::value("SC_VOC_SPLIT", 0);
+    const int voc_split = plane_split >= 0 ? plane_split : voc_split_knob;
     const int voc_single = (voc_split & 1 ? 0 : 1) | (voc_split & 4 ? 0 : 4);
     for (int i = 0; i < c.voc_num_upsamples; ++i) {
         const ConvT& up = m.voc_ups[i];
@@ -700,7 +707,7 @@ void vocode_batch(Model& m, const int* d_units, const int* d_lang, const int* d_
         rate = rate2;
     }
     // F.leaky_relu default slope 0.01, conv_post, tanh (hifigan.py:192-194)
-    conv1d(m, x, m.voc_post, nullptr, d_wav, n, t, 1, 3, 1, nullptr, IN_LRELU_001, ACT_TANH, pk, rate);
+    conv1d(m, x, m.voc_post, nullptr, d_wav, n, t, 1, 3, 1, nullptr, IN_LRELU_001, post_act, pk, rate);
 }
 
 // Unit frames of context a kept output sample can depend on, per side: conv_pre (3) + per stage the transposed
@@ -806,6 +813,18 @@ void vocoder_tile_tables(const Model& m, PackedItems& pk) {
 }
 
 }  // namespace
+
+int64_t hifigan_packed_row_cap(const Model& m, int hop) { return vocoder_packed_row_cap(m, hop); }
+
+void run_hifigan_rows(Model& m, const float* d_rows_in, PackedItems& pk, float* d_out, int plane_split) {
+    vocoder_tile_tables(m, pk);
+    Buf<int> tabs(m.pp(), pk.tabs.size());
+    SC_HIP(hipMemcpyAsync(tabs.get(), pk.tabs.data(), pk.tabs.size() * sizeof(int), hipMemcpyHostToDevice, m.stream));
+    pk.d_tabs = tabs.get();
+    vocode_batch(m, nullptr, nullptr, nullptr, pk.n, pk.longest(), d_out, &pk, d_rows_in, ACT_NONE, plane_split);
+    SC_HIP(hipStreamSynchronize(m.stream));  // pk.tabs (pageable host memory) and `tabs` stay alive until the copy and its readers are done
+    pk.d_tabs = nullptr;
+}
 
 std::vector<int> plan_packed_groups(const std::vector<int>& need, int64_t budget_rows) {
     std::vector<int> first;

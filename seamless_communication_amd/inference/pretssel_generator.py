@@ -1,10 +1,14 @@
-"""``PretsselGenerator``: the acoustic model of the PRETSSEL expressive vocoder (models/generator/vocoder.py) on one MI355X.
+"""``PretsselGenerator``: the PRETSSEL expressive vocoder (models/generator/vocoder.py) on one MI355X.
 
 ``predict_mel`` restates ``PretsselGenerator.predict`` of the reference (cli/expressivity/predict/pretssel_generator.py) up to the
 mel spectrogram that ``PretsselVocoder.forward`` hands to its waveform generator: host preparation of the units, the prosody
 vector from the gcmvn-normalised fbank (:class:`ProsodyEncoder`), and the FiLM-conditioned encoder, variance adaptor, Gaussian
-upsampling, decoder, projection, post-net and gcmvn de-normalisation inside libseamless_hip (``sc_pretssel_mel``).  The waveform
-generator (mel HiFi-GAN with a SEANet-style encoder / decoder and LSTMs) is not built yet: ``predict`` says so.
+upsampling, decoder, projection, post-net and gcmvn de-normalisation inside libseamless_hip (``sc_pretssel_mel``).
+
+``predict`` goes on to the waveform, as the reference's does: per item, by itself, ``(mel - mean) / scale``, the mel HiFi-GAN, the
+SEANet-style encoder, two 2-layer LSTMs and decoder over its output, and ``0.8 * h[:L] + tanh(skip)`` (``sc_pretssel_wave``, a
+handle of its own).  It needs a checkpoint that holds the complete waveform half (``layers.<post_layers>...``, ``mean``,
+``scale``); on a mel-only checkpoint ``predict`` raises ``NotImplementedError`` and ``predict_mel`` is what there is.
 """
 from __future__ import annotations
 
@@ -16,7 +20,7 @@ from torch import Tensor
 
 from .. import synthetic as _syn
 from ..config import PretsselConfig, pretssel_config
-from ..runtime import HipPretssel
+from ..runtime import HipPretssel, HipPretsselWave
 from .prosody_encoder import ProsodyEncoder
 
 SequenceData = Dict[str, Any]
@@ -26,7 +30,7 @@ class PretsselGenerator:
     """``PretsselGenerator(card_or_state_dict, vocab_info=None, device=..., dtype=torch.float32)``.
 
     A card is a dict with ``model_arch`` (``16khz`` / ``24khz`` / ``small``), ``checkpoint`` (``file://<path>`` of a torch
-    checkpoint or ``synthetic://<seed>``), ``model_config.langs``, ``model_config.gcmvn_stats`` (``mean`` / ``std``) and
+    checkpoint or ``synthetic://<seed>`` for the acoustic model alone, ``synthetic-full://<seed>`` with the waveform half), ``model_config.langs``, ``model_config.gcmvn_stats`` (``mean`` / ``std``) and
     ``sample_rate``.  A bare state dict takes ``langs`` / ``gcmvn_stats`` / ``config`` as keyword arguments.  The prosody encoder
     is built from the same state dict (``encoder_frontend.prosody_encoder.*``).  ``vocab_info`` (anything with ``pad_idx`` and
     ``eos_idx``) defaults to the architecture's.
@@ -63,11 +67,14 @@ class PretsselGenerator:
             uri = card.get("checkpoint", "")
             if uri.startswith("synthetic://"):
                 sd = _syn.make_pretssel_state_dict(self.cfg, int(uri[len("synthetic://"):] or 0))
+            elif uri.startswith("synthetic-full://"):
+                seed = int(uri[len("synthetic-full://"):] or 0)
+                sd = {**_syn.make_pretssel_state_dict(self.cfg, seed), **_syn.make_pretssel_wave_state_dict(self.cfg, seed)}
             elif uri.startswith("file://"):
                 sd = torch.load(uri[len("file://"):], map_location="cpu")
                 sd = sd.get("model", sd)
             else:
-                raise ValueError(f"card '{card.get('name')}': checkpoint '{uri}' is not reachable offline; use file://<path> or synthetic://<seed>")
+                raise ValueError(f"card '{card.get('name')}': checkpoint '{uri}' is not reachable offline; use file://<path>, synthetic://<seed> or synthetic-full://<seed>")
         if not langs or len(langs) != self.cfg.num_langs:
             raise ValueError(f"model_config.langs must name the {self.cfg.num_langs} languages of embed_lang, got {langs}")
         if not gcmvn_stats or "mean" not in gcmvn_stats or "std" not in gcmvn_stats:
@@ -88,6 +95,8 @@ class PretsselGenerator:
             raise ValueError(f"the state dict holds no prosody encoder under '{pre}'")
         self.prosody_encoder = ProsodyEncoder(ecapa, device=dev, config=self.cfg.prosody_encoder)
         self.model = HipPretssel(self.cfg, sd, self.gcmvn_mean, self.gcmvn_std, device=dev.index or 0)
+        # the waveform generator: only from a checkpoint that holds its every tensor
+        self.wave_model = HipPretsselWave(self.cfg, sd, device=dev.index or 0) if HipPretsselWave.is_complete(self.cfg, sd) else None
 
     @staticmethod
     def units_to_tokens(units: List[List[int]], eos_idx: int, pad_idx: int = 1) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -135,6 +144,15 @@ class PretsselGenerator:
         mel, flens = self.model.mel(tk, tl, du, self.lang_to_index[tgt_lang], pv)
         return mel.to(self.dtype), torch.from_numpy(flens.astype(np.int64))
 
+    @torch.inference_mode()
     def predict(self, units: List[List[int]], tgt_lang: str, prosody_encoder_input: SequenceData):
-        raise NotImplementedError("PretsselGenerator.predict needs the PRETSSEL waveform generator (mel HiFi-GAN + SEANet-style encoder / decoder with "
-                                  "LSTMs), which is not built yet; predict_mel returns the mel spectrogram it would consume")
+        """-> ``BatchedSpeechOutput(units, audio_wavs, sample_rate)``; ``audio_wavs[i]`` is (1, 1, frames_i * hop), as in the
+        reference, every item computed by itself from its own mel frames."""
+        if self.wave_model is None:
+            raise NotImplementedError("PretsselGenerator.predict needs the waveform generator, and this checkpoint does not hold its tensors "
+                                      "(layers.<post_layers>..., mean, scale); predict_mel returns the mel spectrogram it would consume")
+        from .translator import BatchedSpeechOutput
+
+        mel, flens = self.predict_mel(units, tgt_lang, prosody_encoder_input)
+        wavs = self.wave_model.wave(mel.to(torch.float32), flens.numpy())
+        return BatchedSpeechOutput(units=units, audio_wavs=[w.to(self.dtype).reshape(1, 1, -1) for w in wavs], sample_rate=self.output_sample_rate)

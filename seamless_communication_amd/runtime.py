@@ -820,3 +820,117 @@ class HipPretssel:
 
     def last_launches(self) -> int:
         return int(self.lib.sc_op_pretssel_last_launches(self.handle))
+
+
+class HipPretsselWave:
+    """Waveform generator of the PRETSSEL vocoder resident in one GPU's HBM (``sc_pretssel_wave*``): a handle of its own, next to
+    :class:`HipPretssel`, which makes the mel spectrogram it consumes."""
+
+    @staticmethod
+    def tensor_names(cfg) -> List[str]:
+        from . import synthetic as _syn
+
+        return _syn.wave_tensor_names(cfg)
+
+    @classmethod
+    def is_complete(cls, cfg, state_dict: Dict[str, torch.Tensor]) -> bool:
+        """Whether the state dict holds every tensor of the waveform half."""
+        return all(k in state_dict for k in cls.tensor_names(cfg))
+
+    @classmethod
+    def select_tensors(cls, cfg, state_dict: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """The waveform half in the precision the library holds it in: weights fp16, biases / ``mean`` / ``scale`` fp32."""
+        sd = {}
+        for k in cls.tensor_names(cfg):
+            if k not in state_dict:
+                raise ValueError(f"the state dict lacks '{k}' of the waveform generator")
+            v = state_dict[k]
+            sd[k] = v.to(torch.float16) if v.dim() >= 2 else v.to(torch.float32)
+        return sd
+
+    def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], device: int = 0) -> None:
+        self.lib = _lib.load_library()
+        self.cfg = cfg
+        w = cfg.waveform
+        if len(w.ratios) != 4 or len(w.resblock_kernel_sizes) != 3 or any(len(d) != 3 for d in w.resblock_dilation_sizes):
+            raise ValueError("the waveform generator is built for 4 ratios and 3 ResBlock kernels x 3 dilations")
+        if not 1 <= len(w.upsample_rates) <= 8 or len(w.upsample_rates) != len(w.upsample_kernel_sizes):
+            raise ValueError("1..8 upsample rates with as many kernel sizes")
+        if w.kernel_size != 7 or w.residual_kernel_size != 3:
+            raise ValueError("the waveform generator is built for kernel_size 7 and residual_kernel_size 3")
+        sd = self.select_tensors(cfg, state_dict)
+        self.device_index = int(device)
+        self.device = torch.device("cuda", self.device_index)
+        if not torch.cuda.is_available():
+            raise SeamlessHipError("no HIP device is visible; the HIP path has no CPU fallback")
+        descs, keep = _tensor_descs(sd)
+        c = _lib.sc_pretssel_wave_config()
+        c.abi_version = _lib.SC_ABI_VERSION
+        c.mel_dim, c.post_layers = int(cfg.mel_dim), int(cfg.post_layers)
+        c.upsample_initial_channel, c.num_upsamples = int(w.upsample_initial_channel), len(w.upsample_rates)
+        for i, (u, k) in enumerate(zip(w.upsample_rates, w.upsample_kernel_sizes)):
+            c.upsample_rates[i], c.upsample_kernel_sizes[i] = int(u), int(k)
+        for j in range(3):
+            c.resblock_kernel_sizes[j] = int(w.resblock_kernel_sizes[j])
+            for d in range(3):
+                c.resblock_dilation_sizes[j][d] = int(w.resblock_dilation_sizes[j][d])
+        c.n_filters, c.dimension = int(w.n_filters), int(w.dimension)
+        for i in range(4):
+            c.ratios[i] = int(w.ratios[i])
+        self._c = c
+        self.hop = w.hop
+        self.handle = self.lib.sc_pretssel_wave_load(descs, len(sd), C.byref(c), self.device_index)
+        if not self.handle:
+            msg = self.lib.sc_last_error()
+            raise SeamlessHipError(f"sc_pretssel_wave_load failed: {msg.decode() if msg else '?'}")
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self.lib.sc_pretssel_wave_free(self.handle)
+            self.handle = None
+
+    def __del__(self) -> None:  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def wave(self, mel: torch.Tensor, frame_lens, two_plane: bool = False, probes: bool = False):
+        """mel (B, T_max, mel_dim) on the device, frame_lens (B,) -> one float32 tensor (frames_i * hop,) per item, each item
+        computed by itself.  ``two_plane``: the HiFi-GAN ResBlock products on two fp16 planes.  ``probes``: also a dict of the
+        packed stage outputs (``hifi``, ``lstm_enc``, ``lstm_dec``, ``dec``) and the per-item (samples, steps, decoder samples)."""
+        fl = _i32(frame_lens).reshape(-1)
+        if mel.device != self.device:
+            raise ValueError(f"the mel spectrogram lives on {mel.device}, the model on {self.device}")
+        x = mel.detach().to(torch.float32).contiguous()
+        if x.dim() != 3 or x.shape[0] != fl.shape[0] or x.shape[2] != self.cfg.mel_dim:
+            raise ValueError(f"mel must be (B, T, {self.cfg.mel_dim}) with B lengths, got {tuple(x.shape)}")
+        n, t_cap = int(x.shape[0]), int(x.shape[1])
+        wav_cap = max(1, int(fl.max(initial=1)) * self.hop)
+        out = torch.empty(n, wav_cap, dtype=torch.float32, device=self.device)
+        wl = np.zeros(n, dtype=np.int32)
+        pr = None
+        if probes:
+            lens = [self.cfg.waveform.lengths(int(f)) for f in fl]
+            H = 16 * self.cfg.waveform.n_filters
+            z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=self.device)  # noqa: E731
+            pr = {"hifi": z(sum(l[0] for l in lens)), "lstm_enc": z(sum(l[1] for l in lens), H), "lstm_dec": z(sum(l[1] for l in lens), H),
+                  "dec": z(sum(l[2] for l in lens), self.cfg.waveform.n_filters), "lens": lens}
+        torch.cuda.current_stream(self.device).synchronize()  # the handle runs on a stream of its own
+        if probes:
+            check(self.lib.sc_op_pretssel_wave_probe(self.handle, _ptr(pr["hifi"]), _ptr(pr["lstm_enc"]), _ptr(pr["lstm_dec"]), _ptr(pr["dec"])),
+                  "sc_op_pretssel_wave_probe")
+        check(self.lib.sc_pretssel_wave(self.handle, _ptr(x), n, t_cap, _ptr(fl), _ptr(out), wav_cap, _ptr(wl), 1 if two_plane else 0), "sc_pretssel_wave")
+        wavs = [out[i, :int(wl[i])].clone() for i in range(n)]
+        return (wavs, pr) if probes else wavs
+
+    def last_launches(self) -> int:
+        return int(self.lib.sc_op_pretssel_wave_last_launches(self.handle))
+
+    STAGES = ("hifigan", "encoder", "lstm_enc", "bottleneck", "lstm_dec", "decoder")
+
+    def last_stage_ms(self) -> Dict[str, float]:
+        """Device time per stage of the last ``wave`` call (events on the handle's stream)."""
+        ms = np.zeros(6, dtype=np.float32)
+        check(self.lib.sc_op_pretssel_wave_stage_ms(self.handle, _ptr(ms)), "sc_op_pretssel_wave_stage_ms")
+        return dict(zip(self.STAGES, (float(v) for v in ms)))
