@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256) void gemvp_kernel(GemvPArgs p) {
                     v[e] = (red[0][i][o] + red[1][i][o]) + (red[2][i][o] + red[3][i][o]);
                     const int feat = nt * 32 + 8 * g + e;
                     if (p.bias && feat < p.N) v[e] += p.bias[feat];
-                    if (p.act == ACT_RELU) v[e] = v[e] > 0.f ? v[e] : 0.f;
+                    if (p.act == ACT_RELU) v[e] = !(v[e] <= 0.f) ? v[e] : 0.f;  // NaN stays NaN
                     if (feat >= p.N) v[e] = 0.f;
                 }
                 if (m < live && (nt * 4 + g) * 8 < p.N) {

@@ -312,7 +312,7 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3_kernel(Gemv3Args p) {
 #pragma unroll
                 for (int c = 0; c < WAVES; ++c) s += red[c][jj][o];
                 s += bias8[it][e];
-                if (p.act == ACT_RELU) s = s > 0.f ? s : 0.f;
+                if (p.act == ACT_RELU) s = !(s <= 0.f) ? s : 0.f;  // NaN stays NaN
                 if ((nt0 + jt) * 32 + 8 * g + e >= p.N) s = 0.f;
                 v[e] = s;
             }
@@ -608,7 +608,7 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3s_kernel(Gemv3Args p) {
 #pragma unroll
                     for (int c = 0; c < WAVES; ++c) s += red[c][jj][o];
                     s += bias8[it][e];
-                    if (p.act == ACT_RELU) s = s > 0.f ? s : 0.f;
+                    if (p.act == ACT_RELU) s = !(s <= 0.f) ? s : 0.f;  // NaN stays NaN
                     if ((nt0 + jt) * 32 + 8 * gq + e >= p.N) s = 0.f;
                     v[e] = s;
                 }

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void engine_finalize_kernel(EngineFinalizeArgs
             bidx = a.eos_idx;
         }
         const float lprob = best - (m + logf(ssum));
-        tok = bidx;
+        tok = argmax_stored_index(bidx);
         R.score[r] += lprob;
         R.hist[(int64_t)r * R.cap + pos + 1] = tok;
         if (tok == a.eos_idx) {

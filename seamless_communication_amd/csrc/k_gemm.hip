@@ -32,7 +32,7 @@ static constexpr int BK = 32;
 static constexpr int LDS_LD = 40;  // halfs per LDS row (32 + 8 pad)
 
 __device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == ACT_RELU) return v > 0.f ? v : 0.f;
+    if (act == ACT_RELU) return !(v <= 0.f) ? v : 0.f;  // NaN stays NaN, -0 -> +0
     if (act == ACT_SILU) return v / (1.f + expf(-v));
     if (act == ACT_TANH) return tanhf(v);
     if (act == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));

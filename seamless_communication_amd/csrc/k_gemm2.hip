@@ -38,7 +38,7 @@ constexpr int FLD = 40;  // halfs per LDS row (32 + 8 pad): 16-byte fragment rea
 
 template <int ACT>
 __device__ __forceinline__ float act_fn(float v) {
-    if (ACT == ACT_RELU) return v > 0.f ? v : 0.f;
+    if (ACT == ACT_RELU) return !(v <= 0.f) ? v : 0.f;  // NaN stays NaN, -0 -> +0
     if (ACT == ACT_SILU) return v / (1.f + expf(-v));
     if (ACT == ACT_TANH) return tanhf(v);
     if (ACT == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(256) void gemm_fast_kernel(GemmArgs p, int tiles_n,
             if (CONV) x = a_ok[i] ? x : f32x4_t{0.f, 0.f, 0.f, 0.f};                            \
             if (IN_ACT) {                                                                       \
                 _Pragma("unroll") for (int j = 0; j < 4; ++j)                                   \
-                    x[j] = fmaxf(x[j], 0.f) + in_slope * fminf(x[j], 0.f);                      \
+                    x[j] = lrelu_in(x[j], in_slope);                                            \
             }                                                                                   \
             const half4_t hi = __builtin_convertvector(x, half4_t);                             \
             const f32x4_t back = __builtin_convertvector(hi, f32x4_t);                          \
@@ -494,7 +494,7 @@ __global__ __launch_bounds__(256) void gemm_fast2_kernel(GemmArgs p, int tiles_n
             f32x4_t x = AR[i];                                                                  \
             if (IN_ACT) {                                                                       \
                 _Pragma("unroll") for (int j = 0; j < 4; ++j)                                   \
-                    x[j] = fmaxf(x[j], 0.f) + in_slope * fminf(x[j], 0.f);                      \
+                    x[j] = lrelu_in(x[j], in_slope);                                            \
             }                                                                                   \
             const half4_t hi = __builtin_convertvector(x, half4_t);                             \
             const f32x4_t back = __builtin_convertvector(hi, f32x4_t);                          \

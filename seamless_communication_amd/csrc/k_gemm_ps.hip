@@ -34,7 +34,7 @@ constexpr int PBK = 32;
 
 template <int ACT>
 __device__ __forceinline__ float ps_act(float v) {
-    if (ACT == ACT_RELU) return v > 0.f ? v : 0.f;
+    if (ACT == ACT_RELU) return !(v <= 0.f) ? v : 0.f;  // NaN stays NaN, -0 -> +0
     if (ACT == ACT_SILU) return v / (1.f + expf(-v));
     if (ACT == ACT_TANH) return tanhf(v);
     return v;
@@ -95,7 +95,7 @@ __device__ __forceinline__ void ps_epilogue(const GemmPsArgs& p, const float* ep
             if (p.Ch) {
                 if (p.plane_neg_slope != 1.0f) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f) + p.plane_neg_slope * fminf(v[e], 0.f);
+                    for (int e = 0; e < 4; ++e) v[e] = lrelu_in(v[e], p.plane_neg_slope);
                 }
                 const h4_t hi = __builtin_convertvector(v, h4_t);
                 *reinterpret_cast<h4_t*>(reinterpret_cast<_Float16*>(p.Ch) + m * p.ldcs + col) = hi;
@@ -111,7 +111,7 @@ __device__ __forceinline__ void ps_epilogue(const GemmPsArgs& p, const float* ep
                 if (p.res && !dead) x += p.res[m * p.ldr + col + e];
                 if (p.C) p.C[m * p.ldc + col + e] = x;
                 if (p.Ch) {
-                    if (p.plane_neg_slope != 1.0f) x = fmaxf(x, 0.f) + p.plane_neg_slope * fminf(x, 0.f);
+                    if (p.plane_neg_slope != 1.0f) x = lrelu_in(x, p.plane_neg_slope);
                     const _Float16 h = (_Float16)x;
                     reinterpret_cast<_Float16*>(p.Ch)[m * p.ldcs + col + e] = h;
                     if (p.Cl) reinterpret_cast<_Float16*>(p.Cl)[m * p.ldcs + col + e] = (_Float16)(x - (float)h);
@@ -699,7 +699,7 @@ __global__ __launch_bounds__(256) void amax_finish_kernel(const float2* __restri
             bidx = oi;
         }
     }
-    if (lane == 0) out_idx[row] = bidx;
+    if (lane == 0) out_idx[row] = argmax_stored_index(bidx);
 }
 }  // namespace
 

@@ -105,7 +105,7 @@ __global__ __launch_bounds__(1024) void argmax_rows_kernel(const float* __restri
             ssum = a + b;
             m = nm;
         }
-        out_idx[row] = bidx;
+        out_idx[row] = argmax_stored_index(bidx);
         if (out_lprob) out_lprob[row] = best - (m + logf(ssum));
     }
 }
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void argmax_plain_rows_kernel(const float* __r
             bidx = oi;
         }
     }
-    if (lane == 0) out_idx[row] = bidx;
+    if (lane == 0) out_idx[row] = argmax_stored_index(bidx);
 }
 
 void launch_argmax_rows(const float* logits, int64_t ld, int rows, int V, const int* d_pos,
@@ -445,7 +445,7 @@ __global__ void lrelu_split_f32_kernel(const float* __restrict__ x, float neg_sl
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         f4_t v = reinterpret_cast<const f4_t*>(x)[i];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f) + neg_slope * fminf(v[e], 0.f);  // the expression of k_gemm2.hip's in_act
+        for (int e = 0; e < 4; ++e) v[e] = lrelu_in(v[e], neg_slope);  // the expression of k_gemm2.hip's in_act
         const h4_t h = __builtin_convertvector(v, h4_t);
         reinterpret_cast<h4_t*>(hi)[i] = h;
         if (lo) reinterpret_cast<h4_t*>(lo)[i] = __builtin_convertvector(v - __builtin_convertvector(h, f4_t), h4_t);

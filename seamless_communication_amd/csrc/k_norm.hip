@@ -12,7 +12,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 __device__ __forceinline__ float act_f(float v, int act) {
-    if (act == ACT_RELU) return v > 0.f ? v : 0.f;
+    if (act == ACT_RELU) return !(v <= 0.f) ? v : 0.f;  // NaN stays NaN, -0 -> +0
     if (act == ACT_SILU) return v / (1.f + expf(-v));
     if (act == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
     return v;

@@ -31,7 +31,7 @@ typedef float float16_t __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float sk_act(float v, int act) {
-    if (act == ACT_RELU) return v > 0.f ? v : 0.f;
+    if (act == ACT_RELU) return !(v <= 0.f) ? v : 0.f;  // NaN stays NaN, -0 -> +0
     if (act == ACT_SILU) return v / (1.f + expf(-v));
     if (act == ACT_TANH) return tanhf(v);
     return v;
@@ -540,7 +540,7 @@ __global__ __launch_bounds__(256) void argmax_finalize_kernel(const float4* __re
             bidx = eos_idx;
         }
         const float lprob = best - (m + logf(ssum));
-        int tok = bidx;
+        int tok = argmax_stored_index(bidx);
         if (finished[b]) {
             tok = pad_idx;
         } else {

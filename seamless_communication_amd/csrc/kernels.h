@@ -6,10 +6,25 @@
 //   * GEMM weights: fp16 [N_out, K] with K contiguous (nn.Linear layout); Conv1d
 //     weights are repacked at load to [C_out, tap * C_in + c];
 //   * every dense product is "A(fp32) x W(fp16)": A is split on the fly into
-//     hi + lo fp16 halves and both halves go through
-//     v_mfma_f32_32x32x16_f16 with fp32 accumulation, which reproduces an
-//     fp32 x fp16 product to ~2^-22 relative (needed for bit-exact greedy ids
-//     against the fp32 CPU reference) at 2x the fp16 MFMA cost.
+//     hi = fp16(x), lo = fp16(x - hi) (round to nearest even, fp16 subnormals
+//     kept) and both halves go through v_mfma_f32_32x32x16_f16 with fp32
+//     accumulation, at 2x the fp16 MFMA cost.  Numeric range (DESIGN.md 4b,
+//     tests/split_model.py is the same statement as code):
+//       - rows of about unit scale and larger: an fp32 x fp16 product to
+//         ~2^-22 relative (needed for bit-exact greedy ids against the fp32
+//         CPU reference).  Below |x| ~ 2^-3 the lo half is an fp16 subnormal
+//         and a row that is small as a whole loses bits: ~6e-7 of the row's
+//         maximum at 2^-4, 1e-5 at 2^-8, 2e-4 at 2^-12, 3e-3 at 2^-16;
+//       - finite for |x| < 65520.  An element beyond it splits into inf and
+//         -inf and its row of the product is NaN in every column;
+//       - NaN stays NaN through every activation (ReLU is !(v <= 0) ? v : 0,
+//         LeakyReLU in front of a split is lrelu_in below) and stays in its
+//         row: the other rows of the launch keep their bits;
+//       - the row arg-max kernels store an index inside the row whatever the
+//         row holds (argmax_stored_index below); a NaN row's log-probability
+//         is NaN.  The beam-search candidate kernels are not covered;
+//       - the fp32 FMA GEMV (launch_gemv) does not split: exact fp32 x fp16
+//         at every scale, no overflow at 65520.
 #pragma once
 #include <atomic>
 
@@ -22,6 +37,19 @@ namespace sc {
 // launchers - launch_gemm_presplit and launch_skinny refuse it
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_TANH = 3, ACT_GELU = 4 };
 enum InAct { IN_NONE = 0, IN_LRELU_01 = 1, IN_LRELU_001 = 2 };
+
+// What a row arg-max stores: its running index starts at 0x7fffffff and no comparison with NaN is true, so a row that is all
+// NaN would hand that value on as a token id (the next step's embedding reads emb + tok * M).  Such a row gets index 0; its
+// log-probability is NaN, which is how the caller sees it.  Every other row, all -inf included, has its index in range already.
+__device__ __forceinline__ int argmax_stored_index(int idx) { return idx == 0x7fffffff ? 0 : idx; }
+
+// LeakyReLU in front of a split (conv input activation, activated output planes).  One expression for every kernel that
+// claims the bits of another; fmaxf / fminf drop a NaN operand, so NaN is handed through by hand - an input that is not a
+// number must not turn into a finite product.  Finite and infinite x keep the bits the bare expression gives.
+__device__ __forceinline__ float lrelu_in(float x, float slope) {
+    const float r = fmaxf(x, 0.f) + slope * fminf(x, 0.f);
+    return x != x ? x : r;
+}
 
 struct GemmArgs {
     const float* A = nullptr;

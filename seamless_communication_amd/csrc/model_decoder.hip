@@ -128,7 +128,7 @@ __global__ __launch_bounds__(256) void energy_level_kernel(const __half* const* 
         for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
         if (lane == 0 && n0 + f < M) {
             const float v = acc + (Bt[l] ? Bt[l][n0 + f] : 0.f);
-            out[(int64_t)l * M + n0 + f] = v > 0.f ? v : 0.f;
+            out[(int64_t)l * M + n0 + f] = !(v <= 0.f) ? v : 0.f;  // NaN stays NaN
         }
     }
 }
