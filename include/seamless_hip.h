@@ -137,6 +137,27 @@ int sc_abi_version(void);
  * folds weight-norm, fuses QKV.  Replaces load_unity_model/load_vocoder_model +
  * model.to(device) (inference/translator.py:113-154). */
 sc_model* sc_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_config* cfg, int device);
+/* sc_load for the models sc_config cannot describe (added within ABI v10, purely additive; sc_config keeps its layout): the
+ * SeamlessExpressive model `seamless_expressivity` (unity arch `expressivity_v2`, T2U arch `expressivity_nar`;
+ * models/unity/builder.py:195-224, t2u_builder.py:235-281).
+ *   ffn_activation      inner activation of the adaptor layer's FFN and of every NLLB FFN (use_gelu: builder.py:509-513, :581-590)
+ *   t2u_ffn_activation  inner activation of the T2U encoder's FFNs (t2u_builder.py:697)
+ *   film_cond_dim       > 0: the NAR T2U is FiLM-conditioned (models/unity/film.py) on a vector of this width.  Loads
+ *                       t2u_model.decoder.layers.N.film.{proj.weight,proj.bias,s_gamma,s_beta}, t2u_model.decoder_frontend.
+ *                       variance_adaptor.duration_predictor.film.* and t2u_model.prosody_proj.{weight,bias}.  Such a model runs
+ *                       the packed T2U pass only (SC_T2U_PACKED=0 is ignored, with a message): model_dim and
+ *                       var_pred_hidden_dim must be multiples of 64 up to 1024, t2u_conv_inner_dim a multiple of 32, the kernel
+ *                       sizes odd - anything else fails here.  Needs the non-autoregressive T2U.
+ * ext == NULL or an all-zero struct: sc_load.  Otherwise ext->abi_version must be SC_ABI_VERSION.  A GELU model is refused under
+ * the SC_DECODER_GEN1 / SC_DECODER_GEN2 debug switches.  sc_fork carries all of it. */
+typedef enum sc_ffn_activation { SC_FFN_RELU = 0, SC_FFN_GELU = 1 } sc_ffn_activation;
+typedef struct sc_load_ext_opts {
+    int32_t abi_version;
+    int32_t ffn_activation;     /* sc_ffn_activation */
+    int32_t t2u_ffn_activation; /* sc_ffn_activation */
+    int32_t film_cond_dim;      /* 0 = no FiLM */
+} sc_load_ext_opts;
+sc_model* sc_load_ext(const sc_tensor_desc* tensors, size_t n_tensors, const sc_config* cfg, const sc_load_ext_opts* ext, int device);
 /* A second handle on the SAME weights with its own HIP stream, scratch pool and result slots, so that
  * several micro-batches can be in flight on one GPU (one host thread per handle).  The parent must
  * outlive its forks; freeing a fork releases only its own scratch.  NAR tables set on the parent
@@ -301,6 +322,15 @@ int sc_decode_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, co
 int sc_t2u_nar(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text, const int32_t* h_text_lens,
                const int32_t* h_text_seqs, float duration_factor, int32_t* h_unit_lens, int32_t* out_s_unit_max,
                int32_t* out_s_char_max);
+/* sc_t2u_nar of a FiLM-conditioned model (sc_load_ext with film_cond_dim > 0; UnitYNART2UModel.forward with film_cond_emb,
+ * models/unity/model.py:379-403): d_cond [n][film_cond_dim] fp32 on the device, one conditioning vector per item (the prosody
+ * encoder's output, inference/generator.py:305-314).  prosody_proj(cond) is added to the T2U encoder output of every position;
+ * the duration predictor and every FFT decoder layer apply FiLM behind their last LayerNorm.  An item's result does not depend on
+ * its companions.  SC_ERR_INVALID: a model without FiLM here, a FiLM model in sc_t2u_nar or sc_s2st - no entry produces
+ * unconditioned units from a conditioned model. */
+int sc_t2u_nar_cond(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text, const int32_t* h_text_lens,
+                    const int32_t* h_text_seqs, float duration_factor, const float* d_cond, int32_t* h_unit_lens,
+                    int32_t* out_s_unit_max, int32_t* out_s_char_max);
 int sc_get_units(sc_model* m, int32_t* h_units /* [n][s_unit_max], pad = unit_pad_idx */);
 int sc_get_durations(sc_model* m, int32_t* h_durations /* [n][s_char_max] */, int32_t* h_char_ids,
                      int32_t* h_char_seq_lens);

@@ -80,7 +80,7 @@ int sc_op_dstep_argmax(const float* d_x, const void* d_w_f16, int32_t M, int32_t
 int sc_op_dstep_attention(const float* d_proj, int32_t S, const float* d_bias, float* d_kcache, float* d_vcache, int32_t cap,
                           int32_t pos, const int32_t* d_lens, int32_t cross, int32_t nb, int32_t heads, float* d_out);
 /* Third-generation decoder-step kernels (k_dstep3.hip): row-group products that apply the preceding LayerNorm and the
- * bias / residual / ReLU themselves.  sc_op_dstep3_gemv, rg = rows per row group (0 = default):
+ * bias / residual / ReLU (act = 1) or exact-erf GELU (act = 4, mode 2 only) themselves.  sc_op_dstep3_gemv, rg = rows per row group (0 = default):
  *   mode 0: y = LayerNorm(x; gamma, beta) . W^T + b                         (K <= 1024)
  *   mode 1: y = res + x . W^T + b                                           (K <= 1024, res [M][N])
  *   mode 2: y = act(LayerNorm(x) . W^T + b) through the split-plane epilogue (K <= 1024)
@@ -321,6 +321,9 @@ float sc_op_pretssel_ups_cutoff(void);
 int sc_op_pretssel_postnet(sc_pretssel* p, const float* d_proj, int32_t n, const int32_t* h_frame_lens, float* d_mel, int32_t t_cap);
 int32_t sc_op_pretssel_postnet_tile(int32_t rows, int32_t dim);
 int32_t sc_op_pretssel_last_launches(sc_pretssel* p);
+/* launch calls of the handle's last sc_t2u_nar / sc_t2u_nar_cond call behind the T2U encoder (decoder front end, duration predictor,
+ * packed FFT decoder, projection; every product / convolution / row-pass call counts once); 0 when the length buckets ran */
+int32_t sc_op_t2u_last_launches(sc_model* m);
 
 /* Kernels of the PRETSSEL waveform generator's SEANet half by themselves (k_seanet.hip; tests/test_pretssel_wave_gpu.py).  Packed
  * items: the rows [time][C] of item i follow those of item i - 1, h_lens [n] on the host.

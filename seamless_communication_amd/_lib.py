@@ -74,6 +74,26 @@ class sc_config(C.Structure):
     ]
 
 
+SC_FFN_RELU, SC_FFN_GELU = 0, 1
+
+
+class sc_load_ext_opts(C.Structure):
+    _fields_ = [("abi_version", _i), ("ffn_activation", _i), ("t2u_ffn_activation", _i), ("film_cond_dim", _i)]
+
+
+def make_load_ext(cfg) -> sc_load_ext_opts:
+    """The sc_load_ext extension of a config: zeroed (= sc_load) for every model but the expressive one."""
+    acts = {"relu": SC_FFN_RELU, "gelu": SC_FFN_GELU}
+    e = sc_load_ext_opts()
+    fa, ta, fd = getattr(cfg, "ffn_activation", "relu"), getattr(cfg, "t2u_ffn_activation", "relu"), int(getattr(cfg, "film_cond_dim", 0))
+    if fa not in acts or ta not in acts:
+        raise ValueError(f"unknown FFN activation ({fa!r}, {ta!r}); supported: relu, gelu")
+    if fa != "relu" or ta != "relu" or fd:
+        e.abi_version = SC_ABI_VERSION
+        e.ffn_activation, e.t2u_ffn_activation, e.film_cond_dim = acts[fa], acts[ta], fd
+    return e
+
+
 class sc_gen_opts(C.Structure):
     _fields_ = [
         ("beam_size", _i), ("soft_max_seq_len_a", C.c_float), ("soft_max_seq_len_b", _i),
@@ -142,6 +162,7 @@ SIGNATURES = {
     "sc_last_error": (C.c_char_p, []),
     "sc_abi_version": (C.c_int, []),
     "sc_load": (_P, [C.POINTER(sc_tensor_desc), C.c_size_t, C.POINTER(sc_config), C.c_int]),
+    "sc_load_ext": (_P, [C.POINTER(sc_tensor_desc), C.c_size_t, C.POINTER(sc_config), C.POINTER(sc_load_ext_opts), C.c_int]),
     "sc_fork": (_P, [_P]),
     "sc_free": (None, [_P]),
     "sc_synchronize": (C.c_int, [_P]),
@@ -167,6 +188,8 @@ SIGNATURES = {
     "sc_engine_expect": (C.c_int, [_P, _i]),
     "sc_engine_get_stats": (C.c_int, [_P, C.POINTER(sc_engine_stats), _i]),
     "sc_t2u_nar": (C.c_int, [_P, _P, _i, _i, _P, _P, C.c_float, _P, _PI, _PI]),
+    "sc_t2u_nar_cond": (C.c_int, [_P, _P, _i, _i, _P, _P, C.c_float, _P, _P, _PI, _PI]),
+    "sc_op_t2u_last_launches": (C.c_int32, [_P]),
     "sc_get_units": (C.c_int, [_P, _P]),
     "sc_get_durations": (C.c_int, [_P, _P, _P, _P]),
     "sc_vocoder_hop": (_i, [_P]),

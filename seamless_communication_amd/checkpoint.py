@@ -32,7 +32,11 @@ FAIRSEQ2_MARKER = "speech_encoder.inner.layers.0.self_attn_layer_norm.weight"
 NLLB100_FAIRSEQ_VOCAB = 256103
 
 # fairseq module prefixes of the S2T + NAR-T2U layout (loader.py:187-192)
-_ENC, _DEC, _T2U_ENC, _T2U_DEC = "encoder", "target_letter_decoder", "synthesizer_encoder", "decoder"
+_PLAIN_PREFIXES = ("encoder", "target_letter_decoder", "synthesizer_encoder", "decoder")
+# the expressive model's layout (loader.py:181-186, "ExpressiveUnitY model (from multi_arch codebase)"); its prosody encoder
+# sits under `global_prosody.`, its prosody projection under `t2s_model.global_proj_enc.`
+_EXPRESSIVE_PREFIXES = ("s2t_model.encoder", "s2t_model.decoder", "t2s_model.encoder", "t2s_model.decoder")
+_ENC, _DEC, _T2U_ENC, _T2U_DEC = _PLAIN_PREFIXES
 _W2V = _ENC + ".w2v_encoder.w2v_model."
 
 # sub-keys of a fairseq transformer layer -> fairseq2 names (shared by text encoder / decoders / T2U encoder)
@@ -104,9 +108,14 @@ def _plain(pairs: Sequence[Tuple[str, str]]) -> List[Tuple[re.Pattern, str]]:
     return [(re.compile("^" + re.escape(old)), new) for old, new in pairs]
 
 
-def unity_v2_key_rules() -> List[Tuple[re.Pattern, str]]:
+def unity_v2_key_rules(expressive: bool = False) -> List[Tuple[re.Pattern, str]]:
     """Ordered rename rules for the base_v2 layout; the FIRST rule that changes a key wins, like
-    fairseq2's convert_fairseq_checkpoint does with the reference's dict (insertion order)."""
+    fairseq2's convert_fairseq_checkpoint does with the reference's dict (insertion order).
+    ``expressive``: the config has a prosody encoder (expressivity_v2) - the module prefixes of that layout, and the rules of
+    loader.py:336-343 (FiLM of the NAR decoder layers, the prosody encoder, the prosody projection; the duration predictor's
+    ``film.`` keys ride on its prefix rule)."""
+    _ENC, _DEC, _T2U_ENC, _T2U_DEC = _EXPRESSIVE_PREFIXES if expressive else _PLAIN_PREFIXES
+    _W2V = _ENC + ".w2v_encoder.w2v_model."
     rules: List[Tuple[re.Pattern, str]] = []
     # speech encoder frontend (fbank models have no feature extractor; the rules are harmless if absent)
     rules += _plain([
@@ -133,6 +142,9 @@ def unity_v2_key_rules() -> List[Tuple[re.Pattern, str]]:
         (_DEC + ".layer_norm.", "text_decoder.layer_norm."),
         (_DEC + ".output_projection.", "final_proj."),
     ])
+    if expressive:
+        rules += _stack(_T2U_DEC + ".", "t2u_model.decoder.", [("film.", "film.")])
+        rules += _plain([("global_prosody.", "prosody_encoder_model."), ("t2s_model.global_proj_enc.", "t2u_model.prosody_proj.")])
     # T2U encoder, NAR decoder frontend, NAR decoder
     rules += _stack(_T2U_ENC + ".", "t2u_model.encoder.", _XFMR_LAYER)
     rules += _plain([
@@ -169,13 +181,15 @@ def char_index_mapping(spm_tokens: Sequence[str]) -> List[int]:
 
 
 def convert_unity_checkpoint(checkpoint: Mapping[str, Any], char_spm_tokens: Optional[Sequence[str]] = None,
-                             use_text_encoder: bool = True) -> Dict[str, torch.Tensor]:
+                             use_text_encoder: bool = True, expressive: bool = False) -> Dict[str, torch.Tensor]:
     """fairseq-keyed UnitY2 checkpoint (``{"model": state_dict}`` or a bare state dict) -> fairseq2-keyed
-    state dict.  A checkpoint that is already fairseq2-keyed passes through (loader.py:32-34)."""
+    state dict.  A checkpoint that is already fairseq2-keyed passes through (loader.py:32-34).
+    ``expressive``: the config has a prosody encoder (the expressive key map, unity_v2_key_rules)."""
     sd_in = checkpoint["model"] if "model" in checkpoint else checkpoint
     if FAIRSEQ2_MARKER in sd_in:
         return dict(sd_in)
-    rules = unity_v2_key_rules()
+    rules = unity_v2_key_rules(expressive)
+    _ENC, _DEC, _T2U_ENC, _T2U_DEC = _EXPRESSIVE_PREFIXES if expressive else _PLAIN_PREFIXES
     # fairseq2's convert_fairseq_checkpoint drops these before renaming
     generic_drop = {"encoder.version", "decoder.version", "encoder.embed_positions._float_tensor",
                     "decoder.embed_positions._float_tensor"}
@@ -258,13 +272,14 @@ def convert_unity2_aligner_checkpoint(checkpoint: Mapping[str, Any], char_spm_to
     return sd
 
 
-def load_converted_checkpoint(path: str, kind: str, char_spm_tokens: Optional[Sequence[str]] = None) -> Dict[str, torch.Tensor]:
+def load_converted_checkpoint(path: str, kind: str, char_spm_tokens: Optional[Sequence[str]] = None,
+                              expressive: bool = False) -> Dict[str, torch.Tensor]:
     ckpt = torch.load(path, map_location="cpu", weights_only=True)
     if kind == "vocoder":
         return convert_vocoder_checkpoint(ckpt)
     if kind == "aligner":
         return convert_unity2_aligner_checkpoint(ckpt, char_spm_tokens=char_spm_tokens)
-    return convert_unity_checkpoint(ckpt, char_spm_tokens=char_spm_tokens)
+    return convert_unity_checkpoint(ckpt, char_spm_tokens=char_spm_tokens, expressive=expressive)
 
 
 def convert_wav2vec2_checkpoint(checkpoint: Mapping[str, Any]) -> Dict[str, torch.Tensor]:

@@ -14,7 +14,7 @@ The S2ST path is speech in -> text -> units -> waveform; the NLLB text encoder
 from __future__ import annotations
 
 from dataclasses import dataclass, field, asdict
-from typing import Any, Dict, List, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 
 @dataclass
@@ -113,6 +113,16 @@ class S2STConfig:
     var_pred_kernel_size: int = 3
 
     vocoder: VocoderConfig = field(default_factory=VocoderConfig)
+
+    # SeamlessExpressive (unity arch `expressivity_v2`, T2U arch `expressivity_nar`; builder.py:195-224, t2u_builder.py:235-281).
+    # ffn_activation: inner activation of the adaptor layer's FFN and the NLLB FFNs (use_gelu; "relu" or "gelu" = torch.nn.GELU(),
+    # the erf form); t2u_ffn_activation: the same of the T2U encoder FFNs; film_cond_dim > 0: FiLM in the duration predictor and
+    # every FFT decoder layer plus `t2u_model.prosody_proj`, all conditioned on the output of `prosody_encoder` (the model's own
+    # ECAPA-TDNN, tensors `prosody_encoder_model.*`).  The defaults describe every other model.
+    ffn_activation: str = "relu"
+    t2u_ffn_activation: str = "relu"
+    film_cond_dim: int = 0
+    prosody_encoder: Optional["EcapaTDNNConfig"] = None
 
     @property
     def head_dim(self) -> int:
@@ -330,6 +340,29 @@ def seamless_m4t_medium() -> S2STConfig:
     return S2STConfig(name="seamlessM4T_medium", enc_variant=1, enc_layers=12, text_enc_layers=12, text_enc_ffn_dim=4096,
                       dec_layers=12, dec_ffn_dim=4096, text_vocab_size=256206, text_max_seq_len=1024, t2u_variant=1,
                       t2u_enc_layers=4, t2u_dec_layers=4, unit_max_seq_len=2048)
+
+
+def seamless_expressivity() -> S2STConfig:
+    """seamless_expressivity, unity arch `expressivity_v2` (models/unity/builder.py:195-224) over the T2U arch `expressivity_nar`
+    (t2u_builder.py:235-281): GELU feed-forward networks, no NLLB text encoder, 4 + 4 T2U layers over 10005 units and 10904
+    characters, sequences up to 10000, FiLM conditioning on the 512-wide output of its own ECAPA-TDNN (arch `base`)."""
+    return S2STConfig(name="seamless_expressivity", text_enc_layers=0, mma_layers=0, text_max_seq_len=10000, t2u_enc_layers=4, t2u_dec_layers=4,
+                      unit_vocab_size=10005, unit_max_seq_len=10000, char_vocab_size=10904, char_max_seq_len=10000,
+                      ffn_activation="gelu", t2u_ffn_activation="gelu", film_cond_dim=512, prosody_encoder=ecapa_tdnn_config("base"))
+
+
+def tiny_expressive_config() -> S2STConfig:
+    """tiny_config() with what the expressive model changes (parity tests): GELU, FiLM on a 64-wide conditioning vector from the
+    `small` ECAPA-TDNN, no text encoder, no monotonic decoder."""
+    c = tiny_config()
+    c.name = "tiny_expressive"
+    c.text_enc_layers = 0
+    c.mma_layers = 0
+    c.ffn_activation = "gelu"
+    c.t2u_ffn_activation = "gelu"
+    c.film_cond_dim = 64
+    c.prosody_encoder = ecapa_tdnn_config("small")
+    return c
 
 
 def tiny_v1_config() -> S2STConfig:

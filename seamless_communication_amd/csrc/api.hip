@@ -76,10 +76,22 @@ extern "C" {
 const char* sc_last_error(void) { return sc::get_error(); }
 int sc_abi_version(void) { return SC_ABI_VERSION; }
 
-sc_model* sc_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_config* cfg, int device) {
+// sc_load / sc_load_ext; ext == null: the ReLU, unconditioned model of sc_load
+static sc_model* load_handle(const sc_tensor_desc* tensors, size_t n_tensors, const sc_config* cfg, const sc_load_ext_opts* ext, int device) {
     sc_model* h = nullptr;
     try {
         SC_CHECK(tensors && cfg, "sc_load: null argument");
+        int ffn_act = ACT_RELU, t2u_ffn_act = ACT_RELU, film_cond_dim = 0;
+        if (ext && (ext->abi_version != 0 || ext->ffn_activation != 0 || ext->t2u_ffn_activation != 0 || ext->film_cond_dim != 0)) {
+            SC_CHECK(ext->abi_version == SC_ABI_VERSION, "sc_load_ext: extension ABI version %d != library %d", ext->abi_version, SC_ABI_VERSION);
+            SC_CHECK((ext->ffn_activation == SC_FFN_RELU || ext->ffn_activation == SC_FFN_GELU) &&
+                         (ext->t2u_ffn_activation == SC_FFN_RELU || ext->t2u_ffn_activation == SC_FFN_GELU),
+                     "sc_load_ext: unknown FFN activation (%d, %d)", ext->ffn_activation, ext->t2u_ffn_activation);
+            SC_CHECK(ext->film_cond_dim >= 0, "sc_load_ext: film_cond_dim=%d", ext->film_cond_dim);
+            ffn_act = ext->ffn_activation == SC_FFN_GELU ? ACT_GELU : ACT_RELU;
+            t2u_ffn_act = ext->t2u_ffn_activation == SC_FFN_GELU ? ACT_GELU : ACT_RELU;
+            film_cond_dim = ext->film_cond_dim;
+        }
         SC_CHECK(cfg->abi_version == SC_ABI_VERSION, "sc_load: config ABI version %d != library %d", cfg->abi_version,
                  SC_ABI_VERSION);
         int ndev = 0;
@@ -90,6 +102,7 @@ sc_model* sc_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_conf
         h = new sc_model();
         h->m.cfg = *cfg;
         h->m.device = device;
+        h->m.ffn_act = ffn_act, h->m.t2u_ffn_act = t2u_ffn_act, h->m.film_cond_dim = film_cond_dim;
         SC_HIP(hipStreamCreateWithFlags(&h->m.stream, hipStreamNonBlocking));
         h->m.pool.set_stream(h->m.stream);
         h->m.hook_pool(h->m.pool);
@@ -101,6 +114,14 @@ sc_model* sc_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_conf
     }
     delete h;
     return nullptr;
+}
+
+sc_model* sc_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_config* cfg, int device) {
+    return load_handle(tensors, n_tensors, cfg, nullptr, device);
+}
+
+sc_model* sc_load_ext(const sc_tensor_desc* tensors, size_t n_tensors, const sc_config* cfg, const sc_load_ext_opts* ext, int device) {
+    return load_handle(tensors, n_tensors, cfg, ext, device);
 }
 
 sc_model* sc_fork(sc_model* parent) {
@@ -373,6 +394,19 @@ int sc_t2u_nar(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text
     SC_API_END
 }
 
+int sc_t2u_nar_cond(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text, const int32_t* h_text_lens,
+                    const int32_t* h_text_seqs, float duration_factor, const float* d_cond, int32_t* h_unit_lens, int32_t* out_s_unit_max,
+                    int32_t* out_s_char_max) {
+    SC_API_BEGIN
+    SC_CHECK(m && d_dec_hidden && h_text_lens && h_text_seqs && d_cond, "sc_t2u_nar_cond: null argument");
+    SC_HIP(hipSetDevice(m->m.device));
+    run_t2u_nar(m->m, d_dec_hidden, n, s_text, h_text_lens, h_text_seqs, duration_factor, h_unit_lens, out_s_unit_max, out_s_char_max,
+                d_cond);
+    SC_API_END
+}
+
+int32_t sc_op_t2u_last_launches(sc_model* m) { return m ? m->m.last_t2u_launches : -1; }
+
 int sc_get_units(sc_model* m, int32_t* h_units) {
     SC_API_BEGIN
     SC_CHECK(m && h_units, "sc_get_units: null argument");
@@ -460,6 +494,8 @@ int sc_s2st(sc_model* m, const float* d_fbank, int32_t n, int32_t t_frames, cons
                  h_unit_lens && d_wav,
              "sc_s2st: null argument");
     Model& M = m->m;
+    SC_CHECK(M.film_cond_dim == 0, "sc_s2st: this T2U is FiLM-conditioned and the fused chain takes no conditioning vectors; run the stages "
+             "(sc_encode_speech, sc_generate_text, sc_t2u_nar_cond)");
     SC_HIP(hipSetDevice(M.device));
     const int D = M.cfg.model_dim;
     // speech encoder
@@ -909,6 +945,9 @@ int sc_op_dstep3_gemv(int32_t mode, const float* d_x, const void* d_w_f16, const
     } else if (mode == 2) {
         __half* oh = scratch.get<__half>((size_t)N * RB);
         __half* ol = scratch.get<__half>((size_t)N * RB);
+        // NaN in every slot of the output planes: a row the kernel leaves alone (behind the live rows) comes back as NaN
+        SC_HIP(hipMemsetAsync(oh, 0xff, (size_t)N * RB * 2, g_op_stream));
+        SC_HIP(hipMemsetAsync(ol, 0xff, (size_t)N * RB * 2, g_op_stream));
         a.epi = EPI3_PLANES, a.act = act, a.Oh = oh, a.Ol = ol, a.ORB = RB;
         launch_gemv3(a, g_op_stream);
         launch_planes_to_rows(oh, ol, RB, d_y, N, M, N, g_op_stream);

@@ -43,6 +43,10 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc3(const void* base, uint32
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
 }
 
+// ACT_GELU (kernels.h): the exact erf form of torch.nn.GELU(); erff(NaN) is NaN, so a NaN stays NaN.  A compile-time variant
+// of the plane epilogues (template parameter GELU): the kernels of the ReLU models are the instantiations they were.
+__device__ __forceinline__ float gelu3(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
+
 __device__ __forceinline__ void split8v(const float* x, half8_t& hi, half8_t& lo) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -59,8 +63,9 @@ __device__ __forceinline__ void split8v(const float* x, half8_t& hi, half8_t& lo
 //   k-steps number (w + blockIdx.x) % WAVES (rotated: the workgroups of one row group read the same activations and
 //   would otherwise hit the same L2 channel at the same time, profiles/r3_micro_percu.txt "in order" vs "rotated").
 // --------------------------------------------------------------------------------------------- //
-template <int NT, int MT, int WAVES, int KSW, int IN, int EPI>
+template <int NT, int MT, int WAVES, int KSW, int IN, int EPI, bool GELU = false>
 __global__ __launch_bounds__(64 * WAVES) void gemv3_kernel(Gemv3Args p) {
+    static_assert(!GELU || EPI == EPI3_PLANES, "gemv3_kernel: the GELU epilogue belongs to the plane output (FFN-in)");
     constexpr int T = 64 * WAVES;
     constexpr int NJ = NT * MT;
     __shared__ float red[WAVES][NJ][32 * 33];
@@ -312,7 +317,8 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3_kernel(Gemv3Args p) {
 #pragma unroll
                 for (int c = 0; c < WAVES; ++c) s += red[c][jj][o];
                 s += bias8[it][e];
-                if (p.act == ACT_RELU) s = !(s <= 0.f) ? s : 0.f;  // NaN stays NaN
+                if constexpr (GELU) s = gelu3(s);
+                else if (p.act == ACT_RELU) s = !(s <= 0.f) ? s : 0.f;  // NaN stays NaN
                 if ((nt0 + jt) * 32 + 8 * g + e >= p.N) s = 0.f;
                 v[e] = s;
             }
@@ -359,8 +365,9 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3_kernel(Gemv3Args p) {
 // same LDS sum over chunks): bit-identical, tests/test_dstep3_gpu.py::test_gemv3_stationary_bit_identical.
 // Only the two shapes the wide step needs: (IN3_LN, EPI3_PLANES) FFN-in and (IN3_PLANES, EPI3_PARTIAL) FFN-out.
 // --------------------------------------------------------------------------------------------- //
-template <int NT, int MT, int WAVES, int KSW, int IN, int EPI>
+template <int NT, int MT, int WAVES, int KSW, int IN, int EPI, bool GELU = false>
 __global__ __launch_bounds__(64 * WAVES) void gemv3s_kernel(Gemv3Args p) {
+    static_assert(!GELU || EPI == EPI3_PLANES, "gemv3s_kernel: the GELU epilogue belongs to the plane output (FFN-in)");
     static_assert((IN == IN3_LN && EPI == EPI3_PLANES && MT == 1) || (IN == IN3_PLANES && EPI == EPI3_PARTIAL),
                   "gemv3s_kernel: FFN-in and FFN-out shapes only");
     constexpr int T = 64 * WAVES;
@@ -608,7 +615,8 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3s_kernel(Gemv3Args p) {
 #pragma unroll
                     for (int c = 0; c < WAVES; ++c) s += red[c][jj][o];
                     s += bias8[it][e];
-                    if (p.act == ACT_RELU) s = !(s <= 0.f) ? s : 0.f;  // NaN stays NaN
+                    if constexpr (GELU) s = gelu3(s);
+                    else if (p.act == ACT_RELU) s = !(s <= 0.f) ? s : 0.f;  // NaN stays NaN
                     if ((nt0 + jt) * 32 + 8 * gq + e >= p.N) s = 0.f;
                     v[e] = s;
                 }
@@ -1159,6 +1167,12 @@ static void gemv3_dispatch(const Gemv3Args& a, dim3 grid, hipStream_t s) {
     }
     if (MT == 1) {
         G3_CASE(IN3_LN, EPI3_ROWS)
+        if constexpr (MT == 1) {  // (no GELU kernel is built for the two-row-tile shapes, which take K-slice products only)
+            if (a.in_mode == IN3_LN && a.epi == EPI3_PLANES && a.act == ACT_GELU) {
+                hipLaunchKernelGGL((gemv3_kernel<NT, 1, WAVES, KSW, IN3_LN, EPI3_PLANES, true>), grid, dim3(64 * WAVES), 0, s, a);
+                return;
+            }
+        }
         G3_CASE(IN3_LN, EPI3_PLANES)
         G3_CASE(IN3_PLANES, EPI3_RESID)
         G3_CASE(IN3_PLANES, EPI3_ROWS)
@@ -1173,6 +1187,8 @@ void launch_gemv3(const Gemv3Args& a0, hipStream_t s) {
     SC_CHECK(gemv3_supported(a.M, a.N, a.K, a.in_mode), "gemv3: M=%d N=%d K=%d mode %d unsupported", a.M, a.N, a.K, a.in_mode);
     SC_CHECK(a.RB >= 32 && a.RB % 32 == 0 && a.RB >= a.M, "gemv3: RB=%d for M=%d", a.RB, a.M);
     SC_CHECK(a.shape == G3_T1 || a.shape == G3_T2K8 || a.shape == G3_T2K4, "gemv3: shape %d", a.shape);
+    SC_CHECK(a.epi != EPI3_PLANES || a.act == ACT_NONE || a.act == ACT_RELU || (a.act == ACT_GELU && a.in_mode == IN3_LN),
+             "gemv3: the plane epilogue has no activation %d for input mode %d (none, ReLU; GELU behind the fused LayerNorm)", a.act, a.in_mode);
     a.KS = a.K / 16;
     a.NT_total = cdiv(a.N, 32);
     a.w_bytes = (uint32_t)(packed_weight_halfs(a.N, a.K) * 2);
@@ -1214,7 +1230,8 @@ void launch_gemv3(const Gemv3Args& a0, hipStream_t s) {
             static const int touch = knob::value("SC_G3_TOUCH", 3);
             a.xcd_swizzle = ffn_out && gy == 1 && grid.z % 8 == 0 && (touch & 2) ? 1 : 0;
             a.touch = (touch & 1) && (ffn_in ? grid.z == 1 : a.xcd_swizzle) ? 1 : 0;
-            if (ffn_in) hipLaunchKernelGGL((gemv3s_kernel<2, 1, 8, 8, IN3_LN, EPI3_PLANES>), grid, dim3(512), 0, s, a);
+            if (ffn_in && a.act == ACT_GELU) hipLaunchKernelGGL((gemv3s_kernel<2, 1, 8, 8, IN3_LN, EPI3_PLANES, true>), grid, dim3(512), 0, s, a);
+            else if (ffn_in) hipLaunchKernelGGL((gemv3s_kernel<2, 1, 8, 8, IN3_LN, EPI3_PLANES>), grid, dim3(512), 0, s, a);
             else hipLaunchKernelGGL((gemv3s_kernel<2, 2, 8, 4, IN3_PLANES, EPI3_PARTIAL>), grid, dim3(512), 0, s, a);
             SC_LAUNCH_CHECK();
             return;

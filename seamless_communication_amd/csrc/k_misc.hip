@@ -281,6 +281,36 @@ void launch_gather_rows(const float* src, int64_t lds_, const int* row_idx, floa
     SC_LAUNCH_CHECK();
 }
 
+// The same gather with a per-item vector added on the way: dst[r] = src[row_idx[r]] + add[r / rows_per_item] (the expressive
+// T2U: encoder_output + prosody_proj(cond), models/unity/model.py:391-392, applied where the encoder rows become characters;
+// the padded text rows never reach a character).  row_idx < 0: exact zeros, as above.
+__global__ __launch_bounds__(256) void gather_rows_add_kernel(const float* __restrict__ src, int64_t lds_, const int* __restrict__ row_idx,
+                                                              const float* __restrict__ add, int64_t ld_add, int rows_per_item,
+                                                              float* __restrict__ dst, int64_t ldd, int C) {
+    const int r = blockIdx.x;
+    const int sidx = row_idx[r];
+    const int cv = C >> 2;
+    float4* d4 = reinterpret_cast<float4*>(dst + (int64_t)r * ldd);
+    if (sidx < 0) {
+        for (int c = threadIdx.x; c < cv; c += 256) d4[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+        const float4* s4 = reinterpret_cast<const float4*>(src + (int64_t)sidx * lds_);
+        const float4* a4 = reinterpret_cast<const float4*>(add + (int64_t)(r / rows_per_item) * ld_add);
+        for (int c = threadIdx.x; c < cv; c += 256) {
+            const float4 v = s4[c], a = a4[c];
+            d4[c] = make_float4(v.x + a.x, v.y + a.y, v.z + a.z, v.w + a.w);
+        }
+    }
+}
+void launch_gather_rows_add(const float* src, int64_t lds_, const int* row_idx, const float* add, int64_t ld_add, int rows_per_item, float* dst,
+                            int64_t ldd, int rows, int C, hipStream_t s) {
+    SC_CHECK(C % 4 == 0 && lds_ % 4 == 0 && ldd % 4 == 0 && ld_add % 4 == 0 && (reinterpret_cast<uintptr_t>(add) & 15) == 0 && rows_per_item > 0,
+             "gather_rows_add: alignment");
+    if (rows <= 0) return;
+    hipLaunchKernelGGL(gather_rows_add_kernel, dim3(rows), dim3(256), 0, s, src, lds_, row_idx, add, ld_add, rows_per_item, dst, ldd, C);
+    SC_LAUNCH_CHECK();
+}
+
 // NARDecoderFrontend.character_level_upsampling tail (nar_decoder_frontend.py:270-283):
 //   pos = alpha * ((x + PE[t]) - x);  pos += E_char[id] * scale;  x += pos
 __global__ __launch_bounds__(256) void char_embed_add_kernel(float* __restrict__ seqs, int64_t ld,

@@ -252,7 +252,7 @@ __global__ __launch_bounds__(256) void postnet_out_kernel(const float* __restric
 
 void launch_pretssel_film(const float* pros, int P, const float* lang, int Lg, const __half* W, const float* bias, const float* mul, const float* add,
                           int n, int N, float* out, hipStream_t s) {
-    SC_CHECK(pros && lang && W && bias && mul && add && out && n > 0 && N > 0 && P >= 0 && Lg >= 0 && P + Lg > 0, "pretssel film: bad argument");
+    SC_CHECK(pros && (lang || Lg == 0) && W && bias && mul && add && out && n > 0 && N > 0 && P >= 0 && Lg >= 0 && P + Lg > 0, "pretssel film: bad argument");
     SC_CHECK(n <= 65535, "pretssel film: %d items exceed the grid", n);
     hipLaunchKernelGGL(film_proj_kernel, dim3(cdiv(N, 4), n), dim3(256), 0, s, pros, P, lang, Lg, W, bias, mul, add, N, out);
     SC_LAUNCH_CHECK();

@@ -33,8 +33,9 @@
 
 namespace sc {
 
-// ACT_GELU: exact (erf) GELU; implemented by launch_gemm (both the fast and the general kernel) and the LayerNorm
-// launchers - launch_gemm_presplit and launch_skinny refuse it
+// ACT_GELU: exact (erf) GELU, 0.5 v (1 + erf(v / sqrt 2)); implemented by launch_gemm (both the fast and the general kernel),
+// the LayerNorm launchers and the plane epilogue of launch_gemv3 behind its fused LayerNorm (the FFN-in of the row-group
+// decoder step) - launch_gemm_presplit, launch_skinny and launch_gemvp refuse or ignore it
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_TANH = 3, ACT_GELU = 4 };
 enum InAct { IN_NONE = 0, IN_LRELU_01 = 1, IN_LRELU_001 = 2 };
 
@@ -404,7 +405,7 @@ struct Gemv3Args {
     __half* Oh = nullptr;
     __half* Ol = nullptr;
     int ORB = 32;
-    int act = ACT_NONE;
+    int act = ACT_NONE;  // EPI3_PLANES: ACT_NONE, ACT_RELU, or ACT_GELU (IN3_LN only: a kernel variant of its own)
     // beam search: *d_rows = live rows (the rows of utterances still searching, packed to the front); row groups that start
     // behind it return at once.  null: all M rows.
     const int* d_rows = nullptr;
@@ -664,6 +665,9 @@ void launch_weight_norm_fold(const __half* v, const __half* g, float* out, int d
                              hipStream_t s);
 void launch_gather_rows(const float* src, int64_t lds, const int* row_idx /*-1 => zero*/, float* dst,
                         int64_t ldd, int rows, int C, hipStream_t s);
+// dst[r] = src[row_idx[r]] + add[r / rows_per_item] (add rows ld_add apart, 16-byte aligned); row_idx < 0: zeros
+void launch_gather_rows_add(const float* src, int64_t lds, const int* row_idx, const float* add, int64_t ld_add, int rows_per_item, float* dst,
+                            int64_t ldd, int rows, int C, hipStream_t s);
 void launch_char_embed_add(float* seqs /*in-place [rows][M]*/, int64_t ld, const int* char_ids,
                            const __half* embed_char, const float* pos_table, int t_per_batch,
                            float alpha, float scale, int rows, int M, hipStream_t s);
@@ -825,7 +829,9 @@ void launch_ecapa_gcmvn(const float* x, const float* mean, const float* stdv, co
 
 // ---- PRETSSEL acoustic model (k_pretssel.hip; reference models/generator/vocoder.py:488-513) --------------------------
 // Every FiLM projection of a call: out[i][j] = mul[j] * (W[j] . [pros_i | lang] + bias[j]) + add[j] for the N stacked output rows
-// of all FiLM layers (W [N][P + Lg] fp16; mul = s_gamma / s_beta, add = 1 / 0 of the gamma / beta halves), fp32 FMA
+// of all FiLM layers (W [N][P + Lg] fp16; mul = s_gamma / s_beta, add = 1 / 0 of the gamma / beta halves), fp32 FMA.  Lg == 0
+// (lang may be null): the conditioning vector alone; rows with mul = 1, add = 0 are plain linear slices (the expressive T2U's
+// prosody_proj rides in the same launch)
 void launch_pretssel_film(const float* pros, int P, const float* lang, int Lg, const __half* W, const float* bias, const float* mul, const float* add,
                           int n, int N, float* out, hipStream_t s);
 // y = mask(FiLM(LayerNorm(x))) per row and group: x [rows][ldx] holds `groups` slices of C channels, g / b [groups][C] (eps 1e-5);

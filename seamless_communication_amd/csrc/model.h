@@ -129,6 +129,7 @@ struct DecStack {
     const std::vector<DecoderLayer>* layers = nullptr;
     const LNorm* final_ln = nullptr;
     int ffn_dim = 0;
+    int ffn_act = ACT_RELU;  // inner activation of the FFNs (ACT_GELU: the expressive model's NLLB decoder)
     const std::vector<PChooseLayer>* pchoose = nullptr;
     // vocabulary of the stack (beam search): size, special symbols, longest sequence of the position table
     int vocab = 0, pad_idx = 0, unk_idx = 1, eos_idx = 3, max_seq_len = 0;
@@ -141,6 +142,7 @@ struct FFTLayer {  // NAR decoder layer (post-LN)
     Linear qkv, attn_out;
     LNorm attn_ln, conv_ln;
     Conv conv1, conv2;
+    int film_off = 0;  // FiLM models: where the layer's gamma' | beta' sit in a row of the conditioning table
 };
 struct ResBlock {
     std::vector<Conv> convs1, convs2;
@@ -152,6 +154,9 @@ struct ResBlock {
 struct ModelData {
     sc_config cfg{};
     int device = 0;
+    // sc_load_ext: inner activation of the adaptor / NLLB FFNs and of the T2U encoder FFNs (ACT_RELU or ACT_GELU), width of the
+    // FiLM conditioning vector of the NAR T2U (0: no FiLM)
+    int ffn_act = ACT_RELU, t2u_ffn_act = ACT_RELU, film_cond_dim = 0;
 
     // raw uploaded tensors by name
     struct Raw {
@@ -217,6 +222,14 @@ struct ModelData {
     const float* dp_proj_b = nullptr;
     std::vector<FFTLayer> t2u_dec;
     LNorm t2u_dec_ln;
+    // FiLM-conditioned NAR T2U (film_cond_dim > 0): every projection that reads the conditioning vector stacked into one matrix
+    // [t2u_film_n][film_cond_dim] - the decoder layers' FiLM (2 M rows each), the duration predictor's (2 H rows), prosody_proj
+    // (M rows) - with s_gamma / s_beta and the + 1 folded into mul / add (launch_pretssel_film)
+    const __half* t2u_film_w = nullptr;
+    const float* t2u_film_b = nullptr;
+    const float* t2u_film_mul = nullptr;
+    const float* t2u_film_add = nullptr;
+    int t2u_film_n = 0, t2u_film_dp_off = 0, t2u_film_pros_off = 0;
     // NAR char tables (host)
     std::vector<int32_t> tok_len;
     std::vector<uint8_t> starts_space, is_punct;
@@ -272,6 +285,7 @@ struct Model : ModelData {
     // results of the last sc_t2u_nar call
     std::vector<int32_t> last_units, last_durations, last_char_ids, last_char_seq_lens;
     int last_n = 0, last_su = 0, last_sc = 0;
+    int last_t2u_launches = 0;  // launch calls of the last sc_t2u_nar* call behind the T2U encoder (decoder front end + FFT decoder)
     int64_t last_padded_unit_rows = 0;  // unit rows the NAR decoder really computed (length buckets), vs last_n * last_su
     int64_t last_vocoder_unit_rows = 0; // unit frames the vocoder really computed in the last sc_vocode* call
     int last_vocoder_packed_groups = 0; // groups of the packed pass in the last sc_vocode* call; 0: padded batch / length buckets
@@ -366,9 +380,10 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
                        const sc_gen_opts& o, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
                        int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, const int32_t* h_forced_tokens,
                        int forced_len, const XattnCapture* xcap = nullptr, const BannedHost* banned = nullptr);
+// d_cond: [n][film_cond_dim] on the device for a FiLM model, null otherwise (a mismatch is an error)
 void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const int32_t* h_text_lens,
                  const int32_t* h_text_seqs, float duration_factor, int32_t* h_unit_lens, int32_t* out_su,
-                 int32_t* out_sc);
+                 int32_t* out_sc, const float* d_cond = nullptr);
 // h_unit_lens == null: the whole padded batch.  Otherwise only the first h_unit_lens[i] * hop samples of row i are
 // guaranteed (computed exactly as in the padded batch), the rest of the row is zero.
 // Conv1d (stride 1, 'same'-style padding) on pre-split planes through the DMA GEMM (k_gemm_ps.hip, implicit-conv mode):

@@ -44,6 +44,7 @@ DecStack unity_stack(const Model& m) {
     w.layers = &m.dec;
     w.final_ln = &m.dec_final_ln;
     w.ffn_dim = m.cfg.dec_ffn_dim;
+    w.ffn_act = m.ffn_act;
     w.pchoose = nullptr;
     w.vocab = m.cfg.text_vocab_size;
     w.pad_idx = m.cfg.pad_idx;
@@ -459,12 +460,14 @@ int choose_family(const Model& m, const DecStack& W, int rows, int caller) {
         const bool gen2 = step2_eligible(m, W, rows) && (forced || W.embed_p != nullptr);
         const bool fused_argmax = !forced && rows <= 64 && M % 64 == 0;
         const bool gen3 = gen2 && step3_eligible(m, W, rows) && (forced || (fused_argmax && W.embed_p && vocab3_supported(rows, W.vocab, M)));
+        if (W.ffn_act == ACT_GELU) return gen3 ? 3 : 1;  // the packed chain's FFN epilogue knows ReLU only
         return gen3 ? 3 : (gen2 ? 2 : 1);
     }
     // beam search: packed-weight step kernels up to 64 live rows, the wide row-group chain above
     const bool packed = step2_eligible(m, W, rows) || step3_wide_eligible(m, W, rows);
     if (!packed) return 1;
     if (rows > 64) return 4;
+    if (W.ffn_act == ACT_GELU) return step3_eligible(m, W, rows) ? 3 : 1;
     return step3_eligible(m, W, rows) ? 3 : 2;
 }
 
@@ -580,7 +583,7 @@ void decoder_step3(Model& m, StepCtx& c, bool project, const DecStack& W) {
         x.slot_rp = c.slot_rp;
         launch_dattn(x, /*cross=*/true, m.stream);
         // feed-forward network: the inner activation stays in split planes
-        if (c.ffn_in_mode == 0 && nb <= 64) {  // K-range partials + reduce / LayerNorm launch, then the packed product on planes
+        if (c.ffn_in_mode == 0 && nb <= 64 && W.ffn_act != ACT_GELU) {  // (the packed product knows no GELU) K-range partials + reduce / LayerNorm launch, then the packed product on planes
             gemv2(m, c, c.attH, c.attL, l.cross_out, 4, &sp);
             reduce_ln3(sp, l.cross_out.b, l.ffn_ln, false);
             GemvPArgs f;
@@ -594,8 +597,10 @@ void decoder_step3(Model& m, StepCtx& c, bool project, const DecStack& W) {
                 Gemv3Args f;
                 f.Wp = l.ffn_in.wp, f.M = nb, f.N = W.ffn_dim, f.K = M;
                 f.in_mode = IN3_LN, f.xg = c.xg, f.gamma = l.ffn_ln.g, f.beta = l.ffn_ln.b, f.RB = c.rb, f.rg = c.rg_ffn;
-                f.shape = c.ffn_in_mode == 1 ? G3_T2K8 : G3_T1;
-                f.epi = EPI3_PLANES, f.bias = l.ffn_in.b, f.act = ACT_RELU, f.Oh = c.wideH, f.Ol = c.wideL, f.ORB = c.rb;
+                // (a GELU stack under SC_D3_FFN_IN=0 lands here too: it takes the default's shape, not the one-tile shape of mode 2)
+                const bool gelu_mode0 = c.ffn_in_mode == 0 && nb <= 64 && W.ffn_act == ACT_GELU;
+                f.shape = (c.ffn_in_mode == 1 || gelu_mode0) ? G3_T2K8 : G3_T1;
+                f.epi = EPI3_PLANES, f.bias = l.ffn_in.b, f.act = W.ffn_act, f.Oh = c.wideH, f.Ol = c.wideL, f.ORB = c.rb;
                 f.d_rows = c.d_rows;
                 launch_gemv3(f, m.stream);
             }
@@ -710,7 +715,7 @@ void decoder_step(Model& m, StepCtx& c, bool project) {
                                     m.stream);
         }
         out_proj_res_ln(m, c, c.att, M, l.cross_out, l.ffn_ln, c.h);
-        linear(m, c.h, M, l.ffn_in, nullptr, 0, c.wide, W.ffn_dim, nb, ACT_RELU, 1.f);
+        linear(m, c.h, M, l.ffn_in, nullptr, 0, c.wide, W.ffn_dim, nb, W.ffn_act, 1.f);
         out_proj_res_ln(m, c, c.wide, W.ffn_dim, l.ffn_out, last ? *W.final_ln : layers[li + 1].self_ln, last ? c.hN : c.h);
     }
     if (c.dec_hidden) {
@@ -1158,7 +1163,7 @@ void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, con
         linear(m, att, M, l.cross_out, x, M, x, M, rows, ACT_NONE, 1.f);
         // feed-forward network
         layernorm(m, x, l.ffn_ln, h, rows);
-        linear(m, h, M, l.ffn_in, nullptr, 0, wide, cfg.dec_ffn_dim, rows, ACT_RELU, 1.f);
+        linear(m, h, M, l.ffn_in, nullptr, 0, wide, cfg.dec_ffn_dim, rows, m.ffn_act, 1.f);
         linear(m, wide, cfg.dec_ffn_dim, l.ffn_out, x, M, x, M, rows, ACT_NONE, 1.f);
     }
     layernorm(m, x, m.dec_final_ln, x, rows);

@@ -341,7 +341,7 @@ void run_encode_speech(Model& m, const float* d_fbank, int n, int t_frames, cons
     attention_self(m, aw, M, ah, n, Sa, d_alens, nullptr);
     linear(m, ah, M, a.attn_out, res, M, y, M, arows, ACT_NONE, 1.f);
     layernorm(m, y, a.ffn_ln, ah, arows);
-    linear(m, ah, M, a.ffn_in, nullptr, 0, aw, c.adaptor_ffn_dim, arows, ACT_RELU, 1.f);
+    linear(m, ah, M, a.ffn_in, nullptr, 0, aw, c.adaptor_ffn_dim, arows, m.ffn_act, 1.f);
     linear(m, aw, c.adaptor_ffn_dim, a.ffn_out, y, M, y, M, arows, ACT_NONE, 1.f);
     launch_layernorm(y, M, m.enc_final_ln.g, m.enc_final_ln.b, d_out, M, arows, M, ACT_NONE, nullptr, 1, m.stream);
     SC_HIP(hipStreamSynchronize(m.stream));

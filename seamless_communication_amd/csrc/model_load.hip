@@ -1,6 +1,7 @@
 // Weight loading: upload, fp16->fp32 for small parameters, QKV fusion, Conv1d
 // repack to GEMM layout, weight-norm folding, ConvTranspose1d polyphase split.
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
 #include <cstdlib>
@@ -376,6 +377,13 @@ void upload_tensors(Model& m, const sc_tensor_desc* t, size_t n) {
 
 void load_model(Model& m, const sc_tensor_desc* t, size_t n) {
     const sc_config& c = m.cfg;
+    if (m.ffn_act == ACT_GELU) {
+        // the one-line ReLU sites of the older step generations behind these debug switches know no GELU
+        SC_CHECK(!knob::is_set("SC_DECODER_GEN1") && !knob::is_set("SC_DECODER_GEN2"),
+                 "sc_load_ext: a GELU model does not run under the SC_DECODER_GEN1 / SC_DECODER_GEN2 debug switches (their decoder steps apply ReLU)");
+    }
+    if (m.film_cond_dim > 0 && knob::value("SC_T2U_PACKED", 1) == 0)
+        fprintf(stderr, "libseamless_hip: SC_T2U_PACKED=0 IGNORED for a FiLM-conditioned T2U: it runs the packed pass only\n");
     SC_CHECK(c.model_dim == c.num_heads * 64, "sc_load: head_dim must be 64 (model_dim=%d, heads=%d)", c.model_dim,
              c.num_heads);
     SC_CHECK(c.model_dim % 32 == 0, "sc_load: model_dim must be a multiple of 32");
@@ -606,8 +614,55 @@ void load_model(Model& m, const sc_tensor_desc* t, size_t n) {
             l.conv_ln = L.ln(p + ".conv1d_layer_norm", M);
         }
         m.t2u_dec_ln = L.ln("t2u_model.decoder.layer_norm", M);
+        if (m.film_cond_dim > 0) {
+            // FiLM-conditioned NAR T2U (models/unity/film.py; fft_decoder_layer.py:185-191, length_regulator.py:205-216,
+            // model.py:391-392): one stacked matrix for everything that reads the conditioning vector.  Such a model runs the
+            // packed FFT pass only, so the shapes that pass cannot take are refused here.
+            const int D = m.film_cond_dim, Ci = c.t2u_conv_inner_dim, Kc = c.t2u_conv_kernel, nl = c.t2u_dec_layers;
+            SC_CHECK(D >= 1 && D <= 8192, "sc_load_ext: film_cond_dim=%d outside 1..8192", D);
+            SC_CHECK(nl >= 1 && M % 32 == 0 && Ci % 32 == 0 && Kc % 2 == 1 && M == c.num_heads * 64 && m.t2u_dec[0].conv1.kpad == M * Kc &&
+                         m.t2u_dec[0].conv2.kpad == Ci * Kc,
+                     "sc_load_ext: a FiLM-conditioned T2U runs the packed FFT pass only, which does not take this decoder (model_dim=%d, "
+                     "conv inner dim %d, kernel %d)", M, Ci, Kc);
+            SC_CHECK(pretssel_ln_supported(M) && pretssel_ln_supported(H),
+                     "sc_load_ext: the fused LayerNorm + FiLM pass takes widths that are multiples of 64 up to 1024 (model_dim=%d, "
+                     "var_pred_hidden_dim=%d)", M, H);
+            m.t2u_film_dp_off = nl * 2 * M;
+            m.t2u_film_pros_off = m.t2u_film_dp_off + 2 * H;
+            m.t2u_film_n = m.t2u_film_pros_off + M;
+            const int N = m.t2u_film_n;
+            __half* fw = static_cast<__half*>(L.dalloc((size_t)N * D * 2));
+            float* fb = static_cast<float*>(L.dalloc((size_t)N * 4));
+            std::vector<float> mul((size_t)N, 1.f), add((size_t)N, 0.f);
+            auto stack = [&](const std::string& p, int off, int rows) {  // a Linear D -> rows into the rows [off, off + rows)
+                const __half* w = L.f16(p + ".weight", {rows, D});
+                const float* b = L.f32(p + ".bias", {rows});
+                SC_HIP(hipMemcpyAsync(fw + (size_t)off * D, w, (size_t)rows * D * 2, hipMemcpyDeviceToDevice, m.stream));
+                SC_HIP(hipMemcpyAsync(fb + off, b, (size_t)rows * 4, hipMemcpyDeviceToDevice, m.stream));
+            };
+            auto film = [&](const std::string& p, int off, int C) {  // gamma' = s_gamma * g + 1, beta' = s_beta * b
+                stack(p + ".proj", off, 2 * C);
+                const float sg = L.scalar(p + ".s_gamma"), sb = L.scalar(p + ".s_beta");
+                for (int j = 0; j < C; ++j) {
+                    mul[(size_t)off + j] = sg, add[(size_t)off + j] = 1.f;
+                    mul[(size_t)off + C + j] = sb, add[(size_t)off + C + j] = 0.f;
+                }
+            };
+            for (int i = 0; i < nl; ++i) {
+                m.t2u_dec[i].film_off = i * 2 * M;
+                film("t2u_model.decoder.layers." + std::to_string(i) + ".film", i * 2 * M, M);
+            }
+            film(d + ".film", m.t2u_film_dp_off, H);
+            stack("t2u_model.prosody_proj", m.t2u_film_pros_off, M);
+            float* fm = static_cast<float*>(L.dalloc((size_t)N * 4));
+            float* fa = static_cast<float*>(L.dalloc((size_t)N * 4));
+            SC_HIP(hipMemcpy(fm, mul.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+            SC_HIP(hipMemcpy(fa, add.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+            m.t2u_film_w = fw, m.t2u_film_b = fb, m.t2u_film_mul = fm, m.t2u_film_add = fa;
+        }
       }
     }
+    SC_CHECK(m.film_cond_dim == 0 || (c.has_t2u && c.t2u_variant == 0), "sc_load_ext: film_cond_dim needs the non-autoregressive T2U");
 
     // ---- vocoder -------------------------------------------------------------------
     if (c.has_vocoder) {

@@ -177,7 +177,7 @@ void run_encode_text(Model& m, const int32_t* h_tokens, int n, int s_text, const
         attention_self(m, wide, M, att, n, s_text, d_lens);
         linear(m, att, M, l.attn_out, x, M, x, M, rows, ACT_NONE, 1.f);
         layernorm(m, x, l.ffn_ln, h, rows);
-        linear(m, h, M, l.ffn_in, nullptr, 0, wide, c.text_enc_ffn_dim, rows, ACT_RELU, 1.f);
+        linear(m, h, M, l.ffn_in, nullptr, 0, wide, c.text_enc_ffn_dim, rows, m.ffn_act, 1.f);
         linear(m, wide, c.text_enc_ffn_dim, l.ffn_out, x, M, x, M, rows, ACT_NONE, 1.f);
     }
     layernorm(m, x, m.text_enc_ln, x, rows);
@@ -198,7 +198,7 @@ void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, con
         attention_self(m, wide, M, att, n, s_text, d_text_lens);
         linear(m, att, M, l.attn_out, x, M, x, M, rows, ACT_NONE, 1.f);
         layernorm(m, x, l.ffn_ln, h, rows);
-        linear(m, h, M, l.ffn_in, nullptr, 0, wide, c.t2u_ffn_dim, rows, ACT_RELU, 1.f);
+        linear(m, h, M, l.ffn_in, nullptr, 0, wide, c.t2u_ffn_dim, rows, m.t2u_ffn_act, 1.f);
         linear(m, wide, c.t2u_ffn_dim, l.ffn_out, x, M, x, M, rows, ACT_NONE, 1.f);
     }
     layernorm(m, x, m.t2u_enc_ln, x, rows);
@@ -206,10 +206,16 @@ void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, con
 
 void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const int32_t* h_text_lens,
                  const int32_t* h_text_seqs, float duration_factor, int32_t* h_unit_lens, int32_t* out_su,
-                 int32_t* out_sc) {
+                 int32_t* out_sc, const float* d_cond) {
     const sc_config& c = m.cfg;
     const int M = c.model_dim;
     SC_CHECK(c.has_t2u, "sc_t2u_nar: the model was loaded without a T2U sub-model");
+    const bool film = m.film_cond_dim > 0;
+    SC_CHECK(!film || d_cond, "sc_t2u_nar: this T2U is FiLM-conditioned (film_cond_dim=%d): the conditioning vectors are required "
+             "(sc_t2u_nar_cond); units without them would not be the model's", m.film_cond_dim);
+    SC_CHECK(film || !d_cond, "sc_t2u_nar_cond: the model was loaded without FiLM conditioning (film_cond_dim = 0)");
+    SC_CHECK(!film || n <= 65535, "sc_t2u_nar_cond: %d items exceed the projection's grid", n);
+    int launches = 0;  // launch calls behind the T2U encoder (Model::last_t2u_launches)
     prof::set_tag("t2u");
     SC_CHECK(n > 0 && s_text >= 2, "sc_t2u_nar: need at least the 2-token prefix (s_text=%d)", s_text);
     const int rows = n * s_text;
@@ -251,7 +257,25 @@ void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const i
 
     // ---- character-level upsampling + duration predictor -----------------------------
     Buf<float> cs(m.pp(), (size_t)crows * M);
-    launch_gather_rows(x, M, d_gidx, cs, M, crows, M, m.stream);
+    // FiLM model: prosody_proj(cond) and every FiLM pair gamma' | beta' of the call from ONE launch (ftab [n][t2u_film_n]); the
+    // prosody term joins the encoder rows where they are gathered to characters
+    Buf<float> ftab;
+    Buf<int> d_citem;
+    std::vector<int32_t> citem;  // the character rows' items; -1 behind an item's characters (exact zeros).  Alive until the sync below
+    if (film) {
+        ftab = Buf<float>(m.pp(), (size_t)n * m.t2u_film_n);
+        launch_pretssel_film(d_cond, m.film_cond_dim, nullptr, 0, m.t2u_film_w, m.t2u_film_b, m.t2u_film_mul, m.t2u_film_add, n, m.t2u_film_n, ftab,
+                             m.stream);
+        ++launches;
+        citem.assign((size_t)crows, -1);
+        for (int b = 0; b < n; ++b)
+            for (int k = 0; k < cseq_lens[b]; ++k) citem[(size_t)b * Sc + k] = b;
+        d_citem = Buf<int>(m.pp(), crows);
+        SC_HIP(hipMemcpyAsync(d_citem.get(), citem.data(), (size_t)crows * 4, hipMemcpyHostToDevice, m.stream));
+        launch_gather_rows_add(x, M, d_gidx, ftab.get() + m.t2u_film_pros_off, m.t2u_film_n, Sc, cs, M, crows, M, m.stream);
+    } else {
+        launch_gather_rows(x, M, d_gidx, cs, M, crows, M, m.stream);
+    }
     launch_char_embed_add(cs, M, d_cid, m.char_embed, m.char_pos, Sc, m.pos_alpha_char, sqrtf((float)M), crows, M, m.stream);
     std::vector<int32_t> dur((size_t)crows);
     {
@@ -260,7 +284,16 @@ void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const i
         conv1d(m, cs, m.dp_conv1, nullptr, a, n, Sc, 1, K / 2, 1, d_clens, IN_NONE, ACT_RELU);
         layernorm(m, a, m.dp_ln1, b, crows);
         conv1d(m, b, m.dp_conv2, nullptr, a, n, Sc, 1, K / 2, 1, d_clens, IN_NONE, ACT_RELU);
-        layernorm(m, a, m.dp_ln2, b, crows);
+        if (film) {  // ln2 -> mask -> FiLM -> mask in one pass (length_regulator.py:205-216)
+            PretsselLnArgs f;
+            f.x = a, f.ldx = H, f.g = m.dp_ln2.g, f.b = m.dp_ln2.b;
+            f.film = ftab, f.film_ld = m.t2u_film_n, f.film_off = m.t2u_film_dp_off, f.row_item = d_citem;
+            f.y = b, f.ldy = H, f.rows = crows, f.C = H;
+            launch_pretssel_film_ln(f, m.stream);
+        } else {
+            layernorm(m, a, m.dp_ln2, b, crows);
+        }
+        launches += 7;  // gather, character embedding, conv, LayerNorm, conv, LayerNorm (+ FiLM), durations
         launch_durations(b, H, m.dp_proj_w, m.dp_proj_b, crows, H, Sc, d_clens, duration_factor, 1, d_dur, m.stream);
         SC_HIP(hipMemcpyAsync(dur.data(), d_dur.get(), (size_t)crows * 4, hipMemcpyDeviceToHost, m.stream));
         SC_HIP(hipStreamSynchronize(m.stream));
@@ -301,6 +334,7 @@ void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const i
                 if (v == c.unit_pad_idx) v = c.unit_pad_idx + 4;
                 m.last_units[(size_t)b * Su + t] = v - 4;
             }
+        m.last_t2u_launches = launches;
         m.last_durations = dur;
         m.last_char_ids = cid_flat;
         m.last_char_seq_lens = cseq_lens;
@@ -321,7 +355,9 @@ void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const i
         const int K = c.t2u_conv_kernel, Ci = c.t2u_conv_inner_dim;
         int64_t R64 = 0;
         for (int b = 0; b < n; ++b) R64 += ulens[b];
-        const bool packed = want_packed && M % 32 == 0 && Ci % 32 == 0 && K % 2 == 1 && !m.t2u_dec.empty() && M == c.num_heads * 64 &&
+        SC_CHECK(!film || (R64 * std::max(M, Ci) * 2 < (1ll << 31) && R64 * (int64_t)c.unit_vocab_size < (1ll << 31)),
+                 "sc_t2u_nar_cond: %lld unit rows exceed what one packed pass addresses (a FiLM-conditioned T2U runs no other)", (long long)R64);
+        const bool packed = (want_packed || film) && M % 32 == 0 && Ci % 32 == 0 && K % 2 == 1 && !m.t2u_dec.empty() && M == c.num_heads * 64 &&
                             m.t2u_dec[0].conv1.kpad == M * K && m.t2u_dec[0].conv2.kpad == Ci * K &&
                             R64 * std::max(M, Ci) * 2 < (1ll << 31) && R64 * (int64_t)c.unit_vocab_size < (1ll << 31);
         if (packed) {
@@ -340,6 +376,14 @@ void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const i
                     }
             }
             Buf<int> d_uidx(m.pp(), R), d_row_t(m.pp(), R), d_row_off(m.pp(), n), d_pos2(m.pp(), (size_t)2 * R), d_ids(m.pp(), R);
+            std::vector<int32_t> uitem;  // FiLM: the item of every packed unit row
+            Buf<int> d_uitem;
+            if (film) {
+                uitem.resize((size_t)R);
+                for (int b = 0; b < n; ++b) std::fill(uitem.begin() + row_off[b], uitem.begin() + row_off[b] + ulens[b], b);
+                d_uitem = Buf<int>(m.pp(), R);
+                SC_HIP(hipMemcpyAsync(d_uitem.get(), uitem.data(), (size_t)R * 4, hipMemcpyHostToDevice, m.stream));
+            }
             SC_HIP(hipMemcpyAsync(d_uidx.get(), uidx.data(), (size_t)R * 4, hipMemcpyHostToDevice, m.stream));
             SC_HIP(hipMemcpyAsync(d_row_t.get(), row_t.data(), (size_t)R * 4, hipMemcpyHostToDevice, m.stream));
             SC_HIP(hipMemcpyAsync(d_row_off.get(), row_off.data(), (size_t)n * 4, hipMemcpyHostToDevice, m.stream));
@@ -401,8 +445,18 @@ void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const i
                 launch_layernorm_both(y, M, l.attn_ln.g, l.attn_ln.b, y, M, yp_h, yp_l, M, R, M, ACT_NONE, nullptr, 1, m.stream);
                 conv1d_presplit(m, yp_h, yp_l, l.conv1, nullptr, nullptr, wp_h, wp_l, 0, 0, K / 2, 1, nullptr, ACT_RELU, R, d_row_pos);
                 conv1d_presplit(m, wp_h, wp_l, l.conv2, y, u, nullptr, nullptr, 0, 0, K / 2, 1, nullptr, ACT_NONE, R, d_row_pos);
-                launch_layernorm_both(u, M, l.conv_ln.g, l.conv_ln.b, u, M, up_h, up_l, M, R, M, ACT_NONE, nullptr, 1, m.stream);
+                if (film) {  // conv1d_layer_norm -> FiLM (-> mask: packed rows are all live) in one pass (fft_decoder_layer.py:185-191)
+                    PretsselLnArgs f;
+                    f.x = u, f.ldx = M, f.g = l.conv_ln.g, f.b = l.conv_ln.b;
+                    f.film = ftab, f.film_ld = m.t2u_film_n, f.film_off = l.film_off, f.row_item = d_uitem;
+                    f.y = u, f.ldy = M, f.yh = up_h, f.yl = up_l, f.ldh = M, f.rows = R, f.C = M;
+                    launch_pretssel_film_ln(f, m.stream);
+                } else {
+                    launch_layernorm_both(u, M, l.conv_ln.g, l.conv_ln.b, u, M, up_h, up_l, M, R, M, ACT_NONE, nullptr, 1, m.stream);
+                }
+                launches += 7;  // QKV, attention, out-projection, LayerNorm, conv, conv, LayerNorm (+ FiLM)
             }
+            launches += 6;  // gather, positions, split, final LayerNorm, projection + arg-max, arg-max finish
             launch_layernorm_split(u, M, m.t2u_dec_ln.g, m.t2u_dec_ln.b, up_h, up_l, M, R, M, ACT_NONE, nullptr, 1, m.stream);
             // project + arg-max (model.py:438-441, generator.py:346).  The arg-max rides in the product's epilogue: the
             // [R][10 082] fp32 logits (1.36 GB per 64-utterance pass, written and read back once) never exist; what leaves the
@@ -432,6 +486,7 @@ void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const i
             return;
         }
     }
+    SC_CHECK(!film, "sc_t2u_nar_cond: the packed pass is unavailable and a FiLM-conditioned T2U runs no other");
     std::vector<std::vector<int32_t>> keep_alive;  // host staging of every group until the final synchronisation
     std::vector<Buf<int>> id_bufs;
     keep_alive.reserve(3 * groups.size());
@@ -494,6 +549,7 @@ void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const i
         for (size_t gi = 0; gi < grp.size(); ++gi)
             for (int t = 0; t < ulens[grp[gi]]; ++t) ids[(size_t)grp[gi] * Su + t] = gids[gi * Lg + t];
     }
+    launches = 0;  // (the length buckets are not counted)
     finish(ids, rows_done);
 }
 

@@ -8,9 +8,11 @@ Mirrors src/seamless_communication/inference/translator.py of the reference:
 argument names, defaults, return types and error behaviour.  ``apply_mintox``
 (:128-132, :263-266, :335-379) runs the reference's MinTox flow: the checker is
 loaded from ``Translator.mintox_card`` and the re-decode bans the words' token
-sequences inside the HIP beam-search step (``toxicity/mintox.py``).  The
-expressive (prosody) inputs are outside the hot path and
-raise ``NotImplementedError``.
+sequences inside the HIP beam-search step (``toxicity/mintox.py``).
+``prosody_encoder_input`` drives the expressive model (card ``seamless_expressivity``):
+its own ECAPA-TDNN runs on the given gcmvn-normalised fbank and its output conditions
+the T2U on the device (inference/generator.py:305-314, :338-344); a model without a
+prosody encoder refuses the input with a ``ValueError``.
 
 Models are named by asset cards like in the reference; a card is a dict with
 the reference schema (``model_arch``, ``checkpoint``, ...).  Offline, the
@@ -33,7 +35,8 @@ from torch import Tensor
 
 from .. import cards as _cards
 from .. import synthetic as _syn
-from ..config import S2STConfig, seamless_m4t_large, seamless_m4t_medium, seamless_m4t_v2_large, tiny_config, tiny_v1_config
+from ..config import (S2STConfig, seamless_expressivity, seamless_m4t_large, seamless_m4t_medium, seamless_m4t_v2_large, tiny_config,
+                      tiny_expressive_config, tiny_v1_config)
 from ..runtime import HipS2STModel
 from ..tokenizer import CharTokenizer, NllbTextTokenizer, UnitTokenizer
 from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, SequenceGeneratorOptions
@@ -71,8 +74,15 @@ class BatchedSpeechOutput:
 
 # unity architectures (models/unity/builder.py:109-192): `base` / `medium` are the v1 models (w2v-BERT with relative
 # positions, autoregressive T2U, duration-predicting vocoder), `base_v2` the UnitY2 model of the north-star path
+# `expressivity_v2` is SeamlessExpressive (builder.py:195-224: GELU, FiLM-conditioned T2U, its own prosody encoder)
 _ARCHS = {"base_v2": seamless_m4t_v2_large, "tiny_v2": tiny_config, "base": seamless_m4t_large, "medium": seamless_m4t_medium,
-          "tiny_v1": tiny_v1_config}
+          "tiny_v1": tiny_v1_config, "expressivity_v2": seamless_expressivity, "tiny_expressivity_v2": tiny_expressive_config}
+
+
+class NoProsodyEncoderError(ValueError, NotImplementedError):
+    """``prosody_encoder_input`` was given to a model that has no prosody encoder.  A ``ValueError`` (the argument does not fit
+    the model); also a ``NotImplementedError``, which is what this path raised for the argument before the expressive model was
+    built, so that callers written against that keep working."""
 
 DEFAULT_CARDS: Dict[str, Dict[str, Any]] = {
     "seamlessM4T_v2_large": {
@@ -91,6 +101,11 @@ DEFAULT_CARDS: Dict[str, Dict[str, Any]] = {
     },
     "seamlessM4T_large": {
         "name": "seamlessM4T_large", "model_arch": "base", "checkpoint": "synthetic://20240901",
+        "num_units": _cards.NUM_UNITS, "unit_langs": _cards.UNIT_LANGS, "langs": _cards.TEXT_LANGS, "default_lang": "eng",
+    },
+    # SeamlessExpressive (cards/seamless_expressivity.yaml): its units feed PretsselGenerator, not the unit vocoder
+    "seamless_expressivity": {
+        "name": "seamless_expressivity", "model_arch": "expressivity_v2", "checkpoint": "synthetic://20240901",
         "num_units": _cards.NUM_UNITS, "unit_langs": _cards.UNIT_LANGS, "langs": _cards.TEXT_LANGS, "default_lang": "eng",
     },
     "vocoder_36langs": {
@@ -145,7 +160,8 @@ def _load_state_dict(card: Dict[str, Any], cfg: S2STConfig, kind: str, with_t2u:
 
         # fairseq-keyed checkpoints (what the model cards publish) are converted like the reference's
         # convert_unity_checkpoint / convert_vocoder_checkpoint do
-        sd = load_converted_checkpoint(uri[len("file://"):], kind, char_spm_tokens=char_pieces)
+        sd = load_converted_checkpoint(uri[len("file://"):], kind, char_spm_tokens=char_pieces,
+                                       expressive=kind == "unity" and getattr(cfg, "prosody_encoder", None) is not None)
         if kind == "unity" and not with_text_encoder:  # translator.py:100-102: skip loading the text encoder
             sd = {k: v for k, v in sd.items() if not k.startswith("text_encoder")}
         return sd
@@ -178,7 +194,7 @@ class Translator:
         # reference: dtype of weights (fp16 on GPU).  Activations are fp32 in HBM.
         self.dtype = dtype
         # translator.py:97-106: the text encoder is skipped for input_modality=SPEECH, the T2U model for output TEXT
-        with_text_encoder = input_modality != Modality.SPEECH
+        with_text_encoder = input_modality != Modality.SPEECH and self.cfg.text_enc_layers > 0  # (expressivity_v2 has none)
         with_t2u = output_modality is None or output_modality == Modality.SPEECH
         self.char_tokenizer = CharTokenizer(self.cfg.char_vocab_size, card.get("char_tokenizer_path"))
         # Char pieces re-order `embed_char` of a fairseq-keyed checkpoint (models/unity/loader.py:158-176).  Without a
@@ -295,8 +311,9 @@ class Translator:
         src_text: Optional[StringLike] = None,
     ) -> Tuple[List[StringLike], Optional[BatchedSpeechOutput]]:
         input_modality, output_modality = self.get_modalities_from_task_str(task_str)
-        if prosody_encoder_input is not None:
-            raise NotImplementedError("expressive (prosody) models are outside the MI355X S2ST hot path")
+        if prosody_encoder_input is not None and getattr(self.model, "prosody_encoder", None) is None:
+            raise NoProsodyEncoderError(f"model '{self.cfg.name}' has no prosody encoder: prosody_encoder_input is for the expressive "
+                                        "model (card 'seamless_expressivity')")
         if self.apply_mintox and not (src_lang is not None or src_text is not None):  # translator.py:263-266
             raise ValueError("`src_lang` must be specified when `apply_mintox` is `True` or you need to specify src_text.")
 
@@ -486,8 +503,13 @@ class Translator:
         ``unit_generation_opts`` and ``unit_generation_ngram_filtering`` are disregarded for the NAR T2U model like in
         the reference (translator.py:173-177, generator.py:338-353).  ``_trace`` (not part of the reference API)
         receives the ids / per-stage data the batch driver and the parity tests read back."""
-        if prosody_encoder_input is not None:
-            raise NotImplementedError("expressive (prosody) models are outside the MI355X S2ST hot path")
+        prosody_encoder = getattr(model, "prosody_encoder", None)
+        if prosody_encoder_input is not None and prosody_encoder is None:
+            raise NoProsodyEncoderError("the model has no prosody encoder: prosody_encoder_input is for the expressive model "
+                                        "(card 'seamless_expressivity')")
+        if prosody_encoder is not None and prosody_encoder_input is None and output_modality == Modality.SPEECH:
+            # inference/generator.py:305-307 asserts; units without the conditioning would not be the model's
+            raise ValueError("the model has a prosody encoder: speech output needs prosody_encoder_input (the gcmvn-normalised fbank)")
         if padding_mask is None:
             src_lens = [int(seqs.shape[1])] * int(seqs.shape[0])
         else:
@@ -569,7 +591,20 @@ class Translator:
             trace["stage_ms"]["t2u"] = (time.perf_counter() - t3) * 1e3
             trace["t2u"] = None
             return texts, torch.from_numpy(units)
-        units, unit_lens, dur, cids, clens = model.t2u_nar(hidden, text_seqs, text_lens, duration_factor)
+        cond_kw: Dict[str, Any] = {}
+        if prosody_encoder is not None:
+            # generator.py:305-314: the model's own ECAPA-TDNN on the caller's gcmvn-normalised fbank; its output stays on the
+            # device and conditions the T2U there (prosody_proj + FiLM)
+            assert prosody_encoder_input is not None
+            p_seqs = prosody_encoder_input["seqs"]
+            p_lens = prosody_encoder_input.get("seq_lens")
+            # get_seqs_and_padding_mask: no mask for a batch that is not ragged (the encoder then masks nothing, as the reference's)
+            if p_lens is not None and not prosody_encoder_input.get("is_ragged", True) and int(torch.as_tensor(p_lens).min()) == p_seqs.shape[1]:
+                p_lens = None
+            if p_seqs.dim() != 3 or p_seqs.shape[0] != hidden.shape[0]:
+                raise ValueError(f"prosody_encoder_input['seqs'] must be (N, T, {prosody_encoder.cfg.input_dim}) with N = {hidden.shape[0]}")
+            cond_kw["cond"] = prosody_encoder.encode(p_seqs.to(model.device, torch.float32), p_lens)
+        units, unit_lens, dur, cids, clens = model.t2u_nar(hidden, text_seqs, text_lens, duration_factor, **cond_kw)
         trace["stage_ms"]["t2u"] = (time.perf_counter() - t3) * 1e3
         trace["t2u"] = {"units": units, "unit_lens": unit_lens, "durations": dur, "char_ids": cids, "char_seq_lens": clens}
         return texts, torch.from_numpy(units.astype(np.int64))

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import threading
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -86,7 +87,11 @@ class HipS2STModel:
         has_t2u = any(k.startswith("t2u_model.") for k in unity_state_dict)
         self.has_text_encoder = any(k.startswith("text_encoder.layers.") for k in unity_state_dict)
         tensors: Dict[str, torch.Tensor] = {}
+        prosody_sd: Dict[str, torch.Tensor] = {}
         for k, v in unity_state_dict.items():
+            if k.startswith("prosody_encoder_model."):
+                prosody_sd[k] = v  # the expressive model's own ECAPA-TDNN: a handle of its own (sc_prosody_encoder_*)
+                continue
             if k in ("final_proj.weight", "t2u_model.final_proj.weight"):
                 continue  # TiedProjection: same storage as the embedding (builder.py:451)
             if k.startswith("text_encoder_frontend."):
@@ -116,10 +121,23 @@ class HipS2STModel:
         ccfg = _lib.make_config(cfg, has_t2u=has_t2u, has_vocoder=vocoder_state_dict is not None,
                                 has_text_encoder=self.has_text_encoder, has_monotonic_decoder=self.has_monotonic_decoder,
                                 has_vocoder_dur_predictor=self.has_vocoder_dur_predictor)
-        self.handle = self.lib.sc_load(descs, len(tensors), C.byref(ccfg), self.device_index)
+        # what sc_config cannot describe (the expressive model: GELU FFNs, FiLM-conditioned T2U) rides in sc_load_ext's extension;
+        # every other config loads through sc_load as before
+        ext = _lib.make_load_ext(cfg)
+        self.film_cond_dim = int(ext.film_cond_dim) if has_t2u else 0
+        ext.film_cond_dim = self.film_cond_dim
+        if ext.abi_version:
+            self.handle = self.lib.sc_load_ext(descs, len(tensors), C.byref(ccfg), C.byref(ext), self.device_index)
+        else:
+            self.handle = self.lib.sc_load(descs, len(tensors), C.byref(ccfg), self.device_index)
         if not self.handle:
             msg = self.lib.sc_last_error()
             raise SeamlessHipError(f"sc_load failed: {msg.decode() if msg else '?'}")
+        self.prosody_encoder: Optional["HipProsodyEncoder"] = None
+        if getattr(cfg, "prosody_encoder", None) is not None and has_t2u:
+            if not prosody_sd:
+                raise SeamlessHipError("the config has a prosody encoder but the state dict holds no 'prosody_encoder_model.*' tensors")
+            self.prosody_encoder = HipProsodyEncoder(cfg.prosody_encoder, prosody_sd, device=self.device_index)
         self.hop = self.lib.sc_vocoder_hop(self.handle) if vocoder_state_dict is not None else 0
         self._has_nar_tables = False
 
@@ -138,8 +156,14 @@ class HipS2STModel:
         child._has_nar_tables = self._has_nar_tables
         child.has_text_encoder = self.has_text_encoder
         child.has_monotonic_decoder = self.has_monotonic_decoder
+        child.film_cond_dim = self.film_cond_dim
+        child.prosody_encoder = self.prosody_encoder  # shared: one small handle per model, its encode() takes a lock
         child._parent = self  # the parent owns the weights and must outlive the fork
         return child
+
+    def t2u_last_launches(self) -> int:
+        """Launch calls of the last ``t2u_nar`` behind the T2U encoder (``sc_op_t2u_last_launches``)."""
+        return int(self.lib.sc_op_t2u_last_launches(self.handle))
 
     def close(self) -> None:
         if getattr(self, "handle", None):
@@ -337,8 +361,10 @@ class HipS2STModel:
         return hidden
 
     def t2u_nar(self, dec_hidden: torch.Tensor, text_seqs: np.ndarray, text_lens: Sequence[int],
-                duration_factor: float = 1.0):
-        """-> units (n, S_u) int32 (pad = unit_pad_idx), unit_lens, durations (n, S_c), char ids, char_seq_lens."""
+                duration_factor: float = 1.0, cond: Optional[torch.Tensor] = None):
+        """-> units (n, S_u) int32 (pad = unit_pad_idx), unit_lens, durations (n, S_c), char ids, char_seq_lens.
+        ``cond`` (n, film_cond_dim) float32 on the device: the conditioning vectors of a FiLM-conditioned model
+        (``sc_t2u_nar_cond``); the library refuses a FiLM model without them and any other model with them."""
         if not self._has_nar_tables:
             raise SeamlessHipError("set_nar_tables() must be called before t2u_nar()")
         assert dec_hidden.is_cuda and dec_hidden.is_contiguous()
@@ -348,9 +374,19 @@ class HipS2STModel:
         tl = _i32(text_lens)
         ulens = np.zeros(n, dtype=np.int32)
         su, sc_ = C.c_int32(0), C.c_int32(0)
+        if cond is not None:
+            if not (cond.is_cuda and cond.dtype == torch.float32 and cond.dim() == 2 and cond.shape[0] == n):
+                raise ValueError(f"cond must be a float32 device tensor of shape ({n}, film_cond_dim), got {tuple(cond.shape)} {cond.dtype}")
+            if self.film_cond_dim and cond.shape[1] != self.film_cond_dim:
+                raise ValueError(f"cond has {cond.shape[1]} columns, the model's film_cond_dim is {self.film_cond_dim}")
+            cond = cond.contiguous()
         self._after_torch()
-        check(self.lib.sc_t2u_nar(self.handle, _ptr(dec_hidden), n, s_text, _ptr(tl), _ptr(ts), float(duration_factor),
-                                  _ptr(ulens), C.byref(su), C.byref(sc_)), "sc_t2u_nar")
+        if cond is not None:
+            check(self.lib.sc_t2u_nar_cond(self.handle, _ptr(dec_hidden), n, s_text, _ptr(tl), _ptr(ts), float(duration_factor), _ptr(cond),
+                                           _ptr(ulens), C.byref(su), C.byref(sc_)), "sc_t2u_nar_cond")
+        else:
+            check(self.lib.sc_t2u_nar(self.handle, _ptr(dec_hidden), n, s_text, _ptr(tl), _ptr(ts), float(duration_factor),
+                                      _ptr(ulens), C.byref(su), C.byref(sc_)), "sc_t2u_nar")
         units = np.zeros((n, su.value), dtype=np.int32)
         check(self.lib.sc_get_units(self.handle, _ptr(units)), "sc_get_units")
         dur = np.zeros((n, sc_.value), dtype=np.int32)
@@ -677,6 +713,7 @@ class HipProsodyEncoder:
         for i in range(c.n_blocks):
             c.channels[i], c.kernel_sizes[i], c.dilations[i] = int(cfg.channels[i]), int(cfg.kernel_sizes[i]), int(cfg.dilations[i])
         self._c = c
+        self._lock = threading.Lock()
         self.handle = self.lib.sc_prosody_encoder_load(descs, len(sd), C.byref(c), self.device_index)
         if not self.handle:
             msg = self.lib.sc_last_error()
@@ -717,7 +754,9 @@ class HipProsodyEncoder:
                 raise ValueError(f"gcmvn statistics must hold {self.cfg.input_dim} values")
         out = torch.empty(n, self.cfg.embed_dim, dtype=torch.float32, device=self.device)
         torch.cuda.current_stream(self.device).synchronize()  # the handle runs on a stream of its own
-        check(self.lib.sc_prosody_encode(self.handle, _ptr(x), n, t, _ptr(hl), _ptr(mean), _ptr(std), _ptr(out)), "sc_prosody_encode")
+        # one stream and one scratch pool per handle: the forks of a model share it from their own host threads, one call at a time
+        with self._lock:
+            check(self.lib.sc_prosody_encode(self.handle, _ptr(x), n, t, _ptr(hl), _ptr(mean), _ptr(std), _ptr(out)), "sc_prosody_encode")
         return out
 
     def last_launches(self) -> int:

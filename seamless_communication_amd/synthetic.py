@@ -388,6 +388,27 @@ def make_unity_state_dict(
         g.conv1d(f"{p}.conv1d.conv2", M, cfg.t2u_conv_inner_dim, cfg.t2u_conv_kernel)
         g.layer_norm(f"{p}.conv1d_layer_norm", M)
     g.layer_norm("t2u_model.decoder.layer_norm", M)
+    D = int(getattr(cfg, "film_cond_dim", 0))
+    if D > 0:
+        # FiLM (models/unity/film.py) of every FFT decoder layer and of the duration predictor, and prosody_proj.  The
+        # conditioning vector is L2-normalised (|c| = 1), so the projections are drawn large enough (entries ~ U(-3, 3) / sqrt(D)
+        # scaled) that gamma and beta move the LayerNorm outputs by tens of percent: conditioning visibly changes durations and
+        # units.  s_gamma and s_beta are not 1, so that a dropped scale shows.
+        def film(prefix: str, width: int, s_gamma: float, s_beta: float) -> None:
+            g.uniform(f"{prefix}.proj.weight", (2 * width, D), 1.5)
+            g.uniform(f"{prefix}.proj.bias", (2 * width,), 0.1)
+            g.sd[f"{prefix}.s_gamma"] = torch.tensor([s_gamma], dtype=dtype)
+            g.sd[f"{prefix}.s_beta"] = torch.tensor([s_beta], dtype=dtype)
+
+        for i in range(cfg.t2u_dec_layers):
+            film(f"t2u_model.decoder.layers.{i}.film", M, 0.625 + 0.125 * (i % 3), 1.375 - 0.125 * (i % 3))
+        film(f"{d}.film", H, 0.75, 1.25)
+        g.uniform("t2u_model.prosody_proj.weight", (M, D), 2.0)
+        g.uniform("t2u_model.prosody_proj.bias", (M,), 0.1)
+    pe = getattr(cfg, "prosody_encoder", None)
+    if pe is not None:  # the model's own ECAPA-TDNN (loader.py:338-341: global_prosody. -> prosody_encoder_model.)
+        for k, v in make_ecapa_state_dict(pe, seed).items():
+            g.sd[k if k.startswith("prosody_encoder_model.") else "prosody_encoder_model." + k] = v
     return g.sd.resolve()
 
 
