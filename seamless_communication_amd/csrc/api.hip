@@ -5,14 +5,14 @@
 #include <mutex>
 #include <set>
 
-#include "../../include/seamless_hip_internal.h"
 #include "engine.h"
-#include "model.h"
+#include "handle.h"
 
 using namespace sc;
 
 struct sc_model {
     Model m;
+    sc_config& cfg = m.cfg;  // where open_handle puts the entry's config
 };
 
 struct sc_engine {
@@ -38,32 +38,9 @@ static void detach_locked(sc_model* m) {
     m->m.engine_announced = 0;
 }
 
-#define SC_API_BEGIN try {
-#define SC_API_END                                                       \
-    }                                                                    \
-    catch (const sc::Error& e) { return e.code; }                        \
-    catch (const std::exception& e) {                                    \
-        sc::set_error("unexpected C++ exception: %s", e.what());         \
-        return SC_ERR_INTERNAL;                                          \
-    }                                                                    \
-    return SC_OK;
-
 static hipStream_t g_op_stream = nullptr;  // ops use the default stream
 
 namespace {
-struct OpScratch {  // hipMalloc'ed scratch of one op call
-    std::vector<void*> ptrs;
-    template <typename T>
-    T* get(size_t n) {
-        void* p = nullptr;
-        SC_HIP(hipMalloc(&p, std::max<size_t>(n * sizeof(T), 256)));
-        ptrs.push_back(p);
-        return static_cast<T*>(p);
-    }
-    ~OpScratch() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-};
 std::vector<int32_t> op_read_ints(const int32_t* d, size_t n) {  // n ints of device memory, synchronously
     std::vector<int32_t> h(n);
     if (n) SC_HIP(hipMemcpy(h.data(), d, n * 4, hipMemcpyDeviceToHost));
@@ -78,42 +55,19 @@ int sc_abi_version(void) { return SC_ABI_VERSION; }
 
 // sc_load / sc_load_ext; ext == null: the ReLU, unconditioned model of sc_load
 static sc_model* load_handle(const sc_tensor_desc* tensors, size_t n_tensors, const sc_config* cfg, const sc_load_ext_opts* ext, int device) {
-    sc_model* h = nullptr;
-    try {
-        SC_CHECK(tensors && cfg, "sc_load: null argument");
-        int ffn_act = ACT_RELU, t2u_ffn_act = ACT_RELU, film_cond_dim = 0;
+    return open_handle<sc_model>("sc_load", tensors, n_tensors, cfg, device, [ext](sc_model& h, const sc_tensor_desc* t, size_t n) {
         if (ext && (ext->abi_version != 0 || ext->ffn_activation != 0 || ext->t2u_ffn_activation != 0 || ext->film_cond_dim != 0)) {
             SC_CHECK(ext->abi_version == SC_ABI_VERSION, "sc_load_ext: extension ABI version %d != library %d", ext->abi_version, SC_ABI_VERSION);
             SC_CHECK((ext->ffn_activation == SC_FFN_RELU || ext->ffn_activation == SC_FFN_GELU) &&
                          (ext->t2u_ffn_activation == SC_FFN_RELU || ext->t2u_ffn_activation == SC_FFN_GELU),
                      "sc_load_ext: unknown FFN activation (%d, %d)", ext->ffn_activation, ext->t2u_ffn_activation);
             SC_CHECK(ext->film_cond_dim >= 0, "sc_load_ext: film_cond_dim=%d", ext->film_cond_dim);
-            ffn_act = ext->ffn_activation == SC_FFN_GELU ? ACT_GELU : ACT_RELU;
-            t2u_ffn_act = ext->t2u_ffn_activation == SC_FFN_GELU ? ACT_GELU : ACT_RELU;
-            film_cond_dim = ext->film_cond_dim;
+            h.m.ffn_act = ext->ffn_activation == SC_FFN_GELU ? ACT_GELU : ACT_RELU;
+            h.m.t2u_ffn_act = ext->t2u_ffn_activation == SC_FFN_GELU ? ACT_GELU : ACT_RELU;
+            h.m.film_cond_dim = ext->film_cond_dim;
         }
-        SC_CHECK(cfg->abi_version == SC_ABI_VERSION, "sc_load: config ABI version %d != library %d", cfg->abi_version,
-                 SC_ABI_VERSION);
-        int ndev = 0;
-        SC_HIP(hipGetDeviceCount(&ndev));
-        SC_CHECK(device >= 0 && device < ndev, "sc_load: device %d not available (%d visible)", device, ndev);
-        knob::report_once();  // every SC_* switch found in the environment, and the ones ignored because they change results
-        SC_HIP(hipSetDevice(device));
-        h = new sc_model();
-        h->m.cfg = *cfg;
-        h->m.device = device;
-        h->m.ffn_act = ffn_act, h->m.t2u_ffn_act = t2u_ffn_act, h->m.film_cond_dim = film_cond_dim;
-        SC_HIP(hipStreamCreateWithFlags(&h->m.stream, hipStreamNonBlocking));
-        h->m.pool.set_stream(h->m.stream);
-        h->m.hook_pool(h->m.pool);
-        load_model(h->m, tensors, n_tensors);
-        return h;
-    } catch (const sc::Error&) {
-    } catch (const std::exception& e) {
-        sc::set_error("sc_load: unexpected C++ exception: %s", e.what());
-    }
-    delete h;
-    return nullptr;
+        load_model(h.m, t, n);
+    });
 }
 
 sc_model* sc_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_config* cfg, int device) {
@@ -131,9 +85,7 @@ sc_model* sc_fork(sc_model* parent) {
         SC_HIP(hipSetDevice(parent->m.device));
         h = new sc_model();
         static_cast<ModelData&>(h->m) = static_cast<const ModelData&>(parent->m);
-        SC_HIP(hipStreamCreateWithFlags(&h->m.stream, hipStreamNonBlocking));
-        h->m.pool.set_stream(h->m.stream);
-        h->m.hook_pool(h->m.pool);
+        open_stream(h->m);
         return h;
     } catch (const sc::Error&) {
     } catch (const std::exception& e) {

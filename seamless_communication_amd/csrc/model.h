@@ -334,12 +334,6 @@ struct SideScope {
 // stage implementations (model_*.hip)
 struct PackedItems;
 void load_model(Model& m, const sc_tensor_desc* t, size_t n);
-void upload_tensors(Model& m, const sc_tensor_desc* t, size_t n);
-struct HifiganNames {
-    std::string pre, post;
-    std::vector<std::string> ups, res;
-};
-void load_hifigan_stack(Model& m, const HifiganNames& nm, int in_dim);
 // The HiFi-GAN stack on packed items from conv_pre's input rows [pk.rows()][in_dim] -> d_out [pk.rows() * hop], conv_post without
 // the tanh.  pk.off / pk.n / pk.d_off set by the caller.  plane_split: bit 0 wide stages, bit 2 narrow stages on two fp16 planes
 // (0: the unit vocoder's default, hi plane only).  Synchronises the handle's stream.

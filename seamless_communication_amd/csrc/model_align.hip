@@ -9,10 +9,9 @@
 #include <algorithm>
 #include <cmath>
 #include <string>
-#include <unordered_map>
 
-#include "../../include/seamless_hip_internal.h"
-#include "model.h"
+#include "handle.h"
+#include "loader.h"
 
 using namespace sc;
 
@@ -28,113 +27,13 @@ struct sc_aligner {
 
 namespace {
 
-struct AlignLoader {
-    sc_aligner& a;
-    struct Raw {
-        void* p;
-        int dtype;
-        std::vector<int64_t> shape;
-        int64_t numel;
-    };
-    std::unordered_map<std::string, Raw> raw;
-    std::vector<void*> uploads;  // the tensors as uploaded: freed by finish() unless the handle uses one as it is
-    std::vector<const void*> used_as_is;
-
-    void* dalloc(size_t bytes) {
-        void* p = nullptr;
-        SC_HIP(hipMalloc(&p, std::max<size_t>(bytes, 256)));
-        a.m.owned.push_back(p);
-        return p;
-    }
-    void upload(const sc_tensor_desc* t, size_t n) {
-        for (size_t i = 0; i < n; ++i) {
-            const sc_tensor_desc& d = t[i];
-            SC_CHECK(d.name && d.data && d.ndim >= 0 && d.ndim <= 4, "sc_aligner_load: bad tensor descriptor #%zu", i);
-            SC_CHECK(d.dtype == SC_F16 || d.dtype == SC_F32, "sc_aligner_load: tensor '%s' has unsupported dtype %d", d.name, d.dtype);
-            Raw r;
-            r.dtype = d.dtype;
-            r.numel = 1;
-            for (int k = 0; k < d.ndim; ++k) {
-                r.shape.push_back(d.shape[k]);
-                r.numel *= d.shape[k];
-            }
-            const size_t bytes = (size_t)r.numel * (d.dtype == SC_F16 ? 2 : 4);
-            SC_HIP(hipMalloc(&r.p, std::max<size_t>(bytes, 256)));
-            uploads.push_back(r.p);
-            SC_HIP(hipMemcpy(r.p, d.data, bytes, d.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-            raw[d.name] = std::move(r);
-        }
-    }
-    const Raw& get(const std::string& k, std::initializer_list<int64_t> shape) const {
-        auto it = raw.find(k);
-        SC_CHECK(it != raw.end(), "sc_aligner_load: tensor '%s' is missing from the weight table", k.c_str());
-        const Raw& r = it->second;
-        bool ok = r.shape.size() == shape.size();
-        size_t i = 0;
-        for (int64_t s : shape) ok = ok && r.shape[i++] == s;
-        SC_CHECK(ok, "sc_aligner_load: tensor '%s' has an unexpected shape", k.c_str());
-        return r;
-    }
-    const __half* f16(const std::string& k, std::initializer_list<int64_t> shape) {
-        const Raw& r = get(k, shape);
-        if (r.dtype == SC_F16) {
-            used_as_is.push_back(r.p);
-            return static_cast<const __half*>(r.p);
-        }
-        __half* d = static_cast<__half*>(dalloc((size_t)r.numel * 2));
-        launch_cvt_f32_f16(static_cast<const float*>(r.p), d, r.numel, a.m.stream);
-        return d;
-    }
-    const float* f32(const std::string& k, std::initializer_list<int64_t> shape) {
-        const Raw& r = get(k, shape);
-        if (r.dtype == SC_F32) {
-            used_as_is.push_back(r.p);
-            return static_cast<const float*>(r.p);
-        }
-        float* d = static_cast<float*>(dalloc((size_t)r.numel * 4));
-        launch_cvt_f16_f32(static_cast<const __half*>(r.p), d, r.numel, a.m.stream);
-        return d;
-    }
-    Conv conv(const std::string& p, int cout, int cin, int k) {
-        Conv c;
-        c.cout = cout;
-        c.cin = cin;
-        c.k = k;
-        c.kpad = (int)align_up((int64_t)cin * k, 32);
-        const Raw& rw = get(p + ".weight", {cout, cin, k});
-        const __half* w = static_cast<const __half*>(rw.p);  // the packer's input only: not kept
-        if (rw.dtype != SC_F16) {
-            __half* h = static_cast<__half*>(dalloc((size_t)rw.numel * 2));
-            launch_cvt_f32_f16(static_cast<const float*>(rw.p), h, rw.numel, a.m.stream);
-            w = h;
-        }
-        __half* d = static_cast<__half*>(dalloc((size_t)cout * c.kpad * 2));
-        launch_pack_conv_weight(w, d, cout, cin, k, c.kpad, a.m.stream);
-        c.w = d;
-        c.b = f32(p + ".bias", {cout});
-        return c;
-    }
-    // After the conversions have run: an upload the handle points into stays (owned by the handle), the others - conv weights
-    // in their checkpoint layout, tensors of the other precision - are freed.  Also the clean-up when loading fails.
-    void finish() {
-        (void)hipStreamSynchronize(a.m.stream);
-        for (void* p : uploads) {
-            if (std::find(used_as_is.begin(), used_as_is.end(), p) != used_as_is.end()) a.m.owned.push_back(p);
-            else (void)hipFree(p);
-        }
-        uploads.clear();
-    }
-    ~AlignLoader() { finish(); }
-};
-
 void load_aligner(sc_aligner& a, const sc_tensor_desc* t, size_t n) {
     const sc_aligner_config& c = a.cfg;
     SC_CHECK(c.model_dim > 0 && c.model_dim % 32 == 0 && c.feat_dim > 0 && c.feat_dim % 32 == 0,
              "sc_aligner_load: model_dim=%d / feat_dim=%d must be positive multiples of 32", c.model_dim, c.feat_dim);
     SC_CHECK(c.text_layers >= 1 && c.feat_layers >= 1 && c.text_layers <= 16 && c.feat_layers <= 16, "sc_aligner_load: bad layer counts");
     SC_CHECK(c.reduction_factor >= 1 && c.char_vocab_size > 0 && c.unit_vocab_size > 0, "sc_aligner_load: bad configuration");
-    AlignLoader L{a};
-    L.upload(t, n);
+    Loader L(a.m, "sc_aligner_load", t, n);
     a.embed_text = L.f16("alignment_frontend.embed_text.weight", {c.char_vocab_size, c.model_dim});
     a.embed_unit = L.f16("alignment_frontend.embed_unit.weight", {c.unit_vocab_size, c.feat_dim});
     // the Conv1d modules sit at positions 1, 4, 7, ... of the nn.Sequential (Permute12, then Conv1d / ReLU / Dropout per layer)
@@ -143,8 +42,7 @@ void load_aligner(sc_aligner& a, const sc_tensor_desc* t, size_t n) {
     for (int i = 0; i < c.feat_layers; ++i)
         a.f_conv.push_back(L.conv("alignment_encoder.f_conv." + std::to_string(1 + 3 * i), c.model_dim, i == 0 ? c.feat_dim : c.model_dim,
                                   i < c.feat_layers - 1 ? 3 : 1));
-    SC_HIP(hipStreamSynchronize(a.m.stream));
-    L.finish();
+    L.release_unused();
 }
 
 void check_lens(const char* who, const int32_t* lens, int n, int cap, const char* what, int* longest) {
@@ -217,67 +115,15 @@ void run_align(sc_aligner& a, const int32_t* h_text_ids, int n, int St, const in
     SC_HIP(hipStreamSynchronize(m.stream));  // the host arrays are the caller's; outputs complete on return
 }
 
-// device copies of two host length tables for the op hooks (default stream, freed on scope exit)
-struct OpLens {
-    int* d_t = nullptr;
-    int* d_f = nullptr;
-    OpLens(const int32_t* h_t, const int32_t* h_f, int n) {
-        SC_HIP(hipMalloc(&d_t, std::max(n * 4, 256)));
-        SC_HIP(hipMalloc(&d_f, std::max(n * 4, 256)));
-        SC_HIP(hipMemcpy(d_t, h_t, (size_t)n * 4, hipMemcpyHostToDevice));
-        SC_HIP(hipMemcpy(d_f, h_f, (size_t)n * 4, hipMemcpyHostToDevice));
-    }
-    ~OpLens() {
-        (void)hipFree(d_t);
-        (void)hipFree(d_f);
-    }
-};
-
 }  // namespace
-
-#define SC_API_BEGIN try {
-#define SC_API_END                                                 \
-    }                                                                    \
-    catch (const sc::Error& e) { return e.code; }                        \
-    catch (const std::exception& e) {                                    \
-        sc::set_error("unexpected C++ exception: %s", e.what());         \
-        return SC_ERR_INTERNAL;                                          \
-    }                                                                    \
-    return SC_OK;
 
 extern "C" {
 
 sc_aligner* sc_aligner_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_aligner_config* cfg, int device) {
-    sc_aligner* h = nullptr;
-    try {
-        SC_CHECK(tensors && cfg, "sc_aligner_load: null argument");
-        SC_CHECK(cfg->abi_version == SC_ABI_VERSION, "sc_aligner_load: config ABI version %d != library %d", cfg->abi_version, SC_ABI_VERSION);
-        int ndev = 0;
-        SC_HIP(hipGetDeviceCount(&ndev));
-        SC_CHECK(device >= 0 && device < ndev, "sc_aligner_load: device %d not available (%d visible)", device, ndev);
-        knob::report_once();
-        SC_HIP(hipSetDevice(device));
-        h = new sc_aligner();
-        h->cfg = *cfg;
-        h->m.device = device;
-        SC_HIP(hipStreamCreateWithFlags(&h->m.stream, hipStreamNonBlocking));
-        h->m.pool.set_stream(h->m.stream);
-        h->m.hook_pool(h->m.pool);
-        load_aligner(*h, tensors, n_tensors);
-        return h;
-    } catch (const sc::Error&) {
-    } catch (const std::exception& e) {
-        sc::set_error("sc_aligner_load: unexpected C++ exception: %s", e.what());
-    }
-    delete h;
-    return nullptr;
+    return open_handle<sc_aligner>("sc_aligner_load", tensors, n_tensors, cfg, device, load_aligner);
 }
 
-void sc_aligner_free(sc_aligner* a) {
-    if (!a) return;
-    (void)hipSetDevice(a->m.device);
-    delete a;
-}
+void sc_aligner_free(sc_aligner* a) { free_handle(a); }
 
 int sc_align(sc_aligner* a, const int32_t* h_text_ids, int32_t n, int32_t s_text, const int32_t* h_text_lens, const int32_t* h_unit_ids,
              int32_t s_unit, const int32_t* h_unit_lens, int32_t* h_durations, float* d_lprob_or_null) {
@@ -296,8 +142,10 @@ int sc_op_align_lprob(const float* d_text, const float* d_feat, int32_t n, int32
     int mt = 0, mf = 0;
     check_lens("sc_op_align_lprob", h_text_lens, n, s_text, "text_lens", &mt);
     check_lens("sc_op_align_lprob", h_feat_lens, n, s_feat, "feat_lens", &mf);
-    OpLens lens(h_text_lens, h_feat_lens, n);
-    launch_align_lprob(d_text, d_feat, n, s_text, s_feat, C, lens.d_t, lens.d_f, temperature, d_lprob, nullptr);
+    OpScratch sc_;
+    const int* d_t = sc_.put(std::vector<int>(h_text_lens, h_text_lens + n));
+    const int* d_f = sc_.put(std::vector<int>(h_feat_lens, h_feat_lens + n));
+    launch_align_lprob(d_text, d_feat, n, s_text, s_feat, C, d_t, d_f, temperature, d_lprob, nullptr);
     SC_HIP(hipStreamSynchronize(nullptr));
     SC_API_END
 }
@@ -312,20 +160,13 @@ int sc_op_mas(const float* d_lprob, int32_t n, int32_t s_text, int32_t s_feat, c
     check_lens("sc_op_mas", h_feat_lens, n, s_feat, "feat_lens", &mf);
     SC_CHECK(mt <= mas_max_text(), "sc_op_mas: %d text positions exceed the limit of %d per item", mt, mas_max_text());
     SC_CHECK(mf <= mas_max_feat(), "sc_op_mas: %d frames exceed the limit of %d per item", mf, mas_max_feat());
-    OpLens lens(h_text_lens, h_feat_lens, n);
-    struct Scratch {
-        void* bits = nullptr;
-        void* dur = nullptr;
-        ~Scratch() {
-            (void)hipFree(bits);
-            (void)hipFree(dur);
-        }
-    } sc_;
-    SC_HIP(hipMalloc(&sc_.bits, std::max<size_t>((size_t)n * mas_bits_words(mt, s_feat) * 8, 256)));
-    SC_HIP(hipMalloc(&sc_.dur, std::max<size_t>((size_t)n * s_text * 4, 256)));
-    launch_mas(d_lprob, n, s_text, s_feat, lens.d_t, lens.d_f, mt, mf, static_cast<unsigned long long*>(sc_.bits), static_cast<int*>(sc_.dur),
-               nullptr);
-    SC_HIP(hipMemcpy(h_durations, sc_.dur, (size_t)n * s_text * 4, hipMemcpyDeviceToHost));
+    OpScratch sc_;
+    const int* d_t = sc_.put(std::vector<int>(h_text_lens, h_text_lens + n));
+    const int* d_f = sc_.put(std::vector<int>(h_feat_lens, h_feat_lens + n));
+    unsigned long long* bits = sc_.get<unsigned long long>((size_t)n * mas_bits_words(mt, s_feat));
+    int* dur = sc_.get<int>((size_t)n * s_text);
+    launch_mas(d_lprob, n, s_text, s_feat, d_t, d_f, mt, mf, bits, dur, nullptr);
+    SC_HIP(hipMemcpy(h_durations, dur, (size_t)n * s_text * 4, hipMemcpyDeviceToHost));
     SC_API_END
 }
 

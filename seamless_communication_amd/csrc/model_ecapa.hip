@@ -12,10 +12,9 @@
 #include <algorithm>
 #include <cmath>
 #include <string>
-#include <unordered_map>
 
-#include "../../include/seamless_hip_internal.h"
-#include "model.h"
+#include "handle.h"
+#include "loader.h"
 
 using namespace sc;
 
@@ -51,95 +50,12 @@ namespace {
 
 constexpr int PE_MAX_FRAMES = 4096;
 
-struct PeLoader {
-    sc_prosody_encoder& a;
-    struct Raw {
-        void* p;
-        int dtype;
-        std::vector<int64_t> shape;
-        int64_t numel;
-    };
-    std::unordered_map<std::string, Raw> raw;
-    std::vector<void*> uploads;
-
-    void* dalloc(size_t bytes) {
-        void* p = nullptr;
-        SC_HIP(hipMalloc(&p, std::max<size_t>(bytes, 256)));
-        a.m.owned.push_back(p);
-        return p;
-    }
-    void upload(const sc_tensor_desc* t, size_t n) {
-        for (size_t i = 0; i < n; ++i) {
-            const sc_tensor_desc& d = t[i];
-            SC_CHECK(d.name && d.data && d.ndim >= 0 && d.ndim <= 4, "sc_prosody_encoder_load: bad tensor descriptor #%zu", i);
-            SC_CHECK(d.dtype == SC_F16 || d.dtype == SC_F32, "sc_prosody_encoder_load: tensor '%s' has unsupported dtype %d", d.name, d.dtype);
-            Raw r;
-            r.dtype = d.dtype;
-            r.numel = 1;
-            for (int k = 0; k < d.ndim; ++k) {
-                r.shape.push_back(d.shape[k]);
-                r.numel *= d.shape[k];
-            }
-            const size_t bytes = (size_t)r.numel * (d.dtype == SC_F16 ? 2 : 4);
-            SC_HIP(hipMalloc(&r.p, std::max<size_t>(bytes, 256)));
-            uploads.push_back(r.p);
-            SC_HIP(hipMemcpy(r.p, d.data, bytes, d.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-            raw[d.name] = std::move(r);
-        }
-    }
-    const Raw& get(const std::string& k, std::initializer_list<int64_t> shape) const {
-        auto it = raw.find(k);
-        SC_CHECK(it != raw.end(), "sc_prosody_encoder_load: tensor '%s' is missing from the weight table", k.c_str());
-        const Raw& r = it->second;
-        bool ok = r.shape.size() == shape.size();
-        size_t i = 0;
-        for (int64_t s : shape) ok = ok && r.shape[i++] == s;
-        SC_CHECK(ok, "sc_prosody_encoder_load: tensor '%s' has an unexpected shape", k.c_str());
-        return r;
-    }
-    // copies the handle owns, in the wanted precision
-    __half* f16(const std::string& k, std::initializer_list<int64_t> shape) {
-        const Raw& r = get(k, shape);
-        __half* dst = static_cast<__half*>(dalloc((size_t)r.numel * 2));
-        if (r.dtype == SC_F16) SC_HIP(hipMemcpyAsync(dst, r.p, (size_t)r.numel * 2, hipMemcpyDeviceToDevice, a.m.stream));
-        else launch_cvt_f32_f16(static_cast<const float*>(r.p), dst, r.numel, a.m.stream);
-        return dst;
-    }
-    float* f32(const std::string& k, std::initializer_list<int64_t> shape) {
-        const Raw& r = get(k, shape);
-        float* dst = static_cast<float*>(dalloc((size_t)r.numel * 4));
-        if (r.dtype == SC_F32) SC_HIP(hipMemcpyAsync(dst, r.p, (size_t)r.numel * 4, hipMemcpyDeviceToDevice, a.m.stream));
-        else launch_cvt_f16_f32(static_cast<const __half*>(r.p), dst, r.numel, a.m.stream);
-        return dst;
-    }
-    Conv conv(const std::string& p, int cout, int cin, int k) {  // packed tap-major rows [cout][kpad]
-        Conv c;
-        c.cout = cout;
-        c.cin = cin;
-        c.k = k;
-        c.kpad = (int)align_up((int64_t)cin * k, 32);
-        const __half* w = f16(p + ".weight", {cout, cin, k});
-        __half* d = static_cast<__half*>(dalloc((size_t)cout * c.kpad * 2));
-        launch_pack_conv_weight(w, d, cout, cin, k, c.kpad, a.m.stream);
-        c.w = d;
-        c.b = f32(p + ".bias", {cout});
-        return c;
-    }
-    Tdnn tdnn(const std::string& p, int cout, int cin, int k) {
-        Tdnn t;
-        t.conv = conv(p + ".conv", cout, cin, k);
-        t.norm.dim = cout;
-        t.norm.g = f32(p + ".norm.weight", {cout});
-        t.norm.b = f32(p + ".norm.bias", {cout});
-        return t;
-    }
-    void finish() {
-        (void)hipStreamSynchronize(a.m.stream);
-        for (void* p : uploads) (void)hipFree(p);
-        uploads.clear();
-    }
-    ~PeLoader() { finish(); }
-};
+Tdnn load_tdnn(Loader& L, const std::string& p, int cout, int cin, int k) {
+    Tdnn t;
+    t.conv = L.conv(p + ".conv", cout, cin, k);
+    t.norm = L.ln(p + ".norm", cout);
+    return t;
+}
 
 void check_config(const sc_prosody_encoder_config& c) {
     SC_CHECK(c.n_blocks >= 3 && c.n_blocks <= SC_PE_MAX_BLOCKS, "sc_prosody_encoder_load: n_blocks=%d outside 3..%d", c.n_blocks, SC_PE_MAX_BLOCKS);
@@ -170,32 +86,28 @@ void load_prosody_encoder(sc_prosody_encoder& a, const sc_tensor_desc* t, size_t
     const sc_prosody_encoder_config& c = a.cfg;
     check_config(c);
     const int C = c.channels[0], nb = c.n_blocks, CM = c.channels[nb - 1], w = C / c.res2net_scale;
-    PeLoader L{a};
-    L.upload(t, n);
-    a.first = L.tdnn("blocks.0", C, c.input_dim, c.kernel_sizes[0]);
+    Loader L(a.m, "sc_prosody_encoder_load", t, n);
+    a.first = load_tdnn(L, "blocks.0", C, c.input_dim, c.kernel_sizes[0]);
     for (int i = 1; i < nb - 1; ++i) {
         const std::string p = "blocks." + std::to_string(i);
         SeRes2Net b;
         b.dil = c.dilations[i];
-        b.tdnn1 = L.tdnn(p + ".tdnn1", C, C, 1);
-        for (int j = 0; j + 1 < c.res2net_scale; ++j) b.chain.push_back(L.tdnn(p + ".res2net_block.blocks." + std::to_string(j), w, w, c.kernel_sizes[i]));
-        b.tdnn2 = L.tdnn(p + ".tdnn2", C, C, 1);
+        b.tdnn1 = load_tdnn(L, p + ".tdnn1", C, C, 1);
+        for (int j = 0; j + 1 < c.res2net_scale; ++j) b.chain.push_back(load_tdnn(L, p + ".res2net_block.blocks." + std::to_string(j), w, w, c.kernel_sizes[i]));
+        b.tdnn2 = load_tdnn(L, p + ".tdnn2", C, C, 1);
         b.se_w1 = L.f16(p + ".se_block.conv1.weight", {c.se_channels, C, 1});
         b.se_b1 = L.f32(p + ".se_block.conv1.bias", {c.se_channels});
         b.se_w2 = L.f16(p + ".se_block.conv2.weight", {C, c.se_channels, 1});
         b.se_b2 = L.f32(p + ".se_block.conv2.bias", {C});
         a.blocks.push_back(std::move(b));
     }
-    a.mfa = L.tdnn("mfa", CM, CM, 1);
-    a.asp_tdnn = L.tdnn("asp.tdnn", c.attention_channels, 3 * CM, 1);
+    a.mfa = load_tdnn(L, "mfa", CM, CM, 1);
+    a.asp_tdnn = load_tdnn(L, "asp.tdnn", c.attention_channels, 3 * CM, 1);
     a.asp_conv = L.conv("asp.conv", CM, c.attention_channels, 1);
-    a.asp_norm.dim = 2 * CM;
-    a.asp_norm.g = L.f32("asp_norm.weight", {2 * CM});
-    a.asp_norm.b = L.f32("asp_norm.bias", {2 * CM});
+    a.asp_norm = L.ln("asp_norm", 2 * CM);
     a.fc_w = L.f16("fc.weight", {c.embed_dim, 2 * CM, 1});
     a.fc_b = L.f32("fc.bias", {c.embed_dim});
-    SC_HIP(hipStreamSynchronize(a.m.stream));
-    L.finish();
+    L.release_unused();
 }
 
 // y[rows][ldc] = x[rows][lda] (*) conv (implicit convolution, 'same' padding) + bias (nullable); K = the first `cin_used` input
@@ -323,72 +235,17 @@ void run_prosody_encode(sc_prosody_encoder& a, const float* d_fbank, int n, int 
     SC_HIP(hipStreamSynchronize(m.stream));  // the caller's stream is not ours: the output is complete on return
 }
 
-struct OpBufs {  // hipMalloc'ed scratch of one op call
-    std::vector<void*> ptrs;
-    template <typename T>
-    T* get(size_t n) {
-        void* p = nullptr;
-        SC_HIP(hipMalloc(&p, std::max<size_t>(n * sizeof(T), 256)));
-        ptrs.push_back(p);
-        return static_cast<T*>(p);
-    }
-    int* lens(const int32_t* h, int n) {
-        if (!h) return nullptr;
-        int* d = get<int>(n);
-        SC_HIP(hipMemcpy(d, h, (size_t)n * 4, hipMemcpyHostToDevice));
-        return d;
-    }
-    ~OpBufs() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-};
+int* op_lens(OpScratch& sc_, const int32_t* h, int n) { return h ? sc_.put(std::vector<int>(h, h + n)) : nullptr; }
 
 }  // namespace
-
-#define SC_API_BEGIN try {
-#define SC_API_END                                                 \
-    }                                                                    \
-    catch (const sc::Error& e) { return e.code; }                        \
-    catch (const std::exception& e) {                                    \
-        sc::set_error("unexpected C++ exception: %s", e.what());         \
-        return SC_ERR_INTERNAL;                                          \
-    }                                                                    \
-    return SC_OK;
 
 extern "C" {
 
 sc_prosody_encoder* sc_prosody_encoder_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_prosody_encoder_config* cfg, int device) {
-    sc_prosody_encoder* h = nullptr;
-    try {
-        SC_CHECK(tensors && cfg, "sc_prosody_encoder_load: null argument");
-        SC_CHECK(cfg->abi_version == SC_ABI_VERSION, "sc_prosody_encoder_load: config ABI version %d != library %d", cfg->abi_version, SC_ABI_VERSION);
-        check_config(*cfg);
-        int ndev = 0;
-        SC_HIP(hipGetDeviceCount(&ndev));
-        SC_CHECK(device >= 0 && device < ndev, "sc_prosody_encoder_load: device %d not available (%d visible)", device, ndev);
-        knob::report_once();
-        SC_HIP(hipSetDevice(device));
-        h = new sc_prosody_encoder();
-        h->cfg = *cfg;
-        h->m.device = device;
-        SC_HIP(hipStreamCreateWithFlags(&h->m.stream, hipStreamNonBlocking));
-        h->m.pool.set_stream(h->m.stream);
-        h->m.hook_pool(h->m.pool);
-        load_prosody_encoder(*h, tensors, n_tensors);
-        return h;
-    } catch (const sc::Error&) {
-    } catch (const std::exception& e) {
-        sc::set_error("sc_prosody_encoder_load: unexpected C++ exception: %s", e.what());
-    }
-    delete h;
-    return nullptr;
+    return open_handle<sc_prosody_encoder>("sc_prosody_encoder_load", tensors, n_tensors, cfg, device, load_prosody_encoder);
 }
 
-void sc_prosody_encoder_free(sc_prosody_encoder* p) {
-    if (!p) return;
-    (void)hipSetDevice(p->m.device);
-    delete p;
-}
+void sc_prosody_encoder_free(sc_prosody_encoder* p) { free_handle(p); }
 
 int sc_prosody_encode(sc_prosody_encoder* p, const float* d_fbank, int32_t n, int32_t t_rows, const int32_t* h_lens_or_null,
                       const float* d_gcmvn_mean_or_null, const float* d_gcmvn_std_or_null, float* d_out) {
@@ -412,7 +269,7 @@ int sc_op_ecapa_chain(const float* d_x, const void* d_w_f16, const float* d_bias
     SC_CHECK(ecapa_chain_supported(chunk, scale, 3, dil), "sc_op_ecapa_chain: unsupported chunk width %d (32 or 64), scale %d (2..8) or dilation %d (1..8)",
              chunk, scale, dil);
     SC_CHECK(nb > 0 && T > 0 && T <= PE_MAX_FRAMES && (int64_t)nb * T * scale * chunk < (1ll << 31), "sc_op_ecapa_chain: bad geometry");
-    OpBufs sc_;
+    OpScratch sc_;
     const int kpad = (int)align_up(3 * chunk, 32);
     __half* packed = sc_.get<__half>((size_t)(scale - 1) * chunk * kpad);
     EcapaChainArgs a;
@@ -452,8 +309,8 @@ int sc_op_ecapa_se_gate(const float* d_x, int32_t nb, int32_t T, const int32_t* 
     SC_API_BEGIN
     SC_CHECK(d_x && d_w1_f16 && d_b1 && d_w2_f16 && d_b2 && d_gate && nb > 0 && T > 0, "sc_op_ecapa_se_gate: null argument");
     check_lens("sc_op_ecapa_se_gate", h_lens, nb, T);
-    OpBufs sc_;
-    launch_ecapa_se_gate(d_x, C, nb, T, sc_.lens(h_lens, nb), C, S, static_cast<const __half*>(d_w1_f16), d_b1, static_cast<const __half*>(d_w2_f16), d_b2,
+    OpScratch sc_;
+    launch_ecapa_se_gate(d_x, C, nb, T, op_lens(sc_, h_lens, nb), C, S, static_cast<const __half*>(d_w1_f16), d_b1, static_cast<const __half*>(d_w2_f16), d_b2,
                          d_gate, nullptr);
     SC_HIP(hipStreamSynchronize(nullptr));
     SC_API_END
@@ -463,8 +320,8 @@ int sc_op_ecapa_pool(const float* d_x, const float* d_logits, int32_t nb, int32_
     SC_API_BEGIN
     SC_CHECK(d_x && nb > 0 && T > 0 && C > 0 && (!d_pooled || d_logits), "sc_op_ecapa_pool: null argument");
     check_lens("sc_op_ecapa_pool", h_lens, nb, T);
-    OpBufs sc_;
-    const int* lens = sc_.lens(h_lens, nb);
+    OpScratch sc_;
+    const int* lens = op_lens(sc_, h_lens, nb);
     if (d_gstats) launch_ecapa_gstats(d_x, nb, T, C, lens, d_gstats, nullptr);
     if (d_pooled) launch_ecapa_pool(d_x, d_logits, nb, T, C, lens, d_pooled, nullptr);
     SC_HIP(hipStreamSynchronize(nullptr));

@@ -6,7 +6,7 @@
 
 #include <cstdlib>
 
-#include "model.h"
+#include "loader.h"
 
 namespace sc {
 
@@ -127,187 +127,204 @@ Model::SideChain& Model::side_chain(int k) {
 }
 
 // --------------------------------------------------------------------------- //
+// Loader (loader.h)
+Loader::Loader(Model& mm, const char* entry, const sc_tensor_desc* t, size_t n) : m(mm), who(entry) { upload_tensors(m, who, t, n); }
+void* Loader::dalloc(size_t bytes) {
+    void* p = nullptr;
+    SC_HIP(hipMalloc(&p, std::max<size_t>(bytes, 256)));
+    m.owned.push_back(p);
+    return p;
+}
+const Model::Raw& Loader::get(const std::string& k) const {
+    auto it = m.raw.find(k);
+    SC_CHECK(it != m.raw.end(), "%s: tensor '%s' is missing from the weight table", who, k.c_str());
+    return it->second;
+}
+const Model::Raw& Loader::get(const std::string& k, Shape shape) const {
+    const Model::Raw& r = get(k);
+    if (r.shape.size() != shape.size() || !std::equal(shape.begin(), shape.end(), r.shape.begin())) {
+        std::string got, want;
+        for (auto s : r.shape) got += std::to_string(s) + ",";
+        for (auto s : shape) want += std::to_string(s) + ",";
+        SC_CHECK(false, "%s: tensor '%s' has shape (%s) but (%s) is expected", who, k.c_str(), got.c_str(), want.c_str());
+    }
+    return r;
+}
+const __half* Loader::f16(const std::string& k, Shape shape, bool keep) {
+    const Model::Raw& r = get(k, shape);
+    if (r.dtype == SC_F16) {
+        if (keep) handed_out.insert(r.p);
+        return static_cast<const __half*>(r.p);
+    }
+    __half* d = static_cast<__half*>(dalloc(r.numel * 2));
+    launch_cvt_f32_f16(static_cast<const float*>(r.p), d, r.numel, m.stream);
+    return d;
+}
+const float* Loader::f32(const std::string& k, Shape shape, bool keep) {
+    const Model::Raw& r = get(k, shape);
+    if (r.dtype == SC_F32) {
+        if (keep) handed_out.insert(r.p);
+        return static_cast<const float*>(r.p);
+    }
+    float* d = static_cast<float*>(dalloc(r.numel * 4));
+    launch_cvt_f16_f32(static_cast<const __half*>(r.p), d, r.numel, m.stream);
+    return d;
+}
+void Loader::f16_into(const std::string& k, Shape shape, __half* dst) {
+    const Model::Raw& r = get(k, shape);
+    if (r.dtype == SC_F16) SC_HIP(hipMemcpyAsync(dst, r.p, (size_t)r.numel * 2, hipMemcpyDeviceToDevice, m.stream));
+    else launch_cvt_f32_f16(static_cast<const float*>(r.p), dst, r.numel, m.stream);
+}
+void Loader::f32_into(const std::string& k, Shape shape, float* dst) {
+    const Model::Raw& r = get(k, shape);
+    if (r.dtype == SC_F32) SC_HIP(hipMemcpyAsync(dst, r.p, (size_t)r.numel * 4, hipMemcpyDeviceToDevice, m.stream));
+    else launch_cvt_f16_f32(static_cast<const __half*>(r.p), dst, r.numel, m.stream);
+}
+float Loader::scalar(const std::string& k) {
+    const Model::Raw& r = get(k);
+    SC_CHECK(r.numel == 1, "%s: '%s' must be a scalar", who, k.c_str());
+    SC_HIP(hipStreamSynchronize(m.stream));
+    if (r.dtype == SC_F32) {
+        float v;
+        SC_HIP(hipMemcpy(&v, r.p, 4, hipMemcpyDeviceToHost));
+        return v;
+    }
+    __half h;
+    SC_HIP(hipMemcpy(&h, r.p, 2, hipMemcpyDeviceToHost));
+    return __half2float(h);
+}
+LNorm Loader::ln(const std::string& p, int dim) {
+    LNorm l;
+    l.g = f32(p + ".weight", {dim});
+    l.b = f32(p + ".bias", {dim});
+    l.dim = dim;
+    return l;
+}
+Linear Loader::lin(const std::string& p, int out, int in, bool bias) {
+    SC_CHECK(in % 32 == 0, "%s: '%s' input dim %d must be a multiple of 32", who, p.c_str(), in);
+    Linear l;
+    l.w = f16(p + ".weight", {out, in});
+    l.ldw = in;
+    l.kpad = in;
+    l.out = out;
+    l.in = in;
+    l.b = bias ? f32(p + ".bias", {out}) : nullptr;
+    return l;
+}
+Linear Loader::lin_pw(const std::string& p, int out, int in) {
+    SC_CHECK(in % 32 == 0, "%s: '%s' input dim %d must be a multiple of 32", who, p.c_str(), in);
+    Linear l;
+    l.w = f16(p + ".weight", {out, in, 1});
+    l.ldw = in;
+    l.kpad = in;
+    l.out = out;
+    l.in = in;
+    return l;
+}
+// the row-major weight stays for the many-row products of the same layer (encoder K/V projection, teacher-forced pass)
+const __half* Loader::packed(const __half* w, int64_t ldw, int out, int in) {
+    if (in % 64 != 0 || packed_weight_halfs(out, in) * 2 >= (1ll << 32)) return nullptr;
+    __half* d = static_cast<__half*>(dalloc((size_t)packed_weight_halfs(out, in) * 2));
+    launch_pack_weight(w, ldw, out, in, d, m.stream);
+    return d;
+}
+void Loader::pack_decoder_layer(DecoderLayer& l) {
+    for (Linear* x : {&l.qkv, &l.self_out, &l.cross_q, &l.cross_out, &l.ffn_in, &l.ffn_out}) x->wp = packed(x->w, x->ldw, x->out, x->in);
+}
+Linear Loader::fuse(const std::vector<std::string>& ps, int out_each, int in) {
+    SC_CHECK(in % 32 == 0, "%s: fused projection input dim %d must be a multiple of 32", who, in);
+    const int n = (int)ps.size();
+    __half* w = static_cast<__half*>(dalloc((size_t)n * out_each * in * 2));
+    float* b = static_cast<float*>(dalloc((size_t)n * out_each * 4));
+    for (int i = 0; i < n; ++i) {
+        f16_into(ps[i] + ".weight", {out_each, in}, w + (size_t)i * out_each * in);
+        f32_into(ps[i] + ".bias", {out_each}, b + (size_t)i * out_each);
+    }
+    Linear l;
+    l.w = w;
+    l.ldw = in;
+    l.kpad = in;
+    l.b = b;
+    l.out = n * out_each;
+    l.in = in;
+    return l;
+}
+void Loader::pack_conv(const std::string& name, int cout, int cin, int k, int cin_pad, int kpad, __half* dst) {
+    const __half* w = f16(name, {cout, cin, k}, /*keep=*/false);
+    Buf<__half> padded;
+    if (cin_pad != cin) {
+        padded = Buf<__half>(m.pp(), (size_t)cout * cin_pad * k);
+        SC_HIP(hipMemsetAsync(padded.get(), 0, (size_t)cout * cin_pad * k * 2, m.stream));
+        SC_HIP(hipMemcpy2DAsync(padded.get(), (size_t)cin_pad * k * 2, w, (size_t)cin * k * 2, (size_t)cin * k * 2, cout, hipMemcpyDeviceToDevice, m.stream));
+        w = padded;
+    }
+    launch_pack_conv_weight(w, dst, cout, cin_pad, k, kpad, m.stream);
+}
+Conv Loader::conv(const std::string& p, int cout, int cin, int k, bool bias, int cin_pad) {
+    Conv c;
+    c.cout = cout;
+    c.cin = cin_pad ? cin_pad : cin;
+    c.k = k;
+    c.kpad = (int)align_up((int64_t)c.cin * k, 32);
+    __half* d = static_cast<__half*>(dalloc((size_t)cout * c.kpad * 2));
+    pack_conv(p + ".weight", cout, cin, k, c.cin, c.kpad, d);
+    c.w = d;
+    c.b = bias ? f32(p + ".bias", {cout}) : nullptr;
+    return c;
+}
+// weight_g (cout,1,1), weight_v (cout,cin,k)
+Conv Loader::conv_wn(const std::string& p, int cout, int cin, int k) {
+    Conv c;
+    c.cout = cout;
+    c.cin = cin;
+    c.k = k;
+    c.kpad = (int)align_up((int64_t)cin * k, 32);
+    const __half* v = f16(p + ".weight_v", {cout, cin, k}, /*keep=*/false);
+    const __half* g = f16(p + ".weight_g", {cout, 1, 1}, /*keep=*/false);
+    Buf<float> folded(m.pp(), (size_t)cout * cin * k);
+    Buf<__half> folded16(m.pp(), (size_t)cout * cin * k);
+    launch_weight_norm_fold(v, g, folded, cout, cin * k, m.stream);
+    launch_cvt_f32_f16(folded, folded16, (int64_t)cout * cin * k, m.stream);
+    __half* d = static_cast<__half*>(dalloc((size_t)cout * c.kpad * 2));
+    launch_pack_conv_weight(folded16, d, cout, cin, k, c.kpad, m.stream);
+    c.w = d;
+    c.b = f32(p + ".bias", {cout});
+    return c;
+}
+// weight_g (cin,1,1), weight_v (cin,cout,k)
+ConvT Loader::convT_wn(const std::string& p, int cin, int cout, int k, int stride) {
+    ConvT c;
+    c.cin = cin;
+    c.cout = cout;
+    c.k = k;
+    c.stride = stride;
+    // k - stride odd (the PRETSSEL generator's k = 2u at odd u): padding rounded up with output_padding 1, still stride * L out
+    c.pad = (k - stride + 1) / 2;
+    c.taps = cdiv(k, stride);
+    c.kpad = (int)align_up((int64_t)cin * c.taps, 32);
+    SC_CHECK(k >= stride && k - 2 * c.pad + (k - stride) % 2 == stride, "%s: '%s' ConvTranspose1d(k=%d,stride=%d) does not upsample by its stride", who,
+             p.c_str(), k, stride);
+    const __half* v = f16(p + ".weight_v", {cin, cout, k}, /*keep=*/false);
+    const __half* g = f16(p + ".weight_g", {cin, 1, 1}, /*keep=*/false);
+    Buf<float> folded(m.pp(), (size_t)cin * cout * k);
+    launch_weight_norm_fold(v, g, folded, cin, cout * k, m.stream);
+    __half* d = static_cast<__half*>(dalloc((size_t)stride * cout * c.kpad * 2));
+    launch_pack_convT_weight(folded, d, cin, cout, k, stride, c.kpad, m.stream);
+    c.w = d;
+    c.b = f32(p + ".bias", {cout});
+    return c;
+}
+void Loader::release_unused() {
+    SC_HIP(hipStreamSynchronize(m.stream));  // the conversions and repacking launches read the uploads
+    std::unordered_set<void*> unused;
+    for (const auto& kv : m.raw)
+        if (!handed_out.count(kv.second.p)) unused.insert(kv.second.p);
+    m.owned.erase(std::remove_if(m.owned.begin(), m.owned.end(), [&](void* p) { return unused.count(p) != 0; }), m.owned.end());
+    for (void* p : unused) (void)hipFree(p);
+    m.raw.clear();
+}
+
 namespace {
-
-struct Loader {
-    Model& m;
-    explicit Loader(Model& mm) : m(mm) {}
-
-    void* dalloc(size_t bytes) {
-        void* p = nullptr;
-        SC_HIP(hipMalloc(&p, std::max<size_t>(bytes, 256)));
-        m.owned.push_back(p);
-        return p;
-    }
-    bool has(const std::string& k) const { return m.raw.count(k) != 0; }
-    const Model::Raw& get(const std::string& k) const {
-        auto it = m.raw.find(k);
-        SC_CHECK(it != m.raw.end(), "sc_load: tensor '%s' is missing from the weight table", k.c_str());
-        return it->second;
-    }
-    const Model::Raw& get(const std::string& k, std::initializer_list<int64_t> shape) const {
-        const Model::Raw& r = get(k);
-        bool ok = r.shape.size() == shape.size();
-        if (ok) {
-            size_t i = 0;
-            for (int64_t s : shape) ok = ok && (r.shape[i++] == s);
-        }
-        if (!ok) {
-            std::string got, want;
-            for (auto s : r.shape) got += std::to_string(s) + ",";
-            for (auto s : shape) want += std::to_string(s) + ",";
-            SC_CHECK(false, "sc_load: tensor '%s' has shape (%s) but (%s) is expected", k.c_str(), got.c_str(),
-                     want.c_str());
-        }
-        return r;
-    }
-    const __half* f16(const std::string& k, std::initializer_list<int64_t> shape) {
-        const Model::Raw& r = get(k, shape);
-        if (r.dtype == SC_F16) return static_cast<const __half*>(r.p);
-        __half* d = static_cast<__half*>(dalloc(r.numel * 2));
-        launch_cvt_f32_f16(static_cast<const float*>(r.p), d, r.numel, m.stream);
-        return d;
-    }
-    const float* f32(const std::string& k, std::initializer_list<int64_t> shape) {
-        const Model::Raw& r = get(k, shape);
-        if (r.dtype == SC_F32) return static_cast<const float*>(r.p);
-        float* d = static_cast<float*>(dalloc(r.numel * 4));
-        launch_cvt_f16_f32(static_cast<const __half*>(r.p), d, r.numel, m.stream);
-        return d;
-    }
-    float scalar(const std::string& k) {
-        const Model::Raw& r = get(k);
-        SC_CHECK(r.numel == 1, "sc_load: '%s' must be a scalar", k.c_str());
-        SC_HIP(hipStreamSynchronize(m.stream));
-        if (r.dtype == SC_F32) {
-            float v;
-            SC_HIP(hipMemcpy(&v, r.p, 4, hipMemcpyDeviceToHost));
-            return v;
-        }
-        __half h;
-        SC_HIP(hipMemcpy(&h, r.p, 2, hipMemcpyDeviceToHost));
-        return __half2float(h);
-    }
-    LNorm ln(const std::string& p, int dim) {
-        LNorm l;
-        l.g = f32(p + ".weight", {dim});
-        l.b = f32(p + ".bias", {dim});
-        l.dim = dim;
-        return l;
-    }
-    Linear lin(const std::string& p, int out, int in, bool bias = true) {
-        SC_CHECK(in % 32 == 0, "sc_load: '%s' input dim %d must be a multiple of 32", p.c_str(), in);
-        Linear l;
-        l.w = f16(p + ".weight", {out, in});
-        l.ldw = in;
-        l.kpad = in;
-        l.out = out;
-        l.in = in;
-        l.b = bias ? f32(p + ".bias", {out}) : nullptr;
-        return l;
-    }
-    // pointwise Conv1d stored as (out, in, 1)
-    Linear lin_pw(const std::string& p, int out, int in) {
-        SC_CHECK(in % 32 == 0, "sc_load: '%s' input dim %d must be a multiple of 32", p.c_str(), in);
-        Linear l;
-        l.w = f16(p + ".weight", {out, in, 1});
-        l.ldw = in;
-        l.kpad = in;
-        l.out = out;
-        l.in = in;
-        return l;
-    }
-    // second copy of a decoder-step weight in MFMA fragment order (k_dstep.hip); the row-major one stays for the
-    // many-row products of the same layer (encoder K/V projection, teacher-forced pass)
-    const __half* packed(const __half* w, int64_t ldw, int out, int in) {
-        if (in % 64 != 0 || packed_weight_halfs(out, in) * 2 >= (1ll << 32)) return nullptr;
-        __half* d = static_cast<__half*>(dalloc((size_t)packed_weight_halfs(out, in) * 2));
-        launch_pack_weight(w, ldw, out, in, d, m.stream);
-        return d;
-    }
-    void pack(Linear& l) { l.wp = packed(l.w, l.ldw, l.out, l.in); }
-    void pack_decoder_layer(DecoderLayer& l) {
-        pack(l.qkv), pack(l.self_out), pack(l.cross_q), pack(l.cross_out), pack(l.ffn_in), pack(l.ffn_out);
-    }
-    // concatenate several (out_i, in) projections into one [sum out_i][in] weight
-    Linear fuse(const std::vector<std::string>& ps, int out_each, int in) {
-        SC_CHECK(in % 32 == 0, "sc_load: fused projection input dim %d must be a multiple of 32", in);
-        const int n = (int)ps.size();
-        __half* w = static_cast<__half*>(dalloc((size_t)n * out_each * in * 2));
-        float* b = static_cast<float*>(dalloc((size_t)n * out_each * 4));
-        for (int i = 0; i < n; ++i) {
-            const __half* wi = f16(ps[i] + ".weight", {out_each, in});
-            const float* bi = f32(ps[i] + ".bias", {out_each});
-            SC_HIP(hipMemcpyAsync(w + (size_t)i * out_each * in, wi, (size_t)out_each * in * 2, hipMemcpyDeviceToDevice,
-                                  m.stream));
-            SC_HIP(hipMemcpyAsync(b + (size_t)i * out_each, bi, (size_t)out_each * 4, hipMemcpyDeviceToDevice, m.stream));
-        }
-        Linear l;
-        l.w = w;
-        l.ldw = in;
-        l.kpad = in;
-        l.b = b;
-        l.out = n * out_each;
-        l.in = in;
-        return l;
-    }
-    Conv conv(const std::string& p, int cout, int cin, int k, bool bias = true) {
-        Conv c;
-        c.cout = cout;
-        c.cin = cin;
-        c.k = k;
-        c.kpad = (int)align_up((int64_t)cin * k, 32);
-        const __half* w = f16(p + ".weight", {cout, cin, k});
-        __half* d = static_cast<__half*>(dalloc((size_t)cout * c.kpad * 2));
-        launch_pack_conv_weight(w, d, cout, cin, k, c.kpad, m.stream);
-        c.w = d;
-        c.b = bias ? f32(p + ".bias", {cout}) : nullptr;
-        return c;
-    }
-    // weight-normed Conv1d: weight_g (cout,1,1), weight_v (cout,cin,k)
-    Conv conv_wn(const std::string& p, int cout, int cin, int k) {
-        Conv c;
-        c.cout = cout;
-        c.cin = cin;
-        c.k = k;
-        c.kpad = (int)align_up((int64_t)cin * k, 32);
-        const __half* v = f16(p + ".weight_v", {cout, cin, k});
-        const __half* g = f16(p + ".weight_g", {cout, 1, 1});
-        Buf<float> folded(m.pp(), (size_t)cout * cin * k);
-        Buf<__half> folded16(m.pp(), (size_t)cout * cin * k);
-        launch_weight_norm_fold(v, g, folded, cout, cin * k, m.stream);
-        launch_cvt_f32_f16(folded, folded16, (int64_t)cout * cin * k, m.stream);
-        __half* d = static_cast<__half*>(dalloc((size_t)cout * c.kpad * 2));
-        launch_pack_conv_weight(folded16, d, cout, cin, k, c.kpad, m.stream);
-        c.w = d;
-        c.b = f32(p + ".bias", {cout});
-        return c;
-    }
-    // weight-normed ConvTranspose1d: weight_g (cin,1,1), weight_v (cin,cout,k)
-    ConvT convT_wn(const std::string& p, int cin, int cout, int k, int stride) {
-        ConvT c;
-        c.cin = cin;
-        c.cout = cout;
-        c.k = k;
-        c.stride = stride;
-        // k - stride odd (the PRETSSEL generator's k = 2u at odd u): padding rounded up with output_padding 1, still stride * L out
-        c.pad = (k - stride + 1) / 2;
-        c.taps = cdiv(k, stride);
-        c.kpad = (int)align_up((int64_t)cin * c.taps, 32);
-        SC_CHECK(k >= stride && k - 2 * c.pad + (k - stride) % 2 == stride, "sc_load: '%s' ConvTranspose1d(k=%d,stride=%d) does not upsample by its stride",
-                 p.c_str(), k, stride);
-        const __half* v = f16(p + ".weight_v", {cin, cout, k});
-        const __half* g = f16(p + ".weight_g", {cin, 1, 1});
-        Buf<float> folded(m.pp(), (size_t)cin * cout * k);
-        launch_weight_norm_fold(v, g, folded, cin, cout * k, m.stream);
-        __half* d = static_cast<__half*>(dalloc((size_t)stride * cout * c.kpad * 2));
-        launch_pack_convT_weight(folded, d, cin, cout, k, stride, c.kpad, m.stream);
-        c.w = d;
-        c.b = f32(p + ".bias", {cout});
-        return c;
-    }
-};
-
 // kaldi-native-fbank constants (reference ggml/examples/kaldi-native-fbank/csrc/
 // feature-window.cc:30-55 povey window; mel-computations.cc:107-210 mel banks).
 void build_fbank_consts(Model& m) {
@@ -346,12 +363,12 @@ void build_fbank_consts(Model& m) {
 }  // namespace
 
 // the caller's tensors into memory the handle owns, by name (m.raw); tied tensors share storage
-void upload_tensors(Model& m, const sc_tensor_desc* t, size_t n) {
-    std::unordered_map<const void*, void*> seen;  // tied tensors share storage
+void upload_tensors(Model& m, const char* who, const sc_tensor_desc* t, size_t n) {
+    std::map<std::pair<const void*, size_t>, void*> seen;  // tied tensors (same address, same size) share storage
     for (size_t i = 0; i < n; ++i) {
         const sc_tensor_desc& d = t[i];
-        SC_CHECK(d.name && d.data && d.ndim >= 0 && d.ndim <= 4, "sc_load: bad tensor descriptor #%zu", i);
-        SC_CHECK(d.dtype == SC_F16 || d.dtype == SC_F32, "sc_load: tensor '%s' has unsupported dtype %d", d.name, d.dtype);
+        SC_CHECK(d.name && d.data && d.ndim >= 0 && d.ndim <= 4, "%s: bad tensor descriptor #%zu", who, i);
+        SC_CHECK(d.dtype == SC_F16 || d.dtype == SC_F32, "%s: tensor '%s' has unsupported dtype %d", who, d.name, d.dtype);
         Model::Raw r;
         r.dtype = d.dtype;
         r.numel = 1;
@@ -360,17 +377,13 @@ void upload_tensors(Model& m, const sc_tensor_desc* t, size_t n) {
             r.numel *= d.shape[k];
         }
         const size_t bytes = (size_t)r.numel * (d.dtype == SC_F16 ? 2 : 4);
-        auto it = seen.find(d.data);
-        if (it != seen.end()) {
-            r.p = it->second;
-        } else {
-            void* p = nullptr;
+        void*& p = seen[{d.data, bytes}];
+        if (!p) {
             SC_HIP(hipMalloc(&p, std::max<size_t>(bytes, 256)));
             m.owned.push_back(p);
             SC_HIP(hipMemcpy(p, d.data, bytes, d.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-            r.p = p;
-            seen[d.data] = p;
         }
+        r.p = p;
         m.raw[d.name] = std::move(r);
     }
 }
@@ -387,8 +400,7 @@ void load_model(Model& m, const sc_tensor_desc* t, size_t n) {
     SC_CHECK(c.model_dim == c.num_heads * 64, "sc_load: head_dim must be 64 (model_dim=%d, heads=%d)", c.model_dim,
              c.num_heads);
     SC_CHECK(c.model_dim % 32 == 0, "sc_load: model_dim must be a multiple of 32");
-    upload_tensors(m, t, n);
-    Loader L(m);
+    Loader L(m, "sc_load", t, n);
     const int M = c.model_dim;
     build_fbank_consts(m);
 
@@ -635,10 +647,8 @@ void load_model(Model& m, const sc_tensor_desc* t, size_t n) {
             float* fb = static_cast<float*>(L.dalloc((size_t)N * 4));
             std::vector<float> mul((size_t)N, 1.f), add((size_t)N, 0.f);
             auto stack = [&](const std::string& p, int off, int rows) {  // a Linear D -> rows into the rows [off, off + rows)
-                const __half* w = L.f16(p + ".weight", {rows, D});
-                const float* b = L.f32(p + ".bias", {rows});
-                SC_HIP(hipMemcpyAsync(fw + (size_t)off * D, w, (size_t)rows * D * 2, hipMemcpyDeviceToDevice, m.stream));
-                SC_HIP(hipMemcpyAsync(fb + off, b, (size_t)rows * 4, hipMemcpyDeviceToDevice, m.stream));
+                L.f16_into(p + ".weight", {rows, D}, fw + (size_t)off * D);
+                L.f32_into(p + ".bias", {rows}, fb + off);
             };
             auto film = [&](const std::string& p, int off, int C) {  // gamma' = s_gamma * g + 1, beta' = s_beta * b
                 stack(p + ".proj", off, 2 * C);
@@ -706,11 +716,9 @@ void load_model(Model& m, const sc_tensor_desc* t, size_t n) {
     SC_HIP(hipStreamSynchronize(m.stream));
 }
 
-// The HiFi-GAN stack of a handle whose tensors carry other names (the PRETSSEL waveform generator: layers.N): geometry from
-// m.cfg's voc_* fields, conv_pre over `in_dim` input channels.  res holds num_upsamples * num_resblock_kernels names.
-void load_hifigan_stack(Model& m, const HifiganNames& nm, int in_dim) {
+void load_hifigan_stack(Loader& L, const HifiganNames& nm, int in_dim) {
+    Model& m = L.m;
     const sc_config& c = m.cfg;
-    Loader L(m);
     const int nk = c.voc_num_resblock_kernels;
     SC_CHECK((int)nm.ups.size() == c.voc_num_upsamples && (int)nm.res.size() == c.voc_num_upsamples * nk, "load_hifigan_stack: %zu + %zu names", nm.ups.size(),
              nm.res.size());

@@ -16,10 +16,9 @@
 #include <algorithm>
 #include <cmath>
 #include <string>
-#include <unordered_map>
 
-#include "../../include/seamless_hip_internal.h"
-#include "model.h"
+#include "handle.h"
+#include "loader.h"
 
 using namespace sc;
 
@@ -77,134 +76,6 @@ namespace {
 
 constexpr int PRETSSEL_MAX_ITEMS = 1024;
 
-struct PtLoader {
-    sc_pretssel& a;
-    struct Raw {
-        void* p;
-        int dtype;
-        std::vector<int64_t> shape;
-        int64_t numel;
-    };
-    std::unordered_map<std::string, Raw> raw;
-    std::vector<void*> uploads;
-
-    void* dalloc(size_t bytes) {
-        void* p = nullptr;
-        SC_HIP(hipMalloc(&p, std::max<size_t>(bytes, 256)));
-        a.m.owned.push_back(p);
-        return p;
-    }
-    void upload(const sc_tensor_desc* t, size_t n) {
-        for (size_t i = 0; i < n; ++i) {
-            const sc_tensor_desc& d = t[i];
-            SC_CHECK(d.name && d.data && d.ndim >= 0 && d.ndim <= 4, "sc_pretssel_load: bad tensor descriptor #%zu", i);
-            SC_CHECK(d.dtype == SC_F16 || d.dtype == SC_F32, "sc_pretssel_load: tensor '%s' has unsupported dtype %d", d.name, d.dtype);
-            Raw r;
-            r.dtype = d.dtype;
-            r.numel = 1;
-            for (int k = 0; k < d.ndim; ++k) {
-                r.shape.push_back(d.shape[k]);
-                r.numel *= d.shape[k];
-            }
-            const size_t bytes = (size_t)r.numel * (d.dtype == SC_F16 ? 2 : 4);
-            SC_HIP(hipMalloc(&r.p, std::max<size_t>(bytes, 256)));
-            uploads.push_back(r.p);
-            SC_HIP(hipMemcpy(r.p, d.data, bytes, d.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-            raw[d.name] = std::move(r);
-        }
-    }
-    const Raw& get(const std::string& k, std::initializer_list<int64_t> shape) const {
-        auto it = raw.find(k);
-        SC_CHECK(it != raw.end(), "sc_pretssel_load: tensor '%s' is missing from the weight table", k.c_str());
-        const Raw& r = it->second;
-        bool ok = r.shape.size() == shape.size();
-        size_t i = 0;
-        for (int64_t s : shape) ok = ok && r.shape[i++] == s;
-        SC_CHECK(ok, "sc_pretssel_load: tensor '%s' has an unexpected shape", k.c_str());
-        return r;
-    }
-    // copies into memory the handle owns, in the wanted precision
-    void f16_into(const std::string& k, std::initializer_list<int64_t> shape, __half* dst) {
-        const Raw& r = get(k, shape);
-        if (r.dtype == SC_F16) SC_HIP(hipMemcpyAsync(dst, r.p, (size_t)r.numel * 2, hipMemcpyDeviceToDevice, a.m.stream));
-        else launch_cvt_f32_f16(static_cast<const float*>(r.p), dst, r.numel, a.m.stream);
-    }
-    void f32_into(const std::string& k, std::initializer_list<int64_t> shape, float* dst) {
-        const Raw& r = get(k, shape);
-        if (r.dtype == SC_F32) SC_HIP(hipMemcpyAsync(dst, r.p, (size_t)r.numel * 4, hipMemcpyDeviceToDevice, a.m.stream));
-        else launch_cvt_f16_f32(static_cast<const __half*>(r.p), dst, r.numel, a.m.stream);
-    }
-    __half* f16(const std::string& k, std::initializer_list<int64_t> shape) {
-        __half* dst = static_cast<__half*>(dalloc((size_t)get(k, shape).numel * 2));
-        f16_into(k, shape, dst);
-        return dst;
-    }
-    float* f32(const std::string& k, std::initializer_list<int64_t> shape) {
-        float* dst = static_cast<float*>(dalloc((size_t)get(k, shape).numel * 4));
-        f32_into(k, shape, dst);
-        return dst;
-    }
-    float scalar(const std::string& k) {
-        const float* d = f32(k, {1});
-        float v = 0.f;
-        SC_HIP(hipStreamSynchronize(a.m.stream));
-        SC_HIP(hipMemcpy(&v, d, 4, hipMemcpyDeviceToHost));
-        return v;
-    }
-    // Conv1d weight [cout][cin][k] -> packed tap-major rows [cout][k * cin_pad] at dst (input channels cin .. cin_pad-1 zeros)
-    void pack_conv(const std::string& p, int cout, int cin, int k, int cin_pad, __half* dst, float* bias_dst) {
-        const Raw& r = get(p + ".weight", {cout, cin, k});
-        __half* w = static_cast<__half*>(dalloc((size_t)cout * cin_pad * k * 2));
-        if (cin_pad == cin) {
-            f16_into(p + ".weight", {cout, cin, k}, w);
-        } else {
-            __half* tmp = static_cast<__half*>(dalloc((size_t)r.numel * 2));
-            f16_into(p + ".weight", {cout, cin, k}, tmp);
-            SC_HIP(hipMemsetAsync(w, 0, (size_t)cout * cin_pad * k * 2, a.m.stream));
-            SC_HIP(hipMemcpy2DAsync(w, (size_t)cin_pad * k * 2, tmp, (size_t)cin * k * 2, (size_t)cin * k * 2, cout, hipMemcpyDeviceToDevice, a.m.stream));
-        }
-        launch_pack_conv_weight(w, dst, cout, cin_pad, k, cin_pad * k, a.m.stream);
-        f32_into(p + ".bias", {cout}, bias_dst);
-    }
-    Conv conv(const std::string& p, int cout, int cin, int k, int cin_pad = 0) {
-        if (!cin_pad) cin_pad = cin;
-        Conv c;
-        c.cout = cout;
-        c.cin = cin_pad;
-        c.k = k;
-        c.kpad = cin_pad * k;
-        __half* d = static_cast<__half*>(dalloc((size_t)cout * c.kpad * 2));
-        float* b = static_cast<float*>(dalloc((size_t)cout * 4));
-        pack_conv(p, cout, cin, k, cin_pad, d, b);
-        c.w = d;
-        c.b = b;
-        return c;
-    }
-    Linear linear(const std::string& p, int out, int in) {
-        Linear l;
-        l.w = f16(p + ".weight", {out, in});
-        l.b = f32(p + ".bias", {out});
-        l.ldw = in;
-        l.kpad = in;
-        l.in = in;
-        l.out = out;
-        return l;
-    }
-    LNorm lnorm(const std::string& p, int dim) {
-        LNorm n;
-        n.dim = dim;
-        n.g = f32(p + ".weight", {dim});
-        n.b = f32(p + ".bias", {dim});
-        return n;
-    }
-    void finish() {
-        (void)hipStreamSynchronize(a.m.stream);
-        for (void* p : uploads) (void)hipFree(p);
-        uploads.clear();
-    }
-    ~PtLoader() { finish(); }
-};
-
 void check_config(const sc_pretssel_config& c) {
     SC_CHECK(c.num_heads >= 1 && c.model_dim == c.num_heads * 128, "sc_pretssel_load: model_dim=%d with %d heads: only head dimension 128 is built", c.model_dim,
              c.num_heads);
@@ -230,9 +101,9 @@ void check_config(const sc_pretssel_config& c) {
 
 void load_pretssel(sc_pretssel& a, const sc_tensor_desc* t, size_t n) {
     const sc_pretssel_config& c = a.cfg;
+    check_config(c);
     const int M = c.model_dim, Ci = c.conv_inner_dim, H = c.pred_hidden_dim, D = c.film_cond_dim, K = c.conv_kernel, PK = c.pred_kernel;
-    PtLoader L{a};
-    L.upload(t, n);
+    Loader L(a.m, "sc_pretssel_load", t, n);
     a.embed = L.f16("encoder_frontend.embed_tokens.weight", {c.vocab_size, M});
     a.lang = L.f32("encoder_frontend.embed_lang.weight", {c.num_langs, c.lang_embed_dim});
     a.pos = L.f32("pos_encoder.freqs", {c.max_seq_len, M});
@@ -258,22 +129,12 @@ void load_pretssel(sc_pretssel& a, const sc_tensor_desc* t, size_t n) {
     // ---- FFT layers ----
     auto layer = [&](const std::string& p, int off) {
         PretsselLayer l;
-        __half* w = static_cast<__half*>(L.dalloc((size_t)3 * M * M * 2));
-        float* b = static_cast<float*>(L.dalloc((size_t)3 * M * 4));
-        const char* names[3] = {"q_proj", "k_proj", "v_proj"};
-        for (int j = 0; j < 3; ++j) {
-            L.f16_into(p + ".self_attn." + names[j] + ".weight", {M, M}, w + (size_t)j * M * M);
-            L.f32_into(p + ".self_attn." + names[j] + ".bias", {M}, b + (size_t)j * M);
-        }
-        l.fft.qkv.w = w;
-        l.fft.qkv.b = b;
-        l.fft.qkv.ldw = l.fft.qkv.kpad = l.fft.qkv.in = M;
-        l.fft.qkv.out = 3 * M;
-        l.fft.attn_out = L.linear(p + ".self_attn.output_proj", M, M);
-        l.fft.attn_ln = L.lnorm(p + ".self_attn_layer_norm", M);
+        l.fft.qkv = L.fuse({p + ".self_attn.q_proj", p + ".self_attn.k_proj", p + ".self_attn.v_proj"}, M, M);
+        l.fft.attn_out = L.lin(p + ".self_attn.output_proj", M, M);
+        l.fft.attn_ln = L.ln(p + ".self_attn_layer_norm", M);
         l.fft.conv1 = L.conv(p + ".conv1d.conv1", Ci, M, K);
         l.fft.conv2 = L.conv(p + ".conv1d.conv2", M, Ci, K);
-        l.fft.conv_ln = L.lnorm(p + ".conv1d_layer_norm", M);
+        l.fft.conv_ln = L.ln(p + ".conv1d_layer_norm", M);
         l.film.off = off;
         film(p + ".film", off, M);
         return l;
@@ -299,7 +160,8 @@ void load_pretssel(sc_pretssel& a, const sc_tensor_desc* t, size_t n) {
         float* pb = static_cast<float*>(L.dalloc(3 * 4));
         for (int j = 0; j < 3; ++j) {
             const std::string p = va + preds[j];
-            L.pack_conv(p + ".conv1.0", H, M, PK, M, w + (size_t)j * H * s.kpad, b + (size_t)j * H);
+            L.pack_conv(p + ".conv1.0.weight", H, M, PK, M, s.kpad, w + (size_t)j * H * s.kpad);
+            L.f32_into(p + ".conv1.0.bias", {H}, b + (size_t)j * H);
             a.pred_c2[j] = L.conv(p + ".conv2.0", H, H, PK);
             L.f32_into(p + ".ln1.weight", {H}, g1 + (size_t)j * H);
             L.f32_into(p + ".ln1.bias", {H}, b1 + (size_t)j * H);
@@ -331,16 +193,16 @@ void load_pretssel(sc_pretssel& a, const sc_tensor_desc* t, size_t n) {
     a.film_mul = fm;
     a.film_add = fa;
     // ---- projection, post-net, gcmvn ----
-    a.proj = L.linear("final_proj", c.mel_dim, M);
+    a.proj = L.lin("final_proj", c.mel_dim, M);
     a.mel_pad = (int)align_up(c.mel_dim, 32);
     for (int i = 0; i < c.post_layers; ++i) {
         const std::string p = "layers." + std::to_string(i);
         const int cin = i == 0 ? c.mel_dim : c.post_dim, cout = i == c.post_layers - 1 ? c.mel_dim : c.post_dim;
-        a.post.push_back(L.conv(p + ".0", cout, cin, c.post_kernel, i == 0 ? a.mel_pad : cin));
-        const float* g = L.f32(p + ".1.weight", {cout});
-        const float* b = L.f32(p + ".1.bias", {cout});
-        const float* mu = L.f32(p + ".1.running_mean", {cout});
-        const float* var = L.f32(p + ".1.running_var", {cout});
+        a.post.push_back(L.conv(p + ".0", cout, cin, c.post_kernel, /*bias=*/true, i == 0 ? a.mel_pad : cin));
+        const float* g = L.f32(p + ".1.weight", {cout}, /*keep=*/false);
+        const float* b = L.f32(p + ".1.bias", {cout}, /*keep=*/false);
+        const float* mu = L.f32(p + ".1.running_mean", {cout}, /*keep=*/false);
+        const float* var = L.f32(p + ".1.running_var", {cout}, /*keep=*/false);
         float* scale = static_cast<float*>(L.dalloc((size_t)cout * 4));
         float* shift = static_cast<float*>(L.dalloc((size_t)cout * 4));
         launch_bn_fold(g, b, mu, var, 1e-5f, cout, scale, shift, a.m.stream);
@@ -348,8 +210,7 @@ void load_pretssel(sc_pretssel& a, const sc_tensor_desc* t, size_t n) {
     }
     a.gmean = L.f32("gcmvn_mean", {c.mel_dim});
     a.gstd = L.f32("gcmvn_std", {c.mel_dim});
-    SC_HIP(hipStreamSynchronize(a.m.stream));
-    L.finish();
+    L.release_unused();
 }
 
 template <typename T>
@@ -668,72 +529,15 @@ void run_pretssel_mel(sc_pretssel& a, const int32_t* h_tokens, int n, int s_tok,
     SC_HIP(hipStreamSynchronize(m.stream));  // the caller's stream is not ours: the output is complete on return
 }
 
-struct OpBufs {  // hipMalloc'ed scratch of one op call
-    std::vector<void*> ptrs;
-    template <typename T>
-    T* get(size_t n) {
-        void* p = nullptr;
-        SC_HIP(hipMalloc(&p, std::max<size_t>(n * sizeof(T), 256)));
-        ptrs.push_back(p);
-        return static_cast<T*>(p);
-    }
-    template <typename T>
-    T* put(const std::vector<T>& h) {
-        T* d = get<T>(h.size());
-        if (!h.empty()) SC_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-        return d;
-    }
-    ~OpBufs() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-};
-
 }  // namespace
-
-#define SC_API_BEGIN try {
-#define SC_API_END                                                 \
-    }                                                                    \
-    catch (const sc::Error& e) { return e.code; }                        \
-    catch (const std::exception& e) {                                    \
-        sc::set_error("unexpected C++ exception: %s", e.what());         \
-        return SC_ERR_INTERNAL;                                          \
-    }                                                                    \
-    return SC_OK;
 
 extern "C" {
 
 sc_pretssel* sc_pretssel_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_pretssel_config* cfg, int device) {
-    sc_pretssel* h = nullptr;
-    try {
-        SC_CHECK(tensors && cfg, "sc_pretssel_load: null argument");
-        SC_CHECK(cfg->abi_version == SC_ABI_VERSION, "sc_pretssel_load: config ABI version %d != library %d", cfg->abi_version, SC_ABI_VERSION);
-        check_config(*cfg);
-        int ndev = 0;
-        SC_HIP(hipGetDeviceCount(&ndev));
-        SC_CHECK(device >= 0 && device < ndev, "sc_pretssel_load: device %d not available (%d visible)", device, ndev);
-        knob::report_once();
-        SC_HIP(hipSetDevice(device));
-        h = new sc_pretssel();
-        h->cfg = *cfg;
-        h->m.device = device;
-        SC_HIP(hipStreamCreateWithFlags(&h->m.stream, hipStreamNonBlocking));
-        h->m.pool.set_stream(h->m.stream);
-        h->m.hook_pool(h->m.pool);
-        load_pretssel(*h, tensors, n_tensors);
-        return h;
-    } catch (const sc::Error&) {
-    } catch (const std::exception& e) {
-        sc::set_error("sc_pretssel_load: unexpected C++ exception: %s", e.what());
-    }
-    delete h;
-    return nullptr;
+    return open_handle<sc_pretssel>("sc_pretssel_load", tensors, n_tensors, cfg, device, load_pretssel);
 }
 
-void sc_pretssel_free(sc_pretssel* p) {
-    if (!p) return;
-    (void)hipSetDevice(p->m.device);
-    delete p;
-}
+void sc_pretssel_free(sc_pretssel* p) { free_handle(p); }
 
 int sc_pretssel_mel(sc_pretssel* p, const int32_t* h_tokens, int32_t n, int32_t s_tok, const int32_t* h_tok_lens, const int32_t* h_durations,
                     int32_t lang_index, const float* d_prosody, float* d_mel, int32_t t_cap, int32_t* h_frame_lens_or_null) {
@@ -866,7 +670,7 @@ int sc_op_pretssel_upsample(const float* d_x, const int32_t* h_tok_lens, const i
         tok_off[(size_t)i + 1] = tok_off[i] + h_tok_lens[i];
         frame_off[(size_t)i + 1] = frame_off[i] + (int)frames;
     }
-    OpBufs sc_;
+    OpScratch sc_;
     PretsselUpsArgs a;
     a.x = d_x;
     a.dur = sc_.put(dur);

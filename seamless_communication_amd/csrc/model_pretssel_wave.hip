@@ -6,31 +6,12 @@
 #include <string>
 #include <vector>
 
-#include "../../include/seamless_hip_internal.h"
-#include "model.h"
+#include "handle.h"
+#include "loader.h"
 
 using namespace sc;
 
 namespace {
-
-struct Scratch {  // hipMalloc'ed buffers of one call
-    std::vector<void*> ptrs;
-    template <typename T>
-    T* get(size_t n) {
-        void* p = nullptr;
-        SC_HIP(hipMalloc(&p, std::max<size_t>(n * sizeof(T), 256)));
-        ptrs.push_back(p);
-        return static_cast<T*>(p);
-    }
-    int* offsets(const std::vector<int>& off) {
-        int* d = get<int>(off.size());
-        SC_HIP(hipMemcpy(d, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
-        return d;
-    }
-    ~Scratch() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-};
 
 constexpr int WAVE_MAX_ITEMS = 1024;
 
@@ -142,51 +123,19 @@ namespace {
 constexpr int WAVE_STREAM_K = 7, WAVE_RES_K = 3;
 constexpr int64_t WAVE_GROUP_SAMPLES = 1ll << 22;
 
-struct WaveLoader {
-    sc_pretssel_wave_model& a;
-    Model& m;
-    explicit WaveLoader(sc_pretssel_wave_model& h) : a(h), m(h.m) {}
-    void* dalloc(size_t bytes) {
-        void* p = nullptr;
-        SC_HIP(hipMalloc(&p, std::max<size_t>(bytes, 256)));
-        m.owned.push_back(p);
-        return p;
-    }
-    const Model::Raw& get(const std::string& k, std::initializer_list<int64_t> shape) const {
-        auto it = m.raw.find(k);
-        SC_CHECK(it != m.raw.end(), "sc_pretssel_wave_load: tensor '%s' is missing from the weight table", k.c_str());
-        const Model::Raw& r = it->second;
-        bool ok = r.shape.size() == shape.size();
-        size_t i = 0;
-        for (int64_t s : shape) ok = ok && r.shape[i++] == s;
-        SC_CHECK(ok, "sc_pretssel_wave_load: tensor '%s' has an unexpected shape", k.c_str());
-        return r;
-    }
-    const __half* f16(const std::string& k, std::initializer_list<int64_t> shape) {
-        const Model::Raw& r = get(k, shape);
-        if (r.dtype == SC_F16) return static_cast<const __half*>(r.p);
-        __half* d = static_cast<__half*>(dalloc((size_t)r.numel * 2));
-        launch_cvt_f32_f16(static_cast<const float*>(r.p), d, r.numel, m.stream);
-        return d;
-    }
-    const float* f32(const std::string& k, std::initializer_list<int64_t> shape) {
-        const Model::Raw& r = get(k, shape);
-        if (r.dtype == SC_F32) return static_cast<const float*>(r.p);
-        float* d = static_cast<float*>(dalloc((size_t)r.numel * 4));
-        launch_cvt_f16_f32(static_cast<const __half*>(r.p), d, r.numel, m.stream);
-        return d;
-    }
+struct WaveLoader : Loader {  // what is the waveform generator's own
+    using Loader::Loader;
     // weight-normed weight [d0][d1][k] with g [d0][1][1] -> folded fp32 (scratch of the pool)
     Buf<float> folded(const std::string& p, int d0, int d1, int k) {
-        const __half* v = f16(p + ".weight_v", {d0, d1, k});
-        const __half* g = f16(p + ".weight_g", {d0, 1, 1});
+        const __half* v = f16(p + ".weight_v", {d0, d1, k}, /*keep=*/false);
+        const __half* g = f16(p + ".weight_g", {d0, 1, 1}, /*keep=*/false);
         Buf<float> f(m.pp(), (size_t)d0 * d1 * k);
         launch_weight_norm_fold(v, g, f, d0, d1 * k, m.stream);
         return f;
     }
     SConv sconv(const std::string& p, int cin, int cout, int k, int stride, bool transposed) {
         SC_CHECK(transposed ? (k == 2 * stride && (size_t)cin * 5 * 4 <= 48 * 1024) : sconv_supported(cin, cout, k, stride),
-                 "sc_pretssel_wave_load: '%s' %d -> %d k=%d stride=%d is outside the convolution kernels' limits", p.c_str(), cin, cout, k, stride);
+                 "%s: '%s' %d -> %d k=%d stride=%d is outside the convolution kernels' limits", who, p.c_str(), cin, cout, k, stride);
         SConv c;
         c.cin = cin, c.cout = cout, c.k = k, c.stride = stride;
         Buf<float> f = transposed ? folded(p, cin, cout, k) : folded(p, cout, cin, k);
@@ -206,7 +155,7 @@ struct WaveLoader {
         return d;
     }
     SRes res(const std::string& p, int C) {
-        SC_CHECK(C >= 2 && C % 2 == 0, "sc_pretssel_wave_load: residual block at %d channels", C);
+        SC_CHECK(C >= 2 && C % 2 == 0, "%s: residual block at %d channels", who, C);
         SRes r;
         r.C = C;
         const std::string p1 = p + ".block.1.conv.conv", p2 = p + ".block.3.conv.conv";
@@ -226,8 +175,8 @@ struct WaveLoader {
         w.H = H;
         w.wih0 = f16(p + ".weight_ih_l0", {4 * H, H});
         w.whh0 = f16(p + ".weight_hh_l0", {4 * H, H});
-        const __half* wih1 = f16(p + ".weight_ih_l1", {4 * H, H});
-        const __half* whh1 = f16(p + ".weight_hh_l1", {4 * H, H});
+        const __half* wih1 = f16(p + ".weight_ih_l1", {4 * H, H}, /*keep=*/false);
+        const __half* whh1 = f16(p + ".weight_hh_l1", {4 * H, H}, /*keep=*/false);
         __half* w1 = static_cast<__half*>(dalloc((size_t)4 * H * 2 * H * 2));  // [W_ih1 | W_hh1]
         SC_HIP(hipMemcpy2DAsync(w1, (size_t)2 * H * 2, wih1, (size_t)H * 2, (size_t)H * 2, (size_t)4 * H, hipMemcpyDeviceToDevice, m.stream));
         SC_HIP(hipMemcpy2DAsync(w1 + H, (size_t)2 * H * 2, whh1, (size_t)H * 2, (size_t)H * 2, (size_t)4 * H, hipMemcpyDeviceToDevice, m.stream));
@@ -268,12 +217,13 @@ void check_wave_config(const sc_pretssel_wave_config& c) {
 
 void load_wave(sc_pretssel_wave_model& a, const sc_tensor_desc* t, size_t n) {
     const sc_pretssel_wave_config& c = a.cfg;
+    check_wave_config(c);
     Model& m = a.m;
     const int P = c.post_layers, U = c.num_upsamples, F = c.n_filters;
     const auto layer = [](int i) { return "layers." + std::to_string(i); };
     const int chunk[4] = {P, P + 9, P + 17 + U, P + 25 + 4 * U};
     const auto stream = [&](int i) { return layer(chunk[i / 8] + i % 8); };
-    upload_tensors(m, t, n);
+    WaveLoader L(m, "sc_pretssel_wave_load", t, n);
     // ---- the HiFi-GAN: the unit vocoder's Model fields and loaders ----
     sc_config& v = m.cfg;
     v.voc_num_upsamples = U;
@@ -296,10 +246,9 @@ void load_wave(sc_pretssel_wave_model& a, const sc_tensor_desc* t, size_t n) {
         for (int d = 0; d < 3; ++d) v.voc_resblock_dilation_sizes[j][d] = c.resblock_dilation_sizes[j][d];
     }
     for (int i = 0; i < 3 * U; ++i) nm.res.push_back(layer(P + 25 + U + i));
-    load_hifigan_stack(m, nm, c.mel_dim);
+    load_hifigan_stack(L, nm, c.mel_dim);
     SC_CHECK(hifigan_packed_row_cap(m, a.hop) > 0, "sc_pretssel_wave_load: a HiFi-GAN stage has a shape no packed-item kernel takes");
     // ---- normalisation ----
-    WaveLoader L(a);
     a.mean = L.f32("mean", {c.mel_dim});
     a.scale = L.f32("scale", {c.mel_dim});
     {
@@ -332,7 +281,7 @@ void load_wave(sc_pretssel_wave_model& a, const sc_tensor_desc* t, size_t n) {
     a.tail_w = L.packed_rows(stream(31) + ".conv.conv", 1, F, WAVE_STREAM_K);
     a.tail_b = L.f32(stream(31) + ".conv.conv.bias", {1});
     a.tail_k = WAVE_STREAM_K;
-    SC_HIP(hipStreamSynchronize(m.stream));
+    L.release_unused();
 }
 
 // lengths of one item of `samples` samples: the encoder's four levels down (ceil), the decoder's four levels up
@@ -495,50 +444,13 @@ void run_wave(sc_pretssel_wave_model& a, const float* d_mel, int n, int t_cap, c
 
 }  // namespace
 
-#define SC_API_BEGIN try {
-#define SC_API_END                                                 \
-    }                                                                    \
-    catch (const sc::Error& e) { return e.code; }                        \
-    catch (const std::exception& e) {                                    \
-        sc::set_error("unexpected C++ exception: %s", e.what());         \
-        return SC_ERR_INTERNAL;                                          \
-    }                                                                    \
-    return SC_OK;
-
 extern "C" {
 
 sc_pretssel_wave_model* sc_pretssel_wave_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_pretssel_wave_config* cfg, int device) {
-    sc_pretssel_wave_model* h = nullptr;
-    try {
-        SC_CHECK(tensors && cfg, "sc_pretssel_wave_load: null argument");
-        SC_CHECK(cfg->abi_version == SC_ABI_VERSION, "sc_pretssel_wave_load: config ABI version %d != library %d", cfg->abi_version, SC_ABI_VERSION);
-        check_wave_config(*cfg);
-        int ndev = 0;
-        SC_HIP(hipGetDeviceCount(&ndev));
-        SC_CHECK(device >= 0 && device < ndev, "sc_pretssel_wave_load: device %d not available (%d visible)", device, ndev);
-        knob::report_once();
-        SC_HIP(hipSetDevice(device));
-        h = new sc_pretssel_wave_model();
-        h->cfg = *cfg;
-        h->m.device = device;
-        SC_HIP(hipStreamCreateWithFlags(&h->m.stream, hipStreamNonBlocking));
-        h->m.pool.set_stream(h->m.stream);
-        h->m.hook_pool(h->m.pool);
-        load_wave(*h, tensors, n_tensors);
-        return h;
-    } catch (const sc::Error&) {
-    } catch (const std::exception& e) {
-        sc::set_error("sc_pretssel_wave_load: unexpected C++ exception: %s", e.what());
-    }
-    delete h;
-    return nullptr;
+    return open_handle<sc_pretssel_wave_model>("sc_pretssel_wave_load", tensors, n_tensors, cfg, device, load_wave);
 }
 
-void sc_pretssel_wave_free(sc_pretssel_wave_model* p) {
-    if (!p) return;
-    (void)hipSetDevice(p->m.device);
-    delete p;
-}
+void sc_pretssel_wave_free(sc_pretssel_wave_model* p) { free_handle(p); }
 
 int sc_pretssel_wave(sc_pretssel_wave_model* p, const float* d_mel, int32_t n, int32_t t_cap, const int32_t* h_frame_lens, float* d_wav, int32_t wav_cap,
                      int32_t* h_wav_lens_or_null, int32_t flags) {
@@ -585,7 +497,7 @@ int sc_op_lstm2(const float* d_x, const int32_t* h_lens, int32_t n, int32_t H, c
     const int longest = offsets_of("sc_op_lstm2", h_lens, n, off);
     const int rows = off[n];
     SC_CHECK((int64_t)rows * 4 * H < (1ll << 31), "sc_op_lstm2: %d rows at H=%d", rows, H);
-    Scratch sc_;
+    OpScratch sc_;
     Lstm2 w;
     w.H = H;
     w.wih0 = static_cast<const __half*>(d_wih0_f16);
@@ -600,7 +512,7 @@ int sc_op_lstm2(const float* d_x, const int32_t* h_lens, int32_t n, int32_t H, c
     w.b_ih1 = d_b_ih1;
     w.b_hh1 = d_b_hh1;
     if (d_max_pre_or_null) SC_HIP(hipMemset(d_max_pre_or_null, 0, sizeof(float)));
-    const int launches = run_lstm2(w, d_x, sc_.offsets(off), n, rows, longest, sc_.get<float>((size_t)rows * 4 * H), sc_.get<float>((size_t)rows * H),
+    const int launches = run_lstm2(w, d_x, sc_.put(off), n, rows, longest, sc_.get<float>((size_t)rows * 4 * H), sc_.get<float>((size_t)rows * H),
                                    sc_.get<float>((size_t)rows * H), sc_.get<float>((size_t)2 * n * H), d_y, d_max_pre_or_null, nullptr);
     if (h_launches_or_null) *h_launches_or_null = launches;
     SC_HIP(hipStreamSynchronize(nullptr));
@@ -616,7 +528,7 @@ int sc_op_seanet_resblock(const float* d_x, const int32_t* h_lens, int32_t n, in
     SC_CHECK(seanet_resblock_supported(C), "sc_op_seanet_resblock: C=%d (32 or 64)", C);
     std::vector<int> off;
     const int longest = offsets_of("sc_op_seanet_resblock", h_lens, n, off);
-    Scratch sc_;
+    OpScratch sc_;
     __half* w1 = sc_.get<__half>((size_t)(C / 2) * 3 * C);
     launch_pack_conv_weight(static_cast<const __half*>(d_w1_f16), w1, C / 2, C, 3, 3 * C, nullptr);
     SeanetResArgs a;
@@ -626,7 +538,7 @@ int sc_op_seanet_resblock(const float* d_x, const int32_t* h_lens, int32_t n, in
     a.w2 = static_cast<const __half*>(d_w2_f16);  // [C][C/2][1] is [C][C/2]
     a.b2 = d_b2;
     a.y = d_y;
-    a.row_off = sc_.offsets(off);
+    a.row_off = sc_.put(off);
     a.n = n;
     a.longest = longest;
     a.C = C;
@@ -650,7 +562,7 @@ int sc_op_sconv(const float* d_x, const int32_t* h_lens, int32_t n, int32_t cin,
     }
     const int longest_out = offsets_of("sc_op_sconv", out_lens.data(), n, out_off);
     std::copy(out_lens.begin(), out_lens.end(), h_out_lens);
-    Scratch sc_;
+    OpScratch sc_;
     __half* wt = sc_.get<__half>((size_t)k * cin * cout);
     launch_pack_sconv_weight(d_w, wt, cin, cout, k, transposed != 0, nullptr);
     SconvArgs a;
@@ -659,8 +571,8 @@ int sc_op_sconv(const float* d_x, const int32_t* h_lens, int32_t n, int32_t cin,
     a.bias = d_bias;
     a.res = d_res_or_null;
     a.y = d_y;
-    a.in_off = sc_.offsets(in_off);
-    a.out_off = sc_.offsets(out_off);
+    a.in_off = sc_.put(in_off);
+    a.out_off = sc_.put(out_off);
     a.n = n;
     a.longest_out = longest_out;
     a.cin = cin;
@@ -686,7 +598,7 @@ int sc_op_seanet_tail(const float* d_h, const int32_t* h_dec_lens, const int32_t
     for (int i = 0; i < n; ++i)
         SC_CHECK(h_out_lens[i] <= h_dec_lens[i] && (!wav_stride || h_out_lens[i] <= wav_stride), "sc_op_seanet_tail: item %d keeps %d of %d samples (row of %lld)", i,
                  h_out_lens[i], h_dec_lens[i], (long long)wav_stride);
-    Scratch sc_;
+    OpScratch sc_;
     __half* w = sc_.get<__half>((size_t)k * cin);
     launch_pack_conv_weight(static_cast<const __half*>(d_w_f16), w, 1, cin, k, k * cin, nullptr);
     SeanetTailArgs a;
@@ -695,8 +607,8 @@ int sc_op_seanet_tail(const float* d_h, const int32_t* h_dec_lens, const int32_t
     a.bias = d_bias;
     a.skip = d_skip;
     a.wav = d_wav;
-    a.in_off = sc_.offsets(in_off);
-    a.out_off = sc_.offsets(out_off);
+    a.in_off = sc_.put(in_off);
+    a.out_off = sc_.put(out_off);
     a.wav_stride = wav_stride;
     a.n = n;
     a.longest_out = longest_out;

@@ -9,10 +9,9 @@
 #include <algorithm>
 #include <cmath>
 #include <string>
-#include <unordered_map>
 
-#include "../../include/seamless_hip_internal.h"
-#include "model.h"
+#include "handle.h"
+#include "loader.h"
 
 using namespace sc;
 
@@ -36,132 +35,6 @@ namespace {
 
 constexpr int UE_MAX_FRAMES = 4096;
 
-struct UeLoader {
-    sc_unit_extractor& a;
-    struct Raw {
-        void* p;
-        int dtype;
-        std::vector<int64_t> shape;
-        int64_t numel;
-    };
-    std::unordered_map<std::string, Raw> raw;
-    std::vector<void*> uploads;
-    std::vector<const void*> used_as_is;
-
-    void* dalloc(size_t bytes) {
-        void* p = nullptr;
-        SC_HIP(hipMalloc(&p, std::max<size_t>(bytes, 256)));
-        a.m.owned.push_back(p);
-        return p;
-    }
-    void upload(const sc_tensor_desc* t, size_t n) {
-        for (size_t i = 0; i < n; ++i) {
-            const sc_tensor_desc& d = t[i];
-            SC_CHECK(d.name && d.data && d.ndim >= 0 && d.ndim <= 4, "sc_unit_extractor_load: bad tensor descriptor #%zu", i);
-            SC_CHECK(d.dtype == SC_F16 || d.dtype == SC_F32, "sc_unit_extractor_load: tensor '%s' has unsupported dtype %d", d.name, d.dtype);
-            Raw r;
-            r.dtype = d.dtype;
-            r.numel = 1;
-            for (int k = 0; k < d.ndim; ++k) {
-                r.shape.push_back(d.shape[k]);
-                r.numel *= d.shape[k];
-            }
-            const size_t bytes = (size_t)r.numel * (d.dtype == SC_F16 ? 2 : 4);
-            SC_HIP(hipMalloc(&r.p, std::max<size_t>(bytes, 256)));
-            uploads.push_back(r.p);
-            SC_HIP(hipMemcpy(r.p, d.data, bytes, d.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
-            raw[d.name] = std::move(r);
-        }
-    }
-    const Raw& get(const std::string& k, std::initializer_list<int64_t> shape) const {
-        auto it = raw.find(k);
-        SC_CHECK(it != raw.end(), "sc_unit_extractor_load: tensor '%s' is missing from the weight table", k.c_str());
-        const Raw& r = it->second;
-        bool ok = r.shape.size() == shape.size();
-        size_t i = 0;
-        for (int64_t s : shape) ok = ok && r.shape[i++] == s;
-        SC_CHECK(ok, "sc_unit_extractor_load: tensor '%s' has an unexpected shape", k.c_str());
-        return r;
-    }
-    // a copy the handle owns, in the wanted precision, at dst (dst == null: a fresh allocation)
-    __half* f16_to(const std::string& k, std::initializer_list<int64_t> shape, __half* dst) {
-        const Raw& r = get(k, shape);
-        if (!dst) dst = static_cast<__half*>(dalloc((size_t)r.numel * 2));
-        if (r.dtype == SC_F16) SC_HIP(hipMemcpyAsync(dst, r.p, (size_t)r.numel * 2, hipMemcpyDeviceToDevice, a.m.stream));
-        else launch_cvt_f32_f16(static_cast<const float*>(r.p), dst, r.numel, a.m.stream);
-        return dst;
-    }
-    float* f32_to(const std::string& k, std::initializer_list<int64_t> shape, float* dst) {
-        const Raw& r = get(k, shape);
-        if (!dst) dst = static_cast<float*>(dalloc((size_t)r.numel * 4));
-        if (r.dtype == SC_F32) SC_HIP(hipMemcpyAsync(dst, r.p, (size_t)r.numel * 4, hipMemcpyDeviceToDevice, a.m.stream));
-        else launch_cvt_f16_f32(static_cast<const __half*>(r.p), dst, r.numel, a.m.stream);
-        return dst;
-    }
-    LNorm ln(const std::string& p, int dim) {
-        LNorm l;
-        l.dim = dim;
-        l.g = f32_to(p + ".weight", {dim}, nullptr);
-        l.b = f32_to(p + ".bias", {dim}, nullptr);
-        return l;
-    }
-    Linear linear(const std::string& p, int out, int in) {
-        SC_CHECK(in % 32 == 0, "sc_unit_extractor_load: '%s' has %d input features, not a multiple of 32", p.c_str(), in);
-        Linear l;
-        l.out = out;
-        l.in = in;
-        l.kpad = in;
-        l.ldw = in;
-        l.w = f16_to(p + ".weight", {out, in}, nullptr);
-        l.b = f32_to(p + ".bias", {out}, nullptr);
-        return l;
-    }
-    // q / k / v projections as one [3M][M] product
-    Linear qkv(const std::string& p, int M) {
-        SC_CHECK(M % 32 == 0, "sc_unit_extractor_load: model_dim %d is not a multiple of 32", M);
-        Linear l;
-        l.out = 3 * M;
-        l.in = M;
-        l.kpad = M;
-        l.ldw = M;
-        __half* w = static_cast<__half*>(dalloc((size_t)3 * M * M * 2));
-        float* b = static_cast<float*>(dalloc((size_t)3 * M * 4));
-        const char* names[3] = {".q_proj", ".k_proj", ".v_proj"};
-        for (int i = 0; i < 3; ++i) {
-            f16_to(p + names[i] + ".weight", {M, M}, w + (size_t)i * M * M);
-            f32_to(p + names[i] + ".bias", {M}, b + (size_t)i * M);
-        }
-        l.w = w;
-        l.b = b;
-        return l;
-    }
-    Conv conv(const std::string& p, int cout, int cin, int k) {
-        Conv c;
-        c.cout = cout;
-        c.cin = cin;
-        c.k = k;
-        c.kpad = (int)align_up((int64_t)cin * k, 32);
-        const Raw& rw = get(p + ".weight", {cout, cin, k});
-        const __half* w = static_cast<const __half*>(rw.p);
-        if (rw.dtype != SC_F16) {
-            __half* h = static_cast<__half*>(dalloc((size_t)rw.numel * 2));
-            launch_cvt_f32_f16(static_cast<const float*>(rw.p), h, rw.numel, a.m.stream);
-            w = h;
-        }
-        __half* d = static_cast<__half*>(dalloc((size_t)cout * c.kpad * 2));
-        launch_pack_conv_weight(w, d, cout, cin, k, c.kpad, a.m.stream);
-        c.w = d;
-        c.b = f32_to(p + ".bias", {cout}, nullptr);
-        return c;
-    }
-    void finish() {
-        (void)hipStreamSynchronize(a.m.stream);
-        for (void* p : uploads) (void)hipFree(p);
-        uploads.clear();
-    }
-    ~UeLoader() { finish(); }
-};
-
 void check_config(const sc_unit_extractor_config& c) {
     SC_CHECK(c.model_dim > 0 && c.heads > 0 && c.model_dim % c.heads == 0 && (c.model_dim / c.heads == 64 || c.model_dim / c.heads == 80),
              "sc_unit_extractor_load: model_dim=%d heads=%d (the head dimension must be 64 or 80)", c.model_dim, c.heads);
@@ -184,49 +57,47 @@ void load_unit_extractor(sc_unit_extractor& a, const sc_tensor_desc* t, size_t n
     const sc_unit_extractor_config& c = a.cfg;
     check_config(c);
     const int M = c.model_dim, F = c.feature_dim;
-    UeLoader L{a};
-    L.upload(t, n);
+    Loader L(a.m, "sc_unit_extractor_load", t, n);
     const std::string fe = "encoder_frontend.feature_extractor.layers.";
-    a.c0_w = L.f32_to(fe + "0.conv.weight", {F, 1, c.fe_kernel[0]}, nullptr);
-    a.c0_b = L.f32_to(fe + "0.conv.bias", {F}, nullptr);
+    a.c0_w = L.f32(fe + "0.conv.weight", {F, 1, c.fe_kernel[0]});
+    a.c0_b = L.f32(fe + "0.conv.bias", {F});
     a.fe_conv.resize(c.fe_layers);
     for (int i = 0; i < c.fe_layers; ++i) {
         a.fe_ln.push_back(L.ln(fe + std::to_string(i) + ".layer_norm", F));
         if (i > 0) a.fe_conv[i] = L.conv(fe + std::to_string(i) + ".conv", F, F, c.fe_kernel[i]);
     }
     a.post_ln = L.ln("encoder_frontend.post_extract_layer_norm", F);
-    a.proj = L.linear("encoder_frontend.model_dim_proj", M, F);
+    a.proj = L.lin("encoder_frontend.model_dim_proj", M, F);
     {
         // the weight-norm (dim = 2) is folded by the caller: "weight" is g * v / |v| in fp32
         const int cg = M / c.pos_conv_groups, K = c.pos_conv_kernel;
-        const float* w = L.f32_to("encoder_frontend.pos_encoder.conv.weight", {M, cg, K}, nullptr);
+        const float* w = L.f32("encoder_frontend.pos_encoder.conv.weight", {M, cg, K}, /*keep=*/false);
         float* packed = static_cast<float*>(L.dalloc((size_t)M * cg * K * 4));
         launch_w2v2_pack_pos_weight(w, packed, M, c.pos_conv_groups, K, a.m.stream);
         a.pos_w = packed;
-        a.pos_b = L.f32_to("encoder_frontend.pos_encoder.conv.bias", {M}, nullptr);
+        a.pos_b = L.f32("encoder_frontend.pos_encoder.conv.bias", {M});
     }
     for (int i = 0; i < c.layers; ++i) {
         const std::string p = "encoder.layers." + std::to_string(i);
         EncoderLayer l;
         l.attn_ln = L.ln(p + ".self_attn_layer_norm", M);
-        l.qkv = L.qkv(p + ".self_attn", M);
-        l.attn_out = L.linear(p + ".self_attn.output_proj", M, M);
+        l.qkv = L.fuse({p + ".self_attn.q_proj", p + ".self_attn.k_proj", p + ".self_attn.v_proj"}, M, M);
+        l.attn_out = L.lin(p + ".self_attn.output_proj", M, M);
         l.ffn_ln = L.ln(p + ".ffn_layer_norm", M);
-        l.ffn_in = L.linear(p + ".ffn.inner_proj", c.ffn_dim, M);
-        l.ffn_out = L.linear(p + ".ffn.output_proj", M, c.ffn_dim);
+        l.ffn_in = L.lin(p + ".ffn.inner_proj", c.ffn_dim, M);
+        l.ffn_out = L.lin(p + ".ffn.output_proj", M, c.ffn_dim);
         a.layers.push_back(l);
     }
     {
         const int K = c.num_centroids;
-        const float* cent = L.f32_to("kmeans.centroids", {M, K}, nullptr);  // the reference's transposed layout (kmeans.py:19)
+        const float* cent = L.f32("kmeans.centroids", {M, K}, /*keep=*/false);  // the reference's transposed layout (kmeans.py:19)
         __half* w = static_cast<__half*>(L.dalloc((size_t)K * 2 * M * 2));
         float* b = static_cast<float*>(L.dalloc((size_t)K * 4));
         launch_w2v2_pack_centroids(cent, M, K, w, b, a.m.stream);
         a.km_w = w;
         a.km_bias = b;
     }
-    SC_HIP(hipStreamSynchronize(a.m.stream));
-    L.finish();
+    L.release_unused();
 }
 
 // frames of `num_samples` samples behind the first `upto` extractor layers: floor((L - k) / s) + 1 each, 0 once a layer's
@@ -353,65 +224,15 @@ void run_extract_units(sc_unit_extractor& a, const float* h_wav, int n, int64_t 
     }
 }
 
-struct OpBufs {  // hipMalloc'ed scratch of one op call
-    std::vector<void*> ptrs;
-    template <typename T>
-    T* get(size_t n) {
-        void* p = nullptr;
-        SC_HIP(hipMalloc(&p, std::max<size_t>(n * sizeof(T), 256)));
-        ptrs.push_back(p);
-        return static_cast<T*>(p);
-    }
-    ~OpBufs() {
-        for (void* p : ptrs) (void)hipFree(p);
-    }
-};
-
 }  // namespace
-
-#define SC_API_BEGIN try {
-#define SC_API_END                                                 \
-    }                                                                    \
-    catch (const sc::Error& e) { return e.code; }                        \
-    catch (const std::exception& e) {                                    \
-        sc::set_error("unexpected C++ exception: %s", e.what());         \
-        return SC_ERR_INTERNAL;                                          \
-    }                                                                    \
-    return SC_OK;
 
 extern "C" {
 
 sc_unit_extractor* sc_unit_extractor_load(const sc_tensor_desc* tensors, size_t n_tensors, const sc_unit_extractor_config* cfg, int device) {
-    sc_unit_extractor* h = nullptr;
-    try {
-        SC_CHECK(tensors && cfg, "sc_unit_extractor_load: null argument");
-        SC_CHECK(cfg->abi_version == SC_ABI_VERSION, "sc_unit_extractor_load: config ABI version %d != library %d", cfg->abi_version, SC_ABI_VERSION);
-        int ndev = 0;
-        SC_HIP(hipGetDeviceCount(&ndev));
-        SC_CHECK(device >= 0 && device < ndev, "sc_unit_extractor_load: device %d not available (%d visible)", device, ndev);
-        knob::report_once();
-        SC_HIP(hipSetDevice(device));
-        h = new sc_unit_extractor();
-        h->cfg = *cfg;
-        h->m.device = device;
-        SC_HIP(hipStreamCreateWithFlags(&h->m.stream, hipStreamNonBlocking));
-        h->m.pool.set_stream(h->m.stream);
-        h->m.hook_pool(h->m.pool);
-        load_unit_extractor(*h, tensors, n_tensors);
-        return h;
-    } catch (const sc::Error&) {
-    } catch (const std::exception& e) {
-        sc::set_error("sc_unit_extractor_load: unexpected C++ exception: %s", e.what());
-    }
-    delete h;
-    return nullptr;
+    return open_handle<sc_unit_extractor>("sc_unit_extractor_load", tensors, n_tensors, cfg, device, load_unit_extractor);
 }
 
-void sc_unit_extractor_free(sc_unit_extractor* u) {
-    if (!u) return;
-    (void)hipSetDevice(u->m.device);
-    delete u;
-}
+void sc_unit_extractor_free(sc_unit_extractor* u) { free_handle(u); }
 
 int32_t sc_unit_extractor_num_frames(const sc_unit_extractor_config* cfg, int64_t num_samples) {
     if (!cfg || num_samples < 0 || cfg->fe_layers < 1 || cfg->fe_layers > SC_UE_MAX_FE_LAYERS) return -1;
@@ -459,9 +280,8 @@ int sc_op_w2v2_frontend(const float* d_wav, int64_t wav_stride, const int32_t* h
     for (int b = 0; b < nb; ++b)
         SC_CHECK(h_num_samples[b] >= 1 && h_num_samples[b] <= wav_stride, "sc_op_w2v2_frontend: num_samples[%d]=%d outside 1..stride", b,
                  h_num_samples[b]);
-    OpBufs sc_;
-    int* d_ns = sc_.get<int>(nb);
-    SC_HIP(hipMemcpy(d_ns, h_num_samples, (size_t)nb * 4, hipMemcpyHostToDevice));
+    OpScratch sc_;
+    const int* d_ns = sc_.put(std::vector<int>(h_num_samples, h_num_samples + nb));
     launch_w2v2_wave_stats(d_wav, wav_stride, d_ns, nb, d_stats, nullptr);
     launch_w2v2_conv0(d_wav, wav_stride, d_ns, d_stats, nb, d_w, d_bias, d_gamma, d_beta, C, k, stride, d_out, t_rows, nullptr);
     SC_HIP(hipStreamSynchronize(nullptr));
@@ -472,7 +292,7 @@ int sc_op_w2v2_pos_conv(const float* d_x, const float* d_w, const float* d_bias,
                         int32_t k, const int32_t* d_lens) {
     SC_API_BEGIN
     SC_CHECK(d_x && d_w && d_bias && d_y && groups > 0 && C > 0 && C % groups == 0 && k > 0, "sc_op_w2v2_pos_conv: bad argument");
-    OpBufs sc_;
+    OpScratch sc_;
     float* packed = sc_.get<float>((size_t)C * (C / groups) * k);
     launch_w2v2_pack_pos_weight(d_w, packed, C, groups, k, nullptr);
     launch_w2v2_pos_conv(d_x, packed, d_bias, d_y, nb, T, C, groups, k, d_lens, nullptr);
@@ -483,7 +303,7 @@ int sc_op_w2v2_pos_conv(const float* d_x, const float* d_w, const float* d_bias,
 int sc_op_kmeans(const float* d_x, const float* d_centroids, int32_t rows, int32_t C, int32_t K, int32_t* d_idx) {
     SC_API_BEGIN
     SC_CHECK(d_x && d_centroids && d_idx && rows > 0 && C > 0 && C % 16 == 0 && K > 0, "sc_op_kmeans: bad argument (C must be a multiple of 16)");
-    OpBufs sc_;
+    OpScratch sc_;
     __half* w = sc_.get<__half>((size_t)K * 2 * C);
     float* b = sc_.get<float>(K);
     launch_w2v2_pack_centroids(d_centroids, C, K, w, b, nullptr);

@@ -67,8 +67,46 @@ def _tensor_descs(tensors: Dict[str, torch.Tensor]):
     return descs, keep
 
 
-class HipS2STModel:
+def _failed(lib, what: str) -> SeamlessHipError:
+    msg = lib.sc_last_error()
+    return SeamlessHipError(f"{what} failed: {msg.decode() if msg else '?'}")
+
+
+class _Handle:
+    """What the handle classes share: the library and the device, the load call with its error, and the free entry."""
+
+    _free = ""  # name of the entry that frees ``handle``
+
+    def _open_device(self, device: int) -> None:
+        self.lib = _lib.load_library()
+        self.device_index = int(device)
+        self.device = torch.device("cuda", self.device_index)
+        if not torch.cuda.is_available():
+            raise SeamlessHipError("no HIP device is visible; the HIP path has no CPU fallback")
+
+    def _load(self, entry: str, tensors: Dict[str, torch.Tensor], *cfg_args, what: Optional[str] = None) -> None:
+        """``handle = entry(tensors, n, *cfg_args, device)``; ``what`` names the entry in the error when it is not ``entry``."""
+        descs, keep = _tensor_descs(tensors)  # `keep` holds the converted tensors until the library has copied them
+        self.handle = getattr(self.lib, entry)(descs, len(tensors), *cfg_args, self.device_index)
+        if not self.handle:
+            raise _failed(self.lib, what or entry)
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            getattr(self.lib, self._free)(self.handle)
+            self.handle = None
+
+    def __del__(self) -> None:  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HipS2STModel(_Handle):
     """Weights of one UnitY2 (+ vocoder) model resident in one GPU's HBM."""
+
+    _free = "sc_free"
 
     def __init__(
         self,
@@ -78,12 +116,8 @@ class HipS2STModel:
         device: int = 0,
         monotonic_state_dict: Optional[Dict[str, torch.Tensor]] = None,
     ) -> None:
-        self.lib = _lib.load_library()
         self.cfg = cfg
-        self.device_index = int(device)
-        self.device = torch.device("cuda", self.device_index)
-        if not torch.cuda.is_available():
-            raise SeamlessHipError("no HIP device is visible; the HIP path has no CPU fallback")
+        self._open_device(device)
         has_t2u = any(k.startswith("t2u_model.") for k in unity_state_dict)
         self.has_text_encoder = any(k.startswith("text_encoder.layers.") for k in unity_state_dict)
         tensors: Dict[str, torch.Tensor] = {}
@@ -115,7 +149,6 @@ class HipS2STModel:
         if vocoder_state_dict is not None:
             for k, v in vocoder_state_dict.items():
                 tensors[k] = v  # dur_predictor.* included: sc_vocoder_durations (dur_prediction=True, translator.py:385-389)
-        descs, keep = _tensor_descs(tensors)  # `keep` holds the converted tensors until the library has copied them
         self.has_vocoder_dur_predictor = vocoder_state_dict is not None and any(
             ".dur_predictor." in k for k in vocoder_state_dict)
         ccfg = _lib.make_config(cfg, has_t2u=has_t2u, has_vocoder=vocoder_state_dict is not None,
@@ -127,12 +160,9 @@ class HipS2STModel:
         self.film_cond_dim = int(ext.film_cond_dim) if has_t2u else 0
         ext.film_cond_dim = self.film_cond_dim
         if ext.abi_version:
-            self.handle = self.lib.sc_load_ext(descs, len(tensors), C.byref(ccfg), C.byref(ext), self.device_index)
+            self._load("sc_load_ext", tensors, C.byref(ccfg), C.byref(ext), what="sc_load")
         else:
-            self.handle = self.lib.sc_load(descs, len(tensors), C.byref(ccfg), self.device_index)
-        if not self.handle:
-            msg = self.lib.sc_last_error()
-            raise SeamlessHipError(f"sc_load failed: {msg.decode() if msg else '?'}")
+            self._load("sc_load", tensors, C.byref(ccfg))
         self.prosody_encoder: Optional["HipProsodyEncoder"] = None
         if getattr(cfg, "prosody_encoder", None) is not None and has_t2u:
             if not prosody_sd:
@@ -150,8 +180,7 @@ class HipS2STModel:
         child.device_index, child.device = self.device_index, self.device
         child.handle = self.lib.sc_fork(self.handle)
         if not child.handle:
-            msg = self.lib.sc_last_error()
-            raise SeamlessHipError(f"sc_fork failed: {msg.decode() if msg else '?'}")
+            raise _failed(self.lib, "sc_fork")
         child.hop = self.hop
         child._has_nar_tables = self._has_nar_tables
         child.has_text_encoder = self.has_text_encoder
@@ -164,17 +193,6 @@ class HipS2STModel:
     def t2u_last_launches(self) -> int:
         """Launch calls of the last ``t2u_nar`` behind the T2U encoder (``sc_op_t2u_last_launches``)."""
         return int(self.lib.sc_op_t2u_last_launches(self.handle))
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            self.lib.sc_free(self.handle)
-            self.handle = None
-
-    def __del__(self) -> None:  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ---- decode engine (sc_engine_*) --------------------------------------------------------------------- #
     def engine_expect(self, n_rows: int) -> None:
@@ -484,11 +502,13 @@ class HipS2STModel:
         return {"t2u_rows_computed": a.value, "t2u_rows_padded": b.value, "vocoder_rows_computed": c.value}
 
 
-class DecodeEngine:
+class DecodeEngine(_Handle):
     """One greedy decoder-step chain per GPU shared by every handle it is attached to (``sc_engine_*``, include/
     seamless_hip.h): rows of all passes in flight share the slots of one captured step, each at its own position; finished
     rows leave at once and waiting rows take their slots.  Per row the results are those of ``generate_text`` without an
     engine, bit for bit.  Not part of the reference API (the reference generates one batch at a time)."""
+
+    _free = "sc_engine_free"
 
     def __init__(self, model: HipS2STModel, max_len: int, s_enc: int, slots: int = 64, rows: int = 0, min_seq_len: int = 1,
                  unk_penalty: float = 0.0, poll: int = 4, low_water: int = 0, max_wait_ms: int = 100, use_graph: bool = True) -> None:
@@ -502,8 +522,7 @@ class DecodeEngine:
                          poll=int(poll) or 4, low_water=int(low_water), max_wait_ms=int(max_wait_ms) or 100, use_graph=bool(use_graph))
         self.handle = self.lib.sc_engine_create(model.handle, C.byref(o))
         if not self.handle:
-            msg = self.lib.sc_last_error()
-            raise SeamlessHipError(f"sc_engine_create failed: {msg.decode() if msg else '?'}")
+            raise _failed(self.lib, "sc_engine_create")
         self._attached: List[HipS2STModel] = []
 
     def attach(self, model: HipS2STModel) -> None:
@@ -524,14 +543,7 @@ class DecodeEngine:
         if getattr(self, "handle", None):
             for m in list(self._attached):
                 self.detach(m)
-            self.lib.sc_engine_free(self.handle)
-            self.handle = None
-
-    def __del__(self) -> None:  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
 def postprocess_alignment(durations: np.ndarray, text_lens: Sequence[int], feat_lens: Sequence[int], reduction_factor: int) -> np.ndarray:
@@ -549,39 +561,22 @@ def postprocess_alignment(durations: np.ndarray, text_lens: Sequence[int], feat_
     return dur
 
 
-class HipAligner:
+class HipAligner(_Handle):
     """The UnitY2 forced aligner resident in one GPU's HBM (``sc_aligner_*``): a handle of its own, next to any
     :class:`HipS2STModel` on the same device."""
 
+    _free = "sc_aligner_free"
+
     def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], device: int = 0) -> None:
-        self.lib = _lib.load_library()
         self.cfg = cfg
-        self.device_index = int(device)
-        self.device = torch.device("cuda", self.device_index)
-        if not torch.cuda.is_available():
-            raise SeamlessHipError("no HIP device is visible; the HIP path has no CPU fallback")
-        descs, keep = _tensor_descs(state_dict)
+        self._open_device(device)
         c = _lib.sc_aligner_config()
         c.abi_version = _lib.SC_ABI_VERSION
         c.model_dim, c.feat_dim = int(cfg.model_dim), int(cfg.feat_dim)
         c.text_layers, c.feat_layers = int(cfg.num_text_layers), int(cfg.num_feat_layers)
         c.temperature, c.reduction_factor = float(cfg.temperature), int(cfg.reduction_factor)
         c.char_vocab_size, c.unit_vocab_size = int(cfg.char_vocab_size), int(cfg.unit_vocab_size)
-        self.handle = self.lib.sc_aligner_load(descs, len(state_dict), C.byref(c), self.device_index)
-        if not self.handle:
-            msg = self.lib.sc_last_error()
-            raise SeamlessHipError(f"sc_aligner_load failed: {msg.decode() if msg else '?'}")
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            self.lib.sc_aligner_free(self.handle)
-            self.handle = None
-
-    def __del__(self) -> None:  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._load("sc_aligner_load", state_dict, C.byref(c))
 
     def align(self, text_ids: Sequence[Sequence[int]], unit_ids: Sequence[Sequence[int]],
               return_lprob: bool = False) -> Tuple[np.ndarray, Optional[torch.Tensor]]:
@@ -618,16 +613,14 @@ def fold_weight_norm_dim2(weight_g: torch.Tensor, weight_v: torch.Tensor) -> tor
     return (g * v / v.pow(2).sum(dim=(0, 1), keepdim=True).sqrt()).to(torch.float32)
 
 
-class HipUnitExtractor:
+class HipUnitExtractor(_Handle):
     """wav2vec 2.0 encoder + k-means table resident in one GPU's HBM (``sc_unit_extractor_*``): a handle of its own."""
 
+    _free = "sc_unit_extractor_free"
+
     def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], centroids: torch.Tensor, device: int = 0) -> None:
-        self.lib = _lib.load_library()
         self.cfg = cfg
-        self.device_index = int(device)
-        self.device = torch.device("cuda", self.device_index)
-        if not torch.cuda.is_available():
-            raise SeamlessHipError("no HIP device is visible; the HIP path has no CPU fallback")
+        self._open_device(device)
         if centroids.dim() != 2 or centroids.shape[0] != cfg.model_dim:
             raise ValueError(f"centroids must be [model_dim={cfg.model_dim}, K] (the reference's transposed table), got {tuple(centroids.shape)}")
         sd = {k: v for k, v in state_dict.items() if k.startswith(("encoder_frontend.", "encoder.layers."))}
@@ -638,7 +631,6 @@ class HipUnitExtractor:
         sd = {k: (v.to(torch.float16) if k.endswith(keep16) and not k.startswith(pre) and ".layers.0.conv." not in k else v.to(torch.float32))
               for k, v in sd.items()}
         sd["kmeans.centroids"] = centroids.detach().to(torch.float32)
-        descs, keep = _tensor_descs(sd)
         c = _lib.sc_unit_extractor_config()
         c.abi_version = _lib.SC_ABI_VERSION
         c.model_dim, c.heads, c.ffn_dim, c.layers = int(cfg.model_dim), int(cfg.num_heads), int(cfg.ffn_dim), int(cfg.num_layers)
@@ -648,21 +640,7 @@ class HipUnitExtractor:
         c.pos_conv_kernel, c.pos_conv_groups = int(cfg.pos_conv_kernel), int(cfg.pos_conv_groups)
         c.num_centroids = int(centroids.shape[1])
         self._c = c
-        self.handle = self.lib.sc_unit_extractor_load(descs, len(sd), C.byref(c), self.device_index)
-        if not self.handle:
-            msg = self.lib.sc_last_error()
-            raise SeamlessHipError(f"sc_unit_extractor_load failed: {msg.decode() if msg else '?'}")
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            self.lib.sc_unit_extractor_free(self.handle)
-            self.handle = None
-
-    def __del__(self) -> None:  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._load("sc_unit_extractor_load", sd, C.byref(c))
 
     def extract(self, waves: Sequence[np.ndarray], out_layer_idx: int, return_features: bool = False):
         """Ragged batch of mono fp32 waveforms -> (units (n, longest) int64 zero-padded, frames (n,), layer output
@@ -684,18 +662,16 @@ class HipUnitExtractor:
         return units.astype(np.int64), frames, feats
 
 
-class HipProsodyEncoder:
+class HipProsodyEncoder(_Handle):
     """ECAPA-TDNN prosody encoder resident in one GPU's HBM (``sc_prosody_encoder_*``): a handle of its own."""
+
+    _free = "sc_prosody_encoder_free"
 
     MAX_FRAMES = 4096
 
     def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], device: int = 0) -> None:
-        self.lib = _lib.load_library()
         self.cfg = cfg
-        self.device_index = int(device)
-        self.device = torch.device("cuda", self.device_index)
-        if not torch.cuda.is_available():
-            raise SeamlessHipError("no HIP device is visible; the HIP path has no CPU fallback")
+        self._open_device(device)
         if any(int(g) != 1 for g in cfg.groups):
             raise ValueError(f"groups={tuple(cfg.groups)}: only groups of 1 (arch base) are built")
         if not (len(cfg.channels) == len(cfg.kernel_sizes) == len(cfg.dilations)) or not 3 <= len(cfg.channels) <= 8:
@@ -704,7 +680,6 @@ class HipProsodyEncoder:
 
         sd = strip_ecapa_prefix(state_dict)
         sd = {k: (v.to(torch.float16) if k.endswith(".weight") and v.dim() == 3 else v.to(torch.float32)) for k, v in sd.items()}
-        descs, keep = _tensor_descs(sd)
         c = _lib.sc_prosody_encoder_config()
         c.abi_version = _lib.SC_ABI_VERSION
         c.input_dim, c.embed_dim, c.res2net_scale = int(cfg.input_dim), int(cfg.embed_dim), int(cfg.res2net_scale)
@@ -714,21 +689,7 @@ class HipProsodyEncoder:
             c.channels[i], c.kernel_sizes[i], c.dilations[i] = int(cfg.channels[i]), int(cfg.kernel_sizes[i]), int(cfg.dilations[i])
         self._c = c
         self._lock = threading.Lock()
-        self.handle = self.lib.sc_prosody_encoder_load(descs, len(sd), C.byref(c), self.device_index)
-        if not self.handle:
-            msg = self.lib.sc_last_error()
-            raise SeamlessHipError(f"sc_prosody_encoder_load failed: {msg.decode() if msg else '?'}")
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            self.lib.sc_prosody_encoder_free(self.handle)
-            self.handle = None
-
-    def __del__(self) -> None:  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._load("sc_prosody_encoder_load", sd, C.byref(c))
 
     def encode(self, fbank: torch.Tensor, lens=None, gcmvn_mean: Optional[torch.Tensor] = None, gcmvn_std: Optional[torch.Tensor] = None) -> torch.Tensor:
         """fbank (B, T, input_dim) on the device, lens (B,) or None -> (B, embed_dim) float32 on the device, L2-normalised rows.
@@ -763,9 +724,11 @@ class HipProsodyEncoder:
         return int(self.lib.sc_op_prosody_last_launches(self.handle))
 
 
-class HipPretssel:
+class HipPretssel(_Handle):
     """Acoustic model of the PRETSSEL vocoder resident in one GPU's HBM (``sc_pretssel_*``): a handle of its own.  The prosody
     encoder is a separate handle (:class:`HipProsodyEncoder`); this one takes its vector."""
+
+    _free = "sc_pretssel_free"
 
     _FP32_2D = ("embed_lang.weight", "_predictor.proj.weight", "embed_pitch.weight", "embed_energy.weight")
 
@@ -786,12 +749,8 @@ class HipPretssel:
         return sd
 
     def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], gcmvn_mean, gcmvn_std, device: int = 0) -> None:
-        self.lib = _lib.load_library()
         self.cfg = cfg
-        self.device_index = int(device)
-        self.device = torch.device("cuda", self.device_index)
-        if not torch.cuda.is_available():
-            raise SeamlessHipError("no HIP device is visible; the HIP path has no CPU fallback")
+        self._open_device(device)
         sd = self.select_tensors(cfg, state_dict)
         sd["pos_encoder.freqs"] = sinusoidal_freqs(cfg.max_seq_len, cfg.model_dim, cfg.pad_idx)
         mean = torch.as_tensor(gcmvn_mean, dtype=torch.float64).reshape(-1).to(torch.float32)
@@ -799,7 +758,6 @@ class HipPretssel:
         if mean.numel() != cfg.mel_dim or std.numel() != cfg.mel_dim:
             raise ValueError(f"gcmvn statistics must hold {cfg.mel_dim} values")
         sd["gcmvn_mean"], sd["gcmvn_std"] = mean, std
-        descs, keep = _tensor_descs(sd)
         c = _lib.sc_pretssel_config()
         c.abi_version = _lib.SC_ABI_VERSION
         c.model_dim, c.num_heads, c.enc_layers, c.dec_layers = int(cfg.model_dim), int(cfg.num_heads), int(cfg.encoder_layers), int(cfg.decoder_layers)
@@ -810,21 +768,7 @@ class HipPretssel:
         c.post_layers, c.post_dim, c.post_kernel = int(cfg.post_layers), int(cfg.post_dim), int(cfg.post_kernel)
         c.upsample_delta = float(cfg.upsample_delta)
         self._c = c
-        self.handle = self.lib.sc_pretssel_load(descs, len(sd), C.byref(c), self.device_index)
-        if not self.handle:
-            msg = self.lib.sc_last_error()
-            raise SeamlessHipError(f"sc_pretssel_load failed: {msg.decode() if msg else '?'}")
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            self.lib.sc_pretssel_free(self.handle)
-            self.handle = None
-
-    def __del__(self) -> None:  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._load("sc_pretssel_load", sd, C.byref(c))
 
     def mel(self, tokens, tok_lens, durations, lang_index: int, prosody: torch.Tensor) -> Tuple[torch.Tensor, np.ndarray]:
         """tokens / durations (B, S) host integers (rows padded behind tok_lens), prosody (B, film_cond_dim - lang_embed_dim) on the
@@ -861,9 +805,11 @@ class HipPretssel:
         return int(self.lib.sc_op_pretssel_last_launches(self.handle))
 
 
-class HipPretsselWave:
+class HipPretsselWave(_Handle):
     """Waveform generator of the PRETSSEL vocoder resident in one GPU's HBM (``sc_pretssel_wave*``): a handle of its own, next to
     :class:`HipPretssel`, which makes the mel spectrogram it consumes."""
+
+    _free = "sc_pretssel_wave_free"
 
     @staticmethod
     def tensor_names(cfg) -> List[str]:
@@ -888,7 +834,6 @@ class HipPretsselWave:
         return sd
 
     def __init__(self, cfg, state_dict: Dict[str, torch.Tensor], device: int = 0) -> None:
-        self.lib = _lib.load_library()
         self.cfg = cfg
         w = cfg.waveform
         if len(w.ratios) != 4 or len(w.resblock_kernel_sizes) != 3 or any(len(d) != 3 for d in w.resblock_dilation_sizes):
@@ -898,11 +843,7 @@ class HipPretsselWave:
         if w.kernel_size != 7 or w.residual_kernel_size != 3:
             raise ValueError("the waveform generator is built for kernel_size 7 and residual_kernel_size 3")
         sd = self.select_tensors(cfg, state_dict)
-        self.device_index = int(device)
-        self.device = torch.device("cuda", self.device_index)
-        if not torch.cuda.is_available():
-            raise SeamlessHipError("no HIP device is visible; the HIP path has no CPU fallback")
-        descs, keep = _tensor_descs(sd)
+        self._open_device(device)
         c = _lib.sc_pretssel_wave_config()
         c.abi_version = _lib.SC_ABI_VERSION
         c.mel_dim, c.post_layers = int(cfg.mel_dim), int(cfg.post_layers)
@@ -918,21 +859,7 @@ class HipPretsselWave:
             c.ratios[i] = int(w.ratios[i])
         self._c = c
         self.hop = w.hop
-        self.handle = self.lib.sc_pretssel_wave_load(descs, len(sd), C.byref(c), self.device_index)
-        if not self.handle:
-            msg = self.lib.sc_last_error()
-            raise SeamlessHipError(f"sc_pretssel_wave_load failed: {msg.decode() if msg else '?'}")
-
-    def close(self) -> None:
-        if getattr(self, "handle", None):
-            self.lib.sc_pretssel_wave_free(self.handle)
-            self.handle = None
-
-    def __del__(self) -> None:  # pragma: no cover
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._load("sc_pretssel_wave_load", sd, C.byref(c))
 
     def wave(self, mel: torch.Tensor, frame_lens, two_plane: bool = False, probes: bool = False):
         """mel (B, T_max, mel_dim) on the device, frame_lens (B,) -> one float32 tensor (frames_i * hop,) per item, each item
