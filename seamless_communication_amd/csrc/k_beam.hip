@@ -6,7 +6,9 @@
 //   log-softmax (row max + log-sum-exp by block reductions), the generation step rules
 //   (`_tweak_lprobs`: EOS masked before min_seq_len, only EOS at the length limit, PAD never, UNK
 //   penalty), + the beam's cumulative score, then the best K = 2*beam candidates over the flattened
-//   (beam, token) space (first step: beam 0 only), best first, ties to the lower flattened index.
+//   (beam, token) space (first step: beam 0 only), best first, ties to the lower flattened index.  The order is total and
+//   that of torch.topk (order_key: NaN above +inf), every (beam, token) pair is a candidate whatever its value, so the K
+//   stored indices are always real ones; a row whose log-sum-exp is NaN gives NaN candidates (candidate_value).
 //   HBM traffic: each logit row is read three times (max, sum, scan), L2 resident (1 MB per row).
 //   Step processor (NGramRepeatBlockProcessor): the tokens that would complete an n-gram already in the row's
 //   sequence (read from the device-resident sequence buffer) are overwritten with -inf in the logit row AFTER
@@ -44,15 +46,17 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__device__ __forceinline__ bool better(float v, int i, float w, int j) { return v > w || (v == w && i < j); }
-
-// Order-preserving map of a non-NaN fp32 value to int32 (-0 and +0 map to the same key; -inf to the smallest key) and back.
+// Order-preserving map of an fp32 value to int32 (-0 and +0 map to the same key; -inf to the smallest key; a NaN of any sign
+// and payload to ONE key above that of +inf - the order of torch.topk, which the reference's search uses) and back (a NaN
+// comes back as the quiet NaN 0x7fc00000).  Every candidate path (plain, banned, chunked) orders by these keys.
 // beam_candidates_kernel orders its per-thread lists by these keys: with fp32 comparisons in that insertion network, the
 // compiled kernel dropped every -inf candidate of a thread whose list had not yet taken a finite value (a forced-EOS step:
 // the list filled with another thread's -inf entries out of index order, or with the 0x7fffffff sentinel), although the
-// source and its IR order them correctly.  Integer keys give the same total order as better() without float compares.
+// source and its IR order them correctly.  Integer keys give a total order (NaN included) without float compares.
+constexpr int KEY_NAN = 0x7fc00000;
 __device__ __forceinline__ int order_key(float v) {
     const int k = __float_as_int(v + 0.f);  // -0 + 0 = +0
+    if ((k & 0x7fffffff) > 0x7f800000) return KEY_NAN;
     return k >= 0 ? k : k ^ 0x7fffffff;
 }
 __device__ __forceinline__ float key_value(int k) { return __int_as_float(k >= 0 ? k : k ^ 0x7fffffff); }
@@ -78,6 +82,17 @@ __device__ __forceinline__ void banned_block_row(float* row, int V, const int* _
         const int t = bl.tokens[o + P];
         if (same && t >= 0 && t < V) row[t] = -INFINITY;
     }
+}
+
+// Value of the candidate (row, token t): log-softmax of the logit x (l: the row's log-sum-exp), the generation step rules, + the
+// beam's cumulative score.  A token that a rule excludes (EOS before min_seq_len, everything but EOS at the length limit, PAD)
+// is -inf whatever the row and the score hold: a beam that carries NaN still never emits PAD and still ends at the limit.
+__device__ __forceinline__ float candidate_value(float x, float l, float base, int t, int no_eos, int force_eos, int pad_idx, int eos_idx,
+                                                 int unk_idx, float unk_penalty) {
+    float lp = x - l;
+    if (t == unk_idx) lp -= unk_penalty;
+    const bool excluded = (no_eos && t == eos_idx) || (force_eos && t != eos_idx) || t == pad_idx;
+    return excluded ? -INFINITY : lp + base;
 }
 
 template <bool BANNED>
@@ -145,12 +160,7 @@ __device__ __forceinline__ void beam_candidates_body(float* logits, int64_t ld, 
         const float base = cum[(int64_t)n * beams + b];
         const float l = lse[b];
         for (int t = tid; t < V; t += 256) {
-            float lp = row[t] - l;
-            if (no_eos && t == eos_idx) lp = -INFINITY;
-            if (force_eos && t != eos_idx) lp = -INFINITY;
-            if (t == pad_idx) lp = -INFINITY;
-            if (t == unk_idx) lp -= unk_penalty;
-            const int v = order_key(lp + base);
+            const int v = order_key(candidate_value(row[t], l, base, t, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty));
             const int idx = b * V + t;
             if (better_key(v, idx, wv, wi)) {
                 // insertion into the sorted list (K <= 16, fully unrolled compare-and-shift)
@@ -272,15 +282,16 @@ __global__ __launch_bounds__(256) void beam_lse_partial_kernel(const float* __re
         for (int u = 0; u < 8; ++u) mx = fmaxf(mx, v[u]);
     }
     mx = block_reduce_max(mx, red);
+    // fmaxf drops NaN: a chunk of -inf and NaN only has mx = -inf; its sum is taken around 0 instead (exp(-inf) = 0, exp(NaN) =
+    // NaN), so that a NaN anywhere in the row reaches the row's log-sum-exp as it does in the single-workgroup search
+    const float shift = mx > -INFINITY ? mx : 0.f;
     float sm = 0.f;
-    if (mx > -INFINITY) {
-        for (int i = start + tid; i < end; i += 256 * 8) {  // the chunk (32 KB) is cache resident now
-            float v[8];
+    for (int i = start + tid; i < end; i += 256 * 8) {  // the chunk (32 KB) is cache resident now
+        float v[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = (i + 256 * u < end) ? row[i + 256 * u] : -INFINITY;
+        for (int u = 0; u < 8; ++u) v[u] = (i + 256 * u < end) ? row[i + 256 * u] : -INFINITY;
 #pragma unroll
-            for (int u = 0; u < 8; ++u) sm += expf(v[u] - mx);  // exp(-inf) = 0 for the slots behind the chunk
-        }
+        for (int u = 0; u < 8; ++u) sm += expf(v[u] - shift);  // exp(-inf) = 0 for the slots behind the chunk
     }
     sm = block_reduce_sum(sm, red);
     if (tid == 0) part[(int64_t)r * BEAM_CH + c] = make_float2(mx, sm);
@@ -324,13 +335,13 @@ __global__ __launch_bounds__(256) void step_processors_kernel(float* logits, int
     banned_block_row(row, V, seq, S, bl, s_tail);
 }
 
-// block-wide arg-best of one (value, flattened index) per thread; every thread returns the winner
-__device__ __forceinline__ void block_argbest(float& v, int& i, float* s_val, int* s_idx) {
+// block-wide arg-best of one (order_key(value), flattened index) per thread; every thread returns the winner
+__device__ __forceinline__ void block_argbest(int& v, int& i, int* s_val, int* s_idx) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o);
+        const int ov = __shfl_xor(v, o);
         const int oi = __shfl_xor(i, o);
-        if (better(ov, oi, v, i)) {
+        if (better_key(ov, oi, v, i)) {
             v = ov;
             i = oi;
         }
@@ -344,7 +355,7 @@ __device__ __forceinline__ void block_argbest(float& v, int& i, float* s_val, in
     i = s_idx[0];
 #pragma unroll
     for (int w = 1; w < 4; ++w)
-        if (better(s_val[w], s_idx[w], v, i)) {
+        if (better_key(s_val[w], s_idx[w], v, i)) {
             v = s_val[w];
             i = s_idx[w];
         }
@@ -352,17 +363,18 @@ __device__ __forceinline__ void block_argbest(float& v, int& i, float* s_val, in
 }
 
 // K rounds of "every thread offers the best of its not yet taken elements, the block picks one" over EPT elements per
-// thread held in registers (val / idx).  Same order as the sorted-list search of beam_candidates_kernel: value first, ties
-// to the lower flattened index, -inf entries with a real index are candidates too (they fill the list on a forced-EOS step).
+// thread held in registers (val: order_key of the value, idx).  Same order as the sorted-list search of beam_candidates_kernel:
+// key first (NaN above +inf), ties to the lower flattened index, -inf entries with a real index are candidates too (they fill
+// the list on a forced-EOS step).
 template <int EPT>
-__device__ __forceinline__ void block_select_k(const float (&val)[EPT], const int (&idx)[EPT], unsigned taken, int K, float* s_val, int* s_idx,
+__device__ __forceinline__ void block_select_k(const int (&val)[EPT], const int (&idx)[EPT], unsigned taken, int K, int* s_val, int* s_idx,
                                                float* out_val, int* out_idx) {
     for (int r = 0; r < K; ++r) {
-        float bv = -INFINITY;
+        int bv = order_key(-INFINITY);
         int bi = 0x7fffffff, be = -1;
 #pragma unroll
         for (int e = 0; e < EPT; ++e)
-            if (!((taken >> e) & 1u) && better(val[e], idx[e], bv, bi)) {
+            if (!((taken >> e) & 1u) && better_key(val[e], idx[e], bv, bi)) {
                 bv = val[e];
                 bi = idx[e];
                 be = e;
@@ -370,7 +382,7 @@ __device__ __forceinline__ void block_select_k(const float (&val)[EPT], const in
         const int mine = bi;
         block_argbest(bv, bi, s_val, s_idx);
         if (threadIdx.x == 0) {
-            out_val[r] = bv;
+            out_val[r] = key_value(bv);
             out_idx[r] = bi;
         }
         if (mine == bi && be >= 0) taken |= 1u << be;  // flattened indices are unique: exactly one thread owns the winner
@@ -382,7 +394,7 @@ __global__ __launch_bounds__(256) void beam_topk_partial_kernel(const float* __r
                                                                 int pad_idx, int eos_idx, int unk_idx, float unk_penalty, int K,
                                                                 const float2* __restrict__ part, float* __restrict__ pval,
                                                                 int* __restrict__ pidx, const int* __restrict__ d_rows) {
-    __shared__ float s_val[4];
+    __shared__ int s_val[4];
     __shared__ int s_idx[4];
     constexpr int EPT = 32;  // elements per thread: chunks of at most 8192 logits
     const int c = blockIdx.x, r = blockIdx.y, tid = threadIdx.x;
@@ -404,49 +416,45 @@ __global__ __launch_bounds__(256) void beam_topk_partial_kernel(const float* __r
     float sm = 0.f;
     for (int q = 0; q < BEAM_CH; ++q) {
         const float2 p = part[(int64_t)r * BEAM_CH + q];
-        if (p.x > -INFINITY) sm += p.y * expf(p.x - m);
+        sm += p.x > -INFINITY ? p.y * expf(p.x - m) : p.y;  // a chunk without a number: 0, or NaN when it holds one
     }
     const float l = m + logf(sm);
     const float base = cum[r];
     const float* row = logits + (int64_t)r * ld;
-    float val[EPT];
+    float x[EPT];
+    int val[EPT];
     int idx[EPT];
     unsigned taken = 0;
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {
         const int t = start + tid + 256 * e;
-        val[e] = (t < end) ? row[t] : -INFINITY;
+        x[e] = (t < end) ? row[t] : -INFINITY;
         idx[e] = b * V + t;
         if (t >= end) taken |= 1u << e;
     }
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {
         const int t = start + tid + 256 * e;
-        float lp = val[e] - l;
-        if (no_eos && t == eos_idx) lp = -INFINITY;
-        if (force_eos && t != eos_idx) lp = -INFINITY;
-        if (t == pad_idx) lp = -INFINITY;
-        if (t == unk_idx) lp -= unk_penalty;
-        val[e] = lp + base;
+        val[e] = order_key(candidate_value(x[e], l, base, t, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty));
     }
     block_select_k<EPT>(val, idx, taken, K, s_val, s_idx, out_val, out_idx);
 }
 
 __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict__ pval, const int* __restrict__ pidx, int entries, int K,
                                                          float* __restrict__ cand_val, int* __restrict__ cand_idx, const int* __restrict__ d_slots) {
-    __shared__ float s_val[4];
+    __shared__ int s_val[4];
     __shared__ int s_idx[4];
     constexpr int EPT = 16;  // beams x 32 chunks x K <= 16 x 32 x 16 = 8192 entries... the launcher checks entries <= 256 * EPT
     const int n = blockIdx.x, tid = threadIdx.x;
     if (d_slots && n >= *d_slots) return;  // an idle slot
-    float val[EPT];
+    int val[EPT];
     int idx[EPT];
     unsigned taken = 0;
 #pragma unroll
     for (int e = 0; e < EPT; ++e) {
         const int q = tid + 256 * e;
         const bool ok = q < entries;
-        val[e] = ok ? pval[(int64_t)n * entries + q] : -INFINITY;
+        val[e] = order_key(ok ? pval[(int64_t)n * entries + q] : -INFINITY);
         idx[e] = ok ? pidx[(int64_t)n * entries + q] : 0x7fffffff;
         if (!ok || idx[e] == 0x7fffffff) taken |= 1u << e;  // empty slots (first step: beams > 0) are not candidates
     }

@@ -22,7 +22,12 @@
 //         row: the other rows of the launch keep their bits;
 //       - the row arg-max kernels store an index inside the row whatever the
 //         row holds (argmax_stored_index below); a NaN row's log-probability
-//         is NaN.  The beam-search candidate kernels are not covered;
+//         is NaN.  The beam-search candidate kernels (plain, banned, chunked)
+//         store only indices of real (beam, token) pairs and order them as
+//         torch.topk does: NaN of any sign above +inf, then descending value,
+//         ties (among NaNs too) to the lower flattened index; a token that a
+//         step rule excludes is -inf even in a NaN row; the host picks the
+//         best finished hypothesis in the same order (k_beam.hip order_key);
 //       - the fp32 FMA GEMV (launch_gemv) does not split: exact fp32 x fp16
 //         at every scale, no overflow at 65520.
 #pragma once

@@ -1900,9 +1900,12 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
     int longest = 0;
     for (int u = 0; u < n; ++u) {
         SC_CHECK(fin_count[u] > 0, "sc_generate_text: beam search returned no hypothesis for item %d", u);
+        // the order of the candidate search (k_beam.hip order_key): NaN first, then the higher score, ties to the earlier one
         int best = 0;
-        for (int i = 1; i < fin_count[u]; ++i)
-            if (fin_score[u * B + i] > fin_score[u * B + best]) best = i;
+        for (int i = 1; i < fin_count[u]; ++i) {
+            const float s = fin_score[u * B + i], t = fin_score[u * B + best];
+            if (std::isnan(t) ? false : (std::isnan(s) || s > t)) best = i;
+        }
         const int len = fin_len[u * B + best];
         const int32_t* hs = &fin_seq[(size_t)(u * B + best) * max_len];
         for (int t = 0; t < max_len; ++t) h_out_ids[(size_t)u * max_len + t] = t < len ? hs[t] : cfg.pad_idx;
