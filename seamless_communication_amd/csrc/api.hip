@@ -157,6 +157,8 @@ int sc_set_nar_tables(sc_model* m, int32_t vocab, const int32_t* tok_len, const 
 int sc_fbank(sc_model* m, const float* d_wav, int32_t n, int64_t wav_stride, const int32_t* h_num_samples,
              int32_t standardize, float* d_out, int32_t t_rows, int32_t* h_out_frames) {
     SC_API_BEGIN
+    // a batch without a single frame has a 0-row output, whose pointer may well be null: name the cause
+    SC_CHECK(n > 0 && t_rows > 0, "sc_fbank: empty batch");
     SC_CHECK(m && d_wav && h_num_samples && d_out, "sc_fbank: null argument");
     SC_HIP(hipSetDevice(m->m.device));
     run_fbank(m->m, d_wav, n, wav_stride, h_num_samples, standardize, d_out, t_rows, h_out_frames);
@@ -168,6 +170,7 @@ int32_t sc_encoder_out_len(const sc_model* m, int32_t t_frames) { return m ? enc
 int sc_fbank_rate(sc_model* m, const float* d_wav, int32_t n, int64_t wav_stride, const int32_t* h_num_samples, int32_t sample_rate,
                   int32_t standardize, float* d_out, int32_t t_rows, int32_t* h_out_frames) {
     SC_API_BEGIN
+    SC_CHECK(n > 0 && t_rows > 0, "sc_fbank: empty batch");
     SC_CHECK(m && d_wav && h_num_samples && d_out, "sc_fbank_rate: null argument");
     SC_HIP(hipSetDevice(m->m.device));
     run_fbank(m->m, d_wav, n, wav_stride, h_num_samples, standardize, d_out, t_rows, h_out_frames, sample_rate);

@@ -23,6 +23,14 @@ __device__ __forceinline__ float block_sum_256(float v, float* s_red) {
     return r;
 }
 
+// log(max(e, FLT_EPSILON)) of feature-fbank.cc:105.  The floor is written as the constant the reference's host logf returns,
+// the correctly rounded log(2^-23): the device logf is one float step below it there, and digital silence fills whole
+// stretches of an utterance with this one value.  A NaN energy fails the comparison and stays NaN.
+static constexpr float FBANK_FLT_EPS = 1.1920928955078125e-07f;
+static constexpr float FBANK_LOG_FLT_EPS = -15.9423847198486328125f;
+
+__device__ __forceinline__ float floored_log(float e) { return e < FBANK_FLT_EPS ? FBANK_LOG_FLT_EPS : logf(e); }
+
 // consts layout: window[400] | melT[256][80] | tw_cos[256] | tw_sin[256]
 __global__ __launch_bounds__(256) void fbank_kernel(const float* __restrict__ wav, int64_t wav_stride,
                                                     const int* __restrict__ num_samples,
@@ -99,7 +107,7 @@ __global__ __launch_bounds__(256) void fbank_kernel(const float* __restrict__ wa
         for (int k = 0; k < 256; ++k) e = fmaf(melT[k * NBINS + tid], s_x[k], e);
         // std::max(e, FLT_EPS) of feature-fbank.cc:105 keeps a NaN energy (corrupted audio must stay visible to
         // the caller's NaN filter, cli/m4t/evaluate/evaluate.py:278-289); fmaxf would replace it by the floor
-        orow[tid] = logf(e < 1.1920928955078125e-07f ? 1.1920928955078125e-07f : e);
+        orow[tid] = floored_log(e);
     }
 }
 
@@ -187,7 +195,7 @@ __global__ __launch_bounds__(256) void fbank_any_kernel(const float* __restrict_
     if (tid < NBINS) {
         float e = 0.f;
         for (int k = 0; k < HALF; ++k) e = fmaf(melT[k * NBINS + tid], s_x[k], e);
-        orow[tid] = logf(e < 1.1920928955078125e-07f ? 1.1920928955078125e-07f : e);
+        orow[tid] = floored_log(e);
     }
 }
 
