@@ -27,11 +27,19 @@ or scripted models):
     t2u(features, token_ids, duration_factor) -> (units, durations per text position)
     vocode(units, lang, spkr) -> waveform
 
+and, for the expressive chains (the last stage is the PRETSSEL vocoder, conditioned on everything heard so far):
+
+    expressive_card() -> (languages, sample rate)              of the PRETSSEL vocoder; raises when the backend has none
+    reset_expressive()                                         a new session: the prosody history starts over
+    speak_expressive(heard_samples, units, lang) -> waveform   all samples heard since the reset + one unit chunk
+
 Behaviour notes carry the reference location they were derived from as (file:line) under streaming/agents/.
 """
 from __future__ import annotations
 
+import copy
 import enum
+import logging
 from argparse import Namespace
 from dataclasses import dataclass
 from typing import Any, Callable, Iterable, List, Optional, Sequence, Set, Tuple
@@ -43,13 +51,16 @@ from torch import Tensor
 from .simul import (Action, AgentPipeline, AgentStates, GenericAgent, ReadAction, Segment, SpeechSegment, TextSegment,
                     WriteAction)
 
+logger = logging.getLogger(__name__)
+
 SHIFT_SIZE = 10
 WINDOW_SIZE = 25
 SAMPLE_RATE = 16000
 FEATURE_DIM = 80
 
 # option name -> default; grouped by the stage that reads it.  The values are the reference's argparse defaults
-# (tests/test_streaming_policy_cpu.py::test_default_args_equal_the_reference_argparse_defaults reads them from its source).
+# (tests/test_streaming_policy_cpu.py::test_default_args_equal_the_reference_argparse_defaults reads them from its source;
+# the expressive stages' in tests/test_seamless_streaming_policy_cpu.py; `expr_vocoder_name` is required there, so None here).
 _OPTION_DEFAULTS = {
     "framing": dict(shift_size=SHIFT_SIZE, window_size=WINDOW_SIZE, sample_rate=SAMPLE_RATE, feature_dim=FEATURE_DIM,
                     denormalize=False),
@@ -58,6 +69,7 @@ _OPTION_DEFAULTS = {
                  tgt_lang="eng", decision_threshold=0.5, decision_method="min", p_choose_start_layer=0, block_ngrams=False),
     "units": dict(min_unit_chunk_size=50, d_factor=1.0),
     "vocoder": dict(vocoder_speaker_id=-1),
+    "expressive": dict(vocoder_name="vocoder_pretssel", upstream_idx=0, expressive=False, expr_vocoder_name=None),
     "detok": dict(detokenize_only=True),
 }
 
@@ -187,13 +199,41 @@ class SampleRing:
         return out
 
 
-class FeatureStates(StageStates):
-    """`source` keeps only the most recent waveform chunk; older samples live in the ring as far as they are still needed."""
+class HeardSamples:
+    """Every sample since the last reset in ONE growing float32 array: `extend` appends (capacity doubles when a chunk does not
+    fit), `view` is a window on the array, not a copy.  The expressive vocoder stage reads it through `upstream_states`: the
+    reference keeps a list of chunk lists there and flattens it on every call (pretssel_vocoder.py:99-104)."""
 
-    FIELDS = {"ring": None}
+    def __init__(self, capacity: int = 1 << 16) -> None:
+        self._buf = np.zeros(capacity, dtype=np.float32)
+        self._fill = 0
+
+    def __len__(self) -> int:
+        return self._fill
+
+    def extend(self, samples: Iterable[float]) -> None:
+        x = np.asarray(samples, dtype=np.float32).reshape(-1)
+        need = self._fill + x.size
+        if need > self._buf.size:
+            grown = np.zeros(max(need, 2 * self._buf.size), dtype=np.float32)
+            grown[: self._fill] = self._buf[: self._fill]
+            self._buf = grown
+        self._buf[self._fill : need] = x
+        self._fill = need
+
+    def view(self) -> np.ndarray:
+        return self._buf[: self._fill]
+
+
+class FeatureStates(StageStates):
+    """`source` keeps only the most recent waveform chunk; older samples live in the ring as far as they are still needed, and
+    all of them since the last reset in `heard`."""
+
+    FIELDS = {"ring": None, "heard": HeardSamples}
 
     def absorb(self, seg: Segment) -> None:
         self.source = [seg.content]
+        self.heard.extend(seg.content)
 
     previous_residual_samples = property(
         lambda self: np.zeros(0) if self.ring is None else self.ring._peek(len(self.ring)),
@@ -595,6 +635,137 @@ class VocoderAgent(Stage):
         return self.emit(SpeechSegment(content=wav.reshape(-1).tolist(), finished=done, sample_rate=self.sample_rate, tgt_lang=lang), done)
 
 
+# =========================================================================================================== #
+# Stage 5, expressive - the PRETSSEL vocoder, conditioned on the prosody of everything the first stage has heard since its
+# last reset (pretssel_vocoder.py:78-143), and the stage that holds both vocoders (dual_vocoder_agent.py:31-116)
+# =========================================================================================================== #
+def pretssel_chunk_tokens(units: Iterable[int]) -> Tuple[List[int], List[int]]:
+    """A unit chunk as the streaming stage feeds it to the PRETSSEL vocoder (:90-97): unit + 4, runs collapsed, two frames per
+    unit of a run.  Unlike the offline `PretsselGenerator.units_to_tokens` no EOS is appended and the last run keeps its count."""
+    tokens: List[int] = []
+    frames: List[int] = []
+    for u in units:
+        t = int(u) + 4
+        if tokens and tokens[-1] == t:
+            frames[-1] += 2
+        else:
+            tokens.append(t)
+            frames.append(2)
+    return tokens, frames
+
+
+def heard_samples(upstream: Any) -> np.ndarray:
+    """The samples an upstream stage has heard: stage 1's `heard` record; of any other states object its `source`, flat or as a
+    list of chunks (what the reference's stage reads)."""
+    heard = getattr(upstream, "heard", None)
+    if isinstance(heard, HeardSamples):
+        return heard.view()
+    src = upstream.source
+    if isinstance(src, list) and src and isinstance(src[0], (list, tuple, np.ndarray)):
+        return np.concatenate([np.asarray(c, dtype=np.float32).reshape(-1) for c in src])
+    return np.asarray(src, dtype=np.float32).reshape(-1)
+
+
+class ExpressiveVocoderStates(AgentStates):
+    """The plain vocoder stage's chunk queue plus one flag: after a reset the backend's prosody history has to start over too
+    (also when the states are the caller's own and only they were reset)."""
+
+    def reset(self) -> None:
+        AgentStates.reset(self)
+        self.history_stale = True
+
+
+class PretsselVocoderAgent(Stage):
+    source_type, target_type = "text", "speech"
+    OPTIONS = {"tgt_lang": "tgt_lang", "upstream_idx": "upstream_idx"}
+    STATES = ExpressiveVocoderStates
+
+    def __init__(self, backend, args: Namespace) -> None:
+        if "pretssel" not in str(args.vocoder_name):
+            raise AssertionError(f"vocoder_name '{args.vocoder_name}' is not a PRETSSEL vocoder")
+        # the vocoder card's languages and sample rate (:51-53); a backend without the vocoder refuses here
+        self.vocoder_langs, self.vocoder_sample_rate = backend.expressive_card()
+        Stage.__init__(self, args, backend)
+
+    def policy(self, states: ExpressiveVocoderStates) -> Action:
+        queue = states.source
+        first = queue[0] if len(queue) else ()
+        if len(first) == 0:  # no chunk, or the empty closing chunk
+            return self.close([]) if states.source_finished else self.wait()
+        lang = states.tgt_lang or self.tgt_lang
+        content: List[float] = []
+        if lang not in self.vocoder_langs:
+            logger.warning(f"{lang} not supported!")  # an empty segment is still written (:120-122)
+        else:
+            if states.history_stale:
+                self.backend.reset_expressive()
+                states.history_stale = False
+            heard = heard_samples(states.upstream_states[self.upstream_idx])
+            with torch.inference_mode():
+                wav = self.backend.speak_expressive(heard, [int(u) for u in first[0].tolist()], lang)
+            content = wav.reshape(-1).tolist()
+        states.source = []
+        done = states.source_finished
+        return self.emit(SpeechSegment(content=content, finished=done, sample_rate=self.vocoder_sample_rate, tgt_lang=lang), done)
+
+
+class DualVocoderStates(AgentStates):
+    """Both vocoders' states behind one: every segment feeds both, the stream has ended when either says so."""
+
+    def __init__(self, plain: AgentStates, expressive: AgentStates) -> None:
+        self.vocoder_states, self.expr_vocoder_states = plain, expressive
+        self.config: dict = {}
+        self.upstream_states: dict = {}
+
+    both = property(lambda self: (self.vocoder_states, self.expr_vocoder_states))
+    target_finished = property(lambda self: any(s.target_finished for s in self.both))
+
+    def reset(self) -> None:
+        for s in self.both:
+            s.reset()
+        self.config = {}
+
+    def update_source(self, seg: Segment) -> None:
+        for s in self.both:
+            s.update_config(seg.config)
+            s.update_source(seg)
+
+    def update_target(self, seg: Segment) -> None:
+        for s in self.both:
+            s.update_target(seg)
+
+
+class DualVocoderAgent(Stage):
+    """Speaks each chunk with the PRETSSEL vocoder or the plain one: the segment's `config["expressive"]` decides, else the
+    `expressive` option.  A chunk is spoken once: when the vocoder in use has emptied its queue the other's is emptied too."""
+
+    source_type, target_type = "text", "speech"
+    OPTIONS = {"expressive": "expressive"}
+
+    def __init__(self, backend, args: Namespace) -> None:
+        self.vocoder = VocoderAgent(backend, args)
+        expr_args = copy.copy(args)
+        expr_args.vocoder_name = args.expr_vocoder_name
+        self.expr_vocoder = PretsselVocoderAgent(backend, expr_args)
+        Stage.__init__(self, args, backend)
+
+    def build_states(self) -> DualVocoderStates:
+        return DualVocoderStates(self.vocoder.build_states(), self.expr_vocoder.build_states())
+
+    def policy(self, states: DualVocoderStates) -> Action:
+        config = states.config
+        expressive = config["expressive"] if config is not None and "expressive" in config else self.expressive
+        if expressive:
+            agent, used, idle = self.expr_vocoder, states.expr_vocoder_states, states.vocoder_states
+            used.upstream_states = states.upstream_states
+        else:
+            agent, used, idle = self.vocoder, states.vocoder_states, states.expr_vocoder_states
+        action = agent.policy(used)
+        if len(used.source) == 0:
+            idle.source = []
+        return action
+
+
 class DetokenizerAgent(Stage):
     """SentencePiece pieces -> words.  `detokenize_only`: every batch of pieces is converted and written at once; otherwise
     a word is written when the next one has started (its last piece is known then)."""
@@ -651,6 +822,25 @@ class SeamlessStreamingS2STAgent(UnitYAgentPipeline):
         args = args or default_args()
         super().__init__(_front(backend, args) + [UnitYMMATextDecoderAgent(backend, text_tokenizer, args),
                                                   NARUnitYUnitDecoderAgent(backend, args), VocoderAgent(backend, args)])
+
+
+class SeamlessS2STAgent(UnitYAgentPipeline):
+    """The expressive chain (seamless_s2st.py:34-41): the S2ST chain with the PRETSSEL vocoder as its last stage."""
+
+    def __init__(self, backend, text_tokenizer, args: Optional[Namespace] = None) -> None:
+        args = args or default_args()
+        super().__init__(_front(backend, args) + [UnitYMMATextDecoderAgent(backend, text_tokenizer, args),
+                                                  NARUnitYUnitDecoderAgent(backend, args), PretsselVocoderAgent(backend, args)])
+
+
+class SeamlessS2STDualVocoderAgent(UnitYAgentPipeline):
+    """The same chain ending in the stage that holds both vocoders.  The reference has this stage only behind its VAD tree
+    pipeline (seamless_s2st.py:56-65), which is not restated; this is its linear counterpart."""
+
+    def __init__(self, backend, text_tokenizer, args: Optional[Namespace] = None) -> None:
+        args = args or default_args()
+        super().__init__(_front(backend, args) + [UnitYMMATextDecoderAgent(backend, text_tokenizer, args),
+                                                  NARUnitYUnitDecoderAgent(backend, args), DualVocoderAgent(backend, args)])
 
 
 class SeamlessStreamingS2TDetokAgent(UnitYAgentPipeline):

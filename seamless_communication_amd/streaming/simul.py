@@ -12,12 +12,23 @@ tests/golden/make_streaming_goldens.py and their traces are replayed on streamin
   an action: a read gives an ``EmptySegment``; a write gives its content (wrapped into the agent's target segment type
   unless it already is a segment);
 * speech segments extend ``states.source`` (samples / frames), text segments append to it.
+
+What the expressive chain's last stages observably need of simuleval 1.1 is restated the same way (a restatement, not
+simuleval's code; pretssel_vocoder.py:99-104 reads ``states.upstream_states[upstream_idx].source``, dual_vocoder_agent.py:98-99
+reads ``states.config["expressive"]``):
+
+* a segment carries an optional ``config`` dict; ``push`` stores it on the states (``update_config``), and a pipeline copies the
+  incoming segment's ``config`` onto the output of every stage but the last, so that each stage sees it;
+* ``AgentPipeline.push`` hands each stage, before that stage's ``push``, the states of the stages before it as
+  ``states.upstream_states``, indexed 0 and up.
+
+Every signature keeps working without the new arguments.
 """
 from __future__ import annotations
 
 from argparse import Namespace
 from dataclasses import dataclass, field
-from typing import Any, List, Optional
+from typing import Any, Dict, List, Optional
 
 
 # --------------------------------------------------------------------------- segments
@@ -94,6 +105,11 @@ class AgentStates:
         self.target_finished = False
         self.source_sample_rate = 0
         self.tgt_lang: Optional[str] = None
+        self.config: Dict[str, Any] = {}
+        self.upstream_states: Dict[int, "AgentStates"] = {}
+
+    def update_config(self, config: Optional[Dict[str, Any]]) -> None:
+        self.config = config
 
     def update_source(self, segment: Segment) -> None:
         self.source_finished = segment.finished
@@ -129,8 +145,12 @@ class GenericAgent:
     def policy(self, states: AgentStates) -> Action:
         raise NotImplementedError
 
-    def push(self, source_segment: Segment, states: Optional[AgentStates] = None) -> None:
-        (states if states is not None else self.states).update_source(source_segment)
+    def push(self, source_segment: Segment, states: Optional[AgentStates] = None,
+             upstream_states: Optional[Dict[int, AgentStates]] = None) -> None:
+        states = states if states is not None else self.states
+        states.upstream_states = upstream_states if upstream_states is not None else {}
+        states.update_config(source_segment.config)
+        states.update_source(source_segment)
 
     def pop(self, states: Optional[AgentStates] = None) -> Segment:
         states = states if states is not None else self.states
@@ -147,8 +167,9 @@ class GenericAgent:
         states.update_target(segment)
         return segment
 
-    def pushpop(self, segment: Segment, states: Optional[AgentStates] = None) -> Segment:
-        self.push(segment, states)
+    def pushpop(self, segment: Segment, states: Optional[AgentStates] = None,
+                upstream_states: Optional[Dict[int, AgentStates]] = None) -> Segment:
+        self.push(segment, states, upstream_states)
         return self.pop(states)
 
 
@@ -168,17 +189,23 @@ class AgentPipeline(GenericAgent):
         for m in self.module_list:
             m.reset()
 
-    def push(self, segment: Segment, states: Optional[List[Optional[AgentStates]]] = None) -> None:
+    def push(self, segment: Segment, states: Optional[List[Optional[AgentStates]]] = None,
+             upstream_states: Optional[Dict[int, AgentStates]] = None) -> None:
         states = states if states is not None else [None] * len(self.module_list)
         assert len(states) == len(self.module_list)
+        upstream = upstream_states if upstream_states is not None else {}
         for i, module in enumerate(self.module_list[:-1]):
-            segment = module.pushpop(segment, states[i])
-        self.module_list[-1].push(segment, states[-1])
+            config = segment.config
+            segment = module.pushpop(segment, states[i], upstream)
+            segment.config = config
+            upstream[i] = states[i] if states[i] is not None else module.states
+        self.module_list[-1].push(segment, states[-1], upstream)
 
     def pop(self, states: Optional[List[Optional[AgentStates]]] = None) -> Segment:
         last = None if states is None else states[-1]
         return self.module_list[-1].pop(last)
 
-    def pushpop(self, segment: Segment, states: Optional[List[Optional[AgentStates]]] = None) -> Segment:
-        self.push(segment, states)
+    def pushpop(self, segment: Segment, states: Optional[List[Optional[AgentStates]]] = None,
+                upstream_states: Optional[Dict[int, AgentStates]] = None) -> Segment:
+        self.push(segment, states, upstream_states)
         return self.pop(states)
