@@ -570,6 +570,35 @@ void sc_pretssel_wave_free(sc_pretssel_wave_model* p);
 int sc_pretssel_wave(sc_pretssel_wave_model* p, const float* d_mel, int32_t n, int32_t t_cap, const int32_t* h_frame_lens, float* d_wav, int32_t wav_cap,
                      int32_t* h_wav_lens_or_null, int32_t flags);
 
+/* ---- Audio resampling (added within ABI v10, purely additive): the windowed-sinc polyphase resampler the reference calls as
+ * torchaudio.functional.resample in front of every model that opens a file (cli/m4t/predict/predict.py:226-231,
+ * cli/expressivity/predict/predict.py:115, models/aligner/alignment_extractor.py:63-71).  A restatement of that algorithm, not
+ * torchaudio itself (DESIGN.md section 7h has the definition).  With g = gcd(orig_freq, new_freq), orig = orig_freq / g,
+ * new = new_freq / g: out_len = ceil(new * L / orig), y[f * new + p] = sum_k h[p][k] * x[f * orig + k - width] with x = 0 outside
+ * [0, L); the bank h is built on the host in double, rounded to fp32 and cached per (orig, new, options); sums are fp32 in
+ * ascending tap order, one output per thread, so a row's result does not depend on its companions, to the bit.
+ * No handle: the resampler has no weights.  It runs on the CURRENT device, on the default stream (ordered behind the caller's
+ * work there), and returns when the output is complete.
+ *   d_in  [n][in_stride] fp32, row i valid up to h_in_len[i] (what lies behind is never read into a result)
+ *   d_out [n][out_stride] fp32, row i holds h_out_len[i] samples and zeros up to out_stride; must not overlap d_in
+ *   opts  NULL or all-zero: lowpass_filter_width 6, rolloff 0.99, hann.  Otherwise abi_version must be SC_ABI_VERSION and every
+ *         field is taken as given, except that beta == 0 is the default 14.769656459379492 and that rolloff / beta equal to
+ *         their default rounded to fp32 stand for the default in double (the bank is built in double).
+ * orig == new is a row copy.  SC_ERR_INVALID, before any device work: a null pointer, rates <= 0, orig or new above 1024 after
+ * reduction, a bank (new x taps per phase x 4 bytes) above 64 KB, lowpass_filter_width < 1, rolloff outside (0, 1], an unknown
+ * method, n outside 1..65535, a length above in_stride, out_stride below the longest out_len, overlapping buffers.
+ * sc_resample_len: out_len of num_samples samples (host only; negative on rates <= 0 or a negative length). */
+typedef struct sc_resample_opts {
+    int32_t abi_version;
+    int32_t lowpass_filter_width;
+    float rolloff;
+    int32_t method; /* 0 hann (sinc_interp_hann), 1 kaiser (sinc_interp_kaiser) */
+    float beta;     /* kaiser only */
+} sc_resample_opts;
+int64_t sc_resample_len(int64_t num_samples, int32_t orig_freq, int32_t new_freq);
+int sc_resample(const float* d_in, int32_t n, int64_t in_stride, const int64_t* h_in_len, int32_t orig_freq, int32_t new_freq,
+                const sc_resample_opts* opts, float* d_out, int64_t out_stride, int64_t* h_out_len);
+
 /* The kernel-level test hooks (sc_op_*) and the dispatch introspection the parity tests drive are exported too but are NOT part
  * of the drop-in boundary: include/seamless_hip_internal.h. */
 

@@ -358,6 +358,19 @@ int sc_op_sconv(const float* d_x, const int32_t* h_lens, int32_t n, int32_t cin,
 int sc_op_seanet_tail(const float* d_h, const int32_t* h_dec_lens, const int32_t* h_out_lens, int32_t n, int32_t cin, int32_t k, const void* d_w_f16,
                       const float* d_bias, const float* d_skip, float* d_wav, int64_t wav_stride);
 
+
+/* The resampler's host side by itself (k_resample.hip; tests/test_resample_cpu.py, test_resample_gpu.py): no device work, callable
+ * without a GPU.  sc_op_resample_bank: the compact bank sc_resample multiplies with - *width, *S (taps kept per phase: the
+ * longest support rounded up to a multiple of 4), h_k0 [new] the first tap of every phase's support, h_taps [new][S] fp32, zeros
+ * behind a phase's own support (which the kernel does not read: a sample under a padding tap reaches no output).  h_k0 / h_taps
+ * may both be NULL (sizes only); cap counts the floats h_taps can hold, SC_ERR_CAPACITY below new * S.  orig == new has no bank
+ * (width = S = 0).
+ * sc_op_resample_plan: h_plan6 = {orig, new, F, F * new, F * orig, LDS bytes}: the reduced rates, the frames one workgroup
+ * owns, its outputs and input samples, and the LDS it asks for. */
+int sc_op_resample_bank(int32_t orig_freq, int32_t new_freq, const sc_resample_opts* opts, int32_t* width, int32_t* S, int32_t* h_k0,
+                        float* h_taps, int64_t cap);
+int sc_op_resample_plan(int32_t orig_freq, int32_t new_freq, const sc_resample_opts* opts, int32_t* h_plan6);
+
 #ifdef __cplusplus
 }
 #endif

@@ -61,14 +61,20 @@ def expressive_fbanks(translator, wavs: Sequence[Tensor], gcmvn_mean: Tensor, gc
 @torch.inference_mode()
 def expressive_predict(translator, pretssel_generator, wav_16k: Union[Tensor, Sequence[Tensor]], tgt_lang: str, gcmvn_mean, gcmvn_std,
                        duration_factor: float = 1.0, text_generation_opts: Optional[Any] = None, unit_generation_opts: Optional[Any] = None,
-                       unit_generation_ngram_filtering: bool = False):
+                       unit_generation_ngram_filtering: bool = False, sample_rate: int = 16000):
     """-> (texts without prosody tokens, raw texts, ``BatchedSpeechOutput`` of the PRETSSEL generator).
 
     ``translator``: a :class:`~seamless_communication_amd.inference.Translator` of the expressive model, loaded with
     ``vocoder_name_or_card=None`` (predict.py:87-92); ``pretssel_generator``: a
     :class:`~seamless_communication_amd.inference.PretsselGenerator`; ``wav_16k``: one waveform or a sequence of them;
-    ``gcmvn_mean`` / ``gcmvn_std``: the vocoder card's statistics (80 values each)."""
+    ``gcmvn_mean`` / ``gcmvn_std``: the vocoder card's statistics (80 values each); ``sample_rate``: the waveforms' rate - at
+    another rate than 16 kHz they are resampled on the device first (predict.py:115)."""
     wavs = [wav_16k] if isinstance(wav_16k, Tensor) or not isinstance(wav_16k, (list, tuple)) else list(wav_16k)
+    if int(sample_rate) != 16000:
+        from .audio import resample
+
+        # (T,) or (T, 1) -> time last on the device, resampled, back in the caller's layout
+        wavs = [resample(torch.as_tensor(w).to(translator.device).transpose(0, -1), int(sample_rate), 16000).transpose(0, -1) for w in wavs]
     src, src_gcmvn = expressive_fbanks(translator, wavs, gcmvn_mean, gcmvn_std)
     texts, unit_out = translator.predict(src, "s2st", tgt_lang, text_generation_opts=text_generation_opts,
                                          unit_generation_opts=unit_generation_opts,

@@ -143,6 +143,34 @@ class AlignmentExtractor:
             units = torch.tensor([int(u) for u in units.split(" ")])
         return self.encode_unit(units)
 
+    def load_audio(self, audio_path: str, sampling_rate: int = 16_000) -> Tuple[Tensor, int]:
+        """alignment_extractor.py:63-71: the file as (channels, time) on the device, resampled to ``sampling_rate`` when its own
+        rate differs."""
+        import os
+        from pathlib import Path
+
+        from ..evaluate import load_audio
+
+        assert os.path.exists(audio_path)
+        samples, rate = load_audio(Path(audio_path), all_channels=True)  # (frames, channels)
+        audio = torch.from_numpy(samples).t().contiguous().to(self.device)
+        if rate != sampling_rate:
+            from ..audio import resample
+
+            audio = resample(audio, rate, sampling_rate)
+            rate = sampling_rate
+        return audio, rate
+
+    def prepare_audio(self, audio: Union[str, Tensor]) -> Tensor:
+        """alignment_extractor.py:73-88: a path is loaded at 16 kHz; (channels, time) is averaged over the channels."""
+        if isinstance(audio, str):
+            audio, _ = self.load_audio(audio, sampling_rate=16_000)
+        if audio.ndim > 1:
+            assert audio.size(0) < audio.size(1), "Expected [Channel,Time] shape, but Channel > Time"
+            audio = audio.mean(0)
+        assert audio.ndim == 1, "After channel averaging audio shape expected to be [Time] i.e. mono audio"
+        return audio.to(self.device, self.dtype)
+
     def _units_of(self, audio: Union[str, Tensor]) -> Tensor:
         if isinstance(audio, Tensor) and not torch.is_floating_point(audio):
             return audio.reshape(-1)
@@ -152,6 +180,8 @@ class AlignmentExtractor:
             # alignment_extractor.py:94: an assigned extractor (inference.UnitExtractor) turns waveforms and paths into units
             if not self.unit_extractor_output_layer:
                 raise ValueError("set unit_extractor_output_layer (the reference uses 35) next to unit_extractor")
+            if isinstance(audio, str):  # alignment_extractor.py:113: a path goes through prepare_audio (resampled to 16 kHz, mono)
+                audio = self.prepare_audio(audio)
             return self.unit_extractor.predict(audio, self.unit_extractor_output_layer - 1)
         raise NotImplementedError("audio input (a waveform tensor or a path) needs the UnitExtractor (XLS-R 1B + k-means), which is not "
                                   "part of this project: pass the units as an integer tensor or a space-separated string")

@@ -900,3 +900,42 @@ class HipPretsselWave(_Handle):
         ms = np.zeros(6, dtype=np.float32)
         check(self.lib.sc_op_pretssel_wave_stage_ms(self.handle, _ptr(ms)), "sc_op_pretssel_wave_stage_ms")
         return dict(zip(self.STAGES, (float(v) for v in ms)))
+
+
+RESAMPLING_METHODS = {"sinc_interp_hann": 0, "sinc_interp_kaiser": 1}
+
+
+def resample_opts(lowpass_filter_width: int = 6, rolloff: float = 0.99, resampling_method: str = "sinc_interp_hann",
+                  beta: Optional[float] = None) -> _lib.sc_resample_opts:
+    """The options of ``sc_resample`` from torchaudio's keyword names (``beta=None``: the default)."""
+    if resampling_method not in RESAMPLING_METHODS:
+        raise ValueError(f"unknown resampling_method {resampling_method!r}; supported: {sorted(RESAMPLING_METHODS)}")
+    return _lib.sc_resample_opts(_lib.SC_ABI_VERSION, int(lowpass_filter_width), float(rolloff), RESAMPLING_METHODS[resampling_method],
+                                 0.0 if beta is None else float(beta))
+
+
+def resample_rows(rows: torch.Tensor, lens: Sequence[int], orig_freq: int, new_freq: int,
+                  opts: Optional[_lib.sc_resample_opts] = None) -> Tuple[torch.Tensor, np.ndarray]:
+    """``sc_resample`` on ``rows`` (n, stride) fp32 on a HIP device, row i valid up to ``lens[i]`` -> ((n, longest out_len) with
+    zeros behind every row's own length, the lengths).  No handle: the call runs on the tensor's device, on the default stream."""
+    lib = _lib.load_library()
+    assert rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2 and rows.is_contiguous()
+    n = rows.shape[0]
+    in_len = np.ascontiguousarray(np.asarray(lens, dtype=np.int64))
+    assert in_len.shape == (n,)
+    out_len = np.asarray([lib.sc_resample_len(int(x), int(orig_freq), int(new_freq)) for x in in_len], dtype=np.int64)
+    if n and out_len.min() < 0:
+        raise SeamlessHipError(f"sc_resample_len: bad sample rates {orig_freq} -> {new_freq} or a negative length")
+    stride = int(out_len.max()) if n else 0
+    out = torch.empty(n, stride, dtype=torch.float32, device=rows.device)
+    if n == 0:
+        return out, out_len
+    got = np.zeros(n, dtype=np.int64)
+    with torch.cuda.device(rows.device):
+        # the entry launches on the default stream: order it behind the producer of `rows` when that is another stream
+        cur = torch.cuda.current_stream(rows.device)
+        if cur.cuda_stream != 0:
+            cur.synchronize()
+        check(lib.sc_resample(_ptr(rows), n, rows.shape[1], _ptr(in_len), int(orig_freq), int(new_freq),
+                              C.byref(opts) if opts is not None else None, _ptr(out), stride, _ptr(got)), "sc_resample")
+    return out, got
