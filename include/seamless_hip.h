@@ -314,6 +314,29 @@ int sc_engine_get_stats(sc_engine* e, sc_engine_stats* out, int32_t reset);
 int sc_decode_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
                    const int32_t* h_tokens, int32_t s_text, float* d_dec_hidden);
 
+/* Teacher-forced scoring: how probable the model finds GIVEN target sequences (forced-decoding scores, n-best re-ranking,
+ * perplexity / held-out loss, token accuracy) - the forward half of the reference's evaluation loss
+ * (cli/m4t/finetune/trainer.py:100-125 UnitYFinetuneWrapper.forward, S2T half: encode, teacher-forced decode, final_proj;
+ * :155-188 CalcLoss).  d_enc / h_enc_lens: sc_encode_speech or sc_encode_text output, as for sc_generate_text.
+ *   h_tokens   [n][s_text]  whole sequences, prompt ... EOS (</s> __lang__ w1 ... </s>), pad-filled behind tok_lens[b]
+ *   h_tok_lens [n]          2 .. s_text;  s_text <= text_max_seq_len
+ * Position p < tok_lens[b] - 1 feeds tokens[b][p] (with everything in front of it) and scores tokens[b][p + 1]:
+ *   h_tok_lprob [n][s_text-1]            log p(tokens[b][p+1] | tokens[b][..p]), always <= 0
+ *   h_sum_lprob [n][s_text-1] (nullable) sum over the vocabulary of the log-probabilities at p (label smoothing's term)
+ *   h_top1      [n][s_text-1] (nullable) the arg-max token at p (lowest id among equal values)
+ * Positions behind tok_lens[b] - 1 hold 0 (h_top1: -1).  d_dec_hidden (nullable) [n][s_text-1][model_dim] receives the decoder
+ * output of tokens[:, :-1].  An item's results do not depend, to the bit, on what else is in the batch or on the padded
+ * widths: the decoder pass runs its tiled products whatever the row count, and the vocabulary projection keeps per-row
+ * log-softmax statistics in the product's epilogue (no [rows][vocab] buffer exists).  d_dec_hidden therefore equals
+ * sc_decode_text's output to the bit wherever that runs the tiled products too (more than 64 rows, n * (s_text - 1));
+ * below, sc_decode_text takes skinny products with another summation order and the two agree to fp32 re-association.
+ * Runs on the handle's own stream (never the decode engine); works on forked handles and for every text decoder the
+ * handle can hold.  SC_ERR_INVALID before any device work for a NULL pointer, a
+ * tok_lens / enc_lens entry out of range, a token outside the vocabulary or s_text > text_max_seq_len. */
+int sc_score_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens,
+                  const int32_t* h_tok_lens, int32_t s_text, float* h_tok_lprob, float* h_sum_lprob, int32_t* h_top1,
+                  float* d_dec_hidden);
+
 /* a12-a17: UnitYNART2UModel.forward + argmax + unit decoding
  * (models/unity/model.py:379-441, generator.py:338-353).  h_text_seqs
  * [n][s_text] is text_seqs[:, :-1] (pad filled), h_text_lens its PaddingMask.

@@ -118,6 +118,21 @@ int sc_op_linear_presplit(const float* d_x, const void* d_w_f16, const float* d_
  * the arg-max of sc_op_linear_presplit's d_y, lowest index among equal values. */
 int sc_op_linear_presplit_argmax(const float* d_x, const void* d_w_f16, const float* d_bias, int32_t* d_idx, int32_t M, int32_t N,
                                  int32_t K);
+/* Log-softmax statistics of v = x.W^T + b per row with NO logits in memory (the vocabulary projection of sc_score_text): the
+ * pre-split product's epilogue keeps one {max, sum exp(v - max), sum v, v[target], arg-max} record per row and column range
+ * (sc_op_score_record_cols(N) columns, a function of N alone), a finish kernel folds them in column order.  Per row m:
+ *   d_lse[m] = log sum_j exp v[m][j];  d_lprob[m] = v[m][target[m]] - d_lse[m]  (0 where target[m] < 0; always <= 0);
+ *   d_sum_lprob[m] = sum_j v[m][j] - N d_lse[m];  d_top1[m] = arg-max, lowest column among equal values (inside [0, N) for
+ *   every row).  A row's results depend on that row alone, to the bit: not on M, nor on the row group.  A NaN in a row of x
+ *   makes that row's three floats NaN and touches no other row.  Any of the four outputs may be NULL (not all).
+ * _grouped: rows go through in groups of group_rows (0: as many as 32 MB of record scratch hold, sc_op_score_group_rows(N)). */
+int sc_op_linear_presplit_score(const float* d_x, const void* d_w_f16, const float* d_bias, const int32_t* d_target, float* d_lprob,
+                                float* d_sum_lprob, float* d_lse, int32_t* d_top1, int32_t M, int32_t N, int32_t K);
+int sc_op_linear_presplit_score_grouped(const float* d_x, const void* d_w_f16, const float* d_bias, const int32_t* d_target,
+                                        float* d_lprob, float* d_sum_lprob, float* d_lse, int32_t* d_top1, int32_t M, int32_t N,
+                                        int32_t K, int32_t group_rows);
+int32_t sc_op_score_record_cols(int32_t N);
+int32_t sc_op_score_group_rows(int32_t N);
 /* Conv1d (stride 1) through the pre-split product kernel's implicit-convolution mode: x [nb][t][cin] is split into two
  * fp16 planes, output row (i, t) reads rows t + tap*dil - pad of item i (zeros outside the item), weights packed by
  * sc_op_pack_conv_weight.  d_row_valid (nullable, [nb*t] bytes on the device): rows with 0 are written as exact zeros.

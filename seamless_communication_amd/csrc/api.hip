@@ -338,6 +338,16 @@ int sc_decode_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, co
     SC_API_END
 }
 
+int sc_score_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens,
+                  const int32_t* h_tok_lens, int32_t s_text, float* h_tok_lprob, float* h_sum_lprob, int32_t* h_top1,
+                  float* d_dec_hidden) {
+    SC_API_BEGIN
+    SC_CHECK(m && d_enc && h_enc_lens && h_tokens && h_tok_lens && h_tok_lprob, "sc_score_text: null argument");
+    SC_HIP(hipSetDevice(m->m.device));
+    run_score_text(m->m, d_enc, n, s_enc, h_enc_lens, h_tokens, h_tok_lens, s_text, h_tok_lprob, h_sum_lprob, h_top1, d_dec_hidden);
+    SC_API_END
+}
+
 int sc_t2u_nar(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text, const int32_t* h_text_lens,
                const int32_t* h_text_seqs, float duration_factor, int32_t* h_unit_lens, int32_t* out_s_unit_max,
                int32_t* out_s_char_max) {
@@ -1236,6 +1246,54 @@ int sc_op_linear_presplit_argmax(const float* d_x, const void* d_w_f16, const fl
     (void)hipFree(part);
     SC_API_END
 }
+
+int sc_op_linear_presplit_score_grouped(const float* d_x, const void* d_w_f16, const float* d_bias, const int32_t* d_target,
+                                        float* d_lprob, float* d_sum_lprob, float* d_lse, int32_t* d_top1, int32_t M, int32_t N,
+                                        int32_t K, int32_t group_rows) {
+    SC_API_BEGIN
+    SC_CHECK(d_x && d_w_f16 && d_target && (d_lprob || d_sum_lprob || d_lse || d_top1), "sc_op_linear_presplit_score: null argument");
+    SC_CHECK(M > 0 && N > 0 && K > 0 && group_rows >= 0, "sc_op_linear_presplit_score: M=%d N=%d K=%d group_rows=%d", M, N, K, group_rows);
+    const int group = std::min(group_rows > 0 ? group_rows : gemm_score_group_rows(N), M);
+    const size_t rec_bytes = (size_t)group * gemm_score_records(N) * SCORE_REC_FLOATS * 4;
+    __half *hi = nullptr, *lo = nullptr;
+    float* rec = nullptr;
+    SC_HIP(hipMalloc(&hi, (size_t)M * K * 2));
+    SC_HIP(hipMalloc(&lo, (size_t)M * K * 2));
+    SC_HIP(hipMalloc(&rec, rec_bytes));
+    try {
+        SC_HIP(hipMemsetAsync(rec, 0xff, rec_bytes, g_op_stream));  // NaN / -1: every record must be written
+        launch_split_f32(d_x, hi, lo, (int64_t)M * K, g_op_stream);
+        GemmPsArgs a;
+        a.Ah = hi;
+        a.Al = lo;
+        a.lda = K;
+        a.W = static_cast<const __half*>(d_w_f16);
+        a.ldw = K;
+        a.bias = d_bias;
+        a.M = M;
+        a.N = N;
+        a.K = K;
+        launch_gemm_presplit_score(a, d_target, rec, group, d_lprob, d_sum_lprob, d_lse, d_top1, g_op_stream);
+        SC_HIP(hipStreamSynchronize(g_op_stream));
+    } catch (...) {
+        (void)hipFree(hi);
+        (void)hipFree(lo);
+        (void)hipFree(rec);
+        throw;
+    }
+    (void)hipFree(hi);
+    (void)hipFree(lo);
+    (void)hipFree(rec);
+    SC_API_END
+}
+
+int sc_op_linear_presplit_score(const float* d_x, const void* d_w_f16, const float* d_bias, const int32_t* d_target, float* d_lprob,
+                                float* d_sum_lprob, float* d_lse, int32_t* d_top1, int32_t M, int32_t N, int32_t K) {
+    return sc_op_linear_presplit_score_grouped(d_x, d_w_f16, d_bias, d_target, d_lprob, d_sum_lprob, d_lse, d_top1, M, N, K, 0);
+}
+
+int32_t sc_op_score_record_cols(int32_t N) { return N > 0 ? gemm_score_record_cols(N) : -1; }
+int32_t sc_op_score_group_rows(int32_t N) { return N > 0 ? gemm_score_group_rows(N) : -1; }
 
 int sc_op_conv1d_presplit(const float* d_x, const void* d_w_f16_packed, const float* d_bias, const float* d_res, float* d_y,
                           void* d_yh_f16, void* d_yl_f16, int32_t nb, int32_t t, int32_t cin, int32_t cout, int32_t k, int32_t pad,

@@ -17,6 +17,7 @@
 //     stay in flight) - __syncthreads() would drain them all;
 //   * rows beyond M / N get an out-of-range buffer offset and arrive as zeros;
 //   * same MFMA order as the other kernels: per 16-wide K chunk and fragment pair, hi then lo.
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
@@ -128,6 +129,9 @@ __device__ __forceinline__ void ps_epilogue(const GemmPsArgs& p, const float* ep
 // SPLIT = false (GemmPsArgs::split == 0): the lo plane is neither fetched nor multiplied - A rounded to fp16 once.
 // AMAX: the epilogue keeps, per row, the largest value of the wave's columns and its (lowest) column instead of writing the
 // tile (GemmPsArgs::amax); a separate instantiation, so that the other kernels' code does not change by a single instruction.
+// SCORE: the epilogue keeps, per row, one log-softmax record of the wave's columns (GemmScoreArgs, kernels.h) instead of
+// writing the tile - the vocabulary projection of teacher-forced scoring; a kernel of its own (gemm_score_kernel) around the
+// same body, so that gemm_ps_kernel keeps its instantiations, their names and their code.
 //
 // The K loop's schedule follows from SPLIT and the wave count; every schedule issues the same instructions per accumulator
 // in the same order (slab, 16-wide K chunk, hi then lo): bit-identical results.
@@ -163,462 +167,51 @@ __device__ __forceinline__ void ps_epilogue(const GemmPsArgs& p, const float* ep
 //     Ordering: the DMAs of slab s+1 are awaited (counted vmcnt, the 6 of slab s+2 stay in flight) in front of the barrier
 //     that ends segment 4s+3 and read from segment 4s+4 on; a stage is refilled (slab s+2 -> stage of slab s-1) from
 //     segment 4s on, its last reads were issued in segment 4s-1 and retired (lgkmcnt(0)) in front of that segment's barrier.
+// The kernel body lives in k_gemm_ps_body.h and is included by two kernels: gemm_ps_kernel (store and arg-max epilogues, the
+// kernel arguments, instantiations and names it always had) and gemm_score_kernel (the SCORE epilogue, GemmScoreArgs behind the
+// same arguments).  The body reads the template parameters BM, BN, WGM, WGN, SPLIT, CONV, AMAX, SCORE and the arguments by name.
 template <int BM, int BN, int WGM, int WGN, bool SPLIT, bool CONV, bool AMAX>
 __global__ __launch_bounds__(WGM* WGN * 64) void gemm_ps_kernel(GemmPsArgs p, int tiles_n, int tiles_total, int tiles_per_xcd,
                                                                  uint32_t a_bytes, uint32_t w_bytes) {
-    constexpr int NWAVE = WGM * WGN;
-    constexpr bool ALTERNATE = SPLIT && NWAVE == 8;  // the K loop's schedule, see above
-    constexpr bool MID_BARRIER = SPLIT && !ALTERNATE;
-    constexpr int WM = BM / WGM, WN = BN / WGN;
-    constexpr int TM = WM / 32, TN = WN / 32;
-    constexpr int ACH = BM / (16 * NWAVE);  // 1 KB chunks (16 rows) of the A tile per wave
-    constexpr int BCH = BN / (16 * NWAVE);
-    constexpr uint32_t OOB = 0x80000000u;
-    constexpr int A_TILE = BM * 32, B_TILE = BN * 32;  // halfs per stage
+    constexpr bool SCORE = false;
+    const GemmScoreArgs sc{};  // never read: every use sits behind `if constexpr (SCORE)`
+#include "k_gemm_ps_body.h"
+}
 
-    // three stages of [A_hi | A_lo | W] tiles (without SPLIT: [A_hi | W] - no LDS is set aside for a plane nobody stages: the
-    // 128 x 128 tile then takes 48 KB instead of 72 and a CU holds three workgroups instead of two); after the K loop the same
-    // memory holds one fp32 tile per wave for the transposed (row-major, 16 bytes per lane) epilogue
-    constexpr int A_PL = SPLIT ? 2 : 1;
-    constexpr int STAGE_BYTES = (A_PL * A_TILE + B_TILE) * 2;
-    // columns of a wave's tile that go through LDS per epilogue pass: 64 where the stage memory holds such tiles, else 32
-    constexpr int EPN = WN < 64 ? WN : (NWAVE * WM * (64 + 4) * 4 <= 3 * STAGE_BYTES ? 64 : 32);
-    constexpr int EP_LD = EPN + 4;          // floats per row of a wave's epilogue tile
-    static_assert(NWAVE * WM * EP_LD * 4 <= 3 * STAGE_BYTES, "epilogue tiles must fit in the stage memory");
-    __shared__ __attribute__((aligned(16))) char smem[3 * STAGE_BYTES];
-    _Float16* const sAh0 = reinterpret_cast<_Float16*>(smem);
-    _Float16* const sAl0 = sAh0 + (A_PL - 1) * A_TILE;  // = sAh0 without SPLIT (never used then)
-    _Float16* const sB0 = sAh0 + A_PL * A_TILE;
-    _Float16* const sAh1 = reinterpret_cast<_Float16*>(smem + STAGE_BYTES);
-    _Float16* const sAl1 = sAh1 + (A_PL - 1) * A_TILE;
-    _Float16* const sB1 = sAh1 + A_PL * A_TILE;
-    _Float16* const sAh2 = reinterpret_cast<_Float16*>(smem + 2 * STAGE_BYTES);
-    _Float16* const sAl2 = sAh2 + (A_PL - 1) * A_TILE;
-    _Float16* const sB2 = sAh2 + A_PL * A_TILE;
-
-    const int bid = blockIdx.x;
-    const int tile = (bid & 7) * tiles_per_xcd + (bid >> 3);
-    if (tile >= tiles_total) return;
-    const int tm = tile / tiles_n;
-    const int tn = tile - tm * tiles_n;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave / WGN, wn = wave % WGN;
-    const int m0 = tm * BM, n0 = tn * BN;
-
-    const i32x4_t rah = make_rsrc_words(p.Ah, a_bytes);
-    const i32x4_t ral = make_rsrc_words(p.Al, a_bytes);
-    const i32x4_t rw = make_rsrc_words(p.W, w_bytes);
-
-    // this lane's fixed LDS position inside a chunk: row (lane >> 2), segment slot (lane & 3); it fetches the
-    // global segment that the swizzle maps to that slot
-    uint32_t a_voff[ACH], b_voff[BCH];
-    int a_t[ACH];    // CONV: position of the lane's row inside its item
-    int a_len[ACH];  // CONV: length of that item (rows_per_item, or row_pos[row].y for packed items)
-#pragma unroll
-    for (int j = 0; j < ACH; ++j) {
-        const int row = 16 * (wave * ACH + j) + (lane >> 2);
-        const int seg = (lane & 3) ^ ((row >> 2) & 3);
-        a_voff[j] = (m0 + row) < p.M ? (uint32_t)(((int64_t)(m0 + row) * p.lda + seg * 8) * 2) : OOB;
-        a_t[j] = 0;
-        a_len[j] = 0;
-        if (CONV) {
-            if (p.row_pos) {
-                const int2 rp = (m0 + row) < p.M ? p.row_pos[m0 + row] : make_int2(0, 0);
-                a_t[j] = rp.x;
-                a_len[j] = rp.y;
-            } else {
-                a_t[j] = (m0 + row) % p.rows_per_item;
-                a_len[j] = p.rows_per_item;
-            }
-        }
-    }
-    // CONV: (tap, 32-wide channel slab) of the NEXT slab to be issued - slabs are issued strictly in K order - and the
-    // operand addresses of that slab: K byte offset inside the row (ka_) and row offset per chunk (va_), rows of another
-    // item or outside the matrix as out-of-range offsets (hardware zero fill = the convolution's zero padding)
-    int nx_tap = 0, nx_cs = 0, nx_slab = 0;
-    const int spt = CONV ? p.conv_cin / PBK : 1;
-    const uint32_t row_bytes = (uint32_t)(p.lda * 2);
-    uint32_t va_[ACH];
-    int ka_ = 0;
-#define PS_NEXT_ADDR()                                                                                  \
-    do {                                                                                                \
-        if (CONV) {                                                                                     \
-            const int dt_ = nx_tap * p.conv_dil - p.conv_pad;                                           \
-            ka_ = nx_cs * (PBK * 2);                                                                    \
-            _Pragma("unroll") for (int j = 0; j < ACH; ++j) {                                           \
-                const bool in_ = (uint32_t)(a_t[j] + dt_) < (uint32_t)a_len[j] && a_voff[j] != OOB;     \
-                va_[j] = in_ ? a_voff[j] + (uint32_t)dt_ * row_bytes : OOB;                             \
-            }                                                                                           \
-            if (++nx_cs == spt) {                                                                       \
-                nx_cs = 0;                                                                              \
-                ++nx_tap;                                                                               \
-            }                                                                                           \
-        } else {                                                                                        \
-            ka_ = nx_slab * (PBK * 2);                                                                  \
-            _Pragma("unroll") for (int j = 0; j < ACH; ++j) va_[j] = a_voff[j];                         \
-        }                                                                                               \
-        ++nx_slab;                                                                                      \
-    } while (0)
-#pragma unroll
-    for (int j = 0; j < BCH; ++j) {
-        const int row = 16 * (wave * BCH + j) + (lane >> 2);
-        const int seg = (lane & 3) ^ ((row >> 2) & 3);
-        b_voff[j] = (n0 + row) < p.N ? (uint32_t)(((int64_t)(n0 + row) * p.ldw + seg * 8) * 2) : OOB;
-    }
-
-    float16_t acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    // fragment read offsets (bytes) per 16-wide K chunk kc = 0, 1
-    int a_off[TM][2], b_off[TN][2];
-#pragma unroll
-    for (int kc = 0; kc < 2; ++kc) {
-        const int s = kc * 2 + (lane >> 5);
-#pragma unroll
-        for (int i = 0; i < TM; ++i) a_off[i][kc] = swz(wm * WM + i * 32 + (lane & 31), s);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) b_off[j][kc] = swz(wn * WN + j * 32 + (lane & 31), s);
-    }
-
-// One LDS-DMA instruction: M0 = LDS byte address of this wave's 1 KB chunk, lane p lands at +16 p.  Issued as
-// inline asm on purpose: the compiler cannot tell which LDS stage an in-flight DMA targets and would drain
-// every outstanding DMA (s_waitcnt vmcnt(0)) before each ds_read; completion is awaited explicitly in PS_STEP.
-#define PS_DMA(RSRC, LDSP, VOFF, SOFF)                                                                        \
-    asm volatile("s_mov_b32 m0, %0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"                              \
-                 :                                                                                            \
-                 : "s"(__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)SC_LDS_PTR(LDSP))), "v"(VOFF), \
-                   "s"(RSRC), "s"((int)(SOFF))                                                                \
-                 : "memory")
-#define PS_ISSUE(AH, AL, BB, KOFF)                                                             \
-    do {                                                                                       \
-        PS_NEXT_ADDR();                                                                        \
-        _Pragma("unroll") for (int j = 0; j < ACH; ++j) {                                      \
-            PS_DMA(rah, &AH[(wave * ACH + j) * 512], va_[j], ka_);                             \
-            if (SPLIT) PS_DMA(ral, &AL[(wave * ACH + j) * 512], va_[j], ka_);                  \
-        }                                                                                      \
-        _Pragma("unroll") for (int j = 0; j < BCH; ++j)                                        \
-            PS_DMA(rw, &BB[(wave * BCH + j) * 512], b_voff[j], (KOFF));                        \
-    } while (0)
-
-    constexpr int NDMA = 2 * ACH + BCH;                   // DMA slots per wave and slab (the lo slots stay empty without SPLIT)
-    constexpr int NLIVE = SPLIT ? NDMA : ACH + BCH;       // DMA instructions really issued per wave and slab
-    static_assert(NDMA == 6 || NDMA == 3, "two or one 1 KB chunk per operand and wave");
-    static_assert(NLIVE < 16, "vmcnt(NLIVE) in the low bits of s_waitcnt");
-
-// DMA number Q (0 .. NDMA-1) of a slab, in the order of PS_ISSUE: A_hi / A_lo chunk pairs, then the W chunks
-#define PS_DMA_Q(Q, AH, AL, BB, KOFF)                                                                         \
-    do {                                                                                                      \
-        if ((Q) < 2 * ACH) {                                                                                  \
-            if (((Q) & 1) == 0) PS_DMA(rah, &AH[(wave * ACH + (Q) / 2) * 512], va_[(Q) / 2], ka_);             \
-            else if (SPLIT) PS_DMA(ral, &AL[(wave * ACH + (Q) / 2) * 512], va_[(Q) / 2], ka_);                 \
-        } else {                                                                                              \
-            PS_DMA(rw, &BB[(wave * BCH + ((Q) - 2 * ACH)) * 512], b_voff[(Q) - 2 * ACH], (KOFF));              \
-        }                                                                                                     \
-    } while (0)
-#define PS_LDS8(BASE, OFF) (*reinterpret_cast<const half8_t*>(reinterpret_cast<const char*>(BASE) + (OFF)))
-
-// Hi plane only.  Slab S sits in stage (CAH, CB); the DMAs of slab S+1 (if any) are the youngest outstanding ones: wait
-// until only those remain, make the landed data visible to every wave, then request every fragment of the slab (both
-// 16-wide K chunks) from LDS before the first matrix instruction, so that the LDS latency of the second chunk runs under
-// the first chunk's MFMAs, and spread the refill of the stage read at slab S-1 (NAH, NB) over the slab: DMA slot q
-// follows the q-th MFMA.
-#define PS_STEP(S, CAH, CB, NAH, NB)                                                                                   \
-    do {                                                                                                               \
-        if ((S) + 1 < nslab) __builtin_amdgcn_s_waitcnt(0x0070 | NLIVE); /* vmcnt(NLIVE) lgkmcnt(0) */                \
-        else __builtin_amdgcn_s_waitcnt(0x0070);                         /* vmcnt(0) lgkmcnt(0) */                     \
-        __builtin_amdgcn_s_barrier();                                                                                  \
-        asm volatile("" ::: "memory");                                                                                 \
-        const bool more_ = (S) + 2 < nslab;                                                                            \
-        half8_t ah[2][TM], bf[2][TN];                                                                                  \
-        _Pragma("unroll") for (int kc = 0; kc < 2; ++kc) {                                                             \
-            _Pragma("unroll") for (int i = 0; i < TM; ++i) ah[kc][i] = PS_LDS8(CAH, a_off[i][kc]);                     \
-            _Pragma("unroll") for (int j = 0; j < TN; ++j) bf[kc][j] = PS_LDS8(CB, b_off[j][kc]);                      \
-        }                                                                                                              \
-        if (more_) PS_NEXT_ADDR();                                                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        int q_ = 0;                                                                                                    \
-        _Pragma("unroll") for (int kc = 0; kc < 2; ++kc) {                                                             \
-            _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                             \
-                _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                       \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[kc][i], bf[kc][j], acc[i][j], 0, 0, 0);       \
-                    if (q_ < NDMA) {                                                                                   \
-                        __builtin_amdgcn_sched_barrier(0);                                                             \
-                        if (more_) PS_DMA_Q(q_, NAH, NAH, NB, ((S) + 2) * (PBK * 2));                                  \
-                        __builtin_amdgcn_sched_barrier(0);                                                             \
-                    }                                                                                                  \
-                    ++q_;                                                                                              \
-                }                                                                                                      \
-        }                                                                                                              \
-        /* tiles with fewer MFMAs than DMA slots (64 x 64: 2 MFMAs, 3 slots): the rest follows the last one */         \
-        _Pragma("unroll") for (int q2 = 2 * TM * TN; q2 < NDMA; ++q2)                                                  \
-            if (more_) PS_DMA_Q(q2, NAH, NAH, NB, ((S) + 2) * (PBK * 2));                                              \
-        asm volatile("" ::: "memory");                                                                                 \
-    } while (0)
-
-    const int nslab = p.K / PBK;
-    if constexpr (ALTERNATE) {
-        static_assert(NDMA == 6, "the alternating schedule is written for the split 8-wave tile");
-        constexpr int NH = NDMA / 2;  // DMAs of a slab per 16-wide K chunk and wave, all issued by the chunk's LOAD segment
-        const bool grp_b = __builtin_amdgcn_readfirstlane(wave) >= NWAVE / 2;
-        half8_t f_ah[TM], f_al[TM], f_bf[TN];  // the fragments of one 16-wide K chunk
-// LOAD segment of chunk KC of slab S (stage C*): the chunk's 8 fragment reads, then the wave's NH DMAs of that chunk for
-// slab S+2 (stage N*), then every read retired (the stage may be refilled one segment after the barrier that follows)
-#define PP_LOADSEG(S, KC, CAH, CAL, CB, NAH, NAL, NB)                                           \
-    do {                                                                                        \
-        _Pragma("unroll") for (int j = 0; j < TN; ++j) f_bf[j] = PS_LDS8(CB, b_off[j][KC]);     \
-        _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                        \
-            f_ah[i] = PS_LDS8(CAH, a_off[i][KC]);                                               \
-            f_al[i] = PS_LDS8(CAL, a_off[i][KC]);                                               \
-        }                                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                      \
-        if ((S) + 2 < nslab) {                                                                  \
-            if ((KC) == 0) PS_NEXT_ADDR();                                                      \
-            _Pragma("unroll") for (int q = (KC) * NH; q < (KC) * NH + NH; ++q) PS_DMA_Q(q, NAH, NAL, NB, ((S) + 2) * (PBK * 2)); \
-        }                                                                                       \
-        __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0), vmcnt untouched */                   \
-        __builtin_amdgcn_sched_barrier(0);                                                      \
-    } while (0)
-// COMPUTE segment: the chunk's hi products of all eight accumulators, then the lo products (an accumulator's two instructions
-// are eight issues apart; its order hi, lo is the one of every other schedule)
-#define PP_COMPUTE()                                                                                               \
-    do {                                                                                                           \
-        __builtin_amdgcn_s_setprio(1);                                                                             \
-        _Pragma("unroll") for (int h_ = 0; h_ < 2; ++h_)                                                           \
-            _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                         \
-                _Pragma("unroll") for (int j = 0; j < TN; ++j)                                                     \
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(h_ == 0 ? f_ah[i] : f_al[i], f_bf[j], acc[i][j], 0, 0, 0); \
-        __builtin_amdgcn_s_setprio(0);                                                                             \
-    } while (0)
-#define PP_BARRIER()                            \
-    do {                                        \
-        __builtin_amdgcn_sched_barrier(0);      \
-        __builtin_amdgcn_s_barrier();           \
-        asm volatile("" ::: "memory");          \
-        __builtin_amdgcn_sched_barrier(0);      \
-    } while (0)
-// slab S (stage C*; N* = stage of slab S+2, the one slab S-1 sat in): four segments.  ROLE_B = false (waves 0-3): load /
-// compute / load / compute; true (waves 4-7): compute (the previous chunk) / load / compute / load.  The two roles are two
-// separate loops (no control flow joins inside the K loop: the 128 accumulator registers stay where they are); both execute
-// the same number of barriers.  At the end of the step both roles have issued all 6 DMAs of slab S+2, and slab S+1 must
-// have landed.
-#define PP_STEP(ROLE_B, S, CAH, CAL, CB, NAH, NAL, NB)                                          \
-    do {                                                                                        \
-        if (!(ROLE_B)) PP_LOADSEG(S, 0, CAH, CAL, CB, NAH, NAL, NB);                            \
-        else if ((S) > 0) PP_COMPUTE();                                                         \
-        PP_BARRIER();                                                                           \
-        if (!(ROLE_B)) PP_COMPUTE();                                                            \
-        else PP_LOADSEG(S, 0, CAH, CAL, CB, NAH, NAL, NB);                                      \
-        PP_BARRIER();                                                                           \
-        if (!(ROLE_B)) PP_LOADSEG(S, 1, CAH, CAL, CB, NAH, NAL, NB);                            \
-        else PP_COMPUTE();                                                                      \
-        PP_BARRIER();                                                                           \
-        if (!(ROLE_B)) PP_COMPUTE();                                                            \
-        else PP_LOADSEG(S, 1, CAH, CAL, CB, NAH, NAL, NB);                                      \
-        if ((S) + 2 < nslab) __builtin_amdgcn_s_waitcnt(0x0076); /* vmcnt(6) lgkmcnt(0) */      \
-        else __builtin_amdgcn_s_waitcnt(0x0070);                                                \
-        PP_BARRIER();                                                                           \
-    } while (0)
-#define PP_LOOP(ROLE_B)                                                                         \
-    do {                                                                                        \
-        for (int s = 0; s < nslab; s += 3) {                                                    \
-            PP_STEP(ROLE_B, s, sAh0, sAl0, sB0, sAh2, sAl2, sB2);                               \
-            if (s + 1 < nslab) PP_STEP(ROLE_B, s + 1, sAh1, sAl1, sB1, sAh0, sAl0, sB0);        \
-            if (s + 2 < nslab) PP_STEP(ROLE_B, s + 2, sAh2, sAl2, sB2, sAh1, sAl1, sB1);        \
-        }                                                                                       \
-        if (ROLE_B) PP_COMPUTE(); /* the last chunk of waves 4-7 */                             \
-    } while (0)
-        PS_ISSUE(sAh0, sAl0, sB0, 0);
-        if (nslab > 1) PS_ISSUE(sAh1, sAl1, sB1, PBK * 2);
-        if (nslab > 1) __builtin_amdgcn_s_waitcnt(0x0076);
-        else __builtin_amdgcn_s_waitcnt(0x0070);
-        PP_BARRIER();
-        if (grp_b) PP_LOOP(true);
-        else PP_LOOP(false);
-#undef PP_LOOP
-#undef PP_STEP
-#undef PP_BARRIER
-#undef PP_LOADSEG
-#undef PP_COMPUTE
-    } else if constexpr (MID_BARRIER) {
-        constexpr int NH = NDMA / 2;  // DMAs of a slab issued in the second half of step s-3; the rest in the first half of step s-2
-        half8_t c_ah[TM], c_al[TM], c_bf[TN];  // chunk-0 fragments of the current slab, carried from the previous step
-#define PS_READ_C0(AH, AL, BB)                                                                  \
-    do {                                                                                        \
-        _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                        \
-            c_ah[i] = PS_LDS8(AH, a_off[i][0]);                                                 \
-            c_al[i] = PS_LDS8(AL, a_off[i][0]);                                                 \
-        }                                                                                       \
-        _Pragma("unroll") for (int j = 0; j < TN; ++j) c_bf[j] = PS_LDS8(BB, b_off[j][0]);      \
-    } while (0)
-// C* = stage of slab S (and of S+3), N* = stage of S+1, O* = stage of S+2
-#define PS_HSTEP(S, CAH, CAL, CB, NAH, NAL, NB, OAH, OAL, OB)                                                          \
-    do {                                                                                                               \
-        half8_t ah1[TM], al1[TM], bf1[TN];                                                                             \
-        _Pragma("unroll") for (int i = 0; i < TM; ++i) {                                                               \
-            ah1[i] = PS_LDS8(CAH, a_off[i][1]);                                                                        \
-            al1[i] = PS_LDS8(CAL, a_off[i][1]);                                                                        \
-        }                                                                                                              \
-        _Pragma("unroll") for (int j = 0; j < TN; ++j) bf1[j] = PS_LDS8(CB, b_off[j][1]);                              \
-        const bool iss2_ = (S) + 2 < nslab;                                                                            \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        int q_ = NH;                                                                                                   \
-        _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                                 \
-            _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                           \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c_ah[i], c_bf[j], acc[i][j], 0, 0, 0);               \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(c_al[i], c_bf[j], acc[i][j], 0, 0, 0);               \
-                if (q_ < NDMA) {                                                                                       \
-                    __builtin_amdgcn_sched_barrier(0);                                                                 \
-                    if (iss2_) PS_DMA_Q(q_, OAH, OAL, OB, ((S) + 2) * (PBK * 2));                                      \
-                    __builtin_amdgcn_sched_barrier(0);                                                                 \
-                }                                                                                                      \
-                ++q_;                                                                                                  \
-            }                                                                                                          \
-        _Pragma("unroll") for (int q2 = NH + TM * TN; q2 < NDMA; ++q2)                                                 \
-            if (iss2_) PS_DMA_Q(q2, OAH, OAL, OB, ((S) + 2) * (PBK * 2));                                              \
-        if ((S) + 1 < nslab) {                                                                                         \
-            if (iss2_) __builtin_amdgcn_s_waitcnt(NDMA == 6 ? 0x0076 : 0x0073); /* vmcnt(6 | 3) lgkmcnt(0) */          \
-            else __builtin_amdgcn_s_waitcnt(0x0070);                            /* vmcnt(0) lgkmcnt(0) */              \
-            __builtin_amdgcn_s_barrier();                                                                              \
-            asm volatile("" ::: "memory");                                                                             \
-            PS_READ_C0(NAH, NAL, NB);                                                                                  \
-        }                                                                                                              \
-        const bool iss3_ = (S) + 3 < nslab;                                                                            \
-        if (iss3_) PS_NEXT_ADDR();                                                                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        q_ = 0;                                                                                                        \
-        _Pragma("unroll") for (int i = 0; i < TM; ++i)                                                                 \
-            _Pragma("unroll") for (int j = 0; j < TN; ++j) {                                                           \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah1[i], bf1[j], acc[i][j], 0, 0, 0);                 \
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al1[i], bf1[j], acc[i][j], 0, 0, 0);                 \
-                if (q_ < NH) {                                                                                         \
-                    __builtin_amdgcn_sched_barrier(0);                                                                 \
-                    if (iss3_) PS_DMA_Q(q_, CAH, CAL, CB, ((S) + 3) * (PBK * 2));                                      \
-                    __builtin_amdgcn_sched_barrier(0);                                                                 \
-                }                                                                                                      \
-                ++q_;                                                                                                  \
-            }                                                                                                          \
-        asm volatile("" ::: "memory");                                                                                 \
-    } while (0)
-
-        // prologue: slabs 0 and 1 whole, the first NH DMAs of slab 2; slab 0 must have landed before its fragments are read
-        PS_ISSUE(sAh0, sAl0, sB0, 0);
-        if (nslab > 1) PS_ISSUE(sAh1, sAl1, sB1, PBK * 2);
-        if (nslab > 2) {
-            PS_NEXT_ADDR();
-#pragma unroll
-            for (int q = 0; q < NH; ++q) PS_DMA_Q(q, sAh2, sAl2, sB2, 2 * (PBK * 2));
-        }
-        if (nslab > 2) __builtin_amdgcn_s_waitcnt(NDMA == 6 ? 0x0079 : 0x0074);       // vmcnt(NDMA + NH)
-        else if (nslab > 1) __builtin_amdgcn_s_waitcnt(NDMA == 6 ? 0x0076 : 0x0073);  // vmcnt(NDMA)
-        else __builtin_amdgcn_s_waitcnt(0x0070);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        PS_READ_C0(sAh0, sAl0, sB0);
-        for (int s = 0; s < nslab; s += 3) {
-            PS_HSTEP(s, sAh0, sAl0, sB0, sAh1, sAl1, sB1, sAh2, sAl2, sB2);
-            if (s + 1 < nslab) PS_HSTEP(s + 1, sAh1, sAl1, sB1, sAh2, sAl2, sB2, sAh0, sAl0, sB0);
-            if (s + 2 < nslab) PS_HSTEP(s + 2, sAh2, sAl2, sB2, sAh0, sAl0, sB0, sAh1, sAl1, sB1);
-        }
-#undef PS_HSTEP
-#undef PS_READ_C0
-    } else {
-        PS_ISSUE(sAh0, sAl0, sB0, 0);
-        if (nslab > 1) PS_ISSUE(sAh1, sAl1, sB1, PBK * 2);
-        for (int s = 0; s < nslab; s += 3) {
-            PS_STEP(s, sAh0, sB0, sAh2, sB2);
-            if (s + 1 < nslab) PS_STEP(s + 1, sAh1, sB1, sAh0, sB0);
-            if (s + 2 < nslab) PS_STEP(s + 2, sAh2, sB2, sAh1, sB1);
-        }
-    }
-#undef PS_STEP
-#undef PS_LDS8
-#undef PS_DMA_Q
-#undef PS_NEXT_ADDR
-#undef PS_ISSUE
-#undef PS_DMA
-
-    // ---- epilogue through LDS: accumulators (column per lane) -> row-major tile of this wave -> 16-byte rows ----
-    __builtin_amdgcn_s_waitcnt(0x0070);
-    __builtin_amdgcn_s_barrier();  // every wave is done reading the last stage
-    asm volatile("" ::: "memory");
-    float* ep = reinterpret_cast<float*>(smem) + wave * (WM * EP_LD);
-    const int m0w = m0 + wm * WM;
-    // the wave's tile leaves in passes of EPN columns through its private LDS region (the LDS queue of a wave is in
-    // order: a pass's writes follow the previous pass's reads)
-    float am_best = -INFINITY;  // AMAX: lane r < WM scans row r of the wave's tile, columns ascending over the passes
-    int am_idx = 0x7fffffff;
-    auto pass = [&](auto hc) {  // compile-time pass number: the accumulator registers are indexed by constants
-        constexpr int h = decltype(hc)::value;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < EPN / 32; ++j)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    ep[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * EP_LD + j * 32 + (lane & 31)] = acc[i][h * (EPN / 32) + j][r];
-        const int n0w = n0 + wn * WN + h * EPN;
-        if constexpr (AMAX) {
-            typedef float f4_t __attribute__((ext_vector_type(4)));
-            if (lane < WM) {
-                const float* row = ep + lane * EP_LD;
-#pragma unroll
-                for (int c4 = 0; c4 < EPN / 4; ++c4) {
-                    const f4_t a = *reinterpret_cast<const f4_t*>(row + 4 * c4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int col = n0w + 4 * c4 + e;
-                        if (col < p.N) {
-                            const float v = (a[e] + (p.bias ? p.bias[col] : 0.f)) * p.alpha;  // = ps_epilogue's value with ACT_NONE
-                            if (v > am_best) {  // strictly: the lowest column among equal values stays
-                                am_best = v;
-                                am_idx = col;
-                            }
-                        }
-                    }
-                }
-            }
-            return;
-        }
-        if (p.act == ACT_NONE) ps_epilogue<WM, EPN, EP_LD, ACT_NONE>(p, ep, m0w, n0w, lane);
-        else if (p.act == ACT_RELU) ps_epilogue<WM, EPN, EP_LD, ACT_RELU>(p, ep, m0w, n0w, lane);
-        else if (p.act == ACT_SILU) ps_epilogue<WM, EPN, EP_LD, ACT_SILU>(p, ep, m0w, n0w, lane);
-        else ps_epilogue<WM, EPN, EP_LD, ACT_TANH>(p, ep, m0w, n0w, lane);
-    };
-    static_assert(WN % EPN == 0 && WN / EPN >= 1 && WN / EPN <= 4, "one to four epilogue passes");
-    pass(std::integral_constant<int, 0>{});
-    if constexpr (WN / EPN > 1) pass(std::integral_constant<int, 1>{});
-    if constexpr (WN / EPN > 2) pass(std::integral_constant<int, 2>{});
-    if constexpr (WN / EPN > 3) pass(std::integral_constant<int, 3>{});
-    if constexpr (AMAX) {
-        const int64_t m = m0w + lane;
-        if (lane < WM && m < p.M) p.amax[m * p.amax_ld + tn * WGN + wn] = make_float2(am_best, __int_as_float(am_idx));
-    }
+// the split plain product with the SCORE epilogue (launch_gemm_presplit_score)
+template <int BM, int BN, int WGM, int WGN>
+__global__ __launch_bounds__(WGM* WGN * 64) void gemm_score_kernel(GemmPsArgs p, int tiles_n, int tiles_total, int tiles_per_xcd,
+                                                                    uint32_t a_bytes, uint32_t w_bytes, GemmScoreArgs sc) {
+    constexpr bool SPLIT = true, CONV = false, AMAX = false, SCORE = true;
+#include "k_gemm_ps_body.h"
 }
 
 template <int BM, int BN, int WGM, int WGN>
-void launch_ps_cfg(const GemmPsArgs& a, hipStream_t s) {
+void launch_ps_cfg(const GemmPsArgs& a, hipStream_t s, const GemmScoreArgs* score = nullptr) {
     const int tiles_m = cdiv(a.M, BM), tiles_n = cdiv(a.N, BN);
     const int tiles_total = tiles_m * tiles_n;
     const int tiles_per_xcd = cdiv(tiles_total, 8);
     char name[64];
     snprintf(name, sizeof(name), "gemm_%dx%d_presplit", BM, BN);
     prof::Scope scope(name, 2.0 * a.M * (double)a.N * a.K,
-                      4.0 * a.M * (double)a.K + 2.0 * a.N * (double)a.K + (a.amax ? 8.0 * a.M * (double)a.amax_ld : 4.0 * a.M * (double)a.N * (a.res ? 2.0 : 1.0)), s);
+                      4.0 * a.M * (double)a.K + 2.0 * a.N * (double)a.K + (score ? 4.0 * SCORE_REC_FLOATS * a.M * (double)score->ld : a.amax ? 8.0 * a.M * (double)a.amax_ld : 4.0 * a.M * (double)a.N * (a.res ? 2.0 : 1.0)), s);
     const dim3 grid(tiles_per_xcd * 8), block(WGM * WGN * 64);
     const uint32_t ab = (uint32_t)((int64_t)a.M * a.lda * 2), wb = (uint32_t)((int64_t)a.N * a.ldw * 2);
     const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb); };
     const bool conv = a.conv_taps > 0;
-    if (a.amax) launch(gemm_ps_kernel<BM, BN, WGM, WGN, true, false, true>);  // split, plain product (launch_gemm_presplit)
+    if (score) hipLaunchKernelGGL((gemm_score_kernel<BM, BN, WGM, WGN>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb, *score);
+    else if (a.amax) launch(gemm_ps_kernel<BM, BN, WGM, WGN, true, false, true>);  // split, plain product (launch_gemm_presplit)
     else if (a.split && conv) launch(gemm_ps_kernel<BM, BN, WGM, WGN, true, true, false>);
     else if (a.split) launch(gemm_ps_kernel<BM, BN, WGM, WGN, true, false, false>);
     else if (conv) launch(gemm_ps_kernel<BM, BN, WGM, WGN, false, true, false>);
     else launch(gemm_ps_kernel<BM, BN, WGM, WGN, false, false, false>);
 }
+
+// The scoring product's tile, from N alone: a row's record boundaries - and with them the order in which its exponentials
+// are summed - must not move with the number of rows in the launch, nor with a tile-choice switch (SC_PS_TILE and its kin
+// change no result, and here the tile decides the summation order).  The widest tile from 1024 columns on (128-column
+// records: the fewest records, and the product streams W once per 256 rows), 128 x 128 from 256, 64 x 64 below.
+int score_tile(int N) { return N >= 1024 ? 256 : N >= 256 ? 128 : 64; }
 
 // tile choice: 256 x 256 (8 waves) once it fills the chip about once, 128 x 128 down to one round of 256 tiles,
 // 64 x 64 below.  SC_PS_TILE=128 (development A/B) keeps the round-1 choice.  All three accumulate every output
@@ -707,6 +300,107 @@ void launch_amax_finish(const float2* part, int ld, int rows, int* out_idx, hipS
     if (rows <= 0) return;
     hipLaunchKernelGGL(amax_finish_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, s, part, ld, rows, out_idx);
     SC_LAUNCH_CHECK();
+}
+
+// ---- teacher-forced scoring: log-softmax statistics of A x W^T without the logits ----
+int gemm_score_record_cols(int N) { return score_tile(N) / 2; }  // two waves side by side in every tile shape
+int gemm_score_records(int N) { return cdiv(N, gemm_score_record_cols(N)); }
+int gemm_score_group_rows(int N) {
+    const int64_t per_row = (int64_t)gemm_score_records(N) * SCORE_REC_FLOATS * 4;
+    const int64_t rows = SCORE_SCRATCH_BYTES / per_row;
+    return (int)std::min<int64_t>(std::max<int64_t>(rows / 256 * 256, 256), 1 << 20);  // whole 256-row tiles; one tile row at the least
+}
+
+namespace {
+// One wave per row.  Lane l takes records l, l + 64, ... in ascending order, the 64 partial results meet in a butterfly
+// (xor 32 ... 1): the order depends on the number of records only.  First the row's maximum and its lowest column, then the
+// records' sums rescaled to that maximum.
+__global__ __launch_bounds__(256) void score_finish_kernel(const float* __restrict__ rec, int ld, int rows, int N, int cols,
+                                                            const int* __restrict__ target, float* __restrict__ lprob,
+                                                            float* __restrict__ sum_lprob, float* __restrict__ lse_out,
+                                                            int* __restrict__ top1) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* pr = rec + (int64_t)row * ld * SCORE_REC_FLOATS;
+    float best = -INFINITY;
+    int bidx = 0x7fffffff;
+    for (int i = lane; i < ld; i += 64) {
+        const float v = pr[i * SCORE_REC_FLOATS];
+        const int vi = __float_as_int(pr[i * SCORE_REC_FLOATS + 4]);
+        if (v > best || (v == best && vi < bidx)) {
+            best = v;
+            bidx = vi;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o);
+        const int oi = __shfl_xor(bidx, o);
+        if (ob > best || (ob == best && oi < bidx)) {
+            best = ob;
+            bidx = oi;
+        }
+    }
+    float tot = 0.f, sv = 0.f;
+    for (int i = lane; i < ld; i += 64) {
+        tot += pr[i * SCORE_REC_FLOATS + 1] * expf(pr[i * SCORE_REC_FLOATS] - best);
+        sv += pr[i * SCORE_REC_FLOATS + 2];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        tot += __shfl_xor(tot, o);
+        sv += __shfl_xor(sv, o);
+    }
+    if (lane != 0) return;
+    // the record that holds the maximum contributes its own sum unscaled, and that sum holds exp(0) = 1: tot >= 1, log >= 0
+    const float lt = logf(tot);
+    const float lse = best + lt;
+    const int tgt = target[row];
+    if (lprob) {
+        float lp = 0.f;  // no target (< 0 or outside the row): 0
+        if (tgt >= 0 && tgt < N) lp = (pr[(tgt / cols) * SCORE_REC_FLOATS + 3] - best) - lt;  // <= 0; exactly -log(tot) at the maximum
+        lprob[row] = lp;
+    }
+    if (sum_lprob) sum_lprob[row] = sv - (float)N * lse;
+    if (lse_out) lse_out[row] = lse;
+    if (top1) top1[row] = argmax_stored_index(bidx);
+}
+}  // namespace
+
+void launch_gemm_presplit_score(const GemmPsArgs& a, const int* target, float* rec, int rec_rows, float* lprob, float* sum_lprob,
+                                float* lse, int* top1, hipStream_t s) {
+    SC_CHECK(a.Ah && a.Al && a.W && target && rec && rec_rows > 0, "presplit score: null operand");
+    SC_CHECK(a.split && a.conv_taps == 0 && !a.C && !a.Ch && !a.Cl && !a.res && !a.row_valid && !a.amax && a.act == ACT_NONE,
+             "presplit score: takes a plain product (no C / planes / residual / activation)");
+    SC_CHECK(a.M > 0 && a.N > 0 && a.K > 0 && a.K % PBK == 0, "presplit score: M=%d N=%d K=%d (K must be a multiple of 32)", a.M, a.N, a.K);
+    SC_CHECK(a.lda % 8 == 0 && a.ldw % 8 == 0 && a.ldw >= a.K && a.lda >= a.K, "presplit score: lda=%lld ldw=%lld", (long long)a.lda,
+             (long long)a.ldw);
+    SC_CHECK(((reinterpret_cast<uintptr_t>(a.Ah) | reinterpret_cast<uintptr_t>(a.Al) | reinterpret_cast<uintptr_t>(a.W)) & 15) == 0 &&
+                 (reinterpret_cast<uintptr_t>(rec) & 7) == 0,
+             "presplit score: operands must be 16-byte aligned");
+    SC_CHECK((int64_t)a.N * a.ldw * 2 < (1ll << 31), "presplit score: weight larger than 2 GB");
+    const int tile = score_tile(a.N), cols = tile / 2, ld = cdiv(a.N, cols);
+    // rows in groups of rec_rows: the records of one group at a time (a row's results do not depend on its group)
+    for (int r0 = 0; r0 < a.M; r0 += rec_rows) {
+        GemmPsArgs g = a;
+        g.M = std::min(rec_rows, a.M - r0);
+        g.Ah = a.Ah + (int64_t)r0 * a.lda;
+        g.Al = a.Al + (int64_t)r0 * a.lda;
+        SC_CHECK((int64_t)g.M * a.lda * 2 < (1ll << 31), "presplit score: row group larger than 2 GB");
+        GemmScoreArgs sa;
+        sa.rec = rec;
+        sa.target = target + r0;
+        sa.ld = ld;
+        if (tile == 256) launch_ps_cfg<256, 256, 4, 2>(g, s, &sa);
+        else if (tile == 128) launch_ps_cfg<128, 128, 2, 2>(g, s, &sa);
+        else launch_ps_cfg<64, 64, 2, 2>(g, s, &sa);
+        SC_LAUNCH_CHECK();
+        hipLaunchKernelGGL(score_finish_kernel, dim3(cdiv(g.M, 4)), dim3(256), 0, s, rec, ld, g.M, a.N, cols, target + r0,
+                           lprob ? lprob + r0 : nullptr, sum_lprob ? sum_lprob + r0 : nullptr, lse ? lse + r0 : nullptr,
+                           top1 ? top1 + r0 : nullptr);
+        SC_LAUNCH_CHECK();
+    }
 }
 
 }  // namespace sc

@@ -185,6 +185,30 @@ int gemm_presplit_tile(int M, int N);         // rows (= columns) of the tile la
 int gemm_presplit_amax_chunks(int M, int N);  // partial results per row the tile choice for this shape produces
 void launch_amax_finish(const float2* part, int ld, int rows, int* out_idx, hipStream_t s);
 
+// Teacher-forced scoring: per row m of the split plain product v = alpha * (A.W^T + bias), the log-softmax statistics
+//   lse[m] = log sum_j exp(v[m][j]),  lprob[m] = v[m][target[m]] - lse[m]  (0 where target[m] < 0),
+//   sum_lprob[m] = sum_j v[m][j] - N * lse[m],  top1[m] = arg-max (lowest column among equal values, launch_argmax_rows' rule)
+// without the [M][N] logits: the product's epilogue writes, per row and per wave's column range (gemm_score_record_cols(N)
+// columns, chosen from N alone), one record
+//   {max, sum of exp(v - max), sum of v, v at the target column if it lies in the range, lowest column of max, -}
+// (columns ascending inside a record), and a finish kernel folds a row's records in a fixed order.  A row's four results
+// depend on that row of A, W, bias and its target only - not on M, not on the other rows, not on the row group.
+// Rows go through in groups of rec_rows (the capacity of `rec`: rec_rows * gemm_score_records(N) * SCORE_REC_FLOATS floats);
+// gemm_score_group_rows(N) keeps `rec` within SCORE_SCRATCH_BYTES.  A NaN in a row of A gives NaN lse / lprob / sum_lprob for
+// that row only, top1 inside [0, N); a logit of +-inf makes its row NaN as well.  Any of the four outputs may be null.
+constexpr int SCORE_REC_FLOATS = 6;
+constexpr int64_t SCORE_SCRATCH_BYTES = 32ll << 20;
+struct GemmScoreArgs {
+    float* rec = nullptr;         // [rows of the launch][ld][SCORE_REC_FLOATS]
+    const int* target = nullptr;  // [rows of the launch]
+    int ld = 0;                   // records per row
+};
+int gemm_score_record_cols(int N);
+int gemm_score_records(int N);
+int gemm_score_group_rows(int N);
+void launch_gemm_presplit_score(const GemmPsArgs& a, const int* target, float* rec, int rec_rows, float* lprob, float* sum_lprob,
+                                float* lse, int* top1, hipStream_t s);
+
 // k_resblock.hip: out = x + conv2_{k,1}(lrelu(conv1_{k,dil}(lrelu(x)) + b1)) + b2 for C in {16, 32, 64}, the
 // intermediate kept in LDS; optionally out = ((avg_a + avg_b) + that) / 3.  Weights packed [C][ldw], tap-major.
 struct ResPairArgs {

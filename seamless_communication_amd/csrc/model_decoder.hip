@@ -1108,8 +1108,10 @@ void setup_session(Model& m, DecodeSession& S, int n, int max_len, int s_enc, bo
 // the chosen hypotheses feed the T2U model) and by sc_decode_text; SC_DECODE_STEPWISE=1 keeps the step-by-step pass.
 // Same modules in the same order as decoder_step (fairseq2.cpp:979-1094); results agree with the stepwise pass to fp32
 // re-association (tests/test_stages_gpu.py: test_generated_hidden_equals_teacher_forced_pass, 2e-4).
+// row_independent (sc_score_text): every product is the tiled one whatever the row count, so that an item's rows carry the same
+// bits alone and in any batch; otherwise up to 64 rows take the skinny products (another summation order, linear()).
 void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens, int s_text,
-                             float* d_hidden) {
+                             float* d_hidden, bool row_independent = false) {
     const sc_config& cfg = m.cfg;
     const int M = cfg.model_dim, rows = n * s_text, erows = n * s_enc;
     SC_CHECK(s_text <= cfg.text_max_seq_len, "sc_decode_text: %d tokens exceed text_max_seq_len=%d", s_text, cfg.text_max_seq_len);
@@ -1128,7 +1130,7 @@ void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, con
     for (const DecoderLayer& l : m.dec) {
         // causal self-attention
         layernorm(m, x, l.self_ln, h, rows);
-        linear(m, h, M, l.qkv, nullptr, 0, wide, 3 * M, rows, ACT_NONE, 1.f);
+        linear(m, h, M, l.qkv, nullptr, 0, wide, 3 * M, rows, ACT_NONE, 1.f, row_independent);
         AttnArgs a;
         a.q = wide;
         a.k = wide.get() + M;
@@ -1141,10 +1143,10 @@ void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, con
         a.Sq = a.Skv = s_text;
         a.causal = 1;
         launch_attention(a, m.stream);
-        linear(m, att, M, l.self_out, x, M, x, M, rows, ACT_NONE, 1.f);
+        linear(m, att, M, l.self_out, x, M, x, M, rows, ACT_NONE, 1.f, row_independent);
         // encoder-decoder attention
         layernorm(m, x, l.cross_ln, h, rows);
-        linear(m, h, M, l.cross_q, nullptr, 0, wide, M, rows, ACT_NONE, 1.f);
+        linear(m, h, M, l.cross_q, nullptr, 0, wide, M, rows, ACT_NONE, 1.f, row_independent);
         project_cross_kv(m, d_enc, l.cross_kv, ckv, erows);
         AttnArgs c;
         c.q = wide;
@@ -1160,14 +1162,88 @@ void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, con
         c.Skv = s_enc;
         c.kv_lens = d_elens;
         launch_attention(c, m.stream);
-        linear(m, att, M, l.cross_out, x, M, x, M, rows, ACT_NONE, 1.f);
+        linear(m, att, M, l.cross_out, x, M, x, M, rows, ACT_NONE, 1.f, row_independent);
         // feed-forward network
         layernorm(m, x, l.ffn_ln, h, rows);
-        linear(m, h, M, l.ffn_in, nullptr, 0, wide, cfg.dec_ffn_dim, rows, m.ffn_act, 1.f);
-        linear(m, wide, cfg.dec_ffn_dim, l.ffn_out, x, M, x, M, rows, ACT_NONE, 1.f);
+        linear(m, h, M, l.ffn_in, nullptr, 0, wide, cfg.dec_ffn_dim, rows, m.ffn_act, 1.f, row_independent);
+        linear(m, wide, cfg.dec_ffn_dim, l.ffn_out, x, M, x, M, rows, ACT_NONE, 1.f, row_independent);
     }
     layernorm(m, x, m.dec_final_ln, x, rows);
     SC_HIP(hipStreamSynchronize(m.stream));  // h_tokens / h_enc_lens are the caller's; outputs complete on return
+}
+
+// Teacher-forced scoring (sc_score_text): the batched causal pass over tokens[:, :-1], then final_proj (tied to the embedding,
+// no bias) and log-softmax over the vocabulary for the rows that have a target - position p < tok_lens[b] - 1 scores
+// tokens[b][p + 1] - packed back to back as the T2U and vocoder passes pack theirs.  The [rows][V] logits are never formed:
+// launch_gemm_presplit_score keeps per-row statistics in the product's epilogue.  The reference's evaluation loss runs the same
+// three steps through PyTorch (cli/m4t/finetune/trainer.py:100-125, :155-188).  Own stream, never the decode engine.
+void run_score_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens,
+                    const int32_t* h_tok_lens, int s_text, float* h_tok_lprob, float* h_sum_lprob, int32_t* h_top1, float* d_dec_hidden) {
+    const sc_config& cfg = m.cfg;
+    const int M = cfg.model_dim, V = cfg.text_vocab_size, S1 = s_text - 1;
+    // every argument error before any device work
+    SC_CHECK(n > 0 && s_enc > 0, "sc_score_text: empty batch");
+    SC_CHECK(!m.dec.empty() && m.text_embed, "sc_score_text: the handle holds no text decoder");
+    SC_CHECK(s_text >= 2, "sc_score_text: s_text=%d (a sequence holds a prompt token and a target at the least)", s_text);
+    SC_CHECK(s_text <= cfg.text_max_seq_len, "sc_score_text: %d tokens exceed text_max_seq_len=%d", s_text, cfg.text_max_seq_len);
+    SC_CHECK(M % 32 == 0, "sc_score_text: model_dim=%d is not a multiple of 32", M);
+    int R = 0;
+    for (int b = 0; b < n; ++b) {
+        SC_CHECK(h_tok_lens[b] >= 2 && h_tok_lens[b] <= s_text, "sc_score_text: tok_lens[%d]=%d outside [2, %d]", b, h_tok_lens[b], s_text);
+        SC_CHECK(h_enc_lens[b] > 0 && h_enc_lens[b] <= s_enc, "sc_score_text: enc_lens[%d]=%d out of range", b, h_enc_lens[b]);
+        R += h_tok_lens[b] - 1;
+    }
+    for (int64_t i = 0; i < (int64_t)n * s_text; ++i)
+        SC_CHECK(h_tokens[i] >= 0 && h_tokens[i] < V, "sc_score_text: token %d outside the vocabulary", h_tokens[i]);
+    std::vector<int32_t> in_tok((size_t)n * S1), row_idx((size_t)R), tgt((size_t)R);
+    for (int b = 0, r = 0; b < n; ++b) {
+        for (int p = 0; p < S1; ++p) in_tok[(size_t)b * S1 + p] = h_tokens[(size_t)b * s_text + p];
+        for (int p = 0; p < h_tok_lens[b] - 1; ++p, ++r) {
+            row_idx[r] = b * S1 + p;
+            tgt[r] = h_tokens[(size_t)b * s_text + p + 1];
+        }
+    }
+    Buf<float> own_hidden(m.pp(), d_dec_hidden ? 0 : (size_t)n * S1 * M);
+    float* hidden = d_dec_hidden ? d_dec_hidden : own_hidden.get();
+    // row-independent products: a sequence's scores must not depend on what it is batched with (n-best lists are compared)
+    run_decode_text_batched(m, d_enc, n, s_enc, h_enc_lens, in_tok.data(), S1, hidden, /*row_independent=*/true);
+    prof::set_tag("score");
+    const int group = std::min(gemm_score_group_rows(V), (R + 255) / 256 * 256);
+    Buf<int> d_idx(m.pp(), R), d_tgt(m.pp(), R), d_top1(m.pp(), R);
+    Buf<float> packed(m.pp(), (size_t)R * M), d_lp(m.pp(), R), d_sum(m.pp(), R),
+        rec(m.pp(), (size_t)group * gemm_score_records(V) * SCORE_REC_FLOATS);
+    Buf<__half> ph(m.pp(), (size_t)R * M), pl(m.pp(), (size_t)R * M);
+    SC_HIP(hipMemcpyAsync(d_idx.get(), row_idx.data(), (size_t)R * 4, hipMemcpyHostToDevice, m.stream));
+    SC_HIP(hipMemcpyAsync(d_tgt.get(), tgt.data(), (size_t)R * 4, hipMemcpyHostToDevice, m.stream));
+    launch_gather_rows(hidden, M, d_idx, packed, M, R, M, m.stream);
+    launch_split_f32(packed, ph, pl, (int64_t)R * M, m.stream);
+    GemmPsArgs a;
+    a.Ah = ph;
+    a.Al = pl;
+    a.lda = M;
+    a.W = m.text_embed;
+    a.ldw = M;
+    a.M = R;
+    a.N = V;
+    a.K = M;
+    launch_gemm_presplit_score(a, d_tgt, rec, group, d_lp, h_sum_lprob ? d_sum.get() : nullptr, nullptr, h_top1 ? d_top1.get() : nullptr,
+                               m.stream);
+    std::vector<float> lp((size_t)R), sl(h_sum_lprob ? (size_t)R : 0);
+    std::vector<int32_t> t1(h_top1 ? (size_t)R : 0);
+    SC_HIP(hipMemcpyAsync(lp.data(), d_lp.get(), (size_t)R * 4, hipMemcpyDeviceToHost, m.stream));
+    if (h_sum_lprob) SC_HIP(hipMemcpyAsync(sl.data(), d_sum.get(), (size_t)R * 4, hipMemcpyDeviceToHost, m.stream));
+    if (h_top1) SC_HIP(hipMemcpyAsync(t1.data(), d_top1.get(), (size_t)R * 4, hipMemcpyDeviceToHost, m.stream));
+    SC_HIP(hipStreamSynchronize(m.stream));
+    // positions behind an item's last target: 0, and -1 for the arg-max
+    for (int b = 0, r = 0; b < n; ++b)
+        for (int p = 0; p < S1; ++p) {
+            const bool live = p < h_tok_lens[b] - 1;
+            const size_t o = (size_t)b * S1 + p;
+            h_tok_lprob[o] = live ? lp[r] : 0.f;
+            if (h_sum_lprob) h_sum_lprob[o] = live ? sl[r] : 0.f;
+            if (h_top1) h_top1[o] = live ? t1[r] : -1;
+            r += live;
+        }
 }
 
 // forced_tokens != null: teacher-forced pass over the given tokens (no arg-max

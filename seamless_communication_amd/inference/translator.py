@@ -40,6 +40,7 @@ from ..config import (S2STConfig, seamless_expressivity, seamless_m4t_large, sea
 from ..runtime import HipS2STModel
 from ..tokenizer import CharTokenizer, NllbTextTokenizer, UnitTokenizer
 from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, SequenceGeneratorOptions
+from ..scoring import score as _score
 
 logger = logging.getLogger(__name__)
 
@@ -294,29 +295,11 @@ class Translator:
         fb, frames = self.model.fbank(wav, [wav.shape[1]], standardize=True, pad_to_multiple=2, sample_rate=int(sample_rate))
         return {"seqs": fb, "seq_lens": torch.tensor(frames.astype(np.int64)), "is_ragged": False}
 
-    @torch.inference_mode()
-    def predict(
-        self,
-        input: Union[str, Tensor, SequenceData],
-        task_str: str,
-        tgt_lang: str,
-        src_lang: Optional[str] = None,
-        text_generation_opts: Optional[SequenceGeneratorOptions] = None,
-        unit_generation_opts: Optional[SequenceGeneratorOptions] = None,
-        spkr: Optional[int] = -1,
-        sample_rate: int = 16000,
-        unit_generation_ngram_filtering: bool = False,
-        duration_factor: float = 1.0,
-        prosody_encoder_input: Optional[SequenceData] = None,
-        src_text: Optional[StringLike] = None,
-    ) -> Tuple[List[StringLike], Optional[BatchedSpeechOutput]]:
-        input_modality, output_modality = self.get_modalities_from_task_str(task_str)
-        if prosody_encoder_input is not None and getattr(self.model, "prosody_encoder", None) is None:
-            raise NoProsodyEncoderError(f"model '{self.cfg.name}' has no prosody encoder: prosody_encoder_input is for the expressive "
-                                        "model (card 'seamless_expressivity')")
-        if self.apply_mintox and not (src_lang is not None or src_text is not None):  # translator.py:263-266
-            raise ValueError("`src_lang` must be specified when `apply_mintox` is `True` or you need to specify src_text.")
-
+    def _source_batch(self, input: Union[str, Tensor, SequenceData], input_modality: Modality, src_lang: Optional[str],
+                      sample_rate: int) -> Tuple[SequenceData, Tensor, List[int], int]:
+        """What ``predict`` hands to the model for ``input`` (translator.py:268-303): the collated SequenceData, its ``seqs`` as
+        the model takes them (fbank on the device / token indices), the source lengths and the sample rate (a file's own).  Shared
+        with ``score``."""
         if isinstance(input, dict):
             src = input
         elif input_modality == Modality.SPEECH:
@@ -359,6 +342,32 @@ class Translator:
             seqs = seqs.to(self.device, torch.float32).contiguous()
         elif seqs.dim() != 2 or seqs.dtype.is_floating_point:
             raise ValueError("SequenceData['seqs'] must be (N, S) token indices for text input")
+        return src, seqs, src_lens, sample_rate
+
+    @torch.inference_mode()
+    def predict(
+        self,
+        input: Union[str, Tensor, SequenceData],
+        task_str: str,
+        tgt_lang: str,
+        src_lang: Optional[str] = None,
+        text_generation_opts: Optional[SequenceGeneratorOptions] = None,
+        unit_generation_opts: Optional[SequenceGeneratorOptions] = None,
+        spkr: Optional[int] = -1,
+        sample_rate: int = 16000,
+        unit_generation_ngram_filtering: bool = False,
+        duration_factor: float = 1.0,
+        prosody_encoder_input: Optional[SequenceData] = None,
+        src_text: Optional[StringLike] = None,
+    ) -> Tuple[List[StringLike], Optional[BatchedSpeechOutput]]:
+        input_modality, output_modality = self.get_modalities_from_task_str(task_str)
+        if prosody_encoder_input is not None and getattr(self.model, "prosody_encoder", None) is None:
+            raise NoProsodyEncoderError(f"model '{self.cfg.name}' has no prosody encoder: prosody_encoder_input is for the expressive "
+                                        "model (card 'seamless_expressivity')")
+        if self.apply_mintox and not (src_lang is not None or src_text is not None):  # translator.py:263-266
+            raise ValueError("`src_lang` must be specified when `apply_mintox` is `True` or you need to specify src_text.")
+
+        src, seqs, src_lens, sample_rate = self._source_batch(input, input_modality, src_lang, sample_rate)
 
         if text_generation_opts is None:
             text_generation_opts = SequenceGeneratorOptions(beam_size=5, soft_max_seq_len=(1, 200))
@@ -444,6 +453,9 @@ class Translator:
                 keep = int(wav.size(-1) * len(speech_units[i]) / units.shape[1])
                 audio_wavs.append(wav[i, :, :keep].unsqueeze(0))
         return texts, BatchedSpeechOutput(units=speech_units, audio_wavs=audio_wavs, sample_rate=sample_rate)
+
+    # teacher-forced scoring of given targets (scoring.py)
+    score = _score
 
     def _speech_from_ar_units(self, units: np.ndarray, pad: int, tgt_lang: str, spkr: Optional[int], sample_rate: int,
                               t_start: float) -> BatchedSpeechOutput:

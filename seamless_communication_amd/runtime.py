@@ -378,6 +378,40 @@ class HipS2STModel(_Handle):
               "sc_decode_text")
         return hidden
 
+    def score_text(self, enc: torch.Tensor, enc_lens: Sequence[int], tokens: np.ndarray, tok_lens: Sequence[int],
+                   want_sum: bool = False, want_top1: bool = False, want_hidden: bool = False):
+        """Teacher-forced scoring (sc_score_text): tokens (n, s_text) whole sequences ``</s> __lang__ ... </s>`` (pad filled),
+        tok_lens (n,) -> dict with ``tok_lprob`` (n, s_text - 1) float32: log-probability of tokens[b, p + 1] given
+        tokens[b, :p + 1]; ``sum_lprob`` (the log-probabilities at p summed over the vocabulary) and ``top1`` (the arg-max
+        token at p) on request; ``hidden`` (n, s_text - 1, M) on the device on request.  Positions behind tok_lens[b] - 1
+        hold 0 (top1: -1).  No (rows, vocabulary) buffer is formed."""
+        assert enc.is_cuda and enc.is_contiguous()
+        n, s_enc, M = enc.shape
+        tok = _i32(tokens)
+        if tok.ndim != 2 or tok.shape[0] != n:
+            raise ValueError(f"tokens must be (n={n}, s_text), got {tok.shape}")
+        s_text = tok.shape[1]
+        tl = _i32(tok_lens).reshape(-1)
+        el = _i32(enc_lens).reshape(-1)
+        if len(tl) != n or len(el) != n:
+            raise ValueError("enc_lens and tok_lens must hold one entry per item")
+        s1 = max(s_text - 1, 0)
+        lprob = np.zeros((n, s1), dtype=np.float32)
+        sum_lprob = np.zeros((n, s1), dtype=np.float32) if want_sum else None
+        top1 = np.full((n, s1), -1, dtype=np.int32) if want_top1 else None
+        hidden = torch.empty(n, s1, M, dtype=torch.float32, device=self.device) if want_hidden else None
+        self._after_torch()
+        check(self.lib.sc_score_text(self.handle, _ptr(enc), n, s_enc, _ptr(el), _ptr(tok), _ptr(tl), s_text, _ptr(lprob),
+                                     _ptr(sum_lprob), _ptr(top1), _ptr(hidden)), "sc_score_text")
+        out = {"tok_lprob": lprob}
+        if want_sum:
+            out["sum_lprob"] = sum_lprob
+        if want_top1:
+            out["top1"] = top1
+        if want_hidden:
+            out["hidden"] = hidden
+        return out
+
     def t2u_nar(self, dec_hidden: torch.Tensor, text_seqs: np.ndarray, text_lens: Sequence[int],
                 duration_factor: float = 1.0, cond: Optional[torch.Tensor] = None):
         """-> units (n, S_u) int32 (pad = unit_pad_idx), unit_lens, durations (n, S_c), char ids, char_seq_lens.
