@@ -271,7 +271,7 @@ int sc_op_align_lprob(const float* d_text, const float* d_feat, int32_t n, int32
                       const int32_t* h_text_lens, const int32_t* h_feat_lens, float temperature, float* d_lprob);
 int sc_op_mas(const float* d_lprob, int32_t n, int32_t s_text, int32_t s_feat, const int32_t* h_text_lens, const int32_t* h_feat_lens,
               int32_t* h_durations);
-/* UnitExtractor kernels by themselves (k_attn80.hip, k_w2v2.hip; tests/test_unit_extractor_gpu.py).
+/* UnitExtractor kernels by themselves (k_attn_hd.hip at head_dim 80, k_w2v2.hip; tests/test_unit_extractor_gpu.py).
  * sc_op_attention_hd: plain attention with a key-length mask at head_dim 64 (the kernel of sc_op_attention) or 80.
  * sc_op_w2v2_frontend: utterance statistics (d_stats [nb][2] = mean, 1/sqrt(var + 1e-5); odd lengths count one more sample of
  *   1.0) and the first extractor layer with its LayerNorm + GELU fused: d_w [C][k], d_out [nb][t_rows][C].
@@ -309,7 +309,7 @@ int sc_op_ecapa_tail(const float* d_pooled, int32_t nb, int32_t C2, const float*
                      int32_t E, float* d_out);
 int32_t sc_op_prosody_last_launches(sc_prosody_encoder* p);
 
-/* PRETSSEL kernels by themselves (k_attn128.hip, k_pretssel.hip; tests/test_pretssel_gpu.py).  Device pointers unless named h_.
+/* PRETSSEL kernels by themselves (k_attn_hd.hip at head_dim 128, k_pretssel.hip; tests/test_pretssel_gpu.py).  Device pointers unless named h_.
  * sc_op_attention128: launch_attention at head_dim 128: q / k / v rows with strides ld*, d_kv_lens (nullable), d_row_off (nullable:
  *   packed rows, needs d_kv_lens and sq == skv), fp32 rows d_out (ldo) or the planes d_out_hi / d_out_lo (ldoh) when those are given.
  * sc_op_pretssel_film: d_out [n][N] = mul * (W [N][P + Lg] fp16 . [pros_i | lang] + bias) + add.

@@ -2,7 +2,7 @@
 // log-softmax score matrix, and the monotonic alignment search with its back-track.
 #include <cmath>
 
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
@@ -87,10 +87,6 @@ __global__ __launch_bounds__(256) void align_dist_kernel(const float* __restrict
 
 __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
 

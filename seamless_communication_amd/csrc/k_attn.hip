@@ -9,7 +9,7 @@
 //   (the first-generation decoder step, kept for the geometries the packed step kernels of k_dstep.hip do not take).
 #include <cstdlib>
 
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
@@ -41,27 +41,14 @@ static constexpr int HD = 64;  // head dim
 static constexpr int MQ = 128;   // queries per workgroup
 static constexpr int MKV = 32;   // keys per iteration
 static constexpr int KS = 68;    // padded row stride of the R staging / output tile (floats)
-typedef _Float16 a16_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 a16_h4 __attribute__((ext_vector_type(4)));
 static constexpr int KH_LD = 72;  // halfs per K-plane row (64 dims + 8 pad)
 static constexpr int VT_LD = 40;  // halfs per V^T-plane row (32 keys + 8 pad)
-
-__device__ __forceinline__ void a16_split8(const float* x, a16_h8& hi, a16_h8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const _Float16 h = (_Float16)x[e];
-        hi[e] = h;
-        lo[e] = (_Float16)(x[e] - (float)h);
-    }
-}
 
 // MODE 0: plain, 1: Shaw relative keys (v2 encoder), 2: Transformer-XL relative positions (v1 encoder, see AttnArgs)
 template <int MODE>
 __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
     constexpr bool SHAW = MODE == 1;
     constexpr bool RELPOS = MODE == 2;
-    typedef float f16v __attribute__((ext_vector_type(16)));
-    typedef float f4v __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) float smem[];
     // [0, 4*32*KS) floats: K/V planes during the loop (19 456 B), the four output tiles afterwards, the relative keys before
     _Float16* sKh = reinterpret_cast<_Float16*>(smem);  // [32][KH_LD]
@@ -110,8 +97,8 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
         float qreg[32];
 #pragma unroll
         for (int g = 0; g < 8; ++g) {
-            f4v v = {0.f, 0.f, 0.f, 0.f};
-            if (qok) v = *reinterpret_cast<const f4v*>(qrow + 8 * g + 4 * hh);
+            f32x4_t v = {0.f, 0.f, 0.f, 0.f};
+            if (qok) v = *reinterpret_cast<const f32x4_t*>(qrow + 8 * g + 4 * hh);
             qreg[4 * g + 0] = v[0];
             qreg[4 * g + 1] = v[1];
             qreg[4 * g + 2] = v[2];
@@ -119,18 +106,18 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
         }
         for (int idx = tid; idx < npos * (HD / 4); idx += 256) {
             const int r = idx >> 4, c4 = idx & 15;
-            *reinterpret_cast<f4v*>(&sR[r * KS + c4 * 4]) = *reinterpret_cast<const f4v*>(p.rel_k + r * HD + c4 * 4);
+            *reinterpret_cast<f32x4_t*>(&sR[r * KS + c4 * 4]) = *reinterpret_cast<const f32x4_t*>(p.rel_k + r * HD + c4 * 4);
         }
         __syncthreads();
 #pragma unroll 1
         for (int f = 0; f < 3; ++f) {
             if (f * 32 >= npos) break;
-            f16v qr;
+            float16_t qr;
 #pragma unroll
             for (int r = 0; r < 16; ++r) qr[r] = 0.f;
 #pragma unroll
             for (int g = 0; g < 8; ++g) {
-                const f4v r4 = *reinterpret_cast<const f4v*>(&sR[(f * 32 + ql) * KS + 8 * g + 4 * hh]);
+                const f32x4_t r4 = *reinterpret_cast<const f32x4_t*>(&sR[(f * 32 + ql) * KS + 8 * g + 4 * hh]);
                 qr = __builtin_amdgcn_mfma_f32_32x32x2f32(r4[0], qreg[4 * g + 0], qr, 0, 0, 0);
                 qr = __builtin_amdgcn_mfma_f32_32x32x2f32(r4[1], qreg[4 * g + 1], qr, 0, 0, 0);
                 qr = __builtin_amdgcn_mfma_f32_32x32x2f32(r4[2], qreg[4 * g + 2], qr, 0, 0, 0);
@@ -146,15 +133,15 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
 
     // Q^T operand: chunk c (dims 16c .. 16c+15), this lane's half holds dims 16c + 8 hh .. + 7.  RELPOS: q + u for the
     // content term, q + v (second operand set) for the position term.
-    a16_h8 qh[4], qlo[4], qvh[RELPOS ? 4 : 1], qvl[RELPOS ? 4 : 1];
+    half8_t qh[4], qlo[4], qvh[RELPOS ? 4 : 1], qvl[RELPOS ? 4 : 1];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         float x[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) x[e] = 0.f;
         if (qok) {
-            const f4v v0 = *reinterpret_cast<const f4v*>(qrow + 16 * c + 8 * hh);
-            const f4v v1 = *reinterpret_cast<const f4v*>(qrow + 16 * c + 8 * hh + 4);
+            const f32x4_t v0 = *reinterpret_cast<const f32x4_t*>(qrow + 16 * c + 8 * hh);
+            const f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(qrow + 16 * c + 8 * hh + 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 x[e] = v0[e];
@@ -168,14 +155,14 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
                 xu[e] = x[e] + p.q_bias_u[h * HD + 16 * c + 8 * hh + e];
                 xv[e] = x[e] + p.q_bias_v[h * HD + 16 * c + 8 * hh + e];
             }
-            a16_split8(xu, qh[c], qlo[c]);
-            a16_split8(xv, qvh[c], qvl[c]);
+            split8(xu, qh[c], qlo[c]);
+            split8(xv, qvh[c], qvl[c]);
         } else {
-            a16_split8(x, qh[c], qlo[c]);
+            split8(x, qh[c], qlo[c]);
         }
     }
 
-    f16v o0, o1;  // O^T: dims 0..31 / 32..63 (rows) x queries (lanes)
+    float16_t o0, o1;  // O^T: dims 0..31 / 32..63 (rows) x queries (lanes)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         o0[r] = 0.f;
@@ -188,17 +175,17 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
 
     // staging role of this thread: float4 pieces idx = tid, tid + 256 of the [32 keys][16 pieces] tile
     const int sr0 = tid >> 4, sc4 = tid & 15;  // keys sr0 and sr0 + 16, dims 4 sc4 .. 4 sc4 + 3
-    f4v kf[2], vf[2];
+    f32x4_t kf[2], vf[2];
     auto fetch = [&](int k0) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int r = sr0 + 16 * u;
-            kf[u] = f4v{0.f, 0.f, 0.f, 0.f};
+            kf[u] = f32x4_t{0.f, 0.f, 0.f, 0.f};
             vf[u] = kf[u];
             if (k0 + r < kv_len) {
                 const int64_t row = kvbase + k0 + r;
-                kf[u] = *reinterpret_cast<const f4v*>(p.k + row * p.ldk + h * HD + sc4 * 4);
-                vf[u] = *reinterpret_cast<const f4v*>(p.v + row * p.ldv + h * HD + sc4 * 4);
+                kf[u] = *reinterpret_cast<const f32x4_t*>(p.k + row * p.ldk + h * HD + sc4 * 4);
+                vf[u] = *reinterpret_cast<const f32x4_t*>(p.v + row * p.ldv + h * HD + sc4 * 4);
             }
         }
     };
@@ -209,7 +196,7 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int r = sr0 + 16 * u;
-            a16_h4 khi, klo, vhi, vlo;
+            half4_t khi, klo, vhi, vlo;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const _Float16 a = (_Float16)kf[u][e];
@@ -219,8 +206,8 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
                 vhi[e] = b;
                 vlo[e] = (_Float16)(vf[u][e] - (float)b);
             }
-            *reinterpret_cast<a16_h4*>(&sKh[r * KH_LD + 4 * sc4]) = khi;
-            *reinterpret_cast<a16_h4*>(&sKl[r * KH_LD + 4 * sc4]) = klo;
+            *reinterpret_cast<half4_t*>(&sKh[r * KH_LD + 4 * sc4]) = khi;
+            *reinterpret_cast<half4_t*>(&sKl[r * KH_LD + 4 * sc4]) = klo;
             // V^T: position of key r inside its 16-chunk = 8 * half + e with key = (e & 3) + 8 (e >> 2) + 4 half
             const int w = r & 15;
             const int pos = (r & 16) + 8 * ((w >> 2) & 1) + (w & 3) + 4 * (w >> 3);
@@ -270,13 +257,13 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
             for (int blk = 0; blk < 2; ++blk) {
                 const int trow = min(max(t0w + blk * 32 + ql, 0), t_max);
                 const float* rrow = p.rp_table + (int64_t)trow * p.rp_ld + h * HD + 8 * hh;
-                f4v ra[4][2];
+                f32x4_t ra[4][2];
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    ra[c][0] = *reinterpret_cast<const f4v*>(rrow + 16 * c);
-                    ra[c][1] = *reinterpret_cast<const f4v*>(rrow + 16 * c + 4);
+                    ra[c][0] = *reinterpret_cast<const f32x4_t*>(rrow + 16 * c);
+                    ra[c][1] = *reinterpret_cast<const f32x4_t*>(rrow + 16 * c + 4);
                 }
-                f16v tt;
+                float16_t tt;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) tt[r] = 0.f;
 #pragma unroll
@@ -287,8 +274,8 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
                         x[e] = ra[c][0][e];
                         x[4 + e] = ra[c][1][e];
                     }
-                    a16_h8 rh, rl;
-                    a16_split8(x, rh, rl);
+                    half8_t rh, rl;
+                    split8(x, rh, rl);
                     tt = __builtin_amdgcn_mfma_f32_32x32x16_f16(rh, qvh[c], tt, 0, 0, 0);
                     tt = __builtin_amdgcn_mfma_f32_32x32x16_f16(rh, qvl[c], tt, 0, 0, 0);
                     tt = __builtin_amdgcn_mfma_f32_32x32x16_f16(rl, qvh[c], tt, 0, 0, 0);
@@ -303,13 +290,13 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
             }
         }
         // ---- S^T = K . Q^T (rows = keys, lanes = queries): three terms per 16-wide chunk ------------------
-        f16v st;
+        float16_t st;
 #pragma unroll
         for (int r = 0; r < 16; ++r) st[r] = 0.f;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            const a16_h8 kh = *reinterpret_cast<const a16_h8*>(&sKh[ql * KH_LD + 16 * c + 8 * hh]);
-            const a16_h8 kl = *reinterpret_cast<const a16_h8*>(&sKl[ql * KH_LD + 16 * c + 8 * hh]);
+            const half8_t kh = *reinterpret_cast<const half8_t*>(&sKh[ql * KH_LD + 16 * c + 8 * hh]);
+            const half8_t kl = *reinterpret_cast<const half8_t*>(&sKl[ql * KH_LD + 16 * c + 8 * hh]);
             st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qh[c], st, 0, 0, 0);
             st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh, qlo[c], st, 0, 0, 0);
             st = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl, qh[c], st, 0, 0, 0);
@@ -353,12 +340,12 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
             float x[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) x[e] = st[8 * c + e];
-            a16_h8 ph, pl;
-            a16_split8(x, ph, pl);
-            const a16_h8 v0h = *reinterpret_cast<const a16_h8*>(&sVh[ql * VT_LD + 16 * c + 8 * hh]);
-            const a16_h8 v0l = *reinterpret_cast<const a16_h8*>(&sVl[ql * VT_LD + 16 * c + 8 * hh]);
-            const a16_h8 v1h = *reinterpret_cast<const a16_h8*>(&sVh[(32 + ql) * VT_LD + 16 * c + 8 * hh]);
-            const a16_h8 v1l = *reinterpret_cast<const a16_h8*>(&sVl[(32 + ql) * VT_LD + 16 * c + 8 * hh]);
+            half8_t ph, pl;
+            split8(x, ph, pl);
+            const half8_t v0h = *reinterpret_cast<const half8_t*>(&sVh[ql * VT_LD + 16 * c + 8 * hh]);
+            const half8_t v0l = *reinterpret_cast<const half8_t*>(&sVl[ql * VT_LD + 16 * c + 8 * hh]);
+            const half8_t v1h = *reinterpret_cast<const half8_t*>(&sVh[(32 + ql) * VT_LD + 16 * c + 8 * hh]);
+            const half8_t v1l = *reinterpret_cast<const half8_t*>(&sVl[(32 + ql) * VT_LD + 16 * c + 8 * hh]);
             o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0h, ph, o0, 0, 0, 0);
             o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v1h, ph, o1, 0, 0, 0);
             o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(v0h, pl, o0, 0, 0, 0);
@@ -383,16 +370,16 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
         const int row = it * 4 + (lane >> 4);
         const int c0 = (lane & 15) * 4;
         const int qq = q0 + row;
-        const f4v of = *reinterpret_cast<const f4v*>(&ot[row * KS + c0]);
+        const f32x4_t of = *reinterpret_cast<const f32x4_t*>(&ot[row * KS + c0]);
         if (qq >= sq_n) continue;
         if (p.out_hi) {
-            const a16_h4 hi = __builtin_convertvector(of, a16_h4);
-            const f4v back = __builtin_convertvector(hi, f4v);
+            const half4_t hi = __builtin_convertvector(of, half4_t);
+            const f32x4_t back = __builtin_convertvector(hi, f32x4_t);
             const int64_t off = (qbase + qq) * p.ldoh + h * HD + c0;
-            *reinterpret_cast<a16_h4*>(p.out_hi + off) = hi;
-            *reinterpret_cast<a16_h4*>(p.out_lo + off) = __builtin_convertvector(of - back, a16_h4);
+            *reinterpret_cast<half4_t*>(p.out_hi + off) = hi;
+            *reinterpret_cast<half4_t*>(p.out_lo + off) = __builtin_convertvector(of - back, half4_t);
         } else {
-            *reinterpret_cast<f4v*>(p.out + (qbase + qq) * p.ldo + h * HD + c0) = of;
+            *reinterpret_cast<f32x4_t*>(p.out + (qbase + qq) * p.ldo + h * HD + c0) = of;
         }
     }
 }
@@ -400,12 +387,8 @@ __global__ __launch_bounds__(256) void attn_mfma16_kernel(AttnArgs p) {
 static bool g_attn_attr_set = false;
 
 void launch_attention(const AttnArgs& a, hipStream_t s) {
-    if (a.head_dim == 80) {
-        launch_attention80(a, s);
-        return;
-    }
-    if (a.head_dim == 128) {
-        launch_attention128(a, s);
+    if (a.head_dim == 80 || a.head_dim == 128) {
+        launch_attention_hd(a, s);
         return;
     }
     SC_CHECK(a.head_dim == HD, "attention: head_dim=%d (64, 80 and 128 exist)", a.head_dim);

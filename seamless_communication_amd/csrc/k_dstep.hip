@@ -21,36 +21,15 @@
 //
 // Reference semantics of the step: ggml/examples/unity/fairseq2.cpp:979-1094 (StandardTransformerDecoderLayer),
 // src/seamless_communication/models/unity/model.py:233-260 (decode / project).
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef float float16_t __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
 namespace {
 
-constexpr uint32_t OOB = 0x80000000u;  // >= num_records of every buffer used here (all below 2 GB): reads as zero
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ds_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
-
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 nt_load4(const float* p) {  // 16-byte non-temporal load
     const f32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const f32x4_t*>(p));
     return make_float4(v[0], v[1], v[2], v[3]);
-}
-
-__device__ __forceinline__ void split8(const float* x, half8_t& hi, half8_t& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const _Float16 h = (_Float16)x[e];
-        hi[e] = h;
-        lo[e] = (_Float16)(x[e] - (float)h);
-    }
 }
 
 // --------------------------------------------------------------------------------------------- //
@@ -89,9 +68,9 @@ __global__ __launch_bounds__(256) void gemvp_kernel(GemvPArgs p) {
     const int ks_end = min(p.KS, (split + 1) * p.ks_per_wg);
     const int ks_w0 = split * p.ks_per_wg + wave * (4 * NCH);
 
-    const __amdgpu_buffer_rsrc_t rw = ds_rsrc(p.Wp, p.w_bytes);
-    const __amdgpu_buffer_rsrc_t rah = ds_rsrc(p.Ah, p.a_bytes);
-    const __amdgpu_buffer_rsrc_t ral = ds_rsrc(p.Al, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rw = raw_buffer_rsrc(p.Wp, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t rah = raw_buffer_rsrc(p.Ah, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t ral = raw_buffer_rsrc(p.Al, p.a_bytes);
     const uint32_t w_voff = (uint32_t)lane * 16u;
     uint32_t a_voff[MT];
     const int live = p.d_rows ? min(*p.d_rows, p.M) : p.M;  // rows behind the live rows are neither read nor written
@@ -202,7 +181,7 @@ __global__ __launch_bounds__(256) void gemvp_kernel(GemvPArgs p) {
                     v[e] = (red[0][i][o] + red[1][i][o]) + (red[2][i][o] + red[3][i][o]);
                     const int feat = nt * 32 + 8 * g + e;
                     if (p.bias && feat < p.N) v[e] += p.bias[feat];
-                    if (p.act == ACT_RELU) v[e] = !(v[e] <= 0.f) ? v[e] : 0.f;  // NaN stays NaN
+                    if (p.act == ACT_RELU) v[e] = relu_keep_nan(v[e]);
                     if (feat >= p.N) v[e] = 0.f;
                 }
                 if (m < live && (nt * 4 + g) * 8 < p.N) {
@@ -391,7 +370,7 @@ __global__ __launch_bounds__(256) void reduce_ln_kernel(ReduceLnArgs p) {
         half4_t hi, lo;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const _Float16 hh = (_Float16)o4[e];
+            const _Float16 hh = (_Float16)o4[e];  // the split, inline: split1 through temporaries changes the instruction stream
             hi[e] = hh;
             lo[e] = (_Float16)(o4[e] - (float)hh);
         }
@@ -604,9 +583,10 @@ __global__ __launch_bounds__(256) void dattn_kernel(DAttnArgs p) {
         half4_t hi, lo;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const _Float16 hh = (_Float16)o4[e];
-            hi[e] = hh;
-            lo[e] = (_Float16)(o4[e] - (float)hh);
+            _Float16 s_hi, s_lo;  // a vector lane does not bind to a reference
+            split1(o4[e], s_hi, s_lo);
+            hi[e] = s_hi;
+            lo[e] = s_lo;
         }
         const int64_t off = ((int64_t)(hd * 8 + (c >> 1)) * p.ORB + b) * 8 + (c & 1) * 4;
         *reinterpret_cast<half4_t*>(p.Oh + off) = hi;
@@ -630,10 +610,8 @@ __global__ __launch_bounds__(256) void rows_to_planes_kernel(const float* __rest
     if (idx >= rows * C) return;
     const int row = idx / C, k = idx - row * C;
     const float v = x[(int64_t)row * ldx + k];
-    const _Float16 hh = (_Float16)v;
     const int64_t off = ((int64_t)(k >> 3) * RB + row) * 8 + (k & 7);
-    reinterpret_cast<_Float16*>(Hh)[off] = hh;
-    reinterpret_cast<_Float16*>(Hl)[off] = (_Float16)(v - (float)hh);
+    split1(v, reinterpret_cast<_Float16*>(Hh)[off], reinterpret_cast<_Float16*>(Hl)[off]);
 }
 
 }  // namespace

@@ -25,36 +25,14 @@
 //
 // Reference semantics: ggml/examples/unity/fairseq2.cpp:979-1094 (StandardTransformerDecoderLayer, pre-LN),
 // src/seamless_communication/models/unity/model.py:233-260 (decode / project).
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef float float16_t __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 namespace {
 
-constexpr uint32_t OOB = 0x80000000u;  // >= num_records of every buffer used here (all below 2 GB): reads as zero
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc3(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
-
-// ACT_GELU (kernels.h): the exact erf form of torch.nn.GELU(); erff(NaN) is NaN, so a NaN stays NaN.  A compile-time variant
-// of the plane epilogues (template parameter GELU): the kernels of the ReLU models are the instantiations they were.
-__device__ __forceinline__ float gelu3(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
-
-__device__ __forceinline__ void split8v(const float* x, half8_t& hi, half8_t& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const _Float16 h = (_Float16)x[e];
-        hi[e] = h;
-        lo[e] = (_Float16)(x[e] - (float)h);
-    }
-}
+// gelu_erf (ACT_GELU) is a compile-time variant of the plane epilogues (template parameter GELU): the kernels of the ReLU
+// models are the instantiations they were.
 
 // --------------------------------------------------------------------------------------------- //
 // gemv3_kernel<NT, MT, WAVES, KSW, IN, EPI>
@@ -95,7 +73,7 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3_kernel(Gemv3Args p) {
     const int chunk = (wave + rot) % WAVES;
     const int ks_w0 = (blockIdx.z * WAVES + chunk) * KSW;
 
-    const __amdgpu_buffer_rsrc_t rw = rsrc3(p.Wp, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t rw = raw_buffer_rsrc(p.Wp, p.w_bytes);
     const uint32_t w_voff = (uint32_t)lane * 16u;
 
     // ---- every global load of the workgroup is issued here, before the first use ---------------------------------
@@ -123,8 +101,8 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3_kernel(Gemv3Args p) {
     u32x4_t ah[IN == IN3_PLANES ? MT : 1][KSW], al[IN == IN3_PLANES ? MT : 1][KSW];
     float xr[IN == IN3_LN ? MT : 1][KSW][8];
     if (IN == IN3_PLANES) {
-        const __amdgpu_buffer_rsrc_t rah = rsrc3(p.Ah, p.a_bytes);
-        const __amdgpu_buffer_rsrc_t ral = rsrc3(p.Al, p.a_bytes);
+        const __amdgpu_buffer_rsrc_t rah = raw_buffer_rsrc(p.Ah, p.a_bytes);
+        const __amdgpu_buffer_rsrc_t ral = raw_buffer_rsrc(p.Al, p.a_bytes);
         const uint32_t a_kstep = (uint32_t)(2 * p.RB * 16);  // bytes per k-step in a plane
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
@@ -138,7 +116,7 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3_kernel(Gemv3Args p) {
             }
         }
     } else {
-        const __amdgpu_buffer_rsrc_t rx = rsrc3(p.xg, p.a_bytes);
+        const __amdgpu_buffer_rsrc_t rx = raw_buffer_rsrc(p.xg, p.a_bytes);
         const uint32_t x_kstep = (uint32_t)(2 * p.RB * 32);  // bytes per k-step of the fp32 stream
 #pragma unroll
         for (int i = 0; i < MT; ++i) {
@@ -275,7 +253,7 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3_kernel(Gemv3Args p) {
                 float y[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) y[e] = (xr[i][j][e] - mean[i]) * rstd[i] * g8[e] + b8[e];
-                split8v(y, bh[i], bl[i]);
+                split8(y, bh[i], bl[i]);
             }
         }
 #pragma unroll
@@ -317,14 +295,14 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3_kernel(Gemv3Args p) {
 #pragma unroll
                 for (int c = 0; c < WAVES; ++c) s += red[c][jj][o];
                 s += bias8[it][e];
-                if constexpr (GELU) s = gelu3(s);
-                else if (p.act == ACT_RELU) s = !(s <= 0.f) ? s : 0.f;  // NaN stays NaN
+                if constexpr (GELU) s = gelu_erf(s);
+                else if (p.act == ACT_RELU) s = relu_keep_nan(s);
                 if ((nt0 + jt) * 32 + 8 * g + e >= p.N) s = 0.f;
                 v[e] = s;
             }
             if (32 * i + rn < p.rg && row < live && ((nt0 + jt) * 4 + g) * 8 < p.N) {
                 half8_t hi, lo;
-                split8v(v, hi, lo);
+                split8(v, hi, lo);
                 const int64_t off = ((int64_t)((nt0 + jt) * 4 + g) * p.ORB + row) * 8;
                 *reinterpret_cast<half8_t*>(p.Oh + off) = hi;
                 *reinterpret_cast<half8_t*>(p.Ol + off) = lo;
@@ -405,7 +383,7 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3s_kernel(Gemv3Args p) {
     const int ks_w0 = (bz * WAVES + chunk) * KSW;
 
     // ---- the workgroup's weights: once, before anything else --------------------------------------------------------
-    const __amdgpu_buffer_rsrc_t rw = rsrc3(p.Wp, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t rw = raw_buffer_rsrc(p.Wp, p.w_bytes);
     const uint32_t w_voff = (uint32_t)lane * 16u;
     u32x4_t w[NT][KSW];
 #pragma unroll
@@ -419,8 +397,8 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3s_kernel(Gemv3Args p) {
                                       : __builtin_amdgcn_raw_buffer_load_b128(rw, w_voff | tkill | kk, w_tile + (uint32_t)(ks_w0 + j) * 1024u, 0);
         }
     }
-    const __amdgpu_buffer_rsrc_t ra0 = rsrc3(IN == IN3_PLANES ? (const void*)p.Ah : (const void*)p.xg, p.a_bytes);
-    const __amdgpu_buffer_rsrc_t ra1 = rsrc3(IN == IN3_PLANES ? (const void*)p.Al : (const void*)p.xg, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t ra0 = raw_buffer_rsrc(IN == IN3_PLANES ? (const void*)p.Ah : (const void*)p.xg, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t ra1 = raw_buffer_rsrc(IN == IN3_PLANES ? (const void*)p.Al : (const void*)p.xg, p.a_bytes);
     constexpr uint32_t ESZ = IN == IN3_PLANES ? 16u : 32u;        // bytes of a row's 8 columns
     const uint32_t a_kstep = (uint32_t)(2 * p.RB) * ESZ;          // bytes per k-step
     // ---- touch: the launch's workgroups on this XCD bring the live rows of the k-groups they will read into its L2, each a
@@ -573,7 +551,7 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3s_kernel(Gemv3Args p) {
                         y[e] = (v0[e] - mean[i]) * rstd[i] * g8[e] + b8[e];
                         y[4 + e] = (v1[e] - mean[i]) * rstd[i] * g8[4 + e] + b8[4 + e];
                     }
-                    split8v(y, bh[i], bl[i]);
+                    split8(y, bh[i], bl[i]);
                 }
             }
 #pragma unroll
@@ -615,14 +593,14 @@ __global__ __launch_bounds__(64 * WAVES) void gemv3s_kernel(Gemv3Args p) {
 #pragma unroll
                     for (int c = 0; c < WAVES; ++c) s += red[c][jj][o];
                     s += bias8[it][e];
-                    if constexpr (GELU) s = gelu3(s);
-                    else if (p.act == ACT_RELU) s = !(s <= 0.f) ? s : 0.f;  // NaN stays NaN
+                    if constexpr (GELU) s = gelu_erf(s);
+                    else if (p.act == ACT_RELU) s = relu_keep_nan(s);
                     if ((nt0 + jt) * 32 + 8 * gq + e >= p.N) s = 0.f;
                     v[e] = s;
                 }
                 if (32 * i + rn < p.rg && row < live && ((nt0 + jt) * 4 + gq) * 8 < p.N) {
                     half8_t hi, lo;
-                    split8v(v, hi, lo);
+                    split8(v, hi, lo);
                     const int64_t off = ((int64_t)((nt0 + jt) * 4 + gq) * p.ORB + row) * 8;
                     *reinterpret_cast<half8_t*>(p.Oh + off) = hi;
                     *reinterpret_cast<half8_t*>(p.Ol + off) = lo;
@@ -687,7 +665,7 @@ __global__ __launch_bounds__(1024) void gemv3t_kernel(Gemv3Args p) {
 
     // ---- the workgroup's weight fragments -> LDS (fragment order: one wave instruction = one KiB) ----------------------
     {
-        const __amdgpu_buffer_rsrc_t rw = rsrc3(p.Wp, p.w_bytes);
+        const __amdgpu_buffer_rsrc_t rw = raw_buffer_rsrc(p.Wp, p.w_bytes);
         constexpr int U = (2 * KSL * 64) / 1024;
         u32x4_t wr[U];
 #pragma unroll
@@ -707,8 +685,8 @@ __global__ __launch_bounds__(1024) void gemv3t_kernel(Gemv3Args p) {
     __syncthreads();
 
     const int ft = wave & 1, rt = wave >> 1;
-    const __amdgpu_buffer_rsrc_t rah = rsrc3(p.Ah, p.a_bytes);
-    const __amdgpu_buffer_rsrc_t ral = rsrc3(p.Al, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t rah = raw_buffer_rsrc(p.Ah, p.a_bytes);
+    const __amdgpu_buffer_rsrc_t ral = raw_buffer_rsrc(p.Al, p.a_bytes);
     const uint32_t a_kstep = (uint32_t)(2 * p.RB * 16);
     for (int pass0 = 0; pass0 + rt * 32 < live; pass0 += 256) {
         asm volatile("" ::: "memory");  // the weight fragments are read from LDS per pass (hoisted out of the loop they are 128 registers: spills)
@@ -843,7 +821,7 @@ __global__ __launch_bounds__(256) void reduce3_kernel(Reduce3Args p) {
         half4_t hi, lo;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const _Float16 hh = (_Float16)o4[e];
+            const _Float16 hh = (_Float16)o4[e];  // the split, inline: split1 through temporaries changes the instruction stream
             hi[e] = hh;
             lo[e] = (_Float16)(o4[e] - (float)hh);
         }
@@ -899,9 +877,10 @@ __global__ __launch_bounds__(256) void ln3_kernel(const float* __restrict__ xg, 
     half4_t hi, lo;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const _Float16 hh = (_Float16)o4[e];
-        hi[e] = hh;
-        lo[e] = (_Float16)(o4[e] - (float)hh);
+        _Float16 s_hi, s_lo;  // a vector lane does not bind to a reference
+        split1(o4[e], s_hi, s_lo);
+        hi[e] = s_hi;
+        lo[e] = s_lo;
     }
     const int64_t off = ((int64_t)(tid >> 1) * RB + row) * 8 + (tid & 1) * 4;
     *reinterpret_cast<half4_t*>(Hh + off) = hi;
@@ -984,7 +963,7 @@ __global__ __launch_bounds__(64 * WAVES) void vocab3_kernel(Vocab3Args p) {
     if (p.d_rows && r0 >= *p.d_rows) return;  // beam search: a row group of finished utterances
     const int t_lo = grp * p.tpg, t_hi = min(p.NT_total, t_lo + p.tpg);
 
-    const __amdgpu_buffer_rsrc_t rw = rsrc3(p.Wp, p.w_bytes);
+    const __amdgpu_buffer_rsrc_t rw = raw_buffer_rsrc(p.Wp, p.w_bytes);
     const uint32_t w_voff = (uint32_t)lane * 16u;
     u32x4_t wb[2][16];
 #define V3_LOADW(B, TILE, C)                                                                                          \

@@ -24,29 +24,17 @@
 //   ecapa_gcmvn_kernel    (x - mean) / std on the frames in front of an item's length, zeros behind.
 #include <algorithm>
 
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float float16_t __attribute__((ext_vector_type(16)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 namespace {
-
-// ReLU that keeps NaN (fmaxf would answer 0): an overflowed row must stay visible
-__device__ __forceinline__ float relu_nan(float v) { return !(v <= 0.f) ? v : 0.f; }
 
 constexpr int EC_ROWS = 256;     // frames a workgroup computes per stage: 8 waves x one 32-row MFMA fragment
 constexpr int EC_G = 8;          // zero guard rows on both sides of the planes = the largest dilation
 constexpr int EC_THREADS = 512;
 constexpr float EC_EPS = 1e-12f;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
 __device__ __forceinline__ float half_wave_sum(float v) {  // over the 32 lanes that share lane >> 5
 #pragma unroll
     for (int m = 16; m >= 1; m >>= 1) v += __shfl_xor(v, m);
@@ -104,9 +92,7 @@ __global__ __launch_bounds__(EC_THREADS) void ecapa_chain_kernel(EcapaChainArgs 
                 const int t = t_first + j;
                 float v = 0.f;
                 if (t >= 0 && t < T) v = xn[(int64_t)t * p.ldx + s * CW + col] + y[nf][r];
-                const _Float16 h = (_Float16)v;
-                ph[(EC_G + j) * CS + col] = h;
-                pl[(EC_G + j) * CS + col] = (_Float16)(v - (float)h);
+                split1(v, ph[(EC_G + j) * CS + col], pl[(EC_G + j) * CS + col]);
             }
         }
         {
@@ -153,7 +139,7 @@ __global__ __launch_bounds__(EC_THREADS) void ecapa_chain_kernel(EcapaChainArgs 
             float v[NF], sum = 0.f;
 #pragma unroll
             for (int nf = 0; nf < NF; ++nf) {
-                v[nf] = relu_nan(acc[nf][r] + bs[nf]);
+                v[nf] = relu_keep_nan(acc[nf][r] + bs[nf]);
                 sum += v[nf];
             }
             const float mean = half_wave_sum(sum) * (1.0f / CW);
@@ -186,17 +172,17 @@ __global__ __launch_bounds__(256) void ecapa_relu_ln_kernel(const float* __restr
     const float* xr = x + (int64_t)row * ldx;
     const float* ib = item_bias ? item_bias + (int64_t)(row / t_per_item) * C : nullptr;
     float sum = 0.f;
-    for (int c = lane; c < C; c += 64) sum += relu_nan(xr[c] + (ib ? ib[c] : 0.f));
+    for (int c = lane; c < C; c += 64) sum += relu_keep_nan(xr[c] + (ib ? ib[c] : 0.f));
     const float mean = wave_sum(sum) / (float)C;
     float sq = 0.f;
     for (int c = lane; c < C; c += 64) {
-        const float d = relu_nan(xr[c] + (ib ? ib[c] : 0.f)) - mean;
+        const float d = relu_keep_nan(xr[c] + (ib ? ib[c] : 0.f)) - mean;
         sq += d * d;
     }
     const float inv = 1.0f / sqrtf(wave_sum(sq) / (float)C + EC_EPS);
     float* yr = y + (int64_t)row * ldy;
     for (int c = lane; c < C; c += 64) {  // y may be x: a lane reads an element before it writes the same element
-        float o = (relu_nan(xr[c] + (ib ? ib[c] : 0.f)) - mean) * inv * g[c] + b[c];
+        float o = (relu_keep_nan(xr[c] + (ib ? ib[c] : 0.f)) - mean) * inv * g[c] + b[c];
         if (act == ACT_TANH) o = tanhf(o);
         yr[c] = o;
     }
@@ -232,7 +218,7 @@ __global__ __launch_bounds__(1024) void ecapa_se_gate_kernel(const float* __rest
         float a = 0.f;
         for (int c = lane; c < C; c += 64) a += __half2float(w1[(int64_t)j * C + c]) * sm[c];
         a = wave_sum(a);
-        if (lane == 0) hh[j] = relu_nan(a + b1[j]);
+        if (lane == 0) hh[j] = relu_keep_nan(a + b1[j]);
     }
     __syncthreads();
     for (int c = tid; c < C; c += 1024) {

@@ -18,26 +18,14 @@
 #include <atomic>
 #include <cstdlib>
 
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
 std::atomic<int> g_force_general_gemm{0};
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef float float16_t __attribute__((ext_vector_type(16)));
-
 static constexpr int BK = 32;
 static constexpr int LDS_LD = 40;  // halfs per LDS row (32 + 8 pad)
-
-__device__ __forceinline__ float apply_act(float v, int act) {
-    if (act == ACT_RELU) return !(v <= 0.f) ? v : 0.f;  // NaN stays NaN, -0 -> +0
-    if (act == ACT_SILU) return v / (1.f + expf(-v));
-    if (act == ACT_TANH) return tanhf(v);
-    if (act == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-    return v;
-}
 
 __device__ __forceinline__ float apply_in_act(float v, int in_act) {
     if (in_act == IN_LRELU_01) return v > 0.f ? v : 0.1f * v;
@@ -170,7 +158,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float v = apply_in_act(x[j], p.in_act);
-                const _Float16 h = (_Float16)v;
+                const _Float16 h = (_Float16)v;  // the split, inline: split1 through temporaries changes the instruction stream
                 hi[j] = h;
                 lo[j] = (_Float16)(v - (float)h);
             }
@@ -257,7 +245,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
                 if (col >= p.N) continue;
                 float v = acc[i][j][r];
                 if (p.bias) v += p.bias[col];
-                v = apply_act(v, p.act) * p.alpha;
+                v = act(v, p.act) * p.alpha;
                 if (p.res) v += p.res[row * p.ldr + col];
                 p.C[row * p.ldc + col] = v;
             }
@@ -375,7 +363,7 @@ __global__ __launch_bounds__(256) void gemv_kernel(const float* __restrict__ x, 
         if (lane == 0 && m < M) {
             float v = a;
             if (bias) v += bias[n];
-            v = apply_act(v, act) * alpha;
+            v = sc::act(v, act) * alpha;
             if (res) v += res[m * ldr + n];
             out[m * ldo + n] = v;
         }

@@ -19,15 +19,9 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
-
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef float float16_t __attribute__((ext_vector_type(16)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -35,15 +29,6 @@ constexpr int GEMM_GROUP_M_DEFAULT = 1;
 constexpr int GEMM_PF2_DEFAULT = 1;
 constexpr int FBK = 32;
 constexpr int FLD = 40;  // halfs per LDS row (32 + 8 pad): 16-byte fragment reads of a lane group hit distinct banks
-
-template <int ACT>
-__device__ __forceinline__ float act_fn(float v) {
-    if (ACT == ACT_RELU) return !(v <= 0.f) ? v : 0.f;  // NaN stays NaN, -0 -> +0
-    if (ACT == ACT_SILU) return v / (1.f + expf(-v));
-    if (ACT == ACT_TANH) return tanhf(v);
-    if (ACT == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-    return v;
-}
 
 template <int TM, int TN, int WM, int WN, int ACT, bool HAS_RES>
 __device__ __forceinline__ void epilogue(const GemmArgs& p, float16_t (&acc)[TM][TN], int m0w, int n0w, int lane,
@@ -81,7 +66,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& p, float16_t (&acc)[TM]
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
                 if (col[j] >= p.N) continue;
-                float v = act_fn<ACT>(acc[i][j][r] + bcol[j]) * p.alpha;
+                float v = act<ACT>(acc[i][j][r] + bcol[j]) * p.alpha;
                 if (HAS_RES) v += p.res[row * p.ldr + col[j]];
                 p.C[row * p.ldc + col[j]] = v;
             }
@@ -144,7 +129,7 @@ __device__ __forceinline__ void epilogue_lds(const GemmArgs& p, float16_t (&acc)
             }
             f32x4_t v;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = act_fn<ACT>(a[e] + b4[e]) * p.alpha;
+            for (int e = 0; e < 4; ++e) v[e] = act<ACT>(a[e] + b4[e]) * p.alpha;
             if (vec_ok) {
                 if (HAS_RES) v += *reinterpret_cast<const f32x4_t*>(p.res + row * p.ldr + col);
                 *reinterpret_cast<f32x4_t*>(p.C + row * p.ldc + col) = v;
@@ -376,10 +361,6 @@ __global__ __launch_bounds__(256) void gemm_fast_kernel(GemmArgs p, int tiles_n,
 // while slab s is multiplied out of LDS, slab s+1 is in one set and the loads of slab s+2 go into the
 // other, so a load has two MFMA phases to arrive.  Same arithmetic and K order as the kernels above.
 // ------------------------------------------------------------------------------------------------- //
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
-}
-
 template <int BM, int BN, int WGM, int WGN, bool IN_ACT>
 __global__ __launch_bounds__(256) void gemm_fast2_kernel(GemmArgs p, int tiles_n, int tiles_mn, int tiles_total,
                                                          int tiles_per_xcd, float in_slope, uint32_t a_bytes, uint32_t w_bytes) {
@@ -388,7 +369,6 @@ __global__ __launch_bounds__(256) void gemm_fast2_kernel(GemmArgs p, int tiles_n
     constexpr int TM = WM / 32, TN = WN / 32;
     constexpr int A_IT = BM / 32;
     constexpr int B_IT = (BN * 4 + 255) / 256;
-    constexpr uint32_t OOB = 0x80000000u;  // >= num_records of either buffer: the load returns zeros
 
     // one LDS block: [2 stages of A_hi | 2 stages of A_lo | 2 stages of W]; reused by the epilogue as one fp32
     // tile of 32 rows per wave
@@ -414,8 +394,8 @@ __global__ __launch_bounds__(256) void gemm_fast2_kernel(GemmArgs p, int tiles_n
     const int m0 = tm * BM;
     const int n0 = tn * BN;
     const int out_off = p.out_off + phase * p.out_off_phase_step;
-    const __amdgpu_buffer_rsrc_t ra = make_rsrc(p.A, a_bytes);
-    const __amdgpu_buffer_rsrc_t rb = make_rsrc(p.W + (int64_t)phase * p.w_phase_stride, w_bytes);
+    const __amdgpu_buffer_rsrc_t ra = raw_buffer_rsrc(p.A, a_bytes);
+    const __amdgpu_buffer_rsrc_t rb = raw_buffer_rsrc(p.W + (int64_t)phase * p.w_phase_stride, w_bytes);
 
     const int a_kq = tid & 7;
     const int a_r = tid >> 3;

@@ -21,27 +21,16 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float float16_t __attribute__((ext_vector_type(16)));
 
 namespace {
 
 constexpr int PBK = 32;
 #define SC_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
-template <int ACT>
-__device__ __forceinline__ float ps_act(float v) {
-    if (ACT == ACT_RELU) return !(v <= 0.f) ? v : 0.f;  // NaN stays NaN, -0 -> +0
-    if (ACT == ACT_SILU) return v / (1.f + expf(-v));
-    if (ACT == ACT_TANH) return tanhf(v);
-    return v;
-}
-
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
 
 // raw buffer resource: base (48 bit), stride 0, num_records = bytes, dword 3 as for every gfx9 raw buffer
 __device__ __forceinline__ i32x4_t make_rsrc_words(const void* base, uint32_t bytes) {
@@ -62,8 +51,6 @@ __device__ __forceinline__ int swz(int row, int s) { return row * 64 + ((s ^ ((r
 // conflict free and every global access is a run of 16-byte pieces of one output row.
 template <int WM, int WN, int EP_LD, int ACT>
 __device__ __forceinline__ void ps_epilogue(const GemmPsArgs& p, const float* ep, int m0w, int n0w, int lane) {
-    typedef float f4_t __attribute__((ext_vector_type(4)));
-    typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
     constexpr int LPR = WN / 4;        // lanes per row
     constexpr int RPG = 16 / LPR;      // rows per 16-lane group
     constexpr int RPI = 4 * RPG;       // rows per wave instruction
@@ -75,7 +62,7 @@ __device__ __forceinline__ void ps_epilogue(const GemmPsArgs& p, const float* ep
     const int c0 = (rank % LPR) * 4;
     const int col = n0w + c0;
     const bool vec_ok = (col + 3 < p.N) && ((p.ldc | p.ldr | p.ldcs) % 4 == 0) && (n0w % 4 == 0);
-    f4_t b4 = {0.f, 0.f, 0.f, 0.f};
+    f32x4_t b4 = {0.f, 0.f, 0.f, 0.f};
     if (p.bias) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) b4[e] = (col + e < p.N) ? p.bias[col + e] : 0.f;
@@ -84,25 +71,25 @@ __device__ __forceinline__ void ps_epilogue(const GemmPsArgs& p, const float* ep
     for (int it = 0; it < WM / RPI; ++it) {
         const int row = it * RPI + row_in;
         const int64_t m = m0w + row;
-        const f4_t a = *reinterpret_cast<const f4_t*>(ep + row * EP_LD + c0);
+        const f32x4_t a = *reinterpret_cast<const f32x4_t*>(ep + row * EP_LD + c0);
         if (m >= p.M || col >= p.N) continue;
         const bool dead = p.row_valid && p.row_valid[m] == 0;  // padded row of a length bucket: exact zeros
-        f4_t v;
+        f32x4_t v;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = dead ? 0.f : ps_act<ACT>(a[e] + b4[e]) * p.alpha;
+        for (int e = 0; e < 4; ++e) v[e] = dead ? 0.f : act<ACT>(a[e] + b4[e]) * p.alpha;
         if (vec_ok) {
-            if (p.res && !dead) v += *reinterpret_cast<const f4_t*>(p.res + m * p.ldr + col);
-            if (p.C) *reinterpret_cast<f4_t*>(p.C + m * p.ldc + col) = v;
+            if (p.res && !dead) v += *reinterpret_cast<const f32x4_t*>(p.res + m * p.ldr + col);
+            if (p.C) *reinterpret_cast<f32x4_t*>(p.C + m * p.ldc + col) = v;
             if (p.Ch) {
                 if (p.plane_neg_slope != 1.0f) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = lrelu_in(v[e], p.plane_neg_slope);
                 }
-                const h4_t hi = __builtin_convertvector(v, h4_t);
-                *reinterpret_cast<h4_t*>(reinterpret_cast<_Float16*>(p.Ch) + m * p.ldcs + col) = hi;
+                const half4_t hi = __builtin_convertvector(v, half4_t);
+                *reinterpret_cast<half4_t*>(reinterpret_cast<_Float16*>(p.Ch) + m * p.ldcs + col) = hi;
                 if (p.Cl)  // null: the consumer multiplies the hi plane only (GemmPsArgs::split == 0), no lo plane is produced
-                    *reinterpret_cast<h4_t*>(reinterpret_cast<_Float16*>(p.Cl) + m * p.ldcs + col) =
-                        __builtin_convertvector(v - __builtin_convertvector(hi, f4_t), h4_t);
+                    *reinterpret_cast<half4_t*>(reinterpret_cast<_Float16*>(p.Cl) + m * p.ldcs + col) =
+                        __builtin_convertvector(v - __builtin_convertvector(hi, f32x4_t), half4_t);
             }
         } else {
 #pragma unroll
@@ -113,7 +100,7 @@ __device__ __forceinline__ void ps_epilogue(const GemmPsArgs& p, const float* ep
                 if (p.C) p.C[m * p.ldc + col + e] = x;
                 if (p.Ch) {
                     if (p.plane_neg_slope != 1.0f) x = lrelu_in(x, p.plane_neg_slope);
-                    const _Float16 h = (_Float16)x;
+                    const _Float16 h = (_Float16)x;  // not split1: the lo half is formed only where p.Cl takes it
                     reinterpret_cast<_Float16*>(p.Ch)[m * p.ldcs + col + e] = h;
                     if (p.Cl) reinterpret_cast<_Float16*>(p.Cl)[m * p.ldcs + col + e] = (_Float16)(x - (float)h);
                 }

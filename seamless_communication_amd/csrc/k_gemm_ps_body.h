@@ -3,6 +3,7 @@
 //   template / constexpr parameters  BM, BN, WGM, WGN, SPLIT, CONV, AMAX, SCORE
 //   arguments                        GemmPsArgs p, tiles_n, tiles_total, tiles_per_xcd, a_bytes, w_bytes, GemmScoreArgs sc
 // so that the two kernels share every instruction of the K loop while gemm_ps_kernel keeps its own argument list.
+// OOB and the vector types are device_util.h's, which k_gemm_ps.hip includes (this text sits inside a function body).
     constexpr int NWAVE = WGM * WGN;
     constexpr bool ALTERNATE = SPLIT && NWAVE == 8;  // the K loop's schedule, see above
     constexpr bool MID_BARRIER = SPLIT && !ALTERNATE;
@@ -10,7 +11,6 @@
     constexpr int TM = WM / 32, TN = WN / 32;
     constexpr int ACH = BM / (16 * NWAVE);  // 1 KB chunks (16 rows) of the A tile per wave
     constexpr int BCH = BN / (16 * NWAVE);
-    constexpr uint32_t OOB = 0x80000000u;
     constexpr int A_TILE = BM * 32, B_TILE = BN * 32;  // halfs per stage
 
     // three stages of [A_hi | A_lo | W] tiles (without SPLIT: [A_hi | W] - no LDS is set aside for a plane nobody stages: the
@@ -407,12 +407,11 @@
                     ep[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * EP_LD + j * 32 + (lane & 31)] = acc[i][h * (EPN / 32) + j][r];
         const int n0w = n0 + wn * WN + h * EPN;
         if constexpr (AMAX) {
-            typedef float f4_t __attribute__((ext_vector_type(4)));
             if (lane < WM) {
                 const float* row = ep + lane * EP_LD;
 #pragma unroll
                 for (int c4 = 0; c4 < EPN / 4; ++c4) {
-                    const f4_t a = *reinterpret_cast<const f4_t*>(row + 4 * c4);
+                    const f32x4_t a = *reinterpret_cast<const f32x4_t*>(row + 4 * c4);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int col = n0w + 4 * c4 + e;
@@ -429,7 +428,6 @@
             return;
         }
         if constexpr (SCORE) {
-            typedef float f4_t __attribute__((ext_vector_type(4)));
             if (lane < WM && n0w < p.N) {  // (a pass without a column below N leaves the record as it is)
                 const float* row = ep + lane * EP_LD;
                 const float mx_old = am_best;
@@ -437,7 +435,7 @@
                 // is formed twice by the same instructions, the tile is read from LDS twice
 #pragma unroll
                 for (int c4 = 0; c4 < EPN / 4; ++c4) {
-                    const f4_t a = *reinterpret_cast<const f4_t*>(row + 4 * c4);
+                    const f32x4_t a = *reinterpret_cast<const f32x4_t*>(row + 4 * c4);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int col = n0w + 4 * c4 + e;
@@ -456,7 +454,7 @@
                 if (h > 0) sc_sum *= expf(mx_old - am_best);
 #pragma unroll
                 for (int c4 = 0; c4 < EPN / 4; ++c4) {
-                    const f4_t a = *reinterpret_cast<const f4_t*>(row + 4 * c4);
+                    const f32x4_t a = *reinterpret_cast<const f32x4_t*>(row + 4 * c4);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int col = n0w + 4 * c4 + e;

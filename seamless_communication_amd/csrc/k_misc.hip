@@ -1,7 +1,7 @@
 // Small HBM-bound kernels: embedding lookups, arg-max with the beam-search step
 // rules, weight repacking at load time, hard-upsampling gathers, positional
 // terms, duration rounding, vocoder input assembly.
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
@@ -452,13 +452,11 @@ __global__ void avg3_kernel(const float* __restrict__ a, const float* __restrict
         out[i] = ((a[i] + b[i]) + c[i]) / 3.0f;
 }
 __global__ void split_f32_kernel(const float* __restrict__ x, __half* __restrict__ hi, __half* __restrict__ lo, int64_t n4) {
-    typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-    typedef float f4_t __attribute__((ext_vector_type(4)));
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        const f4_t v = reinterpret_cast<const f4_t*>(x)[i];
-        const h4_t h = __builtin_convertvector(v, h4_t);
-        reinterpret_cast<h4_t*>(hi)[i] = h;
-        reinterpret_cast<h4_t*>(lo)[i] = __builtin_convertvector(v - __builtin_convertvector(h, f4_t), h4_t);
+        const f32x4_t v = reinterpret_cast<const f32x4_t*>(x)[i];
+        const half4_t h = __builtin_convertvector(v, half4_t);
+        reinterpret_cast<half4_t*>(hi)[i] = h;
+        reinterpret_cast<half4_t*>(lo)[i] = __builtin_convertvector(v - __builtin_convertvector(h, f32x4_t), half4_t);
     }
 }
 void launch_split_f32(const float* x, __half* hi, __half* lo, int64_t n, hipStream_t s) {
@@ -470,15 +468,13 @@ void launch_split_f32(const float* x, __half* hi, __half* lo, int64_t n, hipStre
 
 __global__ void lrelu_split_f32_kernel(const float* __restrict__ x, float neg_slope, __half* __restrict__ hi, __half* __restrict__ lo,
                                        int64_t n4) {
-    typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-    typedef float f4_t __attribute__((ext_vector_type(4)));
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        f4_t v = reinterpret_cast<const f4_t*>(x)[i];
+        f32x4_t v = reinterpret_cast<const f32x4_t*>(x)[i];
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = lrelu_in(v[e], neg_slope);  // the expression of k_gemm2.hip's in_act
-        const h4_t h = __builtin_convertvector(v, h4_t);
-        reinterpret_cast<h4_t*>(hi)[i] = h;
-        if (lo) reinterpret_cast<h4_t*>(lo)[i] = __builtin_convertvector(v - __builtin_convertvector(h, f4_t), h4_t);
+        const half4_t h = __builtin_convertvector(v, half4_t);
+        reinterpret_cast<half4_t*>(hi)[i] = h;
+        if (lo) reinterpret_cast<half4_t*>(lo)[i] = __builtin_convertvector(v - __builtin_convertvector(h, f32x4_t), half4_t);
     }
 }
 // lo == null: the hi plane only (consumers that multiply one plane)
@@ -505,7 +501,6 @@ __global__ __launch_bounds__(256) void conv_to_mono_kernel(const float* __restri
                                                            float slope, int act, float* __restrict__ y, int T,
                                                            const int* __restrict__ item_off, int item_mul) {
     constexpr int RS = C + 4, ROWS = 256 + K - 1, VPR = C / 4;
-    typedef float f4_t __attribute__((ext_vector_type(4)));
     __shared__ __attribute__((aligned(16))) float tile[ROWS * RS];
     __shared__ __attribute__((aligned(16))) float sw[K * C];
     const int tid = threadIdx.x, n = blockIdx.y;
@@ -520,11 +515,11 @@ __global__ __launch_bounds__(256) void conv_to_mono_kernel(const float* __restri
     for (int i = tid; i < ROWS * VPR; i += 256) {
         const int r = i / VPR, c4 = i - r * VPR;
         const int t = t0 - K / 2 + r;
-        f4_t v = {0.f, 0.f, 0.f, 0.f};
-        if (t >= 0 && t < T) v = *reinterpret_cast<const f4_t*>(xn + (int64_t)t * C + c4 * 4);
+        f32x4_t v = {0.f, 0.f, 0.f, 0.f};
+        if (t >= 0 && t < T) v = *reinterpret_cast<const f32x4_t*>(xn + (int64_t)t * C + c4 * 4);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = v[j] > 0.f ? v[j] : slope * v[j];
-        *reinterpret_cast<f4_t*>(tile + r * RS + c4 * 4) = v;
+        *reinterpret_cast<f32x4_t*>(tile + r * RS + c4 * 4) = v;
     }
     for (int i = tid; i < K * C; i += 256) sw[i] = __half2float(w[i]);  // packed row: column = tap * C + channel
     __syncthreads();
@@ -535,8 +530,8 @@ __global__ __launch_bounds__(256) void conv_to_mono_kernel(const float* __restri
     for (int tap = 0; tap < K; ++tap)
 #pragma unroll
         for (int c4 = 0; c4 < VPR; ++c4) {
-            const f4_t xv = *reinterpret_cast<const f4_t*>(tile + (tid + tap) * RS + c4 * 4);
-            const f4_t wv = *reinterpret_cast<const f4_t*>(sw + tap * C + c4 * 4);
+            const f32x4_t xv = *reinterpret_cast<const f32x4_t*>(tile + (tid + tap) * RS + c4 * 4);
+            const f32x4_t wv = *reinterpret_cast<const f32x4_t*>(sw + tap * C + c4 * 4);
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc = fmaf(xv[j], wv[j], acc);
         }

@@ -1,20 +1,15 @@
 // Row-wise normalisation and the Conformer convolution middle section.
 // All kernels are HBM-bound: one pass over the data with 16-byte loads, wave64
 // shuffle reductions, no LDS round trip.
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ float act_f(float v, int act) {
-    if (act == ACT_RELU) return !(v <= 0.f) ? v : 0.f;  // NaN stays NaN, -0 -> +0
-    if (act == ACT_SILU) return v / (1.f + expf(-v));
-    if (act == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
+// not act(v, int): the run-time TANH case would add a compare to kernels that no caller asks it of
+__device__ __forceinline__ float act_f(float v, int a) {
+    if (a == ACT_RELU) return relu_keep_nan(v);
+    if (a == ACT_SILU) return v / (1.f + expf(-v));
+    if (a == ACT_GELU) return gelu_erf(v);
     return v;
 }
 
@@ -34,10 +29,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     const float4* xr = reinterpret_cast<const float4*>(x + (int64_t)row * ldx);
     float4* yr = reinterpret_cast<float4*>(y + (int64_t)row * ldy);
     // yh != null: the result is written as two fp16 planes (hi, lo) for launch_gemm_presplit instead of fp32
-    typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-    typedef float f4_t __attribute__((ext_vector_type(4)));
-    h4_t* yhr = reinterpret_cast<h4_t*>(yh + (yh ? (int64_t)row * ldh : 0));
-    h4_t* ylr = reinterpret_cast<h4_t*>(yl + (yl ? (int64_t)row * ldh : 0));
+    half4_t* yhr = reinterpret_cast<half4_t*>(yh + (yh ? (int64_t)row * ldh : 0));
+    half4_t* ylr = reinterpret_cast<half4_t*>(yl + (yl ? (int64_t)row * ldh : 0));
     // y AND yh given ("both"): fp32 rows as well as planes; the length mask then zeroes the planes only (the fp32 copy is
     // a residual stream, the planes are the next convolution's operand and carry its zero padding behind an item's end)
     const bool both = y != nullptr && yh != nullptr;
@@ -48,8 +41,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         if (t >= lens[n]) {
             for (int i = lane; i < nv; i += 64) {
                 if (yh) {
-                    yhr[i] = h4_t{0, 0, 0, 0};
-                    ylr[i] = h4_t{0, 0, 0, 0};
+                    yhr[i] = half4_t{0, 0, 0, 0};
+                    ylr[i] = half4_t{0, 0, 0, 0};
                 } else {
                     yr[i] = make_float4(0.f, 0.f, 0.f, 0.f);
                 }
@@ -91,11 +84,11 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
             o.z = act_f((v[i].z - mean) * rstd * g.z + b.z, act);
             o.w = act_f((v[i].w - mean) * rstd * g.w + b.w, act);
             if (yh && !masked) {
-                const f4_t of = {o.x, o.y, o.z, o.w};
-                const h4_t hi = __builtin_convertvector(of, h4_t);
-                const f4_t back = __builtin_convertvector(hi, f4_t);
+                const f32x4_t of = {o.x, o.y, o.z, o.w};
+                const half4_t hi = __builtin_convertvector(of, half4_t);
+                const f32x4_t back = __builtin_convertvector(hi, f32x4_t);
                 yhr[idx] = hi;
-                ylr[idx] = __builtin_convertvector(of - back, h4_t);
+                ylr[idx] = __builtin_convertvector(of - back, half4_t);
             }
             if (!yh || both) yr[idx] = o;
         }
@@ -110,16 +103,14 @@ __global__ __launch_bounds__(256) void layernorm2_kernel(const float* __restrict
                                                          const float* __restrict__ ba, float* __restrict__ y, int64_t ldy,
                                                          const float* __restrict__ gb2, const float* __restrict__ bb2,
                                                          __half* __restrict__ yh, __half* __restrict__ yl, int64_t ldh, int rows, int C) {
-    typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-    typedef float f4_t __attribute__((ext_vector_type(4)));
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int nv = C >> 2;
     const float4* xr = reinterpret_cast<const float4*>(x + (int64_t)row * ldx);
     float4* yr = reinterpret_cast<float4*>(y + (int64_t)row * ldy);
-    h4_t* yhr = reinterpret_cast<h4_t*>(yh + (int64_t)row * ldh);
-    h4_t* ylr = reinterpret_cast<h4_t*>(yl + (int64_t)row * ldh);
+    half4_t* yhr = reinterpret_cast<half4_t*>(yh + (int64_t)row * ldh);
+    half4_t* ylr = reinterpret_cast<half4_t*>(yl + (int64_t)row * ldh);
     float4 v[4];
     float s = 0.f;
 #pragma unroll
@@ -169,12 +160,12 @@ __global__ __launch_bounds__(256) void layernorm2_kernel(const float* __restrict
         const int idx = lane + 64 * i;
         if (idx < nv) {
             const float4 g = reinterpret_cast<const float4*>(gb2)[idx], b = reinterpret_cast<const float4*>(bb2)[idx];
-            const f4_t of = {(v[i].x - mean) * rstd * g.x + b.x, (v[i].y - mean) * rstd * g.y + b.y, (v[i].z - mean) * rstd * g.z + b.z,
+            const f32x4_t of = {(v[i].x - mean) * rstd * g.x + b.x, (v[i].y - mean) * rstd * g.y + b.y, (v[i].z - mean) * rstd * g.z + b.z,
                              (v[i].w - mean) * rstd * g.w + b.w};
-            const h4_t hi = __builtin_convertvector(of, h4_t);
-            const f4_t back = __builtin_convertvector(hi, f4_t);
+            const half4_t hi = __builtin_convertvector(of, half4_t);
+            const f32x4_t back = __builtin_convertvector(hi, f32x4_t);
             yhr[idx] = hi;
-            ylr[idx] = __builtin_convertvector(of - back, h4_t);
+            ylr[idx] = __builtin_convertvector(of - back, half4_t);
         }
     }
 }
@@ -391,8 +382,6 @@ __global__ __launch_bounds__(1024) void glu_dwconv_ln_kernel(const float* __rest
                                                              __half* __restrict__ yh, __half* __restrict__ yl, int64_t ldh, int T, int C,
                                                              const int* __restrict__ lens, int range) {
     __shared__ float tile[2][TT][1024];
-    typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-    typedef float f4_t __attribute__((ext_vector_type(4)));
     const int c = threadIdx.x;  // channel (blockDim.x == C)
     const int lane = c & 63, wv = c >> 6, waves = C >> 6;
     const int n = blockIdx.y;
@@ -450,8 +439,8 @@ __global__ __launch_bounds__(1024) void glu_dwconv_ln_kernel(const float* __rest
         for (int r = wv; r < TT && tc + r < t_end; r += waves) {
             const float4* xr = reinterpret_cast<const float4*>(&tile[buf][r][0]);
             const int64_t row = (int64_t)n * T + tc + r;
-            h4_t* yhr = reinterpret_cast<h4_t*>(yh + row * ldh);
-            h4_t* ylr = reinterpret_cast<h4_t*>(yl + row * ldh);
+            half4_t* yhr = reinterpret_cast<half4_t*>(yh + row * ldh);
+            half4_t* ylr = reinterpret_cast<half4_t*>(yl + row * ldh);
             // (the row is re-read from LDS in each of the three passes instead of being held in 16 registers: the thread's
             //  sliding window, taps and prefetched rows already fill the 128-register budget of a 1024-thread workgroup)
             float s = 0.f;
@@ -486,11 +475,11 @@ __global__ __launch_bounds__(1024) void glu_dwconv_ln_kernel(const float* __rest
                     o.y = act_f((vv.y - mean) * rstd * gg.y + bb.y, act);
                     o.z = act_f((vv.z - mean) * rstd * gg.z + bb.z, act);
                     o.w = act_f((vv.w - mean) * rstd * gg.w + bb.w, act);
-                    const f4_t of = {o.x, o.y, o.z, o.w};
-                    const h4_t hi = __builtin_convertvector(of, h4_t);
-                    const f4_t back = __builtin_convertvector(hi, f4_t);
+                    const f32x4_t of = {o.x, o.y, o.z, o.w};
+                    const half4_t hi = __builtin_convertvector(of, half4_t);
+                    const f32x4_t back = __builtin_convertvector(hi, f32x4_t);
                     yhr[idx] = hi;
-                    ylr[idx] = __builtin_convertvector(of - back, h4_t);
+                    ylr[idx] = __builtin_convertvector(of - back, half4_t);
                 }
             }
         }

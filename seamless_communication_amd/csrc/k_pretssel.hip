@@ -2,22 +2,15 @@
 // models/unity/film.py, models/unity/length_regulator.py): every FiLM projection of a call in one launch, LayerNorm -> FiLM ->
 // mask in one pass, the variance adaptor's tail, the fused Gaussian upsampling, and the post-net's row passes.
 // All of them are row kernels: one wave per row (or per output value), lanes over the channels, fp32 arithmetic.
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
 namespace {
 
-typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 __device__ __forceinline__ void store_planes(__half* yh, __half* yl, int64_t off, float v) {
-    const _Float16 h = (_Float16)v;
+    const _Float16 h = (_Float16)v;  // the split, inline: split1 binds both planes first, which moves a store in film_ln_kernel
     reinterpret_cast<_Float16*>(yh)[off] = h;
     reinterpret_cast<_Float16*>(yl)[off] = (_Float16)(v - (float)h);
 }

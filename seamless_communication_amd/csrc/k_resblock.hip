@@ -23,14 +23,10 @@
 // same epilogue expressions, so the results are bit-identical to conv1d + conv1d (tests/test_ops_gpu.py).
 #include <algorithm>
 
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
-typedef float float16_t __attribute__((ext_vector_type(16)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -260,7 +256,7 @@ __global__ __launch_bounds__(256) void resblock_pair_kernel(ResPairArgs p, int t
                 const int t = t0 - H2 + j;
                 float v = (t >= 0 && t < T) ? (acc[nf][r] + b) * 1.0f : 0.f;  // conv2 sees zero padding outside [0, T)
                 v = lrelu(v, slope);
-                const _Float16 h = (_Float16)v;
+                const _Float16 h = (_Float16)v;  // not split1: SINGLE forms and stores the hi half only
                 th[j * CS + col] = h;
                 if (!SINGLE) tl[j * CS + col] = (_Float16)(v - (float)h);
             }
@@ -351,7 +347,6 @@ constexpr int MRF_G = 32;
 constexpr int MRF_THREADS = 1024;
 constexpr int MRF_KMAX = 11;
 
-typedef int mrf_i32x4_t __attribute__((ext_vector_type(4)));
 #define MRF_LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 
 // One convolution's packed weights global -> LDS by the buffer unit (`buffer_load_dwordx4 ... lds`: lane p of a wave
@@ -366,7 +361,7 @@ __device__ __forceinline__ void mrf_w_dma(const __half* __restrict__ W, int64_t 
     const int vpr1 = k * C / 8 + 1;
     const int slots = C * vpr1;
     const uint64_t base = reinterpret_cast<uint64_t>(W);
-    mrf_i32x4_t rsrc;
+    i32x4_t rsrc;
     rsrc[0] = __builtin_amdgcn_readfirstlane((int)(uint32_t)base);
     rsrc[1] = __builtin_amdgcn_readfirstlane((int)(uint32_t)((base >> 32) & 0xffff));
     rsrc[2] = __builtin_amdgcn_readfirstlane((int)(uint32_t)(C * ldw * 2));
@@ -421,7 +416,7 @@ __device__ __forceinline__ void mrf_conv(const _Float16* __restrict__ ph, const 
 template <bool SINGLE = false>
 __device__ __forceinline__ void mrf_put(_Float16* __restrict__ ph, _Float16* __restrict__ pl, int idx, float v, float slope) {
     v = fmaxf(v, slope * v);  // LeakyReLU for 0 < slope < 1, same bits as v > 0 ? v : slope * v
-    const _Float16 h = (_Float16)v;
+    const _Float16 h = (_Float16)v;  // not split1: SINGLE forms and stores the hi half only
     ph[idx] = h;
     if (!SINGLE) pl[idx] = (_Float16)(v - (float)h);
 }

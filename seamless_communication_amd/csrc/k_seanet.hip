@@ -8,7 +8,7 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
@@ -17,12 +17,6 @@ namespace {
 __device__ __forceinline__ float elu1(float v) { return v > 0.f ? v : expm1f(v); }
 __device__ __forceinline__ float sigmoid1(float v) { return 1.f / (1.f + expf(-v)); }
 __device__ __forceinline__ float in_act1(float v, int act) { return act == SEANET_IN_ELU ? elu1(v) : act == SEANET_IN_TANH ? tanhf(v) : v; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // ---- LSTM ------------------------------------------------------------------------------------------------------------------
 // One launch per time step t = 0 .. max steps: layer 0 at t, layer 1 at t - 1 (both read what the launch before wrote).

@@ -22,18 +22,15 @@
 // reduce_res_ln_kernel:  x += bias + sum_s partial[s];  h = LayerNorm(x)
 //   (the residual add that follows every attention / FFN output projection in
 //   a pre-LN decoder layer, fused with the next sub-layer's LayerNorm).
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-typedef float float16_t __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float sk_act(float v, int act) {
-    if (act == ACT_RELU) return !(v <= 0.f) ? v : 0.f;  // NaN stays NaN, -0 -> +0
-    if (act == ACT_SILU) return v / (1.f + expf(-v));
-    if (act == ACT_TANH) return tanhf(v);
+// not act(v, int): the run-time GELU case would add a compare to every epilogue of a kernel that is never launched with it
+__device__ __forceinline__ float sk_act(float v, int a) {
+    if (a == ACT_RELU) return relu_keep_nan(v);
+    if (a == ACT_SILU) return v / (1.f + expf(-v));
+    if (a == ACT_TANH) return tanhf(v);
     return v;
 }
 
@@ -107,12 +104,7 @@ __global__ __launch_bounds__(256) void skinny_kernel(SkinnyArgs p) {
                         const float x[8] = {av[2 * j].x,     av[2 * j].y,     av[2 * j].z,     av[2 * j].w,
                                             av[2 * j + 1].x, av[2 * j + 1].y, av[2 * j + 1].z, av[2 * j + 1].w};
                         half8_t hi, lo;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) {
-                            const _Float16 h = (_Float16)x[e];
-                            hi[e] = h;
-                            lo[e] = (_Float16)(x[e] - (float)h);
-                        }
+                        split8(x, hi, lo);
 #pragma unroll
                         for (int t = 0; t < NT; ++t) {
                             const half8_t bf = *reinterpret_cast<const half8_t*>(&wv[s][t][j]);

@@ -8,19 +8,12 @@
 // weights (weight-norm folded, not representable in fp16) and is 2 * 80 * 128 flops per output element.
 #include <algorithm>
 
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
 namespace {
 
-__device__ __forceinline__ float gelu_f(float v) { return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f)); }
-
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -107,23 +100,23 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ wa
         const float* yr = sy + f * C;
         float s = 0.f;
         for (int c = lane; c < C; c += 64) s += yr[c];
-        const float mu = wave_sum_f(s) / (float)C;
+        const float mu = wave_sum(s) / (float)C;
         float q = 0.f;
         for (int c = lane; c < C; c += 64) {
             const float d = yr[c] - mu;
             q += d * d;
         }
-        const float rs = 1.0f / sqrtf(wave_sum_f(q) / (float)C + 1e-5f);
+        const float rs = 1.0f / sqrtf(wave_sum(q) / (float)C + 1e-5f);
         float* orow = out + ((int64_t)b * t_rows + t) * C;
         for (int c4 = lane; c4 < C / 4; c4 += 64) {
             const float4 y = *reinterpret_cast<const float4*>(yr + 4 * c4);
             const float4 g = *reinterpret_cast<const float4*>(gamma + 4 * c4);
             const float4 be = *reinterpret_cast<const float4*>(beta + 4 * c4);
             float4 o;
-            o.x = gelu_f((y.x - mu) * rs * g.x + be.x);
-            o.y = gelu_f((y.y - mu) * rs * g.y + be.y);
-            o.z = gelu_f((y.z - mu) * rs * g.z + be.z);
-            o.w = gelu_f((y.w - mu) * rs * g.w + be.w);
+            o.x = gelu_erf((y.x - mu) * rs * g.x + be.x);
+            o.y = gelu_erf((y.y - mu) * rs * g.y + be.y);
+            o.z = gelu_erf((y.z - mu) * rs * g.z + be.z);
+            o.w = gelu_erf((y.w - mu) * rs * g.w + be.w);
             *reinterpret_cast<float4*>(orow + 4 * c4) = o;
         }
     }
@@ -181,7 +174,7 @@ __global__ __launch_bounds__(512) void pos_conv_kernel(const float* __restrict__
         const int t = t0 + ty + r * PC_TY;
         if (t < T) {
             const int64_t o = ((int64_t)b * T + t) * C + g * cg + c;
-            y[o] = x[o] + gelu_f(acc[r] + bc);
+            y[o] = x[o] + gelu_erf(acc[r] + bc);
         }
     }
 }
@@ -217,7 +210,7 @@ __global__ __launch_bounds__(256) void pack_centroids_kernel(const float* __rest
         const float s = __half2float(h) + __half2float(l);
         q = fmaf(s, s, q);
     }
-    q = wave_sum_f(q);
+    q = wave_sum(q);
     if (lane == 0) bias[j] = -0.5f * q;
 }
 

@@ -570,14 +570,13 @@ struct AttnArgs {
     __half* out_hi = nullptr;
     __half* out_lo = nullptr;
     int64_t ldoh = 0;
-    // 64: the kernel of k_attn.hip (every mode above).  80: k_attn80.hip (wav2vec 2.0 / XLS-R), plain mode with kv_lens only,
-    // head h at column h*80, logits scaled by 80^-0.5.  128: k_attn128.hip (PRETSSEL), kv_lens, packed rows and plane output,
-    // head h at column h*128, logits scaled by 128^-0.5
+    // 64: the kernel of k_attn.hip (every mode above).  80 and 128: the kernel template of k_attn_hd.hip.  80 (wav2vec 2.0 /
+    // XLS-R): plain mode with kv_lens only, head h at column h*80, logits scaled by 80^-0.5.  128 (PRETSSEL): kv_lens, packed
+    // rows and plane output, head h at column h*128, logits scaled by 128^-0.5
     int head_dim = 64;
 };
 void launch_attention(const AttnArgs& a, hipStream_t s);
-void launch_attention80(const AttnArgs& a, hipStream_t s);  // k_attn80.hip; reached through launch_attention
-void launch_attention128(const AttnArgs& a, hipStream_t s);  // k_attn128.hip; reached through launch_attention
+void launch_attention_hd(const AttnArgs& a, hipStream_t s);  // k_attn_hd.hip (head_dim 80 and 128); reached through launch_attention
 
 // Single-query attention over a KV cache (decoder step).  q: [nb][heads*64];
 // key/value row j of (b, h) lives at base + b*cache_bs + j*cache_ld + h*64.  If k_new != null the
