@@ -245,6 +245,36 @@ int sc_generate_text_banned(sc_model* m, const float* d_enc, int32_t n, int32_t 
                             int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden, const int32_t* h_banned_tokens,
                             const int32_t* h_banned_offsets /* [n_banned + 1] */, int32_t n_banned);
 
+/* Sampled text generation (additive, ABI 10; fairseq2 0.2 SamplingSeq2SeqGenerator with TopKSampler / TopPSampler - not part
+ * of the reference tree, restated from memory: UNVERIFIED): num_gens stochastic hypotheses per utterance, drawn inside the step
+ * loop.  At every step the logits are divided by `temperature`, the step processors (opts->no_repeat_ngram_size, the banned
+ * list) and the step rules of sc_generate_text apply, top_k (0 = off) keeps the k most probable tokens, top_p then keeps a token
+ * iff the probability mass strictly before it (descending order) is <= top_p, and one token is drawn from the kept set.  The
+ * draw is a pure function of (row of logits, options, seed, stream id of the utterance, hypothesis number, position): integer
+ * masses floor(p * 2^36) and Philox4x32-10, neither torch's generator nor the batch composition enters it (a token of
+ * probability below 2^-36 is never drawn).  top_k == 1 is the arg-max with ties to the lowest index.
+ * h_streams [n] (NULL: 0 .. n-1): the caller's 64-bit id of each utterance.  Outputs, per utterance sorted by score (NaN first,
+ * then descending, ties in hypothesis order): h_out_ids [n][num_gens][max_len] (max_len = sc_text_max_len), h_out_lens and
+ * h_out_scores [n][num_gens] (the score of sc_generate_text: the sum of the log-probabilities under the temperature and the
+ * rules, prompt echo included, normalised as opts says), h_step_lprob [n][num_gens][max_len] (nullable; the log-probability of
+ * every drawn token at its position, 0 elsewhere), d_dec_hidden [n][max_len - 1][M] (nullable; the teacher-forced decoder
+ * outputs of hypothesis 0 after sorting).  opts->beam_size is ignored.  Runs the host-driven step loop, never the decode
+ * engine.  SC_ERR_INVALID before any device work: num_gens outside 1..64, n * num_gens above 512, temperature not positive and
+ * finite, top_k < 0, top_p outside (0, 1], a bad banned list (limits of sc_generate_text_banned). */
+typedef struct sc_sample_opts {
+    int32_t abi_version; /* SC_ABI_VERSION */
+    int32_t num_gens;
+    int32_t top_k;
+    float top_p;
+    float temperature;
+    uint64_t seed;
+} sc_sample_opts;
+int sc_generate_text_sampled(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
+                             const sc_gen_opts* opts, const sc_sample_opts* sample_opts, const uint64_t* h_streams /* [n] or NULL */,
+                             const int32_t* h_prefix, int32_t prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_out_scores,
+                             float* h_step_lprob, float* d_dec_hidden, const int32_t* h_banned_tokens,
+                             const int32_t* h_banned_offsets /* [n_banned + 1] */, int32_t n_banned);
+
 /* Greedy generation that also returns what the reference's Transcriber hooks into the model (ABI 10;
  * inference/transcriber.py:39-57, 124-127): per utterance and per FED position p (prompt positions included) the
  * probabilities of the last decoder layer's encoder-decoder attention of the query fed at p, summed over the heads,

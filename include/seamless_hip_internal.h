@@ -203,6 +203,17 @@ int sc_op_beam_candidates_banned(float* d_logits, int64_t ld, int32_t n_utt, int
                                  float unk_penalty, int32_t K, float* d_cand_val, int32_t* d_cand_idx, const int32_t* d_seqs,
                                  int32_t seq_ld, int32_t S, int32_t G, const int32_t* d_rows, const int32_t* d_slots, int32_t chunked,
                                  const int32_t* d_banned_tokens, const int32_t* d_banned_offsets, int32_t n_banned);
+/* The sampling step of sc_generate_text_sampled (k_sample.hip; tests/test_sample_kernel_gpu.py, restated in tests/sample_oracle.py):
+ * one top-k / top-p draw per logit row [rows][ld] under the step rules, a pure function of (row, options, seed, d_stream[r],
+ * d_gen[r], d_position[r]).  temperature > 0; top_k 0 = off; 0 < top_p <= 1.  d_seqs (nullable) with S, G and the banned list as
+ * sc_op_beam_candidates_banned (blocked logits are overwritten with -inf; not on a forced-EOS step).  Per row: d_tok the drawn
+ * token, d_lprob its value v_t (log-softmax of logits / temperature under the rules), d_kept the size of the kept set and
+ * d_z_kept its integer mass (sum of floor(exp(v) * 2^36)). */
+int sc_op_sample_rows(float* d_logits, int64_t ld, int32_t rows, int32_t V, const uint64_t* d_stream, const int32_t* d_gen,
+                      const int32_t* d_position, float temperature, int32_t top_k, float top_p, uint64_t seed, int32_t no_eos, int32_t force_eos,
+                      int32_t pad_idx, int32_t eos_idx, int32_t unk_idx, float unk_penalty, const int32_t* d_seqs, int32_t seq_ld, int32_t S,
+                      int32_t G, const int32_t* d_banned_tokens, const int32_t* d_banned_offsets, int32_t n_banned, int32_t* d_tok,
+                      float* d_lprob, int32_t* d_kept, uint64_t* d_z_kept);
 int sc_op_beam_select(const float* d_cand_val, const int32_t* d_cand_idx, const int32_t* d_seqs_cur, int32_t* d_seqs_new, float* d_fin_score,
                       int32_t* d_fin_len, int32_t* d_fin_seq, int32_t* d_fin_count, int32_t* d_done, int32_t* d_remaining, int32_t* d_tok,
                       int32_t* d_src_row, float* d_cum, int32_t* d_anc, int32_t anc_ld, const int32_t* d_slot_utt, const int32_t* d_slots,

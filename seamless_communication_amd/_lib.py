@@ -102,6 +102,10 @@ class sc_gen_opts(C.Structure):
     ]
 
 
+class sc_sample_opts(C.Structure):
+    _fields_ = [("abi_version", _i), ("num_gens", _i), ("top_k", _i), ("top_p", C.c_float), ("temperature", C.c_float), ("seed", C.c_uint64)]
+
+
 class sc_engine_opts(C.Structure):
     _fields_ = [
         ("slots", _i), ("rows", _i), ("max_len", _i), ("s_enc", _i), ("min_seq_len", _i), ("unk_penalty", C.c_float),
@@ -184,6 +188,8 @@ SIGNATURES = {
     "sc_text_max_len": (_i, [_P, C.POINTER(sc_gen_opts), _i]),
     "sc_generate_text": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P]),
     "sc_generate_text_banned": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P, _P, _P, _i]),
+    "sc_generate_text_sampled": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), C.POINTER(sc_sample_opts), _P, _P, _i, _P, _P, _P, _P, _P,
+                                           _P, _P, _i]),
     "sc_generate_text_capture": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P, _P, _P]),
     "sc_decode_text": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P]),
     "sc_score_text": (C.c_int, [_P, _P, _i, _i, _P, _P, _P, _i, _P, _P, _P, _P]),
@@ -306,6 +312,8 @@ SIGNATURES = {
                                         _P, _P, _i]),
     "sc_op_beam_candidates_banned": (C.c_int, [_P, C.c_int64, _i, _i, _i, _P, _i, _i, _i, _i, _i, _i, C.c_float, _i, _P, _P, _P, _i, _i,
                                                _i, _P, _P, _i, _P, _P, _i]),
+    "sc_op_sample_rows": (C.c_int, [_P, C.c_int64, _i, _i, _P, _P, _P, C.c_float, _i, C.c_float, C.c_uint64, _i, _i, _i, _i, _i, C.c_float,
+                                    _P, _i, _i, _i, _P, _P, _i, _P, _P, _P, _P]),
     "sc_op_beam_select": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _i, _i, _i, _i, _i, _i, _i, _i,
                                     _i, C.c_float]),
     "sc_op_beam_compact": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _i]),

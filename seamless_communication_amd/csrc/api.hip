@@ -244,6 +244,23 @@ int sc_generate_text_banned(sc_model* m, const float* d_enc, int32_t n, int32_t 
     SC_API_END
 }
 
+int sc_generate_text_sampled(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
+                             const sc_gen_opts* opts, const sc_sample_opts* sample_opts, const uint64_t* h_streams, const int32_t* h_prefix,
+                             int32_t prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_out_scores, float* h_step_lprob,
+                             float* d_dec_hidden, const int32_t* h_banned_tokens, const int32_t* h_banned_offsets, int32_t n_banned) {
+    SC_API_BEGIN
+    SC_CHECK(m && d_enc && h_enc_lens && opts && sample_opts && h_prefix && h_out_ids && h_out_lens, "sc_generate_text_sampled: null argument");
+    SC_CHECK(sample_opts->abi_version == SC_ABI_VERSION, "sc_generate_text_sampled: options ABI version %d != library %d",
+             sample_opts->abi_version, SC_ABI_VERSION);
+    SC_CHECK(n_banned >= 0 && (n_banned == 0 || (h_banned_tokens && h_banned_offsets)), "sc_generate_text_sampled: bad banned list");
+    BannedHost b;
+    b.tokens = h_banned_tokens, b.offsets = h_banned_offsets, b.n = n_banned;
+    SC_HIP(hipSetDevice(m->m.device));
+    run_generate_sampled(m->m, d_enc, n, s_enc, h_enc_lens, *opts, *sample_opts, h_streams, h_prefix, prefix_len, h_out_ids, h_out_lens,
+                         h_out_scores, h_step_lprob, d_dec_hidden, n_banned > 0 ? &b : nullptr);
+    SC_API_END
+}
+
 int sc_generate_text_capture(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
                              const sc_gen_opts* opts, const int32_t* h_prefix, int32_t prefix_len, int32_t* h_out_ids,
                              int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden, float* d_xattn, float* h_step_lprob) {
@@ -1583,6 +1600,36 @@ int sc_op_beam_candidates_banned(float* d_logits, int64_t ld, int32_t n_utt, int
     return op_beam_candidates(d_logits, ld, n_utt, beams, V, d_cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K,
                               d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, d_rows, d_slots, chunked, d_banned_tokens, d_banned_offsets,
                               n_banned);
+}
+
+// the sampling step (k_sample.hip) through the launcher run_generate_sampled calls
+int sc_op_sample_rows(float* d_logits, int64_t ld, int32_t rows, int32_t V, const uint64_t* d_stream, const int32_t* d_gen,
+                      const int32_t* d_position, float temperature, int32_t top_k, float top_p, uint64_t seed, int32_t no_eos, int32_t force_eos,
+                      int32_t pad_idx, int32_t eos_idx, int32_t unk_idx, float unk_penalty, const int32_t* d_seqs, int32_t seq_ld, int32_t S,
+                      int32_t G, const int32_t* d_banned_tokens, const int32_t* d_banned_offsets, int32_t n_banned, int32_t* d_tok,
+                      float* d_lprob, int32_t* d_kept, uint64_t* d_z_kept) {
+    SC_API_BEGIN
+    SC_CHECK(d_logits && d_stream && d_gen && d_position && d_tok && d_lprob && d_kept && d_z_kept, "sc_op_sample_rows: null argument");
+    SampleArgs a;
+    if (n_banned != 0) {  // read back and checked on the host first, as sc_op_beam_candidates_banned does
+        SC_CHECK(n_banned > 0 && n_banned <= BANNED_MAX_SEQS && d_banned_tokens && d_banned_offsets && d_seqs,
+                 "sc_op_sample_rows: bad banned list (n_banned=%d; needs d_seqs)", n_banned);
+        const std::vector<int32_t> off = op_read_ints(d_banned_offsets, (size_t)n_banned + 1);
+        SC_CHECK(off[0] == 0 && off[n_banned] >= 0 && off[n_banned] <= BANNED_MAX_TOKENS, "sc_op_sample_rows: bad offsets");
+        for (int q = 0; q < n_banned; ++q) SC_CHECK(off[q + 1] >= off[q], "sc_op_sample_rows: offsets decrease at %d", q);
+        const std::vector<int32_t> tok = op_read_ints(d_banned_tokens, (size_t)off[n_banned]);
+        validate_banned_host(tok.data(), off.data(), n_banned, V, &a.banned.max_len);
+        a.banned.tokens = d_banned_tokens, a.banned.offsets = d_banned_offsets, a.banned.n = n_banned;
+    }
+    a.logits = d_logits, a.ld = ld, a.rows = rows, a.V = V;
+    a.stream = reinterpret_cast<const unsigned long long*>(d_stream), a.gen = d_gen, a.position = d_position;
+    a.temperature = temperature, a.top_k = top_k, a.top_p = top_p, a.seed = seed;
+    a.no_eos = no_eos, a.force_eos = force_eos, a.pad_idx = pad_idx, a.eos_idx = eos_idx, a.unk_idx = unk_idx, a.unk_penalty = unk_penalty;
+    a.seqs_in = d_seqs, a.seq_ld = seq_ld, a.S = S, a.G = G;
+    a.tok = d_tok, a.lprob = d_lprob, a.kept = d_kept, a.z_kept = reinterpret_cast<unsigned long long*>(d_z_kept);
+    launch_sample_rows(a, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
 }
 
 int sc_op_beam_select(const float* d_cand_val, const int32_t* d_cand_idx, const int32_t* d_seqs_cur, int32_t* d_seqs_new, float* d_fin_score,

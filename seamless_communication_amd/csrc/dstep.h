@@ -72,6 +72,7 @@ bool step2_eligible(const Model& m, const DecStack& W, int nb);
 bool step3_eligible(const Model& m, const DecStack& W, int nb);
 bool step3_wide_eligible(const Model& m, const DecStack& W, int nb);
 void alloc_step2(Model& m, StepCtx& c, int ffn_dim);
+int choose_family(const Model& m, const DecStack& W, int rows, int caller);
 // One decoder step for all batch rows: feeds d_tok at position *d_pos (engine: every slot at its row's position)
 void decoder_step(Model& m, StepCtx& c, bool project);
 // graph captures and instantiations are serialised process-wide (another handle's host thread may allocate while one records)

@@ -663,6 +663,46 @@ void launch_row_token_lprob(const float* logits, int64_t ld, int rows, int V, in
 void launch_gather_cache(const float* src, float* dst, const int* src_row, int rows, int len, int cap, int M, int layers,
                          int64_t layer_stride, hipStream_t s);
 
+// sampled generation (k_sample.hip): one top-k / top-p draw per live logit row, one workgroup per row.  The draw
+// is a pure function of (row, options, seed, stream, gen, position): integer masses floor(exp(v) * 2^36), Philox4x32-10.
+struct SampleArgs {
+    float* logits = nullptr;  // [rows][ld]; the step processors write -inf into it
+    int64_t ld = 0;
+    int rows = 0, V = 0;
+    const unsigned long long* stream = nullptr;  // [rows] the utterance's 64-bit id
+    const int* gen = nullptr;                    // [rows] hypothesis number
+    const int* position = nullptr;               // [rows] index the drawn token will occupy; null: `pos` for every row
+    int pos = 0;
+    float temperature = 1.f, top_p = 1.f;
+    int top_k = 0;
+    unsigned long long seed = 0;
+    int no_eos = 0, force_eos = 0, pad_idx = 0, eos_idx = 0, unk_idx = 0;
+    float unk_penalty = 0.f;
+    // step processors (seqs nullable = none): S tokens so far per row, n-gram size G (0 = off), banned list (n == 0: none)
+    const int* seqs_in = nullptr;
+    int seq_ld = 0, S = 0, G = 0;
+    BannedList banned;
+    // results per row (each nullable)
+    int* tok = nullptr;
+    float* lprob = nullptr;
+    int* kept = nullptr;
+    unsigned long long* z_kept = nullptr;
+    // loop state (run_generate_sampled; all nullable together): a finished row is skipped; otherwise the token is appended to
+    // seqs[r][pos], fed next (next_tok), cum += lprob, step_lprob[r][pos] = lprob, and EOS finishes the row (out_len = pos + 1,
+    // *remaining -= 1)
+    int* seqs = nullptr;        // [rows][seq_ld]
+    int* next_tok = nullptr;    // [rows]
+    float* cum = nullptr;       // [rows]
+    float* step_lprob = nullptr;  // [rows][seq_ld]
+    int* finished = nullptr;    // [rows]
+    int* out_len = nullptr;     // [rows]
+    int* remaining = nullptr;   // [1]
+};
+void launch_sample_rows(const SampleArgs& a, hipStream_t s);
+// out[i] += y[token] - lse(y) with y = logits[i * row_stride] / temperature (the echoed prompt's score under the sampler's temperature)
+void launch_sample_prompt_lprob(const float* logits, int64_t ld, int rows, int V, int row_stride, int token, float temperature, float* out,
+                                hipStream_t s);
+
 // fbank front-end
 // consts = window[400] | melT[256][80] | twiddle cos[256] | twiddle sin[256]
 void launch_fbank(const float* wav, int64_t wav_stride, const int* num_samples, int nb, float* out,

@@ -396,6 +396,10 @@ void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, con
 void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                        const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
                        float* d_dec_hidden, int max_len, const BannedHost* banned = nullptr);
+// sampled generation (model_sample.hip): outputs [n][num_gens][...], hypotheses of an utterance sorted by score
+void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
+                          const sc_sample_opts& so, const uint64_t* h_streams, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
+                          int32_t* h_out_lens, float* h_scores, float* h_step_lprob, float* d_dec_hidden, const BannedHost* banned);
 void run_vocode(Model& m, const int32_t* h_units, int n, int s_units, const int32_t* h_lang, const int32_t* h_spkr,
                 float* d_wav, const int32_t* h_unit_lens = nullptr);
 std::vector<std::vector<int>> plan_length_groups(const std::vector<int>& lens, int overhead_rows, int max_groups);

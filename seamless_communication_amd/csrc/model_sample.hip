@@ -1,0 +1,280 @@
+// Sampled text generation (sc_generate_text_sampled): num_gens stochastic hypotheses per utterance, drawn with temperature and
+// top-k / top-p inside the step loop (fairseq2 0.2 SamplingSeq2SeqGenerator + TopKSampler / TopPSampler, restated).
+// A sibling of run_generate_beam (model_decoder.hip) on the same step chain: row u * num_gens + g is hypothesis g of utterance
+// u, the encoder K / V are projected once per utterance, and rows never change places - no ancestor table, no cache
+// re-ordering, a finished row rides along (its draws are skipped, its results are already stored).  Per step: decoder step,
+// vocabulary projection, ONE sampling launch (k_sample.hip: log-softmax under the temperature, step processors, step rules,
+// kept set, draw, and the bookkeeping of the row: sequence, next token, cumulative score, finished flag).  The host polls the
+// count of unfinished rows every fourth step.
+#include <algorithm>
+#include <cmath>
+#include <mutex>
+
+#include "dstep.h"
+#include "engine.h"
+
+namespace sc {
+
+void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
+                          const sc_sample_opts& so, const uint64_t* h_streams, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
+                          int32_t* h_out_lens, float* h_scores, float* h_step_lprob, float* d_dec_hidden, const BannedHost* banned) {
+    const DecStack W = unity_stack(m);
+    const sc_config& cfg = m.cfg;
+    const std::vector<DecoderLayer>& dec_layers = *W.layers;
+    const int M = cfg.model_dim, V = W.vocab, B = so.num_gens, L = (int)dec_layers.size();
+    // ---- limits, before any device work ---------------------------------------------------------------------------------
+    SC_CHECK(n > 0 && s_enc > 0, "sc_generate_text_sampled: empty batch");
+    SC_CHECK(B >= 1 && B <= 64, "sc_generate_text_sampled: num_gens %d (1..64)", B);
+    SC_CHECK((int64_t)n * B <= 512, "sc_generate_text_sampled: %d x %d rows (at most 512: the widest step chain)", n, B);
+    SC_CHECK(so.temperature > 0.f && std::isfinite(so.temperature), "sc_generate_text_sampled: temperature %g (positive and finite)",
+             (double)so.temperature);
+    SC_CHECK(so.top_k >= 0, "sc_generate_text_sampled: top_k %d", so.top_k);
+    SC_CHECK(so.top_p > 0.f && so.top_p <= 1.f, "sc_generate_text_sampled: top_p %g (0 < top_p <= 1)", (double)so.top_p);
+    SC_CHECK(o.no_repeat_ngram_size >= 0, "sc_generate_text_sampled: no_repeat_ngram_size=%d", o.no_repeat_ngram_size);
+    const int nb = n * B;
+    const int max_len = text_max_len(m, o, s_enc);
+    SC_CHECK(prefix_len >= 1, "sc_generate_text_sampled: the prompt must hold at least one token");
+    SC_CHECK(o.min_seq_len <= max_len, "sc_generate_text_sampled: min_seq_len %d > effective max length %d", o.min_seq_len, max_len);
+    SC_CHECK(prefix_len < max_len, "sc_generate_text_sampled: prompt length %d >= effective max length %d", prefix_len, max_len);
+    SC_CHECK(max_len <= 4096 && max_len <= W.max_seq_len + 1, "sc_generate_text_sampled: length %d exceeds the decoder limit", max_len);
+    SC_CHECK(s_enc <= 4096, "sc_generate_text_sampled: encoder length %d > 4096", s_enc);
+    for (int i = 0; i < n; ++i)
+        SC_CHECK(h_enc_lens[i] > 0 && h_enc_lens[i] <= s_enc, "sc_generate_text_sampled: enc_lens[%d]=%d out of range", i, h_enc_lens[i]);
+    BannedList bl;
+    if (banned && banned->n > 0) validate_banned_host(banned->tokens, banned->offsets, banned->n, V, &bl.max_len);
+    prof::set_tag("dec");
+    if (m.engine) m.engine->expect(m, -n);  // never on the decode engine, like the banned-sequence calls
+
+    Buf<int> d_banned(m.pp(), 4);
+    if (banned && banned->n > 0) {
+        const int total = banned->offsets[banned->n];
+        d_banned = Buf<int>(m.pp(), (size_t)total + banned->n + 1);
+        SC_HIP(hipMemcpyAsync(d_banned.get(), banned->tokens, (size_t)total * 4, hipMemcpyHostToDevice, m.stream));
+        SC_HIP(hipMemcpyAsync(d_banned.get() + total, banned->offsets, (size_t)(banned->n + 1) * 4, hipMemcpyHostToDevice, m.stream));
+        SC_HIP(hipStreamSynchronize(m.stream));  // the list is the caller's
+        bl.tokens = d_banned.get(), bl.offsets = d_banned.get() + total, bl.n = banned->n;
+    }
+
+    // ---- the step context: as run_generate_beam sets it up, without the ancestor table -------------------------------------
+    const int family = choose_family(m, W, nb, 1);
+    const bool packed_step = family != 1;
+    Buf<float> enc_rep(m.pp(), packed_step ? 4 : (size_t)nb * s_enc * M);
+    if (!packed_step) {  // the general step reads one encoder K / V per row: fan the encoder output out to the hypotheses
+        std::vector<int32_t> idx((size_t)nb * s_enc);
+        for (int r = 0; r < nb; ++r)
+            for (int t = 0; t < s_enc; ++t) idx[(size_t)r * s_enc + t] = (r / B) * s_enc + t;
+        Buf<int> d_idx(m.pp(), idx.size());
+        SC_HIP(hipMemcpyAsync(d_idx.get(), idx.data(), idx.size() * 4, hipMemcpyHostToDevice, m.stream));
+        launch_gather_rows(d_enc, M, d_idx, enc_rep, M, nb * s_enc, M, m.stream);
+        SC_HIP(hipStreamSynchronize(m.stream));  // idx is a host temporary
+    }
+    StepCtx c;
+    c.stack = &W;
+    c.nb = nb, c.cap = max_len, c.s_enc = s_enc;
+    c.min_seq_len = o.min_seq_len, c.force_eos_step = max_len - 2, c.unk_penalty = o.unk_penalty;
+    Buf<int> ints(m.pp(), (size_t)8 + 4 * nb);
+    c.d_pos = ints;
+    c.d_tok = ints.get() + 8;
+    c.d_finished = c.d_tok + nb;
+    c.d_out_len = c.d_finished + nb;
+    c.d_enc_lens = c.d_out_len + nb;
+    const int wideN = std::max(3 * M, W.ffn_dim);
+    Buf<float> x(m.pp(), (size_t)nb * M), h(m.pp(), (size_t)nb * M), wide(m.pp(), (size_t)nb * wideN), att(m.pp(), (size_t)nb * M),
+        hN(m.pp(), (size_t)nb * M), logits(m.pp(), (size_t)nb * (V + 3));
+    Buf<float> partial(m.pp(), (size_t)std::max(1, std::max(M, W.ffn_dim) / 256) * nb * 3 * M);
+    c.partial = partial, c.x = x, c.h = h, c.wide = wide, c.att = att, c.hN = hN, c.logits = logits;
+    Buf<float> xg3(m.pp(), 4), qkvr3(m.pp(), 4), qkv3w(m.pp(), 4);
+    if (packed_step) {
+        alloc_step2(m, c, W.ffn_dim);
+        if (family >= 3) {
+            c.gen3 = true;
+            xg3 = Buf<float>(m.pp(), (size_t)M * c.rb);
+            qkvr3 = Buf<float>(m.pp(), (size_t)nb * M);
+            c.xg = xg3, c.qkvr = qkvr3;
+            if (nb > 64) {
+                qkv3w = Buf<float>(m.pp(), (size_t)nb * 3 * M);
+                c.qkv3 = qkv3w;
+            }
+            c.rg_small = nb > 128 ? 32 : 16;
+        }
+    }
+    const bool proj_v3 = c.rb > 0 && W.embed_p != nullptr && vocab3_supported(nb, V, M);
+    const int64_t ldl = proj_v3 ? (int64_t)align_up(V, 4) : V;
+    const int64_t layer_stride = (int64_t)nb * max_len * M;
+    Buf<float> kv(m.pp(), (size_t)2 * L * layer_stride);
+    for (int li = 0; li < L; ++li) {
+        c.kcache.push_back(kv.get() + (int64_t)(2 * li) * layer_stride);
+        c.vcache.push_back(kv.get() + (int64_t)(2 * li + 1) * layer_stride);
+    }
+    std::vector<Buf<float>> cross;
+    cross.reserve(L);
+    const int cross_rows = packed_step ? n : nb;
+    c.cross_row_div = packed_step ? B : 1;  // one encoder K / V per utterance
+    for (int li = 0; li < L; ++li) {
+        cross.emplace_back(m.pp(), (size_t)cross_rows * s_enc * 2 * M);
+        c.cross_kv.push_back(cross.back());
+        project_cross_kv(m, packed_step ? d_enc : enc_rep.get(), dec_layers[li].cross_kv, c.cross_kv.back(), cross_rows * s_enc);
+    }
+    Linear proj;
+    proj.w = W.embed, proj.ldw = M, proj.kpad = M, proj.in = M, proj.out = V;
+    auto project_rows = [&]() {
+        if (proj_v3) {
+            Vocab3Args v;
+            v.Wp = W.embed_p, v.Ah = c.hH, v.Al = c.hL, v.RB = c.rb, v.M = nb, v.N = V, v.K = M;
+            v.logits = c.logits, v.ldl = ldl;
+            launch_vocab3(v, m.stream);
+        } else {
+            linear(m, c.hN, M, proj, nullptr, 0, c.logits, V, nb, ACT_NONE, 1.f);
+        }
+    };
+
+    // ---- per-row state, device resident ----------------------------------------------------------------------------------------
+    std::vector<int32_t> seqs((size_t)nb * max_len, W.pad_idx), init(8 + 4 * nb, 0), tok(nb), gens(nb);
+    std::vector<unsigned long long> streams(nb);
+    for (int r = 0; r < nb; ++r) {
+        for (int t = 0; t < prefix_len; ++t) seqs[(size_t)r * max_len + t] = h_prefix[t];
+        init[8 + r] = h_prefix[0];
+        init[8 + 3 * nb + r] = h_enc_lens[r / B];
+        gens[r] = r % B;
+        streams[r] = h_streams ? h_streams[r / B] : (unsigned long long)(r / B);
+    }
+    Buf<int> d_seqs(m.pp(), (size_t)nb * max_len), d_state(m.pp(), (size_t)3 * nb + 1);
+    Buf<float> d_cum(m.pp(), (size_t)nb), d_slp(m.pp(), (size_t)nb * max_len), d_pref(m.pp(), (size_t)n);
+    Buf<unsigned long long> d_streams(m.pp(), (size_t)nb);
+    int* d_gen = d_state.get();
+    int* d_fin = d_state.get() + nb;
+    int* d_len = d_state.get() + 2 * nb;
+    int* d_remaining = d_state.get() + 3 * nb;
+    {
+        std::vector<int32_t> st((size_t)3 * nb + 1, 0);
+        std::copy(gens.begin(), gens.end(), st.begin());
+        st[3 * nb] = nb;
+        SC_HIP(hipMemcpyAsync(ints.get(), init.data(), init.size() * 4, hipMemcpyHostToDevice, m.stream));
+        SC_HIP(hipMemcpyAsync(d_state.get(), st.data(), st.size() * 4, hipMemcpyHostToDevice, m.stream));
+        SC_HIP(hipMemcpyAsync(d_seqs.get(), seqs.data(), seqs.size() * 4, hipMemcpyHostToDevice, m.stream));
+        SC_HIP(hipMemcpyAsync(d_streams.get(), streams.data(), streams.size() * 8, hipMemcpyHostToDevice, m.stream));
+        SC_HIP(hipMemsetAsync(d_slp.get(), 0, (size_t)nb * max_len * 4, m.stream));
+        SC_HIP(hipMemsetAsync(d_pref.get(), 0, (size_t)n * 4, m.stream));
+        SC_HIP(hipStreamSynchronize(m.stream));  // `st` is a host temporary
+    }
+
+    // ---- prompt echo: feed prefix[:-1]; cum = sum_j lprob(prefix[j] | prefix[<j]) under the temperature, the same for every
+    // hypothesis of an utterance --------------------------------------------------------------------------------------------------
+    for (int t = 0; t + 1 < prefix_len; ++t) {
+        decoder_step(m, c, /*project=*/false);
+        project_rows();
+        launch_sample_prompt_lprob(c.logits, ldl, n, V, B, h_prefix[t + 1], so.temperature, d_pref, m.stream);
+        for (int r = 0; r < nb; ++r) tok[r] = h_prefix[t + 1];
+        SC_HIP(hipMemcpyAsync(c.d_tok, tok.data(), (size_t)nb * 4, hipMemcpyHostToDevice, m.stream));
+        SC_HIP(hipStreamSynchronize(m.stream));
+    }
+    {
+        std::vector<float> pref(n), cum(nb);
+        SC_HIP(hipMemcpyAsync(pref.data(), d_pref.get(), (size_t)n * 4, hipMemcpyDeviceToHost, m.stream));
+        SC_HIP(hipStreamSynchronize(m.stream));
+        for (int r = 0; r < nb; ++r) cum[r] = pref[r / B];
+        SC_HIP(hipMemcpyAsync(d_cum.get(), cum.data(), (size_t)nb * 4, hipMemcpyHostToDevice, m.stream));
+        SC_HIP(hipStreamSynchronize(m.stream));
+    }
+
+    // ---- generation: device work only; the host polls `remaining` every fourth step --------------------------------------------
+    struct StepGraph {
+        hipGraph_t g = nullptr;
+        hipGraphExec_t e = nullptr;
+        ~StepGraph() {
+            if (e) (void)hipGraphExecDestroy(e);
+            if (g) (void)hipGraphDestroy(g);
+        }
+    } graph;
+    const bool step_graph = o.use_graph != 0 && c.rb > 0;
+    const int start = prefix_len - 1, G = o.no_repeat_ngram_size;
+    int remaining = nb;
+    for (int step = start; step <= max_len - 2 && remaining > 0; ++step) {
+        if (step_graph) {
+            if (!graph.e) {
+                std::lock_guard<std::mutex> lock(capture_mutex());
+                SC_HIP(hipStreamBeginCapture(m.stream, hipStreamCaptureModeThreadLocal));
+                try {
+                    decoder_step(m, c, /*project=*/false);
+                } catch (...) {
+                    hipGraph_t dead = nullptr;
+                    (void)hipStreamEndCapture(m.stream, &dead);
+                    if (dead) (void)hipGraphDestroy(dead);
+                    throw;
+                }
+                SC_HIP(hipStreamEndCapture(m.stream, &graph.g));
+                SC_HIP(hipGraphInstantiate(&graph.e, graph.g, nullptr, nullptr, 0));
+            }
+            SC_HIP(hipGraphLaunch(graph.e, m.stream));
+        } else {
+            decoder_step(m, c, /*project=*/false);  // feeds d_tok at position `step`, advances *d_pos
+        }
+        project_rows();
+        SampleArgs a;
+        a.logits = c.logits, a.ld = ldl, a.rows = nb, a.V = V;
+        a.stream = d_streams.get(), a.gen = d_gen, a.pos = step + 1;
+        a.temperature = so.temperature, a.top_k = so.top_k, a.top_p = so.top_p, a.seed = so.seed;
+        a.no_eos = step < o.min_seq_len, a.force_eos = step == max_len - 2;
+        a.pad_idx = W.pad_idx, a.eos_idx = W.eos_idx, a.unk_idx = W.unk_idx, a.unk_penalty = o.unk_penalty;
+        if ((G > 0 || bl.n > 0) && !a.force_eos) {  // step processors: not on the forced-EOS step
+            a.seqs_in = d_seqs.get(), a.S = step + 1, a.G = G, a.banned = bl;
+        }
+        a.seq_ld = max_len;
+        a.seqs = d_seqs.get(), a.next_tok = c.d_tok, a.cum = d_cum.get(), a.step_lprob = d_slp.get();
+        a.finished = d_fin, a.out_len = d_len, a.remaining = d_remaining;
+        launch_sample_rows(a, m.stream);
+        if (((step - start) & 3) == 3 || step == max_len - 2) {
+            SC_HIP(hipMemcpyAsync(&remaining, d_remaining, 4, hipMemcpyDeviceToHost, m.stream));
+            SC_HIP(hipStreamSynchronize(m.stream));
+        }
+    }
+
+    // ---- results: hypotheses of an utterance sorted by score (NaN first, then the higher score, ties keep the gen order) ----
+    std::vector<int32_t> lens(nb);
+    std::vector<float> cum(nb), slp((size_t)nb * max_len);
+    SC_HIP(hipMemcpyAsync(seqs.data(), d_seqs.get(), seqs.size() * 4, hipMemcpyDeviceToHost, m.stream));
+    SC_HIP(hipMemcpyAsync(lens.data(), d_len, (size_t)nb * 4, hipMemcpyDeviceToHost, m.stream));
+    SC_HIP(hipMemcpyAsync(cum.data(), d_cum.get(), (size_t)nb * 4, hipMemcpyDeviceToHost, m.stream));
+    SC_HIP(hipMemcpyAsync(slp.data(), d_slp.get(), slp.size() * 4, hipMemcpyDeviceToHost, m.stream));
+    SC_HIP(hipStreamSynchronize(m.stream));
+    std::vector<float> score(nb);
+    for (int r = 0; r < nb; ++r) {
+        SC_CHECK(lens[r] > prefix_len && lens[r] <= max_len, "sc_generate_text_sampled: row %d did not finish (length %d)", r, lens[r]);
+        // beam_select_kernel's expression: the EOS is appended at step = len - 2
+        score[r] = o.normalize_scores ? cum[r] / powf((float)(lens[r] - 1), o.len_penalty) : cum[r];
+    }
+    int longest = 0;  // of the best hypotheses (slot 0 of every utterance after sorting)
+    for (int u = 0; u < n; ++u) {
+        std::vector<int> ord(B);
+        for (int g = 0; g < B; ++g) ord[g] = u * B + g;
+        std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) {
+            const float s = score[a], t = score[b];
+            return std::isnan(t) ? false : (std::isnan(s) || s > t);
+        });
+        for (int g = 0; g < B; ++g) {
+            const int r = ord[g], dst = u * B + g, len = lens[r];
+            for (int t = 0; t < max_len; ++t) {
+                h_out_ids[(size_t)dst * max_len + t] = t < len ? seqs[(size_t)r * max_len + t] : W.pad_idx;
+                if (h_step_lprob) h_step_lprob[(size_t)dst * max_len + t] = t < len ? slp[(size_t)r * max_len + t] : 0.f;
+            }
+            h_out_lens[dst] = len;
+            if (h_scores) h_scores[dst] = score[r];
+        }
+        longest = std::max(longest, h_out_lens[u * B]);
+    }
+    // ---- decoder outputs of the best hypothesis per utterance: the teacher-forced pass, as behind a beam search ----------------
+    if (d_dec_hidden) {
+        const int fl = longest - 1;  // text_seqs[:, :-1]
+        std::vector<int32_t> forced((size_t)n * fl, W.pad_idx);
+        for (int u = 0; u < n; ++u)
+            for (int t = 0; t < fl && t < h_out_lens[u * B]; ++t) forced[(size_t)u * fl + t] = h_out_ids[(size_t)u * B * max_len + t];
+        Buf<float> hid(m.pp(), (size_t)n * fl * M);
+        run_generate_text(m, d_enc, n, s_enc, h_enc_lens, o, nullptr, 0, nullptr, nullptr, nullptr, hid, forced.data(), fl);
+        SC_HIP(hipMemsetAsync(d_dec_hidden, 0, (size_t)n * (max_len - 1) * M * 4, m.stream));
+        SC_HIP(hipMemcpy2DAsync(d_dec_hidden, (size_t)(max_len - 1) * M * 4, hid.get(), (size_t)fl * M * 4, (size_t)fl * M * 4, n,
+                                hipMemcpyDeviceToDevice, m.stream));
+        SC_HIP(hipStreamSynchronize(m.stream));
+    }
+}
+
+}  // namespace sc

@@ -1,10 +1,10 @@
 from .aligner import AlignmentExtractor, word_timestamps
-from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, SequenceGeneratorOptions
+from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, SequenceGeneratorOptions, TopKSampler, TopPSampler
 from .pretssel_generator import PretsselGenerator
 from .prosody_encoder import ProsodyEncoder
 from .transcriber import Transcriber, Transcription, TranscriptionToken, TranscriptionTokenStats
 from .unit_extractor import UnitExtractor
-from .translator import BatchedSpeechOutput, Modality, Task, Translator
+from .translator import BatchedSpeechOutput, Modality, SampledHypothesis, Task, Translator
 
-__all__ = ["AlignmentExtractor", "BannedSequenceProcessor", "BatchedSpeechOutput", "Modality", "NGramRepeatBlockProcessor", "PretsselGenerator", "ProsodyEncoder", "SequenceGeneratorOptions", "Task", "Transcriber", "Transcription", "TranscriptionToken",
+__all__ = ["AlignmentExtractor", "BannedSequenceProcessor", "BatchedSpeechOutput", "Modality", "NGramRepeatBlockProcessor", "PretsselGenerator", "ProsodyEncoder", "SampledHypothesis", "SequenceGeneratorOptions", "Task", "TopKSampler", "TopPSampler", "Transcriber", "Transcription", "TranscriptionToken",
            "TranscriptionTokenStats", "Translator", "UnitExtractor", "word_timestamps"]

@@ -79,6 +79,51 @@ class BannedSequenceProcessor:
             probs[hit, b[-1]] = fill
 
 
+class TopKSampler:
+    """Sampling from the ``k`` most probable tokens (fairseq2 0.2 ``TopKSampler``, restated from memory: UNVERIFIED).  On the HIP
+    path the draw runs inside the generation step (``sc_generate_text_sampled``)."""
+
+    def __init__(self, k: int = 10) -> None:
+        if isinstance(k, bool) or int(k) != k or k < 1:
+            raise ValueError(f"`k` must be an integer greater than or equal to 1, but is {k!r} instead.")
+        self.k = int(k)
+
+    top_p = 1.0
+
+    @property
+    def top_k(self) -> int:
+        return self.k
+
+
+class TopPSampler:
+    """Nucleus sampling: the smallest set of most probable tokens whose mass exceeds ``p`` (fairseq2 0.2 ``TopPSampler``,
+    restated from memory: UNVERIFIED); ``p = 1`` samples from the whole distribution."""
+
+    def __init__(self, p: float = 0.9) -> None:
+        p = float(p)
+        if not 0.0 < p <= 1.0:
+            raise ValueError(f"`p` must be greater than 0 and less than or equal to 1, but is {p} instead.")
+        self.p = p
+
+    top_k = 0
+
+    @property
+    def top_p(self) -> float:
+        return self.p
+
+
+def check_sampling(sampler, temperature: float, num_gens: int = 1) -> None:
+    """The limits ``sc_generate_text_sampled`` enforces, raised as ``ValueError`` before any device work."""
+    import math
+
+    if not isinstance(sampler, (TopKSampler, TopPSampler)):
+        raise ValueError(f"`sampler` must be a TopKSampler or a TopPSampler, but is {type(sampler).__name__} instead.")
+    if not (math.isfinite(temperature) and temperature > 0):
+        raise ValueError(f"`temperature` must be positive and finite, but is {temperature} instead.")
+    if isinstance(num_gens, bool) or int(num_gens) != num_gens or not 1 <= num_gens <= 64:
+        raise ValueError(f"`num_gens` must be an integer in 1..64, but is {num_gens!r} instead.")
+
+
 @dataclass
 class SequenceGeneratorOptions:
     """Holds the options to pass to a sequence generator."""
@@ -102,6 +147,15 @@ class SequenceGeneratorOptions:
 
     len_penalty: float = 1.0
     """The length penalty (beam search only)."""
+
+    sampler: Optional[Any] = None
+    """A :class:`TopKSampler` / :class:`TopPSampler`: sampled generation instead of beam search (``beam_size`` is ignored)."""
+
+    temperature: float = 1.0
+    """The logit temperature of sampled generation."""
+
+    seed: int = 0
+    """The 64-bit seed of sampled generation (the random stream is this library's, not torch's)."""
 
 
 def remove_consecutive_repeated_ngrams(sequence: List[int], min_size: int = 1, max_size: int = 40) -> List[int]:

@@ -27,7 +27,7 @@ import warnings
 from pathlib import Path
 from dataclasses import dataclass
 from enum import Enum, auto
-from typing import Any, Dict, List, Optional, Tuple, Union
+from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -39,7 +39,7 @@ from ..config import (S2STConfig, seamless_expressivity, seamless_m4t_large, sea
                       tiny_expressive_config, tiny_v1_config)
 from ..runtime import HipS2STModel
 from ..tokenizer import CharTokenizer, NllbTextTokenizer, UnitTokenizer
-from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, SequenceGeneratorOptions
+from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, SequenceGeneratorOptions, check_sampling
 from ..scoring import score as _score
 
 logger = logging.getLogger(__name__)
@@ -71,6 +71,22 @@ class BatchedSpeechOutput:
 
     sample_rate: int = 16000
     """Sample rate of the audio waveforms."""
+
+
+@dataclass
+class SampledHypothesis:
+    """One hypothesis of ``Translator.sample``."""
+
+    text: StringLike
+    token_ids: List[int]
+    """The whole sequence: prompt, drawn tokens, EOS."""
+
+    step_lprobs: List[float]
+    """Per position of ``token_ids``: the log-probability the token was drawn with (temperature and step rules applied),
+    0 at prompt positions."""
+
+    score: float
+    """The hypothesis score (sum of the log-probabilities, prompt included, length-normalised as beam-search scores are)."""
 
 
 # unity architectures (models/unity/builder.py:109-192): `base` / `medium` are the v1 models (w2v-BERT with relative
@@ -487,6 +503,74 @@ class Translator:
             self.last_stage_ms["vocoder"] = (time.perf_counter() - t_start) * 1e3
         return BatchedSpeechOutput(units=speech_units, audio_wavs=audio_wavs, sample_rate=sample_rate)
 
+    @staticmethod
+    def _step_processor_args(opts: SequenceGeneratorOptions) -> Tuple[int, Dict[str, Any]]:
+        """``opts.step_processor`` as the generation calls take it: (no_repeat_ngram_size, extra keywords - passed only when set:
+        models without the keyword keep working)."""
+        ngram = 0
+        step_kw: Dict[str, Any] = {}
+        proc = opts.step_processor
+        if proc is not None:
+            if isinstance(proc, NGramRepeatBlockProcessor):
+                ngram = proc.ngram_size
+            elif isinstance(proc, BannedSequenceProcessor):
+                if proc.banned_seqs:
+                    step_kw["banned_seqs"] = proc.banned_seqs
+            else:
+                raise NotImplementedError("the HIP path runs NGramRepeatBlockProcessor and BannedSequenceProcessor step processors only")
+        return ngram, step_kw
+
+    @torch.inference_mode()
+    def sample(
+        self,
+        input: Union[str, Tensor, SequenceData],
+        task_str: str,
+        tgt_lang: str,
+        src_lang: Optional[str] = None,
+        *,
+        sampler: Any,
+        num_gens: int = 1,
+        temperature: float = 1.0,
+        seed: int = 0,
+        streams: Optional[Sequence[int]] = None,
+        text_generation_opts: Optional[SequenceGeneratorOptions] = None,
+        sample_rate: int = 16000,
+    ) -> List[List["SampledHypothesis"]]:
+        """``num_gens`` sampled text hypotheses per input item (S2TT, ASR, T2TT), each list sorted by score - candidates for
+        ``score`` / a re-ranker.  Not part of the reference's ``Translator``; the semantics follow fairseq2 0.2's
+        ``SamplingSeq2SeqGenerator`` with ``TopKSampler`` / ``TopPSampler``.  The draws depend on
+        ``seed``, the item's id in ``streams`` (default: its index), the hypothesis number and the position only - not on
+        torch's generator, nor on what else is in the batch.  ``text_generation_opts`` supplies the length limits, ``unk_penalty``,
+        ``len_penalty`` and the step processor; its ``beam_size`` is ignored."""
+        input_modality, output_modality = self.get_modalities_from_task_str(task_str)
+        if output_modality != Modality.TEXT:
+            raise ValueError(f"Translator.sample covers text output (S2TT, ASR, T2TT); for {task_str} use "
+                             "predict(..., text_generation_opts=SequenceGeneratorOptions(sampler=...))")
+        check_sampling(sampler, temperature, num_gens)
+        opts = text_generation_opts or SequenceGeneratorOptions(beam_size=5, soft_max_seq_len=(1, 200))
+        ngram, step_kw = self._step_processor_args(opts)
+        _, seqs, src_lens, _ = self._source_batch(input, input_modality, src_lang, sample_rate)
+        if streams is not None and len(streams) != len(src_lens):
+            raise ValueError(f"`streams` must hold one id per input item ({len(src_lens)}), but holds {len(streams)} instead.")
+        if input_modality == Modality.SPEECH:
+            enc, enc_lens = self.model.encode_speech(seqs, src_lens)
+        else:
+            enc, enc_lens = self.model.encode_text(seqs.cpu().numpy(), src_lens), np.asarray(src_lens, dtype=np.int32)
+        ids, lens, scores, step_lprob, _ = self.model.generate_text_sampled(
+            enc, enc_lens.tolist(), self.text_tokenizer.target_prefix(tgt_lang), num_gens=num_gens, top_k=sampler.top_k,
+            top_p=sampler.top_p, temperature=temperature, seed=seed, streams=streams, len_penalty=opts.len_penalty,
+            soft_max_seq_len=opts.soft_max_seq_len, hard_max_seq_len=opts.hard_max_seq_len, unk_penalty=opts.unk_penalty,
+            no_repeat_ngram_size=ngram, use_graph=self.use_graph, source_len=int(max(src_lens)), **step_kw)
+        out: List[List[SampledHypothesis]] = []
+        for b in range(ids.shape[0]):
+            hyps = []
+            for g in range(ids.shape[1]):
+                toks = ids[b, g, : lens[b, g]].tolist()
+                hyps.append(SampledHypothesis(text=self.text_tokenizer.decode(toks), token_ids=toks,
+                                              step_lprobs=step_lprob[b, g, : lens[b, g]].tolist(), score=float(scores[b, g])))
+            out.append(hyps)
+        return out
+
     # translator.py:155-196
     @classmethod
     def get_prediction(
@@ -527,19 +611,14 @@ class Translator:
         else:
             lens = getattr(padding_mask, "seq_lens", padding_mask)
             src_lens = [int(x) for x in (lens.tolist() if isinstance(lens, Tensor) else lens)]
-        if not 1 <= text_generation_opts.beam_size <= 8:
+        sampler = getattr(text_generation_opts, "sampler", None)
+        if sampler is not None:
+            check_sampling(sampler, text_generation_opts.temperature)
+            if text_generation_opts.beam_size not in (1, 5):
+                logger.warning("text_generation_opts.sampler is set: beam_size=%d is ignored.", text_generation_opts.beam_size)
+        elif not 1 <= text_generation_opts.beam_size <= 8:
             raise ValueError("beam_size must be in [1, 8] on the HIP path")
-        ngram = 0
-        step_kw: Dict[str, Any] = {}  # passed only when set: models without the keyword keep working
-        if text_generation_opts.step_processor is not None:
-            proc = text_generation_opts.step_processor
-            if isinstance(proc, NGramRepeatBlockProcessor):
-                ngram = proc.ngram_size
-            elif isinstance(proc, BannedSequenceProcessor):
-                if proc.banned_seqs:
-                    step_kw["banned_seqs"] = proc.banned_seqs
-            else:
-                raise NotImplementedError("the HIP path runs NGramRepeatBlockProcessor and BannedSequenceProcessor step processors only")
+        ngram, step_kw = cls._step_processor_args(text_generation_opts)
         trace = _trace if _trace is not None else {}
         want_speech = output_modality == Modality.SPEECH
 
@@ -551,9 +630,18 @@ class Translator:
             enc, enc_lens = model.encode_text(seqs.cpu().numpy(), src_lens), np.asarray(src_lens, dtype=np.int32)
         t1 = time.perf_counter()
         prefix = text_tokenizer.target_prefix(tgt_lang)
-        ids, out_lens, scores, hidden = model.generate_text(
+        gen_kw: Dict[str, Any] = {"beam_size": text_generation_opts.beam_size}
+        generate = model.generate_text
+        if sampler is not None:  # one sampled hypothesis per utterance feeds the rest of the chain
+            def generate(*a: Any, **kw: Any):
+                i, l, s, _, h = model.generate_text_sampled(*a, **kw)
+                return i[:, 0], l[:, 0], s[:, 0], h
+
+            gen_kw = {"num_gens": 1, "top_k": sampler.top_k, "top_p": sampler.top_p, "temperature": text_generation_opts.temperature,
+                      "seed": text_generation_opts.seed}
+        ids, out_lens, scores, hidden = generate(
             enc, enc_lens.tolist(), prefix,
-            beam_size=text_generation_opts.beam_size,
+            **gen_kw,
             len_penalty=text_generation_opts.len_penalty,
             soft_max_seq_len=text_generation_opts.soft_max_seq_len,
             hard_max_seq_len=text_generation_opts.hard_max_seq_len,

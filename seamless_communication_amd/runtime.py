@@ -339,6 +339,45 @@ class HipS2STModel(_Handle):
                                         _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden)), "sc_generate_text")
         return ids, lens, scores, hidden
 
+    def generate_text_sampled(self, enc: torch.Tensor, enc_lens: Sequence[int], prefix: Sequence[int], num_gens: int = 1,
+                              top_k: int = 0, top_p: float = 1.0, temperature: float = 1.0, seed: int = 0, streams=None,
+                              soft_max_seq_len=(1, 200), hard_max_seq_len: int = 1024, min_seq_len: int = 1,
+                              unk_penalty: float = 0.0, use_graph: bool = True, want_hidden: bool = False,
+                              len_penalty: float = 1.0, normalize_scores: bool = True, no_repeat_ngram_size: int = 0,
+                              source_len: int = 0, banned_seqs=None):
+        """Sampled generation (sc_generate_text_sampled): ``num_gens`` hypotheses per utterance, sorted by score.
+        -> (ids (n, num_gens, max_len) int32, lens (n, num_gens), scores (n, num_gens), step_lprob (n, num_gens, max_len),
+        hidden (n, max_len-1, M) of hypothesis 0 or None).  ``streams``: one 64-bit id per utterance (None: 0 .. n-1); with
+        ``seed`` it fixes the draws whatever else shares the batch.  The other arguments are generate_text's."""
+        assert enc.is_cuda and enc.is_contiguous()
+        n, s_enc, M = enc.shape
+        o = self._gen_opts(1, soft_max_seq_len, hard_max_seq_len, min_seq_len, unk_penalty, use_graph, len_penalty,
+                           normalize_scores, no_repeat_ngram_size, source_len)
+        so = _lib.sc_sample_opts()
+        so.abi_version, so.num_gens, so.top_k = _lib.SC_ABI_VERSION, int(num_gens), int(top_k)
+        so.top_p, so.temperature, so.seed = float(top_p), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF
+        g = max(1, min(64, int(num_gens)))  # (an invalid num_gens is refused by the call; the buffers only need a sane size)
+        max_len = self.lib.sc_text_max_len(self.handle, C.byref(o), s_enc)
+        ids = np.zeros((n, g, max_len), dtype=np.int32)
+        lens = np.zeros((n, g), dtype=np.int32)
+        scores = np.zeros((n, g), dtype=np.float32)
+        step_lprob = np.zeros((n, g, max_len), dtype=np.float32)
+        hidden = torch.empty(n, max_len - 1, M, dtype=torch.float32, device=self.device) if want_hidden else None
+        pre, el = _i32(prefix), _i32(enc_lens)
+        st = None
+        if streams is not None:
+            st = np.ascontiguousarray(np.asarray([int(s) & 0xFFFFFFFFFFFFFFFF for s in streams], dtype=np.uint64))
+            if st.shape != (n,):
+                raise ValueError(f"`streams` must hold one id per utterance ({n}), but holds {st.shape} instead.")
+        b_tok = b_off = None
+        if banned_seqs is not None and len(banned_seqs) > 0:
+            b_tok, b_off = _lib.banned_csr(banned_seqs)
+        self._after_torch()
+        check(self.lib.sc_generate_text_sampled(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), C.byref(so), _ptr(st), _ptr(pre),
+                                                len(pre), _ptr(ids), _ptr(lens), _ptr(scores), _ptr(step_lprob), _ptr(hidden), _ptr(b_tok),
+                                                _ptr(b_off), 0 if b_off is None else len(b_off) - 1), "sc_generate_text_sampled")
+        return ids, lens, scores, step_lprob, hidden
+
     def generate_text_capture(self, enc: torch.Tensor, enc_lens: Sequence[int], prefix: Sequence[int],
                               soft_max_seq_len=(1, 200), hard_max_seq_len: int = 1024, min_seq_len: int = 1,
                               unk_penalty: float = 0.0, use_graph: bool = True, want_hidden: bool = False,
