@@ -367,6 +367,34 @@ int sc_score_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, con
                   const int32_t* h_tok_lens, int32_t s_text, float* h_tok_lprob, float* h_sum_lprob, int32_t* h_top1,
                   float* d_dec_hidden);
 
+/* Spoken-language identification (additive, ABI 10): which __lang__ token the text decoder expects after the prompt - the
+ * reference's "LID scores" (ggml/examples/unity/fairseq2.cpp:1208-1221: the decoder is fed the prompt's </s>, the log-softmax of
+ * the next position is read at every language token; its target language `unk` takes their arg-max, :1227-1236).
+ *   h_prefix [prefix_len]   the tokens fed, normally {</s>}; 1 <= prefix_len <= text_max_seq_len; one prompt for all items
+ *   h_cand   [n_cand]       candidate token ids, strictly ascending, inside the vocabulary; 1 <= n_cand <= 512
+ *   h_lprob  [n][n_cand]    log-softmax over the WHOLE vocabulary at the position behind the prompt, read at the candidates:
+ *                           raw (no step rules, not renormalised over the candidates), always <= 0
+ *   h_best   [n]            index into h_cand of the largest value (the lowest index among equal values)
+ * The prompt goes through sc_score_text's batched causal pass and the vocabulary projection reads the candidate columns in its
+ * epilogue: h_lprob[b][j] carries the bits of sc_score_text's h_tok_lprob at the last position of the sequence
+ * prefix + {h_cand[j]}, at the cost of ONE pass over the projection weight, and an item's results do not depend on what else is
+ * in the batch.  Runs on the handle's own stream (never the decode engine); works on forked handles and for every text decoder
+ * the handle can hold.  SC_ERR_INVALID before any device work for a NULL pointer, n_cand outside 1..512, a list that is not
+ * strictly ascending, an id outside the vocabulary, an enc_lens entry out of range or prefix_len outside 1..text_max_seq_len. */
+int sc_identify_language(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix,
+                         int32_t prefix_len, const int32_t* h_cand, int32_t n_cand, float* h_lprob, int32_t* h_best);
+
+/* sc_generate_text with ONE PROMPT PER ROW (additive, ABI 10): h_prefix_rows [n][prefix_len], row b is fed its own prompt - a
+ * batch in mixed target languages, e.g. the languages sc_identify_language chose.  All prompts of a call have the same length.
+ * Everything else is sc_generate_text's, on every path it takes: the handle's greedy chain, the decode engine (per-row tokens
+ * in the admit record) and the host-driven beam / n-gram loop (every beam of an utterance gets its utterance's prompt).  A row's
+ * results carry the bits of the sc_generate_text call whose shared prompt is that row's.  SC_ERR_INVALID for a prompt token
+ * outside the vocabulary.  sc_generate_text_banned, sc_generate_text_sampled and sc_generate_text_capture keep the shared
+ * prompt. */
+int sc_generate_text_rows(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
+                          const sc_gen_opts* opts, const int32_t* h_prefix_rows /* [n][prefix_len] */, int32_t prefix_len,
+                          int32_t* h_out_ids, int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden);
+
 /* a12-a17: UnitYNART2UModel.forward + argmax + unit decoding
  * (models/unity/model.py:379-441, generator.py:338-353).  h_text_seqs
  * [n][s_text] is text_seqs[:, :-1] (pad filled), h_text_lens its PaddingMask.

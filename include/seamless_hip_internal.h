@@ -131,6 +131,13 @@ int sc_op_linear_presplit_score(const float* d_x, const void* d_w_f16, const flo
 int sc_op_linear_presplit_score_grouped(const float* d_x, const void* d_w_f16, const float* d_bias, const int32_t* d_target,
                                         float* d_lprob, float* d_sum_lprob, float* d_lse, int32_t* d_top1, int32_t M, int32_t N,
                                         int32_t K, int32_t group_rows);
+/* The candidate-set form (the vocabulary projection of sc_identify_language): h_cand [n_cand] on the host, strictly ascending
+ * columns inside [0, N), 1 <= n_cand <= 512 (anything else: SC_ERR_INVALID before any launch).  Each wave of the product also
+ * writes v at the candidate columns of its range; the finish kernel gives d_lprob [M][n_cand] = v[m][cand[j]] - lse[m] - bit for
+ * bit sc_op_linear_presplit_score's d_lprob with target cand[j] - and d_best [M] = the j of the largest v[m][cand[j]], the lowest
+ * j among equal values.  A NaN row: NaN log-probabilities, d_best 0, no other row touched. */
+int sc_op_score_candidates(const float* d_x, const void* d_w_f16, const float* d_bias, const int32_t* h_cand, int32_t n_cand, float* d_lprob,
+                           int32_t* d_best, int32_t M, int32_t N, int32_t K);
 int32_t sc_op_score_record_cols(int32_t N);
 int32_t sc_op_score_group_rows(int32_t N);
 /* Conv1d (stride 1) through the pre-split product kernel's implicit-convolution mode: x [nb][t][cin] is split into two

@@ -193,6 +193,8 @@ SIGNATURES = {
     "sc_generate_text_capture": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P, _P, _P]),
     "sc_decode_text": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P]),
     "sc_score_text": (C.c_int, [_P, _P, _i, _i, _P, _P, _P, _i, _P, _P, _P, _P]),
+    "sc_identify_language": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P, _i, _P, _P]),
+    "sc_generate_text_rows": (C.c_int, [_P, _P, _i, _i, _P, _P, _P, _i, _P, _P, _P, _P]),
     "sc_engine_create": (_P, [_P, C.POINTER(sc_engine_opts)]),
     "sc_engine_free": (None, [_P]),
     "sc_engine_attach": (C.c_int, [_P, _P]),
@@ -297,6 +299,7 @@ SIGNATURES = {
     "sc_op_linear_presplit_argmax": (C.c_int, [_P, _P, _P, _P, _i, _i, _i]),
     "sc_op_linear_presplit_score": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i]),
     "sc_op_linear_presplit_score_grouped": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i]),
+    "sc_op_score_candidates": (C.c_int, [_P, _P, _P, _P, _i, _P, _P, _i, _i, _i]),
     "sc_op_score_record_cols": (_i, [_i]),
     "sc_op_score_group_rows": (_i, [_i]),
     "sc_op_conv1d_presplit": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _i, _i, _P, _i]),

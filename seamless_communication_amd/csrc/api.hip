@@ -365,6 +365,32 @@ int sc_score_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, con
     SC_API_END
 }
 
+int sc_identify_language(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix,
+                         int32_t prefix_len, const int32_t* h_cand, int32_t n_cand, float* h_lprob, int32_t* h_best) {
+    SC_API_BEGIN
+    // (the count first: an empty list may well come with a null pointer, and the caller should read which of the two it was)
+    SC_CHECK(n_cand >= 1 && n_cand <= SCORE_MAX_CAND, "sc_identify_language: n_cand=%d outside 1..%d", n_cand, SCORE_MAX_CAND);
+    SC_CHECK(m && d_enc && h_enc_lens && h_prefix && h_cand && h_lprob && h_best, "sc_identify_language: null argument");
+    SC_HIP(hipSetDevice(m->m.device));
+    run_identify_language(m->m, d_enc, n, s_enc, h_enc_lens, h_prefix, prefix_len, h_cand, n_cand, h_lprob, h_best);
+    SC_API_END
+}
+
+int sc_generate_text_rows(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
+                          const sc_gen_opts* opts, const int32_t* h_prefix_rows, int32_t prefix_len, int32_t* h_out_ids,
+                          int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden) {
+    SC_API_BEGIN
+    SC_CHECK(m && d_enc && h_enc_lens && opts && h_prefix_rows && h_out_ids && h_out_lens, "sc_generate_text_rows: null argument");
+    SC_CHECK(n > 0 && prefix_len >= 1, "sc_generate_text_rows: n=%d prefix_len=%d", n, prefix_len);
+    for (int64_t i = 0; i < (int64_t)n * prefix_len; ++i)
+        SC_CHECK(h_prefix_rows[i] >= 0 && h_prefix_rows[i] < m->m.cfg.text_vocab_size,
+                 "sc_generate_text_rows: prompt token %d (row %d) outside the vocabulary", h_prefix_rows[i], (int)(i / prefix_len));
+    SC_HIP(hipSetDevice(m->m.device));
+    run_generate_text(m->m, d_enc, n, s_enc, h_enc_lens, *opts, h_prefix_rows, prefix_len, h_out_ids, h_out_lens, h_out_scores,
+                      d_dec_hidden, nullptr, 0, nullptr, nullptr, /*prefix_stride=*/prefix_len);
+    SC_API_END
+}
+
 int sc_t2u_nar(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text, const int32_t* h_text_lens,
                const int32_t* h_text_seqs, float duration_factor, int32_t* h_unit_lens, int32_t* out_s_unit_max,
                int32_t* out_s_char_max) {
@@ -1307,6 +1333,54 @@ int sc_op_linear_presplit_score_grouped(const float* d_x, const void* d_w_f16, c
 int sc_op_linear_presplit_score(const float* d_x, const void* d_w_f16, const float* d_bias, const int32_t* d_target, float* d_lprob,
                                 float* d_sum_lprob, float* d_lse, int32_t* d_top1, int32_t M, int32_t N, int32_t K) {
     return sc_op_linear_presplit_score_grouped(d_x, d_w_f16, d_bias, d_target, d_lprob, d_sum_lprob, d_lse, d_top1, M, N, K, 0);
+}
+
+int sc_op_score_candidates(const float* d_x, const void* d_w_f16, const float* d_bias, const int32_t* h_cand, int32_t n_cand, float* d_lprob,
+                           int32_t* d_best, int32_t M, int32_t N, int32_t K) {
+    SC_API_BEGIN
+    SC_CHECK(d_x && d_w_f16 && h_cand && d_lprob && d_best, "sc_op_score_candidates: null argument");
+    SC_CHECK(M > 0 && N > 0 && K > 0, "sc_op_score_candidates: M=%d N=%d K=%d", M, N, K);
+    check_score_candidates(h_cand, n_cand, N, "sc_op_score_candidates");
+    const int group = std::min(gemm_score_group_rows(N), M);
+    const size_t rec_bytes = (size_t)group * gemm_score_records(N) * SCORE_REC_FLOATS * 4, cv_bytes = (size_t)group * n_cand * 4;
+    __half *hi = nullptr, *lo = nullptr;
+    float *rec = nullptr, *cv = nullptr;
+    int* cand = nullptr;
+    const auto free_all = [&] {
+        (void)hipFree(hi);
+        (void)hipFree(lo);
+        (void)hipFree(rec);
+        (void)hipFree(cv);
+        (void)hipFree(cand);
+    };
+    try {
+        SC_HIP(hipMalloc(&hi, (size_t)M * K * 2));
+        SC_HIP(hipMalloc(&lo, (size_t)M * K * 2));
+        SC_HIP(hipMalloc(&rec, rec_bytes));
+        SC_HIP(hipMalloc(&cv, cv_bytes));
+        SC_HIP(hipMalloc(&cand, (size_t)n_cand * 4));
+        SC_HIP(hipMemsetAsync(rec, 0xff, rec_bytes, g_op_stream));  // NaN / -1: every record and every value must be written
+        SC_HIP(hipMemsetAsync(cv, 0xff, cv_bytes, g_op_stream));
+        SC_HIP(hipMemcpyAsync(cand, h_cand, (size_t)n_cand * 4, hipMemcpyHostToDevice, g_op_stream));
+        launch_split_f32(d_x, hi, lo, (int64_t)M * K, g_op_stream);
+        GemmPsArgs a;
+        a.Ah = hi;
+        a.Al = lo;
+        a.lda = K;
+        a.W = static_cast<const __half*>(d_w_f16);
+        a.ldw = K;
+        a.bias = d_bias;
+        a.M = M;
+        a.N = N;
+        a.K = K;
+        launch_gemm_presplit_score_cand(a, cand, n_cand, rec, cv, group, d_lprob, d_best, g_op_stream);
+        SC_HIP(hipStreamSynchronize(g_op_stream));
+    } catch (...) {
+        free_all();
+        throw;
+    }
+    free_all();
+    SC_API_END
 }
 
 int32_t sc_op_score_record_cols(int32_t N) { return N > 0 ? gemm_score_record_cols(N) : -1; }

@@ -25,7 +25,7 @@ class Engine {
     void stats(sc_engine_stats* out, bool reset);
     // greedy generation of n rows through the shared chain; blocks until every row has finished.  Arguments as run_generate_text.
     void generate(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix, int prefix_len,
-                  int max_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores, float* d_dec_hidden);
+                  int max_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, int prefix_stride = 0);
 
    private:
     struct Impl;

@@ -38,6 +38,7 @@ namespace {
 
 struct Request {
     int n = 0, s_enc = 0, max_len = 0, prefix_len = 0;
+    int prefix_stride = 0;  // 0: one prompt for every row; otherwise row i's prompt starts at h_prefix[i * prefix_stride]
     const int32_t* h_prefix = nullptr;
     const int32_t* h_enc_lens = nullptr;
     float* d_hidden = nullptr;
@@ -255,7 +256,8 @@ void Engine::Impl::admit(const std::vector<Live>& rows) {
         a.limit = q->max_len;
         a.prefix_len = q->prefix_len;
         a.enc_len = q->h_enc_lens[rows[i].row];
-        for (int t = 0; t < ENGINE_MAX_PREFIX; ++t) a.prefix[t] = t < q->prefix_len ? q->h_prefix[t] : cfg.pad_idx;
+        const int32_t* pre = q->h_prefix + (size_t)rows[i].row * q->prefix_stride;
+        for (int t = 0; t < ENGINE_MAX_PREFIX; ++t) a.prefix[t] = t < q->prefix_len ? pre[t] : cfg.pad_idx;
     }
     SC_HIP(hipMemcpyAsync(d_admit.get(), h_admit.p, rows.size() * sizeof(EngineAdmitRec), hipMemcpyHostToDevice, em.stream));
     launch_engine_admit(d_admit, (int)rows.size(), er, cfg.pad_idx, em.stream);
@@ -477,13 +479,13 @@ void Engine::stats(sc_engine_stats* out, bool reset) {
 }
 
 void Engine::generate(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix, int prefix_len,
-                      int max_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores, float* d_dec_hidden) {
+                      int max_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, int prefix_stride) {
     Impl& E = *p_;
     const sc_config& cfg = m.cfg;
     const int M = cfg.model_dim, se = E.o.s_enc;
     Request q;
     q.n = n, q.s_enc = s_enc, q.max_len = max_len, q.prefix_len = prefix_len;
-    q.h_prefix = h_prefix, q.h_enc_lens = h_enc_lens, q.d_hidden = d_dec_hidden;
+    q.h_prefix = h_prefix, q.prefix_stride = prefix_stride, q.h_enc_lens = h_enc_lens, q.d_hidden = d_dec_hidden;
     q.ids.assign((size_t)n * max_len, cfg.pad_idx);
     q.lens.assign(n, 0);
     q.scores.assign(n, 0.f);

@@ -191,9 +191,11 @@ __global__ __launch_bounds__(256) void beam_candidates_banned_kernel(float* logi
 }
 
 __global__ __launch_bounds__(256) void row_token_lprob_kernel(const float* __restrict__ logits, int64_t ld, int V,
-                                                              int row_stride, int token, float* __restrict__ out) {
+                                                              int row_stride, int token, const int* __restrict__ row_tokens,
+                                                              float* __restrict__ out) {
     __shared__ float red[4];
     const float* row = logits + (int64_t)blockIdx.x * row_stride * ld;
+    if (row_tokens) token = row_tokens[(int64_t)blockIdx.x * row_stride];  // the per-row form: the token of the same row
     float mx = -INFINITY;
     for (int i = threadIdx.x; i < V; i += 256) mx = fmaxf(mx, row[i]);
     mx = block_reduce_max(mx, red);
@@ -663,7 +665,13 @@ void launch_beam_compact(const BeamCompactArgs& a, hipStream_t s) {
 
 void launch_row_token_lprob(const float* logits, int64_t ld, int rows, int V, int row_stride, int token, float* out, hipStream_t s) {
     SC_CHECK(token >= 0 && token < V, "row_token_lprob: token %d out of range", token);
-    hipLaunchKernelGGL(row_token_lprob_kernel, dim3(rows), dim3(256), 0, s, logits, ld, V, row_stride, token, out);
+    hipLaunchKernelGGL(row_token_lprob_kernel, dim3(rows), dim3(256), 0, s, logits, ld, V, row_stride, token, (const int*)nullptr, out);
+    SC_LAUNCH_CHECK();
+}
+
+void launch_row_tokens_lprob(const float* logits, int64_t ld, int rows, int V, int row_stride, const int* row_tokens, float* out, hipStream_t s) {
+    SC_CHECK(row_tokens, "row_tokens_lprob: null token array");
+    hipLaunchKernelGGL(row_token_lprob_kernel, dim3(rows), dim3(256), 0, s, logits, ld, V, row_stride, 0, row_tokens, out);
     SC_LAUNCH_CHECK();
 }
 

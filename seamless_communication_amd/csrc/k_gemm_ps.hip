@@ -160,8 +160,9 @@ __device__ __forceinline__ void ps_epilogue(const GemmPsArgs& p, const float* ep
 template <int BM, int BN, int WGM, int WGN, bool SPLIT, bool CONV, bool AMAX>
 __global__ __launch_bounds__(WGM* WGN * 64) void gemm_ps_kernel(GemmPsArgs p, int tiles_n, int tiles_total, int tiles_per_xcd,
                                                                  uint32_t a_bytes, uint32_t w_bytes) {
-    constexpr bool SCORE = false;
+    constexpr bool SCORE = false, CAND = false;
     const GemmScoreArgs sc{};  // never read: every use sits behind `if constexpr (SCORE)`
+    const GemmCandArgs cd{};   // nor this one (`if constexpr (CAND)`)
 #include "k_gemm_ps_body.h"
 }
 
@@ -169,24 +170,35 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm_ps_kernel(GemmPsArgs p, in
 template <int BM, int BN, int WGM, int WGN>
 __global__ __launch_bounds__(WGM* WGN * 64) void gemm_score_kernel(GemmPsArgs p, int tiles_n, int tiles_total, int tiles_per_xcd,
                                                                     uint32_t a_bytes, uint32_t w_bytes, GemmScoreArgs sc) {
-    constexpr bool SPLIT = true, CONV = false, AMAX = false, SCORE = true;
+    constexpr bool SPLIT = true, CONV = false, AMAX = false, SCORE = true, CAND = false;
+    const GemmCandArgs cd{};  // never read: every use sits behind `if constexpr (CAND)`
+#include "k_gemm_ps_body.h"
+}
+
+// the SCORE epilogue with a candidate list instead of a target per row (launch_gemm_presplit_score_cand); a kernel of its own
+// for the same reason: the two above keep their code
+template <int BM, int BN, int WGM, int WGN>
+__global__ __launch_bounds__(WGM* WGN * 64) void gemm_cand_kernel(GemmPsArgs p, int tiles_n, int tiles_total, int tiles_per_xcd,
+                                                                   uint32_t a_bytes, uint32_t w_bytes, GemmScoreArgs sc, GemmCandArgs cd) {
+    constexpr bool SPLIT = true, CONV = false, AMAX = false, SCORE = true, CAND = true;
 #include "k_gemm_ps_body.h"
 }
 
 template <int BM, int BN, int WGM, int WGN>
-void launch_ps_cfg(const GemmPsArgs& a, hipStream_t s, const GemmScoreArgs* score = nullptr) {
+void launch_ps_cfg(const GemmPsArgs& a, hipStream_t s, const GemmScoreArgs* score = nullptr, const GemmCandArgs* cand = nullptr) {
     const int tiles_m = cdiv(a.M, BM), tiles_n = cdiv(a.N, BN);
     const int tiles_total = tiles_m * tiles_n;
     const int tiles_per_xcd = cdiv(tiles_total, 8);
     char name[64];
     snprintf(name, sizeof(name), "gemm_%dx%d_presplit", BM, BN);
     prof::Scope scope(name, 2.0 * a.M * (double)a.N * a.K,
-                      4.0 * a.M * (double)a.K + 2.0 * a.N * (double)a.K + (score ? 4.0 * SCORE_REC_FLOATS * a.M * (double)score->ld : a.amax ? 8.0 * a.M * (double)a.amax_ld : 4.0 * a.M * (double)a.N * (a.res ? 2.0 : 1.0)), s);
+                      4.0 * a.M * (double)a.K + 2.0 * a.N * (double)a.K + (score ? 4.0 * a.M * (SCORE_REC_FLOATS * (double)score->ld + (cand ? cand->n_cand : 0)) : a.amax ? 8.0 * a.M * (double)a.amax_ld : 4.0 * a.M * (double)a.N * (a.res ? 2.0 : 1.0)), s);
     const dim3 grid(tiles_per_xcd * 8), block(WGM * WGN * 64);
     const uint32_t ab = (uint32_t)((int64_t)a.M * a.lda * 2), wb = (uint32_t)((int64_t)a.N * a.ldw * 2);
     const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb); };
     const bool conv = a.conv_taps > 0;
-    if (score) hipLaunchKernelGGL((gemm_score_kernel<BM, BN, WGM, WGN>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb, *score);
+    if (score && cand) hipLaunchKernelGGL((gemm_cand_kernel<BM, BN, WGM, WGN>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb, *score, *cand);
+    else if (score) hipLaunchKernelGGL((gemm_score_kernel<BM, BN, WGM, WGN>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb, *score);
     else if (a.amax) launch(gemm_ps_kernel<BM, BN, WGM, WGN, true, false, true>);  // split, plain product (launch_gemm_presplit)
     else if (a.split && conv) launch(gemm_ps_kernel<BM, BN, WGM, WGN, true, true, false>);
     else if (a.split) launch(gemm_ps_kernel<BM, BN, WGM, WGN, true, false, false>);
@@ -302,16 +314,10 @@ namespace {
 // One wave per row.  Lane l takes records l, l + 64, ... in ascending order, the 64 partial results meet in a butterfly
 // (xor 32 ... 1): the order depends on the number of records only.  First the row's maximum and its lowest column, then the
 // records' sums rescaled to that maximum.
-__global__ __launch_bounds__(256) void score_finish_kernel(const float* __restrict__ rec, int ld, int rows, int N, int cols,
-                                                            const int* __restrict__ target, float* __restrict__ lprob,
-                                                            float* __restrict__ sum_lprob, float* __restrict__ lse_out,
-                                                            int* __restrict__ top1) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const float* pr = rec + (int64_t)row * ld * SCORE_REC_FLOATS;
-    float best = -INFINITY;
-    int bidx = 0x7fffffff;
+// (every lane of the wave ends up with the row's four values)
+__device__ __forceinline__ void score_fold(const float* __restrict__ pr, int ld, int lane, float& best, int& bidx, float& tot, float& sv) {
+    best = -INFINITY;
+    bidx = 0x7fffffff;
     for (int i = lane; i < ld; i += 64) {
         const float v = pr[i * SCORE_REC_FLOATS];
         const int vi = __float_as_int(pr[i * SCORE_REC_FLOATS + 4]);
@@ -329,9 +335,17 @@ __global__ __launch_bounds__(256) void score_finish_kernel(const float* __restri
             bidx = oi;
         }
     }
-    float tot = 0.f, sv = 0.f;
+    tot = 0.f, sv = 0.f;
     for (int i = lane; i < ld; i += 64) {
-        tot += pr[i * SCORE_REC_FLOATS + 1] * expf(pr[i * SCORE_REC_FLOATS] - best);
+        // product and sum rounded separately, by pragma: left to the compiler, score_finish_kernel rounds twice (it adds tot
+        // and sv as a pair) while a kernel that drops sv fuses the two into one fma - and a lane with more than one record
+        // (ld > 64: the full-size vocabulary) then sums to other bits
+        const float ex = expf(pr[i * SCORE_REC_FLOATS] - best);
+        {
+#pragma clang fp contract(off)
+            const float term = pr[i * SCORE_REC_FLOATS + 1] * ex;
+            tot = tot + term;
+        }
         sv += pr[i * SCORE_REC_FLOATS + 2];
     }
 #pragma unroll
@@ -339,6 +353,19 @@ __global__ __launch_bounds__(256) void score_finish_kernel(const float* __restri
         tot += __shfl_xor(tot, o);
         sv += __shfl_xor(sv, o);
     }
+}
+
+__global__ __launch_bounds__(256) void score_finish_kernel(const float* __restrict__ rec, int ld, int rows, int N, int cols,
+                                                            const int* __restrict__ target, float* __restrict__ lprob,
+                                                            float* __restrict__ sum_lprob, float* __restrict__ lse_out,
+                                                            int* __restrict__ top1) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* pr = rec + (int64_t)row * ld * SCORE_REC_FLOATS;
+    float best, tot, sv;
+    int bidx;
+    score_fold(pr, ld, lane, best, bidx, tot, sv);
     if (lane != 0) return;
     // the record that holds the maximum contributes its own sum unscaled, and that sum holds exp(0) = 1: tot >= 1, log >= 0
     const float lt = logf(tot);
@@ -352,6 +379,40 @@ __global__ __launch_bounds__(256) void score_finish_kernel(const float* __restri
     if (sum_lprob) sum_lprob[row] = sv - (float)N * lse;
     if (lse_out) lse_out[row] = lse;
     if (top1) top1[row] = argmax_stored_index(bidx);
+}
+
+// The candidate form's finish: the same fold, then lane l takes candidates l, l + 64, ...: the log-probability by the target
+// form's expression, and the arg-max over the candidates' values (the lowest j among equal values; NaN never wins, a row of
+// NaN keeps the sentinel = stored as 0).
+__global__ __launch_bounds__(256) void cand_finish_kernel(const float* __restrict__ rec, int ld, int rows, const float* __restrict__ cand_v,
+                                                           int n_cand, float* __restrict__ lprob, int* __restrict__ best_j) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    float best, tot, sv;
+    int bidx;
+    score_fold(rec + (int64_t)row * ld * SCORE_REC_FLOATS, ld, lane, best, bidx, tot, sv);
+    const float lt = logf(tot);
+    float cb = -INFINITY;
+    int cj = 0x7fffffff;
+    for (int j = lane; j < n_cand; j += 64) {
+        const float v = cand_v[(int64_t)row * n_cand + j];
+        lprob[(int64_t)row * n_cand + j] = (v - best) - lt;
+        if (v > cb || (v == cb && j < cj)) {
+            cb = v;
+            cj = j;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(cb, o);
+        const int oj = __shfl_xor(cj, o);
+        if (ob > cb || (ob == cb && oj < cj)) {
+            cb = ob;
+            cj = oj;
+        }
+    }
+    if (lane == 0) best_j[row] = argmax_stored_index(cj);
 }
 }  // namespace
 
@@ -386,6 +447,53 @@ void launch_gemm_presplit_score(const GemmPsArgs& a, const int* target, float* r
         hipLaunchKernelGGL(score_finish_kernel, dim3(cdiv(g.M, 4)), dim3(256), 0, s, rec, ld, g.M, a.N, cols, target + r0,
                            lprob ? lprob + r0 : nullptr, sum_lprob ? sum_lprob + r0 : nullptr, lse ? lse + r0 : nullptr,
                            top1 ? top1 + r0 : nullptr);
+        SC_LAUNCH_CHECK();
+    }
+}
+
+void check_score_candidates(const int32_t* h_cand, int n_cand, int N, const char* who) {
+    SC_CHECK(h_cand, "%s: null candidate list", who);
+    SC_CHECK(n_cand >= 1 && n_cand <= SCORE_MAX_CAND, "%s: n_cand=%d outside 1..%d", who, n_cand, SCORE_MAX_CAND);
+    for (int j = 0; j < n_cand; ++j) {
+        SC_CHECK(h_cand[j] >= 0 && h_cand[j] < N, "%s: candidate %d (entry %d) outside the vocabulary [0, %d)", who, h_cand[j], j, N);
+        SC_CHECK(j == 0 || h_cand[j] > h_cand[j - 1], "%s: the candidate list is not strictly ascending at entry %d (%d after %d)", who, j,
+                 h_cand[j], h_cand[j - 1]);
+    }
+}
+
+void launch_gemm_presplit_score_cand(const GemmPsArgs& a, const int* cand, int n_cand, float* rec, float* cand_v, int rec_rows,
+                                     float* lprob, int* best_j, hipStream_t s) {
+    SC_CHECK(a.Ah && a.Al && a.W && cand && rec && cand_v && lprob && best_j && rec_rows > 0, "presplit candidates: null operand");
+    SC_CHECK(n_cand >= 1 && n_cand <= SCORE_MAX_CAND, "presplit candidates: %d candidates outside 1..%d", n_cand, SCORE_MAX_CAND);
+    SC_CHECK(a.split && a.conv_taps == 0 && !a.C && !a.Ch && !a.Cl && !a.res && !a.row_valid && !a.amax && a.act == ACT_NONE,
+             "presplit candidates: takes a plain product (no C / planes / residual / activation)");
+    SC_CHECK(a.M > 0 && a.N > 0 && a.K > 0 && a.K % PBK == 0, "presplit candidates: M=%d N=%d K=%d (K must be a multiple of 32)", a.M, a.N, a.K);
+    SC_CHECK(a.lda % 8 == 0 && a.ldw % 8 == 0 && a.ldw >= a.K && a.lda >= a.K, "presplit candidates: lda=%lld ldw=%lld", (long long)a.lda,
+             (long long)a.ldw);
+    SC_CHECK(((reinterpret_cast<uintptr_t>(a.Ah) | reinterpret_cast<uintptr_t>(a.Al) | reinterpret_cast<uintptr_t>(a.W)) & 15) == 0 &&
+                 (reinterpret_cast<uintptr_t>(rec) & 7) == 0,
+             "presplit candidates: operands must be 16-byte aligned");
+    SC_CHECK((int64_t)a.N * a.ldw * 2 < (1ll << 31), "presplit candidates: weight larger than 2 GB");
+    const int tile = score_tile(a.N), cols = tile / 2, ld = cdiv(a.N, cols);
+    for (int r0 = 0; r0 < a.M; r0 += rec_rows) {  // row groups as in launch_gemm_presplit_score
+        GemmPsArgs g = a;
+        g.M = std::min(rec_rows, a.M - r0);
+        g.Ah = a.Ah + (int64_t)r0 * a.lda;
+        g.Al = a.Al + (int64_t)r0 * a.lda;
+        SC_CHECK((int64_t)g.M * a.lda * 2 < (1ll << 31), "presplit candidates: row group larger than 2 GB");
+        GemmScoreArgs sa;
+        sa.rec = rec;
+        sa.ld = ld;
+        GemmCandArgs ca;
+        ca.cand = cand;
+        ca.v = cand_v;
+        ca.n_cand = n_cand;
+        if (tile == 256) launch_ps_cfg<256, 256, 4, 2>(g, s, &sa, &ca);
+        else if (tile == 128) launch_ps_cfg<128, 128, 2, 2>(g, s, &sa, &ca);
+        else launch_ps_cfg<64, 64, 2, 2>(g, s, &sa, &ca);
+        SC_LAUNCH_CHECK();
+        hipLaunchKernelGGL(cand_finish_kernel, dim3(cdiv(g.M, 4)), dim3(256), 0, s, rec, ld, g.M, cand_v, n_cand,
+                           lprob + (int64_t)r0 * n_cand, best_j + r0);
         SC_LAUNCH_CHECK();
     }
 }

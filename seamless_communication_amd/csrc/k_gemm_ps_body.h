@@ -1,8 +1,11 @@
 // Body of the pre-split product kernels of k_gemm_ps.hip (the schedule is described there).  NOT a stand-alone header: it is
 // included inside the braces of gemm_ps_kernel and of gemm_score_kernel, which supply
-//   template / constexpr parameters  BM, BN, WGM, WGN, SPLIT, CONV, AMAX, SCORE
-//   arguments                        GemmPsArgs p, tiles_n, tiles_total, tiles_per_xcd, a_bytes, w_bytes, GemmScoreArgs sc
-// so that the two kernels share every instruction of the K loop while gemm_ps_kernel keeps its own argument list.
+//   template / constexpr parameters  BM, BN, WGM, WGN, SPLIT, CONV, AMAX, SCORE, CAND
+//   arguments                        GemmPsArgs p, tiles_n, tiles_total, tiles_per_xcd, a_bytes, w_bytes, GemmScoreArgs sc,
+//                                    GemmCandArgs cd
+// so that the kernels share every instruction of the K loop while gemm_ps_kernel keeps its own argument list.
+// CAND (with SCORE; gemm_cand_kernel only): no target column; the wave also writes its value at every candidate column of
+// cd.cand that lies in its column range.  Every statement of it sits behind `if constexpr (CAND)`.
 // OOB and the vector types are device_util.h's, which k_gemm_ps.hip includes (this text sits inside a function body).
     constexpr int NWAVE = WGM * WGN;
     constexpr bool ALTERNATE = SPLIT && NWAVE == 8;  // the K loop's schedule, see above
@@ -393,8 +396,28 @@
     // maximum (am_best, its lowest column am_idx), sum of exp(v - maximum), sum of v, v at the row's target column
     float sc_sum = 0.f, sc_sumv = 0.f, sc_vt = 0.f;
     int sc_tgt = -1;
-    if constexpr (SCORE) {
+    if constexpr (SCORE && !CAND) {
         if (lane < WM && m0w + lane < p.M) sc_tgt = sc.target[m0w + lane];
+    }
+    // CAND: the candidates [cd_j, cd_j1) of the sorted list lie in the wave's columns [n0 + wn * WN, + WN): two binary searches
+    // per wave, wave-uniform (scalar loads); the passes then consume them in ascending order
+    int cd_j = 0, cd_j1 = 0;
+    if constexpr (CAND) {
+        const int c_lo = __builtin_amdgcn_readfirstlane(n0 + wn * WN);
+        int lo = 0, hi = cd.n_cand;  // first candidate >= c_lo
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (cd.cand[mid] < c_lo) lo = mid + 1;
+            else hi = mid;
+        }
+        cd_j = lo;
+        hi = cd.n_cand;  // first candidate >= c_lo + WN
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (cd.cand[mid] < c_lo + WN) lo = mid + 1;
+            else hi = mid;
+        }
+        cd_j1 = lo;
     }
     auto pass = [&](auto hc) {  // compile-time pass number: the accumulator registers are indexed by constants
         constexpr int h = decltype(hc)::value;
@@ -463,6 +486,20 @@
                             sc_sum += expf(v - am_best);
                         }
                     }
+                }
+            }
+            if constexpr (CAND) {
+                // the candidates inside this pass's columns (all below N: the list is checked on the host), out of the tile
+                // that still sits in LDS: lane r reads row r at the candidate's column and forms v as above
+                while (cd_j < cd_j1) {
+                    const int col = cd.cand[cd_j];
+                    if (col >= n0w + EPN) break;
+                    if (lane < WM && m0w + lane < p.M) {
+                        const float a = ep[lane * EP_LD + (col - n0w)];
+                        const float v = (a + (p.bias ? p.bias[col] : 0.f)) * p.alpha;
+                        cd.v[(int64_t)(m0w + lane) * cd.n_cand + cd_j] = v;
+                    }
+                    ++cd_j;
                 }
             }
             return;

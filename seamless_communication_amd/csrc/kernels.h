@@ -209,6 +209,25 @@ int gemm_score_group_rows(int N);
 void launch_gemm_presplit_score(const GemmPsArgs& a, const int* target, float* rec, int rec_rows, float* lprob, float* sum_lprob,
                                 float* lse, int* top1, hipStream_t s);
 
+// Candidate-set form of the same product (language identification): instead of one target per row, a strictly ascending
+// device list cand[0 .. n_cand) of columns shared by all rows, 1 <= n_cand <= SCORE_MAX_CAND, every entry inside [0, N) (the
+// caller checks the list: the kernel trusts it).  Each wave writes, besides its record, v at every candidate column inside
+// its column range - the record's own expression, read from the same LDS pass - to cand_v[m][j]; the finish kernel folds the
+// records in launch_gemm_presplit_score's order and writes
+//   lprob[m][j] = (cand_v[m][j] - max) - log(sum)   = bit for bit what the target form returns for target cand[j],
+//   best_j[m]   = arg-max_j cand_v[m][j], the lowest j among equal values; 0 for a row whose values are all NaN.
+// cand_v holds rec_rows * n_cand floats.  A row's results depend on that row only, as above.
+constexpr int SCORE_MAX_CAND = 512;
+struct GemmCandArgs {
+    const int* cand = nullptr;  // [n_cand], strictly ascending
+    float* v = nullptr;         // [rows of the launch][n_cand]
+    int n_cand = 0;
+};
+// the host's check of a candidate list (1 .. SCORE_MAX_CAND entries, strictly ascending, inside [0, N)); throws, naming `who`
+void check_score_candidates(const int32_t* h_cand, int n_cand, int N, const char* who);
+void launch_gemm_presplit_score_cand(const GemmPsArgs& a, const int* cand, int n_cand, float* rec, float* cand_v, int rec_rows,
+                                     float* lprob, int* best_j, hipStream_t s);
+
 // k_resblock.hip: out = x + conv2_{k,1}(lrelu(conv1_{k,dil}(lrelu(x)) + b1)) + b2 for C in {16, 32, 64}, the
 // intermediate kept in LDS; optionally out = ((avg_a + avg_b) + that) / 3.  Weights packed [C][ldw], tap-major.
 struct ResPairArgs {
@@ -660,6 +679,9 @@ struct BeamCompactArgs {
 };
 void launch_beam_compact(const BeamCompactArgs& a, hipStream_t s);
 void launch_row_token_lprob(const float* logits, int64_t ld, int rows, int V, int row_stride, int token, float* out, hipStream_t s);
+// the per-row-token form: output i is the log-softmax value of row_tokens[i * row_stride] (a device array with one token per
+// logit row, e.g. StepCtx::d_tok; the caller has checked the tokens against V) in logit row i * row_stride
+void launch_row_tokens_lprob(const float* logits, int64_t ld, int rows, int V, int row_stride, const int* row_tokens, float* out, hipStream_t s);
 void launch_gather_cache(const float* src, float* dst, const int* src_row, int rows, int len, int cap, int M, int layers,
                          int64_t layer_stride, hipStream_t s);
 

@@ -373,7 +373,9 @@ void banned_blocked_tokens(const int32_t* seq, int S, const BannedHost& b, std::
 void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens,
                        const sc_gen_opts& o, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
                        int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, const int32_t* h_forced_tokens,
-                       int forced_len, const XattnCapture* xcap = nullptr, const BannedHost* banned = nullptr);
+                       int forced_len, const XattnCapture* xcap = nullptr, const BannedHost* banned = nullptr, int prefix_stride = 0);
+void run_identify_language(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix,
+                           int prefix_len, const int32_t* h_cand, int n_cand, float* h_lprob, int32_t* h_best);
 void run_score_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens,
                     const int32_t* h_tok_lens, int s_text, float* h_tok_lprob, float* h_sum_lprob, int32_t* h_top1, float* d_dec_hidden);
 // d_cond: [n][film_cond_dim] on the device for a FiLM model, null otherwise (a mismatch is an error)
@@ -395,7 +397,7 @@ void run_t2u_ar(Model& m, const float* d_dec_hidden, int n, int s_text, const in
 void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, const int* d_text_lens, float* d_out);
 void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                        const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                       float* d_dec_hidden, int max_len, const BannedHost* banned = nullptr);
+                       float* d_dec_hidden, int max_len, const BannedHost* banned = nullptr, int prefix_stride = 0);
 // sampled generation (model_sample.hip): outputs [n][num_gens][...], hypotheses of an utterance sorted by score
 void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                           const sc_sample_opts& so, const uint64_t* h_streams, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,

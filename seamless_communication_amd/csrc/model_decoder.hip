@@ -28,7 +28,7 @@ int text_max_len(const Model& m, const sc_gen_opts& o, int s_enc) {
 
 void run_generate_text_beam(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                             const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                            float* d_dec_hidden, const BannedHost* banned = nullptr);
+                            float* d_dec_hidden, const BannedHost* banned = nullptr, int prefix_stride = 0);
 
 namespace {
 
@@ -1246,12 +1246,67 @@ void run_score_text(Model& m, const float* d_enc, int n, int s_enc, const int32_
         }
 }
 
+// Spoken-language identification (sc_identify_language): the prompt (normally {</s>}) goes through run_score_text's batched
+// causal pass, and the NEXT position's log-softmax over the whole vocabulary is read at the candidate tokens - raw, no step
+// rules: the reference's "LID scores" (ggml/examples/unity/fairseq2.cpp:1208-1221; its `unk` target language is the arg-max of
+// them, :1227-1236).  The candidate values come out of the projection's epilogue (launch_gemm_presplit_score_cand), so item b's
+// lprob[j] carries the bits sc_score_text returns for the sequence prefix + {cand[j]} at its last position, and depends on
+// item b alone.  Own stream, never the decode engine.
+void run_identify_language(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix,
+                           int prefix_len, const int32_t* h_cand, int n_cand, float* h_lprob, int32_t* h_best) {
+    const sc_config& cfg = m.cfg;
+    const int M = cfg.model_dim, V = cfg.text_vocab_size;
+    // every argument error before any device work
+    SC_CHECK(n > 0 && s_enc > 0, "sc_identify_language: empty batch");
+    SC_CHECK(!m.dec.empty() && m.text_embed, "sc_identify_language: the handle holds no text decoder");
+    SC_CHECK(prefix_len >= 1 && prefix_len <= cfg.text_max_seq_len, "sc_identify_language: prefix_len=%d outside [1, %d]", prefix_len,
+             cfg.text_max_seq_len);
+    SC_CHECK(M % 32 == 0, "sc_identify_language: model_dim=%d is not a multiple of 32", M);
+    check_score_candidates(h_cand, n_cand, V, "sc_identify_language");
+    for (int b = 0; b < n; ++b)
+        SC_CHECK(h_enc_lens[b] > 0 && h_enc_lens[b] <= s_enc, "sc_identify_language: enc_lens[%d]=%d out of range", b, h_enc_lens[b]);
+    for (int t = 0; t < prefix_len; ++t)
+        SC_CHECK(h_prefix[t] >= 0 && h_prefix[t] < V, "sc_identify_language: prompt token %d outside the vocabulary", h_prefix[t]);
+    std::vector<int32_t> in_tok((size_t)n * prefix_len), row_idx((size_t)n);
+    for (int b = 0; b < n; ++b) {
+        std::copy(h_prefix, h_prefix + prefix_len, in_tok.begin() + (size_t)b * prefix_len);
+        row_idx[b] = b * prefix_len + prefix_len - 1;  // the position that predicts the language token
+    }
+    Buf<float> hidden(m.pp(), (size_t)n * prefix_len * M);
+    run_decode_text_batched(m, d_enc, n, s_enc, h_enc_lens, in_tok.data(), prefix_len, hidden, /*row_independent=*/true);
+    prof::set_tag("lid");
+    const int group = std::min(gemm_score_group_rows(V), (n + 255) / 256 * 256);
+    Buf<int> d_idx(m.pp(), n), d_cand(m.pp(), n_cand), d_best(m.pp(), n);
+    Buf<float> packed(m.pp(), (size_t)n * M), d_lp(m.pp(), (size_t)n * n_cand), cand_v(m.pp(), (size_t)group * n_cand),
+        rec(m.pp(), (size_t)group * gemm_score_records(V) * SCORE_REC_FLOATS);
+    Buf<__half> ph(m.pp(), (size_t)n * M), pl(m.pp(), (size_t)n * M);
+    SC_HIP(hipMemcpyAsync(d_idx.get(), row_idx.data(), (size_t)n * 4, hipMemcpyHostToDevice, m.stream));
+    SC_HIP(hipMemcpyAsync(d_cand.get(), h_cand, (size_t)n_cand * 4, hipMemcpyHostToDevice, m.stream));
+    launch_gather_rows(hidden, M, d_idx, packed, M, n, M, m.stream);
+    launch_split_f32(packed, ph, pl, (int64_t)n * M, m.stream);
+    GemmPsArgs a;
+    a.Ah = ph;
+    a.Al = pl;
+    a.lda = M;
+    a.W = m.text_embed;
+    a.ldw = M;
+    a.M = n;
+    a.N = V;
+    a.K = M;
+    launch_gemm_presplit_score_cand(a, d_cand, n_cand, rec, cand_v, group, d_lp, d_best, m.stream);
+    SC_HIP(hipMemcpyAsync(h_lprob, d_lp.get(), (size_t)n * n_cand * 4, hipMemcpyDeviceToHost, m.stream));
+    SC_HIP(hipMemcpyAsync(h_best, d_best.get(), (size_t)n * 4, hipMemcpyDeviceToHost, m.stream));
+    SC_HIP(hipStreamSynchronize(m.stream));  // row_idx / h_cand are host memory; outputs complete on return
+}
+
 // forced_tokens != null: teacher-forced pass over the given tokens (no arg-max
 // feedback, hidden states only).  Otherwise greedy generation.
+// prefix_stride: 0 = every row is fed h_prefix[0 .. prefix_len); otherwise row b is fed h_prefix[b * prefix_stride + ...]
+// (sc_generate_text_rows).
 void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens,
                        const sc_gen_opts& o, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
                        int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, const int32_t* h_forced_tokens,
-                       int forced_len, const XattnCapture* xcap, const BannedHost* banned) {
+                       int forced_len, const XattnCapture* xcap, const BannedHost* banned, int prefix_stride) {
     const sc_config& cfg = m.cfg;
     const int M = cfg.model_dim;
     SC_CHECK(n > 0 && s_enc > 0, "sc_generate_text: empty batch");
@@ -1278,7 +1333,7 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
         if (o.beam_size > 1 || o.no_repeat_ngram_size > 0 || has_banned) {  // step processors run in the host-driven step loop
             if (m.engine) m.engine->expect(m, -n);
             run_generate_text_beam(m, d_enc, n, s_enc, h_enc_lens, o, h_prefix, prefix_len, h_out_ids, h_out_lens, h_scores,
-                                   d_dec_hidden, has_banned ? banned : nullptr);
+                                   d_dec_hidden, has_banned ? banned : nullptr, prefix_stride);
             return;
         }
         SC_CHECK(prefix_len >= 1, "sc_generate_text: the prompt must hold at least one token");
@@ -1296,7 +1351,8 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
     if (!forced && m.engine && xcap) m.engine->expect(m, -n);
     if (!forced && m.engine && !xcap) {
         if (m.engine->fits(n, s_enc, max_len, prefix_len, o) && m.engine->has_company()) {
-            m.engine->generate(m, d_enc, n, s_enc, h_enc_lens, h_prefix, prefix_len, max_len, h_out_ids, h_out_lens, h_scores, d_dec_hidden);
+            m.engine->generate(m, d_enc, n, s_enc, h_enc_lens, h_prefix, prefix_len, max_len, h_out_ids, h_out_lens, h_scores, d_dec_hidden,
+                               prefix_stride);
             return;
         }
         m.engine->expect(m, -n);  // announced rows that run on the handle's own chain after all
@@ -1355,7 +1411,7 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
     std::vector<int32_t> hist((size_t)n * max_len, cfg.pad_idx), init(8 + 4 * n, 0);
     const int feed_len = forced ? forced_len : prefix_len;
     for (int b = 0; b < n; ++b)
-        for (int t = 0; t < feed_len; ++t) hist[(size_t)b * max_len + t] = forced ? h_forced_tokens[(size_t)b * forced_len + t] : h_prefix[t];
+        for (int t = 0; t < feed_len; ++t) hist[(size_t)b * max_len + t] = forced ? h_forced_tokens[(size_t)b * forced_len + t] : h_prefix[(size_t)b * prefix_stride + t];
     init[1] = n;  // live rows (StepCtx::d_rows_greedy)
     for (int b = 0; b < n; ++b) {
         init[8 + b] = hist[(size_t)b * max_len];  // token fed at position 0
@@ -1607,10 +1663,10 @@ void banned_blocked_tokens(const int32_t* seq, int S, const BannedHost& b, std::
 
 void run_generate_text_beam(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                             const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                            float* d_dec_hidden, const BannedHost* banned) {
+                            float* d_dec_hidden, const BannedHost* banned, int prefix_stride) {
     const DecStack W = unity_stack(m);
     run_generate_beam(m, W, d_enc, n, s_enc, h_enc_lens, o, h_prefix, prefix_len, h_out_ids, h_out_lens, h_scores, d_dec_hidden,
-                      text_max_len(m, o, s_enc), banned);
+                      text_max_len(m, o, s_enc), banned, prefix_stride);
 }
 
 // UnitYT2UModel generation of the v1 models (inference/generator.py:316-336): T2U encoder over the text decoder output,
@@ -1640,7 +1696,8 @@ void run_t2u_ar(Model& m, const float* d_dec_hidden, int n, int s_text, const in
 // Beam search over one decoder stack (the UnitY text decoder or the v1 autoregressive unit decoder).
 void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                        const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                       float* d_dec_hidden, int max_len, const BannedHost* banned) {
+                       float* d_dec_hidden, int max_len, const BannedHost* banned, int prefix_stride) {
+    // prefix_stride: 0 = one prompt for all; otherwise utterance u's prompt is h_prefix[u * prefix_stride + ...], fed to each of its beams
     struct VocabView {  // the names the body used for the text vocabulary, now the stack's
         int pad_idx, unk_idx, eos_idx, text_max_seq_len, model_dim, dec_ffn_dim;
     };
@@ -1807,8 +1864,9 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
     std::vector<int32_t> seqs((size_t)nb * max_len, cfg.pad_idx), init(8 + 5 * nb, 0), tok(nb);
     std::vector<float> cum(nb, 0.f);
     for (int r = 0; r < nb; ++r) {
-        for (int t = 0; t < prefix_len; ++t) seqs[(size_t)r * max_len + t] = h_prefix[t];
-        init[8 + r] = h_prefix[0];
+        const int32_t* pre = h_prefix + (size_t)(r / B) * prefix_stride;
+        for (int t = 0; t < prefix_len; ++t) seqs[(size_t)r * max_len + t] = pre[t];
+        init[8 + r] = pre[0];
         init[8 + 3 * nb + r] = h_enc_lens[r / B];
     }
     SC_HIP(hipMemcpyAsync(ints.get(), init.data(), init.size() * 4, hipMemcpyHostToDevice, m.stream));
@@ -1856,10 +1914,14 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
     for (int t = 0; t + 1 < prefix_len; ++t) {
         decoder_step(m, c, /*project=*/false);
         project_rows();
-        launch_row_token_lprob(c.logits, ldl, n, V, B, h_prefix[t + 1], d_pref, m.stream);
-        for (int r = 0; r < nb; ++r) tok[r] = h_prefix[t + 1];
-        SC_HIP(hipMemcpyAsync(pref.data(), d_pref.get(), (size_t)n * 4, hipMemcpyDeviceToHost, m.stream));
+        // (the step has consumed d_tok: the next tokens go up first, and the per-row-token kernel reads them from there)
+        for (int r = 0; r < nb; ++r) {
+            tok[r] = h_prefix[(size_t)(r / B) * prefix_stride + t + 1];
+            SC_CHECK(tok[r] >= 0 && tok[r] < V, "sc_generate_text: prompt token %d out of range", tok[r]);
+        }
         SC_HIP(hipMemcpyAsync(c.d_tok, tok.data(), (size_t)nb * 4, hipMemcpyHostToDevice, m.stream));
+        launch_row_tokens_lprob(c.logits, ldl, n, V, B, c.d_tok, d_pref, m.stream);
+        SC_HIP(hipMemcpyAsync(pref.data(), d_pref.get(), (size_t)n * 4, hipMemcpyDeviceToHost, m.stream));
         SC_HIP(hipStreamSynchronize(m.stream));
         for (int r = 0; r < nb; ++r) cum[r] += pref[r / B];
     }

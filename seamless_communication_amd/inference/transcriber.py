@@ -24,6 +24,7 @@ from torch import Tensor
 from ..runtime import HipS2STModel
 from ..tokenizer import NllbTextTokenizer
 from .. import cards as _cards
+from ..lid import identify_encoded
 from .translator import _ARCHS, _load_state_dict, _resolve_card
 
 # generator options the reference passes to fairseq2's BeamSearchSeq2SeqGenerator (transcriber.py run_inference); the
@@ -56,10 +57,14 @@ class TranscriptionToken:
 class Transcription:
     text: str
     tokens: List[TranscriptionToken]
+    lang: Optional[str]  # the language transcribed in: the caller's src_lang, or the identified one (src_lang=None)
+    lid: Optional[Any]   # the lid.LanguageId behind an identified `lang`; None when src_lang was given
 
-    def __init__(self, tokens: List[TranscriptionToken]):
+    def __init__(self, tokens: List[TranscriptionToken], lang: Optional[str] = None, lid: Optional[Any] = None):
         self.tokens = tokens
         self.text = " ".join(t.text for t in tokens)
+        self.lang = lang
+        self.lid = lid
 
     def __add__(self, other: "Transcription") -> "Transcription":
         self.text += " " + other.text
@@ -187,26 +192,32 @@ class Transcriber:
             o["max_seq_len"] = min(int(o["max_seq_len"]), prefix_len + int(gen))
         return soft, int(o["max_seq_len"]), float(o["unk_penalty"])
 
-    def _decode(self, wav: Tensor, sample_rate: int, src_lang: str, opts: Dict[str, Any]):
+    def _decode(self, wav: Tensor, sample_rate: int, src_lang: Optional[str], opts: Dict[str, Any]):
         """-> (token ids without prompt and EOS, step scores of those tokens, attention rows of the reference's hook
-        without its last row)."""
+        without its last row, the language, its identification or None).  ``src_lang=None``: the language token the decoder
+        expects behind ``</s>`` (lid.identify_encoded on the same encoder output)."""
         model = self.model
         w = wav[:, 0].to(torch.float32).contiguous().unsqueeze(0).to(self.device)
         # standardize=True, waveform_scale 2**15 inside the HIP front end; no padding, no padding mask
         fb, frames = model.fbank(w, [w.shape[1]], standardize=True, pad_to_multiple=1, sample_rate=int(sample_rate))
         enc, enc_lens = model.encode_speech(fb, frames)
+        lid = None
+        if src_lang is None:
+            lid = identify_encoded(model, self.tokenizer, enc, enc_lens)[0]
+            src_lang = lid.lang
         prefix = self.tokenizer.target_prefix(src_lang)
         soft, hard, unk = self._gen_limits(opts, len(prefix), int(frames[0]))
         ids, lens, _, xattn, step_lprob, _ = model.generate_text_capture(
             enc, enc_lens.tolist(), prefix, soft_max_seq_len=soft, hard_max_seq_len=hard, unk_penalty=unk,
             use_graph=self.use_graph, source_len=int(frames[0]))
-        return restate_hook_rows(ids[0], int(lens[0]), len(prefix), xattn[0, :, : int(enc_lens[0])].cpu().numpy(), step_lprob[0])
+        return (*restate_hook_rows(ids[0], int(lens[0]), len(prefix), xattn[0, :, : int(enc_lens[0])].cpu().numpy(), step_lprob[0]),
+                src_lang, lid)
 
     @torch.inference_mode()
     def transcribe(
         self,
         audio: Union[str, Tensor],
-        src_lang: str,
+        src_lang: Optional[str],
         filter_width: int = 3,
         sample_rate: int = 16000,
         denoise: bool = False,
@@ -216,7 +227,8 @@ class Transcriber:
         **sequence_generator_options: Dict,
     ) -> Optional[Transcription]:
         """audio: a file path or a (T, C) waveform tensor at ``sample_rate`` -> the words with their start times and
-        probabilities.  ``sequence_generator_options``: BeamSearchSeq2SeqGenerator's (beam_size 1 only)."""
+        probabilities.  ``sequence_generator_options``: BeamSearchSeq2SeqGenerator's (beam_size 1 only).
+        ``src_lang=None``: the language is identified first; the result's ``lang`` names it and ``lid`` holds the scores."""
         if denoise:
             raise NotImplementedError("denoise=True: the Demucs denoiser is not part of this project")
         if isinstance(audio, (str, Path)):
@@ -238,12 +250,12 @@ class Transcriber:
         beam_size = opts.pop("beam_size", None) or 1
         if beam_size > 1:
             raise NotImplementedError("beam_size > 1: the attention capture runs on the greedy decoder step only")
-        token_ids, step_scores, rows = self._decode(wav, sample_rate, src_lang, opts)
+        token_ids, step_scores, rows, lang, lid = self._decode(wav, sample_rate, src_lang, opts)
         if not token_ids:  # EOS first: no token, no timestamp
-            return Transcription([])
+            return Transcription([], lang, lid)
         times = self._extract_timestamps(rows, length_seconds, filter_width)
         pieces = [self.tokenizer.index_to_token(t) for t in token_ids]
-        return Transcription(self._collect_word_level_stats(pieces=pieces, token_timestamps=times, step_scores=step_scores))
+        return Transcription(self._collect_word_level_stats(pieces=pieces, token_timestamps=times, step_scores=step_scores), lang, lid)
 
 
 def restate_hook_rows(ids: np.ndarray, length: int, prefix_len: int, xattn: np.ndarray,

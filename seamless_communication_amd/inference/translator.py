@@ -41,6 +41,7 @@ from ..runtime import HipS2STModel
 from ..tokenizer import CharTokenizer, NllbTextTokenizer, UnitTokenizer
 from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, SequenceGeneratorOptions, check_sampling
 from ..scoring import score as _score
+from ..lid import LanguageId, identify_encoded as _identify_encoded, identify_language as _identify_language
 
 logger = logging.getLogger(__name__)
 
@@ -253,6 +254,7 @@ class Translator:
         self.last_stage_ms: Dict[str, float] = {}
         self.last_t2u: Optional[Dict[str, Any]] = None  # units / durations / char ids of the last speech-output call
         self.last_wav_full: Optional[Tensor] = None     # un-trimmed vocoder output (N, 1, S_u * hop) of the last call
+        self.last_lid: Optional[List[LanguageId]] = None  # the identifications of the last predict(..., tgt_lang=None)
 
     def fork(self) -> "Translator":
         """A view of this translator for another host thread: same weights and tokenizers, own HIP
@@ -262,7 +264,7 @@ class Translator:
         view = copy.copy(self)
         view.model = self.model.fork()
         view.last_text_ids, view.last_stage_ms = [], {}
-        view.last_t2u, view.last_wav_full = None, None
+        view.last_t2u, view.last_wav_full, view.last_lid = None, None, None
         return view
 
     # translator.py:199-213
@@ -365,7 +367,7 @@ class Translator:
         self,
         input: Union[str, Tensor, SequenceData],
         task_str: str,
-        tgt_lang: str,
+        tgt_lang: Optional[str],
         src_lang: Optional[str] = None,
         text_generation_opts: Optional[SequenceGeneratorOptions] = None,
         unit_generation_opts: Optional[SequenceGeneratorOptions] = None,
@@ -376,7 +378,18 @@ class Translator:
         prosody_encoder_input: Optional[SequenceData] = None,
         src_text: Optional[StringLike] = None,
     ) -> Tuple[List[StringLike], Optional[BatchedSpeechOutput]]:
+        """``tgt_lang=None`` (text output only - s2tt, asr, t2tt; not part of the reference's ``predict``, its native port's
+        target language ``unk``): the model picks every row's language token itself (``identify_language`` on the encoder
+        output) and the batch is generated with one prompt per row; ``last_lid`` then holds the identifications."""
         input_modality, output_modality = self.get_modalities_from_task_str(task_str)
+        if tgt_lang is None:  # refused before any device work
+            if output_modality != Modality.TEXT:
+                raise ValueError(f"`tgt_lang` must be specified for {task_str}: the T2U model and the vocoder need a stated language "
+                                 "(tgt_lang=None identifies the language for s2tt, asr and t2tt).")
+            if self.apply_mintox:
+                raise ValueError("`tgt_lang` must be specified when `apply_mintox` is `True`.")
+            if getattr(text_generation_opts, "sampler", None) is not None:
+                raise ValueError("`tgt_lang` must be specified for sampled generation.")
         if prosody_encoder_input is not None and getattr(self.model, "prosody_encoder", None) is None:
             raise NoProsodyEncoderError(f"model '{self.cfg.name}' has no prosody encoder: prosody_encoder_input is for the expressive "
                                         "model (card 'seamless_expressivity')")
@@ -439,6 +452,7 @@ class Translator:
         self.last_text_ids = trace["text_ids"]
         self.last_stage_ms = trace["stage_ms"]
         self.last_t2u = trace.get("t2u")
+        self.last_lid = trace.get("lid")
         if output_modality == Modality.TEXT:
             return texts, None
 
@@ -472,6 +486,8 @@ class Translator:
 
     # teacher-forced scoring of given targets (scoring.py)
     score = _score
+    # spoken-language identification (lid.py)
+    identify_language = _identify_language
 
     def _speech_from_ar_units(self, units: np.ndarray, pad: int, tgt_lang: str, spkr: Optional[int], sample_rate: int,
                               t_start: float) -> BatchedSpeechOutput:
@@ -582,7 +598,7 @@ class Translator:
         padding_mask: Any,
         input_modality: Modality,
         output_modality: Modality,
-        tgt_lang: str,
+        tgt_lang: Optional[str],
         text_generation_opts: SequenceGeneratorOptions,
         unit_generation_opts: Optional[SequenceGeneratorOptions],
         unit_generation_ngram_filtering: bool = False,
@@ -621,6 +637,8 @@ class Translator:
         ngram, step_kw = cls._step_processor_args(text_generation_opts)
         trace = _trace if _trace is not None else {}
         want_speech = output_modality == Modality.SPEECH
+        if tgt_lang is None and (want_speech or sampler is not None or step_kw):
+            raise ValueError("`tgt_lang=None` (identify the language) covers text output without a sampler or banned sequences")
 
         # every sc_* stage call returns with its stream drained, so host timers are stage times
         t0 = time.perf_counter()
@@ -629,7 +647,11 @@ class Translator:
         else:
             enc, enc_lens = model.encode_text(seqs.cpu().numpy(), src_lens), np.asarray(src_lens, dtype=np.int32)
         t1 = time.perf_counter()
-        prefix = text_tokenizer.target_prefix(tgt_lang)
+        if tgt_lang is None:  # one prompt per row, each with the language token the decoder itself expects behind </s>
+            trace["lid"] = _identify_encoded(model, text_tokenizer, enc, enc_lens)
+            prefix: Any = np.asarray([text_tokenizer.target_prefix(l.lang) for l in trace["lid"]], dtype=np.int32)
+        else:
+            prefix = text_tokenizer.target_prefix(tgt_lang)
         gen_kw: Dict[str, Any] = {"beam_size": text_generation_opts.beam_size}
         generate = model.generate_text
         if sampler is not None:  # one sampled hypothesis per utterance feeds the rest of the chain

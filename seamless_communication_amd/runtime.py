@@ -316,9 +316,15 @@ class HipS2STModel(_Handle):
         """-> (ids (n, max_len) int32, lens (n,), scores (n,), hidden (n, max_len-1, M) or None).
         ``source_len``: padded length of the source sequences the soft length rule refers to (fbank frames for speech);
         0 = the encoder output length.  ``banned_seqs``: token sequences (lists of ints) for the banned-sequence step
-        processor (sc_generate_text_banned); None or an empty list is the plain call."""
+        processor (sc_generate_text_banned); None or an empty list is the plain call.  ``prefix``: the prompt of every row,
+        or an (n, prefix_len) array with one prompt per row (sc_generate_text_rows; not with ``banned_seqs``)."""
         assert enc.is_cuda and enc.is_contiguous()
         n, s_enc, M = enc.shape
+        pre = _i32(prefix)
+        if pre.ndim == 2 and pre.shape[0] != n:
+            raise ValueError(f"a per-row prefix must be (n={n}, prefix_len), got {pre.shape}")
+        if pre.ndim == 2 and banned_seqs is not None and len(banned_seqs) > 0:
+            raise ValueError("banned_seqs take one prompt for all rows (sc_generate_text_banned)")
         o = self._gen_opts(beam_size, soft_max_seq_len, hard_max_seq_len, min_seq_len, unk_penalty, use_graph, len_penalty,
                            normalize_scores, no_repeat_ngram_size, source_len)
         max_len = self.lib.sc_text_max_len(self.handle, C.byref(o), s_enc)
@@ -326,9 +332,12 @@ class HipS2STModel(_Handle):
         lens = np.zeros(n, dtype=np.int32)
         scores = np.zeros(n, dtype=np.float32)
         hidden = torch.empty(n, max_len - 1, M, dtype=torch.float32, device=self.device) if want_hidden else None
-        pre = _i32(prefix)
         el = _i32(enc_lens)
         self._after_torch()
+        if pre.ndim == 2:
+            check(self.lib.sc_generate_text_rows(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(pre), pre.shape[1],
+                                                 _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden)), "sc_generate_text_rows")
+            return ids, lens, scores, hidden
         if banned_seqs is not None and len(banned_seqs) > 0:
             b_tok, b_off = _lib.banned_csr(banned_seqs)
             check(self.lib.sc_generate_text_banned(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(pre), len(pre),
@@ -450,6 +459,25 @@ class HipS2STModel(_Handle):
         if want_hidden:
             out["hidden"] = hidden
         return out
+
+    def identify_language(self, enc: torch.Tensor, enc_lens: Sequence[int], cand_ids: Sequence[int], prefix=None):
+        """Spoken-language identification (sc_identify_language): -> (lprob (n, L) float32, best (n,) int32).  lprob[b, j] is
+        the log-softmax over the whole vocabulary at the position behind ``prefix`` (default: ``</s>``), read at token
+        ``cand_ids[j]`` - the bits of score_text on ``prefix + [cand_ids[j]]``; best[b] indexes ``cand_ids``.  ``cand_ids``:
+        strictly ascending token ids, 1 .. 512 of them."""
+        assert enc.is_cuda and enc.is_contiguous()
+        n, s_enc, _ = enc.shape
+        cand = _i32(cand_ids).reshape(-1)
+        pre = _i32([self.cfg.eos_idx] if prefix is None else prefix).reshape(-1)
+        el = _i32(enc_lens).reshape(-1)
+        if len(el) != n:
+            raise ValueError("enc_lens must hold one entry per item")
+        lprob = np.zeros((n, len(cand)), dtype=np.float32)
+        best = np.zeros(n, dtype=np.int32)
+        self._after_torch()
+        check(self.lib.sc_identify_language(self.handle, _ptr(enc), n, s_enc, _ptr(el), _ptr(pre), len(pre), _ptr(cand), len(cand),
+                                            _ptr(lprob), _ptr(best)), "sc_identify_language")
+        return lprob, best
 
     def t2u_nar(self, dec_hidden: torch.Tensor, text_seqs: np.ndarray, text_lens: Sequence[int],
                 duration_factor: float = 1.0, cond: Optional[torch.Tensor] = None):
