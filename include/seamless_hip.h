@@ -367,6 +367,24 @@ int sc_score_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, con
                   const int32_t* h_tok_lens, int32_t s_text, float* h_tok_lprob, float* h_sum_lprob, int32_t* h_top1,
                   float* d_dec_hidden);
 
+/* sc_score_text with the decoder's cross-attention rows (additive, ABI 10): forced alignment - WHEN the words of a given text
+ * were spoken.  The reference's Transcriber hooks the last decoder layer's encoder-decoder attention while it generates
+ * (inference/transcriber.py:39-57); here the same quantity comes out of the one batched teacher-forced pass, for known tokens:
+ *   d_xattn [n][s_text-1][s_enc] (device)  d_xattn[b][p][j] = sum over the heads, in head order, of
+ *                                          softmax_j(q_h(b, p) . k_h(b, j) / 8) of the LAST decoder layer, for
+ *                                          p < tok_lens[b] - 1 and j < enc_lens[b]; 0 everywhere else (the call writes
+ *                                          those zeros: the buffer need not be cleared).  A live row sums to the head count.
+ * Everything sc_score_text documents holds unchanged, and h_tok_lprob / h_sum_lprob / h_top1 / d_dec_hidden carry the bits
+ * sc_score_text returns on the same arguments: the call adds ONE launch behind the last layer's query and key products
+ * (fp32 scores, soft-max and head sum; k_xattn.hip states the arithmetic order) and changes nothing else.  An item's rows do
+ * not depend, to the bit, on what else is in the batch or on the padded widths.  They agree with sc_generate_text_capture's
+ * rows for the same tokens to fp32 re-association, not to the bit (other products form the queries).  Runs on the handle's
+ * own stream (never the decode engine); works on forked handles.  SC_ERR_INVALID before any device work for a NULL d_xattn,
+ * for everything sc_score_text rejects, and for a decoder whose heads are not 64 wide or number more than 16. */
+int sc_score_text_capture(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens,
+                          const int32_t* h_tok_lens, int32_t s_text, float* h_tok_lprob, float* h_sum_lprob, int32_t* h_top1,
+                          float* d_dec_hidden, float* d_xattn);
+
 /* Spoken-language identification (additive, ABI 10): which __lang__ token the text decoder expects after the prompt - the
  * reference's "LID scores" (ggml/examples/unity/fairseq2.cpp:1208-1221: the decoder is fed the prompt's </s>, the log-softmax of
  * the next position is read at every language token; its target language `unk` takes their arg-max, :1227-1236).

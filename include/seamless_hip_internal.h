@@ -140,6 +140,15 @@ int sc_op_score_candidates(const float* d_x, const void* d_w_f16, const float* d
                            int32_t* d_best, int32_t M, int32_t N, int32_t K);
 int32_t sc_op_score_record_cols(int32_t N);
 int32_t sc_op_score_group_rows(int32_t N);
+/* The cross-attention rows of sc_score_text_capture by themselves (k_xattn.hip: xattn_rows_kernel; tests/test_xattn_rows_kernel_gpu.py):
+ * d_q [n * s1] query rows (stride ldq floats), d_k [n * s_enc] key rows (stride ldk), head h in columns h * 64 .. h * 64 + 63 of both;
+ * h_enc_lens [n] in 1..s_enc, h_tok_lens [n] in 2..s1 + 1 (whole sequence lengths: item b has tok_lens[b] - 1 live rows).
+ * d_xattn [n][s1][s_enc] = sum over the heads in head order of softmax_j(q_h . k_h / 8), 0 behind the live rows and keys
+ * (written by the kernel).  1..16 heads; q / k 16-byte aligned, ldq / ldk multiples of 4.
+ * sc_op_xattn_rows_tile(0): query rows one workgroup owns; (1): key rows staged in LDS at a time. */
+int sc_op_xattn_rows(const float* d_q, int64_t ldq, const float* d_k, int64_t ldk, int32_t n, int32_t s1, int32_t s_enc, int32_t heads,
+                     const int32_t* h_enc_lens, const int32_t* h_tok_lens, float* d_xattn);
+int32_t sc_op_xattn_rows_tile(int32_t which);
 /* Conv1d (stride 1) through the pre-split product kernel's implicit-convolution mode: x [nb][t][cin] is split into two
  * fp16 planes, output row (i, t) reads rows t + tap*dil - pad of item i (zeros outside the item), weights packed by
  * sc_op_pack_conv_weight.  d_row_valid (nullable, [nb*t] bytes on the device): rows with 0 are written as exact zeros.

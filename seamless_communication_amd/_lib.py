@@ -193,6 +193,9 @@ SIGNATURES = {
     "sc_generate_text_capture": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P, _P, _P]),
     "sc_decode_text": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P]),
     "sc_score_text": (C.c_int, [_P, _P, _i, _i, _P, _P, _P, _i, _P, _P, _P, _P]),
+    "sc_score_text_capture": (C.c_int, [_P, _P, _i, _i, _P, _P, _P, _i, _P, _P, _P, _P, _P]),
+    "sc_op_xattn_rows": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _i, _i, _i, _i, _P, _P, _P]),
+    "sc_op_xattn_rows_tile": (C.c_int32, [_i]),
     "sc_identify_language": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P, _i, _P, _P]),
     "sc_generate_text_rows": (C.c_int, [_P, _P, _i, _i, _P, _P, _P, _i, _P, _P, _P, _P]),
     "sc_engine_create": (_P, [_P, C.POINTER(sc_engine_opts)]),

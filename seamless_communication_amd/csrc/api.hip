@@ -365,6 +365,44 @@ int sc_score_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, con
     SC_API_END
 }
 
+int sc_score_text_capture(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens,
+                          const int32_t* h_tok_lens, int32_t s_text, float* h_tok_lprob, float* h_sum_lprob, int32_t* h_top1,
+                          float* d_dec_hidden, float* d_xattn) {
+    SC_API_BEGIN
+    SC_CHECK(m && d_enc && h_enc_lens && h_tokens && h_tok_lens && h_tok_lprob, "sc_score_text_capture: null argument");
+    SC_CHECK(d_xattn, "sc_score_text_capture: null d_xattn (sc_score_text is the call without the attention rows)");
+    SC_HIP(hipSetDevice(m->m.device));
+    run_score_text(m->m, d_enc, n, s_enc, h_enc_lens, h_tokens, h_tok_lens, s_text, h_tok_lprob, h_sum_lprob, h_top1, d_dec_hidden, d_xattn);
+    SC_API_END
+}
+
+int32_t sc_op_xattn_rows_tile(int32_t which) { return which == 0 ? XROWS_QT : which == 1 ? XROWS_KC : 0; }
+
+int sc_op_xattn_rows(const float* d_q, int64_t ldq, const float* d_k, int64_t ldk, int32_t n, int32_t s1, int32_t s_enc, int32_t heads,
+                     const int32_t* h_enc_lens, const int32_t* h_tok_lens, float* d_xattn) {
+    SC_API_BEGIN
+    SC_CHECK(d_q && d_k && h_enc_lens && h_tok_lens && d_xattn, "sc_op_xattn_rows: null argument");
+    SC_CHECK(n > 0 && s1 > 0 && s_enc > 0, "sc_op_xattn_rows: n=%d s1=%d s_enc=%d", n, s1, s_enc);
+    check_xattn_rows_geometry(heads, heads * 64, "sc_op_xattn_rows");
+    for (int b = 0; b < n; ++b) {
+        SC_CHECK(h_tok_lens[b] >= 2 && h_tok_lens[b] <= s1 + 1, "sc_op_xattn_rows: tok_lens[%d]=%d outside [2, %d]", b, h_tok_lens[b], s1 + 1);
+        SC_CHECK(h_enc_lens[b] > 0 && h_enc_lens[b] <= s_enc, "sc_op_xattn_rows: enc_lens[%d]=%d out of range", b, h_enc_lens[b]);
+    }
+    int* d_lens = nullptr;
+    SC_HIP(hipMalloc(&d_lens, (size_t)2 * n * sizeof(int)));
+    std::unique_ptr<int, void (*)(int*)> guard(d_lens, [](int* p) { (void)hipFree(p); });
+    SC_HIP(hipMemcpy(d_lens, h_enc_lens, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    SC_HIP(hipMemcpy(d_lens + n, h_tok_lens, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+    XattnRowsArgs a;
+    a.q = d_q, a.k = d_k, a.ldq = ldq, a.ldk = ldk;
+    a.enc_lens = d_lens, a.tok_lens = d_lens + n;
+    a.xattn = d_xattn;
+    a.n = n, a.S1 = s1, a.s_enc = s_enc, a.heads = heads;
+    launch_xattn_rows(a, nullptr);
+    SC_HIP(hipStreamSynchronize(nullptr));
+    SC_API_END
+}
+
 int sc_identify_language(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix,
                          int32_t prefix_len, const int32_t* h_cand, int32_t n_cand, float* h_lprob, int32_t* h_best) {
     SC_API_BEGIN

@@ -835,6 +835,24 @@ struct XattnCapArgs {
 };
 void launch_xattn_capture(const XattnCapArgs& a, hipStream_t s);
 
+// The same rows for a whole teacher-forced pass (k_xattn.hip; sc_score_text_capture): xattn[b][p][j] = sum over the heads, in
+// head order, of softmax_j(q_h(b, p) . k_h(b, j) / 8) for p < tok_lens[b] - 1 and j < enc_lens[b], 0 everywhere else (the
+// kernel writes the zeros: the output needs no memset).  One workgroup per XROWS_QT query rows of one item, keys staged
+// XROWS_KC rows at a time.  A row's bits depend on its own item only.  Head width 64, at most XCAP_MAX_HEADS heads.
+constexpr int XROWS_QT = 16, XROWS_KC = 64;
+struct XattnRowsArgs {
+    const float* q = nullptr;  // [n * S1] query rows, stride ldq, head h at column h * 64
+    const float* k = nullptr;  // [n * s_enc] key rows, stride ldk, head h at column h * 64
+    int64_t ldq = 0, ldk = 0;
+    const int* enc_lens = nullptr;  // [n] on the device
+    const int* tok_lens = nullptr;  // [n] on the device: whole sequence lengths, tok_lens[b] - 1 live rows
+    float* xattn = nullptr;         // [n][S1][s_enc]
+    int n = 0, S1 = 0, s_enc = 0, heads = 0;
+};
+void launch_xattn_rows(const XattnRowsArgs& a, hipStream_t s);
+// SC_CHECK that `heads` heads of width 64 make up model_dim and fit XCAP_MAX_HEADS; `who` opens the message
+void check_xattn_rows_geometry(int heads, int model_dim, const char* who);
+
 // ---- UnitY2 forced aligner (k_align.hip; reference models/aligner/model.py) --------------------------------------
 // out[row] = table[ids[row]] (fp16 table, no scale, no positions)
 void launch_align_embed(const int* ids, int rows, const __half* table, int C, float* out, hipStream_t s);

@@ -377,7 +377,8 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
 void run_identify_language(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix,
                            int prefix_len, const int32_t* h_cand, int n_cand, float* h_lprob, int32_t* h_best);
 void run_score_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens,
-                    const int32_t* h_tok_lens, int s_text, float* h_tok_lprob, float* h_sum_lprob, int32_t* h_top1, float* d_dec_hidden);
+                    const int32_t* h_tok_lens, int s_text, float* h_tok_lprob, float* h_sum_lprob, int32_t* h_top1, float* d_dec_hidden,
+                    float* d_xattn = nullptr);
 // d_cond: [n][film_cond_dim] on the device for a FiLM model, null otherwise (a mismatch is an error)
 void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const int32_t* h_text_lens,
                  const int32_t* h_text_seqs, float duration_factor, int32_t* h_unit_lens, int32_t* out_su,

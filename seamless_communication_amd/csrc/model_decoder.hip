@@ -1110,8 +1110,10 @@ void setup_session(Model& m, DecodeSession& S, int n, int max_len, int s_enc, bo
 // re-association (tests/test_stages_gpu.py: test_generated_hidden_equals_teacher_forced_pass, 2e-4).
 // row_independent (sc_score_text): every product is the tiled one whatever the row count, so that an item's rows carry the same
 // bits alone and in any batch; otherwise up to 64 rows take the skinny products (another summation order, linear()).
+// d_xattn (sc_score_text_capture; with h_seq_lens [n], whole sequence lengths): one more launch in the LAST layer, behind its
+// cross_q product and project_cross_kv - the head-summed attention rows of every item (launch_xattn_rows).  Nothing else changes.
 void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens, int s_text,
-                             float* d_hidden, bool row_independent = false) {
+                             float* d_hidden, bool row_independent = false, float* d_xattn = nullptr, const int32_t* h_seq_lens = nullptr) {
     const sc_config& cfg = m.cfg;
     const int M = cfg.model_dim, rows = n * s_text, erows = n * s_enc;
     SC_CHECK(s_text <= cfg.text_max_seq_len, "sc_decode_text: %d tokens exceed text_max_seq_len=%d", s_text, cfg.text_max_seq_len);
@@ -1119,9 +1121,10 @@ void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, con
         SC_CHECK(h_tokens[i] >= 0 && h_tokens[i] < cfg.text_vocab_size, "sc_decode_text: token %d outside the vocabulary", h_tokens[i]);
     for (int b = 0; b < n; ++b) SC_CHECK(h_enc_lens[b] > 0 && h_enc_lens[b] <= s_enc, "sc_decode_text: enc_lens[%d]=%d out of range", b, h_enc_lens[b]);
     prof::set_tag("dec");
-    Buf<int> d_tok(m.pp(), rows), d_elens(m.pp(), n);
+    Buf<int> d_tok(m.pp(), rows), d_elens(m.pp(), n), d_slens(m.pp(), d_xattn ? n : 0);
     SC_HIP(hipMemcpyAsync(d_tok.get(), h_tokens, (size_t)rows * 4, hipMemcpyHostToDevice, m.stream));
     SC_HIP(hipMemcpyAsync(d_elens.get(), h_enc_lens, (size_t)n * 4, hipMemcpyHostToDevice, m.stream));
+    if (d_xattn) SC_HIP(hipMemcpyAsync(d_slens.get(), h_seq_lens, (size_t)n * 4, hipMemcpyHostToDevice, m.stream));
     const int wideN = std::max(3 * M, cfg.dec_ffn_dim);
     Buf<float> h(m.pp(), (size_t)rows * M), wide(m.pp(), (size_t)rows * wideN), att(m.pp(), (size_t)rows * M),
         ckv(m.pp(), (size_t)erows * 2 * M);
@@ -1148,6 +1151,18 @@ void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, con
         layernorm(m, x, l.cross_ln, h, rows);
         linear(m, h, M, l.cross_q, nullptr, 0, wide, M, rows, ACT_NONE, 1.f, row_independent);
         project_cross_kv(m, d_enc, l.cross_kv, ckv, erows);
+        if (d_xattn && &l == &m.dec.back()) {
+            XattnRowsArgs xr;
+            xr.q = wide;
+            xr.k = ckv;
+            xr.ldq = M;
+            xr.ldk = 2 * M;
+            xr.enc_lens = d_elens;
+            xr.tok_lens = d_slens;
+            xr.xattn = d_xattn;
+            xr.n = n, xr.S1 = s_text, xr.s_enc = s_enc, xr.heads = cfg.num_heads;
+            launch_xattn_rows(xr, m.stream);
+        }
         AttnArgs c;
         c.q = wide;
         c.k = ckv;
@@ -1177,8 +1192,11 @@ void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, con
 // tokens[b][p + 1] - packed back to back as the T2U and vocoder passes pack theirs.  The [rows][V] logits are never formed:
 // launch_gemm_presplit_score keeps per-row statistics in the product's epilogue.  The reference's evaluation loss runs the same
 // three steps through PyTorch (cli/m4t/finetune/trainer.py:100-125, :155-188).  Own stream, never the decode engine.
+// d_xattn (sc_score_text_capture): [n][s_text - 1][s_enc], the last layer's head-summed encoder-decoder attention of the same
+// pass; every other output carries the bits of the call without it.
 void run_score_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens,
-                    const int32_t* h_tok_lens, int s_text, float* h_tok_lprob, float* h_sum_lprob, int32_t* h_top1, float* d_dec_hidden) {
+                    const int32_t* h_tok_lens, int s_text, float* h_tok_lprob, float* h_sum_lprob, int32_t* h_top1, float* d_dec_hidden,
+                    float* d_xattn) {
     const sc_config& cfg = m.cfg;
     const int M = cfg.model_dim, V = cfg.text_vocab_size, S1 = s_text - 1;
     // every argument error before any device work
@@ -1187,6 +1205,7 @@ void run_score_text(Model& m, const float* d_enc, int n, int s_enc, const int32_
     SC_CHECK(s_text >= 2, "sc_score_text: s_text=%d (a sequence holds a prompt token and a target at the least)", s_text);
     SC_CHECK(s_text <= cfg.text_max_seq_len, "sc_score_text: %d tokens exceed text_max_seq_len=%d", s_text, cfg.text_max_seq_len);
     SC_CHECK(M % 32 == 0, "sc_score_text: model_dim=%d is not a multiple of 32", M);
+    if (d_xattn) check_xattn_rows_geometry(cfg.num_heads, M, "sc_score_text_capture");
     int R = 0;
     for (int b = 0; b < n; ++b) {
         SC_CHECK(h_tok_lens[b] >= 2 && h_tok_lens[b] <= s_text, "sc_score_text: tok_lens[%d]=%d outside [2, %d]", b, h_tok_lens[b], s_text);
@@ -1206,7 +1225,7 @@ void run_score_text(Model& m, const float* d_enc, int n, int s_enc, const int32_
     Buf<float> own_hidden(m.pp(), d_dec_hidden ? 0 : (size_t)n * S1 * M);
     float* hidden = d_dec_hidden ? d_dec_hidden : own_hidden.get();
     // row-independent products: a sequence's scores must not depend on what it is batched with (n-best lists are compared)
-    run_decode_text_batched(m, d_enc, n, s_enc, h_enc_lens, in_tok.data(), S1, hidden, /*row_independent=*/true);
+    run_decode_text_batched(m, d_enc, n, s_enc, h_enc_lens, in_tok.data(), S1, hidden, /*row_independent=*/true, d_xattn, h_tok_lens);
     prof::set_tag("score");
     const int group = std::min(gemm_score_group_rows(V), (R + 255) / 256 * 256);
     Buf<int> d_idx(m.pp(), R), d_tgt(m.pp(), R), d_top1(m.pp(), R);

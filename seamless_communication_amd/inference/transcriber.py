@@ -7,9 +7,14 @@ decoder layer's encoder-decoder attention and runs a beam search of width 1; her
 libseamless_hip records the same attention rows on the device (sc_generate_text_capture), and the timestamp and word
 bookkeeping below runs on the host in numpy.
 
+Beyond the reference: ``align`` / ``align_batch`` time the words of a text that is already
+known (forced alignment; ragged batches), and ``transcribe_beam`` times the winning hypothesis of a beam search.  Both
+take the same attention rows from ONE batched teacher-forced decoder pass over the known tokens
+(sc_score_text_capture) instead of the step loop, and share the host bookkeeping with ``transcribe``.
+
 Not available (``NotImplementedError``): ``denoise=True`` (the Demucs denoiser is not part of
 this project), inputs longer than ``chunk_size_sec`` (the reference splits them with Silero VAD, which cannot be
-obtained offline) and ``beam_size > 1``.
+obtained offline) and ``transcribe(beam_size > 1)`` (``transcribe_beam`` is the call for that).
 """
 from __future__ import annotations
 
@@ -25,6 +30,7 @@ from ..runtime import HipS2STModel
 from ..tokenizer import NllbTextTokenizer
 from .. import cards as _cards
 from ..lid import identify_encoded
+from ..scoring import pad_sequences, target_sequence
 from .translator import _ARCHS, _load_state_dict, _resolve_card
 
 # generator options the reference passes to fairseq2's BeamSearchSeq2SeqGenerator (transcriber.py run_inference); the
@@ -112,6 +118,9 @@ class Transcriber:
                                            card.get("default_lang", "eng"), card.get("tokenizer_path"))
         self.model = HipS2STModel(self.cfg, unity_sd, None, device=dev.index or 0)
         self.use_graph = True  # replay the decoder step from a captured hipGraph (not part of the reference API)
+        # what the last align / align_batch / transcribe_beam call took from the device, per item: {"ids": the whole sequence,
+        # "xattn": (len - 1, enc_len) float32, "tok_lprob": (len - 1,) float32}; None for an item without text
+        self.last_capture: List[Optional[Dict[str, Any]]] = []
 
     @staticmethod
     def generate_lis(arr: List[Tuple[int, int]]) -> Tuple[int, List[Tuple[int, int]]]:
@@ -231,17 +240,7 @@ class Transcriber:
         ``src_lang=None``: the language is identified first; the result's ``lang`` names it and ``lid`` holds the scores."""
         if denoise:
             raise NotImplementedError("denoise=True: the Demucs denoiser is not part of this project")
-        if isinstance(audio, (str, Path)):
-            from ..evaluate import load_audio  # evaluate imports this package: not at module level
-
-            data, rate = load_audio(Path(audio), all_channels=True)
-            wav = torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32))
-        else:
-            wav, rate = audio, sample_rate
-            if wav.dim() != 2:
-                raise ValueError("the audio tensor must be (T, C)")
-        if int(rate) != sample_rate:
-            raise AssertionError(f"decoded sample rate {rate} != sample_rate {sample_rate}")
+        wav = _waveform(audio, sample_rate)
         length_seconds = wav.size(0) / sample_rate
         if length_seconds > chunk_size_sec:
             raise NotImplementedError(f"input of {length_seconds:.2f} s > chunk_size_sec={chunk_size_sec}: the reference segments "
@@ -256,6 +255,155 @@ class Transcriber:
         times = self._extract_timestamps(rows, length_seconds, filter_width)
         pieces = [self.tokenizer.index_to_token(t) for t in token_ids]
         return Transcription(self._collect_word_level_stats(pieces=pieces, token_timestamps=times, step_scores=step_scores), lang, lid)
+
+    # ---- known tokens: one batched teacher-forced pass with the attention rows (sc_score_text_capture) -------------------
+    def _sequence(self, text: Union[str, Sequence[int]], lang: str) -> Optional[List[int]]:
+        """``</s> __lang__ w1 ... </s>`` as scoring.target_sequence builds it (ValueError for an unknown language, a token
+        outside the vocabulary or more than text_max_seq_len tokens); None for a text without a token."""
+        self.tokenizer.lang_token_idx(lang)
+        if isinstance(text, str):
+            if not self.tokenizer.encode_pieces(text):
+                return None
+        else:
+            text = [int(t) for t in text]
+            if not text:
+                return None
+        return target_sequence(self.tokenizer, lang, text, self.cfg.text_max_seq_len)
+
+    def _encode(self, wavs: List[Tensor], sample_rate: int, padded_encoder: bool = False):
+        """One fbank call for all items (an item's frames do not depend on the batch), then the speech encoder -> (enc, enc_lens,
+        frames).  The encoder runs item by item on each item's own frames unless ``padded_encoder``: like the reference's, its
+        adaptor applies no padding mask in front of its strided convolutions, so the output of a padded item depends on its batch
+        (DESIGN section 4), and up to 64 rows take other products than more.  ``padded_encoder``: one call on the padded batch."""
+        model = self.model
+        n = len(wavs)
+        ns = [int(w.shape[0]) for w in wavs]
+        batch = torch.zeros(n, max(ns), dtype=torch.float32)
+        for i, w in enumerate(wavs):
+            batch[i, : ns[i]] = w[:, 0].to(torch.float32)
+        together = padded_encoder and n > 1
+        fb, frames = model.fbank(batch.to(self.device).contiguous(), ns, standardize=True, pad_to_multiple=2 if together else 1,
+                                 sample_rate=int(sample_rate))
+        if together or n == 1:
+            enc, enc_lens = model.encode_speech(fb, frames)
+            return enc, enc_lens, frames
+        parts = [model.encode_speech(fb[i : i + 1, : int(frames[i])].contiguous(), frames[i : i + 1]) for i in range(n)]
+        enc = torch.zeros(n, max(e.shape[1] for e, _ in parts), parts[0][0].shape[2], dtype=torch.float32, device=parts[0][0].device)
+        for i, (e, _) in enumerate(parts):
+            enc[i, : e.shape[1]] = e[0]
+        return enc, np.concatenate([l for _, l in parts]).astype(np.int32), frames
+
+    def _timed(self, seqs: List[Optional[List[int]]], enc: Tensor, enc_lens: np.ndarray, seconds: List[float], filter_width: int,
+               langs: List[str], lids: List[Optional[Any]]) -> List[Transcription]:
+        """one sc_score_text_capture call over the items that have text, then the host bookkeeping of ``transcribe``"""
+        self.last_capture = [None] * len(seqs)
+        out = [Transcription([], langs[i], lids[i]) for i in range(len(seqs))]
+        pick = [i for i, s in enumerate(seqs) if s is not None]
+        if not pick:
+            return out
+        tokens, tok_lens = pad_sequences([seqs[i] for i in pick], self.tokenizer.vocab_info.pad_idx)
+        e = enc if len(pick) == len(seqs) else enc[pick].contiguous()
+        res = self.model.score_text(e, [int(enc_lens[i]) for i in pick], tokens, tok_lens, want_xattn=True)
+        xattn = res["xattn"].cpu().numpy()
+        for b, i in enumerate(pick):
+            L, el = int(tok_lens[b]), int(enc_lens[i])
+            rows_x, lp = xattn[b, : L - 1, :el], res["tok_lprob"][b, : L - 1]
+            self.last_capture[i] = {"ids": list(seqs[i]), "xattn": rows_x, "tok_lprob": lp}
+            token_ids, scores, rows = restate_hook_rows(tokens[b], L, 2, rows_x, lp)
+            times = self._extract_timestamps(rows, seconds[i], filter_width)
+            pieces = [self.tokenizer.index_to_token(t) for t in token_ids]
+            out[i] = Transcription(self._collect_word_level_stats(pieces=pieces, token_timestamps=times, step_scores=scores),
+                                   langs[i], lids[i])
+        return out
+
+    @torch.inference_mode()
+    def align_batch(
+        self,
+        audios: Sequence[Union[str, Tensor]],
+        texts: Sequence[Union[str, Sequence[int]]],
+        src_langs: Union[None, str, Sequence[Optional[str]]],
+        filter_width: int = 3,
+        sample_rate: int = 16000,
+        padded_encoder: bool = False,
+    ) -> List[Transcription]:
+        """Forced alignment of a ragged batch: when the words of ``texts[i]`` were spoken in ``audios[i]``.  ``texts[i]``: a
+        string, or its token ids without prompt and ``</s>``; ``src_langs``: one language for all items or one per item
+        (None: identified first, as ``transcribe`` does).  One fbank call and one decoder call (sc_score_text_capture) for the
+        batch.  Item i equals ``align`` of item i alone - times and texts exactly, probabilities to the bit - because the speech
+        encoder, whose output for a padded item depends on its batch, runs item by item; ``padded_encoder=True`` runs it once
+        on the padded batch instead (faster; results are then those of ``Translator.predict`` on such a batch, close to but not
+        equal to the item's own).  A word's ``prob`` is the mean of exp(log p(piece | the pieces before it)) - the
+        raw log-probability, no step rules.  An item without text gives an empty ``Transcription``.  No ``chunk_size_sec``
+        limit (nothing is generated): the limits are the encoder's and ``text_max_seq_len``."""
+        audios, texts = list(audios), list(texts)
+        n = len(audios)
+        if n == 0:
+            raise ValueError("no audio to align")
+        if len(texts) != n:
+            raise ValueError(f"{len(texts)} texts for {n} audios")
+        langs = [src_langs] * n if src_langs is None or isinstance(src_langs, str) else list(src_langs)
+        if len(langs) != n:
+            raise ValueError(f"{len(langs)} languages for {n} audios (one for all, or one per item)")
+        # every argument error before any device work
+        seqs = [self._sequence(t, l) if l is not None else None for t, l in zip(texts, langs)]
+        wavs = [_waveform(a, sample_rate) for a in audios]
+        seconds = [w.size(0) / sample_rate for w in wavs]
+        enc, enc_lens, _ = self._encode(wavs, sample_rate, padded_encoder)
+        lids: List[Optional[Any]] = [None] * n
+        if any(l is None for l in langs):
+            found = identify_encoded(self.model, self.tokenizer, enc, enc_lens)
+            for i in range(n):
+                if langs[i] is None:
+                    lids[i], langs[i] = found[i], found[i].lang
+                    seqs[i] = self._sequence(texts[i], langs[i])
+        return self._timed(seqs, enc, enc_lens, seconds, filter_width, langs, lids)
+
+    def align(self, audio: Union[str, Tensor], text: Union[str, Sequence[int]], src_lang: Optional[str], filter_width: int = 3,
+              sample_rate: int = 16000) -> Transcription:
+        """``align_batch`` of one item: the words of ``text`` with their start times in ``audio`` and their probabilities."""
+        return self.align_batch([audio], [text], src_lang, filter_width=filter_width, sample_rate=sample_rate)[0]
+
+    @torch.inference_mode()
+    def transcribe_beam(self, audio: Union[str, Tensor], src_lang: Optional[str], beam_size: int = 5, filter_width: int = 3,
+                        sample_rate: int = 16000, **sequence_generator_options: Dict) -> Transcription:
+        """``transcribe`` with a beam search: sc_generate_text at ``beam_size`` with ``transcribe``'s generator options and
+        defaults, then the attention rows of the WINNING hypothesis from one teacher-forced pass.  (The reference's hook
+        sums the rows over every live beam)  A word's ``prob`` is the raw log-probability's, as
+        in ``align``."""
+        model = self.model
+        wav = _waveform(audio, sample_rate)
+        opts = dict(sequence_generator_options)
+        enc, enc_lens, frames = self._encode([wav], sample_rate)
+        lid = None
+        if src_lang is None:
+            lid = identify_encoded(model, self.tokenizer, enc, enc_lens)[0]
+            src_lang = lid.lang
+        prefix = self.tokenizer.target_prefix(src_lang)
+        soft, hard, unk = self._gen_limits(opts, len(prefix), int(frames[0]))
+        o = {**GENERATOR_DEFAULTS, **opts}
+        ids, lens, _, _ = model.generate_text(enc, enc_lens.tolist(), prefix, beam_size=int(beam_size), soft_max_seq_len=soft,
+                                              hard_max_seq_len=hard, unk_penalty=unk, use_graph=self.use_graph, want_hidden=False,
+                                              len_penalty=float(o["len_penalty"]), normalize_scores=bool(o["normalize_scores"]),
+                                              source_len=int(frames[0]))
+        seq = [int(t) for t in ids[0, : int(lens[0])]]
+        seqs = [seq if len(seq) > len(prefix) + 1 else None]  # EOS first: no token, no timestamp
+        return self._timed(seqs, enc, enc_lens, [wav.size(0) / sample_rate], filter_width, [src_lang], [lid])[0]
+
+
+def _waveform(audio: Union[str, Path, Tensor], sample_rate: int) -> Tensor:
+    """a file path or a (T, C) tensor at ``sample_rate`` -> the (T, C) waveform"""
+    if isinstance(audio, (str, Path)):
+        from ..evaluate import load_audio  # evaluate imports this package: not at module level
+
+        data, rate = load_audio(Path(audio), all_channels=True)
+        wav = torch.from_numpy(np.ascontiguousarray(data, dtype=np.float32))
+    else:
+        wav, rate = audio, sample_rate
+        if wav.dim() != 2:
+            raise ValueError("the audio tensor must be (T, C)")
+    if int(rate) != sample_rate:
+        raise AssertionError(f"decoded sample rate {rate} != sample_rate {sample_rate}")
+    return wav
 
 
 def restate_hook_rows(ids: np.ndarray, length: int, prefix_len: int, xattn: np.ndarray,

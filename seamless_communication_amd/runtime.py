@@ -427,12 +427,15 @@ class HipS2STModel(_Handle):
         return hidden
 
     def score_text(self, enc: torch.Tensor, enc_lens: Sequence[int], tokens: np.ndarray, tok_lens: Sequence[int],
-                   want_sum: bool = False, want_top1: bool = False, want_hidden: bool = False):
+                   want_sum: bool = False, want_top1: bool = False, want_hidden: bool = False, want_xattn: bool = False):
         """Teacher-forced scoring (sc_score_text): tokens (n, s_text) whole sequences ``</s> __lang__ ... </s>`` (pad filled),
         tok_lens (n,) -> dict with ``tok_lprob`` (n, s_text - 1) float32: log-probability of tokens[b, p + 1] given
         tokens[b, :p + 1]; ``sum_lprob`` (the log-probabilities at p summed over the vocabulary) and ``top1`` (the arg-max
         token at p) on request; ``hidden`` (n, s_text - 1, M) on the device on request.  Positions behind tok_lens[b] - 1
-        hold 0 (top1: -1).  No (rows, vocabulary) buffer is formed."""
+        hold 0 (top1: -1).  No (rows, vocabulary) buffer is formed.  ``want_xattn`` (sc_score_text_capture): ``xattn``
+        (n, s_text - 1, s_enc) float32 on the device, the last decoder layer's encoder-decoder attention probabilities of the
+        query fed at position p summed over the heads, 0 behind tok_lens[b] - 1 and enc_lens[b]; the other results keep
+        their bits."""
         assert enc.is_cuda and enc.is_contiguous()
         n, s_enc, M = enc.shape
         tok = _i32(tokens)
@@ -448,9 +451,14 @@ class HipS2STModel(_Handle):
         sum_lprob = np.zeros((n, s1), dtype=np.float32) if want_sum else None
         top1 = np.full((n, s1), -1, dtype=np.int32) if want_top1 else None
         hidden = torch.empty(n, s1, M, dtype=torch.float32, device=self.device) if want_hidden else None
+        xattn = torch.empty(n, s1, s_enc, dtype=torch.float32, device=self.device) if want_xattn else None
         self._after_torch()
-        check(self.lib.sc_score_text(self.handle, _ptr(enc), n, s_enc, _ptr(el), _ptr(tok), _ptr(tl), s_text, _ptr(lprob),
-                                     _ptr(sum_lprob), _ptr(top1), _ptr(hidden)), "sc_score_text")
+        if want_xattn:
+            check(self.lib.sc_score_text_capture(self.handle, _ptr(enc), n, s_enc, _ptr(el), _ptr(tok), _ptr(tl), s_text, _ptr(lprob),
+                                                 _ptr(sum_lprob), _ptr(top1), _ptr(hidden), _ptr(xattn)), "sc_score_text_capture")
+        else:
+            check(self.lib.sc_score_text(self.handle, _ptr(enc), n, s_enc, _ptr(el), _ptr(tok), _ptr(tl), s_text, _ptr(lprob),
+                                         _ptr(sum_lprob), _ptr(top1), _ptr(hidden)), "sc_score_text")
         out = {"tok_lprob": lprob}
         if want_sum:
             out["sum_lprob"] = sum_lprob
@@ -458,6 +466,8 @@ class HipS2STModel(_Handle):
             out["top1"] = top1
         if want_hidden:
             out["hidden"] = hidden
+        if want_xattn:
+            out["xattn"] = xattn
         return out
 
     def identify_language(self, enc: torch.Tensor, enc_lens: Sequence[int], cand_ids: Sequence[int], prefix=None):
