@@ -698,6 +698,41 @@ int64_t sc_resample_len(int64_t num_samples, int32_t orig_freq, int32_t new_freq
 int sc_resample(const float* d_in, int32_t n, int64_t in_stride, const int64_t* h_in_len, int32_t orig_freq, int32_t new_freq,
                 const sc_resample_opts* opts, float* d_out, int64_t out_stride, int64_t* h_out_len);
 
+/* ---- Speech detection (added within ABI v10, purely additive): a speech probability per window of `window` samples, the track
+ * the reference takes from Silero VAD (segment/silero_vad.py get_speech_probs) in front of its segmentation of long input.  NOT a
+ * learned model: an energy detector whose threshold adapts to the row (DESIGN.md section 7m has the definition; its constants are
+ * this project's choice and their quality on real speech has not been measured).  For a row x[0..L), n_w = ceil(L / window):
+ *   db_w = 10 log10(max(e_w, 1e-10)), e_w the variance of window w zero-padded to `window` (two passes in fp32, fixed order);
+ *          NaN for a window that holds a non-finite sample (or whose fp32 energy is not finite)
+ *   F_q, P = the order statistics floor(floor_quantile (k-1)) and floor(peak_quantile (k-1)) of the k finite db_w (exact, no
+ *          interpolation), F = min(F_q, noise_ceiling_db), c = F + max(min_margin_db, range_fraction (P - F))
+ *   s_w  = the largest finite db within `hangover` windows of w;  p_w = 1 / (1 + exp(-(s_w - c) / slope_db)), NaN where db_w is
+ * No handle: it runs on the CURRENT device, on the default stream, and returns when the output is complete.  A row's bits do not
+ * depend on its companions or on the strides.
+ *   d_wav   [n][wav_stride] fp32, row i valid up to h_num_samples[i]
+ *   d_probs [n][probs_stride] fp32: n_w probabilities, zeros behind them
+ *   d_db    NULL, or [n][probs_stride] fp32: db_w, zeros behind them
+ *   h_stats NULL, or [n][4] fp32 on the host: F, P, c, k (all NaN but k = 0 for a row without a finite window)
+ *   opts    NULL or all-zero: the defaults below.  Otherwise abi_version must be SC_ABI_VERSION and a zero field stands for its
+ *           default; hangover -1 is no hangover.  The quantiles equal to their default rounded to fp32 stand for it in double.
+ * SC_ERR_INVALID, before any device work: a null pointer, window outside 32..8192, n outside 1..65535, a negative length, a length
+ * above wav_stride, more than 2^20 windows in a row, probs_stride below the most windows of a row, a quantile outside [0, 1],
+ * slope_db <= 0, min_margin_db < 0, range_fraction < 0, hangover outside -1..8, a field that is not a number.
+ * sc_vad_windows: ceil(num_samples / window) (host only; negative on a negative length or window <= 0). */
+typedef struct sc_vad_opts {
+    int32_t abi_version;
+    int32_t hangover;       /* windows each side, 0..8, default 1; -1: none */
+    float floor_quantile;   /* 0.10 */
+    float peak_quantile;    /* 0.95 */
+    float noise_ceiling_db; /* -45 */
+    float min_margin_db;    /* 6 */
+    float range_fraction;   /* 0.35 */
+    float slope_db;         /* 1.5 */
+} sc_vad_opts;
+int64_t sc_vad_windows(int64_t num_samples, int32_t window);
+int sc_vad_probs(const float* d_wav, int32_t n, int64_t wav_stride, const int64_t* h_num_samples, int32_t window, const sc_vad_opts* opts,
+                 float* d_probs, int64_t probs_stride, float* d_db, float* h_stats);
+
 /* The kernel-level test hooks (sc_op_*) and the dispatch introspection the parity tests drive are exported too but are NOT part
  * of the drop-in boundary: include/seamless_hip_internal.h. */
 

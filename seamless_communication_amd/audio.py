@@ -1,4 +1,5 @@
-"""Audio resampling on the device: ``torchaudio.functional.resample``'s windowed-sinc polyphase algorithm, restated.
+"""Audio resampling on the device: ``torchaudio.functional.resample``'s windowed-sinc polyphase algorithm, restated - and, at the
+end of the file, speech detection on the device (``speech_probs``: the probability track the speech segmenter splits long input by).
 
 The reference resamples to 16 kHz with torchaudio in front of every model that opens a file (cli/m4t/predict/predict.py:226-231,
 cli/expressivity/predict/predict.py:115, models/aligner/alignment_extractor.py:63-71).  torchaudio is not a dependency here; the
@@ -57,3 +58,55 @@ def resample_ragged(waves: Sequence[Tensor], orig_freq: int, new_freq: int, lowp
         rows[i, : lens[i]] = w
     out, out_lens = _rt.resample_rows(rows, lens, int(orig_freq), int(new_freq), opts)
     return [out[i, : int(out_lens[i])].to(waves[i].dtype) for i in range(len(waves))]
+
+
+# ---- speech detection (sc_vad_probs) ---------------------------------------------------------------------
+
+def _first_bad_window(wave: Tensor, window: int) -> int:
+    bad = (~torch.isfinite(wave)).nonzero()
+    return int(bad[0, 0]) // window if bad.numel() else -1
+
+
+def speech_probs(waveform: Tensor, window_size_samples: int = 1536, **opts) -> Tensor:
+    """A speech probability per window of ``window_size_samples`` samples: ``waveform`` 1-D or (T, C) (channel 0 is used, as the
+    Transcriber does) on a HIP device -> (ceil(T / window_size_samples),) float32 on that device.  The track has the shape and the
+    meaning of the one the reference takes from Silero VAD (``SileroVADSegmenter.get_speech_probs``) but comes from an energy
+    detector, not from a learned model: a window is speech when its level in dB stands above a threshold between the row's quiet
+    and loud windows.  ``opts``: ``hangover`` (1), ``floor_quantile`` (0.10), ``peak_quantile`` (0.95),
+    ``noise_ceiling_db`` (-45), ``min_margin_db`` (6), ``range_fraction`` (0.35), ``slope_db`` (1.5); a zero stands for the
+    default, ``hangover=-1`` for none.  These constants are this project's choice; their quality on real speech has not been
+    measured.  ``ValueError`` for a sample that is not finite; it names the first window that holds one."""
+    if isinstance(waveform, Tensor) and waveform.dim() == 2:
+        waveform = waveform[:, 0]
+    return speech_probs_ragged([waveform], window_size_samples, **opts)[0]
+
+
+def speech_probs_ragged(waves: Sequence[Tensor], window_size_samples: int = 1536, **opts) -> List[Tensor]:
+    """1-D waveforms of different lengths in ONE device call; per item what :func:`speech_probs` returns for it alone, to the bit."""
+    waves = list(waves)
+    for w in waves:
+        _check(w, "every waveform")
+        if w.dim() != 1:
+            raise ValueError(f"speech_probs_ragged takes 1-D waveforms, got shape {tuple(w.shape)}")
+    if not waves:
+        return []
+    if len({w.device for w in waves}) != 1:
+        raise ValueError("the waveforms must be on one device")
+    o = _rt.vad_opts(**opts)
+    window = int(window_size_samples)
+    lens = [int(w.shape[0]) for w in waves]
+    if len(waves) == 1:
+        rows = waves[0].to(torch.float32).contiguous().unsqueeze(0)
+    else:
+        rows = torch.zeros(len(waves), max(max(lens), 1), dtype=torch.float32, device=waves[0].device)
+        for i, w in enumerate(waves):
+            rows[i, : lens[i]] = w
+    probs, n_w, _, stats = _rt.vad_probs_rows(rows, lens, window, o)
+    for i in range(len(waves)):
+        if int(stats[i, 3]) != int(n_w[i]):  # a window without a level: NaN is loud
+            first = _first_bad_window(waves[i], window)
+            if first < 0:  # finite samples whose fp32 energy is not
+                raise ValueError(f"waveform {i} holds samples too large for an fp32 energy (above about 1e19)")
+            raise ValueError(f"waveform {i} holds a sample that is not finite, first in window {first} of {int(n_w[i])} "
+                             f"(window_size_samples={window})")
+    return [probs[i, : int(n_w[i])].clone() for i in range(len(waves))]

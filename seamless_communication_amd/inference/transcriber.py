@@ -12,9 +12,16 @@ known (forced alignment; ragged batches), and ``transcribe_beam`` times the winn
 take the same attention rows from ONE batched teacher-forced decoder pass over the known tokens
 (sc_score_text_capture) instead of the step loop, and share the host bookkeeping with ``transcribe``.
 
+Long input: ``transcribe_long`` splits the audio with ``segment.SpeechSegmenter`` (the reference's segmentation algorithm on
+the device's own speech detector, or on any ``vad=`` callable), decodes the segments as batches of up to 64 rows of
+sc_generate_text_capture (``_decode_batch``; ``transcribe_batch`` is the same for a list of short inputs) and returns ONE
+``Transcription`` of all segments with absolute times, the per-segment results in ``Transcription.segments``.
+``transcribe(..., segmenter=obj)`` goes there for input over ``chunk_size_sec``.
+
 Not available (``NotImplementedError``): ``denoise=True`` (the Demucs denoiser is not part of
-this project), inputs longer than ``chunk_size_sec`` (the reference splits them with Silero VAD, which cannot be
-obtained offline) and ``transcribe(beam_size > 1)`` (``transcribe_beam`` is the call for that).
+this project), ``transcribe`` of input longer than ``chunk_size_sec`` WITHOUT ``segmenter=`` (the reference splits it with
+Silero VAD, which cannot be obtained offline; nothing is segmented behind the caller's back with another detector) and
+``transcribe(beam_size > 1)`` (``transcribe_beam`` is the call for that).
 """
 from __future__ import annotations
 
@@ -65,12 +72,16 @@ class Transcription:
     tokens: List[TranscriptionToken]
     lang: Optional[str]  # the language transcribed in: the caller's src_lang, or the identified one (src_lang=None)
     lid: Optional[Any]   # the lid.LanguageId behind an identified `lang`; None when src_lang was given
+    # transcribe_long only: (start_s, end_s, the segment's own Transcription with times relative to start_s); None elsewhere
+    segments: Optional[List[Tuple[float, float, "Transcription"]]]
 
-    def __init__(self, tokens: List[TranscriptionToken], lang: Optional[str] = None, lid: Optional[Any] = None):
+    def __init__(self, tokens: List[TranscriptionToken], lang: Optional[str] = None, lid: Optional[Any] = None,
+                 segments: Optional[List[Tuple[float, float, "Transcription"]]] = None):
         self.tokens = tokens
         self.text = " ".join(t.text for t in tokens)
         self.lang = lang
         self.lid = lid
+        self.segments = segments
 
     def __add__(self, other: "Transcription") -> "Transcription":
         self.text += " " + other.text
@@ -201,6 +212,15 @@ class Transcriber:
             o["max_seq_len"] = min(int(o["max_seq_len"]), prefix_len + int(gen))
         return soft, int(o["max_seq_len"]), float(o["unk_penalty"])
 
+    def _whole_strides(self, fb: Tensor, frames: np.ndarray) -> Tuple[Tensor, np.ndarray]:
+        """An unpadded fbank with a frame count that is no multiple of ``fbank_stride`` loses the frames that do not fill a stride,
+        as in fairseq2's fbank feature extractor, which the reference's Transcriber feeds without a Collater (the library's
+        entry takes whole strides only; an item's own length is divided the same way there).  A segment cut at a window edge
+        has an odd frame count as often as an even one."""
+        stride = self.cfg.fbank_stride
+        whole = fb.shape[1] - fb.shape[1] % stride
+        return fb[:, :whole].contiguous(), np.minimum(np.asarray(frames), whole).astype(np.int32)
+
     def _decode(self, wav: Tensor, sample_rate: int, src_lang: Optional[str], opts: Dict[str, Any]):
         """-> (token ids without prompt and EOS, step scores of those tokens, attention rows of the reference's hook
         without its last row, the language, its identification or None).  ``src_lang=None``: the language token the decoder
@@ -209,7 +229,7 @@ class Transcriber:
         w = wav[:, 0].to(torch.float32).contiguous().unsqueeze(0).to(self.device)
         # standardize=True, waveform_scale 2**15 inside the HIP front end; no padding, no padding mask
         fb, frames = model.fbank(w, [w.shape[1]], standardize=True, pad_to_multiple=1, sample_rate=int(sample_rate))
-        enc, enc_lens = model.encode_speech(fb, frames)
+        enc, enc_lens = model.encode_speech(*self._whole_strides(fb, frames))
         lid = None
         if src_lang is None:
             lid = identify_encoded(model, self.tokenizer, enc, enc_lens)[0]
@@ -237,15 +257,26 @@ class Transcriber:
     ) -> Optional[Transcription]:
         """audio: a file path or a (T, C) waveform tensor at ``sample_rate`` -> the words with their start times and
         probabilities.  ``sequence_generator_options``: BeamSearchSeq2SeqGenerator's (beam_size 1 only).
-        ``src_lang=None``: the language is identified first; the result's ``lang`` names it and ``lid`` holds the scores."""
+        ``src_lang=None``: the language is identified first; the result's ``lang`` names it and ``lid`` holds the scores.
+        ``segmenter=obj`` (a keyword beyond the reference's, taken out of ``sequence_generator_options`` so that the
+        signature stays the reference's): input longer than ``chunk_size_sec`` goes to ``transcribe_long`` with it - ``True`` for
+        the built-in ``SpeechSegmenter``, or any object with ``segment_long_input``.  Without it long input is refused."""
         if denoise:
             raise NotImplementedError("denoise=True: the Demucs denoiser is not part of this project")
         wav = _waveform(audio, sample_rate)
         length_seconds = wav.size(0) / sample_rate
-        if length_seconds > chunk_size_sec:
-            raise NotImplementedError(f"input of {length_seconds:.2f} s > chunk_size_sec={chunk_size_sec}: the reference segments "
-                                      "long input with Silero VAD, which cannot be obtained offline")
         opts = dict(sequence_generator_options)
+        segmenter = opts.pop("segmenter", None)
+        if length_seconds > chunk_size_sec:
+            if segmenter is None:
+                raise NotImplementedError(f"input of {length_seconds:.2f} s > chunk_size_sec={chunk_size_sec}: the reference segments "
+                                          "long input with Silero VAD, which cannot be obtained offline; pass segmenter= (True: this "
+                                          "project's energy detector, or a SpeechSegmenter around a vad= callable) or call transcribe_long")
+            if (opts.get("beam_size") or 1) > 1:
+                raise NotImplementedError("beam_size > 1: the attention capture runs on the greedy decoder step only")
+            opts.pop("beam_size", None)
+            return self.transcribe_long(wav, src_lang, filter_width=filter_width, sample_rate=sample_rate, chunk_size_sec=chunk_size_sec,
+                                        pause_length_sec=pause_length_sec, segmenter=None if segmenter is True else segmenter, **opts)
         beam_size = opts.pop("beam_size", None) or 1
         if beam_size > 1:
             raise NotImplementedError("beam_size > 1: the attention capture runs on the greedy decoder step only")
@@ -255,6 +286,134 @@ class Transcriber:
         times = self._extract_timestamps(rows, length_seconds, filter_width)
         pieces = [self.tokenizer.index_to_token(t) for t in token_ids]
         return Transcription(self._collect_word_level_stats(pieces=pieces, token_timestamps=times, step_scores=step_scores), lang, lid)
+
+    # ---- batches of short inputs and long input: fbank -> encoder -> capture calls of up to 64 rows --------------------------
+    CAPTURE_ROWS = 64  # the row limit of sc_generate_text_capture
+
+    def _decode_batch(self, wavs: List[Tensor], sample_rate: int, lang: Optional[str], opts: Dict[str, Any], padded_encoder: bool = False,
+                      lid_item: Optional[int] = None):
+        """``_decode`` for many items in ONE language -> ([(token ids, step scores, attention rows)] in input order, the language,
+        its identification or None).  One fbank call and the encoder as in ``_encode`` (item by item unless ``padded_encoder``, so
+        an item's encoder output does not depend on its batch), then generate_text_capture calls of at most ``CAPTURE_ROWS`` rows
+        over the items sorted by encoder length (rows of one call have similar lengths).  ``lang=None``: the language identified
+        on item ``lid_item`` serves all items.  A ``max_gen_len`` of the form (a, b) refers to the source length, which a
+        capture call takes once for all its rows: such a call holds items of one frame count only."""
+        model = self.model
+        enc, enc_lens, frames = self._encode(wavs, sample_rate, padded_encoder)
+        lid = None
+        if lang is None:
+            i = int(lid_item or 0)
+            lid = identify_encoded(model, self.tokenizer, enc[i : i + 1, : int(enc_lens[i])].contiguous(), enc_lens[i : i + 1])[0]
+            lang = lid.lang
+        prefix = self.tokenizer.target_prefix(lang)
+        n = len(wavs)
+        order = sorted(range(n), key=lambda i: (int(enc_lens[i]), i))
+        per_source = self._gen_limits(opts, len(prefix), 1)[0][0] != 0.0
+        calls: List[List[int]] = []
+        for i in order:
+            full = not calls or len(calls[-1]) >= self.CAPTURE_ROWS
+            if full or (per_source and int(frames[calls[-1][0]]) != int(frames[i])):
+                calls.append([])
+            calls[-1].append(i)
+        out: List[Any] = [None] * n
+        for pick in calls:
+            width = max(int(enc_lens[i]) for i in pick)
+            e = enc[pick, :width].contiguous()
+            src = max(int(frames[i]) for i in pick)
+            soft, hard, unk = self._gen_limits(opts, len(prefix), src)
+            ids, lens, _, xattn, step_lprob, _ = model.generate_text_capture(
+                e, [int(enc_lens[i]) for i in pick], prefix, soft_max_seq_len=soft, hard_max_seq_len=hard, unk_penalty=unk,
+                use_graph=self.use_graph, source_len=src)
+            xattn = xattn.cpu().numpy()
+            for b, i in enumerate(pick):
+                out[i] = restate_hook_rows(ids[b], int(lens[b]), len(prefix), xattn[b, :, : int(enc_lens[i])], step_lprob[b])
+        return out, lang, lid
+
+    def _words(self, decoded, seconds: float, filter_width: int, lang: Optional[str], lid: Optional[Any]) -> Transcription:
+        """the host bookkeeping of ``transcribe`` on one item of ``_decode_batch``"""
+        token_ids, step_scores, rows = decoded
+        if not token_ids:  # EOS first: no token, no timestamp
+            return Transcription([], lang, lid)
+        times = self._extract_timestamps(rows, seconds, filter_width)
+        pieces = [self.tokenizer.index_to_token(t) for t in token_ids]
+        return Transcription(self._collect_word_level_stats(pieces=pieces, token_timestamps=times, step_scores=step_scores), lang, lid)
+
+    @staticmethod
+    def _greedy_options(opts: Dict[str, Any]) -> Dict[str, Any]:
+        opts = dict(opts)
+        if (opts.pop("beam_size", None) or 1) > 1:
+            raise NotImplementedError("beam_size > 1: the attention capture runs on the greedy decoder step only")
+        return opts
+
+    @torch.inference_mode()
+    def transcribe_batch(self, audios: Sequence[Union[str, Tensor]], src_lang: Optional[str], filter_width: int = 3, sample_rate: int = 16000,
+                         padded_encoder: bool = False, **sequence_generator_options: Dict) -> List[Transcription]:
+        """``transcribe`` of every item of a ragged list (each at most 20 s, the reference's default ``chunk_size_sec``) with batched
+        decoder calls; item i equals ``transcribe(audios[i], src_lang)``.  One language per call - the capture call takes one shared
+        prompt; ``src_lang=None`` identifies every item and runs one group per identified language."""
+        opts = self._greedy_options(sequence_generator_options)
+        wavs = [_waveform(a, sample_rate) for a in audios]
+        for i, w in enumerate(wavs):
+            if w.size(0) / sample_rate > 20:
+                raise ValueError(f"item {i} holds {w.size(0) / sample_rate:.2f} s, above the limit of 20 s of a batch item (transcribe_long segments long input)")
+            if w.size(0) == 0:
+                raise ValueError(f"item {i} is empty")
+        if not wavs:
+            return []
+        self._gen_limits(opts, 2, 1)  # option errors before any device work
+        seconds = [w.size(0) / sample_rate for w in wavs]
+        if src_lang is not None:
+            self.tokenizer.target_prefix(src_lang)
+            decoded, lang, _ = self._decode_batch(wavs, sample_rate, src_lang, opts, padded_encoder)
+            return [self._words(d, seconds[i], filter_width, lang, None) for i, d in enumerate(decoded)]
+        enc, enc_lens, _ = self._encode(wavs, sample_rate, padded_encoder)
+        found = identify_encoded(self.model, self.tokenizer, enc, enc_lens)
+        out: List[Optional[Transcription]] = [None] * len(wavs)
+        for lang in sorted({f.lang for f in found}):
+            pick = [i for i, f in enumerate(found) if f.lang == lang]
+            decoded, _, _ = self._decode_batch([wavs[i] for i in pick], sample_rate, lang, opts, padded_encoder)
+            for i, d in zip(pick, decoded):
+                out[i] = self._words(d, seconds[i], filter_width, lang, found[i])
+        return out  # type: ignore[return-value]
+
+    @torch.inference_mode()
+    def transcribe_long(self, audio: Union[str, Tensor], src_lang: Optional[str], filter_width: int = 3, sample_rate: int = 16000,
+                        chunk_size_sec: float = 20, pause_length_sec: float = 1, segmenter: Optional[Any] = None, padded_encoder: bool = False,
+                        **sequence_generator_options: Dict) -> Transcription:
+        """Audio of any length -> ONE ``Transcription`` with the words of every speech segment in order and ABSOLUTE ``time_s``
+        (the segment's ``start / sample_rate`` plus the time inside the segment).  ``segments`` holds
+        ``(start_s, end_s, Transcription)`` per segment with segment-relative times, as ``transcribe`` of that slice returns them.
+        ``segmenter=None``: ``SpeechSegmenter(sample_rate, chunk_size_sec, pause_length_sec)`` on this device (an energy detector,
+        NOT the reference's Silero VAD); else any object with ``segment_long_input(wave_1d) -> [(start, end)]``
+        in samples.  Segments are clamped to the waveform, empty ones dropped.  No speech: an empty result with ``segments == []``.
+        ``src_lang=None``: the language is identified on the longest segment and used for all; ``lid`` holds that identification.
+        Two departures from the reference: its ``transcribe`` returns the LAST segment only (a bug of
+        its joining loop) and leaves every time relative to its segment."""
+        opts = self._greedy_options(sequence_generator_options)
+        wav = _waveform(audio, sample_rate)
+        if src_lang is not None:
+            self.tokenizer.target_prefix(src_lang)
+        self._gen_limits(opts, 2, 1)  # option errors before any device work
+        if segmenter is None:
+            from ..segment import SpeechSegmenter
+
+            segmenter = SpeechSegmenter(sample_rate, chunk_size_sec, pause_length_sec, device=self.device)
+        total = int(wav.size(0))
+        spans = []
+        for start, end in segmenter.segment_long_input(wav[:, 0]):
+            start, end = max(0, min(int(start), total)), max(0, min(int(end), total))
+            if end > start:
+                spans.append((start, end))
+        if not spans:
+            return Transcription([], src_lang, None, segments=[])
+        longest = max(range(len(spans)), key=lambda i: (spans[i][1] - spans[i][0], -i))
+        decoded, lang, lid = self._decode_batch([wav[a:b] for a, b in spans], sample_rate, src_lang, opts, padded_encoder, lid_item=longest)
+        segments, tokens = [], []
+        for (a, b), d in zip(spans, decoded):
+            one = self._words(d, (b - a) / sample_rate, filter_width, lang, None)
+            segments.append((a / sample_rate, b / sample_rate, one))
+            tokens += [TranscriptionToken(t.text, a / sample_rate + t.time_s, t.prob) for t in one.tokens]
+        return Transcription(tokens, lang, lid, segments=segments)
 
     # ---- known tokens: one batched teacher-forced pass with the attention rows (sc_score_text_capture) -------------------
     def _sequence(self, text: Union[str, Sequence[int]], lang: str) -> Optional[List[int]]:
@@ -285,9 +444,9 @@ class Transcriber:
         fb, frames = model.fbank(batch.to(self.device).contiguous(), ns, standardize=True, pad_to_multiple=2 if together else 1,
                                  sample_rate=int(sample_rate))
         if together or n == 1:
-            enc, enc_lens = model.encode_speech(fb, frames)
+            enc, enc_lens = model.encode_speech(*self._whole_strides(fb, frames))
             return enc, enc_lens, frames
-        parts = [model.encode_speech(fb[i : i + 1, : int(frames[i])].contiguous(), frames[i : i + 1]) for i in range(n)]
+        parts = [model.encode_speech(*self._whole_strides(fb[i : i + 1, : int(frames[i])], frames[i : i + 1])) for i in range(n)]
         enc = torch.zeros(n, max(e.shape[1] for e, _ in parts), parts[0][0].shape[2], dtype=torch.float32, device=parts[0][0].device)
         for i, (e, _) in enumerate(parts):
             enc[i, : e.shape[1]] = e[0]

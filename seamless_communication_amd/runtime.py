@@ -1013,6 +1013,52 @@ class HipPretsselWave(_Handle):
         return dict(zip(self.STAGES, (float(v) for v in ms)))
 
 
+VAD_OPTION_NAMES = ("hangover", "floor_quantile", "peak_quantile", "noise_ceiling_db", "min_margin_db", "range_fraction", "slope_db")
+
+
+def vad_opts(**options) -> Optional[_lib.sc_vad_opts]:
+    """The options of ``sc_vad_probs`` by name (None without any: the defaults).  As in the C struct a zero stands for the
+    option's default and ``hangover=-1`` for no hangover."""
+    unknown = set(options) - set(VAD_OPTION_NAMES)
+    if unknown:
+        raise TypeError(f"unexpected speech detector option(s) {sorted(unknown)}; known: {list(VAD_OPTION_NAMES)}")
+    if not options:
+        return None
+    o = _lib.sc_vad_opts()
+    o.abi_version = _lib.SC_ABI_VERSION
+    for k, v in options.items():
+        setattr(o, k, int(v) if k == "hangover" else float(v))
+    return o
+
+
+def vad_probs_rows(rows: torch.Tensor, lens: Sequence[int], window: int, opts: Optional[_lib.sc_vad_opts] = None, want_db: bool = False,
+                   probs_stride: Optional[int] = None):
+    """``sc_vad_probs`` on ``rows`` (n, stride) fp32 on a HIP device, row i valid up to ``lens[i]`` -> (probs (n, probs_stride) with
+    zeros behind every row's windows, the window counts, db (n, probs_stride) or None, stats (n, 4): F, P, c, finite windows).
+    ``probs_stride``: the most windows of a row unless given.  No handle: the tensor's device, the default stream."""
+    lib = _lib.load_library()
+    assert rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2 and (rows.shape[1] <= 1 or rows.stride(1) == 1)
+    n = rows.shape[0]
+    wav_stride = rows.stride(0) if n > 1 else max(rows.shape[1], 1)
+    num =np.ascontiguousarray(np.asarray(lens, dtype=np.int64))
+    assert num.shape == (n,) and n >= 1
+    n_w = np.asarray([lib.sc_vad_windows(int(x), int(window)) for x in num], dtype=np.int64)
+    if n_w.min() < 0:
+        raise SeamlessHipError(f"sc_vad_windows: window {window} or a negative length")
+    stride = int(n_w.max()) if probs_stride is None else int(probs_stride)
+    probs = torch.empty(n, stride, dtype=torch.float32, device=rows.device)
+    db = torch.empty(n, stride, dtype=torch.float32, device=rows.device) if want_db else None
+    stats = np.zeros((n, 4), dtype=np.float32)
+    with torch.cuda.device(rows.device):
+        # the entry launches on the default stream: order it behind the producer of `rows` when that is another stream
+        cur = torch.cuda.current_stream(rows.device)
+        if cur.cuda_stream != 0:
+            cur.synchronize()
+        check(lib.sc_vad_probs(_ptr(rows), n, wav_stride, _ptr(num), int(window), C.byref(opts) if opts is not None else None,
+                               _ptr(probs), stride, _ptr(db), _ptr(stats)), "sc_vad_probs")
+    return probs, n_w, db, stats
+
+
 RESAMPLING_METHODS = {"sinc_interp_hann": 0, "sinc_interp_kaiser": 1}
 
 
