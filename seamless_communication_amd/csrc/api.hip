@@ -5,6 +5,7 @@
 #include <mutex>
 #include <set>
 
+#include "dstep.h"
 #include "engine.h"
 #include "handle.h"
 
@@ -1162,22 +1163,20 @@ int sc_op_chain_bench(int32_t kind, int32_t rows, int32_t n, int32_t reps, float
             launch_dattn(a, k == 6, st);
         }
     };
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    SC_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < n; ++i) {
-        if (kind == 7) one(i & 1 ? 1 : 2);
-        else one(kind);
-    }
-    SC_HIP(hipStreamEndCapture(st, &g));
-    SC_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    for (int r = 0; r < 2; ++r) SC_HIP(hipGraphLaunch(ge, st));
+    StepGraph g;
+    g.ensure(st, [&] {
+        for (int i = 0; i < n; ++i) {
+            if (kind == 7) one(i & 1 ? 1 : 2);
+            else one(kind);
+        }
+    });
+    for (int r = 0; r < 2; ++r) g.launch(st);
     SC_HIP(hipStreamSynchronize(st));
     hipEvent_t e0, e1;
     SC_HIP(hipEventCreate(&e0));
     SC_HIP(hipEventCreate(&e1));
     SC_HIP(hipEventRecord(e0, st));
-    for (int r = 0; r < reps; ++r) SC_HIP(hipGraphLaunch(ge, st));
+    for (int r = 0; r < reps; ++r) g.launch(st);
     SC_HIP(hipEventRecord(e1, st));
     SC_HIP(hipStreamSynchronize(st));
     float ms = 0.f;
@@ -1185,8 +1184,7 @@ int sc_op_chain_bench(int32_t kind, int32_t rows, int32_t n, int32_t reps, float
     *us_per_kernel = 1e3f * ms / (float)(reps * n);
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    (void)hipGraphExecDestroy(ge);
-    (void)hipGraphDestroy(g);
+    g = StepGraph();  // before its stream goes
     (void)hipStreamDestroy(st);
     SC_API_END
 }

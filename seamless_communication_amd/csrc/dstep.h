@@ -1,5 +1,6 @@
-// Decoder-step context shared by the callers of the step chain: greedy generation and beam search (model_decoder.hip) and
-// the decode engine (engine.hip).
+// Decoder-step context, scratch and graph replay shared by every loop that drives the step chain (model_dstep.hip:
+// decoder_step and its three kernel families): greedy generation, the teacher-forced stepwise pass, beam search and the
+// streaming monotonic decoder (model_decoder.hip), sampled generation (model_sample.hip) and the decode engine (engine.hip).
 #pragma once
 #include <mutex>
 
@@ -67,15 +68,126 @@ struct StepCtx {
     int* prefix_row = nullptr;
 };
 
+// ---- the step chain (model_dstep.hip) ---------------------------------------------------------------------------------
 DecStack unity_stack(const Model& m);
+DecStack t2u_ar_stack(const Model& m);
+DecStack mma_stack(const Model& m);
 bool step2_eligible(const Model& m, const DecStack& W, int nb);
 bool step3_eligible(const Model& m, const DecStack& W, int nb);
 bool step3_wide_eligible(const Model& m, const DecStack& W, int nb);
-void alloc_step2(Model& m, StepCtx& c, int ffn_dim);
 int choose_family(const Model& m, const DecStack& W, int rows, int caller);
 // One decoder step for all batch rows: feeds d_tok at position *d_pos (engine: every slot at its row's position)
 void decoder_step(Model& m, StepCtx& c, bool project);
+// the six planes of a context of c.nb rows (sets c.rb, owns them in c.planes) / the same layout over an existing allocation
+void alloc_step2(Model& m, StepCtx& c, int ffn_dim);
+void alloc_step2_views(Model& m, StepCtx& c, int ffn_dim, __half* base);
+// monotonic decoder: EnergyProjection, (Linear, ReLU) x n on `rows` rows (returns the buffer holding the result), and one
+// level of it for every layer in one launch (energy_level_kernel: Wt / Bt are one level's pointer tables)
+float* energy_mlp(Model& m, const std::vector<Linear>& layers, const float* in, int64_t ld_in, float* a, float* b, int rows);
+void launch_energy_level(Model& m, const __half* const* Wt, const float* const* Bt, int layers, const float* in, int64_t in_ls, float* out);
+
+// Row-group tuning of the third-generation chain (StepCtx::rg_small / rg_ffn / ffn_in_mode / ffn_out_mode).  Which caller
+// honours which knob is kept as found:
+//   greedy generation and beam search read SC_D3_* (from_knobs);
+//   sampled generation: not honoured; kept as found (defaults);
+//   the decode engine: not honoured; kept as found - it has its own SC_ENGINE_RG_SMALL, above 64 slots (engine.hip).
+struct StepTuning {
+    int rg_small = 16, rg_ffn = 32, ffn_in_mode = 1, ffn_out_mode = 1;
+    // N = M products: 16-row groups are tuned for <= 64 rows; above 128 live rows 32-row groups halve the workgroups that
+    // re-read a weight tile - same bits whatever the grouping (tests/test_dstep3_gpu.py)
+    static StepTuning defaults(int rows) {
+        StepTuning t;
+        t.rg_small = rows > 128 ? 32 : 16;
+        return t;
+    }
+    // the knobs, clamped to what the launches accept (an out-of-range value would otherwise only surface as a failed check
+    // inside a captured step)
+    static StepTuning from_knobs(int rows);
+};
+
+// The buffers a step needs whatever loop drives it.  What differs per caller - the int / float state blocks, logits, the
+// arg-max records, dec_hidden, the self and cross K / V - stays with the caller.
+struct StepScratch {
+    Buf<float> x, h, wide, att, hN, partial, xg, qkvr, qkv3;
+};
+// The packed chains' share, for c.nb = `rows` rows on kernel family `family` (choose_family): hN, partial, the six planes
+// (family >= 2), xg / qkvr and c.gen3 (family >= 3), qkv3 (the wide step's complete q | k | v rows: > 64 rows, never
+// the decode engine, whose slots keep the packed product), and the tuning fields.  The decode engine calls this alone.
+void init_chain_scratch(Model& m, StepScratch& s, StepCtx& c, const DecStack& W, int rows, int family, const StepTuning& t);
+// ... plus the general step's fp32 rows x / h / att / wide.  wide_always = false (the greedy session, kept across calls):
+// a 4-element placeholder when a packed chain runs, which never reads it.
+void init_step_scratch(Model& m, StepScratch& s, StepCtx& c, const DecStack& W, int rows, int family, const StepTuning& t,
+                       bool wide_always = true);
+
 // graph captures and instantiations are serialised process-wide (another handle's host thread may allocate while one records)
 std::mutex& capture_mutex();
+
+// One captured step chain: THE capture site of the library.  ensure() records once (thread-local capture under
+// capture_mutex(); an exception out of `record` ends the capture, drops the dead graph and goes on up); launch() replays.
+// Kept apart so that a caller's profiler scope can cover the replay alone.
+class StepGraph {
+   public:
+    StepGraph() = default;
+    StepGraph(const StepGraph&) = delete;
+    StepGraph& operator=(const StepGraph&) = delete;
+    StepGraph(StepGraph&& o) noexcept : graph_(o.graph_), exec_(o.exec_) { o.graph_ = nullptr, o.exec_ = nullptr; }
+    StepGraph& operator=(StepGraph&& o) noexcept {
+        if (this != &o) {
+            reset();
+            graph_ = o.graph_, exec_ = o.exec_;
+            o.graph_ = nullptr, o.exec_ = nullptr;
+        }
+        return *this;
+    }
+    ~StepGraph() { reset(); }
+    bool ready() const { return exec_ != nullptr; }
+    template <class F>
+    void ensure(hipStream_t stream, F&& record) {
+        if (ready()) return;
+        std::lock_guard<std::mutex> lock(capture_mutex());
+        reset();  // a graph whose instantiation failed last time
+        SC_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+        try {
+            record();
+        } catch (...) {
+            hipGraph_t dead = nullptr;
+            (void)hipStreamEndCapture(stream, &dead);
+            if (dead) (void)hipGraphDestroy(dead);
+            throw;
+        }
+        SC_HIP(hipStreamEndCapture(stream, &graph_));
+        SC_HIP(hipGraphInstantiate(&exec_, graph_, nullptr, nullptr, 0));
+    }
+    void launch(hipStream_t stream) { SC_HIP(hipGraphLaunch(exec_, stream)); }
+
+   private:
+    void reset() {
+        if (exec_) (void)hipGraphExecDestroy(exec_);
+        if (graph_) (void)hipGraphDestroy(graph_);
+        graph_ = nullptr, exec_ = nullptr;
+    }
+    hipGraph_t graph_ = nullptr;
+    hipGraphExec_t exec_ = nullptr;
+};
+
+// ---- shared by beam search (model_decoder.hip) and sampled generation (model_sample.hip) ------------------------------
+// the limits of a generation call, before any device work; `who` prefixes every message
+void check_generation_limits(const char* who, const sc_gen_opts& o, int prefix_len, int max_len, int decoder_max_seq_len, int n, int s_enc,
+                             const int32_t* h_enc_lens);
+// the caller's banned sequences on the device (validated on the host first; an empty list makes no device work)
+struct BannedDevice {
+    BannedList list;
+    Buf<int> store;
+};
+BannedDevice upload_banned(Model& m, const BannedHost* banned, int V);
+// the general step reads one encoder K / V per row: the encoder output [n][s_enc][M] repeated `per_item` times per item
+Buf<float> fan_out_encoder(Model& m, const float* d_enc, int n, int per_item, int s_enc);
+// vocabulary logits of the live rows into c.logits (row stride ldl): the streaming kernel on the packed embedding when v3
+// (it stops at *c.d_rows where the caller set that), the tiled product on c.hN otherwise
+void project_logits(Model& m, StepCtx& c, const DecStack& W, bool v3, int64_t ldl);
+// decoder outputs of the chosen hypothesis per utterance (row u * ids_stride of h_ids / h_lens): the reference's
+// teacher-forced pass over text_seqs[:, :-1] (generator.py:281-299) into d_dec_hidden [n][max_len - 1][M]
+void hidden_of_best(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o, const int32_t* h_ids,
+                    const int32_t* h_lens, int ids_stride, int max_len, int pad_idx, float* d_dec_hidden);
 
 }  // namespace sc

@@ -81,7 +81,8 @@ struct Engine::Impl {
     int L = 0, M = 0;
     // device state
     Buf<int> ints, d_rids, d_stage;
-    Buf<float> fl, hidden, xg, qkvr, partial, am_eos, hN;
+    Buf<float> fl, hidden, am_eos;
+    StepScratch scratch;  // the row-group chain's share only (init_chain_scratch)
     Buf<float4> am_part;
     Buf<EngineAdmitRec> d_admit;
     Buf<EngineRetireRec> d_retire;
@@ -91,8 +92,7 @@ struct Engine::Impl {
     Pinned<int> h_fin, h_rids, h_stage;
     Pinned<EngineAdmitRec> h_admit;
     Pinned<EngineRetireRec> h_retire;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
+    StepGraph graph;
     // shared with the submitting threads (mu)
     std::mutex mu;
     std::condition_variable cv, cv_free, cv_done;
@@ -112,11 +112,6 @@ struct Engine::Impl {
     bool slots_dirty = false;
     double waited_us = 0;
     std::thread th;
-
-    ~Impl() {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-    }
 
     void setup(const Model& parent);
     void loop();
@@ -177,22 +172,15 @@ void Engine::Impl::setup(const Model& parent) {
     fl = Buf<float>(em.pp(), (size_t)R);
     SC_HIP(hipMemsetAsync(fl.get(), 0, (size_t)R * 4, em.stream));
     c.d_score = fl;
-    alloc_step2(em, c, cfg.dec_ffn_dim);  // the six planes, rb = slots rounded up to 32
-    c.gen3 = true;
+    // rows per row group of the N = 1024 products (out-projections, cross-attention query): 16 is tuned for <= 64 rows
+    // (latency); SC_ENGINE_RG_SMALL for A/B timing of the wide step (same bits whatever the grouping)
+    // (16 up to 128 slots, 32 above: 3.38 -> 3.22 ms per 192-slot step alone, profiles/r5_engine_sweep.txt)
+    StepTuning tune;
+    if (S > 64) tune.rg_small = std::min(32, std::max(8, knob::value("SC_ENGINE_RG_SMALL", S > 128 ? 32 : 16)));
+    // hN, partial, the six planes (rb = slots rounded up to 32), xg, qkvr: the step is always the row-group chain
+    init_chain_scratch(em, scratch, c, W, S, S > 64 ? 4 : 3, tune);  // family: row-group, wide above 64 slots
     c.am_ntl = 4;
     c.am_tiles = vocab3_groups(S);
-    xg = Buf<float>(em.pp(), (size_t)M * c.rb);
-    qkvr = Buf<float>(em.pp(), (size_t)S * M);
-    hN = Buf<float>(em.pp(), (size_t)S * M);
-    c.xg = xg, c.qkvr = qkvr, c.hN = hN;
-    if (S > 64) {
-        // rows per row group of the N = 1024 products (out-projections, cross-attention query): 16 is tuned for <= 64 rows
-        // (latency); SC_ENGINE_RG_SMALL for A/B timing of the wide step (same bits whatever the grouping)
-        // (16 up to 128 slots, 32 above: 3.38 -> 3.22 ms per 192-slot step alone, profiles/r5_engine_sweep.txt)
-        c.rg_small = std::min(32, std::max(8, knob::value("SC_ENGINE_RG_SMALL", S > 128 ? 32 : 16)));
-    }
-    partial = Buf<float>(em.pp(), (size_t)std::max(1, std::max(M, cfg.dec_ffn_dim) / 256) * S * 3 * M);
-    c.partial = partial;
     am_part = Buf<float4>(em.pp(), (size_t)c.am_tiles * S);
     am_eos = Buf<float>(em.pp(), (size_t)S);
     c.am_part = am_part, c.am_eos_logit = am_eos;
@@ -286,22 +274,9 @@ void Engine::Impl::steps(int k) {
             decoder_step(em, c, true);
             continue;
         }
-        if (!exec) {
-            std::lock_guard<std::mutex> lock(capture_mutex());
-            SC_HIP(hipStreamBeginCapture(em.stream, hipStreamCaptureModeThreadLocal));
-            try {
-                decoder_step(em, c, true);
-            } catch (...) {
-                hipGraph_t dead = nullptr;
-                (void)hipStreamEndCapture(em.stream, &dead);
-                if (dead) (void)hipGraphDestroy(dead);
-                throw;
-            }
-            SC_HIP(hipStreamEndCapture(em.stream, &graph));
-            SC_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        }
+        graph.ensure(em.stream, [&] { decoder_step(em, c, true); });
         prof::Scope scope("step_graph", (double)n * w_bytes, w_bytes + kv_bytes, em.stream);
-        SC_HIP(hipGraphLaunch(exec, em.stream));
+        graph.launch(em.stream);
     }
 }
 

@@ -187,7 +187,7 @@ struct ModelData {
     std::vector<DecoderLayer> mma_dec;
     std::vector<PChooseLayer> mma_pc;
     // query-side energy MLPs of all layers as device pointer tables [energy_layers][mma_layers] (weights fp16 [M][ldw],
-    // biases fp32 [M]) + the per-layer energy bias pointers: one batched launch per MLP level (model_decoder.hip)
+    // biases fp32 [M]) + the per-layer energy bias pointers: one batched launch per MLP level (model_dstep.hip)
     const __half* const* mma_qe_w = nullptr;
     const float* const* mma_qe_b = nullptr;
     const float* const* mma_ebias = nullptr;

@@ -1,5 +1,6 @@
 // NLLB text decoder: greedy autoregressive generation with a KV cache, the
-// per-step launch sequence optionally replayed from a captured hipGraph.
+// per-step launch sequence optionally replayed from a captured hipGraph; the streaming monotonic decoder, the
+// teacher-forced passes, scoring, language identification and beam search.  The step itself: model_dstep.hip.
 //
 // Reference call sites (src/seamless_communication/...):
 //   inference/generator.py:147-156,261-263   BeamSearchSeq2SeqGenerator (beam 1 here)
@@ -8,15 +9,11 @@
 // Step rules restated from ggml/examples/unity/fairseq2.cpp:1097-1126 (max length),
 // :1269-1305 (_tweak_lprobs), :1463-1594 (step loop).
 #include <cstdlib>
-#include <mutex>
 
 #include "dstep.h"
 #include "engine.h"
 
 namespace sc {
-
-static std::mutex g_capture_mutex;
-std::mutex& capture_mutex() { return g_capture_mutex; }
 
 int text_max_len(const Model& m, const sc_gen_opts& o, int s_enc) {
     int max_len;
@@ -29,740 +26,6 @@ int text_max_len(const Model& m, const sc_gen_opts& o, int s_enc) {
 void run_generate_text_beam(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                             const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
                             float* d_dec_hidden, const BannedHost* banned = nullptr, int prefix_stride = 0);
-
-namespace {
-
-DecStack mma_stack(const Model& m);  // defined with the streaming decoder below
-
-}  // namespace
-
-DecStack unity_stack(const Model& m) {
-    DecStack w;
-    w.embed = m.text_embed;
-    w.embed_p = m.text_embed_p;
-    w.pos = m.text_pos;
-    w.layers = &m.dec;
-    w.final_ln = &m.dec_final_ln;
-    w.ffn_dim = m.cfg.dec_ffn_dim;
-    w.ffn_act = m.ffn_act;
-    w.pchoose = nullptr;
-    w.vocab = m.cfg.text_vocab_size;
-    w.pad_idx = m.cfg.pad_idx;
-    w.unk_idx = m.cfg.unk_idx;
-    w.eos_idx = m.cfg.eos_idx;
-    w.max_seq_len = m.cfg.text_max_seq_len;
-    return w;
-}
-
-namespace {
-
-// the v1 autoregressive T2U decoder (unit vocabulary: bos 0, pad 1, eos 2, unk 3; t2u_builder.py:143-147)
-DecStack t2u_ar_stack(const Model& m) {
-    DecStack w;
-    w.embed = m.t2u_ar_embed;
-    w.embed_p = nullptr;
-    w.pos = m.t2u_ar_pos;
-    w.layers = &m.t2u_ar_dec;
-    w.final_ln = &m.t2u_ar_final_ln;
-    w.ffn_dim = m.cfg.t2u_ffn_dim;
-    w.pchoose = nullptr;
-    w.vocab = m.cfg.unit_vocab_size;
-    w.pad_idx = m.cfg.unit_pad_idx;
-    w.unk_idx = 3;
-    w.eos_idx = m.cfg.unit_eos_idx;
-    w.max_seq_len = m.cfg.unit_max_seq_len;
-    return w;
-}
-
-// p_choose[h] = sigmoid(((q_h . k_h) / sqrt(head_dim) + energy_bias) / temperature) for one query row and one
-// pooled key (PChooseLayer.forward, models/monotonic_decoder/p_choose.py:120-148, last query x last key only:
-// the streaming policy reads p_choose[..., -1, -1], streaming/agents/online_text_decoder.py:236-241).
-__global__ void pchoose_kernel(const float* __restrict__ q, const float* __restrict__ k, int head_dim,
-                               const float* __restrict__ energy_bias, float temperature, float* __restrict__ out) {
-    const int h = blockIdx.x, lane = threadIdx.x;
-    float acc = 0.f;
-    for (int c = lane; c < head_dim; c += 64) acc = fmaf(q[h * head_dim + c], k[h * head_dim + c], acc);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if (lane == 0) {
-        float e = acc * rsqrtf((float)head_dim);
-        if (energy_bias) e += energy_bias[0];
-        out[h] = 1.f / (1.f + expf(-(e / temperature)));
-    }
-}
-
-// One level of the query-side EnergyProjection of EVERY layer in one launch (the streaming step's p_choose hook):
-//   out[l][n] = relu(b[l][n] + W[l][n][:] . in[l][:])      one row per layer, fp16 weights, fp32 arithmetic.
-// grid (M / 32, layers); a wave owns 8 output features: all 16 weight loads (8 features x 2 K halves of 512) are issued
-// before the first use, the row vector sits in registers (16 floats per lane), wave reduction by shuffles.
-__global__ __launch_bounds__(256) void energy_level_kernel(const __half* const* __restrict__ Wt, const float* const* __restrict__ Bt,
-                                                           int ldw, const float* __restrict__ in, int64_t in_ls,
-                                                           float* __restrict__ out, int M) {
-    typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
-    const int l = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n0 = blockIdx.x * 32 + wave * 8;
-    const __half* W = Wt[l];
-    const float* x = in + (int64_t)l * in_ls;  // in_ls = 0: the same row for every layer
-    float xv[2][8];
-    h8_t w[8][2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const int k = c * 512 + lane * 8;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) xv[c][e] = k + e < M ? x[k + e] : 0.f;
-#pragma unroll
-        for (int f = 0; f < 8; ++f) {
-            h8_t z;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) z[e] = (_Float16)0.f;
-            w[f][c] = (k < M && n0 + f < M) ? *reinterpret_cast<const h8_t*>(W + (int64_t)(n0 + f) * ldw + k) : z;
-        }
-    }
-#pragma unroll
-    for (int f = 0; f < 8; ++f) {
-        float acc = 0.f;
-#pragma unroll
-        for (int c = 0; c < 2; ++c)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) acc = fmaf((float)w[f][c][e], xv[c][e], acc);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-        if (lane == 0 && n0 + f < M) {
-            const float v = acc + (Bt[l] ? Bt[l][n0 + f] : 0.f);
-            out[(int64_t)l * M + n0 + f] = !(v <= 0.f) ? v : 0.f;  // NaN stays NaN
-        }
-    }
-}
-
-// p_choose of every (layer, head): grid (heads, layers), see pchoose_kernel
-__global__ void pchoose_all_kernel(const float* __restrict__ q, const float* __restrict__ k, int M, int head_dim,
-                                   const float* const* __restrict__ energy_bias, float temperature, float* __restrict__ out) {
-    const int h = blockIdx.x, l = blockIdx.y, lane = threadIdx.x, H = gridDim.x;
-    const float* ql = q + (int64_t)l * M + h * head_dim;
-    const float* kl = k + (int64_t)l * M + h * head_dim;
-    float acc = 0.f;
-    for (int c = lane; c < head_dim; c += 64) acc = fmaf(ql[c], kl[c], acc);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if (lane == 0) {
-        float e = acc * rsqrtf((float)head_dim);
-        if (energy_bias[l]) e += energy_bias[l][0];
-        out[l * H + h] = 1.f / (1.f + expf(-(e / temperature)));
-    }
-}
-
-// EnergyProjection (p_choose.py:17-45): (Linear, ReLU) x n on `rows` rows; returns the buffer holding the result.
-float* energy_mlp(Model& m, const std::vector<Linear>& layers, const float* in, int64_t ld_in, float* a, float* b, int rows) {
-    const int M = m.cfg.model_dim;
-    const float* src = in;
-    int64_t ld = ld_in;
-    float* dst = a;
-    for (const Linear& L : layers) {
-        linear(m, src, ld, L, nullptr, 0, dst, M, rows, ACT_RELU, 1.f);
-        src = dst;
-        ld = M;
-        dst = (dst == a) ? b : a;
-    }
-    return const_cast<float*>(src);
-}
-
-__global__ void store_hidden_kernel(const float* __restrict__ hN, float* __restrict__ dst, int M, int hid_rows,
-                                    const int* __restrict__ d_pos) {
-    const int b = blockIdx.x;
-    const int pos = *d_pos;
-    if (pos >= hid_rows) return;
-    const float4* s = reinterpret_cast<const float4*>(hN + (int64_t)b * M);
-    float4* d = reinterpret_cast<float4*>(dst + ((int64_t)b * hid_rows + pos) * M);
-    for (int c = threadIdx.x; c < M / 4; c += blockDim.x) d[c] = s[c];
-}
-
-// out-projection + residual + the NEXT LayerNorm:  x += in . W^T + b ;  h_out = LN_next(x).
-// Up to 64 rows: split-K skinny product into K-range partials, summed in fixed order by the fused
-// reduce + residual + LayerNorm kernel.  More rows: the MFMA GEMM with a residual epilogue + LayerNorm.
-void out_proj_res_ln(Model& m, StepCtx& c, const float* in, int64_t ld_in, const Linear& L, const LNorm& next,
-                     float* h_out) {
-    const int nb = c.nb, M = m.cfg.model_dim;
-    if (nb <= 64 && L.in % 64 == 0 && L.out == M && M % 4 == 0) {
-        SkinnyArgs a;
-        a.A = in;
-        a.lda = ld_in;
-        a.W = L.w;
-        a.ldw = L.ldw;
-        a.M = nb;
-        a.N = L.out;
-        a.K = L.in;
-        a.splits = skinny_splits(nb, L.out, L.in, 1);
-        a.partial = c.partial;
-        launch_skinny(a, m.stream);
-        launch_reduce_res_ln(c.partial, a.splits, L.b, c.x, next.g, next.b, h_out, nb, M, m.stream);
-    } else {
-        linear(m, in, ld_in, L, c.x, M, c.x, M, nb, ACT_NONE, 1.f);
-        layernorm(m, c.x, next, h_out, nb);
-    }
-}
-
-// in . W^T as `*splits` K-range partial sums in c.partial (no bias): the consumer adds them up.
-// Returns false when the shape is outside the skinny kernel's domain (caller falls back to linear()).
-bool proj_partials(Model& m, StepCtx& c, const float* in, int64_t ld_in, const Linear& L, int* splits) {
-    if (c.nb > 64 || L.in % 64 != 0) return false;
-    SkinnyArgs a;
-    a.A = in;
-    a.lda = ld_in;
-    a.W = L.w;
-    a.ldw = L.ldw;
-    a.M = c.nb;
-    a.N = L.out;
-    a.K = L.in;
-    a.splits = skinny_splits(c.nb, L.out, L.in, 1);
-    a.partial = c.partial;
-    launch_skinny(a, m.stream);
-    *splits = a.splits;
-    return true;
-}
-
-}  // namespace
-
-// ---- second-generation step (k_dstep.hip) --------------------------------------------------------------------
-bool step2_eligible(const Model& m, const DecStack& W, int nb) {
-    const int M = m.cfg.model_dim;
-    static const bool off = knob::is_set("SC_DECODER_GEN1");  // A/B switch: the first-generation kernels
-    if (off || nb < 1 || nb > 64 || M % 64 != 0 || M > 1024 || W.ffn_dim % 64 != 0 || M != m.cfg.num_heads * 64) return false;
-    for (const DecoderLayer& l : *W.layers)
-        if (!l.qkv.wp || !l.self_out.wp || !l.cross_q.wp || !l.cross_out.wp || !l.ffn_in.wp || !l.ffn_out.wp) return false;
-    return true;
-}
-
-// plane buffers of one decoder-step context (rows beyond nb are never read: their lanes load out of range)
-void alloc_step2(Model& m, StepCtx& c, int ffn_dim) {
-    const int M = m.cfg.model_dim;
-    c.rb = (int)align_up(c.nb, 32);  // 32 / 64 up to 64 rows; more for the wide step of the beam search
-    const size_t pm = (size_t)M * c.rb, pf = (size_t)ffn_dim * c.rb;
-    c.planes = Buf<__half>(m.pp(), 4 * pm + 2 * pf);
-    c.hH = c.planes.get();
-    c.hL = c.hH + pm;
-    c.attH = c.hL + pm;
-    c.attL = c.attH + pm;
-    c.wideH = c.attL + pm;
-    c.wideL = c.wideH + pf;
-}
-
-namespace {
-
-
-// the same plane layout over an existing allocation (streaming state: the planes outlive the call)
-void alloc_step2_views(Model& m, StepCtx& c, int ffn_dim, __half* base) {
-    const int M = m.cfg.model_dim;
-    c.rb = c.nb <= 32 ? 32 : 64;
-    const size_t pm = (size_t)M * c.rb, pf = (size_t)ffn_dim * c.rb;
-    c.hH = base;
-    c.hL = c.hH + pm;
-    c.attH = c.hL + pm;
-    c.attL = c.attH + pm;
-    c.wideH = c.attL + pm;
-    c.wideL = c.wideH + pf;
-}
-
-static void gemv2(Model& m, StepCtx& c, const __half* Ah, const __half* Al, const Linear& L, int want_splits, int* splits) {
-    GemvPArgs a;
-    a.Wp = L.wp;
-    a.Ah = Ah;
-    a.Al = Al;
-    a.RB = c.rb;
-    a.M = c.nb;
-    a.N = L.out;
-    a.K = L.in;
-    a.splits = want_splits;
-    a.epi = EPI_PARTIAL;
-    a.partial = c.partial;
-    a.d_rows = c.d_rows;
-    launch_gemvp(a, m.stream);
-    *splits = gemvp_splits(L.in, want_splits);
-}
-
-// One decoder step for all batch rows on the second-generation kernels: 11 launches per layer
-// (QKV | self-attention | out-proj | +res+LN | q | cross-attention | out-proj | +res+LN | FFN-in | FFN-out | +res+LN).
-void decoder_step2(Model& m, StepCtx& c, bool project, const DecStack& W) {
-    const sc_config& cfg = m.cfg;
-    const int M = cfg.model_dim, nb = c.nb, H = cfg.num_heads;
-    const std::vector<DecoderLayer>& layers = *W.layers;
-    const int n_layers = (int)layers.size();
-    launch_embed_ln(c.d_tok, W.embed, sqrtf((float)M), W.pos, c.d_pos, c.x, layers[0].self_ln.g, layers[0].self_ln.b, c.hH, c.hL,
-                    c.rb, nb, M, m.stream);
-    for (int li = 0; li < n_layers; ++li) {
-        const DecoderLayer& l = layers[li];
-        const bool last = li + 1 == n_layers;
-        int sp = 1;
-        // self attention
-        gemv2(m, c, c.hH, c.hL, l.qkv, 2, &sp);
-        DAttnArgs a;
-        a.q = c.partial;
-        a.ldq = 3 * M;
-        a.sstride = (int64_t)nb * 3 * M;
-        a.S = sp;
-        a.koff = M;
-        a.voff = 2 * M;
-        a.bias = l.qkv.b;
-        a.kcache = c.kcache[li];
-        a.vcache = c.vcache[li];
-        a.cache_ld = M;
-        a.cache_bs = (int64_t)c.cap * M;
-        a.cap = c.cap;
-        a.d_pos = c.d_pos;
-        a.Oh = c.attH;
-        a.Ol = c.attL;
-        a.ORB = c.rb;
-        a.nb = nb;
-        a.heads = H;
-        a.anc = c.anc;
-        a.d_rows = c.d_rows;
-        launch_dattn(a, /*cross=*/false, m.stream);
-        gemv2(m, c, c.attH, c.attL, l.self_out, 4, &sp);
-        // monotonic decoder, p_choose step: the normed cross-attention input (monotonic_decoder_layer.py:170-172) of every
-        // layer is kept as an fp32 row; the energy MLPs of all layers run batched after the last layer
-        launch_reduce_ln(c.partial, sp, l.self_out.b, c.x, l.cross_ln.g, l.cross_ln.b, c.hH, c.hL, c.rb, nullptr, 0, 0, nullptr, nb, M,
-                         m.stream, c.pchoose ? c.d_hq + (int64_t)li * M : nullptr);
-        // encoder-decoder attention over the K/V projected once per utterance
-        gemv2(m, c, c.hH, c.hL, l.cross_q, 4, &sp);
-        DAttnArgs x;
-        x.q = c.partial;
-        x.ldq = M;
-        x.sstride = (int64_t)nb * M;
-        x.S = sp;
-        x.bias = l.cross_q.b;
-        x.kcache = c.cross_kv[li];
-        x.vcache = c.cross_kv[li] + M;
-        x.cache_ld = 2 * M;
-        x.cache_bs = (int64_t)c.s_enc * 2 * M;
-        x.cap = c.s_enc;
-        x.kv_lens = c.d_enc_lens;
-        x.kv_row_div = c.cross_row_div;
-        x.kv_item = c.kv_item;
-        x.d_rows = c.d_rows;
-        x.Oh = c.attH;
-        x.Ol = c.attL;
-        x.ORB = c.rb;
-        x.nb = nb;
-        x.heads = H;
-        launch_dattn(x, /*cross=*/true, m.stream);
-        gemv2(m, c, c.attH, c.attL, l.cross_out, 4, &sp);
-        launch_reduce_ln(c.partial, sp, l.cross_out.b, c.x, l.ffn_ln.g, l.ffn_ln.b, c.hH, c.hL, c.rb, nullptr, 0, 0, nullptr, nb, M,
-                         m.stream);
-        // feed-forward network: the inner activation stays in split planes
-        GemvPArgs f;
-        f.Wp = l.ffn_in.wp;
-        f.Ah = c.hH;
-        f.Al = c.hL;
-        f.RB = c.rb;
-        f.M = nb;
-        f.N = W.ffn_dim;
-        f.K = M;
-        f.splits = 1;
-        f.epi = EPI_PLANES;
-        f.bias = l.ffn_in.b;
-        f.act = ACT_RELU;
-        f.Oh = c.wideH;
-        f.Ol = c.wideL;
-        f.ORB = c.rb;
-        launch_gemvp(f, m.stream);
-        gemv2(m, c, c.wideH, c.wideL, l.ffn_out, 8, &sp);
-        const LNorm& next = last ? *W.final_ln : layers[li + 1].self_ln;
-        // the last layer's LayerNorm is the decoder output: also kept as fp32 rows (c.hN) and, when asked for, captured
-        // per position (the teacher-forced pass of the reference, generator.py:294-299)
-        if (last) {
-            launch_reduce_ln(c.partial, sp, l.ffn_out.b, c.x, next.g, next.b, c.hH, c.hL, c.rb, c.dec_hidden,
-                             (int64_t)(c.cap - 1) * M, c.dec_hidden ? c.cap - 1 : 0, c.d_pos, nb, M, m.stream, c.hN);
-        } else {
-            launch_reduce_ln(c.partial, sp, l.ffn_out.b, c.x, next.g, next.b, c.hH, c.hL, c.rb, nullptr, 0, 0, nullptr, nb, M, m.stream);
-        }
-    }
-    if (c.pchoose) {
-        SC_CHECK(nb == 1 && W.pchoose && m.mma_qe_w && M <= 1024, "p_choose hook: one row on the monotonic stack only");
-        const int E = cfg.mma_energy_layers;
-        const float* src = c.d_hq;
-        float* dst = c.qe0;
-        for (int e = 0; e < E; ++e) {
-            hipLaunchKernelGGL(energy_level_kernel, dim3(cdiv(M, 32), n_layers), dim3(256), 0, m.stream, m.mma_qe_w + (size_t)e * n_layers,
-                               m.mma_qe_b + (size_t)e * n_layers, m.mma_qe_ldw, src, (int64_t)M, dst, M);
-            SC_LAUNCH_CHECK();
-            src = dst;
-            dst = (dst == c.qe0) ? c.qe1 : c.qe0;
-        }
-        hipLaunchKernelGGL(pchoose_all_kernel, dim3(H, n_layers), dim3(64), 0, m.stream, src, c.d_kenergy, M, M / H, m.mma_ebias,
-                           cfg.mma_temperature, c.d_pchoose);
-        SC_LAUNCH_CHECK();
-    }
-    if (project) {
-        SC_CHECK(W.embed_p, "decoder_step2: the fused vocabulary projection needs the packed embedding of this decoder stack");
-        GemvPArgs v;
-        v.Wp = W.embed_p;
-        v.Ah = c.hH;
-        v.Al = c.hL;
-        v.RB = c.rb;
-        v.M = nb;
-        v.N = W.vocab;
-        v.K = M;
-        v.splits = 1;
-        v.ntl = c.am_ntl;
-        v.epi = EPI_ARGMAX;
-        v.am_part = c.am_part;
-        v.am_tiles_cap = c.am_tiles;
-        v.am_eos_logit = c.am_eos_logit;
-        v.am_pos = c.d_pos;
-        v.am_min_step_for_eos = c.min_seq_len;
-        v.am_force_eos_step = c.force_eos_step;
-        v.am_pad_idx = W.pad_idx;
-        v.am_eos_idx = W.eos_idx;
-        v.am_unk_idx = W.unk_idx;
-        v.am_unk_penalty = c.unk_penalty;
-        launch_gemvp(v, m.stream);
-        launch_argmax_finalize(c.am_part, gemvp_argmax_tiles(W.vocab, c.am_ntl), nb, c.am_eos_logit, c.d_pos,
-                               c.force_eos_step, W.pad_idx, W.eos_idx, c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len,
-                               c.d_score, m.stream);
-    }
-    launch_add_i32(c.d_pos, 1, m.stream);
-}
-
-}  // namespace
-
-// ---- third-generation step (k_dstep3.hip) ---------------------------------------------------------------------
-// 9 launches per layer: QKV (packed product, K-range partials) | self-attention | out-proj (+bias +residual inside) |
-// q (LayerNorm inside) | cross-attention | out-proj (+bias +residual inside) | FFN-in (LayerNorm inside, ReLU, planes) |
-// FFN-out (K-slice partials) | reduce + bias + residual + the NEXT LayerNorm as planes (after the last layer: the decoder output).
-bool step3_eligible(const Model& m, const DecStack& W, int nb) {
-    static const bool off = knob::is_set("SC_DECODER_GEN2");  // A/B switch: the second-generation chain
-    if (off || !step2_eligible(m, W, nb)) return false;
-    const int M = m.cfg.model_dim;
-    return gemv3_supported(nb, 3 * M, M, IN3_LN) && gemv3_supported(nb, M, W.ffn_dim, IN3_PLANES) && M % 8 == 0;
-}
-
-// > 64 live rows (beam search at the benchmark batch: 64 utterances x 5 beams): the same chain, every product cut into row
-// groups, q | k | v on the row-group kernel too (the packed split-K product stops at 64 rows)
-bool step3_wide_eligible(const Model& m, const DecStack& W, int nb) {
-    static const bool off = knob::is_set("SC_DECODER_GEN2") || knob::is_set("SC_DECODER_GEN1");
-    const int M = m.cfg.model_dim;
-    if (off || nb <= 64 || nb > 512 || M % 64 != 0 || M > 1024 || W.ffn_dim % 64 != 0 || M != m.cfg.num_heads * 64) return false;
-    for (const DecoderLayer& l : *W.layers)
-        if (!l.qkv.wp || !l.self_out.wp || !l.cross_q.wp || !l.cross_out.wp || !l.ffn_in.wp || !l.ffn_out.wp) return false;
-    return gemv3_supported(nb, 3 * M, M, IN3_PLANES) && gemv3_supported(nb, M, W.ffn_dim, IN3_PLANES) &&
-           gemv3_supported(nb, M, M, IN3_LN) && gemv3_supported(nb, W.ffn_dim, M, IN3_LN);  // the LayerNorm-fused q / FFN-in launches
-}
-
-// THE dispatch decision (setup_session, run_generate_beam, the streaming step and decoder_step_family's report all call this
-// and nothing else composes the predicates): which kernel family a step of `rows` rows over stack W runs on for caller
-// 0 greedy generation, 1 / 3 beam search (text / v1 unit decoder), 2 the streaming monotonic step, 4 the teacher-forced
-// stepwise pass.  SC_STEP_GENERAL 1, SC_STEP_PACKED 2, SC_STEP_ROWGROUP 3, SC_STEP_ROWGROUP_WIDE 4 (model.h).
-int choose_family(const Model& m, const DecStack& W, int rows, int caller) {
-    const int M = m.cfg.model_dim;
-    if (caller == 2) return step2_eligible(m, W, 1) ? 2 : 1;
-    if (caller == 0 || caller == 4) {
-        const bool forced = caller == 4;
-        // the packed step projects through the packed embedding (a failed pack leaves it null: first-generation step then)
-        const bool gen2 = step2_eligible(m, W, rows) && (forced || W.embed_p != nullptr);
-        const bool fused_argmax = !forced && rows <= 64 && M % 64 == 0;
-        const bool gen3 = gen2 && step3_eligible(m, W, rows) && (forced || (fused_argmax && W.embed_p && vocab3_supported(rows, W.vocab, M)));
-        if (W.ffn_act == ACT_GELU) return gen3 ? 3 : 1;  // the packed chain's FFN epilogue knows ReLU only
-        return gen3 ? 3 : (gen2 ? 2 : 1);
-    }
-    // beam search: packed-weight step kernels up to 64 live rows, the wide row-group chain above
-    const bool packed = step2_eligible(m, W, rows) || step3_wide_eligible(m, W, rows);
-    if (!packed) return 1;
-    if (rows > 64) return 4;
-    if (W.ffn_act == ACT_GELU) return step3_eligible(m, W, rows) ? 3 : 1;
-    return step3_eligible(m, W, rows) ? 3 : 2;
-}
-
-namespace {
-
-
-static int env_int(const char* name, int dflt) {
-    return knob::value(name, dflt);
-}
-
-void decoder_step3(Model& m, StepCtx& c, bool project, const DecStack& W) {
-    const sc_config& cfg = m.cfg;
-    const int M = cfg.model_dim, nb = c.nb, H = cfg.num_heads;
-    const std::vector<DecoderLayer>& layers = *W.layers;
-    const int n_layers = (int)layers.size();
-    launch_embed3(c.d_tok, W.embed, sqrtf((float)M), W.pos, c.d_pos, c.xg, c.rb, nb, M, m.stream, c.slot_rp, c.slot_rp ? c.d_rows : nullptr);
-    launch_ln3(c.xg, c.rb, layers[0].self_ln.g, layers[0].self_ln.b, c.hH, c.hL, c.rb, nb, M, m.stream);
-    auto out_resid = [&](const Linear& L) {  // x += att . W^T + b, finished inside the product
-        Gemv3Args a;
-        a.Wp = L.wp, a.M = nb, a.N = L.out, a.K = L.in;
-        a.in_mode = IN3_PLANES, a.Ah = c.attH, a.Al = c.attL, a.RB = c.rb, a.rg = c.rg_small;
-        a.epi = EPI3_RESID, a.bias = L.b, a.xres = c.xg, a.XRB = c.rb;
-        a.d_rows = c.d_rows;
-        launch_gemv3(a, m.stream);
-    };
-    // x += bias + partials; h = LayerNorm(x) as planes: the K-slice products' closing launch
-    auto reduce_ln3 = [&](int S, const float* bias, const LNorm& ln, bool decoder_output) {
-        Reduce3Args r;
-        r.partial = c.partial, r.S = S, r.bias = bias, r.xg = c.xg, r.XRB = c.rb, r.rows = nb, r.C = M;
-        r.gamma = ln.g, r.beta = ln.b, r.Hh = c.hH, r.Hl = c.hL, r.RB = c.rb;
-        r.d_rows = c.d_rows;
-        if (decoder_output) {  // also fp32 rows (c.hN) and the per-position capture (the reference's teacher-forced pass)
-            r.hrow = c.dec_hidden, r.hrow_bs = (int64_t)(c.cap - 1) * M, r.hrow_rows = c.dec_hidden ? c.cap - 1 : 0, r.d_pos = c.d_pos;
-            r.hfix = c.hN;
-            r.slot_rp = c.slot_rp;
-        }
-        launch_reduce3(r, m.stream);
-    };
-    for (int li = 0; li < n_layers; ++li) {
-        const DecoderLayer& l = layers[li];
-        const bool last = li + 1 == n_layers;
-        int sp = 1;
-        DAttnArgs a;
-        if (nb <= 64 || c.slot_rp) {
-            // self attention: q | k | v as K-range partials of the packed product (summed by the attention kernel); the decode
-            // engine keeps this product above 64 slots too (in blocks of 64 rows): a row gets the bits it gets in a 64-slot step
-            gemv2(m, c, c.hH, c.hL, l.qkv, 2, &sp);
-            a.q = c.partial;
-            a.sstride = (int64_t)nb * 3 * M;
-            a.S = sp;
-            a.bias = l.qkv.b;
-        } else {  // wide step: complete rows from the row-group kernel
-            Gemv3Args q;
-            q.Wp = l.qkv.wp, q.M = nb, q.N = 3 * M, q.K = M;
-            q.in_mode = IN3_PLANES, q.Ah = c.hH, q.Al = c.hL, q.RB = c.rb, q.rg = 32;
-            q.epi = EPI3_ROWS, q.bias = l.qkv.b, q.out = c.qkv3, q.ldo = 3 * M;
-            q.d_rows = c.d_rows;
-            launch_gemv3(q, m.stream);
-            a.q = c.qkv3;
-            a.sstride = 0;
-            a.S = 1;
-            a.bias = nullptr;
-        }
-        a.ldq = 3 * M;
-        a.koff = M;
-        a.voff = 2 * M;
-        a.kcache = c.kcache[li];
-        a.vcache = c.vcache[li];
-        a.cache_ld = M;
-        a.cache_bs = (int64_t)c.cap * M;
-        a.cap = c.cap;
-        a.d_pos = c.d_pos;
-        a.Oh = c.attH;
-        a.Ol = c.attL;
-        a.ORB = c.rb;
-        a.nb = nb;
-        a.heads = H;
-        a.anc = c.anc;
-        a.d_rows = c.d_rows;
-        a.slot_rp = c.slot_rp;
-        a.slot_lane = c.slot_lane;
-        launch_dattn(a, /*cross=*/false, m.stream);
-        out_resid(l.self_out);
-        // encoder-decoder attention: the query projection applies its LayerNorm itself
-        {
-            Gemv3Args q;
-            q.Wp = l.cross_q.wp, q.M = nb, q.N = M, q.K = M;
-            q.in_mode = IN3_LN, q.xg = c.xg, q.gamma = l.cross_ln.g, q.beta = l.cross_ln.b, q.RB = c.rb, q.rg = c.rg_small;
-            q.epi = EPI3_ROWS, q.bias = l.cross_q.b, q.out = c.qkvr, q.ldo = M;
-            q.d_rows = c.d_rows;
-            launch_gemv3(q, m.stream);
-        }
-        DAttnArgs x;
-        x.q = c.qkvr;
-        x.ldq = M;
-        x.sstride = 0;
-        x.S = 1;
-        x.bias = nullptr;  // added by the projection
-        x.kcache = c.cross_kv[li];
-        x.vcache = c.cross_kv[li] + M;
-        x.cache_ld = 2 * M;
-        x.cache_bs = (int64_t)c.s_enc * 2 * M;
-        x.cap = c.s_enc;
-        x.kv_lens = c.d_enc_lens;
-        x.kv_row_div = c.cross_row_div;
-        x.kv_item = c.kv_item;
-        x.d_rows = c.d_rows;
-        x.Oh = c.attH;
-        x.Ol = c.attL;
-        x.ORB = c.rb;
-        x.nb = nb;
-        x.heads = H;
-        x.slot_rp = c.slot_rp;
-        launch_dattn(x, /*cross=*/true, m.stream);
-        // feed-forward network: the inner activation stays in split planes
-        if (c.ffn_in_mode == 0 && nb <= 64 && W.ffn_act != ACT_GELU) {  // (the packed product knows no GELU) K-range partials + reduce / LayerNorm launch, then the packed product on planes
-            gemv2(m, c, c.attH, c.attL, l.cross_out, 4, &sp);
-            reduce_ln3(sp, l.cross_out.b, l.ffn_ln, false);
-            GemvPArgs f;
-            f.Wp = l.ffn_in.wp, f.Ah = c.hH, f.Al = c.hL, f.RB = c.rb, f.M = nb, f.N = W.ffn_dim, f.K = M;
-            f.splits = 1, f.epi = EPI_PLANES, f.bias = l.ffn_in.b, f.act = ACT_RELU;
-            f.Oh = c.wideH, f.Ol = c.wideL, f.ORB = c.rb;
-            launch_gemvp(f, m.stream);
-        } else {  // the out-projection finishes x itself, FFN-in applies the LayerNorm itself
-            out_resid(l.cross_out);
-            {
-                Gemv3Args f;
-                f.Wp = l.ffn_in.wp, f.M = nb, f.N = W.ffn_dim, f.K = M;
-                f.in_mode = IN3_LN, f.xg = c.xg, f.gamma = l.ffn_ln.g, f.beta = l.ffn_ln.b, f.RB = c.rb, f.rg = c.rg_ffn;
-                // (a GELU stack under SC_D3_FFN_IN=0 lands here too: it takes the default's shape, not the one-tile shape of mode 2)
-                const bool gelu_mode0 = c.ffn_in_mode == 0 && nb <= 64 && W.ffn_act == ACT_GELU;
-                f.shape = (c.ffn_in_mode == 1 || gelu_mode0) ? G3_T2K8 : G3_T1;
-                f.epi = EPI3_PLANES, f.bias = l.ffn_in.b, f.act = W.ffn_act, f.Oh = c.wideH, f.Ol = c.wideL, f.ORB = c.rb;
-                f.d_rows = c.d_rows;
-                launch_gemv3(f, m.stream);
-            }
-        }
-        if (c.ffn_out_mode == 0 && nb <= 64) {
-            gemv2(m, c, c.wideH, c.wideL, l.ffn_out, 8, &sp);
-        } else {
-            Gemv3Args o;
-            o.Wp = l.ffn_out.wp, o.M = nb, o.N = M, o.K = W.ffn_dim;
-            o.in_mode = IN3_PLANES, o.Ah = c.wideH, o.Al = c.wideL, o.RB = c.rb, o.mt2 = 1;
-            o.shape = c.ffn_out_mode == 1 ? G3_T2K4 : G3_T1;
-            o.epi = EPI3_PARTIAL, o.out = c.partial;
-            o.d_rows = c.d_rows;
-            launch_gemv3(o, m.stream);
-            sp = gemv3_splits(W.ffn_dim, o.shape);
-        }
-        reduce_ln3(sp, l.ffn_out.b, last ? *W.final_ln : layers[li + 1].self_ln, last);
-    }
-    if (project) {
-        Vocab3Args v;
-        v.Wp = W.embed_p, v.Ah = c.hH, v.Al = c.hL, v.RB = c.rb, v.M = nb, v.N = W.vocab, v.K = M;
-        v.am_part = c.am_part, v.am_tiles_cap = c.am_tiles, v.am_eos_logit = c.am_eos_logit, v.am_pos = c.d_pos;
-        v.am_min_step_for_eos = c.min_seq_len, v.am_force_eos_step = c.force_eos_step;
-        v.am_pad_idx = W.pad_idx, v.am_eos_idx = W.eos_idx, v.am_unk_idx = W.unk_idx, v.am_unk_penalty = c.unk_penalty;
-        v.d_rows = c.d_rows;
-        v.slot_rp = c.slot_rp, v.limit_row = c.limit_row;
-        launch_vocab3(v, m.stream);
-        if (c.slot_rp) {  // decode engine: per-row rules and positions (the closing launch advances them)
-            EngineFinalizeArgs f;
-            f.part = c.am_part, f.tiles = vocab3_groups(nb), f.slots = nb, f.eos_logit = c.am_eos_logit;
-            f.slot_rp = c.slot_rp, f.d_rows = c.d_rows, f.pad_idx = W.pad_idx, f.eos_idx = W.eos_idx;
-            f.rows.tok = c.d_tok, f.rows.pos = c.pos_row, f.rows.finished = c.d_finished, f.rows.out_len = c.d_out_len;
-            f.rows.limit = c.limit_row, f.rows.prefix_len = c.prefix_row, f.rows.enc_lens = c.d_enc_lens, f.rows.score = c.d_score;
-            f.rows.hist = c.d_hist, f.rows.hidden = c.dec_hidden, f.rows.cap = c.cap, f.rows.M = M;
-            launch_engine_finalize(f, m.stream);
-            return;
-        }
-        launch_argmax_finalize(c.am_part, vocab3_groups(nb), nb, c.am_eos_logit, c.d_pos, c.force_eos_step, W.pad_idx, W.eos_idx,
-                               c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len, c.d_score, m.stream);
-    }
-    SC_CHECK(!c.slot_rp, "decoder step: the decode engine's step always projects");
-    launch_add_i32(c.d_pos, 1, m.stream);
-}
-
-}  // namespace
-
-// Which kernel family a decoder step of `rows` live rows runs on, decided by the SAME predicates the callers use (the
-// dispatch matrix in one place; tests/test_dispatch_gpu.py pins it).  caller: 0 greedy text generation (setup_session),
-// 1 beam search over the text decoder, 2 the streaming monotonic decoder's step, 3 beam search over the v1 unit decoder,
-// 4 teacher-forced stepwise pass.  Returns SC_STEP_GENERAL (1: split-K skinny products up to 64 rows, tiled GEMMs above),
-// SC_STEP_PACKED (2: packed-fragment products, k_dstep.hip), SC_STEP_ROWGROUP (3: row-group products with fused LayerNorm /
-// residual, k_dstep3.hip) or SC_STEP_ROWGROUP_WIDE (4: the same chain cut into row groups, > 64 rows).
-int decoder_step_family(const Model& m, int rows, int caller) {
-    if (caller == 2) {
-        if (m.mma_dec.empty()) return SC_ERR_INVALID;
-        return choose_family(m, mma_stack(m), 1, 2);
-    }
-    if (caller == 3 && m.t2u_ar_dec.empty()) return SC_ERR_INVALID;
-    return choose_family(m, caller == 3 ? t2u_ar_stack(m) : unity_stack(m), rows, caller);
-}
-
-// One decoder step for all batch rows: feeds d_tok at position *d_pos.
-void decoder_step(Model& m, StepCtx& c, bool project) {
-    const sc_config& cfg = m.cfg;
-    const int M = cfg.model_dim, nb = c.nb;
-    const DecStack own = unity_stack(m);
-    const DecStack& W = c.stack ? *c.stack : own;
-    if (c.gen3) {
-        decoder_step3(m, c, project, W);
-        return;
-    }
-    if (c.rb > 0) {
-        decoder_step2(m, c, project, W);
-        return;
-    }
-    const std::vector<DecoderLayer>& layers = *W.layers;
-    const int n_layers = (int)layers.size();
-    launch_embed_tokens(c.d_tok, nb, W.embed, M, sqrtf((float)M), W.pos, c.d_pos, 0, c.x, M, m.stream);
-    layernorm(m, c.x, layers[0].self_ln, c.h, nb);
-    for (int li = 0; li < n_layers; ++li) {
-        const DecoderLayer& l = layers[li];
-        const bool last = li + 1 == n_layers;
-        int sp = 1;
-        // self attention: q/k/v partials are summed (+bias) by the attention kernel itself
-        if (proj_partials(m, c, c.h, M, l.qkv, &sp)) {
-            const int64_t stride = (int64_t)nb * 3 * M;
-            launch_decode_attention(c.partial, 3 * M, c.partial + M, c.partial + 2 * M, 3 * M, c.kcache[li], c.vcache[li], M,
-                                    (int64_t)c.cap * M, c.cap, c.att, M, nb, cfg.num_heads, c.d_pos, nullptr, 0, m.stream, sp,
-                                    stride, l.qkv.b, l.qkv.b ? l.qkv.b + M : nullptr, l.qkv.b ? l.qkv.b + 2 * M : nullptr);
-        } else {
-            linear(m, c.h, M, l.qkv, nullptr, 0, c.wide, 3 * M, nb, ACT_NONE, 1.f);
-            launch_decode_attention(c.wide, 3 * M, c.wide + M, c.wide + 2 * M, 3 * M, c.kcache[li], c.vcache[li], M,
-                                    (int64_t)c.cap * M, c.cap, c.att, M, nb, cfg.num_heads, c.d_pos, nullptr, 0, m.stream);
-        }
-        out_proj_res_ln(m, c, c.att, M, l.self_out, l.cross_ln, c.h);
-        if (c.pchoose) {  // monotonic decoder: p_choose of the normed cross-attention input (monotonic_decoder_layer.py:170-172)
-            const PChooseLayer& pc = (*W.pchoose)[li];
-            const float* qe = energy_mlp(m, pc.q, c.h, M, c.qe0, c.qe1, 1);
-            hipLaunchKernelGGL(pchoose_kernel, dim3(cfg.num_heads), dim3(64), 0, m.stream, qe, c.d_kenergy + (int64_t)li * M,
-                               M / cfg.num_heads, pc.energy_bias, cfg.mma_temperature, c.d_pchoose + (int64_t)li * cfg.num_heads);
-            SC_LAUNCH_CHECK();
-        }
-        // encoder-decoder attention over the K/V projected once per utterance
-        if (proj_partials(m, c, c.h, M, l.cross_q, &sp)) {
-            launch_decode_attention(c.partial, M, nullptr, nullptr, 0, c.cross_kv[li], c.cross_kv[li] + M, 2 * M,
-                                    (int64_t)c.s_enc * 2 * M, c.s_enc, c.att, M, nb, cfg.num_heads, nullptr, c.d_enc_lens, 1,
-                                    m.stream, sp, (int64_t)nb * M, l.cross_q.b, nullptr, nullptr);
-        } else {
-            linear(m, c.h, M, l.cross_q, nullptr, 0, c.wide, M, nb, ACT_NONE, 1.f);
-            launch_decode_attention(c.wide, M, nullptr, nullptr, 0, c.cross_kv[li], c.cross_kv[li] + M, 2 * M,
-                                    (int64_t)c.s_enc * 2 * M, c.s_enc, c.att, M, nb, cfg.num_heads, nullptr, c.d_enc_lens, 1,
-                                    m.stream);
-        }
-        out_proj_res_ln(m, c, c.att, M, l.cross_out, l.ffn_ln, c.h);
-        linear(m, c.h, M, l.ffn_in, nullptr, 0, c.wide, W.ffn_dim, nb, W.ffn_act, 1.f);
-        out_proj_res_ln(m, c, c.wide, W.ffn_dim, l.ffn_out, last ? *W.final_ln : layers[li + 1].self_ln, last ? c.hN : c.h);
-    }
-    if (c.dec_hidden) {
-        hipLaunchKernelGGL(store_hidden_kernel, dim3(nb), dim3(256), 0, m.stream, c.hN, c.dec_hidden, M, c.cap - 1, c.d_pos);
-        SC_LAUNCH_CHECK();
-    }
-    if (project) {
-        if (nb <= 64 && M % 64 == 0) {
-            // vocabulary projection with the arg-max folded into its epilogue: no logits in HBM
-            SkinnyArgs a;
-            a.A = c.hN;
-            a.lda = M;
-            a.W = W.embed;
-            a.ldw = M;
-            a.M = nb;
-            a.N = W.vocab;
-            a.K = M;
-            a.am_part = c.am_part;
-            a.am_tiles_cap = c.am_tiles;
-            a.am_eos_logit = c.am_eos_logit;
-            a.am_pos = c.d_pos;
-            a.am_min_step_for_eos = c.min_seq_len;
-            a.am_force_eos_step = c.force_eos_step;
-            a.am_pad_idx = W.pad_idx;
-            a.am_eos_idx = W.eos_idx;
-            a.am_unk_idx = W.unk_idx;
-            a.am_unk_penalty = c.unk_penalty;
-            launch_skinny(a, m.stream);
-            launch_argmax_finalize(c.am_part, c.am_tiles, nb, c.am_eos_logit, c.d_pos, c.force_eos_step, W.pad_idx,
-                                   W.eos_idx, c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len, c.d_score, m.stream);
-        } else {
-            Linear proj;
-            proj.w = W.embed;
-            proj.ldw = M;
-            proj.kpad = M;
-            proj.in = M;
-            proj.out = W.vocab;
-            linear(m, c.hN, M, proj, nullptr, 0, c.logits, W.vocab, nb, ACT_NONE, 1.f);
-            launch_argmax_rows(c.logits, W.vocab, nb, W.vocab, c.d_pos, c.min_seq_len,
-                               c.force_eos_step, W.pad_idx, W.eos_idx, W.unk_idx, c.unk_penalty, c.d_tok, c.d_lprob,
-                               m.stream);
-            launch_step_update(c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len, c.d_lprob, c.d_score, nb, c.d_pos,
-                               W.pad_idx, W.eos_idx, nullptr, m.stream);
-        }
-    }
-    launch_add_i32(c.d_pos, 1, m.stream);
-}
 
 // --------------------------------------------------------------------------------------------- //
 // Streaming monotonic decoder (cfg 5).  One row; the state lives in the handle between calls.
@@ -812,18 +75,6 @@ MmaWork mma_work(const Model& m, float* base, size_t* total) {
     w.pooled = take(M);
     w.hq = take((size_t)std::max(1, c.mma_layers) * M);
     if (total) *total = o;
-    return w;
-}
-
-DecStack mma_stack(const Model& m) {
-    DecStack w;
-    w.embed = m.mma_embed;
-    w.embed_p = m.mma_embed_p;
-    w.pos = m.text_pos;  // same sinusoidal table (builder.py:169-176: max_seq_len 4096, _legacy_pad_idx=1)
-    w.layers = &m.mma_dec;
-    w.final_ln = &m.mma_final_ln;
-    w.ffn_dim = m.cfg.mma_ffn_dim;
-    w.pchoose = &m.mma_pc;
     return w;
 }
 
@@ -877,9 +128,7 @@ void run_mma_begin(Model& m, const float* d_enc, int s_enc, int max_len) {
         int64_t src_ls = 0;
         for (int e = 0; e < E; ++e) {
             float* dst = (e + 1 == E) ? st.kenergy.get() : ((e & 1) ? w.qe1 : w.qe0);
-            hipLaunchKernelGGL(energy_level_kernel, dim3(cdiv(M, 32), L), dim3(256), 0, m.stream, m.mma_ke_w + (size_t)e * L,
-                               m.mma_ke_b + (size_t)e * L, m.mma_qe_ldw, src, src_ls, dst, M);
-            SC_LAUNCH_CHECK();
+            launch_energy_level(m, m.mma_ke_w + (size_t)e * L, m.mma_ke_b + (size_t)e * L, L, src, src_ls, dst);
             src = dst;
             src_ls = M;
         }
@@ -987,23 +236,15 @@ struct DecodeSession {
     float unk_penalty = 0.f;
     StepCtx c;
     Buf<int> ints;
-    Buf<float> fl, x, h, wide, att, hN, logits, partial, am_eos, hidden, xg, qkvr;
+    StepScratch scratch;
+    Buf<float> fl, logits, am_eos, hidden;
     Buf<float4> am_part;
     std::vector<Buf<float>> caches;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
     // cross-attention capture (sc_generate_text_capture): its own step graph (the step + the capture launch) and the buffers
     // that graph writes, allocated by the first capture call on this session; a plain call never replays this graph
     Buf<float> xattn, xlprob;  // [n][max_len][s_enc], [n][max_len]
     Buf<int> slot_tab;         // [n] utterance held by each row slot
-    hipGraph_t cgraph = nullptr;
-    hipGraphExec_t cexec = nullptr;
-    ~DecodeSession() {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (cexec) (void)hipGraphExecDestroy(cexec);
-        if (cgraph) (void)hipGraphDestroy(cgraph);
-    }
+    StepGraph graph, cgraph;   // declared last: gone before the buffers their nodes point into
 };
 
 void delete_decode_session(DecodeSession* s) { delete s; }
@@ -1036,40 +277,19 @@ void setup_session(Model& m, DecodeSession& S, int n, int max_len, int s_enc, bo
     c.d_score = S.fl.get() + n;
     const DecStack W = unity_stack(m);
     const int family = choose_family(m, W, n, forced ? 4 : 0);
-    const bool gen2 = family >= 2;
-    const int wideN = std::max(3 * M, cfg.dec_ffn_dim);
     const bool fused_argmax = !forced && n <= 64 && M % 64 == 0;
     S.fused_argmax = fused_argmax;
-    S.x = Buf<float>(m.pp(), (size_t)n * M);
-    S.h = Buf<float>(m.pp(), (size_t)n * M);
-    S.wide = Buf<float>(m.pp(), gen2 ? 4 : (size_t)n * wideN);
-    S.att = Buf<float>(m.pp(), (size_t)n * M);
-    S.hN = Buf<float>(m.pp(), (size_t)n * M);
+    init_step_scratch(m, S.scratch, c, W, n, family, StepTuning::from_knobs(n), /*wide_always=*/false);
     S.logits = Buf<float>(m.pp(), (forced || fused_argmax) ? 4 : (size_t)n * cfg.text_vocab_size);
-    // worst case: K/256 ranges of an [n][M] out-projection, or M/256 ranges of the [n][3M] q/k/v projection
-    S.partial = Buf<float>(m.pp(), (size_t)std::max(1, std::max(M, cfg.dec_ffn_dim) / 256) * n * 3 * M);
-    c.partial = S.partial;
-    const bool gen3 = family == 3;
-    if (gen2) {
-        alloc_step2(m, c, cfg.dec_ffn_dim);
+    c.logits = S.logits;
+    if (family >= 2) {
         c.am_ntl = 4;
         c.am_tiles = fused_argmax ? gemvp_argmax_tiles(cfg.text_vocab_size, c.am_ntl) : 0;
-        if (gen3) {
-            c.gen3 = true;
+        if (family == 3) {
             // greedy generation: the row-group kernels and the attention skip the row groups / rows behind *d_rows (= n until
             // the live-row compaction of run_generate_text lowers it); the captured step reads the counter on every replay
             if (!forced) c.d_rows = c.d_rows_greedy;
-            S.xg = Buf<float>(m.pp(), (size_t)M * c.rb);
-            S.qkvr = Buf<float>(m.pp(), (size_t)n * M);
-            c.xg = S.xg;
-            c.qkvr = S.qkvr;
             c.am_tiles = std::max(c.am_tiles, vocab3_groups(n));
-            // tuning knobs, read once per session and clamped to what the launches accept (an out-of-range value would
-            // otherwise only surface as a failed check inside a captured step)
-            c.rg_small = std::min(32, std::max(1, env_int("SC_D3_RG_SMALL", 16)));
-            c.rg_ffn = std::min(32, std::max(1, env_int("SC_D3_RG_FFN", 32)));
-            c.ffn_in_mode = std::min(2, std::max(0, env_int("SC_D3_FFN_IN", 1)));
-            c.ffn_out_mode = std::min(2, std::max(0, env_int("SC_D3_FFN_OUT", 1)));
         }
     } else {
         c.am_tiles = fused_argmax ? skinny_argmax_tiles(n, cfg.text_vocab_size) : 0;
@@ -1078,12 +298,6 @@ void setup_session(Model& m, DecodeSession& S, int n, int max_len, int s_enc, bo
     S.am_eos = Buf<float>(m.pp(), (size_t)n);
     c.am_part = S.am_part;
     c.am_eos_logit = S.am_eos;
-    c.x = S.x;
-    c.h = S.h;
-    c.wide = S.wide;
-    c.att = S.att;
-    c.hN = S.hN;
-    c.logits = S.logits;
     if (want_hidden) {
         S.hidden = Buf<float>(m.pp(), (size_t)n * (max_len - 1) * M);
         c.dec_hidden = S.hidden;
@@ -1454,37 +668,15 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
     // positions 0 .. feed_len-2 are fed without projection; the next input is read from hist.
     // teacher forcing over more than a few positions (the re-pass behind a beam search: ~40 steps of ~220 launches): the
     // step is captured once and replayed, like the generation step below
-    hipGraph_t fgraph = nullptr;
-    hipGraphExec_t fexec = nullptr;
-    struct FGuard {
-        hipGraph_t& g;
-        hipGraphExec_t& e;
-        ~FGuard() {
-            if (e) (void)hipGraphExecDestroy(e);
-            if (g) (void)hipGraphDestroy(g);
-        }
-    } fguard{fgraph, fexec};
+    StepGraph fgraph;
     const bool forced_graph = forced && o.use_graph != 0 && c.rb > 0 && feed_len >= 8;
     auto fed_step = [&]() {
         if (!forced_graph) {
             decoder_step(m, c, /*project=*/false);
             return;
         }
-        if (!fexec) {
-            std::lock_guard<std::mutex> lock(g_capture_mutex);
-            SC_HIP(hipStreamBeginCapture(m.stream, hipStreamCaptureModeThreadLocal));
-            try {
-                decoder_step(m, c, /*project=*/false);
-            } catch (...) {
-                hipGraph_t dead = nullptr;
-                (void)hipStreamEndCapture(m.stream, &dead);
-                if (dead) (void)hipGraphDestroy(dead);
-                throw;
-            }
-            SC_HIP(hipStreamEndCapture(m.stream, &fgraph));
-            SC_HIP(hipGraphInstantiate(&fexec, fgraph, nullptr, nullptr, 0));
-        }
-        SC_HIP(hipGraphLaunch(fexec, m.stream));
+        fgraph.ensure(m.stream, [&] { decoder_step(m, c, /*project=*/false); });
+        fgraph.launch(m.stream);
     };
     for (int t = 0; t + 1 < feed_len; ++t) {
         fed_step();
@@ -1524,40 +716,14 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
                 decoder_step(m, c, true);
                 capture_node(true);
             } else {
-                if (!S->cexec) {  // as the plain step graph below, with the capture launch at its end
-                    std::lock_guard<std::mutex> lock(g_capture_mutex);
-                    SC_HIP(hipStreamBeginCapture(m.stream, hipStreamCaptureModeThreadLocal));
-                    try {
-                        decoder_step(m, c, true);
-                        capture_node(true);
-                    } catch (...) {
-                        hipGraph_t dead = nullptr;
-                        (void)hipStreamEndCapture(m.stream, &dead);
-                        if (dead) (void)hipGraphDestroy(dead);
-                        throw;
-                    }
-                    SC_HIP(hipStreamEndCapture(m.stream, &S->cgraph));
-                    SC_HIP(hipGraphInstantiate(&S->cexec, S->cgraph, nullptr, nullptr, 0));
-                }
-                SC_HIP(hipGraphLaunch(S->cexec, m.stream));
+                S->cgraph.ensure(m.stream, [&] {  // as the plain step graph below, with the capture launch at its end
+                    decoder_step(m, c, true);
+                    capture_node(true);
+                });
+                S->cgraph.launch(m.stream);
             }
         } else if (use_graph) {
-            if (!S->exec) {
-                // Thread-local capture: another handle's host thread may allocate scratch (hipMalloc) while
-                // this one records; captures and instantiations are serialised process-wide.
-                std::lock_guard<std::mutex> lock(g_capture_mutex);
-                SC_HIP(hipStreamBeginCapture(m.stream, hipStreamCaptureModeThreadLocal));
-                try {
-                    decoder_step(m, c, true);
-                } catch (...) {
-                    hipGraph_t dead = nullptr;
-                    (void)hipStreamEndCapture(m.stream, &dead);
-                    if (dead) (void)hipGraphDestroy(dead);
-                    throw;
-                }
-                SC_HIP(hipStreamEndCapture(m.stream, &S->graph));
-                SC_HIP(hipGraphInstantiate(&S->exec, S->graph, nullptr, nullptr, 0));
-            }
+            S->graph.ensure(m.stream, [&] { decoder_step(m, c, true); });
             {
                 // one profiler record per replayed step (launches inside the graph cannot carry events): the algorithmic
                 // bytes of a step are the fp16 weights of the layers and of the tied projection, read once for all rows,
@@ -1566,7 +732,7 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
                                               (double)cfg.text_vocab_size * M);
                 const double kv_bytes = 4.0 * cfg.dec_layers * (double)n * M * (2.0 * (step + 1) + 2.0 * s_enc);
                 prof::Scope scope("step_graph", (double)n * w_bytes, w_bytes + kv_bytes, m.stream);
-                SC_HIP(hipGraphLaunch(S->exec, m.stream));
+                S->graph.launch(m.stream);
             }
         } else {
             decoder_step(m, c, true);
@@ -1712,42 +878,94 @@ void run_t2u_ar(Model& m, const float* d_dec_hidden, int n, int s_text, const in
     run_generate_beam(m, W, enc, n, s_text, h_text_lens, uo, h_prefix, prefix_len, h_out_ids, h_out_lens, h_scores, nullptr, max_len);
 }
 
+// ---- pieces shared with sampled generation (model_sample.hip) ------------------------------------------------------------
+void check_generation_limits(const char* who, const sc_gen_opts& o, int prefix_len, int max_len, int decoder_max_seq_len, int n, int s_enc,
+                             const int32_t* h_enc_lens) {
+    SC_CHECK(prefix_len >= 1, "%s: the prompt must hold at least one token", who);
+    SC_CHECK(o.min_seq_len <= max_len, "%s: min_seq_len %d > effective max length %d", who, o.min_seq_len, max_len);
+    SC_CHECK(prefix_len < max_len, "%s: prompt length %d >= effective max length %d", who, prefix_len, max_len);
+    SC_CHECK(max_len <= 4096 && max_len <= decoder_max_seq_len + 1, "%s: length %d exceeds the decoder limit", who, max_len);
+    SC_CHECK(s_enc <= 4096, "%s: encoder length %d > 4096", who, s_enc);
+    for (int i = 0; i < n; ++i)
+        SC_CHECK(h_enc_lens[i] > 0 && h_enc_lens[i] <= s_enc, "%s: enc_lens[%d]=%d out of range", who, i, h_enc_lens[i]);
+}
+
+// BannedSequenceProcessor: the list is checked on the host (before any launch) and copied to the device once per call
+BannedDevice upload_banned(Model& m, const BannedHost* banned, int V) {
+    BannedDevice d;
+    if (!banned || banned->n <= 0) return d;
+    validate_banned_host(banned->tokens, banned->offsets, banned->n, V, &d.list.max_len);
+    const int total = banned->offsets[banned->n];
+    d.store = Buf<int>(m.pp(), (size_t)total + banned->n + 1);
+    SC_HIP(hipMemcpyAsync(d.store.get(), banned->tokens, (size_t)total * 4, hipMemcpyHostToDevice, m.stream));
+    SC_HIP(hipMemcpyAsync(d.store.get() + total, banned->offsets, (size_t)(banned->n + 1) * 4, hipMemcpyHostToDevice, m.stream));
+    SC_HIP(hipStreamSynchronize(m.stream));  // the list is the caller's
+    d.list.tokens = d.store.get();
+    d.list.offsets = d.store.get() + total;
+    d.list.n = banned->n;
+    return d;
+}
+
+// fairseq2.cpp `_fan_out_encoder_output`: row r of the result is the encoder output of item r / per_item
+Buf<float> fan_out_encoder(Model& m, const float* d_enc, int n, int per_item, int s_enc) {
+    const int M = m.cfg.model_dim, nb = n * per_item;
+    Buf<float> enc_rep(m.pp(), (size_t)nb * s_enc * M);
+    std::vector<int32_t> idx((size_t)nb * s_enc);
+    for (int r = 0; r < nb; ++r)
+        for (int t = 0; t < s_enc; ++t) idx[(size_t)r * s_enc + t] = (r / per_item) * s_enc + t;
+    Buf<int> d_idx(m.pp(), idx.size());
+    SC_HIP(hipMemcpyAsync(d_idx.get(), idx.data(), idx.size() * 4, hipMemcpyHostToDevice, m.stream));
+    launch_gather_rows(d_enc, M, d_idx, enc_rep, M, nb * s_enc, M, m.stream);
+    SC_HIP(hipStreamSynchronize(m.stream));  // idx is a host temporary
+    return enc_rep;
+}
+
+void project_logits(Model& m, StepCtx& c, const DecStack& W, bool v3, int64_t ldl) {
+    const int M = m.cfg.model_dim;
+    if (v3) {
+        Vocab3Args v;
+        v.Wp = W.embed_p, v.Ah = c.hH, v.Al = c.hL, v.RB = c.rb, v.M = c.nb, v.N = W.vocab, v.K = M;
+        v.logits = c.logits, v.ldl = ldl;
+        v.d_rows = c.d_rows;
+        launch_vocab3(v, m.stream);
+    } else {
+        Linear proj;
+        proj.w = W.embed, proj.ldw = M, proj.kpad = M, proj.in = M, proj.out = W.vocab;
+        linear(m, c.hN, M, proj, nullptr, 0, c.logits, W.vocab, c.nb, ACT_NONE, 1.f);
+    }
+}
+
+void hidden_of_best(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o, const int32_t* h_ids,
+                    const int32_t* h_lens, int ids_stride, int max_len, int pad_idx, float* d_dec_hidden) {
+    const int M = m.cfg.model_dim;
+    int longest = 0;
+    for (int u = 0; u < n; ++u) longest = std::max(longest, h_lens[(size_t)u * ids_stride]);
+    const int fl = longest - 1;  // text_seqs[:, :-1]
+    std::vector<int32_t> forced((size_t)n * fl, pad_idx);
+    for (int u = 0; u < n; ++u)
+        for (int t = 0; t < fl && t < h_lens[(size_t)u * ids_stride]; ++t) forced[(size_t)u * fl + t] = h_ids[(size_t)u * ids_stride * max_len + t];
+    Buf<float> hid(m.pp(), (size_t)n * fl * M);
+    run_generate_text(m, d_enc, n, s_enc, h_enc_lens, o, nullptr, 0, nullptr, nullptr, nullptr, hid, forced.data(), fl);
+    SC_HIP(hipMemsetAsync(d_dec_hidden, 0, (size_t)n * (max_len - 1) * M * 4, m.stream));
+    SC_HIP(hipMemcpy2DAsync(d_dec_hidden, (size_t)(max_len - 1) * M * 4, hid.get(), (size_t)fl * M * 4, (size_t)fl * M * 4, n,
+                            hipMemcpyDeviceToDevice, m.stream));
+    SC_HIP(hipStreamSynchronize(m.stream));
+}
+
 // Beam search over one decoder stack (the UnitY text decoder or the v1 autoregressive unit decoder).
 void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                        const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
                        float* d_dec_hidden, int max_len, const BannedHost* banned, int prefix_stride) {
     // prefix_stride: 0 = one prompt for all; otherwise utterance u's prompt is h_prefix[u * prefix_stride + ...], fed to each of its beams
-    struct VocabView {  // the names the body used for the text vocabulary, now the stack's
-        int pad_idx, unk_idx, eos_idx, text_max_seq_len, model_dim, dec_ffn_dim;
-    };
-    const VocabView cfg{W.pad_idx, W.unk_idx, W.eos_idx, W.max_seq_len, m.cfg.model_dim, W.ffn_dim};
     const std::vector<DecoderLayer>& dec_layers = *W.layers;
-    const int M = cfg.model_dim, V = W.vocab, B = o.beam_size, L = (int)dec_layers.size();
+    const int M = m.cfg.model_dim, V = W.vocab, B = o.beam_size, L = (int)dec_layers.size();
     const int nb = n * B;
     const int K = std::min(2 * B, V - 1);
     SC_CHECK(B <= 8, "sc_generate_text: beam_size %d > 8", B);
-    SC_CHECK(prefix_len >= 1, "sc_generate_text: the prompt must hold at least one token");
     SC_CHECK(d_dec_hidden == nullptr || W.layers == &m.dec, "beam search: decoder outputs are captured for the text decoder only");
-    SC_CHECK(o.min_seq_len <= max_len, "sc_generate_text: min_seq_len %d > effective max length %d", o.min_seq_len, max_len);
-    SC_CHECK(prefix_len < max_len, "sc_generate_text: prompt length %d >= effective max length %d", prefix_len, max_len);
-    SC_CHECK(max_len <= 4096 && max_len <= cfg.text_max_seq_len + 1, "sc_generate_text: length %d exceeds the decoder limit", max_len);
-    SC_CHECK(s_enc <= 4096, "sc_generate_text: encoder length %d > 4096", s_enc);
-    for (int i = 0; i < n; ++i)
-        SC_CHECK(h_enc_lens[i] > 0 && h_enc_lens[i] <= s_enc, "sc_generate_text: enc_lens[%d]=%d out of range", i, h_enc_lens[i]);
-    // BannedSequenceProcessor: the list is checked on the host (before any launch) and copied to the device once per call
-    BannedList bl;
-    Buf<int> d_banned(m.pp(), 4);
-    if (banned && banned->n > 0) {
-        validate_banned_host(banned->tokens, banned->offsets, banned->n, V, &bl.max_len);
-        const int total = banned->offsets[banned->n];
-        d_banned = Buf<int>(m.pp(), (size_t)total + banned->n + 1);
-        SC_HIP(hipMemcpyAsync(d_banned.get(), banned->tokens, (size_t)total * 4, hipMemcpyHostToDevice, m.stream));
-        SC_HIP(hipMemcpyAsync(d_banned.get() + total, banned->offsets, (size_t)(banned->n + 1) * 4, hipMemcpyHostToDevice, m.stream));
-        SC_HIP(hipStreamSynchronize(m.stream));  // the list is the caller's
-        bl.tokens = d_banned.get();
-        bl.offsets = d_banned.get() + total;
-        bl.n = banned->n;
-    }
+    check_generation_limits("sc_generate_text", o, prefix_len, max_len, W.max_seq_len, n, s_enc, h_enc_lens);
+    const BannedDevice banned_dev = upload_banned(m, banned, V);
+    const BannedList& bl = banned_dev.list;
     const float len_penalty = o.len_penalty;
     const bool normalize = o.normalize_scores != 0;
 
@@ -1755,17 +973,8 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
     // utterance instead of one per beam (5 x fewer bytes to project, to keep and to stream per step)
     const int family = choose_family(m, W, nb, 1);  // (the v1 unit decoder's search decides the same way: callers 1 and 3)
     const bool packed_step = family != 1;
-    // ---- fan the encoder output out to the beams (fairseq2.cpp `_fan_out_encoder_output`) ----------
-    Buf<float> enc_rep(m.pp(), packed_step ? 4 : (size_t)nb * s_enc * M);
-    if (!packed_step) {
-        std::vector<int32_t> idx((size_t)nb * s_enc);
-        for (int r = 0; r < nb; ++r)
-            for (int t = 0; t < s_enc; ++t) idx[(size_t)r * s_enc + t] = (r / B) * s_enc + t;
-        Buf<int> d_idx(m.pp(), idx.size());
-        SC_HIP(hipMemcpyAsync(d_idx.get(), idx.data(), idx.size() * 4, hipMemcpyHostToDevice, m.stream));
-        launch_gather_rows(d_enc, M, d_idx, enc_rep, M, nb * s_enc, M, m.stream);
-        SC_HIP(hipStreamSynchronize(m.stream));  // idx is a host temporary
-    }
+    Buf<float> enc_rep;  // the general step: the encoder output fanned out to the beams
+    if (!packed_step) enc_rep = fan_out_encoder(m, d_enc, n, B, s_enc);
 
     StepCtx c;
     c.stack = &W;
@@ -1782,42 +991,14 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
     c.d_out_len = c.d_finished + nb;
     c.d_enc_lens = c.d_out_len + nb;
     int* d_src_row = c.d_enc_lens + nb;
-    const int wideN = std::max(3 * M, cfg.dec_ffn_dim);
-    Buf<float> x(m.pp(), (size_t)nb * M), h(m.pp(), (size_t)nb * M), wide(m.pp(), (size_t)nb * wideN), att(m.pp(), (size_t)nb * M),
-        hN(m.pp(), (size_t)nb * M), logits(m.pp(), (size_t)nb * (V + 3));
-    Buf<float> partial(m.pp(), (size_t)std::max(1, std::max(M, cfg.dec_ffn_dim) / 256) * nb * 3 * M);
+    // packed-weight step kernels up to 64 live rows, the wide third-generation chain up to 512 (the step runs without its
+    // projection here)
+    StepScratch scratch;
+    init_step_scratch(m, scratch, c, W, nb, family, StepTuning::from_knobs(nb));
+    Buf<float> logits(m.pp(), (size_t)nb * (V + 3));
     Buf<float> d_cum(m.pp(), (size_t)nb), d_cand_val(m.pp(), (size_t)n * K), d_pref(m.pp(), (size_t)n);
     Buf<int> d_cand_idx(m.pp(), (size_t)n * K);
-    c.partial = partial;
-    c.x = x;
-    c.h = h;
-    c.wide = wide;
-    c.att = att;
-    c.hN = hN;
     c.logits = logits;
-    Buf<float> xg3(m.pp(), 4), qkvr3(m.pp(), 4), qkv3w(m.pp(), 4);
-    if (packed_step) {  // packed-weight step kernels (<= 64 live rows; the wide third-generation chain up to 512)
-        alloc_step2(m, c, cfg.dec_ffn_dim);
-        if (family >= 3) {  // third-generation chain (the step runs without its projection here)
-            c.gen3 = true;
-            xg3 = Buf<float>(m.pp(), (size_t)M * c.rb);
-            qkvr3 = Buf<float>(m.pp(), (size_t)nb * M);
-            c.xg = xg3;
-            c.qkvr = qkvr3;
-            if (nb > 64) {
-                qkv3w = Buf<float>(m.pp(), (size_t)nb * 3 * M);
-                c.qkv3 = qkv3w;
-            }
-            // tuning knobs, read once per session and clamped to what the launches accept (an out-of-range value would
-            // otherwise only surface as a failed check inside a captured step)
-            // (N = 1024 products: 16-row groups are tuned for <= 64 rows; above 128 live rows 32-row groups halve the workgroups that
-            //  re-read a weight tile - same bits whatever the grouping, tests/test_dstep3_gpu.py)
-            c.rg_small = std::min(32, std::max(1, env_int("SC_D3_RG_SMALL", nb > 128 ? 32 : 16)));
-            c.rg_ffn = std::min(32, std::max(1, env_int("SC_D3_RG_FFN", 32)));
-            c.ffn_in_mode = std::min(2, std::max(0, env_int("SC_D3_FFN_IN", 1)));
-            c.ffn_out_mode = std::min(2, std::max(0, env_int("SC_D3_FFN_OUT", 1)));
-        }
-    }
     // vocabulary projection of the live rows: the LDS-staged streaming kernel on the packed embedding when the step left
     // the decoder output as split planes (<= 64 rows: at 60 rows the tiled GEMM needed ~10 ms per step, this one ~0.12)
     const bool proj_v3 = c.rb > 0 && W.embed_p != nullptr && vocab3_supported(nb, V, M);
@@ -1857,30 +1038,14 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
         c.cross_kv.push_back(cross.back());
         project_cross_kv(m, packed_step ? d_enc : enc_rep.get(), dec_layers[li].cross_kv, c.cross_kv.back(), cross_rows * s_enc);
     }
-    Linear proj;
-    proj.w = W.embed;
-    proj.ldw = M;
-    proj.kpad = M;
-    proj.in = M;
-    proj.out = V;
 
     const bool chunked = beam_chunked(V, B, K);  // large vocabulary: candidate search spread over (row, chunk) workgroups
     Buf<float> ws_f(m.pp(), chunked ? beam_ws_floats(nb, K) : 4);
     Buf<int> ws_i(m.pp(), chunked ? beam_ws_ints(nb, K) : 4);
-    auto project_rows = [&]() {
-        if (proj_v3) {
-            Vocab3Args v;
-            v.Wp = W.embed_p, v.Ah = c.hH, v.Al = c.hL, v.RB = c.rb, v.M = nb, v.N = V, v.K = M;
-            v.logits = c.logits, v.ldl = ldl;
-            v.d_rows = c.d_rows;
-            launch_vocab3(v, m.stream);
-        } else {
-            linear(m, c.hN, M, proj, nullptr, 0, c.logits, V, nb, ACT_NONE, 1.f);
-        }
-    };
+    auto project_rows = [&]() { project_logits(m, c, W, proj_v3, ldl); };
 
     // ---- search state: device resident (sequences, cumulative scores, finished hypotheses, counters) ----------
-    std::vector<int32_t> seqs((size_t)nb * max_len, cfg.pad_idx), init(8 + 5 * nb, 0), tok(nb);
+    std::vector<int32_t> seqs((size_t)nb * max_len, W.pad_idx), init(8 + 5 * nb, 0), tok(nb);
     std::vector<float> cum(nb, 0.f);
     for (int r = 0; r < nb; ++r) {
         const int32_t* pre = h_prefix + (size_t)(r / B) * prefix_stride;
@@ -1953,35 +1118,13 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
     // launching alone cost ~2.5 ms per step at 320 rows).  The K/V caches alternate between two allocations (re-ordered from
     // one into the other after every step), so there are two graphs, one per parity; everything the step reads besides its
     // baked-in buffer addresses lives in device memory (*d_pos, d_tok).
-    struct StepGraphs {
-        hipGraph_t g[2] = {nullptr, nullptr};
-        hipGraphExec_t e[2] = {nullptr, nullptr};
-        ~StepGraphs() {
-            for (int i = 0; i < 2; ++i) {
-                if (e[i]) (void)hipGraphExecDestroy(e[i]);
-                if (g[i]) (void)hipGraphDestroy(g[i]);
-            }
-        }
-    } graphs;
+    StepGraph graphs[2];
     const bool step_graph = o.use_graph != 0 && c.rb > 0;
     for (int step = start; step <= max_len - 2 && remaining > 0; ++step) {
         if (step_graph) {
-            const int par = kv_cur == kv_a.get() ? 0 : 1;
-            if (!graphs.e[par]) {
-                std::lock_guard<std::mutex> lock(g_capture_mutex);
-                SC_HIP(hipStreamBeginCapture(m.stream, hipStreamCaptureModeThreadLocal));
-                try {
-                    decoder_step(m, c, /*project=*/false);
-                } catch (...) {
-                    hipGraph_t dead = nullptr;
-                    (void)hipStreamEndCapture(m.stream, &dead);
-                    if (dead) (void)hipGraphDestroy(dead);
-                    throw;
-                }
-                SC_HIP(hipStreamEndCapture(m.stream, &graphs.g[par]));
-                SC_HIP(hipGraphInstantiate(&graphs.e[par], graphs.g[par], nullptr, nullptr, 0));
-            }
-            SC_HIP(hipGraphLaunch(graphs.e[par], m.stream));
+            StepGraph& g = graphs[kv_cur == kv_a.get() ? 0 : 1];
+            g.ensure(m.stream, [&] { decoder_step(m, c, /*project=*/false); });
+            g.launch(m.stream);
         } else {
             decoder_step(m, c, /*project=*/false);  // feeds d_tok at position `step`, advances *d_pos
         }
@@ -1990,12 +1133,12 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
         const bool ban = (G > 0 || bl.n > 0) && step != max_len - 2;
         if (chunked) {
             launch_beam_candidates_chunked(c.logits, ldl, n, B, V, d_cum, step == start, step < o.min_seq_len, step == max_len - 2,
-                                           cfg.pad_idx, cfg.eos_idx, cfg.unk_idx, o.unk_penalty, K, d_cand_val, d_cand_idx,
+                                           W.pad_idx, W.eos_idx, W.unk_idx, o.unk_penalty, K, d_cand_val, d_cand_idx,
                                            ban ? d_seqs_cur : nullptr, max_len, step + 1, G, ws_f, ws_i, m.stream,
                                            compact ? d_rows_live : nullptr, compact ? d_slots : nullptr, bl.n > 0 ? &bl : nullptr);
         } else {
-            launch_beam_candidates(c.logits, ldl, n, B, V, d_cum, step == start, step < o.min_seq_len, step == max_len - 2, cfg.pad_idx,
-                                   cfg.eos_idx, cfg.unk_idx, o.unk_penalty, K, d_cand_val, d_cand_idx, ban ? d_seqs_cur : nullptr, max_len,
+            launch_beam_candidates(c.logits, ldl, n, B, V, d_cum, step == start, step < o.min_seq_len, step == max_len - 2, W.pad_idx,
+                                   W.eos_idx, W.unk_idx, o.unk_penalty, K, d_cand_val, d_cand_idx, ban ? d_seqs_cur : nullptr, max_len,
                                    step + 1, G, m.stream, compact ? d_slots : nullptr, bl.n > 0 ? &bl : nullptr);
         }
         BeamSelectArgs a;
@@ -2017,8 +1160,8 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
         a.V = V;
         a.max_len = max_len;
         a.step = step;
-        a.eos_idx = cfg.eos_idx;
-        a.pad_idx = cfg.pad_idx;
+        a.eos_idx = W.eos_idx;
+        a.pad_idx = W.pad_idx;
         a.normalize = normalize ? 1 : 0;
         a.len_penalty = len_penalty;
         a.anc = use_anc ? d_anc.get() : nullptr;
@@ -2054,7 +1197,6 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
     SC_HIP(hipMemcpyAsync(fin_score.data(), d_fin_score.get(), fin_score.size() * 4, hipMemcpyDeviceToHost, m.stream));
     SC_HIP(hipMemcpyAsync(fin_count.data(), d_fin_count, (size_t)n * 4, hipMemcpyDeviceToHost, m.stream));
     SC_HIP(hipStreamSynchronize(m.stream));
-    int longest = 0;
     for (int u = 0; u < n; ++u) {
         SC_CHECK(fin_count[u] > 0, "sc_generate_text: beam search returned no hypothesis for item %d", u);
         // the order of the candidate search (k_beam.hip order_key): NaN first, then the higher score, ties to the earlier one
@@ -2065,24 +1207,12 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
         }
         const int len = fin_len[u * B + best];
         const int32_t* hs = &fin_seq[(size_t)(u * B + best) * max_len];
-        for (int t = 0; t < max_len; ++t) h_out_ids[(size_t)u * max_len + t] = t < len ? hs[t] : cfg.pad_idx;
+        for (int t = 0; t < max_len; ++t) h_out_ids[(size_t)u * max_len + t] = t < len ? hs[t] : W.pad_idx;
         h_out_lens[u] = len;
         if (h_scores) h_scores[u] = fin_score[u * B + best];
-        longest = std::max(longest, len);
     }
     // ---- decoder outputs of the chosen hypotheses: the reference's teacher-forced pass (generator.py:281-299)
-    if (d_dec_hidden) {
-        const int fl = longest - 1;  // text_seqs[:, :-1]
-        std::vector<int32_t> forced((size_t)n * fl, cfg.pad_idx);
-        for (int u = 0; u < n; ++u)
-            for (int t = 0; t < fl && t < h_out_lens[u]; ++t) forced[(size_t)u * fl + t] = h_out_ids[(size_t)u * max_len + t];
-        Buf<float> hid(m.pp(), (size_t)n * fl * M);
-        run_generate_text(m, d_enc, n, s_enc, h_enc_lens, o, nullptr, 0, nullptr, nullptr, nullptr, hid, forced.data(), fl);
-        SC_HIP(hipMemsetAsync(d_dec_hidden, 0, (size_t)n * (max_len - 1) * M * 4, m.stream));
-        SC_HIP(hipMemcpy2DAsync(d_dec_hidden, (size_t)(max_len - 1) * M * 4, hid.get(), (size_t)fl * M * 4, (size_t)fl * M * 4, n,
-                                hipMemcpyDeviceToDevice, m.stream));
-        SC_HIP(hipStreamSynchronize(m.stream));
-    }
+    if (d_dec_hidden) hidden_of_best(m, d_enc, n, s_enc, h_enc_lens, o, h_out_ids, h_out_lens, 1, max_len, W.pad_idx, d_dec_hidden);
 }
 
 }  // namespace sc

@@ -1,14 +1,13 @@
 // Sampled text generation (sc_generate_text_sampled): num_gens stochastic hypotheses per utterance, drawn with temperature and
 // top-k / top-p inside the step loop (fairseq2 0.2 SamplingSeq2SeqGenerator + TopKSampler / TopPSampler, restated).
-// A sibling of run_generate_beam (model_decoder.hip) on the same step chain: row u * num_gens + g is hypothesis g of utterance
-// u, the encoder K / V are projected once per utterance, and rows never change places - no ancestor table, no cache
-// re-ordering, a finished row rides along (its draws are skipped, its results are already stored).  Per step: decoder step,
+// A sibling of run_generate_beam (model_decoder.hip) on the same step chain and the same shared pieces (dstep.h): row
+// u * num_gens + g is hypothesis g of utterance u, the encoder K / V are projected once per utterance, and rows never change
+// places - no ancestor table, no cache re-ordering, a finished row rides along (its draws are skipped).  Per step: decoder step,
 // vocabulary projection, ONE sampling launch (k_sample.hip: log-softmax under the temperature, step processors, step rules,
 // kept set, draw, and the bookkeeping of the row: sequence, next token, cumulative score, finished flag).  The host polls the
 // count of unfinished rows every fourth step.
 #include <algorithm>
 #include <cmath>
-#include <mutex>
 
 #include "dstep.h"
 #include "engine.h"
@@ -33,41 +32,17 @@ void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const 
     SC_CHECK(o.no_repeat_ngram_size >= 0, "sc_generate_text_sampled: no_repeat_ngram_size=%d", o.no_repeat_ngram_size);
     const int nb = n * B;
     const int max_len = text_max_len(m, o, s_enc);
-    SC_CHECK(prefix_len >= 1, "sc_generate_text_sampled: the prompt must hold at least one token");
-    SC_CHECK(o.min_seq_len <= max_len, "sc_generate_text_sampled: min_seq_len %d > effective max length %d", o.min_seq_len, max_len);
-    SC_CHECK(prefix_len < max_len, "sc_generate_text_sampled: prompt length %d >= effective max length %d", prefix_len, max_len);
-    SC_CHECK(max_len <= 4096 && max_len <= W.max_seq_len + 1, "sc_generate_text_sampled: length %d exceeds the decoder limit", max_len);
-    SC_CHECK(s_enc <= 4096, "sc_generate_text_sampled: encoder length %d > 4096", s_enc);
-    for (int i = 0; i < n; ++i)
-        SC_CHECK(h_enc_lens[i] > 0 && h_enc_lens[i] <= s_enc, "sc_generate_text_sampled: enc_lens[%d]=%d out of range", i, h_enc_lens[i]);
-    BannedList bl;
-    if (banned && banned->n > 0) validate_banned_host(banned->tokens, banned->offsets, banned->n, V, &bl.max_len);
+    check_generation_limits("sc_generate_text_sampled", o, prefix_len, max_len, W.max_seq_len, n, s_enc, h_enc_lens);
+    const BannedDevice banned_dev = upload_banned(m, banned, V);  // validated here, before any other device work
+    const BannedList& bl = banned_dev.list;
     prof::set_tag("dec");
     if (m.engine) m.engine->expect(m, -n);  // never on the decode engine, like the banned-sequence calls
 
-    Buf<int> d_banned(m.pp(), 4);
-    if (banned && banned->n > 0) {
-        const int total = banned->offsets[banned->n];
-        d_banned = Buf<int>(m.pp(), (size_t)total + banned->n + 1);
-        SC_HIP(hipMemcpyAsync(d_banned.get(), banned->tokens, (size_t)total * 4, hipMemcpyHostToDevice, m.stream));
-        SC_HIP(hipMemcpyAsync(d_banned.get() + total, banned->offsets, (size_t)(banned->n + 1) * 4, hipMemcpyHostToDevice, m.stream));
-        SC_HIP(hipStreamSynchronize(m.stream));  // the list is the caller's
-        bl.tokens = d_banned.get(), bl.offsets = d_banned.get() + total, bl.n = banned->n;
-    }
-
-    // ---- the step context: as run_generate_beam sets it up, without the ancestor table -------------------------------------
+    // ---- the step context: hypotheses of an utterance share its encoder K / V; rows never change places ------------------
     const int family = choose_family(m, W, nb, 1);
     const bool packed_step = family != 1;
-    Buf<float> enc_rep(m.pp(), packed_step ? 4 : (size_t)nb * s_enc * M);
-    if (!packed_step) {  // the general step reads one encoder K / V per row: fan the encoder output out to the hypotheses
-        std::vector<int32_t> idx((size_t)nb * s_enc);
-        for (int r = 0; r < nb; ++r)
-            for (int t = 0; t < s_enc; ++t) idx[(size_t)r * s_enc + t] = (r / B) * s_enc + t;
-        Buf<int> d_idx(m.pp(), idx.size());
-        SC_HIP(hipMemcpyAsync(d_idx.get(), idx.data(), idx.size() * 4, hipMemcpyHostToDevice, m.stream));
-        launch_gather_rows(d_enc, M, d_idx, enc_rep, M, nb * s_enc, M, m.stream);
-        SC_HIP(hipStreamSynchronize(m.stream));  // idx is a host temporary
-    }
+    Buf<float> enc_rep;  // the general step reads one encoder K / V per row: the encoder output fanned out to the hypotheses
+    if (!packed_step) enc_rep = fan_out_encoder(m, d_enc, n, B, s_enc);
     StepCtx c;
     c.stack = &W;
     c.nb = nb, c.cap = max_len, c.s_enc = s_enc;
@@ -78,26 +53,10 @@ void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const 
     c.d_finished = c.d_tok + nb;
     c.d_out_len = c.d_finished + nb;
     c.d_enc_lens = c.d_out_len + nb;
-    const int wideN = std::max(3 * M, W.ffn_dim);
-    Buf<float> x(m.pp(), (size_t)nb * M), h(m.pp(), (size_t)nb * M), wide(m.pp(), (size_t)nb * wideN), att(m.pp(), (size_t)nb * M),
-        hN(m.pp(), (size_t)nb * M), logits(m.pp(), (size_t)nb * (V + 3));
-    Buf<float> partial(m.pp(), (size_t)std::max(1, std::max(M, W.ffn_dim) / 256) * nb * 3 * M);
-    c.partial = partial, c.x = x, c.h = h, c.wide = wide, c.att = att, c.hN = hN, c.logits = logits;
-    Buf<float> xg3(m.pp(), 4), qkvr3(m.pp(), 4), qkv3w(m.pp(), 4);
-    if (packed_step) {
-        alloc_step2(m, c, W.ffn_dim);
-        if (family >= 3) {
-            c.gen3 = true;
-            xg3 = Buf<float>(m.pp(), (size_t)M * c.rb);
-            qkvr3 = Buf<float>(m.pp(), (size_t)nb * M);
-            c.xg = xg3, c.qkvr = qkvr3;
-            if (nb > 64) {
-                qkv3w = Buf<float>(m.pp(), (size_t)nb * 3 * M);
-                c.qkv3 = qkv3w;
-            }
-            c.rg_small = nb > 128 ? 32 : 16;
-        }
-    }
+    StepScratch scratch;
+    init_step_scratch(m, scratch, c, W, nb, family, StepTuning::defaults(nb));
+    Buf<float> logits(m.pp(), (size_t)nb * (V + 3));
+    c.logits = logits;
     const bool proj_v3 = c.rb > 0 && W.embed_p != nullptr && vocab3_supported(nb, V, M);
     const int64_t ldl = proj_v3 ? (int64_t)align_up(V, 4) : V;
     const int64_t layer_stride = (int64_t)nb * max_len * M;
@@ -115,18 +74,7 @@ void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const 
         c.cross_kv.push_back(cross.back());
         project_cross_kv(m, packed_step ? d_enc : enc_rep.get(), dec_layers[li].cross_kv, c.cross_kv.back(), cross_rows * s_enc);
     }
-    Linear proj;
-    proj.w = W.embed, proj.ldw = M, proj.kpad = M, proj.in = M, proj.out = V;
-    auto project_rows = [&]() {
-        if (proj_v3) {
-            Vocab3Args v;
-            v.Wp = W.embed_p, v.Ah = c.hH, v.Al = c.hL, v.RB = c.rb, v.M = nb, v.N = V, v.K = M;
-            v.logits = c.logits, v.ldl = ldl;
-            launch_vocab3(v, m.stream);
-        } else {
-            linear(m, c.hN, M, proj, nullptr, 0, c.logits, V, nb, ACT_NONE, 1.f);
-        }
-    };
+    auto project_rows = [&]() { project_logits(m, c, W, proj_v3, ldl); };  // c.d_rows stays null: every row, always
 
     // ---- per-row state, device resident ----------------------------------------------------------------------------------------
     std::vector<int32_t> seqs((size_t)nb * max_len, W.pad_idx), init(8 + 4 * nb, 0), tok(nb), gens(nb);
@@ -178,34 +126,14 @@ void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const 
     }
 
     // ---- generation: device work only; the host polls `remaining` every fourth step --------------------------------------------
-    struct StepGraph {
-        hipGraph_t g = nullptr;
-        hipGraphExec_t e = nullptr;
-        ~StepGraph() {
-            if (e) (void)hipGraphExecDestroy(e);
-            if (g) (void)hipGraphDestroy(g);
-        }
-    } graph;
+    StepGraph graph;
     const bool step_graph = o.use_graph != 0 && c.rb > 0;
     const int start = prefix_len - 1, G = o.no_repeat_ngram_size;
     int remaining = nb;
     for (int step = start; step <= max_len - 2 && remaining > 0; ++step) {
         if (step_graph) {
-            if (!graph.e) {
-                std::lock_guard<std::mutex> lock(capture_mutex());
-                SC_HIP(hipStreamBeginCapture(m.stream, hipStreamCaptureModeThreadLocal));
-                try {
-                    decoder_step(m, c, /*project=*/false);
-                } catch (...) {
-                    hipGraph_t dead = nullptr;
-                    (void)hipStreamEndCapture(m.stream, &dead);
-                    if (dead) (void)hipGraphDestroy(dead);
-                    throw;
-                }
-                SC_HIP(hipStreamEndCapture(m.stream, &graph.g));
-                SC_HIP(hipGraphInstantiate(&graph.e, graph.g, nullptr, nullptr, 0));
-            }
-            SC_HIP(hipGraphLaunch(graph.e, m.stream));
+            graph.ensure(m.stream, [&] { decoder_step(m, c, /*project=*/false); });
+            graph.launch(m.stream);
         } else {
             decoder_step(m, c, /*project=*/false);  // feeds d_tok at position `step`, advances *d_pos
         }
@@ -243,7 +171,6 @@ void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const 
         // beam_select_kernel's expression: the EOS is appended at step = len - 2
         score[r] = o.normalize_scores ? cum[r] / powf((float)(lens[r] - 1), o.len_penalty) : cum[r];
     }
-    int longest = 0;  // of the best hypotheses (slot 0 of every utterance after sorting)
     for (int u = 0; u < n; ++u) {
         std::vector<int> ord(B);
         for (int g = 0; g < B; ++g) ord[g] = u * B + g;
@@ -260,21 +187,10 @@ void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const 
             h_out_lens[dst] = len;
             if (h_scores) h_scores[dst] = score[r];
         }
-        longest = std::max(longest, h_out_lens[u * B]);
     }
     // ---- decoder outputs of the best hypothesis per utterance: the teacher-forced pass, as behind a beam search ----------------
-    if (d_dec_hidden) {
-        const int fl = longest - 1;  // text_seqs[:, :-1]
-        std::vector<int32_t> forced((size_t)n * fl, W.pad_idx);
-        for (int u = 0; u < n; ++u)
-            for (int t = 0; t < fl && t < h_out_lens[u * B]; ++t) forced[(size_t)u * fl + t] = h_out_ids[(size_t)u * B * max_len + t];
-        Buf<float> hid(m.pp(), (size_t)n * fl * M);
-        run_generate_text(m, d_enc, n, s_enc, h_enc_lens, o, nullptr, 0, nullptr, nullptr, nullptr, hid, forced.data(), fl);
-        SC_HIP(hipMemsetAsync(d_dec_hidden, 0, (size_t)n * (max_len - 1) * M * 4, m.stream));
-        SC_HIP(hipMemcpy2DAsync(d_dec_hidden, (size_t)(max_len - 1) * M * 4, hid.get(), (size_t)fl * M * 4, (size_t)fl * M * 4, n,
-                                hipMemcpyDeviceToDevice, m.stream));
-        SC_HIP(hipStreamSynchronize(m.stream));
-    }
+    // (slot 0 of every utterance after sorting)
+    if (d_dec_hidden) hidden_of_best(m, d_enc, n, s_enc, h_enc_lens, o, h_out_ids, h_out_lens, B, max_len, W.pad_idx, d_dec_hidden);
 }
 
 }  // namespace sc

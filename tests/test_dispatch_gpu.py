@@ -1,5 +1,5 @@
 """The decoder-step dispatch matrix as data: which kernel family each (live rows, caller) pair runs on
-(sc_decoder_step_family evaluates the predicates the stages themselves use - model_decoder.hip: decoder_step_family).  Three
+(sc_decoder_step_family evaluates the predicates the stages themselves use - model_dstep.hip: decoder_step_family).  Three
 families are live: 1 general (split-K skinny products / tiled GEMMs: the fallback for geometries the packed kernels do not
 take and for more than 512 live rows), 2 packed-fragment products (k_dstep.hip: the streaming decoder's step with its
 p_choose hook, the v1 unit decoder's beam search - no packed embedding), 3 / 4 row-group products (k_dstep3.hip: greedy text

@@ -127,6 +127,16 @@ def test_sampled_run_verifies_post_hoc(env):
     assert steps > 40 and near <= 0.02 * steps and used <= 0.02 * steps
 
 
+def test_graph_replay_equals_eager_launching(env):
+    """use_graph=True (the step replayed from its captured graph) and use_graph=False (the same launches made one by one)
+    return the same ids, lengths, scores and step log-probabilities, bit for bit: 2 utterances x 3 hypotheses."""
+    kw = dict(rows=[0, 1], num_gens=3, top_p=0.9, temperature=0.8, seed=20240901)
+    eager, graph = sample(env, use_graph=False, **kw), sample(env, use_graph=True, **kw)
+    assert eager[0].shape[:2] == (2, 3)
+    for a, b in zip(eager[:4], graph[:4]):
+        assert np.array_equal(a, b)
+
+
 def test_streams_make_an_utterance_independent_of_its_batch(env):
     kw = dict(num_gens=4, top_p=0.9, temperature=0.8, seed=11)
     batch = sample(env, streams=[7, 8, 9], **kw)

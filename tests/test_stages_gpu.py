@@ -364,6 +364,22 @@ def test_beam_search_wide_step_matches_oracle(env, report_dir, n_utt, beam):
     assert not bad, (bad, [got[b] for b in bad], [want[b] for b in bad])
 
 
+def test_beam_search_graph_replay_equals_eager_launching(env):
+    """use_graph=True (the step of run_generate_beam replayed from its captured graph) and use_graph=False (the same launches
+    made one by one) return the same ids, lengths, scores and decoder outputs, bit for bit, at the smallest utterance count
+    whose 5-beam step runs on the wide row-group chain (family 4: 13 utterances = 65 live rows on the tiny model)."""
+    cfg, tt, ct, orc, hip = env
+    n_utt = next(n for n in range(1, 104) if int(hip.lib.sc_decoder_step_family(hip.handle, n * 5, 1)) == 4)
+    print(f"family 4 from {n_utt} utterances x 5 beams")
+    fb, lens = orc.collate_fbank(common.waves([0.9 + 0.11 * (i % 9) for i in range(n_utt)]))
+    enc, enc_lens = hip.encode_speech(fb.cuda(), lens.tolist())
+    prefix = tt.target_prefix("fra")
+    eager, graph = (hip.generate_text(enc, enc_lens.tolist(), prefix, beam_size=5, hard_max_seq_len=11, use_graph=g) for g in (False, True))
+    for a, b in zip(eager[:3], graph[:3]):
+        assert np.array_equal(a, b)
+    assert torch.equal(eager[3], graph[3])
+
+
 def test_beam_size_one_equals_greedy(env):
     from oracle import unity as ou
 
