@@ -245,6 +245,29 @@ int sc_generate_text_banned(sc_model* m, const float* d_enc, int32_t n, int32_t 
                             int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden, const int32_t* h_banned_tokens,
                             const int32_t* h_banned_offsets /* [n_banned + 1] */, int32_t n_banned);
 
+/* sc_generate_text_banned with phrase boosting (additive, ABI 10; "hot words" / contextual biasing.  An extension of this
+ * library: the rule is in neither the reference nor fairseq2 0.2, and its effect on real speech has not been evaluated).
+ * h_boost_tokens / h_boost_offsets [n_boost + 1]: the phrases as token sequences in CSR form, in any order; boost: the bonus in
+ * log-probability units per matched token.  For a row whose sequence so far is y (prompt included): d(y) = the length of the
+ * longest suffix of y that is a prefix of some phrase (a whole phrase counts; 0 if none); dp(y) = d(y) if that suffix is a
+ * proper prefix of a phrase, 0 if it is a whole phrase; for every token t, k(y, t) = d(y + t) - dp(y) (-63 .. 64) and the row's
+ * logit becomes fmaf(boost, (float)k, x[t]) - one fp32 operation on the unmodified logit, k == 0 keeps the bits.  Applied after
+ * the row's log-sum-exp (not renormalised), after the n-gram and banned processors (-inf stays -inf), at every step but the
+ * forced-EOS one, on the first step for beam 0 only.  So extending a match earns +boost, completing a phrase keeps what was
+ * earned, and leaving a match of depth d unfinished costs every non-continuing token (EOS included) -boost * d: over a
+ * hypothesis the sum is boost * (the summed lengths of the completed phrase occurrences) + boost * dp(final), the last term
+ * non-zero only for a hypothesis cut at the length limit.  The returned scores INCLUDE the bonus.  boost < 0 is a soft ban.
+ * n_boost == 0 or boost == 0 is sc_generate_text_banned.  Otherwise the call runs the host-driven step loop for every beam_size
+ * (1 included), never the decode engine.  The list is sorted and copied to the device once per call.  Limits (SC_ERR_INVALID
+ * before any device work, sc_last_error names the reason): n_boost <= 4096, 1..64 tokens per phrase, 65536 tokens in all, every
+ * token inside the text vocabulary and neither pad nor EOS, no phrase a prefix of another (duplicates included), boost finite
+ * with |boost| <= 100.  sc_generate_text_sampled, sc_generate_text_capture and sc_s2st take no phrase list. */
+int sc_generate_text_boosted(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
+                             const sc_gen_opts* opts, const int32_t* h_prefix, int32_t prefix_len, int32_t* h_out_ids,
+                             int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden, const int32_t* h_banned_tokens,
+                             const int32_t* h_banned_offsets /* [n_banned + 1] */, int32_t n_banned, const int32_t* h_boost_tokens,
+                             const int32_t* h_boost_offsets /* [n_boost + 1] */, int32_t n_boost, float boost);
+
 /* Sampled text generation (additive, ABI 10; fairseq2 0.2 SamplingSeq2SeqGenerator with TopKSampler / TopPSampler - not part
  * of the reference tree, restated from memory: UNVERIFIED): num_gens stochastic hypotheses per utterance, drawn inside the step
  * loop.  At every step the logits are divided by `temperature`, the step processors (opts->no_repeat_ngram_size, the banned
@@ -502,6 +525,14 @@ int32_t sc_ngram_blocked_tokens(const int32_t* h_seq, int32_t len, int32_t ngram
  * there are, or a negative status. */
 int32_t sc_banned_blocked_tokens(const int32_t* h_seq, int32_t len, const int32_t* h_banned_tokens, const int32_t* h_banned_offsets,
                                  int32_t n_banned, int32_t* h_out, int32_t cap);
+
+/* Host logic of the phrase-boost step processor (no device work; callable without a GPU): for the `len` tokens y of `h_seq`
+ * and the list of sc_generate_text_boosted (same limits, except that there is no vocabulary, pad or EOS to check tokens
+ * against), the tokens t with d(y + t) > 0 in ascending order to h_out_tokens and d(y + t) to h_out_k (at most `cap` each),
+ * dp(y) to *out_dp (nullable).  k(y, t) = d(y + t) - dp(y); every token not listed has d(y + t) = 0.  Returns how many tokens
+ * there are, or a negative status. */
+int32_t sc_boost_deltas(const int32_t* h_seq, int32_t len, const int32_t* h_boost_tokens, const int32_t* h_boost_offsets, int32_t n_boost,
+                        int32_t* h_out_tokens, int32_t* h_out_k, int32_t cap, int32_t* out_dp);
 
 /* UnitY2 forced aligner (the `nar_t2u_aligner` card; added within ABI v10, purely additive).  A handle of its own: the aligner
  * is a separate checkpoint with its own vocabularies, stream and scratch pool.  Configuration as

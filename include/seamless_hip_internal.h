@@ -219,6 +219,16 @@ int sc_op_beam_candidates_banned(float* d_logits, int64_t ld, int32_t n_utt, int
                                  float unk_penalty, int32_t K, float* d_cand_val, int32_t* d_cand_idx, const int32_t* d_seqs,
                                  int32_t seq_ld, int32_t S, int32_t G, const int32_t* d_rows, const int32_t* d_slots, int32_t chunked,
                                  const int32_t* d_banned_tokens, const int32_t* d_banned_offsets, int32_t n_banned);
+/* sc_op_beam_candidates_banned plus a boost phrase list in DEVICE memory (CSR, any order; tests/test_boost_gpu.py): the list is
+ * read back, checked against the limits of sc_generate_text_boosted (pad_idx / eos_idx are the call's) and sorted on the host,
+ * then beam_candidates_boost_kernel / step_processors_boost_kernel run.  Needs d_seqs.  n_boost == 0 or boost == 0 is
+ * sc_op_beam_candidates_banned. */
+int sc_op_beam_candidates_boost(float* d_logits, int64_t ld, int32_t n_utt, int32_t beams, int32_t V, const float* d_cum,
+                                int32_t first_step, int32_t no_eos, int32_t force_eos, int32_t pad_idx, int32_t eos_idx, int32_t unk_idx,
+                                float unk_penalty, int32_t K, float* d_cand_val, int32_t* d_cand_idx, const int32_t* d_seqs,
+                                int32_t seq_ld, int32_t S, int32_t G, const int32_t* d_rows, const int32_t* d_slots, int32_t chunked,
+                                const int32_t* d_banned_tokens, const int32_t* d_banned_offsets, int32_t n_banned,
+                                const int32_t* d_boost_tokens, const int32_t* d_boost_offsets, int32_t n_boost, float boost);
 /* The sampling step of sc_generate_text_sampled (k_sample.hip; tests/test_sample_kernel_gpu.py, restated in tests/sample_oracle.py):
  * one top-k / top-p draw per logit row [rows][ld] under the step rules, a pure function of (row, options, seed, d_stream[r],
  * d_gen[r], d_position[r]).  temperature > 0; top_k 0 = off; 0 < top_p <= 1.  d_seqs (nullable) with S, G and the banned list as

@@ -193,6 +193,8 @@ SIGNATURES = {
     "sc_text_max_len": (_i, [_P, C.POINTER(sc_gen_opts), _i]),
     "sc_generate_text": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P]),
     "sc_generate_text_banned": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P, _P, _P, _i]),
+    "sc_generate_text_boosted": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P, _P, _P, _i, _P, _P, _i,
+                                           C.c_float]),
     "sc_generate_text_sampled": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), C.POINTER(sc_sample_opts), _P, _P, _i, _P, _P, _P, _P, _P,
                                            _P, _P, _i]),
     "sc_generate_text_capture": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P, _P, _P]),
@@ -228,6 +230,7 @@ SIGNATURES = {
                                          _P, _P, C.c_int32, _P]),
     "sc_ngram_blocked_tokens": (C.c_int32, [_PI, C.c_int32, C.c_int32, _PI, C.c_int32]),
     "sc_banned_blocked_tokens": (C.c_int32, [_PI, C.c_int32, _PI, _PI, C.c_int32, _PI, C.c_int32]),
+    "sc_boost_deltas": (C.c_int32, [_PI, C.c_int32, _PI, _PI, C.c_int32, _PI, _PI, C.c_int32, _PI]),
     "sc_aligner_load": (_P, [C.POINTER(sc_tensor_desc), C.c_size_t, C.POINTER(sc_aligner_config), C.c_int]),
     "sc_aligner_free": (None, [_P]),
     "sc_align": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P, _P, _P]),
@@ -325,6 +328,8 @@ SIGNATURES = {
                                         _P, _P, _i]),
     "sc_op_beam_candidates_banned": (C.c_int, [_P, C.c_int64, _i, _i, _i, _P, _i, _i, _i, _i, _i, _i, C.c_float, _i, _P, _P, _P, _i, _i,
                                                _i, _P, _P, _i, _P, _P, _i]),
+    "sc_op_beam_candidates_boost": (C.c_int, [_P, C.c_int64, _i, _i, _i, _P, _i, _i, _i, _i, _i, _i, C.c_float, _i, _P, _P, _P, _i, _i,
+                                              _i, _P, _P, _i, _P, _P, _i, _P, _P, _i, C.c_float]),
     "sc_op_sample_rows": (C.c_int, [_P, C.c_int64, _i, _i, _P, _P, _P, C.c_float, _i, C.c_float, C.c_uint64, _i, _i, _i, _i, _i, C.c_float,
                                     _P, _i, _i, _i, _P, _P, _i, _P, _P, _P, _P]),
     "sc_op_beam_select": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _i, _i, _i, _i, _i, _i, _i, _i,

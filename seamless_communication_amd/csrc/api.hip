@@ -245,6 +245,35 @@ int sc_generate_text_banned(sc_model* m, const float* d_enc, int32_t n, int32_t 
     SC_API_END
 }
 
+int sc_generate_text_boosted(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
+                             const sc_gen_opts* opts, const int32_t* h_prefix, int32_t prefix_len, int32_t* h_out_ids,
+                             int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden, const int32_t* h_banned_tokens,
+                             const int32_t* h_banned_offsets, int32_t n_banned, const int32_t* h_boost_tokens,
+                             const int32_t* h_boost_offsets, int32_t n_boost, float boost) {
+    SC_API_BEGIN
+    SC_CHECK(m && d_enc && h_enc_lens && opts && h_prefix && h_out_ids && h_out_lens, "sc_generate_text_boosted: null argument");
+    SC_CHECK(n_banned >= 0 && (n_banned == 0 || (h_banned_tokens && h_banned_offsets)), "sc_generate_text_boosted: bad banned list");
+    SC_CHECK(n_boost >= 0 && (n_boost == 0 || (h_boost_tokens && h_boost_offsets)), "sc_generate_text_boosted: bad phrase list");
+    BannedHost b;
+    b.tokens = h_banned_tokens, b.offsets = h_banned_offsets, b.n = n_banned;
+    BoostHost p;
+    p.tokens = h_boost_tokens, p.offsets = h_boost_offsets, p.n = n_boost, p.boost = boost;
+    // refused before any device work (the call itself checks and sorts the list again where it copies it)
+    validate_banned_host(b.tokens, b.offsets, b.n, m->m.cfg.text_vocab_size, nullptr);
+    {
+        const DecStack W = unity_stack(m->m);
+        BoostSorted sorted;
+        const std::string why = boost_list_build(p.tokens, p.offsets, p.n, W.vocab, W.pad_idx, W.eos_idx, sorted);
+        SC_CHECK(why.empty(), "%s", why.c_str());
+        const std::string bad = boost_value_check(boost);
+        SC_CHECK(bad.empty(), "%s", bad.c_str());
+    }
+    SC_HIP(hipSetDevice(m->m.device));
+    run_generate_text(m->m, d_enc, n, s_enc, h_enc_lens, *opts, h_prefix, prefix_len, h_out_ids, h_out_lens, h_out_scores,
+                      d_dec_hidden, nullptr, 0, nullptr, n_banned > 0 ? &b : nullptr, 0, n_boost > 0 && boost != 0.f ? &p : nullptr);
+    SC_API_END
+}
+
 int sc_generate_text_sampled(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
                              const sc_gen_opts* opts, const sc_sample_opts* sample_opts, const uint64_t* h_streams, const int32_t* h_prefix,
                              int32_t prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_out_scores, float* h_step_lprob,
@@ -649,6 +678,27 @@ int32_t sc_banned_blocked_tokens(const int32_t* h_seq, int32_t len, const int32_
         sc::banned_blocked_tokens(h_seq, len, b, out);
         for (size_t i = 0; i < out.size() && i < (size_t)cap; ++i) h_out[i] = out[i];
         return (int32_t)out.size();
+    } catch (const sc::Error& e) {
+        return e.code;
+    } catch (const std::exception& e) {
+        sc::set_error("unexpected C++ exception: %s", e.what());
+        return SC_ERR_INTERNAL;
+    }
+}
+
+int32_t sc_boost_deltas(const int32_t* h_seq, int32_t len, const int32_t* h_boost_tokens, const int32_t* h_boost_offsets, int32_t n_boost,
+                        int32_t* h_out_tokens, int32_t* h_out_k, int32_t cap, int32_t* out_dp) {
+    try {
+        SC_CHECK(len >= 0 && cap >= 0 && (h_seq || len == 0) && ((h_out_tokens && h_out_k) || cap == 0), "sc_boost_deltas: bad argument");
+        sc::BoostSorted sorted;
+        const std::string why = sc::boost_list_build(h_boost_tokens, h_boost_offsets, n_boost, -1, -1, -1, sorted);
+        SC_CHECK(why.empty(), "%s", why.c_str());
+        std::vector<int32_t> toks, depth;
+        int dp = 0;
+        sc::boost_deltas(h_seq, len, sorted, toks, depth, &dp);
+        for (size_t i = 0; i < toks.size() && i < (size_t)cap; ++i) h_out_tokens[i] = toks[i], h_out_k[i] = depth[i];
+        if (out_dp) *out_dp = dp;
+        return (int32_t)toks.size();
     } catch (const sc::Error& e) {
         return e.code;
     } catch (const std::exception& e) {
@@ -1655,8 +1705,31 @@ static int op_beam_candidates(float* d_logits, int64_t ld, int32_t n_utt, int32_
                               int32_t no_eos, int32_t force_eos, int32_t pad_idx, int32_t eos_idx, int32_t unk_idx, float unk_penalty, int32_t K,
                               float* d_cand_val, int32_t* d_cand_idx, const int32_t* d_seqs, int32_t seq_ld, int32_t S, int32_t G,
                               const int32_t* d_rows, const int32_t* d_slots, int32_t chunked, const int32_t* d_banned_tokens,
-                              const int32_t* d_banned_offsets, int32_t n_banned) {
+                              const int32_t* d_banned_offsets, int32_t n_banned, const int32_t* d_boost_tokens = nullptr,
+                              const int32_t* d_boost_offsets = nullptr, int32_t n_boost = 0, float boost_value = 0.f) {
     SC_API_BEGIN
+    // the phrase list is read back, checked and sorted on the host, and the sorted list goes up again
+    BoostList bo;
+    OpScratch boost_scratch;
+    if (n_boost != 0 && boost_value != 0.f) {
+        SC_CHECK(n_boost > 0 && n_boost <= BOOST_MAX_PHRASES && d_boost_tokens && d_boost_offsets && d_seqs,
+                 "boost phrases: bad list (%d phrases, at most %d; needs d_seqs)", n_boost, BOOST_MAX_PHRASES);
+        const std::vector<int32_t> off = op_read_ints(d_boost_offsets, (size_t)n_boost + 1);
+        SC_CHECK(off[0] == 0 && off[n_boost] >= 0, "boost phrases: bad offsets");
+        for (int q = 0; q < n_boost; ++q) SC_CHECK(off[q + 1] >= off[q], "boost phrases: offsets decrease at %d", q);
+        SC_CHECK(off[n_boost] <= BOOST_MAX_TOKENS, "boost phrases: %d tokens in all (at most %d)", off[n_boost], BOOST_MAX_TOKENS);
+        const std::vector<int32_t> tok = op_read_ints(d_boost_tokens, (size_t)off[n_boost]);
+        BoostSorted sorted;
+        const std::string why = boost_list_build(tok.data(), off.data(), n_boost, V, pad_idx, eos_idx, sorted);
+        SC_CHECK(why.empty(), "%s", why.c_str());
+        const std::string bad = boost_value_check(boost_value);
+        SC_CHECK(bad.empty(), "%s", bad.c_str());
+        int* store = boost_scratch.get<int>(sorted.tokens.size() + sorted.n + 1);
+        SC_HIP(hipMemcpy(store, sorted.tokens.data(), sorted.tokens.size() * 4, hipMemcpyHostToDevice));
+        SC_HIP(hipMemcpy(store + sorted.tokens.size(), sorted.offsets.data(), (size_t)(sorted.n + 1) * 4, hipMemcpyHostToDevice));
+        bo.tokens = store, bo.offsets = store + sorted.tokens.size(), bo.n = sorted.n, bo.max_len = sorted.max_len, bo.beta = boost_value;
+    }
+    const BoostList* boost = bo.n > 0 ? &bo : nullptr;
     // the device list is read back and checked on the host first: a bad one is an error, not an out-of-bounds access
     BannedList bl;
     if (n_banned != 0) {
@@ -1683,12 +1756,13 @@ static int op_beam_candidates(float* d_logits, int64_t ld, int32_t n_utt, int32_
         SC_HIP(hipMemsetAsync(ws_f, 0xff, beam_ws_floats(rows, K) * 4, g_op_stream));  // NaN / -1: unwritten entries show
         SC_HIP(hipMemsetAsync(ws_i, 0xff, beam_ws_ints(rows, K) * 4, g_op_stream));
         launch_beam_candidates_chunked(d_logits, ld, n_utt, beams, V, d_cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx,
-                                       unk_penalty, K, d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, ws_f, ws_i, g_op_stream, d_rows, d_slots, banned);
+                                       unk_penalty, K, d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, ws_f, ws_i, g_op_stream, d_rows, d_slots, banned,
+                                       boost);
         SC_HIP(hipStreamSynchronize(g_op_stream));
     } else {
         SC_CHECK(!d_rows, "sc_op_beam_candidates: d_rows is an argument of the chunked search only (the single-workgroup one takes d_slots)");
         launch_beam_candidates(d_logits, ld, n_utt, beams, V, d_cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K,
-                               d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, g_op_stream, d_slots, banned);
+                               d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, g_op_stream, d_slots, banned, boost);
         SC_HIP(hipStreamSynchronize(g_op_stream));
     }
     SC_API_END
@@ -1710,6 +1784,17 @@ int sc_op_beam_candidates_banned(float* d_logits, int64_t ld, int32_t n_utt, int
     return op_beam_candidates(d_logits, ld, n_utt, beams, V, d_cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K,
                               d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, d_rows, d_slots, chunked, d_banned_tokens, d_banned_offsets,
                               n_banned);
+}
+
+int sc_op_beam_candidates_boost(float* d_logits, int64_t ld, int32_t n_utt, int32_t beams, int32_t V, const float* d_cum,
+                                int32_t first_step, int32_t no_eos, int32_t force_eos, int32_t pad_idx, int32_t eos_idx, int32_t unk_idx,
+                                float unk_penalty, int32_t K, float* d_cand_val, int32_t* d_cand_idx, const int32_t* d_seqs,
+                                int32_t seq_ld, int32_t S, int32_t G, const int32_t* d_rows, const int32_t* d_slots, int32_t chunked,
+                                const int32_t* d_banned_tokens, const int32_t* d_banned_offsets, int32_t n_banned,
+                                const int32_t* d_boost_tokens, const int32_t* d_boost_offsets, int32_t n_boost, float boost) {
+    return op_beam_candidates(d_logits, ld, n_utt, beams, V, d_cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K,
+                              d_cand_val, d_cand_idx, d_seqs, seq_ld, S, G, d_rows, d_slots, chunked, d_banned_tokens, d_banned_offsets,
+                              n_banned, d_boost_tokens, d_boost_offsets, n_boost, boost);
 }
 
 // the sampling step (k_sample.hip) through the launcher run_generate_sampled calls

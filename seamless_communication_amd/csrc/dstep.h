@@ -180,6 +180,12 @@ struct BannedDevice {
     Buf<int> store;
 };
 BannedDevice upload_banned(Model& m, const BannedHost* banned, int V);
+// the caller's boost phrases on the device, sorted (checked on the host first; an empty list or boost == 0 makes no device work)
+struct BoostDevice {
+    BoostList list;
+    Buf<int> store;
+};
+BoostDevice upload_boost(Model& m, const BoostHost* boost, int V, int pad_idx, int eos_idx);
 // the general step reads one encoder K / V per row: the encoder output [n][s_enc][M] repeated `per_item` times per item
 Buf<float> fan_out_encoder(Model& m, const float* d_enc, int n, int per_item, int s_enc);
 // vocabulary logits of the live rows into c.logits (row stride ldl): the streaming kernel on the packed embedding when v3

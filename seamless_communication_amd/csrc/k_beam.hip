@@ -16,6 +16,9 @@
 //   Step processor (BannedSequenceProcessor, the MinTox re-decode): a list of banned token sequences (CSR in device memory);
 //   a sequence whose first L-1 tokens equal the last L-1 tokens of the row's sequence blocks its last token the same way
 //   (banned_block_row; beam_candidates_banned_kernel / step_processors_kernel - a call without a list launches neither).
+//   Step processor (PhraseBoostProcessor, this project's own): a sorted, prefix-free list of phrases and one boost; the row's
+//   logits move by boost * k(y, t) after the other two processors (boost_row; beam_candidates_boost_kernel /
+//   step_processors_boost_kernel - a call without phrases launches neither).
 // beam_select_kernel: the per-step candidate walk (finalise EOS hypotheses, refill the beams, append tokens);
 //   sequences, finished hypotheses and counters live in device memory, the host only polls `remaining`.
 // row_token_lprob_kernel: log-softmax value of ONE given token per row (scores of the echoed prompt).
@@ -47,12 +50,13 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-template <bool BANNED>
+template <bool BANNED, bool BOOST = false>
 __device__ __forceinline__ void beam_candidates_body(float* logits, int64_t ld, int beams, int V, const float* __restrict__ cum,
                                                      int first_step, int no_eos, int force_eos, int pad_idx, int eos_idx, int unk_idx,
                                                      float unk_penalty, int K, float* __restrict__ cand_val, int* __restrict__ cand_idx,
                                                      const int* __restrict__ seqs, int seq_ld, int S, int G,
-                                                     const int* __restrict__ d_slots, const BannedList& bl) {
+                                                     const int* __restrict__ d_slots, const BannedList& bl,
+                                                     const BoostList& bo = BoostList{}) {
     __shared__ float red[4];
     __shared__ float lse[BEAM_MAX_K];
     __shared__ int s_key[256];
@@ -93,6 +97,14 @@ __device__ __forceinline__ void beam_candidates_body(float* logits, int64_t ld, 
         if (seqs && bl.n > 0) {  // uniform over the workgroup
             for (int b = 0; b < nb; ++b)
                 banned_block_row(logits + ((int64_t)n * beams + b) * ld, V, seqs + ((int64_t)n * beams + b) * seq_ld, S, bl, s_tail);
+            __syncthreads();
+        }
+    }
+    if constexpr (BOOST) {
+        __shared__ BoostShared s_boost;
+        if (seqs && bo.n > 0) {  // uniform over the workgroup
+            for (int b = 0; b < nb; ++b)
+                boost_row(logits + ((int64_t)n * beams + b) * ld, V, seqs + ((int64_t)n * beams + b) * seq_ld, S, bo, s_boost);
             __syncthreads();
         }
     }
@@ -188,6 +200,18 @@ __global__ __launch_bounds__(256) void beam_candidates_banned_kernel(float* logi
                                                                      BannedList bl) {
     beam_candidates_body<true>(logits, ld, beams, V, cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val,
                                cand_idx, seqs, seq_ld, S, G, d_slots, bl);
+}
+
+// the same search with a phrase list (and a banned-sequence list, which may be empty)
+__global__ __launch_bounds__(256) void beam_candidates_boost_kernel(float* logits, int64_t ld, int beams, int V,
+                                                                    const float* __restrict__ cum, int first_step, int no_eos,
+                                                                    int force_eos, int pad_idx, int eos_idx, int unk_idx,
+                                                                    float unk_penalty, int K, float* __restrict__ cand_val,
+                                                                    int* __restrict__ cand_idx, const int* __restrict__ seqs,
+                                                                    int seq_ld, int S, int G, const int* __restrict__ d_slots,
+                                                                    BannedList bl, BoostList bo) {
+    beam_candidates_body<true, true>(logits, ld, beams, V, cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K,
+                                     cand_val, cand_idx, seqs, seq_ld, S, G, d_slots, bl, bo);
 }
 
 __global__ __launch_bounds__(256) void row_token_lprob_kernel(const float* __restrict__ logits, int64_t ld, int V,
@@ -287,6 +311,29 @@ __global__ __launch_bounds__(256) void step_processors_kernel(float* logits, int
         }
     }
     banned_block_row(row, V, seq, S, bl, s_tail);
+}
+
+// the three step processors in one launch (a call with a phrase list): n-gram, banned sequences (the list may be empty), boost
+__global__ __launch_bounds__(256) void step_processors_boost_kernel(float* logits, int64_t ld, int V, int beams, int first_step,
+                                                                    const int* __restrict__ seqs, int seq_ld, int S, int G, BannedList bl,
+                                                                    BoostList bo, const int* __restrict__ d_rows) {
+    __shared__ int s_tail[BANNED_MAX_LEN];
+    __shared__ BoostShared s_boost;
+    if (d_rows && (int)blockIdx.x >= *d_rows) return;
+    if (first_step && blockIdx.x % beams != 0) return;
+    float* row = logits + (int64_t)blockIdx.x * ld;
+    const int* seq = seqs + (int64_t)blockIdx.x * seq_ld;
+    if (G > 0 && G < S) {
+        const int* tail = seq + S - (G - 1);
+        for (int j = threadIdx.x; j + G <= S; j += 256) {
+            bool same = true;
+            for (int e = 0; e + 1 < G; ++e) same = same && (seq[j + e] == tail[e]);
+            const int t = seq[j + G - 1];
+            if (same && t >= 0 && t < V) row[t] = -INFINITY;
+        }
+    }
+    if (bl.n > 0) banned_block_row(row, V, seq, S, bl, s_tail);  // uniform over the workgroup
+    boost_row(row, V, seq, S, bo, s_boost);
 }
 
 // block-wide arg-best of one (order_key(value), flattened index) per thread; every thread returns the winner
@@ -594,16 +641,28 @@ void check_banned_list(const BannedList& bl, int seq_ld, int S) {
              "banned sequences: bad device list (n=%d max_len=%d)", bl.n, bl.max_len);
     SC_CHECK(S >= 0 && S <= seq_ld, "banned sequences: %d tokens in rows of %d", S, seq_ld);
 }
+void check_boost_list(const BoostList& bo, int seq_ld, int S) {
+    SC_CHECK(bo.tokens && bo.offsets && bo.n <= BOOST_MAX_PHRASES && bo.max_len >= 1 && bo.max_len <= BOOST_MAX_LEN && std::isfinite(bo.beta),
+             "boost phrases: bad device list (n=%d max_len=%d)", bo.n, bo.max_len);
+    SC_CHECK(S >= 0 && S <= seq_ld, "boost phrases: %d tokens in rows of %d", S, seq_ld);
+}
 }  // namespace
 
 void launch_beam_candidates(float* logits, int64_t ld, int n_utt, int beams, int V, const float* cum, int first_step,
                             int no_eos, int force_eos, int pad_idx, int eos_idx, int unk_idx, float unk_penalty, int K,
                             float* cand_val, int* cand_idx, const int* seqs, int seq_ld, int S, int G, hipStream_t s, const int* d_slots,
-                            const BannedList* banned) {
+                            const BannedList* banned, const BoostList* boost) {
     SC_CHECK(K >= 1 && K <= BEAM_MAX_K && beams >= 1 && beams <= BEAM_MAX_K, "beam search: beam_size %d / K %d out of range (max %d candidates)",
              beams, K, BEAM_MAX_K);
     SC_CHECK((int64_t)beams * V < (1ll << 31) - 1, "beam search: beam * vocabulary overflows the candidate index");
-    if (banned && banned->n > 0 && seqs) {
+    const bool has_banned = banned && banned->n > 0 && seqs;
+    if (boost && boost->n > 0 && seqs) {
+        if (has_banned) check_banned_list(*banned, seq_ld, S);
+        check_boost_list(*boost, seq_ld, S);
+        hipLaunchKernelGGL(beam_candidates_boost_kernel, dim3(n_utt), dim3(256), 0, s, logits, ld, beams, V, cum, first_step, no_eos,
+                           force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val, cand_idx, seqs, seq_ld, S, G, d_slots,
+                           has_banned ? *banned : BannedList{}, *boost);
+    } else if (has_banned) {
         check_banned_list(*banned, seq_ld, S);
         hipLaunchKernelGGL(beam_candidates_banned_kernel, dim3(n_utt), dim3(256), 0, s, logits, ld, beams, V, cum, first_step, no_eos,
                            force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val, cand_idx, seqs, seq_ld, S, G, d_slots, *banned);
@@ -626,7 +685,7 @@ size_t beam_ws_ints(int rows, int K) { return (size_t)rows * BEAM_CH * K; }
 void launch_beam_candidates_chunked(float* logits, int64_t ld, int n_utt, int beams, int V, const float* cum, int first_step, int no_eos,
                                     int force_eos, int pad_idx, int eos_idx, int unk_idx, float unk_penalty, int K, float* cand_val,
                                     int* cand_idx, const int* seqs, int seq_ld, int S, int G, float* ws_f, int* ws_i, hipStream_t s,
-                                    const int* d_rows, const int* d_slots, const BannedList* banned) {
+                                    const int* d_rows, const int* d_slots, const BannedList* banned, const BoostList* boost) {
     SC_CHECK(K >= 1 && K <= BEAM_MAX_K && beams >= 1 && beams <= BEAM_MAX_K, "beam search: beam_size %d / K %d out of range (max %d candidates)",
              beams, K, BEAM_MAX_K);
     SC_CHECK((int64_t)beams * V < (1ll << 31) - 1, "beam search: beam * vocabulary overflows the candidate index");
@@ -637,7 +696,13 @@ void launch_beam_candidates_chunked(float* logits, int64_t ld, int n_utt, int be
     float2* part = reinterpret_cast<float2*>(ws_f);
     float* pval = ws_f + (size_t)rows * BEAM_CH * 2;
     hipLaunchKernelGGL(beam_lse_partial_kernel, dim3(BEAM_CH, rows), dim3(256), 0, s, logits, ld, V, clen, part, d_rows);
-    if (banned && banned->n > 0 && seqs) {  // both step processors in ONE launch
+    if (boost && boost->n > 0 && seqs) {  // the three step processors in ONE launch
+        const bool has_banned = banned && banned->n > 0;
+        if (has_banned) check_banned_list(*banned, seq_ld, S);
+        check_boost_list(*boost, seq_ld, S);
+        hipLaunchKernelGGL(step_processors_boost_kernel, dim3(rows), dim3(256), 0, s, logits, ld, V, beams, first_step, seqs, seq_ld, S, G,
+                           has_banned ? *banned : BannedList{}, *boost, d_rows);
+    } else if (banned && banned->n > 0 && seqs) {  // both step processors in ONE launch
         check_banned_list(*banned, seq_ld, S);
         hipLaunchKernelGGL(step_processors_kernel, dim3(rows), dim3(256), 0, s, logits, ld, V, beams, first_step, seqs, seq_ld, S, G, *banned,
                            d_rows);

@@ -34,6 +34,7 @@
 #include <atomic>
 
 #include "common.h"
+#include "boost_list.h"
 #include "prof.h"
 
 namespace sc {
@@ -619,13 +620,23 @@ struct BannedList {
     int max_len = 0;  // longest sequence
 };
 void validate_banned_host(const int32_t* tokens, const int32_t* offsets, int n_banned, int V, int* out_max_len);
+// Boost phrases of a call (PhraseBoostProcessor; the rule and the limits: boost_list.h), CSR in device memory, the phrases in
+// lexicographic order and prefix-free (boost_list_build made the list).  The row's logit of token t moves by beta * k(y, t).
+struct BoostList {
+    const int* tokens = nullptr;
+    const int* offsets = nullptr;  // [n + 1]
+    int n = 0;
+    int max_len = 0;  // longest phrase
+    float beta = 0.f;
+};
 // seqs [n_utt*beams][seq_ld] (nullable): the rows' sequences so far (S tokens) for the n-gram step processor (G = n-gram
 // size, 0 = off); logits is modified (blocked tokens).  banned (nullable): the call's banned-sequence list, applied to the same
-// rows when seqs is given (another kernel then: beam_candidates_banned_kernel / one step_processors_kernel launch for both rules)
+// rows when seqs is given (another kernel then: beam_candidates_banned_kernel / one step_processors_kernel launch for both rules).
+// boost (nullable): the call's phrase list, applied after the other two (beam_candidates_boost_kernel / step_processors_boost_kernel)
 void launch_beam_candidates(float* logits, int64_t ld, int n_utt, int beams, int V, const float* cum, int first_step,
                             int no_eos, int force_eos, int pad_idx, int eos_idx, int unk_idx, float unk_penalty, int K,
                             float* cand_val, int* cand_idx, const int* seqs, int seq_ld, int S, int G, hipStream_t s,
-                            const int* d_slots = nullptr, const BannedList* banned = nullptr);
+                            const int* d_slots = nullptr, const BannedList* banned = nullptr, const BoostList* boost = nullptr);
 // the same search for large vocabularies: every (row, 1/32 of V) on its own workgroup, then a merge per utterance;
 // ws_f / ws_i: workspaces of beam_ws_floats / beam_ws_ints elements
 bool beam_chunked(int V, int beams, int K);
@@ -634,7 +645,8 @@ size_t beam_ws_ints(int rows, int K);
 void launch_beam_candidates_chunked(float* logits, int64_t ld, int n_utt, int beams, int V, const float* cum, int first_step, int no_eos,
                                     int force_eos, int pad_idx, int eos_idx, int unk_idx, float unk_penalty, int K, float* cand_val,
                                     int* cand_idx, const int* seqs, int seq_ld, int S, int G, float* ws_f, int* ws_i, hipStream_t s,
-                                    const int* d_rows = nullptr, const int* d_slots = nullptr, const BannedList* banned = nullptr);
+                                    const int* d_rows = nullptr, const int* d_slots = nullptr, const BannedList* banned = nullptr,
+                                    const BoostList* boost = nullptr);
 // device-resident beam-search state of one sc_generate_text call (k_beam.hip: beam_select_kernel)
 struct BeamSelectArgs {
     const float* cand_val = nullptr;  // [n][K] best first

@@ -370,10 +370,19 @@ struct BannedHost {
     int n = 0;
 };
 void banned_blocked_tokens(const int32_t* seq, int S, const BannedHost& b, std::vector<int32_t>& out);
+// sc_generate_text_boosted: the caller's boost phrases (host CSR, any order; PhraseBoostProcessor) and the boost per matched
+// token; checked, sorted (boost_list.h) and copied to the device once per call by run_generate_beam
+struct BoostHost {
+    const int32_t* tokens = nullptr;
+    const int32_t* offsets = nullptr;  // [n + 1]
+    int n = 0;
+    float boost = 0.f;
+};
 void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens,
                        const sc_gen_opts& o, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
                        int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, const int32_t* h_forced_tokens,
-                       int forced_len, const XattnCapture* xcap = nullptr, const BannedHost* banned = nullptr, int prefix_stride = 0);
+                       int forced_len, const XattnCapture* xcap = nullptr, const BannedHost* banned = nullptr, int prefix_stride = 0,
+                       const BoostHost* boost = nullptr);
 void run_identify_language(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix,
                            int prefix_len, const int32_t* h_cand, int n_cand, float* h_lprob, int32_t* h_best);
 void run_score_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens,
@@ -398,7 +407,8 @@ void run_t2u_ar(Model& m, const float* d_dec_hidden, int n, int s_text, const in
 void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, const int* d_text_lens, float* d_out);
 void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                        const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                       float* d_dec_hidden, int max_len, const BannedHost* banned = nullptr, int prefix_stride = 0);
+                       float* d_dec_hidden, int max_len, const BannedHost* banned = nullptr, int prefix_stride = 0,
+                       const BoostHost* boost = nullptr);
 // sampled generation (model_sample.hip): outputs [n][num_gens][...], hypotheses of an utterance sorted by score
 void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                           const sc_sample_opts& so, const uint64_t* h_streams, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,

@@ -25,7 +25,7 @@ int text_max_len(const Model& m, const sc_gen_opts& o, int s_enc) {
 
 void run_generate_text_beam(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                             const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                            float* d_dec_hidden, const BannedHost* banned = nullptr, int prefix_stride = 0);
+                            float* d_dec_hidden, const BannedHost* banned = nullptr, int prefix_stride = 0, const BoostHost* boost = nullptr);
 
 // --------------------------------------------------------------------------------------------- //
 // Streaming monotonic decoder (cfg 5).  One row; the state lives in the handle between calls.
@@ -539,7 +539,7 @@ void run_identify_language(Model& m, const float* d_enc, int n, int s_enc, const
 void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens,
                        const sc_gen_opts& o, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
                        int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, const int32_t* h_forced_tokens,
-                       int forced_len, const XattnCapture* xcap, const BannedHost* banned, int prefix_stride) {
+                       int forced_len, const XattnCapture* xcap, const BannedHost* banned, int prefix_stride, const BoostHost* boost) {
     const sc_config& cfg = m.cfg;
     const int M = cfg.model_dim;
     SC_CHECK(n > 0 && s_enc > 0, "sc_generate_text: empty batch");
@@ -563,10 +563,12 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
                  o.beam_size, o.no_repeat_ngram_size);
         const bool has_banned = banned && banned->n > 0;
         SC_CHECK(!xcap || !has_banned, "sc_generate_text_capture: banned sequences are not supported");
-        if (o.beam_size > 1 || o.no_repeat_ngram_size > 0 || has_banned) {  // step processors run in the host-driven step loop
+        const bool has_boost = boost && boost->n > 0 && boost->boost != 0.f;
+        SC_CHECK(!xcap || !has_boost, "sc_generate_text_capture: boost phrases are not supported");
+        if (o.beam_size > 1 || o.no_repeat_ngram_size > 0 || has_banned || has_boost) {  // step processors run in the host-driven step loop
             if (m.engine) m.engine->expect(m, -n);
             run_generate_text_beam(m, d_enc, n, s_enc, h_enc_lens, o, h_prefix, prefix_len, h_out_ids, h_out_lens, h_scores,
-                                   d_dec_hidden, has_banned ? banned : nullptr, prefix_stride);
+                                   d_dec_hidden, has_banned ? banned : nullptr, prefix_stride, has_boost ? boost : nullptr);
             return;
         }
         SC_CHECK(prefix_len >= 1, "sc_generate_text: the prompt must hold at least one token");
@@ -848,10 +850,10 @@ void banned_blocked_tokens(const int32_t* seq, int S, const BannedHost& b, std::
 
 void run_generate_text_beam(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                             const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                            float* d_dec_hidden, const BannedHost* banned, int prefix_stride) {
+                            float* d_dec_hidden, const BannedHost* banned, int prefix_stride, const BoostHost* boost) {
     const DecStack W = unity_stack(m);
     run_generate_beam(m, W, d_enc, n, s_enc, h_enc_lens, o, h_prefix, prefix_len, h_out_ids, h_out_lens, h_scores, d_dec_hidden,
-                      text_max_len(m, o, s_enc), banned, prefix_stride);
+                      text_max_len(m, o, s_enc), banned, prefix_stride, boost);
 }
 
 // UnitYT2UModel generation of the v1 models (inference/generator.py:316-336): T2U encoder over the text decoder output,
@@ -906,6 +908,28 @@ BannedDevice upload_banned(Model& m, const BannedHost* banned, int V) {
     return d;
 }
 
+// PhraseBoostProcessor: the list is checked and sorted on the host (before any launch) and copied to the device once per call
+BoostDevice upload_boost(Model& m, const BoostHost* boost, int V, int pad_idx, int eos_idx) {
+    BoostDevice d;
+    if (!boost || boost->n <= 0 || boost->boost == 0.f) return d;
+    BoostSorted sorted;
+    const std::string why = boost_list_build(boost->tokens, boost->offsets, boost->n, V, pad_idx, eos_idx, sorted);
+    SC_CHECK(why.empty(), "%s", why.c_str());
+    const std::string bad = boost_value_check(boost->boost);
+    SC_CHECK(bad.empty(), "%s", bad.c_str());
+    const size_t total = sorted.tokens.size();
+    d.store = Buf<int>(m.pp(), total + sorted.n + 1);
+    SC_HIP(hipMemcpyAsync(d.store.get(), sorted.tokens.data(), total * 4, hipMemcpyHostToDevice, m.stream));
+    SC_HIP(hipMemcpyAsync(d.store.get() + total, sorted.offsets.data(), (size_t)(sorted.n + 1) * 4, hipMemcpyHostToDevice, m.stream));
+    SC_HIP(hipStreamSynchronize(m.stream));  // `sorted` is a host temporary
+    d.list.tokens = d.store.get();
+    d.list.offsets = d.store.get() + total;
+    d.list.n = sorted.n;
+    d.list.max_len = sorted.max_len;
+    d.list.beta = boost->boost;
+    return d;
+}
+
 // fairseq2.cpp `_fan_out_encoder_output`: row r of the result is the encoder output of item r / per_item
 Buf<float> fan_out_encoder(Model& m, const float* d_enc, int n, int per_item, int s_enc) {
     const int M = m.cfg.model_dim, nb = n * per_item;
@@ -955,7 +979,7 @@ void hidden_of_best(Model& m, const float* d_enc, int n, int s_enc, const int32_
 // Beam search over one decoder stack (the UnitY text decoder or the v1 autoregressive unit decoder).
 void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                        const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                       float* d_dec_hidden, int max_len, const BannedHost* banned, int prefix_stride) {
+                       float* d_dec_hidden, int max_len, const BannedHost* banned, int prefix_stride, const BoostHost* boost) {
     // prefix_stride: 0 = one prompt for all; otherwise utterance u's prompt is h_prefix[u * prefix_stride + ...], fed to each of its beams
     const std::vector<DecoderLayer>& dec_layers = *W.layers;
     const int M = m.cfg.model_dim, V = W.vocab, B = o.beam_size, L = (int)dec_layers.size();
@@ -966,6 +990,8 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
     check_generation_limits("sc_generate_text", o, prefix_len, max_len, W.max_seq_len, n, s_enc, h_enc_lens);
     const BannedDevice banned_dev = upload_banned(m, banned, V);
     const BannedList& bl = banned_dev.list;
+    const BoostDevice boost_dev = upload_boost(m, boost, V, W.pad_idx, W.eos_idx);
+    const BoostList& bo = boost_dev.list;
     const float len_penalty = o.len_penalty;
     const bool normalize = o.normalize_scores != 0;
 
@@ -1130,16 +1156,17 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
         }
         project_rows();
         // step processors: not on the forced-EOS step (blocking EOS there would leave no hypothesis)
-        const bool ban = (G > 0 || bl.n > 0) && step != max_len - 2;
+        const bool ban = (G > 0 || bl.n > 0 || bo.n > 0) && step != max_len - 2;
         if (chunked) {
             launch_beam_candidates_chunked(c.logits, ldl, n, B, V, d_cum, step == start, step < o.min_seq_len, step == max_len - 2,
                                            W.pad_idx, W.eos_idx, W.unk_idx, o.unk_penalty, K, d_cand_val, d_cand_idx,
                                            ban ? d_seqs_cur : nullptr, max_len, step + 1, G, ws_f, ws_i, m.stream,
-                                           compact ? d_rows_live : nullptr, compact ? d_slots : nullptr, bl.n > 0 ? &bl : nullptr);
+                                           compact ? d_rows_live : nullptr, compact ? d_slots : nullptr, bl.n > 0 ? &bl : nullptr,
+                                           bo.n > 0 ? &bo : nullptr);
         } else {
             launch_beam_candidates(c.logits, ldl, n, B, V, d_cum, step == start, step < o.min_seq_len, step == max_len - 2, W.pad_idx,
                                    W.eos_idx, W.unk_idx, o.unk_penalty, K, d_cand_val, d_cand_idx, ban ? d_seqs_cur : nullptr, max_len,
-                                   step + 1, G, m.stream, compact ? d_slots : nullptr, bl.n > 0 ? &bl : nullptr);
+                                   step + 1, G, m.stream, compact ? d_slots : nullptr, bl.n > 0 ? &bl : nullptr, bo.n > 0 ? &bo : nullptr);
         }
         BeamSelectArgs a;
         a.cand_val = d_cand_val;

@@ -1,10 +1,10 @@
 from .aligner import AlignmentExtractor, word_timestamps
-from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, SequenceGeneratorOptions, TopKSampler, TopPSampler
+from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, PhraseBoostProcessor, SequenceGeneratorOptions, TopKSampler, TopPSampler
 from .pretssel_generator import PretsselGenerator
 from .prosody_encoder import ProsodyEncoder
 from .transcriber import Transcriber, Transcription, TranscriptionToken, TranscriptionTokenStats
 from .unit_extractor import UnitExtractor
 from .translator import BatchedSpeechOutput, LanguageId, Modality, SampledHypothesis, Task, Translator
 
-__all__ = ["AlignmentExtractor", "BannedSequenceProcessor", "BatchedSpeechOutput", "LanguageId", "Modality", "NGramRepeatBlockProcessor", "PretsselGenerator", "ProsodyEncoder", "SampledHypothesis", "SequenceGeneratorOptions", "Task", "TopKSampler", "TopPSampler", "Transcriber", "Transcription", "TranscriptionToken",
+__all__ = ["AlignmentExtractor", "BannedSequenceProcessor", "BatchedSpeechOutput", "LanguageId", "Modality", "NGramRepeatBlockProcessor", "PhraseBoostProcessor", "PretsselGenerator", "ProsodyEncoder", "SampledHypothesis", "SequenceGeneratorOptions", "Task", "TopKSampler", "TopPSampler", "Transcriber", "Transcription", "TranscriptionToken",
            "TranscriptionTokenStats", "Translator", "UnitExtractor", "word_timestamps"]

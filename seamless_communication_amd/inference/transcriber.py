@@ -38,6 +38,7 @@ from ..tokenizer import NllbTextTokenizer
 from .. import cards as _cards
 from ..lid import identify_encoded
 from ..scoring import pad_sequences, target_sequence
+from .generator import PhraseBoostProcessor, encode_bias_phrases
 from .translator import _ARCHS, _load_state_dict, _resolve_card
 
 # generator options the reference passes to fairseq2's BeamSearchSeq2SeqGenerator (transcriber.py run_inference); the
@@ -376,9 +377,57 @@ class Transcriber:
                 out[i] = self._words(d, seconds[i], filter_width, lang, found[i])
         return out  # type: ignore[return-value]
 
+    def _boost_args(self, bias_phrases, bias_boost: float) -> Dict[str, Any]:
+        """``bias_phrases`` (strings or token lists) as generate_text's phrase-boost keywords; checked here, before any device
+        work (``ValueError``).  No phrases or ``bias_boost == 0``: no keyword, the plain call."""
+        if not bias_phrases:
+            return {}
+        proc = PhraseBoostProcessor(encode_bias_phrases(self.tokenizer, bias_phrases), bias_boost)
+        return {"boost_seqs": proc.phrases, "boost": proc.boost} if proc.phrases and proc.boost != 0.0 else {}
+
+    def _long_biased(self, wavs: List[Tensor], seconds: List[float], sample_rate: int, lang: Optional[str], opts: Dict[str, Any],
+                     padded_encoder: bool, lid_item: int, filter_width: int, boost_kw: Dict[str, Any]):
+        """The segments of ``transcribe_long`` with boost phrases: generate_text (the host-driven step loop, where the step
+        processors run) in calls of up to ``CAPTURE_ROWS`` rows, grouped as ``_decode_batch`` groups them, then one teacher-forced
+        capture pass for the times, as ``transcribe_beam`` does -> ([Transcription], the language, its identification or None)."""
+        model = self.model
+        opts = dict(opts)
+        beam_size = int(opts.pop("beam_size", None) or 1)
+        enc, enc_lens, frames = self._encode(wavs, sample_rate, padded_encoder)
+        lid = None
+        if lang is None:
+            i = int(lid_item)
+            lid = identify_encoded(model, self.tokenizer, enc[i : i + 1, : int(enc_lens[i])].contiguous(), enc_lens[i : i + 1])[0]
+            lang = lid.lang
+        prefix = self.tokenizer.target_prefix(lang)
+        n = len(wavs)
+        order = sorted(range(n), key=lambda i: (int(enc_lens[i]), i))
+        per_source = self._gen_limits(opts, len(prefix), 1)[0][0] != 0.0
+        calls: List[List[int]] = []
+        for i in order:
+            full = not calls or len(calls[-1]) >= self.CAPTURE_ROWS
+            if full or (per_source and int(frames[calls[-1][0]]) != int(frames[i])):
+                calls.append([])
+            calls[-1].append(i)
+        o = {**GENERATOR_DEFAULTS, **opts}
+        seqs: List[Optional[List[int]]] = [None] * n
+        for pick in calls:
+            width = max(int(enc_lens[i]) for i in pick)
+            src = max(int(frames[i]) for i in pick)
+            soft, hard, unk = self._gen_limits(opts, len(prefix), src)
+            ids, lens, _, _ = model.generate_text(enc[pick, :width].contiguous(), [int(enc_lens[i]) for i in pick], prefix, beam_size=beam_size,
+                                                  soft_max_seq_len=soft, hard_max_seq_len=hard, unk_penalty=unk, use_graph=self.use_graph,
+                                                  want_hidden=False, len_penalty=float(o["len_penalty"]),
+                                                  normalize_scores=bool(o["normalize_scores"]), source_len=src, **boost_kw)
+            for b, i in enumerate(pick):
+                seq = [int(t) for t in ids[b, : int(lens[b])]]
+                seqs[i] = seq if len(seq) > len(prefix) + 1 else None  # EOS first: no token, no timestamp
+        return self._timed(seqs, enc, enc_lens, seconds, filter_width, [lang] * n, [None] * n), lang, lid
+
     @torch.inference_mode()
     def transcribe_long(self, audio: Union[str, Tensor], src_lang: Optional[str], filter_width: int = 3, sample_rate: int = 16000,
                         chunk_size_sec: float = 20, pause_length_sec: float = 1, segmenter: Optional[Any] = None, padded_encoder: bool = False,
+                        bias_phrases: Optional[Sequence[Any]] = None, bias_boost: float = 2.0,
                         **sequence_generator_options: Dict) -> Transcription:
         """Audio of any length -> ONE ``Transcription`` with the words of every speech segment in order and ABSOLUTE ``time_s``
         (the segment's ``start / sample_rate`` plus the time inside the segment).  ``segments`` holds
@@ -388,12 +437,17 @@ class Transcriber:
         in samples.  Segments are clamped to the waveform, empty ones dropped.  No speech: an empty result with ``segments == []``.
         ``src_lang=None``: the language is identified on the longest segment and used for all; ``lid`` holds that identification.
         Two departures from the reference: its ``transcribe`` returns the LAST segment only (a bug of
-        its joining loop) and leaves every time relative to its segment."""
-        opts = self._greedy_options(sequence_generator_options)
+        its joining loop) and leaves every time relative to its segment.
+        ``bias_phrases`` (strings or token lists) with ``bias_boost``: phrase boosting (``PhraseBoostProcessor``; an extension
+        whose effect on real speech has not been evaluated).  The segments are then generated by sc_generate_text_boosted in
+        calls of up to 64 rows (``beam_size`` defaults to 1 and may be larger) and timed by the teacher-forced capture pass,
+        as ``transcribe_beam`` does; a word's ``prob`` is then the raw log-probability's."""
+        boost_kw = self._boost_args(bias_phrases, bias_boost)
+        opts = dict(sequence_generator_options) if boost_kw else self._greedy_options(sequence_generator_options)
         wav = _waveform(audio, sample_rate)
         if src_lang is not None:
             self.tokenizer.target_prefix(src_lang)
-        self._gen_limits(opts, 2, 1)  # option errors before any device work
+        self._gen_limits({k: v for k, v in opts.items() if not (boost_kw and k == "beam_size")}, 2, 1)  # option errors before any device work
         if segmenter is None:
             from ..segment import SpeechSegmenter
 
@@ -407,6 +461,14 @@ class Transcriber:
         if not spans:
             return Transcription([], src_lang, None, segments=[])
         longest = max(range(len(spans)), key=lambda i: (spans[i][1] - spans[i][0], -i))
+        if boost_kw:
+            ones, lang, lid = self._long_biased([wav[a:b] for a, b in spans], [(b - a) / sample_rate for a, b in spans], sample_rate, src_lang,
+                                                opts, padded_encoder, longest, filter_width, boost_kw)
+            segments, tokens = [], []
+            for (a, b), one in zip(spans, ones):
+                segments.append((a / sample_rate, b / sample_rate, one))
+                tokens += [TranscriptionToken(t.text, a / sample_rate + t.time_s, t.prob) for t in one.tokens]
+            return Transcription(tokens, lang, lid, segments=segments)
         decoded, lang, lid = self._decode_batch([wav[a:b] for a, b in spans], sample_rate, src_lang, opts, padded_encoder, lid_item=longest)
         segments, tokens = [], []
         for (a, b), d in zip(spans, decoded):
@@ -524,12 +586,15 @@ class Transcriber:
 
     @torch.inference_mode()
     def transcribe_beam(self, audio: Union[str, Tensor], src_lang: Optional[str], beam_size: int = 5, filter_width: int = 3,
-                        sample_rate: int = 16000, **sequence_generator_options: Dict) -> Transcription:
+                        sample_rate: int = 16000, bias_phrases: Optional[Sequence[Any]] = None, bias_boost: float = 2.0,
+                        **sequence_generator_options: Dict) -> Transcription:
         """``transcribe`` with a beam search: sc_generate_text at ``beam_size`` with ``transcribe``'s generator options and
         defaults, then the attention rows of the WINNING hypothesis from one teacher-forced pass.  (The reference's hook
         sums the rows over every live beam)  A word's ``prob`` is the raw log-probability's, as
-        in ``align``."""
+        in ``align``.  ``bias_phrases`` (strings or token lists) with ``bias_boost``: phrase boosting inside the search
+        (``PhraseBoostProcessor``; an extension whose effect on real speech has not been evaluated)."""
         model = self.model
+        boost_kw = self._boost_args(bias_phrases, bias_boost)
         wav = _waveform(audio, sample_rate)
         opts = dict(sequence_generator_options)
         enc, enc_lens, frames = self._encode([wav], sample_rate)
@@ -543,7 +608,7 @@ class Transcriber:
         ids, lens, _, _ = model.generate_text(enc, enc_lens.tolist(), prefix, beam_size=int(beam_size), soft_max_seq_len=soft,
                                               hard_max_seq_len=hard, unk_penalty=unk, use_graph=self.use_graph, want_hidden=False,
                                               len_penalty=float(o["len_penalty"]), normalize_scores=bool(o["normalize_scores"]),
-                                              source_len=int(frames[0]))
+                                              source_len=int(frames[0]), **boost_kw)
         seq = [int(t) for t in ids[0, : int(lens[0])]]
         seqs = [seq if len(seq) > len(prefix) + 1 else None]  # EOS first: no token, no timestamp
         return self._timed(seqs, enc, enc_lens, [wav.size(0) / sample_rate], filter_width, [src_lang], [lid])[0]

@@ -39,7 +39,7 @@ from ..config import (S2STConfig, seamless_expressivity, seamless_m4t_large, sea
                       tiny_expressive_config, tiny_v1_config)
 from ..runtime import HipS2STModel
 from ..tokenizer import CharTokenizer, NllbTextTokenizer, UnitTokenizer
-from .generator import BannedSequenceProcessor, NGramRepeatBlockProcessor, SequenceGeneratorOptions, check_sampling
+from .generator import SequenceGeneratorOptions, check_sampling, encode_bias_phrases, split_step_processors
 from ..scoring import score as _score
 from ..lid import LanguageId, identify_encoded as _identify_encoded, identify_language as _identify_language
 
@@ -523,18 +523,20 @@ class Translator:
     def _step_processor_args(opts: SequenceGeneratorOptions) -> Tuple[int, Dict[str, Any]]:
         """``opts.step_processor`` as the generation calls take it: (no_repeat_ngram_size, extra keywords - passed only when set:
         models without the keyword keep working)."""
-        ngram = 0
         step_kw: Dict[str, Any] = {}
-        proc = opts.step_processor
-        if proc is not None:
-            if isinstance(proc, NGramRepeatBlockProcessor):
-                ngram = proc.ngram_size
-            elif isinstance(proc, BannedSequenceProcessor):
-                if proc.banned_seqs:
-                    step_kw["banned_seqs"] = proc.banned_seqs
-            else:
-                raise NotImplementedError("the HIP path runs NGramRepeatBlockProcessor and BannedSequenceProcessor step processors only")
-        return ngram, step_kw
+        ngram_proc, banned, boost = split_step_processors(opts.step_processor)
+        if banned is not None and banned.banned_seqs:
+            step_kw["banned_seqs"] = banned.banned_seqs
+        if boost is not None and boost.phrases and boost.boost != 0.0:
+            step_kw["boost_seqs"] = boost.phrases
+            step_kw["boost"] = boost.boost
+        return (ngram_proc.ngram_size if ngram_proc is not None else 0), step_kw
+
+    def encode_bias_phrases(self, phrases: Sequence[str]) -> List[List[int]]:
+        """Strings -> the token sequences a ``PhraseBoostProcessor`` takes: each string as the tokenizer writes it inside a
+        sentence (its first piece carries the word-boundary mark).  Strings without a token and duplicates are dropped; of two
+        phrases in a prefix relation the shorter is kept, with a warning (the list must be prefix-free)."""
+        return encode_bias_phrases(self.text_tokenizer, phrases)
 
     @torch.inference_mode()
     def sample(
@@ -565,6 +567,8 @@ class Translator:
         check_sampling(sampler, temperature, num_gens)
         opts = text_generation_opts or SequenceGeneratorOptions(beam_size=5, soft_max_seq_len=(1, 200))
         ngram, step_kw = self._step_processor_args(opts)
+        if "boost_seqs" in step_kw:
+            raise ValueError("sampled generation takes no PhraseBoostProcessor (the boost runs in the beam-search step)")
         _, seqs, src_lens, _ = self._source_batch(input, input_modality, src_lang, sample_rate)
         if streams is not None and len(streams) != len(src_lens):
             raise ValueError(f"`streams` must hold one id per input item ({len(src_lens)}), but holds {len(streams)} instead.")
@@ -635,10 +639,12 @@ class Translator:
         elif not 1 <= text_generation_opts.beam_size <= 8:
             raise ValueError("beam_size must be in [1, 8] on the HIP path")
         ngram, step_kw = cls._step_processor_args(text_generation_opts)
+        if sampler is not None and "boost_seqs" in step_kw:
+            raise ValueError("sampled generation takes no PhraseBoostProcessor (the boost runs in the beam-search step)")
         trace = _trace if _trace is not None else {}
         want_speech = output_modality == Modality.SPEECH
         if tgt_lang is None and (want_speech or sampler is not None or step_kw):
-            raise ValueError("`tgt_lang=None` (identify the language) covers text output without a sampler or banned sequences")
+            raise ValueError("`tgt_lang=None` (identify the language) covers text output without a sampler, banned sequences or boost phrases")
 
         # every sc_* stage call returns with its stream drained, so host timers are stage times
         t0 = time.perf_counter()

@@ -312,15 +312,21 @@ class HipS2STModel(_Handle):
                       soft_max_seq_len=(1, 200), hard_max_seq_len: int = 1024, min_seq_len: int = 1,
                       unk_penalty: float = 0.0, use_graph: bool = True, want_hidden: bool = True,
                       len_penalty: float = 1.0, normalize_scores: bool = True, no_repeat_ngram_size: int = 0,
-                      source_len: int = 0, banned_seqs=None):
+                      source_len: int = 0, banned_seqs=None, boost_seqs=None, boost: float = 0.0):
         """-> (ids (n, max_len) int32, lens (n,), scores (n,), hidden (n, max_len-1, M) or None).
         ``source_len``: padded length of the source sequences the soft length rule refers to (fbank frames for speech);
         0 = the encoder output length.  ``banned_seqs``: token sequences (lists of ints) for the banned-sequence step
         processor (sc_generate_text_banned); None or an empty list is the plain call.  ``prefix``: the prompt of every row,
-        or an (n, prefix_len) array with one prompt per row (sc_generate_text_rows; not with ``banned_seqs``)."""
+        or an (n, prefix_len) array with one prompt per row (sc_generate_text_rows; not with ``banned_seqs``).
+        ``boost_seqs`` / ``boost``: phrases as token sequences and the bonus per matched token for the phrase-boost step
+        processor (sc_generate_text_boosted; the scores include the bonus); no phrases or ``boost == 0`` is the call
+        without them.  They take one prompt for all rows, like ``banned_seqs``."""
         assert enc.is_cuda and enc.is_contiguous()
         n, s_enc, M = enc.shape
         pre = _i32(prefix)
+        boosted = boost_seqs is not None and len(boost_seqs) > 0 and float(boost) != 0.0
+        if pre.ndim == 2 and boosted:
+            raise ValueError("boost_seqs take one prompt for all rows (sc_generate_text_boosted)")
         if pre.ndim == 2 and pre.shape[0] != n:
             raise ValueError(f"a per-row prefix must be (n={n}, prefix_len), got {pre.shape}")
         if pre.ndim == 2 and banned_seqs is not None and len(banned_seqs) > 0:
@@ -337,6 +343,16 @@ class HipS2STModel(_Handle):
         if pre.ndim == 2:
             check(self.lib.sc_generate_text_rows(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(pre), pre.shape[1],
                                                  _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden)), "sc_generate_text_rows")
+            return ids, lens, scores, hidden
+        if boosted:
+            b_tok = b_off = None
+            if banned_seqs is not None and len(banned_seqs) > 0:
+                b_tok, b_off = _lib.banned_csr(banned_seqs)
+            p_tok, p_off = _lib.banned_csr(boost_seqs)
+            check(self.lib.sc_generate_text_boosted(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(pre), len(pre),
+                                                    _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden), _ptr(b_tok), _ptr(b_off),
+                                                    0 if b_off is None else len(b_off) - 1, _ptr(p_tok), _ptr(p_off), len(p_off) - 1,
+                                                    float(boost)), "sc_generate_text_boosted")
             return ids, lens, scores, hidden
         if banned_seqs is not None and len(banned_seqs) > 0:
             b_tok, b_off = _lib.banned_csr(banned_seqs)
