@@ -764,6 +764,44 @@ int64_t sc_vad_windows(int64_t num_samples, int32_t window);
 int sc_vad_probs(const float* d_wav, int32_t n, int64_t wav_stride, const int64_t* h_num_samples, int32_t window, const sc_vad_opts* opts,
                  float* d_probs, int64_t probs_stride, float* d_db, float* h_stats);
 
+/* ---- Minimum-Bayes-risk selection (added within ABI v10, purely additive): of the hypotheses sampled for an utterance
+ * (sc_generate_text_sampled), the one with the highest expected utility against all of them.  An extension without a counterpart
+ * in the reference; the utility is this project's "token n-gram F-score" (DESIGN.md section 7o has the definition; it has not
+ * been evaluated on real translations).  For a hypothesis h and a pseudo-reference r (int32 token ids) and n = 1..max_order:
+ *   m_n = sum over n-grams g of min(count of g in h, count of g in r), H_n = max(|h| - n + 1, 0), R_n = max(|r| - n + 1, 0);
+ *   over the E orders with H_n > 0 and R_n > 0 (ascending n): P = (sum m_n / H_n) / E, R = (sum m_n / R_n) / E;
+ *   U(h, r) = (1 + beta^2) P R / (beta^2 P + R), 0 where E = 0 or the denominator is 0; all of it in double.
+ *   expected_i = (sum_j w_j U(h_i, h_j)) / (sum_j w_j) over ascending j, j = i included; best = the lowest i with the largest
+ *   expected_i.  n-grams are compared as token tuples (exact for every non-negative int32 id); every sum has a fixed order, so
+ *   an utterance's bits do not depend on its companions and equal hypotheses get equal values.
+ * No handle: it runs on the CURRENT device, on the default stream, and returns when the outputs are complete.  All pointers are
+ * HOST memory (the ids are on the host for detokenisation anyway).
+ *   typedef struct sc_mbr_opts { int32_t abi_version; int32_t max_order; float beta; int32_t reserved; } sc_mbr_opts;
+ *   int sc_mbr_select(const int32_t* h_ids,           [n][hyp_stride][len_stride]
+ *                     int32_t n, int32_t hyp_stride, int32_t len_stride,
+ *                     const int32_t* h_num_hyps,      [n], 1..hyp_stride
+ *                     const int32_t* h_lens,          [n][hyp_stride], 0..len_stride
+ *                     const float* h_weights_or_null, [n][hyp_stride]; NULL: every weight 1
+ *                     const sc_mbr_opts* opts,        NULL or all-zero = defaults (max_order 4, beta 1)
+ *                     double* h_expected,             [n][hyp_stride], 0 behind num_hyps
+ *                     int32_t* h_best,                [n]
+ *                     double* h_utility_or_null,      [n][hyp_stride][hyp_stride]: U(h_i, h_j), 0 behind num_hyps
+ *                     int32_t* h_match_or_null);      [n][hyp_stride][hyp_stride][4]: m_1..m_4, 0 for orders above max_order
+ *   opts: otherwise abi_version must be SC_ABI_VERSION; max_order 0 and beta 0 stand for their defaults; beta is used as
+ *         (double)beta.
+ * SC_ERR_INVALID, before any device work: a null required pointer, n outside 1..4096, hyp_stride outside 1..128, len_stride
+ * outside 1..1024, a count outside 1..hyp_stride, a length outside 0..len_stride, a negative token, max_order outside 0..4, a
+ * beta that is negative or not finite, a weight that is negative or not finite, an utterance whose weights sum to 0. */
+typedef struct sc_mbr_opts {
+    int32_t abi_version;
+    int32_t max_order; /* 1..4, default 4 */
+    float beta;        /* recall counts beta times as much as precision; default 1 */
+    int32_t reserved;
+} sc_mbr_opts;
+int sc_mbr_select(const int32_t* h_ids, int32_t n, int32_t hyp_stride, int32_t len_stride, const int32_t* h_num_hyps, const int32_t* h_lens,
+                  const float* h_weights_or_null, const sc_mbr_opts* opts, double* h_expected, int32_t* h_best, double* h_utility_or_null,
+                  int32_t* h_match_or_null);
+
 /* The kernel-level test hooks (sc_op_*) and the dispatch introspection the parity tests drive are exported too but are NOT part
  * of the drop-in boundary: include/seamless_hip_internal.h. */
 

@@ -160,6 +160,10 @@ class sc_vad_opts(C.Structure):
                 ("noise_ceiling_db", C.c_float), ("min_margin_db", C.c_float), ("range_fraction", C.c_float), ("slope_db", C.c_float)]
 
 
+class sc_mbr_opts(C.Structure):
+    _fields_ = [("abi_version", _i), ("max_order", _i), ("beta", C.c_float), ("reserved", _i)]
+
+
 class sc_aligner_config(C.Structure):
     _fields_ = [
         ("abi_version", _i), ("model_dim", _i), ("feat_dim", _i), ("text_layers", _i), ("feat_layers", _i),
@@ -282,6 +286,7 @@ SIGNATURES = {
     "sc_resample": (C.c_int, [_P, _i, C.c_int64, _P, _i, _i, C.POINTER(sc_resample_opts), _P, C.c_int64, _P]),
     "sc_vad_windows": (C.c_int64, [C.c_int64, _i]),
     "sc_vad_probs": (C.c_int, [_P, _i, C.c_int64, _P, _i, C.POINTER(sc_vad_opts), _P, C.c_int64, _P, _P]),
+    "sc_mbr_select": (C.c_int, [_P, _i, _i, _i, _P, _P, _P, C.POINTER(sc_mbr_opts), _P, _P, _P, _P]),
     "sc_op_resample_bank": (C.c_int, [_i, _i, C.POINTER(sc_resample_opts), _PI, _PI, _P, _P, C.c_int64]),
     "sc_op_resample_plan": (C.c_int, [_i, _i, C.POINTER(sc_resample_opts), _P]),
     "sc_op_knob": (C.c_int, [C.c_char_p, C.c_int]),

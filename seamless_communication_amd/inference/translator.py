@@ -41,6 +41,7 @@ from ..runtime import HipS2STModel
 from ..tokenizer import CharTokenizer, NllbTextTokenizer, UnitTokenizer
 from .generator import SequenceGeneratorOptions, check_sampling, encode_bias_phrases, split_step_processors
 from ..scoring import score as _score
+from ..mbr import MBRHypothesis, mbr_decode as _mbr_decode
 from ..lid import LanguageId, identify_encoded as _identify_encoded, identify_language as _identify_language
 
 logger = logging.getLogger(__name__)
@@ -590,6 +591,9 @@ class Translator:
                                               step_lprobs=step_lprob[b, g, : lens[b, g]].tolist(), score=float(scores[b, g])))
             out.append(hyps)
         return out
+
+    # sampling, then minimum-Bayes-risk selection among the samples (mbr.py)
+    mbr_decode = _mbr_decode
 
     # translator.py:155-196
     @classmethod
