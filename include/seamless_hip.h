@@ -436,6 +436,34 @@ int sc_generate_text_rows(sc_model* m, const float* d_enc, int32_t n, int32_t s_
                           const sc_gen_opts* opts, const int32_t* h_prefix_rows /* [n][prefix_len] */, int32_t prefix_len,
                           int32_t* h_out_ids, int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden);
 
+/* FORCED TARGET PREFIXES: sc_generate_text with one prompt per row, of ANY length per row (additive, ABI 10).  Row b is fed
+ * h_prompt_rows[b][0 .. h_prompt_lens[b]) - normally `</s> __lang__ p1 .. pk`, k = 0 allowed - and generates from there; what
+ * lies behind a row's length is ignored.  max_len = sc_text_max_len(opts, s_enc), shared by the call.
+ * The contract: for every row b the ids, the length, the score and the decoder-output rows are, bit for bit, those of row b of
+ * the uniform call (sc_generate_text / _banned / _boosted) on the same batch whose shared prompt is row b's prompt.  Hence: a
+ * greedy score leaves the prompt out, a beam score includes the echoed prompt's raw log-probabilities; the step processors
+ * (n-gram, banned sequences, boost phrases) see the prompt as part of the row's sequence, but nothing is chosen, blocked or
+ * boosted at a forced position; min_seq_len, unk_penalty and the forced EOS at max_len - 2 act on free positions only.
+ * One qualification, for d_dec_hidden in a beam search (beam_size > 1 or any step processor): there the decoder outputs do not
+ * come from the step but from one teacher-forced pass over the chosen hypotheses of the whole batch, whose products are chosen
+ * by its row count n * (longest hypothesis - 1), at most 64 rows or more.  They carry the uniform call's bits when both calls'
+ * passes fall on the same side of that threshold and agree to fp32 re-association otherwise - as with sc_generate_text_rows;
+ * ids, lengths and scores are not affected.
+ * With all lengths equal the call IS sc_generate_text_rows (with the banned / boost lists of sc_generate_text_boosted).  Mixed
+ * lengths stay ONE batch on every path: the greedy chain and the beam loop echo the prompts up to the shortest one on the host
+ * and handle the longer ones inside the step, per row; the decode engine takes the per-row lengths in its admit record, which
+ * holds at most 12 prompt tokens - a call with a longer prompt runs on the handle's own chain as a whole.
+ * Lists as sc_generate_text_boosted's (n_banned == 0 / n_boost == 0: none).
+ * SC_ERR_INVALID before any device work, sc_last_error naming the row: a NULL pointer, a length outside 1 .. prompt_stride or
+ * >= max_len, a token outside the vocabulary, pad or EOS at any prompt position but 0, and whatever the banned / boosted
+ * entries reject.  Not evaluated on real speech.  sc_generate_text_sampled and sc_generate_text_capture keep the shared prompt. */
+int sc_generate_text_prompts(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
+                             const sc_gen_opts* opts, const int32_t* h_prompt_rows /* [n][prompt_stride] */, int32_t prompt_stride,
+                             const int32_t* h_prompt_lens /* [n], 1 .. prompt_stride */, int32_t* h_out_ids, int32_t* h_out_lens,
+                             float* h_out_scores, float* d_dec_hidden, const int32_t* h_banned_tokens,
+                             const int32_t* h_banned_offsets, int32_t n_banned, const int32_t* h_boost_tokens,
+                             const int32_t* h_boost_offsets, int32_t n_boost, float boost);
+
 /* a12-a17: UnitYNART2UModel.forward + argmax + unit decoding
  * (models/unity/model.py:379-441, generator.py:338-353).  h_text_seqs
  * [n][s_text] is text_seqs[:, :-1] (pad filled), h_text_lens its PaddingMask.

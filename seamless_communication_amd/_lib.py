@@ -209,6 +209,8 @@ SIGNATURES = {
     "sc_op_xattn_rows_tile": (C.c_int32, [_i]),
     "sc_identify_language": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P, _i, _P, _P]),
     "sc_generate_text_rows": (C.c_int, [_P, _P, _i, _i, _P, _P, _P, _i, _P, _P, _P, _P]),
+    "sc_generate_text_prompts": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _i,
+                                           C.c_float]),
     "sc_engine_create": (_P, [_P, C.POINTER(sc_engine_opts)]),
     "sc_engine_free": (None, [_P]),
     "sc_engine_attach": (C.c_int, [_P, _P]),

@@ -459,6 +459,53 @@ int sc_generate_text_rows(sc_model* m, const float* d_enc, int32_t n, int32_t s_
     SC_API_END
 }
 
+int sc_generate_text_prompts(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
+                             const sc_gen_opts* opts, const int32_t* h_prompt_rows, int32_t prompt_stride, const int32_t* h_prompt_lens,
+                             int32_t* h_out_ids, int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden,
+                             const int32_t* h_banned_tokens, const int32_t* h_banned_offsets, int32_t n_banned,
+                             const int32_t* h_boost_tokens, const int32_t* h_boost_offsets, int32_t n_boost, float boost) {
+    SC_API_BEGIN
+    SC_CHECK(m && d_enc && h_enc_lens && opts && h_prompt_rows && h_prompt_lens && h_out_ids && h_out_lens,
+             "sc_generate_text_prompts: null argument");
+    SC_CHECK(n > 0 && prompt_stride >= 1, "sc_generate_text_prompts: n=%d prompt_stride=%d", n, prompt_stride);
+    SC_CHECK(n_banned >= 0 && (n_banned == 0 || (h_banned_tokens && h_banned_offsets)), "sc_generate_text_prompts: bad banned list");
+    SC_CHECK(n_boost >= 0 && (n_boost == 0 || (h_boost_tokens && h_boost_offsets)), "sc_generate_text_prompts: bad phrase list");
+    const DecStack W = unity_stack(m->m);
+    const int max_len = text_max_len(m->m, *opts, s_enc);
+    int shortest = prompt_stride, longest = 0;
+    for (int b = 0; b < n; ++b) {
+        const int len = h_prompt_lens[b];
+        SC_CHECK(len >= 1 && len <= prompt_stride, "sc_generate_text_prompts: row %d: prompt length %d outside 1..%d", b, len, prompt_stride);
+        SC_CHECK(len < max_len, "sc_generate_text_prompts: row %d: prompt length %d >= effective max length %d", b, len, max_len);
+        const int32_t* p = h_prompt_rows + (size_t)b * prompt_stride;
+        for (int t = 0; t < len; ++t) {
+            SC_CHECK(p[t] >= 0 && p[t] < W.vocab, "sc_generate_text_prompts: row %d: prompt token %d outside the vocabulary", b, p[t]);
+            SC_CHECK(t == 0 || (p[t] != W.pad_idx && p[t] != W.eos_idx), "sc_generate_text_prompts: row %d: pad / EOS (%d) at prompt position %d", b,
+                     p[t], t);
+        }
+        shortest = std::min(shortest, len), longest = std::max(longest, len);
+    }
+    BannedHost bh;
+    bh.tokens = h_banned_tokens, bh.offsets = h_banned_offsets, bh.n = n_banned;
+    BoostHost ph;
+    ph.tokens = h_boost_tokens, ph.offsets = h_boost_offsets, ph.n = n_boost, ph.boost = boost;
+    validate_banned_host(bh.tokens, bh.offsets, bh.n, W.vocab, nullptr);
+    if (n_boost > 0) {
+        BoostSorted sorted;
+        const std::string why = boost_list_build(ph.tokens, ph.offsets, ph.n, W.vocab, W.pad_idx, W.eos_idx, sorted);
+        SC_CHECK(why.empty(), "%s", why.c_str());
+        const std::string bad = boost_value_check(boost);
+        SC_CHECK(bad.empty(), "%s", bad.c_str());
+    }
+    SC_HIP(hipSetDevice(m->m.device));
+    // equal lengths: sc_generate_text_rows with the lists; otherwise the shortest prompt is echoed for all rows and the per-row
+    // lengths go down with the call
+    run_generate_text(m->m, d_enc, n, s_enc, h_enc_lens, *opts, h_prompt_rows, shortest, h_out_ids, h_out_lens, h_out_scores, d_dec_hidden,
+                      nullptr, 0, nullptr, n_banned > 0 ? &bh : nullptr, /*prefix_stride=*/prompt_stride,
+                      n_boost > 0 && boost != 0.f ? &ph : nullptr, shortest == longest ? nullptr : h_prompt_lens);
+    SC_API_END
+}
+
 int sc_t2u_nar(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text, const int32_t* h_text_lens,
                const int32_t* h_text_seqs, float duration_factor, int32_t* h_unit_lens, int32_t* out_s_unit_max,
                int32_t* out_s_char_max) {

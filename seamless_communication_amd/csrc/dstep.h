@@ -16,6 +16,9 @@ struct StepCtx {
     int* d_finished = nullptr;
     int* d_out_len = nullptr;
     int* d_enc_lens = nullptr;
+    // greedy generation with per-row prompts (sc_generate_text_prompts): [nb] prompt lengths, read by the step's closing
+    // launch; it lives in the session's own int block (a replayed step graph holds this pointer) and is written per call
+    int* d_prompt_len = nullptr;
     float* d_lprob = nullptr;
     float* d_score = nullptr;
     float *x = nullptr, *h = nullptr, *wide = nullptr, *att = nullptr, *hN = nullptr, *logits = nullptr;

@@ -40,6 +40,7 @@ struct Request {
     int n = 0, s_enc = 0, max_len = 0, prefix_len = 0;
     int prefix_stride = 0;  // 0: one prompt for every row; otherwise row i's prompt starts at h_prefix[i * prefix_stride]
     const int32_t* h_prefix = nullptr;
+    const int32_t* h_prefix_lens = nullptr;  // per-row prompt lengths (sc_generate_text_prompts); null: prefix_len for every row
     const int32_t* h_enc_lens = nullptr;
     float* d_hidden = nullptr;
     hipEvent_t ready = nullptr;  // the rows' encoder K / V are written (recorded on the submitter's stream)
@@ -242,10 +243,10 @@ void Engine::Impl::admit(const std::vector<Live>& rows) {
         EngineAdmitRec& a = h_admit.p[i];
         a.rid = rows[i].rid;
         a.limit = q->max_len;
-        a.prefix_len = q->prefix_len;
+        a.prefix_len = q->h_prefix_lens ? q->h_prefix_lens[rows[i].row] : q->prefix_len;  // (Engine::fits: <= ENGINE_MAX_PREFIX)
         a.enc_len = q->h_enc_lens[rows[i].row];
         const int32_t* pre = q->h_prefix + (size_t)rows[i].row * q->prefix_stride;
-        for (int t = 0; t < ENGINE_MAX_PREFIX; ++t) a.prefix[t] = t < q->prefix_len ? pre[t] : cfg.pad_idx;
+        for (int t = 0; t < ENGINE_MAX_PREFIX; ++t) a.prefix[t] = t < a.prefix_len ? pre[t] : cfg.pad_idx;
     }
     SC_HIP(hipMemcpyAsync(d_admit.get(), h_admit.p, rows.size() * sizeof(EngineAdmitRec), hipMemcpyHostToDevice, em.stream));
     launch_engine_admit(d_admit, (int)rows.size(), er, cfg.pad_idx, em.stream);
@@ -454,13 +455,14 @@ void Engine::stats(sc_engine_stats* out, bool reset) {
 }
 
 void Engine::generate(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix, int prefix_len,
-                      int max_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, int prefix_stride) {
+                      int max_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, int prefix_stride,
+                      const int32_t* h_prefix_lens) {
     Impl& E = *p_;
     const sc_config& cfg = m.cfg;
     const int M = cfg.model_dim, se = E.o.s_enc;
     Request q;
     q.n = n, q.s_enc = s_enc, q.max_len = max_len, q.prefix_len = prefix_len;
-    q.h_prefix = h_prefix, q.prefix_stride = prefix_stride, q.h_enc_lens = h_enc_lens, q.d_hidden = d_dec_hidden;
+    q.h_prefix = h_prefix, q.prefix_stride = prefix_stride, q.h_prefix_lens = h_prefix_lens, q.h_enc_lens = h_enc_lens, q.d_hidden = d_dec_hidden;
     q.ids.assign((size_t)n * max_len, cfg.pad_idx);
     q.lens.assign(n, 0);
     q.scores.assign(n, 0.f);

@@ -50,12 +50,20 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// Where slot `slot` stands against its utterance's prompt (BeamPrompt): 0 = free step, 1 = the first free step (beam 0 only),
+// 2 = still inside the prompt.  Without per-utterance prompts the launch's own first_step flag decides.
+__device__ __forceinline__ int prompt_phase(const BeamPrompt& bp, int slot, int first_step) {
+    if (!bp.len) return first_step ? 1 : 0;
+    const int len = bp.len[bp.slot_utt ? bp.slot_utt[slot] : slot];
+    return bp.step + 1 < len ? 2 : (bp.step + 1 == len ? 1 : 0);
+}
+
 template <bool BANNED, bool BOOST = false>
 __device__ __forceinline__ void beam_candidates_body(float* logits, int64_t ld, int beams, int V, const float* __restrict__ cum,
                                                      int first_step, int no_eos, int force_eos, int pad_idx, int eos_idx, int unk_idx,
                                                      float unk_penalty, int K, float* __restrict__ cand_val, int* __restrict__ cand_idx,
                                                      const int* __restrict__ seqs, int seq_ld, int S, int G,
-                                                     const int* __restrict__ d_slots, const BannedList& bl,
+                                                     const int* __restrict__ d_slots, const BeamPrompt& bp, const BannedList& bl,
                                                      const BoostList& bo = BoostList{}) {
     __shared__ float red[4];
     __shared__ float lse[BEAM_MAX_K];
@@ -64,6 +72,9 @@ __device__ __forceinline__ void beam_candidates_body(float* logits, int64_t ld, 
     __shared__ int s_winner;
     const int n = blockIdx.x, tid = threadIdx.x;
     if (d_slots && n >= *d_slots) return;  // an idle slot (its utterance finished)
+    const int phase = prompt_phase(bp, n, first_step);  // uniform over the workgroup
+    if (phase == 2) return;                             // inside its prompt: beam_prompt_kernel wrote the list
+    first_step = phase;
     const int nb = first_step ? 1 : beams;
     for (int b = 0; b < nb; ++b) {
         const float* row = logits + ((int64_t)n * beams + b) * ld;
@@ -185,9 +196,9 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(float* logits, int
                                                               int force_eos, int pad_idx, int eos_idx, int unk_idx,
                                                               float unk_penalty, int K, float* __restrict__ cand_val,
                                                               int* __restrict__ cand_idx, const int* __restrict__ seqs,
-                                                              int seq_ld, int S, int G, const int* __restrict__ d_slots) {
+                                                              int seq_ld, int S, int G, const int* __restrict__ d_slots, BeamPrompt bp) {
     beam_candidates_body<false>(logits, ld, beams, V, cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val,
-                                cand_idx, seqs, seq_ld, S, G, d_slots, BannedList{});
+                                cand_idx, seqs, seq_ld, S, G, d_slots, bp, BannedList{});
 }
 
 // the same search with a banned-sequence list (launched only when the call carries one)
@@ -197,9 +208,9 @@ __global__ __launch_bounds__(256) void beam_candidates_banned_kernel(float* logi
                                                                      float unk_penalty, int K, float* __restrict__ cand_val,
                                                                      int* __restrict__ cand_idx, const int* __restrict__ seqs,
                                                                      int seq_ld, int S, int G, const int* __restrict__ d_slots,
-                                                                     BannedList bl) {
+                                                                     BannedList bl, BeamPrompt bp) {
     beam_candidates_body<true>(logits, ld, beams, V, cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val,
-                               cand_idx, seqs, seq_ld, S, G, d_slots, bl);
+                               cand_idx, seqs, seq_ld, S, G, d_slots, bp, bl);
 }
 
 // the same search with a phrase list (and a banned-sequence list, which may be empty)
@@ -209,9 +220,9 @@ __global__ __launch_bounds__(256) void beam_candidates_boost_kernel(float* logit
                                                                     float unk_penalty, int K, float* __restrict__ cand_val,
                                                                     int* __restrict__ cand_idx, const int* __restrict__ seqs,
                                                                     int seq_ld, int S, int G, const int* __restrict__ d_slots,
-                                                                    BannedList bl, BoostList bo) {
+                                                                    BannedList bl, BoostList bo, BeamPrompt bp) {
     beam_candidates_body<true, true>(logits, ld, beams, V, cum, first_step, no_eos, force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K,
-                                     cand_val, cand_idx, seqs, seq_ld, S, G, d_slots, bl, bo);
+                                     cand_val, cand_idx, seqs, seq_ld, S, G, d_slots, bp, bl, bo);
 }
 
 __global__ __launch_bounds__(256) void row_token_lprob_kernel(const float* __restrict__ logits, int64_t ld, int V,
@@ -227,6 +238,35 @@ __global__ __launch_bounds__(256) void row_token_lprob_kernel(const float* __res
     for (int i = threadIdx.x; i < V; i += 256) sm += expf(row[i] - mx);
     sm = block_reduce_sum(sm, red);
     if (threadIdx.x == 0) out[blockIdx.x] = row[token] - (mx + logf(sm));
+}
+
+// The forced step of an utterance inside its prompt (launch_beam_prompt): row_token_lprob_kernel's log-probability of the known
+// token in beam 0's row (the same loops and reductions: the same bits), then one candidate per beam - the beam itself with
+// that token, cum + lprob as one fp32 add (the host echo's `cum[r] += pref`).  Entries behind `beams` are never read:
+// beam_select_kernel stops at the beams-th live candidate, and a prompt holds no EOS behind position 0.
+__global__ __launch_bounds__(256) void beam_prompt_kernel(const float* __restrict__ logits, int64_t ld, int beams, int V,
+                                                          const float* __restrict__ cum, const int* __restrict__ seqs, int seq_ld, int K,
+                                                          float* __restrict__ cand_val, int* __restrict__ cand_idx, BeamPrompt bp,
+                                                          const int* __restrict__ d_slots) {
+    __shared__ float red[4];
+    const int u = blockIdx.x;
+    if (d_slots && u >= *d_slots) return;     // an idle slot
+    if (prompt_phase(bp, u, 0) != 2) return;  // uniform over the workgroup
+    const float* row = logits + (int64_t)u * beams * ld;
+    const int token = seqs[(int64_t)u * beams * seq_ld + bp.step + 1];
+    float mx = -INFINITY;
+    for (int i = threadIdx.x; i < V; i += 256) mx = fmaxf(mx, row[i]);
+    mx = block_reduce_max(mx, red);
+    float sm = 0.f;
+    for (int i = threadIdx.x; i < V; i += 256) sm += expf(row[i] - mx);
+    sm = block_reduce_sum(sm, red);
+    if ((int)threadIdx.x < K) {
+        const int i = threadIdx.x, beam = i % beams;
+        const bool in_vocab = token >= 0 && token < V;  // (the host checked the prompt against V)
+        const float lprob = in_vocab ? row[token] - (mx + logf(sm)) : -INFINITY;
+        cand_val[(int64_t)u * K + i] = i < beams ? cum[(int64_t)u * beams + beam] + lprob : -INFINITY;
+        cand_idx[(int64_t)u * K + i] = beam * V + (in_vocab ? token : 0);  // always a real (beam, token) pair
+    }
 }
 
 // --------------------------------------------------------------------------------------------- //
@@ -295,10 +335,12 @@ __global__ __launch_bounds__(256) void ngram_block_kernel(float* logits, int64_t
 // left alone (as in the single-workgroup search).
 __global__ __launch_bounds__(256) void step_processors_kernel(float* logits, int64_t ld, int V, int beams, int first_step,
                                                               const int* __restrict__ seqs, int seq_ld, int S, int G, BannedList bl,
-                                                              const int* __restrict__ d_rows) {
+                                                              const int* __restrict__ d_rows, BeamPrompt bp) {
     __shared__ int s_tail[BANNED_MAX_LEN];
     if (d_rows && (int)blockIdx.x >= *d_rows) return;
-    if (first_step && blockIdx.x % beams != 0) return;
+    const int phase = prompt_phase(bp, blockIdx.x / beams, first_step);
+    if (phase == 2) return;  // inside its prompt: no processor runs
+    if (phase == 1 && blockIdx.x % beams != 0) return;
     float* row = logits + (int64_t)blockIdx.x * ld;
     const int* seq = seqs + (int64_t)blockIdx.x * seq_ld;
     if (G > 0 && G < S) {
@@ -316,11 +358,13 @@ __global__ __launch_bounds__(256) void step_processors_kernel(float* logits, int
 // the three step processors in one launch (a call with a phrase list): n-gram, banned sequences (the list may be empty), boost
 __global__ __launch_bounds__(256) void step_processors_boost_kernel(float* logits, int64_t ld, int V, int beams, int first_step,
                                                                     const int* __restrict__ seqs, int seq_ld, int S, int G, BannedList bl,
-                                                                    BoostList bo, const int* __restrict__ d_rows) {
+                                                                    BoostList bo, const int* __restrict__ d_rows, BeamPrompt bp) {
     __shared__ int s_tail[BANNED_MAX_LEN];
     __shared__ BoostShared s_boost;
     if (d_rows && (int)blockIdx.x >= *d_rows) return;
-    if (first_step && blockIdx.x % beams != 0) return;
+    const int phase = prompt_phase(bp, blockIdx.x / beams, first_step);
+    if (phase == 2) return;  // inside its prompt: no processor runs
+    if (phase == 1 && blockIdx.x % beams != 0) return;
     float* row = logits + (int64_t)blockIdx.x * ld;
     const int* seq = seqs + (int64_t)blockIdx.x * seq_ld;
     if (G > 0 && G < S) {
@@ -394,7 +438,7 @@ __global__ __launch_bounds__(256) void beam_topk_partial_kernel(const float* __r
                                                                 const float* __restrict__ cum, int first_step, int no_eos, int force_eos,
                                                                 int pad_idx, int eos_idx, int unk_idx, float unk_penalty, int K,
                                                                 const float2* __restrict__ part, float* __restrict__ pval,
-                                                                int* __restrict__ pidx, const int* __restrict__ d_rows) {
+                                                                int* __restrict__ pidx, const int* __restrict__ d_rows, BeamPrompt bp) {
     __shared__ int s_val[4];
     __shared__ int s_idx[4];
     constexpr int EPT = 32;  // elements per thread: chunks of at most 8192 logits
@@ -404,7 +448,8 @@ __global__ __launch_bounds__(256) void beam_topk_partial_kernel(const float* __r
     float* out_val = pval + ((int64_t)r * BEAM_CH + c) * K;
     int* out_idx = pidx + ((int64_t)r * BEAM_CH + c) * K;
     const int start = c * clen, end = min(V, start + clen);
-    if ((first_step && b != 0) || start >= end) {  // first step: beam 0 only
+    const int phase = prompt_phase(bp, r / beams, first_step);  // (inside its prompt: the merge leaves the utterance's list alone)
+    if (phase == 2 || (phase == 1 && b != 0) || start >= end) {  // first step: beam 0 only
         if (tid < K) {
             out_val[tid] = -INFINITY;
             out_idx[tid] = 0x7fffffff;
@@ -442,12 +487,14 @@ __global__ __launch_bounds__(256) void beam_topk_partial_kernel(const float* __r
 }
 
 __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict__ pval, const int* __restrict__ pidx, int entries, int K,
-                                                         float* __restrict__ cand_val, int* __restrict__ cand_idx, const int* __restrict__ d_slots) {
+                                                         float* __restrict__ cand_val, int* __restrict__ cand_idx, const int* __restrict__ d_slots,
+                                                         BeamPrompt bp) {
     __shared__ int s_val[4];
     __shared__ int s_idx[4];
     constexpr int EPT = 16;  // beams x 32 chunks x K <= 16 x 32 x 16 = 8192 entries... the launcher checks entries <= 256 * EPT
     const int n = blockIdx.x, tid = threadIdx.x;
     if (d_slots && n >= *d_slots) return;  // an idle slot
+    if (prompt_phase(bp, n, 0) == 2) return;  // inside its prompt: beam_prompt_kernel wrote the list
     int val[EPT];
     int idx[EPT];
     unsigned taken = 0;
@@ -651,7 +698,7 @@ void check_boost_list(const BoostList& bo, int seq_ld, int S) {
 void launch_beam_candidates(float* logits, int64_t ld, int n_utt, int beams, int V, const float* cum, int first_step,
                             int no_eos, int force_eos, int pad_idx, int eos_idx, int unk_idx, float unk_penalty, int K,
                             float* cand_val, int* cand_idx, const int* seqs, int seq_ld, int S, int G, hipStream_t s, const int* d_slots,
-                            const BannedList* banned, const BoostList* boost) {
+                            const BannedList* banned, const BoostList* boost, const BeamPrompt& bp) {
     SC_CHECK(K >= 1 && K <= BEAM_MAX_K && beams >= 1 && beams <= BEAM_MAX_K, "beam search: beam_size %d / K %d out of range (max %d candidates)",
              beams, K, BEAM_MAX_K);
     SC_CHECK((int64_t)beams * V < (1ll << 31) - 1, "beam search: beam * vocabulary overflows the candidate index");
@@ -661,14 +708,14 @@ void launch_beam_candidates(float* logits, int64_t ld, int n_utt, int beams, int
         check_boost_list(*boost, seq_ld, S);
         hipLaunchKernelGGL(beam_candidates_boost_kernel, dim3(n_utt), dim3(256), 0, s, logits, ld, beams, V, cum, first_step, no_eos,
                            force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val, cand_idx, seqs, seq_ld, S, G, d_slots,
-                           has_banned ? *banned : BannedList{}, *boost);
+                           has_banned ? *banned : BannedList{}, *boost, bp);
     } else if (has_banned) {
         check_banned_list(*banned, seq_ld, S);
         hipLaunchKernelGGL(beam_candidates_banned_kernel, dim3(n_utt), dim3(256), 0, s, logits, ld, beams, V, cum, first_step, no_eos,
-                           force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val, cand_idx, seqs, seq_ld, S, G, d_slots, *banned);
+                           force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val, cand_idx, seqs, seq_ld, S, G, d_slots, *banned, bp);
     } else {
         hipLaunchKernelGGL(beam_candidates_kernel, dim3(n_utt), dim3(256), 0, s, logits, ld, beams, V, cum, first_step, no_eos, force_eos,
-                           pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val, cand_idx, seqs, seq_ld, S, G, d_slots);
+                           pad_idx, eos_idx, unk_idx, unk_penalty, K, cand_val, cand_idx, seqs, seq_ld, S, G, d_slots, bp);
     }
     SC_LAUNCH_CHECK();
 }
@@ -685,7 +732,7 @@ size_t beam_ws_ints(int rows, int K) { return (size_t)rows * BEAM_CH * K; }
 void launch_beam_candidates_chunked(float* logits, int64_t ld, int n_utt, int beams, int V, const float* cum, int first_step, int no_eos,
                                     int force_eos, int pad_idx, int eos_idx, int unk_idx, float unk_penalty, int K, float* cand_val,
                                     int* cand_idx, const int* seqs, int seq_ld, int S, int G, float* ws_f, int* ws_i, hipStream_t s,
-                                    const int* d_rows, const int* d_slots, const BannedList* banned, const BoostList* boost) {
+                                    const int* d_rows, const int* d_slots, const BannedList* banned, const BoostList* boost, const BeamPrompt& bp) {
     SC_CHECK(K >= 1 && K <= BEAM_MAX_K && beams >= 1 && beams <= BEAM_MAX_K, "beam search: beam_size %d / K %d out of range (max %d candidates)",
              beams, K, BEAM_MAX_K);
     SC_CHECK((int64_t)beams * V < (1ll << 31) - 1, "beam search: beam * vocabulary overflows the candidate index");
@@ -701,17 +748,18 @@ void launch_beam_candidates_chunked(float* logits, int64_t ld, int n_utt, int be
         if (has_banned) check_banned_list(*banned, seq_ld, S);
         check_boost_list(*boost, seq_ld, S);
         hipLaunchKernelGGL(step_processors_boost_kernel, dim3(rows), dim3(256), 0, s, logits, ld, V, beams, first_step, seqs, seq_ld, S, G,
-                           has_banned ? *banned : BannedList{}, *boost, d_rows);
+                           has_banned ? *banned : BannedList{}, *boost, d_rows, bp);
     } else if (banned && banned->n > 0 && seqs) {  // both step processors in ONE launch
         check_banned_list(*banned, seq_ld, S);
         hipLaunchKernelGGL(step_processors_kernel, dim3(rows), dim3(256), 0, s, logits, ld, V, beams, first_step, seqs, seq_ld, S, G, *banned,
-                           d_rows);
+                           d_rows, bp);
     } else if (seqs && G > 0 && G < S) {
+        // (rows of an utterance inside its prompt are blocked too: launch_beam_prompt has read them already, nothing else will)
         hipLaunchKernelGGL(ngram_block_kernel, dim3(rows), dim3(256), 0, s, logits, ld, V, seqs, seq_ld, S, G, d_rows);
     }
     hipLaunchKernelGGL(beam_topk_partial_kernel, dim3(BEAM_CH, rows), dim3(256), 0, s, logits, ld, beams, V, clen, cum, first_step, no_eos,
-                       force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, part, pval, ws_i, d_rows);
-    hipLaunchKernelGGL(beam_merge_kernel, dim3(n_utt), dim3(256), 0, s, pval, ws_i, beams * BEAM_CH * K, K, cand_val, cand_idx, d_slots);
+                       force_eos, pad_idx, eos_idx, unk_idx, unk_penalty, K, part, pval, ws_i, d_rows, bp);
+    hipLaunchKernelGGL(beam_merge_kernel, dim3(n_utt), dim3(256), 0, s, pval, ws_i, beams * BEAM_CH * K, K, cand_val, cand_idx, d_slots, bp);
     SC_LAUNCH_CHECK();
 }
 
@@ -725,6 +773,14 @@ void launch_beam_compact(const BeamCompactArgs& a, hipStream_t s) {
     SC_CHECK(a.n >= 1 && a.n <= 1024 && a.beams >= 1 && a.done && a.slot_utt && a.d_slots && a.d_rows && a.seqs && a.cum && a.tok && a.enc_lens,
              "beam compact: bad arguments (n=%d)", a.n);
     hipLaunchKernelGGL(beam_compact_kernel, dim3(1), dim3(256), 0, s, a);
+    SC_LAUNCH_CHECK();
+}
+
+void launch_beam_prompt(const float* logits, int64_t ld, int n_utt, int beams, int V, const float* cum, const int* seqs, int seq_ld, int K,
+                        float* cand_val, int* cand_idx, const BeamPrompt& bp, const int* d_slots, hipStream_t s) {
+    SC_CHECK(bp.len && seqs && cum && K >= beams && K <= BEAM_MAX_K && beams >= 1 && bp.step >= 0 && bp.step + 1 < seq_ld,
+             "beam prompt: bad arguments (beams=%d K=%d step=%d)", beams, K, bp.step);
+    hipLaunchKernelGGL(beam_prompt_kernel, dim3(n_utt), dim3(256), 0, s, logits, ld, beams, V, cum, seqs, seq_ld, K, cand_val, cand_idx, bp, d_slots);
     SC_LAUNCH_CHECK();
 }
 

@@ -601,14 +601,20 @@ void launch_add_i32(int* p, int v, hipStream_t s) {
 
 // Generation bookkeeping after each decoder step (greedy, beam_size = 1):
 //   tok = finished ? pad : next_tok;  hist[b][pos+1] = tok;  EOS closes the item.
+//   prompt_len (nullable): a row with pos + 1 < prompt_len[b] is fed the token hist already holds (argmax_finalize_kernel).
 __global__ void step_update_kernel(int* __restrict__ next_tok, int* __restrict__ hist, int hist_ld,
                                    int* __restrict__ finished, int* __restrict__ out_len,
                                    const float* __restrict__ lprob, float* __restrict__ score, int nb,
                                    const int* __restrict__ d_pos, int pad_idx, int eos_idx,
-                                   int* __restrict__ n_unfinished) {
+                                   int* __restrict__ n_unfinished, const int* __restrict__ prompt_len) {
     const int pos = *d_pos;
     int unfinished = 0;
     for (int b = threadIdx.x; b < nb; b += blockDim.x) {
+        if (prompt_len && pos + 1 < prompt_len[b]) {  // inside the row's prompt
+            next_tok[b] = hist[(int64_t)b * hist_ld + pos + 1];
+            unfinished = 1;
+            continue;
+        }
         int tok = next_tok[b];
         if (finished[b]) {
             tok = pad_idx;
@@ -628,9 +634,9 @@ __global__ void step_update_kernel(int* __restrict__ next_tok, int* __restrict__
 }
 void launch_step_update(int* next_tok, int* hist, int hist_ld, int* finished, int* out_len, const float* lprob,
                         float* score, int nb, const int* d_pos, int pad_idx, int eos_idx, int* n_unfinished,
-                        hipStream_t s) {
+                        hipStream_t s, const int* prompt_len) {
     hipLaunchKernelGGL(step_update_kernel, dim3(1), dim3(256), 0, s, next_tok, hist, hist_ld, finished, out_len, lprob,
-                       score, nb, d_pos, pad_idx, eos_idx, n_unfinished);
+                       score, nb, d_pos, pad_idx, eos_idx, n_unfinished, prompt_len);
     SC_LAUNCH_CHECK();
 }
 
@@ -657,6 +663,7 @@ __global__ __launch_bounds__(256) void row_swap_kernel(RowSwapArgs a) {
         t = a.finished[src], a.finished[src] = a.finished[dst], a.finished[dst] = t;
         t = a.out_len[src], a.out_len[src] = a.out_len[dst], a.out_len[dst] = t;
         t = a.enc_lens[src], a.enc_lens[src] = a.enc_lens[dst], a.enc_lens[dst] = t;
+        if (a.prompt_len) t = a.prompt_len[src], a.prompt_len[src] = a.prompt_len[dst], a.prompt_len[dst] = t;
         float f;
         f = a.lprob[src], a.lprob[src] = a.lprob[dst], a.lprob[dst] = f;
         f = a.score[src], a.score[src] = a.score[dst], a.score[dst] = f;

@@ -464,6 +464,9 @@ void launch_reduce_res_ln(const float* partial, int splits, const float* bias, f
 // Final stage of the fused vocabulary projection + arg-max: combines the per-tile
 // (best, idx, max, sumexp) records of one row, applies the forced-EOS rule, and performs the
 // generation bookkeeping of step_update_kernel for that row.  One workgroup per batch row.
+// prompt_len (nullable, [nb]): a row with pos + 1 < prompt_len[row] is still inside its prompt (sc_generate_text_prompts):
+// its next token is the one hist already holds; nothing is chosen, scored or finished, and the forced-EOS rule does not
+// apply - what engine_finalize_kernel does for such a row.
 // --------------------------------------------------------------------------- //
 __global__ __launch_bounds__(256) void argmax_finalize_kernel(const float4* __restrict__ part, int tiles, int nb,
                                                               const float* __restrict__ eos_logit,
@@ -471,11 +474,18 @@ __global__ __launch_bounds__(256) void argmax_finalize_kernel(const float4* __re
                                                               int pad_idx, int eos_idx, int* __restrict__ next_tok,
                                                               int* __restrict__ hist, int hist_ld,
                                                               int* __restrict__ finished, int* __restrict__ out_len,
-                                                              float* __restrict__ score) {
+                                                              float* __restrict__ score, const int* __restrict__ prompt_len) {
     __shared__ float s_v[4], s_m[4], s_s[4];
     __shared__ int s_i[4];
     const int b = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (prompt_len) {  // uniform over the workgroup
+        const int p = *d_pos;
+        if (p + 1 < prompt_len[b]) {
+            if (tid == 0) next_tok[b] = hist[(int64_t)b * hist_ld + p + 1];
+            return;
+        }
+    }
     float best = -INFINITY, m = -INFINITY, ssum = 0.f;
     int bidx = 0x7fffffff;
     for (int t = tid; t < tiles; t += 256) {
@@ -549,9 +559,9 @@ __global__ __launch_bounds__(256) void argmax_finalize_kernel(const float4* __re
 
 void launch_argmax_finalize(const float4* part, int tiles, int nb, const float* eos_logit, const int* d_pos,
                             int force_eos_step, int pad_idx, int eos_idx, int* next_tok, int* hist, int hist_ld,
-                            int* finished, int* out_len, float* score, hipStream_t s) {
+                            int* finished, int* out_len, float* score, hipStream_t s, const int* prompt_len) {
     hipLaunchKernelGGL(argmax_finalize_kernel, dim3(nb), dim3(256), 0, s, part, tiles, nb, eos_logit, d_pos,
-                       force_eos_step, pad_idx, eos_idx, next_tok, hist, hist_ld, finished, out_len, score);
+                       force_eos_step, pad_idx, eos_idx, next_tok, hist, hist_ld, finished, out_len, score, prompt_len);
     SC_LAUNCH_CHECK();
 }
 

@@ -325,7 +325,7 @@ struct SkinnyArgs {
 int skinny_argmax_tiles(int M, int N);
 void launch_argmax_finalize(const float4* part, int tiles, int nb, const float* eos_logit, const int* d_pos,
                             int force_eos_step, int pad_idx, int eos_idx, int* next_tok, int* hist, int hist_ld,
-                            int* finished, int* out_len, float* score, hipStream_t s);
+                            int* finished, int* out_len, float* score, hipStream_t s, const int* prompt_len = nullptr);
 void launch_skinny(const SkinnyArgs& a, hipStream_t s);
 // number of K ranges that brings the grid to >= 256 workgroups (1 when want_split == 0)
 int skinny_splits(int M, int N, int K, int want_split);
@@ -629,6 +629,24 @@ struct BoostList {
     int max_len = 0;  // longest phrase
     float beta = 0.f;
 };
+// Per-utterance prompts of a beam search (sc_generate_text_prompts).  len == null: every utterance's prompt ended before the
+// search's first step (the launch's first_step flag says whether this is that step).  Otherwise len[utterance] is its prompt
+// length (the utterance of slot u is slot_utt[u], or u), `step` the search step, and at a step with
+//   step + 1 <  len: the utterance is still inside its prompt - the candidate search and the step processors leave its rows
+//                    and its candidate list alone (launch_beam_prompt wrote the list);
+//   step + 1 == len: this is the utterance's first free step: beam 0 only (its beams are copies of each other).
+struct BeamPrompt {
+    const int* len = nullptr;
+    const int* slot_utt = nullptr;
+    int step = 0;
+};
+// The forced step of the utterances still inside their prompt: candidate i < beams of such an utterance is (beam i, the token
+// seqs already holds at position step + 1), valued cum[beam i] + that token's raw log-probability in beam 0's logit row - the
+// value launch_row_tokens_lprob gives (same reductions), so the cumulative score gets the bits of the host's prompt echo;
+// beam_select_kernel then continues every beam with itself.  Launched BEFORE the candidate search of the step (the step
+// processors write into the logit rows).  One workgroup per slot; other utterances' lists are not touched.
+void launch_beam_prompt(const float* logits, int64_t ld, int n_utt, int beams, int V, const float* cum, const int* seqs, int seq_ld, int K,
+                        float* cand_val, int* cand_idx, const BeamPrompt& bp, const int* d_slots, hipStream_t s);
 // seqs [n_utt*beams][seq_ld] (nullable): the rows' sequences so far (S tokens) for the n-gram step processor (G = n-gram
 // size, 0 = off); logits is modified (blocked tokens).  banned (nullable): the call's banned-sequence list, applied to the same
 // rows when seqs is given (another kernel then: beam_candidates_banned_kernel / one step_processors_kernel launch for both rules).
@@ -636,7 +654,8 @@ struct BoostList {
 void launch_beam_candidates(float* logits, int64_t ld, int n_utt, int beams, int V, const float* cum, int first_step,
                             int no_eos, int force_eos, int pad_idx, int eos_idx, int unk_idx, float unk_penalty, int K,
                             float* cand_val, int* cand_idx, const int* seqs, int seq_ld, int S, int G, hipStream_t s,
-                            const int* d_slots = nullptr, const BannedList* banned = nullptr, const BoostList* boost = nullptr);
+                            const int* d_slots = nullptr, const BannedList* banned = nullptr, const BoostList* boost = nullptr,
+                            const BeamPrompt& bp = BeamPrompt{});
 // the same search for large vocabularies: every (row, 1/32 of V) on its own workgroup, then a merge per utterance;
 // ws_f / ws_i: workspaces of beam_ws_floats / beam_ws_ints elements
 bool beam_chunked(int V, int beams, int K);
@@ -646,7 +665,7 @@ void launch_beam_candidates_chunked(float* logits, int64_t ld, int n_utt, int be
                                     int force_eos, int pad_idx, int eos_idx, int unk_idx, float unk_penalty, int K, float* cand_val,
                                     int* cand_idx, const int* seqs, int seq_ld, int S, int G, float* ws_f, int* ws_i, hipStream_t s,
                                     const int* d_rows = nullptr, const int* d_slots = nullptr, const BannedList* banned = nullptr,
-                                    const BoostList* boost = nullptr);
+                                    const BoostList* boost = nullptr, const BeamPrompt& bp = BeamPrompt{});
 // device-resident beam-search state of one sc_generate_text call (k_beam.hip: beam_select_kernel)
 struct BeamSelectArgs {
     const float* cand_val = nullptr;  // [n][K] best first
@@ -753,7 +772,7 @@ void launch_embed_tokens(const int* tokens, int rows, const __half* emb, int M, 
                          int64_t ldo, hipStream_t s);
 void launch_step_update(int* next_tok, int* hist, int hist_ld, int* finished, int* out_len,
                         const float* lprob, float* score, int nb, const int* d_pos, int pad_idx,
-                        int eos_idx, int* n_unfinished, hipStream_t s);
+                        int eos_idx, int* n_unfinished, hipStream_t s, const int* prompt_len = nullptr);
 void launch_argmax_rows(const float* logits, int64_t ld, int rows, int V, const int* d_pos,
                         int min_pos_for_eos, int force_eos_pos, int pad_idx, int eos_idx, int unk_idx,
                         float unk_penalty, int* out_idx, float* out_lprob, hipStream_t s);
@@ -815,6 +834,7 @@ struct RowSwapArgs {
     int* finished = nullptr;
     int* out_len = nullptr;
     int* enc_lens = nullptr;
+    int* prompt_len = nullptr;  // per-row prompt lengths (nullable): a row may move while it is still inside its prompt
     float* lprob = nullptr;
     float* score = nullptr;
     int* hist = nullptr;      // [rows][cap]

@@ -382,7 +382,7 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
                        const sc_gen_opts& o, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
                        int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, const int32_t* h_forced_tokens,
                        int forced_len, const XattnCapture* xcap = nullptr, const BannedHost* banned = nullptr, int prefix_stride = 0,
-                       const BoostHost* boost = nullptr);
+                       const BoostHost* boost = nullptr, const int32_t* h_prefix_lens = nullptr);
 void run_identify_language(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix,
                            int prefix_len, const int32_t* h_cand, int n_cand, float* h_lprob, int32_t* h_best);
 void run_score_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens,
@@ -408,7 +408,7 @@ void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, con
 void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                        const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
                        float* d_dec_hidden, int max_len, const BannedHost* banned = nullptr, int prefix_stride = 0,
-                       const BoostHost* boost = nullptr);
+                       const BoostHost* boost = nullptr, const int32_t* h_prefix_lens = nullptr);
 // sampled generation (model_sample.hip): outputs [n][num_gens][...], hypotheses of an utterance sorted by score
 void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                           const sc_sample_opts& so, const uint64_t* h_streams, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,

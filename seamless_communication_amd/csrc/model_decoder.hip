@@ -25,7 +25,8 @@ int text_max_len(const Model& m, const sc_gen_opts& o, int s_enc) {
 
 void run_generate_text_beam(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                             const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                            float* d_dec_hidden, const BannedHost* banned = nullptr, int prefix_stride = 0, const BoostHost* boost = nullptr);
+                            float* d_dec_hidden, const BannedHost* banned = nullptr, int prefix_stride = 0, const BoostHost* boost = nullptr,
+                            const int32_t* h_prefix_lens = nullptr);
 
 // --------------------------------------------------------------------------------------------- //
 // Streaming monotonic decoder (cfg 5).  One row; the state lives in the handle between calls.
@@ -264,14 +265,15 @@ void setup_session(Model& m, DecodeSession& S, int n, int max_len, int s_enc, bo
     c.min_seq_len = o.min_seq_len;
     c.force_eos_step = max_len - 2;
     c.unk_penalty = o.unk_penalty;
-    S.ints = Buf<int>(m.pp(), (size_t)8 + 4 * n + (size_t)n * max_len);
+    S.ints = Buf<int>(m.pp(), (size_t)8 + 5 * n + (size_t)n * max_len);
     c.d_pos = S.ints;
     c.d_rows_greedy = S.ints.get() + 1;  // becomes StepCtx::d_rows of a row-group (gen-3) generation session below
     c.d_tok = S.ints.get() + 8;
     c.d_finished = c.d_tok + n;
     c.d_out_len = c.d_finished + n;
     c.d_enc_lens = c.d_out_len + n;
-    c.d_hist = c.d_enc_lens + n;
+    c.d_prompt_len = c.d_enc_lens + n;
+    c.d_hist = c.d_prompt_len + n;
     S.fl = Buf<float>(m.pp(), (size_t)2 * n);
     c.d_lprob = S.fl;
     c.d_score = S.fl.get() + n;
@@ -536,13 +538,25 @@ void run_identify_language(Model& m, const float* d_enc, int n, int s_enc, const
 // feedback, hidden states only).  Otherwise greedy generation.
 // prefix_stride: 0 = every row is fed h_prefix[0 .. prefix_len); otherwise row b is fed h_prefix[b * prefix_stride + ...]
 // (sc_generate_text_rows).
+// h_prefix_lens (sc_generate_text_prompts, with prefix_stride > 0): row b's prompt is h_prefix_lens[b] tokens long and
+// prefix_len is the SHORTEST of them: the prompt echo runs that far for all rows, and the rows whose prompt is longer are
+// fed the rest of it by the closing launch of the step (argmax_finalize_kernel), position by position, while the other
+// rows already generate.
 void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens,
                        const sc_gen_opts& o, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
                        int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, const int32_t* h_forced_tokens,
-                       int forced_len, const XattnCapture* xcap, const BannedHost* banned, int prefix_stride, const BoostHost* boost) {
+                       int forced_len, const XattnCapture* xcap, const BannedHost* banned, int prefix_stride, const BoostHost* boost,
+                       const int32_t* h_prefix_lens) {
     const sc_config& cfg = m.cfg;
     const int M = cfg.model_dim;
     SC_CHECK(n > 0 && s_enc > 0, "sc_generate_text: empty batch");
+    SC_CHECK(!h_prefix_lens || (!h_forced_tokens && !xcap && prefix_stride > 0), "sc_generate_text: per-row prompt lengths need per-row prompts");
+    int longest_prefix = prefix_len;
+    if (h_prefix_lens)
+        for (int b = 0; b < n; ++b) {
+            SC_CHECK(h_prefix_lens[b] >= prefix_len && h_prefix_lens[b] <= prefix_stride, "sc_generate_text: prompt length %d of row %d", h_prefix_lens[b], b);
+            longest_prefix = std::max(longest_prefix, h_prefix_lens[b]);
+        }
     prof::set_tag("dec");
     const bool forced = h_forced_tokens != nullptr;
     static const bool stepwise_forced = knob::is_set("SC_DECODE_STEPWISE");
@@ -568,13 +582,13 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
         if (o.beam_size > 1 || o.no_repeat_ngram_size > 0 || has_banned || has_boost) {  // step processors run in the host-driven step loop
             if (m.engine) m.engine->expect(m, -n);
             run_generate_text_beam(m, d_enc, n, s_enc, h_enc_lens, o, h_prefix, prefix_len, h_out_ids, h_out_lens, h_scores,
-                                   d_dec_hidden, has_banned ? banned : nullptr, prefix_stride, has_boost ? boost : nullptr);
+                                   d_dec_hidden, has_banned ? banned : nullptr, prefix_stride, has_boost ? boost : nullptr, h_prefix_lens);
             return;
         }
         SC_CHECK(prefix_len >= 1, "sc_generate_text: the prompt must hold at least one token");
         max_len = text_max_len(m, o, s_enc);
         SC_CHECK(o.min_seq_len <= max_len, "sc_generate_text: min_seq_len %d > effective max length %d", o.min_seq_len, max_len);
-        SC_CHECK(prefix_len < max_len, "sc_generate_text: prompt length %d >= effective max length %d", prefix_len, max_len);
+        SC_CHECK(longest_prefix < max_len, "sc_generate_text: prompt length %d >= effective max length %d", longest_prefix, max_len);
     }
     SC_CHECK(max_len <= 4096 && max_len <= cfg.text_max_seq_len + 1, "sc_generate_text: length %d exceeds the decoder limit", max_len);
     SC_CHECK(s_enc <= 4096, "sc_generate_text: encoder length %d > 4096", s_enc);
@@ -585,9 +599,11 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
     // (a capture call does not fit: it runs on the handle's own chain, whose step the capture launch follows)
     if (!forced && m.engine && xcap) m.engine->expect(m, -n);
     if (!forced && m.engine && !xcap) {
-        if (m.engine->fits(n, s_enc, max_len, prefix_len, o) && m.engine->has_company()) {
+        // (per-row prompts: the longest one decides - a call with a prompt beyond the admit record's capacity runs on the
+        // handle's own chain as a whole)
+        if (m.engine->fits(n, s_enc, max_len, longest_prefix, o) && m.engine->has_company()) {
             m.engine->generate(m, d_enc, n, s_enc, h_enc_lens, h_prefix, prefix_len, max_len, h_out_ids, h_out_lens, h_scores, d_dec_hidden,
-                               prefix_stride);
+                               prefix_stride, h_prefix_lens);
             return;
         }
         m.engine->expect(m, -n);  // announced rows that run on the handle's own chain after all
@@ -643,10 +659,13 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
     for (int li = 0; li < cfg.dec_layers; ++li) project_cross_kv(m, d_enc, m.dec[li].cross_kv, c.cross_kv[li], n * s_enc);
 
     // ---- initial state ------------------------------------------------------------
-    std::vector<int32_t> hist((size_t)n * max_len, cfg.pad_idx), init(8 + 4 * n, 0);
+    std::vector<int32_t> hist((size_t)n * max_len, cfg.pad_idx), init(8 + 5 * n, 0);
     const int feed_len = forced ? forced_len : prefix_len;
-    for (int b = 0; b < n; ++b)
-        for (int t = 0; t < feed_len; ++t) hist[(size_t)b * max_len + t] = forced ? h_forced_tokens[(size_t)b * forced_len + t] : h_prefix[(size_t)b * prefix_stride + t];
+    for (int b = 0; b < n; ++b) {
+        const int own_len = forced ? forced_len : h_prefix_lens ? h_prefix_lens[b] : prefix_len;
+        for (int t = 0; t < own_len; ++t) hist[(size_t)b * max_len + t] = forced ? h_forced_tokens[(size_t)b * forced_len + t] : h_prefix[(size_t)b * prefix_stride + t];
+        init[8 + 4 * n + b] = forced ? 0 : own_len;  // StepCtx::d_prompt_len (a uniform call writes the shared length)
+    }
     init[1] = n;  // live rows (StepCtx::d_rows_greedy)
     for (int b = 0; b < n; ++b) {
         init[8 + b] = hist[(size_t)b * max_len];  // token fed at position 0
@@ -755,6 +774,7 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
                     for (int li = 0; li < cfg.dec_layers; ++li) rs.k[li] = c.kcache[li], rs.v[li] = c.vcache[li], rs.cross[li] = c.cross_kv[li];
                     rs.M = M, rs.cap = c.cap, rs.s_enc = c.s_enc, rs.filled = step + 1;
                     rs.tok = c.d_tok, rs.finished = c.d_finished, rs.out_len = c.d_out_len, rs.enc_lens = c.d_enc_lens;
+                    rs.prompt_len = c.d_prompt_len;
                     rs.lprob = c.d_lprob, rs.score = c.d_score, rs.hist = c.d_hist, rs.hidden = c.dec_hidden;
                     int free_slot = 0;
                     for (int b = want; b < live_slots; ++b) {
@@ -850,10 +870,11 @@ void banned_blocked_tokens(const int32_t* seq, int S, const BannedHost& b, std::
 
 void run_generate_text_beam(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                             const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                            float* d_dec_hidden, const BannedHost* banned, int prefix_stride, const BoostHost* boost) {
+                            float* d_dec_hidden, const BannedHost* banned, int prefix_stride, const BoostHost* boost,
+                            const int32_t* h_prefix_lens) {
     const DecStack W = unity_stack(m);
     run_generate_beam(m, W, d_enc, n, s_enc, h_enc_lens, o, h_prefix, prefix_len, h_out_ids, h_out_lens, h_scores, d_dec_hidden,
-                      text_max_len(m, o, s_enc), banned, prefix_stride, boost);
+                      text_max_len(m, o, s_enc), banned, prefix_stride, boost, h_prefix_lens);
 }
 
 // UnitYT2UModel generation of the v1 models (inference/generator.py:316-336): T2U encoder over the text decoder output,
@@ -979,8 +1000,24 @@ void hidden_of_best(Model& m, const float* d_enc, int n, int s_enc, const int32_
 // Beam search over one decoder stack (the UnitY text decoder or the v1 autoregressive unit decoder).
 void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                        const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                       float* d_dec_hidden, int max_len, const BannedHost* banned, int prefix_stride, const BoostHost* boost) {
+                       float* d_dec_hidden, int max_len, const BannedHost* banned, int prefix_stride, const BoostHost* boost,
+                       const int32_t* h_prefix_lens) {
     // prefix_stride: 0 = one prompt for all; otherwise utterance u's prompt is h_prefix[u * prefix_stride + ...], fed to each of its beams
+    // h_prefix_lens (nullable; sc_generate_text_prompts): utterance u's prompt is h_prefix_lens[u] tokens long and prefix_len is
+    // the SHORTEST of them.  The host echo below runs that far; from there an utterance that is still inside its prompt is
+    // handled on the device (beam_prompt_kernel): each of its beams continues itself with the known token and adds that
+    // token's raw log-probability - the echo's bits, added in the echo's order - while the candidate search and the step
+    // processors leave the utterance alone; its "beam 0 only" step is the one at its own prompt's end.
+    int longest_prefix = prefix_len;
+    if (h_prefix_lens) {
+        SC_CHECK(prefix_stride > 0, "sc_generate_text: per-row prompt lengths need per-row prompts");
+        for (int u = 0; u < n; ++u) {
+            SC_CHECK(h_prefix_lens[u] >= prefix_len && h_prefix_lens[u] <= prefix_stride, "sc_generate_text: prompt length %d of row %d", h_prefix_lens[u], u);
+            longest_prefix = std::max(longest_prefix, h_prefix_lens[u]);
+        }
+        SC_CHECK(longest_prefix < max_len, "sc_generate_text: prompt length %d >= effective max length %d", longest_prefix, max_len);
+    }
+    const bool ragged = longest_prefix > prefix_len;
     const std::vector<DecoderLayer>& dec_layers = *W.layers;
     const int M = m.cfg.model_dim, V = W.vocab, B = o.beam_size, L = (int)dec_layers.size();
     const int nb = n * B;
@@ -1075,7 +1112,11 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
     std::vector<float> cum(nb, 0.f);
     for (int r = 0; r < nb; ++r) {
         const int32_t* pre = h_prefix + (size_t)(r / B) * prefix_stride;
-        for (int t = 0; t < prefix_len; ++t) seqs[(size_t)r * max_len + t] = pre[t];
+        const int own_len = h_prefix_lens ? h_prefix_lens[r / B] : prefix_len;
+        for (int t = 0; t < own_len; ++t) {
+            SC_CHECK(pre[t] >= 0 && pre[t] < V, "sc_generate_text: prompt token %d out of range", pre[t]);
+            seqs[(size_t)r * max_len + t] = pre[t];
+        }
         init[8 + r] = pre[0];
         init[8 + 3 * nb + r] = h_enc_lens[r / B];
     }
@@ -1098,6 +1139,11 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
     }
     std::vector<float> pref(n);
     const int G = o.no_repeat_ngram_size;
+    Buf<int> d_plen(m.pp(), ragged ? (size_t)n : 4);  // by UTTERANCE (read through slot_utt when the slots are packed)
+    if (ragged) {
+        SC_HIP(hipMemcpyAsync(d_plen.get(), h_prefix_lens, (size_t)n * 4, hipMemcpyHostToDevice, m.stream));
+        SC_HIP(hipStreamSynchronize(m.stream));  // the lengths are the caller's
+    }
 
     // ---- live-slot bookkeeping (row-group chain + ancestor table only): the slots of utterances that are still searching are
     // packed to the front every time the host looks at the counters (every 4th step); kernels skip the rows / slots behind
@@ -1157,16 +1203,23 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
         project_rows();
         // step processors: not on the forced-EOS step (blocking EOS there would leave no hypothesis)
         const bool ban = (G > 0 || bl.n > 0 || bo.n > 0) && step != max_len - 2;
+        BeamPrompt bp;  // empty unless an utterance may still be inside its prompt or at its end
+        if (ragged && step < longest_prefix) {
+            bp.len = d_plen, bp.slot_utt = compact ? d_slot_utt : nullptr, bp.step = step;
+            // first in the stream: it reads the logit rows before a step processor writes into them
+            launch_beam_prompt(c.logits, ldl, n, B, V, d_cum, d_seqs_cur, max_len, K, d_cand_val, d_cand_idx, bp, compact ? d_slots : nullptr,
+                               m.stream);
+        }
         if (chunked) {
             launch_beam_candidates_chunked(c.logits, ldl, n, B, V, d_cum, step == start, step < o.min_seq_len, step == max_len - 2,
                                            W.pad_idx, W.eos_idx, W.unk_idx, o.unk_penalty, K, d_cand_val, d_cand_idx,
                                            ban ? d_seqs_cur : nullptr, max_len, step + 1, G, ws_f, ws_i, m.stream,
                                            compact ? d_rows_live : nullptr, compact ? d_slots : nullptr, bl.n > 0 ? &bl : nullptr,
-                                           bo.n > 0 ? &bo : nullptr);
+                                           bo.n > 0 ? &bo : nullptr, bp);
         } else {
             launch_beam_candidates(c.logits, ldl, n, B, V, d_cum, step == start, step < o.min_seq_len, step == max_len - 2, W.pad_idx,
                                    W.eos_idx, W.unk_idx, o.unk_penalty, K, d_cand_val, d_cand_idx, ban ? d_seqs_cur : nullptr, max_len,
-                                   step + 1, G, m.stream, compact ? d_slots : nullptr, bl.n > 0 ? &bl : nullptr, bo.n > 0 ? &bo : nullptr);
+                                   step + 1, G, m.stream, compact ? d_slots : nullptr, bl.n > 0 ? &bl : nullptr, bo.n > 0 ? &bo : nullptr, bp);
         }
         BeamSelectArgs a;
         a.cand_val = d_cand_val;
@@ -1208,7 +1261,8 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
                 BeamCompactArgs k;
                 k.done = d_done, k.slot_utt = d_slot_utt, k.d_slots = d_slots, k.d_rows = d_rows_live;
                 k.seqs = d_seqs_cur, k.cum = d_cum, k.tok = c.d_tok, k.enc_lens = c.d_enc_lens, k.anc = d_anc;
-                k.n = n, k.beams = B, k.max_len = max_len, k.anc_ld = max_len, k.seq_len = step + 2, k.anc_len = step + 1;
+                // (a slot that is still inside its prompt carries the rest of the prompt behind the positions written so far)
+                k.n = n, k.beams = B, k.max_len = max_len, k.anc_ld = max_len, k.seq_len = std::max(step + 2, longest_prefix), k.anc_len = step + 1;
                 launch_beam_compact(k, m.stream);
             }
             SC_HIP(hipMemcpyAsync(&remaining, d_remaining, 4, hipMemcpyDeviceToHost, m.stream));

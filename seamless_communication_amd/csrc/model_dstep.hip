@@ -514,7 +514,7 @@ void decoder_step2(Model& m, StepCtx& c, bool project, const DecStack& W) {
         launch_gemvp(v, m.stream);
         launch_argmax_finalize(c.am_part, gemvp_argmax_tiles(W.vocab, c.am_ntl), nb, c.am_eos_logit, c.d_pos,
                                c.force_eos_step, W.pad_idx, W.eos_idx, c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len,
-                               c.d_score, m.stream);
+                               c.d_score, m.stream, c.d_prompt_len);
     }
     launch_add_i32(c.d_pos, 1, m.stream);
 }
@@ -653,7 +653,7 @@ void decoder_step3(Model& m, StepCtx& c, bool project, const DecStack& W) {
             return;
         }
         launch_argmax_finalize(c.am_part, vocab3_groups(nb), nb, c.am_eos_logit, c.d_pos, c.force_eos_step, W.pad_idx, W.eos_idx,
-                               c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len, c.d_score, m.stream);
+                               c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len, c.d_score, m.stream, c.d_prompt_len);
     }
     SC_CHECK(!c.slot_rp, "decoder step: the decode engine's step always projects");
     launch_add_i32(c.d_pos, 1, m.stream);
@@ -744,7 +744,7 @@ void decoder_step(Model& m, StepCtx& c, bool project) {
             a.am_unk_penalty = c.unk_penalty;
             launch_skinny(a, m.stream);
             launch_argmax_finalize(c.am_part, c.am_tiles, nb, c.am_eos_logit, c.d_pos, c.force_eos_step, W.pad_idx,
-                                   W.eos_idx, c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len, c.d_score, m.stream);
+                                   W.eos_idx, c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len, c.d_score, m.stream, c.d_prompt_len);
         } else {
             Linear proj;
             proj.w = W.embed;
@@ -757,7 +757,7 @@ void decoder_step(Model& m, StepCtx& c, bool project) {
                                c.force_eos_step, W.pad_idx, W.eos_idx, W.unk_idx, c.unk_penalty, c.d_tok, c.d_lprob,
                                m.stream);
             launch_step_update(c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len, c.d_lprob, c.d_score, nb, c.d_pos,
-                               W.pad_idx, W.eos_idx, nullptr, m.stream);
+                               W.pad_idx, W.eos_idx, nullptr, m.stream, c.d_prompt_len);
         }
     }
     launch_add_i32(c.d_pos, 1, m.stream);

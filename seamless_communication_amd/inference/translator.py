@@ -134,6 +134,78 @@ DEFAULT_CARDS: Dict[str, Dict[str, Any]] = {
 }
 
 
+def _prefix_ids(text_tokenizer: NllbTextTokenizer, entry: Any) -> List[int]:
+    """One forced prefix as token ids: a string is tokenised on its own (no control tokens), ids are checked."""
+    if entry is None:
+        return []
+    if isinstance(entry, str):
+        return [int(t) for t in text_tokenizer.encode_pieces(entry)]
+    ids = [int(t) for t in (entry.tolist() if hasattr(entry, "tolist") else entry)]
+    vi = text_tokenizer.vocab_info
+    for t in ids:
+        if t < 0 or t >= vi.size:
+            raise ValueError(f"`forced_prefix` holds token {t} outside the vocabulary of {vi.size}")
+        if t in (vi.pad_idx, vi.eos_idx):
+            raise ValueError(f"`forced_prefix` holds the pad / EOS token {t}: a prefix is text pieces only")
+    return ids
+
+
+def parse_forced_prefix(text_tokenizer: NllbTextTokenizer, forced_prefix: Any, tgt_lang: Optional[str]) -> Any:
+    """``forced_prefix`` as the generation calls take it, checked on the host: None, one id list for every item (a string
+    or a sequence of token ids was given), or a tuple with one id list per item (a list of strings / id sequences / None)."""
+    if forced_prefix is None:
+        return None
+    if tgt_lang is None:
+        raise ValueError("`tgt_lang` must be specified with `forced_prefix` (the prefix follows the language token)")
+    if isinstance(forced_prefix, str):
+        return _prefix_ids(text_tokenizer, forced_prefix)
+    entries = forced_prefix.tolist() if hasattr(forced_prefix, "tolist") else list(forced_prefix)
+    if all(isinstance(e, (int, np.integer)) for e in entries):
+        return _prefix_ids(text_tokenizer, entries)
+    return tuple(_prefix_ids(text_tokenizer, e) for e in entries)
+
+
+def forced_prompts(text_tokenizer: NllbTextTokenizer, parsed: Any, tgt_lang: str, n: int) -> Optional[List[List[int]]]:
+    """The prompt of each of ``n`` items - ``</s> __lang__`` and the item's prefix - or None when no item has a prefix."""
+    if parsed is None:
+        return None
+    if isinstance(parsed, tuple):
+        if len(parsed) != n:
+            raise ValueError(f"`forced_prefix` must hold one entry per input item ({n}), but holds {len(parsed)} instead.")
+        per_item = list(parsed)
+    else:
+        per_item = [parsed] * n
+    if not any(per_item):
+        return None
+    head = text_tokenizer.target_prefix(tgt_lang)
+    return [list(head) + list(p) for p in per_item]
+
+
+def sampled_by_prompt(model: Any, enc: Tensor, enc_lens: Sequence[int], prompts: List[List[int]], streams: Optional[Sequence[int]],
+                      **kw: Any):
+    """``generate_text_sampled`` over items with different prompts: sc_generate_text_sampled keeps one prompt per call, so the
+    items are grouped by prompt and each group is one call.  Every item keeps its own stream id (default: its index), so its
+    draws are those of any other grouping.  -> (ids, lens, scores, step_lprob, hidden) in item order."""
+    n = len(prompts)
+    streams = list(range(n)) if streams is None else [int(s) for s in streams]
+    groups: Dict[Tuple[int, ...], List[int]] = {}
+    for b, p in enumerate(prompts):
+        groups.setdefault(tuple(p), []).append(b)
+    out: Optional[List[Any]] = None
+    for prompt, rows in groups.items():
+        idx = torch.as_tensor(rows, device=enc.device)
+        res = model.generate_text_sampled(enc.index_select(0, idx).contiguous(), [int(enc_lens[b]) for b in rows], list(prompt),
+                                          streams=[streams[b] for b in rows], **kw)
+        if out is None:
+            out = [np.zeros((n,) + r.shape[1:], dtype=r.dtype) if isinstance(r, np.ndarray) else
+                   (None if r is None else torch.zeros((n,) + tuple(r.shape[1:]), dtype=r.dtype, device=r.device)) for r in res]
+        for dst, r in zip(out, res):
+            if dst is not None:
+                dst[idx.cpu().numpy() if isinstance(dst, np.ndarray) else idx] = r
+    assert out is not None
+    return tuple(out)
+
+
 def parse_synthetic_uri(uri: str) -> Tuple[int, Dict[str, str]]:
     """``synthetic://<seed>[?key=value[&key=value]]`` -> (seed, options).  Options: ``eos_ramp`` (synthetic.EosRamp)."""
     body = uri[len("synthetic://"):]
@@ -378,11 +450,21 @@ class Translator:
         duration_factor: float = 1.0,
         prosody_encoder_input: Optional[SequenceData] = None,
         src_text: Optional[StringLike] = None,
+        *,
+        forced_prefix: Any = None,
     ) -> Tuple[List[StringLike], Optional[BatchedSpeechOutput]]:
-        """``tgt_lang=None`` (text output only - s2tt, asr, t2tt; not part of the reference's ``predict``, its native port's
+        """``forced_prefix`` (not part of the reference's ``predict``; the ``target_prefix`` of CTranslate2): the translation
+        begins with these tokens and the model continues from there - a string (``encode_forced_prefix``), a sequence of token
+        ids (no ``</s>``, no language token), or a list with one entry per input item, None for an item without a prefix.
+        The returned texts, ``last_text_ids`` and, for speech output, the units cover the WHOLE hypothesis, prefix included.
+        Items with prefixes of different lengths stay one batch (sc_generate_text_prompts).  Not evaluated on real speech.
+
+        ``tgt_lang=None`` (text output only - s2tt, asr, t2tt; not part of the reference's ``predict``, its native port's
         target language ``unk``): the model picks every row's language token itself (``identify_language`` on the encoder
         output) and the batch is generated with one prompt per row; ``last_lid`` then holds the identifications."""
         input_modality, output_modality = self.get_modalities_from_task_str(task_str)
+        # (refused before any device work)
+        forced = parse_forced_prefix(self.text_tokenizer, forced_prefix, tgt_lang) if forced_prefix is not None else None
         if tgt_lang is None:  # refused before any device work
             if output_modality != Modality.TEXT:
                 raise ValueError(f"`tgt_lang` must be specified for {task_str}: the T2U model and the vocoder need a stated language "
@@ -409,7 +491,7 @@ class Translator:
             self.model, self.text_tokenizer, self.unit_tokenizer, seqs, src_lens, input_modality, output_modality,
             tgt_lang, text_generation_opts, unit_generation_opts,
             unit_generation_ngram_filtering=unit_generation_ngram_filtering, duration_factor=duration_factor,
-            prosody_encoder_input=prosody_encoder_input, _trace=trace,
+            prosody_encoder_input=prosody_encoder_input, _trace=trace, forced_prefix=forced,
         )
         if self.apply_mintox and task_str.upper() != Task.ASR.name:  # translator.py:335-379
             if input_modality == Modality.SPEECH:
@@ -435,7 +517,7 @@ class Translator:
                 output_modality=output_modality, src_texts=src_texts, original_texts=texts, original_units=units_t,
                 unit_generation_ngram_filtering=unit_generation_ngram_filtering, text_generation_opts=text_generation_opts,
                 unit_generation_opts=unit_generation_opts, bad_word_checker=self.bad_word_checker,
-                duration_factor=duration_factor, prosody_encoder_input=prosody_encoder_input, _trace=redo)
+                duration_factor=duration_factor, prosody_encoder_input=prosody_encoder_input, _trace=redo, forced_prefix=forced)
             if "text_ids" in redo:  # rows were generated again: the introspection data describe the last generation call
                 if len(redo["text_ids"]) == n_rows:
                     trace = redo
@@ -539,6 +621,15 @@ class Translator:
         phrases in a prefix relation the shorter is kept, with a warning (the list must be prefix-free)."""
         return encode_bias_phrases(self.text_tokenizer, phrases)
 
+    def encode_forced_prefix(self, text: str, tgt_lang: str) -> List[int]:
+        """A string -> the token ids ``forced_prefix`` takes: the text tokenised on its own, without ``</s>`` and without the
+        language token of ``tgt_lang`` (which only has to be a language of the tokenizer).  The prefix should end at a word
+        boundary: SentencePiece may split a word that is cut short differently from the same letters inside the full
+        sentence, and the model then continues from pieces it would not have written.  Token ids give exact control, e.g. the
+        first k tokens of an earlier output, ``tr.last_text_ids[b][2:2 + k]``."""
+        self.text_tokenizer.lang_token_idx(tgt_lang)  # an unknown language is an error here, not in the generation call
+        return _prefix_ids(self.text_tokenizer, text)
+
     @torch.inference_mode()
     def sample(
         self,
@@ -554,14 +645,18 @@ class Translator:
         streams: Optional[Sequence[int]] = None,
         text_generation_opts: Optional[SequenceGeneratorOptions] = None,
         sample_rate: int = 16000,
+        forced_prefix: Any = None,
     ) -> List[List["SampledHypothesis"]]:
         """``num_gens`` sampled text hypotheses per input item (S2TT, ASR, T2TT), each list sorted by score - candidates for
         ``score`` / a re-ranker.  Not part of the reference's ``Translator``; the semantics follow fairseq2 0.2's
         ``SamplingSeq2SeqGenerator`` with ``TopKSampler`` / ``TopPSampler``.  The draws depend on
         ``seed``, the item's id in ``streams`` (default: its index), the hypothesis number and the position only - not on
         torch's generator, nor on what else is in the batch.  ``text_generation_opts`` supplies the length limits, ``unk_penalty``,
-        ``len_penalty`` and the step processor; its ``beam_size`` is ignored."""
+        ``len_penalty`` and the step processor; its ``beam_size`` is ignored.  ``forced_prefix``: as ``predict``'s - every
+        hypothesis of an item begins with the item's prefix; the items are sampled in one call per distinct prompt, each under
+        its own stream id, so the draws do not depend on the grouping."""
         input_modality, output_modality = self.get_modalities_from_task_str(task_str)
+        forced = parse_forced_prefix(self.text_tokenizer, forced_prefix, tgt_lang) if forced_prefix is not None else None
         if output_modality != Modality.TEXT:
             raise ValueError(f"Translator.sample covers text output (S2TT, ASR, T2TT); for {task_str} use "
                              "predict(..., text_generation_opts=SequenceGeneratorOptions(sampler=...))")
@@ -577,11 +672,16 @@ class Translator:
             enc, enc_lens = self.model.encode_speech(seqs, src_lens)
         else:
             enc, enc_lens = self.model.encode_text(seqs.cpu().numpy(), src_lens), np.asarray(src_lens, dtype=np.int32)
-        ids, lens, scores, step_lprob, _ = self.model.generate_text_sampled(
-            enc, enc_lens.tolist(), self.text_tokenizer.target_prefix(tgt_lang), num_gens=num_gens, top_k=sampler.top_k,
-            top_p=sampler.top_p, temperature=temperature, seed=seed, streams=streams, len_penalty=opts.len_penalty,
+        sample_kw: Dict[str, Any] = dict(
+            num_gens=num_gens, top_k=sampler.top_k, top_p=sampler.top_p, temperature=temperature, seed=seed, len_penalty=opts.len_penalty,
             soft_max_seq_len=opts.soft_max_seq_len, hard_max_seq_len=opts.hard_max_seq_len, unk_penalty=opts.unk_penalty,
             no_repeat_ngram_size=ngram, use_graph=self.use_graph, source_len=int(max(src_lens)), **step_kw)
+        prompts = forced_prompts(self.text_tokenizer, forced, tgt_lang, len(src_lens))
+        if prompts is None:
+            ids, lens, scores, step_lprob, _ = self.model.generate_text_sampled(
+                enc, enc_lens.tolist(), self.text_tokenizer.target_prefix(tgt_lang), streams=streams, **sample_kw)
+        else:
+            ids, lens, scores, step_lprob, _ = sampled_by_prompt(self.model, enc, enc_lens.tolist(), prompts, streams, **sample_kw)
         out: List[List[SampledHypothesis]] = []
         for b in range(ids.shape[0]):
             hyps = []
@@ -613,6 +713,7 @@ class Translator:
         duration_factor: float = 1.0,
         prosody_encoder_input: Optional[SequenceData] = None,
         _trace: Optional[Dict[str, Any]] = None,
+        forced_prefix: Any = None,
     ) -> Tuple[List[StringLike], Optional[Tensor]]:
         """``UnitYGenerator(model, ...)(seqs, padding_mask, ...)`` of the reference (inference/generator.py:86-353)
         on the HIP model: returns the texts and, for speech output, the decoded unit matrix ``(N, S_u)`` int64 with
@@ -622,7 +723,10 @@ class Translator:
         tensor of lengths, or any object with a ``seq_lens`` attribute (fairseq2 ``PaddingMask``).
         ``unit_generation_opts`` and ``unit_generation_ngram_filtering`` are disregarded for the NAR T2U model like in
         the reference (translator.py:173-177, generator.py:338-353).  ``_trace`` (not part of the reference API)
-        receives the ids / per-stage data the batch driver and the parity tests read back."""
+        receives the ids / per-stage data the batch driver and the parity tests read back.  ``forced_prefix`` (not part of
+        the reference API): as ``predict``'s; the decoder outputs of the forced positions feed the T2U model like any others."""
+        # (a parsed value passes through unchanged)
+        forced = parse_forced_prefix(text_tokenizer, forced_prefix, tgt_lang) if forced_prefix is not None else None
         prosody_encoder = getattr(model, "prosody_encoder", None)
         if prosody_encoder_input is not None and prosody_encoder is None:
             raise NoProsodyEncoderError("the model has no prosody encoder: prosody_encoder_input is for the expressive model "
@@ -635,6 +739,7 @@ class Translator:
         else:
             lens = getattr(padding_mask, "seq_lens", padding_mask)
             src_lens = [int(x) for x in (lens.tolist() if isinstance(lens, Tensor) else lens)]
+        prompts = forced_prompts(text_tokenizer, forced, tgt_lang, len(src_lens)) if forced is not None else None
         sampler = getattr(text_generation_opts, "sampler", None)
         if sampler is not None:
             check_sampling(sampler, text_generation_opts.temperature)
@@ -660,13 +765,18 @@ class Translator:
         if tgt_lang is None:  # one prompt per row, each with the language token the decoder itself expects behind </s>
             trace["lid"] = _identify_encoded(model, text_tokenizer, enc, enc_lens)
             prefix: Any = np.asarray([text_tokenizer.target_prefix(l.lang) for l in trace["lid"]], dtype=np.int32)
+        elif prompts is not None:  # forced target prefixes: one prompt per row, of any length (sc_generate_text_prompts)
+            prefix = prompts
         else:
             prefix = text_tokenizer.target_prefix(tgt_lang)
         gen_kw: Dict[str, Any] = {"beam_size": text_generation_opts.beam_size}
         generate = model.generate_text
         if sampler is not None:  # one sampled hypothesis per utterance feeds the rest of the chain
-            def generate(*a: Any, **kw: Any):
-                i, l, s, _, h = model.generate_text_sampled(*a, **kw)
+            def generate(g_enc: Any, g_lens: Any, g_prefix: Any, **kw: Any):
+                if prompts is not None:  # one call per distinct prompt, every item under its own stream id
+                    i, l, s, _, h = sampled_by_prompt(model, g_enc, g_lens, prompts, None, **kw)
+                else:
+                    i, l, s, _, h = model.generate_text_sampled(g_enc, g_lens, g_prefix, **kw)
                 return i[:, 0], l[:, 0], s[:, 0], h
 
             gen_kw = {"num_gens": 1, "top_k": sampler.top_k, "top_p": sampler.top_p, "temperature": text_generation_opts.temperature,

@@ -130,14 +130,15 @@ def content_tokens(token_ids: Sequence[int], prefix_len: int, eos_idx: int) -> L
 
 def mbr_decode(self, input, task_str: str, tgt_lang: str, src_lang: Optional[str] = None, *, sampler: Any, num_gens: int = 16,
                temperature: float = 1.0, seed: int = 0, streams: Optional[Sequence[int]] = None, text_generation_opts: Any = None,
-               max_order: int = 4, beta: float = 1.0, sample_rate: int = 16000) -> List[MBRHypothesis]:
+               max_order: int = 4, beta: float = 1.0, sample_rate: int = 16000, forced_prefix: Any = None) -> List[MBRHypothesis]:
     """``Translator.mbr_decode``: ``num_gens`` sampled hypotheses per input item (``Translator.sample``, same arguments and
     the same tasks: S2TT, ASR, T2TT), then the hypothesis with the highest expected token n-gram F-score against all of them
     (:func:`select` on the content tokens: target prefix and closing EOS stripped).  Not part of the reference's
-    ``Translator``; the utility has not been evaluated on real translations."""
+    ``Translator``; the utility has not been evaluated on real translations.  ``forced_prefix``:
+    ``Translator.sample``'s - the candidates all begin with the item's prefix, which counts as content."""
     _check_options(max_order, beta)
     sampled = self.sample(input, task_str, tgt_lang, src_lang, sampler=sampler, num_gens=num_gens, temperature=temperature, seed=seed,
-                          streams=streams, text_generation_opts=text_generation_opts, sample_rate=sample_rate)
+                          streams=streams, text_generation_opts=text_generation_opts, sample_rate=sample_rate, forced_prefix=forced_prefix)
     prefix_len = len(self.text_tokenizer.target_prefix(tgt_lang))
     eos = self.text_tokenizer.vocab_info.eos_idx
     picked = select([[content_tokens(h.token_ids, prefix_len, eos) for h in hyps] for hyps in sampled], max_order=max_order, beta=beta)

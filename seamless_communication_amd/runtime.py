@@ -39,6 +39,34 @@ def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
 
 
+def _ragged_prompts(prefix, n: int, with_lists: bool = False):
+    """The per-row prompt forms of generate_text that carry their own lengths: ``(rows, lens)`` with rows (n, stride), or a
+    list with one prompt per row - of different lengths, or (``with_lists``: the call carries banned sequences or boost
+    phrases, which only sc_generate_text_prompts combines with per-row prompts) of any lengths.  -> (rows (n, stride) int32,
+    lens (n,) int32), or None for the shared prompt, the (n, prefix_len) array and a list of equally long prompts without
+    lists, which keep their routes."""
+    if isinstance(prefix, tuple) and len(prefix) == 2 and np.ndim(prefix[0]) == 2:
+        rows, lens = _i32(prefix[0]), _i32(prefix[1])
+        if rows.shape[0] != n or lens.shape != (n,):
+            raise ValueError(f"per-row prompts must be ((n={n}, stride), (n,)), got {rows.shape} and {lens.shape}")
+        if rows.shape[1] < 1 or int(lens.min()) < 1 or int(lens.max()) > rows.shape[1]:
+            raise ValueError(f"prompt lengths must lie in 1..{rows.shape[1]}, got {lens.tolist()}")
+        return rows, lens
+    if isinstance(prefix, (list, tuple)) and len(prefix) > 0 and all(np.ndim(p) == 1 for p in prefix):
+        lens = [len(p) for p in prefix]
+        if min(lens) == max(lens) and not with_lists:
+            return None
+        if len(prefix) != n:
+            raise ValueError(f"per-row prompts: {len(prefix)} prompts for {n} rows")
+        if min(lens) < 1:
+            raise ValueError("per-row prompts: an empty prompt")
+        rows = np.zeros((n, max(lens)), dtype=np.int32)
+        for b, p in enumerate(prefix):
+            rows[b, : lens[b]] = np.asarray(p, dtype=np.int32)
+        return rows, _i32(lens)
+    return None
+
+
 def _ptr(a) -> C.c_void_p:
     if a is None:
         return C.c_void_p(0)
@@ -320,11 +348,41 @@ class HipS2STModel(_Handle):
         or an (n, prefix_len) array with one prompt per row (sc_generate_text_rows; not with ``banned_seqs``).
         ``boost_seqs`` / ``boost``: phrases as token sequences and the bonus per matched token for the phrase-boost step
         processor (sc_generate_text_boosted; the scores include the bonus); no phrases or ``boost == 0`` is the call
-        without them.  They take one prompt for all rows, like ``banned_seqs``."""
+        without them.  They take one prompt for all rows, like ``banned_seqs``.
+        Forced target prefixes: ``prefix`` may also be a list with one prompt per row of DIFFERENT lengths, or a tuple
+        ``(rows (n, stride), lens (n,))`` - row b is fed rows[b, :lens[b]] and generates from there
+        (sc_generate_text_prompts: one batch, each row with the bits of the call whose shared prompt is its own; these two
+        forms take ``banned_seqs`` and ``boost_seqs``, a list of equally long prompts included).  Equal lengths without lists keep
+        the sc_generate_text_rows route."""
         assert enc.is_cuda and enc.is_contiguous()
         n, s_enc, M = enc.shape
-        pre = _i32(prefix)
         boosted = boost_seqs is not None and len(boost_seqs) > 0 and float(boost) != 0.0
+        has_banned = banned_seqs is not None and len(banned_seqs) > 0
+        ragged = _ragged_prompts(prefix, n, boosted or has_banned)
+        if ragged is not None:
+            rows, plens = ragged
+            if int(plens.min()) == int(plens.max()) and not boosted and not has_banned:
+                prefix = np.ascontiguousarray(rows[:, : int(plens[0])])  # equal lengths: today's route (sc_generate_text_rows)
+                ragged = None
+        pre = _i32(prefix) if ragged is None else ragged[0]
+        if ragged is not None:
+            o = self._gen_opts(beam_size, soft_max_seq_len, hard_max_seq_len, min_seq_len, unk_penalty, use_graph, len_penalty,
+                               normalize_scores, no_repeat_ngram_size, source_len)
+            max_len = self.lib.sc_text_max_len(self.handle, C.byref(o), s_enc)
+            ids = np.zeros((n, max(1, max_len)), dtype=np.int32)
+            lens = np.zeros(n, dtype=np.int32)
+            scores = np.zeros(n, dtype=np.float32)
+            hidden = torch.empty(n, max(1, max_len - 1), M, dtype=torch.float32, device=self.device) if want_hidden else None
+            el = _i32(enc_lens)
+            b_tok, b_off = _lib.banned_csr(banned_seqs) if has_banned else (None, None)
+            p_tok, p_off = _lib.banned_csr(boost_seqs) if boosted else (None, None)
+            self._after_torch()
+            check(self.lib.sc_generate_text_prompts(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(pre), pre.shape[1],
+                                                    _ptr(ragged[1]), _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden), _ptr(b_tok),
+                                                    _ptr(b_off), 0 if b_off is None else len(b_off) - 1, _ptr(p_tok), _ptr(p_off),
+                                                    0 if p_off is None else len(p_off) - 1, float(boost) if boosted else 0.0),
+                  "sc_generate_text_prompts")
+            return ids, lens, scores, hidden
         if pre.ndim == 2 and boosted:
             raise ValueError("boost_seqs take one prompt for all rows (sc_generate_text_boosted)")
         if pre.ndim == 2 and pre.shape[0] != n:

@@ -77,8 +77,10 @@ def mintox_pipeline(
     duration_factor: float = 1.0,
     prosody_encoder_input: Optional[SequenceData] = None,
     _trace: Optional[Dict[str, Any]] = None,
+    forced_prefix: Any = None,
 ) -> Tuple[List[StringLike], Optional[Tensor]]:
-    """MinTox: Mitigation at INference time of added TOXicity (reference signature; ``_trace`` is this package's)."""
+    """MinTox: Mitigation at INference time of added TOXicity (reference signature; ``_trace`` and ``forced_prefix`` are this
+    package's: the rows generated again keep their forced target prefix, ``Translator.predict``'s argument)."""
     from ..inference.translator import Modality, Translator
 
     if text_generation_opts is None:
@@ -108,6 +110,8 @@ def mintox_pipeline(
         lens = model_input["seq_lens"]
         lens = lens if isinstance(lens, Tensor) else torch.tensor(list(lens))
         model_input["seq_lens"] = torch.index_select(lens, 0, rows_t.to(lens.device))
+        if isinstance(forced_prefix, tuple):  # one entry per item: those of the rows generated again
+            forced_prefix = tuple(forced_prefix[r] for r in toxic_rows)
     seqs = model_input["seqs"]
     # the lengths go along whenever the input has them, as in Translator.predict's own first call (the reference builds a
     # padding mask for ragged input only; for a full-length batch the two are the same)
@@ -117,7 +121,7 @@ def mintox_pipeline(
         input_modality=input_modality, output_modality=output_modality, tgt_lang=tgt_lang,
         unit_generation_ngram_filtering=unit_generation_ngram_filtering, text_generation_opts=text_generation_opts,
         unit_generation_opts=unit_generation_opts, duration_factor=duration_factor, prosody_encoder_input=prosody_encoder_input,
-        _trace=_trace,
+        _trace=_trace, forced_prefix=forced_prefix,
     )
     batched = len(original_texts) > 1
     if batched:
