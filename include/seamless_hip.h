@@ -464,6 +464,32 @@ int sc_generate_text_prompts(sc_model* m, const float* d_enc, int32_t n, int32_t
                              const int32_t* h_banned_offsets, int32_t n_banned, const int32_t* h_boost_tokens,
                              const int32_t* h_boost_offsets, int32_t n_boost, float boost);
 
+/* Beam n-best lists with per-token scores: sc_generate_text_prompts' arguments (one prompt per row, of any length; lists as
+ * sc_generate_text_boosted's), but EVERY finished hypothesis of the search leaves, best first - the reference generator's list of
+ * hypotheses with seq, score and step_scores (ggml/examples/unity/fairseq2.cpp:1310-1348, :1597-1602).  beam_size is 1..8 and the
+ * call always runs the host-driven beam loop (never the decode engine or the greedy chain); nbest is 1..beam_size.
+ * Outputs (host): h_out_ids [n][nbest][max_len] (max_len = sc_text_max_len(opts, s_enc); pad behind a hypothesis' length),
+ * h_out_lens / h_out_scores [n][nbest], h_out_counts [n] = min(finished hypotheses, nbest) >= 1, and h_step_scores (nullable)
+ * [n][nbest][max_len]: step[0] = 0, step[t] = c[t] - c[t-1] for 1 <= t < len, one fp32 subtraction of the search's cumulative
+ * scores c (prompt positions: the echoed prompt's raw log-probabilities; the last one: the EOS candidate's un-normalised score),
+ * 0 behind the length.  So sum(step) is the hypothesis' un-normalised score and score = sum / (len - 1)^len_penalty when
+ * normalize_scores is set.  Hypothesis rows behind h_out_counts[u] are pad / length 0 / score 0 / step 0.  The order is the one
+ * the other entries pick their winner in: NaN first, then the higher score, ties to the hypothesis that finished earlier.
+ * The contract: hypothesis 0 of every utterance equals sc_generate_text_prompts on the same arguments bit for bit - ids, length
+ * and score.  With a boost list the scores and the step scores include the bonus, as sc_generate_text_boosted documents.
+ * The score history lives in device memory beside the beams' sequences and is allocated by this entry alone.
+ * SC_ERR_INVALID before any device work, sc_last_error naming the reason: a NULL pointer (h_step_scores may be NULL), beam_size
+ * outside 1..8, nbest outside 1..beam_size, and everything sc_generate_text_prompts refuses.  An utterance without a finished
+ * hypothesis is an error, as it is there.  Decoder outputs are not captured (the n-best of sc_t2u_ar / sc_s2st: not built). */
+int sc_generate_text_nbest(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens, const sc_gen_opts* opts,
+                           const int32_t* h_prompt_rows /* [n][prompt_stride] */, int32_t prompt_stride,
+                           const int32_t* h_prompt_lens /* [n], 1 .. prompt_stride */, int32_t nbest,
+                           int32_t* h_out_ids /* [n][nbest][max_len] */, int32_t* h_out_lens /* [n][nbest] */,
+                           float* h_out_scores /* [n][nbest] */, int32_t* h_out_counts /* [n] */,
+                           float* h_step_scores /* [n][nbest][max_len], nullable */, const int32_t* h_banned_tokens,
+                           const int32_t* h_banned_offsets, int32_t n_banned, const int32_t* h_boost_tokens,
+                           const int32_t* h_boost_offsets, int32_t n_boost, float boost);
+
 /* a12-a17: UnitYNART2UModel.forward + argmax + unit decoding
  * (models/unity/model.py:379-441, generator.py:338-353).  h_text_seqs
  * [n][s_text] is text_seqs[:, :-1] (pad filled), h_text_lens its PaddingMask.

@@ -248,6 +248,26 @@ int sc_op_beam_select(const float* d_cand_val, const int32_t* d_cand_idx, const 
 int sc_op_beam_compact(const int32_t* d_done, int32_t* d_slot_utt, int32_t* d_slots, int32_t* d_rows, int32_t* d_seqs, float* d_cum,
                        int32_t* d_tok, int32_t* d_enc_lens, int32_t* d_anc, int32_t n, int32_t beams, int32_t max_len, int32_t anc_ld,
                        int32_t seq_len, int32_t anc_len);
+/* The score history of sc_generate_text_nbest (tests/test_nbest_kernels_gpu.py).  sc_op_beam_select_hist is sc_op_beam_select with
+ * d_hist_cur / d_hist_new [n*beams][max_len] and d_fin_hist [n][beams][max_len] (fp32; beam_select_kernel<true>): history rows follow
+ * their parents as the sequence rows do, the new candidate's score lands at step + 1, a finished hypothesis keeps its parent's
+ * history and the raw score of its EOS candidate at step + 1, 0 behind it.  sc_op_beam_compact_hist is sc_op_beam_compact with
+ * d_hist [n*beams][max_len], moved with the slots (seq_len positions).  sc_op_beam_nbest (beam_nbest_kernel): the fin_count[u]
+ * finished hypotheses of utterance u ranked NaN first, then by the higher score, ties to the earlier slot; the first nbest
+ * (<= beams <= 8) packed into d_out_ids / d_out_step [n][nbest][max_len], d_out_lens / d_out_scores [n][nbest], d_out_counts [n];
+ * step[0] = 0, step[t] = hist[t] - hist[t-1]; pad_idx / 0 behind lengths and counts. */
+int sc_op_beam_select_hist(const float* d_cand_val, const int32_t* d_cand_idx, const int32_t* d_seqs_cur, int32_t* d_seqs_new,
+                           float* d_fin_score, int32_t* d_fin_len, int32_t* d_fin_seq, int32_t* d_fin_count, int32_t* d_done,
+                           int32_t* d_remaining, int32_t* d_tok, int32_t* d_src_row, float* d_cum, int32_t* d_anc, int32_t anc_ld,
+                           const int32_t* d_slot_utt, const int32_t* d_slots, int32_t n, int32_t beams, int32_t K, int32_t V, int32_t max_len,
+                           int32_t step, int32_t eos_idx, int32_t pad_idx, int32_t normalize, float len_penalty, const float* d_hist_cur,
+                           float* d_hist_new, float* d_fin_hist);
+int sc_op_beam_compact_hist(const int32_t* d_done, int32_t* d_slot_utt, int32_t* d_slots, int32_t* d_rows, int32_t* d_seqs, float* d_cum,
+                            int32_t* d_tok, int32_t* d_enc_lens, int32_t* d_anc, int32_t n, int32_t beams, int32_t max_len, int32_t anc_ld,
+                            int32_t seq_len, int32_t anc_len, float* d_hist);
+int sc_op_beam_nbest(const int32_t* d_fin_seq, const int32_t* d_fin_len, const float* d_fin_score, const float* d_fin_hist,
+                     const int32_t* d_fin_count, int32_t n, int32_t beams, int32_t nbest, int32_t max_len, int32_t pad_idx, int32_t* d_out_ids,
+                     int32_t* d_out_lens, float* d_out_scores, int32_t* d_out_counts, float* d_out_step);
 int sc_op_gather_cache(const float* d_src, float* d_dst, const int32_t* d_src_row, int32_t rows, int32_t len, int32_t cap, int32_t M,
                        int32_t layers, int64_t layer_stride);
 int sc_op_row_token_lprob(const float* d_logits, int64_t ld, int32_t rows, int32_t V, int32_t row_stride, int32_t token, float* d_out);

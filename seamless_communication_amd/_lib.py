@@ -211,6 +211,8 @@ SIGNATURES = {
     "sc_generate_text_rows": (C.c_int, [_P, _P, _i, _i, _P, _P, _P, _i, _P, _P, _P, _P]),
     "sc_generate_text_prompts": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _i,
                                            C.c_float]),
+    "sc_generate_text_nbest": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _i, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P,
+                                         _i, C.c_float]),
     "sc_engine_create": (_P, [_P, C.POINTER(sc_engine_opts)]),
     "sc_engine_free": (None, [_P]),
     "sc_engine_attach": (C.c_int, [_P, _P]),
@@ -342,6 +344,10 @@ SIGNATURES = {
     "sc_op_beam_select": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _i, _i, _i, _i, _i, _i, _i, _i,
                                     _i, C.c_float]),
     "sc_op_beam_compact": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _i]),
+    "sc_op_beam_select_hist": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _P, _i, _i, _i, _i, _i, _i, _i,
+                                         _i, _i, C.c_float, _P, _P, _P]),
+    "sc_op_beam_compact_hist": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _i, _P]),
+    "sc_op_beam_nbest": (C.c_int, [_P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _P, _P, _P, _P, _P]),
     "sc_op_gather_cache": (C.c_int, [_P, _P, _P, _i, _i, _i, _i, _i, C.c_int64]),
     "sc_op_row_token_lprob": (C.c_int, [_P, C.c_int64, _i, _i, _i, _i, _P]),
     "sc_op_dstep_attention_ex": (C.c_int, [_P, _i, _P, _P, _P, _i, _i, _i, _P, _i, _i, _i, _P, _P, _P, _P, _i, _P, _P]),

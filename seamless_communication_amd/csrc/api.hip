@@ -459,28 +459,26 @@ int sc_generate_text_rows(sc_model* m, const float* d_enc, int32_t n, int32_t s_
     SC_API_END
 }
 
-int sc_generate_text_prompts(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
-                             const sc_gen_opts* opts, const int32_t* h_prompt_rows, int32_t prompt_stride, const int32_t* h_prompt_lens,
-                             int32_t* h_out_ids, int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden,
-                             const int32_t* h_banned_tokens, const int32_t* h_banned_offsets, int32_t n_banned,
-                             const int32_t* h_boost_tokens, const int32_t* h_boost_offsets, int32_t n_boost, float boost) {
-    SC_API_BEGIN
-    SC_CHECK(m && d_enc && h_enc_lens && opts && h_prompt_rows && h_prompt_lens && h_out_ids && h_out_lens,
-             "sc_generate_text_prompts: null argument");
-    SC_CHECK(n > 0 && prompt_stride >= 1, "sc_generate_text_prompts: n=%d prompt_stride=%d", n, prompt_stride);
-    SC_CHECK(n_banned >= 0 && (n_banned == 0 || (h_banned_tokens && h_banned_offsets)), "sc_generate_text_prompts: bad banned list");
-    SC_CHECK(n_boost >= 0 && (n_boost == 0 || (h_boost_tokens && h_boost_offsets)), "sc_generate_text_prompts: bad phrase list");
+namespace {
+// The argument checks of sc_generate_text_prompts (shared with sc_generate_text_nbest), on the host before any device work
+void check_prompts_call(const char* who, sc_model* m, int32_t n, int32_t s_enc, const sc_gen_opts* opts, const int32_t* h_prompt_rows,
+                        int32_t prompt_stride, const int32_t* h_prompt_lens, const int32_t* h_banned_tokens, const int32_t* h_banned_offsets,
+                        int32_t n_banned, const int32_t* h_boost_tokens, const int32_t* h_boost_offsets, int32_t n_boost, float boost,
+                        int* out_shortest, int* out_longest) {
+    SC_CHECK(n > 0 && prompt_stride >= 1, "%s: n=%d prompt_stride=%d", who, n, prompt_stride);
+    SC_CHECK(n_banned >= 0 && (n_banned == 0 || (h_banned_tokens && h_banned_offsets)), "%s: bad banned list", who);
+    SC_CHECK(n_boost >= 0 && (n_boost == 0 || (h_boost_tokens && h_boost_offsets)), "%s: bad phrase list", who);
     const DecStack W = unity_stack(m->m);
     const int max_len = text_max_len(m->m, *opts, s_enc);
     int shortest = prompt_stride, longest = 0;
     for (int b = 0; b < n; ++b) {
         const int len = h_prompt_lens[b];
-        SC_CHECK(len >= 1 && len <= prompt_stride, "sc_generate_text_prompts: row %d: prompt length %d outside 1..%d", b, len, prompt_stride);
-        SC_CHECK(len < max_len, "sc_generate_text_prompts: row %d: prompt length %d >= effective max length %d", b, len, max_len);
+        SC_CHECK(len >= 1 && len <= prompt_stride, "%s: row %d: prompt length %d outside 1..%d", who, b, len, prompt_stride);
+        SC_CHECK(len < max_len, "%s: row %d: prompt length %d >= effective max length %d", who, b, len, max_len);
         const int32_t* p = h_prompt_rows + (size_t)b * prompt_stride;
         for (int t = 0; t < len; ++t) {
-            SC_CHECK(p[t] >= 0 && p[t] < W.vocab, "sc_generate_text_prompts: row %d: prompt token %d outside the vocabulary", b, p[t]);
-            SC_CHECK(t == 0 || (p[t] != W.pad_idx && p[t] != W.eos_idx), "sc_generate_text_prompts: row %d: pad / EOS (%d) at prompt position %d", b,
+            SC_CHECK(p[t] >= 0 && p[t] < W.vocab, "%s: row %d: prompt token %d outside the vocabulary", who, b, p[t]);
+            SC_CHECK(t == 0 || (p[t] != W.pad_idx && p[t] != W.eos_idx), "%s: row %d: pad / EOS (%d) at prompt position %d", who, b,
                      p[t], t);
         }
         shortest = std::min(shortest, len), longest = std::max(longest, len);
@@ -497,12 +495,66 @@ int sc_generate_text_prompts(sc_model* m, const float* d_enc, int32_t n, int32_t
         const std::string bad = boost_value_check(boost);
         SC_CHECK(bad.empty(), "%s", bad.c_str());
     }
+    *out_shortest = shortest, *out_longest = longest;
+}
+}  // namespace
+
+int sc_generate_text_prompts(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
+                             const sc_gen_opts* opts, const int32_t* h_prompt_rows, int32_t prompt_stride, const int32_t* h_prompt_lens,
+                             int32_t* h_out_ids, int32_t* h_out_lens, float* h_out_scores, float* d_dec_hidden,
+                             const int32_t* h_banned_tokens, const int32_t* h_banned_offsets, int32_t n_banned,
+                             const int32_t* h_boost_tokens, const int32_t* h_boost_offsets, int32_t n_boost, float boost) {
+    SC_API_BEGIN
+    SC_CHECK(m && d_enc && h_enc_lens && opts && h_prompt_rows && h_prompt_lens && h_out_ids && h_out_lens,
+             "sc_generate_text_prompts: null argument");
+    int shortest = 0, longest = 0;
+    check_prompts_call("sc_generate_text_prompts", m, n, s_enc, opts, h_prompt_rows, prompt_stride, h_prompt_lens, h_banned_tokens, h_banned_offsets,
+                       n_banned, h_boost_tokens, h_boost_offsets, n_boost, boost, &shortest, &longest);
+    BannedHost bh;
+    bh.tokens = h_banned_tokens, bh.offsets = h_banned_offsets, bh.n = n_banned;
+    BoostHost ph;
+    ph.tokens = h_boost_tokens, ph.offsets = h_boost_offsets, ph.n = n_boost, ph.boost = boost;
     SC_HIP(hipSetDevice(m->m.device));
     // equal lengths: sc_generate_text_rows with the lists; otherwise the shortest prompt is echoed for all rows and the per-row
     // lengths go down with the call
     run_generate_text(m->m, d_enc, n, s_enc, h_enc_lens, *opts, h_prompt_rows, shortest, h_out_ids, h_out_lens, h_out_scores, d_dec_hidden,
                       nullptr, 0, nullptr, n_banned > 0 ? &bh : nullptr, /*prefix_stride=*/prompt_stride,
                       n_boost > 0 && boost != 0.f ? &ph : nullptr, shortest == longest ? nullptr : h_prompt_lens);
+    SC_API_END
+}
+
+int sc_generate_text_nbest(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens, const sc_gen_opts* opts,
+                           const int32_t* h_prompt_rows, int32_t prompt_stride, const int32_t* h_prompt_lens, int32_t nbest,
+                           int32_t* h_out_ids, int32_t* h_out_lens, float* h_out_scores, int32_t* h_out_counts, float* h_step_scores,
+                           const int32_t* h_banned_tokens, const int32_t* h_banned_offsets, int32_t n_banned,
+                           const int32_t* h_boost_tokens, const int32_t* h_boost_offsets, int32_t n_boost, float boost) {
+    SC_API_BEGIN
+    SC_CHECK(m && d_enc && h_enc_lens && opts && h_prompt_rows && h_prompt_lens && h_out_ids && h_out_lens && h_out_scores && h_out_counts,
+             "sc_generate_text_nbest: null argument");
+    SC_CHECK(opts->beam_size >= 1 && opts->beam_size <= 8, "sc_generate_text_nbest: beam_size %d outside 1..8", opts->beam_size);
+    SC_CHECK(nbest >= 1 && nbest <= opts->beam_size, "sc_generate_text_nbest: nbest %d outside 1..beam_size (%d)", nbest, opts->beam_size);
+    SC_CHECK(opts->no_repeat_ngram_size >= 0, "sc_generate_text_nbest: no_repeat_ngram_size=%d", opts->no_repeat_ngram_size);
+    int shortest = 0, longest = 0;
+    check_prompts_call("sc_generate_text_nbest", m, n, s_enc, opts, h_prompt_rows, prompt_stride, h_prompt_lens, h_banned_tokens, h_banned_offsets,
+                       n_banned, h_boost_tokens, h_boost_offsets, n_boost, boost, &shortest, &longest);
+    SC_CHECK(s_enc > 0, "sc_generate_text_nbest: empty batch");
+    const DecStack W = unity_stack(m->m);
+    const int max_len = text_max_len(m->m, *opts, s_enc);
+    check_generation_limits("sc_generate_text_nbest", *opts, shortest, max_len, W.max_seq_len, n, s_enc, h_enc_lens);
+    BannedHost bh;
+    bh.tokens = h_banned_tokens, bh.offsets = h_banned_offsets, bh.n = n_banned;
+    BoostHost ph;
+    ph.tokens = h_boost_tokens, ph.offsets = h_boost_offsets, ph.n = n_boost, ph.boost = boost;
+    BeamNbestOut out;
+    out.nbest = nbest, out.h_ids = h_out_ids, out.h_lens = h_out_lens, out.h_scores = h_out_scores, out.h_counts = h_out_counts;
+    out.h_step = h_step_scores;
+    SC_HIP(hipSetDevice(m->m.device));
+    // always the host-driven beam loop (run_generate_text's beam branch, whatever the beam size), prompts as sc_generate_text_prompts
+    prof::set_tag("dec");
+    if (m->m.engine) m->m.engine->expect(m->m, -n);
+    run_generate_beam(m->m, W, d_enc, n, s_enc, h_enc_lens, *opts, h_prompt_rows, shortest, nullptr, nullptr, nullptr, nullptr, max_len,
+                      n_banned > 0 ? &bh : nullptr, /*prefix_stride=*/prompt_stride, n_boost > 0 && boost != 0.f ? &ph : nullptr,
+                      shortest == longest ? nullptr : h_prompt_lens, &out);
     SC_API_END
 }
 
@@ -1918,6 +1970,87 @@ int sc_op_beam_compact(const int32_t* d_done, int32_t* d_slot_utt, int32_t* d_sl
     a.seqs = d_seqs, a.cum = d_cum, a.tok = d_tok, a.enc_lens = d_enc_lens, a.anc = d_anc;
     a.n = n, a.beams = beams, a.max_len = max_len, a.anc_ld = anc_ld, a.seq_len = seq_len, a.anc_len = anc_len;
     launch_beam_compact(a, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+// the same walk with the score history (BeamHistArgs): beam_select_kernel<true>
+int sc_op_beam_select_hist(const float* d_cand_val, const int32_t* d_cand_idx, const int32_t* d_seqs_cur, int32_t* d_seqs_new,
+                           float* d_fin_score, int32_t* d_fin_len, int32_t* d_fin_seq, int32_t* d_fin_count, int32_t* d_done,
+                           int32_t* d_remaining, int32_t* d_tok, int32_t* d_src_row, float* d_cum, int32_t* d_anc, int32_t anc_ld,
+                           const int32_t* d_slot_utt, const int32_t* d_slots, int32_t n, int32_t beams, int32_t K, int32_t V, int32_t max_len,
+                           int32_t step, int32_t eos_idx, int32_t pad_idx, int32_t normalize, float len_penalty, const float* d_hist_cur,
+                           float* d_hist_new, float* d_fin_hist) {
+    SC_API_BEGIN
+    SC_CHECK(d_cand_val && d_cand_idx && d_seqs_cur && d_seqs_new && d_fin_score && d_fin_len && d_fin_seq && d_fin_count && d_done &&
+                 d_remaining && d_tok && d_src_row && d_cum && (!d_anc || anc_ld >= 1) && d_hist_cur && d_hist_new && d_fin_hist,
+             "sc_op_beam_select_hist: null argument");
+    SC_CHECK(n >= 1 && beams >= 1 && K >= 1 && V >= 1 && step >= 0 && step + 1 < max_len, "sc_op_beam_select_hist: bad shape (n=%d beams=%d K=%d "
+             "V=%d step=%d max_len=%d)", n, beams, K, V, step, max_len);
+    for (int32_t c : op_read_ints(d_cand_idx, (size_t)n * K))
+        SC_CHECK(c >= 0 && (int64_t)c < (int64_t)beams * V, "sc_op_beam_select_hist: candidate index %d outside beams * V", c);
+    if (d_slot_utt)
+        for (int32_t u : op_read_ints(d_slot_utt, n)) SC_CHECK(u >= 0 && u < n, "sc_op_beam_select_hist: slot_utt entry %d outside 0..%d", u, n - 1);
+    if (d_slots) {
+        const int32_t slots = op_read_ints(d_slots, 1)[0];
+        SC_CHECK(slots >= 0 && slots <= n, "sc_op_beam_select_hist: *d_slots = %d outside 0..%d", slots, n);
+    }
+    const std::vector<int32_t> done = op_read_ints(d_done, n), count = op_read_ints(d_fin_count, n);
+    for (int u = 0; u < n; ++u)  // a searching utterance has a free hypothesis slot
+        SC_CHECK(done[u] || (count[u] >= 0 && count[u] < beams), "sc_op_beam_select_hist: fin_count[%d] = %d with done = 0", u, count[u]);
+    BeamSelectArgs a;
+    a.cand_val = d_cand_val, a.cand_idx = d_cand_idx, a.seqs_cur = d_seqs_cur, a.seqs_new = d_seqs_new;
+    a.fin_score = d_fin_score, a.fin_len = d_fin_len, a.fin_seq = d_fin_seq, a.fin_count = d_fin_count, a.done = d_done;
+    a.remaining = d_remaining, a.tok = d_tok, a.src_row = d_src_row, a.cum = d_cum, a.anc = d_anc, a.anc_ld = anc_ld;
+    a.slot_utt = d_slot_utt, a.d_slots = d_slots;
+    BeamHistArgs h;
+    h.cur = d_hist_cur, h.next = d_hist_new, h.fin = d_fin_hist;
+    a.beams = beams, a.K = K, a.V = V, a.max_len = max_len, a.step = step;
+    a.eos_idx = eos_idx, a.pad_idx = pad_idx, a.normalize = normalize, a.len_penalty = len_penalty;
+    launch_beam_select(a, n, g_op_stream, &h);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_beam_compact_hist(const int32_t* d_done, int32_t* d_slot_utt, int32_t* d_slots, int32_t* d_rows, int32_t* d_seqs, float* d_cum,
+                            int32_t* d_tok, int32_t* d_enc_lens, int32_t* d_anc, int32_t n, int32_t beams, int32_t max_len, int32_t anc_ld,
+                            int32_t seq_len, int32_t anc_len, float* d_hist) {
+    SC_API_BEGIN
+    SC_CHECK(d_slot_utt && d_slots && d_hist && n >= 1 && n <= 1024, "sc_op_beam_compact_hist: bad arguments (n=%d)", n);
+    SC_CHECK(seq_len >= 0 && seq_len <= max_len && anc_len >= 0 && (!d_anc || anc_len <= anc_ld), "sc_op_beam_compact_hist: bad lengths");
+    const int32_t slots = op_read_ints(d_slots, 1)[0];
+    SC_CHECK(slots >= 0 && slots <= n, "sc_op_beam_compact_hist: *d_slots = %d outside 0..%d", slots, n);
+    for (int32_t u : op_read_ints(d_slot_utt, slots)) SC_CHECK(u >= 0 && u < n, "sc_op_beam_compact_hist: slot_utt entry %d outside 0..%d", u, n - 1);
+    BeamCompactArgs a;
+    a.done = d_done, a.slot_utt = d_slot_utt, a.d_slots = d_slots, a.d_rows = d_rows;
+    a.seqs = d_seqs, a.cum = d_cum, a.tok = d_tok, a.enc_lens = d_enc_lens, a.anc = d_anc;
+    a.n = n, a.beams = beams, a.max_len = max_len, a.anc_ld = anc_ld, a.seq_len = seq_len, a.anc_len = anc_len;
+    launch_beam_compact(a, g_op_stream, d_hist);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_beam_nbest(const int32_t* d_fin_seq, const int32_t* d_fin_len, const float* d_fin_score, const float* d_fin_hist,
+                     const int32_t* d_fin_count, int32_t n, int32_t beams, int32_t nbest, int32_t max_len, int32_t pad_idx, int32_t* d_out_ids,
+                     int32_t* d_out_lens, float* d_out_scores, int32_t* d_out_counts, float* d_out_step) {
+    SC_API_BEGIN
+    SC_CHECK(d_fin_seq && d_fin_len && d_fin_score && d_fin_hist && d_fin_count && d_out_ids && d_out_lens && d_out_scores && d_out_counts &&
+                 d_out_step,
+             "sc_op_beam_nbest: null argument");
+    SC_CHECK(n >= 1 && beams >= 1 && beams <= 8 && nbest >= 1 && nbest <= beams && max_len >= 1,
+             "sc_op_beam_nbest: bad shape (n=%d beams=%d nbest=%d max_len=%d)", n, beams, nbest, max_len);
+    const std::vector<int32_t> count = op_read_ints(d_fin_count, n), lens = op_read_ints(d_fin_len, (size_t)n * beams);
+    for (int u = 0; u < n; ++u) {
+        SC_CHECK(count[u] >= 0 && count[u] <= beams, "sc_op_beam_nbest: fin_count[%d] = %d outside 0..%d", u, count[u], beams);
+        for (int i = 0; i < count[u]; ++i)
+            SC_CHECK(lens[(size_t)u * beams + i] >= 0 && lens[(size_t)u * beams + i] <= max_len, "sc_op_beam_nbest: fin_len[%d][%d] = %d", u, i,
+                     lens[(size_t)u * beams + i]);
+    }
+    BeamNbestArgs a;
+    a.fin_seq = d_fin_seq, a.fin_len = d_fin_len, a.fin_score = d_fin_score, a.fin_hist = d_fin_hist, a.fin_count = d_fin_count;
+    a.out_ids = d_out_ids, a.out_lens = d_out_lens, a.out_scores = d_out_scores, a.out_counts = d_out_counts, a.out_step = d_out_step;
+    a.n = n, a.beams = beams, a.nbest = nbest, a.max_len = max_len, a.pad_idx = pad_idx;
+    launch_beam_nbest(a, g_op_stream);
     SC_HIP(hipStreamSynchronize(g_op_stream));
     SC_API_END
 }

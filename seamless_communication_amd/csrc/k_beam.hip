@@ -21,6 +21,8 @@
 //   step_processors_boost_kernel - a call without phrases launches neither).
 // beam_select_kernel: the per-step candidate walk (finalise EOS hypotheses, refill the beams, append tokens);
 //   sequences, finished hypotheses and counters live in device memory, the host only polls `remaining`.
+//   With a score history (sc_generate_text_nbest: beam_select_kernel<true>, beam_compact_kernel<true>) the cumulative score of
+//   every position travels with the sequences; beam_nbest_kernel ranks and packs the finished hypotheses at the end.
 // row_token_lprob_kernel: log-softmax value of ONE given token per row (scores of the echoed prompt).
 // gather_cache_kernel: K/V cache rows re-ordered by the surviving beams (all layers in one launch).
 #include "kernels.h"
@@ -516,9 +518,14 @@ __global__ __launch_bounds__(256) void beam_merge_kernel(const float* __restrict
 // become the live beams.  Then the whole workgroup copies the sequences: finished hypotheses into their slots, the
 // surviving beams' rows from the current into the other sequence buffer with the new token appended.  Outputs for the
 // next step: token and source row per beam row (K/V re-order), cumulative scores.
-__global__ __launch_bounds__(256) void beam_select_kernel(BeamSelectArgs a) {
+// HIST (sc_generate_text_nbest): the score history travels with the sequences (BeamHistArgs).  A compile-time switch with an
+// argument block of its own: beam_select_kernel<false> takes an empty one and is the kernel every other call always ran.
+struct BeamNoHist {};
+template <bool HIST>
+__global__ __launch_bounds__(256) void beam_select_kernel(BeamSelectArgs a, std::conditional_t<HIST, BeamHistArgs, BeamNoHist> h) {
     __shared__ int sh_beam[BEAM_MAX_K], sh_tok[BEAM_MAX_K], sh_fbeam[BEAM_MAX_K], sh_fslot[BEAM_MAX_K];
     __shared__ float sh_sc[BEAM_MAX_K], sh_fscore[BEAM_MAX_K];
+    __shared__ float sh_fraw[HIST ? BEAM_MAX_K : 1];  // the EOS candidates' un-normalised scores
     __shared__ int sh_nfin, sh_done;
     const int u = blockIdx.x, tid = threadIdx.x, B = a.beams, K = a.K, step = a.step, L = a.max_len;
     if (a.d_slots && u >= *a.d_slots) return;  // an idle slot
@@ -536,6 +543,7 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamSelectArgs a) {
                     sh_fbeam[nfin] = beam;
                     sh_fslot[nfin] = count;
                     sh_fscore[nfin] = a.normalize ? sc / powf((float)(step + 1), a.len_penalty) : sc;
+                    if constexpr (HIST) sh_fraw[nfin] = sc;
                     ++nfin;
                     ++count;
                     if (count == B) {
@@ -568,6 +576,11 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamSelectArgs a) {
         const int* src = a.seqs_cur + (int64_t)(u * B + sh_fbeam[f]) * L;
         int* dst = a.fin_seq + (int64_t)(ut * B + sh_fslot[f]) * L;
         for (int t = tid; t < L; t += 256) dst[t] = t <= step ? src[t] : (t == step + 1 ? a.eos_idx : a.pad_idx);
+        if constexpr (HIST) {
+            const float* hsrc = h.cur + (int64_t)(u * B + sh_fbeam[f]) * L;
+            float* hdst = h.fin + (int64_t)(ut * B + sh_fslot[f]) * L;
+            for (int t = tid; t < L; t += 256) hdst[t] = t <= step ? hsrc[t] : (t == step + 1 ? sh_fraw[f] : 0.f);
+        }
         if (tid == 0) {
             a.fin_len[ut * B + sh_fslot[f]] = step + 2;
             a.fin_score[ut * B + sh_fslot[f]] = sh_fscore[f];
@@ -594,6 +607,11 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamSelectArgs a) {
         const int* src = a.seqs_cur + (int64_t)sr * L;
         int* dst = a.seqs_new + (int64_t)r * L;
         for (int t = tid; t < L; t += 256) dst[t] = (!sh_done && t == step + 1) ? sh_tok[b] : src[t];
+        if constexpr (HIST) {
+            const float* hsrc = h.cur + (int64_t)sr * L;
+            float* hdst = h.next + (int64_t)r * L;
+            for (int t = tid; t < L; t += 256) hdst[t] = (!sh_done && t == step + 1) ? sh_sc[b] : hsrc[t];
+        }
         if (tid == 0) {
             a.src_row[r] = sr;
             a.tok[r] = sh_done ? a.eos_idx : sh_tok[b];
@@ -602,10 +620,13 @@ __global__ __launch_bounds__(256) void beam_select_kernel(BeamSelectArgs a) {
     }
 }
 
+
 // beam_compact_kernel (BeamCompactArgs): one workgroup.  Slots whose utterance is done are dropped, the others keep their
 // order and move to the front; a moved slot's rows are copied to rows with LOWER indices that were vacated (or already moved)
 // earlier in the same sweep, so the sweep is in place.  Nothing moves when no slot was dropped.
-__global__ __launch_bounds__(256) void beam_compact_kernel(BeamCompactArgs a) {
+// HIST: the live rows' score history moves with the sequences (sc_generate_text_nbest)
+template <bool HIST>
+__global__ __launch_bounds__(256) void beam_compact_kernel(BeamCompactArgs a, std::conditional_t<HIST, float*, BeamNoHist> hist) {
     __shared__ int s_src[1024];  // new slot -> old slot
     __shared__ int s_keep;
     const int tid = threadIdx.x, B = a.beams;
@@ -625,6 +646,8 @@ __global__ __launch_bounds__(256) void beam_compact_kernel(BeamCompactArgs a) {
             for (int b = 0; b < B; ++b) {
                 const int64_t src = (int64_t)u * B + b, dst = (int64_t)v * B + b;
                 for (int t = tid; t < a.seq_len && t < a.max_len; t += 256) a.seqs[dst * a.max_len + t] = a.seqs[src * a.max_len + t];
+                if constexpr (HIST)  // the score history of the same positions (BeamHistArgs)
+                    for (int t = tid; t < a.seq_len && t < a.max_len; t += 256) hist[dst * a.max_len + t] = hist[src * a.max_len + t];
                 if (a.anc)
                     for (int t = tid; t < a.anc_len && t < a.anc_ld; t += 256) a.anc[dst * a.anc_ld + t] = a.anc[src * a.anc_ld + t];
                 if (tid == 0) {
@@ -646,6 +669,58 @@ __global__ __launch_bounds__(256) void beam_compact_kernel(BeamCompactArgs a) {
         for (int v = 0; v < keep; ++v) a.slot_utt[v] = s_src[v];
         *a.d_slots = keep;
         *a.d_rows = keep * B;
+    }
+}
+
+
+// beam_nbest_kernel (BeamNbestArgs): one workgroup per utterance.  Thread 0 ranks the utterance's finished hypotheses (at most
+// 8: an insertion sort over (order_key(score), finish slot) in LDS - the host's winner rule of run_generate_beam made a total
+// order), then the workgroup copies the first `nbest` of them, a thread per position: coalesced over t.
+__global__ __launch_bounds__(256) void beam_nbest_kernel(BeamNbestArgs a) {
+    __shared__ int s_key[BEAM_MAX_K], s_slot[BEAM_MAX_K];
+    __shared__ int s_count;
+    const int u = blockIdx.x, tid = threadIdx.x, B = a.beams, L = a.max_len;
+    if (tid == 0) {
+        const int count = min(max(a.fin_count[u], 0), B);
+        for (int i = 0; i < count; ++i) {
+            const int k = order_key(a.fin_score[u * B + i]);
+            int q = i;  // slot i goes in front of every ranked slot with a strictly lower key: ties keep finish order
+            for (; q > 0 && s_key[q - 1] < k; --q) {
+                s_key[q] = s_key[q - 1];
+                s_slot[q] = s_slot[q - 1];
+            }
+            s_key[q] = k;
+            s_slot[q] = i;
+        }
+        s_count = min(count, a.nbest);
+        a.out_counts[u] = s_count;
+    }
+    __syncthreads();
+    for (int h = 0; h < a.nbest; ++h) {
+        const int64_t o = (int64_t)u * a.nbest + h;
+        if (h < s_count) {
+            const int64_t f = (int64_t)u * B + s_slot[h];
+            const int len = min(max(a.fin_len[f], 0), L);
+            const int* seq = a.fin_seq + f * L;
+            const float* hist = a.fin_hist + f * L;
+            for (int t = tid; t < L; t += 256) {
+                a.out_ids[o * L + t] = t < len ? seq[t] : a.pad_idx;
+                a.out_step[o * L + t] = (t >= 1 && t < len) ? hist[t] - hist[t - 1] : 0.f;
+            }
+            if (tid == 0) {
+                a.out_lens[o] = len;
+                a.out_scores[o] = a.fin_score[f];
+            }
+        } else {
+            for (int t = tid; t < L; t += 256) {
+                a.out_ids[o * L + t] = a.pad_idx;
+                a.out_step[o * L + t] = 0.f;
+            }
+            if (tid == 0) {
+                a.out_lens[o] = 0;
+                a.out_scores[o] = 0.f;
+            }
+        }
     }
 }
 
@@ -763,16 +838,29 @@ void launch_beam_candidates_chunked(float* logits, int64_t ld, int n_utt, int be
     SC_LAUNCH_CHECK();
 }
 
-void launch_beam_select(const BeamSelectArgs& a, int n_utt, hipStream_t s) {
+void launch_beam_select(const BeamSelectArgs& a, int n_utt, hipStream_t s, const BeamHistArgs* hist) {
     SC_CHECK(a.beams >= 1 && a.beams <= BEAM_MAX_K && a.K <= BEAM_MAX_K, "beam select: beam_size %d / K %d out of range", a.beams, a.K);
-    hipLaunchKernelGGL(beam_select_kernel, dim3(n_utt), dim3(256), 0, s, a);
+    SC_CHECK(!hist || (hist->cur && hist->next && hist->fin), "beam select: the score history needs all three of its buffers");
+    if (hist) hipLaunchKernelGGL(beam_select_kernel<true>, dim3(n_utt), dim3(256), 0, s, a, *hist);
+    else hipLaunchKernelGGL(beam_select_kernel<false>, dim3(n_utt), dim3(256), 0, s, a, BeamNoHist{});
     SC_LAUNCH_CHECK();
 }
 
-void launch_beam_compact(const BeamCompactArgs& a, hipStream_t s) {
+void launch_beam_compact(const BeamCompactArgs& a, hipStream_t s, float* hist) {
     SC_CHECK(a.n >= 1 && a.n <= 1024 && a.beams >= 1 && a.done && a.slot_utt && a.d_slots && a.d_rows && a.seqs && a.cum && a.tok && a.enc_lens,
              "beam compact: bad arguments (n=%d)", a.n);
-    hipLaunchKernelGGL(beam_compact_kernel, dim3(1), dim3(256), 0, s, a);
+    if (hist) hipLaunchKernelGGL(beam_compact_kernel<true>, dim3(1), dim3(256), 0, s, a, hist);
+    else hipLaunchKernelGGL(beam_compact_kernel<false>, dim3(1), dim3(256), 0, s, a, BeamNoHist{});
+    SC_LAUNCH_CHECK();
+}
+
+void launch_beam_nbest(const BeamNbestArgs& a, hipStream_t s) {
+    SC_CHECK(a.fin_seq && a.fin_len && a.fin_score && a.fin_hist && a.fin_count && a.out_ids && a.out_lens && a.out_scores && a.out_counts &&
+                 a.out_step,
+             "beam nbest: null argument");
+    SC_CHECK(a.n >= 1 && a.beams >= 1 && a.beams <= BEAM_MAX_K && a.nbest >= 1 && a.nbest <= a.beams && a.max_len >= 1,
+             "beam nbest: bad shape (n=%d beams=%d nbest=%d max_len=%d)", a.n, a.beams, a.nbest, a.max_len);
+    hipLaunchKernelGGL(beam_nbest_kernel, dim3(a.n), dim3(256), 0, s, a);
     SC_LAUNCH_CHECK();
 }
 

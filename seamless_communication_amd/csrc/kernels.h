@@ -691,7 +691,17 @@ struct BeamSelectArgs {
     int eos_idx = 0, pad_idx = 0, normalize = 1;
     float len_penalty = 1.f;
 };
-void launch_beam_select(const BeamSelectArgs& a, int n_utt, hipStream_t s);
+// Score history of a beam search (sc_generate_text_nbest only; its own argument block, so that the kernel of every other call
+// keeps its arguments and its code): hist[r][t] = cumulative score of row r's hypothesis after position t, moved exactly as the
+// sequence rows are - the parent's row, then the candidate's score at step + 1; a finished hypothesis keeps its parent's
+// history and the RAW (un-normalised) score of its EOS candidate at step + 1, 0 behind it.
+struct BeamHistArgs {
+    const float* cur = nullptr;  // [n*beams][max_len]
+    float* next = nullptr;       // [n*beams][max_len]
+    float* fin = nullptr;        // [n][beams][max_len]
+};
+// hist == null: beam_select_kernel<false>, the kernel without it; otherwise beam_select_kernel<true> (the same walk, the history moved with the sequences)
+void launch_beam_select(const BeamSelectArgs& a, int n_utt, hipStream_t s, const BeamHistArgs* hist = nullptr);
 // Packs the slots of utterances that are still searching to the front (stable), in place: per-row sequences, cumulative
 // scores, next tokens, encoder lengths and K/V ancestor rows move with their slot; slot_utt follows; *d_slots / *d_rows = the
 // new counts.  One workgroup (the arrays are a few hundred KB).  K/V cache rows do not move: the ancestor table names them.
@@ -708,7 +718,26 @@ struct BeamCompactArgs {
     int n = 0, beams = 0, max_len = 0, anc_ld = 0;
     int seq_len = 0, anc_len = 0;  // sequence positions / table positions in use
 };
-void launch_beam_compact(const BeamCompactArgs& a, hipStream_t s);
+// hist (nullable): the live rows' score history [n*beams][max_len] (BeamHistArgs), moved like seqs (beam_compact_kernel<true>)
+void launch_beam_compact(const BeamCompactArgs& a, hipStream_t s, float* hist = nullptr);
+// The n-best list of a finished beam search (sc_generate_text_nbest), one workgroup per utterance: the utterance's fin_count
+// finished hypotheses ranked in the order the host picks the winner in (order_key: NaN first, then the higher score, ties to the
+// earlier finish slot), the first `nbest` packed into the outputs.  out_step[t] = hist[t] - hist[t-1] (one fp32 subtraction,
+// fairseq2.cpp:1333-1341), out_step[0] = 0.  Behind a hypothesis' length: pad / 0; rows behind out_counts[u]: pad, length 0, score 0.
+struct BeamNbestArgs {
+    const int* fin_seq = nullptr;      // [n][beams][max_len]
+    const int* fin_len = nullptr;      // [n][beams]
+    const float* fin_score = nullptr;  // [n][beams]
+    const float* fin_hist = nullptr;   // [n][beams][max_len]
+    const int* fin_count = nullptr;    // [n]
+    int* out_ids = nullptr;            // [n][nbest][max_len]
+    int* out_lens = nullptr;           // [n][nbest]
+    float* out_scores = nullptr;       // [n][nbest]
+    int* out_counts = nullptr;         // [n] = min(fin_count, nbest)
+    float* out_step = nullptr;         // [n][nbest][max_len]
+    int n = 0, beams = 0, nbest = 0, max_len = 0, pad_idx = 0;
+};
+void launch_beam_nbest(const BeamNbestArgs& a, hipStream_t s);
 void launch_row_token_lprob(const float* logits, int64_t ld, int rows, int V, int row_stride, int token, float* out, hipStream_t s);
 // the per-row-token form: output i is the log-softmax value of row_tokens[i * row_stride] (a device array with one token per
 // logit row, e.g. StepCtx::d_tok; the caller has checked the tokens against V) in logit row i * row_stride

@@ -405,10 +405,19 @@ void run_t2u_ar(Model& m, const float* d_dec_hidden, int n, int s_text, const in
                 const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores);
 // T2U encoder (pre-LN StandardTransformerEncoder over the text decoder output; shared by the NAR and the AR T2U)
 void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, const int* d_text_lens, float* d_out);
+// sc_generate_text_nbest: where the ranked finished hypotheses of a beam search go (host memory; h_step nullable)
+struct BeamNbestOut {
+    int nbest = 0;
+    int32_t* h_ids = nullptr;     // [n][nbest][max_len]
+    int32_t* h_lens = nullptr;    // [n][nbest]
+    float* h_scores = nullptr;    // [n][nbest]
+    int32_t* h_counts = nullptr;  // [n]
+    float* h_step = nullptr;      // [n][nbest][max_len]
+};
 void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                        const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
                        float* d_dec_hidden, int max_len, const BannedHost* banned = nullptr, int prefix_stride = 0,
-                       const BoostHost* boost = nullptr, const int32_t* h_prefix_lens = nullptr);
+                       const BoostHost* boost = nullptr, const int32_t* h_prefix_lens = nullptr, const BeamNbestOut* nbest_out = nullptr);
 // sampled generation (model_sample.hip): outputs [n][num_gens][...], hypotheses of an utterance sorted by score
 void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                           const sc_sample_opts& so, const uint64_t* h_streams, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,

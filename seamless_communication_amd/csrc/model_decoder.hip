@@ -1001,7 +1001,9 @@ void hidden_of_best(Model& m, const float* d_enc, int n, int s_enc, const int32_
 void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
                        const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
                        float* d_dec_hidden, int max_len, const BannedHost* banned, int prefix_stride, const BoostHost* boost,
-                       const int32_t* h_prefix_lens) {
+                       const int32_t* h_prefix_lens, const BeamNbestOut* nbest_out) {
+    // nbest_out (nullable; sc_generate_text_nbest): every finished hypothesis leaves instead of the best one - the score history
+    // (BeamHistArgs) exists only then, and h_out_ids / h_out_lens / h_scores are not written.
     // prefix_stride: 0 = one prompt for all; otherwise utterance u's prompt is h_prefix[u * prefix_stride + ...], fed to each of its beams
     // h_prefix_lens (nullable; sc_generate_text_prompts): utterance u's prompt is h_prefix_lens[u] tokens long and prefix_len is
     // the SHORTEST of them.  The host echo below runs that far; from there an utterance that is still inside its prompt is
@@ -1024,6 +1026,9 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
     const int K = std::min(2 * B, V - 1);
     SC_CHECK(B <= 8, "sc_generate_text: beam_size %d > 8", B);
     SC_CHECK(d_dec_hidden == nullptr || W.layers == &m.dec, "beam search: decoder outputs are captured for the text decoder only");
+    const bool want_hist = nbest_out != nullptr;
+    SC_CHECK(!want_hist || (nbest_out->nbest >= 1 && nbest_out->nbest <= B && !d_dec_hidden), "sc_generate_text_nbest: nbest %d outside 1..%d",
+             want_hist ? nbest_out->nbest : 0, B);
     check_generation_limits("sc_generate_text", o, prefix_len, max_len, W.max_seq_len, n, s_enc, h_enc_lens);
     const BannedDevice banned_dev = upload_banned(m, banned, V);
     const BannedList& bl = banned_dev.list;
@@ -1137,6 +1142,20 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
         SC_HIP(hipMemsetAsync(d_fin_len.get(), 0, (size_t)nb * 4, m.stream));
         SC_HIP(hipStreamSynchronize(m.stream));  // `st` is a host temporary
     }
+    // score history of the live rows and of the finished hypotheses (n-best only): position 0 holds 0
+    // (allocated by that entry alone: the other callers of this function allocate what they always did)
+    Buf<float> d_hist_a, d_hist_b, d_fin_hist;
+    std::vector<float> hist_rows;
+    if (want_hist) {
+        d_hist_a = Buf<float>(m.pp(), (size_t)nb * max_len);
+        d_hist_b = Buf<float>(m.pp(), (size_t)nb * max_len);
+        d_fin_hist = Buf<float>(m.pp(), (size_t)nb * max_len);
+        hist_rows.assign((size_t)nb * max_len, 0.f);
+        SC_HIP(hipMemsetAsync(d_hist_b.get(), 0, (size_t)nb * max_len * 4, m.stream));
+        SC_HIP(hipMemsetAsync(d_fin_hist.get(), 0, (size_t)nb * max_len * 4, m.stream));
+    }
+    float* d_hist_cur = d_hist_a.get();
+    float* d_hist_new = d_hist_b.get();
     std::vector<float> pref(n);
     const int G = o.no_repeat_ngram_size;
     Buf<int> d_plen(m.pp(), ragged ? (size_t)n : 4);  // by UTTERANCE (read through slot_utt when the slots are packed)
@@ -1180,8 +1199,11 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
         SC_HIP(hipMemcpyAsync(pref.data(), d_pref.get(), (size_t)n * 4, hipMemcpyDeviceToHost, m.stream));
         SC_HIP(hipStreamSynchronize(m.stream));
         for (int r = 0; r < nb; ++r) cum[r] += pref[r / B];
+        if (want_hist)  // the partial sums, as they are added
+            for (int r = 0; r < nb; ++r) hist_rows[(size_t)r * max_len + t + 1] = cum[r];
     }
     SC_HIP(hipMemcpyAsync(d_cum.get(), cum.data(), (size_t)nb * 4, hipMemcpyHostToDevice, m.stream));
+    if (want_hist) SC_HIP(hipMemcpyAsync(d_hist_cur, hist_rows.data(), hist_rows.size() * 4, hipMemcpyHostToDevice, m.stream));
 
     // ---- search: every step is device work only; the host polls the `remaining` counter every 4th step --------
     const int start = prefix_len - 1;
@@ -1248,8 +1270,11 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
         a.anc_ld = max_len;
         a.slot_utt = compact ? d_slot_utt : nullptr;
         a.d_slots = compact ? d_slots : nullptr;
-        launch_beam_select(a, n, m.stream);
+        BeamHistArgs bh;
+        bh.cur = d_hist_cur, bh.next = d_hist_new, bh.fin = d_fin_hist;
+        launch_beam_select(a, n, m.stream, want_hist ? &bh : nullptr);
         std::swap(d_seqs_cur, d_seqs_new);
+        std::swap(d_hist_cur, d_hist_new);
         if (!use_anc) {
             // K/V rows follow their beams (all layers, one launch; rows of finished utterances map onto themselves)
             launch_gather_cache(kv_cur, kv_alt, d_src_row, nb, step + 1, max_len, M, 2 * L, layer_stride, m.stream);
@@ -1263,11 +1288,36 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
                 k.seqs = d_seqs_cur, k.cum = d_cum, k.tok = c.d_tok, k.enc_lens = c.d_enc_lens, k.anc = d_anc;
                 // (a slot that is still inside its prompt carries the rest of the prompt behind the positions written so far)
                 k.n = n, k.beams = B, k.max_len = max_len, k.anc_ld = max_len, k.seq_len = std::max(step + 2, longest_prefix), k.anc_len = step + 1;
-                launch_beam_compact(k, m.stream);
+                launch_beam_compact(k, m.stream, want_hist ? d_hist_cur : nullptr);
             }
             SC_HIP(hipMemcpyAsync(&remaining, d_remaining, 4, hipMemcpyDeviceToHost, m.stream));
             SC_HIP(hipStreamSynchronize(m.stream));
         }
+    }
+
+    // ---- every finished hypothesis, ranked on the device (beam_nbest_kernel: the order of the loop below) ----
+    if (want_hist) {
+        const int nbest = nbest_out->nbest;
+        const size_t rows = (size_t)n * nbest;
+        std::vector<int32_t> fin_count(n);
+        SC_HIP(hipMemcpyAsync(fin_count.data(), d_fin_count, (size_t)n * 4, hipMemcpyDeviceToHost, m.stream));
+        SC_HIP(hipStreamSynchronize(m.stream));
+        for (int u = 0; u < n; ++u) SC_CHECK(fin_count[u] > 0, "sc_generate_text_nbest: beam search returned no hypothesis for item %d", u);
+        Buf<int> d_out_i(m.pp(), rows * max_len + rows + n);
+        Buf<float> d_out_f(m.pp(), rows * max_len + rows);
+        BeamNbestArgs k;
+        k.fin_seq = d_fin_seq, k.fin_len = d_fin_len, k.fin_score = d_fin_score, k.fin_hist = d_fin_hist, k.fin_count = d_fin_count;
+        k.out_ids = d_out_i, k.out_lens = d_out_i.get() + rows * max_len, k.out_counts = k.out_lens + rows;
+        k.out_step = d_out_f, k.out_scores = d_out_f.get() + rows * max_len;
+        k.n = n, k.beams = B, k.nbest = nbest, k.max_len = max_len, k.pad_idx = W.pad_idx;
+        launch_beam_nbest(k, m.stream);
+        SC_HIP(hipMemcpyAsync(nbest_out->h_ids, k.out_ids, rows * max_len * 4, hipMemcpyDeviceToHost, m.stream));
+        SC_HIP(hipMemcpyAsync(nbest_out->h_lens, k.out_lens, rows * 4, hipMemcpyDeviceToHost, m.stream));
+        SC_HIP(hipMemcpyAsync(nbest_out->h_counts, k.out_counts, (size_t)n * 4, hipMemcpyDeviceToHost, m.stream));
+        SC_HIP(hipMemcpyAsync(nbest_out->h_scores, k.out_scores, rows * 4, hipMemcpyDeviceToHost, m.stream));
+        if (nbest_out->h_step) SC_HIP(hipMemcpyAsync(nbest_out->h_step, k.out_step, rows * max_len * 4, hipMemcpyDeviceToHost, m.stream));
+        SC_HIP(hipStreamSynchronize(m.stream));
+        return;
     }
 
     // ---- best hypothesis per utterance (sorted by score, fairseq2.cpp:1597-1602) ----------------------

@@ -4,7 +4,7 @@ from .pretssel_generator import PretsselGenerator
 from .prosody_encoder import ProsodyEncoder
 from .transcriber import Transcriber, Transcription, TranscriptionToken, TranscriptionTokenStats
 from .unit_extractor import UnitExtractor
-from .translator import BatchedSpeechOutput, LanguageId, MBRHypothesis, Modality, SampledHypothesis, Task, Translator
+from .translator import BatchedSpeechOutput, BeamHypothesis, LanguageId, MBRHypothesis, Modality, SampledHypothesis, Task, Translator
 
-__all__ = ["AlignmentExtractor", "BannedSequenceProcessor", "BatchedSpeechOutput", "LanguageId", "MBRHypothesis", "Modality", "NGramRepeatBlockProcessor", "PhraseBoostProcessor", "PretsselGenerator", "ProsodyEncoder", "SampledHypothesis", "SequenceGeneratorOptions", "Task", "TopKSampler", "TopPSampler", "Transcriber", "Transcription", "TranscriptionToken",
+__all__ = ["AlignmentExtractor", "BannedSequenceProcessor", "BatchedSpeechOutput", "BeamHypothesis", "LanguageId", "MBRHypothesis", "Modality", "NGramRepeatBlockProcessor", "PhraseBoostProcessor", "PretsselGenerator", "ProsodyEncoder", "SampledHypothesis", "SequenceGeneratorOptions", "Task", "TopKSampler", "TopPSampler", "Transcriber", "Transcription", "TranscriptionToken",
            "TranscriptionTokenStats", "Translator", "UnitExtractor", "word_timestamps"]

@@ -41,7 +41,7 @@ from ..runtime import HipS2STModel
 from ..tokenizer import CharTokenizer, NllbTextTokenizer, UnitTokenizer
 from .generator import SequenceGeneratorOptions, check_sampling, encode_bias_phrases, split_step_processors
 from ..scoring import score as _score
-from ..mbr import MBRHypothesis, mbr_decode as _mbr_decode
+from ..mbr import MBRHypothesis, mbr_decode as _mbr_decode, mbr_decode_beam as _mbr_decode_beam
 from ..lid import LanguageId, identify_encoded as _identify_encoded, identify_language as _identify_language
 
 logger = logging.getLogger(__name__)
@@ -89,6 +89,25 @@ class SampledHypothesis:
 
     score: float
     """The hypothesis score (sum of the log-probabilities, prompt included, length-normalised as beam-search scores are)."""
+
+
+@dataclass
+class BeamHypothesis:
+    """One hypothesis of ``Translator.predict_nbest``."""
+
+    text: StringLike
+    token_ids: List[int]
+    """The whole sequence: prompt, content, EOS."""
+
+    score: float
+    """The beam-search score (length-normalised unless ``normalize_scores`` is off)."""
+
+    step_scores: List[float]
+    """Per position of ``token_ids``: the score the position added (the token's log-probability under the step rules, a
+    phrase boost included); 0 at position 0.  Their sum is the un-normalised score."""
+
+    rank: int
+    """Its place in the item's list: 0 is what ``predict`` returns."""
 
 
 # unity architectures (models/unity/builder.py:109-192): `base` / `medium` are the v1 models (w2v-BERT with relative
@@ -692,8 +711,63 @@ class Translator:
             out.append(hyps)
         return out
 
+    @torch.inference_mode()
+    def predict_nbest(
+        self,
+        input: Union[str, Tensor, SequenceData],
+        task_str: str,
+        tgt_lang: str,
+        src_lang: Optional[str] = None,
+        *,
+        nbest: Optional[int] = None,
+        text_generation_opts: Optional[SequenceGeneratorOptions] = None,
+        sample_rate: int = 16000,
+        forced_prefix: Any = None,
+    ) -> List[List["BeamHypothesis"]]:
+        """The beam search's n-best list per input item (S2TT, ASR, T2TT), best first, each hypothesis with its per-token
+        scores - what the reference's generator hands back (``seq``, ``score``, ``step_scores``) and its ``Translator``
+        drops.  ``nbest``: 1..beam_size (None: ``beam_size``); an item may have fewer finished hypotheses than that.
+        ``text_generation_opts`` supplies ``beam_size`` (1..8), the length limits, penalties and step processors as for
+        ``predict``; hypothesis 0 is ``predict``'s text.  ``forced_prefix``: as ``predict``'s."""
+        input_modality, output_modality = self.get_modalities_from_task_str(task_str)
+        forced = parse_forced_prefix(self.text_tokenizer, forced_prefix, tgt_lang) if forced_prefix is not None else None
+        if output_modality != Modality.TEXT:
+            raise ValueError(f"Translator.predict_nbest covers text output (S2TT, ASR, T2TT); for {task_str} use predict(...)")
+        opts = text_generation_opts or SequenceGeneratorOptions(beam_size=5, soft_max_seq_len=(1, 200))
+        if getattr(opts, "sampler", None) is not None:
+            raise ValueError("Translator.predict_nbest runs the beam search: text_generation_opts.sampler must be None "
+                             "(Translator.sample draws hypotheses)")
+        if not 1 <= opts.beam_size <= 8:
+            raise ValueError("beam_size must be in [1, 8] on the HIP path")
+        nbest = opts.beam_size if nbest is None else nbest
+        if isinstance(nbest, bool) or int(nbest) != nbest or not 1 <= nbest <= opts.beam_size:
+            raise ValueError(f"`nbest` must be an integer in 1..beam_size ({opts.beam_size}), but is {nbest!r} instead.")
+        ngram, step_kw = self._step_processor_args(opts)
+        _, seqs, src_lens, _ = self._source_batch(input, input_modality, src_lang, sample_rate)
+        if input_modality == Modality.SPEECH:
+            enc, enc_lens = self.model.encode_speech(seqs, src_lens)
+        else:
+            enc, enc_lens = self.model.encode_text(seqs.cpu().numpy(), src_lens), np.asarray(src_lens, dtype=np.int32)
+        prompts = forced_prompts(self.text_tokenizer, forced, tgt_lang, len(src_lens))
+        prefix: Any = prompts if prompts is not None else self.text_tokenizer.target_prefix(tgt_lang)
+        ids, lens, scores, counts, step = self.model.generate_text_nbest(
+            enc, enc_lens.tolist(), prefix, beam_size=opts.beam_size, nbest=int(nbest), len_penalty=opts.len_penalty,
+            soft_max_seq_len=opts.soft_max_seq_len, hard_max_seq_len=opts.hard_max_seq_len, unk_penalty=opts.unk_penalty,
+            no_repeat_ngram_size=ngram, use_graph=self.use_graph, source_len=int(max(src_lens)), **step_kw)
+        out: List[List[BeamHypothesis]] = []
+        for b in range(ids.shape[0]):
+            hyps = []
+            for h in range(int(counts[b])):
+                toks = ids[b, h, : lens[b, h]].tolist()
+                hyps.append(BeamHypothesis(text=self.text_tokenizer.decode(toks), token_ids=toks, score=float(scores[b, h]),
+                                           step_scores=step[b, h, : lens[b, h]].tolist(), rank=h))
+            out.append(hyps)
+        return out
+
     # sampling, then minimum-Bayes-risk selection among the samples (mbr.py)
     mbr_decode = _mbr_decode
+    # the same selection among the beam search's n-best list
+    mbr_decode_beam = _mbr_decode_beam
 
     # translator.py:155-196
     @classmethod

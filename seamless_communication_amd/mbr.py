@@ -148,3 +148,47 @@ def mbr_decode(self, input, task_str: str, tgt_lang: str, src_lang: Optional[str
         out.append(MBRHypothesis(text=h.text, token_ids=list(h.token_ids), expected_utility=float(r.expected[r.index]), score=h.score,
                                  index=r.index, candidates=hyps))
     return out
+
+
+def posterior_weights(step_scores: Sequence[Sequence[float]]) -> List[float]:
+    """The ``"posterior"`` weights of ``Translator.mbr_decode_beam`` for one item: ``exp(sum(step_scores) - max)`` per
+    hypothesis, in double - each hypothesis weighs in with its (un-normalised) model probability relative to the best one."""
+    totals = [math.fsum(float(x) for x in s) for s in step_scores]
+    finite = [t for t in totals if math.isfinite(t)]
+    top = max(finite) if finite else 0.0
+    return [math.exp(t - top) if math.isfinite(t) else 0.0 for t in totals]
+
+
+def mbr_decode_beam(self, input, task_str: str, tgt_lang: str, src_lang: Optional[str] = None, *, beam_size: int = 8,
+                    weights: str = "uniform", text_generation_opts: Any = None, max_order: int = 4, beta: float = 1.0,
+                    sample_rate: int = 16000, forced_prefix: Any = None) -> List[MBRHypothesis]:
+    """``Translator.mbr_decode_beam``: the candidates are the beam search's n-best list (``Translator.predict_nbest`` with
+    ``beam_size`` and ``nbest = beam_size``; same tasks: S2TT, ASR, T2TT) instead of samples, then :func:`select` on their
+    content tokens.  ``weights``: ``"uniform"``, or ``"posterior"`` - every pseudo-reference counts with
+    ``exp(sum(step_scores) - max)`` (:func:`posterior_weights`).  ``text_generation_opts`` supplies the length limits,
+    penalties and step processors; its ``beam_size`` is replaced.  Not part of the reference's ``Translator``; neither the
+    utility nor the posterior weighting has been evaluated on real translations."""
+    _check_options(max_order, beta)
+    if weights not in ("uniform", "posterior"):
+        raise ValueError(f"`weights` must be 'uniform' or 'posterior', but is {weights!r} instead.")
+    if isinstance(beam_size, bool) or int(beam_size) != beam_size or not 1 <= beam_size <= 8:
+        raise ValueError(f"`beam_size` must be an integer in 1..8, but is {beam_size!r} instead.")
+    import dataclasses
+
+    from .inference.generator import SequenceGeneratorOptions
+
+    base = text_generation_opts or SequenceGeneratorOptions(beam_size=5, soft_max_seq_len=(1, 200))
+    opts = dataclasses.replace(base, beam_size=int(beam_size))
+    nbest = self.predict_nbest(input, task_str, tgt_lang, src_lang, nbest=int(beam_size), text_generation_opts=opts,
+                               sample_rate=sample_rate, forced_prefix=forced_prefix)
+    prefix_len = len(self.text_tokenizer.target_prefix(tgt_lang))
+    eos = self.text_tokenizer.vocab_info.eos_idx
+    w = [posterior_weights([h.step_scores for h in hyps]) for hyps in nbest] if weights == "posterior" else None
+    picked = select([[content_tokens(h.token_ids, prefix_len, eos) for h in hyps] for hyps in nbest], weights=w, max_order=max_order,
+                    beta=beta)
+    out = []
+    for hyps, r in zip(nbest, picked):
+        h = hyps[r.index]
+        out.append(MBRHypothesis(text=h.text, token_ids=list(h.token_ids), expected_utility=float(r.expected[r.index]), score=h.score,
+                                 index=r.index, candidates=hyps))
+    return out

@@ -422,6 +422,56 @@ class HipS2STModel(_Handle):
                                         _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden)), "sc_generate_text")
         return ids, lens, scores, hidden
 
+    def generate_text_nbest(self, enc: torch.Tensor, enc_lens: Sequence[int], prefix, beam_size: int = 5, nbest: Optional[int] = None,
+                            soft_max_seq_len=(1, 200), hard_max_seq_len: int = 1024, min_seq_len: int = 1,
+                            unk_penalty: float = 0.0, use_graph: bool = True, len_penalty: float = 1.0,
+                            normalize_scores: bool = True, no_repeat_ngram_size: int = 0, source_len: int = 0,
+                            banned_seqs=None, boost_seqs=None, boost: float = 0.0, want_step_scores: bool = True):
+        """Beam n-best lists with per-token scores (sc_generate_text_nbest): every finished hypothesis of the beam search,
+        best first.  -> (ids (n, nbest, max_len) int32, lens (n, nbest), scores (n, nbest), counts (n,), step_scores
+        (n, nbest, max_len) float32 or None).  ``nbest``: 1..beam_size (None: beam_size); ``prefix``: any form generate_text
+        takes (one prompt, an (n, prefix_len) array, a list of per-row prompts, ``(rows, lens)``).  Hypothesis 0 is
+        generate_text's result on the same arguments, bit for bit; ``step_scores[u, h, t]`` is the score position t added
+        (prompt positions included, 0 at position 0 and behind the length), so their sum is the un-normalised score.  Rows
+        behind ``counts[u]`` are pad / 0.  The other arguments are generate_text's."""
+        assert enc.is_cuda and enc.is_contiguous()
+        n, s_enc, M = enc.shape
+        beam_size = int(beam_size)
+        nbest = beam_size if nbest is None else int(nbest)
+        if not 1 <= beam_size <= 8:
+            raise ValueError(f"`beam_size` must lie in 1..8, but is {beam_size} instead.")
+        if not 1 <= nbest <= beam_size:
+            raise ValueError(f"`nbest` must lie in 1..beam_size ({beam_size}), but is {nbest} instead.")
+        boosted = boost_seqs is not None and len(boost_seqs) > 0 and float(boost) != 0.0
+        has_banned = banned_seqs is not None and len(banned_seqs) > 0
+        ragged = _ragged_prompts(prefix, n, True)
+        if ragged is None:
+            pre = _i32(prefix)
+            if pre.ndim == 1:
+                pre = np.ascontiguousarray(np.broadcast_to(pre, (n, len(pre))))
+            if pre.ndim != 2 or pre.shape[0] != n or pre.shape[1] < 1:
+                raise ValueError(f"a per-row prefix must be (n={n}, prefix_len), got {pre.shape}")
+            ragged = pre, np.full(n, pre.shape[1], dtype=np.int32)
+        rows, plens = ragged
+        o = self._gen_opts(beam_size, soft_max_seq_len, hard_max_seq_len, min_seq_len, unk_penalty, use_graph, len_penalty,
+                           normalize_scores, no_repeat_ngram_size, source_len)
+        max_len = max(1, self.lib.sc_text_max_len(self.handle, C.byref(o), s_enc))
+        ids = np.zeros((n, nbest, max_len), dtype=np.int32)
+        lens = np.zeros((n, nbest), dtype=np.int32)
+        scores = np.zeros((n, nbest), dtype=np.float32)
+        counts = np.zeros(n, dtype=np.int32)
+        step = np.zeros((n, nbest, max_len), dtype=np.float32) if want_step_scores else None
+        el = _i32(enc_lens)
+        b_tok, b_off = _lib.banned_csr(banned_seqs) if has_banned else (None, None)
+        p_tok, p_off = _lib.banned_csr(boost_seqs) if boosted else (None, None)
+        self._after_torch()
+        check(self.lib.sc_generate_text_nbest(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(rows), rows.shape[1],
+                                              _ptr(plens), nbest, _ptr(ids), _ptr(lens), _ptr(scores), _ptr(counts), _ptr(step),
+                                              _ptr(b_tok), _ptr(b_off), 0 if b_off is None else len(b_off) - 1, _ptr(p_tok),
+                                              _ptr(p_off), 0 if p_off is None else len(p_off) - 1, float(boost) if boosted else 0.0),
+              "sc_generate_text_nbest")
+        return ids, lens, scores, counts, step
+
     def generate_text_sampled(self, enc: torch.Tensor, enc_lens: Sequence[int], prefix: Sequence[int], num_gens: int = 1,
                               top_k: int = 0, top_p: float = 1.0, temperature: float = 1.0, seed: int = 0, streams=None,
                               soft_max_seq_len=(1, 200), hard_max_seq_len: int = 1024, min_seq_len: int = 1,
