@@ -113,6 +113,12 @@ int sc_op_conv_transpose1d(const float* d_x, const void* d_v_f16, const void* d_
  * fp16 planes, the format the next product consumes) may be requested.  Same bits as sc_op_linear(split=1). */
 int sc_op_linear_presplit(const float* d_x, const void* d_w_f16, const float* d_bias, const float* d_res, float* d_y,
                           void* d_yh_f16, void* d_yl_f16, int32_t M, int32_t N, int32_t K, int32_t act, float alpha);
+/* y [M][N / 2] = GLU(x.W^T + b) = value * sigmoid(gate), W [N][K] with the N / 2 value rows first and the gate rows behind them
+ * (the first pointwise convolution of the Conformer convolution module).  fused = 1: the rows of W interleaved on the device and
+ * the GLU applied in the pre-split product's epilogue (launch_gemm_presplit_glu); fused = 0: sc_op_linear_presplit's product to
+ * fp32 followed by the GLU kernel.  The two must be bit-identical (tests/test_encoder_glu_epilogue_gpu.py).  N % 4 == 0. */
+int sc_op_linear_presplit_glu(const float* d_x, const void* d_w_f16, const float* d_bias, float* d_y, int32_t M, int32_t N, int32_t K,
+                              int32_t fused);
 /* d_idx[m] = arg-max over n of (x.W^T + b)[m][n] with the arg-max FUSED into the pre-split product's epilogue (no logits in
  * memory; the unit projection of the NAR T2U, reference models/unity/model.py:438-441 + inference/generator.py:346): equal to
  * the arg-max of sc_op_linear_presplit's d_y, lowest index among equal values. */
@@ -396,6 +402,12 @@ int32_t sc_op_pretssel_last_launches(sc_pretssel* p);
 /* launch calls of the handle's last sc_t2u_nar / sc_t2u_nar_cond call behind the T2U encoder (decoder front end, duration predictor,
  * packed FFT decoder, projection; every product / convolution / row-pass call counts once); 0 when the length buckets ran */
 int32_t sc_op_t2u_last_launches(sc_model* m);
+/* The T2U encoder by itself (run_t2u_encoder, the first stage of sc_t2u_nar / sc_t2u_ar): d_dec_hidden and d_out are
+ * [n][s_text][model_dim] fp32 on the device, h_text_lens [n] on the host.  *out_rows (nullable) = rows the call computed: the sum
+ * of the lengths on the packed pass (which returns exact zeros at and behind an item's length), n * s_text on the padded one
+ * (SC_T2U_ENC_PACKED=0, read per call; tests/test_t2u_encoder_packed_gpu.py). */
+int sc_op_t2u_encoder(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text, const int32_t* h_text_lens, float* d_out,
+                      int64_t* out_rows);
 
 /* Kernels of the PRETSSEL waveform generator's SEANet half by themselves (k_seanet.hip; tests/test_pretssel_wave_gpu.py).  Packed
  * items: the rows [time][C] of item i follow those of item i - 1, h_lens [n] on the host.

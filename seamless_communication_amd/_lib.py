@@ -221,6 +221,7 @@ SIGNATURES = {
     "sc_t2u_nar": (C.c_int, [_P, _P, _i, _i, _P, _P, C.c_float, _P, _PI, _PI]),
     "sc_t2u_nar_cond": (C.c_int, [_P, _P, _i, _i, _P, _P, C.c_float, _P, _P, _PI, _PI]),
     "sc_op_t2u_last_launches": (C.c_int32, [_P]),
+    "sc_op_t2u_encoder": (C.c_int, [_P, _P, _i, _i, _P, _P, _P]),
     "sc_get_units": (C.c_int, [_P, _P]),
     "sc_get_durations": (C.c_int, [_P, _P, _P, _P]),
     "sc_vocoder_hop": (_i, [_P]),
@@ -318,6 +319,7 @@ SIGNATURES = {
     "sc_op_pack_conv_weight": (C.c_int, [_P, _P, _i, _i, _i]),
     "sc_op_conv_transpose1d": (C.c_int, [_P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _i, _i, _i]),
     "sc_op_linear_presplit": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i, C.c_float]),
+    "sc_op_linear_presplit_glu": (C.c_int, [_P, _P, _P, _P, _i, _i, _i, _i]),
     "sc_op_linear_presplit_argmax": (C.c_int, [_P, _P, _P, _P, _i, _i, _i]),
     "sc_op_linear_presplit_score": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i]),
     "sc_op_linear_presplit_score_grouped": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i]),

@@ -582,6 +582,22 @@ int sc_t2u_nar_cond(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s
 
 int32_t sc_op_t2u_last_launches(sc_model* m) { return m ? m->m.last_t2u_launches : -1; }
 
+int sc_op_t2u_encoder(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text, const int32_t* h_text_lens, float* d_out,
+                      int64_t* out_rows) {
+    SC_API_BEGIN
+    SC_CHECK(m && d_dec_hidden && h_text_lens && d_out, "sc_op_t2u_encoder: null argument");
+    SC_CHECK(m->m.cfg.has_t2u, "sc_op_t2u_encoder: the model was loaded without a T2U sub-model");
+    SC_CHECK(n > 0 && s_text > 0, "sc_op_t2u_encoder: empty batch");
+    SC_HIP(hipSetDevice(m->m.device));
+    prof::set_tag("t2u");
+    Buf<int> d_tlens(m->m.pp(), n);
+    SC_HIP(hipMemcpyAsync(d_tlens.get(), h_text_lens, (size_t)n * 4, hipMemcpyHostToDevice, m->m.stream));
+    run_t2u_encoder(m->m, d_dec_hidden, n, s_text, d_tlens, d_out, h_text_lens);
+    SC_HIP(hipStreamSynchronize(m->m.stream));
+    if (out_rows) *out_rows = m->m.last_t2u_enc_rows;
+    SC_API_END
+}
+
 int sc_get_units(sc_model* m, int32_t* h_units) {
     SC_API_BEGIN
     SC_CHECK(m && h_units, "sc_get_units: null argument");
@@ -1432,6 +1448,44 @@ int sc_op_linear_presplit(const float* d_x, const void* d_w_f16, const float* d_
     }
     (void)hipFree(hi);
     (void)hipFree(lo);
+    SC_API_END
+}
+
+int sc_op_linear_presplit_glu(const float* d_x, const void* d_w_f16, const float* d_bias, float* d_y, int32_t M, int32_t N, int32_t K,
+                              int32_t fused) {
+    SC_API_BEGIN
+    SC_CHECK(d_x && d_w_f16 && d_y && M > 0 && N > 0 && N % 2 == 0 && K > 0, "sc_op_linear_presplit_glu: bad argument");
+    OpScratch scratch;
+    __half* hi = scratch.get<__half>((size_t)M * K);
+    __half* lo = scratch.get<__half>((size_t)M * K);
+    launch_split_f32(d_x, hi, lo, (int64_t)M * K, g_op_stream);
+    GemmPsArgs a;
+    a.Ah = hi;
+    a.Al = lo;
+    a.lda = K;
+    a.ldw = K;
+    a.M = M;
+    a.N = N;
+    a.K = K;
+    if (fused) {
+        __half* wg = scratch.get<__half>((size_t)N * K);
+        float* bg = d_bias ? scratch.get<float>((size_t)N) : nullptr;
+        launch_glu_interleave_rows(static_cast<const __half*>(d_w_f16), K, d_bias, N / 2, K, wg, K, bg, g_op_stream);
+        a.W = wg;
+        a.bias = bg;
+        a.C = d_y;
+        a.ldc = N / 2;
+        launch_gemm_presplit_glu(a, g_op_stream);
+    } else {
+        float* wide = scratch.get<float>((size_t)M * N);
+        a.W = static_cast<const __half*>(d_w_f16);
+        a.bias = d_bias;
+        a.C = wide;
+        a.ldc = N;
+        launch_gemm_presplit(a, g_op_stream);
+        launch_glu(wide, N, d_y, N / 2, M, N / 2, g_op_stream);
+    }
+    SC_HIP(hipStreamSynchronize(g_op_stream));
     SC_API_END
 }
 

@@ -52,6 +52,8 @@ const Knob knob_table[] = {
     // re-read per call
     {"SC_BEAM_COMPACT", 2, "0: beam search keeps finished utterances' slots"},
     {"SC_GREEDY_COMPACT", 2, "0: greedy generation keeps finished rows in their slots"}, {"SC_GREEDY_POLL", 2, "steps between looks at the finished flags"},
+    {"SC_T2U_ENC_PACKED", 2, "0: T2U encoder over the padded rows on the fp32-operand GEMM"},
+    {"SC_ENC_GLU_EPI", 2, "0: Conformer conv module writes both GLU halves and gates them in the depthwise kernel"},
 };
 constexpr int N_KNOBS = sizeof(knob_table) / sizeof(knob_table[0]);
 struct State {

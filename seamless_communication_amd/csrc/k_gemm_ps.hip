@@ -109,6 +109,39 @@ __device__ __forceinline__ void ps_epilogue(const GemmPsArgs& p, const float* ep
     }
 }
 
+// GLU epilogue (launch_gemm_presplit_glu): the weight's rows were interleaved at load (column 2j = value j, column 2j + 1 =
+// gate j), so a lane's 16-byte piece holds (a_j, g_j, a_j+1, g_j+1) after the bias; it stores a * sigmoid(g) of both pairs -
+// glu_kernel's expression - to an fp32 C of N / 2 columns.  Same lane -> (row, column) walk as ps_epilogue; N % 4 == 0.
+template <int WM, int WN, int EP_LD>
+__device__ __forceinline__ void ps_epilogue_glu(const GemmPsArgs& p, const float* ep, int m0w, int n0w, int lane) {
+    constexpr int LPR = WN / 4;
+    constexpr int RPG = 16 / LPR;
+    constexpr int RPI = 4 * RPG;
+    const int l5 = lane & 31;
+    const bool g1 = (l5 >= 4 && l5 < 12) || (l5 >= 16 && l5 < 20) || l5 >= 28;
+    const int rank = g1 ? (l5 < 12 ? l5 - 4 : l5 < 20 ? l5 - 8 : l5 - 16) : (l5 < 4 ? l5 : l5 < 16 ? l5 - 8 : l5 - 12);
+    const int grp = (lane >> 5) * 2 + (g1 ? 1 : 0);
+    const int row_in = grp * RPG + rank / LPR;
+    const int c0 = (rank % LPR) * 4;
+    const int col = n0w + c0;
+    f32x4_t b4 = {0.f, 0.f, 0.f, 0.f};
+    if (p.bias && col < p.N) b4 = *reinterpret_cast<const f32x4_t*>(p.bias + col);
+#pragma unroll
+    for (int it = 0; it < WM / RPI; ++it) {
+        const int row = it * RPI + row_in;
+        const int64_t m = m0w + row;
+        const f32x4_t acc = *reinterpret_cast<const f32x4_t*>(ep + row * EP_LD + c0);
+        if (m >= p.M || col >= p.N) continue;
+        f32x4_t v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = act<ACT_NONE>(acc[e] + b4[e]) * p.alpha;  // = what ps_epilogue stores to C
+        float2 o;
+        o.x = v[0] / (1.f + expf(-v[1]));
+        o.y = v[2] / (1.f + expf(-v[3]));
+        *reinterpret_cast<float2*>(p.C + m * p.ldc + (col >> 1)) = o;
+    }
+}
+
 // WGM x WGN waves per workgroup.  2 x 2 waves on a 128 x 128 (64 x 64) tile is the round-1 shape; 4 x 2 waves on a
 // 256 x 256 tile (wave tile 64 x 128) halves the barriers per MFMA (32 matrix instructions per slab and wave instead of
 // 16) and takes the fragment reads from 0.75 to 0.5 ds_read_b128 per MFMA at the same 6 DMAs per wave and slab; its
@@ -160,7 +193,7 @@ __device__ __forceinline__ void ps_epilogue(const GemmPsArgs& p, const float* ep
 template <int BM, int BN, int WGM, int WGN, bool SPLIT, bool CONV, bool AMAX>
 __global__ __launch_bounds__(WGM* WGN * 64) void gemm_ps_kernel(GemmPsArgs p, int tiles_n, int tiles_total, int tiles_per_xcd,
                                                                  uint32_t a_bytes, uint32_t w_bytes) {
-    constexpr bool SCORE = false, CAND = false;
+    constexpr bool SCORE = false, CAND = false, GLU = false;
     const GemmScoreArgs sc{};  // never read: every use sits behind `if constexpr (SCORE)`
     const GemmCandArgs cd{};   // nor this one (`if constexpr (CAND)`)
 #include "k_gemm_ps_body.h"
@@ -170,7 +203,7 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm_ps_kernel(GemmPsArgs p, in
 template <int BM, int BN, int WGM, int WGN>
 __global__ __launch_bounds__(WGM* WGN * 64) void gemm_score_kernel(GemmPsArgs p, int tiles_n, int tiles_total, int tiles_per_xcd,
                                                                     uint32_t a_bytes, uint32_t w_bytes, GemmScoreArgs sc) {
-    constexpr bool SPLIT = true, CONV = false, AMAX = false, SCORE = true, CAND = false;
+    constexpr bool SPLIT = true, CONV = false, AMAX = false, SCORE = true, CAND = false, GLU = false;
     const GemmCandArgs cd{};  // never read: every use sits behind `if constexpr (CAND)`
 #include "k_gemm_ps_body.h"
 }
@@ -180,25 +213,38 @@ __global__ __launch_bounds__(WGM* WGN * 64) void gemm_score_kernel(GemmPsArgs p,
 template <int BM, int BN, int WGM, int WGN>
 __global__ __launch_bounds__(WGM* WGN * 64) void gemm_cand_kernel(GemmPsArgs p, int tiles_n, int tiles_total, int tiles_per_xcd,
                                                                    uint32_t a_bytes, uint32_t w_bytes, GemmScoreArgs sc, GemmCandArgs cd) {
-    constexpr bool SPLIT = true, CONV = false, AMAX = false, SCORE = true, CAND = true;
+    constexpr bool SPLIT = true, CONV = false, AMAX = false, SCORE = true, CAND = true, GLU = false;
+#include "k_gemm_ps_body.h"
+}
+
+// the split plain product with the GLU epilogue (launch_gemm_presplit_glu: the first pointwise convolution of the Conformer
+// convolution module); a kernel of its own like the two above: the K loop is the shared body, the others keep their code
+template <int BM, int BN, int WGM, int WGN>
+__global__ __launch_bounds__(WGM* WGN * 64) void gemm_glu_kernel(GemmPsArgs p, int tiles_n, int tiles_total, int tiles_per_xcd,
+                                                                  uint32_t a_bytes, uint32_t w_bytes) {
+    constexpr bool SPLIT = true, CONV = false, AMAX = false, SCORE = false, CAND = false, GLU = true;
+    const GemmScoreArgs sc{};  // never read: every use sits behind `if constexpr (SCORE)`
+    const GemmCandArgs cd{};   // nor this one (`if constexpr (CAND)`)
 #include "k_gemm_ps_body.h"
 }
 
 template <int BM, int BN, int WGM, int WGN>
-void launch_ps_cfg(const GemmPsArgs& a, hipStream_t s, const GemmScoreArgs* score = nullptr, const GemmCandArgs* cand = nullptr) {
+void launch_ps_cfg(const GemmPsArgs& a, hipStream_t s, const GemmScoreArgs* score = nullptr, const GemmCandArgs* cand = nullptr,
+                   bool glu = false) {
     const int tiles_m = cdiv(a.M, BM), tiles_n = cdiv(a.N, BN);
     const int tiles_total = tiles_m * tiles_n;
     const int tiles_per_xcd = cdiv(tiles_total, 8);
     char name[64];
     snprintf(name, sizeof(name), "gemm_%dx%d_presplit", BM, BN);
     prof::Scope scope(name, 2.0 * a.M * (double)a.N * a.K,
-                      4.0 * a.M * (double)a.K + 2.0 * a.N * (double)a.K + (score ? 4.0 * a.M * (SCORE_REC_FLOATS * (double)score->ld + (cand ? cand->n_cand : 0)) : a.amax ? 8.0 * a.M * (double)a.amax_ld : 4.0 * a.M * (double)a.N * (a.res ? 2.0 : 1.0)), s);
+                      4.0 * a.M * (double)a.K + 2.0 * a.N * (double)a.K + (score ? 4.0 * a.M * (SCORE_REC_FLOATS * (double)score->ld + (cand ? cand->n_cand : 0)) : a.amax ? 8.0 * a.M * (double)a.amax_ld : glu ? 2.0 * a.M * (double)a.N : 4.0 * a.M * (double)a.N * (a.res ? 2.0 : 1.0)), s);
     const dim3 grid(tiles_per_xcd * 8), block(WGM * WGN * 64);
     const uint32_t ab = (uint32_t)((int64_t)a.M * a.lda * 2), wb = (uint32_t)((int64_t)a.N * a.ldw * 2);
     const auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb); };
     const bool conv = a.conv_taps > 0;
     if (score && cand) hipLaunchKernelGGL((gemm_cand_kernel<BM, BN, WGM, WGN>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb, *score, *cand);
     else if (score) hipLaunchKernelGGL((gemm_score_kernel<BM, BN, WGM, WGN>), grid, block, 0, s, a, tiles_n, tiles_total, tiles_per_xcd, ab, wb, *score);
+    else if (glu) launch(gemm_glu_kernel<BM, BN, WGM, WGN>);
     else if (a.amax) launch(gemm_ps_kernel<BM, BN, WGM, WGN, true, false, true>);  // split, plain product (launch_gemm_presplit)
     else if (a.split && conv) launch(gemm_ps_kernel<BM, BN, WGM, WGN, true, true, false>);
     else if (a.split) launch(gemm_ps_kernel<BM, BN, WGM, WGN, true, false, false>);
@@ -257,6 +303,27 @@ void launch_gemm_presplit(const GemmPsArgs& a, hipStream_t s) {
     if (tile == 256) launch_ps_cfg<256, 256, 4, 2>(a, s);
     else if (tile == 128) launch_ps_cfg<128, 128, 2, 2>(a, s);
     else launch_ps_cfg<64, 64, 2, 2>(a, s);
+    SC_LAUNCH_CHECK();
+}
+
+// C [M][N / 2] = GLU over the column pairs (2j, 2j + 1) of A.W^T + bias: W (and bias) with the value and the gate rows
+// interleaved (launch_glu_interleave_rows).  Tile choice and K loop are launch_gemm_presplit's for (M, N): every value and
+// every gate is accumulated exactly as that call would, and gated with launch_glu's expression.
+void launch_gemm_presplit_glu(const GemmPsArgs& a, hipStream_t s) {
+    SC_CHECK(a.Ah && a.Al && a.W && a.C && a.split, "presplit glu gemm: null operand");
+    SC_CHECK(!a.Ch && !a.Cl && !a.res && !a.row_valid && !a.amax && a.conv_taps == 0 && a.act == ACT_NONE && a.alpha == 1.0f,
+             "presplit glu gemm: a plain product (no planes / residual / activation / scale)");
+    SC_CHECK(a.M > 0 && a.N > 0 && a.N % 4 == 0 && a.K > 0 && a.K % PBK == 0, "presplit glu gemm: M=%d N=%d K=%d (N %% 4, K %% 32)", a.M, a.N, a.K);
+    SC_CHECK(a.lda % 8 == 0 && a.ldw % 8 == 0 && a.ldw >= a.K && a.lda >= a.K && a.ldc % 2 == 0 && a.ldc >= a.N / 2,
+             "presplit glu gemm: lda=%lld ldw=%lld ldc=%lld", (long long)a.lda, (long long)a.ldw, (long long)a.ldc);
+    SC_CHECK(((reinterpret_cast<uintptr_t>(a.Ah) | reinterpret_cast<uintptr_t>(a.Al) | reinterpret_cast<uintptr_t>(a.W) |
+               reinterpret_cast<uintptr_t>(a.C) | reinterpret_cast<uintptr_t>(a.bias)) & 15) == 0,
+             "presplit glu gemm: operands must be 16-byte aligned");
+    SC_CHECK((int64_t)a.M * a.lda * 2 < (1ll << 31) && (int64_t)a.N * a.ldw * 2 < (1ll << 31), "presplit glu gemm: operand larger than 2 GB");
+    const int tile = ps_tile(a.M, a.N);
+    if (tile == 256) launch_ps_cfg<256, 256, 4, 2>(a, s, nullptr, nullptr, true);
+    else if (tile == 128) launch_ps_cfg<128, 128, 2, 2>(a, s, nullptr, nullptr, true);
+    else launch_ps_cfg<64, 64, 2, 2>(a, s, nullptr, nullptr, true);
     SC_LAUNCH_CHECK();
 }
 

@@ -1,6 +1,6 @@
 // Body of the pre-split product kernels of k_gemm_ps.hip (the schedule is described there).  NOT a stand-alone header: it is
 // included inside the braces of gemm_ps_kernel and of gemm_score_kernel, which supply
-//   template / constexpr parameters  BM, BN, WGM, WGN, SPLIT, CONV, AMAX, SCORE, CAND
+//   template / constexpr parameters  BM, BN, WGM, WGN, SPLIT, CONV, AMAX, SCORE, CAND, GLU
 //   arguments                        GemmPsArgs p, tiles_n, tiles_total, tiles_per_xcd, a_bytes, w_bytes, GemmScoreArgs sc,
 //                                    GemmCandArgs cd
 // so that the kernels share every instruction of the K loop while gemm_ps_kernel keeps its own argument list.
@@ -502,6 +502,10 @@
                     ++cd_j;
                 }
             }
+            return;
+        }
+        if constexpr (GLU) {
+            ps_epilogue_glu<WM, EPN, EP_LD>(p, ep, m0w, n0w, lane);
             return;
         }
         if (p.act == ACT_NONE) ps_epilogue<WM, EPN, EP_LD, ACT_NONE>(p, ep, m0w, n0w, lane);

@@ -281,6 +281,22 @@ void launch_gather_rows(const float* src, int64_t lds_, const int* row_idx, floa
     SC_LAUNCH_CHECK();
 }
 
+// GLU weight interleave (launch_gemm_presplit_glu): one workgroup per destination row
+__global__ __launch_bounds__(256) void glu_interleave_rows_kernel(const __half* __restrict__ src, int64_t ld_src, const float* __restrict__ bias,
+                                                                  int C, int K, __half* __restrict__ dst, int64_t ld_dst,
+                                                                  float* __restrict__ bias_dst) {
+    const int r = blockIdx.x;  // destination row < 2 * C
+    const int sr = (r >> 1) + (r & 1) * C;
+    for (int k = threadIdx.x; k < K; k += 256) dst[(int64_t)r * ld_dst + k] = src[(int64_t)sr * ld_src + k];
+    if (bias && threadIdx.x == 0) bias_dst[r] = bias[sr];
+}
+void launch_glu_interleave_rows(const __half* src, int64_t ld_src, const float* bias, int C, int K, __half* dst, int64_t ld_dst,
+                                float* bias_dst, hipStream_t s) {
+    SC_CHECK(src && dst && C > 0 && K > 0 && ld_src >= K && ld_dst >= K && (!bias || bias_dst), "glu_interleave_rows: bad argument");
+    hipLaunchKernelGGL(glu_interleave_rows_kernel, dim3(2 * C), dim3(256), 0, s, src, ld_src, bias, C, K, dst, ld_dst, bias_dst);
+    SC_LAUNCH_CHECK();
+}
+
 // The same gather with a per-item vector added on the way: dst[r] = src[row_idx[r]] + add[r / rows_per_item] (the expressive
 // T2U: encoder_output + prosody_proj(cond), models/unity/model.py:391-392, applied where the encoder rows become characters;
 // the padded text rows never reach a character).  row_idx < 0: exact zeros, as above.

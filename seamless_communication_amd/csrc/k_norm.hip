@@ -375,8 +375,12 @@ void launch_relpos_table(int S, int M, float* out, hipStream_t s) {
 // of one item: the GLU'd window lives in registers and slides by TT rows per trip (the 30-row halo is read once per time
 // range, not once per tile), the TT x C convolution outputs go to LDS, and one wave per row normalises them there and
 // writes the planes.  Bit-identical to glu_dwconv_kernel + layernorm_kernel (same expressions, same summation order).
+// GATED: x is [rows][C] and already holds GLU(.) - the first pointwise product gated it in its epilogue
+// (launch_gemm_presplit_glu) - so a row costs one load per channel and no exponential; everything behind the window (taps,
+// causal left edge, item length, LayerNorm, activation, split) is the same code.  A separate instantiation: the un-gated
+// kernel keeps its instructions.
 // --------------------------------------------------------------------------------------------- //
-template <int K, int TT>
+template <int K, int TT, bool GATED>
 __global__ __launch_bounds__(1024) void glu_dwconv_ln_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta, int act,
                                                              __half* __restrict__ yh, __half* __restrict__ yl, int64_t ldh, int T, int C,
@@ -399,18 +403,23 @@ __global__ __launch_bounds__(1024) void glu_dwconv_ln_kernel(const float* __rest
         float v = 0.f;
         if (t >= 0 && t < len) {
             const float a = xn[(int64_t)t * ldx + c];
-            const float b = xn[(int64_t)t * ldx + C + c];
-            v = a / (1.f + expf(-b));
+            if constexpr (GATED) {
+                v = a;
+            } else {
+                const float b = xn[(int64_t)t * ldx + C + c];
+                v = a / (1.f + expf(-b));
+            }
         }
         g[i] = v;
     }
     float ra[TT], rb[TT];  // raw rows of the chunk about to be convolved (prefetched one chunk ahead)
+    (void)rb;              // GATED: no gate rows
 #pragma unroll
     for (int i = 0; i < TT; ++i) {
         const int t = t_begin + i;
         const bool ok = t < t_end && t < len;
         ra[i] = ok ? xn[(int64_t)t * ldx + c] : 0.f;
-        rb[i] = ok ? xn[(int64_t)t * ldx + C + c] : 0.f;
+        if constexpr (!GATED) rb[i] = ok ? xn[(int64_t)t * ldx + C + c] : 0.f;
     }
     const int nv = C >> 2;
     int buf = 0;
@@ -418,14 +427,15 @@ __global__ __launch_bounds__(1024) void glu_dwconv_ln_kernel(const float* __rest
 #pragma unroll
         for (int i = 0; i < TT; ++i) {
             const int t = tc + i;
-            g[K - 1 + i] = (t < t_end && t < len) ? ra[i] / (1.f + expf(-rb[i])) : 0.f;
+            if constexpr (GATED) g[K - 1 + i] = (t < t_end && t < len) ? ra[i] : 0.f;
+            else g[K - 1 + i] = (t < t_end && t < len) ? ra[i] / (1.f + expf(-rb[i])) : 0.f;
         }
 #pragma unroll
         for (int i = 0; i < TT; ++i) {  // next chunk's rows travel during the convolution and the LayerNorm phase
             const int t = tc + TT + i;
             const bool ok = t < t_end && t < len;
             ra[i] = ok ? xn[(int64_t)t * ldx + c] : 0.f;
-            rb[i] = ok ? xn[(int64_t)t * ldx + C + c] : 0.f;
+            if constexpr (!GATED) rb[i] = ok ? xn[(int64_t)t * ldx + C + c] : 0.f;
         }
 #pragma unroll
         for (int tt = 0; tt < TT; ++tt) {
@@ -492,7 +502,7 @@ __global__ __launch_bounds__(1024) void glu_dwconv_ln_kernel(const float* __rest
 bool glu_dwconv_ln_supported(int C, int ksize) { return ksize == 31 && C % 64 == 0 && C >= 64 && C <= 1024; }
 
 void launch_glu_dwconv_ln(const float* x, int64_t ldx, const float* w, const float* gamma, const float* beta, int act, __half* yh,
-                          __half* yl, int64_t ldh, int nb, int T, int C, int ksize, const int* lens, hipStream_t s) {
+                          __half* yl, int64_t ldh, int nb, int T, int C, int ksize, const int* lens, hipStream_t s, bool gated) {
     SC_CHECK(glu_dwconv_ln_supported(C, ksize) && ldh % 4 == 0, "glu_dwconv_ln: C=%d k=%d ldh=%lld unsupported", C, ksize, (long long)ldh);
     if (nb <= 0 || T <= 0) return;
     constexpr int TT = 8;
@@ -501,9 +511,13 @@ void launch_glu_dwconv_ln(const float* x, int64_t ldx, const float* w, const flo
     const int range = cdiv(cdiv(T, ranges), TT) * TT;
     ranges = cdiv(T, range);
     const double rows = (double)nb * T;
-    prof::Scope scope("glu_dwconv_ln", 2.0 * rows * C * ksize, rows * C * (8.0 + 4.0), s);
-    hipLaunchKernelGGL((glu_dwconv_ln_kernel<31, TT>), dim3(ranges, nb), dim3(C), 0, s, x, ldx, w, gamma, beta, act, yh, yl, ldh, T, C, lens,
-                       range);
+    prof::Scope scope("glu_dwconv_ln", 2.0 * rows * C * ksize, rows * C * ((gated ? 4.0 : 8.0) + 4.0), s);
+    if (gated)
+        hipLaunchKernelGGL((glu_dwconv_ln_kernel<31, TT, true>), dim3(ranges, nb), dim3(C), 0, s, x, ldx, w, gamma, beta, act, yh, yl, ldh, T, C,
+                           lens, range);
+    else
+        hipLaunchKernelGGL((glu_dwconv_ln_kernel<31, TT, false>), dim3(ranges, nb), dim3(C), 0, s, x, ldx, w, gamma, beta, act, yh, yl, ldh, T, C,
+                           lens, range);
     SC_LAUNCH_CHECK();
 }
 

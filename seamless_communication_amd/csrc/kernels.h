@@ -182,6 +182,16 @@ struct GemmPsArgs {
     int amax_ld = 0;
 };
 void launch_gemm_presplit(const GemmPsArgs& a, hipStream_t s);
+// The split plain product with GLU in its epilogue: W [N][K] (and bias [N]) hold the value and the gate rows of a [2C][K]
+// weight INTERLEAVED (row 2j = value j, row 2j + 1 = gate j: launch_glu_interleave_rows), C [M][N / 2] fp32 receives
+// value * sigmoid(gate).  Bit-identical to launch_gemm_presplit on the original weight followed by launch_glu: every element is
+// accumulated in the same order (a column's place in the tile does not enter its arithmetic) and gated by the same expression.
+// No planes / residual / activation / alpha; N % 4 == 0.
+void launch_gemm_presplit_glu(const GemmPsArgs& a, hipStream_t s);
+// dst row 2j = src row j, dst row 2j + 1 = src row C + j for j < C; rows of K halfs (ld_src / ld_dst apart); the bias
+// (nullable, with its destination) likewise.  Done once per weight at load.
+void launch_glu_interleave_rows(const __half* src, int64_t ld_src, const float* bias, int C, int K, __half* dst, int64_t ld_dst,
+                                float* bias_dst, hipStream_t s);
 int gemm_presplit_tile(int M, int N);         // rows (= columns) of the tile launch_gemm_presplit chooses for this shape
 int gemm_presplit_amax_chunks(int M, int N);  // partial results per row the tile choice for this shape produces
 void launch_amax_finish(const float2* part, int ld, int rows, int* out_idx, hipStream_t s);
@@ -552,9 +562,10 @@ void launch_glu(const float* x, int64_t ldx, float* y, int64_t ldy, int rows, in
 
 // The same followed by LayerNorm over the channels + activation, written as split planes, in one pass (k = 31, C % 64 == 0,
 // C <= 1024): bit-identical to launch_glu_dwconv + launch_layernorm_split
+// gated: x is [rows][C] and already holds GLU(.) (launch_gemm_presplit_glu wrote it); the same bits from half the input bytes
 bool glu_dwconv_ln_supported(int C, int ksize);
 void launch_glu_dwconv_ln(const float* x, int64_t ldx, const float* w, const float* gamma, const float* beta, int act, __half* yh,
-                          __half* yl, int64_t ldh, int nb, int T, int C, int ksize, const int* lens, hipStream_t s);
+                          __half* yl, int64_t ldh, int nb, int T, int C, int ksize, const int* lens, hipStream_t s, bool gated = false);
 // Conformer conv middle: g = GLU(x) (masked by lens), y = causal depthwise conv_k(g)
 void launch_glu_dwconv(const float* x, int64_t ldx, const float* w, float* y, int64_t ldy, int nb, int T,
                        int C, int ksize, const int* lens, hipStream_t s, int left = -1, const float* bn_scale = nullptr,

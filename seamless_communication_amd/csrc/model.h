@@ -98,6 +98,7 @@ struct ConvT {
 struct ConformerLayer {
     LNorm ffn1_ln, attn_ln, conv_ln, conv_inner_ln, ffn2_ln, final_ln;
     Linear ffn1_in, ffn1_out, ffn2_in, ffn2_out, qkv, attn_out, pw1, pw2;
+    Linear pw1g;  // enc_variant 0: pw1 with its value and gate rows interleaved, for the GLU epilogue (launch_gemm_presplit_glu)
     const float* rel_k = nullptr;  // [npos][64] fp32 (enc_variant 0)
     const float* dw = nullptr;     // [C][k] fp32
     // enc_variant 1 (v1 w2v-BERT): Transformer-XL relative positions + BatchNorm folded to scale / shift
@@ -286,6 +287,8 @@ struct Model : ModelData {
     std::vector<int32_t> last_units, last_durations, last_char_ids, last_char_seq_lens;
     int last_n = 0, last_su = 0, last_sc = 0;
     int last_t2u_launches = 0;  // launch calls of the last sc_t2u_nar* call behind the T2U encoder (decoder front end + FFT decoder)
+    int64_t last_t2u_enc_rows = 0;      // rows the last run_t2u_encoder call computed: sum of the text lengths (packed) or n * s_text
+    std::vector<int32_t> t2u_enc_stage; // host side of the packed encoder's index tables, alive until the caller's synchronisation
     int64_t last_padded_unit_rows = 0;  // unit rows the NAR decoder really computed (length buckets), vs last_n * last_su
     int64_t last_vocoder_unit_rows = 0; // unit frames the vocoder really computed in the last sc_vocode* call
     int last_vocoder_packed_groups = 0; // groups of the packed pass in the last sc_vocode* call; 0: padded batch / length buckets
@@ -404,7 +407,9 @@ void run_vocoder_durations(Model& m, const int32_t* h_units, int n, int s_units,
 void run_t2u_ar(Model& m, const float* d_dec_hidden, int n, int s_text, const int32_t* h_text_lens, const sc_gen_opts& o,
                 const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores);
 // T2U encoder (pre-LN StandardTransformerEncoder over the text decoder output; shared by the NAR and the AR T2U)
-void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, const int* d_text_lens, float* d_out);
+// h_text_lens (nullable): the same lengths on the host; with them the encoder computes the live rows only (model_t2u.hip)
+void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, const int* d_text_lens, float* d_out,
+                     const int32_t* h_text_lens = nullptr);
 // sc_generate_text_nbest: where the ranked finished hypotheses of a beam search go (host memory; h_step nullable)
 struct BeamNbestOut {
     int nbest = 0;

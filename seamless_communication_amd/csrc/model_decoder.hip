@@ -890,7 +890,7 @@ void run_t2u_ar(Model& m, const float* d_dec_hidden, int n, int s_text, const in
     Buf<int> d_tlens(m.pp(), n);
     SC_HIP(hipMemcpyAsync(d_tlens.get(), h_text_lens, (size_t)n * 4, hipMemcpyHostToDevice, m.stream));
     Buf<float> enc(m.pp(), (size_t)n * s_text * M);
-    run_t2u_encoder(m, d_dec_hidden, n, s_text, d_tlens, enc);
+    run_t2u_encoder(m, d_dec_hidden, n, s_text, d_tlens, enc, h_text_lens);
     const DecStack W = t2u_ar_stack(m);
     // length rule of the unit generator: min(hard, int(a * S_text) + b), prompt included, capped by the position table
     sc_gen_opts uo = o;

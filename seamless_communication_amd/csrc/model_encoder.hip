@@ -215,6 +215,9 @@ void run_encode_speech(Model& m, const float* d_fbank, int n, int t_frames, cons
     static const bool fuse = knob::value("SC_ENC_FUSE", 1) != 0;
     const bool fuse_conv = fuse && glu_dwconv_ln_supported(M, c.depthwise_conv_kernel_size);
     const bool fuse_ln = fuse && M <= 1024;
+    // GLU of the convolution module inside the first pointwise product (SC_ENC_GLU_EPI=0, read per call: pw1 writes both halves
+    // and the depthwise kernel gates them; same bits)
+    const bool glu_epi = ps_ok && fuse_conv && knob::value("SC_SPLIT_MODE", 0) != 1 && knob::live("SC_ENC_GLU_EPI", 1) != 0;
     bool ffn1_planes_ready = false;  // the previous layer's closing launch already wrote LN_ffn1(x) as planes
     for (int li = 0; li < c.enc_layers; ++li) {
         const ConformerLayer& l = m.enc[li];
@@ -249,11 +252,30 @@ void run_encode_speech(Model& m, const float* d_fbank, int n, int t_frames, cons
             ps(as_hi, as_lo, l.attn_out, ACT_NONE, 1.f, x, x, nullptr, nullptr);
             // x += Conv(LN(x))
             ln_split(x, l.conv_ln, ACT_NONE);
-            ps(hs_hi, hs_lo, l.pw1, ACT_NONE, 1.f, nullptr, wide, nullptr, nullptr);
-            if (fuse_conv) {
+            if (glu_epi) {
+                // the product's epilogue gates: `wide` is [rows][M], the gate half never reaches HBM (131 MB written and read
+                // back per layer at 64 x 10 s), and the depthwise kernel loads one value per element instead of two
+                GemmPsArgs a;
+                a.Ah = hs_hi;
+                a.Al = hs_lo;
+                a.lda = M;
+                a.W = l.pw1g.w;
+                a.ldw = l.pw1g.ldw;
+                a.bias = l.pw1g.b;
+                a.C = wide;
+                a.ldc = M;
+                a.M = rows;
+                a.N = 2 * M;
+                a.K = M;
+                launch_gemm_presplit_glu(a, m.stream);
+                launch_glu_dwconv_ln(wide, M, l.dw, l.conv_inner_ln.g, l.conv_inner_ln.b, ACT_SILU, hs_hi, hs_lo, M, n, S, M,
+                                     c.depthwise_conv_kernel_size, d_lens, m.stream, /*gated=*/true);
+            } else if (fuse_conv) {
+                ps(hs_hi, hs_lo, l.pw1, ACT_NONE, 1.f, nullptr, wide, nullptr, nullptr);
                 launch_glu_dwconv_ln(wide, 2 * M, l.dw, l.conv_inner_ln.g, l.conv_inner_ln.b, ACT_SILU, hs_hi, hs_lo, M, n, S, M,
                                      c.depthwise_conv_kernel_size, d_lens, m.stream);
             } else {
+                ps(hs_hi, hs_lo, l.pw1, ACT_NONE, 1.f, nullptr, wide, nullptr, nullptr);
                 launch_glu_dwconv(wide, 2 * M, l.dw, att, M, n, S, M, c.depthwise_conv_kernel_size, d_lens, m.stream);
                 ln_split(att, l.conv_inner_ln, ACT_SILU);
             }

@@ -438,6 +438,15 @@ void load_model(Model& m, const sc_tensor_desc* t, size_t n) {
         } else {
             l.rel_k = L.f32(p + ".self_attn.sdpa.rel_k_embed.weight", {npos, 64});
             l.conv_inner_ln = L.ln(p + ".conv.layer_norm", M);
+            // the same weight once more with column 2j = value j, column 2j + 1 = gate j: the product's epilogue then holds both
+            // halves of a GLU pair in one lane (4 MB per layer at full size; pw1 itself stays for the other paths)
+            l.pw1g = l.pw1;
+            __half* wg = static_cast<__half*>(L.dalloc((size_t)2 * M * M * 2));
+            float* bg = l.pw1.b ? static_cast<float*>(L.dalloc((size_t)2 * M * 4)) : nullptr;
+            launch_glu_interleave_rows(l.pw1.w, l.pw1.ldw, l.pw1.b, M, M, wg, M, bg, m.stream);
+            l.pw1g.w = wg;
+            l.pw1g.ldw = M;
+            l.pw1g.b = bg;
         }
         l.pw2 = L.lin_pw(p + ".conv.pointwise_conv2", M, M);
         l.ffn2_ln = L.ln(p + ".ffn2_layer_norm", M);

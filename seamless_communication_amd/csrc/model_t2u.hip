@@ -186,10 +186,112 @@ void run_encode_text(Model& m, const int32_t* h_tokens, int n, int s_text, const
 
 // T2U encoder: pre-LN StandardTransformerEncoder + final LayerNorm over the text decoder output (UnitYT2UModel.encode /
 // UnitYNART2UModel.encode, models/unity/model.py:330-343, 404-412), key padding mask from d_text_lens.
-void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, const int* d_text_lens, float* x) {
+//
+// Packed pass (default, when the caller hands in the lengths on the host and the geometry fits the DMA GEMM): only the rows
+// below each item's length are computed - item b at packed rows [off[b], off[b] + len[b]), nothing in between - on split
+// planes, the way the Conformer and the packed NAR decoder run.  Exact per live row: LayerNorm and the products act on single
+// rows (launch_layernorm_split / launch_gemm_presplit give the bits of launch_layernorm / launch_gemm), the attention masks
+// the keys behind an item's length and walks its keys in 32-key tiles from the item's first row either way.  The rows at and
+// behind an item's length come back as exact zeros (the padded path leaves finite leftovers there; the NAR gather index never
+// points at them and the AR decoder masks them as keys).  SC_T2U_ENC_PACKED=0 (read per call): the padded rows on the
+// fp32-operand GEMM.  Batches of up to 64 padded rows stay there too: at that size linear() takes the split-K skinny kernel,
+// whose summation order the tiled products do not share.
+void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, const int* d_text_lens, float* x, const int32_t* h_text_lens) {
     const sc_config& c = m.cfg;
     const int M = c.model_dim, rows = n * s_text;
-    const int wideN = std::max(3 * M, c.t2u_ffn_dim);
+    const int Fd = c.t2u_ffn_dim;
+    int64_t R64 = 0;
+    bool lens_ok = h_text_lens != nullptr;
+    for (int b = 0; lens_ok && b < n; ++b) {
+        lens_ok = h_text_lens[b] >= 1 && h_text_lens[b] <= s_text;
+        R64 += h_text_lens[b];
+    }
+    const bool packed = lens_ok && knob::live("SC_T2U_ENC_PACKED", 1) != 0 && rows > 64 && M % 32 == 0 && Fd % 32 == 0 && M == c.num_heads * 64 &&
+                        m.t2u_ffn_act != ACT_GELU && R64 * std::max(M, Fd) * 2 < (1ll << 31) && !m.t2u_enc.empty() &&
+                        m.t2u_enc[0].qkv.in == M && m.t2u_enc[0].ffn_out.in == Fd;
+    m.last_t2u_enc_rows = packed ? R64 : rows;
+    if (packed) {
+        const int R = (int)R64;
+        // host staging kept on the handle: every caller synchronises the stream before it returns, this function does not
+        std::vector<int32_t>& st = m.t2u_enc_stage;
+        st.assign((size_t)n + R + rows, -1);
+        int32_t* off = st.data();         // [n]    first packed row of item b
+        int32_t* pidx = off + n;          // [R]    padded row behind packed row r
+        int32_t* uidx = pidx + R;         // [rows] packed row behind padded row, -1 (zeros) at and behind the item's length
+        double pairs = 0;
+        for (int b = 0, r = 0; b < n; ++b) {
+            off[b] = r;
+            for (int t = 0; t < h_text_lens[b]; ++t, ++r) {
+                pidx[r] = b * s_text + t;
+                uidx[b * s_text + t] = r;
+            }
+            pairs += (double)h_text_lens[b] * h_text_lens[b];
+        }
+        Buf<int> d_st(m.pp(), st.size());
+        SC_HIP(hipMemcpyAsync(d_st.get(), st.data(), st.size() * 4, hipMemcpyHostToDevice, m.stream));
+        const int* d_off = d_st.get();
+        const int* d_pidx = d_off + n;
+        const int* d_uidx = d_pidx + R;
+        Buf<float> xp(m.pp(), (size_t)R * M), wide(m.pp(), (size_t)R * 3 * M);
+        Buf<__half> planes(m.pp(), (size_t)R * (4 * M + 2 * Fd));
+        __half* hp_h = planes.get();
+        __half* hp_l = hp_h + (size_t)R * M;
+        __half* ap_h = hp_l + (size_t)R * M;
+        __half* ap_l = ap_h + (size_t)R * M;
+        __half* wp_h = ap_l + (size_t)R * M;
+        __half* wp_l = wp_h + (size_t)R * Fd;
+        auto ps = [&](const __half* ah, const __half* al, const Linear& L, int act, const float* res, float* C, __half* Ch, __half* Cl) {
+            GemmPsArgs a;
+            a.Ah = ah;
+            a.Al = al;
+            a.lda = L.in;
+            a.W = L.w;
+            a.ldw = L.ldw;
+            a.bias = L.b;
+            a.res = res;
+            a.ldr = L.out;
+            a.C = C;
+            a.ldc = L.out;
+            a.Ch = Ch;
+            a.Cl = Cl;
+            a.ldcs = L.out;
+            a.M = R;
+            a.N = L.out;
+            a.K = L.in;
+            a.act = act;
+            launch_gemm_presplit(a, m.stream);
+        };
+        launch_gather_rows(d_dec_hidden, M, d_pidx, xp, M, R, M, m.stream);
+        for (const EncoderLayer& l : m.t2u_enc) {
+            launch_layernorm_split(xp, M, l.attn_ln.g, l.attn_ln.b, hp_h, hp_l, M, R, M, ACT_NONE, nullptr, 1, m.stream);
+            ps(hp_h, hp_l, l.qkv, ACT_NONE, nullptr, wide, nullptr, nullptr);
+            AttnArgs a;
+            a.q = wide;
+            a.k = wide.get() + M;
+            a.v = wide.get() + 2 * M;
+            a.out_hi = ap_h;
+            a.out_lo = ap_l;
+            a.ldoh = M;
+            a.ldq = a.ldk = a.ldv = 3 * M;
+            a.ldo = M;
+            a.nb = n;
+            a.heads = c.num_heads;
+            a.Sq = s_text;
+            a.Skv = s_text;
+            a.kv_lens = d_text_lens;
+            a.row_off = d_off;
+            a.pairs = pairs;
+            launch_attention(a, m.stream);
+            ps(ap_h, ap_l, l.attn_out, ACT_NONE, xp, xp, nullptr, nullptr);
+            launch_layernorm_split(xp, M, l.ffn_ln.g, l.ffn_ln.b, hp_h, hp_l, M, R, M, ACT_NONE, nullptr, 1, m.stream);
+            ps(hp_h, hp_l, l.ffn_in, m.t2u_ffn_act, nullptr, nullptr, wp_h, wp_l);
+            ps(wp_h, wp_l, l.ffn_out, ACT_NONE, xp, xp, nullptr, nullptr);
+        }
+        layernorm(m, xp, m.t2u_enc_ln, xp, R);
+        launch_gather_rows(xp, M, d_uidx, x, M, rows, M, m.stream);
+        return;
+    }
+    const int wideN = std::max(3 * M, Fd);
     Buf<float> h(m.pp(), (size_t)rows * M), wide(m.pp(), (size_t)rows * wideN), att(m.pp(), (size_t)rows * M);
     SC_HIP(hipMemcpyAsync(x, d_dec_hidden, (size_t)rows * M * 4, hipMemcpyDeviceToDevice, m.stream));
     for (const EncoderLayer& l : m.t2u_enc) {
@@ -198,8 +300,8 @@ void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, con
         attention_self(m, wide, M, att, n, s_text, d_text_lens);
         linear(m, att, M, l.attn_out, x, M, x, M, rows, ACT_NONE, 1.f);
         layernorm(m, x, l.ffn_ln, h, rows);
-        linear(m, h, M, l.ffn_in, nullptr, 0, wide, c.t2u_ffn_dim, rows, m.t2u_ffn_act, 1.f);
-        linear(m, wide, c.t2u_ffn_dim, l.ffn_out, x, M, x, M, rows, ACT_NONE, 1.f);
+        linear(m, h, M, l.ffn_in, nullptr, 0, wide, Fd, rows, m.t2u_ffn_act, 1.f);
+        linear(m, wide, Fd, l.ffn_out, x, M, x, M, rows, ACT_NONE, 1.f);
     }
     layernorm(m, x, m.t2u_enc_ln, x, rows);
 }
@@ -225,7 +327,7 @@ void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const i
     // ---- T2U encoder (model.py:404-412) --------------------------------------------
     const int wideN = std::max(3 * M, std::max(c.t2u_ffn_dim, c.t2u_conv_inner_dim));
     Buf<float> x(m.pp(), (size_t)rows * M);
-    run_t2u_encoder(m, d_dec_hidden, n, s_text, d_tlens, x);
+    run_t2u_encoder(m, d_dec_hidden, n, s_text, d_tlens, x, h_text_lens);
 
     // ---- host: characters ---------------------------------------------------------
     std::vector<int32_t> char_lens;

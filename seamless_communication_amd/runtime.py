@@ -648,6 +648,18 @@ class HipS2STModel(_Handle):
         check(self.lib.sc_get_durations(self.handle, _ptr(dur), _ptr(cids), _ptr(clens)), "sc_get_durations")
         return units, ulens, dur, cids, clens
 
+    def t2u_encoder(self, dec_hidden: torch.Tensor, text_lens: Sequence[int]):
+        """The T2U encoder by itself (``sc_op_t2u_encoder``) -> (output (n, s_text, M) float32 on the device, rows computed)."""
+        assert dec_hidden.is_cuda and dec_hidden.is_contiguous() and dec_hidden.dtype == torch.float32
+        n, s_text, _ = dec_hidden.shape
+        tl = _i32(text_lens)
+        assert tl.shape == (n,)
+        out = torch.empty_like(dec_hidden)
+        rows = C.c_int64(0)
+        self._after_torch()
+        check(self.lib.sc_op_t2u_encoder(self.handle, _ptr(dec_hidden), n, s_text, _ptr(tl), _ptr(out), C.byref(rows)), "sc_op_t2u_encoder")
+        return out, int(rows.value)
+
     def t2u_ar(self, dec_hidden: torch.Tensor, text_lens: Sequence[int], prefix: Sequence[int], beam_size: int = 5,
                soft_max_seq_len=(25, 50), hard_max_seq_len: int = 1024, min_seq_len: int = 1, unk_penalty: float = 0.0,
                len_penalty: float = 1.0, normalize_scores: bool = True):
