@@ -197,6 +197,20 @@ int32_t sc_encoder_out_len(const sc_model* m, int32_t t_frames);
 int sc_encode_speech(sc_model* m, const float* d_fbank, int32_t n, int32_t t_frames, const int32_t* h_frame_lens,
                      float* d_enc_out, int32_t* h_out_lens);
 
+/* The same on a RAGGED batch in one packed pass: item i is encoded from its own h_frame_lens[i] / fbank_stride stacked rows (a
+ * trailing frame that does not fill a stride is dropped) and nothing else, so the batch costs the rows it has and an item's output
+ * has the same bits in any batch, in any order and alone.  Above 64 stacked and 64 output rows they are the bits of
+ * sc_encode_speech on the item alone; below, sc_encode_speech takes split-K products and the two agree to the encoder tolerance.
+ * d_fbank [n][t_frames][80]: t_frames is the buffer's row stride only (any value >= the longest item).  d_enc_out
+ * [n][s_enc_cap][model_dim] receives item i's h_out_lens[i] rows followed by zeros.  Runs on the handle's stream (forked handles
+ * too) and returns with the stream drained.
+ * SC_ERR_INVALID, sc_last_error naming the reason: a v1 model (enc_variant 1), dimensions the packed kernels do not take
+ * (model_dim a multiple of 64 up to 1024, enc_ffn_dim a multiple of 32, 31 depthwise taps), an item with fewer than fbank_stride
+ * frames, a frame length outside [0, t_frames].  SC_ERR_CAPACITY: s_enc_cap below the longest output length, or more packed rows
+ * than a product operand of 2^31 elements holds (encode the batch in groups).  Nothing is written in either case. */
+int sc_encode_speech_ragged(sc_model* m, const float* d_fbank, int32_t n, int32_t t_frames, const int32_t* h_frame_lens,
+                            float* d_enc_out /* [n][s_enc_cap][model_dim] */, int32_t s_enc_cap, int32_t* h_out_lens);
+
 /* a8-a11: greedy text generation with KV cache (BeamSearchSeq2SeqGenerator with
  * beam_size=1, echo_prompt=True; generator.py:147-156, :261-263).  h_out_ids
  * [n][max_len] (pad filled), h_out_lens[n] include prompt and EOS.  If

@@ -200,6 +200,12 @@ int sc_op_glu_dwconv(const float* d_x, const float* d_w, float* d_y, int32_t nb,
  * and the planes of LN_b(y). */
 int sc_op_glu_dwconv_ln(const float* d_x, const float* d_w, const float* d_gamma, const float* d_beta, int32_t act, void* d_yh_f16,
                         void* d_yl_f16, int32_t nb, int32_t T, int32_t C, int32_t k, const int32_t* d_lens, int32_t fused);
+/* fused = 2 above: the gated form of the fused kernel, x [nb*T][C] already holds GLU(.).
+ * sc_op_glu_dwconv_ln_packed: the same kernel on packed rows (the ragged speech encoder) - item i owns rows h_row_off[i] ..
+ * h_row_off[i] + h_lens[i] of x ([rows][2C], gated: [rows][C]) and of the planes; the work table is built here from the two host
+ * lists.  An item's rows must equal sc_op_glu_dwconv_ln on the item alone bit for bit; rows no item owns are not written. */
+int sc_op_glu_dwconv_ln_packed(const float* d_x, const float* d_w, const float* d_gamma, const float* d_beta, int32_t act, void* d_yh_f16,
+                               void* d_yl_f16, int32_t n, const int32_t* h_row_off, const int32_t* h_lens, int32_t C, int32_t k, int32_t gated);
 int sc_op_layernorm2(const float* d_x, const float* d_ga, const float* d_ba, const float* d_gb, const float* d_bb, float* d_y,
                      void* d_yh_f16, void* d_yl_f16, int32_t rows, int32_t C, int32_t fused);
 int sc_op_argmax(const float* d_logits, int32_t rows, int32_t V, int32_t* d_idx, float* d_lprob);

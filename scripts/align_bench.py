@@ -6,6 +6,8 @@ align      Transcriber.align_batch over `--batch` items of 10 s: one fbank call,
            equals align of item i alone), one sc_score_text_capture call (the batched teacher-forced decoder pass with the
            cross-attention rows kernel), host bookkeeping.
 padded     the same with padded_encoder=True: one encoder call on the padded batch.
+ragged     the same with ragged_encoder=True: one packed encoder pass over each item's own rows; item i equals this
+           call on item i alone.  The three lines come from this one process on the same inputs.
 greedy     Transcriber.transcribe on the same items one by one, at most `--tokens` generated tokens each: fbank, encoder and
            a greedy decode with one capture launch behind every step, per utterance.  The texts `align` times are the ids these
            calls generated (taken in the warm-up pass), so both routes time the same words.
@@ -64,20 +66,23 @@ def timed(fn):
     return out, time.perf_counter() - t0
 
 
-t_align, t_padded, t_greedy = [], [], []
+t_align, t_padded, t_ragged, t_greedy = [], [], [], []
 for it in range(a.warmup + a.reps):
     got, dt = timed(lambda: tr.align_batch(audios, texts, "eng"))
     _, dp = timed(lambda: tr.align_batch(audios, texts, "eng", padded_encoder=True))
+    _, dr = timed(lambda: tr.align_batch(audios, texts, "eng", ragged_encoder=True))
     ref, dg = timed(lambda: [tr.transcribe(w, "eng", max_gen_len=a.tokens) for w in audios])
     if it >= a.warmup:
         t_align.append(dt)
         t_padded.append(dp)
+        t_ragged.append(dr)
         t_greedy.append(dg)
 same_words = sum([x.text for x in g.tokens] == [x.text for x in r.tokens] for g, r in zip(got, ref))
 same_times = sum([x.time_s for x in g.tokens] == [x.time_s for x in r.tokens] for g, r in zip(got, ref))
-ta, tp, tg = np.asarray(t_align) * 1e3, np.asarray(t_padded) * 1e3, np.asarray(t_greedy) * 1e3
+ta, tp, tr_, tg = np.asarray(t_align) * 1e3, np.asarray(t_padded) * 1e3, np.asarray(t_ragged) * 1e3, np.asarray(t_greedy) * 1e3
 say(f"align_batch, {len(audios)} items, encoder item by item: {np.median(ta):9.2f} ms median (min {ta.min():.2f}, max {ta.max():.2f}, {a.reps} reps)")
 say(f"align_batch, padded_encoder=True:              {np.median(tp):9.2f} ms median (min {tp.min():.2f}, max {tp.max():.2f}, {a.reps} reps)")
+say(f"align_batch, ragged_encoder=True:              {np.median(tr_):9.2f} ms median (min {tr_.min():.2f}, max {tr_.max():.2f}, {a.reps} reps)")
 say(f"greedy transcribe, one by one:                 {np.median(tg):9.2f} ms median (min {tg.min():.2f}, max {tg.max():.2f}, {a.reps} reps)")
 say(f"greedy / align = {np.median(tg) / np.median(ta):.2f}; items with the same words {same_words}/{len(audios)}, the same start times {same_times}/{len(audios)} "
     "(seeded weights: attention rows are nearly flat, so arg-max ties may fall differently)")

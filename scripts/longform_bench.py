@@ -7,7 +7,8 @@ detector   audio.speech_probs on the whole waveform already on the device (sc_va
            probabilities), and with the upload of the waveform from the host in front of it.
 segmenter  SpeechSegmenter.segment_long_input on the host with the recorded probabilities (a vad= callable): pdac and the joining.
 long       Transcriber.transcribe_long with that segmenter: one fbank call, the speech encoder item by item, capture calls of up
-           to 64 rows, host bookkeeping; and with padded_encoder=True.
+           to 64 rows, host bookkeeping; with padded_encoder=True; and with ragged_encoder=True (one packed encoder pass over
+           the segments' own rows).  The three lines come from this one process on the same segments.
 one by one Transcriber.transcribe on the same segments one after the other: what a caller had to do before.
 At most `--tokens` generated tokens per segment in both routes.  Host clocks around calls that end in a device synchronise,
 after `--warmup` untimed passes.  There is no pass / fail ratio: the file is the record."""
@@ -91,11 +92,15 @@ got, t_long, lo, hi = median_ms(lambda: tr.transcribe_long(w2, "eng", chunk_size
 say(f"transcribe_long, encoder item by item:   {t_long:10.1f} ms median (min {lo:.1f}, max {hi:.1f}, {a.reps} reps)")
 _, t_pad, lo, hi = median_ms(lambda: tr.transcribe_long(w2, "eng", chunk_size_sec=a.chunk, segmenter=seg, padded_encoder=True, max_gen_len=a.tokens))
 say(f"transcribe_long, padded_encoder=True:    {t_pad:10.1f} ms median (min {lo:.1f}, max {hi:.1f}, {a.reps} reps)")
+rag, t_rag, lo, hi = median_ms(lambda: tr.transcribe_long(w2, "eng", chunk_size_sec=a.chunk, segmenter=seg, ragged_encoder=True, max_gen_len=a.tokens))
+say(f"transcribe_long, ragged_encoder=True:    {t_rag:10.1f} ms median (min {lo:.1f}, max {hi:.1f}, {a.reps} reps)")
 ref, t_one, lo, hi = median_ms(lambda: [tr.transcribe(w2[s:e], "eng", max_gen_len=a.tokens) for s, e in spans])
 say(f"transcribe of the segments one by one:   {t_one:10.1f} ms median (min {lo:.1f}, max {hi:.1f}, {a.reps} reps)")
 same_words = sum([x.text for x in g[2].tokens] == [x.text for x in r.tokens] for g, r in zip(got.segments, ref))
 same_times = sum([x.time_s for x in g[2].tokens] == [x.time_s for x in r.tokens] for g, r in zip(got.segments, ref))
 say(f"one by one / transcribe_long = {t_one / t_long:.2f}; segments with the same words {same_words}/{len(spans)}, the same start times {same_times}/{len(spans)}; "
     f"{len(got.tokens)} words, {len(wav) / RATE / (t_long / 1e3):.0f} x real time")
+rag_words = sum([x.text for x in g[2].tokens] == [x.text for x in r[2].tokens] for g, r in zip(got.segments, rag.segments))
+say(f"ragged / item by item = {t_rag / t_long:.2f}, ragged / padded = {t_rag / t_pad:.2f}; segments with the same words as item by item {rag_words}/{len(spans)}")
 Path(a.out).parent.mkdir(parents=True, exist_ok=True)
 Path(a.out).write_text("\n".join(lines) + "\n")

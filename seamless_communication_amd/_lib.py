@@ -191,6 +191,7 @@ SIGNATURES = {
     "sc_fbank_frames": (_i, [C.c_int64, _i]),
     "sc_encoder_out_len": (_i, [_P, _i]),
     "sc_encode_speech": (C.c_int, [_P, _P, _i, _i, _P, _P, _P]),
+    "sc_encode_speech_ragged": (C.c_int, [_P, _P, _i, _i, _P, _P, _i, _P]),
     "sc_encode_text": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "sc_mma_begin": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
     "sc_mma_step": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
@@ -310,6 +311,7 @@ SIGNATURES = {
     "sc_op_dstep_argmax": (C.c_int, [_P, _P, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_float, _i, _P, _P]),
     "sc_op_resblock_pair_ps": (C.c_int, [_P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _i]),
     "sc_op_glu_dwconv_ln": (C.c_int, [_P, _P, _P, _P, _i, _P, _P, _i, _i, _i, _i, _P, _i]),
+    "sc_op_glu_dwconv_ln_packed": (C.c_int, [_P, _P, _P, _P, _i, _P, _P, _i, _P, _P, _i, _i, _i]),
     "sc_op_layernorm2": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i]),
     "sc_op_dstep3_gemv": (C.c_int, [_i, _P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _i, _i]),
     "sc_op_dstep3_argmax": (C.c_int, [_P, _P, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_float, _P, _P]),

@@ -189,6 +189,15 @@ int sc_encode_speech(sc_model* m, const float* d_fbank, int32_t n, int32_t t_fra
     SC_API_END
 }
 
+int sc_encode_speech_ragged(sc_model* m, const float* d_fbank, int32_t n, int32_t t_frames, const int32_t* h_frame_lens, float* d_enc_out,
+                            int32_t s_enc_cap, int32_t* h_out_lens) {
+    SC_API_BEGIN
+    SC_CHECK(m && d_fbank && h_frame_lens && d_enc_out, "sc_encode_speech_ragged: null argument");
+    SC_HIP(hipSetDevice(m->m.device));
+    run_encode_speech_ragged(m->m, d_fbank, n, t_frames, h_frame_lens, d_enc_out, s_enc_cap, h_out_lens);
+    SC_API_END
+}
+
 int sc_encode_text(sc_model* m, const int32_t* h_tokens, int32_t n, int32_t s_text, const int32_t* h_lens, float* d_enc_out) {
     SC_API_BEGIN
     SC_CHECK(m && h_tokens && h_lens && d_enc_out, "sc_encode_text: null argument");
@@ -1814,7 +1823,9 @@ int sc_op_glu_dwconv_ln(const float* d_x, const float* d_w, const float* d_gamma
     SC_CHECK(d_x && d_w && d_gamma && d_beta && d_yh_f16 && d_yl_f16, "sc_op_glu_dwconv_ln: null argument");
     __half* yh = static_cast<__half*>(d_yh_f16);
     __half* yl = static_cast<__half*>(d_yl_f16);
-    if (fused) {
+    if (fused == 2) {  // the gated form: x [nb*T][C] already holds GLU(.)
+        launch_glu_dwconv_ln(d_x, C, d_w, d_gamma, d_beta, act, yh, yl, C, nb, T, C, k, d_lens, g_op_stream, /*gated=*/true);
+    } else if (fused) {
         launch_glu_dwconv_ln(d_x, 2 * C, d_w, d_gamma, d_beta, act, yh, yl, C, nb, T, C, k, d_lens, g_op_stream);
     } else {
         OpScratch scratch;
@@ -1823,6 +1834,23 @@ int sc_op_glu_dwconv_ln(const float* d_x, const float* d_w, const float* d_gamma
         launch_layernorm_split(mid, C, d_gamma, d_beta, yh, yl, C, nb * T, C, act, nullptr, 1, g_op_stream);
         SC_HIP(hipStreamSynchronize(g_op_stream));
     }
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_glu_dwconv_ln_packed(const float* d_x, const float* d_w, const float* d_gamma, const float* d_beta, int32_t act, void* d_yh_f16,
+                               void* d_yl_f16, int32_t n, const int32_t* h_row_off, const int32_t* h_lens, int32_t C, int32_t k, int32_t gated) {
+    SC_API_BEGIN
+    SC_CHECK(d_x && d_w && d_gamma && d_beta && d_yh_f16 && d_yl_f16 && h_row_off && h_lens && n > 0, "sc_op_glu_dwconv_ln_packed: null argument");
+    std::vector<int32_t> work;
+    glu_dwconv_ln_packed_work(h_row_off, h_lens, n, work);
+    double rows = 0;
+    for (int i = 0; i < n; ++i) rows += h_lens[i];
+    OpScratch scratch;
+    int* d_work = scratch.get<int>(work.size());
+    SC_HIP(hipMemcpyAsync(d_work, work.data(), work.size() * 4, hipMemcpyHostToDevice, g_op_stream));
+    launch_glu_dwconv_ln_packed(d_x, gated ? C : 2 * C, d_w, d_gamma, d_beta, act, static_cast<__half*>(d_yh_f16), static_cast<__half*>(d_yl_f16),
+                                C, d_work, (int)(work.size() / 4), rows, C, k, g_op_stream, gated != 0);
     SC_HIP(hipStreamSynchronize(g_op_stream));
     SC_API_END
 }

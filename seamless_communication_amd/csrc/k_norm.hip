@@ -1,6 +1,8 @@
 // Row-wise normalisation and the Conformer convolution middle section.
 // All kernels are HBM-bound: one pass over the data with 16-byte loads, wave64
 // shuffle reductions, no LDS round trip.
+#include <vector>
+
 #include "device_util.h"
 
 namespace sc {
@@ -379,8 +381,13 @@ void launch_relpos_table(int S, int M, float* out, hipStream_t s) {
 // (launch_gemm_presplit_glu) - so a row costs one load per channel and no exponential; everything behind the window (taps,
 // causal left edge, item length, LayerNorm, activation, split) is the same code.  A separate instantiation: the un-gated
 // kernel keeps its instructions.
+// PACKED (launch_glu_dwconv_ln_packed; its own instantiations too): items of different lengths lie back to back in x / yh / yl,
+// no padding rows.  The grid is a host-built table of work items instead of (range, item): `lens` points at int4 records
+// {first packed row of the item, its length, t_begin, t_end}, T and `range` are unused.  The window, the taps, the causal left
+// edge, the LayerNorm, the activation and the split are the expressions above in the same order, with T = len: rows outside
+// [0, len) of the workgroup's OWN item enter the window as zeros - never a neighbour's rows - and no row outside it is written.
 // --------------------------------------------------------------------------------------------- //
-template <int K, int TT, bool GATED>
+template <int K, int TT, bool GATED, bool PACKED = false>
 __global__ __launch_bounds__(1024) void glu_dwconv_ln_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta, int act,
                                                              __half* __restrict__ yh, __half* __restrict__ yl, int64_t ldh, int T, int C,
@@ -388,11 +395,13 @@ __global__ __launch_bounds__(1024) void glu_dwconv_ln_kernel(const float* __rest
     __shared__ float tile[2][TT][1024];
     const int c = threadIdx.x;  // channel (blockDim.x == C)
     const int lane = c & 63, wv = c >> 6, waves = C >> 6;
+    int4 wk = {0, 0, 0, 0};  // PACKED: this workgroup's record {item's first row, item length, t_begin, t_end}
+    if constexpr (PACKED) wk = reinterpret_cast<const int4*>(lens)[blockIdx.x];
     const int n = blockIdx.y;
-    const int t_begin = blockIdx.x * range, t_end = min(T, t_begin + range);
+    const int t_begin = PACKED ? wk.z : blockIdx.x * range, t_end = PACKED ? min(wk.w, wk.y) : min(T, t_begin + range);
     if (t_begin >= t_end) return;
-    const int len = lens ? min(lens[n], T) : T;
-    const float* xn = x + (int64_t)n * T * ldx;
+    const int len = PACKED ? wk.y : (lens ? min(lens[n], T) : T);
+    const float* xn = PACKED ? x + (int64_t)wk.x * ldx : x + (int64_t)n * T * ldx;
     float wr[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) wr[j] = w[c * K + j];
@@ -448,7 +457,7 @@ __global__ __launch_bounds__(1024) void glu_dwconv_ln_kernel(const float* __rest
         // LayerNorm + activation + split of the chunk's rows: one wave per row (the body of layernorm_kernel<4>)
         for (int r = wv; r < TT && tc + r < t_end; r += waves) {
             const float4* xr = reinterpret_cast<const float4*>(&tile[buf][r][0]);
-            const int64_t row = (int64_t)n * T + tc + r;
+            const int64_t row = PACKED ? (int64_t)wk.x + tc + r : (int64_t)n * T + tc + r;
             half4_t* yhr = reinterpret_cast<half4_t*>(yh + row * ldh);
             half4_t* ylr = reinterpret_cast<half4_t*>(yl + row * ldh);
             // (the row is re-read from LDS in each of the three passes instead of being held in 16 registers: the thread's
@@ -518,6 +527,44 @@ void launch_glu_dwconv_ln(const float* x, int64_t ldx, const float* w, const flo
     else
         hipLaunchKernelGGL((glu_dwconv_ln_kernel<31, TT, false>), dim3(ranges, nb), dim3(C), 0, s, x, ldx, w, gamma, beta, act, yh, yl, ldh, T, C,
                            lens, range);
+    SC_LAUNCH_CHECK();
+}
+
+// The work table of the packed kernel: items cut into time ranges of at least 32 rows (a range re-reads a 30-row halo), each a
+// multiple of TT = 8, with enough ranges over the whole batch for the chip - about 256 workgroups, shared out by row count, so
+// a batch of one long and many short items does not pay dim3(ranges of the longest, items).
+void glu_dwconv_ln_packed_work(const int32_t* row_off, const int32_t* lens, int n, std::vector<int32_t>& work) {
+    constexpr int TT = 8;
+    work.clear();
+    int64_t R = 0;
+    for (int i = 0; i < n; ++i) R += std::max(lens[i], 0);
+    const int per_wg = (int)std::max<int64_t>(32, cdiv64(cdiv64(R, 256), TT) * TT);  // rows per workgroup if rows were one item
+    for (int i = 0; i < n; ++i) {
+        const int len = lens[i];
+        if (len <= 0) continue;
+        const int ranges = std::max(1, std::min(cdiv(len, per_wg), cdiv(len, 32)));
+        const int range = cdiv(cdiv(len, ranges), TT) * TT;
+        for (int t = 0; t < len; t += range) {
+            const int32_t rec[4] = {row_off[i], len, t, std::min(len, t + range)};
+            work.insert(work.end(), rec, rec + 4);
+        }
+    }
+}
+
+void launch_glu_dwconv_ln_packed(const float* x, int64_t ldx, const float* w, const float* gamma, const float* beta, int act, __half* yh,
+                                 __half* yl, int64_t ldh, const int* d_work, int n_work, double rows, int C, int ksize, hipStream_t s,
+                                 bool gated) {
+    SC_CHECK(glu_dwconv_ln_supported(C, ksize) && ldh % 4 == 0 && (reinterpret_cast<uintptr_t>(d_work) & 15) == 0,
+             "glu_dwconv_ln_packed: C=%d k=%d ldh=%lld unsupported", C, ksize, (long long)ldh);
+    if (n_work <= 0) return;
+    constexpr int TT = 8;
+    prof::Scope scope("glu_dwconv_ln_packed", 2.0 * rows * C * ksize, rows * C * ((gated ? 4.0 : 8.0) + 4.0), s);
+    if (gated)
+        hipLaunchKernelGGL((glu_dwconv_ln_kernel<31, TT, true, true>), dim3(n_work), dim3(C), 0, s, x, ldx, w, gamma, beta, act, yh, yl, ldh, 0, C,
+                           d_work, 0);
+    else
+        hipLaunchKernelGGL((glu_dwconv_ln_kernel<31, TT, false, true>), dim3(n_work), dim3(C), 0, s, x, ldx, w, gamma, beta, act, yh, yl, ldh, 0, C,
+                           d_work, 0);
     SC_LAUNCH_CHECK();
 }
 

@@ -32,6 +32,7 @@
 //         at every scale, no overflow at 65520.
 #pragma once
 #include <atomic>
+#include <vector>
 
 #include "common.h"
 #include "boost_list.h"
@@ -566,6 +567,15 @@ void launch_glu(const float* x, int64_t ldx, float* y, int64_t ldy, int rows, in
 bool glu_dwconv_ln_supported(int C, int ksize);
 void launch_glu_dwconv_ln(const float* x, int64_t ldx, const float* w, const float* gamma, const float* beta, int act, __half* yh,
                           __half* yl, int64_t ldh, int nb, int T, int C, int ksize, const int* lens, hipStream_t s, bool gated = false);
+// The same on PACKED rows (the ragged speech encoder): item i owns rows row_off[i] .. row_off[i] + lens[i] of x / yh / yl, nothing
+// in between; an item's rows carry the bits launch_glu_dwconv_ln gives them when the item runs alone (T = its length), whatever
+// its neighbours hold.  glu_dwconv_ln_packed_work builds the launch's work table on the host - int4 records {row_off, len,
+// t_begin, t_end}, ranges of at least 32 rows in multiples of 8, about 256 workgroups over the whole batch - and d_work is its
+// copy on the device (16-byte aligned, n_work = work.size() / 4 records); rows = sum of the lengths (profiler only).
+void glu_dwconv_ln_packed_work(const int32_t* row_off, const int32_t* lens, int n, std::vector<int32_t>& work);
+void launch_glu_dwconv_ln_packed(const float* x, int64_t ldx, const float* w, const float* gamma, const float* beta, int act, __half* yh,
+                                 __half* yl, int64_t ldh, const int* d_work, int n_work, double rows, int C, int ksize, hipStream_t s,
+                                 bool gated = false);
 // Conformer conv middle: g = GLU(x) (masked by lens), y = causal depthwise conv_k(g)
 void launch_glu_dwconv(const float* x, int64_t ldx, const float* w, float* y, int64_t ldy, int nb, int T,
                        int C, int ksize, const int* lens, hipStream_t s, int left = -1, const float* bn_scale = nullptr,

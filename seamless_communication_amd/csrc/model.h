@@ -350,6 +350,9 @@ int fbank_num_frames(int64_t num_samples, int sample_rate);
 int encoder_out_len(const Model& m, int t_frames);
 void run_encode_speech(Model& m, const float* d_fbank, int n, int t_frames, const int32_t* h_lens, float* d_out,
                        int32_t* h_out_lens);
+// the same on each item's own rows in one packed pass (model_encoder.hip): d_out [n][s_enc_cap][model_dim], zeros behind a length
+void run_encode_speech_ragged(Model& m, const float* d_fbank, int n, int t_frames, const int32_t* h_lens, float* d_out, int s_enc_cap,
+                              int32_t* h_out_lens);
 void run_mma_begin(Model& m, const float* d_enc, int s_enc, int max_len);
 void run_mma_step(Model& m, const int32_t* h_tokens, int n_tokens, const int32_t* h_blocked, int n_blocked, int32_t* out_index,
                   float* h_pchoose, float* d_features);

@@ -369,4 +369,248 @@ void run_encode_speech(Model& m, const float* d_fbank, int n, int t_frames, cons
     SC_HIP(hipStreamSynchronize(m.stream));
 }
 
+// The speech encoder on a ragged batch in ONE packed pass (sc_encode_speech_ragged).  Item i contributes its own
+// S_i = frame_lens[i] / fbank_stride stacked rows and nothing else: the Conformer stack runs on R = sum S_i rows, the adaptor
+// layer on Ra = sum adaptor_len(S_i) rows, items back to back.  Every stage either acts on single rows (LayerNorm, the tiled
+// products - linear() with row_independent, launch_gemm_presplit: every tile shape walks K in the same order) or on one item's
+// own rows (packed attention, the packed convolution module, the adaptor's strided windows, which see zeros outside the item as
+// the Conv1d padding of an item that runs alone does).  An item's output therefore carries the same bits in any batch, and -
+// where run_encode_speech takes the tiled products as well, i.e. above 64 rows everywhere - the bits of run_encode_speech on the
+// item alone.  One form only: the pre-split planes path with the fused passes (SC_PRESPLIT / SC_ENC_FUSE do not apply;
+// SC_ENC_GLU_EPI is read per call, same bits).
+// The adaptor's two strided convolutions are plain products over gathered windows: row j of item i holds the
+// adaptor_kernel_size packed rows j * stride - pad .. tap-major, the order of the packed Conv1d weight [C_out][tap * C_in + c].
+void run_encode_speech_ragged(Model& m, const float* d_fbank, int n, int t_frames, const int32_t* h_lens, float* d_out, int s_enc_cap,
+                              int32_t* h_out_lens) {
+    const sc_config& c = m.cfg;
+    const int M = c.model_dim, Fd = c.enc_ffn_dim;
+    const int stride = c.fbank_stride, feat = c.num_fbank_channels * c.fbank_stride;
+    const int k = c.adaptor_kernel_size, st = c.adaptor_stride, pad = k / 2;
+    const AdaptorLayer& ad = m.adaptor;
+    SC_CHECK(n > 0 && t_frames > 0 && s_enc_cap > 0, "sc_encode_speech_ragged: empty batch");
+    SC_CHECK(c.enc_variant != 1, "sc_encode_speech_ragged: the v1 speech encoder (enc_variant 1) has no packed pass; use sc_encode_speech");
+    SC_CHECK(M % 32 == 0 && Fd % 32 == 0 && glu_dwconv_ln_supported(M, c.depthwise_conv_kernel_size) && feat % 4 == 0 &&
+                 ad.res_conv.kpad == k * M && ad.attn_conv.kpad == k * M,
+             "sc_encode_speech_ragged: model_dim=%d, enc_ffn_dim=%d, %d depthwise taps: the packed pass needs dimensions that are multiples "
+             "of 32, model_dim a multiple of 64 up to 1024 and 31 taps",
+             M, Fd, c.depthwise_conv_kernel_size);
+    SC_CHECK((int64_t)n * t_frames < (1ll << 31) && (int64_t)n * s_enc_cap < (1ll << 31), "sc_encode_speech_ragged: n=%d x t_frames=%d rows", n, t_frames);
+    std::vector<int32_t> lens(n), alens(n), off(n), aoff(n);
+    int64_t R64 = 0, Ra64 = 0;
+    int S = 0, Sa = 0;
+    double pairs = 0, apairs = 0;
+    for (int i = 0; i < n; ++i) {
+        SC_CHECK(h_lens[i] >= 0 && h_lens[i] <= t_frames, "sc_encode_speech_ragged: frame_lens[%d]=%d outside [0, t_frames=%d]", i, h_lens[i], t_frames);
+        SC_CHECK(h_lens[i] >= stride, "sc_encode_speech_ragged: item %d has %d frames, fewer than one stride of %d", i, h_lens[i], stride);
+        lens[i] = h_lens[i] / stride;
+        alens[i] = adaptor_len(c, lens[i]);
+        SC_CHECK(alens[i] >= 1, "sc_encode_speech_ragged: item %d has no output row", i);
+        R64 += lens[i];
+        Ra64 += alens[i];
+        S = std::max(S, lens[i]);
+        Sa = std::max(Sa, alens[i]);
+        pairs += (double)lens[i] * lens[i];
+        apairs += (double)alens[i] * alens[i];
+    }
+    auto capacity = [](bool ok, const char* fmt, auto... args) {
+        if (ok) return;
+        set_error(fmt, args...);
+        throw Error{SC_ERR_CAPACITY};
+    };
+    capacity(s_enc_cap >= Sa, "sc_encode_speech_ragged: the longest item has %d output rows, s_enc_cap is %d", Sa, s_enc_cap);
+    capacity(R64 * std::max(std::max(M, Fd), feat) * 2 < (1ll << 31) && Ra64 * k * M < (1ll << 31),
+             "sc_encode_speech_ragged: %lld packed rows exceed the 2^31-element bound of a product operand; encode the batch in groups",
+             (long long)R64);
+    const int R = (int)R64, Ra = (int)Ra64;
+    prof::set_tag("enc");
+    for (int i = 0, r = 0, ra = 0; i < n; r += lens[i], ra += alens[i], ++i) {
+        off[i] = r;
+        aoff[i] = ra;
+        if (h_out_lens) h_out_lens[i] = alens[i];
+    }
+
+    // host tables, one upload: the convolution module's work table first (16-byte records), then offsets and lengths, then the
+    // three row-index lists of the gathers (-1: a row of zeros)
+    std::vector<int32_t> tab;
+    glu_dwconv_ln_packed_work(off.data(), lens.data(), n, tab);
+    const int n_work = (int)(tab.size() / 4);
+    const size_t o_off = tab.size(), o_lens = o_off + n, o_aoff = o_lens + n, o_alens = o_aoff + n, o_fidx = o_alens + n,
+                 o_widx = o_fidx + R, o_sidx = o_widx + (size_t)Ra * k;
+    tab.resize(o_sidx + (size_t)n * s_enc_cap, -1);
+    for (int i = 0; i < n; ++i) {
+        tab[o_off + i] = off[i];
+        tab[o_lens + i] = lens[i];
+        tab[o_aoff + i] = aoff[i];
+        tab[o_alens + i] = alens[i];
+        for (int t = 0; t < lens[i]; ++t) tab[o_fidx + off[i] + t] = i * t_frames + t * stride;  // fbank row of the stacked row's first frame
+        for (int j = 0; j < alens[i]; ++j) {
+            tab[o_sidx + (size_t)i * s_enc_cap + j] = aoff[i] + j;
+            for (int tap = 0; tap < k; ++tap) {
+                const int t = j * st - pad + tap;
+                if (t >= 0 && t < lens[i]) tab[o_widx + (size_t)(aoff[i] + j) * k + tap] = off[i] + t;
+            }
+        }
+    }
+    Buf<int> d_tab(m.pp(), tab.size());
+    SC_HIP(hipMemcpyAsync(d_tab.get(), tab.data(), tab.size() * 4, hipMemcpyHostToDevice, m.stream));
+    const int* d_work = d_tab.get();
+    const int *d_off = d_work + o_off, *d_lens = d_work + o_lens, *d_aoff = d_work + o_aoff, *d_alens = d_work + o_alens,
+              *d_fidx = d_work + o_fidx, *d_widx = d_work + o_widx, *d_sidx = d_work + o_sidx;
+
+    const int F = std::max(c.adaptor_proj_dim, 3 * M);
+    Buf<float> x(m.pp(), (size_t)R * M), h(m.pp(), (size_t)R * std::max(M, feat)), wide(m.pp(), (size_t)R * F);
+    Buf<__half> planes(m.pp(), (size_t)R * (4 * M + 2 * Fd));
+    __half* hs_hi = planes.get();
+    __half* hs_lo = hs_hi + (size_t)R * M;
+    __half* as_hi = hs_lo + (size_t)R * M;
+    __half* as_lo = as_hi + (size_t)R * M;
+    __half* ws_hi = as_lo + (size_t)R * M;
+    __half* ws_lo = ws_hi + (size_t)R * Fd;
+
+    // frontend: stack fbank_stride frames of the item's own rows into packed order, LayerNorm, Linear
+    launch_gather_rows(d_fbank, c.num_fbank_channels, d_fidx, h, feat, R, feat, m.stream);
+    launch_layernorm(h, feat, m.fe_ln.g, m.fe_ln.b, h, feat, R, feat, ACT_NONE, nullptr, 1, m.stream);
+    linear(m, h, feat, m.fe_proj, nullptr, 0, x, M, R, ACT_NONE, 1.f, /*row_independent=*/true);
+
+    auto ln_split = [&](const float* src, const LNorm& L) {
+        launch_layernorm_split(src, L.dim, L.g, L.b, hs_hi, hs_lo, L.dim, R, L.dim, ACT_NONE, nullptr, 1, m.stream);
+    };
+    auto ps = [&](const __half* ah, const __half* al, const Linear& L, int act, float alpha, const float* res, float* C, __half* Ch, __half* Cl) {
+        GemmPsArgs a;
+        a.Ah = ah;
+        a.Al = al;
+        a.lda = L.in;
+        a.W = L.w;
+        a.ldw = L.ldw;
+        a.bias = L.b;
+        a.res = res;
+        a.ldr = L.out;
+        a.C = C;
+        a.ldc = L.out;
+        a.Ch = Ch;
+        a.Cl = Cl;
+        a.ldcs = L.out;
+        a.M = R;
+        a.N = L.out;
+        a.K = L.in;
+        a.act = act;
+        a.alpha = alpha;
+        launch_gemm_presplit(a, m.stream);
+    };
+    const bool glu_epi = knob::live("SC_ENC_GLU_EPI", 1) != 0;
+    for (int li = 0; li < c.enc_layers; ++li) {
+        const ConformerLayer& l = m.enc[li];
+        // x += 0.5 * FFN1(LN(x))   (the planes of LN_ffn1(x) come from the previous layer's closing launch)
+        if (li == 0) ln_split(x, l.ffn1_ln);
+        ps(hs_hi, hs_lo, l.ffn1_in, ACT_SILU, 1.f, nullptr, nullptr, ws_hi, ws_lo);
+        ps(ws_hi, ws_lo, l.ffn1_out, ACT_NONE, 0.5f, x, x, nullptr, nullptr);
+        // x += MHA_shaw(LN(x)) over each item's own rows
+        ln_split(x, l.attn_ln);
+        ps(hs_hi, hs_lo, l.qkv, ACT_NONE, 1.f, nullptr, wide, nullptr, nullptr);
+        {
+            AttnArgs a;
+            a.q = wide;
+            a.k = wide.get() + M;
+            a.v = wide.get() + 2 * M;
+            a.out_hi = as_hi;
+            a.out_lo = as_lo;
+            a.ldoh = M;
+            a.ldq = a.ldk = a.ldv = 3 * M;
+            a.ldo = M;
+            a.nb = n;
+            a.heads = c.num_heads;
+            a.Sq = S;
+            a.Skv = S;
+            a.kv_lens = d_lens;
+            a.row_off = d_off;
+            a.pairs = pairs;
+            a.rel_k = l.rel_k;
+            a.rel_left = c.shaw_max_left;
+            a.rel_right = c.shaw_max_right;
+            launch_attention(a, m.stream);
+        }
+        ps(as_hi, as_lo, l.attn_out, ACT_NONE, 1.f, x, x, nullptr, nullptr);
+        // x += Conv(LN(x))
+        ln_split(x, l.conv_ln);
+        if (glu_epi) {
+            GemmPsArgs a;
+            a.Ah = hs_hi;
+            a.Al = hs_lo;
+            a.lda = M;
+            a.W = l.pw1g.w;
+            a.ldw = l.pw1g.ldw;
+            a.bias = l.pw1g.b;
+            a.C = wide;
+            a.ldc = M;
+            a.M = R;
+            a.N = 2 * M;
+            a.K = M;
+            launch_gemm_presplit_glu(a, m.stream);
+        } else {
+            ps(hs_hi, hs_lo, l.pw1, ACT_NONE, 1.f, nullptr, wide, nullptr, nullptr);
+        }
+        launch_glu_dwconv_ln_packed(wide, glu_epi ? M : 2 * M, l.dw, l.conv_inner_ln.g, l.conv_inner_ln.b, ACT_SILU, hs_hi, hs_lo, M, d_work,
+                                    n_work, (double)R, M, c.depthwise_conv_kernel_size, m.stream, /*gated=*/glu_epi);
+        ps(hs_hi, hs_lo, l.pw2, ACT_NONE, 1.f, x, x, nullptr, nullptr);
+        // x += 0.5 * FFN2(LN(x)); x = LN(x)
+        ln_split(x, l.ffn2_ln);
+        ps(hs_hi, hs_lo, l.ffn2_in, ACT_SILU, 1.f, nullptr, nullptr, ws_hi, ws_lo);
+        ps(ws_hi, ws_lo, l.ffn2_out, ACT_NONE, 0.5f, x, x, nullptr, nullptr);
+        if (li + 1 < c.enc_layers) {
+            const LNorm& nx = m.enc[li + 1].ffn1_ln;
+            launch_layernorm2_split(x, M, l.final_ln.g, l.final_ln.b, x, M, nx.g, nx.b, hs_hi, hs_lo, M, R, M, m.stream);
+        } else {
+            layernorm(m, x, l.final_ln, x, R);
+        }
+    }
+    // adaptor head (adaptor_block.py:105-109)
+    layernorm(m, x, m.enc_inner_ln, x, R);
+    linear(m, x, M, m.enc_proj1, nullptr, 0, wide, c.adaptor_proj_dim, R, ACT_RELU, 1.f, true);
+    linear(m, wide, c.adaptor_proj_dim, m.enc_proj2, x, M, x, M, R, ACT_NONE, 0.5f, true);
+
+    // adaptor layer (adaptor_block.py:249-314) on Ra packed rows
+    Buf<float> win(m.pp(), (size_t)Ra * k * M), res(m.pp(), (size_t)Ra * M), y(m.pp(), (size_t)Ra * M), conv(m.pp(), (size_t)Ra * 2 * M),
+        aw(m.pp(), (size_t)Ra * std::max(3 * M, c.adaptor_ffn_dim)), ah(m.pp(), (size_t)Ra * M);
+    auto strided_conv_glu = [&](const LNorm& L, const Conv& cv, float* out) {
+        layernorm(m, x, L, h, R);
+        launch_gather_rows(h, M, d_widx, win, M, Ra * k, M, m.stream);  // win [Ra][k * M]: tap-major windows
+        Linear w;
+        w.w = cv.w;
+        w.ldw = cv.kpad;
+        w.b = cv.b;
+        w.out = cv.cout;
+        w.in = w.kpad = cv.kpad;
+        linear(m, win, (int64_t)k * M, w, nullptr, 0, conv, 2 * M, Ra, ACT_NONE, 1.f, true);
+        launch_glu(conv, 2 * M, out, M, Ra, M, m.stream);
+    };
+    strided_conv_glu(ad.res_ln, ad.res_conv, res);
+    strided_conv_glu(ad.attn_ln, ad.attn_conv, y);
+    linear(m, y, M, ad.qkv, nullptr, 0, aw, 3 * M, Ra, ACT_NONE, 1.f, true);
+    {
+        AttnArgs a;
+        a.q = aw;
+        a.k = aw.get() + M;
+        a.v = aw.get() + 2 * M;
+        a.out = ah;
+        a.ldq = a.ldk = a.ldv = 3 * M;
+        a.ldo = M;
+        a.nb = n;
+        a.heads = c.num_heads;
+        a.Sq = Sa;
+        a.Skv = Sa;
+        a.kv_lens = d_alens;
+        a.row_off = d_aoff;
+        a.pairs = apairs;
+        launch_attention(a, m.stream);
+    }
+    linear(m, ah, M, ad.attn_out, res, M, y, M, Ra, ACT_NONE, 1.f, true);
+    layernorm(m, y, ad.ffn_ln, ah, Ra);
+    linear(m, ah, M, ad.ffn_in, nullptr, 0, aw, c.adaptor_ffn_dim, Ra, m.ffn_act, 1.f, true);
+    linear(m, aw, c.adaptor_ffn_dim, ad.ffn_out, y, M, y, M, Ra, ACT_NONE, 1.f, true);
+    layernorm(m, y, m.enc_final_ln, y, Ra);
+    // packed rows into the padded [n][s_enc_cap][M] output, zeros behind each item's length
+    launch_gather_rows(y, M, d_sidx, d_out, M, n * s_enc_cap, M, m.stream);
+    SC_HIP(hipStreamSynchronize(m.stream));
+}
+
 }  // namespace sc

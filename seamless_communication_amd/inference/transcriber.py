@@ -292,7 +292,7 @@ class Transcriber:
     CAPTURE_ROWS = 64  # the row limit of sc_generate_text_capture
 
     def _decode_batch(self, wavs: List[Tensor], sample_rate: int, lang: Optional[str], opts: Dict[str, Any], padded_encoder: bool = False,
-                      lid_item: Optional[int] = None):
+                      lid_item: Optional[int] = None, ragged_encoder: bool = False):
         """``_decode`` for many items in ONE language -> ([(token ids, step scores, attention rows)] in input order, the language,
         its identification or None).  One fbank call and the encoder as in ``_encode`` (item by item unless ``padded_encoder``, so
         an item's encoder output does not depend on its batch), then generate_text_capture calls of at most ``CAPTURE_ROWS`` rows
@@ -300,7 +300,7 @@ class Transcriber:
         on item ``lid_item`` serves all items.  A ``max_gen_len`` of the form (a, b) refers to the source length, which a
         capture call takes once for all its rows: such a call holds items of one frame count only."""
         model = self.model
-        enc, enc_lens, frames = self._encode(wavs, sample_rate, padded_encoder)
+        enc, enc_lens, frames = self._encode(wavs, sample_rate, padded_encoder, ragged_encoder)
         lid = None
         if lang is None:
             i = int(lid_item or 0)
@@ -348,10 +348,12 @@ class Transcriber:
 
     @torch.inference_mode()
     def transcribe_batch(self, audios: Sequence[Union[str, Tensor]], src_lang: Optional[str], filter_width: int = 3, sample_rate: int = 16000,
-                         padded_encoder: bool = False, **sequence_generator_options: Dict) -> List[Transcription]:
+                         padded_encoder: bool = False, ragged_encoder: bool = False, **sequence_generator_options: Dict) -> List[Transcription]:
         """``transcribe`` of every item of a ragged list (each at most 20 s, the reference's default ``chunk_size_sec``) with batched
         decoder calls; item i equals ``transcribe(audios[i], src_lang)``.  One language per call - the capture call takes one shared
-        prompt; ``src_lang=None`` identifies every item and runs one group per identified language."""
+        prompt; ``src_lang=None`` identifies every item and runs one group per identified language.  ``ragged_encoder=True``: the
+        encoder runs once, on each item's own rows in one packed pass (``_encode``); item i then equals this call on item i alone."""
+        self._encoder_choice(padded_encoder, ragged_encoder)
         opts = self._greedy_options(sequence_generator_options)
         wavs = [_waveform(a, sample_rate) for a in audios]
         for i, w in enumerate(wavs):
@@ -365,14 +367,14 @@ class Transcriber:
         seconds = [w.size(0) / sample_rate for w in wavs]
         if src_lang is not None:
             self.tokenizer.target_prefix(src_lang)
-            decoded, lang, _ = self._decode_batch(wavs, sample_rate, src_lang, opts, padded_encoder)
+            decoded, lang, _ = self._decode_batch(wavs, sample_rate, src_lang, opts, padded_encoder, ragged_encoder=ragged_encoder)
             return [self._words(d, seconds[i], filter_width, lang, None) for i, d in enumerate(decoded)]
-        enc, enc_lens, _ = self._encode(wavs, sample_rate, padded_encoder)
+        enc, enc_lens, _ = self._encode(wavs, sample_rate, padded_encoder, ragged_encoder)
         found = identify_encoded(self.model, self.tokenizer, enc, enc_lens)
         out: List[Optional[Transcription]] = [None] * len(wavs)
         for lang in sorted({f.lang for f in found}):
             pick = [i for i, f in enumerate(found) if f.lang == lang]
-            decoded, _, _ = self._decode_batch([wavs[i] for i in pick], sample_rate, lang, opts, padded_encoder)
+            decoded, _, _ = self._decode_batch([wavs[i] for i in pick], sample_rate, lang, opts, padded_encoder, ragged_encoder=ragged_encoder)
             for i, d in zip(pick, decoded):
                 out[i] = self._words(d, seconds[i], filter_width, lang, found[i])
         return out  # type: ignore[return-value]
@@ -386,14 +388,14 @@ class Transcriber:
         return {"boost_seqs": proc.phrases, "boost": proc.boost} if proc.phrases and proc.boost != 0.0 else {}
 
     def _long_biased(self, wavs: List[Tensor], seconds: List[float], sample_rate: int, lang: Optional[str], opts: Dict[str, Any],
-                     padded_encoder: bool, lid_item: int, filter_width: int, boost_kw: Dict[str, Any]):
+                     padded_encoder: bool, lid_item: int, filter_width: int, boost_kw: Dict[str, Any], ragged_encoder: bool = False):
         """The segments of ``transcribe_long`` with boost phrases: generate_text (the host-driven step loop, where the step
         processors run) in calls of up to ``CAPTURE_ROWS`` rows, grouped as ``_decode_batch`` groups them, then one teacher-forced
         capture pass for the times, as ``transcribe_beam`` does -> ([Transcription], the language, its identification or None)."""
         model = self.model
         opts = dict(opts)
         beam_size = int(opts.pop("beam_size", None) or 1)
-        enc, enc_lens, frames = self._encode(wavs, sample_rate, padded_encoder)
+        enc, enc_lens, frames = self._encode(wavs, sample_rate, padded_encoder, ragged_encoder)
         lid = None
         if lang is None:
             i = int(lid_item)
@@ -427,7 +429,7 @@ class Transcriber:
     @torch.inference_mode()
     def transcribe_long(self, audio: Union[str, Tensor], src_lang: Optional[str], filter_width: int = 3, sample_rate: int = 16000,
                         chunk_size_sec: float = 20, pause_length_sec: float = 1, segmenter: Optional[Any] = None, padded_encoder: bool = False,
-                        bias_phrases: Optional[Sequence[Any]] = None, bias_boost: float = 2.0,
+                        bias_phrases: Optional[Sequence[Any]] = None, bias_boost: float = 2.0, ragged_encoder: bool = False,
                         **sequence_generator_options: Dict) -> Transcription:
         """Audio of any length -> ONE ``Transcription`` with the words of every speech segment in order and ABSOLUTE ``time_s``
         (the segment's ``start / sample_rate`` plus the time inside the segment).  ``segments`` holds
@@ -441,7 +443,10 @@ class Transcriber:
         ``bias_phrases`` (strings or token lists) with ``bias_boost``: phrase boosting (``PhraseBoostProcessor``; an extension
         whose effect on real speech has not been evaluated).  The segments are then generated by sc_generate_text_boosted in
         calls of up to 64 rows (``beam_size`` defaults to 1 and may be larger) and timed by the teacher-forced capture pass,
-        as ``transcribe_beam`` does; a word's ``prob`` is then the raw log-probability's."""
+        as ``transcribe_beam`` does; a word's ``prob`` is then the raw log-probability's.
+        ``ragged_encoder=True``: the segments' encoder runs as one packed pass (``_encode``); the segments are then those of
+        ``transcribe_batch(..., ragged_encoder=True)`` on the spans."""
+        self._encoder_choice(padded_encoder, ragged_encoder)
         boost_kw = self._boost_args(bias_phrases, bias_boost)
         opts = dict(sequence_generator_options) if boost_kw else self._greedy_options(sequence_generator_options)
         wav = _waveform(audio, sample_rate)
@@ -463,13 +468,14 @@ class Transcriber:
         longest = max(range(len(spans)), key=lambda i: (spans[i][1] - spans[i][0], -i))
         if boost_kw:
             ones, lang, lid = self._long_biased([wav[a:b] for a, b in spans], [(b - a) / sample_rate for a, b in spans], sample_rate, src_lang,
-                                                opts, padded_encoder, longest, filter_width, boost_kw)
+                                                opts, padded_encoder, longest, filter_width, boost_kw, ragged_encoder)
             segments, tokens = [], []
             for (a, b), one in zip(spans, ones):
                 segments.append((a / sample_rate, b / sample_rate, one))
                 tokens += [TranscriptionToken(t.text, a / sample_rate + t.time_s, t.prob) for t in one.tokens]
             return Transcription(tokens, lang, lid, segments=segments)
-        decoded, lang, lid = self._decode_batch([wav[a:b] for a, b in spans], sample_rate, src_lang, opts, padded_encoder, lid_item=longest)
+        decoded, lang, lid = self._decode_batch([wav[a:b] for a, b in spans], sample_rate, src_lang, opts, padded_encoder, lid_item=longest,
+                                               ragged_encoder=ragged_encoder)
         segments, tokens = [], []
         for (a, b), d in zip(spans, decoded):
             one = self._words(d, (b - a) / sample_rate, filter_width, lang, None)
@@ -491,11 +497,20 @@ class Transcriber:
                 return None
         return target_sequence(self.tokenizer, lang, text, self.cfg.text_max_seq_len)
 
-    def _encode(self, wavs: List[Tensor], sample_rate: int, padded_encoder: bool = False):
+    @staticmethod
+    def _encoder_choice(padded_encoder: bool, ragged_encoder: bool) -> None:
+        if padded_encoder and ragged_encoder:
+            raise ValueError("padded_encoder and ragged_encoder exclude each other: one encoder call on the padded batch, or one on "
+                             "each item's own rows")
+
+    def _encode(self, wavs: List[Tensor], sample_rate: int, padded_encoder: bool = False, ragged_encoder: bool = False):
         """One fbank call for all items (an item's frames do not depend on the batch), then the speech encoder -> (enc, enc_lens,
         frames).  The encoder runs item by item on each item's own frames unless ``padded_encoder``: like the reference's, its
         adaptor applies no padding mask in front of its strided convolutions, so the output of a padded item depends on its batch
-        (DESIGN section 4), and up to 64 rows take other products than more.  ``padded_encoder``: one call on the padded batch."""
+        (DESIGN section 4), and up to 64 rows take other products than more.  ``padded_encoder``: one call on the padded batch.
+        ``ragged_encoder``: one call of the packed pass (``encode_speech_ragged``) on the unpadded fbank - each
+        item's own whole strides, no copy per item; an item's output does not depend on the batch, a single item included."""
+        self._encoder_choice(padded_encoder, ragged_encoder)
         model = self.model
         n = len(wavs)
         ns = [int(w.shape[0]) for w in wavs]
@@ -505,6 +520,9 @@ class Transcriber:
         together = padded_encoder and n > 1
         fb, frames = model.fbank(batch.to(self.device).contiguous(), ns, standardize=True, pad_to_multiple=2 if together else 1,
                                  sample_rate=int(sample_rate))
+        if ragged_encoder:
+            enc, enc_lens = model.encode_speech_ragged(fb, frames)
+            return enc, enc_lens, frames
         if together or n == 1:
             enc, enc_lens = model.encode_speech(*self._whole_strides(fb, frames))
             return enc, enc_lens, frames
@@ -546,6 +564,7 @@ class Transcriber:
         filter_width: int = 3,
         sample_rate: int = 16000,
         padded_encoder: bool = False,
+        ragged_encoder: bool = False,
     ) -> List[Transcription]:
         """Forced alignment of a ragged batch: when the words of ``texts[i]`` were spoken in ``audios[i]``.  ``texts[i]``: a
         string, or its token ids without prompt and ``</s>``; ``src_langs``: one language for all items or one per item
@@ -555,7 +574,9 @@ class Transcriber:
         on the padded batch instead (faster; results are then those of ``Translator.predict`` on such a batch, close to but not
         equal to the item's own).  A word's ``prob`` is the mean of exp(log p(piece | the pieces before it)) - the
         raw log-probability, no step rules.  An item without text gives an empty ``Transcription``.  No ``chunk_size_sec``
-        limit (nothing is generated): the limits are the encoder's and ``text_max_seq_len``."""
+        limit (nothing is generated): the limits are the encoder's and ``text_max_seq_len``.  ``ragged_encoder=True``: the
+        encoder runs once, as one packed pass over each item's own rows; item i then equals this call on item i alone."""
+        self._encoder_choice(padded_encoder, ragged_encoder)
         audios, texts = list(audios), list(texts)
         n = len(audios)
         if n == 0:
@@ -569,7 +590,7 @@ class Transcriber:
         seqs = [self._sequence(t, l) if l is not None else None for t, l in zip(texts, langs)]
         wavs = [_waveform(a, sample_rate) for a in audios]
         seconds = [w.size(0) / sample_rate for w in wavs]
-        enc, enc_lens, _ = self._encode(wavs, sample_rate, padded_encoder)
+        enc, enc_lens, _ = self._encode(wavs, sample_rate, padded_encoder, ragged_encoder)
         lids: List[Optional[Any]] = [None] * n
         if any(l is None for l in langs):
             found = identify_encoded(self.model, self.tokenizer, enc, enc_lens)

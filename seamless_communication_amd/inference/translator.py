@@ -37,7 +37,7 @@ from .. import cards as _cards
 from .. import synthetic as _syn
 from ..config import (S2STConfig, seamless_expressivity, seamless_m4t_large, seamless_m4t_medium, seamless_m4t_v2_large, tiny_config,
                       tiny_expressive_config, tiny_v1_config)
-from ..runtime import HipS2STModel
+from ..runtime import HipS2STModel, encode_source_speech
 from ..tokenizer import CharTokenizer, NllbTextTokenizer, UnitTokenizer
 from .generator import SequenceGeneratorOptions, check_sampling, encode_bias_phrases, split_step_processors
 from ..scoring import score as _score
@@ -383,6 +383,12 @@ class Translator:
     #   "error" refuse.
     multi_channel: str = "first"
 
+    # True: speech input is encoded by the packed pass (HipS2STModel.encode_speech_ragged) - the batch costs the rows it has and
+    # an item's encoder output, hence its text, does not depend on its companions.  Forwarded to the model where the source
+    # batch is built, so it reaches predict, predict_nbest, sample, score, identify_language and the MinTox re-generation; text
+    # input is untouched.  Not the reference's behaviour (its padded item depends on its batch).
+    ragged_encoder: bool = False
+
     # The asset card `apply_mintox=True` loads the ETOX checker from (translator.py:130 names "mintox"): the bare name has
     # no offline source, so set a card dict (toxicity/etox_bad_word_checker.py: load_etox_bad_word_checker) on the class
     # or a subclass before constructing; `self.bad_word_checker` may also be assigned afterwards.
@@ -450,6 +456,7 @@ class Translator:
             if seqs.shape[1] % self.cfg.fbank_stride:  # Collater(pad_to_multiple=2)
                 seqs = torch.nn.functional.pad(seqs, (0, 0, 0, self.cfg.fbank_stride - seqs.shape[1] % self.cfg.fbank_stride))
             seqs = seqs.to(self.device, torch.float32).contiguous()
+            self.model.ragged_encoder = bool(self.ragged_encoder)  # read by encode_source_speech, here and in the MinTox pass
         elif seqs.dim() != 2 or seqs.dtype.is_floating_point:
             raise ValueError("SequenceData['seqs'] must be (N, S) token indices for text input")
         return src, seqs, src_lens, sample_rate
@@ -688,7 +695,7 @@ class Translator:
         if streams is not None and len(streams) != len(src_lens):
             raise ValueError(f"`streams` must hold one id per input item ({len(src_lens)}), but holds {len(streams)} instead.")
         if input_modality == Modality.SPEECH:
-            enc, enc_lens = self.model.encode_speech(seqs, src_lens)
+            enc, enc_lens = encode_source_speech(self.model, seqs, src_lens)
         else:
             enc, enc_lens = self.model.encode_text(seqs.cpu().numpy(), src_lens), np.asarray(src_lens, dtype=np.int32)
         sample_kw: Dict[str, Any] = dict(
@@ -745,7 +752,7 @@ class Translator:
         ngram, step_kw = self._step_processor_args(opts)
         _, seqs, src_lens, _ = self._source_batch(input, input_modality, src_lang, sample_rate)
         if input_modality == Modality.SPEECH:
-            enc, enc_lens = self.model.encode_speech(seqs, src_lens)
+            enc, enc_lens = encode_source_speech(self.model, seqs, src_lens)
         else:
             enc, enc_lens = self.model.encode_text(seqs.cpu().numpy(), src_lens), np.asarray(src_lens, dtype=np.int32)
         prompts = forced_prompts(self.text_tokenizer, forced, tgt_lang, len(src_lens))
@@ -832,7 +839,7 @@ class Translator:
         # every sc_* stage call returns with its stream drained, so host timers are stage times
         t0 = time.perf_counter()
         if input_modality == Modality.SPEECH:
-            enc, enc_lens = model.encode_speech(seqs, src_lens)
+            enc, enc_lens = encode_source_speech(model, seqs, src_lens)
         else:
             enc, enc_lens = model.encode_text(seqs.cpu().numpy(), src_lens), np.asarray(src_lens, dtype=np.int32)
         t1 = time.perf_counter()

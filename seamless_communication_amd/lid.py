@@ -17,6 +17,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .runtime import encode_source_speech
+
 
 @dataclass
 class LanguageId:
@@ -91,7 +93,7 @@ def identify_language(self, input, input_modality=None, src_lang: Optional[str] 
     candidate_tokens(self.text_tokenizer, langs)  # an unknown name is refused before any device work
     _, seqs, src_lens, _ = self._source_batch(input, input_modality, src_lang, sample_rate)
     if input_modality == Modality.SPEECH:
-        enc, enc_lens = self.model.encode_speech(seqs, src_lens)
+        enc, enc_lens = encode_source_speech(self.model, seqs, src_lens)
     else:
         enc, enc_lens = self.model.encode_text(seqs.cpu().numpy(), src_lens), np.asarray(src_lens, dtype=np.int32)
     return identify_encoded(self.model, self.text_tokenizer, enc, enc_lens, langs)

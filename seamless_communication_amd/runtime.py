@@ -39,6 +39,34 @@ def _i32(a) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(a, dtype=np.int32))
 
 
+# stacked rows one sc_encode_speech_ragged call takes by default: those of the benchmark's batch, 64 items of 10 s (499 rows each)
+RAGGED_MAX_ROWS = 64 * 499
+
+
+def plan_row_groups(rows: Sequence[int], max_rows: int) -> List[Tuple[int, int]]:
+    """Cuts items of ``rows[i]`` rows each into consecutive groups ``[(first, last + 1)]`` in the items' order: a group is
+    closed when the next item would take it beyond ``max_rows``; a single item above ``max_rows`` is a group of its own."""
+    if max_rows < 1:
+        raise ValueError(f"max_rows must be positive, got {max_rows}")
+    groups: List[Tuple[int, int]] = []
+    first, held = 0, 0
+    for i, r in enumerate(rows):
+        if i > first and held + int(r) > max_rows:
+            groups.append((first, i))
+            first, held = i, 0
+        held += int(r)
+    if len(rows) > first:
+        groups.append((first, len(rows)))
+    return groups
+
+
+def encode_source_speech(model, fbank: torch.Tensor, frame_lens: Sequence[int]):
+    """The speech encoder call of the Translator's entries: the packed pass when the model's ``ragged_encoder`` is set."""
+    if getattr(model, "ragged_encoder", False):
+        return model.encode_speech_ragged(fbank, frame_lens)
+    return model.encode_speech(fbank, frame_lens)
+
+
 def _ragged_prompts(prefix, n: int, with_lists: bool = False):
     """The per-row prompt forms of generate_text that carry their own lengths: ``(rows, lens)`` with rows (n, stride), or a
     list with one prompt per row - of different lengths, or (``with_lists``: the call carries banned sequences or boost
@@ -280,6 +308,30 @@ class HipS2STModel(_Handle):
         self._after_torch()
         check(self.lib.sc_encode_speech(self.handle, _ptr(fbank), n, T, _ptr(lens), _ptr(out), _ptr(out_lens)),
               "sc_encode_speech")
+        return out, out_lens
+
+    # speech input of the Translator goes through encode_speech_ragged when set (Translator.ragged_encoder forwards it)
+    ragged_encoder: bool = False
+
+    def encode_speech_ragged(self, fbank: torch.Tensor, frame_lens: Sequence[int],
+                             max_rows: Optional[int] = None) -> Tuple[torch.Tensor, np.ndarray]:
+        """The speech encoder on a ragged batch in one packed pass (sc_encode_speech_ragged): fbank (n, T, 80) with T >= every
+        length (T need not be a multiple of ``fbank_stride``; a trailing frame of an item that does not fill a stride is dropped)
+        -> (enc (n, longest output, M) with zeros behind each item's length, enc_lens).  The pass computes each item's own rows
+        only, and an item's output has the same bits in any batch.  Batches of more than ``max_rows`` stacked rows (default
+        ``RAGGED_MAX_ROWS``) run as consecutive groups, which therefore changes no bit."""
+        assert fbank.is_cuda and fbank.dtype == torch.float32 and fbank.is_contiguous() and fbank.dim() == 3
+        n, T, _ = fbank.shape
+        lens = _i32(frame_lens)
+        stride = int(self.cfg.fbank_stride)
+        rows = [int(x) // stride for x in lens]
+        cap = max(1, max(int(self.lib.sc_encoder_out_len(self.handle, r * stride)) for r in rows))
+        out = torch.empty(n, cap, self.cfg.model_dim, dtype=torch.float32, device=self.device)
+        out_lens = np.zeros(n, dtype=np.int32)
+        self._after_torch()
+        for a, b in plan_row_groups(rows, RAGGED_MAX_ROWS if max_rows is None else int(max_rows)):
+            check(self.lib.sc_encode_speech_ragged(self.handle, _ptr(fbank[a:b]), b - a, T, _ptr(lens[a:b]), _ptr(out[a:b]), cap,
+                                                   _ptr(out_lens[a:b])), "sc_encode_speech_ragged")
         return out, out_lens
 
     def encode_text(self, tokens, lens: Sequence[int]) -> torch.Tensor:

@@ -19,6 +19,9 @@ from typing import Any, Dict, Iterable, List, Optional, Sequence, Union
 import numpy as np
 import torch
 
+from .runtime import encode_source_speech
+
+
 SCORE_TASKS = ("S2TT", "ASR", "T2TT")
 # CalcLoss: `prefix_skip_len = 1  # language tokens to skip` (trainer.py:175), handed on as ignore_prefix_size
 IGNORE_PREFIX_SIZE = 1
@@ -115,7 +118,7 @@ def score(self, input, task_str: str, tgt_lang: str, targets, src_lang: Optional
 
     _, seqs, src_lens, _ = self._source_batch(input, input_modality, src_lang, sample_rate)
     if input_modality == Modality.SPEECH:
-        enc, enc_lens = self.model.encode_speech(seqs, src_lens)
+        enc, enc_lens = encode_source_speech(self.model, seqs, src_lens)
     else:
         enc, enc_lens = self.model.encode_text(seqs.cpu().numpy(), src_lens), np.asarray(src_lens, dtype=np.int32)
     n = len(seq_ids)
