@@ -238,6 +238,43 @@ int sc_mma_begin(sc_model* m, const float* d_enc, int32_t s_enc, int32_t max_len
 int sc_mma_step(sc_model* m, const int32_t* h_tokens, int32_t n_tokens, const int32_t* h_blocked, int32_t n_blocked,
                 int32_t* out_index, float* h_pchoose, float* d_features);
 
+/* Streaming session pool (additive, ABI 10; no reference counterpart - SimulEval drives one stream): `sessions` concurrent
+ * streams of the monotonic decoder share every decoder step.  Each session owns a self-attention K / V lane of max_len
+ * positions, an encoder-decoder K / V lane of s_enc_cap rows per layer, its key-side energies, its position and its encoder
+ * length; all memory is fixed at creation (sc_mma_pool_get_stats).  The pool runs on m's stream (forked handles work) and must
+ * be freed before m; one host thread calls at a time.  A session's results do not depend on which other sessions exist, are
+ * named in the same call, feed how many tokens or sit in which lanes: they are those of the same calls on a pool of one session,
+ * bit for bit (they agree with sc_mma_step to fp32 re-association, not to the bit: other products, other summation order).
+ * sc_mma_pool_begin = sc_mma_begin for the k sessions h_sessions[0..k) at once: d_enc holds their encoder outputs packed
+ * [sum h_s_enc][model_dim] in call order; their positions return to 0.
+ * sc_mma_pool_step = sc_mma_step for the k named sessions: session j feeds h_tokens[j * tok_stride .. + h_n_tokens[j]).  The call
+ * runs max(h_n_tokens) decoder steps with the feeds right-aligned (session j joins at step max - h_n_tokens[j]), so that every
+ * session's last token falls into the last step; for that token it returns h_out_index[j] (arg-max of the logits with the
+ * session's h_blocked[j * blocked_stride .. + h_n_blocked[j]) entries at -inf; h_blocked may be NULL) and h_pchoose
+ * [k][mma_layers][num_heads]; d_features receives the decoder outputs of all fed tokens, packed [sum h_n_tokens][model_dim] in
+ * call order.  Sessions a call does not name are not touched.
+ * SC_ERR_INVALID before any device work, no state changed: a NULL pointer, k outside 1..sessions, a session id out of range or
+ * named twice, s_enc outside 1..s_enc_cap, a token outside the vocabulary, n_tokens < 1 or > tok_stride, position + n_tokens >
+ * max_len (sc_last_error names the session), n_blocked outside 0..min(32, blocked_stride), a step on a session that never began.
+ * sc_mma_pool_create returns NULL (sc_last_error) for a model without a monotonic decoder, sessions outside 1..512, or a model the
+ * row-group step chain does not take.
+ * Stats: the three byte counts are fixed at creation; begins = sessions begun, steps = decoder steps run, row_steps = rows those
+ * steps carried (row_steps / steps = mean rows per step). */
+typedef struct sc_mma_pool sc_mma_pool;
+typedef struct sc_mma_pool_opts {
+    int32_t abi_version, sessions /* 1..512 */, max_len, s_enc_cap;
+} sc_mma_pool_opts;
+typedef struct sc_mma_pool_stats {
+    int64_t self_kv_bytes, cross_kv_bytes, work_bytes, begins, steps, row_steps;
+} sc_mma_pool_stats;
+sc_mma_pool* sc_mma_pool_create(sc_model* m, const sc_mma_pool_opts* opts);
+void sc_mma_pool_free(sc_mma_pool* p);
+int sc_mma_pool_begin(sc_mma_pool* p, const int32_t* h_sessions, int32_t k, const float* d_enc, const int32_t* h_s_enc);
+int sc_mma_pool_step(sc_mma_pool* p, const int32_t* h_sessions, int32_t k, const int32_t* h_tokens, int32_t tok_stride,
+                     const int32_t* h_n_tokens, const int32_t* h_blocked, int32_t blocked_stride, const int32_t* h_n_blocked,
+                     int32_t* h_out_index, float* h_pchoose, float* d_features);
+int sc_mma_pool_get_stats(sc_mma_pool* p, sc_mma_pool_stats* out, int32_t reset);
+
 int32_t sc_text_max_len(const sc_model* m, const sc_gen_opts* opts, int32_t s_enc);
 int sc_generate_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
                      const sc_gen_opts* opts, const int32_t* h_prefix, int32_t prefix_len, int32_t* h_out_ids,

@@ -121,6 +121,15 @@ class sc_engine_stats(C.Structure):
     ]
 
 
+class sc_mma_pool_opts(C.Structure):
+    _fields_ = [("abi_version", _i), ("sessions", _i), ("max_len", _i), ("s_enc_cap", _i)]
+
+
+class sc_mma_pool_stats(C.Structure):
+    _fields_ = [("self_kv_bytes", C.c_int64), ("cross_kv_bytes", C.c_int64), ("work_bytes", C.c_int64), ("begins", C.c_int64),
+                ("steps", C.c_int64), ("row_steps", C.c_int64)]
+
+
 class sc_unit_extractor_config(C.Structure):
     _fields_ = [
         ("abi_version", _i), ("model_dim", _i), ("heads", _i), ("ffn_dim", _i), ("layers", _i), ("feature_dim", _i), ("fe_layers", _i),
@@ -195,6 +204,11 @@ SIGNATURES = {
     "sc_encode_text": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P]),
     "sc_mma_begin": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
     "sc_mma_step": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    "sc_mma_pool_create": (_P, [_P, C.POINTER(sc_mma_pool_opts)]),
+    "sc_mma_pool_free": (None, [_P]),
+    "sc_mma_pool_begin": (C.c_int, [_P, _P, _i, _P, _P]),
+    "sc_mma_pool_step": (C.c_int, [_P, _P, _i, _P, _i, _P, _P, _i, _P, _P, _P, _P]),
+    "sc_mma_pool_get_stats": (C.c_int, [_P, C.POINTER(sc_mma_pool_stats), _i]),
     "sc_text_max_len": (_i, [_P, C.POINTER(sc_gen_opts), _i]),
     "sc_generate_text": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P]),
     "sc_generate_text_banned": (C.c_int, [_P, _P, _i, _i, _P, C.POINTER(sc_gen_opts), _P, _i, _P, _P, _P, _P, _P, _P, _i]),

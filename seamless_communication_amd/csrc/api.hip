@@ -223,6 +223,56 @@ int sc_mma_step(sc_model* m, const int32_t* h_tokens, int32_t n_tokens, const in
     SC_API_END
 }
 
+sc_mma_pool* sc_mma_pool_create(sc_model* m, const sc_mma_pool_opts* opts) {
+    try {
+        SC_CHECK(m && opts, "sc_mma_pool_create: null argument");
+        SC_CHECK(opts->abi_version == SC_ABI_VERSION, "sc_mma_pool_create: options ABI version %d != library %d", opts->abi_version,
+                 SC_ABI_VERSION);
+        SC_HIP(hipSetDevice(m->m.device));
+        return reinterpret_cast<sc_mma_pool*>(mma_pool_create(m->m, *opts));
+    } catch (const sc::Error&) {
+    } catch (const std::exception& e) {
+        sc::set_error("sc_mma_pool_create: unexpected C++ exception: %s", e.what());
+    }
+    return nullptr;
+}
+
+void sc_mma_pool_free(sc_mma_pool* p) {
+    if (!p) return;
+    MmaPool* q = reinterpret_cast<MmaPool*>(p);
+    (void)hipSetDevice(mma_pool_device(*q));
+    mma_pool_free(q);
+}
+
+int sc_mma_pool_begin(sc_mma_pool* p, const int32_t* h_sessions, int32_t k, const float* d_enc, const int32_t* h_s_enc) {
+    SC_API_BEGIN
+    SC_CHECK(p && h_sessions && d_enc && h_s_enc, "sc_mma_pool_begin: null argument");
+    MmaPool& q = *reinterpret_cast<MmaPool*>(p);
+    SC_HIP(hipSetDevice(mma_pool_device(q)));
+    mma_pool_begin(q, h_sessions, k, d_enc, h_s_enc);
+    SC_API_END
+}
+
+int sc_mma_pool_step(sc_mma_pool* p, const int32_t* h_sessions, int32_t k, const int32_t* h_tokens, int32_t tok_stride,
+                     const int32_t* h_n_tokens, const int32_t* h_blocked, int32_t blocked_stride, const int32_t* h_n_blocked,
+                     int32_t* h_out_index, float* h_pchoose, float* d_features) {
+    SC_API_BEGIN
+    SC_CHECK(p && h_sessions && h_tokens && h_n_tokens && h_out_index && h_pchoose && d_features && (!h_blocked || h_n_blocked),
+             "sc_mma_pool_step: null argument");
+    MmaPool& q = *reinterpret_cast<MmaPool*>(p);
+    SC_HIP(hipSetDevice(mma_pool_device(q)));
+    mma_pool_step(q, h_sessions, k, h_tokens, tok_stride, h_n_tokens, h_blocked, blocked_stride, h_n_blocked, h_out_index, h_pchoose,
+                  d_features);
+    SC_API_END
+}
+
+int sc_mma_pool_get_stats(sc_mma_pool* p, sc_mma_pool_stats* out, int32_t reset) {
+    SC_API_BEGIN
+    SC_CHECK(p && out, "sc_mma_pool_get_stats: null argument");
+    mma_pool_stats(*reinterpret_cast<MmaPool*>(p), out, reset != 0);
+    SC_API_END
+}
+
 int32_t sc_text_max_len(const sc_model* m, const sc_gen_opts* opts, int32_t s_enc) {
     return (m && opts) ? text_max_len(m->m, *opts, s_enc) : -1;
 }

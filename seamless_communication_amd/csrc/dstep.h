@@ -8,6 +8,13 @@
 
 namespace sc {
 
+struct PoolStep {  // what a step of the streaming session pool adds to the slot-mode chain (StepCtx::pool)
+    bool capture = false;       // the call's last step: keep the p_choose hook's inputs
+    float* hq = nullptr;        // [layers][slots][M]
+    const int* feat_row = nullptr;  // [slots] row of `features` slot b's decoder output goes to
+    float* features = nullptr;  // the caller's packed [sum n_tokens][M]
+};
+
 struct StepCtx {
     int nb = 0, cap = 0, s_enc = 0;
     int* d_pos = nullptr;
@@ -69,7 +76,19 @@ struct StepCtx {
     int* pos_row = nullptr;
     int* limit_row = nullptr;
     int* prefix_row = nullptr;
+    // streaming session pool (mma_pool.hip): a slot-mode step without generation rules.  The step is never projected; its
+    // closing launch (launch_pool_close) takes engine_finalize_kernel's place, and a step with `capture` keeps every layer's
+    // normed cross-attention input of the live slots for the row-batched p_choose hook.  null: not a pool step.
+    const PoolStep* pool = nullptr;
 };
+
+// the pool's closing launch: slot b < *d_rows copies its decoder output hN[b] into row feat_row[b] of the caller's packed
+// feature matrix and advances pos_row of its row state (nothing else: no EOS rule, no score)
+void launch_pool_close(const float* hN, const int2* slot_rp, const int* d_rows, int* pos_row, const int* feat_row, float* features,
+                       int slots, int M, hipStream_t s);
+// out[b] = LayerNorm(x[b]) of the k-group-major residual stream as fp32 rows [slots][M], live slots only (ln3_kernel's arithmetic)
+void launch_pool_capture_ln(const float* xg, int XRB, const float* gamma, const float* beta, float* out, int slots, int M,
+                            const int* d_rows, hipStream_t s);
 
 // ---- the step chain (model_dstep.hip) ---------------------------------------------------------------------------------
 DecStack unity_stack(const Model& m);

@@ -356,6 +356,17 @@ void run_encode_speech_ragged(Model& m, const float* d_fbank, int n, int t_frame
 void run_mma_begin(Model& m, const float* d_enc, int s_enc, int max_len);
 void run_mma_step(Model& m, const int32_t* h_tokens, int n_tokens, const int32_t* h_blocked, int n_blocked, int32_t* out_index,
                   float* h_pchoose, float* d_features);
+// Streaming session pool (mma_pool.hip): N sessions of the monotonic decoder on one row-group step chain in slot mode.
+// The pool lives on m's stream and scratch pool and has to go before m.
+struct MmaPool;
+MmaPool* mma_pool_create(Model& m, const sc_mma_pool_opts& o);
+void mma_pool_free(MmaPool* p);
+int mma_pool_device(const MmaPool& p);
+void mma_pool_begin(MmaPool& p, const int32_t* h_sessions, int k, const float* d_enc, const int32_t* h_s_enc);
+void mma_pool_step(MmaPool& p, const int32_t* h_sessions, int k, const int32_t* h_tokens, int tok_stride, const int32_t* h_n_tokens,
+                   const int32_t* h_blocked, int blocked_stride, const int32_t* h_n_blocked, int32_t* h_out_index, float* h_pchoose,
+                   float* d_features);
+void mma_pool_stats(MmaPool& p, sc_mma_pool_stats* out, bool reset);
 int text_to_char_seqs_host(int vocab, const int32_t* tok_len, const uint8_t* starts_space, const uint8_t* is_punct,
                            const int64_t* offs, const int32_t* ids, int pad_idx, int unk_idx, int eos_idx, const int32_t* text_seqs,
                            int n, int s_text, int32_t* out_char_lens, int32_t* out_char_ids, int cap, int32_t* out_seq_lens);

@@ -580,6 +580,10 @@ void decoder_step3(Model& m, StepCtx& c, bool project, const DecStack& W) {
         a.slot_lane = c.slot_lane;
         launch_dattn(a, /*cross=*/false, m.stream);
         out_resid(l.self_out);
+        // session pool, p_choose step: the query projection below normalises inside the product, so the normed
+        // cross-attention input (monotonic_decoder_layer.py:170-172) of the live slots is written out by a launch of its own
+        if (c.pool && c.pool->capture)
+            launch_pool_capture_ln(c.xg, c.rb, l.cross_ln.g, l.cross_ln.b, c.pool->hq + (int64_t)li * nb * M, nb, M, c.d_rows, m.stream);
         // encoder-decoder attention: the query projection applies its LayerNorm itself
         {
             Gemv3Args q;
@@ -654,6 +658,11 @@ void decoder_step3(Model& m, StepCtx& c, bool project, const DecStack& W) {
         }
         launch_argmax_finalize(c.am_part, vocab3_groups(nb), nb, c.am_eos_logit, c.d_pos, c.force_eos_step, W.pad_idx, W.eos_idx,
                                c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len, c.d_score, m.stream, c.d_prompt_len);
+    }
+    if (c.pool) {  // session pool: per-slot positions, decoder outputs into the caller's packed rows; the caller projects
+        SC_CHECK(c.slot_rp && c.d_rows && c.pos_row && !project, "decoder step: a pool step runs in slot mode and is not projected here");
+        launch_pool_close(c.hN, c.slot_rp, c.d_rows, c.pos_row, c.pool->feat_row, c.pool->features, nb, M, m.stream);
+        return;
     }
     SC_CHECK(!c.slot_rp, "decoder step: the decode engine's step always projects");
     launch_add_i32(c.d_pos, 1, m.stream);

@@ -372,6 +372,13 @@ class HipS2STModel(_Handle):
                                    _ptr(pch), _ptr(feats)), "sc_mma_step")
         return int(index[0]), pch, feats
 
+    def mma_pool(self, sessions: int, max_len: int, s_enc_cap: int) -> "MonotonicDecoderPool":
+        """A streaming session pool on this handle (``sc_mma_pool_*``): ``sessions`` concurrent streams of the monotonic decoder
+        share every decoder step.  Close it before the handle."""
+        if not self.has_monotonic_decoder:
+            raise SeamlessHipError("the model was loaded without a monotonic decoder")
+        return MonotonicDecoderPool(self, sessions, max_len, s_enc_cap)
+
     def _gen_opts(self, beam_size, soft_max_seq_len, hard_max_seq_len, min_seq_len, unk_penalty, use_graph,
                   len_penalty=1.0, normalize_scores=True, no_repeat_ngram_size=0, source_len=0):
         o = _lib.sc_gen_opts()
@@ -843,6 +850,73 @@ class DecodeEngine(_Handle):
             for m in list(self._attached):
                 self.detach(m)
         super().close()
+
+
+class MonotonicDecoderPool(_Handle):
+    """N concurrent sessions of the streaming monotonic decoder on one step chain (``sc_mma_pool_*``, include/seamless_hip.h).
+    Per session the calls are ``mma_begin`` / ``mma_step``; a session's results do not depend on the other sessions, bit for
+    bit.  Not part of the reference API (SimulEval drives one stream)."""
+
+    _free = "sc_mma_pool_free"
+
+    def __init__(self, model: HipS2STModel, sessions: int, max_len: int, s_enc_cap: int) -> None:
+        self.lib = model.lib
+        self._model = model  # the pool runs on the handle's stream: the handle must outlive it
+        self.cfg, self.device = model.cfg, model.device
+        self.sessions, self.max_len, self.s_enc_cap = int(sessions), int(max_len), int(s_enc_cap)
+        o = _lib.sc_mma_pool_opts()
+        o.abi_version = _lib.SC_ABI_VERSION
+        o.sessions, o.max_len, o.s_enc_cap = self.sessions, self.max_len, self.s_enc_cap
+        self.handle = self.lib.sc_mma_pool_create(model.handle, C.byref(o))
+        if not self.handle:
+            raise _failed(self.lib, "sc_mma_pool_create")
+
+    def begin(self, ids: Sequence[int], encs: Sequence[torch.Tensor]) -> None:
+        """``mma_begin`` for the sessions ``ids`` at once: encs[i] (S_i, M) or (1, S_i, M) fp32."""
+        if len(ids) != len(encs):
+            raise ValueError(f"{len(ids)} sessions but {len(encs)} encoder outputs")
+        rows = [(e[0] if e.dim() == 3 else e).to(self.device, torch.float32) for e in encs]
+        lens = _i32([r.shape[0] for r in rows])
+        packed = torch.cat(rows, dim=0).contiguous() if rows else torch.empty(0, self.cfg.model_dim, device=self.device)
+        sid = _i32(list(ids)).reshape(-1)
+        self._model._after_torch()
+        check(self.lib.sc_mma_pool_begin(self.handle, _ptr(sid), len(sid), _ptr(packed), _ptr(lens)), "sc_mma_pool_begin")
+
+    def step(self, ids: Sequence[int], feeds: Sequence[Sequence[int]], blocked: Optional[Sequence[Sequence[int]]] = None):
+        """``mma_step`` for the sessions ``ids`` in shared decoder steps (feeds right-aligned) -> (arg-max ids [k], p_choose
+        (k, layers, heads) of each session's last token, [decoder outputs (len(feeds[i]), M) on the device])."""
+        k = len(ids)
+        if len(feeds) != k or (blocked is not None and len(blocked) != k):
+            raise ValueError(f"{k} sessions but {len(feeds)} feeds" + ("" if blocked is None else f" / {len(blocked)} blocked lists"))
+        n_tok = _i32([len(f) for f in feeds])
+        stride = max(1, int(n_tok.max()) if k else 1)
+        tok = np.zeros((max(k, 1), stride), dtype=np.int32)
+        for j, f in enumerate(feeds):
+            tok[j, : len(f)] = np.asarray(list(f), dtype=np.int32)
+        if blocked is not None and any(len(b) for b in blocked):
+            n_blk = _i32([len(b) for b in blocked])
+            bstride = int(n_blk.max())
+            blk = np.zeros((k, bstride), dtype=np.int32)
+            for j, b in enumerate(blocked):
+                blk[j, : len(b)] = np.asarray(list(b), dtype=np.int32)
+            p_blk, p_nblk = _ptr(blk), _ptr(n_blk)
+        else:
+            bstride, p_blk, p_nblk = 0, _ptr(None), _ptr(None)
+        total = int(n_tok.sum()) if k else 0
+        feats = torch.empty(max(total, 1), self.cfg.model_dim, dtype=torch.float32, device=self.device)
+        index = np.zeros(max(k, 1), dtype=np.int32)
+        pch = np.zeros((max(k, 1), self.cfg.mma_layers, self.cfg.num_heads), dtype=np.float32)
+        sid = _i32(list(ids)).reshape(-1)
+        self._model._after_torch()
+        check(self.lib.sc_mma_pool_step(self.handle, _ptr(sid), k, _ptr(tok), stride, _ptr(n_tok), p_blk, bstride, p_nblk, _ptr(index),
+                                        _ptr(pch), _ptr(feats)), "sc_mma_pool_step")
+        offs = np.concatenate([[0], np.cumsum(n_tok)]).astype(np.int64)
+        return [int(x) for x in index[:k]], pch[:k], [feats[offs[j]: offs[j + 1]] for j in range(k)]
+
+    def stats(self, reset: bool = False) -> Dict[str, int]:
+        st = _lib.sc_mma_pool_stats()
+        check(self.lib.sc_mma_pool_get_stats(self.handle, C.byref(st), int(reset)), "sc_mma_pool_get_stats")
+        return {k: int(getattr(st, k)) for k, _ in st._fields_}
 
 
 def postprocess_alignment(durations: np.ndarray, text_lens: Sequence[int], feat_lens: Sequence[int], reduction_factor: int) -> np.ndarray:

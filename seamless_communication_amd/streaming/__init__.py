@@ -4,10 +4,11 @@ from .agents import (DetokenizerAgent, DualVocoderAgent, MMATextDecoderAgent, NA
                      SeamlessStreamingS2TAgent, SeamlessStreamingS2TDetokAgent,
                      UnitYMMATextDecoderAgent, VocoderAgent, default_args)
 from .backend import HipStreamingBackend
+from .pool import HipPoolBackend, SerialPoolBackend, StreamingSessionPool
 from .simul import EmptySegment, ReadAction, Segment, SpeechSegment, TextSegment, WriteAction
 
 __all__ = [
-    "DetokenizerAgent", "DualVocoderAgent", "EmptySegment", "HipStreamingBackend", "MMATextDecoderAgent", "NARUnitYUnitDecoderAgent", "OfflineWav2VecBertEncoderAgent",
+    "DetokenizerAgent", "DualVocoderAgent", "EmptySegment", "HipPoolBackend", "HipStreamingBackend", "MMATextDecoderAgent", "NARUnitYUnitDecoderAgent", "OfflineWav2VecBertEncoderAgent",
     "OnlineFeatureExtractorAgent", "PretsselVocoderAgent", "ReadAction", "SeamlessS2STAgent", "SeamlessS2STDualVocoderAgent", "SeamlessStreamingS2STAgent", "SeamlessStreamingS2TAgent", "SeamlessStreamingS2TDetokAgent", "Segment",
-    "SpeechSegment", "TextSegment", "UnitYMMATextDecoderAgent", "VocoderAgent", "WriteAction", "default_args",
+    "SerialPoolBackend", "SpeechSegment", "StreamingSessionPool", "TextSegment", "UnitYMMATextDecoderAgent", "VocoderAgent", "WriteAction", "default_args",
 ]

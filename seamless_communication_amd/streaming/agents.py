@@ -403,6 +403,16 @@ _STATISTICS = {
 }
 
 
+class BackendRequest(tuple):
+    """A decoder call the text stage asks for: ("begin", source, room) or ("step", fed, banned).  A step request also carries
+    `pred`, the `run_decoder` argument it was made from (the agent's own backend is asked through `run_decoder`)."""
+
+    def __new__(cls, kind: str, first: Any, second: Any, pred: Optional[List[int]] = None) -> "BackendRequest":
+        self = super().__new__(cls, (kind, first, second))
+        self.pred = pred
+        return self
+
+
 class MMATextDecoderAgent(Stage):
     """Stage 3, text output (S2TT): written pieces joined by blanks."""
 
@@ -425,10 +435,10 @@ class MMATextDecoderAgent(Stage):
         return self.max_len_b + self.max_len_a * int(st.source.shape[1])
 
     # -- one decoder call ------------------------------------------------------------------------------------- #
-    def run_decoder(self, states: DecoderAgentStates, pred_indices: List[int]) -> Tuple[int, float, Tensor]:
-        """Feeds what the decoder has not seen yet in this round - on the first call the language prefix plus all text
-        of earlier rounds (the incremental state is rebuilt per round, online_text_decoder.py:317), afterwards the one
-        token accepted last - and returns (arg-max id, decision statistic, decoder rows (1, fed, M))."""
+    def step_request(self, states: DecoderAgentStates, pred_indices: List[int]) -> "BackendRequest":
+        """What a decoder call feeds - on the first call of a round the language prefix plus all text of earlier rounds (the
+        incremental state is rebuilt per round, online_text_decoder.py:317), afterwards the one token accepted last - and
+        which indices it bans, as the request ("step", fed, banned)."""
         if pred_indices:
             fed = [pred_indices[-1]]
         else:
@@ -437,10 +447,18 @@ class MMATextDecoderAgent(Stage):
             fed = self.prefix_indices + states.target_indices
         # once the source has ended the last four tokens may not be produced again (:232-235)
         banned = (states.target_indices + pred_indices)[-4:] if self.block_ngrams and states.source_finished else ()
-        index, p_choose, rows = self.backend.mma_step(fed, banned)
+        return BackendRequest("step", fed, banned, pred=pred_indices)
+
+    def step_reply(self, index: int, p_choose: Any, rows: Tensor) -> Tuple[int, float, Tensor]:
+        """A backend's answer to a step request -> (arg-max id, decision statistic, decoder rows (1, fed, M))."""
         p = np.asarray(p_choose, dtype=np.float32)[self.p_choose_start_layer:]
         stat = _STATISTICS.get(self.decision_method, _STATISTICS["median"])(p)
         return index, stat, rows.unsqueeze(0)
+
+    def run_decoder(self, states: DecoderAgentStates, pred_indices: List[int]) -> Tuple[int, float, Tensor]:
+        """One decoder call on the agent's own backend: `step_request`, the backend, `step_reply`."""
+        _, fed, banned = self.step_request(states, pred_indices)
+        return self.step_reply(*self.backend.mma_step(fed, banned))
 
     # -- one write round --------------------------------------------------------------------------------------- #
     def _weigh(self, states: DecoderAgentStates, accepted: List[int], guard: Optional[RepeatGuard], index: int, stat: float) -> Tuple[Outcome, int]:
@@ -468,6 +486,27 @@ class MMATextDecoderAgent(Stage):
             return self._round(states)
 
     def _round(self, states: DecoderAgentStates) -> Action:
+        """The round on the agent's own backend."""
+        return self._serve(states, self.round_requests(states))
+
+    def _serve(self, states: DecoderAgentStates, requests):
+        """Answers a request generator from the agent's own backend and returns the generator's value."""
+        reply = None
+        while True:
+            try:
+                ask = requests.send(reply)
+            except StopIteration as done:
+                return done.value
+            if ask[0] == "begin":
+                reply = self.backend.mma_begin(ask[1], ask[2])
+            else:
+                reply = self.run_decoder(states, ask.pred)
+
+    def round_requests(self, states: DecoderAgentStates):
+        """One `policy` call as a generator: it yields the backend calls it needs - ("begin", source, room), answered with
+        anything, and ("step", fed, banned), answered with `step_reply` of the backend's (index, p_choose, rows) - and returns the
+        Action.  `_round` answers from the agent's own backend; the session pool (streaming/pool.py) answers the requests of
+        many agents from shared calls."""
         nothing_heard = len(states.source) == 0
         warming_up = states.source_len < self.min_starting_wait and not states.source_finished
         if nothing_heard or warming_up:
@@ -476,7 +515,7 @@ class MMATextDecoderAgent(Stage):
             return self.close()
 
         room = len(self.prefix_indices) + len(states.target_indices) + self.max_consecutive_writes + 4
-        self.backend.mma_begin(states.source, room)
+        yield BackendRequest("begin", states.source, room)
         states.source_len = states.source.shape[1]
 
         accepted: List[int] = []
@@ -484,7 +523,7 @@ class MMATextDecoderAgent(Stage):
         guard = RepeatGuard(states.target_indices) if self.block_ngrams else None
         outcome, give_back = Outcome.EXTEND, 0
         while outcome is Outcome.EXTEND:
-            index, stat, rows = self.run_decoder(states, accepted)
+            index, stat, rows = yield self.step_request(states, accepted)
             chunks.append(rows)
             outcome, run_len = self._weigh(states, accepted, guard, index, stat)
             if outcome is Outcome.EXTEND:
@@ -505,12 +544,19 @@ class MMATextDecoderAgent(Stage):
         # (:374-376 counts the round's tokens on top of the already extended text)
         ends_stream = ends_stream or len(states.target_indices) + len(accepted) > self.max_len(states)
         states.ngram_block_count *= 0  # a write forgives the guard's trips
-        return self.emit(self.postprocess(states, accepted, ends_stream, features), ends_stream)
+        segment = yield from self.postprocess_requests(states, accepted, ends_stream, features)
+        return self.emit(segment, ends_stream)
 
     def postprocess(self, states: DecoderAgentStates, pred_indices: List[int], finished: bool,
                     decoder_features_out: Optional[Tensor] = None) -> TextSegment:
+        return self._serve(states, self.postprocess_requests(states, pred_indices, finished, decoder_features_out))
+
+    def postprocess_requests(self, states: DecoderAgentStates, pred_indices: List[int], finished: bool,
+                             decoder_features_out: Optional[Tensor] = None):
+        """`postprocess` as a request generator (see `round_requests`); the text chain's asks for nothing."""
         pieces = map(self.text_tokenizer.index_to_token, pred_indices)
         return TextSegment(content=" ".join(pieces), finished=finished, tgt_lang=states.tgt_lang)
+        yield  # a generator without requests
 
 
 class UnitYMMATextDecoderAgent(MMATextDecoderAgent):
@@ -518,15 +564,15 @@ class UnitYMMATextDecoderAgent(MMATextDecoderAgent):
     sentence is closed with "," (fed through the decoder like a written token) so that the partial phrase is synthesised
     with a natural ending (online_text_decoder.py:402-444)."""
 
-    def postprocess(self, states: DecoderAgentStates, pred_indices: List[int], finished: bool,
-                    decoder_features_out: Optional[Tensor] = None) -> TextSegment:
+    def postprocess_requests(self, states: DecoderAgentStates, pred_indices: List[int], finished: bool,
+                             decoder_features_out: Optional[Tensor] = None):
         if not isinstance(decoder_features_out, Tensor):
             raise AssertionError("the unit decoder needs the decoder rows")
         ids = self.prefix_indices + states.target_indices
         open_phrase = bool(pred_indices) and pred_indices[-1] != self.eos_idx
         if open_phrase:
             comma = self.text_tokenizer.token_to_index(",")
-            _, _, comma_rows = self.run_decoder(states, [comma])
+            _, _, comma_rows = yield self.step_request(states, [comma])
             ids = ids + [comma]
             decoder_features_out = torch.cat([decoder_features_out, comma_rows], dim=1)
         out = UnitYTextDecoderOutput(decoder_features=decoder_features_out,
