@@ -16,8 +16,8 @@ extern "C" {
 #endif
 
 /* Introspection: the kernel family a decoder step of `rows` live rows is dispatched to for `caller` (0 greedy text
- * generation, 1 beam search over the text decoder, 2 streaming monotonic decoder, 3 beam search over the v1 unit decoder,
- * 4 teacher-forced stepwise pass): 1 general (split-K skinny products up to 64 rows, tiled GEMMs above), 2 packed-fragment
+ * generation, 1 beam search over the text decoder, 2 streaming monotonic decoder, 3 beam search over the v1 unit
+ * decoder): 1 general (split-K skinny products up to 64 rows, tiled GEMMs above), 2 packed-fragment
  * products, 3 row-group products with fused LayerNorm / residual, 4 the row-group chain cut into row groups (> 64 rows);
  * negative sc_status when the model has no such decoder.  Decided by the predicates the stages themselves use. */
 int sc_decoder_step_family(sc_model* m, int rows, int caller);

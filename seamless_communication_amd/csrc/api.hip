@@ -47,6 +47,57 @@ std::vector<int32_t> op_read_ints(const int32_t* d, size_t n) {  // n ints of de
     if (n) SC_HIP(hipMemcpy(h.data(), d, n * 4, hipMemcpyDeviceToHost));
     return h;
 }
+
+// The caller's lists as the records a GenRequest holds, refused under the entry's name `who` when a count is negative or a
+// pointer is missing.  An empty list is no list (BannedHost::any, BoostHost::any) - nothing else converts one.  What the lists
+// hold is checked by validate_banned_host / check_boost_host, where each entry always made those checks.
+BannedHost banned_arg(const char* who, const int32_t* tokens, const int32_t* offsets, int32_t n) {
+    SC_CHECK(n >= 0 && (n == 0 || (tokens && offsets)), "%s: bad banned list", who);
+    BannedHost b;
+    b.tokens = tokens, b.offsets = offsets, b.n = n;
+    return b;
+}
+BoostHost boost_arg(const char* who, const int32_t* tokens, const int32_t* offsets, int32_t n, float boost) {
+    SC_CHECK(n >= 0 && (n == 0 || (tokens && offsets)), "%s: bad phrase list", who);
+    BoostHost p;
+    p.tokens = tokens, p.offsets = offsets, p.n = n, p.boost = boost;
+    return p;
+}
+
+// The argument checks of sc_generate_text_prompts (shared with sc_generate_text_nbest), on the host before any device work,
+// and what they found: the shortest and the longest prompt, the two lists
+struct PromptsCall {
+    int shortest = 0, longest = 0;
+    BannedHost banned;
+    BoostHost boost;
+};
+PromptsCall check_prompts_call(const char* who, sc_model* m, int32_t n, int32_t s_enc, const sc_gen_opts* opts, const int32_t* h_prompt_rows,
+                               int32_t prompt_stride, const int32_t* h_prompt_lens, const int32_t* h_banned_tokens,
+                               const int32_t* h_banned_offsets, int32_t n_banned, const int32_t* h_boost_tokens, const int32_t* h_boost_offsets,
+                               int32_t n_boost, float boost) {
+    SC_CHECK(n > 0 && prompt_stride >= 1, "%s: n=%d prompt_stride=%d", who, n, prompt_stride);
+    PromptsCall call;
+    call.banned = banned_arg(who, h_banned_tokens, h_banned_offsets, n_banned);
+    call.boost = boost_arg(who, h_boost_tokens, h_boost_offsets, n_boost, boost);
+    const DecStack W = unity_stack(m->m);
+    const int max_len = text_max_len(m->m, *opts, s_enc);
+    call.shortest = prompt_stride;
+    for (int b = 0; b < n; ++b) {
+        const int len = h_prompt_lens[b];
+        SC_CHECK(len >= 1 && len <= prompt_stride, "%s: row %d: prompt length %d outside 1..%d", who, b, len, prompt_stride);
+        SC_CHECK(len < max_len, "%s: row %d: prompt length %d >= effective max length %d", who, b, len, max_len);
+        const int32_t* p = h_prompt_rows + (size_t)b * prompt_stride;
+        for (int t = 0; t < len; ++t) {
+            SC_CHECK(p[t] >= 0 && p[t] < W.vocab, "%s: row %d: prompt token %d outside the vocabulary", who, b, p[t]);
+            SC_CHECK(t == 0 || (p[t] != W.pad_idx && p[t] != W.eos_idx), "%s: row %d: pad / EOS (%d) at prompt position %d", who, b,
+                     p[t], t);
+        }
+        call.shortest = std::min(call.shortest, len), call.longest = std::max(call.longest, len);
+    }
+    validate_banned_host(call.banned.tokens, call.banned.offsets, call.banned.n, W.vocab, nullptr);
+    if (n_boost > 0) check_boost_host(call.boost, W.vocab, W.pad_idx, W.eos_idx);
+    return call;
+}
 }  // namespace
 
 extern "C" {
@@ -118,7 +169,7 @@ int sc_synchronize(sc_model* m) {
 }
 
 int sc_decoder_step_family(sc_model* m, int rows, int caller) {
-    if (!m || rows < 1 || caller < 0 || caller > 4) return SC_ERR_INVALID;
+    if (!m || rows < 1 || caller < 0 || caller > 3) return SC_ERR_INVALID;
     try {
         return decoder_step_family(m->m, rows, caller);
     } catch (...) {
@@ -283,8 +334,11 @@ int sc_generate_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, 
     SC_API_BEGIN
     SC_CHECK(m && d_enc && h_enc_lens && opts && h_prefix && h_out_ids && h_out_lens, "sc_generate_text: null argument");
     SC_HIP(hipSetDevice(m->m.device));
-    run_generate_text(m->m, d_enc, n, s_enc, h_enc_lens, *opts, h_prefix, prefix_len, h_out_ids, h_out_lens, h_out_scores,
-                      d_dec_hidden, nullptr, 0);
+    GenRequest q;
+    q.d_enc = d_enc, q.n = n, q.s_enc = s_enc, q.h_enc_lens = h_enc_lens, q.opts = *opts;
+    q.h_prefix = h_prefix, q.prefix_len = prefix_len;
+    q.h_out_ids = h_out_ids, q.h_out_lens = h_out_lens, q.h_scores = h_out_scores, q.d_dec_hidden = d_dec_hidden;
+    route_generate_text(m->m, q);
     SC_API_END
 }
 
@@ -294,13 +348,14 @@ int sc_generate_text_banned(sc_model* m, const float* d_enc, int32_t n, int32_t 
                             const int32_t* h_banned_offsets, int32_t n_banned) {
     SC_API_BEGIN
     SC_CHECK(m && d_enc && h_enc_lens && opts && h_prefix && h_out_ids && h_out_lens, "sc_generate_text_banned: null argument");
-    SC_CHECK(n_banned >= 0 && (n_banned == 0 || (h_banned_tokens && h_banned_offsets)), "sc_generate_text_banned: bad banned list");
-    BannedHost b;
-    b.tokens = h_banned_tokens, b.offsets = h_banned_offsets, b.n = n_banned;
-    validate_banned_host(b.tokens, b.offsets, b.n, m->m.cfg.text_vocab_size, nullptr);  // refused before any device work
+    GenRequest q;
+    q.banned = banned_arg("sc_generate_text_banned", h_banned_tokens, h_banned_offsets, n_banned);
+    validate_banned_host(q.banned.tokens, q.banned.offsets, q.banned.n, m->m.cfg.text_vocab_size, nullptr);  // refused before any device work
     SC_HIP(hipSetDevice(m->m.device));
-    run_generate_text(m->m, d_enc, n, s_enc, h_enc_lens, *opts, h_prefix, prefix_len, h_out_ids, h_out_lens, h_out_scores,
-                      d_dec_hidden, nullptr, 0, nullptr, n_banned > 0 ? &b : nullptr);
+    q.d_enc = d_enc, q.n = n, q.s_enc = s_enc, q.h_enc_lens = h_enc_lens, q.opts = *opts;
+    q.h_prefix = h_prefix, q.prefix_len = prefix_len;
+    q.h_out_ids = h_out_ids, q.h_out_lens = h_out_lens, q.h_scores = h_out_scores, q.d_dec_hidden = d_dec_hidden;
+    route_generate_text(m->m, q);
     SC_API_END
 }
 
@@ -311,25 +366,18 @@ int sc_generate_text_boosted(sc_model* m, const float* d_enc, int32_t n, int32_t
                              const int32_t* h_boost_offsets, int32_t n_boost, float boost) {
     SC_API_BEGIN
     SC_CHECK(m && d_enc && h_enc_lens && opts && h_prefix && h_out_ids && h_out_lens, "sc_generate_text_boosted: null argument");
-    SC_CHECK(n_banned >= 0 && (n_banned == 0 || (h_banned_tokens && h_banned_offsets)), "sc_generate_text_boosted: bad banned list");
-    SC_CHECK(n_boost >= 0 && (n_boost == 0 || (h_boost_tokens && h_boost_offsets)), "sc_generate_text_boosted: bad phrase list");
-    BannedHost b;
-    b.tokens = h_banned_tokens, b.offsets = h_banned_offsets, b.n = n_banned;
-    BoostHost p;
-    p.tokens = h_boost_tokens, p.offsets = h_boost_offsets, p.n = n_boost, p.boost = boost;
+    GenRequest q;
+    q.banned = banned_arg("sc_generate_text_boosted", h_banned_tokens, h_banned_offsets, n_banned);
+    q.boost = boost_arg("sc_generate_text_boosted", h_boost_tokens, h_boost_offsets, n_boost, boost);
     // refused before any device work (the call itself checks and sorts the list again where it copies it)
-    validate_banned_host(b.tokens, b.offsets, b.n, m->m.cfg.text_vocab_size, nullptr);
-    {
-        const DecStack W = unity_stack(m->m);
-        BoostSorted sorted;
-        const std::string why = boost_list_build(p.tokens, p.offsets, p.n, W.vocab, W.pad_idx, W.eos_idx, sorted);
-        SC_CHECK(why.empty(), "%s", why.c_str());
-        const std::string bad = boost_value_check(boost);
-        SC_CHECK(bad.empty(), "%s", bad.c_str());
-    }
+    const DecStack W = unity_stack(m->m);
+    validate_banned_host(q.banned.tokens, q.banned.offsets, q.banned.n, W.vocab, nullptr);
+    check_boost_host(q.boost, W.vocab, W.pad_idx, W.eos_idx);
     SC_HIP(hipSetDevice(m->m.device));
-    run_generate_text(m->m, d_enc, n, s_enc, h_enc_lens, *opts, h_prefix, prefix_len, h_out_ids, h_out_lens, h_out_scores,
-                      d_dec_hidden, nullptr, 0, nullptr, n_banned > 0 ? &b : nullptr, 0, n_boost > 0 && boost != 0.f ? &p : nullptr);
+    q.d_enc = d_enc, q.n = n, q.s_enc = s_enc, q.h_enc_lens = h_enc_lens, q.opts = *opts;
+    q.h_prefix = h_prefix, q.prefix_len = prefix_len;
+    q.h_out_ids = h_out_ids, q.h_out_lens = h_out_lens, q.h_scores = h_out_scores, q.d_dec_hidden = d_dec_hidden;
+    route_generate_text(m->m, q);
     SC_API_END
 }
 
@@ -341,12 +389,13 @@ int sc_generate_text_sampled(sc_model* m, const float* d_enc, int32_t n, int32_t
     SC_CHECK(m && d_enc && h_enc_lens && opts && sample_opts && h_prefix && h_out_ids && h_out_lens, "sc_generate_text_sampled: null argument");
     SC_CHECK(sample_opts->abi_version == SC_ABI_VERSION, "sc_generate_text_sampled: options ABI version %d != library %d",
              sample_opts->abi_version, SC_ABI_VERSION);
-    SC_CHECK(n_banned >= 0 && (n_banned == 0 || (h_banned_tokens && h_banned_offsets)), "sc_generate_text_sampled: bad banned list");
-    BannedHost b;
-    b.tokens = h_banned_tokens, b.offsets = h_banned_offsets, b.n = n_banned;
+    GenRequest q;
+    q.banned = banned_arg("sc_generate_text_sampled", h_banned_tokens, h_banned_offsets, n_banned);  // (its content: upload_banned)
     SC_HIP(hipSetDevice(m->m.device));
-    run_generate_sampled(m->m, d_enc, n, s_enc, h_enc_lens, *opts, *sample_opts, h_streams, h_prefix, prefix_len, h_out_ids, h_out_lens,
-                         h_out_scores, h_step_lprob, d_dec_hidden, n_banned > 0 ? &b : nullptr);
+    q.d_enc = d_enc, q.n = n, q.s_enc = s_enc, q.h_enc_lens = h_enc_lens, q.opts = *opts;
+    q.h_prefix = h_prefix, q.prefix_len = prefix_len;
+    q.h_out_ids = h_out_ids, q.h_out_lens = h_out_lens, q.h_scores = h_out_scores, q.d_dec_hidden = d_dec_hidden;
+    run_generate_sampled(m->m, q, *sample_opts, h_streams, h_step_lprob);
     SC_API_END
 }
 
@@ -360,8 +409,12 @@ int sc_generate_text_capture(sc_model* m, const float* d_enc, int32_t n, int32_t
     XattnCapture xc;
     xc.d_xattn = d_xattn;
     xc.h_step_lprob = h_step_lprob;
-    run_generate_text(m->m, d_enc, n, s_enc, h_enc_lens, *opts, h_prefix, prefix_len, h_out_ids, h_out_lens, h_out_scores,
-                      d_dec_hidden, nullptr, 0, &xc);
+    GenRequest q;
+    q.d_enc = d_enc, q.n = n, q.s_enc = s_enc, q.h_enc_lens = h_enc_lens, q.opts = *opts;
+    q.h_prefix = h_prefix, q.prefix_len = prefix_len;
+    q.xcap = &xc;
+    q.h_out_ids = h_out_ids, q.h_out_lens = h_out_lens, q.h_scores = h_out_scores, q.d_dec_hidden = d_dec_hidden;
+    route_generate_text(m->m, q);
     SC_API_END
 }
 
@@ -436,11 +489,8 @@ int sc_decode_text(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, co
     SC_API_BEGIN
     SC_CHECK(m && d_enc && h_enc_lens && h_tokens && d_dec_hidden && s_text > 0, "sc_decode_text: bad argument");
     SC_HIP(hipSetDevice(m->m.device));
-    sc_gen_opts o{};
-    o.beam_size = 1;
-    o.min_seq_len = 1;
-    run_generate_text(m->m, d_enc, n, s_enc, h_enc_lens, o, nullptr, 0, nullptr, nullptr, nullptr, d_dec_hidden, h_tokens,
-                      s_text);
+    SC_CHECK(n > 0 && s_enc > 0, "sc_generate_text: empty batch");  // (the text callers have always read for this refusal)
+    run_decode_text_batched(m->m, d_enc, n, s_enc, h_enc_lens, h_tokens, s_text, d_dec_hidden);
     SC_API_END
 }
 
@@ -513,50 +563,13 @@ int sc_generate_text_rows(sc_model* m, const float* d_enc, int32_t n, int32_t s_
         SC_CHECK(h_prefix_rows[i] >= 0 && h_prefix_rows[i] < m->m.cfg.text_vocab_size,
                  "sc_generate_text_rows: prompt token %d (row %d) outside the vocabulary", h_prefix_rows[i], (int)(i / prefix_len));
     SC_HIP(hipSetDevice(m->m.device));
-    run_generate_text(m->m, d_enc, n, s_enc, h_enc_lens, *opts, h_prefix_rows, prefix_len, h_out_ids, h_out_lens, h_out_scores,
-                      d_dec_hidden, nullptr, 0, nullptr, nullptr, /*prefix_stride=*/prefix_len);
+    GenRequest q;
+    q.d_enc = d_enc, q.n = n, q.s_enc = s_enc, q.h_enc_lens = h_enc_lens, q.opts = *opts;
+    q.h_prefix = h_prefix_rows, q.prefix_len = prefix_len, q.prefix_stride = prefix_len;
+    q.h_out_ids = h_out_ids, q.h_out_lens = h_out_lens, q.h_scores = h_out_scores, q.d_dec_hidden = d_dec_hidden;
+    route_generate_text(m->m, q);
     SC_API_END
 }
-
-namespace {
-// The argument checks of sc_generate_text_prompts (shared with sc_generate_text_nbest), on the host before any device work
-void check_prompts_call(const char* who, sc_model* m, int32_t n, int32_t s_enc, const sc_gen_opts* opts, const int32_t* h_prompt_rows,
-                        int32_t prompt_stride, const int32_t* h_prompt_lens, const int32_t* h_banned_tokens, const int32_t* h_banned_offsets,
-                        int32_t n_banned, const int32_t* h_boost_tokens, const int32_t* h_boost_offsets, int32_t n_boost, float boost,
-                        int* out_shortest, int* out_longest) {
-    SC_CHECK(n > 0 && prompt_stride >= 1, "%s: n=%d prompt_stride=%d", who, n, prompt_stride);
-    SC_CHECK(n_banned >= 0 && (n_banned == 0 || (h_banned_tokens && h_banned_offsets)), "%s: bad banned list", who);
-    SC_CHECK(n_boost >= 0 && (n_boost == 0 || (h_boost_tokens && h_boost_offsets)), "%s: bad phrase list", who);
-    const DecStack W = unity_stack(m->m);
-    const int max_len = text_max_len(m->m, *opts, s_enc);
-    int shortest = prompt_stride, longest = 0;
-    for (int b = 0; b < n; ++b) {
-        const int len = h_prompt_lens[b];
-        SC_CHECK(len >= 1 && len <= prompt_stride, "%s: row %d: prompt length %d outside 1..%d", who, b, len, prompt_stride);
-        SC_CHECK(len < max_len, "%s: row %d: prompt length %d >= effective max length %d", who, b, len, max_len);
-        const int32_t* p = h_prompt_rows + (size_t)b * prompt_stride;
-        for (int t = 0; t < len; ++t) {
-            SC_CHECK(p[t] >= 0 && p[t] < W.vocab, "%s: row %d: prompt token %d outside the vocabulary", who, b, p[t]);
-            SC_CHECK(t == 0 || (p[t] != W.pad_idx && p[t] != W.eos_idx), "%s: row %d: pad / EOS (%d) at prompt position %d", who, b,
-                     p[t], t);
-        }
-        shortest = std::min(shortest, len), longest = std::max(longest, len);
-    }
-    BannedHost bh;
-    bh.tokens = h_banned_tokens, bh.offsets = h_banned_offsets, bh.n = n_banned;
-    BoostHost ph;
-    ph.tokens = h_boost_tokens, ph.offsets = h_boost_offsets, ph.n = n_boost, ph.boost = boost;
-    validate_banned_host(bh.tokens, bh.offsets, bh.n, W.vocab, nullptr);
-    if (n_boost > 0) {
-        BoostSorted sorted;
-        const std::string why = boost_list_build(ph.tokens, ph.offsets, ph.n, W.vocab, W.pad_idx, W.eos_idx, sorted);
-        SC_CHECK(why.empty(), "%s", why.c_str());
-        const std::string bad = boost_value_check(boost);
-        SC_CHECK(bad.empty(), "%s", bad.c_str());
-    }
-    *out_shortest = shortest, *out_longest = longest;
-}
-}  // namespace
 
 int sc_generate_text_prompts(sc_model* m, const float* d_enc, int32_t n, int32_t s_enc, const int32_t* h_enc_lens,
                              const sc_gen_opts* opts, const int32_t* h_prompt_rows, int32_t prompt_stride, const int32_t* h_prompt_lens,
@@ -566,19 +579,18 @@ int sc_generate_text_prompts(sc_model* m, const float* d_enc, int32_t n, int32_t
     SC_API_BEGIN
     SC_CHECK(m && d_enc && h_enc_lens && opts && h_prompt_rows && h_prompt_lens && h_out_ids && h_out_lens,
              "sc_generate_text_prompts: null argument");
-    int shortest = 0, longest = 0;
-    check_prompts_call("sc_generate_text_prompts", m, n, s_enc, opts, h_prompt_rows, prompt_stride, h_prompt_lens, h_banned_tokens, h_banned_offsets,
-                       n_banned, h_boost_tokens, h_boost_offsets, n_boost, boost, &shortest, &longest);
-    BannedHost bh;
-    bh.tokens = h_banned_tokens, bh.offsets = h_banned_offsets, bh.n = n_banned;
-    BoostHost ph;
-    ph.tokens = h_boost_tokens, ph.offsets = h_boost_offsets, ph.n = n_boost, ph.boost = boost;
+    const PromptsCall call = check_prompts_call("sc_generate_text_prompts", m, n, s_enc, opts, h_prompt_rows, prompt_stride, h_prompt_lens,
+                                                h_banned_tokens, h_banned_offsets, n_banned, h_boost_tokens, h_boost_offsets, n_boost, boost);
     SC_HIP(hipSetDevice(m->m.device));
+    GenRequest q;
+    q.d_enc = d_enc, q.n = n, q.s_enc = s_enc, q.h_enc_lens = h_enc_lens, q.opts = *opts;
     // equal lengths: sc_generate_text_rows with the lists; otherwise the shortest prompt is echoed for all rows and the per-row
     // lengths go down with the call
-    run_generate_text(m->m, d_enc, n, s_enc, h_enc_lens, *opts, h_prompt_rows, shortest, h_out_ids, h_out_lens, h_out_scores, d_dec_hidden,
-                      nullptr, 0, nullptr, n_banned > 0 ? &bh : nullptr, /*prefix_stride=*/prompt_stride,
-                      n_boost > 0 && boost != 0.f ? &ph : nullptr, shortest == longest ? nullptr : h_prompt_lens);
+    q.h_prefix = h_prompt_rows, q.prefix_len = call.shortest, q.prefix_stride = prompt_stride;
+    q.h_prefix_lens = call.shortest == call.longest ? nullptr : h_prompt_lens;
+    q.banned = call.banned, q.boost = call.boost;
+    q.h_out_ids = h_out_ids, q.h_out_lens = h_out_lens, q.h_scores = h_out_scores, q.d_dec_hidden = d_dec_hidden;
+    route_generate_text(m->m, q);
     SC_API_END
 }
 
@@ -593,27 +605,26 @@ int sc_generate_text_nbest(sc_model* m, const float* d_enc, int32_t n, int32_t s
     SC_CHECK(opts->beam_size >= 1 && opts->beam_size <= 8, "sc_generate_text_nbest: beam_size %d outside 1..8", opts->beam_size);
     SC_CHECK(nbest >= 1 && nbest <= opts->beam_size, "sc_generate_text_nbest: nbest %d outside 1..beam_size (%d)", nbest, opts->beam_size);
     SC_CHECK(opts->no_repeat_ngram_size >= 0, "sc_generate_text_nbest: no_repeat_ngram_size=%d", opts->no_repeat_ngram_size);
-    int shortest = 0, longest = 0;
-    check_prompts_call("sc_generate_text_nbest", m, n, s_enc, opts, h_prompt_rows, prompt_stride, h_prompt_lens, h_banned_tokens, h_banned_offsets,
-                       n_banned, h_boost_tokens, h_boost_offsets, n_boost, boost, &shortest, &longest);
+    const PromptsCall call = check_prompts_call("sc_generate_text_nbest", m, n, s_enc, opts, h_prompt_rows, prompt_stride, h_prompt_lens,
+                                                h_banned_tokens, h_banned_offsets, n_banned, h_boost_tokens, h_boost_offsets, n_boost, boost);
     SC_CHECK(s_enc > 0, "sc_generate_text_nbest: empty batch");
     const DecStack W = unity_stack(m->m);
     const int max_len = text_max_len(m->m, *opts, s_enc);
-    check_generation_limits("sc_generate_text_nbest", *opts, shortest, max_len, W.max_seq_len, n, s_enc, h_enc_lens);
-    BannedHost bh;
-    bh.tokens = h_banned_tokens, bh.offsets = h_banned_offsets, bh.n = n_banned;
-    BoostHost ph;
-    ph.tokens = h_boost_tokens, ph.offsets = h_boost_offsets, ph.n = n_boost, ph.boost = boost;
+    check_generation_limits("sc_generate_text_nbest", *opts, call.shortest, max_len, W.max_seq_len, n, s_enc, h_enc_lens);
     BeamNbestOut out;
     out.nbest = nbest, out.h_ids = h_out_ids, out.h_lens = h_out_lens, out.h_scores = h_out_scores, out.h_counts = h_out_counts;
     out.h_step = h_step_scores;
     SC_HIP(hipSetDevice(m->m.device));
-    // always the host-driven beam loop (run_generate_text's beam branch, whatever the beam size), prompts as sc_generate_text_prompts
+    GenRequest q;
+    q.d_enc = d_enc, q.n = n, q.s_enc = s_enc, q.h_enc_lens = h_enc_lens, q.opts = *opts;
+    q.h_prefix = h_prompt_rows, q.prefix_len = call.shortest, q.prefix_stride = prompt_stride;  // prompts as sc_generate_text_prompts
+    q.h_prefix_lens = call.shortest == call.longest ? nullptr : h_prompt_lens;
+    q.banned = call.banned, q.boost = call.boost;
+    q.nbest = &out;
+    // always the host-driven beam loop (route_generate_text's beam route, whatever the beam size)
     prof::set_tag("dec");
     if (m->m.engine) m->m.engine->expect(m->m, -n);
-    run_generate_beam(m->m, W, d_enc, n, s_enc, h_enc_lens, *opts, h_prompt_rows, shortest, nullptr, nullptr, nullptr, nullptr, max_len,
-                      n_banned > 0 ? &bh : nullptr, /*prefix_stride=*/prompt_stride, n_boost > 0 && boost != 0.f ? &ph : nullptr,
-                      shortest == longest ? nullptr : h_prompt_lens, &out);
+    run_generate_beam(m->m, W, q, max_len);
     SC_API_END
 }
 
@@ -760,7 +771,11 @@ int sc_s2st(sc_model* m, const float* d_fbank, int32_t n, int32_t t_frames, cons
     SC_CHECK(text_cap >= max_len, "sc_s2st: text_cap %d < effective maximum text length %d (sc_text_max_len)", text_cap, max_len);
     std::vector<int32_t> ids((size_t)n * max_len), lens(n);
     Buf<float> hidden(&M.pool, (size_t)n * (max_len - 1) * D);
-    run_generate_text(M, enc, n, s_enc, enc_lens.data(), o, h_prefix, prefix_len, ids.data(), lens.data(), nullptr, hidden, nullptr, 0);
+    GenRequest q;
+    q.d_enc = enc, q.n = n, q.s_enc = s_enc, q.h_enc_lens = enc_lens.data(), q.opts = o;
+    q.h_prefix = h_prefix, q.prefix_len = prefix_len;
+    q.h_out_ids = ids.data(), q.h_out_lens = lens.data(), q.d_dec_hidden = hidden;
+    route_generate_text(M, q);
     // generator.py:281-291: the last column is trimmed, every length shrinks by one
     std::vector<int32_t> text_seqs((size_t)n * (max_len - 1)), text_lens(n);
     for (int b = 0; b < n; ++b) {

@@ -29,7 +29,6 @@ const Knob knob_table[] = {
     {"SC_SPLIT_MODE", 1, "1: Conformer products on the hi fp16 plane only (precision study)"},
     {"SC_DECODER_GEN1", 1, "decoder step on the first-generation kernels"},
     {"SC_DECODER_GEN2", 1, "decoder step on the second-generation chain"},
-    {"SC_DECODE_STEPWISE", 1, "teacher-forced pass step by step instead of one batched forward"},
     {"SC_VOC_SPLIT", 1, "vocoder ResBlock products on both fp16 planes of their activations again (bit 0 wide stages, bit 2 narrow stages); default: hi plane only"},
     // same bits, another schedule / kernel variant
     {"SC_GEMM_GENERAL", 0, "general GEMM kernel instead of the fast path"}, {"SC_GEMM_PF2", 0, "GEMM prefetch depth"},

@@ -1,5 +1,5 @@
 // Decoder-step context, scratch and graph replay shared by every loop that drives the step chain (model_dstep.hip:
-// decoder_step and its three kernel families): greedy generation, the teacher-forced stepwise pass, beam search and the
+// decoder_step and its three kernel families): greedy generation, beam search and the
 // streaming monotonic decoder (model_decoder.hip), sampled generation (model_sample.hip) and the decode engine (engine.hip).
 #pragma once
 #include <mutex>
@@ -201,21 +201,40 @@ struct BannedDevice {
     BannedList list;
     Buf<int> store;
 };
-BannedDevice upload_banned(Model& m, const BannedHost* banned, int V);
+BannedDevice upload_banned(Model& m, const BannedHost& banned, int V);
+// the host checks of a phrase list and its boost (boost_list.h; no device work): the sorted list, or the reason as an error
+BoostSorted check_boost_host(const BoostHost& boost, int V, int pad_idx, int eos_idx);
 // the caller's boost phrases on the device, sorted (checked on the host first; an empty list or boost == 0 makes no device work)
 struct BoostDevice {
     BoostList list;
     Buf<int> store;
 };
-BoostDevice upload_boost(Model& m, const BoostHost* boost, int V, int pad_idx, int eos_idx);
+BoostDevice upload_boost(Model& m, const BoostHost& boost, int V, int pad_idx, int eos_idx);
 // the general step reads one encoder K / V per row: the encoder output [n][s_enc][M] repeated `per_item` times per item
 Buf<float> fan_out_encoder(Model& m, const float* d_enc, int n, int per_item, int s_enc);
 // vocabulary logits of the live rows into c.logits (row stride ldl): the streaming kernel on the packed embedding when v3
 // (it stops at *c.d_rows where the caller set that), the tiled product on c.hN otherwise
 void project_logits(Model& m, StepCtx& c, const DecStack& W, bool v3, int64_t ldl);
+// What both loops set up before their first step: q.n * per_item hypothesis rows on one step chain.  The kernel family and,
+// for the general step, the encoder output fanned out to the rows; the step context's scalars and its integer slices
+// (8 + 5 * rows: position block, d_tok, d_finished, d_out_len, d_enc_lens and one spare [rows] slice); the step scratch under
+// `tuning`; the logits with their row stride; the encoder K / V of every layer, projected once per utterance where the packed
+// step kernels run (c.cross_row_div).  The self-attention caches stay with the caller.
+struct HypRows {
+    StepCtx c;
+    bool packed_step = false;  // family != 1: the rows of an utterance share its encoder K / V
+    bool proj_v3 = false;      // project_logits' v3
+    int64_t ldl = 0;           // logits row stride
+    int* d_spare = nullptr;    // the fifth [rows] slice (beam search: the source row of every beam; sampling: unused)
+    Buf<int> ints;
+    Buf<float> enc_rep, logits;
+    StepScratch scratch;
+    std::vector<Buf<float>> cross;
+};
+void setup_hyp_rows(Model& m, HypRows& h, const DecStack& W, const GenRequest& q, int per_item, int max_len, const StepTuning& tuning);
 // decoder outputs of the chosen hypothesis per utterance (row u * ids_stride of h_ids / h_lens): the reference's
 // teacher-forced pass over text_seqs[:, :-1] (generator.py:281-299) into d_dec_hidden [n][max_len - 1][M]
-void hidden_of_best(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o, const int32_t* h_ids,
-                    const int32_t* h_lens, int ids_stride, int max_len, int pad_idx, float* d_dec_hidden);
+void hidden_of_best(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_ids, const int32_t* h_lens,
+                    int ids_stride, int max_len, int pad_idx, float* d_dec_hidden);
 
 }  // namespace sc

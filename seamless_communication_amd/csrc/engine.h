@@ -7,6 +7,7 @@
 namespace sc {
 
 struct Model;
+struct GenRequest;
 
 class Engine {
    public:
@@ -25,11 +26,10 @@ class Engine {
     // n > 0: handle m announces n rows it will submit; n < 0: up to -n announced rows of m arrived or will not come
     void expect(Model& m, int n);
     void stats(sc_engine_stats* out, bool reset);
-    // greedy generation of n rows through the shared chain; blocks until every row has finished.  Arguments as run_generate_text
-    // (h_prefix_lens: per-row prompt lengths, each within the admit record's capacity; the row state keeps its own length).
-    void generate(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix, int prefix_len,
-                  int max_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, int prefix_stride = 0,
-                  const int32_t* h_prefix_lens = nullptr);
+    // greedy generation of q.n rows through the shared chain; blocks until every row has finished.  The request as
+    // run_generate_text takes it (h_prefix_lens: per-row prompt lengths, each within the admit record's capacity; the row state
+    // keeps its own length).
+    void generate(Model& m, const GenRequest& q, int max_len);
 
    private:
     struct Impl;

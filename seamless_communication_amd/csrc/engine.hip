@@ -454,15 +454,15 @@ void Engine::stats(sc_engine_stats* out, bool reset) {
     if (reset) E.st = sc_engine_stats{};
 }
 
-void Engine::generate(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix, int prefix_len,
-                      int max_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, int prefix_stride,
-                      const int32_t* h_prefix_lens) {
+void Engine::generate(Model& m, const GenRequest& g, int max_len) {
     Impl& E = *p_;
     const sc_config& cfg = m.cfg;
-    const int M = cfg.model_dim, se = E.o.s_enc;
+    const int M = cfg.model_dim, se = E.o.s_enc, n = g.n, s_enc = g.s_enc;
+    const float* d_enc = g.d_enc;
     Request q;
-    q.n = n, q.s_enc = s_enc, q.max_len = max_len, q.prefix_len = prefix_len;
-    q.h_prefix = h_prefix, q.prefix_stride = prefix_stride, q.h_prefix_lens = h_prefix_lens, q.h_enc_lens = h_enc_lens, q.d_hidden = d_dec_hidden;
+    q.n = n, q.s_enc = s_enc, q.max_len = max_len, q.prefix_len = g.prefix_len;
+    q.h_prefix = g.h_prefix, q.prefix_stride = g.prefix_stride, q.h_prefix_lens = g.h_prefix_lens, q.h_enc_lens = g.h_enc_lens;
+    q.d_hidden = g.d_dec_hidden;
     q.ids.assign((size_t)n * max_len, cfg.pad_idx);
     q.lens.assign(n, 0);
     q.scores.assign(n, 0.f);
@@ -518,9 +518,9 @@ void Engine::generate(Model& m, const float* d_enc, int n, int s_enc, const int3
         E.cv_done.wait(lk, [&] { return q.done; });
     }
     SC_CHECK(!q.failed, "sc_generate_text: %s", q.error.c_str());
-    memcpy(h_out_ids, q.ids.data(), q.ids.size() * 4);
-    memcpy(h_out_lens, q.lens.data(), (size_t)n * 4);
-    if (h_scores) memcpy(h_scores, q.scores.data(), (size_t)n * 4);
+    memcpy(g.h_out_ids, q.ids.data(), q.ids.size() * 4);
+    memcpy(g.h_out_lens, q.lens.data(), (size_t)n * 4);
+    if (g.h_scores) memcpy(g.h_scores, q.scores.data(), (size_t)n * 4);
 }
 
 }  // namespace sc

@@ -385,6 +385,7 @@ struct BannedHost {
     const int32_t* tokens = nullptr;
     const int32_t* offsets = nullptr;  // [n + 1]
     int n = 0;
+    bool any() const { return n > 0; }  // an empty list is no list
 };
 void banned_blocked_tokens(const int32_t* seq, int S, const BannedHost& b, std::vector<int32_t>& out);
 // sc_generate_text_boosted: the caller's boost phrases (host CSR, any order; PhraseBoostProcessor) and the boost per matched
@@ -394,12 +395,12 @@ struct BoostHost {
     const int32_t* offsets = nullptr;  // [n + 1]
     int n = 0;
     float boost = 0.f;
+    bool any() const { return n > 0 && boost != 0.f; }  // no phrase or no boost is no list
 };
-void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens,
-                       const sc_gen_opts& o, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
-                       int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, const int32_t* h_forced_tokens,
-                       int forced_len, const XattnCapture* xcap = nullptr, const BannedHost* banned = nullptr, int prefix_stride = 0,
-                       const BoostHost* boost = nullptr, const int32_t* h_prefix_lens = nullptr);
+// Teacher-forced decoder pass over known tokens [n][s_text] as one batched forward into d_hidden [n][s_text][M]
+// (model_decoder.hip; sc_decode_text, and the pass behind a beam search, a sampled call, scoring and language identification)
+void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens, int s_text,
+                             float* d_hidden, bool row_independent = false, float* d_xattn = nullptr, const int32_t* h_seq_lens = nullptr);
 void run_identify_language(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_prefix,
                            int prefix_len, const int32_t* h_cand, int n_cand, float* h_lprob, int32_t* h_best);
 void run_score_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens,
@@ -433,14 +434,42 @@ struct BeamNbestOut {
     int32_t* h_counts = nullptr;  // [n]
     float* h_step = nullptr;      // [n][nbest][max_len]
 };
-void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
-                       const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                       float* d_dec_hidden, int max_len, const BannedHost* banned = nullptr, int prefix_stride = 0,
-                       const BoostHost* boost = nullptr, const int32_t* h_prefix_lens = nullptr, const BeamNbestOut* nbest_out = nullptr);
+// One generation request, as a C entry hands it to the loops.  A plain record: a call site sets the fields it means, the
+// others keep their "not given" value.  Filled once per call; the loops read it and never write it.
+struct GenRequest {
+    // the source: encoder output [n][s_enc][M] on the device, its lengths on the host
+    const float* d_enc = nullptr;
+    int n = 0, s_enc = 0;
+    const int32_t* h_enc_lens = nullptr;
+    sc_gen_opts opts{};
+    // the prompt: prefix_len tokens are echoed for all rows.  prefix_stride 0: every row is fed h_prefix[0 .. prefix_len);
+    // otherwise row b is fed h_prefix[b * prefix_stride + ...] (sc_generate_text_rows).  h_prefix_lens (nullable, with
+    // prefix_stride > 0; sc_generate_text_prompts): row b's prompt is h_prefix_lens[b] tokens long and prefix_len is the
+    // SHORTEST of them - the rows whose prompt is longer are fed the rest of it while the other rows already generate
+    const int32_t* h_prefix = nullptr;
+    int prefix_len = 0, prefix_stride = 0;
+    const int32_t* h_prefix_lens = nullptr;
+    // step processors of the host-driven loops (an empty list is no list: BannedHost::any, BoostHost::any)
+    BannedHost banned;
+    BoostHost boost;
+    const XattnCapture* xcap = nullptr;  // greedy generation only (sc_generate_text_capture)
+    // the outputs: ids [n][max_len], lens [n], scores [n] (nullable) on the host, decoder outputs [n][max_len - 1][M] on the
+    // device (nullable).  Sampled generation writes num_gens hypotheses per utterance into the first three
+    int32_t* h_out_ids = nullptr;
+    int32_t* h_out_lens = nullptr;
+    float* h_scores = nullptr;
+    float* d_dec_hidden = nullptr;
+    // beam search (nullable; sc_generate_text_nbest): every finished hypothesis leaves instead of the best one, and
+    // h_out_ids / h_out_lens / h_scores are not written
+    const BeamNbestOut* nbest = nullptr;
+};
+// The checks of a sc_generate_text* call and its route: the host-driven beam loop (beam_size > 1 or a step processor), the
+// decode engine, or greedy generation on the handle's own chain (run_generate_text)
+void route_generate_text(Model& m, const GenRequest& q);
+// beam search over one decoder stack (the UnitY text decoder or the v1 autoregressive unit decoder)
+void run_generate_beam(Model& m, const DecStack& W, const GenRequest& q, int max_len);
 // sampled generation (model_sample.hip): outputs [n][num_gens][...], hypotheses of an utterance sorted by score
-void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
-                          const sc_sample_opts& so, const uint64_t* h_streams, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
-                          int32_t* h_out_lens, float* h_scores, float* h_step_lprob, float* d_dec_hidden, const BannedHost* banned);
+void run_generate_sampled(Model& m, const GenRequest& q, const sc_sample_opts& so, const uint64_t* h_streams, float* h_step_lprob);
 void run_vocode(Model& m, const int32_t* h_units, int n, int s_units, const int32_t* h_lang, const int32_t* h_spkr,
                 float* d_wav, const int32_t* h_unit_lens = nullptr);
 std::vector<std::vector<int>> plan_length_groups(const std::vector<int>& lens, int overhead_rows, int max_groups);

@@ -23,11 +23,6 @@ int text_max_len(const Model& m, const sc_gen_opts& o, int s_enc) {
     return std::min(max_len, m.cfg.text_max_seq_len);
 }
 
-void run_generate_text_beam(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
-                            const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                            float* d_dec_hidden, const BannedHost* banned = nullptr, int prefix_stride = 0, const BoostHost* boost = nullptr,
-                            const int32_t* h_prefix_lens = nullptr);
-
 // --------------------------------------------------------------------------------------------- //
 // Streaming monotonic decoder (cfg 5).  One row; the state lives in the handle between calls.
 // --------------------------------------------------------------------------------------------- //
@@ -227,7 +222,7 @@ void run_mma_step(Model& m, const int32_t* h_tokens, int n_tokens, const int32_t
     st.pos += n_tokens;
 }
 
-// Buffers of one generation / teacher-forcing run and the step context that points into them.  Greedy generation keeps
+// Buffers of one greedy generation run and the step context that points into them.  Greedy generation keeps
 // one of these per handle ACROSS sc_generate_text calls (Model::dec_session): the captured hipGraph of the step bakes
 // the buffer addresses and the scalar step rules in, so a call with the same key replays the cached executable graph
 // instead of capturing and instantiating a new one (round 1 did that on every call).
@@ -253,7 +248,7 @@ void delete_decode_session(DecodeSession* s) { delete s; }
 namespace {
 
 // allocates every buffer of a run and fills the step context (no device work besides the allocations)
-void setup_session(Model& m, DecodeSession& S, int n, int max_len, int s_enc, bool forced, bool want_hidden, const sc_gen_opts& o) {
+void setup_session(Model& m, DecodeSession& S, int n, int max_len, int s_enc, bool want_hidden, const sc_gen_opts& o) {
     const sc_config& cfg = m.cfg;
     const int M = cfg.model_dim;
     StepCtx& c = S.c;
@@ -278,11 +273,11 @@ void setup_session(Model& m, DecodeSession& S, int n, int max_len, int s_enc, bo
     c.d_lprob = S.fl;
     c.d_score = S.fl.get() + n;
     const DecStack W = unity_stack(m);
-    const int family = choose_family(m, W, n, forced ? 4 : 0);
-    const bool fused_argmax = !forced && n <= 64 && M % 64 == 0;
+    const int family = choose_family(m, W, n, 0);
+    const bool fused_argmax = n <= 64 && M % 64 == 0;
     S.fused_argmax = fused_argmax;
     init_step_scratch(m, S.scratch, c, W, n, family, StepTuning::from_knobs(n), /*wide_always=*/false);
-    S.logits = Buf<float>(m.pp(), (forced || fused_argmax) ? 4 : (size_t)n * cfg.text_vocab_size);
+    S.logits = Buf<float>(m.pp(), fused_argmax ? 4 : (size_t)n * cfg.text_vocab_size);
     c.logits = S.logits;
     if (family >= 2) {
         c.am_ntl = 4;
@@ -290,7 +285,7 @@ void setup_session(Model& m, DecodeSession& S, int n, int max_len, int s_enc, bo
         if (family == 3) {
             // greedy generation: the row-group kernels and the attention skip the row groups / rows behind *d_rows (= n until
             // the live-row compaction of run_generate_text lowers it); the captured step reads the counter on every replay
-            if (!forced) c.d_rows = c.d_rows_greedy;
+            c.d_rows = c.d_rows_greedy;
             c.am_tiles = std::max(c.am_tiles, vocab3_groups(n));
         }
     } else {
@@ -321,15 +316,16 @@ void setup_session(Model& m, DecodeSession& S, int n, int max_len, int s_enc, bo
 // way the reference runs it (generator.py:294-299: `decode(text_seqs[:, :-1], ...)`) - instead of `s_text` single-position
 // steps of ~220 dependent launches each: n * s_text rows through the tiled GEMMs, the multi-query attention kernel with its
 // causal mask for the self-attention, the encoder K / V projected once.  Used behind the beam search (the decoder outputs of
-// the chosen hypotheses feed the T2U model) and by sc_decode_text; SC_DECODE_STEPWISE=1 keeps the step-by-step pass.
-// Same modules in the same order as decoder_step (fairseq2.cpp:979-1094); results agree with the stepwise pass to fp32
-// re-association (tests/test_stages_gpu.py: test_generated_hidden_equals_teacher_forced_pass, 2e-4).
+// the chosen hypotheses feed the T2U model) and by sc_decode_text.
+// Same modules in the same order as decoder_step (fairseq2.cpp:979-1094); results agree with the decoder outputs greedy
+// generation keeps step by step to fp32 re-association (tests/test_stages_gpu.py:
+// test_generated_hidden_equals_teacher_forced_pass, 2e-4).
 // row_independent (sc_score_text): every product is the tiled one whatever the row count, so that an item's rows carry the same
 // bits alone and in any batch; otherwise up to 64 rows take the skinny products (another summation order, linear()).
 // d_xattn (sc_score_text_capture; with h_seq_lens [n], whole sequence lengths): one more launch in the LAST layer, behind its
 // cross_q product and project_cross_kv - the head-summed attention rows of every item (launch_xattn_rows).  Nothing else changes.
 void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_tokens, int s_text,
-                             float* d_hidden, bool row_independent = false, float* d_xattn = nullptr, const int32_t* h_seq_lens = nullptr) {
+                             float* d_hidden, bool row_independent, float* d_xattn, const int32_t* h_seq_lens) {
     const sc_config& cfg = m.cfg;
     const int M = cfg.model_dim, rows = n * s_text, erows = n * s_enc;
     SC_CHECK(s_text <= cfg.text_max_seq_len, "sc_decode_text: %d tokens exceed text_max_seq_len=%d", s_text, cfg.text_max_seq_len);
@@ -534,103 +530,91 @@ void run_identify_language(Model& m, const float* d_enc, int n, int s_enc, const
     SC_HIP(hipStreamSynchronize(m.stream));  // row_idx / h_cand are host memory; outputs complete on return
 }
 
-// forced_tokens != null: teacher-forced pass over the given tokens (no arg-max
-// feedback, hidden states only).  Otherwise greedy generation.
-// prefix_stride: 0 = every row is fed h_prefix[0 .. prefix_len); otherwise row b is fed h_prefix[b * prefix_stride + ...]
-// (sc_generate_text_rows).
-// h_prefix_lens (sc_generate_text_prompts, with prefix_stride > 0): row b's prompt is h_prefix_lens[b] tokens long and
-// prefix_len is the SHORTEST of them: the prompt echo runs that far for all rows, and the rows whose prompt is longer are
-// fed the rest of it by the closing launch of the step (argmax_finalize_kernel), position by position, while the other
-// rows already generate.
-void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens,
-                       const sc_gen_opts& o, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
-                       int32_t* h_out_lens, float* h_scores, float* d_dec_hidden, const int32_t* h_forced_tokens,
-                       int forced_len, const XattnCapture* xcap, const BannedHost* banned, int prefix_stride, const BoostHost* boost,
-                       const int32_t* h_prefix_lens) {
+namespace {
+void run_generate_text(Model& m, const GenRequest& q, int max_len);  // the greedy loop, below
+}
+
+// The checks of a generation call and its route (GenRequest, model.h): the host-driven beam loop, the decode engine, or greedy
+// generation on the handle's own chain.  Rows the handle announced to its engine (Engine::expect) are released exactly once
+// on every route: here where the call leaves for a loop that never uses the engine, by Engine::generate where it takes them.
+void route_generate_text(Model& m, const GenRequest& q) {
     const sc_config& cfg = m.cfg;
-    const int M = cfg.model_dim;
+    const sc_gen_opts& o = q.opts;
+    const int n = q.n, s_enc = q.s_enc;
     SC_CHECK(n > 0 && s_enc > 0, "sc_generate_text: empty batch");
-    SC_CHECK(!h_prefix_lens || (!h_forced_tokens && !xcap && prefix_stride > 0), "sc_generate_text: per-row prompt lengths need per-row prompts");
-    int longest_prefix = prefix_len;
-    if (h_prefix_lens)
+    SC_CHECK(!q.h_prefix_lens || (!q.xcap && q.prefix_stride > 0), "sc_generate_text: per-row prompt lengths need per-row prompts");
+    int longest_prefix = q.prefix_len;
+    if (q.h_prefix_lens)
         for (int b = 0; b < n; ++b) {
-            SC_CHECK(h_prefix_lens[b] >= prefix_len && h_prefix_lens[b] <= prefix_stride, "sc_generate_text: prompt length %d of row %d", h_prefix_lens[b], b);
-            longest_prefix = std::max(longest_prefix, h_prefix_lens[b]);
+            SC_CHECK(q.h_prefix_lens[b] >= q.prefix_len && q.h_prefix_lens[b] <= q.prefix_stride, "sc_generate_text: prompt length %d of row %d",
+                     q.h_prefix_lens[b], b);
+            longest_prefix = std::max(longest_prefix, q.h_prefix_lens[b]);
         }
     prof::set_tag("dec");
-    const bool forced = h_forced_tokens != nullptr;
-    static const bool stepwise_forced = knob::is_set("SC_DECODE_STEPWISE");
-    if (forced && !stepwise_forced && d_dec_hidden) {
-        run_decode_text_batched(m, d_enc, n, s_enc, h_enc_lens, h_forced_tokens, forced_len, d_dec_hidden);
+    SC_CHECK(o.beam_size >= 1, "sc_generate_text: beam_size=%d", o.beam_size);
+    SC_CHECK(o.no_repeat_ngram_size >= 0, "sc_generate_text: no_repeat_ngram_size=%d", o.no_repeat_ngram_size);
+    // the capture covers the greedy step chain only: the reference sums the attention over all beams of its beam batch,
+    // whose layout this library does not reproduce, and the step processors run in the host-driven loop
+    SC_CHECK(!q.xcap || (o.beam_size == 1 && o.no_repeat_ngram_size == 0),
+             "sc_generate_text_capture: greedy generation only (beam_size=%d, no_repeat_ngram_size=%d are not supported)", o.beam_size,
+             o.no_repeat_ngram_size);
+    SC_CHECK(!q.xcap || !q.banned.any(), "sc_generate_text_capture: banned sequences are not supported");
+    SC_CHECK(!q.xcap || !q.boost.any(), "sc_generate_text_capture: boost phrases are not supported");
+    const int max_len = text_max_len(m, o, s_enc);
+    if (o.beam_size > 1 || o.no_repeat_ngram_size > 0 || q.banned.any() || q.boost.any()) {  // step processors run in the host-driven step loop
+        if (m.engine) m.engine->expect(m, -n);
+        run_generate_beam(m, unity_stack(m), q, max_len);
         return;
     }
-    int max_len;
-    if (forced) {
-        max_len = forced_len + 1;  // hidden buffer has max_len-1 = forced_len rows
-    } else {
-        SC_CHECK(o.beam_size >= 1, "sc_generate_text: beam_size=%d", o.beam_size);
-        SC_CHECK(o.no_repeat_ngram_size >= 0, "sc_generate_text: no_repeat_ngram_size=%d", o.no_repeat_ngram_size);
-        // the capture covers the greedy step chain only: the reference sums the attention over all beams of its beam batch,
-        // whose layout this library does not reproduce, and the step processors run in the host-driven loop
-        SC_CHECK(!xcap || (o.beam_size == 1 && o.no_repeat_ngram_size == 0),
-                 "sc_generate_text_capture: greedy generation only (beam_size=%d, no_repeat_ngram_size=%d are not supported)",
-                 o.beam_size, o.no_repeat_ngram_size);
-        const bool has_banned = banned && banned->n > 0;
-        SC_CHECK(!xcap || !has_banned, "sc_generate_text_capture: banned sequences are not supported");
-        const bool has_boost = boost && boost->n > 0 && boost->boost != 0.f;
-        SC_CHECK(!xcap || !has_boost, "sc_generate_text_capture: boost phrases are not supported");
-        if (o.beam_size > 1 || o.no_repeat_ngram_size > 0 || has_banned || has_boost) {  // step processors run in the host-driven step loop
-            if (m.engine) m.engine->expect(m, -n);
-            run_generate_text_beam(m, d_enc, n, s_enc, h_enc_lens, o, h_prefix, prefix_len, h_out_ids, h_out_lens, h_scores,
-                                   d_dec_hidden, has_banned ? banned : nullptr, prefix_stride, has_boost ? boost : nullptr, h_prefix_lens);
-            return;
-        }
-        SC_CHECK(prefix_len >= 1, "sc_generate_text: the prompt must hold at least one token");
-        max_len = text_max_len(m, o, s_enc);
-        SC_CHECK(o.min_seq_len <= max_len, "sc_generate_text: min_seq_len %d > effective max length %d", o.min_seq_len, max_len);
-        SC_CHECK(longest_prefix < max_len, "sc_generate_text: prompt length %d >= effective max length %d", longest_prefix, max_len);
-    }
+    SC_CHECK(q.prefix_len >= 1, "sc_generate_text: the prompt must hold at least one token");
+    SC_CHECK(o.min_seq_len <= max_len, "sc_generate_text: min_seq_len %d > effective max length %d", o.min_seq_len, max_len);
+    SC_CHECK(longest_prefix < max_len, "sc_generate_text: prompt length %d >= effective max length %d", longest_prefix, max_len);
     SC_CHECK(max_len <= 4096 && max_len <= cfg.text_max_seq_len + 1, "sc_generate_text: length %d exceeds the decoder limit", max_len);
     SC_CHECK(s_enc <= 4096, "sc_generate_text: encoder length %d > 4096", s_enc);
     for (int i = 0; i < n; ++i)
-        SC_CHECK(h_enc_lens[i] > 0 && h_enc_lens[i] <= s_enc, "sc_generate_text: enc_lens[%d]=%d out of range", i, h_enc_lens[i]);
+        SC_CHECK(q.h_enc_lens[i] > 0 && q.h_enc_lens[i] <= s_enc, "sc_generate_text: enc_lens[%d]=%d out of range", i, q.h_enc_lens[i]);
 
     // ---- decode engine (sc_engine_attach): the rows join the GPU's shared step chain (engine.hip) -------------------------
     // (a capture call does not fit: it runs on the handle's own chain, whose step the capture launch follows)
-    if (!forced && m.engine && xcap) m.engine->expect(m, -n);
-    if (!forced && m.engine && !xcap) {
+    if (m.engine && q.xcap) m.engine->expect(m, -n);
+    if (m.engine && !q.xcap) {
         // (per-row prompts: the longest one decides - a call with a prompt beyond the admit record's capacity runs on the
         // handle's own chain as a whole)
         if (m.engine->fits(n, s_enc, max_len, longest_prefix, o) && m.engine->has_company()) {
-            m.engine->generate(m, d_enc, n, s_enc, h_enc_lens, h_prefix, prefix_len, max_len, h_out_ids, h_out_lens, h_scores, d_dec_hidden,
-                               prefix_stride, h_prefix_lens);
+            m.engine->generate(m, q, max_len);
             return;
         }
         m.engine->expect(m, -n);  // announced rows that run on the handle's own chain after all
     }
+    run_generate_text(m, q, max_len);
+}
 
-    // ---- the run's buffers: a fresh set for teacher forcing, the handle's cached session for generation -------------
+namespace {
+
+// Greedy generation on the handle's own step chain (route_generate_text made the checks; max_len: the effective length limit).
+// With per-row prompt lengths the prompt echo runs as far as the shortest prompt for all rows, and the rows whose prompt is
+// longer are fed the rest of it by the closing launch of the step (argmax_finalize_kernel), position by position, while the
+// other rows already generate.
+void run_generate_text(Model& m, const GenRequest& q, int max_len) {
+    const sc_config& cfg = m.cfg;
+    const sc_gen_opts& o = q.opts;
+    const XattnCapture* xcap = q.xcap;
+    const int M = cfg.model_dim, n = q.n, s_enc = q.s_enc, prefix_len = q.prefix_len;
+    float* d_dec_hidden = q.d_dec_hidden;
+    // ---- the run's buffers: the handle's cached session ---------------------------------------------------------------
     const bool want_hidden = d_dec_hidden != nullptr;
-    std::unique_ptr<DecodeSession> local;
-    DecodeSession* S = nullptr;
-    if (forced) {
-        local.reset(new DecodeSession());
-        S = local.get();
-        setup_session(m, *S, n, max_len, s_enc, forced, want_hidden, o);
-    } else {
-        DecodeSession* cur = m.dec_session.get();
-        const bool hit = cur && cur->n == n && cur->max_len == max_len && cur->s_enc == s_enc && cur->min_seq_len == o.min_seq_len &&
-                         cur->unk_penalty == o.unk_penalty && cur->has_hidden == (int)want_hidden;
-        if (!hit) {
-            m.dec_session.reset();  // the old buffers go back to the pool first
-            // built aside and installed only when complete: an allocation that throws half way must not leave a session
-            // whose key matches the next call but whose buffers are missing
-            std::unique_ptr<DecodeSession, void (*)(DecodeSession*)> fresh(new DecodeSession(), delete_decode_session);
-            setup_session(m, *fresh, n, max_len, s_enc, forced, want_hidden, o);
-            m.dec_session = std::move(fresh);
-        }
-        S = m.dec_session.get();
+    DecodeSession* cur = m.dec_session.get();
+    const bool hit = cur && cur->n == n && cur->max_len == max_len && cur->s_enc == s_enc && cur->min_seq_len == o.min_seq_len &&
+                     cur->unk_penalty == o.unk_penalty && cur->has_hidden == (int)want_hidden;
+    if (!hit) {
+        m.dec_session.reset();  // the old buffers go back to the pool first
+        // built aside and installed only when complete: an allocation that throws half way must not leave a session
+        // whose key matches the next call but whose buffers are missing
+        std::unique_ptr<DecodeSession, void (*)(DecodeSession*)> fresh(new DecodeSession(), delete_decode_session);
+        setup_session(m, *fresh, n, max_len, s_enc, want_hidden, o);
+        m.dec_session = std::move(fresh);
     }
+    DecodeSession* S = m.dec_session.get();
     StepCtx& c = S->c;
     if (xcap) {
         SC_CHECK(xcap->d_xattn && xcap->h_step_lprob, "sc_generate_text_capture: null capture buffer");
@@ -656,22 +640,21 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
     };
 
     // encoder-decoder K/V once per utterance (fairseq2 caches them in the state bag at step 0)
-    for (int li = 0; li < cfg.dec_layers; ++li) project_cross_kv(m, d_enc, m.dec[li].cross_kv, c.cross_kv[li], n * s_enc);
+    for (int li = 0; li < cfg.dec_layers; ++li) project_cross_kv(m, q.d_enc, m.dec[li].cross_kv, c.cross_kv[li], n * s_enc);
 
     // ---- initial state ------------------------------------------------------------
     std::vector<int32_t> hist((size_t)n * max_len, cfg.pad_idx), init(8 + 5 * n, 0);
-    const int feed_len = forced ? forced_len : prefix_len;
     for (int b = 0; b < n; ++b) {
-        const int own_len = forced ? forced_len : h_prefix_lens ? h_prefix_lens[b] : prefix_len;
-        for (int t = 0; t < own_len; ++t) hist[(size_t)b * max_len + t] = forced ? h_forced_tokens[(size_t)b * forced_len + t] : h_prefix[(size_t)b * prefix_stride + t];
-        init[8 + 4 * n + b] = forced ? 0 : own_len;  // StepCtx::d_prompt_len (a uniform call writes the shared length)
+        const int own_len = q.h_prefix_lens ? q.h_prefix_lens[b] : prefix_len;
+        for (int t = 0; t < own_len; ++t) hist[(size_t)b * max_len + t] = q.h_prefix[(size_t)b * q.prefix_stride + t];
+        init[8 + 4 * n + b] = own_len;  // StepCtx::d_prompt_len (a uniform call writes the shared length)
     }
     init[1] = n;  // live rows (StepCtx::d_rows_greedy)
     for (int b = 0; b < n; ++b) {
         init[8 + b] = hist[(size_t)b * max_len];  // token fed at position 0
         init[8 + n + b] = 0;                      // finished
         init[8 + 2 * n + b] = max_len;            // out_len default (forced EOS at the end)
-        init[8 + 3 * n + b] = h_enc_lens[b];
+        init[8 + 3 * n + b] = q.h_enc_lens[b];
     }
     SC_HIP(hipMemcpyAsync(S->ints.get(), init.data(), init.size() * 4, hipMemcpyHostToDevice, m.stream));
     SC_HIP(hipMemcpyAsync(c.d_hist, hist.data(), hist.size() * 4, hipMemcpyHostToDevice, m.stream));
@@ -685,31 +668,11 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
         SC_HIP(hipMemcpyAsync(S->slot_tab.get(), slot_utt.data(), (size_t)n * 4, hipMemcpyHostToDevice, m.stream));
     }
 
-    // ---- feed the known tokens (prompt echo / teacher forcing) ---------------------
-    // positions 0 .. feed_len-2 are fed without projection; the next input is read from hist.
-    // teacher forcing over more than a few positions (the re-pass behind a beam search: ~40 steps of ~220 launches): the
-    // step is captured once and replayed, like the generation step below
-    StepGraph fgraph;
-    const bool forced_graph = forced && o.use_graph != 0 && c.rb > 0 && feed_len >= 8;
-    auto fed_step = [&]() {
-        if (!forced_graph) {
-            decoder_step(m, c, /*project=*/false);
-            return;
-        }
-        fgraph.ensure(m.stream, [&] { decoder_step(m, c, /*project=*/false); });
-        fgraph.launch(m.stream);
-    };
-    for (int t = 0; t + 1 < feed_len; ++t) {
-        fed_step();
+    // ---- prompt echo: positions 0 .. prefix_len-2 are fed without projection; the next input is read from hist ----
+    for (int t = 0; t + 1 < prefix_len; ++t) {
+        decoder_step(m, c, /*project=*/false);
         if (xcap) capture_node(false);
         SC_HIP(hipMemcpy2DAsync(c.d_tok, 4, c.d_hist + t + 1, (size_t)max_len * 4, 4, n, hipMemcpyDeviceToDevice, m.stream));
-    }
-    if (forced) {
-        fed_step();  // last forced position
-        if (want_hidden)
-            SC_HIP(hipMemcpyAsync(d_dec_hidden, c.dec_hidden, (size_t)n * (max_len - 1) * M * 4, hipMemcpyDeviceToDevice, m.stream));
-        SC_HIP(hipStreamSynchronize(m.stream));
-        return;
     }
 
     // ---- generation loop: step_nr = prefix_len-1 .. max_len-2 -----------------------
@@ -823,11 +786,13 @@ void run_generate_text(Model& m, const float* d_enc, int n, int s_enc, const int
     for (int s = 0; s < n; ++s) {
         const int b = slot_utt[s];
         const int len = lens[s];
-        for (int t = 0; t < max_len; ++t) h_out_ids[(size_t)b * max_len + t] = t < len ? hist[(size_t)s * max_len + t] : cfg.pad_idx;
-        h_out_lens[b] = len;
-        if (h_scores) h_scores[b] = scores[s];
+        for (int t = 0; t < max_len; ++t) q.h_out_ids[(size_t)b * max_len + t] = t < len ? hist[(size_t)s * max_len + t] : cfg.pad_idx;
+        q.h_out_lens[b] = len;
+        if (q.h_scores) q.h_scores[b] = scores[s];
     }
 }
+
+}  // namespace
 
 // --------------------------------------------------------------------------------------------- //
 // Beam search (beam_size > 1): BeamSearchSeq2SeqGenerator as the reference constructs it
@@ -868,15 +833,6 @@ void banned_blocked_tokens(const int32_t* seq, int S, const BannedHost& b, std::
     }
 }
 
-void run_generate_text_beam(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
-                            const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                            float* d_dec_hidden, const BannedHost* banned, int prefix_stride, const BoostHost* boost,
-                            const int32_t* h_prefix_lens) {
-    const DecStack W = unity_stack(m);
-    run_generate_beam(m, W, d_enc, n, s_enc, h_enc_lens, o, h_prefix, prefix_len, h_out_ids, h_out_lens, h_scores, d_dec_hidden,
-                      text_max_len(m, o, s_enc), banned, prefix_stride, boost, h_prefix_lens);
-}
-
 // UnitYT2UModel generation of the v1 models (inference/generator.py:316-336): T2U encoder over the text decoder output,
 // then BeamSearchSeq2SeqGenerator over the unit decoder (unit_opts: beam_size 5, soft_max_seq_len (25, 50),
 // generator.py:183-191) with the prompt [eos, lang] of the unit tokenizer.  Same search as the text decoder, other stack.
@@ -893,12 +849,16 @@ void run_t2u_ar(Model& m, const float* d_dec_hidden, int n, int s_text, const in
     run_t2u_encoder(m, d_dec_hidden, n, s_text, d_tlens, enc, h_text_lens);
     const DecStack W = t2u_ar_stack(m);
     // length rule of the unit generator: min(hard, int(a * S_text) + b), prompt included, capped by the position table
-    sc_gen_opts uo = o;
-    const int src = uo.source_len > 0 ? uo.source_len : s_text;
-    int max_len = uo.soft_max_seq_len_a > 0 ? std::min(uo.hard_max_seq_len, (int)(uo.soft_max_seq_len_a * (float)src) + uo.soft_max_seq_len_b)
-                                            : uo.hard_max_seq_len;
+    const int src = o.source_len > 0 ? o.source_len : s_text;
+    int max_len = o.soft_max_seq_len_a > 0 ? std::min(o.hard_max_seq_len, (int)(o.soft_max_seq_len_a * (float)src) + o.soft_max_seq_len_b)
+                                           : o.hard_max_seq_len;
     max_len = std::min(max_len, W.max_seq_len);
-    run_generate_beam(m, W, enc, n, s_text, h_text_lens, uo, h_prefix, prefix_len, h_out_ids, h_out_lens, h_scores, nullptr, max_len);
+    GenRequest q;
+    q.d_enc = enc, q.n = n, q.s_enc = s_text, q.h_enc_lens = h_text_lens;
+    q.opts = o;
+    q.h_prefix = h_prefix, q.prefix_len = prefix_len;
+    q.h_out_ids = h_out_ids, q.h_out_lens = h_out_lens, q.h_scores = h_scores;
+    run_generate_beam(m, W, q, max_len);
 }
 
 // ---- pieces shared with sampled generation (model_sample.hip) ------------------------------------------------------------
@@ -914,30 +874,35 @@ void check_generation_limits(const char* who, const sc_gen_opts& o, int prefix_l
 }
 
 // BannedSequenceProcessor: the list is checked on the host (before any launch) and copied to the device once per call
-BannedDevice upload_banned(Model& m, const BannedHost* banned, int V) {
+BannedDevice upload_banned(Model& m, const BannedHost& banned, int V) {
     BannedDevice d;
-    if (!banned || banned->n <= 0) return d;
-    validate_banned_host(banned->tokens, banned->offsets, banned->n, V, &d.list.max_len);
-    const int total = banned->offsets[banned->n];
-    d.store = Buf<int>(m.pp(), (size_t)total + banned->n + 1);
-    SC_HIP(hipMemcpyAsync(d.store.get(), banned->tokens, (size_t)total * 4, hipMemcpyHostToDevice, m.stream));
-    SC_HIP(hipMemcpyAsync(d.store.get() + total, banned->offsets, (size_t)(banned->n + 1) * 4, hipMemcpyHostToDevice, m.stream));
+    if (!banned.any()) return d;
+    validate_banned_host(banned.tokens, banned.offsets, banned.n, V, &d.list.max_len);
+    const int total = banned.offsets[banned.n];
+    d.store = Buf<int>(m.pp(), (size_t)total + banned.n + 1);
+    SC_HIP(hipMemcpyAsync(d.store.get(), banned.tokens, (size_t)total * 4, hipMemcpyHostToDevice, m.stream));
+    SC_HIP(hipMemcpyAsync(d.store.get() + total, banned.offsets, (size_t)(banned.n + 1) * 4, hipMemcpyHostToDevice, m.stream));
     SC_HIP(hipStreamSynchronize(m.stream));  // the list is the caller's
     d.list.tokens = d.store.get();
     d.list.offsets = d.store.get() + total;
-    d.list.n = banned->n;
+    d.list.n = banned.n;
     return d;
 }
 
 // PhraseBoostProcessor: the list is checked and sorted on the host (before any launch) and copied to the device once per call
-BoostDevice upload_boost(Model& m, const BoostHost* boost, int V, int pad_idx, int eos_idx) {
-    BoostDevice d;
-    if (!boost || boost->n <= 0 || boost->boost == 0.f) return d;
+BoostSorted check_boost_host(const BoostHost& boost, int V, int pad_idx, int eos_idx) {
     BoostSorted sorted;
-    const std::string why = boost_list_build(boost->tokens, boost->offsets, boost->n, V, pad_idx, eos_idx, sorted);
+    const std::string why = boost_list_build(boost.tokens, boost.offsets, boost.n, V, pad_idx, eos_idx, sorted);
     SC_CHECK(why.empty(), "%s", why.c_str());
-    const std::string bad = boost_value_check(boost->boost);
+    const std::string bad = boost_value_check(boost.boost);
     SC_CHECK(bad.empty(), "%s", bad.c_str());
+    return sorted;
+}
+
+BoostDevice upload_boost(Model& m, const BoostHost& boost, int V, int pad_idx, int eos_idx) {
+    BoostDevice d;
+    if (!boost.any()) return d;
+    const BoostSorted sorted = check_boost_host(boost, V, pad_idx, eos_idx);
     const size_t total = sorted.tokens.size();
     d.store = Buf<int>(m.pp(), total + sorted.n + 1);
     SC_HIP(hipMemcpyAsync(d.store.get(), sorted.tokens.data(), total * 4, hipMemcpyHostToDevice, m.stream));
@@ -947,7 +912,7 @@ BoostDevice upload_boost(Model& m, const BoostHost* boost, int V, int pad_idx, i
     d.list.offsets = d.store.get() + total;
     d.list.n = sorted.n;
     d.list.max_len = sorted.max_len;
-    d.list.beta = boost->boost;
+    d.list.beta = boost.boost;
     return d;
 }
 
@@ -980,7 +945,46 @@ void project_logits(Model& m, StepCtx& c, const DecStack& W, bool v3, int64_t ld
     }
 }
 
-void hidden_of_best(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o, const int32_t* h_ids,
+void setup_hyp_rows(Model& m, HypRows& h, const DecStack& W, const GenRequest& q, int per_item, int max_len, const StepTuning& tuning) {
+    const std::vector<DecoderLayer>& dec_layers = *W.layers;
+    const sc_gen_opts& o = q.opts;
+    const int M = m.cfg.model_dim, V = W.vocab, n = q.n, s_enc = q.s_enc, nb = n * per_item;
+    // the packed-weight step kernels read the encoder K / V of live row r from cache row r / per_item: one projection per
+    // utterance instead of one per hypothesis (5 x fewer bytes to project, to keep and to stream per step at beam 5)
+    const int family = choose_family(m, W, nb, 1);  // (the v1 unit decoder's search decides the same way: callers 1 and 3)
+    h.packed_step = family != 1;
+    if (!h.packed_step) h.enc_rep = fan_out_encoder(m, q.d_enc, n, per_item, s_enc);  // the general step: one encoder K / V per row
+    StepCtx& c = h.c;
+    c.stack = &W;
+    c.nb = nb, c.cap = max_len, c.s_enc = s_enc;
+    c.min_seq_len = o.min_seq_len, c.force_eos_step = max_len - 2, c.unk_penalty = o.unk_penalty;
+    h.ints = Buf<int>(m.pp(), (size_t)8 + 5 * nb);
+    c.d_pos = h.ints;
+    c.d_tok = h.ints.get() + 8;
+    c.d_finished = c.d_tok + nb;
+    c.d_out_len = c.d_finished + nb;
+    c.d_enc_lens = c.d_out_len + nb;
+    h.d_spare = c.d_enc_lens + nb;
+    // packed-weight step kernels up to 64 live rows, the wide third-generation chain up to 512 (the step runs without its
+    // projection here)
+    init_step_scratch(m, h.scratch, c, W, nb, family, tuning);
+    h.logits = Buf<float>(m.pp(), (size_t)nb * (V + 3));
+    c.logits = h.logits;
+    // vocabulary projection of the live rows: the LDS-staged streaming kernel on the packed embedding when the step left
+    // the decoder output as split planes (<= 64 rows: at 60 rows the tiled GEMM needed ~10 ms per step, this one ~0.12)
+    h.proj_v3 = c.rb > 0 && W.embed_p != nullptr && vocab3_supported(nb, V, M);
+    h.ldl = h.proj_v3 ? (int64_t)align_up(V, 4) : V;  // 16-byte aligned rows for the streaming kernel
+    const int cross_rows = h.packed_step ? n : nb;
+    c.cross_row_div = h.packed_step ? per_item : 1;
+    h.cross.reserve(dec_layers.size());
+    for (const DecoderLayer& l : dec_layers) {
+        h.cross.emplace_back(m.pp(), (size_t)cross_rows * s_enc * 2 * M);
+        c.cross_kv.push_back(h.cross.back());
+        project_cross_kv(m, h.packed_step ? q.d_enc : h.enc_rep.get(), l.cross_kv, c.cross_kv.back(), cross_rows * s_enc);
+    }
+}
+
+void hidden_of_best(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const int32_t* h_ids,
                     const int32_t* h_lens, int ids_stride, int max_len, int pad_idx, float* d_dec_hidden) {
     const int M = m.cfg.model_dim;
     int longest = 0;
@@ -990,7 +994,7 @@ void hidden_of_best(Model& m, const float* d_enc, int n, int s_enc, const int32_
     for (int u = 0; u < n; ++u)
         for (int t = 0; t < fl && t < h_lens[(size_t)u * ids_stride]; ++t) forced[(size_t)u * fl + t] = h_ids[(size_t)u * ids_stride * max_len + t];
     Buf<float> hid(m.pp(), (size_t)n * fl * M);
-    run_generate_text(m, d_enc, n, s_enc, h_enc_lens, o, nullptr, 0, nullptr, nullptr, nullptr, hid, forced.data(), fl);
+    run_decode_text_batched(m, d_enc, n, s_enc, h_enc_lens, forced.data(), fl, hid);
     SC_HIP(hipMemsetAsync(d_dec_hidden, 0, (size_t)n * (max_len - 1) * M * 4, m.stream));
     SC_HIP(hipMemcpy2DAsync(d_dec_hidden, (size_t)(max_len - 1) * M * 4, hid.get(), (size_t)fl * M * 4, (size_t)fl * M * 4, n,
                             hipMemcpyDeviceToDevice, m.stream));
@@ -998,18 +1002,18 @@ void hidden_of_best(Model& m, const float* d_enc, int n, int s_enc, const int32_
 }
 
 // Beam search over one decoder stack (the UnitY text decoder or the v1 autoregressive unit decoder).
-void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
-                       const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids, int32_t* h_out_lens, float* h_scores,
-                       float* d_dec_hidden, int max_len, const BannedHost* banned, int prefix_stride, const BoostHost* boost,
-                       const int32_t* h_prefix_lens, const BeamNbestOut* nbest_out) {
-    // nbest_out (nullable; sc_generate_text_nbest): every finished hypothesis leaves instead of the best one - the score history
-    // (BeamHistArgs) exists only then, and h_out_ids / h_out_lens / h_scores are not written.
-    // prefix_stride: 0 = one prompt for all; otherwise utterance u's prompt is h_prefix[u * prefix_stride + ...], fed to each of its beams
-    // h_prefix_lens (nullable; sc_generate_text_prompts): utterance u's prompt is h_prefix_lens[u] tokens long and prefix_len is
-    // the SHORTEST of them.  The host echo below runs that far; from there an utterance that is still inside its prompt is
+void run_generate_beam(Model& m, const DecStack& W, const GenRequest& q, int max_len) {
+    // The request's fields: GenRequest (model.h).  The score history (BeamHistArgs) exists only with q.nbest.  A per-row prompt is
+    // fed to each beam of its utterance.  With per-row prompt lengths the host echo below runs as far as the shortest prompt;
+    // from there an utterance that is still inside its prompt is
     // handled on the device (beam_prompt_kernel): each of its beams continues itself with the known token and adds that
     // token's raw log-probability - the echo's bits, added in the echo's order - while the candidate search and the step
     // processors leave the utterance alone; its "beam 0 only" step is the one at its own prompt's end.
+    const sc_gen_opts& o = q.opts;
+    const int n = q.n, s_enc = q.s_enc, prefix_len = q.prefix_len, prefix_stride = q.prefix_stride;
+    const int32_t *h_prefix = q.h_prefix, *h_prefix_lens = q.h_prefix_lens, *h_enc_lens = q.h_enc_lens;
+    const BeamNbestOut* nbest_out = q.nbest;
+    float* d_dec_hidden = q.d_dec_hidden;
     int longest_prefix = prefix_len;
     if (h_prefix_lens) {
         SC_CHECK(prefix_stride > 0, "sc_generate_text: per-row prompt lengths need per-row prompts");
@@ -1030,47 +1034,22 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
     SC_CHECK(!want_hist || (nbest_out->nbest >= 1 && nbest_out->nbest <= B && !d_dec_hidden), "sc_generate_text_nbest: nbest %d outside 1..%d",
              want_hist ? nbest_out->nbest : 0, B);
     check_generation_limits("sc_generate_text", o, prefix_len, max_len, W.max_seq_len, n, s_enc, h_enc_lens);
-    const BannedDevice banned_dev = upload_banned(m, banned, V);
+    const BannedDevice banned_dev = upload_banned(m, q.banned, V);
     const BannedList& bl = banned_dev.list;
-    const BoostDevice boost_dev = upload_boost(m, boost, V, W.pad_idx, W.eos_idx);
+    const BoostDevice boost_dev = upload_boost(m, q.boost, V, W.pad_idx, W.eos_idx);
     const BoostList& bo = boost_dev.list;
     const float len_penalty = o.len_penalty;
     const bool normalize = o.normalize_scores != 0;
 
-    // the packed-weight step kernels read the encoder K / V of live row r from cache row r / beams: one projection per
-    // utterance instead of one per beam (5 x fewer bytes to project, to keep and to stream per step)
-    const int family = choose_family(m, W, nb, 1);  // (the v1 unit decoder's search decides the same way: callers 1 and 3)
-    const bool packed_step = family != 1;
-    Buf<float> enc_rep;  // the general step: the encoder output fanned out to the beams
-    if (!packed_step) enc_rep = fan_out_encoder(m, d_enc, n, B, s_enc);
-
-    StepCtx c;
-    c.stack = &W;
-    c.nb = nb;
-    c.cap = max_len;
-    c.s_enc = s_enc;
-    c.min_seq_len = o.min_seq_len;
-    c.force_eos_step = max_len - 2;
-    c.unk_penalty = o.unk_penalty;
-    Buf<int> ints(m.pp(), (size_t)8 + 5 * nb);
-    c.d_pos = ints;
-    c.d_tok = ints.get() + 8;
-    c.d_finished = c.d_tok + nb;
-    c.d_out_len = c.d_finished + nb;
-    c.d_enc_lens = c.d_out_len + nb;
-    int* d_src_row = c.d_enc_lens + nb;
-    // packed-weight step kernels up to 64 live rows, the wide third-generation chain up to 512 (the step runs without its
-    // projection here)
-    StepScratch scratch;
-    init_step_scratch(m, scratch, c, W, nb, family, StepTuning::from_knobs(nb));
-    Buf<float> logits(m.pp(), (size_t)nb * (V + 3));
+    // the step context of the beam rows (the beams of an utterance share its encoder K / V on the packed step kernels)
+    HypRows hyp;
+    setup_hyp_rows(m, hyp, W, q, B, max_len, StepTuning::from_knobs(nb));
+    StepCtx& c = hyp.c;
+    const bool packed_step = hyp.packed_step;
+    const int64_t ldl = hyp.ldl;
+    int* d_src_row = hyp.d_spare;
     Buf<float> d_cum(m.pp(), (size_t)nb), d_cand_val(m.pp(), (size_t)n * K), d_pref(m.pp(), (size_t)n);
     Buf<int> d_cand_idx(m.pp(), (size_t)n * K);
-    c.logits = logits;
-    // vocabulary projection of the live rows: the LDS-staged streaming kernel on the packed embedding when the step left
-    // the decoder output as split planes (<= 64 rows: at 60 rows the tiled GEMM needed ~10 ms per step, this one ~0.12)
-    const bool proj_v3 = c.rb > 0 && W.embed_p != nullptr && vocab3_supported(nb, V, M);
-    const int64_t ldl = proj_v3 ? (int64_t)align_up(V, 4) : V;  // logits row stride: 16-byte aligned rows for the streaming kernel
     // self-attention K/V caches of all layers in one allocation, twice (re-ordered from one into the other)
     const int64_t layer_stride = (int64_t)nb * max_len * M;
     // packed step kernels: ONE allocation + an ancestor table - a beam that continues another beam reads that beam's history
@@ -1097,20 +1076,11 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
         }
     };
     bind_caches(kv_cur);
-    std::vector<Buf<float>> cross;
-    cross.reserve(L);
-    const int cross_rows = packed_step ? n : nb;
-    c.cross_row_div = packed_step ? B : 1;
-    for (int li = 0; li < L; ++li) {
-        cross.emplace_back(m.pp(), (size_t)cross_rows * s_enc * 2 * M);
-        c.cross_kv.push_back(cross.back());
-        project_cross_kv(m, packed_step ? d_enc : enc_rep.get(), dec_layers[li].cross_kv, c.cross_kv.back(), cross_rows * s_enc);
-    }
 
     const bool chunked = beam_chunked(V, B, K);  // large vocabulary: candidate search spread over (row, chunk) workgroups
     Buf<float> ws_f(m.pp(), chunked ? beam_ws_floats(nb, K) : 4);
     Buf<int> ws_i(m.pp(), chunked ? beam_ws_ints(nb, K) : 4);
-    auto project_rows = [&]() { project_logits(m, c, W, proj_v3, ldl); };
+    auto project_rows = [&]() { project_logits(m, c, W, hyp.proj_v3, ldl); };
 
     // ---- search state: device resident (sequences, cumulative scores, finished hypotheses, counters) ----------
     std::vector<int32_t> seqs((size_t)nb * max_len, W.pad_idx), init(8 + 5 * nb, 0), tok(nb);
@@ -1125,7 +1095,7 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
         init[8 + r] = pre[0];
         init[8 + 3 * nb + r] = h_enc_lens[r / B];
     }
-    SC_HIP(hipMemcpyAsync(ints.get(), init.data(), init.size() * 4, hipMemcpyHostToDevice, m.stream));
+    SC_HIP(hipMemcpyAsync(hyp.ints.get(), init.data(), init.size() * 4, hipMemcpyHostToDevice, m.stream));
     Buf<int> d_seqs_a(m.pp(), (size_t)nb * max_len), d_seqs_b(m.pp(), (size_t)nb * max_len), d_fin_seq(m.pp(), (size_t)nb * max_len),
         d_fin_len(m.pp(), (size_t)nb), d_state(m.pp(), (size_t)2 * n + 1);
     Buf<float> d_fin_score(m.pp(), (size_t)nb);
@@ -1338,12 +1308,12 @@ void run_generate_beam(Model& m, const DecStack& W, const float* d_enc, int n, i
         }
         const int len = fin_len[u * B + best];
         const int32_t* hs = &fin_seq[(size_t)(u * B + best) * max_len];
-        for (int t = 0; t < max_len; ++t) h_out_ids[(size_t)u * max_len + t] = t < len ? hs[t] : W.pad_idx;
-        h_out_lens[u] = len;
-        if (h_scores) h_scores[u] = fin_score[u * B + best];
+        for (int t = 0; t < max_len; ++t) q.h_out_ids[(size_t)u * max_len + t] = t < len ? hs[t] : W.pad_idx;
+        q.h_out_lens[u] = len;
+        if (q.h_scores) q.h_scores[u] = fin_score[u * B + best];
     }
     // ---- decoder outputs of the chosen hypotheses: the reference's teacher-forced pass (generator.py:281-299)
-    if (d_dec_hidden) hidden_of_best(m, d_enc, n, s_enc, h_enc_lens, o, h_out_ids, h_out_lens, 1, max_len, W.pad_idx, d_dec_hidden);
+    if (d_dec_hidden) hidden_of_best(m, q.d_enc, n, s_enc, h_enc_lens, q.h_out_ids, q.h_out_lens, 1, max_len, W.pad_idx, d_dec_hidden);
 }
 
 }  // namespace sc

@@ -308,17 +308,16 @@ bool step3_wide_eligible(const Model& m, const DecStack& W, int nb) {
 
 // THE dispatch decision (setup_session, run_generate_beam, the streaming step and decoder_step_family's report all call this
 // and nothing else composes the predicates): which kernel family a step of `rows` rows over stack W runs on for caller
-// 0 greedy generation, 1 / 3 beam search (text / v1 unit decoder), 2 the streaming monotonic step, 4 the teacher-forced
-// stepwise pass.  SC_STEP_GENERAL 1, SC_STEP_PACKED 2, SC_STEP_ROWGROUP 3, SC_STEP_ROWGROUP_WIDE 4 (model.h).
+// 0 greedy generation, 1 / 3 beam search (text / v1 unit decoder), 2 the streaming monotonic step.
+// SC_STEP_GENERAL 1, SC_STEP_PACKED 2, SC_STEP_ROWGROUP 3, SC_STEP_ROWGROUP_WIDE 4 (model.h).
 int choose_family(const Model& m, const DecStack& W, int rows, int caller) {
     const int M = m.cfg.model_dim;
     if (caller == 2) return step2_eligible(m, W, 1) ? 2 : 1;
-    if (caller == 0 || caller == 4) {
-        const bool forced = caller == 4;
+    if (caller == 0) {
         // the packed step projects through the packed embedding (a failed pack leaves it null: first-generation step then)
-        const bool gen2 = step2_eligible(m, W, rows) && (forced || W.embed_p != nullptr);
-        const bool fused_argmax = !forced && rows <= 64 && M % 64 == 0;
-        const bool gen3 = gen2 && step3_eligible(m, W, rows) && (forced || (fused_argmax && W.embed_p && vocab3_supported(rows, W.vocab, M)));
+        const bool gen2 = step2_eligible(m, W, rows) && W.embed_p != nullptr;
+        const bool fused_argmax = rows <= 64 && M % 64 == 0;
+        const bool gen3 = gen2 && step3_eligible(m, W, rows) && fused_argmax && vocab3_supported(rows, W.vocab, M);
         if (W.ffn_act == ACT_GELU) return gen3 ? 3 : 1;  // the packed chain's FFN epilogue knows ReLU only
         return gen3 ? 3 : (gen2 ? 2 : 1);
     }
@@ -332,8 +331,8 @@ int choose_family(const Model& m, const DecStack& W, int rows, int caller) {
 
 // Which kernel family a decoder step of `rows` live rows runs on, decided by the SAME predicates the callers use (the
 // dispatch matrix in one place; tests/test_dispatch_gpu.py pins it).  caller: 0 greedy text generation (setup_session),
-// 1 beam search over the text decoder, 2 the streaming monotonic decoder's step, 3 beam search over the v1 unit decoder,
-// 4 teacher-forced stepwise pass.  Returns SC_STEP_GENERAL (1: split-K skinny products up to 64 rows, tiled GEMMs above),
+// 1 beam search over the text decoder, 2 the streaming monotonic decoder's step, 3 beam search over the v1 unit decoder.
+// Returns SC_STEP_GENERAL (1: split-K skinny products up to 64 rows, tiled GEMMs above),
 // SC_STEP_PACKED (2: packed-fragment products, k_dstep.hip), SC_STEP_ROWGROUP (3: row-group products with fused LayerNorm /
 // residual, k_dstep3.hip) or SC_STEP_ROWGROUP_WIDE (4: the same chain cut into row groups, > 64 rows).
 int decoder_step_family(const Model& m, int rows, int caller) {

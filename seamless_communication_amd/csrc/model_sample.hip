@@ -14,13 +14,12 @@
 
 namespace sc {
 
-void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const int32_t* h_enc_lens, const sc_gen_opts& o,
-                          const sc_sample_opts& so, const uint64_t* h_streams, const int32_t* h_prefix, int prefix_len, int32_t* h_out_ids,
-                          int32_t* h_out_lens, float* h_scores, float* h_step_lprob, float* d_dec_hidden, const BannedHost* banned) {
+void run_generate_sampled(Model& m, const GenRequest& q, const sc_sample_opts& so, const uint64_t* h_streams, float* h_step_lprob) {
     const DecStack W = unity_stack(m);
-    const sc_config& cfg = m.cfg;
-    const std::vector<DecoderLayer>& dec_layers = *W.layers;
-    const int M = cfg.model_dim, V = W.vocab, B = so.num_gens, L = (int)dec_layers.size();
+    const sc_gen_opts& o = q.opts;
+    const int n = q.n, s_enc = q.s_enc, prefix_len = q.prefix_len;
+    const int32_t *h_prefix = q.h_prefix, *h_enc_lens = q.h_enc_lens;
+    const int M = m.cfg.model_dim, V = W.vocab, B = so.num_gens, L = (int)W.layers->size();
     // ---- limits, before any device work ---------------------------------------------------------------------------------
     SC_CHECK(n > 0 && s_enc > 0, "sc_generate_text_sampled: empty batch");
     SC_CHECK(B >= 1 && B <= 64, "sc_generate_text_sampled: num_gens %d (1..64)", B);
@@ -33,48 +32,23 @@ void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const 
     const int nb = n * B;
     const int max_len = text_max_len(m, o, s_enc);
     check_generation_limits("sc_generate_text_sampled", o, prefix_len, max_len, W.max_seq_len, n, s_enc, h_enc_lens);
-    const BannedDevice banned_dev = upload_banned(m, banned, V);  // validated here, before any other device work
+    const BannedDevice banned_dev = upload_banned(m, q.banned, V);  // validated here, before any other device work
     const BannedList& bl = banned_dev.list;
     prof::set_tag("dec");
     if (m.engine) m.engine->expect(m, -n);  // never on the decode engine, like the banned-sequence calls
 
     // ---- the step context: hypotheses of an utterance share its encoder K / V; rows never change places ------------------
-    const int family = choose_family(m, W, nb, 1);
-    const bool packed_step = family != 1;
-    Buf<float> enc_rep;  // the general step reads one encoder K / V per row: the encoder output fanned out to the hypotheses
-    if (!packed_step) enc_rep = fan_out_encoder(m, d_enc, n, B, s_enc);
-    StepCtx c;
-    c.stack = &W;
-    c.nb = nb, c.cap = max_len, c.s_enc = s_enc;
-    c.min_seq_len = o.min_seq_len, c.force_eos_step = max_len - 2, c.unk_penalty = o.unk_penalty;
-    Buf<int> ints(m.pp(), (size_t)8 + 4 * nb);
-    c.d_pos = ints;
-    c.d_tok = ints.get() + 8;
-    c.d_finished = c.d_tok + nb;
-    c.d_out_len = c.d_finished + nb;
-    c.d_enc_lens = c.d_out_len + nb;
-    StepScratch scratch;
-    init_step_scratch(m, scratch, c, W, nb, family, StepTuning::defaults(nb));
-    Buf<float> logits(m.pp(), (size_t)nb * (V + 3));
-    c.logits = logits;
-    const bool proj_v3 = c.rb > 0 && W.embed_p != nullptr && vocab3_supported(nb, V, M);
-    const int64_t ldl = proj_v3 ? (int64_t)align_up(V, 4) : V;
+    HypRows hyp;
+    setup_hyp_rows(m, hyp, W, q, B, max_len, StepTuning::defaults(nb));
+    StepCtx& c = hyp.c;
+    const int64_t ldl = hyp.ldl;
     const int64_t layer_stride = (int64_t)nb * max_len * M;
     Buf<float> kv(m.pp(), (size_t)2 * L * layer_stride);
     for (int li = 0; li < L; ++li) {
         c.kcache.push_back(kv.get() + (int64_t)(2 * li) * layer_stride);
         c.vcache.push_back(kv.get() + (int64_t)(2 * li + 1) * layer_stride);
     }
-    std::vector<Buf<float>> cross;
-    cross.reserve(L);
-    const int cross_rows = packed_step ? n : nb;
-    c.cross_row_div = packed_step ? B : 1;  // one encoder K / V per utterance
-    for (int li = 0; li < L; ++li) {
-        cross.emplace_back(m.pp(), (size_t)cross_rows * s_enc * 2 * M);
-        c.cross_kv.push_back(cross.back());
-        project_cross_kv(m, packed_step ? d_enc : enc_rep.get(), dec_layers[li].cross_kv, c.cross_kv.back(), cross_rows * s_enc);
-    }
-    auto project_rows = [&]() { project_logits(m, c, W, proj_v3, ldl); };  // c.d_rows stays null: every row, always
+    auto project_rows = [&]() { project_logits(m, c, W, hyp.proj_v3, ldl); };  // c.d_rows stays null: every row, always
 
     // ---- per-row state, device resident ----------------------------------------------------------------------------------------
     std::vector<int32_t> seqs((size_t)nb * max_len, W.pad_idx), init(8 + 4 * nb, 0), tok(nb), gens(nb);
@@ -97,7 +71,7 @@ void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const 
         std::vector<int32_t> st((size_t)3 * nb + 1, 0);
         std::copy(gens.begin(), gens.end(), st.begin());
         st[3 * nb] = nb;
-        SC_HIP(hipMemcpyAsync(ints.get(), init.data(), init.size() * 4, hipMemcpyHostToDevice, m.stream));
+        SC_HIP(hipMemcpyAsync(hyp.ints.get(), init.data(), init.size() * 4, hipMemcpyHostToDevice, m.stream));
         SC_HIP(hipMemcpyAsync(d_state.get(), st.data(), st.size() * 4, hipMemcpyHostToDevice, m.stream));
         SC_HIP(hipMemcpyAsync(d_seqs.get(), seqs.data(), seqs.size() * 4, hipMemcpyHostToDevice, m.stream));
         SC_HIP(hipMemcpyAsync(d_streams.get(), streams.data(), streams.size() * 8, hipMemcpyHostToDevice, m.stream));
@@ -181,16 +155,16 @@ void run_generate_sampled(Model& m, const float* d_enc, int n, int s_enc, const 
         for (int g = 0; g < B; ++g) {
             const int r = ord[g], dst = u * B + g, len = lens[r];
             for (int t = 0; t < max_len; ++t) {
-                h_out_ids[(size_t)dst * max_len + t] = t < len ? seqs[(size_t)r * max_len + t] : W.pad_idx;
+                q.h_out_ids[(size_t)dst * max_len + t] = t < len ? seqs[(size_t)r * max_len + t] : W.pad_idx;
                 if (h_step_lprob) h_step_lprob[(size_t)dst * max_len + t] = t < len ? slp[(size_t)r * max_len + t] : 0.f;
             }
-            h_out_lens[dst] = len;
-            if (h_scores) h_scores[dst] = score[r];
+            q.h_out_lens[dst] = len;
+            if (q.h_scores) q.h_scores[dst] = score[r];
         }
     }
     // ---- decoder outputs of the best hypothesis per utterance: the teacher-forced pass, as behind a beam search ----------------
     // (slot 0 of every utterance after sorting)
-    if (d_dec_hidden) hidden_of_best(m, d_enc, n, s_enc, h_enc_lens, o, h_out_ids, h_out_lens, B, max_len, W.pad_idx, d_dec_hidden);
+    if (q.d_dec_hidden) hidden_of_best(m, q.d_enc, n, s_enc, h_enc_lens, q.h_out_ids, q.h_out_lens, B, max_len, W.pad_idx, q.d_dec_hidden);
 }
 
 }  // namespace sc

@@ -395,6 +395,23 @@ class HipS2STModel(_Handle):
         o.source_len = int(source_len)
         return o
 
+    def _gen_buffers(self, n: int, max_len: int, want_hidden: bool, per_item: Optional[int] = None):
+        """The result buffers of a generation call -> (ids, lens, scores, hidden): ids (n, max_len) int32, lens (n,), scores (n,)
+        on the host - (n, per_item, ...) for an entry that returns several hypotheses per utterance - and hidden
+        (n, max_len - 1, M) on the device, or None."""
+        rows = (n,) if per_item is None else (n, per_item)
+        hidden = torch.empty(n, max_len - 1, self.cfg.model_dim, dtype=torch.float32, device=self.device) if want_hidden else None
+        return np.zeros(rows + (max_len,), dtype=np.int32), np.zeros(rows, dtype=np.int32), np.zeros(rows, dtype=np.float32), hidden
+
+    @staticmethod
+    def _csr(seqs):
+        """Token sequences -> (tokens, offsets, count), the CSR arrays a C entry takes a list as; None or no sequence ->
+        (None, None, 0), the nulls of a call without the list."""
+        if seqs is None or len(seqs) == 0:
+            return None, None, 0
+        tok, off = _lib.banned_csr(seqs)
+        return tok, off, len(off) - 1
+
     def generate_text(self, enc: torch.Tensor, enc_lens: Sequence[int], prefix: Sequence[int], beam_size: int = 1,
                       soft_max_seq_len=(1, 200), hard_max_seq_len: int = 1024, min_seq_len: int = 1,
                       unk_penalty: float = 0.0, use_graph: bool = True, want_hidden: bool = True,
@@ -424,61 +441,36 @@ class HipS2STModel(_Handle):
                 prefix = np.ascontiguousarray(rows[:, : int(plens[0])])  # equal lengths: today's route (sc_generate_text_rows)
                 ragged = None
         pre = _i32(prefix) if ragged is None else ragged[0]
-        if ragged is not None:
-            o = self._gen_opts(beam_size, soft_max_seq_len, hard_max_seq_len, min_seq_len, unk_penalty, use_graph, len_penalty,
-                               normalize_scores, no_repeat_ngram_size, source_len)
-            max_len = self.lib.sc_text_max_len(self.handle, C.byref(o), s_enc)
-            ids = np.zeros((n, max(1, max_len)), dtype=np.int32)
-            lens = np.zeros(n, dtype=np.int32)
-            scores = np.zeros(n, dtype=np.float32)
-            hidden = torch.empty(n, max(1, max_len - 1), M, dtype=torch.float32, device=self.device) if want_hidden else None
-            el = _i32(enc_lens)
-            b_tok, b_off = _lib.banned_csr(banned_seqs) if has_banned else (None, None)
-            p_tok, p_off = _lib.banned_csr(boost_seqs) if boosted else (None, None)
-            self._after_torch()
-            check(self.lib.sc_generate_text_prompts(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(pre), pre.shape[1],
-                                                    _ptr(ragged[1]), _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden), _ptr(b_tok),
-                                                    _ptr(b_off), 0 if b_off is None else len(b_off) - 1, _ptr(p_tok), _ptr(p_off),
-                                                    0 if p_off is None else len(p_off) - 1, float(boost) if boosted else 0.0),
-                  "sc_generate_text_prompts")
-            return ids, lens, scores, hidden
-        if pre.ndim == 2 and boosted:
-            raise ValueError("boost_seqs take one prompt for all rows (sc_generate_text_boosted)")
-        if pre.ndim == 2 and pre.shape[0] != n:
-            raise ValueError(f"a per-row prefix must be (n={n}, prefix_len), got {pre.shape}")
-        if pre.ndim == 2 and banned_seqs is not None and len(banned_seqs) > 0:
-            raise ValueError("banned_seqs take one prompt for all rows (sc_generate_text_banned)")
+        if ragged is None:
+            if pre.ndim == 2 and boosted:
+                raise ValueError("boost_seqs take one prompt for all rows (sc_generate_text_boosted)")
+            if pre.ndim == 2 and pre.shape[0] != n:
+                raise ValueError(f"a per-row prefix must be (n={n}, prefix_len), got {pre.shape}")
+            if pre.ndim == 2 and has_banned:
+                raise ValueError("banned_seqs take one prompt for all rows (sc_generate_text_banned)")
         o = self._gen_opts(beam_size, soft_max_seq_len, hard_max_seq_len, min_seq_len, unk_penalty, use_graph, len_penalty,
                            normalize_scores, no_repeat_ngram_size, source_len)
         max_len = self.lib.sc_text_max_len(self.handle, C.byref(o), s_enc)
-        ids = np.zeros((n, max_len), dtype=np.int32)
-        lens = np.zeros(n, dtype=np.int32)
-        scores = np.zeros(n, dtype=np.float32)
-        hidden = torch.empty(n, max_len - 1, M, dtype=torch.float32, device=self.device) if want_hidden else None
+        ids, lens, scores, hidden = self._gen_buffers(n, max_len if ragged is None else max(1, max_len), want_hidden)
         el = _i32(enc_lens)
+        b_tok, b_off, n_banned = self._csr(banned_seqs)
+        p_tok, p_off, n_boost = self._csr(boost_seqs if boosted else None)
+        src = (self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o))
+        out = (_ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden))
+        banned, phrases = (_ptr(b_tok), _ptr(b_off), n_banned), (_ptr(p_tok), _ptr(p_off), n_boost)
         self._after_torch()
-        if pre.ndim == 2:
-            check(self.lib.sc_generate_text_rows(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(pre), pre.shape[1],
-                                                 _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden)), "sc_generate_text_rows")
-            return ids, lens, scores, hidden
-        if boosted:
-            b_tok = b_off = None
-            if banned_seqs is not None and len(banned_seqs) > 0:
-                b_tok, b_off = _lib.banned_csr(banned_seqs)
-            p_tok, p_off = _lib.banned_csr(boost_seqs)
-            check(self.lib.sc_generate_text_boosted(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(pre), len(pre),
-                                                    _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden), _ptr(b_tok), _ptr(b_off),
-                                                    0 if b_off is None else len(b_off) - 1, _ptr(p_tok), _ptr(p_off), len(p_off) - 1,
-                                                    float(boost)), "sc_generate_text_boosted")
-            return ids, lens, scores, hidden
-        if banned_seqs is not None and len(banned_seqs) > 0:
-            b_tok, b_off = _lib.banned_csr(banned_seqs)
-            check(self.lib.sc_generate_text_banned(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(pre), len(pre),
-                                                   _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden), _ptr(b_tok), _ptr(b_off),
-                                                   len(b_off) - 1), "sc_generate_text_banned")
-            return ids, lens, scores, hidden
-        check(self.lib.sc_generate_text(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(pre), len(pre),
-                                        _ptr(ids), _ptr(lens), _ptr(scores), _ptr(hidden)), "sc_generate_text")
+        if ragged is not None:
+            check(self.lib.sc_generate_text_prompts(*src, _ptr(pre), pre.shape[1], _ptr(ragged[1]), *out, *banned, *phrases,
+                                                    float(boost) if boosted else 0.0), "sc_generate_text_prompts")
+        elif pre.ndim == 2:
+            check(self.lib.sc_generate_text_rows(*src, _ptr(pre), pre.shape[1], *out), "sc_generate_text_rows")
+        elif boosted:
+            check(self.lib.sc_generate_text_boosted(*src, _ptr(pre), len(pre), *out, *banned, *phrases, float(boost)),
+                  "sc_generate_text_boosted")
+        elif has_banned:
+            check(self.lib.sc_generate_text_banned(*src, _ptr(pre), len(pre), *out, *banned), "sc_generate_text_banned")
+        else:
+            check(self.lib.sc_generate_text(*src, _ptr(pre), len(pre), *out), "sc_generate_text")
         return ids, lens, scores, hidden
 
     def generate_text_nbest(self, enc: torch.Tensor, enc_lens: Sequence[int], prefix, beam_size: int = 5, nbest: Optional[int] = None,
@@ -502,7 +494,6 @@ class HipS2STModel(_Handle):
         if not 1 <= nbest <= beam_size:
             raise ValueError(f"`nbest` must lie in 1..beam_size ({beam_size}), but is {nbest} instead.")
         boosted = boost_seqs is not None and len(boost_seqs) > 0 and float(boost) != 0.0
-        has_banned = banned_seqs is not None and len(banned_seqs) > 0
         ragged = _ragged_prompts(prefix, n, True)
         if ragged is None:
             pre = _i32(prefix)
@@ -515,20 +506,17 @@ class HipS2STModel(_Handle):
         o = self._gen_opts(beam_size, soft_max_seq_len, hard_max_seq_len, min_seq_len, unk_penalty, use_graph, len_penalty,
                            normalize_scores, no_repeat_ngram_size, source_len)
         max_len = max(1, self.lib.sc_text_max_len(self.handle, C.byref(o), s_enc))
-        ids = np.zeros((n, nbest, max_len), dtype=np.int32)
-        lens = np.zeros((n, nbest), dtype=np.int32)
-        scores = np.zeros((n, nbest), dtype=np.float32)
+        ids, lens, scores, _ = self._gen_buffers(n, max_len, False, per_item=nbest)
         counts = np.zeros(n, dtype=np.int32)
         step = np.zeros((n, nbest, max_len), dtype=np.float32) if want_step_scores else None
         el = _i32(enc_lens)
-        b_tok, b_off = _lib.banned_csr(banned_seqs) if has_banned else (None, None)
-        p_tok, p_off = _lib.banned_csr(boost_seqs) if boosted else (None, None)
+        b_tok, b_off, n_banned = self._csr(banned_seqs)
+        p_tok, p_off, n_boost = self._csr(boost_seqs if boosted else None)
         self._after_torch()
         check(self.lib.sc_generate_text_nbest(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), _ptr(rows), rows.shape[1],
                                               _ptr(plens), nbest, _ptr(ids), _ptr(lens), _ptr(scores), _ptr(counts), _ptr(step),
-                                              _ptr(b_tok), _ptr(b_off), 0 if b_off is None else len(b_off) - 1, _ptr(p_tok),
-                                              _ptr(p_off), 0 if p_off is None else len(p_off) - 1, float(boost) if boosted else 0.0),
-              "sc_generate_text_nbest")
+                                              _ptr(b_tok), _ptr(b_off), n_banned, _ptr(p_tok), _ptr(p_off), n_boost,
+                                              float(boost) if boosted else 0.0), "sc_generate_text_nbest")
         return ids, lens, scores, counts, step
 
     def generate_text_sampled(self, enc: torch.Tensor, enc_lens: Sequence[int], prefix: Sequence[int], num_gens: int = 1,
@@ -550,24 +538,19 @@ class HipS2STModel(_Handle):
         so.top_p, so.temperature, so.seed = float(top_p), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF
         g = max(1, min(64, int(num_gens)))  # (an invalid num_gens is refused by the call; the buffers only need a sane size)
         max_len = self.lib.sc_text_max_len(self.handle, C.byref(o), s_enc)
-        ids = np.zeros((n, g, max_len), dtype=np.int32)
-        lens = np.zeros((n, g), dtype=np.int32)
-        scores = np.zeros((n, g), dtype=np.float32)
+        ids, lens, scores, hidden = self._gen_buffers(n, max_len, want_hidden, per_item=g)
         step_lprob = np.zeros((n, g, max_len), dtype=np.float32)
-        hidden = torch.empty(n, max_len - 1, M, dtype=torch.float32, device=self.device) if want_hidden else None
         pre, el = _i32(prefix), _i32(enc_lens)
         st = None
         if streams is not None:
             st = np.ascontiguousarray(np.asarray([int(s) & 0xFFFFFFFFFFFFFFFF for s in streams], dtype=np.uint64))
             if st.shape != (n,):
                 raise ValueError(f"`streams` must hold one id per utterance ({n}), but holds {st.shape} instead.")
-        b_tok = b_off = None
-        if banned_seqs is not None and len(banned_seqs) > 0:
-            b_tok, b_off = _lib.banned_csr(banned_seqs)
+        b_tok, b_off, n_banned = self._csr(banned_seqs)
         self._after_torch()
         check(self.lib.sc_generate_text_sampled(self.handle, _ptr(enc), n, s_enc, _ptr(el), C.byref(o), C.byref(so), _ptr(st), _ptr(pre),
                                                 len(pre), _ptr(ids), _ptr(lens), _ptr(scores), _ptr(step_lprob), _ptr(hidden), _ptr(b_tok),
-                                                _ptr(b_off), 0 if b_off is None else len(b_off) - 1), "sc_generate_text_sampled")
+                                                _ptr(b_off), n_banned), "sc_generate_text_sampled")
         return ids, lens, scores, step_lprob, hidden
 
     def generate_text_capture(self, enc: torch.Tensor, enc_lens: Sequence[int], prefix: Sequence[int],
@@ -583,12 +566,9 @@ class HipS2STModel(_Handle):
         n, s_enc, M = enc.shape
         o = self._gen_opts(1, soft_max_seq_len, hard_max_seq_len, min_seq_len, unk_penalty, use_graph, 1.0, True, 0, source_len)
         max_len = self.lib.sc_text_max_len(self.handle, C.byref(o), s_enc)
-        ids = np.zeros((n, max_len), dtype=np.int32)
-        lens = np.zeros(n, dtype=np.int32)
-        scores = np.zeros(n, dtype=np.float32)
+        ids, lens, scores, hidden = self._gen_buffers(n, max_len, want_hidden)
         step_lprob = np.zeros((n, max_len), dtype=np.float32)
         xattn = torch.empty(n, max_len, s_enc, dtype=torch.float32, device=self.device)
-        hidden = torch.empty(n, max_len - 1, M, dtype=torch.float32, device=self.device) if want_hidden else None
         pre = _i32(prefix)
         el = _i32(enc_lens)
         self._after_torch()

@@ -24,7 +24,7 @@ def test_dispatch_matrix_tiny_v2():
     hip = common.make_hip_streaming()
     assert [_family(hip, r, GREEDY) for r in (1, 2, 31, 32, 33, 64)] == [3] * 6      # row-group chain up to 64 rows
     assert _family(hip, 65, GREEDY) == 1 and _family(hip, 512, GREEDY) == 1          # greedy above 64 rows: general path
-    assert [_family(hip, r, FORCED) for r in (1, 64)] == [3, 3] and _family(hip, 65, FORCED) == 1
+    assert _family(hip, 1, FORCED) < 0
     assert [_family(hip, r, BEAM) for r in (5, 60, 64)] == [3, 3, 3]                   # beams x utterances = live rows
     assert [_family(hip, r, BEAM) for r in (65, 80, 320, 512)] == [4] * 4             # wide row-group chain
     assert _family(hip, 513, BEAM) == 1                                                # beyond the wide chain: tiled GEMMs
