@@ -907,6 +907,35 @@ int sc_mbr_select(const int32_t* h_ids, int32_t n, int32_t hyp_stride, int32_t l
                   const float* h_weights_or_null, const sc_mbr_opts* opts, double* h_expected, int32_t* h_best, double* h_utility_or_null,
                   int32_t* h_match_or_null);
 
+/* ---- Quality metrics: the two device primitives (added within ABI v10, purely additive).  BLEU, chrF / chrF++
+ * and chrF as an MBR utility are sums of clipped n-gram matches, WER / CER are sums of edit distances; the strings, the tokenizers and
+ * the score formulas are host work (seamless_communication_amd/metrics.py).  Both entries work on a POOL of int32 symbol sequences
+ * (character code points, interned word ids) and a PAIR LIST into it:
+ *   h_symbols  the sequences one behind the other; every symbol >= 0.  May be NULL when the pool holds no symbol.
+ *   h_offsets  [n_seq + 1] int64: sequence s is h_symbols[h_offsets[s] .. h_offsets[s + 1]); h_offsets[0] = 0, never decreasing
+ *   h_pairs    [n_pairs][2] int32: (a, b), both in 0..n_seq-1; a = b is allowed, and any number of pairs may name a sequence
+ * No handle: they run on the CURRENT device, on the default stream, and return when the output is complete.  All pointers are HOST
+ * memory.  n_pairs = 0 is allowed and does nothing.  A pair's result depends on its two sequences only.
+ *
+ * sc_ngram_match: h_match [n_pairs][6] int32.  For the pair (a, b) and n = 1..max_order,
+ *   h_match[p][n - 1] = sum over the distinct n-grams g of a of min(count of g in a, count of g in b);
+ *   the columns of the orders above max_order are 0.  Every column of every pair is written.
+ *   n-grams are compared as symbol tuples (exact for every non-negative int32 symbol).  A sequence holds 0..4096 symbols; each
+ *   sequence that a pair names is sorted once per launch set (a call is one launch set up to 2^21 symbols of named sequences and
+ *   2^20 pairs), and pairs that follow each other's first sequence share its staged row.
+ * SC_ERR_INVALID, before any device work: a null required pointer, n_seq < 1, n_pairs outside 0..2^31-1, offsets that do not
+ * start at 0 or decrease, a negative symbol, a pair index outside 0..n_seq-1, max_order outside 1..6, a sequence of more than 4096
+ * symbols (whether a pair names it or not).
+ *
+ * sc_edit_distance: h_dist [n_pairs] int32: the Levenshtein distance of a and b with unit costs (substitution, insertion and
+ *   deletion 1 each); an empty side gives the other side's length.  The SHORTER sequence of a pair holds at most 8192 symbols, the
+ *   longer one at most 2^20 = 1048576.
+ * SC_ERR_INVALID, before any device work: as above, and a pair whose shorter side exceeds 8192 or whose longer side exceeds 2^20
+ * (the message names the limit). */
+int sc_ngram_match(const int32_t* h_symbols, const int64_t* h_offsets, int32_t n_seq, const int32_t* h_pairs, int64_t n_pairs, int32_t max_order,
+                   int32_t* h_match);
+int sc_edit_distance(const int32_t* h_symbols, const int64_t* h_offsets, int32_t n_seq, const int32_t* h_pairs, int64_t n_pairs, int32_t* h_dist);
+
 /* The kernel-level test hooks (sc_op_*) and the dispatch introspection the parity tests drive are exported too but are NOT part
  * of the drop-in boundary: include/seamless_hip_internal.h. */
 

@@ -307,6 +307,8 @@ SIGNATURES = {
     "sc_vad_windows": (C.c_int64, [C.c_int64, _i]),
     "sc_vad_probs": (C.c_int, [_P, _i, C.c_int64, _P, _i, C.POINTER(sc_vad_opts), _P, C.c_int64, _P, _P]),
     "sc_mbr_select": (C.c_int, [_P, _i, _i, _i, _P, _P, _P, C.POINTER(sc_mbr_opts), _P, _P, _P, _P]),
+    "sc_ngram_match": (C.c_int, [_P, _P, _i, _P, C.c_int64, _i, _P]),
+    "sc_edit_distance": (C.c_int, [_P, _P, _i, _P, C.c_int64, _P]),
     "sc_op_resample_bank": (C.c_int, [_i, _i, C.POINTER(sc_resample_opts), _PI, _PI, _P, _P, C.c_int64]),
     "sc_op_resample_plan": (C.c_int, [_i, _i, C.POINTER(sc_resample_opts), _P]),
     "sc_op_knob": (C.c_int, [C.c_char_p, C.c_int]),

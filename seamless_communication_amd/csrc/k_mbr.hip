@@ -1,10 +1,8 @@
 // Minimum-Bayes-risk selection over sampled hypotheses (sc_mbr_select): the token n-gram F-score of every
 // pair of hypotheses of an utterance, the expected utility of each hypothesis and the arg-max.  No weights, no handle.
 //
-// An n-gram is compared as the tuple of its tokens, never as a packed or hashed key: a hypothesis' start positions p become the
-// 4-tuples (t[p], t[p+1], t[p+2], t[p+3]) of uint32 with a token t stored as t + 1 and 0 behind the end of the hypothesis.  Sorted
-// lexicographically, the tuples are sorted by their first n components for every n <= 4 at once, the n-grams of order n are the
-// tuples whose n-th component is not 0, and equal n-grams are neighbours.
+// An n-gram is compared as the tuple of its tokens, never as a packed or hashed key; the sorted-tuple counting is seq_match.h at
+// tuple width 4 (sc_ngram_match of k_metrics.hip is the same code at width 6).
 // Pass A, one workgroup per hypothesis: the tuples, a bitonic sort in LDS, and per sorted slot and order the number of times the
 // n-gram occurs where the slot is the first of its run (0 elsewhere).  Both go to scratch, hypothesis after hypothesis.
 // Pass B, one workgroup per (utterance, i): row i's tuples and counts in LDS, one wavefront per j; a lane takes a slot of i, finds
@@ -22,6 +20,7 @@
 
 #include "device_util.h"
 #include "handle.h"
+#include "seq_match.h"
 
 namespace sc {
 
@@ -31,7 +30,8 @@ static constexpr int MBR_MAX_N = 4096, MBR_MAX_HYPS = 128, MBR_MAX_LEN = 1024, M
 // one launch set covers consecutive utterances up to these sums (an utterance is never split: at most 128 x 1024 tokens and
 // 128 x 128 pairs), so scratch stays below 200 MB whatever the call holds
 static constexpr int64_t MBR_CHUNK_TOKENS = (int64_t)1 << 22, MBR_CHUNK_PAIRS = (int64_t)1 << 21;
-static constexpr uint32_t MBR_SORT_PAD = 0xffffffffu;  // above every stored token (at most 2^31)
+using MbrTuple = SeqTuple<MBR_MAX_ORDER>;
+using MbrCounts = SeqCounts<MBR_MAX_ORDER, uint32_t>;
 
 struct MbrHyp {  // one hypothesis of a chunk
     uint32_t off;  // first token / first sorted slot
@@ -46,79 +46,27 @@ struct MbrUtt {
     int32_t reserved;
 };
 
-// -1 / 0 / 1: a against b in the first n components
-__device__ __forceinline__ int mbr_cmp(const u32x4_t a, const u32x4_t b, int n) {
-#pragma unroll
-    for (int c = 0; c < MBR_MAX_ORDER; ++c) {
-        if (c < n && a[c] != b[c]) return a[c] < b[c] ? -1 : 1;
-    }
-    return 0;
-}
-
 // ---- pass A -------------------------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(MBR_THREADS) void mbr_sort_kernel(const int32_t* __restrict__ tok, const MbrHyp* __restrict__ hyps,
-                                                               u32x4_t* __restrict__ keys, u32x4_t* __restrict__ counts) {
-    __shared__ u32x4_t s_key[MBR_MAX_LEN];
-    const int tid = threadIdx.x;
+                                                               MbrTuple* __restrict__ keys, MbrCounts* __restrict__ counts) {
+    __shared__ MbrTuple s_key[MBR_MAX_LEN];
     const MbrHyp h = hyps[blockIdx.x];
-    const int L = h.len;  // 0..MBR_MAX_LEN, checked on the host
-    if (L == 0) return;
-    int P2 = 1;
-    while (P2 < L) P2 <<= 1;
-    const int32_t* t = tok + h.off;
-    for (int p = tid; p < P2; p += MBR_THREADS) {
-        u32x4_t k;
-#pragma unroll
-        for (int c = 0; c < MBR_MAX_ORDER; ++c) k[c] = p >= L ? MBR_SORT_PAD : p + c < L ? (uint32_t)t[p + c] + 1u : 0u;
-        s_key[p] = k;
-    }
-    __syncthreads();
-    for (int k = 2; k <= P2; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int p = tid; p < P2; p += MBR_THREADS) {
-                const int q = p ^ j;
-                if (q > p) {
-                    const u32x4_t a = s_key[p], b = s_key[q];
-                    const bool ascending = (p & k) == 0;
-                    if ((mbr_cmp(a, b, MBR_MAX_ORDER) > 0) == ascending) s_key[p] = b, s_key[q] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int p = tid; p < L; p += MBR_THREADS) {
-        const u32x4_t a = s_key[p];
-        u32x4_t cnt;
-#pragma unroll
-        for (int c = 0; c < MBR_MAX_ORDER; ++c) {
-            const int n = c + 1;
-            cnt[c] = 0;
-            if (a[c] == 0u) continue;                                   // no n-gram starts here: the hypothesis ends first
-            if (p > 0 && mbr_cmp(s_key[p - 1], a, n) == 0) continue;   // inside a run
-            int lo = p + 1, hi = L;                                     // the first slot behind the run
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (mbr_cmp(s_key[mid], a, n) == 0) lo = mid + 1; else hi = mid;
-            }
-            cnt[c] = (uint32_t)(lo - p);
-        }
-        keys[h.off + p] = a;
-        counts[h.off + p] = cnt;
-    }
+    if (h.len == 0) return;  // 0..MBR_MAX_LEN, checked on the host
+    seq_sort_count<MBR_MAX_ORDER, uint32_t>(tok + h.off, h.len, s_key, keys + h.off, counts + h.off);
 }
 
 // ---- pass B -------------------------------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(MBR_THREADS) void mbr_match_kernel(const MbrHyp* __restrict__ hyps, const MbrUtt* __restrict__ utts,
-                                                                const u32x4_t* __restrict__ keys, const u32x4_t* __restrict__ counts,
+                                                                const MbrTuple* __restrict__ keys, const MbrCounts* __restrict__ counts,
                                                                 int max_order, i32x4_t* __restrict__ match) {
-    extern __shared__ u32x4_t s_row[];  // row i: len_i tuples, then len_i counts (the launch sizes it by the longest hypothesis)
+    extern __shared__ MbrTuple s_row[];  // row i: len_i tuples, then len_i counts (the launch sizes it by the longest hypothesis)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const MbrHyp me = hyps[blockIdx.x];
     const MbrUtt u = utts[me.utt];
     const int Li = me.len;
-    u32x4_t* s_cnt = s_row + Li;
+    MbrCounts* s_cnt = reinterpret_cast<MbrCounts*>(s_row + Li);
     for (int p = tid; p < Li; p += MBR_THREADS) {
         s_row[p] = keys[me.off + p];
         s_cnt[p] = counts[me.off + p];
@@ -126,33 +74,9 @@ __global__ __launch_bounds__(MBR_THREADS) void mbr_match_kernel(const MbrHyp* __
     __syncthreads();
     for (int j = wave; j < u.num; j += MBR_WAVES) {  // the whole wavefront takes the same j
         const MbrHyp hj = hyps[u.first + j];
-        const u32x4_t* kj = keys + hj.off;
-        const u32x4_t* cj = counts + hj.off;
-        const int Lj = hj.len;
-        i32x4_t m = {0, 0, 0, 0};
-        for (int p = lane; p < Li; p += 64) {
-            const u32x4_t a = s_row[p], ca = s_cnt[p];
-#pragma unroll
-            for (int c = 0; c < MBR_MAX_ORDER; ++c) {
-                if (c >= max_order || ca[c] == 0u) continue;
-                const int n = c + 1;
-                int lo = 0, hi = Lj;  // the first slot of j that is not below a
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (mbr_cmp(kj[mid], a, n) < 0) lo = mid + 1; else hi = mid;
-                }
-                if (lo < Lj && mbr_cmp(kj[lo], a, n) == 0) {  // the first slot of the run: it carries the run's length
-                    const uint32_t other = cj[lo][c];
-                    m[c] += (int)(ca[c] < other ? ca[c] : other);
-                }
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < MBR_MAX_ORDER; ++c) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) m[c] += __shfl_xor(m[c], o);
-        }
-        if (lane == 0) match[u.pair_off + (uint32_t)me.idx * (uint32_t)u.num + (uint32_t)j] = m;
+        int m[MBR_MAX_ORDER];
+        seq_match_wave<MBR_MAX_ORDER, uint32_t>(s_row, s_cnt, Li, keys + hj.off, counts + hj.off, hj.len, max_order, lane, m);
+        if (lane == 0) match[u.pair_off + (uint32_t)me.idx * (uint32_t)u.num + (uint32_t)j] = i32x4_t{m[0], m[1], m[2], m[3]};
     }
 }
 
@@ -230,26 +154,10 @@ static MbrParams checked_mbr_opts(const sc_mbr_opts* o) {
     return r;
 }
 
-// per device: the buffers of one chunk; grown on demand, never shrunk
-struct MbrBuffer {
-    void* p = nullptr;
-    size_t bytes = 0;
-    template <typename T>
-    T* grow(size_t n) {
-        const size_t need = std::max<size_t>(n * sizeof(T), 256);
-        if (bytes < need) {
-            if (p) (void)hipFree(p);
-            p = nullptr, bytes = 0;
-            const size_t cap = need + need / 4;
-            SC_HIP(hipMalloc(&p, cap));
-            bytes = cap;
-        }
-        return static_cast<T*>(p);
-    }
-};
+// per device: the buffers of one chunk
 struct MbrDevice {
     int device;
-    MbrBuffer tok, hyps, utts, weights, keys, counts, match, utility, expected, best;
+    ScratchBuffer tok, hyps, utts, weights, keys, counts, match, utility, expected, best;
 };
 static std::mutex g_mbr_mutex;
 static std::list<MbrDevice> g_mbr_devices;
@@ -309,7 +217,7 @@ int sc_mbr_select(const int32_t* h_ids, int32_t n, int32_t hyp_stride, int32_t l
     std::lock_guard<std::mutex> lock(g_mbr_mutex);
     MbrDevice& dv = mbr_device_state(device);
     hipStream_t stream = nullptr;  // the default stream, like sc_resample: ordered behind the caller's work on it
-    const size_t row_lds = (size_t)std::max(longest, 1) * 2 * sizeof(u32x4_t);  // at most 32 KB
+    const size_t row_lds = (size_t)std::max(longest, 1) * (sizeof(MbrTuple) + sizeof(MbrCounts));  // at most 32 KB
 
     std::vector<int32_t> tok;
     std::vector<MbrHyp> hyps;
@@ -343,8 +251,8 @@ int sc_mbr_select(const int32_t* h_ids, int32_t n, int32_t hyp_stride, int32_t l
         MbrHyp* d_hyps = dv.hyps.grow<MbrHyp>(H);
         MbrUtt* d_utts = dv.utts.grow<MbrUtt>(U);
         float* d_w = dv.weights.grow<float>(H);
-        u32x4_t* d_keys = dv.keys.grow<u32x4_t>(T);
-        u32x4_t* d_counts = dv.counts.grow<u32x4_t>(T);
+        MbrTuple* d_keys = dv.keys.grow<MbrTuple>(T);
+        MbrCounts* d_counts = dv.counts.grow<MbrCounts>(T);
         i32x4_t* d_match = dv.match.grow<i32x4_t>(Q);
         double* d_utility = dv.utility.grow<double>(Q);
         double* d_expected = dv.expected.grow<double>(H);

@@ -7,7 +7,9 @@ Mirrors src/seamless_communication/cli/m4t/evaluate/evaluate.py of the reference
 fbank per example, ``bucket(batch_size)``, ``Collater(pad_value=0, pad_to_multiple=1)``),
 ``adjust_output_for_corrupted_inputs`` (:205-245) and the loop + writers of ``run_eval`` (:248-350; the
 NaN filter :278-289, the empty-batch rule :292-314, file names and TSV headers :259-274, :324-343).
-Out of scope here: text-input tasks and the quality metrics (Whisper ASR-BLEU / sacrebleu, :352-360).
+The quality metrics of :352-360 are ``metrics.compute_quality_metrics`` (BLEU / chrF++ / WER restated in metrics.py; ASR-BLEU with the
+caller's ASR in Whisper's place): ``run_eval(..., metrics=True)`` computes them from the file it wrote.  Out of scope here: text-input
+tasks.
 
 Differences, all in how bytes reach the path: audio is decoded with the standard library (RIFF/WAVE: PCM 8 - 32 bit,
 float 32 / 64, A-law / mu-law, plain or extensible headers; mono or first channel) or loaded from ``.npy`` because libsndfile / torchaudio are not in
@@ -258,9 +260,13 @@ def adjust_output_for_corrupted_inputs(valid_sequences: Tensor, text_output: Lis
     return adjusted_text, adjusted_speech
 
 
-def run_eval(translator, ctx: EvalContext, fbank_fn: Optional[FbankFn] = None, n_samples: Optional[int] = None) -> Dict[str, Any]:
-    """evaluate.py:248-350 without the metrics: writes ``model-outputs-<stem>.txt``, ``unit_output-<stem>.txt`` and
-    ``waveform_<stem>/<id>_pred.wav`` under ``output_path/<stem>``; returns the paths and the sample count."""
+def run_eval(translator, ctx: EvalContext, fbank_fn: Optional[FbankFn] = None, n_samples: Optional[int] = None, metrics: bool = False,
+             whisper_normalize_text_output: bool = False, asr_model: Optional[Callable[[str, str], str]] = None,
+             normalizer: Optional[Callable[[str], str]] = None) -> Dict[str, Any]:
+    """evaluate.py:248-360: writes ``model-outputs-<stem>.txt``, ``unit_output-<stem>.txt`` and ``waveform_<stem>/<id>_pred.wav`` under
+    ``output_path/<stem>``; returns the paths and the sample count.  ``metrics=True`` (evaluate.py:352-360): then
+    ``metrics.compute_quality_metrics`` on the hypothesis file, its JSON files beside it, and ``"metrics"`` in the returned dict:
+    file name -> parsed content (``asr_model`` / ``normalizer`` / ``whisper_normalize_text_output`` are passed on)."""
     fbank_fn = fbank_fn or gpu_fbank_fn(translator)
     stem = Path(ctx.data_file).stem
     out_dir = Path(ctx.output_path) / stem
@@ -315,5 +321,12 @@ def run_eval(translator, ctx: EvalContext, fbank_fn: Optional[FbankFn] = None, n
             if done:
                 break
     logger.info(f"Processed {sample_id} samples")
-    return {"hypotheses": hyp_path, "units": unit_path if speech_out else None, "waveforms": wav_dir if speech_out else None,
-            "samples": sample_id, "skipped_batches": skipped_batches}
+    result = {"hypotheses": hyp_path, "units": unit_path if speech_out else None, "waveforms": wav_dir if speech_out else None,
+              "samples": sample_id, "skipped_batches": skipped_batches}
+    if metrics:
+        from .metrics import write_quality_metrics
+
+        names = write_quality_metrics(hyp_path, out_dir, ctx.target_lang, ctx.task, device=ctx.device,
+                                      whisper_normalize_text_output=whisper_normalize_text_output, asr_model=asr_model, normalizer=normalizer)
+        result["metrics"] = {name: json.loads((out_dir / name).read_text(encoding="utf-8")) for name in names}
+    return result

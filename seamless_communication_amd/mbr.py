@@ -9,6 +9,11 @@ reference: the utility has NOT been evaluated on real translations, ``beta`` and
 Runs in ``sc_mbr_select`` (csrc/k_mbr.hip) on the current HIP device: the pairwise comparison is exact integer work, one
 workgroup per (utterance, hypothesis).  ``Translator.mbr_decode`` draws the candidates with ``Translator.sample`` and calls
 :func:`select`.
+
+:func:`select_text` is the same selection with the utility of the MBR literature: the sentence chrF / chrF++ of the candidates'
+TEXT (``metrics.py``; ``sc_ngram_match`` counts the character and word n-gram matches on the device).
+``mbr_decode(..., utility="chrf++")`` uses it; the default stays the token utility.  Which of the two selects better translations
+has not been evaluated either - ``metrics.corpus_bleu`` / ``corpus_chrf`` are there to find out.
 """
 from __future__ import annotations
 
@@ -119,6 +124,98 @@ def select(candidates: Sequence[Sequence[Sequence[int]]], weights: Optional[Sequ
     return out
 
 
+MAX_TEXT_LEN = 4096  # non-space characters of a select_text candidate
+TEXT_UTILITIES = ("chrf", "chrf++")
+
+
+def select_text(candidates: Sequence[Sequence[str]], weights: Optional[Sequence[Sequence[float]]] = None, utility: str = "chrf++",
+                char_order: int = 6, word_order: Optional[int] = None, beta: float = 2.0, return_utility: bool = False) -> List[MBRResult]:
+    """:func:`select` on the candidates' TEXT with the utility of the MBR literature: ``U(i, j)`` is the sentence chrF (``"chrf"``) or
+    chrF++ (``"chrf++"``: word bigrams too) of candidate i against candidate j as the pseudo-reference, in [0, 1]
+    (``metrics.sentence_chrf`` / 100).  ``word_order``: overrides the utility's (0 / 2).  The n-gram matches of
+    all utterances come from one ``sc_ngram_match`` call for the characters and one for the words; the expected utilities
+    ``(sum_j w_j U(i, j)) / (sum_j w_j)`` are summed in double for ascending j, and the selected index is the first maximum.  Two
+    equal candidates get equal rows.  Up to 128 candidates per utterance, each of up to 4096 non-space characters."""
+    from . import metrics
+
+    if utility not in TEXT_UTILITIES:
+        raise ValueError(f"`utility` must be one of {TEXT_UTILITIES}, but is {utility!r} instead.")
+    if word_order is None:
+        word_order = 2 if utility == "chrf++" else 0
+    metrics._check_chrf_options(char_order, word_order, beta)
+    n = len(candidates)
+    if n == 0:
+        return []
+    if weights is not None and len(weights) != n:
+        raise ValueError(f"`weights` must hold one list per utterance ({n}), but holds {len(weights)} instead.")
+    chars: List[List[int]] = []
+    words: List[List[int]] = []
+    first: List[int] = []  # an utterance's first sequence in the pools
+    pairs: List[Any] = []
+    intern = metrics._Interner()
+    for u, hyps in enumerate(candidates):
+        if not 1 <= len(hyps) <= MAX_HYPOTHESES:
+            raise ValueError(f"utterance {u} has {len(hyps)} candidates, the limit is 1..{MAX_HYPOTHESES}")
+        if weights is not None:
+            w = [float(x) for x in weights[u]]
+            if len(w) != len(hyps):
+                raise ValueError(f"utterance {u}: {len(w)} weights for {len(hyps)} candidates")
+            if not all(math.isfinite(x) and x >= 0 for x in w) or not sum(w) > 0:
+                raise ValueError(f"utterance {u}: the weights must be finite, non-negative and not all 0")
+        first.append(len(chars))
+        for i, text in enumerate(hyps):
+            if not isinstance(text, str):
+                raise TypeError(f"utterance {u}, candidate {i} is not a string")
+            c = metrics.chrf_characters(text)
+            if len(c) > MAX_TEXT_LEN:
+                raise ValueError(f"utterance {u}, candidate {i} has {len(c)} non-space characters, the limit is {MAX_TEXT_LEN}")
+            chars.append(c)
+            words.append(intern(metrics.chrf_words(text)) if word_order else [])
+        base, N = first[-1], len(hyps)
+        pairs += [(base + i, base + j) for i in range(N) for j in range(N)]  # all pairs of a row together: they share its staged row
+    mc = metrics._match_counts(chars, pairs, char_order)
+    mw = metrics._match_counts(words, pairs, word_order) if word_order else None
+    out: List[MBRResult] = []
+    at = 0
+    for u, hyps in enumerate(candidates):
+        base, N = first[u], len(hyps)
+        w = [1.0] * N if weights is None else [float(x) for x in weights[u]]
+        U = np.zeros((N, N), dtype=np.float64)
+        E = np.zeros(N, dtype=np.float64)
+        for i in range(N):
+            acc = wsum = 0.0
+            for j in range(N):
+                st = metrics._pair_statistics(len(chars[base + i]), len(chars[base + j]), mc[at], char_order)
+                if word_order:
+                    st += metrics._pair_statistics(len(words[base + i]), len(words[base + j]), mw[at], word_order)
+                x = metrics._chrf_from_statistics(st, beta, scale=1.0)
+                U[i, j] = x
+                acc += w[j] * x
+                wsum += w[j]
+                at += 1
+            E[i] = acc / wsum
+        best = 0
+        for k in range(1, N):
+            if E[k] > E[best]:
+                best = k
+        out.append(MBRResult(index=best, expected=E, utility=U if return_utility else None))
+    return out
+
+
+def _check_utility(utility: str) -> None:
+    if utility != "ngram_f" and utility not in TEXT_UTILITIES:
+        raise ValueError(f"`utility` must be 'ngram_f', 'chrf' or 'chrf++', but is {utility!r} instead.")
+
+
+def _pick(hyp_lists, utility: str, prefix_len: int, eos: int, weights, max_order: int, beta: float) -> List[MBRResult]:
+    """The selection of ``mbr_decode`` / ``mbr_decode_beam``: :func:`select` on the content tokens, or :func:`select_text` on the
+    candidates' ``.text`` (``beta`` is the caller's there too; ``max_order`` belongs to the token utility)."""
+    if utility == "ngram_f":
+        return select([[content_tokens(h.token_ids, prefix_len, eos) for h in hyps] for hyps in hyp_lists], weights=weights,
+                      max_order=max_order, beta=beta)
+    return select_text([[str(h.text) for h in hyps] for hyps in hyp_lists], weights=weights, utility=utility, beta=beta)
+
+
 def content_tokens(token_ids: Sequence[int], prefix_len: int, eos_idx: int) -> List[int]:
     """What MBR compares of a sequence ``Translator.sample`` returned: the tokens behind the target prefix, without the
     closing EOS."""
@@ -130,18 +227,21 @@ def content_tokens(token_ids: Sequence[int], prefix_len: int, eos_idx: int) -> L
 
 def mbr_decode(self, input, task_str: str, tgt_lang: str, src_lang: Optional[str] = None, *, sampler: Any, num_gens: int = 16,
                temperature: float = 1.0, seed: int = 0, streams: Optional[Sequence[int]] = None, text_generation_opts: Any = None,
-               max_order: int = 4, beta: float = 1.0, sample_rate: int = 16000, forced_prefix: Any = None) -> List[MBRHypothesis]:
+               max_order: int = 4, beta: float = 1.0, sample_rate: int = 16000, forced_prefix: Any = None,
+               utility: str = "ngram_f") -> List[MBRHypothesis]:
     """``Translator.mbr_decode``: ``num_gens`` sampled hypotheses per input item (``Translator.sample``, same arguments and
     the same tasks: S2TT, ASR, T2TT), then the hypothesis with the highest expected token n-gram F-score against all of them
     (:func:`select` on the content tokens: target prefix and closing EOS stripped).  Not part of the reference's
     ``Translator``; the utility has not been evaluated on real translations.  ``forced_prefix``:
-    ``Translator.sample``'s - the candidates all begin with the item's prefix, which counts as content."""
+    ``Translator.sample``'s - the candidates all begin with the item's prefix, which counts as content.  ``utility``: ``"ngram_f"``
+    (the token utility above), or ``"chrf"`` / ``"chrf++"``: :func:`select_text` on the candidates' ``.text`` with this ``beta``."""
     _check_options(max_order, beta)
+    _check_utility(utility)
     sampled = self.sample(input, task_str, tgt_lang, src_lang, sampler=sampler, num_gens=num_gens, temperature=temperature, seed=seed,
                           streams=streams, text_generation_opts=text_generation_opts, sample_rate=sample_rate, forced_prefix=forced_prefix)
     prefix_len = len(self.text_tokenizer.target_prefix(tgt_lang))
     eos = self.text_tokenizer.vocab_info.eos_idx
-    picked = select([[content_tokens(h.token_ids, prefix_len, eos) for h in hyps] for hyps in sampled], max_order=max_order, beta=beta)
+    picked = _pick(sampled, utility, prefix_len, eos, None, max_order, beta)
     out = []
     for hyps, r in zip(sampled, picked):
         h = hyps[r.index]
@@ -161,14 +261,16 @@ def posterior_weights(step_scores: Sequence[Sequence[float]]) -> List[float]:
 
 def mbr_decode_beam(self, input, task_str: str, tgt_lang: str, src_lang: Optional[str] = None, *, beam_size: int = 8,
                     weights: str = "uniform", text_generation_opts: Any = None, max_order: int = 4, beta: float = 1.0,
-                    sample_rate: int = 16000, forced_prefix: Any = None) -> List[MBRHypothesis]:
+                    sample_rate: int = 16000, forced_prefix: Any = None, utility: str = "ngram_f") -> List[MBRHypothesis]:
     """``Translator.mbr_decode_beam``: the candidates are the beam search's n-best list (``Translator.predict_nbest`` with
     ``beam_size`` and ``nbest = beam_size``; same tasks: S2TT, ASR, T2TT) instead of samples, then :func:`select` on their
     content tokens.  ``weights``: ``"uniform"``, or ``"posterior"`` - every pseudo-reference counts with
     ``exp(sum(step_scores) - max)`` (:func:`posterior_weights`).  ``text_generation_opts`` supplies the length limits,
     penalties and step processors; its ``beam_size`` is replaced.  Not part of the reference's ``Translator``; neither the
-    utility nor the posterior weighting has been evaluated on real translations."""
+    utility nor the posterior weighting has been evaluated on real translations.  ``utility``: as in
+    ``mbr_decode``."""
     _check_options(max_order, beta)
+    _check_utility(utility)
     if weights not in ("uniform", "posterior"):
         raise ValueError(f"`weights` must be 'uniform' or 'posterior', but is {weights!r} instead.")
     if isinstance(beam_size, bool) or int(beam_size) != beam_size or not 1 <= beam_size <= 8:
@@ -184,8 +286,7 @@ def mbr_decode_beam(self, input, task_str: str, tgt_lang: str, src_lang: Optiona
     prefix_len = len(self.text_tokenizer.target_prefix(tgt_lang))
     eos = self.text_tokenizer.vocab_info.eos_idx
     w = [posterior_weights([h.step_scores for h in hyps]) for hyps in nbest] if weights == "posterior" else None
-    picked = select([[content_tokens(h.token_ids, prefix_len, eos) for h in hyps] for hyps in nbest], weights=w, max_order=max_order,
-                    beta=beta)
+    picked = _pick(nbest, utility, prefix_len, eos, w, max_order, beta)
     out = []
     for hyps, r in zip(nbest, picked):
         h = hyps[r.index]
