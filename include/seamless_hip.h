@@ -869,6 +869,52 @@ int64_t sc_vad_windows(int64_t num_samples, int32_t window);
 int sc_vad_probs(const float* d_wav, int32_t n, int64_t wav_stride, const int64_t* h_num_samples, int32_t window, const sc_vad_opts* opts,
                  float* d_probs, int64_t probs_stride, float* d_db, float* h_stats);
 
+/* ---- Streaming speech detection (added within ABI v10, purely additive): the detector above made CAUSAL, for endless streams.
+ * sc_vad_probs takes its threshold from the whole recording; here a lane (one per session) keeps the levels of its last
+ * H = history_windows windows on the device and a window's probability depends on the lane's windows up to it only.  NOT a learned
+ * model, and NOT the reference's Silero VAD: an energy detector whose constants are this project's choice and whose quality on real
+ * speech has not been measured.  For window t (0-based since the lane's reset) of `window` samples:
+ *   db_t as db_w above (whole windows only: nothing is zero-padded)
+ *   S_t  = the finite db_u for max(0, t-H+1) <= u <= t, k = |S_t|, d(0) <= ... <= d(k-1) its sorted values
+ *   F_q = d(floor(floor_quantile (k-1))), P = d(floor(peak_quantile (k-1))) (ranks in double, exact order statistics),
+ *   F = min(F_q, noise_ceiling_db) (no warm-up: a stream that opens with speech has F = noise_ceiling_db and is speech),
+ *   c = F + max(min_margin_db, range_fraction (P - F))
+ *   s_t = the largest finite db of windows t-hangover .. t (BACKWARDS only, clipped at the reset)
+ *   p_t = 1 / (1 + exp(-(s_t - c) / slope_db)); NaN where db_t is NaN (such a window enters neither S nor a later s) or k = 0
+ * How a stream is cut into pushes, who else is in a push and the strides change no bit.
+ * sc_vad_stream_create: host only - device memory is taken on the CURRENT device by the first reset or push, and every later call
+ *   must run on that device.  Work runs on the default stream; reset and push return when their results are complete.
+ *   opts NULL or all-zero: the defaults; otherwise abi_version must be SC_ABI_VERSION, the detector fields follow sc_vad_opts' rules
+ *   and history_windows is 1..1024 (0: 312, 10 s of 512-sample windows at 16 kHz).
+ * sc_vad_stream_reset: the n named lanes start over (t = 0, empty history).  A new handle's lanes are fresh.
+ * sc_vad_stream_push: n >= 0 distinct lanes in one call (two kernel launches whatever n is); named lane i reads
+ *   d_wav[i * wav_stride .. + h_num_samples[i]) and handles floor(h_num_samples[i] / window) whole windows; the samples behind
+ *   them are ignored (not kept for the next push).
+ *   d_probs [n][probs_stride] fp32: the windows' probabilities; nothing is written behind them
+ *   d_db    NULL, or [n][probs_stride] fp32: db_t of the windows handled
+ *   h_stats NULL, or [n][5] fp32 on the host: F, P, c, k of the lane's last window (of an earlier push if this one held none; NaN,
+ *           NaN, NaN, 0 before the first) and the number of windows handled
+ * SC_ERR_INVALID, before any device work: sessions outside 1..65535, window outside 1..8192, a null pointer, more lanes than
+ * sessions, a lane outside 0..sessions-1 or named twice, a negative length, a length above wav_stride, more than 2^20 windows of a
+ * lane in one push, probs_stride below the most windows of a lane, and the option errors of sc_vad_probs. */
+typedef struct sc_vad_stream sc_vad_stream;
+typedef struct sc_vad_stream_opts {
+    int32_t abi_version;
+    int32_t hangover;       /* windows BACK, 0..8, default 1; -1: none */
+    float floor_quantile;   /* 0.10 */
+    float peak_quantile;    /* 0.95 */
+    float noise_ceiling_db; /* -45 */
+    float min_margin_db;    /* 6 */
+    float range_fraction;   /* 0.35 */
+    float slope_db;         /* 1.5 */
+    int32_t history_windows; /* H, 1..1024, default 312 */
+} sc_vad_stream_opts;
+int sc_vad_stream_create(int32_t sessions, int32_t window, const sc_vad_stream_opts* opts, sc_vad_stream** out);
+void sc_vad_stream_destroy(sc_vad_stream* h);
+int sc_vad_stream_reset(sc_vad_stream* h, const int32_t* h_lanes, int32_t n);
+int sc_vad_stream_push(sc_vad_stream* h, const int32_t* h_lanes, int32_t n, const float* d_wav, int64_t wav_stride, const int64_t* h_num_samples,
+                       float* d_probs, int64_t probs_stride, float* d_db, float* h_stats);
+
 /* ---- Minimum-Bayes-risk selection (added within ABI v10, purely additive): of the hypotheses sampled for an utterance
  * (sc_generate_text_sampled), the one with the highest expected utility against all of them.  An extension without a counterpart
  * in the reference; the utility is this project's "token n-gram F-score" (DESIGN.md section 7o has the definition; it has not

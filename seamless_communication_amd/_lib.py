@@ -169,6 +169,10 @@ class sc_vad_opts(C.Structure):
                 ("noise_ceiling_db", C.c_float), ("min_margin_db", C.c_float), ("range_fraction", C.c_float), ("slope_db", C.c_float)]
 
 
+class sc_vad_stream_opts(C.Structure):
+    _fields_ = sc_vad_opts._fields_ + [("history_windows", _i)]
+
+
 class sc_mbr_opts(C.Structure):
     _fields_ = [("abi_version", _i), ("max_order", _i), ("beta", C.c_float), ("reserved", _i)]
 
@@ -306,6 +310,10 @@ SIGNATURES = {
     "sc_resample": (C.c_int, [_P, _i, C.c_int64, _P, _i, _i, C.POINTER(sc_resample_opts), _P, C.c_int64, _P]),
     "sc_vad_windows": (C.c_int64, [C.c_int64, _i]),
     "sc_vad_probs": (C.c_int, [_P, _i, C.c_int64, _P, _i, C.POINTER(sc_vad_opts), _P, C.c_int64, _P, _P]),
+    "sc_vad_stream_create": (C.c_int, [_i, _i, C.POINTER(sc_vad_stream_opts), C.POINTER(_P)]),
+    "sc_vad_stream_destroy": (None, [_P]),
+    "sc_vad_stream_reset": (C.c_int, [_P, _P, _i]),
+    "sc_vad_stream_push": (C.c_int, [_P, _P, _i, _P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
     "sc_mbr_select": (C.c_int, [_P, _i, _i, _i, _P, _P, _P, C.POINTER(sc_mbr_opts), _P, _P, _P, _P]),
     "sc_ngram_match": (C.c_int, [_P, _P, _i, _P, C.c_int64, _i, _P]),
     "sc_edit_distance": (C.c_int, [_P, _P, _i, _P, C.c_int64, _P]),

@@ -110,3 +110,98 @@ def speech_probs_ragged(waves: Sequence[Tensor], window_size_samples: int = 1536
             raise ValueError(f"waveform {i} holds a sample that is not finite, first in window {first} of {int(n_w[i])} "
                              f"(window_size_samples={window})")
     return [probs[i, : int(n_w[i])].clone() for i in range(len(waves))]
+
+
+# ---- streaming speech detection (sc_vad_stream_*) ---------------------------------------------------------
+
+class StreamingSpeechDetector:
+    """The speech detector made causal, for endless streams: ``sessions`` lanes on one HIP device, each with the levels of its last
+    ``history_windows`` windows (default 312: 10 s of 512-sample windows at 16 kHz).  ``push({sid: samples})`` hears the WHOLE
+    windows of every named lane's samples (host or device float32; what fills no window is dropped, as the reference's loop does)
+    in ONE device call and returns ``{sid: float32 array}``, a probability per window.  A window's probability depends on its own
+    lane's windows up to it only: neither the cut into pushes nor the other lanes change a bit.
+
+    NOT a learned model and NOT the reference's Silero VAD: an energy detector (a window is speech when its level stands above a
+    threshold between the quiet and loud windows of the lane's history) whose constants are this project's choice; nobody has
+    evaluated it on real speech.  ``opts`` are those of :func:`speech_probs`; ``hangover`` looks backwards
+    only.  ``ValueError`` for a sample that is not finite; it names the first window that holds one."""
+
+    def __init__(self, sessions: int = 1, window: int = 512, device=None, **opts) -> None:
+        self.device = torch.device("cuda" if device is None else device)
+        if self.device.type != "cuda":
+            raise ValueError("StreamingSpeechDetector needs a HIP device (device='cuda[:N]'): the detector has no CPU path")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.sessions, self.window = int(sessions), int(window)
+        self._stream = _rt.VadStream(self.sessions, self.window, _rt.vad_stream_opts(**opts))
+        self._stats = {}
+
+    calls = property(lambda self: self._stream.pushes, doc="device pushes made so far (one per `push`, whatever the number of lanes)")
+
+    def push(self, chunks) -> dict:
+        import numpy as np
+
+        sids = sorted(chunks)
+        if not sids:
+            return {}
+        waves = []
+        for sid in sids:
+            w = chunks[sid]
+            w = w if isinstance(w, Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(w, dtype=np.float32)))
+            if w.dim() != 1:
+                raise ValueError(f"lane {sid}: push takes 1-D samples, got shape {tuple(w.shape)}")
+            waves.append(w.to(torch.float32))
+        lens = [int(w.shape[0]) for w in waves]
+        if len(waves) == 1 and waves[0].is_cuda:
+            rows = waves[0].to(self.device).contiguous().unsqueeze(0)
+        else:
+            host = torch.zeros(len(waves), max(max(lens), 1), dtype=torch.float32)
+            on_device = [w.is_cuda for w in waves]
+            for i, w in enumerate(waves):
+                if not on_device[i]:
+                    host[i, : lens[i]] = w
+            rows = host.to(self.device)
+            for i, w in enumerate(waves):
+                if on_device[i]:
+                    rows[i, : lens[i]] = w.to(self.device)
+        probs, n_w, _, stats = self._stream.push(sids, rows, lens)
+        probs = probs.cpu().numpy()
+        out = {}
+        for i, sid in enumerate(sids):
+            p = probs[i, : int(n_w[i])].copy()
+            self._stats[sid] = dict(zip(_rt.VadStream.STATS, (float(v) for v in stats[i])))
+            if np.isnan(p).any():  # a window without a level: NaN is loud
+                first = _first_bad_window(waves[i][: int(n_w[i]) * self.window], self.window)
+                if first < 0:
+                    raise ValueError(f"lane {sid} holds samples too large for an fp32 energy (above about 1e19)")
+                raise ValueError(f"lane {sid} holds a sample that is not finite, first in window {first} of {int(n_w[i])} of this push "
+                                 f"(window={self.window})")
+            out[sid] = p
+        return out
+
+    def reset(self, sid: int) -> None:
+        self._stream.reset([int(sid)], self.device)
+        self._stats.pop(sid, None)
+
+    def stats(self, sid: int) -> dict:
+        """F, P, c, k of the lane's last window and the windows its last push handled (NaN, NaN, NaN, 0, 0 before the first)."""
+        return dict(self._stats.get(sid, dict(zip(_rt.VadStream.STATS, (float("nan"),) * 3 + (0.0, 0.0)))))
+
+    def lane(self, sid: int) -> "DetectorLane":
+        return DetectorLane(self, int(sid))
+
+    def close(self) -> None:
+        self._stream.close()
+
+
+class DetectorLane:
+    """One lane of a :class:`StreamingSpeechDetector` as a VAD stage's ``vad=``: ``speech_probs(chunk) -> [float]``."""
+
+    def __init__(self, detector: StreamingSpeechDetector, sid: int) -> None:
+        self.detector, self.sid = detector, sid
+
+    def speech_probs(self, chunk) -> List[float]:
+        return [float(p) for p in self.detector.push({self.sid: chunk})[self.sid]]
+
+    def reset(self) -> None:
+        self.detector.reset(self.sid)

@@ -182,25 +182,179 @@ __global__ __launch_bounds__(VAD_THREADS) void vad_prob_kernel(float* __restrict
     }
 }
 
+// ---- the streaming detector (sc_vad_stream_*) -------------------------------------------------------------
+//
+// State per lane: the levels of the last H windows as a ring (slot = window number mod H; NaN = no level: a slot not written since
+// the reset, or a window that has none), the levels of the last VAD_STREAM_RECENT windows for the hangover (slot = window number
+// mod 8: the hangover does not depend on H), the number of windows since the reset and F, P, c, k of the last window.
+// A push is vad_energy_kernel over the whole windows of every named lane, then this kernel: one workgroup per named lane walks
+// the lane's new windows in order - append, count, radix select of both order statistics over the ring in LDS (the 256 bins of a
+// pass are scanned by one wavefront per statistic: four bins a lane, a shuffle prefix sum, a ballot for the bin that holds the
+// rank - the walk of one thread over the bins that vad_prob_kernel makes once per row would cost about 30 us per window here),
+// backwards maximum, logistic.  A window's result is a function of the lane's levels up to it: neither the cut into pushes nor the
+// companions of a push enter.
+
+static constexpr int VAD_STREAM_MAX_HISTORY = 1024, VAD_STREAM_DEFAULT_HISTORY = 312;
+static constexpr int VAD_STREAM_RECENT = 8;  // >= VAD_MAX_HANGOVER, a power of two
+static constexpr int VAD_STREAM_STATS = 5;   // F, P, c, k, windows handled
+static_assert(VAD_STREAM_RECENT >= VAD_MAX_HANGOVER && (VAD_STREAM_RECENT & (VAD_STREAM_RECENT - 1)) == 0, "hangover ring");
+
+struct VadStreamState {
+    float* ring;     // [sessions][H]
+    float* recent;   // [sessions][VAD_STREAM_RECENT]
+    float* last;     // [sessions][4]: F, P, c, k of the lane's last window
+    int64_t* count;  // [sessions]: windows since the reset
+};
+
+// lanes == nullptr: every lane, blockIdx.x is the lane
+__global__ __launch_bounds__(VAD_THREADS) void vad_stream_reset_kernel(VadStreamState st, int H, const int32_t* __restrict__ lanes) {
+    const int64_t sid = lanes ? lanes[blockIdx.x] : (int)blockIdx.x;
+    const float nan = __builtin_nanf("");
+    for (int i = threadIdx.x; i < H; i += VAD_THREADS) st.ring[sid * H + i] = nan;
+    if (threadIdx.x < VAD_STREAM_RECENT) st.recent[sid * VAD_STREAM_RECENT + threadIdx.x] = nan;
+    if (threadIdx.x < 4) st.last[sid * 4 + threadIdx.x] = threadIdx.x == 3 ? 0.f : nan;
+    if (threadIdx.x == 0) st.count[sid] = 0;
+}
+
+// len[b]: samples of the whole windows of named lane b (a multiple of W); db [n][db_stride] from vad_energy_kernel
+__global__ __launch_bounds__(VAD_THREADS) void vad_stream_kernel(const float* __restrict__ db, int64_t db_stride, const int64_t* __restrict__ len,
+                                                                 const int32_t* __restrict__ lanes, int W, int H, VadParams p, VadStreamState st,
+                                                                 float* __restrict__ probs, int64_t probs_stride, float* __restrict__ stats) {
+    __shared__ float s_ring[VAD_STREAM_MAX_HISTORY];
+    __shared__ float s_recent[VAD_STREAM_RECENT];
+    __shared__ unsigned s_hist[2][256];
+    __shared__ unsigned s_count;
+    __shared__ unsigned s_rank[2], s_prefix[2];
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const int64_t sid = lanes[b];
+    const int nw = (int)(len[b] / W);
+    float* ring = st.ring + sid * H;
+    const float* d = db + b * db_stride;
+    float* pr = probs + b * probs_stride;
+    for (int i = tid; i < H; i += VAD_THREADS) s_ring[i] = ring[i];
+    if (tid < VAD_STREAM_RECENT) s_recent[tid] = st.recent[sid * VAD_STREAM_RECENT + tid];
+    const int64_t t0 = st.count[sid];
+    float F = st.last[sid * 4 + 0], P = st.last[sid * 4 + 1], c = st.last[sid * 4 + 2];
+    unsigned k = (unsigned)st.last[sid * 4 + 3];
+    const float nan = __builtin_nanf("");
+    for (int j = 0; j < nw; ++j) {
+        const int64_t t = t0 + j;
+        const float own = d[j];
+        __syncthreads();  // the loads above; every read of s_count / s_prefix of the window before
+        if (tid == 0) {
+            const int slot = (int)(t % H);
+            s_ring[slot] = own;
+            ring[slot] = own;
+            s_count = 0;
+        }
+        __syncthreads();
+        unsigned mine = 0;
+        for (int i = tid; i < H; i += VAD_THREADS) mine += s_ring[i] == s_ring[i] ? 1u : 0u;
+        if (mine) atomicAdd(&s_count, mine);
+        __syncthreads();
+        k = s_count;
+        if (k == 0) {  // the whole workgroup: no level in the history, so this window has none either
+            F = P = c = nan;
+            if (tid == 0) pr[j] = nan, s_recent[t & (VAD_STREAM_RECENT - 1)] = own;
+            continue;
+        }
+        if (tid < 2) {
+            const double q = tid == 0 ? p.floor_q : p.peak_q;
+            unsigned r = (unsigned)floor(q * (double)(k - 1));
+            s_rank[tid] = r < k ? r : k - 1;
+            s_prefix[tid] = 0;
+        }
+        uint32_t mask = 0;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            s_hist[0][tid] = 0;
+            s_hist[1][tid] = 0;
+            __syncthreads();  // also orders s_rank / s_prefix of the pass before
+            const uint32_t pf0 = s_prefix[0], pf1 = s_prefix[1];
+            for (int i = tid; i < H; i += VAD_THREADS) {
+                const float f = s_ring[i];
+                if (f != f) continue;
+                const uint32_t key = vad_key(f);
+                const unsigned bin = (key >> shift) & 255u;
+                if ((key & mask) == pf0) atomicAdd(&s_hist[0][bin], 1u);
+                if ((key & mask) == pf1) atomicAdd(&s_hist[1][bin], 1u);
+            }
+            __syncthreads();
+            if (tid < 128) {  // the bin that holds the rank among the keys of this prefix: wavefront 0 the floor's, wavefront 1 the peak's
+                const int w = tid >> 6, l = tid & 63;
+                const unsigned r = s_rank[w];
+                const unsigned h0 = s_hist[w][4 * l], h1 = s_hist[w][4 * l + 1], h2 = s_hist[w][4 * l + 2], h3 = s_hist[w][4 * l + 3];
+                const unsigned own4 = h0 + h1 + h2 + h3;
+                unsigned incl = own4;  // keys in the bins 0 .. 4 l + 3
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {
+                    const unsigned up = __shfl_up(incl, o);
+                    if (l >= o) incl += up;
+                }
+                const unsigned long long holds = __ballot(incl > r);  // never empty: the rank is below the number of keys of the prefix
+                if (holds && l == __ffsll((long long)holds) - 1) {
+                    unsigned below = incl - own4;
+                    int bin = 4 * l;
+                    if (below + h0 <= r) {
+                        below += h0, ++bin;
+                        if (below + h1 <= r) {
+                            below += h1, ++bin;
+                            if (below + h2 <= r) below += h2, ++bin;
+                        }
+                    }
+                    s_rank[w] = r - below;
+                    s_prefix[w] |= (uint32_t)bin << shift;
+                }
+            }
+            mask |= 0xffu << shift;
+            __syncthreads();
+        }
+        P = vad_unkey(s_prefix[1]);
+        F = fminf(vad_unkey(s_prefix[0]), p.ceiling_db);
+        c = F + fmaxf(p.margin_db, p.range_fraction * (P - F));
+        if (tid == 0) {
+            float out = nan;
+            if (own == own) {
+                float s = own;
+                for (int i = 1; i <= p.hangover && t - i >= 0; ++i) {  // backwards only, clipped at the reset
+                    const float u = s_recent[(t - i) & (VAD_STREAM_RECENT - 1)];
+                    if (u == u && u > s) s = u;
+                }
+                out = 1.f / (1.f + expf(-(s - c) / p.slope_db));
+            }
+            pr[j] = out;
+            s_recent[t & (VAD_STREAM_RECENT - 1)] = own;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        st.count[sid] = t0 + nw;
+        st.last[sid * 4 + 0] = F, st.last[sid * 4 + 1] = P, st.last[sid * 4 + 2] = c, st.last[sid * 4 + 3] = (float)k;
+        for (int i = 0; i < VAD_STREAM_RECENT; ++i) st.recent[sid * VAD_STREAM_RECENT + i] = s_recent[i];
+        float* o = stats + b * VAD_STREAM_STATS;
+        o[0] = F, o[1] = P, o[2] = c, o[3] = (float)k, o[4] = (float)nw;
+    }
+}
+
 // ---- host ---------------------------------------------------------------------------------------------------------------------
 
 static bool number(float v) { return std::isfinite(v); }
 
 // every check of the options; a zero field stands for its default
-static VadParams checked_vad_opts(const sc_vad_opts* o) {
+static VadParams checked_vad_opts(const sc_vad_opts* o, const char* who = "sc_vad_probs") {
     VadParams r;
     static const sc_vad_opts zero{};
     if (!o || std::memcmp(o, &zero, sizeof(zero)) == 0) return r;
-    SC_CHECK(o->abi_version == SC_ABI_VERSION, "sc_vad_probs: options ABI version %d != library %d", o->abi_version, SC_ABI_VERSION);
-    SC_CHECK(o->hangover >= -1 && o->hangover <= VAD_MAX_HANGOVER, "sc_vad_probs: hangover %d is outside the limit -1..%d", o->hangover, VAD_MAX_HANGOVER);
+    SC_CHECK(o->abi_version == SC_ABI_VERSION, "%s: options ABI version %d != library %d", who, o->abi_version, SC_ABI_VERSION);
+    SC_CHECK(o->hangover >= -1 && o->hangover <= VAD_MAX_HANGOVER, "%s: hangover %d is outside the limit -1..%d", who, o->hangover, VAD_MAX_HANGOVER);
     SC_CHECK(number(o->floor_quantile) && number(o->peak_quantile) && number(o->noise_ceiling_db) && number(o->min_margin_db) &&
                  number(o->range_fraction) && number(o->slope_db),
-             "sc_vad_probs: an option is not a number");
-    SC_CHECK(o->floor_quantile >= 0.f && o->floor_quantile <= 1.f, "sc_vad_probs: floor_quantile %g is outside [0, 1]", (double)o->floor_quantile);
-    SC_CHECK(o->peak_quantile >= 0.f && o->peak_quantile <= 1.f, "sc_vad_probs: peak_quantile %g is outside [0, 1]", (double)o->peak_quantile);
-    SC_CHECK(o->min_margin_db >= 0.f, "sc_vad_probs: min_margin_db %g is negative", (double)o->min_margin_db);
-    SC_CHECK(o->range_fraction >= 0.f, "sc_vad_probs: range_fraction %g is negative", (double)o->range_fraction);
-    SC_CHECK(o->slope_db >= 0.f, "sc_vad_probs: slope_db %g is negative (0 stands for the default)", (double)o->slope_db);
+             "%s: an option is not a number", who);
+    SC_CHECK(o->floor_quantile >= 0.f && o->floor_quantile <= 1.f, "%s: floor_quantile %g is outside [0, 1]", who, (double)o->floor_quantile);
+    SC_CHECK(o->peak_quantile >= 0.f && o->peak_quantile <= 1.f, "%s: peak_quantile %g is outside [0, 1]", who, (double)o->peak_quantile);
+    SC_CHECK(o->min_margin_db >= 0.f, "%s: min_margin_db %g is negative", who, (double)o->min_margin_db);
+    SC_CHECK(o->range_fraction >= 0.f, "%s: range_fraction %g is negative", who, (double)o->range_fraction);
+    SC_CHECK(o->slope_db >= 0.f, "%s: slope_db %g is negative (0 stands for the default)", who, (double)o->slope_db);
     if (o->hangover != 0) r.hangover = o->hangover < 0 ? 0 : o->hangover;
     // the struct carries the quantiles as fp32: a field that holds its default rounded to fp32 stands for the default itself
     if (o->floor_quantile != 0.f && o->floor_quantile != (float)VAD_FLOOR_QUANTILE) r.floor_q = (double)o->floor_quantile;
@@ -256,6 +410,67 @@ static void launch_energy(dim3 grid, hipStream_t stream, const float* d_wav, int
     hipLaunchKernelGGL(vad_energy_kernel<NV>, grid, dim3(VAD_THREADS), 0, stream, d_wav, wav_stride, d_len, W, d_db, db_stride);
 }
 
+static void launch_energy_for(int window, dim3 grid, hipStream_t stream, const float* d_wav, int64_t wav_stride, const int64_t* d_len, float* d_db,
+                              int64_t db_stride) {
+    if (window <= 512)
+        launch_energy<2>(grid, stream, d_wav, wav_stride, d_len, window, d_db, db_stride);
+    else if (window <= 2048)
+        launch_energy<8>(grid, stream, d_wav, wav_stride, d_len, window, d_db, db_stride);
+    else
+        launch_energy<32>(grid, stream, d_wav, wav_stride, d_len, window, d_db, db_stride);
+}
+
+}  // namespace sc
+
+// The streaming detector's handle.  Nothing of it lives on a device until the first reset or push: creation checks and records.
+struct sc_vad_stream {
+    int sessions = 0, window = 0, history = 0;
+    sc::VadParams p;
+    int device = -1;  // the device of the first reset / push; every later call must run on it
+    sc::VadStreamState st{};
+    int64_t* d_len = nullptr;  // [sessions] int64 lengths, then [sessions] int32 lanes: one copy per push
+    float* d_stats = nullptr;  // [sessions][VAD_STREAM_STATS]
+    float* d_db = nullptr;     // the levels of a push without d_db; grown on demand
+    size_t db_floats = 0;
+    std::vector<int64_t> h_meta;
+    std::vector<char> named;
+    std::mutex mutex;
+};
+
+namespace sc {
+
+// mutex held; argument checks done
+static void vad_stream_on_device(sc_vad_stream& h) {
+    int device = 0;
+    SC_HIP(hipGetDevice(&device));
+    if (h.device >= 0) {
+        SC_CHECK(device == h.device, "sc_vad_stream: the handle lives on device %d, the current device is %d", h.device, device);
+        return;
+    }
+    const size_t n = (size_t)h.sessions;
+    SC_HIP(hipMalloc(reinterpret_cast<void**>(&h.st.ring), n * h.history * sizeof(float)));
+    SC_HIP(hipMalloc(reinterpret_cast<void**>(&h.st.recent), n * VAD_STREAM_RECENT * sizeof(float)));
+    SC_HIP(hipMalloc(reinterpret_cast<void**>(&h.st.last), n * 4 * sizeof(float)));
+    SC_HIP(hipMalloc(reinterpret_cast<void**>(&h.st.count), n * sizeof(int64_t)));
+    SC_HIP(hipMalloc(reinterpret_cast<void**>(&h.d_len), n * (sizeof(int64_t) + sizeof(int32_t))));
+    SC_HIP(hipMalloc(reinterpret_cast<void**>(&h.d_stats), n * VAD_STREAM_STATS * sizeof(float)));
+    h.device = device;
+    hipLaunchKernelGGL(vad_stream_reset_kernel, dim3((unsigned)n), dim3(VAD_THREADS), 0, nullptr, h.st, h.history, (const int32_t*)nullptr);
+    SC_LAUNCH_CHECK();
+}
+
+// the named lanes: each inside 0..sessions-1, none twice
+static void check_lanes(sc_vad_stream& h, const char* who, const int32_t* sids, int32_t n) {
+    SC_CHECK(n >= 0 && n <= h.sessions, "%s: %d lanes named, the handle has %d", who, n, h.sessions);
+    SC_CHECK(n == 0 || sids, "%s: null argument", who);
+    h.named.assign((size_t)h.sessions, 0);
+    for (int i = 0; i < n; ++i) {
+        SC_CHECK(sids[i] >= 0 && sids[i] < h.sessions, "%s: lane %d is out of range 0..%d", who, sids[i], h.sessions - 1);
+        SC_CHECK(!h.named[sids[i]], "%s: duplicate lane %d", who, sids[i]);
+        h.named[sids[i]] = 1;
+    }
+}
+
 }  // namespace sc
 
 using namespace sc;
@@ -302,18 +517,122 @@ int sc_vad_probs(const float* d_wav, int32_t n, int64_t wav_stride, const int64_
     SC_HIP(hipMemcpyAsync(dv.d_len, h_num_samples, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, stream));
     if (most > 0) {
         const dim3 grid((unsigned)cdiv64(most, VAD_WAVES), (unsigned)n);
-        if (window <= 512)
-            launch_energy<2>(grid, stream, d_wav, wav_stride, dv.d_len, window, db, db_stride);
-        else if (window <= 2048)
-            launch_energy<8>(grid, stream, d_wav, wav_stride, dv.d_len, window, db, db_stride);
-        else
-            launch_energy<32>(grid, stream, d_wav, wav_stride, dv.d_len, window, db, db_stride);
+        launch_energy_for(window, grid, stream, d_wav, wav_stride, dv.d_len, db, db_stride);
         SC_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(vad_prob_kernel, dim3((unsigned)n), dim3(VAD_THREADS), 0, stream, db, db_stride, d_db ? 1 : 0, dv.d_len, window, p, d_probs,
                        probs_stride, dv.d_stats);
     SC_LAUNCH_CHECK();
     if (h_stats) SC_HIP(hipMemcpyAsync(h_stats, dv.d_stats, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, stream));
+    SC_HIP(hipStreamSynchronize(stream));
+    SC_API_END
+}
+
+int sc_vad_stream_create(int32_t sessions, int32_t window, const sc_vad_stream_opts* opts, sc_vad_stream** out) {
+    SC_API_BEGIN
+    SC_CHECK(out, "sc_vad_stream_create: null argument");
+    *out = nullptr;
+    SC_CHECK(sessions >= 1 && sessions <= 65535, "sc_vad_stream_create: %d sessions, the limit is 1..65535", sessions);
+    SC_CHECK(window >= 1 && window <= VAD_MAX_WINDOW, "sc_vad_stream_create: window %d is outside the limit 1..%d", window, VAD_MAX_WINDOW);
+    int history = VAD_STREAM_DEFAULT_HISTORY;
+    VadParams p;
+    static const sc_vad_stream_opts zero{};
+    if (opts && std::memcmp(opts, &zero, sizeof(zero)) != 0) {
+        SC_CHECK(opts->abi_version == SC_ABI_VERSION, "sc_vad_stream_create: options ABI version %d != library %d", opts->abi_version, SC_ABI_VERSION);
+        const sc_vad_opts base{opts->abi_version, opts->hangover,      opts->floor_quantile, opts->peak_quantile, opts->noise_ceiling_db,
+                               opts->min_margin_db, opts->range_fraction, opts->slope_db};
+        p = checked_vad_opts(&base, "sc_vad_stream_create");
+        SC_CHECK(opts->history_windows >= 0 && opts->history_windows <= VAD_STREAM_MAX_HISTORY,
+                 "sc_vad_stream_create: history_windows %d is outside the limit 1..%d (0 stands for the default)", opts->history_windows,
+                 VAD_STREAM_MAX_HISTORY);
+        if (opts->history_windows != 0) history = opts->history_windows;
+    }
+    sc_vad_stream* h = new sc_vad_stream();
+    h->sessions = sessions, h->window = window, h->history = history, h->p = p;
+    *out = h;
+    SC_API_END
+}
+
+void sc_vad_stream_destroy(sc_vad_stream* h) {
+    if (!h) return;
+    if (h->device >= 0) {
+        int cur = 0;
+        const bool swap = hipGetDevice(&cur) == hipSuccess && cur != h->device && hipSetDevice(h->device) == hipSuccess;
+        for (void* p : {(void*)h->st.ring, (void*)h->st.recent, (void*)h->st.last, (void*)h->st.count, (void*)h->d_len, (void*)h->d_stats, (void*)h->d_db})
+            if (p) (void)hipFree(p);
+        if (swap) (void)hipSetDevice(cur);
+    }
+    delete h;
+}
+
+int sc_vad_stream_reset(sc_vad_stream* h, const int32_t* sids, int32_t n) {
+    SC_API_BEGIN
+    SC_CHECK(h, "sc_vad_stream_reset: null argument");
+    std::lock_guard<std::mutex> lock(h->mutex);
+    check_lanes(*h, "sc_vad_stream_reset", sids, n);
+    if (n == 0) return SC_OK;
+    const bool fresh = h->device < 0;
+    vad_stream_on_device(*h);
+    hipStream_t stream = nullptr;
+    if (!fresh) {  // a handle that has just come to the device holds fresh lanes only
+        int32_t* d_lanes = reinterpret_cast<int32_t*>(h->d_len + h->sessions);
+        SC_HIP(hipMemcpyAsync(d_lanes, sids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(vad_stream_reset_kernel, dim3((unsigned)n), dim3(VAD_THREADS), 0, stream, h->st, h->history, (const int32_t*)d_lanes);
+        SC_LAUNCH_CHECK();
+    }
+    SC_HIP(hipStreamSynchronize(stream));
+    SC_API_END
+}
+
+int sc_vad_stream_push(sc_vad_stream* h, const int32_t* sids, int32_t n, const float* d_wav, int64_t wav_stride, const int64_t* h_num_samples,
+                       float* d_probs, int64_t probs_stride, float* d_db, float* h_stats) {
+    SC_API_BEGIN
+    // every argument check comes before the first device call
+    SC_CHECK(h, "sc_vad_stream_push: null argument");
+    std::lock_guard<std::mutex> lock(h->mutex);
+    check_lanes(*h, "sc_vad_stream_push", sids, n);
+    if (n == 0) return SC_OK;
+    SC_CHECK(h_num_samples, "sc_vad_stream_push: null argument");
+    SC_CHECK(wav_stride >= 0 && probs_stride >= 0, "sc_vad_stream_push: negative stride");
+    const int W = h->window;
+    int64_t most = 0;
+    h->h_meta.assign((size_t)n + ((size_t)n + 1) / 2, 0);
+    for (int i = 0; i < n; ++i) {
+        const int64_t L = h_num_samples[i];
+        SC_CHECK(L >= 0, "sc_vad_stream_push: lane %d has a negative length %lld", sids[i], (long long)L);
+        SC_CHECK(L <= wav_stride, "sc_vad_stream_push: lane %d has %lld samples, wav_stride is %lld", sids[i], (long long)L, (long long)wav_stride);
+        const int64_t nw = L / W;  // the samples behind the last whole window are not heard
+        SC_CHECK(nw <= VAD_MAX_WINDOWS, "sc_vad_stream_push: lane %d has %lld windows, the limit is %lld", sids[i], (long long)nw, (long long)VAD_MAX_WINDOWS);
+        h->h_meta[i] = nw * W;
+        most = std::max(most, nw);
+    }
+    SC_CHECK(probs_stride >= most, "sc_vad_stream_push: probs_stride %lld is below the most windows of a lane, %lld", (long long)probs_stride,
+             (long long)most);
+    SC_CHECK(most == 0 || (d_wav && d_probs), "sc_vad_stream_push: null argument");
+    std::memcpy(reinterpret_cast<char*>(h->h_meta.data()) + (size_t)n * sizeof(int64_t), sids, (size_t)n * sizeof(int32_t));
+    vad_stream_on_device(*h);
+    hipStream_t stream = nullptr;  // the default stream, like sc_vad_probs
+    const int64_t scratch_stride = std::max<int64_t>(most, 1);
+    if (!d_db && h->db_floats < (size_t)n * scratch_stride) {
+        if (h->d_db) (void)hipFree(h->d_db);
+        h->d_db = nullptr, h->db_floats = 0;
+        const size_t want = std::max<size_t>((size_t)n * scratch_stride, (size_t)h->sessions * 16);
+        SC_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_db), want * sizeof(float)));
+        h->db_floats = want;
+    }
+    float* db = d_db ? d_db : h->d_db;
+    const int64_t db_stride = d_db ? probs_stride : scratch_stride;
+    // lengths and lanes in one copy: the lanes of this call sit right behind its n lengths
+    SC_HIP(hipMemcpyAsync(h->d_len, h->h_meta.data(), (size_t)n * (sizeof(int64_t) + sizeof(int32_t)), hipMemcpyHostToDevice, stream));
+    const int32_t* d_lanes = reinterpret_cast<const int32_t*>(h->d_len + n);
+    if (most > 0) {
+        launch_energy_for(W, dim3((unsigned)cdiv64(most, VAD_WAVES), (unsigned)n), stream, d_wav, wav_stride, h->d_len, db, db_stride);
+        SC_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(vad_stream_kernel, dim3((unsigned)n), dim3(VAD_THREADS), 0, stream, db, db_stride, h->d_len, d_lanes, W, h->history, h->p, h->st,
+                       d_probs, probs_stride, h->d_stats);
+    SC_LAUNCH_CHECK();
+    if (h_stats) SC_HIP(hipMemcpyAsync(h_stats, h->d_stats, (size_t)n * VAD_STREAM_STATS * sizeof(float), hipMemcpyDeviceToHost, stream));
     SC_HIP(hipStreamSynchronize(stream));
     SC_API_END
 }

@@ -6,6 +6,7 @@ runs inside the HIP library through its C ABI.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import threading
@@ -1299,6 +1300,81 @@ def vad_probs_rows(rows: torch.Tensor, lens: Sequence[int], window: int, opts: O
         check(lib.sc_vad_probs(_ptr(rows), n, wav_stride, _ptr(num), int(window), C.byref(opts) if opts is not None else None,
                                _ptr(probs), stride, _ptr(db), _ptr(stats)), "sc_vad_probs")
     return probs, n_w, db, stats
+
+
+VAD_STREAM_OPTION_NAMES = VAD_OPTION_NAMES + ("history_windows",)
+
+
+def vad_stream_opts(**options) -> Optional[_lib.sc_vad_stream_opts]:
+    """The options of ``sc_vad_stream_create`` by name (None without any): those of ``vad_opts`` and ``history_windows``."""
+    unknown = set(options) - set(VAD_STREAM_OPTION_NAMES)
+    if unknown:
+        raise TypeError(f"unexpected streaming speech detector option(s) {sorted(unknown)}; known: {list(VAD_STREAM_OPTION_NAMES)}")
+    if not options:
+        return None
+    o = _lib.sc_vad_stream_opts()
+    o.abi_version = _lib.SC_ABI_VERSION
+    for k, v in options.items():
+        setattr(o, k, int(v) if k in ("hangover", "history_windows") else float(v))
+    return o
+
+
+class VadStream:
+    """``sc_vad_stream_*``: the causal speech detector, one lane per session (include/seamless_hip.h).  No model handle; the lanes
+    live on the device of the first ``reset`` / ``push``."""
+
+    STATS = ("F", "P", "c", "k", "windows")
+
+    def __init__(self, sessions: int, window: int, opts: Optional[_lib.sc_vad_stream_opts] = None) -> None:
+        self.lib = _lib.load_library()
+        self.sessions, self.window = int(sessions), int(window)
+        handle = C.c_void_p()
+        self.handle = None
+        check(self.lib.sc_vad_stream_create(self.sessions, self.window, C.byref(opts) if opts is not None else None, C.byref(handle)),
+              "sc_vad_stream_create")
+        self.handle = handle
+        self.pushes = 0
+
+    def reset(self, sids: Sequence[int], device: Optional[torch.device] = None) -> None:
+        lanes = np.ascontiguousarray(np.asarray(list(sids), dtype=np.int32))
+        with torch.cuda.device(device) if device is not None else contextlib.nullcontext():
+            check(self.lib.sc_vad_stream_reset(self.handle, _ptr(lanes), len(lanes)), "sc_vad_stream_reset")
+
+    def push(self, sids: Sequence[int], rows: torch.Tensor, lens: Sequence[int], want_db: bool = False):
+        """``rows`` (n, stride) fp32 on a HIP device, row i = the new samples of lane ``sids[i]``, valid up to ``lens[i]`` ->
+        (probs (n, most windows) - row i holds ``lens[i] // window`` of them -, the window counts, db or None, stats (n, 5): F, P,
+        c, k of the lane's last window and the windows handled).  One call, the default stream."""
+        assert rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2 and (rows.shape[1] <= 1 or rows.stride(1) == 1)
+        n = rows.shape[0]
+        lanes = np.ascontiguousarray(np.asarray(list(sids), dtype=np.int32))
+        num = np.ascontiguousarray(np.asarray(lens, dtype=np.int64))
+        assert lanes.shape == (n,) and num.shape == (n,)
+        wav_stride = rows.stride(0) if n > 1 else max(rows.shape[1], 1)
+        n_w = num // self.window
+        stride = max(int(n_w.max()) if n else 0, 0)
+        probs = torch.zeros(n, stride, dtype=torch.float32, device=rows.device)
+        db = torch.zeros(n, stride, dtype=torch.float32, device=rows.device) if want_db else None
+        stats = np.zeros((n, 5), dtype=np.float32)
+        with torch.cuda.device(rows.device):
+            # the entry launches on the default stream: order it behind the producer of `rows` when that is another stream
+            cur = torch.cuda.current_stream(rows.device)
+            if cur.cuda_stream != 0:
+                cur.synchronize()
+            check(self.lib.sc_vad_stream_push(self.handle, _ptr(lanes), n, _ptr(rows), wav_stride, _ptr(num), _ptr(probs), stride, _ptr(db),
+                                              _ptr(stats)), "sc_vad_stream_push")
+        self.pushes += 1
+        return probs, n_w, db, stats
+
+    def close(self) -> None:
+        if self.handle is not None:
+            self.lib.sc_vad_stream_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self) -> None:
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 RESAMPLING_METHODS = {"sinc_interp_hann": 0, "sinc_interp_kaiser": 1}

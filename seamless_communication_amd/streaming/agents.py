@@ -71,6 +71,9 @@ _OPTION_DEFAULTS = {
     "vocoder": dict(vocoder_speaker_id=-1),
     "expressive": dict(vocoder_name="vocoder_pretssel", upstream_idx=0, expressive=False, expr_vocoder_name=None),
     "detok": dict(detokenize_only=True),
+    # the VAD stage in front of a chain (streaming/vad.py; silero_vad.py's add_args, checked in tests/test_vad_agent_cpu.py)
+    "vad": dict(window_size_samples=512, chunk_size_samples=5120, silence_limit_ms=700, speech_soft_limit_ms=12000,
+                init_speech_prob=0.15),
 }
 
 
@@ -881,7 +884,8 @@ class SeamlessS2STAgent(UnitYAgentPipeline):
 
 class SeamlessS2STDualVocoderAgent(UnitYAgentPipeline):
     """The same chain ending in the stage that holds both vocoders.  The reference has this stage only behind its VAD tree
-    pipeline (seamless_s2st.py:56-65), which is not restated; this is its linear counterpart."""
+    pipeline (seamless_s2st.py:56-65); this is its linear counterpart (with the VAD stage in front: streaming/vad.py,
+    SeamlessS2STDualVocoderVADAgent; the tree form itself is not restated)."""
 
     def __init__(self, backend, text_tokenizer, args: Optional[Namespace] = None) -> None:
         args = args or default_args()

@@ -68,6 +68,7 @@ class HipStreamingBackend:
         if pretssel_generator is not None and pretssel_generator.wave_model is None:
             raise ValueError("the expressive chain needs a PretsselGenerator whose checkpoint holds the waveform generator")
         self._prosody: Optional[ProsodyHistory] = None
+        self._detectors: Dict[int, Any] = {}
 
     # WaveformToFbankConverter(num_mel_bins=80, waveform_scale, standardize=False) (online_feature_extractor.py:65-71).
     # The fbank kernel multiplies by 2**15; scaling the samples by waveform_scale / 2**15 first is exact (power of two).
@@ -87,6 +88,16 @@ class HipStreamingBackend:
             seqs = torch.nn.functional.pad(seqs, (0, 0, 0, self.cfg.fbank_stride - T % self.cfg.fbank_stride))
         enc, lens = self.model.encode_speech(seqs.unsqueeze(0).contiguous(), [T])
         return enc[:, : int(lens[0])]
+
+    def vad_lane(self, window: int = 512) -> Any:
+        """What a VAD-headed chain on this backend scores its windows with when the caller passes no ``vad=``: lane 0 of a
+        ``StreamingSpeechDetector`` of its own (this project's energy detector, not the reference's Silero VAD and not evaluated on
+        real speech).  One backend serves one session at a time."""
+        if window not in self._detectors:
+            from ..audio import StreamingSpeechDetector
+
+            self._detectors[window] = StreamingSpeechDetector(1, window, device=self.model.device)
+        return self._detectors[window].lane(0)
 
     def mma_begin(self, enc: Tensor, max_len: int) -> None:
         self.model.mma_begin(enc, min(int(max_len), self.cfg.text_max_seq_len))

@@ -20,6 +20,14 @@ Pool backends (the interface ``StreamingSessionPool`` drives):
     step(sids, feeds, banned)                 ``mma_step`` for the named sessions -> (ids, p_choose [k][L][H], [rows_i])
     max_len                                   tokens a session may feed between two begins (None: no limit of the pool's own)
 
+Chains with a VAD stage in front (``streaming/vad.py``) are served as endless streams: before the stage loop the pool asks every VAD
+head what it would score (the ask-twice scheme of the encoder stage), scores all of it in ONE ``speech_probs_many``, and after a
+finished output resets that session's chain.  A session whose chunk is silent reaches no encoder call (``stats()``).  For them a
+pool backend also offers
+
+    speech_probs_many(chunks, sids)           -> [probabilities of the whole windows of chunk i]
+    reset_vad(sid)                            a session opens: its detector lane starts over
+
 ``HipPoolBackend`` is the device path (``sc_mma_pool_*`` + the ragged speech encoder); ``SerialPoolBackend`` offers the same
 interface over one single-session backend per session (the CPU oracle, or ``HipStreamingBackend`` on forked handles).
 """
@@ -32,15 +40,27 @@ from torch import Tensor
 
 from .agents import MMATextDecoderAgent, OfflineWav2VecBertEncoderAgent
 from .simul import Action, AgentPipeline, Segment
+from .vad import SpeechVADAgent, open_lane
 
 
 class SerialPoolBackend:
     """The pool interface over one single-session backend per session: every shared call becomes a loop."""
 
-    def __init__(self, backends: Sequence[Any], max_len: Optional[int] = None) -> None:
+    def __init__(self, backends: Sequence[Any], max_len: Optional[int] = None, vads: Optional[Sequence[Any]] = None) -> None:
         self.backends = list(backends)
         self.sessions = len(self.backends)
         self.max_len = max_len
+        self.vads = None if vads is None else list(vads)  # per session: an object with speech_probs(chunk) (and reset())
+
+    def speech_probs_many(self, chunks: Sequence[Any], sids: Sequence[int]) -> List[List[float]]:
+        if self.vads is None:
+            raise ValueError("this pool backend was built without vads=")
+        return [[float(p) for p in self.vads[s].speech_probs(c)] for s, c in zip(sids, chunks)]
+
+    def reset_vad(self, sid: int) -> None:
+        reset = getattr(self.vads[sid], "reset", None) if self.vads is not None else None
+        if callable(reset):
+            reset()
 
     def session_backend(self, sid: int) -> Any:
         return self.backends[sid]
@@ -62,13 +82,35 @@ class HipPoolBackend:
     ``encode_speech_ragged`` (one packed pass, an item's bits independent of the batch) and the text decoder on a
     ``MonotonicDecoderPool``.  The expressive chains are not served (one prosody history per backend)."""
 
-    def __init__(self, model, cfg, sessions: int, max_len: int, s_enc_cap: int, lang_spkr_idx_map: Optional[Dict[str, Any]] = None) -> None:
+    def __init__(self, model, cfg, sessions: int, max_len: int, s_enc_cap: int, lang_spkr_idx_map: Optional[Dict[str, Any]] = None,
+                 vad: bool = False, vad_window: int = 512, **vad_opts: Any) -> None:
+        """``vad=True``: the backend owns one streaming speech detector with a lane per session (``sc_vad_stream_*``: this
+        project's energy detector, not the reference's Silero VAD, not evaluated on real speech) and serves
+        VAD-headed chains.  Off by default."""
         from .backend import HipStreamingBackend
 
         self.model, self.cfg = model, cfg
         self.single = HipStreamingBackend(model, cfg, lang_spkr_idx_map)
         self.sessions, self.max_len, self.s_enc_cap = int(sessions), int(max_len), int(s_enc_cap)
         self.pool = model.mma_pool(sessions, max_len, s_enc_cap)
+        self.detector = None
+        if vad:
+            from ..audio import StreamingSpeechDetector
+
+            self.detector = StreamingSpeechDetector(self.sessions, vad_window, device=model.device, **vad_opts)
+        elif vad_opts:
+            raise TypeError(f"{sorted(vad_opts)} are options of the speech detector; pass vad=True")
+
+    def speech_probs_many(self, chunks: Sequence[Any], sids: Sequence[int]) -> List[List[float]]:
+        """All named sessions' chunks in ONE detector push."""
+        if self.detector is None:
+            raise ValueError("this pool backend was built without vad=True")
+        got = self.detector.push(dict(zip(sids, chunks)))
+        return [[float(p) for p in got[s]] for s in sids]
+
+    def reset_vad(self, sid: int) -> None:
+        if self.detector is not None:
+            self.detector.reset(sid)
 
     def session_backend(self, sid: int) -> Any:
         return self.single
@@ -105,10 +147,16 @@ class HipPoolBackend:
         return self.pool.step(sids, feeds, banned)
 
     def stats(self, reset: bool = False) -> Dict[str, int]:
-        return self.pool.stats(reset)
+        """The decoder pool's counters; with ``vad=True`` also ``vad_calls``, the detector pushes made (never reset)."""
+        st = self.pool.stats(reset)
+        if self.detector is not None:
+            st["vad_calls"] = self.detector.calls
+        return st
 
     def close(self) -> None:
         self.pool.close()
+        if self.detector is not None:
+            self.detector.close()
 
 
 class _Deferred(Exception):
@@ -123,6 +171,11 @@ class _SessionBackend:
         self._inner = inner
         self.wanted: Optional[Tensor] = None
         self.answer: Optional[Tensor] = None
+        self.lane = _PoolLane()
+
+    def vad_lane(self, window: Optional[int] = None) -> "_PoolLane":
+        """What a VAD-headed chain built on this backend scores its windows with: the pool's shared detector call."""
+        return self.lane
 
     def __getattr__(self, name: str) -> Any:
         return getattr(self._inner, name)
@@ -135,6 +188,22 @@ class _SessionBackend:
         return enc
 
 
+class _PoolLane:
+    """A session's detector as its VAD stage sees it, answered by the pool like ``encode_speech``: the first ask of a push records
+    the chunk and defers, the second gets the shared call's probabilities."""
+
+    def __init__(self) -> None:
+        self.wanted: Any = None
+        self.answer: Optional[List[float]] = None
+
+    def speech_probs(self, chunk: Any) -> List[float]:
+        if self.answer is None:
+            self.wanted = chunk
+            raise _Deferred()
+        probs, self.answer, self.wanted = self.answer, None, None
+        return probs
+
+
 class _Session:
     def __init__(self, agent: AgentPipeline, backend: _SessionBackend) -> None:
         self.agent, self.backend = agent, backend
@@ -143,6 +212,8 @@ class _Session:
         self.text = next((i for i, a in enumerate(mods) if isinstance(a, MMATextDecoderAgent)), None)
         if self.encoder is None or self.text is None or self.text <= self.encoder:
             raise ValueError("the session pool drives chains with a speech encoder stage followed by a monotonic text decoder stage")
+        self.vad_headed = isinstance(mods[0], SpeechVADAgent)
+        self.utterance = 0  # of a VAD-headed session: the index its next output carries
 
 
 class StreamingSessionPool:
@@ -155,6 +226,8 @@ class StreamingSessionPool:
     def __init__(self, backend: Any, make_agent: Callable[..., AgentPipeline], sessions: int) -> None:
         self.backend, self.make_agent, self.sessions = backend, make_agent, int(sessions)
         self._open: Dict[int, _Session] = {}
+        self._stats = {"push_rounds": 0, "vad_calls": 0, "encode_calls": 0}
+        self._encoded: Dict[int, int] = {}  # per session: encoder passes its chunks led to
 
     def open(self, sid: int, **agent_args: Any) -> AgentPipeline:
         if not 0 <= sid < self.sessions:
@@ -162,8 +235,19 @@ class StreamingSessionPool:
         if sid in self._open:
             raise ValueError(f"session {sid} is open")
         proxy = _SessionBackend(self.backend.session_backend(sid))
-        self._open[sid] = _Session(self.make_agent(proxy, **agent_args), proxy)
-        return self._open[sid].agent
+        s = self._open[sid] = _Session(self.make_agent(proxy, **agent_args), proxy)
+        self._encoded[sid] = 0
+        if s.vad_headed:  # the session opens: its detector lane starts over
+            if s.agent.module_list[0].vad is proxy.lane:
+                self.backend.reset_vad(sid)
+            else:
+                open_lane(s.agent.module_list[0])
+        return s.agent
+
+    def stats(self) -> Dict[str, Any]:
+        """``push_rounds``, ``vad_calls`` and ``encode_calls`` (shared calls made, at most one of each per round) and
+        ``encoded_by_session`` (sid -> how many of its pushes reached the speech encoder) since the pool was built."""
+        return dict(self._stats, encoded_by_session=dict(self._encoded))
 
     def close(self, sid: int) -> None:
         del self._open[sid]
@@ -187,9 +271,13 @@ class StreamingSessionPool:
         upstream: Dict[int, Dict[int, Any]] = {sid: {} for sid in sids}
         depth = {len(sess[sid].agent.module_list) for sid in sids}
         out: Dict[int, Segment] = {}
+        self._stats["push_rounds"] += 1
+        heard = self._detect(sess, [sid for sid in sids if sess[sid].vad_headed], seg, upstream)
         for i in range(max(depth)):
             here = [sid for sid in sids if i < len(sess[sid].agent.module_list)]
             for sid in here:  # AgentPipeline.push, one stage at a time
+                if i == 0 and sid in heard:
+                    continue  # the VAD head took its segment while it was asked what it would score
                 sess[sid].agent.module_list[i].push(seg[sid], None, upstream[sid])
             shared_enc = [sid for sid in here if sess[sid].encoder == i]
             shared_text = [sid for sid in here if sess[sid].text == i]
@@ -215,7 +303,35 @@ class StreamingSessionPool:
                 finally:
                     if sid in actions:
                         del module.policy
+        for sid in sids:
+            s = sess[sid]
+            if s.vad_headed:  # an endless stream: a finished output ends an utterance, not the session
+                out[sid].utterance = s.utterance
+                if out[sid].finished:
+                    s.agent.reset()
+                    s.utterance += 1
         return out
+
+    def _detect(self, sess: Dict[int, _Session], sids: Sequence[int], seg: Dict[int, Segment], upstream: Dict[int, Dict[int, Any]]) -> set:
+        """The VAD heads: pushes every head its segment - a head on the pool's lane defers at the first thing it does with it, the
+        ask for probabilities -, scores all deferred chunks in one call and leaves the answers where the second push finds them.
+        Returns the sessions whose head has taken its segment already (it asked nothing, or it has a detector of its own)."""
+        asking: List[int] = []
+        taken = set()
+        for sid in sids:
+            s = sess[sid]
+            s.backend.lane.wanted = s.backend.lane.answer = None
+            try:
+                s.agent.module_list[0].push(seg[sid], None, upstream[sid])
+                taken.add(sid)
+            except _Deferred:
+                asking.append(sid)
+        if asking:
+            probs = self.backend.speech_probs_many([sess[sid].backend.lane.wanted for sid in asking], asking)
+            self._stats["vad_calls"] += 1
+            for sid, p in zip(asking, probs):
+                sess[sid].backend.lane.answer = list(p)
+        return taken
 
     def _encode(self, sess: Dict[int, _Session], sids: Sequence[int]) -> None:
         """Stage 2: asks every encoder stage what it would encode, encodes all of it in one call, leaves the answers where the
@@ -234,6 +350,9 @@ class StreamingSessionPool:
         if not asking:
             return
         encs = self.backend.encode_speech_many([sess[sid].backend.wanted for sid in asking], asking)
+        self._stats["encode_calls"] += 1
+        for sid in asking:
+            self._encoded[sid] += 1
         for sid, enc in zip(asking, encs):
             sess[sid].backend.answer = enc
 
