@@ -558,6 +558,21 @@ int sc_t2u_nar(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text
 int sc_t2u_nar_cond(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text, const int32_t* h_text_lens,
                     const int32_t* h_text_seqs, float duration_factor, const float* d_cond, int32_t* h_unit_lens,
                     int32_t* out_s_unit_max, int32_t* out_s_char_max);
+/* sc_t2u_nar with one duration factor PER ITEM, fitted on the device to a unit budget (added within ABI v10, purely additive;
+ * an extension of this project for long-form speech translation, no reference counterpart).  With
+ * e_k = exp(x_k) - 1 of item b's characters (x_k: the duration predictor's output, as in sc_t2u_nar),
+ * dur_k(f) = clamp(round_half_even(e_k * f), 1, 1000000) and U_b(f) = sum_k dur_k(f), the item's factor is the largest point of
+ * the grid f_j = min(hi, lo + (hi - lo) * j / 65536), j = 0..65536 (f_65536 = hi exactly; fp32, each operation rounded), with
+ * U_b(f_j) <= h_target_units[b].  A target of 0 is no budget: the factor is h_hi[b].  If even h_lo[b] does not fit, the factor
+ * is h_lo[b] and bit 0 of h_flags[b] is set.  h_factor [n] and h_flags [n] are written; units, lengths and durations stay in
+ * the handle as for sc_t2u_nar.  Row b equals row b of sc_t2u_nar / sc_t2u_nar_cond on the same batch with duration_factor =
+ * h_factor[b].  d_cond: NULL, or [n][film_cond_dim] for a FiLM-conditioned model (required there, refused elsewhere).
+ * SC_ERR_INVALID before any device work, sc_last_error naming the item: a null pointer, a negative target, a bound that is not
+ * finite, lo <= 0, lo > hi. */
+int sc_t2u_nar_fit(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text, const int32_t* h_text_lens,
+                   const int32_t* h_text_seqs, const int32_t* h_target_units, const float* h_lo, const float* h_hi,
+                   const float* d_cond, int32_t* h_unit_lens, int32_t* out_s_unit_max, int32_t* out_s_char_max, float* h_factor,
+                   int32_t* h_flags);
 int sc_get_units(sc_model* m, int32_t* h_units /* [n][s_unit_max], pad = unit_pad_idx */);
 int sc_get_durations(sc_model* m, int32_t* h_durations /* [n][s_char_max] */, int32_t* h_char_ids,
                      int32_t* h_char_seq_lens);
@@ -833,6 +848,23 @@ typedef struct sc_resample_opts {
 int64_t sc_resample_len(int64_t num_samples, int32_t orig_freq, int32_t new_freq);
 int sc_resample(const float* d_in, int32_t n, int64_t in_stride, const int64_t* h_in_len, int32_t orig_freq, int32_t new_freq,
                 const sc_resample_opts* opts, float* d_out, int64_t out_stride, int64_t* h_out_len);
+
+/* ---- Timeline mix (added within ABI v10, purely additive; an extension for long-form speech translation, no reference
+ * counterpart): n waveforms placed at absolute sample offsets in one track of T samples, with linear fades
+ * at their edges, over an optional bed that is attenuated where a segment sounds.  No handle, current device, default stream,
+ * returns when d_out is complete (the conventions of sc_resample).
+ *   d_seg [n][seg_stride] fp32, row i valid up to h_len[i];  h_start [n] ascending, segment i covers [h_start[i], h_start[i] + h_len[i])
+ *   w_i(k) = min(1, min(k + 1, L_i - k) / (fade + 1));  c(t) = max_i clamp(1 - dist_i(t) / (ramp + 1), 0, 1), dist_i(t) the
+ *   distance in samples from t to segment i (0 inside; an empty segment covers nothing)
+ *   d_out[t] = sum over the segments covering t, ascending i, of h_gain[i] * w_i(t - p_i) * seg_i[t - p_i]
+ *              + d_bed[t] * (1 - (1 - duck) * c(t))            (the bed term last; absent when d_bed is NULL)
+ * in fp32, the exact operation order in k_dub.hip's header.  Overlaps of any depth are legal; every sample of d_out[0, T) is
+ * written (+0.0 where nothing sounds and there is no bed).  SC_ERR_INVALID before any device work: a null pointer, starts not
+ * ascending or negative, a segment past T or longer than seg_stride, duck outside [0, 1], fade or ramp outside 0..2^20, a gain
+ * that is not finite. */
+int sc_mix_timeline(const float* d_seg, int32_t n, int64_t seg_stride, const int32_t* h_len, const int64_t* h_start,
+                    const float* h_gain, int32_t fade, const float* d_bed /* nullable [T] */, float duck, int32_t ramp, float* d_out,
+                    int64_t T);
 
 /* ---- Speech detection (added within ABI v10, purely additive): a speech probability per window of `window` samples, the track
  * the reference takes from Silero VAD (segment/silero_vad.py get_speech_probs) in front of its segmentation of long input.  NOT a

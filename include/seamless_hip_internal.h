@@ -461,6 +461,14 @@ int sc_op_resample_bank(int32_t orig_freq, int32_t new_freq, const sc_resample_o
                         float* h_taps, int64_t cap);
 int sc_op_resample_plan(int32_t orig_freq, int32_t new_freq, const sc_resample_opts* opts, int32_t* h_plan6);
 
+/* The search stage of sc_t2u_nar_fit on GIVEN values e = exp(x) - 1 (k_dub.hip; tests/test_fit_durations_gpu.py): d_e
+ * [n][s_char] fp32 on the device (rows behind h_char_lens[b] are never read), targets / bounds as sc_t2u_nar_fit takes them,
+ * min_dur the lower clamp (0..1000000; the model's is 1).  -> h_durations [n][s_char] (0 behind an item's characters), h_factor
+ * [n], h_total [n] int64 (the item's unit total at its factor), h_flags [n].  No handle, current device, default stream. */
+int sc_op_fit_durations(const float* d_e, int32_t n, int32_t s_char, const int32_t* h_char_lens, const int32_t* h_target,
+                        const float* h_lo, const float* h_hi, int32_t min_dur, int32_t* h_durations, float* h_factor,
+                        int64_t* h_total, int32_t* h_flags);
+
 #ifdef __cplusplus
 }
 #endif

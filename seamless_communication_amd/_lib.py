@@ -239,6 +239,7 @@ SIGNATURES = {
     "sc_engine_get_stats": (C.c_int, [_P, C.POINTER(sc_engine_stats), _i]),
     "sc_t2u_nar": (C.c_int, [_P, _P, _i, _i, _P, _P, C.c_float, _P, _PI, _PI]),
     "sc_t2u_nar_cond": (C.c_int, [_P, _P, _i, _i, _P, _P, C.c_float, _P, _P, _PI, _PI]),
+    "sc_t2u_nar_fit": (C.c_int, [_P, _P, _i, _i, _P, _P, _P, _P, _P, _P, _P, _PI, _PI, _P, _P]),
     "sc_op_t2u_last_launches": (C.c_int32, [_P]),
     "sc_op_t2u_encoder": (C.c_int, [_P, _P, _i, _i, _P, _P, _P]),
     "sc_get_units": (C.c_int, [_P, _P]),
@@ -308,6 +309,7 @@ SIGNATURES = {
     "sc_op_seanet_tail": (C.c_int, [_P, _P, _P, _i, _i, _i, _P, _P, _P, _P, C.c_int64]),
     "sc_resample_len": (C.c_int64, [C.c_int64, _i, _i]),
     "sc_resample": (C.c_int, [_P, _i, C.c_int64, _P, _i, _i, C.POINTER(sc_resample_opts), _P, C.c_int64, _P]),
+    "sc_mix_timeline": (C.c_int, [_P, _i, C.c_int64, _P, _P, _P, _i, _P, C.c_float, _i, _P, C.c_int64]),
     "sc_vad_windows": (C.c_int64, [C.c_int64, _i]),
     "sc_vad_probs": (C.c_int, [_P, _i, C.c_int64, _P, _i, C.POINTER(sc_vad_opts), _P, C.c_int64, _P, _P]),
     "sc_vad_stream_create": (C.c_int, [_i, _i, C.POINTER(sc_vad_stream_opts), C.POINTER(_P)]),
@@ -319,6 +321,7 @@ SIGNATURES = {
     "sc_edit_distance": (C.c_int, [_P, _P, _i, _P, C.c_int64, _P]),
     "sc_op_resample_bank": (C.c_int, [_i, _i, C.POINTER(sc_resample_opts), _PI, _PI, _P, _P, C.c_int64]),
     "sc_op_resample_plan": (C.c_int, [_i, _i, C.POINTER(sc_resample_opts), _P]),
+    "sc_op_fit_durations": (C.c_int, [_P, _i, _i, _P, _P, _P, _P, _i, _P, _P, _P, _P]),
     "sc_op_knob": (C.c_int, [C.c_char_p, C.c_int]),
     "sc_op_force_general_gemm": (C.c_int, [C.c_int]),
     "sc_op_voc_pack_plan": (C.c_int32, [_PI, C.c_int32, C.c_int64, _PI, C.c_int32]),

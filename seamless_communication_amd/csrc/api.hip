@@ -650,6 +650,24 @@ int sc_t2u_nar_cond(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s
     SC_API_END
 }
 
+int sc_t2u_nar_fit(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text, const int32_t* h_text_lens, const int32_t* h_text_seqs,
+                   const int32_t* h_target_units, const float* h_lo, const float* h_hi, const float* d_cond, int32_t* h_unit_lens,
+                   int32_t* out_s_unit_max, int32_t* out_s_char_max, float* h_factor, int32_t* h_flags) {
+    SC_API_BEGIN
+    // every argument check comes before the first device call
+    SC_CHECK(m && d_dec_hidden && h_text_lens && h_text_seqs && h_target_units && h_lo && h_hi && h_factor && h_flags,
+             "sc_t2u_nar_fit: null argument");
+    SC_CHECK(n > 0, "sc_t2u_nar_fit: empty batch");
+    check_fit_items("sc_t2u_nar_fit", n, h_target_units, h_lo, h_hi);
+    SC_CHECK(m->m.film_cond_dim <= 0 || d_cond, "sc_t2u_nar_fit: this T2U is FiLM-conditioned (film_cond_dim=%d): d_cond is required",
+             m->m.film_cond_dim);
+    SC_CHECK(m->m.film_cond_dim > 0 || !d_cond, "sc_t2u_nar_fit: the model was loaded without FiLM conditioning, d_cond must be null");
+    SC_HIP(hipSetDevice(m->m.device));
+    const T2uFit fit{h_target_units, h_lo, h_hi, h_factor, h_flags};
+    run_t2u_nar(m->m, d_dec_hidden, n, s_text, h_text_lens, h_text_seqs, 1.0f, h_unit_lens, out_s_unit_max, out_s_char_max, d_cond, &fit);
+    SC_API_END
+}
+
 int32_t sc_op_t2u_last_launches(sc_model* m) { return m ? m->m.last_t2u_launches : -1; }
 
 int sc_op_t2u_encoder(sc_model* m, const float* d_dec_hidden, int32_t n, int32_t s_text, const int32_t* h_text_lens, float* d_out,

@@ -849,6 +849,29 @@ void launch_pos_add(float* seqs, int64_t ld, const float* pos_table, int t_per_b
 void launch_durations(const float* h /*[rows][H]*/, int64_t ld, const float* w, const float* b,
                       int rows, int H, int t_per_batch, const int* lens, float duration_factor,
                       int min_dur, int* durations, hipStream_t s);
+// The duration rule with one factor per item, fitted on the device to a unit budget (k_dub.hip).  One
+// workgroup per item b of n; rows are [n][s_char].
+struct FitArgs {
+    const float* h = nullptr;  // [n * s_char][ld] duration predictor features; null: e holds the values expf(x) - 1 already
+    int64_t ld = 0;
+    const float* w = nullptr;  // [H], b [1]: VariancePredictor.proj
+    const float* b = nullptr;
+    int H = 0;
+    float* e = nullptr;           // [n][s_char] scratch row per item (written by stage 1, read by the search)
+    int s_char = 0;
+    const int* lens = nullptr;    // [n] characters per item
+    const int* target = nullptr;  // [n] unit budget, 0: none
+    const float* lo = nullptr;    // [n] 0 < lo <= hi
+    const float* hi = nullptr;
+    int min_dur = 1;
+    int* durations = nullptr;     // [n][s_char], 0 behind an item's characters
+    float* factor = nullptr;      // [n]
+    long long* total = nullptr;   // [n] sum of the item's durations
+    int* flags = nullptr;         // [n] bit 0: even lo does not fit the budget
+};
+void launch_fit_durations(const FitArgs& a, int n, hipStream_t s);
+// SC_ERR_INVALID naming the item: a negative target, a bound that is not finite, lo <= 0, lo > hi (host only)
+void check_fit_items(const char* who, int n, const int32_t* h_target, const float* h_lo, const float* h_hi);
 void launch_vocoder_embed(const int* units, int nb, int T, const __half* dict, int E,
                           const __half* lang, int Lg, const int* lang_idx, const __half* spkr, int Sp,
                           const int* spkr_idx, float* out /*[nb*T][Lg+E+Sp]*/, hipStream_t s,

@@ -407,9 +407,18 @@ void run_score_text(Model& m, const float* d_enc, int n, int s_enc, const int32_
                     const int32_t* h_tok_lens, int s_text, float* h_tok_lprob, float* h_sum_lprob, int32_t* h_top1, float* d_dec_hidden,
                     float* d_xattn = nullptr);
 // d_cond: [n][film_cond_dim] on the device for a FiLM model, null otherwise (a mismatch is an error)
+// fit: null runs launch_durations with duration_factor, as ever.  Otherwise the fit kernel (k_dub.hip) takes that one launch's
+// place with one factor per item, duration_factor is unused, and everything behind it reads the per-character durations as before.
+struct T2uFit {
+    const int32_t* h_target;  // [n] unit budget per item, 0: none
+    const float* h_lo;        // [n] bounds of the item's factor
+    const float* h_hi;
+    float* h_factor;          // [n] out
+    int32_t* h_flags;         // [n] out, bit 0: over budget at lo
+};
 void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const int32_t* h_text_lens,
                  const int32_t* h_text_seqs, float duration_factor, int32_t* h_unit_lens, int32_t* out_su,
-                 int32_t* out_sc, const float* d_cond = nullptr);
+                 int32_t* out_sc, const float* d_cond = nullptr, const T2uFit* fit = nullptr);
 // h_unit_lens == null: the whole padded batch.  Otherwise only the first h_unit_lens[i] * hop samples of row i are
 // guaranteed (computed exactly as in the padded batch), the rest of the row is zero.
 // Conv1d (stride 1, 'same'-style padding) on pre-split planes through the DMA GEMM (k_gemm_ps.hip, implicit-conv mode):

@@ -308,7 +308,7 @@ void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, con
 
 void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const int32_t* h_text_lens,
                  const int32_t* h_text_seqs, float duration_factor, int32_t* h_unit_lens, int32_t* out_su,
-                 int32_t* out_sc, const float* d_cond) {
+                 int32_t* out_sc, const float* d_cond, const T2uFit* fit) {
     const sc_config& c = m.cfg;
     const int M = c.model_dim;
     SC_CHECK(c.has_t2u, "sc_t2u_nar: the model was loaded without a T2U sub-model");
@@ -396,9 +396,29 @@ void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const i
             layernorm(m, a, m.dp_ln2, b, crows);
         }
         launches += 7;  // gather, character embedding, conv, LayerNorm, conv, LayerNorm (+ FiLM), durations
-        launch_durations(b, H, m.dp_proj_w, m.dp_proj_b, crows, H, Sc, d_clens, duration_factor, 1, d_dur, m.stream);
-        SC_HIP(hipMemcpyAsync(dur.data(), d_dur.get(), (size_t)crows * 4, hipMemcpyDeviceToHost, m.stream));
-        SC_HIP(hipStreamSynchronize(m.stream));
+        if (!fit) {
+            launch_durations(b, H, m.dp_proj_w, m.dp_proj_b, crows, H, Sc, d_clens, duration_factor, 1, d_dur, m.stream);
+            SC_HIP(hipMemcpyAsync(dur.data(), d_dur.get(), (size_t)crows * 4, hipMemcpyDeviceToHost, m.stream));
+            SC_HIP(hipStreamSynchronize(m.stream));
+        } else {
+            // one factor per item, searched on the device where the log-durations are (k_dub.hip): the same dot product and
+            // exponential, then the duration rule at the largest grid factor whose unit total fits the item's budget
+            Buf<float> e(m.pp(), (size_t)crows), d_bounds(m.pp(), (size_t)3 * n);
+            Buf<int> d_target(m.pp(), (size_t)2 * n);
+            Buf<long long> d_total(m.pp(), n);
+            SC_HIP(hipMemcpyAsync(d_target.get(), fit->h_target, (size_t)n * 4, hipMemcpyHostToDevice, m.stream));
+            SC_HIP(hipMemcpyAsync(d_bounds.get(), fit->h_lo, (size_t)n * 4, hipMemcpyHostToDevice, m.stream));
+            SC_HIP(hipMemcpyAsync(d_bounds.get() + n, fit->h_hi, (size_t)n * 4, hipMemcpyHostToDevice, m.stream));
+            FitArgs f;
+            f.h = b, f.ld = H, f.w = m.dp_proj_w, f.b = m.dp_proj_b, f.H = H;
+            f.e = e, f.s_char = Sc, f.lens = d_clens, f.target = d_target, f.lo = d_bounds, f.hi = d_bounds.get() + n, f.min_dur = 1;
+            f.durations = d_dur, f.factor = d_bounds.get() + 2 * n, f.total = d_total, f.flags = d_target.get() + n;
+            launch_fit_durations(f, n, m.stream);
+            SC_HIP(hipMemcpyAsync(dur.data(), d_dur.get(), (size_t)crows * 4, hipMemcpyDeviceToHost, m.stream));
+            SC_HIP(hipMemcpyAsync(fit->h_factor, f.factor, (size_t)n * 4, hipMemcpyDeviceToHost, m.stream));
+            SC_HIP(hipMemcpyAsync(fit->h_flags, f.flags, (size_t)n * 4, hipMemcpyDeviceToHost, m.stream));
+            SC_HIP(hipStreamSynchronize(m.stream));
+        }
     }
 
     // ---- host: unit-level gather index -------------------------------------------------

@@ -43,6 +43,7 @@ from .generator import SequenceGeneratorOptions, check_sampling, encode_bias_phr
 from ..scoring import score as _score
 from ..mbr import MBRHypothesis, mbr_decode as _mbr_decode, mbr_decode_beam as _mbr_decode_beam
 from ..lid import LanguageId, identify_encoded as _identify_encoded, identify_language as _identify_language
+from ..longform import translate_long as _translate_long
 
 logger = logging.getLogger(__name__)
 
@@ -597,6 +598,8 @@ class Translator:
     score = _score
     # spoken-language identification (lid.py)
     identify_language = _identify_language
+    # long-form speech translation: timed segments and one dubbed track (longform.py)
+    translate_long = _translate_long
 
     def _speech_from_ar_units(self, units: np.ndarray, pad: int, tgt_lang: str, spkr: Optional[int], sample_rate: int,
                               t_start: float) -> BatchedSpeechOutput:
@@ -795,6 +798,7 @@ class Translator:
         prosody_encoder_input: Optional[SequenceData] = None,
         _trace: Optional[Dict[str, Any]] = None,
         forced_prefix: Any = None,
+        unit_fit: Optional[Tuple[Any, Any, Any]] = None,
     ) -> Tuple[List[StringLike], Optional[Tensor]]:
         """``UnitYGenerator(model, ...)(seqs, padding_mask, ...)`` of the reference (inference/generator.py:86-353)
         on the HIP model: returns the texts and, for speech output, the decoded unit matrix ``(N, S_u)`` int64 with
@@ -805,7 +809,12 @@ class Translator:
         ``unit_generation_opts`` and ``unit_generation_ngram_filtering`` are disregarded for the NAR T2U model like in
         the reference (translator.py:173-177, generator.py:338-353).  ``_trace`` (not part of the reference API)
         receives the ids / per-stage data the batch driver and the parity tests read back.  ``forced_prefix`` (not part of
-        the reference API): as ``predict``'s; the decoder outputs of the forced positions feed the T2U model like any others."""
+        the reference API): as ``predict``'s; the decoder outputs of the forced positions feed the T2U model like any others.
+        ``unit_fit`` (not part of the reference API; ``translate_long``): ``(targets, lo, hi)`` - a unit budget per row (0: none)
+        and the bounds of the row's duration factor; the NAR T2U then runs ``t2u_nar_fit`` in place of ``t2u_nar``,
+        ``duration_factor`` is unused and the trace's ``"t2u"`` entry also carries ``factors`` and ``flags``.  None changes nothing."""
+        if unit_fit is not None and getattr(model, "t2u_variant", 0) == 1:
+            raise ValueError("unit_fit needs the NAR T2U (UnitY2): the v1 models take their durations from the vocoder")
         # (a parsed value passes through unchanged)
         forced = parse_forced_prefix(text_tokenizer, forced_prefix, tgt_lang) if forced_prefix is not None else None
         prosody_encoder = getattr(model, "prosody_encoder", None)
@@ -927,7 +936,13 @@ class Translator:
             if p_seqs.dim() != 3 or p_seqs.shape[0] != hidden.shape[0]:
                 raise ValueError(f"prosody_encoder_input['seqs'] must be (N, T, {prosody_encoder.cfg.input_dim}) with N = {hidden.shape[0]}")
             cond_kw["cond"] = prosody_encoder.encode(p_seqs.to(model.device, torch.float32), p_lens)
-        units, unit_lens, dur, cids, clens = model.t2u_nar(hidden, text_seqs, text_lens, duration_factor, **cond_kw)
+        fit_kw: Dict[str, Any] = {}
+        if unit_fit is not None:
+            targets, lo, hi = unit_fit
+            units, unit_lens, dur, cids, clens, factors, flags = model.t2u_nar_fit(hidden, text_seqs, text_lens, targets, lo, hi, **cond_kw)
+            fit_kw = {"factors": factors, "flags": flags}
+        else:
+            units, unit_lens, dur, cids, clens = model.t2u_nar(hidden, text_seqs, text_lens, duration_factor, **cond_kw)
         trace["stage_ms"]["t2u"] = (time.perf_counter() - t3) * 1e3
-        trace["t2u"] = {"units": units, "unit_lens": unit_lens, "durations": dur, "char_ids": cids, "char_seq_lens": clens}
+        trace["t2u"] = {"units": units, "unit_lens": unit_lens, "durations": dur, "char_ids": cids, "char_seq_lens": clens, **fit_kw}
         return texts, torch.from_numpy(units.astype(np.int64))

@@ -10,7 +10,7 @@ import contextlib
 import ctypes as C
 import math
 import threading
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -687,6 +687,44 @@ class HipS2STModel(_Handle):
         clens = np.zeros(n, dtype=np.int32)
         check(self.lib.sc_get_durations(self.handle, _ptr(dur), _ptr(cids), _ptr(clens)), "sc_get_durations")
         return units, ulens, dur, cids, clens
+
+    def t2u_nar_fit(self, dec_hidden: torch.Tensor, text_seqs: np.ndarray, text_lens: Sequence[int], target_units: Sequence[int],
+                    lo: Any, hi: Any, cond: Optional[torch.Tensor] = None):
+        """``t2u_nar`` with one duration factor per item, fitted on the device to a unit budget (``sc_t2u_nar_fit``; DESIGN.md
+        section 7v): item b gets the largest factor of a 65 537-point grid over ``[lo[b], hi[b]]`` whose unit total stays within
+        ``target_units[b]`` (0: no budget, the factor is ``hi[b]``).  ``lo`` / ``hi``: one value for all items or one per item.
+        -> (units, unit_lens, durations, char ids, char_seq_lens, factors (n,) float32, flags (n,) int32 - bit 0: even ``lo`` is
+        over the budget).  Row b equals row b of ``t2u_nar`` on the same batch with ``duration_factor = factors[b]``."""
+        if not self._has_nar_tables:
+            raise SeamlessHipError("set_nar_tables() must be called before t2u_nar_fit()")
+        assert dec_hidden.is_cuda and dec_hidden.is_contiguous()
+        n, s_text, _ = dec_hidden.shape
+        ts = _i32(text_seqs)
+        assert ts.shape == (n, s_text), (ts.shape, (n, s_text))
+        tl = _i32(text_lens)
+        tg = _i32(target_units).reshape(-1)
+        lo_a = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float32), (n,)))
+        hi_a = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float32), (n,)))
+        if tg.shape != (n,):
+            raise ValueError(f"target_units must hold one entry per item ({n}), got {tg.shape}")
+        if cond is not None:
+            if not (cond.is_cuda and cond.dtype == torch.float32 and cond.dim() == 2 and cond.shape[0] == n):
+                raise ValueError(f"cond must be a float32 device tensor of shape ({n}, film_cond_dim), got {tuple(cond.shape)} {cond.dtype}")
+            cond = cond.contiguous()
+        ulens = np.zeros(n, dtype=np.int32)
+        factors = np.zeros(n, dtype=np.float32)
+        flags = np.zeros(n, dtype=np.int32)
+        su, sc_ = C.c_int32(0), C.c_int32(0)
+        self._after_torch()
+        check(self.lib.sc_t2u_nar_fit(self.handle, _ptr(dec_hidden), n, s_text, _ptr(tl), _ptr(ts), _ptr(tg), _ptr(lo_a), _ptr(hi_a), _ptr(cond),
+                                      _ptr(ulens), C.byref(su), C.byref(sc_), _ptr(factors), _ptr(flags)), "sc_t2u_nar_fit")
+        units = np.zeros((n, su.value), dtype=np.int32)
+        check(self.lib.sc_get_units(self.handle, _ptr(units)), "sc_get_units")
+        dur = np.zeros((n, sc_.value), dtype=np.int32)
+        cids = np.zeros((n, sc_.value), dtype=np.int32)
+        clens = np.zeros(n, dtype=np.int32)
+        check(self.lib.sc_get_durations(self.handle, _ptr(dur), _ptr(cids), _ptr(clens)), "sc_get_durations")
+        return units, ulens, dur, cids, clens, factors, flags
 
     def t2u_encoder(self, dec_hidden: torch.Tensor, text_lens: Sequence[int]):
         """The T2U encoder by itself (``sc_op_t2u_encoder``) -> (output (n, s_text, M) float32 on the device, rows computed)."""
@@ -1414,3 +1452,54 @@ def resample_rows(rows: torch.Tensor, lens: Sequence[int], orig_freq: int, new_f
         check(lib.sc_resample(_ptr(rows), n, rows.shape[1], _ptr(in_len), int(orig_freq), int(new_freq),
                               C.byref(opts) if opts is not None else None, _ptr(out), stride, _ptr(got)), "sc_resample")
     return out, got
+
+
+FIT_OVER = 1  # bit 0 of the flags of sc_t2u_nar_fit / sc_op_fit_durations: even the lower bound is over the budget
+
+
+def fit_durations(e: torch.Tensor, char_lens: Sequence[int], targets: Sequence[int], lo: Any, hi: Any, min_dur: int = 1):
+    """``sc_op_fit_durations``: the search stage of ``sc_t2u_nar_fit`` on given values ``e = exp(x) - 1`` (n, s_char) float32 on a
+    HIP device -> (durations (n, s_char) int32, factors (n,) float32, totals (n,) int64, flags (n,) int32)."""
+    lib = _lib.load_library()
+    assert e.is_cuda and e.dtype == torch.float32 and e.dim() == 2 and e.is_contiguous()
+    n, s_char = e.shape
+    cl, tg = _i32(char_lens).reshape(-1), _i32(targets).reshape(-1)
+    lo_a = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float32), (n,)))
+    hi_a = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float32), (n,)))
+    assert cl.shape == (n,) and tg.shape == (n,)
+    dur = np.zeros((n, s_char), dtype=np.int32)
+    factors = np.zeros(n, dtype=np.float32)
+    totals = np.zeros(n, dtype=np.int64)
+    flags = np.zeros(n, dtype=np.int32)
+    with torch.cuda.device(e.device):
+        torch.cuda.current_stream(e.device).synchronize()
+        check(lib.sc_op_fit_durations(_ptr(e), n, s_char, _ptr(cl), _ptr(tg), _ptr(lo_a), _ptr(hi_a), int(min_dur), _ptr(dur), _ptr(factors),
+                                      _ptr(totals), _ptr(flags)), "sc_op_fit_durations")
+    return dur, factors, totals, flags
+
+
+def mix_timeline(segs: torch.Tensor, lens: Sequence[int], starts: Sequence[int], gains: Optional[Sequence[float]], fade: int,
+                 bed: Optional[torch.Tensor], duck: float, ramp: int, total: int) -> torch.Tensor:
+    """``sc_mix_timeline``: ``segs`` (n, stride) float32 on a HIP device, row i valid up to ``lens[i]`` and placed at sample
+    ``starts[i]`` (ascending) of a track of ``total`` samples, with linear fades over ``fade`` samples at its edges, over ``bed``
+    (total,) or None, which is attenuated to ``duck`` under the segments with ramps of ``ramp`` samples -> (total,) float32.
+    No handle: the call runs on the tensor's device, on the default stream."""
+    lib = _lib.load_library()
+    assert segs.is_cuda and segs.dtype == torch.float32 and segs.dim() == 2 and segs.is_contiguous()
+    n = segs.shape[0]
+    ln = _i32(lens).reshape(-1)
+    st = np.ascontiguousarray(np.asarray(starts, dtype=np.int64).reshape(-1))
+    g = np.ascontiguousarray(np.asarray([1.0] * n if gains is None else gains, dtype=np.float32).reshape(-1))
+    if not (ln.shape == st.shape == g.shape == (n,)):
+        raise ValueError(f"lens, starts and gains must hold one entry per segment ({n})")
+    if bed is not None:
+        assert bed.is_cuda and bed.dtype == torch.float32 and bed.is_contiguous() and bed.numel() >= int(total) and bed.device == segs.device
+    out = torch.empty(int(total), dtype=torch.float32, device=segs.device)
+    with torch.cuda.device(segs.device):
+        # the entry launches on the default stream: order it behind the producer of `segs` when that is another stream
+        cur = torch.cuda.current_stream(segs.device)
+        if cur.cuda_stream != 0:
+            cur.synchronize()
+        check(lib.sc_mix_timeline(_ptr(segs) if n else None, n, segs.shape[1], _ptr(ln), _ptr(st), _ptr(g), int(fade), _ptr(bed), float(duck),
+                                  int(ramp), _ptr(out), int(total)), "sc_mix_timeline")
+    return out
