@@ -68,4 +68,64 @@ __device__ __forceinline__ float act(float v, int a) {
     return v;
 }
 
+// The greedy step rules on the logits of one row (ArgmaxEpi, kernels.h), once for the three fused vocabulary projections and
+// the finalize kernels.  A row's state is {best tweaked logit, its lowest index idx} and the online log-sum-exp {m, s} of the
+// raw logits, empty as {-inf, 0x7fffffff, -inf, 0}; as a float4 record it is (best, idx bits, m, s).
+// One logit v of feature `feat` (bias added; the caller keeps the raw EOS logit).  no_eos: the step is before
+// min_step_for_eos; force: it is the forced-EOS step.
+__device__ __forceinline__ void argmax_push(float& best, int& idx, float& m, float& s, float v, int feat, const ArgmaxEpi& e, bool no_eos,
+                                            bool force) {
+    if (v > m) {
+        s = s * expf(m - v) + 1.f;
+        m = v;
+    } else {
+        s += expf(v - m);
+    }
+    float tv = v;
+    if (feat == e.unk_idx) tv -= e.unk_penalty;
+    if (feat == e.pad_idx) tv = -INFINITY;
+    if (no_eos && feat == e.eos_idx) tv = -INFINITY;
+    if (force && feat != e.eos_idx) tv = -INFINITY;
+    if (tv > best || (tv == best && feat < idx)) {
+        best = tv;
+        idx = feat;
+    }
+}
+// another state (ob, oi, om, os) of the same row: by value then lower index; (max, sumexp) with the -inf guard
+__device__ __forceinline__ void argmax_merge(float& best, int& idx, float& m, float& s, float ob, int oi, float om, float os) {
+    if (ob > best || (ob == best && oi < idx)) {
+        best = ob;
+        idx = oi;
+    }
+    const float nm = fmaxf(m, om);
+    const float a = (m == -INFINITY) ? 0.f : s * expf(m - nm);
+    const float b = (om == -INFINITY) ? 0.f : os * expf(om - nm);
+    s = a + b;
+    m = nm;
+}
+__device__ __forceinline__ void argmax_merge_lane(float& best, int& idx, float& m, float& s, int o) {  // the lane at distance o
+    const float ob = __shfl_xor(best, o);
+    const int oi = __shfl_xor(idx, o);
+    const float om = __shfl_xor(m, o);
+    const float os = __shfl_xor(s, o);
+    argmax_merge(best, idx, m, s, ob, oi, om, os);
+}
+// The records part[t * stride + b], t < tiles, of row b combined over a workgroup of 256 threads: valid in thread 0.
+__device__ __forceinline__ void argmax_combine_records(const float4* __restrict__ part, int tiles, int stride, int b, float& best,
+                                                       int& idx, float& m, float& s) {
+    __shared__ float4 s_rec[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    best = -INFINITY, idx = 0x7fffffff, m = -INFINITY, s = 0.f;
+    for (int t = tid; t < tiles; t += 256) {
+        const float4 r = part[(int64_t)t * stride + b];
+        argmax_merge(best, idx, m, s, r.x, __float_as_int(r.y), r.z, r.w);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) argmax_merge_lane(best, idx, m, s, o);
+    if (lane == 0) s_rec[wave] = make_float4(best, __int_as_float(idx), m, s);
+    __syncthreads();
+    if (tid == 0)
+        for (int w = 1; w < 4; ++w) argmax_merge(best, idx, m, s, s_rec[w].x, __float_as_int(s_rec[w].y), s_rec[w].z, s_rec[w].w);
+}
+
 }  // namespace sc

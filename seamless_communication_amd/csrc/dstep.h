@@ -98,6 +98,10 @@ bool step2_eligible(const Model& m, const DecStack& W, int nb);
 bool step3_eligible(const Model& m, const DecStack& W, int nb);
 bool step3_wide_eligible(const Model& m, const DecStack& W, int nb);
 int choose_family(const Model& m, const DecStack& W, int rows, int caller);
+// the greedy step projects with the arg-max in the product's epilogue (no logits in HBM) at this many rows and model width
+inline bool fused_argmax_rows(int rows, int M) { return rows <= 64 && M % 64 == 0; }
+// the step rules of a fused vocabulary projection of this context and decoder stack
+ArgmaxEpi step_argmax_epi(const StepCtx& c, const DecStack& W);
 // One decoder step for all batch rows: feeds d_tok at position *d_pos (engine: every slot at its row's position)
 void decoder_step(Model& m, StepCtx& c, bool project);
 // the six planes of a context of c.nb rows (sets c.rb, owns them in c.planes) / the same layout over an existing allocation

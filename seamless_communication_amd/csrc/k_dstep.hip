@@ -90,9 +90,9 @@ __global__ __launch_bounds__(256) void gemvp_kernel(GemvPArgs p) {
     int am_idx[MT][4];
     bool am_force = false, am_no_eos = false;
     if (EPI == EPI_ARGMAX) {
-        const int am_step = p.am_pos ? *p.am_pos : 0;
-        am_force = (p.am_force_eos_step >= 0 && am_step == p.am_force_eos_step);
-        am_no_eos = am_step < p.am_min_step_for_eos;
+        const int am_step = p.am.pos ? *p.am.pos : 0;
+        am_force = (p.am.force_eos_step >= 0 && am_step == p.am.force_eos_step);
+        am_no_eos = am_step < p.am.min_step_for_eos;
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -208,22 +208,8 @@ __global__ __launch_bounds__(256) void gemvp_kernel(GemvPArgs p) {
                             p.partial[((int64_t)split * p.M + m) * p.N + feat] = v;
                         } else {  // EPI_ARGMAX: generation step rules on the logit of column `feat` (argmax_rows_kernel)
                             if (p.bias) v += p.bias[feat];
-                            if (feat == p.am_eos_idx) p.am_eos_logit[m] = v;
-                            if (v > am_m[i][q]) {
-                                am_s[i][q] = am_s[i][q] * expf(am_m[i][q] - v) + 1.f;
-                                am_m[i][q] = v;
-                            } else {
-                                am_s[i][q] += expf(v - am_m[i][q]);
-                            }
-                            float tv = v;
-                            if (feat == p.am_unk_idx) tv -= p.am_unk_penalty;
-                            if (feat == p.am_pad_idx) tv = -INFINITY;
-                            if (am_no_eos && feat == p.am_eos_idx) tv = -INFINITY;
-                            if (am_force && feat != p.am_eos_idx) tv = -INFINITY;
-                            if (tv > am_best[i][q] || (tv == am_best[i][q] && feat < am_idx[i][q])) {
-                                am_best[i][q] = tv;
-                                am_idx[i][q] = feat;
-                            }
+                            if (feat == p.am.eos_idx) p.am.eos_logit[m] = v;
+                            argmax_push(am_best[i][q], am_idx[i][q], am_m[i][q], am_s[i][q], v, feat, p.am, am_no_eos, am_force);
                         }
                     }
                 }
@@ -241,19 +227,7 @@ __global__ __launch_bounds__(256) void gemvp_kernel(GemvPArgs p) {
                 int bidx = am_idx[i][q];
 #pragma unroll
                 for (int o = 16; o > 0; o >>= 1) {
-                    const float ob = __shfl_xor(best, o);
-                    const int oi = __shfl_xor(bidx, o);
-                    if (ob > best || (ob == best && oi < bidx)) {
-                        best = ob;
-                        bidx = oi;
-                    }
-                    const float om = __shfl_xor(mm, o);
-                    const float os = __shfl_xor(ss, o);
-                    const float nm = fmaxf(mm, om);
-                    const float a = (mm == -INFINITY) ? 0.f : ss * expf(mm - nm);
-                    const float b = (om == -INFINITY) ? 0.f : os * expf(om - nm);
-                    ss = a + b;
-                    mm = nm;
+                    argmax_merge_lane(best, bidx, mm, ss, o);
                 }
                 const int m = rb0 + 32 * i + rbase + 8 * q;
                 if (f == 0 && m < live) {
@@ -262,7 +236,7 @@ __global__ __launch_bounds__(256) void gemvp_kernel(GemvPArgs p) {
                     rec.y = __int_as_float(bidx);
                     rec.z = mm;
                     rec.w = ss;
-                    p.am_part[(int64_t)blockIdx.x * p.M + m] = rec;
+                    p.am.part[(int64_t)blockIdx.x * p.M + m] = rec;
                 }
             }
     }
@@ -676,8 +650,8 @@ void launch_gemvp(const GemvPArgs& a0, hipStream_t s) {
     a.w_bytes = (uint32_t)(packed_weight_halfs(a.N, a.K) * 2);
     a.a_bytes = (uint32_t)((int64_t)(a.K / 8) * a.RB * 16);
     dim3 grid(cdiv(a.NT, a.ntl), splits, a.M > 64 ? cdiv(a.M, 64) : 1);
-    SC_CHECK(a.epi != EPI_ARGMAX || a.am_tiles_cap >= (int)grid.x, "gemvp: arg-max partial buffer holds %d tiles, need %d",
-             a.am_tiles_cap, (int)grid.x);
+    SC_CHECK(a.epi != EPI_ARGMAX || a.am.tiles_cap >= (int)grid.x, "gemvp: arg-max partial buffer holds %d tiles, need %d",
+             a.am.tiles_cap, (int)grid.x);
     SC_CHECK((int64_t)(a.K / 8) * a.RB * 16 < (1ll << 31), "gemvp: activation planes too large");
     prof::Scope scope(a.M <= 32 ? "gemvp_m32" : "gemvp_m64", 2.0 * a.M * (double)a.N * a.K,
                       2.0 * a.N * (double)a.K + 4.0 * a.M * ((double)a.K + (double)a.N * splits), s);

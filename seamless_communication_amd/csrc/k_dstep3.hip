@@ -991,14 +991,14 @@ __global__ __launch_bounds__(64 * WAVES) void vocab3_kernel(Vocab3Args p) {
         }
     }
     const int m = r0 + n;
-    int am_step = p.am_pos ? *p.am_pos : 0, am_force_step = p.am_force_eos_step;
+    int am_step = p.am.pos ? *p.am.pos : 0, am_force_step = p.am.force_eos_step;
     if (!LOGITS && p.slot_rp && m < p.M) {  // decode engine: every row at its own position, with its own length limit
         const int2 rp = p.slot_rp[m];
         am_step = rp.y;
         am_force_step = p.limit_row[rp.x] - 2;
     }
     const bool am_force = (am_force_step >= 0 && am_step == am_force_step);
-    const bool am_no_eos = am_step < p.am_min_step_for_eos;
+    const bool am_no_eos = am_step < p.am.min_step_for_eos;
     float best = -INFINITY, mm = -INFINITY, ss = 0.f;
     int bidx = 0x7fffffff;
     __syncthreads();
@@ -1053,22 +1053,8 @@ __global__ __launch_bounds__(64 * WAVES) void vocab3_kernel(Vocab3Args p) {
             if (feat < p.N) {
                 float v = acc[r];
                 if (p.bias) v += p.bias[feat];
-                if (feat == p.am_eos_idx && m < p.M) p.am_eos_logit[m] = v;
-                if (v > mm) {
-                    ss = ss * expf(mm - v) + 1.f;
-                    mm = v;
-                } else {
-                    ss += expf(v - mm);
-                }
-                float tv = v;
-                if (feat == p.am_unk_idx) tv -= p.am_unk_penalty;
-                if (feat == p.am_pad_idx) tv = -INFINITY;
-                if (am_no_eos && feat == p.am_eos_idx) tv = -INFINITY;
-                if (am_force && feat != p.am_eos_idx) tv = -INFINITY;
-                if (tv > best || (tv == best && feat < bidx)) {
-                    best = tv;
-                    bidx = feat;
-                }
+                if (feat == p.am.eos_idx && m < p.M) p.am.eos_logit[m] = v;
+                argmax_push(best, bidx, mm, ss, v, feat, p.am, am_no_eos, am_force);
             }
         }
         t += WAVES;
@@ -1076,42 +1062,21 @@ __global__ __launch_bounds__(64 * WAVES) void vocab3_kernel(Vocab3Args p) {
 #undef V3_LOADW
     if (LOGITS) return;
     // the two k halves of a lane pair hold different features of the same row: combine, then across the waves
-    {
-        const float ob = __shfl_xor(best, 32);
-        const int oi = __shfl_xor(bidx, 32);
-        if (ob > best || (ob == best && oi < bidx)) {
-            best = ob;
-            bidx = oi;
-        }
-        const float om = __shfl_xor(mm, 32);
-        const float os = __shfl_xor(ss, 32);
-        const float nm = fmaxf(mm, om);
-        const float a = (mm == -INFINITY) ? 0.f : ss * expf(mm - nm);
-        const float c2 = (om == -INFINITY) ? 0.f : os * expf(om - nm);
-        ss = a + c2;
-        mm = nm;
-    }
+    argmax_merge_lane(best, bidx, mm, ss, 32);
     __syncthreads();  // every wave is done with the planes
     float4* rec = reinterpret_cast<float4*>(act_lds);
     if (h == 0) rec[wave * 32 + n] = make_float4(best, __int_as_float(bidx), mm, ss);
     __syncthreads();
     if (tid < 32 && m < p.M) {
         float4 r = rec[tid];
+        int ri = __float_as_int(r.y);
 #pragma unroll
         for (int w2 = 1; w2 < WAVES; ++w2) {
             const float4 o = rec[w2 * 32 + tid];
-            const int oi = __float_as_int(o.y), ri = __float_as_int(r.y);
-            if (o.x > r.x || (o.x == r.x && oi < ri)) {
-                r.x = o.x;
-                r.y = o.y;
-            }
-            const float nm = fmaxf(r.z, o.z);
-            const float a = (r.z == -INFINITY) ? 0.f : r.w * expf(r.z - nm);
-            const float c2 = (o.z == -INFINITY) ? 0.f : o.w * expf(o.z - nm);
-            r.w = a + c2;
-            r.z = nm;
+            argmax_merge(r.x, ri, r.z, r.w, o.x, __float_as_int(o.y), o.z, o.w);
         }
-        p.am_part[(int64_t)grp * p.M + m] = r;
+        r.y = __int_as_float(ri);
+        p.am.part[(int64_t)grp * p.M + m] = r;
     }
 }
 
@@ -1286,7 +1251,7 @@ void launch_vocab3(const Vocab3Args& a0, hipStream_t s) {
     SC_CHECK(a.logits || a.M <= 64 || a.slot_rp, "vocab3: the fused arg-max epilogue takes at most 64 rows outside the decode engine (M=%d)", a.M);
     SC_CHECK(!a.slot_rp || (a.limit_row && !a.logits), "vocab3: the per-slot step rules need limit_row and the fused epilogue");
     a.tpg = cdiv(a.NT_total, groups);
-    SC_CHECK(a.logits || a.am_tiles_cap >= groups, "vocab3: arg-max partial buffer holds %d groups, need %d", a.am_tiles_cap, groups);
+    SC_CHECK(a.logits || a.am.tiles_cap >= groups, "vocab3: arg-max partial buffer holds %d groups, need %d", a.am.tiles_cap, groups);
     SC_CHECK(!a.logits || a.ldl >= a.N, "vocab3: logits row stride %lld < N=%d", (long long)a.ldl, a.N);
     prof::Scope scope(a.M <= 32 ? "vocab3_m32" : "vocab3_m64", 2.0 * a.M * (double)a.N * a.K,
                       2.0 * a.N * (double)a.K + (a.logits ? 4.0 * a.M * (double)a.N : 0.0), s);

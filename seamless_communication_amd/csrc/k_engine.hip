@@ -2,70 +2,21 @@
 // different requests at different positions.  Step rules restated from ggml/examples/unity/fairseq2.cpp:1269-1305
 // (_tweak_lprobs) and :1535-1563 (finished hypotheses), per row instead of per batch; the length rule per row is the
 // request's own (inference/generator.py:227-263).
-#include "kernels.h"
+#include "device_util.h"
 
 namespace sc {
 
 namespace {
 
-// One workgroup per live slot.  The reduction of the per-group records is argmax_finalize_kernel's (k_skinny.hip), expression
-// by expression: a row's token, score and log-sum-exp do not depend on which chain computed them.
+// One workgroup per live slot.  The reduction of the per-group records is argmax_finalize_kernel's (argmax_combine_records):
+// a row's token, score and log-sum-exp do not depend on which chain computed them.
 __global__ __launch_bounds__(256) void engine_finalize_kernel(EngineFinalizeArgs a) {
-    __shared__ float s_v[4], s_m[4], s_s[4];
-    __shared__ int s_i[4];
     const int b = blockIdx.x;
     if (b >= *a.d_rows) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float best = -INFINITY, m = -INFINITY, ssum = 0.f;
-    int bidx = 0x7fffffff;
-    for (int t = tid; t < a.tiles; t += 256) {
-        const float4 r = a.part[(int64_t)t * a.slots + b];
-        const int oi = __float_as_int(r.y);
-        if (r.x > best || (r.x == best && oi < bidx)) {
-            best = r.x;
-            bidx = oi;
-        }
-        const float nm = fmaxf(m, r.z);
-        const float x = (m == -INFINITY) ? 0.f : ssum * expf(m - nm);
-        const float c = (r.z == -INFINITY) ? 0.f : r.w * expf(r.z - nm);
-        ssum = x + c;
-        m = nm;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bidx, o);
-        if (ob > best || (ob == best && oi < bidx)) {
-            best = ob;
-            bidx = oi;
-        }
-        const float om = __shfl_xor(m, o);
-        const float os = __shfl_xor(ssum, o);
-        const float nm = fmaxf(m, om);
-        const float x = (m == -INFINITY) ? 0.f : ssum * expf(m - nm);
-        const float c = (om == -INFINITY) ? 0.f : os * expf(om - nm);
-        ssum = x + c;
-        m = nm;
-    }
-    if (lane == 0) {
-        s_v[wave] = best;
-        s_i[wave] = bidx;
-        s_m[wave] = m;
-        s_s[wave] = ssum;
-    }
-    __syncthreads();
-    if (tid != 0) return;
-    for (int w = 1; w < 4; ++w) {
-        if (s_v[w] > best || (s_v[w] == best && s_i[w] < bidx)) {
-            best = s_v[w];
-            bidx = s_i[w];
-        }
-        const float nm = fmaxf(m, s_m[w]);
-        const float x = (m == -INFINITY) ? 0.f : ssum * expf(m - nm);
-        const float c = (s_m[w] == -INFINITY) ? 0.f : s_s[w] * expf(s_m[w] - nm);
-        ssum = x + c;
-        m = nm;
-    }
+    float best, m, ssum;
+    int bidx;
+    argmax_combine_records(a.part, a.tiles, a.slots, b, best, bidx, m, ssum);
+    if (threadIdx.x != 0) return;
     const EngineRows& R = a.rows;
     const int2 rp = a.slot_rp[b];
     const int r = rp.x, pos = rp.y;

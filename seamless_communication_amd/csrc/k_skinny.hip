@@ -125,10 +125,10 @@ __global__ __launch_bounds__(256) void skinny_kernel(SkinnyArgs p) {
     int am_idx[MT][4];
     int am_step = 0;
     bool am_force = false, am_no_eos = false;
-    if (p.am_part) {
-        am_step = p.am_pos ? *p.am_pos : 0;
-        am_force = (p.am_force_eos_step >= 0 && am_step == p.am_force_eos_step);
-        am_no_eos = am_step < p.am_min_step_for_eos;
+    if (p.am.part) {
+        am_step = p.am.pos ? *p.am.pos : 0;
+        am_force = (p.am.force_eos_step >= 0 && am_step == p.am.force_eos_step);
+        am_no_eos = am_step < p.am.min_step_for_eos;
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -158,25 +158,11 @@ __global__ __launch_bounds__(256) void skinny_kernel(SkinnyArgs p) {
                 const int o = row * 32 + col;
                 float v = (red[0][o] + red[1][o]) + (red[2][o] + red[3][o]);
                 if (m < p.M && n < p.N) {
-                    if (p.am_part) {
+                    if (p.am.part) {
                         // generation step rules on the logit of column n (see argmax_rows_kernel)
                         if (p.bias) v += p.bias[n];
-                        if (n == p.am_eos_idx) p.am_eos_logit[m] = v;
-                        if (v > am_m[i][q]) {
-                            am_s[i][q] = am_s[i][q] * expf(am_m[i][q] - v) + 1.f;
-                            am_m[i][q] = v;
-                        } else {
-                            am_s[i][q] += expf(v - am_m[i][q]);
-                        }
-                        float tv = v;
-                        if (n == p.am_unk_idx) tv -= p.am_unk_penalty;
-                        if (n == p.am_pad_idx) tv = -INFINITY;
-                        if (am_no_eos && n == p.am_eos_idx) tv = -INFINITY;
-                        if (am_force && n != p.am_eos_idx) tv = -INFINITY;
-                        if (tv > am_best[i][q] || (tv == am_best[i][q] && n < am_idx[i][q])) {
-                            am_best[i][q] = tv;
-                            am_idx[i][q] = n;
-                        }
+                        if (n == p.am.eos_idx) p.am.eos_logit[m] = v;
+                        argmax_push(am_best[i][q], am_idx[i][q], am_m[i][q], am_s[i][q], v, n, p.am, am_no_eos, am_force);
                     } else if (p.partial) {
                         p.partial[((int64_t)split * p.M + m) * p.N + n] = v;
                     } else {
@@ -189,7 +175,7 @@ __global__ __launch_bounds__(256) void skinny_kernel(SkinnyArgs p) {
             }
         }
     }
-    if (p.am_part) {
+    if (p.am.part) {
         // the 32 lanes of a half-wave share a row: reduce over the columns
 #pragma unroll
         for (int i = 0; i < MT; ++i)
@@ -199,19 +185,7 @@ __global__ __launch_bounds__(256) void skinny_kernel(SkinnyArgs p) {
                 int bidx = am_idx[i][q];
 #pragma unroll
                 for (int o = 16; o > 0; o >>= 1) {
-                    const float ob = __shfl_xor(best, o);
-                    const int oi = __shfl_xor(bidx, o);
-                    if (ob > best || (ob == best && oi < bidx)) {
-                        best = ob;
-                        bidx = oi;
-                    }
-                    const float om = __shfl_xor(mm, o);
-                    const float os = __shfl_xor(ss, o);
-                    const float nm = fmaxf(mm, om);
-                    const float a = (mm == -INFINITY) ? 0.f : ss * expf(mm - nm);
-                    const float b = (om == -INFINITY) ? 0.f : os * expf(om - nm);
-                    ss = a + b;
-                    mm = nm;
+                    argmax_merge_lane(best, bidx, mm, ss, o);
                 }
                 const int m = 32 * i + rbase + 8 * q;
                 if (col == 0 && m < p.M) {
@@ -220,7 +194,7 @@ __global__ __launch_bounds__(256) void skinny_kernel(SkinnyArgs p) {
                     rec.y = __int_as_float(bidx);
                     rec.z = mm;
                     rec.w = ss;
-                    p.am_part[(int64_t)blockIdx.x * p.M + m] = rec;
+                    p.am.part[(int64_t)blockIdx.x * p.M + m] = rec;
                 }
             }
     }
@@ -263,12 +237,12 @@ void launch_skinny(const SkinnyArgs& a0, hipStream_t s) {
     const int tiles = cdiv(a.N, 32);
     const int nt = (a.M <= 32 && tiles >= 2048) ? 4 : 1;
     dim3 grid(cdiv(tiles, nt), a.splits);
-    SC_CHECK(!a.am_part || a.am_tiles_cap >= (int)grid.x, "skinny gemm: arg-max partial buffer holds %d tiles, need %d",
-             a.am_tiles_cap, (int)grid.x);
+    SC_CHECK(!a.am.part || a.am.tiles_cap >= (int)grid.x, "skinny gemm: arg-max partial buffer holds %d tiles, need %d",
+             a.am.tiles_cap, (int)grid.x);
     prof::Scope scope(a.M <= 32 ? "skinny_m32" : "skinny_m64", 2.0 * a.M * (double)a.N * a.K,
                       2.0 * a.N * (double)a.K + 4.0 * a.M * ((double)a.K + (double)a.N * a.splits), s);
-    SC_CHECK(!a.am_part || a.splits == 1, "skinny gemm: arg-max epilogue cannot be combined with split-K");
-    if (a.am_part) a.am_tiles = (int)grid.x;
+    SC_CHECK(!a.am.part || a.splits == 1, "skinny gemm: arg-max epilogue cannot be combined with split-K");
+    if (a.am.part) a.am_tiles = (int)grid.x;
     if (a.M <= 32) {
         if (nt == 4) hipLaunchKernelGGL((skinny_kernel<1, 4, 2>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((skinny_kernel<1, 1, 4>), grid, dim3(256), 0, s, a);
@@ -475,10 +449,8 @@ __global__ __launch_bounds__(256) void argmax_finalize_kernel(const float4* __re
                                                               int* __restrict__ hist, int hist_ld,
                                                               int* __restrict__ finished, int* __restrict__ out_len,
                                                               float* __restrict__ score, const int* __restrict__ prompt_len) {
-    __shared__ float s_v[4], s_m[4], s_s[4];
-    __shared__ int s_i[4];
     const int b = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     if (prompt_len) {  // uniform over the workgroup
         const int p = *d_pos;
         if (p + 1 < prompt_len[b]) {
@@ -486,56 +458,10 @@ __global__ __launch_bounds__(256) void argmax_finalize_kernel(const float4* __re
             return;
         }
     }
-    float best = -INFINITY, m = -INFINITY, ssum = 0.f;
-    int bidx = 0x7fffffff;
-    for (int t = tid; t < tiles; t += 256) {
-        const float4 r = part[(int64_t)t * nb + b];
-        const int oi = __float_as_int(r.y);
-        if (r.x > best || (r.x == best && oi < bidx)) {
-            best = r.x;
-            bidx = oi;
-        }
-        const float nm = fmaxf(m, r.z);
-        const float a = (m == -INFINITY) ? 0.f : ssum * expf(m - nm);
-        const float c = (r.z == -INFINITY) ? 0.f : r.w * expf(r.z - nm);
-        ssum = a + c;
-        m = nm;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o);
-        const int oi = __shfl_xor(bidx, o);
-        if (ob > best || (ob == best && oi < bidx)) {
-            best = ob;
-            bidx = oi;
-        }
-        const float om = __shfl_xor(m, o);
-        const float os = __shfl_xor(ssum, o);
-        const float nm = fmaxf(m, om);
-        const float a = (m == -INFINITY) ? 0.f : ssum * expf(m - nm);
-        const float c = (om == -INFINITY) ? 0.f : os * expf(om - nm);
-        ssum = a + c;
-        m = nm;
-    }
-    if (lane == 0) {
-        s_v[wave] = best;
-        s_i[wave] = bidx;
-        s_m[wave] = m;
-        s_s[wave] = ssum;
-    }
-    __syncthreads();
+    float best, m, ssum;
+    int bidx;
+    argmax_combine_records(part, tiles, nb, b, best, bidx, m, ssum);
     if (tid == 0) {
-        for (int w = 1; w < 4; ++w) {
-            if (s_v[w] > best || (s_v[w] == best && s_i[w] < bidx)) {
-                best = s_v[w];
-                bidx = s_i[w];
-            }
-            const float nm = fmaxf(m, s_m[w]);
-            const float a = (m == -INFINITY) ? 0.f : ssum * expf(m - nm);
-            const float c = (s_m[w] == -INFINITY) ? 0.f : s_s[w] * expf(s_m[w] - nm);
-            ssum = a + c;
-            m = nm;
-        }
         const int pos = *d_pos;
         if (force_eos_step >= 0 && pos == force_eos_step) {
             best = eos_logit[b];
@@ -557,11 +483,10 @@ __global__ __launch_bounds__(256) void argmax_finalize_kernel(const float4* __re
     }
 }
 
-void launch_argmax_finalize(const float4* part, int tiles, int nb, const float* eos_logit, const int* d_pos,
-                            int force_eos_step, int pad_idx, int eos_idx, int* next_tok, int* hist, int hist_ld,
-                            int* finished, int* out_len, float* score, hipStream_t s, const int* prompt_len) {
-    hipLaunchKernelGGL(argmax_finalize_kernel, dim3(nb), dim3(256), 0, s, part, tiles, nb, eos_logit, d_pos,
-                       force_eos_step, pad_idx, eos_idx, next_tok, hist, hist_ld, finished, out_len, score, prompt_len);
+void launch_argmax_finalize(const ArgmaxEpi& am, int tiles, int nb, int* next_tok, int* hist, int hist_ld, int* finished,
+                            int* out_len, float* score, hipStream_t s, const int* prompt_len) {
+    hipLaunchKernelGGL(argmax_finalize_kernel, dim3(nb), dim3(256), 0, s, am.part, tiles, nb, am.eos_logit, am.pos,
+                       am.force_eos_step, am.pad_idx, am.eos_idx, next_tok, hist, hist_ld, finished, out_len, score, prompt_len);
     SC_LAUNCH_CHECK();
 }
 

@@ -301,6 +301,20 @@ void launch_gemv(const float* x, int64_t ldx, const __half* W, int64_t ldw, cons
                  const float* res, int64_t ldr, float* out, int64_t ldo, int M, int N, int K,
                  int act, float alpha, hipStream_t s);
 
+// The greedy step rules of a fused vocabulary projection (k_skinny.hip, k_dstep.hip EPI_ARGMAX, k_dstep3.hip vocab3), one
+// record for the three kernel families: no logits go to HBM; per (workgroup, row) one record {best tweaked logit, its index,
+// max, sumexp} goes to part[tile][M] and the raw EOS logit to eos_logit[M]; launch_argmax_finalize combines them.  The
+// device side of the rules is argmax_push / argmax_merge (device_util.h).
+struct ArgmaxEpi {
+    float4* part = nullptr;
+    int tiles_cap = 0;  // capacity of part in tiles
+    float* eos_logit = nullptr;
+    const int* pos = nullptr;
+    int min_step_for_eos = 0, force_eos_step = -1;
+    int pad_idx = -1, eos_idx = -1, unk_idx = -1;
+    float unk_penalty = 0.f;
+};
+
 // Skinny product for 1..64 rows (decoder step), see k_skinny.hip.  With partial != nullptr the
 // kernel writes raw K-range partial sums to partial[split][M][N] (no epilogue); otherwise
 // C = alpha*act(A.W^T + bias) + res.
@@ -320,23 +334,14 @@ struct SkinnyArgs {
     float alpha = 1.0f;
     int splits = 1;
     int kc = 0;  // filled by the launcher
-    // fused arg-max epilogue (vocabulary projection of the decoder step): when am_part != nullptr no
-    // logits are written; per workgroup and row one record {best tweaked logit, its index, max, sumexp}
-    // goes to am_part[tile][M] and the raw EOS logit to am_eos_logit[M]; launch_argmax_finalize combines them.
-    float4* am_part = nullptr;
-    int am_tiles_cap = 0;  // capacity of am_part in tiles
-    int am_tiles = 0;      // filled by the launcher: tiles written
-    float* am_eos_logit = nullptr;
-    const int* am_pos = nullptr;
-    int am_min_step_for_eos = 0, am_force_eos_step = -1;
-    int am_pad_idx = -1, am_eos_idx = -1, am_unk_idx = -1;
-    float am_unk_penalty = 0.f;
+    ArgmaxEpi am;      // fused arg-max epilogue: with am.part != nullptr no logits are written
+    int am_tiles = 0;  // filled by the launcher: tiles written
 };
-// number of am_part tiles launch_skinny will write for N output features and M rows
+// number of am.part tiles launch_skinny will write for N output features and M rows
 int skinny_argmax_tiles(int M, int N);
-void launch_argmax_finalize(const float4* part, int tiles, int nb, const float* eos_logit, const int* d_pos,
-                            int force_eos_step, int pad_idx, int eos_idx, int* next_tok, int* hist, int hist_ld,
-                            int* finished, int* out_len, float* score, hipStream_t s, const int* prompt_len = nullptr);
+// combines the `tiles` records per row that a projection wrote under `am` and does the step's bookkeeping for the nb rows
+void launch_argmax_finalize(const ArgmaxEpi& am, int tiles, int nb, int* next_tok, int* hist, int hist_ld, int* finished,
+                            int* out_len, float* score, hipStream_t s, const int* prompt_len = nullptr);
 void launch_skinny(const SkinnyArgs& a, hipStream_t s);
 // number of K ranges that brings the grid to >= 256 workgroups (1 when want_split == 0)
 int skinny_splits(int M, int N, int K, int want_split);
@@ -369,14 +374,7 @@ struct GemvPArgs {
     __half* Oh = nullptr;
     __half* Ol = nullptr;
     int ORB = 32;
-    // arg-max epilogue (same record format and rules as SkinnyArgs)
-    float4* am_part = nullptr;
-    int am_tiles_cap = 0;
-    float* am_eos_logit = nullptr;
-    const int* am_pos = nullptr;
-    int am_min_step_for_eos = 0, am_force_eos_step = -1;
-    int am_pad_idx = -1, am_eos_idx = -1, am_unk_idx = -1;
-    float am_unk_penalty = 0.f;
+    ArgmaxEpi am;  // EPI_ARGMAX
     // filled by the launcher
     int KS = 0, NT = 0, ks_per_wg = 0;
     uint32_t w_bytes = 0, a_bytes = 0;
@@ -518,16 +516,10 @@ struct Vocab3Args {
     const float* bias = nullptr;
     float* logits = nullptr;    // != null: raw logits [M][ldl] fp32 go to HBM and the fused rules are skipped (beam search)
     int64_t ldl = 0;
-    float4* am_part = nullptr;  // [vocab3_groups(M)][M]
-    int am_tiles_cap = 0;
-    float* am_eos_logit = nullptr;
-    const int* am_pos = nullptr;
-    int am_min_step_for_eos = 0, am_force_eos_step = -1;
-    int am_pad_idx = -1, am_eos_idx = -1, am_unk_idx = -1;
-    float am_unk_penalty = 0.f;
+    ArgmaxEpi am;  // part is [vocab3_groups(M)][M]
     const int* d_rows = nullptr;  // see Gemv3Args::d_rows
-    // decode engine: the step rules of slot m are those of row state slot_rp[m].x at position slot_rp[m].y (am_pos unused),
-    // forced EOS at position limit_row[row state] - 2 (am_force_eos_step unused)
+    // decode engine: the step rules of slot m are those of row state slot_rp[m].x at position slot_rp[m].y (am.pos unused),
+    // forced EOS at position limit_row[row state] - 2 (am.force_eos_step unused)
     const int2* slot_rp = nullptr;
     const int* limit_row = nullptr;
     // filled by the launcher

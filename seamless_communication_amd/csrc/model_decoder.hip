@@ -274,7 +274,7 @@ void setup_session(Model& m, DecodeSession& S, int n, int max_len, int s_enc, bo
     c.d_score = S.fl.get() + n;
     const DecStack W = unity_stack(m);
     const int family = choose_family(m, W, n, 0);
-    const bool fused_argmax = n <= 64 && M % 64 == 0;
+    const bool fused_argmax = fused_argmax_rows(n, M);
     S.fused_argmax = fused_argmax;
     init_step_scratch(m, S.scratch, c, W, n, family, StepTuning::from_knobs(n), /*wide_always=*/false);
     S.logits = Buf<float>(m.pp(), fused_argmax ? 4 : (size_t)n * cfg.text_vocab_size);

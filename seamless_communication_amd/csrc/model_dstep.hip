@@ -306,6 +306,14 @@ bool step3_wide_eligible(const Model& m, const DecStack& W, int nb) {
            gemv3_supported(nb, M, M, IN3_LN) && gemv3_supported(nb, W.ffn_dim, M, IN3_LN);  // the LayerNorm-fused q / FFN-in launches
 }
 
+ArgmaxEpi step_argmax_epi(const StepCtx& c, const DecStack& W) {
+    ArgmaxEpi e;
+    e.part = c.am_part, e.tiles_cap = c.am_tiles, e.eos_logit = c.am_eos_logit, e.pos = c.d_pos;
+    e.min_step_for_eos = c.min_seq_len, e.force_eos_step = c.force_eos_step;
+    e.pad_idx = W.pad_idx, e.eos_idx = W.eos_idx, e.unk_idx = W.unk_idx, e.unk_penalty = c.unk_penalty;
+    return e;
+}
+
 // THE dispatch decision (setup_session, run_generate_beam, the streaming step and decoder_step_family's report all call this
 // and nothing else composes the predicates): which kernel family a step of `rows` rows over stack W runs on for caller
 // 0 greedy generation, 1 / 3 beam search (text / v1 unit decoder), 2 the streaming monotonic step.
@@ -316,7 +324,7 @@ int choose_family(const Model& m, const DecStack& W, int rows, int caller) {
     if (caller == 0) {
         // the packed step projects through the packed embedding (a failed pack leaves it null: first-generation step then)
         const bool gen2 = step2_eligible(m, W, rows) && W.embed_p != nullptr;
-        const bool fused_argmax = rows <= 64 && M % 64 == 0;
+        const bool fused_argmax = fused_argmax_rows(rows, M);
         const bool gen3 = gen2 && step3_eligible(m, W, rows) && fused_argmax && vocab3_supported(rows, W.vocab, M);
         if (W.ffn_act == ACT_GELU) return gen3 ? 3 : 1;  // the packed chain's FFN epilogue knows ReLU only
         return gen3 ? 3 : (gen2 ? 2 : 1);
@@ -500,19 +508,9 @@ void decoder_step2(Model& m, StepCtx& c, bool project, const DecStack& W) {
         v.splits = 1;
         v.ntl = c.am_ntl;
         v.epi = EPI_ARGMAX;
-        v.am_part = c.am_part;
-        v.am_tiles_cap = c.am_tiles;
-        v.am_eos_logit = c.am_eos_logit;
-        v.am_pos = c.d_pos;
-        v.am_min_step_for_eos = c.min_seq_len;
-        v.am_force_eos_step = c.force_eos_step;
-        v.am_pad_idx = W.pad_idx;
-        v.am_eos_idx = W.eos_idx;
-        v.am_unk_idx = W.unk_idx;
-        v.am_unk_penalty = c.unk_penalty;
+        v.am = step_argmax_epi(c, W);
         launch_gemvp(v, m.stream);
-        launch_argmax_finalize(c.am_part, gemvp_argmax_tiles(W.vocab, c.am_ntl), nb, c.am_eos_logit, c.d_pos,
-                               c.force_eos_step, W.pad_idx, W.eos_idx, c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len,
+        launch_argmax_finalize(v.am, gemvp_argmax_tiles(W.vocab, c.am_ntl), nb, c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len,
                                c.d_score, m.stream, c.d_prompt_len);
     }
     launch_add_i32(c.d_pos, 1, m.stream);
@@ -639,9 +637,7 @@ void decoder_step3(Model& m, StepCtx& c, bool project, const DecStack& W) {
     if (project) {
         Vocab3Args v;
         v.Wp = W.embed_p, v.Ah = c.hH, v.Al = c.hL, v.RB = c.rb, v.M = nb, v.N = W.vocab, v.K = M;
-        v.am_part = c.am_part, v.am_tiles_cap = c.am_tiles, v.am_eos_logit = c.am_eos_logit, v.am_pos = c.d_pos;
-        v.am_min_step_for_eos = c.min_seq_len, v.am_force_eos_step = c.force_eos_step;
-        v.am_pad_idx = W.pad_idx, v.am_eos_idx = W.eos_idx, v.am_unk_idx = W.unk_idx, v.am_unk_penalty = c.unk_penalty;
+        v.am = step_argmax_epi(c, W);
         v.d_rows = c.d_rows;
         v.slot_rp = c.slot_rp, v.limit_row = c.limit_row;
         launch_vocab3(v, m.stream);
@@ -655,8 +651,8 @@ void decoder_step3(Model& m, StepCtx& c, bool project, const DecStack& W) {
             launch_engine_finalize(f, m.stream);
             return;
         }
-        launch_argmax_finalize(c.am_part, vocab3_groups(nb), nb, c.am_eos_logit, c.d_pos, c.force_eos_step, W.pad_idx, W.eos_idx,
-                               c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len, c.d_score, m.stream, c.d_prompt_len);
+        launch_argmax_finalize(v.am, vocab3_groups(nb), nb, c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len, c.d_score, m.stream,
+                               c.d_prompt_len);
     }
     if (c.pool) {  // session pool: per-slot positions, decoder outputs into the caller's packed rows; the caller projects
         SC_CHECK(c.slot_rp && c.d_rows && c.pos_row && !project, "decoder step: a pool step runs in slot mode and is not projected here");
@@ -730,7 +726,7 @@ void decoder_step(Model& m, StepCtx& c, bool project) {
         SC_LAUNCH_CHECK();
     }
     if (project) {
-        if (nb <= 64 && M % 64 == 0) {
+        if (fused_argmax_rows(nb, M)) {
             // vocabulary projection with the arg-max folded into its epilogue: no logits in HBM
             SkinnyArgs a;
             a.A = c.hN;
@@ -740,19 +736,10 @@ void decoder_step(Model& m, StepCtx& c, bool project) {
             a.M = nb;
             a.N = W.vocab;
             a.K = M;
-            a.am_part = c.am_part;
-            a.am_tiles_cap = c.am_tiles;
-            a.am_eos_logit = c.am_eos_logit;
-            a.am_pos = c.d_pos;
-            a.am_min_step_for_eos = c.min_seq_len;
-            a.am_force_eos_step = c.force_eos_step;
-            a.am_pad_idx = W.pad_idx;
-            a.am_eos_idx = W.eos_idx;
-            a.am_unk_idx = W.unk_idx;
-            a.am_unk_penalty = c.unk_penalty;
+            a.am = step_argmax_epi(c, W);
             launch_skinny(a, m.stream);
-            launch_argmax_finalize(c.am_part, c.am_tiles, nb, c.am_eos_logit, c.d_pos, c.force_eos_step, W.pad_idx,
-                                   W.eos_idx, c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len, c.d_score, m.stream, c.d_prompt_len);
+            launch_argmax_finalize(a.am, c.am_tiles, nb, c.d_tok, c.d_hist, c.cap, c.d_finished, c.d_out_len, c.d_score, m.stream,
+                                   c.d_prompt_len);
         } else {
             Linear proj;
             proj.w = W.embed;
