@@ -331,6 +331,42 @@ int sc_op_step_update(int32_t* d_next_tok, int32_t* d_hist, int32_t hist_ld, int
 int sc_op_row_swap(float* d_k, float* d_v, float* d_cross, int32_t layers, int32_t pairs, const int32_t* h_src, const int32_t* h_dst, int32_t n_rows,
                    int32_t M, int32_t cap, int32_t s_enc, int32_t filled, int32_t* d_tok, int32_t* d_finished, int32_t* d_out_len,
                    int32_t* d_enc_lens, float* d_lprob, float* d_score, int32_t* d_hist, float* d_hidden);
+/* The row kernels between the products by themselves (k_norm.hip, k_misc.hip; tests/test_row_kernels_gpu.py).  Each hook is
+ * the launcher the models call with the caller's strides.
+ * sc_op_layernorm_ex: d_y only: launch_layernorm; planes only: launch_layernorm_split; both: launch_layernorm_both (the length
+ * mask d_lens [rows / t_per_batch] then zeroes the planes, not the fp32 rows).  d_lens NULL: no mask.
+ * sc_op_embed_tokens: out[r] = emb[tok[r]] * scale + pos_table[*d_pos + r % t_per_batch] (d_pos NULL: 0; t_per_batch 0: no row term).
+ * sc_op_gather_rows: dst[r] = src[idx[r]] (+ add[r / rows_per_item] when d_add is given), zeros where idx[r] < 0.
+ * sc_op_char_embed_add / sc_op_pos_add: the NAR decoder front end's positional terms in place; d_row_t [rows] picks the table row
+ * per row (launch_pos_add_rows) instead of r % t_per_batch.
+ * sc_op_durations: d_durations [rows] of the variance adaptor's rule; d_lens NULL: every row live.
+ * sc_op_vocoder_embed: rows [lang | unit | spkr] -> d_out [rows][Lg + E + Sp]; d_item_off [nb + 1] (packed items, rows_total rows)
+ * or NULL (nb items of T rows).  sc_op_item_row_pos: d_row_pos [rows][2] = {row inside its item, rows of the item}.
+ * sc_op_scatter_items: dst[item_of[i] * dst_stride + t] = src[item_off[i] * mul + t]; `longest` = rows of the longest item * mul.
+ * sc_op_glu_dwconv_ex: sc_op_glu_dwconv with `left` taps before the output position (< 0: k - 1, causal) and, when the four
+ * BatchNorm vectors are given, SiLU(BatchNorm(.)) behind the convolution through launch_bn_fold (eps 1e-5).
+ * sc_op_relpos_table: d_out [2S - 1][M], the v1 encoder's relative position table. */
+int sc_op_layernorm_ex(const float* d_x, int64_t ldx, const float* d_gamma, const float* d_beta, float* d_y, int64_t ldy, void* d_yh_f16,
+                       void* d_yl_f16, int64_t ldh, int32_t rows, int32_t C, int32_t act, const int32_t* d_lens, int32_t t_per_batch);
+int sc_op_embed_tokens(const int32_t* d_tok, int32_t rows, const void* d_emb_f16, int32_t M, float scale, const float* d_pos_table,
+                       const int32_t* d_pos, int32_t t_per_batch, float* d_out, int64_t ldo);
+int sc_op_gather_rows(const float* d_src, int64_t lds, const int32_t* d_idx, const float* d_add, int64_t ld_add, int32_t rows_per_item,
+                      float* d_dst, int64_t ldd, int32_t rows, int32_t C);
+int sc_op_char_embed_add(float* d_seqs, int64_t ld, const int32_t* d_char_ids, const void* d_embed_f16, const float* d_pos_table,
+                         int32_t t_per_batch, float alpha, float scale, int32_t rows, int32_t M);
+int sc_op_pos_add(float* d_seqs, int64_t ld, const float* d_pos_table, int32_t t_per_batch, const int32_t* d_row_t, float alpha, int32_t rows,
+                  int32_t M);
+int sc_op_durations(const float* d_h, int64_t ld, const float* d_w, const float* d_b, int32_t rows, int32_t H, int32_t t_per_batch,
+                    const int32_t* d_lens, float duration_factor, int32_t min_dur, int32_t* d_durations);
+int sc_op_vocoder_embed(const int32_t* d_units, int32_t nb, int32_t T, const void* d_dict_f16, int32_t E, const void* d_lang_f16, int32_t Lg,
+                        const int32_t* d_lang_idx, const void* d_spkr_f16, int32_t Sp, const int32_t* d_spkr_idx, float* d_out,
+                        const int32_t* d_item_off, int32_t rows_total);
+int sc_op_item_row_pos(const int32_t* d_item_off, int32_t n_items, int32_t mul, int32_t rows, int32_t* d_row_pos);
+int sc_op_scatter_items(const float* d_src, const int32_t* d_item_off, const int32_t* d_item_of, int32_t n_items, int32_t mul, int32_t longest,
+                        int64_t dst_stride, float* d_dst);
+int sc_op_glu_dwconv_ex(const float* d_x, const float* d_w, float* d_y, int32_t nb, int32_t T, int32_t C, int32_t k, const int32_t* d_lens,
+                        int32_t left, const float* d_bn_g, const float* d_bn_b, const float* d_bn_mean, const float* d_bn_var);
+int sc_op_relpos_table(int32_t S, int32_t M, float* d_out);
 /* Forced aligner kernels by themselves (k_align.hip; tests/test_aligner_gpu.py).  sc_op_align_lprob: encoder states in
  * (d_text [n][s_text][C], d_feat [n][s_feat][C] fp32, C % 32 == 0; lengths on the host), d_lprob [n][s_feat][s_text] out: the
  * masked log-softmax of -temperature * L2 distance.  sc_op_mas: d_lprob [n][s_feat][s_text] and the lengths in, h_durations

@@ -390,6 +390,17 @@ SIGNATURES = {
     "sc_op_dstep3_reduce_capture_ex": (C.c_int, [_P, _i, _P, _P, _P, _P, _P, _P, C.c_int64, _i, _i, _P, _P, _i, _i, _i]),
     "sc_op_step_update": (C.c_int, [_P, _P, _i, _P, _P, _P, _P, _i, _i, _i, _i, _P]),
     "sc_op_row_swap": (C.c_int, [_P, _P, _P, _i, _i, _P, _P, _i, _i, _i, _i, _i, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sc_op_layernorm_ex": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _i, _i, _i, _P, _i]),
+    "sc_op_embed_tokens": (C.c_int, [_P, _i, _P, _i, C.c_float, _P, _P, _i, _P, C.c_int64]),
+    "sc_op_gather_rows": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _i, _P, C.c_int64, _i, _i]),
+    "sc_op_char_embed_add": (C.c_int, [_P, C.c_int64, _P, _P, _P, _i, C.c_float, C.c_float, _i, _i]),
+    "sc_op_pos_add": (C.c_int, [_P, C.c_int64, _P, _i, _P, C.c_float, _i, _i]),
+    "sc_op_durations": (C.c_int, [_P, C.c_int64, _P, _P, _i, _i, _i, _P, C.c_float, _i, _P]),
+    "sc_op_vocoder_embed": (C.c_int, [_P, _i, _i, _P, _i, _P, _i, _P, _P, _i, _P, _P, _P, _i]),
+    "sc_op_item_row_pos": (C.c_int, [_P, _i, _i, _i, _P]),
+    "sc_op_scatter_items": (C.c_int, [_P, _P, _P, _i, _i, _i, C.c_int64, _P]),
+    "sc_op_glu_dwconv_ex": (C.c_int, [_P, _P, _P, _i, _i, _i, _i, _P, _i, _P, _P, _P, _P]),
+    "sc_op_relpos_table": (C.c_int, [_i, _i, _P]),
 }
 
 _lib: Optional[C.CDLL] = None

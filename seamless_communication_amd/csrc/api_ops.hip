@@ -1478,4 +1478,122 @@ int sc_op_row_swap(float* d_k, float* d_v, float* d_cross, int32_t layers, int32
     SC_API_END
 }
 
+// ---- the row kernels between the products (k_norm.hip, k_misc.hip), op level ----------------------------------------
+
+int sc_op_layernorm_ex(const float* d_x, int64_t ldx, const float* d_gamma, const float* d_beta, float* d_y, int64_t ldy, void* d_yh_f16,
+                       void* d_yl_f16, int64_t ldh, int32_t rows, int32_t C, int32_t act, const int32_t* d_lens, int32_t t_per_batch) {
+    SC_API_BEGIN
+    SC_CHECK(d_x && d_gamma && d_beta && (d_y || d_yh_f16) && !d_yh_f16 == !d_yl_f16 && (!d_lens || t_per_batch > 0),
+             "sc_op_layernorm_ex: bad argument");
+    __half* yh = static_cast<__half*>(d_yh_f16);
+    __half* yl = static_cast<__half*>(d_yl_f16);
+    if (!yh) launch_layernorm(d_x, ldx, d_gamma, d_beta, d_y, ldy, rows, C, act, d_lens, t_per_batch, g_op_stream);
+    else if (!d_y) launch_layernorm_split(d_x, ldx, d_gamma, d_beta, yh, yl, ldh, rows, C, act, d_lens, t_per_batch, g_op_stream);
+    else launch_layernorm_both(d_x, ldx, d_gamma, d_beta, d_y, ldy, yh, yl, ldh, rows, C, act, d_lens, t_per_batch, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_embed_tokens(const int32_t* d_tok, int32_t rows, const void* d_emb_f16, int32_t M, float scale, const float* d_pos_table,
+                       const int32_t* d_pos, int32_t t_per_batch, float* d_out, int64_t ldo) {
+    SC_API_BEGIN
+    SC_CHECK(d_tok && d_emb_f16 && d_pos_table && d_out && M > 0 && ldo >= M && t_per_batch >= 0, "sc_op_embed_tokens: bad argument");
+    launch_embed_tokens(d_tok, rows, static_cast<const __half*>(d_emb_f16), M, scale, d_pos_table, d_pos, t_per_batch, d_out, ldo, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_gather_rows(const float* d_src, int64_t lds, const int32_t* d_idx, const float* d_add, int64_t ld_add, int32_t rows_per_item,
+                      float* d_dst, int64_t ldd, int32_t rows, int32_t C) {
+    SC_API_BEGIN
+    SC_CHECK(d_src && d_idx && d_dst && C > 0 && lds >= C && ldd >= C, "sc_op_gather_rows: bad argument");
+    if (d_add) launch_gather_rows_add(d_src, lds, d_idx, d_add, ld_add, rows_per_item, d_dst, ldd, rows, C, g_op_stream);
+    else launch_gather_rows(d_src, lds, d_idx, d_dst, ldd, rows, C, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_char_embed_add(float* d_seqs, int64_t ld, const int32_t* d_char_ids, const void* d_embed_f16, const float* d_pos_table,
+                         int32_t t_per_batch, float alpha, float scale, int32_t rows, int32_t M) {
+    SC_API_BEGIN
+    SC_CHECK(d_seqs && d_char_ids && d_embed_f16 && d_pos_table && t_per_batch > 0 && M > 0 && ld >= M, "sc_op_char_embed_add: bad argument");
+    launch_char_embed_add(d_seqs, ld, d_char_ids, static_cast<const __half*>(d_embed_f16), d_pos_table, t_per_batch, alpha, scale, rows, M,
+                          g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_pos_add(float* d_seqs, int64_t ld, const float* d_pos_table, int32_t t_per_batch, const int32_t* d_row_t, float alpha, int32_t rows,
+                  int32_t M) {
+    SC_API_BEGIN
+    SC_CHECK(d_seqs && d_pos_table && (d_row_t || t_per_batch > 0) && M > 0 && ld >= M, "sc_op_pos_add: bad argument");
+    if (d_row_t) launch_pos_add_rows(d_seqs, ld, d_pos_table, d_row_t, alpha, rows, M, g_op_stream);
+    else launch_pos_add(d_seqs, ld, d_pos_table, t_per_batch, alpha, rows, M, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_durations(const float* d_h, int64_t ld, const float* d_w, const float* d_b, int32_t rows, int32_t H, int32_t t_per_batch,
+                    const int32_t* d_lens, float duration_factor, int32_t min_dur, int32_t* d_durations) {
+    SC_API_BEGIN
+    SC_CHECK(d_h && d_w && d_b && d_durations && H > 0 && ld >= H && t_per_batch > 0, "sc_op_durations: bad argument");
+    launch_durations(d_h, ld, d_w, d_b, rows, H, t_per_batch, d_lens, duration_factor, min_dur, d_durations, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_vocoder_embed(const int32_t* d_units, int32_t nb, int32_t T, const void* d_dict_f16, int32_t E, const void* d_lang_f16, int32_t Lg,
+                        const int32_t* d_lang_idx, const void* d_spkr_f16, int32_t Sp, const int32_t* d_spkr_idx, float* d_out,
+                        const int32_t* d_item_off, int32_t rows_total) {
+    SC_API_BEGIN
+    SC_CHECK(d_units && d_dict_f16 && d_lang_idx && d_spkr_idx && d_out && nb > 0 && E > 0 && Lg >= 0 && Sp >= 0 && (d_item_off || T > 0),
+             "sc_op_vocoder_embed: bad argument");
+    launch_vocoder_embed(d_units, nb, T, static_cast<const __half*>(d_dict_f16), E, static_cast<const __half*>(d_lang_f16), Lg, d_lang_idx,
+                         static_cast<const __half*>(d_spkr_f16), Sp, d_spkr_idx, d_out, g_op_stream, d_item_off, rows_total);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_item_row_pos(const int32_t* d_item_off, int32_t n_items, int32_t mul, int32_t rows, int32_t* d_row_pos) {
+    SC_API_BEGIN
+    SC_CHECK(d_item_off && d_row_pos && n_items > 0 && mul > 0 && (reinterpret_cast<uintptr_t>(d_row_pos) & 7) == 0,
+             "sc_op_item_row_pos: bad argument");
+    launch_item_row_pos(d_item_off, n_items, mul, rows, reinterpret_cast<int2*>(d_row_pos), g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_scatter_items(const float* d_src, const int32_t* d_item_off, const int32_t* d_item_of, int32_t n_items, int32_t mul, int32_t longest,
+                        int64_t dst_stride, float* d_dst) {
+    SC_API_BEGIN
+    SC_CHECK(d_src && d_item_off && d_item_of && d_dst && mul > 0 && dst_stride >= longest, "sc_op_scatter_items: bad argument");
+    launch_scatter_items(d_src, d_item_off, d_item_of, n_items, mul, longest, dst_stride, d_dst, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_glu_dwconv_ex(const float* d_x, const float* d_w, float* d_y, int32_t nb, int32_t T, int32_t C, int32_t k, const int32_t* d_lens,
+                        int32_t left, const float* d_bn_g, const float* d_bn_b, const float* d_bn_mean, const float* d_bn_var) {
+    SC_API_BEGIN
+    SC_CHECK(d_x && d_w && d_y && C > 0 && k > 0 && left < k, "sc_op_glu_dwconv_ex: bad argument");
+    SC_CHECK(!d_bn_g == !d_bn_b && !d_bn_g == !d_bn_mean && !d_bn_g == !d_bn_var, "sc_op_glu_dwconv_ex: BatchNorm needs g, b, mean and var");
+    OpScratch scratch;
+    float* fold = nullptr;
+    if (d_bn_g) {  // the load-time fold of the v1 encoder layer (model_load.hip)
+        fold = scratch.get<float>((size_t)2 * C);
+        launch_bn_fold(d_bn_g, d_bn_b, d_bn_mean, d_bn_var, 1e-5f, C, fold, fold + C, g_op_stream);
+    }
+    launch_glu_dwconv(d_x, 2 * C, d_w, d_y, C, nb, T, C, k, d_lens, g_op_stream, left, fold, fold ? fold + C : nullptr);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
+int sc_op_relpos_table(int32_t S, int32_t M, float* d_out) {
+    SC_API_BEGIN
+    SC_CHECK(d_out && S > 0 && M > 0 && M % 2 == 0, "sc_op_relpos_table: S=%d M=%d", S, M);
+    launch_relpos_table(S, M, d_out, g_op_stream);
+    SC_HIP(hipStreamSynchronize(g_op_stream));
+    SC_API_END
+}
+
 }  // extern "C"

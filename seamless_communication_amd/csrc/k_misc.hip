@@ -412,7 +412,9 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* __restrict_
         if (!lens || t < lens[n]) {
             const float x = acc + b[0];
             const float r = rintf((expf(x) - 1.0f) * duration_factor);
-            long long dl = (long long)r;
+            // the cap is taken before the conversion: from 2^63 on (x > 43.6; expf overflows at 88.7) the converted value
+            // is undefined and came out negative, which the floor then turned into min_dur
+            long long dl = r >= 1000000.f ? 1000000 : (long long)r;
             if (dl < (long long)min_dur) dl = min_dur;
             if (dl > 1000000) dl = 1000000;
             d = (int)dl;
