@@ -866,6 +866,31 @@ int sc_mix_timeline(const float* d_seg, int32_t n, int64_t seg_stride, const int
                     const float* h_gain, int32_t fade, const float* d_bed /* nullable [T] */, float duck, int32_t ramp, float* d_out,
                     int64_t T);
 
+/* ---- Time-scale modification (added within ABI v10, purely additive; an extension of this project, no reference counterpart;
+ * DESIGN.md section 7w): row i of L = h_in_len[i] samples becomes Lo = h_out_len[i] samples at the same pitch, by a
+ * waveform-similarity overlap-add (WSOLA).  No handle, current device, default stream, returns when d_out is complete (the
+ * conventions of sc_resample).  With N = frame (even, 64..2048), Hs = N / 2, D = radius (0..Hs), x = +0 outside [0, L):
+ *   q[i]   = clamp(rint(x[i] * 2^(14 - e)), -32767, 32767), e = floor(log2(max |x| over the finite samples)); 0 for a sample that is
+ *            not finite, and everywhere when no sample is finite or the maximum lies below 2^-100      (for the search only)
+ *   M      = ceil(Lo / Hs) + 1 frames; a_m = floor(m * Hs * L / Lo); c_0 = 0; c_m = a_m + d_m, where d_m in [-D, D] minimises
+ *            SAD(d) = sum_{k < N} |q[c_{m-1} + k] - q[a_m + d - Hs + k]| in integers; ties: the smallest |d|, then the negative one
+ *   y[t]   = w[k + Hs] * x[c_m + k] + w[k] * x[c_{m+1} - Hs + k], m = t / Hs, k = t - m * Hs, w[k] = 0.5 - 0.5 cos(2 pi k / N) built
+ *            in double on the host and rounded to fp32; two fp32 products and one fp32 sum, the order in k_tsm.hip's header
+ * Lo == L is a copy of the row's bits.  Only d_out[i][0, Lo) is written.  An item's result does not depend on its companions, to
+ * the bit.
+ *   opts  NULL or all-zero: frame 512, radius 160.  Otherwise abi_version must be SC_ABI_VERSION; a zero field stands for its
+ *         default, radius -1 for D = 0 (no search: plain overlap-add).
+ * SC_ERR_INVALID, before any device work: a null pointer, n outside 1..65535, a length that is negative or above its stride, L above
+ * 2^30, L == 0 with Lo != 0, L > 0 with Lo < 1, Lo > 4 L or L > 4 Lo, a frame that is odd or outside 64..2048, a radius above
+ * frame / 2, overlapping buffers. */
+typedef struct sc_tsm_opts {
+    int32_t abi_version;
+    int32_t frame;  /* N, samples; 0: 512 */
+    int32_t radius; /* D, samples; 0: 160, -1: none */
+} sc_tsm_opts;
+int sc_time_stretch(const float* d_in, int32_t n, int64_t in_stride, const int64_t* h_in_len, const sc_tsm_opts* opts /* nullable */,
+                    float* d_out, int64_t out_stride, const int64_t* h_out_len);
+
 /* ---- Speech detection (added within ABI v10, purely additive): a speech probability per window of `window` samples, the track
  * the reference takes from Silero VAD (segment/silero_vad.py get_speech_probs) in front of its segmentation of long input.  NOT a
  * learned model: an energy detector whose threshold adapts to the row (DESIGN.md section 7m has the definition; its constants are

@@ -505,6 +505,13 @@ int sc_op_fit_durations(const float* d_e, int32_t n, int32_t s_char, const int32
                         const float* h_lo, const float* h_hi, int32_t min_dur, int32_t* h_durations, float* h_factor,
                         int64_t* h_total, int32_t* h_flags);
 
+/* The search stage of sc_time_stretch by itself (k_tsm.hip; tests/test_tsm_gpu.py, scripts/tsm_bench.py): the peak, the
+ * quantisation and the frame walk of every item, no overlap-add.  Arguments and refusals as sc_time_stretch takes them (there is
+ * no output buffer).  -> h_centres [n][m_stride] int32: item i's M_i = ceil(Lo_i / Hs) + 1 centres c_0 .. c_{M_i - 1}; what lies
+ * behind them is left as it was.  m_stride below the largest M_i is SC_ERR_INVALID.  No handle, current device, default stream. */
+int sc_op_tsm_centres(const float* d_in, int32_t n, int64_t in_stride, const int64_t* h_in_len, const int64_t* h_out_len,
+                      const sc_tsm_opts* opts, int32_t* h_centres, int64_t m_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,6 +13,9 @@ one by one predict(slice, "s2st") for every segment: what a caller had to do bef
 fit        the fit kernel through its hook (sc_op_fit_durations) on e values of the shape of one batch: a host clock around the
            synchronous hook call, which also allocates its scratch and copies the tables and the results.
 mix        sc_mix_timeline on the run's own waveforms and places: a host clock around the synchronous call.
+stretch    translate_long(..., stretch_max=1.25): late waveforms are shortened behind the vocoder (sc_time_stretch) and placed by
+           place_stretched; its time and its late segments stand next to the fit=True row's.  Then the stretch call alone on the
+           waveforms that run shortened, next to the vocoder call that made a batch of 32 of them.
 Host clocks around calls that end in a device synchronise, medians after `--warmup` untimed passes.  There is no pass / fail
 ratio and no figure is promised: the file is the record.  Seeded weights say nothing about how the result sounds."""
 import argparse
@@ -99,6 +102,8 @@ free, t_free, lo, hi = median_ms(lambda: tr.translate_long(wav, "s2st", "fra", s
 say(f"translate_long, fit=False:                {t_free:10.1f} ms median (min {lo:.1f}, max {hi:.1f}, {a.reps} reps)")
 _, t_bed, lo, hi = median_ms(lambda: tr.translate_long(wav, "s2st", "fra", segmenter=seg, keep_source=0.3))
 say(f"translate_long, fit=True, keep_source=0.3:{t_bed:10.1f} ms median (min {lo:.1f}, max {hi:.1f}, {a.reps} reps)")
+tsm, t_tsm, lo, hi = median_ms(lambda: tr.translate_long(wav, "s2st", "fra", segmenter=seg, stretch_max=1.25))
+say(f"translate_long, fit=True, stretch_max=1.25:{t_tsm:9.1f} ms median (min {lo:.1f}, max {hi:.1f}, {a.reps} reps)")
 ref, t_one, lo, hi = median_ms(lambda: [tr.predict(wav[s:e], "s2st", "fra") + (list(tr.last_text_ids[0]),) for s, e in spans])
 say(f"predict on the segments one by one:       {t_one:10.1f} ms median (min {lo:.1f}, max {hi:.1f}, {a.reps} reps)")
 same_text = sum(list(r[2]) == g.token_ids for r, g in zip(ref, free.segments))
@@ -117,6 +122,34 @@ say(f"fit: unit totals {sum(units_free)} -> {sum(units_fit)}; factors min {facs.
     f"({100.0 * sum(s.late_s > 0 for s in res.segments) / n:.0f} %, at most {max(s.late_s for s in res.segments):.2f} s); "
     f"fit=False: starting late {sum(s.late_s > 0 for s in free.segments)}/{n} (at most {max(s.late_s for s in free.segments):.2f} s); "
     f"track {res.audio.shape[1] / RATE:.1f} s")
+
+late = lambda r: [s.late_s for s in r.segments]
+say(f"stretch_max=1.25 against fit=True alone ({t_tsm:.1f} ms against {t_long:.1f} ms): shortened {sum(s.stretch > 1.0 for s in tsm.segments)}/{n} "
+    f"(at the limit 1.25: {sum(s.stretch >= 1.25 for s in tsm.segments)}), starting late {sum(x > 0 for x in late(tsm))}/{n} (at most {max(late(tsm)):.2f} s, "
+    f"median {np.median(late(tsm)):.2f} s) against {sum(x > 0 for x in late(res))}/{n} (at most {max(late(res)):.2f} s, median {np.median(late(res)):.2f} s); "
+    f"track {tsm.audio.shape[1] / RATE:.1f} s")
+short = [k for k, s in enumerate(tsm.segments) if s.stretch > 1.0]
+if short:
+    in_lens = [res.segments[k].wav.shape[-1] for k in short]
+    out_lens = [tsm.segments[k].wav.shape[-1] for k in short]
+    in_rows = torch.zeros(len(short), max(in_lens), device="cuda")
+    for r, k in enumerate(short):
+        in_rows[r, : in_lens[r]] = res.segments[k].wav[0]
+    _, t, lo, hi = median_ms(lambda: rt.time_stretch_rows(in_rows, in_lens, out_lens), reps=max(a.reps, 5))
+    say(f"stretch call alone, the {len(short)} waveforms that run shortened ({sum(in_lens) / RATE:.1f} s -> {sum(out_lens) / RATE:.1f} s of audio): {t:.3f} ms median "
+        f"(min {lo:.3f}, max {hi:.3f}; with the output allocation)")
+    first = short[:32]
+    ul = [res.segments[k].wav.shape[-1] // hop for k in first]
+    pad = tr.unit_tokenizer.vocab_info.pad_idx
+    ub = np.full((len(first), max(ul)), pad, dtype=np.int32)
+    for r, k in enumerate(first):
+        ub[r, : len(res.segments[k].units)] = res.segments[k].units
+    li = [tr.lang_spkr_idx_map["multilingual"]["fra"]] * len(first)
+    si = [tr.lang_spkr_idx_map["multispkr"]["fra"][0]] * len(first)
+    _, tv, lo, hi = median_ms(lambda: tr.model.vocode(ub, li, si, ul), reps=max(a.reps, 5))
+    _, ts, lo2, hi2 = median_ms(lambda: rt.time_stretch_rows(in_rows[: len(first)].contiguous(), in_lens[: len(first)], out_lens[: len(first)]), reps=max(a.reps, 5))
+    say(f"one batch of {len(first)}: vocoder call {tv:.3f} ms median (min {lo:.3f}, max {hi:.3f}); stretch call on its waveforms {ts:.3f} ms median "
+        f"(min {lo2:.3f}, max {hi2:.3f}): {ts / tv:.2f} of the vocoder's time")
 
 # the fit kernel alone: one batch of 32 items with the characters of this run's longest texts
 rows, chars = 32, 256

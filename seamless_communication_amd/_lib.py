@@ -164,6 +164,10 @@ class sc_resample_opts(C.Structure):
     _fields_ = [("abi_version", _i), ("lowpass_filter_width", _i), ("rolloff", C.c_float), ("method", _i), ("beta", C.c_float)]
 
 
+class sc_tsm_opts(C.Structure):
+    _fields_ = [("abi_version", _i), ("frame", _i), ("radius", _i)]
+
+
 class sc_vad_opts(C.Structure):
     _fields_ = [("abi_version", _i), ("hangover", _i), ("floor_quantile", C.c_float), ("peak_quantile", C.c_float),
                 ("noise_ceiling_db", C.c_float), ("min_margin_db", C.c_float), ("range_fraction", C.c_float), ("slope_db", C.c_float)]
@@ -310,6 +314,7 @@ SIGNATURES = {
     "sc_resample_len": (C.c_int64, [C.c_int64, _i, _i]),
     "sc_resample": (C.c_int, [_P, _i, C.c_int64, _P, _i, _i, C.POINTER(sc_resample_opts), _P, C.c_int64, _P]),
     "sc_mix_timeline": (C.c_int, [_P, _i, C.c_int64, _P, _P, _P, _i, _P, C.c_float, _i, _P, C.c_int64]),
+    "sc_time_stretch": (C.c_int, [_P, _i, C.c_int64, _P, C.POINTER(sc_tsm_opts), _P, C.c_int64, _P]),
     "sc_vad_windows": (C.c_int64, [C.c_int64, _i]),
     "sc_vad_probs": (C.c_int, [_P, _i, C.c_int64, _P, _i, C.POINTER(sc_vad_opts), _P, C.c_int64, _P, _P]),
     "sc_vad_stream_create": (C.c_int, [_i, _i, C.POINTER(sc_vad_stream_opts), C.POINTER(_P)]),
@@ -322,6 +327,7 @@ SIGNATURES = {
     "sc_op_resample_bank": (C.c_int, [_i, _i, C.POINTER(sc_resample_opts), _PI, _PI, _P, _P, C.c_int64]),
     "sc_op_resample_plan": (C.c_int, [_i, _i, C.POINTER(sc_resample_opts), _P]),
     "sc_op_fit_durations": (C.c_int, [_P, _i, _i, _P, _P, _P, _P, _i, _P, _P, _P, _P]),
+    "sc_op_tsm_centres": (C.c_int, [_P, _i, C.c_int64, _P, _P, C.POINTER(sc_tsm_opts), _P, C.c_int64]),
     "sc_op_knob": (C.c_int, [C.c_char_p, C.c_int]),
     "sc_op_force_general_gemm": (C.c_int, [C.c_int]),
     "sc_op_voc_pack_plan": (C.c_int32, [_PI, C.c_int32, C.c_int64, _PI, C.c_int32]),

@@ -1,5 +1,6 @@
-"""Audio resampling on the device: ``torchaudio.functional.resample``'s windowed-sinc polyphase algorithm, restated - and, at the
-end of the file, speech detection on the device (``speech_probs``: the probability track the speech segmenter splits long input by).
+"""Audio resampling on the device: ``torchaudio.functional.resample``'s windowed-sinc polyphase algorithm, restated - and, behind
+it, time-scale modification (``time_stretch``: another length at the same pitch, an extension of this project)
+and speech detection on the device (``speech_probs``: the probability track the speech segmenter splits long input by).
 
 The reference resamples to 16 kHz with torchaudio in front of every model that opens a file (cli/m4t/predict/predict.py:226-231,
 cli/expressivity/predict/predict.py:115, models/aligner/alignment_extractor.py:63-71).  torchaudio is not a dependency here; the
@@ -58,6 +59,54 @@ def resample_ragged(waves: Sequence[Tensor], orig_freq: int, new_freq: int, lowp
         rows[i, : lens[i]] = w
     out, out_lens = _rt.resample_rows(rows, lens, int(orig_freq), int(new_freq), opts)
     return [out[i, : int(out_lens[i])].to(waves[i].dtype) for i in range(len(waves))]
+
+
+# ---- time-scale modification (sc_time_stretch) -------------------------------------------------------------
+
+def time_stretch(waveform: Tensor, rate: Optional[float] = None, *, out_len: Optional[int] = None, frame: int = 512,
+                 radius: int = 160) -> Tensor:
+    """``waveform`` (..., time) -> (..., out_len) at the same pitch and sample rate, in the input's dtype (the arithmetic is fp32):
+    a waveform-similarity overlap-add (WSOLA).  Exactly one of ``rate`` (> 1 is faster: ``out_len = max(1, round(time / rate))``)
+    and ``out_len`` is given; the ratio must lie in [1/4, 4].  ``frame`` samples per frame (even, 64..2048; 512 is 32 ms at
+    16 kHz), ``radius`` samples a frame may move to line up with its predecessor (0..frame / 2; 160 is 10 ms).  Every leading index
+    is a row of one device call.  An extension of this project whose constants nobody has evaluated by ear."""
+    _check(waveform, "waveform")
+    if waveform.dim() < 1:
+        raise ValueError("waveform must have a time dimension")
+    if (rate is None) == (out_len is None):
+        raise ValueError("exactly one of rate and out_len must be given")
+    lead, T = waveform.shape[:-1], waveform.shape[-1]
+    if rate is not None:
+        if not (isinstance(rate, (int, float)) and rate == rate and 0 < rate < float("inf")):
+            raise ValueError(f"rate must be a finite number > 0, got {rate!r}")
+        out_len = max(1, round(T / float(rate))) if T else 0
+    out_len = int(out_len)
+    rows = waveform.reshape(-1, T).to(torch.float32).contiguous()
+    out = _rt.time_stretch_rows(rows, [T] * rows.shape[0], [out_len] * rows.shape[0], frame, radius)
+    return out.reshape(*lead, out_len).to(waveform.dtype)
+
+
+def time_stretch_ragged(waves: Sequence[Tensor], out_lens: Sequence[int], frame: int = 512, radius: int = 160) -> List[Tensor]:
+    """1-D waveforms of different lengths, each to its own ``out_lens[i]`` samples, in ONE device call; per item what
+    :func:`time_stretch` returns for it alone, to the bit."""
+    waves = list(waves)
+    for w in waves:
+        _check(w, "every waveform")
+        if w.dim() != 1:
+            raise ValueError(f"time_stretch_ragged takes 1-D waveforms, got shape {tuple(w.shape)}")
+    out_lens = [int(x) for x in out_lens]
+    if len(out_lens) != len(waves):
+        raise ValueError(f"out_lens must hold one entry per waveform ({len(waves)})")
+    if not waves:
+        return []
+    if len({w.device for w in waves}) != 1:
+        raise ValueError("the waveforms must be on one device")
+    lens = [int(w.shape[0]) for w in waves]
+    rows = torch.zeros(len(waves), max(max(lens), 1), dtype=torch.float32, device=waves[0].device)
+    for i, w in enumerate(waves):
+        rows[i, : lens[i]] = w
+    out = _rt.time_stretch_rows(rows, lens, out_lens, frame, radius)
+    return [out[i, : out_lens[i]].to(waves[i].dtype) for i in range(len(waves))]
 
 
 # ---- speech detection (sc_vad_probs; DESIGN.md section 7m) ---------------------------------------------------------------------

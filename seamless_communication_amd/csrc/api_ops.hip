@@ -1596,4 +1596,11 @@ int sc_op_relpos_table(int32_t S, int32_t M, float* d_out) {
     SC_API_END
 }
 
+int sc_op_tsm_centres(const float* d_in, int32_t n, int64_t in_stride, const int64_t* h_in_len, const int64_t* h_out_len,
+                      const sc_tsm_opts* opts, int32_t* h_centres, int64_t m_stride) {
+    SC_API_BEGIN
+    run_time_stretch("sc_op_tsm_centres", d_in, n, in_stride, h_in_len, h_out_len, opts, false, nullptr, 0, h_centres, m_stride);
+    SC_API_END
+}
+
 }  // extern "C"

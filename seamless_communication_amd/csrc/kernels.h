@@ -38,6 +38,8 @@
 #include "boost_list.h"
 #include "prof.h"
 
+struct sc_tsm_opts;  // include/seamless_hip.h
+
 namespace sc {
 
 // ACT_GELU: exact (erf) GELU, 0.5 v (1 + erf(v / sqrt 2)); implemented by launch_gemm (both the fast and the general kernel),
@@ -864,6 +866,12 @@ struct FitArgs {
 void launch_fit_durations(const FitArgs& a, int n, hipStream_t s);
 // SC_ERR_INVALID naming the item: a negative target, a bound that is not finite, lo <= 0, lo > hi (host only)
 void check_fit_items(const char* who, int n, const int32_t* h_target, const float* h_lo, const float* h_hi);
+// Time-scale modification (k_tsm.hip): the body of sc_time_stretch and of sc_op_tsm_centres.  Every
+// argument check (SC_ERR_INVALID naming `who`) comes before the first device call; then the peak, the frame walk (one workgroup
+// per item) and - with d_out - the overlap-add, on the default stream; returns when the results are complete.  with_out: d_out / out_stride
+// are checked and written (sc_time_stretch); otherwise the search alone, and h_centres [n][m_stride] takes the centres.
+void run_time_stretch(const char* who, const float* d_in, int n, int64_t in_stride, const int64_t* h_in_len, const int64_t* h_out_len,
+                      const ::sc_tsm_opts* opts, bool with_out, float* d_out, int64_t out_stride, int32_t* h_centres, int64_t m_stride);
 void launch_vocoder_embed(const int* units, int nb, int T, const __half* dict, int E,
                           const __half* lang, int Lg, const int* lang_idx, const __half* spkr, int Sp,
                           const int* spkr_idx, float* out /*[nb*T][Lg+E+Sp]*/, hipStream_t s,

@@ -17,6 +17,10 @@ The host arithmetic, in integer samples at 16 kHz (``hop`` = samples per unit, 3
   ``target_i = max(1, (limit_i - s_i) // hop)`` units.
 * placement: ``p_i = max(s_i, q_{i-1} + gap)``, ``q_i = p_i + unit_len_i * hop``.  Targets are set from the slots before the drift is
   known: a segment pushed late by its predecessor may pass its limit.  That is reported (``late_s``, ``over``), not hidden.
+* ``stretch_max > 1`` (``place_stretched``): the placement runs behind the vocoder, when the real lengths and the real drift are
+  known.  ``avail_i = limit_i - p_i``; a waveform of ``len_i <= avail_i`` samples stays as it is, a longer one is shortened to
+  ``out_i = max(avail_i, ceil(len_i / stretch_max), 1)`` samples at the same pitch (``sc_time_stretch``), and
+  ``q_i = p_i + out_i``.
 """
 from __future__ import annotations
 
@@ -41,7 +45,8 @@ class DubbedSegment:
     ``wav`` (1, samples) on the device / ``factor`` (the fitted duration factor) / ``target_units`` (the slot's unit budget, 0:
     none) / ``placed_start_s`` / ``placed_end_s`` (where the translation sounds in the track) / ``late_s`` (how much later than
     its source it starts, pushed by its predecessors) / ``over`` (even the lowest factor did not fit the budget): None / 0 / False
-    for text tasks."""
+    for text tasks.  ``stretch``: the waveform was shortened by this factor after the vocoder (``stretch_max``; 1.0: untouched);
+    ``wav`` is the shortened waveform, ``units`` / ``factor`` / ``over`` / ``target_units`` describe what the T2U made."""
     start_s: float
     end_s: float
     text: Any
@@ -54,6 +59,7 @@ class DubbedSegment:
     placed_end_s: Optional[float] = None
     late_s: float = 0.0
     over: bool = False
+    stretch: float = 1.0
 
 
 @dataclass
@@ -101,6 +107,23 @@ def place_segments(starts: Sequence[int], unit_lens: Sequence[int], hop: int, ga
     return p, q
 
 
+def place_stretched(starts: Sequence[int], limits: Sequence[int], lens: Sequence[int], gap: int,
+                    stretch_max: float) -> Tuple[List[int], List[int], List[int]]:
+    """-> (p, q, out): ``place_segments`` on waveforms of ``lens[i]`` samples that may be shortened by up to ``stretch_max``.  One
+    pass in source order, so the drift a segment inherits is known when its length is chosen: it sounds in ``[p_i, q_i)`` with
+    ``out_i`` samples - its own length where that ends by ``limits[i]``, else as short as the limit asks, but not below
+    ``ceil(len_i / stretch_max)``."""
+    p, q, out = [], [], []
+    for i, s in enumerate(starts):
+        pi = int(s) if i == 0 else max(int(s), q[-1] + gap)
+        n, avail = int(lens[i]), int(limits[i]) - pi
+        oi = n if n <= avail else max(avail, math.ceil(n / stretch_max), 1)
+        p.append(pi)
+        q.append(pi + oi)
+        out.append(oi)
+    return p, q, out
+
+
 # ---- the driver ---------------------------------------------------------------------------------------------------------------------
 
 def _samples(value: float, what: str, per_second: float = 1.0) -> int:
@@ -111,7 +134,8 @@ def _samples(value: float, what: str, per_second: float = 1.0) -> int:
 
 
 def check_arguments(self, task_str: str, tgt_lang: Optional[str], sample_rate: int, segmenter: Any, batch_rows: int, min_factor: float,
-                    max_factor: float, spill_sec: float, gap_sec: float, fade_ms: float, keep_source: float, ramp_ms: float) -> bool:
+                    max_factor: float, spill_sec: float, gap_sec: float, fade_ms: float, keep_source: float, ramp_ms: float,
+                    stretch_max: float = 1.0) -> bool:
     """Every refusal of ``translate_long``, before any device work -> whether the task has speech output."""
     task = str(task_str).upper()
     if task not in SPEECH_TASKS + TEXT_TASKS:
@@ -131,6 +155,8 @@ def check_arguments(self, task_str: str, tgt_lang: Optional[str], sample_rate: i
     _samples(spill_sec, "spill_sec"), _samples(gap_sec, "gap_sec"), _samples(fade_ms, "fade_ms", 1e3), _samples(ramp_ms, "ramp_ms", 1e3)
     if not (isinstance(keep_source, (int, float)) and 0.0 <= keep_source <= 1.0):
         raise ValueError(f"keep_source must lie in [0, 1], got {keep_source!r}")
+    if not (isinstance(stretch_max, (int, float)) and math.isfinite(stretch_max) and 1.0 <= stretch_max <= 2.0):
+        raise ValueError(f"stretch_max must be a finite number in [1, 2] (1: no time-scale modification), got {stretch_max!r}")
     if self.multi_channel not in ("first", "mean", "error"):
         raise ValueError(f"Translator.multi_channel must be 'first', 'mean' or 'error', not {self.multi_channel!r}")
     if want_speech:
@@ -171,7 +197,8 @@ def _mono_16k(self, audio: Union[str, Tensor], sample_rate: int) -> Tensor:
 
 
 @torch.inference_mode()
-def translate_long(self, audio: Union[str, Tensor], task_str: str, tgt_lang: Optional[str], src_lang: Optional[str] = None, *,
+def translate_long(self, audio: Union[str, Tensor], task_str: str, tgt_lang: Optional[str], src_lang: Optional[str] = None,
+                   stretch_max: float = 1.0, *,
                    sample_rate: int = RATE, segmenter: Any = None, chunk_size_sec: float = 15, pause_length_sec: float = 0.5,
                    batch_rows: int = 32, fit: bool = True, min_factor: float = 0.75, max_factor: float = 1.0, spill_sec: float = 0.0,
                    gap_sec: float = 0.08, fade_ms: float = 5, keep_source: float = 0.0, ramp_ms: float = 50, match_level: bool = False,
@@ -187,6 +214,11 @@ def translate_long(self, audio: Union[str, Tensor], task_str: str, tgt_lang: Opt
     (module docstring; ``spill_sec`` lets a slot reach into the pause behind it, ``gap_sec`` is kept free in front of the next
     segment).  The defaults never stretch speech beyond the model's own pace and never compress it below 0.75 - this project's
     choice, unevaluated.  ``fit=False``: the model's own pace (factor 1) for all.
+    ``stretch_max > 1`` (at most 2): a finished waveform that would end behind its slot - too long even at ``min_factor``, or pushed
+    late by its predecessors - is shortened at the same pitch by up to this factor, in one ``sc_time_stretch`` call for all such
+    segments (``place_stretched``; ``DubbedSegment.stretch``).  1.0 is off: the launches and the bits of a call without it.
+    Unevaluated like the rest: nobody has listened to speech shortened this way.  (It stands in front of the keyword-only
+    options, whose set tests/test_longform_cpu.py pins; pass it by name.)
     The track: each waveform at its place with linear fades of ``fade_ms``; ``keep_source > 0`` keeps the 16 kHz source underneath,
     attenuated to ``keep_source`` where a translation sounds (ramps of ``ramp_ms``); ``match_level=True`` scales every segment to
     its source's RMS level (gain clamped to [0.25, 4]).
@@ -198,7 +230,7 @@ def translate_long(self, audio: Union[str, Tensor], task_str: str, tgt_lang: Opt
     from .inference.translator import Modality, parse_forced_prefix
 
     want_speech = check_arguments(self, task_str, tgt_lang, sample_rate, segmenter, batch_rows, min_factor, max_factor, spill_sec, gap_sec,
-                                  fade_ms, keep_source, ramp_ms)
+                                  fade_ms, keep_source, ramp_ms, stretch_max)
     forced = parse_forced_prefix(self.text_tokenizer, forced_prefix, tgt_lang) if forced_prefix is not None else None
     self.text_tokenizer.target_prefix(tgt_lang)  # an unknown language is an error here
     spill, gap = _samples(spill_sec, "spill_sec"), _samples(gap_sec, "gap_sec")
@@ -270,7 +302,21 @@ def translate_long(self, audio: Union[str, Tensor], task_str: str, tgt_lang: Opt
 
     from . import runtime as _rt
 
-    p, q = place_segments([s for s, _ in spans], unit_lens, hop, gap)
+    if stretch_max > 1.0:
+        full = [u * hop for u in unit_lens]
+        p, q, outs = place_stretched([s for s, _ in spans], limits, full, gap, float(stretch_max))
+        short = [i for i in range(len(spans)) if outs[i] != full[i] and full[i] > 0]  # (an empty waveform has nothing to shorten)
+        if short:
+            rows = torch.zeros(len(short), max(full[i] for i in short), dtype=torch.float32, device=self.device)
+            for r, i in enumerate(short):
+                rows[r, : full[i]] = wavs[i]
+            done = _rt.time_stretch_rows(rows, [full[i] for i in short], [outs[i] for i in short])
+            for r, i in enumerate(short):
+                segments[i].wav = done[r : r + 1, : outs[i]]
+                segments[i].stretch = full[i] / outs[i]
+                wavs[i] = segments[i].wav[0]
+    else:
+        p, q = place_segments([s for s, _ in spans], unit_lens, hop, gap)
     T = max(total, q[-1] if q else 0)
     gains = [1.0] * len(spans)
     if match_level:

@@ -1503,3 +1503,57 @@ def mix_timeline(segs: torch.Tensor, lens: Sequence[int], starts: Sequence[int],
         check(lib.sc_mix_timeline(_ptr(segs) if n else None, n, segs.shape[1], _ptr(ln), _ptr(st), _ptr(g), int(fade), _ptr(bed), float(duck),
                                   int(ramp), _ptr(out), int(total)), "sc_mix_timeline")
     return out
+
+
+def tsm_opts(frame: int = 512, radius: int = 160) -> _lib.sc_tsm_opts:
+    """The options of ``sc_time_stretch``: ``frame`` samples per frame (even, 64..2048), ``radius`` samples the search may move a
+    frame either way (0..frame / 2; 0 here is "no search", which the C struct spells -1 because its 0 stands for the default)."""
+    frame, radius = int(frame), int(radius)
+    if frame <= 0 or radius < 0:
+        raise ValueError(f"frame must be positive and radius >= 0, got {frame}, {radius}")
+    return _lib.sc_tsm_opts(_lib.SC_ABI_VERSION, frame, -1 if radius == 0 else radius)
+
+
+def _tsm_lens(rows: torch.Tensor, lens: Sequence[int], out_lens: Sequence[int]) -> Tuple[np.ndarray, np.ndarray]:
+    assert rows.is_cuda and rows.dtype == torch.float32 and rows.dim() == 2 and rows.is_contiguous()
+    in_len = np.ascontiguousarray(np.asarray(lens, dtype=np.int64).reshape(-1))
+    out_len = np.ascontiguousarray(np.asarray(out_lens, dtype=np.int64).reshape(-1))
+    if not (in_len.shape == out_len.shape == (rows.shape[0],)):
+        raise ValueError(f"lens and out_lens must hold one entry per row ({rows.shape[0]})")
+    return in_len, out_len
+
+
+def time_stretch_rows(rows: torch.Tensor, lens: Sequence[int], out_lens: Sequence[int], frame: int = 512, radius: int = 160) -> torch.Tensor:
+    """``sc_time_stretch`` on ``rows`` (n, stride) fp32 on a HIP device: row i, valid up to ``lens[i]``, becomes ``out_lens[i]``
+    samples at the same pitch (WSOLA) -> (n, longest out_len) with zeros behind every row's own length.
+    No handle: the call runs on the tensor's device, on the default stream."""
+    lib = _lib.load_library()
+    in_len, out_len = _tsm_lens(rows, lens, out_lens)
+    opts = tsm_opts(frame, radius)
+    n = rows.shape[0]
+    stride = max(int(out_len.max()), 0) if n else 0
+    out = torch.zeros(n, stride, dtype=torch.float32, device=rows.device)
+    if n == 0:
+        return out
+    with torch.cuda.device(rows.device):
+        # the entry launches on the default stream: order it behind the producer of `rows` (and the zeros of `out`)
+        cur = torch.cuda.current_stream(rows.device)
+        if cur.cuda_stream != 0:
+            cur.synchronize()
+        check(lib.sc_time_stretch(_ptr(rows), n, rows.shape[1], _ptr(in_len), C.byref(opts), _ptr(out), stride, _ptr(out_len)), "sc_time_stretch")
+    return out
+
+
+def tsm_centres(rows: torch.Tensor, lens: Sequence[int], out_lens: Sequence[int], frame: int = 512, radius: int = 160) -> List[np.ndarray]:
+    """``sc_op_tsm_centres``: the frame centres ``sc_time_stretch`` finds for every row, int32 arrays of ceil(out_len / (frame / 2)) + 1."""
+    lib = _lib.load_library()
+    in_len, out_len = _tsm_lens(rows, lens, out_lens)
+    opts = tsm_opts(frame, radius)
+    n, hs = rows.shape[0], int(frame) // 2
+    counts = [-(-int(x) // hs) + 1 if hs > 0 and x >= 0 else 1 for x in out_len]
+    m_stride = max(counts + [1])
+    got = np.full((n, m_stride), np.iinfo(np.int32).min, dtype=np.int32)
+    with torch.cuda.device(rows.device):
+        torch.cuda.current_stream(rows.device).synchronize()
+        check(lib.sc_op_tsm_centres(_ptr(rows), n, rows.shape[1], _ptr(in_len), _ptr(out_len), C.byref(opts), _ptr(got), m_stride), "sc_op_tsm_centres")
+    return [got[i, : counts[i]].copy() for i in range(n)]
