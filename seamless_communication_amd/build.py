@@ -18,7 +18,7 @@ LIB = Path(__file__).resolve().parent / "libseamless_hip.so"
 OBJ_DIR = CSRC / "build"
 SOURCES = [
     "common.cpp", "boost_list.cpp", "prof.hip", "k_gemm.hip", "k_gemm2.hip", "k_gemm_ps.hip", "k_resblock.hip", "k_skinny.hip", "k_dstep.hip", "k_dstep3.hip", "k_norm.hip", "k_attn.hip", "k_attn_hd.hip", "k_w2v2.hip", "k_fbank.hip", "k_misc.hip", "k_beam.hip", "k_sample.hip", "k_engine.hip", "k_xattn.hip", "k_align.hip", "k_ecapa.hip", "k_pretssel.hip", "k_seanet.hip", "k_resample.hip", "k_vad.hip", "k_mbr.hip", "k_metrics.hip", "k_dub.hip", "k_tsm.hip",
-    "model_load.hip", "model_encoder.hip", "model_decoder.hip", "model_dstep.hip", "model_sample.hip", "model_t2u.hip", "model_align.hip", "model_w2v2.hip", "model_ecapa.hip", "model_pretssel.hip", "model_pretssel_wave.hip", "engine.hip", "mma_pool.hip", "api.hip", "api_ops.hip",
+    "model_load.hip", "layers.hip", "model_encoder.hip", "model_decoder.hip", "model_dstep.hip", "model_sample.hip", "model_t2u.hip", "model_align.hip", "model_w2v2.hip", "model_ecapa.hip", "model_pretssel.hip", "model_pretssel_wave.hip", "engine.hip", "mma_pool.hip", "api.hip", "api_ops.hip",
 ]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 

@@ -494,6 +494,75 @@ inline void project_cross_kv(Model& m, const float* d_enc, const Linear& L, floa
 }
 void layernorm(Model& m, const float* x, const LNorm& L, float* y, int rows, int act = ACT_NONE,
                const int* lens = nullptr, int t_per_batch = 1);
+
+// ---- products, attention and whole layers shared by the stage passes (layers.hip) ----
+struct Planes {  // an operand of the pre-split products: two fp16 planes [rows][dim]
+    __half* hi = nullptr;
+    __half* lo = nullptr;
+};
+// The rows of a batch, padded or packed.  Padded: item i holds rows [i * S, (i + 1) * S), rows = n * S.  Packed (d_off set):
+// item i holds rows [d_off[i], d_off[i] + d_lens[i]) with nothing in between, rows = their sum, S = the longest item.
+struct BatchRows {
+    int n = 0, S = 0, rows = 0;
+    const int* d_lens = nullptr;  // live rows (= keys) per item; nullable for a padded batch
+    const int* d_off = nullptr;   // null: padded
+    double pairs = 0;             // packed, profiler only: sum of len^2
+};
+// C (fp32) and/or out (split planes) = alpha * act(A . W^T + b) + res over `rows` rows of the planes `a`
+// split 0: the hi plane only (SC_SPLIT_MODE=1, the padded speech encoder's precision study)
+void linear_ps(Model& m, Planes a, const Linear& L, int rows, int act, float alpha, const float* res, float* C, Planes out = {}, int split = 1);
+// Self-attention over a [rows][3M] q | k | v buffer.  The result goes to `out` (fp32 [rows][M]) or to the planes `out_p`.
+struct SelfAttn {
+    int heads = 0, head_dim = 64;
+    float* out = nullptr;
+    Planes out_p;
+    int causal = 0;
+    const float* rel_k = nullptr;  // Shaw relative keys, with rel_left / rel_right
+    int rel_left = 0, rel_right = 0;
+    const float* rp_table = nullptr;  // v1 relative positions [2S - 1][M], with the u / v query biases
+    const float* q_bias_u = nullptr;
+    const float* q_bias_v = nullptr;
+};
+void self_attention(Model& m, const float* qkv, int M, const BatchRows& b, const SelfAttn& o);
+
+// One Conformer layer of the speech encoder on pre-split planes, x [rows][M] in place; padded and packed batches alike, which
+// is why an item carries the same bits through run_encode_speech and run_encode_speech_ragged.
+struct ConformerPass {
+    float* x = nullptr;     // residual stream
+    float* wide = nullptr;  // [rows][3M]
+    float* att = nullptr;   // [rows][M]; only with fuse_conv off
+    Planes hs, as, ws;      // [rows][M], [rows][M], [rows][enc_ffn_dim]
+    bool fuse_conv = true;  // GLU + depthwise conv + LayerNorm + SiLU in one kernel
+    bool fuse_ln = true;    // the closing LayerNorm together with the next layer's first one
+    bool glu_epi = true;    // GLU in the first pointwise product's epilogue (needs fuse_conv)
+    int split = 1;          // linear_ps
+    const int* d_work = nullptr;  // packed: work table of the convolution module (glu_dwconv_ln_packed_work)
+    int n_work = 0;
+};
+// next: the layer behind l (null: l is the last).  ffn1_ready: the previous layer's closing launch already wrote LN_ffn1(x) into
+// p.hs; returns the same for the next layer.
+bool conformer_layer(Model& m, const ConformerLayer& l, const ConformerLayer* next, const BatchRows& b, const ConformerPass& p, bool ffn1_ready);
+// The adaptor layer behind its two strided convolutions (y: the attention branch, res: the residual branch, both [rows][M]):
+// y = FFN(attention(y) + res) without the final LayerNorm.  aw [rows][max(3M, adaptor_ffn_dim)] and ah [rows][M] are scratch.
+void adaptor_layer_tail(Model& m, const AdaptorLayer& a, const BatchRows& b, const float* res, float* y, float* aw, float* ah, bool row_independent);
+// One pre-LN transformer encoder layer on the fp32-operand products, x [rows][M] in place; h, att [rows][M] and
+// wide [rows][max(3M, ffn)] are scratch.
+void encoder_layer(Model& m, const EncoderLayer& l, const BatchRows& b, int heads, int head_dim, int ffn_act, bool row_independent, float* x,
+                   float* h, float* wide, float* att);
+// One post-LN FFT layer (NAR T2U decoder, PRETSSEL) on packed rows: u (fp32) and up (planes) hold the input and receive the
+// output.  film != null: FiLM behind the second LayerNorm from row film_off.. of the table, item of a row in row_item.
+struct FFTPass {
+    float* u = nullptr;
+    float* y = nullptr;
+    float* wide = nullptr;  // [rows][3M]
+    Planes up, yp, ap, wp;  // [rows][M] x 3, [rows][conv inner dim]
+    const int2* d_row_pos = nullptr;  // {position, item length} of every row
+    int heads = 0, head_dim = 64;
+    const float* film = nullptr;
+    int film_ld = 0;
+    const int* row_item = nullptr;
+};
+int fft_layer_packed(Model& m, const FFTLayer& l, int film_off, const BatchRows& b, const FFTPass& p);  // returns the launches made
 // Packed items of a ragged batch (the vocoder's packed pass): item i holds the unit rows [off[i], off[i + 1]) of every
 // buffer, items back to back with no rows in between; at a stage that runs `mul` rows per unit row, the rows
 // [off[i] * mul, off[i + 1] * mul).  Kernels take the device copy of `off` (GemmArgs::item_off and its kin).

@@ -342,22 +342,17 @@ void run_decode_text_batched(Model& m, const float* d_enc, int n, int s_enc, con
         ckv(m.pp(), (size_t)erows * 2 * M);
     float* x = d_hidden;
     launch_embed_tokens(d_tok, rows, m.text_embed, M, sqrtf((float)M), m.text_pos, nullptr, s_text, x, M, m.stream);
+    BatchRows br;
+    br.n = n, br.S = s_text, br.rows = rows;
+    SelfAttn self_at;
+    self_at.heads = cfg.num_heads;
+    self_at.out = att;
+    self_at.causal = 1;
     for (const DecoderLayer& l : m.dec) {
         // causal self-attention
         layernorm(m, x, l.self_ln, h, rows);
         linear(m, h, M, l.qkv, nullptr, 0, wide, 3 * M, rows, ACT_NONE, 1.f, row_independent);
-        AttnArgs a;
-        a.q = wide;
-        a.k = wide.get() + M;
-        a.v = wide.get() + 2 * M;
-        a.out = att;
-        a.ldq = a.ldk = a.ldv = 3 * M;
-        a.ldo = M;
-        a.nb = n;
-        a.heads = cfg.num_heads;
-        a.Sq = a.Skv = s_text;
-        a.causal = 1;
-        launch_attention(a, m.stream);
+        self_attention(m, wide, M, br, self_at);
         linear(m, att, M, l.self_out, x, M, x, M, rows, ACT_NONE, 1.f, row_independent);
         // encoder-decoder attention
         layernorm(m, x, l.cross_ln, h, rows);

@@ -109,26 +109,6 @@ int encoder_out_len(const Model& m, int t_frames) {
     return (S + 2 * pad - c.adaptor_kernel_size) / c.adaptor_stride + 1;  // Conv1d output length
 }
 
-static void attention_self(Model& m, const float* qkv, int Mdim, float* out, int nb, int S, const int* d_lens,
-                           const float* rel_k) {
-    AttnArgs a;
-    a.q = qkv;
-    a.k = qkv + Mdim;
-    a.v = qkv + 2 * Mdim;
-    a.out = out;
-    a.ldq = a.ldk = a.ldv = 3 * Mdim;
-    a.ldo = Mdim;
-    a.nb = nb;
-    a.heads = m.cfg.num_heads;
-    a.Sq = S;
-    a.Skv = S;
-    a.kv_lens = d_lens;
-    a.rel_k = rel_k;
-    a.rel_left = rel_k ? m.cfg.shaw_max_left : 0;
-    a.rel_right = rel_k ? m.cfg.shaw_max_right : 0;
-    launch_attention(a, m.stream);
-}
-
 void run_encode_speech(Model& m, const float* d_fbank, int n, int t_frames, const int32_t* h_lens, float* d_out,
                        int32_t* h_out_lens) {
     const sc_config& c = m.cfg;
@@ -172,126 +152,30 @@ void run_encode_speech(Model& m, const float* d_fbank, int n, int t_frames, cons
     if (v1) launch_relpos_table(S, M, rp_tab, m.stream);
     Buf<__half> hs(m.pp(), ps_ok ? (size_t)2 * rows * M : 0), ws(m.pp(), ps_ok ? (size_t)2 * rows * c.enc_ffn_dim : 0),
         as(m.pp(), ps_ok ? (size_t)2 * rows * M : 0);
-    __half* hs_hi = hs.get();
-    __half* hs_lo = ps_ok ? hs.get() + (size_t)rows * M : nullptr;
-    __half* ws_hi = ws.get();
-    __half* ws_lo = ps_ok ? ws.get() + (size_t)rows * c.enc_ffn_dim : nullptr;
-    __half* as_hi = as.get();
-    __half* as_lo = ps_ok ? as.get() + (size_t)rows * M : nullptr;
-    auto ln_split = [&](const float* src, const LNorm& L, int act) {
-        launch_layernorm_split(src, L.dim, L.g, L.b, hs_hi, hs_lo, L.dim, rows, L.dim, act, nullptr, 1, m.stream);
-    };
-    // C (fp32) and/or Ch/Cl (split planes) = alpha * act(A . W^T + b) + res
-    auto ps = [&](const __half* ah, const __half* al, const Linear& L, int act, float alpha, const float* res, float* C,
-                  __half* Ch, __half* Cl) {
-        GemmPsArgs a;
-        a.Ah = ah;
-        a.Al = al;
-        a.lda = L.in;
-        a.W = L.w;
-        a.ldw = L.ldw;
-        a.bias = L.b;
-        a.res = res;
-        a.ldr = L.out;
-        a.C = C;
-        a.ldc = L.out;
-        a.Ch = Ch;
-        a.Cl = Cl;
-        a.ldcs = L.out;
-        a.M = rows;
-        a.N = L.out;
-        a.K = L.in;
-        a.act = act;
-        a.alpha = alpha;
-        // SC_SPLIT_MODE=1 (precision study, scripts/split_study.py; never the default): the Conformer products use the
-        // hi plane only, i.e. the activation operand is rounded to fp16 once instead of being carried to ~2^-22
-        static const bool single = knob::value("SC_SPLIT_MODE", 0) == 1;
-        a.split = single ? 0 : 1;
-        launch_gemm_presplit(a, m.stream);
-    };
-
+    BatchRows br;
+    br.n = n, br.S = S, br.rows = rows, br.d_lens = d_lens;
     // fused element-wise passes (SC_ENC_FUSE=0: the separate launches, same bits): GLU + depthwise conv + LayerNorm + SiLU
     // in one kernel; a layer's closing LayerNorm together with the next layer's first one
     static const bool fuse = knob::value("SC_ENC_FUSE", 1) != 0;
-    const bool fuse_conv = fuse && glu_dwconv_ln_supported(M, c.depthwise_conv_kernel_size);
-    const bool fuse_ln = fuse && M <= 1024;
+    // SC_SPLIT_MODE=1 (precision study, scripts/split_study.py; never the default): the Conformer products use the
+    // hi plane only, i.e. the activation operand is rounded to fp16 once instead of being carried to ~2^-22
+    static const bool single = knob::value("SC_SPLIT_MODE", 0) == 1;
+    ConformerPass cp;
+    cp.x = x, cp.wide = wide, cp.att = att;
+    cp.hs = {hs.get(), ps_ok ? hs.get() + (size_t)rows * M : nullptr};
+    cp.as = {as.get(), ps_ok ? as.get() + (size_t)rows * M : nullptr};
+    cp.ws = {ws.get(), ps_ok ? ws.get() + (size_t)rows * c.enc_ffn_dim : nullptr};
+    cp.fuse_conv = fuse && glu_dwconv_ln_supported(M, c.depthwise_conv_kernel_size);
+    cp.fuse_ln = fuse && M <= 1024;
     // GLU of the convolution module inside the first pointwise product (SC_ENC_GLU_EPI=0, read per call: pw1 writes both halves
     // and the depthwise kernel gates them; same bits)
-    const bool glu_epi = ps_ok && fuse_conv && knob::value("SC_SPLIT_MODE", 0) != 1 && knob::live("SC_ENC_GLU_EPI", 1) != 0;
+    cp.glu_epi = ps_ok && cp.fuse_conv && !single && knob::live("SC_ENC_GLU_EPI", 1) != 0;
+    cp.split = single ? 0 : 1;
     bool ffn1_planes_ready = false;  // the previous layer's closing launch already wrote LN_ffn1(x) as planes
     for (int li = 0; li < c.enc_layers; ++li) {
         const ConformerLayer& l = m.enc[li];
         if (ps_ok) {
-            // x += 0.5 * FFN1(LN(x))
-            if (!ffn1_planes_ready) ln_split(x, l.ffn1_ln, ACT_NONE);
-            ps(hs_hi, hs_lo, l.ffn1_in, ACT_SILU, 1.f, nullptr, nullptr, ws_hi, ws_lo);
-            ps(ws_hi, ws_lo, l.ffn1_out, ACT_NONE, 0.5f, x, x, nullptr, nullptr);
-            // x += MHA_shaw(LN(x))
-            ln_split(x, l.attn_ln, ACT_NONE);
-            ps(hs_hi, hs_lo, l.qkv, ACT_NONE, 1.f, nullptr, wide, nullptr, nullptr);
-            {
-                AttnArgs a;
-                a.q = wide;
-                a.k = wide.get() + M;
-                a.v = wide.get() + 2 * M;
-                a.out_hi = as_hi;
-                a.out_lo = as_lo;
-                a.ldoh = M;
-                a.ldq = a.ldk = a.ldv = 3 * M;
-                a.ldo = M;
-                a.nb = n;
-                a.heads = c.num_heads;
-                a.Sq = S;
-                a.Skv = S;
-                a.kv_lens = d_lens;
-                a.rel_k = l.rel_k;
-                a.rel_left = c.shaw_max_left;
-                a.rel_right = c.shaw_max_right;
-                launch_attention(a, m.stream);
-            }
-            ps(as_hi, as_lo, l.attn_out, ACT_NONE, 1.f, x, x, nullptr, nullptr);
-            // x += Conv(LN(x))
-            ln_split(x, l.conv_ln, ACT_NONE);
-            if (glu_epi) {
-                // the product's epilogue gates: `wide` is [rows][M], the gate half never reaches HBM (131 MB written and read
-                // back per layer at 64 x 10 s), and the depthwise kernel loads one value per element instead of two
-                GemmPsArgs a;
-                a.Ah = hs_hi;
-                a.Al = hs_lo;
-                a.lda = M;
-                a.W = l.pw1g.w;
-                a.ldw = l.pw1g.ldw;
-                a.bias = l.pw1g.b;
-                a.C = wide;
-                a.ldc = M;
-                a.M = rows;
-                a.N = 2 * M;
-                a.K = M;
-                launch_gemm_presplit_glu(a, m.stream);
-                launch_glu_dwconv_ln(wide, M, l.dw, l.conv_inner_ln.g, l.conv_inner_ln.b, ACT_SILU, hs_hi, hs_lo, M, n, S, M,
-                                     c.depthwise_conv_kernel_size, d_lens, m.stream, /*gated=*/true);
-            } else if (fuse_conv) {
-                ps(hs_hi, hs_lo, l.pw1, ACT_NONE, 1.f, nullptr, wide, nullptr, nullptr);
-                launch_glu_dwconv_ln(wide, 2 * M, l.dw, l.conv_inner_ln.g, l.conv_inner_ln.b, ACT_SILU, hs_hi, hs_lo, M, n, S, M,
-                                     c.depthwise_conv_kernel_size, d_lens, m.stream);
-            } else {
-                ps(hs_hi, hs_lo, l.pw1, ACT_NONE, 1.f, nullptr, wide, nullptr, nullptr);
-                launch_glu_dwconv(wide, 2 * M, l.dw, att, M, n, S, M, c.depthwise_conv_kernel_size, d_lens, m.stream);
-                ln_split(att, l.conv_inner_ln, ACT_SILU);
-            }
-            ps(hs_hi, hs_lo, l.pw2, ACT_NONE, 1.f, x, x, nullptr, nullptr);
-            // x += 0.5 * FFN2(LN(x)); x = LN(x)
-            ln_split(x, l.ffn2_ln, ACT_NONE);
-            ps(hs_hi, hs_lo, l.ffn2_in, ACT_SILU, 1.f, nullptr, nullptr, ws_hi, ws_lo);
-            ps(ws_hi, ws_lo, l.ffn2_out, ACT_NONE, 0.5f, x, x, nullptr, nullptr);
-            if (fuse_ln && li + 1 < c.enc_layers) {  // x = LN_final(x) and the next layer's LN_ffn1(x) planes from one read of x
-                const LNorm& nx = m.enc[li + 1].ffn1_ln;
-                launch_layernorm2_split(x, M, l.final_ln.g, l.final_ln.b, x, M, nx.g, nx.b, hs_hi, hs_lo, M, rows, M, m.stream);
-                ffn1_planes_ready = true;
-            } else {
-                layernorm(m, x, l.final_ln, x, rows);
-                ffn1_planes_ready = false;
-            }
+            ffn1_planes_ready = conformer_layer(m, l, li + 1 < c.enc_layers ? &m.enc[li + 1] : nullptr, br, cp, ffn1_planes_ready);
             continue;
         }
         // x += 0.5 * FFN1(LN(x))
@@ -301,28 +185,20 @@ void run_encode_speech(Model& m, const float* d_fbank, int n, int t_frames, cons
         // x += MHA_shaw(LN(x))   (v1: Transformer-XL relative positions, fairseq2.cpp:605-696)
         layernorm(m, x, l.attn_ln, h, rows);
         linear(m, h, M, l.qkv, nullptr, 0, wide, 3 * M, rows, ACT_NONE, 1.f);
+        SelfAttn at;
+        at.heads = c.num_heads;
+        at.out = att;
         if (v1) {
             linear(m, rp_tab, M, l.r_proj, nullptr, 0, rp_proj, M, 2 * S - 1, ACT_NONE, 1.f);
-            AttnArgs a;
-            a.q = wide;
-            a.k = wide.get() + M;
-            a.v = wide.get() + 2 * M;
-            a.out = att;
-            a.ldq = a.ldk = a.ldv = 3 * M;
-            a.ldo = M;
-            a.nb = n;
-            a.heads = c.num_heads;
-            a.Sq = S;
-            a.Skv = S;
-            a.kv_lens = d_lens;
-            a.rp_table = rp_proj;
-            a.rp_ld = M;
-            a.q_bias_u = l.u_bias;
-            a.q_bias_v = l.v_bias;
-            launch_attention(a, m.stream);
-        } else {
-            attention_self(m, wide, M, att, n, S, d_lens, l.rel_k);
+            at.rp_table = rp_proj;
+            at.q_bias_u = l.u_bias;
+            at.q_bias_v = l.v_bias;
+        } else if (l.rel_k) {
+            at.rel_k = l.rel_k;
+            at.rel_left = c.shaw_max_left;
+            at.rel_right = c.shaw_max_right;
         }
+        self_attention(m, wide, M, br, at);
         linear(m, att, M, l.attn_out, x, M, x, M, rows, ACT_NONE, 1.f);
         // x += Conv(LN(x))
         layernorm(m, x, l.conv_ln, h, rows);
@@ -359,25 +235,19 @@ void run_encode_speech(Model& m, const float* d_fbank, int n, int t_frames, cons
     layernorm(m, x, a.attn_ln, h, rows);
     conv1d(m, h, a.attn_conv, nullptr, conv, n, S, st, pad, 1, nullptr, IN_NONE, ACT_NONE);
     launch_glu(conv, 2 * M, y, M, arows, M, m.stream);
-    linear(m, y, M, a.qkv, nullptr, 0, aw, 3 * M, arows, ACT_NONE, 1.f);
-    attention_self(m, aw, M, ah, n, Sa, d_alens, nullptr);
-    linear(m, ah, M, a.attn_out, res, M, y, M, arows, ACT_NONE, 1.f);
-    layernorm(m, y, a.ffn_ln, ah, arows);
-    linear(m, ah, M, a.ffn_in, nullptr, 0, aw, c.adaptor_ffn_dim, arows, m.ffn_act, 1.f);
-    linear(m, aw, c.adaptor_ffn_dim, a.ffn_out, y, M, y, M, arows, ACT_NONE, 1.f);
+    BatchRows ab;
+    ab.n = n, ab.S = Sa, ab.rows = arows, ab.d_lens = d_alens;
+    adaptor_layer_tail(m, a, ab, res, y, aw, ah, /*row_independent=*/false);
     launch_layernorm(y, M, m.enc_final_ln.g, m.enc_final_ln.b, d_out, M, arows, M, ACT_NONE, nullptr, 1, m.stream);
     SC_HIP(hipStreamSynchronize(m.stream));
 }
 
 // The speech encoder on a ragged batch in ONE packed pass (sc_encode_speech_ragged).  Item i contributes its own
 // S_i = frame_lens[i] / fbank_stride stacked rows and nothing else: the Conformer stack runs on R = sum S_i rows, the adaptor
-// layer on Ra = sum adaptor_len(S_i) rows, items back to back.  Every stage either acts on single rows (LayerNorm, the tiled
-// products - linear() with row_independent, launch_gemm_presplit: every tile shape walks K in the same order) or on one item's
-// own rows (packed attention, the packed convolution module, the adaptor's strided windows, which see zeros outside the item as
-// the Conv1d padding of an item that runs alone does).  An item's output therefore carries the same bits in any batch, and -
-// where run_encode_speech takes the tiled products as well, i.e. above 64 rows everywhere - the bits of run_encode_speech on the
-// item alone.  One form only: the pre-split planes path with the fused passes (SC_PRESPLIT / SC_ENC_FUSE do not apply;
-// SC_ENC_GLU_EPI is read per call, same bits).
+// layer on Ra = sum adaptor_len(S_i) rows, items back to back.  The layers are run_encode_speech's own (conformer_layer,
+// adaptor_layer_tail: layers.hip) on packed rows, every product the tiled one (row_independent), so an item carries the same bits
+// in any batch and - above 64 rows, where run_encode_speech takes the tiled products too - the bits of run_encode_speech on the
+// item alone.  One form only: planes with the fused passes (SC_PRESPLIT / SC_ENC_FUSE do not apply).
 // The adaptor's two strided convolutions are plain products over gathered windows: row j of item i holds the
 // adaptor_kernel_size packed rows j * stride - pad .. tap-major, the order of the packed Conv1d weight [C_out][tap * C_in + c].
 void run_encode_speech_ragged(Model& m, const float* d_fbank, int n, int t_frames, const int32_t* h_lens, float* d_out, int s_enc_cap,
@@ -460,109 +330,27 @@ void run_encode_speech_ragged(Model& m, const float* d_fbank, int n, int t_frame
     const int F = std::max(c.adaptor_proj_dim, 3 * M);
     Buf<float> x(m.pp(), (size_t)R * M), h(m.pp(), (size_t)R * std::max(M, feat)), wide(m.pp(), (size_t)R * F);
     Buf<__half> planes(m.pp(), (size_t)R * (4 * M + 2 * Fd));
-    __half* hs_hi = planes.get();
-    __half* hs_lo = hs_hi + (size_t)R * M;
-    __half* as_hi = hs_lo + (size_t)R * M;
-    __half* as_lo = as_hi + (size_t)R * M;
-    __half* ws_hi = as_lo + (size_t)R * M;
-    __half* ws_lo = ws_hi + (size_t)R * Fd;
+    // the padded entry's layer with this entry's fixed choices: fused passes, both planes, SC_ENC_GLU_EPI read per call
+    ConformerPass cp;
+    cp.x = x, cp.wide = wide;
+    cp.hs = {planes.get(), planes.get() + (size_t)R * M};
+    cp.as = {cp.hs.lo + (size_t)R * M, cp.hs.lo + (size_t)2 * R * M};
+    cp.ws = {cp.as.lo + (size_t)R * M, cp.as.lo + (size_t)R * M + (size_t)R * Fd};
+    cp.glu_epi = knob::live("SC_ENC_GLU_EPI", 1) != 0;
+    cp.d_work = d_work, cp.n_work = n_work;
+    BatchRows br, ab;
+    br.n = ab.n = n;
+    br.S = S, br.rows = R, br.d_lens = d_lens, br.d_off = d_off, br.pairs = pairs;
+    ab.S = Sa, ab.rows = Ra, ab.d_lens = d_alens, ab.d_off = d_aoff, ab.pairs = apairs;
 
     // frontend: stack fbank_stride frames of the item's own rows into packed order, LayerNorm, Linear
     launch_gather_rows(d_fbank, c.num_fbank_channels, d_fidx, h, feat, R, feat, m.stream);
     launch_layernorm(h, feat, m.fe_ln.g, m.fe_ln.b, h, feat, R, feat, ACT_NONE, nullptr, 1, m.stream);
     linear(m, h, feat, m.fe_proj, nullptr, 0, x, M, R, ACT_NONE, 1.f, /*row_independent=*/true);
 
-    auto ln_split = [&](const float* src, const LNorm& L) {
-        launch_layernorm_split(src, L.dim, L.g, L.b, hs_hi, hs_lo, L.dim, R, L.dim, ACT_NONE, nullptr, 1, m.stream);
-    };
-    auto ps = [&](const __half* ah, const __half* al, const Linear& L, int act, float alpha, const float* res, float* C, __half* Ch, __half* Cl) {
-        GemmPsArgs a;
-        a.Ah = ah;
-        a.Al = al;
-        a.lda = L.in;
-        a.W = L.w;
-        a.ldw = L.ldw;
-        a.bias = L.b;
-        a.res = res;
-        a.ldr = L.out;
-        a.C = C;
-        a.ldc = L.out;
-        a.Ch = Ch;
-        a.Cl = Cl;
-        a.ldcs = L.out;
-        a.M = R;
-        a.N = L.out;
-        a.K = L.in;
-        a.act = act;
-        a.alpha = alpha;
-        launch_gemm_presplit(a, m.stream);
-    };
-    const bool glu_epi = knob::live("SC_ENC_GLU_EPI", 1) != 0;
-    for (int li = 0; li < c.enc_layers; ++li) {
-        const ConformerLayer& l = m.enc[li];
-        // x += 0.5 * FFN1(LN(x))   (the planes of LN_ffn1(x) come from the previous layer's closing launch)
-        if (li == 0) ln_split(x, l.ffn1_ln);
-        ps(hs_hi, hs_lo, l.ffn1_in, ACT_SILU, 1.f, nullptr, nullptr, ws_hi, ws_lo);
-        ps(ws_hi, ws_lo, l.ffn1_out, ACT_NONE, 0.5f, x, x, nullptr, nullptr);
-        // x += MHA_shaw(LN(x)) over each item's own rows
-        ln_split(x, l.attn_ln);
-        ps(hs_hi, hs_lo, l.qkv, ACT_NONE, 1.f, nullptr, wide, nullptr, nullptr);
-        {
-            AttnArgs a;
-            a.q = wide;
-            a.k = wide.get() + M;
-            a.v = wide.get() + 2 * M;
-            a.out_hi = as_hi;
-            a.out_lo = as_lo;
-            a.ldoh = M;
-            a.ldq = a.ldk = a.ldv = 3 * M;
-            a.ldo = M;
-            a.nb = n;
-            a.heads = c.num_heads;
-            a.Sq = S;
-            a.Skv = S;
-            a.kv_lens = d_lens;
-            a.row_off = d_off;
-            a.pairs = pairs;
-            a.rel_k = l.rel_k;
-            a.rel_left = c.shaw_max_left;
-            a.rel_right = c.shaw_max_right;
-            launch_attention(a, m.stream);
-        }
-        ps(as_hi, as_lo, l.attn_out, ACT_NONE, 1.f, x, x, nullptr, nullptr);
-        // x += Conv(LN(x))
-        ln_split(x, l.conv_ln);
-        if (glu_epi) {
-            GemmPsArgs a;
-            a.Ah = hs_hi;
-            a.Al = hs_lo;
-            a.lda = M;
-            a.W = l.pw1g.w;
-            a.ldw = l.pw1g.ldw;
-            a.bias = l.pw1g.b;
-            a.C = wide;
-            a.ldc = M;
-            a.M = R;
-            a.N = 2 * M;
-            a.K = M;
-            launch_gemm_presplit_glu(a, m.stream);
-        } else {
-            ps(hs_hi, hs_lo, l.pw1, ACT_NONE, 1.f, nullptr, wide, nullptr, nullptr);
-        }
-        launch_glu_dwconv_ln_packed(wide, glu_epi ? M : 2 * M, l.dw, l.conv_inner_ln.g, l.conv_inner_ln.b, ACT_SILU, hs_hi, hs_lo, M, d_work,
-                                    n_work, (double)R, M, c.depthwise_conv_kernel_size, m.stream, /*gated=*/glu_epi);
-        ps(hs_hi, hs_lo, l.pw2, ACT_NONE, 1.f, x, x, nullptr, nullptr);
-        // x += 0.5 * FFN2(LN(x)); x = LN(x)
-        ln_split(x, l.ffn2_ln);
-        ps(hs_hi, hs_lo, l.ffn2_in, ACT_SILU, 1.f, nullptr, nullptr, ws_hi, ws_lo);
-        ps(ws_hi, ws_lo, l.ffn2_out, ACT_NONE, 0.5f, x, x, nullptr, nullptr);
-        if (li + 1 < c.enc_layers) {
-            const LNorm& nx = m.enc[li + 1].ffn1_ln;
-            launch_layernorm2_split(x, M, l.final_ln.g, l.final_ln.b, x, M, nx.g, nx.b, hs_hi, hs_lo, M, R, M, m.stream);
-        } else {
-            layernorm(m, x, l.final_ln, x, R);
-        }
-    }
+    bool ffn1_planes_ready = false;
+    for (int li = 0; li < c.enc_layers; ++li)
+        ffn1_planes_ready = conformer_layer(m, m.enc[li], li + 1 < c.enc_layers ? &m.enc[li + 1] : nullptr, br, cp, ffn1_planes_ready);
     // adaptor head (adaptor_block.py:105-109)
     layernorm(m, x, m.enc_inner_ln, x, R);
     linear(m, x, M, m.enc_proj1, nullptr, 0, wide, c.adaptor_proj_dim, R, ACT_RELU, 1.f, true);
@@ -585,28 +373,7 @@ void run_encode_speech_ragged(Model& m, const float* d_fbank, int n, int t_frame
     };
     strided_conv_glu(ad.res_ln, ad.res_conv, res);
     strided_conv_glu(ad.attn_ln, ad.attn_conv, y);
-    linear(m, y, M, ad.qkv, nullptr, 0, aw, 3 * M, Ra, ACT_NONE, 1.f, true);
-    {
-        AttnArgs a;
-        a.q = aw;
-        a.k = aw.get() + M;
-        a.v = aw.get() + 2 * M;
-        a.out = ah;
-        a.ldq = a.ldk = a.ldv = 3 * M;
-        a.ldo = M;
-        a.nb = n;
-        a.heads = c.num_heads;
-        a.Sq = Sa;
-        a.Skv = Sa;
-        a.kv_lens = d_alens;
-        a.row_off = d_aoff;
-        a.pairs = apairs;
-        launch_attention(a, m.stream);
-    }
-    linear(m, ah, M, ad.attn_out, res, M, y, M, Ra, ACT_NONE, 1.f, true);
-    layernorm(m, y, ad.ffn_ln, ah, Ra);
-    linear(m, ah, M, ad.ffn_in, nullptr, 0, aw, c.adaptor_ffn_dim, Ra, m.ffn_act, 1.f, true);
-    linear(m, aw, c.adaptor_ffn_dim, ad.ffn_out, y, M, y, M, Ra, ACT_NONE, 1.f, true);
+    adaptor_layer_tail(m, ad, ab, res, y, aw, ah, /*row_independent=*/true);
     layernorm(m, y, m.enc_final_ln, y, Ra);
     // packed rows into the padded [n][s_enc_cap][M] output, zeros behind each item's length
     launch_gather_rows(y, M, d_sidx, d_out, M, n * s_enc_cap, M, m.stream);

@@ -269,7 +269,7 @@ void run_pretssel_mel(sc_pretssel& a, const int32_t* h_tokens, int n, int s_tok,
                       const float* d_pros, float* d_mel, int t_cap, int32_t* h_frame_lens) {
     Model& m = a.m;
     const sc_pretssel_config& c = a.cfg;
-    const int M = c.model_dim, Ci = c.conv_inner_dim, H = c.pred_hidden_dim, K = c.conv_kernel, PK = c.pred_kernel;
+    const int M = c.model_dim, Ci = c.conv_inner_dim, H = c.pred_hidden_dim, PK = c.pred_kernel;
     // ---- every refusal before the first launch ----
     SC_CHECK(n >= 1 && n <= PRETSSEL_MAX_ITEMS, "sc_pretssel_mel: n=%d outside 1..%d", n, PRETSSEL_MAX_ITEMS);
     SC_CHECK(s_tok >= 1 && t_cap >= 1, "sc_pretssel_mel: s_tok=%d t_cap=%d", s_tok, t_cap);
@@ -345,75 +345,20 @@ void run_pretssel_mel(sc_pretssel& a, const int32_t* h_tokens, int n, int s_tok,
     Buf<__half> planes(m.pp(), (size_t)Rmax * (6 * M + 2 * wide));
     __half* up_h = planes.get();
     __half* up_l = up_h + (size_t)Rmax * M;
-    __half* yp_h = up_l + (size_t)Rmax * M;
-    __half* yp_l = yp_h + (size_t)Rmax * M;
-    __half* ap_h = yp_l + (size_t)Rmax * M;
-    __half* ap_l = ap_h + (size_t)Rmax * M;
-    __half* wp_h = ap_l + (size_t)Rmax * M;
+    const size_t RM = (size_t)Rmax * M;
+    __half* wp_h = up_h + 6 * RM;
     __half* wp_l = wp_h + (size_t)Rmax * wide;
-
-    auto ps = [&](const __half* ah, const __half* al, const Linear& L, const float* res, float* C, int R) {
-        GemmPsArgs g;
-        g.Ah = ah;
-        g.Al = al;
-        g.lda = L.in;
-        g.W = L.w;
-        g.ldw = L.ldw;
-        g.bias = L.b;
-        g.res = res;
-        g.ldr = L.out;
-        g.C = C;
-        g.ldc = L.out;
-        g.M = R;
-        g.N = L.out;
-        g.K = L.in;
-        launch_gemm_presplit(g, m.stream);
-        ++a.last_launches;
-    };
-    // one FFT layer on R packed rows: u (fp32) and up_h / up_l (planes) hold the input and receive the output
-    auto fft_layer = [&](const PretsselLayer& l, int R, const int* d_row_off, const int* d_lens, int S, double pairs, const int2* d_row_pos,
-                         const int* d_row_item) {
-        ps(up_h, up_l, l.fft.qkv, nullptr, wbuf, R);
-        AttnArgs at;
-        at.q = wbuf;
-        at.k = wbuf.get() + M;
-        at.v = wbuf.get() + 2 * M;
-        at.out_hi = ap_h;
-        at.out_lo = ap_l;
-        at.ldoh = M;
-        at.ldq = at.ldk = at.ldv = 3 * M;
-        at.ldo = M;
-        at.nb = n;
-        at.heads = c.num_heads;
-        at.Sq = S;
-        at.Skv = S;
-        at.kv_lens = d_lens;
-        at.row_off = d_row_off;
-        at.pairs = pairs;
-        at.head_dim = 128;
-        launch_attention(at, m.stream);
-        ps(ap_h, ap_l, l.fft.attn_out, u, y, R);
-        launch_layernorm_both(y, M, l.fft.attn_ln.g, l.fft.attn_ln.b, y, M, yp_h, yp_l, M, R, M, ACT_NONE, nullptr, 1, m.stream);
-        conv1d_presplit(m, yp_h, yp_l, l.fft.conv1, nullptr, nullptr, wp_h, wp_l, 0, 0, K / 2, 1, nullptr, ACT_RELU, R, d_row_pos);
-        conv1d_presplit(m, wp_h, wp_l, l.fft.conv2, y, u, nullptr, nullptr, 0, 0, K / 2, 1, nullptr, ACT_NONE, R, d_row_pos);
-        PretsselLnArgs f;
-        f.x = u;
-        f.ldx = M;
-        f.g = l.fft.conv_ln.g;
-        f.b = l.fft.conv_ln.b;
-        f.film = film;
-        f.film_ld = a.film_n;
-        f.film_off = l.film.off;
-        f.row_item = d_row_item;
-        f.y = u;
-        f.ldy = M;
-        f.yh = up_h;
-        f.yl = up_l;
-        f.ldh = M;
-        f.rows = R;
-        f.C = M;
-        launch_pretssel_film_ln(f, m.stream);
-        a.last_launches += 5;
+    // the FFT layers on R packed rows: u (fp32) and up_h / up_l (planes) hold the input and receive the output
+    auto fft_layers = [&](const std::vector<PretsselLayer>& layers, int R, const int* d_row_off, const int* d_lens, int S, double pairs,
+                          const int2* d_row_pos, const int* d_row_item) {
+        FFTPass fp;
+        fp.u = u, fp.y = y, fp.wide = wbuf;
+        fp.up = {up_h, up_l}, fp.yp = {up_h + 2 * RM, up_h + 3 * RM}, fp.ap = {up_h + 4 * RM, up_h + 5 * RM}, fp.wp = {wp_h, wp_l};
+        fp.d_row_pos = d_row_pos, fp.heads = c.num_heads, fp.head_dim = 128;
+        fp.film = film, fp.film_ld = a.film_n, fp.row_item = d_row_item;
+        BatchRows br;
+        br.n = n, br.S = S, br.rows = R, br.d_lens = d_lens, br.d_off = d_row_off, br.pairs = pairs;
+        for (const PretsselLayer& l : layers) a.last_launches += fft_layer_packed(m, l.fft, l.film.off, br, fp);
     };
 
     // ---- encoder front end + encoder over the packed tokens ----
@@ -422,7 +367,7 @@ void run_pretssel_mel(sc_pretssel& a, const int32_t* h_tokens, int n, int s_tok,
     ++a.last_launches;
     double pairs = 0;
     for (int i = 0; i < n; ++i) pairs += (double)tok_lens[i] * tok_lens[i];
-    for (const PretsselLayer& l : a.enc) fft_layer(l, Rt, d_tok_off, d_tok_lens, smax, pairs, d_tok_pos2, d_tok_item);
+    fft_layers(a.enc, Rt, d_tok_off, d_tok_lens, smax, pairs, d_tok_pos2, d_tok_item);
 
     // ---- variance adaptor: the three predictors side by side ----
     {
@@ -520,9 +465,10 @@ void run_pretssel_mel(sc_pretssel& a, const int32_t* h_tokens, int n, int s_tok,
     const int2* d_frm_pos2 = reinterpret_cast<const int2*>(d_frm_pos.get());
     pairs = 0;
     for (int i = 0; i < n; ++i) pairs += (double)frame_lens[i] * frame_lens[i];
-    for (const PretsselLayer& l : a.dec) fft_layer(l, Rf, d_frame_off, d_frame_lens, tmax, pairs, d_frm_pos2, d_frm_item);
+    fft_layers(a.dec, Rf, d_frame_off, d_frame_lens, tmax, pairs, d_frm_pos2, d_frm_item);
     Buf<float> proj(m.pp(), (size_t)Rf * c.mel_dim);
-    ps(up_h, up_l, a.proj, nullptr, proj, Rf);
+    linear_ps(m, {up_h, up_l}, a.proj, Rf, ACT_NONE, 1.f, nullptr, proj);
+    ++a.last_launches;
 
     // ---- post-net on the extended rows, de-normalisation ----
     run_postnet(a, proj, n, frame_lens.data(), d_mel, t_cap);

@@ -15,22 +15,6 @@ namespace sc {
 
 namespace {
 
-void attention_self(Model& m, const float* qkv, int M, float* out, int nb, int S, const int* d_lens) {
-    AttnArgs a;
-    a.q = qkv;
-    a.k = qkv + M;
-    a.v = qkv + 2 * M;
-    a.out = out;
-    a.ldq = a.ldk = a.ldv = 3 * M;
-    a.ldo = M;
-    a.nb = nb;
-    a.heads = m.cfg.num_heads;
-    a.Sq = S;
-    a.Skv = S;
-    a.kv_lens = d_lens;
-    launch_attention(a, m.stream);
-}
-
 // NARDecoderFrontend.text_to_char_seqs on the precomputed per-token tables
 // (nar_decoder_frontend.py:31-49 TagManager, :158-225 char lengths, :227-259 char ids).
 void text_to_char_seqs(const Model& m, const int32_t* text_seqs, int n, int s_text, std::vector<int32_t>& char_lens,
@@ -171,15 +155,9 @@ void run_encode_text(Model& m, const int32_t* h_tokens, int n, int s_text, const
     Buf<float> h(m.pp(), (size_t)rows * M), wide(m.pp(), (size_t)rows * wideN), att(m.pp(), (size_t)rows * M);
     float* x = d_out;
     launch_embed_tokens(d_tok, rows, m.text_embed, M, sqrtf((float)M), m.text_pos, nullptr, s_text, x, M, m.stream);
-    for (const EncoderLayer& l : m.text_enc) {
-        layernorm(m, x, l.attn_ln, h, rows);
-        linear(m, h, M, l.qkv, nullptr, 0, wide, 3 * M, rows, ACT_NONE, 1.f);
-        attention_self(m, wide, M, att, n, s_text, d_lens);
-        linear(m, att, M, l.attn_out, x, M, x, M, rows, ACT_NONE, 1.f);
-        layernorm(m, x, l.ffn_ln, h, rows);
-        linear(m, h, M, l.ffn_in, nullptr, 0, wide, c.text_enc_ffn_dim, rows, m.ffn_act, 1.f);
-        linear(m, wide, c.text_enc_ffn_dim, l.ffn_out, x, M, x, M, rows, ACT_NONE, 1.f);
-    }
+    BatchRows br;
+    br.n = n, br.S = s_text, br.rows = rows, br.d_lens = d_lens;
+    for (const EncoderLayer& l : m.text_enc) encoder_layer(m, l, br, c.num_heads, 64, m.ffn_act, false, x, h, wide, att);
     layernorm(m, x, m.text_enc_ln, x, rows);
     SC_HIP(hipStreamSynchronize(m.stream));  // h_tokens / h_lens are the caller's; outputs complete on return
 }
@@ -234,58 +212,22 @@ void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, con
         const int* d_uidx = d_pidx + R;
         Buf<float> xp(m.pp(), (size_t)R * M), wide(m.pp(), (size_t)R * 3 * M);
         Buf<__half> planes(m.pp(), (size_t)R * (4 * M + 2 * Fd));
-        __half* hp_h = planes.get();
-        __half* hp_l = hp_h + (size_t)R * M;
-        __half* ap_h = hp_l + (size_t)R * M;
-        __half* ap_l = ap_h + (size_t)R * M;
-        __half* wp_h = ap_l + (size_t)R * M;
-        __half* wp_l = wp_h + (size_t)R * Fd;
-        auto ps = [&](const __half* ah, const __half* al, const Linear& L, int act, const float* res, float* C, __half* Ch, __half* Cl) {
-            GemmPsArgs a;
-            a.Ah = ah;
-            a.Al = al;
-            a.lda = L.in;
-            a.W = L.w;
-            a.ldw = L.ldw;
-            a.bias = L.b;
-            a.res = res;
-            a.ldr = L.out;
-            a.C = C;
-            a.ldc = L.out;
-            a.Ch = Ch;
-            a.Cl = Cl;
-            a.ldcs = L.out;
-            a.M = R;
-            a.N = L.out;
-            a.K = L.in;
-            a.act = act;
-            launch_gemm_presplit(a, m.stream);
-        };
+        const Planes hp{planes.get(), planes.get() + (size_t)R * M}, ap{hp.lo + (size_t)R * M, hp.lo + (size_t)2 * R * M},
+            wp{ap.lo + (size_t)R * M, ap.lo + (size_t)R * M + (size_t)R * Fd};
+        BatchRows br;  // S: the padded length bounds the longest item
+        br.n = n, br.S = s_text, br.rows = R, br.d_lens = d_text_lens, br.d_off = d_off, br.pairs = pairs;
+        SelfAttn at;
+        at.heads = c.num_heads;
+        at.out_p = ap;
         launch_gather_rows(d_dec_hidden, M, d_pidx, xp, M, R, M, m.stream);
         for (const EncoderLayer& l : m.t2u_enc) {
-            launch_layernorm_split(xp, M, l.attn_ln.g, l.attn_ln.b, hp_h, hp_l, M, R, M, ACT_NONE, nullptr, 1, m.stream);
-            ps(hp_h, hp_l, l.qkv, ACT_NONE, nullptr, wide, nullptr, nullptr);
-            AttnArgs a;
-            a.q = wide;
-            a.k = wide.get() + M;
-            a.v = wide.get() + 2 * M;
-            a.out_hi = ap_h;
-            a.out_lo = ap_l;
-            a.ldoh = M;
-            a.ldq = a.ldk = a.ldv = 3 * M;
-            a.ldo = M;
-            a.nb = n;
-            a.heads = c.num_heads;
-            a.Sq = s_text;
-            a.Skv = s_text;
-            a.kv_lens = d_text_lens;
-            a.row_off = d_off;
-            a.pairs = pairs;
-            launch_attention(a, m.stream);
-            ps(ap_h, ap_l, l.attn_out, ACT_NONE, xp, xp, nullptr, nullptr);
-            launch_layernorm_split(xp, M, l.ffn_ln.g, l.ffn_ln.b, hp_h, hp_l, M, R, M, ACT_NONE, nullptr, 1, m.stream);
-            ps(hp_h, hp_l, l.ffn_in, m.t2u_ffn_act, nullptr, nullptr, wp_h, wp_l);
-            ps(wp_h, wp_l, l.ffn_out, ACT_NONE, xp, xp, nullptr, nullptr);
+            launch_layernorm_split(xp, M, l.attn_ln.g, l.attn_ln.b, hp.hi, hp.lo, M, R, M, ACT_NONE, nullptr, 1, m.stream);
+            linear_ps(m, hp, l.qkv, R, ACT_NONE, 1.f, nullptr, wide);
+            self_attention(m, wide, M, br, at);
+            linear_ps(m, ap, l.attn_out, R, ACT_NONE, 1.f, xp, xp);
+            launch_layernorm_split(xp, M, l.ffn_ln.g, l.ffn_ln.b, hp.hi, hp.lo, M, R, M, ACT_NONE, nullptr, 1, m.stream);
+            linear_ps(m, hp, l.ffn_in, R, m.t2u_ffn_act, 1.f, nullptr, nullptr, wp);
+            linear_ps(m, wp, l.ffn_out, R, ACT_NONE, 1.f, xp, xp);
         }
         layernorm(m, xp, m.t2u_enc_ln, xp, R);
         launch_gather_rows(xp, M, d_uidx, x, M, rows, M, m.stream);
@@ -294,15 +236,9 @@ void run_t2u_encoder(Model& m, const float* d_dec_hidden, int n, int s_text, con
     const int wideN = std::max(3 * M, Fd);
     Buf<float> h(m.pp(), (size_t)rows * M), wide(m.pp(), (size_t)rows * wideN), att(m.pp(), (size_t)rows * M);
     SC_HIP(hipMemcpyAsync(x, d_dec_hidden, (size_t)rows * M * 4, hipMemcpyDeviceToDevice, m.stream));
-    for (const EncoderLayer& l : m.t2u_enc) {
-        layernorm(m, x, l.attn_ln, h, rows);
-        linear(m, h, M, l.qkv, nullptr, 0, wide, 3 * M, rows, ACT_NONE, 1.f);
-        attention_self(m, wide, M, att, n, s_text, d_text_lens);
-        linear(m, att, M, l.attn_out, x, M, x, M, rows, ACT_NONE, 1.f);
-        layernorm(m, x, l.ffn_ln, h, rows);
-        linear(m, h, M, l.ffn_in, nullptr, 0, wide, Fd, rows, m.t2u_ffn_act, 1.f);
-        linear(m, wide, Fd, l.ffn_out, x, M, x, M, rows, ACT_NONE, 1.f);
-    }
+    BatchRows br;
+    br.n = n, br.S = s_text, br.rows = rows, br.d_lens = d_text_lens;
+    for (const EncoderLayer& l : m.t2u_enc) encoder_layer(m, l, br, c.num_heads, 64, m.t2u_ffn_act, false, x, h, wide, att);
     layernorm(m, x, m.t2u_enc_ln, x, rows);
 }
 
@@ -516,68 +452,21 @@ void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const i
             const int wideN = 3 * M;
             Buf<float> u(m.pp(), (size_t)R * M), y(m.pp(), (size_t)R * M), wide(m.pp(), (size_t)R * wideN);
             Buf<__half> planes(m.pp(), (size_t)R * (6 * M + 2 * Ci));
+            const size_t RM = (size_t)R * M;
             __half* up_h = planes.get();
-            __half* up_l = up_h + (size_t)R * M;
-            __half* yp_h = up_l + (size_t)R * M;
-            __half* yp_l = yp_h + (size_t)R * M;
-            __half* ap_h = yp_l + (size_t)R * M;
-            __half* ap_l = ap_h + (size_t)R * M;
-            __half* wp_h = ap_l + (size_t)R * M;
-            __half* wp_l = wp_h + (size_t)R * Ci;
-            auto ps = [&](const __half* ah, const __half* al, const Linear& L, const float* res, float* C) {
-                GemmPsArgs a;
-                a.Ah = ah;
-                a.Al = al;
-                a.lda = L.in;
-                a.W = L.w;
-                a.ldw = L.ldw;
-                a.bias = L.b;
-                a.res = res;
-                a.ldr = L.out;
-                a.C = C;
-                a.ldc = L.out;
-                a.M = R;
-                a.N = L.out;
-                a.K = L.in;
-                launch_gemm_presplit(a, m.stream);
-            };
+            __half* up_l = up_h + RM;
+            FFTPass fp;
+            fp.u = u, fp.y = y, fp.wide = wide;
+            fp.up = {up_h, up_l}, fp.yp = {up_h + 2 * RM, up_h + 3 * RM}, fp.ap = {up_h + 4 * RM, up_h + 5 * RM};
+            fp.wp = {up_h + 6 * RM, up_h + 6 * RM + (size_t)R * Ci};
+            fp.d_row_pos = d_row_pos, fp.heads = c.num_heads;
+            if (film) fp.film = ftab, fp.film_ld = m.t2u_film_n, fp.row_item = d_uitem;
+            BatchRows br;
+            br.n = n, br.S = Su, br.rows = R, br.d_lens = d_ulens, br.d_off = d_row_off, br.pairs = pairs;
             launch_gather_rows(cs, M, d_uidx, u, M, R, M, m.stream);
             launch_pos_add_rows(u, M, m.unit_pos, d_row_t, m.pos_alpha, R, M, m.stream);
             launch_split_f32(u, up_h, up_l, (int64_t)R * M, m.stream);
-            for (const FFTLayer& l : m.t2u_dec) {
-                ps(up_h, up_l, l.qkv, nullptr, wide);
-                AttnArgs a;
-                a.q = wide;
-                a.k = wide.get() + M;
-                a.v = wide.get() + 2 * M;
-                a.out_hi = ap_h;
-                a.out_lo = ap_l;
-                a.ldoh = M;
-                a.ldq = a.ldk = a.ldv = 3 * M;
-                a.ldo = M;
-                a.nb = n;
-                a.heads = c.num_heads;
-                a.Sq = Su;
-                a.Skv = Su;
-                a.kv_lens = d_ulens;
-                a.row_off = d_row_off;
-                a.pairs = pairs;
-                launch_attention(a, m.stream);
-                ps(ap_h, ap_l, l.attn_out, u, y);
-                launch_layernorm_both(y, M, l.attn_ln.g, l.attn_ln.b, y, M, yp_h, yp_l, M, R, M, ACT_NONE, nullptr, 1, m.stream);
-                conv1d_presplit(m, yp_h, yp_l, l.conv1, nullptr, nullptr, wp_h, wp_l, 0, 0, K / 2, 1, nullptr, ACT_RELU, R, d_row_pos);
-                conv1d_presplit(m, wp_h, wp_l, l.conv2, y, u, nullptr, nullptr, 0, 0, K / 2, 1, nullptr, ACT_NONE, R, d_row_pos);
-                if (film) {  // conv1d_layer_norm -> FiLM (-> mask: packed rows are all live) in one pass (fft_decoder_layer.py:185-191)
-                    PretsselLnArgs f;
-                    f.x = u, f.ldx = M, f.g = l.conv_ln.g, f.b = l.conv_ln.b;
-                    f.film = ftab, f.film_ld = m.t2u_film_n, f.film_off = l.film_off, f.row_item = d_uitem;
-                    f.y = u, f.ldy = M, f.yh = up_h, f.yl = up_l, f.ldh = M, f.rows = R, f.C = M;
-                    launch_pretssel_film_ln(f, m.stream);
-                } else {
-                    launch_layernorm_both(u, M, l.conv_ln.g, l.conv_ln.b, u, M, up_h, up_l, M, R, M, ACT_NONE, nullptr, 1, m.stream);
-                }
-                launches += 7;  // QKV, attention, out-projection, LayerNorm, conv, conv, LayerNorm (+ FiLM)
-            }
+            for (const FFTLayer& l : m.t2u_dec) launches += fft_layer_packed(m, l, l.film_off, br, fp);
             launches += 6;  // gather, positions, split, final LayerNorm, projection + arg-max, arg-max finish
             launch_layernorm_split(u, M, m.t2u_dec_ln.g, m.t2u_dec_ln.b, up_h, up_l, M, R, M, ACT_NONE, nullptr, 1, m.stream);
             // project + arg-max (model.py:438-441, generator.py:346).  The arg-max rides in the product's epilogue: the
@@ -639,9 +528,14 @@ void run_t2u_nar(Model& m, const float* d_dec_hidden, int n, int s_text, const i
         launch_gather_rows(cs, M, d_uidx, u, M, grows, M, m.stream);
         launch_pos_add(u, M, m.unit_pos, Lg, m.pos_alpha, grows, M, m.stream);
         const int K = c.t2u_conv_kernel;
+        BatchRows gb;
+        gb.n = ng, gb.S = Lg, gb.rows = grows, gb.d_lens = d_glens;
+        SelfAttn at;
+        at.heads = c.num_heads;
+        at.out = att;
         for (const FFTLayer& l : m.t2u_dec) {
             linear(m, u, M, l.qkv, nullptr, 0, wide, 3 * M, grows, ACT_NONE, 1.f);
-            attention_self(m, wide, M, att, ng, Lg, d_glens);
+            self_attention(m, wide, M, gb, at);
             linear(m, att, M, l.attn_out, u, M, y, M, grows, ACT_NONE, 1.f);
             layernorm(m, y, l.attn_ln, y, grows);
             conv1d(m, y, l.conv1, nullptr, wide, ng, Lg, 1, K / 2, 1, d_glens, IN_NONE, ACT_RELU);

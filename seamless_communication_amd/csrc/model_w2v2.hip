@@ -189,28 +189,9 @@ void run_extract_units(sc_unit_extractor& a, const float* h_wav, int n, int64_t 
     const int wideN = std::max(3 * M, c.ffn_dim);
     Buf<float> wide(m.pp(), (size_t)rows * wideN), att(m.pp(), (size_t)rows * M);
     float* xr = xs;
-    for (int i = 0; i <= out_layer_idx; ++i) {
-        const EncoderLayer& l = a.layers[i];
-        layernorm(m, xr, l.attn_ln, h, rows);
-        linear(m, h, M, l.qkv, nullptr, 0, wide, 3 * M, rows, ACT_NONE, 1.f, true);
-        AttnArgs at;
-        at.q = wide;
-        at.k = wide + M;
-        at.v = wide + 2 * M;
-        at.out = att;
-        at.ldq = at.ldk = at.ldv = 3 * M;
-        at.ldo = M;
-        at.nb = n;
-        at.heads = c.heads;
-        at.Sq = at.Skv = TF;
-        at.kv_lens = d_frames;
-        at.head_dim = M / c.heads;
-        launch_attention(at, m.stream);
-        linear(m, att, M, l.attn_out, xr, M, xr, M, rows, ACT_NONE, 1.f, true);
-        layernorm(m, xr, l.ffn_ln, h, rows);
-        linear(m, h, M, l.ffn_in, nullptr, 0, wide, c.ffn_dim, rows, ACT_GELU, 1.f, true);
-        linear(m, wide, c.ffn_dim, l.ffn_out, xr, M, xr, M, rows, ACT_NONE, 1.f, true);
-    }
+    BatchRows br;
+    br.n = n, br.S = TF, br.rows = rows, br.d_lens = d_frames;
+    for (int i = 0; i <= out_layer_idx; ++i) encoder_layer(m, a.layers[i], br, c.heads, M / c.heads, ACT_GELU, true, xr, h, wide, att);
     if (d_features) SC_HIP(hipMemcpyAsync(d_features, xr, (size_t)rows * M * 4, hipMemcpyDeviceToDevice, m.stream));
     // ---- k-means ----
     Buf<int> d_idx(m.pp(), rows);

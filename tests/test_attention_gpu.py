@@ -229,7 +229,7 @@ def _check(lib, report_dir, group, pb, layout, planes=False, bar_abs=True, **tag
 # 1. layouts
 # ------------------------------------------------------------------------------------------------------------------ #
 LAYOUT_CASES = [
-    # interleaved [rows][3M] q | k | v with padded items: attention_self (model_encoder.hip / model_t2u.hip)
+    # interleaved [rows][3M] q | k | v with padded items: self_attention (layers.hip)
     ("self", dict(nb=3, H=5, Sq=200, Skv=200, lens=[200, 77, 129])),
     # encoder-decoder attention (model_decoder.hip): Sq != Skv, ldq = M, ldk = ldv = 2M, encoder lengths
     ("cross", dict(nb=3, H=4, Sq=37, Skv=301, lens=[301, 150, 7])),
